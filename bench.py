@@ -27,6 +27,14 @@ Rank 0 prints ONE JSON line.  Besides the contract fields it carries
 `--job-notes N --config 4` (or 5) renders ONE fixed job of N notes instead: every rank derives the same
 longest-processing-time assignment from the notes' frame counts, renders its share in sub-batches, and the line reports
 `"scaling": "strong"` with the per-rank frames and the imbalance.
+
+`--dump-outputs DIR` (e.g. bench_outputs/, git-ignored) writes what the last timed step handed back, so that two builds can be
+compared output for output (the inputs are seeded by note id: the same arguments give the same notes):
+  mix.npy           float32, the audio of the dumped notes, concatenated in note-id order
+  note_ids.npy      float64, their note ids
+  note_samples.npy  float64, their lengths in samples (where mix.npy splits)
+Every note of the step when they fit in DUMP_BYTES, else a fixed seeded sample of whole notes (`dump_selection`).  With more
+than one rank, each rank writes its own notes as <name>_rank<r>.npy within DUMP_BYTES / ranks.
 """
 import argparse
 import json
@@ -41,6 +49,8 @@ sys.path.insert(0, HERE)
 
 HBM_PEAK_GBS = 8000.0      # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6.3 TB/s is the measured ceiling
 VALU_PEAK = 1024 * 2.4e9 / 2.0   # wave64 vector instructions/s: 1024 SIMDs, one per 2 cycles on the SIMD-32 (same guide)
+DUMP_BYTES = 60_000_000          # --dump-outputs: everything written, all ranks together, stays under 64 MB
+DUMP_SEED = 0
 
 
 def stage_alg_bytes(stage: str, F: int, N: int, B: int, hop: int, n_fft: int, executed: float = 1.0, E: float = 0.0, K: int = 0) -> float:
@@ -466,6 +476,47 @@ def host_inclusive(wl, ctx, step_s):
     return best
 
 
+def dump_selection(lens, budget_samples, seed=DUMP_SEED):
+    """Ascending indices of the notes --dump-outputs writes: every note when their samples fit `budget_samples`, else whole
+    notes taken in a seeded random order while the budget lasts.  Depends on the seed and the note lengths only."""
+    lens = np.asarray(lens, dtype=np.int64)
+    if int(lens.sum()) <= budget_samples:
+        return np.arange(lens.size)
+    pick, total = [], 0
+    for j in np.random.default_rng(seed).permutation(lens.size):
+        if total + lens[j] <= budget_samples:
+            pick.append(j)
+            total += int(lens[j])
+    return np.sort(np.asarray(pick, dtype=np.int64))
+
+
+def dump_outputs(path, sub_ids, subs, outs, rank, world):
+    """Write the dumped notes of one step under `path` (`outs`: what every sub-batch of the step returned, in order) and return
+    what the result line says about them."""
+    import torch
+    torch.cuda.synchronize()
+    ids = np.concatenate([np.asarray(s, dtype=np.int64) for s in sub_ids])
+    lens = np.concatenate([np.asarray(w.prep["lens"], dtype=np.int64) for w in subs])
+    where = [(b, k) for b, s in enumerate(sub_ids) for k in range(len(s))]
+    budget = DUMP_BYTES // world - 3 * 128 - 16 * ids.size     # npy headers and the two float64 columns at their largest
+    chosen = dump_selection(lens, budget // 4)
+    chosen = chosen[np.argsort(ids[chosen], kind="stable")]
+    parts = []
+    for j in chosen:
+        b, k = where[j]
+        so = subs[b].prep["sample_off"]
+        assert outs[b]["mix"].numel() == int(so[-1])
+        parts.append(outs[b]["mix"][int(so[k]):int(so[k + 1])])
+    arrays = {"mix": torch.cat(parts).cpu().numpy() if parts else np.zeros(0, np.float32),
+              "note_ids": ids[chosen].astype(np.float64), "note_samples": lens[chosen].astype(np.float64)}
+    os.makedirs(path, exist_ok=True)
+    sfx = "_rank%d" % rank if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + sfx + ".npy"), a)
+    return {"dir": os.path.abspath(path), "notes": int(chosen.size), "of_notes": int(ids.size), "samples": int(arrays["mix"].size),
+            "files": [name + sfx + ".npy" for name in arrays]}
+
+
 def launch_ranks(n):
     """`bench.py --gpus N` (N > 1) started WITHOUT a launcher: run the same command under torch.distributed.run, one rank per
     GPU, as a CHILD process and exit with its status.  This process has not touched the GPU (nothing here imports torch), and it
@@ -501,7 +552,10 @@ def main():
     ap.add_argument("--rehearse", action="store_true", help="dress rehearsal of the multi-rank logic WITHOUT a GPU: gloo process "
                     "group, the same assignment / sub-batching / planning / reductions, a sleep standing in for the device step")
     ap.add_argument("--no-legs", action="store_true", help="skip the config4 / config5 legs of the default line")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (see the module text)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(args.gpus)
     if args.rehearse:
@@ -549,10 +603,11 @@ def main():
         # sequential in time), which then hides behind that sub-batch's own envelope assembly instead of a 3 s note stalling
         # a sub-batch of short ones
         ids = sorted(ids, key=lambda i: (-est[i], i))
-        subs = [SamplerWorkload(ctx, args.config, ids[k:k + args.sub_batch]) for k in range(0, len(ids), args.sub_batch)]
+        sub_ids = [ids[k:k + args.sub_batch] for k in range(0, len(ids), args.sub_batch)]
     else:
         ids = list(note_range(rank, world, args.notes))
-        subs = [SamplerWorkload(ctx, args.config, ids)]
+        sub_ids = [ids]
+    subs = [SamplerWorkload(ctx, args.config, s) for s in sub_ids]
     wl = subs[0]
     my_frames, my_samples = sum(w.frames for w in subs), sum(w.samples for w in subs)
     geo = wl.geo
@@ -563,14 +618,20 @@ def main():
         if world > 1:
             dist.barrier()
 
-    def step():
+    def step(keep=None):
+        """One pass over this rank's notes; returns the last sub-batch's output and appends every sub-batch's to `keep`."""
         out = None
         for w in subs:
             out = w.step()
+            if keep is not None:
+                keep.append(out)
         return out
 
+    # --dump-outputs holds on to every sub-batch's output of a step, in the warm-up steps too, so that the allocator already
+    # holds the blocks this takes when the timed steps start
+    dump = args.dump_outputs is not None
     for _ in range(args.warmup):
-        step()
+        step([] if dump else None)
     # Which kernel the roofline is about = the longest single-kernel stage of one more untimed step with every stage bracketed.
     # The timed steps then carry that stage's two HIP events only: the ~20 event records of the full breakdown are 0.06 ms of a
     # 2.3 ms step (scripts/prof_cost.py).  The breakdown itself (stage_ms) comes from a further untimed pass of the same steps.
@@ -585,7 +646,8 @@ def main():
     scan0 = (ctx.counter("pulse_scanned_notes"), ctx.counter("pulse_fallback_notes"))
     t0 = time.perf_counter()
     for k in range(args.steps):
-        last = step()
+        kept = [] if dump else None
+        last = step(kept)
     torch.cuda.synchronize()
     t1 = time.perf_counter()
     barrier()
@@ -602,6 +664,8 @@ def main():
     # the timed path must have produced audio: finite, not silent (the last sub-batch of the last step)
     mix = last["mix"]
     assert bool(torch.isfinite(mix).all()) and float(mix.abs().max()) > 0.0, "the timed steps produced no valid audio"
+    dumped = dump_outputs(args.dump_outputs, sub_ids, subs, kept, rank, world) if dump else None
+    kept = None
     # the assembly call on its own (the synth stages overlap on two streams, so step - sum(stages) no longer isolates it)
     a0, a1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     a0.record()
@@ -805,6 +869,8 @@ def main():
                 line["host_inclusive"] = host_inclusive(wl, ctx, elapsed / args.steps)
         if options:
             line["options"] = options
+        if dumped is not None:
+            line["dump_outputs"] = dumped
         if cpu_line is not None:
             line["cpu_baseline"] = cpu_line
         # BASELINE configs 4 and 5 are 8-GPU jobs: their single-GPU passes ride on the default line, after the timed region,
@@ -869,9 +935,11 @@ def rehearse(args):
     if job:
         assert my_frames == sum(est[i] for i in ids), "the planner and the assignment disagree on frame counts"
 
+    # gloo's own barrier: dist.barrier() asks torch for the machine's accelerator, which opens the GPU in every rank of a
+    # rehearsal that runs on a GPU box
     def barrier():
         if world > 1:
-            dist.barrier()
+            dist.monitored_barrier()
 
     barrier()
     t0 = time.perf_counter()
@@ -900,7 +968,7 @@ def rehearse(args):
                               "uploads and the first device step come on top on the GPU box"}
         print(json.dumps(line))
     if world > 1:
-        dist.barrier()
+        barrier()
         dist.destroy_process_group()
 
 

@@ -664,6 +664,19 @@ def gen_goofy_file():
          **{"formant_%d" % k: np.asarray(v, dtype=np.float64) for k, v in forms2.items()})
 
 
+def gen_manifest():
+    """The reference's OpenUtau manifest (SillySampler.yaml beside SillySampler.py) as parsed data, keys in its order."""
+    import json
+    import yaml
+    with open(os.path.join(os.path.dirname(os.path.abspath(ss.__file__)), "SillySampler.yaml")) as f:
+        data = yaml.safe_load(f)
+    path = os.path.join(HERE, "manifest.json")
+    with open(path, "w") as f:
+        json.dump(data, f, indent=1)
+        f.write("\n")
+    print("%-34s %8.1f KB" % ("manifest.json", os.path.getsize(path) / 1024.0))
+
+
 def gen_post_chain():
     """Time-varying one-pole cascades + jitter generators (§8 f rows 1-2)."""
     out = {}
@@ -809,6 +822,7 @@ elif __name__ == "__main__":
     gen_synthesize_rough()
     gen_flags_pitch()
     gen_goofy_file()
+    gen_manifest()
     gen_post_chain()
     gen_cold_cache()
     gen_index_plans()

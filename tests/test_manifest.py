@@ -1,16 +1,16 @@
 """f4: the OpenUtau manifest is generated from the product's flag table (goofer_amd/flags.py); the committed SillySampler.yaml
-is that output; every flag of the table is one the decoder understands with the table's default; and — in the build container,
-where the reference is mounted — the manifest equals the reference's SillySampler.yaml as parsed data."""
+is that output; every flag of the table is one the decoder understands with the table's default; and the manifest equals the
+reference's SillySampler.yaml as parsed data (tests/golden/manifest.json, written by make_golden.gen_manifest)."""
+import json
 import os
 
-import pytest
 import yaml
 
 from goofer_amd import flags as F
 from goofer_amd import sampler as S
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference/SillySampler.yaml"
+REF = os.path.join(REPO, "tests", "golden", "manifest.json")
 
 
 def test_committed_manifest_is_the_generated_one():
@@ -51,8 +51,8 @@ def test_every_table_flag_decodes_with_its_range_and_default():
             assert o.startswith(f.flag) and o[len(f.flag):].isdigit()
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="the reference is only mounted in the build container")
 def test_manifest_equals_the_reference_manifest_as_data():
-    ref = yaml.safe_load(open(REF))
+    with open(REF) as f:
+        ref = json.load(f)
     assert F.manifest() == ref
     assert list(F.manifest()["expressions"]) == list(ref["expressions"])      # same order, as OpenUtau lists them
