@@ -88,7 +88,6 @@ int launch_stem_gains(goofer_ctx *, float *, float *, float *, const double *, c
 int launch_apply_gain(goofer_ctx *, float *, float *, float *, float *, float *, const int64_t *, int, int64_t,
                       const goofer_note_params *, const float *, bool, hipStream_t);
 
-int launch_note_steps(goofer_ctx *, const int64_t *, int, double *, hipStream_t);
 int launch_mask_upsample(goofer_ctx *, const double *, const int64_t *, int, int64_t, double *, bool, float *, hipStream_t);
 bool stems_supported(const goofer_plan_t &);
 bool ola_split_supported(const goofer_plan_t &);
@@ -289,59 +288,18 @@ static int upload_jitter_taps(goofer_ctx *ctx, double sigma, int slot, const dou
 }
 
 // ---------------------------------------------------------------------------------------------
-// scratch arena
+// scratch arena: 256-byte aligned pieces taken in order.  Without a base it only counts, so the code that carves a call's
+// buffers also sizes them (carve_scratch).
 struct arena {
     char *base;
-    size_t size, used;
+    size_t used;
     template <typename T> T *take(size_t count)
     {
-        size_t bytes = (count * sizeof(T) + 255) & ~(size_t)255;
-        if (used + bytes > size) return nullptr;
-        T *p = reinterpret_cast<T *>(base + used);
-        used += bytes;
+        T *p = base ? reinterpret_cast<T *>(base + used) : nullptr;
+        used += (count * sizeof(T) + 255) & ~(size_t)255;
         return p;
     }
 };
-
-// spectra: 1 = the one-kernel-per-step pipeline will run (complex spectra + windowed frames of the three stems in HBM: 24 KB per
-// frame, the noise envelope); 0 = the stem walkers, which need none of it.  subharm: the 'sg' trackers' fp64 phase increments.
-static size_t scratch_need(const goofer_plan_t &p, int64_t frames, int64_t samples, int64_t notes, int spectra = 1, bool subharm = true)
-{
-    size_t ldc = spec_stride(p.n_bins), ld = (p.n_bins + 3) & ~3;
-    size_t b = 0;
-    auto add = [&](size_t bytes) { b += (bytes + 255) & ~(size_t)255; };
-    add(frames * sizeof(int));                    // frame_note
-    add(frames * sizeof(int64_t));                // row_src
-    add(frames * sizeof(float2));                 // per-frame (f0, mask) picks
-    add(samples * sizeof(float));                 // f0 scaled
-    if (subharm) add(samples * sizeof(double));   // phase increments
-    // onset slots: n / 2 + 16 per note for the pulse train (an f0 above sr / 2 is refused) — n + 16 with the sub-harmonic layer,
-    // whose tracker fires at most once per sample and does so on every sample once its increment passes 1 (the resampler's
-    // vibrato depth of 3 takes the layer to 8 x f0: above sr / 2 from F7 on)
-    const size_t slots = (size_t)(subharm ? samples : samples / 2) + 16 * (size_t)notes + 16;
-    add(slots * ONSET_BYTES);
-    add(slots * sizeof(int32_t));                 // raw onset sample indices
-    add(notes * sizeof(int32_t) + 64);            // onset counts
-    add(64);                                      // overflow flag
-    add(samples * sizeof(float));                 // pulse
-    add((size_t)PULSE_TILE_INTS(samples) * sizeof(int32_t)); // pulse placement: 4 ints per tile
-    if (spectra == 1) {
-        add(3 * frames * ldc * sizeof(float2));       // S_h, S_uv, S_br
-        add(3 * frames * (size_t)p.n_fft * sizeof(float));  // windowed time frames (three stems in the fused path)
-    }
-    add((spectra == 1 ? 2 : 1) * frames * ld * sizeof(float));   // env_h (, env_n)
-    add((samples / 4 + notes + 16) * sizeof(double));  // smoothed decimated mask
-    add(2 * notes * sizeof(float) + 64);          // note_mag, note_peak
-    add(2 * notes * sizeof(double) + 64);         // per-note linspace steps
-    add((size_t)frames + 3 * (size_t)notes + 64); // per-hop stem sparsity bytes of the walkers
-    if (spectra) {                                // per-hop flatness + per-frame skip bits of the LDS-ring pipeline
-        const int64_t reach = (p.n_fft + p.hop - 1) / p.hop;
-        add((size_t)(frames + reach * notes) + 64);
-        add((size_t)frames + 64);
-        add((size_t)(samples / 4 + notes + 16) + 64);
-    }
-    return b + 4096;
-}
 
 static int ensure_scratch(goofer_ctx *ctx, size_t bytes)
 {
@@ -354,6 +312,124 @@ static int ensure_scratch(goofer_ctx *ctx, size_t bytes)
     if (e != hipSuccess) return goofer_fail(ctx, GOOFER_ENOMEM, "scratch hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
     ctx->scratch_bytes = bytes;
     return GOOFER_OK;
+}
+
+// carve(arena &) once counting, make room for what it took (+ 4 KiB behind the last piece), then once over the handle's scratch
+template <typename Carve> static int carve_scratch(goofer_ctx *ctx, Carve &&carve)
+{
+    arena count{nullptr, 0};
+    carve(count);
+    if (int rc = ensure_scratch(ctx, count.used + 4096)) return rc;
+    arena a{(char *)ctx->scratch, 0};
+    carve(a);
+    return GOOFER_OK;
+}
+
+// Which pipeline goofer_synth_batch runs for a batch, decided here only (goofer_synth_batch, goofer_render_batch's warped rows,
+// goofer_reserve).  goofer_amd/render.py's Renderer.run splits mixed batches by the same walkers rule.
+struct synth_route {
+    bool jit_f0, jit_vol, vol_vib;   // 'sh' f0 jitter; 'sr' volume jitter on harm / breath (vol_vib: its vibrato form)
+    bool sub_on, sub_jit;            // 'sg' sub-harmonic pulse layer (sub_jit: with its own f0 jitter)
+    bool f64_on;                     // a private fp64 copy of f0 for the jitters / the sub-harmonic trackers
+    bool walkers;                    // the stem walkers (stems.hip), no spectra in HBM; else the spectra kernels, with
+    bool ola_split, ola_one;         // n_fft 2048: one stem per wave (k_irfft_ola1) + per-note finish; fused overlap-add rings
+    bool skip_frames;                // ola_split with the noise stems' exact sparsity decided per frame up front (k_frame_skip)
+    bool side_on, early;             // the pulse chain on the side stream (early: forked from goofer_render_batch's ev_f0)
+    bool f0_alias, picks_on;         // the input f0 is the scaled f0; the map kernel takes the per-frame (f0, mask) picks
+};
+
+static synth_route synth_route_of(const goofer_ctx *ctx, const goofer_batch *b)
+{
+    const goofer_plan_t &p = ctx->plan;
+    synth_route r;
+    r.jit_f0 = b->noise_f0 != nullptr;
+    r.vol_vib = b->volume_vibrato != 0;
+    r.jit_vol = r.vol_vib || (b->noise_vol_h != nullptr && b->noise_vol_b != nullptr);
+    r.sub_on = b->subharm_ratio > 0.0;
+    r.sub_jit = r.sub_on && b->noise_subharm != nullptr;
+    // gf.synthesize behind its time stretch: f0_interp is a float64 array from there on (GOOFER.py:1053) — the f0 jitter multiplies
+    // it (the pulse train sees the float32 cast of the product, :1071-1074) and the sub-harmonic trackers accumulate it (:1077-1097);
+    // a private copy, since the jitters work in place
+    r.f64_on = b->f0_64 != nullptr && (r.jit_f0 || r.sub_on);
+    // the fused overlap-add rings index by position mod n_fft with a mask: power-of-two transforms only (768 / 1536 take the
+    // separate irFFT + gather kernels; 64 .. 256: Bluestein plans)
+    const bool fused = ctx->ola_fused && p.hop % 2 == 0;
+    r.ola_one = fused && (p.n_fft & (p.n_fft - 1)) == 0 && p.bl_L == 0;
+    // The spectra-in-HBM kernels stay for the other geometries, for the volume-jitter / sub-harmonic layers (which edit the
+    // stems or the pulse train between the steps) and as the A/B path.
+    r.walkers = fused && ctx->stems && stems_supported(p) && !r.sub_on && !r.jit_vol;
+    r.ola_split = !r.walkers && fused && ctx->stems && ola_split_supported(p) && !r.jit_vol;
+    r.skip_frames = r.ola_split && ctx->skip_zero && ctx->overlap && !r.sub_on && p.hop <= 512;
+    r.side_on = ctx->overlap && r.ola_one && !r.sub_on;
+    r.early = r.side_on && !r.jit_f0 && ctx->early_req && ctx->early_f0 == b->f0 && ctx->side != nullptr;
+    // f0 * pitch_shift (GOOFER.py:995).  When the caller vouches that every pitch_shift is 1 (the resampler path: the pitch
+    // lives in the curve) and nothing jitters f0 in place, the input array IS the scaled f0 and the pass is skipped.
+    r.f0_alias = b->unit_pitch_shift && !r.jit_f0 && !r.sub_jit;
+    // the picks ride on the map kernel when the scaled f0 is final at that point of the caller's stream: nothing jitters it in
+    // place later, and it is not being produced on the side stream
+    r.picks_on = !r.jit_f0 && !r.sub_jit && !(r.early && !r.f0_alias);
+    return r;
+}
+
+// The scratch of one goofer_synth_batch, in arena order.  Pieces a route does not use are null or empty.
+struct synth_scratch {
+    size_t slots, spec, tframes, env_noise;   // element counts: onset slots, spectrum / time-frame / noise-envelope floats
+    int *frame_note;
+    int64_t *row_src;
+    float2 *picks, *S_h, *S_uv, *S_br;
+    float *f0s, *pulse, *frames, *frames_u, *frames_b, *env_h, *env_n, *note_mag, *note_peak;
+    onset_t *onsets;
+    int32_t *onset_idx, *onset_cnt, *pulse_tiles;
+    double *short_s, *note_steps, *inc = nullptr, *jit_a = nullptr, *jit_b = nullptr, *jit_c = nullptr, *sub_buf = nullptr,
+           *sub_fm = nullptr, *f0d = nullptr;
+    unsigned long long *jit_max = nullptr, *sub_max = nullptr;
+    unsigned char *hopz, *hop_flat = nullptr, *frame_skip = nullptr, *knot_eq = nullptr, *on_f0 = nullptr, *on_vol = nullptr,
+                  *on_sub = nullptr, *on_subj = nullptr;
+};
+
+static void carve_synth(arena &a, const goofer_plan_t &p, const synth_route &r, int64_t F, int64_t N, int n, int ld, synth_scratch &s)
+{
+    // onset slots: n / 2 + 16 per note for the pulse train (an f0 above sr / 2 is refused) — n + 16 with the sub-harmonic layer,
+    // whose tracker fires at most once per sample and does so on every sample once its increment passes 1 (the resampler's
+    // vibrato depth of 3 takes the layer to 8 x f0: above sr / 2 from F7 on)
+    s.slots = (size_t)(r.sub_on ? N : N / 2) + 16 * (size_t)n + 16;
+    s.spec = r.walkers ? 0 : (size_t)F * spec_stride(p.n_bins);
+    s.tframes = r.walkers ? 0 : (size_t)F * p.n_fft;
+    s.env_noise = r.walkers ? 0 : (size_t)F * ld;
+    s.frame_note = a.take<int>(F);
+    s.row_src = a.take<int64_t>(F);
+    s.picks = a.take<float2>(F);                              // per-frame (f0, mask) picks
+    s.f0s = a.take<float>(N);                                 // f0 scaled
+    if (r.sub_on) s.inc = a.take<double>(N);                  // increments of the sub-harmonic trackers
+    s.onsets = (onset_t *)a.take<char>(s.slots * ONSET_BYTES);
+    s.onset_idx = a.take<int32_t>(s.slots);                   // raw onset sample indices
+    s.onset_cnt = a.take<int32_t>(n + 16);
+    s.pulse = a.take<float>(N);
+    s.pulse_tiles = a.take<int32_t>((size_t)PULSE_TILE_INTS(N));   // pulse placement: 4 ints per tile
+    s.S_h = a.take<float2>(s.spec); s.S_uv = a.take<float2>(s.spec); s.S_br = a.take<float2>(s.spec);
+    s.frames = a.take<float>(s.tframes); s.frames_u = a.take<float>(s.tframes); s.frames_b = a.take<float>(s.tframes);
+    s.env_h = a.take<float>((size_t)F * ld);
+    s.env_n = a.take<float>(s.env_noise);
+    s.short_s = a.take<double>(N / 4 + n + 16);               // smoothed decimated mask
+    s.note_mag = a.take<float>(2 * (size_t)n + 16);           // note_mag, note_peak
+    s.note_steps = a.take<double>(2 * (size_t)n + 16);        // per-note linspace steps
+    // stem walkers: a byte per output hop of a note (T + 3 of them) — which stems the noise walker left unstored because they are
+    // exactly zero there (k_noise_stems -> k_note_finish)
+    s.hopz = a.take<unsigned char>(r.walkers ? (size_t)F + 3 * (size_t)n + 64 : 0);
+    if (r.skip_frames) {                                      // per-hop flatness, per-frame skip bits, knot equalities
+        s.hop_flat = a.take<unsigned char>((size_t)F + (size_t)((p.n_fft + p.hop - 1) / p.hop) * n + 16);
+        s.frame_skip = a.take<unsigned char>((size_t)F + 16);
+        s.knot_eq = a.take<unsigned char>((size_t)(N / 4 + n + 16));
+    }
+    if (r.jit_f0 || r.jit_vol || r.sub_jit) {
+        s.jit_a = a.take<double>(N); s.jit_b = a.take<double>(N); s.jit_c = a.take<double>(N);
+        s.jit_max = a.take<unsigned long long>(3 * (size_t)n + 16); s.on_f0 = a.take<unsigned char>(n + 16); s.on_vol = a.take<unsigned char>(n + 16);
+    }
+    if (r.sub_on) {
+        s.sub_buf = a.take<double>(N); s.sub_fm = a.take<double>(N); s.sub_max = a.take<unsigned long long>(n + 16);
+        s.on_sub = a.take<unsigned char>(n + 16); s.on_subj = a.take<unsigned char>(n + 16);
+    }
+    if (r.f64_on) s.f0d = a.take<double>(N);
 }
 
 static int ensure_small(goofer_ctx *ctx, size_t bytes)
@@ -646,9 +722,19 @@ int goofer_pulse_model(goofer_ctx *ctx, double Ra, double Rg, double Rk)
 int goofer_reserve(goofer_ctx *ctx, int64_t max_frames, int64_t max_samples, int64_t max_notes)
 {
     if (!ctx) return GOOFER_EINVAL;
-    if (!ctx->plan.n_fft) return goofer_fail(ctx, GOOFER_ENOPLAN, "goofer_plan first");
-    const bool walkers = ctx->stems && ctx->ola_fused && stems_supported(ctx->plan);   // else: room for the spectra of the one-kernel-per-step path
-    return ensure_scratch(ctx, scratch_need(ctx->plan, max_frames, max_samples, max_notes, walkers ? 0 : 1, !walkers));
+    const goofer_plan_t &p = ctx->plan;
+    if (!p.n_fft) return goofer_fail(ctx, GOOFER_ENOPLAN, "goofer_plan first");
+    goofer_batch plain = {};
+    plain.total_frames = max_frames;
+    plain.total_samples = max_samples;
+    plain.n_notes = (int)max_notes;
+    synth_route r = synth_route_of(ctx, &plain);
+    // the spectra routes keep room for the 'sg' layer (one onset slot per sample, the trackers) and the skip bits as well
+    if (!r.walkers) r.sub_on = r.skip_frames = true;
+    synth_scratch s;
+    arena count{nullptr, 0};
+    carve_synth(count, p, r, max_frames, max_samples, (int)max_notes, (p.n_bins + 3) & ~3, s);
+    return ensure_scratch(ctx, count.used + 8192);   // (never less than the hand-summed size it replaces)
 }
 
 // copy one plan table to host memory (tests / debugging); which: 0 window 1 freqs 2 boost 3 bright_h
@@ -670,6 +756,8 @@ int goofer_debug_table(goofer_ctx *ctx, int which, float *host_out, int capacity
 // 0 frame_note 1 row_src 2 f0_scaled 3 pulse 4 S_harm 5 S_uv 6 S_breath 7 frames(last stem) 8 env_harm
 // 9 env_noise 10 mask_short 11 note_mag 12 note_peak 13 onset_cnt 14 onset_idx (13, 14: also of the last goofer_pulse_train)
 // 15 frame_skip (the spectra-in-HBM pipeline with per-frame skipping: one byte per frame).
+// onset_idx holds every onset slot: note k's onsets start at sample_off[k] / 2 + 16 k — after a batch with the 'sg' layer at
+// sample_off[k] + 16 k, where k_pulse_onsets_wrap left the sub-harmonic onsets of the last ratio (onset_cnt: their counts).
 // Returns the byte size.
 /* Host helper of the note planner (goofer_amd/sampler.py, SillySampler.py:264-283): Gaussian FIR along the rows of a small
  * fp64 matrix with numpy 'reflect' padding, accumulated tap by tap in ascending order (product rounded, then added: the
@@ -703,7 +791,8 @@ int goofer_host_gauss_rows(const double *x, int64_t rows, int T, const double *t
 }
 
 /* Synchronise the device and report what the asynchronous batch calls could not: a note whose pulse onsets did not fit its
- * onset slots (n / 2 + 16 per note — more than one pulse per two samples; the onsets beyond were dropped).  The flag is a
+ * onset slots (n / 2 + 16 per note — more than one pulse per two samples; the onsets beyond were dropped.  The 'sg' layer's
+ * trackers fire at most once per sample into n + 16 slots per note, the layout such a batch leaves behind).  The flag is a
  * handle-owned word every pulse-chain launch (goofer_pulse_train, goofer_synth_batch / goofer_render_batch incl. the extra
  * synthesis calls of the post chain) raises with atomicMax; it stays up until this call reads and clears it. */
 int goofer_check(goofer_ctx *ctx)
@@ -716,7 +805,7 @@ int goofer_check(goofer_ctx *ctx)
     if (v != 0) {
         HIP_TRY(ctx, hipMemset(ctx->ovf_flag, 0, sizeof(v)));        // reported once
         return goofer_fail(ctx, GOOFER_EINVAL, "note %d of a batch since the last check has more pulse onsets than n / 2 + 16 (f0 above "
-                           "sr / 2?): the pulses beyond its onset slots were dropped", v - 1);
+                           "sr / 2?): the pulses beyond its onset slots were dropped (the 'sg' layer's trackers have n + 16)", v - 1);
     }
     return GOOFER_OK;
 }
@@ -832,6 +921,7 @@ static const char *const PROF_NAMES_STEMS[PROF_STAGES] = {
     "setup_maps", "", "", "phase_inc", "pulse_onsets", "pulse_place", "mask_short", "noise_stems",
     "", "harm_stem", "", "", "", "note_finish", "", "env_edit", "env_rows", "sample_assemble"};
 
+// fused_ola routes; ola_split reports k_irfft_ola1 as irfft_ola3 and k_note_finish as apply_gain (bench.py keys on these names)
 static const char *const PROF_NAMES_OLA[PROF_STAGES] = {
     "setup_maps", "", "", "phase_inc", "pulse_onsets", "pulse_place", "rfft_frames", "harm_shape",
     "", "noise_spectra", "", "", "mask_short", "irfft_ola3", "apply_gain", "env_edit", "env_rows", "sample_assemble"};
@@ -909,21 +999,21 @@ int goofer_pulse_train(goofer_ctx *ctx, const float *f0, const int64_t *sample_o
 {
     NEED_PLAN(ctx);
     hipStream_t st = (hipStream_t)stream;
-    size_t need = total_samples * sizeof(double) + (total_samples / 2 + 16 * (size_t)n_notes + 16) * (ONSET_BYTES + 4) +
-                  n_notes * sizeof(int32_t) + 8192;
-    int rc = ensure_scratch(ctx, need);
+    const size_t slots = (size_t)(total_samples / 2) + 16 * (size_t)n_notes + 16;   // n / 2 + 16 per note: an f0 above sr / 2 is refused
+    double *inc;
+    onset_t *onsets;
+    int32_t *oidx, *cnt;
+    int rc = carve_scratch(ctx, [&](arena &a) {
+        inc = a.take<double>(total_samples + 16);          // (also holds the placement's tile table: 16 bytes per 256 * PP_SPT samples)
+        onsets = (onset_t *)a.take<char>(slots * ONSET_BYTES);
+        oidx = a.take<int32_t>(slots);
+        cnt = a.take<int32_t>(n_notes + 16);
+    });
     if (rc) return rc;
-    arena a{(char *)ctx->scratch, ctx->scratch_bytes, 0};
-    double *inc = a.take<double>(total_samples + 16);          // (also holds the placement's tile table: 16 bytes per 256 * PP_SPT samples)
-    char *onsets = a.take<char>((total_samples / 2 + 16 * (size_t)n_notes + 16) * ONSET_BYTES);
-    int32_t *oidx = a.take<int32_t>(total_samples / 2 + 16 * (size_t)n_notes + 16);
-    int32_t *cnt = a.take<int32_t>(n_notes + 16);
-    int32_t *ovf = ctx->ovf_flag;
-    if (!inc || !onsets || !oidx || !cnt) return goofer_fail(ctx, GOOFER_ENOMEM, "scratch arena too small");
     for (int i = 0; i < 16; ++i) ctx->dbg_ptr[i] = nullptr;
     ctx->dbg_ptr[13] = cnt; ctx->dbg_bytes[13] = n_notes * sizeof(int32_t);
-    ctx->dbg_ptr[14] = oidx; ctx->dbg_bytes[14] = (total_samples / 2 + 16 * (size_t)n_notes) * sizeof(int32_t);
-    return launch_pulse_train(ctx, f0, 1.0f, sample_off, n_notes, total_samples, pulse, inc, (onset_t *)onsets, oidx, cnt, ovf, st);
+    ctx->dbg_ptr[14] = oidx; ctx->dbg_bytes[14] = slots * sizeof(int32_t);
+    return launch_pulse_train(ctx, f0, 1.0f, sample_off, n_notes, total_samples, pulse, inc, onsets, oidx, cnt, ctx->ovf_flag, st);
 }
 
 int goofer_gauss_bins(goofer_ctx *ctx, const float *in, float *out, int64_t rows, int n_bins, int ld, const double *taps,
@@ -953,39 +1043,6 @@ int goofer_warp_bins(goofer_ctx *ctx, const float *in, float *out, int64_t rows,
     return launch_warp_bins(ctx, in, out, rows, n_bins, ld, formants, d_shift, nullptr, nullptr, nullptr, ratio, st);
 }
 
-int goofer_knot_decode(goofer_ctx *ctx, const uint16_t *knots_f16, int K, const float *hz_knots, int64_t rows, float *env,
-                       int n_bins, int ld, void *stream)
-{
-    NEED_PLAN(ctx);
-    if (K < 2 || K > 4096) return goofer_fail(ctx, GOOFER_EINVAL, "bad knot count %d", K);
-    hipStream_t st = (hipStream_t)stream;
-    const goofer_plan_t &p = ctx->plan;
-    // 2-tap lerp plan, fp32 arithmetic like precompute_interp_matrix (GOOFER.py:84-90)
-    std::vector<int> idx(n_bins);
-    std::vector<float> w0(n_bins), w1(n_bins);
-    double val = 1.0 / ((double)p.n_fft * (1.0 / (double)p.sr));
-    for (int b = 0; b < n_bins; ++b) {
-        float f = (float)((double)b * val);
-        int i = (int)(std::upper_bound(hz_knots, hz_knots + K, f) - hz_knots) - 1;   // searchsorted(side='right') - 1
-        i = std::min(std::max(i, 0), K - 2);
-        float x0 = hz_knots[i], x1 = hz_knots[i + 1];
-        float den = std::max(x1 - x0, 1e-12f);
-        float b1 = (f - x0) / den;
-        idx[b] = i; w1[b] = b1; w0[b] = 1.0f - b1;
-    }
-    int rc = ensure_small(ctx, 65536);
-    if (rc) return rc;
-    if ((size_t)n_bins * 12 > 32768) return goofer_fail(ctx, GOOFER_EINVAL, "n_bins too large");
-    char *d = (char *)ctx->small;
-    int *d_idx = (int *)d;
-    float *d_w0 = (float *)(d + 4 * (size_t)n_bins), *d_w1 = (float *)(d + 8 * (size_t)n_bins);
-    HIP_TRY(ctx, hipMemcpyAsync(d_idx, idx.data(), n_bins * sizeof(int), hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(d_w0, w0.data(), n_bins * sizeof(float), hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(d_w1, w1.data(), n_bins * sizeof(float), hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));   // the host vectors die at return
-    return launch_knot_decode(ctx, knots_f16, K, rows, d_idx, d_w0, d_w1, env, n_bins, ld, st);
-}
-
 static void knot_lerp_plan(const goofer_plan_t &p, const float *hz_knots, int K, int n_bins, std::vector<int> &idx,
                            std::vector<float> &w0, std::vector<float> &w1)
 {
@@ -1001,6 +1058,28 @@ static void knot_lerp_plan(const goofer_plan_t &p, const float *hz_knots, int K,
         float b1 = (f - x0) / den;
         idx[b] = i; w1[b] = b1; w0[b] = 1.0f - b1;
     }
+}
+
+int goofer_knot_decode(goofer_ctx *ctx, const uint16_t *knots_f16, int K, const float *hz_knots, int64_t rows, float *env,
+                       int n_bins, int ld, void *stream)
+{
+    NEED_PLAN(ctx);
+    if (K < 2 || K > 4096) return goofer_fail(ctx, GOOFER_EINVAL, "bad knot count %d", K);
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<int> idx;
+    std::vector<float> w0, w1;
+    knot_lerp_plan(ctx->plan, hz_knots, K, n_bins, idx, w0, w1);
+    int rc = ensure_small(ctx, 65536);
+    if (rc) return rc;
+    if ((size_t)n_bins * 12 > 32768) return goofer_fail(ctx, GOOFER_EINVAL, "n_bins too large");
+    char *d = (char *)ctx->small;
+    int *d_idx = (int *)d;
+    float *d_w0 = (float *)(d + 4 * (size_t)n_bins), *d_w1 = (float *)(d + 8 * (size_t)n_bins);
+    HIP_TRY(ctx, hipMemcpyAsync(d_idx, idx.data(), n_bins * sizeof(int), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_w0, w0.data(), n_bins * sizeof(float), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_w1, w1.data(), n_bins * sizeof(float), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));   // the host vectors die at return
+    return launch_knot_decode(ctx, knots_f16, K, rows, d_idx, d_w0, d_w1, env, n_bins, ld, st);
 }
 
 int goofer_mag_rows(goofer_ctx *ctx, const float *S, int ldc, int64_t rows, int n_bins, float *mag, int ld, void *stream)
@@ -1253,21 +1332,19 @@ int goofer_post_batch(goofer_ctx *ctx, const goofer_post *p, void *stream)
     if (!taps20.empty()) memcpy(host.data() + o_t20, taps20.data(), taps20.size() * sizeof(double));
     if (!taps_pd.empty()) memcpy(host.data() + o_tpd, taps_pd.data(), taps_pd.size() * sizeof(double));
 
-    const bool need_tmp = any_fry || any_st;
-    const bool need_d = any_sd || any_pd;
-    size_t need = blob + 4096 + (need_tmp ? 2 * al((size_t)N * sizeof(float)) : 0) +
-                  (need_d ? 2 * al((size_t)N * sizeof(double)) : 0) + (any_pd ? al((size_t)N * sizeof(double)) : 0) +
-                  4 * al((size_t)n * sizeof(double));
-    int rc = ensure_scratch(ctx, need);
+    unsigned char *d_blob;
+    float *tmpA = nullptr, *tmpB = nullptr;                   // fry / st: filtered copies of harm and breath
+    double *tmpD1 = nullptr, *tmpD2 = nullptr, *dyn = nullptr; // sd / pd: smoothed curves; pd: the gain curve
+    double *sums, *ref;
+    int rc = carve_scratch(ctx, [&](arena &a) {
+        d_blob = a.take<unsigned char>(blob);
+        if (any_fry || any_st) { tmpA = a.take<float>(N); tmpB = a.take<float>(N); }
+        if (any_sd || any_pd) { tmpD1 = a.take<double>(N); tmpD2 = a.take<double>(N); }
+        if (any_pd) dyn = a.take<double>(N);
+        sums = a.take<double>(2 * (size_t)n);
+        ref = a.take<double>(n);
+    });
     if (rc) return rc;
-    arena a{(char *)ctx->scratch, ctx->scratch_bytes, 0};
-    unsigned char *d_blob = a.take<unsigned char>(blob);
-    float *tmpA = need_tmp ? a.take<float>(N) : nullptr, *tmpB = need_tmp ? a.take<float>(N) : nullptr;
-    double *tmpD1 = need_d ? a.take<double>(N) : nullptr, *tmpD2 = need_d ? a.take<double>(N) : nullptr;
-    double *dyn = any_pd ? a.take<double>(N) : nullptr;
-    double *sums = a.take<double>(2 * (size_t)n), *ref = a.take<double>(n);
-    if (!d_blob || !sums || !ref || (need_tmp && (!tmpA || !tmpB)) || (need_d && (!tmpD1 || !tmpD2)) || (any_pd && !dyn))
-        return goofer_fail(ctx, GOOFER_ENOMEM, "scratch arena too small");
     HIP_TRY(ctx, hipMemcpyAsync(d_blob, host.data(), blob, hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));                   // the staging vector dies with this call
     const goofer_post_note *d_notes = (const goofer_post_note *)(d_blob + o_notes);
@@ -1329,6 +1406,183 @@ static int ensure_side_stream(goofer_ctx *ctx)
     return GOOFER_OK;
 }
 
+// Per-stage timing of one goofer_synth_batch: stage s runs from event s to event s + 1 on the caller's stream.  Option
+// "prof_only" = s records only the events stage s needs (bench.py's timed steps carry the dominant kernel's two events; the
+// twenty records of the full breakdown cost 0.06 ms of a 2.3 ms step).  When the pulse chain runs on the side stream it is
+// bracketed there (prof_side), and the two kernels launched beside it on the caller's stream (stages 6 / 7 of the stem path,
+// 9 / 12 of the other) by the prof_main2 pair.
+struct stage_clock {
+    goofer_ctx *ctx;
+    hipStream_t st;
+    bool side;
+    hipEvent_t *ev = nullptr;   // this step's PROF_STAGES + 1 events; null: the step is not profiled
+    int next = 0;               // the stage whose opening event comes next
+
+    stage_clock(goofer_ctx *c, hipStream_t s, const synth_route &r) : ctx(c), st(s), side(r.side_on)
+    {
+        if (ctx->prof_on && ctx->prof_steps < ctx->prof_cap) ev = ctx->prof_ev + (size_t)ctx->prof_steps * (PROF_STAGES + 1);
+        if (ev) ctx->prof_stems = r.walkers;
+        if (side || ev) ctx->prof_side_used = side;
+    }
+    int record(bool want, hipEvent_t *pool, size_t i, hipStream_t on)
+    {
+        if (ev && want) HIP_TRY(ctx, hipEventRecord(pool[i], on));
+        return GOOFER_OK;
+    }
+    // open stage s, after the (empty) stages skipped on the way; close(): end the last one
+    int at(int s)
+    {
+        const int o = ctx->prof_only;
+        for (int rc; next <= s; ++next)
+            if ((rc = record(o < 0 || next == o || next == o + 1 || (next == 5 && (o == 6 || o == 9)), ev, next, st))) return rc;
+        return GOOFER_OK;
+    }
+    int close()
+    {
+        const int rc = at(PROF_STAGES);
+        if (!rc && ev) ctx->prof_steps++;
+        return rc;
+    }
+    // boundary k of the pulse chain on the side stream; the end of the q-th kernel launched beside it on the caller's stream
+    int pulse(int k, hipStream_t pst) { return record(side && in(3, 5), ctx->prof_side, (size_t)ctx->prof_steps * 4 + k, pst); }
+    int beside(int q) { return record(in(6, 7) || in(9, 9) || in(12, 12), ctx->prof_main2, (size_t)ctx->prof_steps * 2 + q, st); }
+    bool in(int lo, int hi) const { return ctx->prof_only < 0 || (ctx->prof_only >= lo && ctx->prof_only <= hi); }
+};
+
+// One goofer_synth_batch in flight: what the driver hands to its route's tail, and the launches written once for both
+struct synth_call {
+    goofer_ctx *ctx;
+    const goofer_batch *b;
+    const synth_route &r;
+    synth_scratch &s;
+    stage_clock &clk;
+    hipStream_t st;
+    int64_t F, N;
+    int n;
+
+    int mask_short() const
+    {
+        return launch_mask_short(ctx, b->mask, b->sample_off, n, N, ctx->mask_taps, ctx->mask_taps_radius, ctx->mask_taps_sum, s.short_s, st);
+    }
+    int frame_picks() const
+    {
+        return r.picks_on ? GOOFER_OK : launch_frame_picks(ctx, b->frame_off, s.frame_note, F, b->sample_off, s.f0s, b->mask, s.picks, st);
+    }
+    // aperiodic half of the stem-split path: the two noise stems straight to samples (needs the smoothed mask knots and the final
+    // scaled f0, nothing of the pulse chain)
+    int noise_walker() const
+    {
+        return launch_noise_stems(ctx, b->env_noise ? b->env_noise : b->env, b->ld, s.row_src, b->phi, F, s.frame_note, b->frame_off,
+                                  b->sample_off, s.picks, b->params, b->seed, b->env_noise != nullptr, s.short_s, s.note_steps, b->uv,
+                                  b->bre, s.hopz, st);
+    }
+    // (frame_skip is null unless skip_frames, which runs on the side-stream route)
+    int noise_spectra() const
+    {
+        return launch_noise_spectra(ctx, s.S_uv, s.S_br, spec_stride(ctx->plan.n_bins), F, s.frame_note, b->frame_off, b->sample_off, s.f0s,
+                                    b->mask, b->env_noise ? b->env_noise : b->env, b->phi, b->ld, b->params, b->seed, s.row_src,
+                                    b->env_noise != nullptr, s.frame_skip, st);
+    }
+    // Harmonic envelope rows for the harmonic walker: formant-anchored + uniform warp, one wave per row (GOOFER.py:1004-1017).
+    // Not inside the walker: the crossing-anchor path is several times slower than the sorted one, and a walker wave holds
+    // ~95 frames of ONE note, so the slow notes would set the kernel's time.
+    int warp(hipStream_t on) const
+    {
+        return launch_warp_bins(ctx, b->env, s.env_h, F, ctx->plan.n_bins, b->ld, b->formants, nullptr, b->params, s.frame_note, s.row_src,
+                                1.0, on);
+    }
+    bool keep_stems() const { return !(b->mix_only && (b->mix || b->rec)); }
+
+    // The stem walkers after the pulse chain: mask smoothing, noise walker and warp (unless they ran beside the pulse chain), the
+    // harmonic walker, the per-note finish
+    int walker_tail()
+    {
+        int rc;
+        if ((rc = clk.at(6))) return rc;                        // 6: mask_short
+        if (!r.side_on && (rc = mask_short())) return rc;
+        if ((rc = clk.at(7))) return rc;                        // 7: noise_stems
+        if (!r.side_on) {
+            if ((rc = frame_picks())) return rc;
+            if ((rc = noise_walker())) return rc;
+            if (!ctx->warp_done && (rc = warp(st))) return rc;
+        }
+        if ((rc = clk.at(9))) return rc;                        // 9: harm_stem = rFFT + shaping + irFFT + overlap-add of the harmonic stem
+        // (goofer_render_batch: the assembly already wrote the warped rows)
+        if ((rc = launch_harm_stem(ctx, s.pulse, ctx->warp_done ? ctx->warp_rows : s.env_h, ctx->warp_done ? b->env : nullptr, b->formants != nullptr,
+                                   b->ld, ctx->warp_done ? s.row_src : nullptr, F, s.frame_note, b->frame_off, b->sample_off, s.picks, b->params,
+                                   b->harm, s.note_mag, st)))
+            return rc;
+        if ((rc = clk.at(13))) return rc;                       // 13: harm / max|S|, peak, gain, reconstruct, mix
+        if ((rc = launch_note_finish(ctx, b->harm, b->uv, b->bre, b->rec, b->mix, b->sample_off, n, b->params, s.note_mag, s.note_peak,
+                                     keep_stems(), s.hopz, b->frame_off, st)))
+            return rc;
+        return clk.close();
+    }
+
+    // The spectra in HBM after the pulse chain: rFFT, shaping, irFFTs, then the overlap-add (one stem per wave, three, or separate
+    // kernels) with the gains, the volume jitter, the gain
+    int spectra_tail()
+    {
+        const int ldc = spec_stride(ctx->plan.n_bins);
+        int rc;
+        if ((rc = clk.at(6))) return rc;                        // 6: framewise rFFT of the pulse train
+        if ((rc = launch_rfft_frames_mapped(ctx, s.pulse, b->sample_off, b->frame_off, s.frame_note, F, s.S_h, ldc, st))) return rc;
+        if ((rc = clk.at(7))) return rc;
+        if ((rc = launch_harm_shape(ctx, s.S_h, ldc, F, s.frame_note, b->frame_off, b->sample_off, s.f0s, b->mask, b->env, b->ld, b->params,
+                                    s.note_mag, s.row_src, b->formants, b->no_warp != 0, st)))
+            return rc;
+        if ((rc = clk.at(8))) return rc;
+        if (!r.ola_one && (rc = launch_irfft_frames(ctx, s.S_h, ldc, F, s.frames, st))) return rc;
+        if ((rc = clk.at(9))) return rc;                        // 9: aperiodic spectra
+        if (!r.side_on && (rc = noise_spectra())) return rc;
+        if ((rc = clk.at(10))) return rc;
+        if (!r.ola_one && (rc = launch_irfft_frames(ctx, s.S_br, ldc, F, s.frames_b, st))) return rc;
+        if ((rc = clk.at(11))) return rc;
+        if (!r.ola_one && (rc = launch_irfft_frames(ctx, s.S_uv, ldc, F, s.frames_u, st))) return rc;
+        if ((rc = clk.at(12))) return rc;                       // 12: decimated + smoothed voicing mask
+        if (!r.side_on && (rc = mask_short())) return rc;
+        if ((rc = clk.at(13))) return rc;                       // 13: (irFFT of the three stems +) overlap-add + gains + per-note peak
+        if (r.ola_split) {
+            if ((rc = launch_irfft_ola1(ctx, s.S_h, s.S_uv, s.S_br, ldc, F, s.frame_note, b->frame_off, b->sample_off, n, s.short_s, s.note_steps,
+                                        b->params, b->harm, b->uv, b->bre, s.frame_skip, st)))
+                return rc;
+            if ((rc = clk.at(14))) return rc;
+            if ((rc = launch_note_finish(ctx, b->harm, b->uv, b->bre, b->rec, b->mix, b->sample_off, n, b->params, s.note_mag, s.note_peak,
+                                         keep_stems(), nullptr, nullptr, st)))
+                return rc;
+            return clk.close();
+        }
+        if (r.ola_one) {
+            if ((rc = launch_irfft_ola3(ctx, s.S_h, s.S_uv, s.S_br, ldc, F, s.frame_note, b->frame_off, b->sample_off, n, s.note_mag, s.short_s,
+                                        s.note_steps, b->params, b->harm, b->uv, b->bre, s.note_peak, st)))
+                return rc;
+        } else if ((rc = launch_ola3_gains(ctx, s.frames, s.frames_u, s.frames_b, s.note_mag, s.short_s, b->sample_off, b->frame_off, n, N,
+                                           b->params, s.note_steps, b->harm, b->uv, b->bre, s.note_peak, st)))
+            return rc;
+        if (r.jit_vol) {  // 'sr': volume jitter on harm / breath, then the peak is taken again (GOOFER.py:1185-1193)
+            const double *d_t = nullptr, *d_t20; int rt = 0, r20;
+            if (!r.vol_vib && (rc = upload_jitter_taps(ctx, (double)b->vol_jitter_sigma, 1, &d_t, &rt, st))) return rc;
+            if ((rc = upload_jitter_taps(ctx, 20.0, 2, &d_t20, &r20, st))) return rc;
+            if (!r.vol_vib) {
+                if ((rc = launch_gauss_samples<double>(ctx, b->noise_vol_h, b->sample_off, n, N, d_t, rt, s.on_vol, s.jit_a, st))) return rc;
+                if ((rc = launch_gauss_samples<double>(ctx, b->noise_vol_b, b->sample_off, n, N, d_t, rt, s.on_vol, s.jit_b, st))) return rc;
+                if ((rc = launch_note_absmax(ctx, s.jit_a, b->sample_off, n, N, s.on_vol, s.jit_max + n, st))) return rc;
+                if ((rc = launch_note_absmax(ctx, s.jit_b, b->sample_off, n, N, s.on_vol, s.jit_max + 2 * (size_t)n, st))) return rc;
+            }
+            if ((rc = launch_gauss_samples<float>(ctx, b->mask, b->sample_off, n, N, d_t20, r20, s.on_vol, s.jit_c, st))) return rc;
+            if ((rc = launch_volume_jitter(ctx, b->harm, b->bre, s.jit_a, s.jit_b, s.jit_c, s.jit_max + n, s.jit_max + 2 * (size_t)n, b->sample_off,
+                                           n, N, b->params, r.vol_vib ? 1 : 0, (double)b->vol_jitter_speed, st)))
+                return rc;
+            HIP_TRY(ctx, hipMemsetAsync(s.note_peak, 0, (size_t)n * sizeof(float), st));
+            if ((rc = launch_stem_peak(ctx, b->harm, b->uv, b->bre, b->sample_off, n, N, s.note_peak, st))) return rc;
+        }
+        if ((rc = clk.at(14))) return rc;                       // 14: gain, reconstruct, mix
+        if ((rc = launch_apply_gain(ctx, b->harm, b->uv, b->bre, b->rec, b->mix, b->sample_off, n, N, b->params, s.note_peak, keep_stems(), st)))
+            return rc;
+        return clk.close();
+    }
+};
+
 int goofer_synth_batch(goofer_ctx *ctx, const goofer_batch *b, void *stream)
 {
     NEED_PLAN(ctx);
@@ -1339,98 +1593,22 @@ int goofer_synth_batch(goofer_ctx *ctx, const goofer_batch *b, void *stream)
     hipStream_t st = (hipStream_t)stream;
     ctx->frame_picks = nullptr;
     const int64_t F = b->total_frames, N = b->total_samples;
-    const int n = b->n_notes, ld = b->ld, ldc = spec_stride(p.n_bins);
-
-    const bool jit_f0 = b->noise_f0 != nullptr, vol_vib = b->volume_vibrato != 0,
-               jit_vol = vol_vib || (b->noise_vol_h != nullptr && b->noise_vol_b != nullptr);
-    const bool sub_on = b->subharm_ratio > 0.0;
-    const bool sub_jit = sub_on && b->noise_subharm != nullptr;
-    // gf.synthesize behind its time stretch: f0_interp is a float64 array from there on (GOOFER.py:1053) — the f0 jitter multiplies
-    // it (the pulse train sees the float32 cast of the product, :1071-1074) and the sub-harmonic trackers accumulate it (:1077-1097);
-    // a private copy, since the jitters work in place
-    const bool f64_on = b->f0_64 != nullptr && (jit_f0 || sub_on);
-    const size_t jit_bytes = ((jit_f0 || jit_vol || sub_jit) ? (3 * (size_t)N * sizeof(double) + 3 * 256 * (size_t)n + 8192) : 0) +
-                             (sub_on ? ((size_t)N * (sizeof(double) + sizeof(double)) + 3 * 256 * (size_t)n + 8192) : 0) +
-                             (f64_on ? (size_t)N * sizeof(double) + 1024 : 0);
-    // which pipeline will run decides what the arena holds (the same predicate as `stem_path` below)
-    const bool walkers = ctx->stems && ctx->ola_fused && (p.hop % 2 == 0) && stems_supported(p) && !sub_on && !jit_vol;
-    // n_fft 2048: one stem per wave (two waves per SIMD instead of one), then the per-note finish of the stem-split path
-    const bool ola_split = !walkers && ctx->ola_fused && (p.hop % 2 == 0) && ctx->stems && ola_split_supported(p) && !jit_vol;
-    int rc = ensure_scratch(ctx, scratch_need(p, F, N, n, walkers ? 0 : 1, sub_on) + (size_t)F * (ld - ((p.n_bins + 3) & ~3)) * 2 * sizeof(float) + jit_bytes);
+    const int n = b->n_notes;
+    const synth_route r = synth_route_of(ctx, b);
+    synth_scratch s;
+    int rc = carve_scratch(ctx, [&](arena &a) { carve_synth(a, p, r, F, N, n, b->ld, s); });
     if (rc) return rc;
-    arena a{(char *)ctx->scratch, ctx->scratch_bytes, 0};
-    int *frame_note = a.take<int>(F);
-    int64_t *row_src = a.take<int64_t>(F);
-    float2 *picks = a.take<float2>(F);
-    float *f0s = a.take<float>(N);
-    double *inc = sub_on ? a.take<double>(N) : nullptr;       // increments of the sub-harmonic trackers ('sg') only
-    const size_t onset_slots = (size_t)(sub_on ? N : N / 2) + 16 * (size_t)n + 16;   // (see scratch_need)
-    char *onsets = a.take<char>(onset_slots * ONSET_BYTES);
-    int32_t *onset_idx = a.take<int32_t>(onset_slots);
-    int32_t *onset_cnt = a.take<int32_t>(n + 16);
-    int32_t *ovf = ctx->ovf_flag;
-    float *pulse = a.take<float>(N);
-    int32_t *pulse_tiles = a.take<int32_t>((size_t)PULSE_TILE_INTS(N));
-    const size_t spec_n = walkers ? 0 : (size_t)F * ldc, frame_n = walkers ? 0 : (size_t)F * p.n_fft;
-    float2 *S_h = a.take<float2>(spec_n);
-    float2 *S_uv = a.take<float2>(spec_n);
-    float2 *S_br = a.take<float2>(spec_n);
-    float *frames = a.take<float>(frame_n);
-    float *frames_u = a.take<float>(frame_n);
-    float *frames_b = a.take<float>(frame_n);
-    float *env_h = a.take<float>((size_t)F * ld);
-    float *env_n = a.take<float>(walkers ? 0 : (size_t)F * ld);
-    double *short_s = a.take<double>(N / 4 + n + 16);
-    float *note_mag = a.take<float>(2 * (size_t)n + 16);
-    double *note_steps = a.take<double>(2 * (size_t)n + 16);
-    // stem walkers: a byte per output hop of a note (T + 3 of them) — which stems the noise walker left unstored because they are
-    // exactly zero there (k_noise_stems -> k_note_finish)
-    unsigned char *hopz = a.take<unsigned char>(walkers ? (size_t)F + 3 * (size_t)n + 64 : 0);
-    // ... with the exact sparsity of the noise stems decided per frame up front (k_frame_skip)
-    const bool skip_frames = ola_split && ctx->skip_zero && ctx->overlap && !sub_on && p.hop <= 512;
-    unsigned char *hop_flat = skip_frames ? a.take<unsigned char>((size_t)F + (size_t)((p.n_fft + p.hop - 1) / p.hop) * n + 16) : nullptr;
-    unsigned char *frame_skip = skip_frames ? a.take<unsigned char>((size_t)F + 16) : nullptr;
-    unsigned char *knot_eq = skip_frames ? a.take<unsigned char>((size_t)(N / 4 + n + 16)) : nullptr;
-    if (skip_frames && (!hop_flat || !frame_skip || !knot_eq)) return goofer_fail(ctx, GOOFER_ENOMEM, "scratch arena too small");
-    if (!picks || !frames_u || !frames_b || !frame_note || !row_src || !f0s || (sub_on && !inc) || !onsets || !onset_idx || !onset_cnt || !ovf || !pulse || !pulse_tiles || !S_h || !S_uv || !S_br || !frames ||
-        !env_h || !env_n || !short_s || !note_mag || !note_steps || !hopz)
-        return goofer_fail(ctx, GOOFER_ENOMEM, "scratch arena too small");
-    float *note_peak = note_mag + n;
-    double *jit_a = nullptr, *jit_b = nullptr, *jit_c = nullptr;
-    unsigned long long *jit_max = nullptr;
-    unsigned char *on_f0 = nullptr, *on_vol = nullptr;
-    if (jit_f0 || jit_vol || sub_jit) {
-        jit_a = a.take<double>(N); jit_b = a.take<double>(N); jit_c = a.take<double>(N);
-        jit_max = a.take<unsigned long long>(3 * (size_t)n + 16);
-        on_f0 = a.take<unsigned char>(n + 16); on_vol = a.take<unsigned char>(n + 16);
-        if (!jit_a || !jit_b || !jit_c || !jit_max || !on_f0 || !on_vol) return goofer_fail(ctx, GOOFER_ENOMEM, "scratch arena too small");
-    }
-    double *sub_buf = nullptr;
-    double *sub_fm = nullptr;
-    unsigned long long *sub_max = nullptr;
-    unsigned char *on_sub = nullptr, *on_subj = nullptr;
-    if (sub_on) {
-        sub_buf = a.take<double>(N); sub_fm = a.take<double>(N);
-        sub_max = a.take<unsigned long long>(n + 16); on_sub = a.take<unsigned char>(n + 16);
-        on_subj = a.take<unsigned char>(n + 16);
-        if (!sub_buf || !sub_fm || !sub_max || !on_sub || !on_subj) return goofer_fail(ctx, GOOFER_ENOMEM, "scratch arena too small");
-    }
-    double *f0d = nullptr;
-    if (f64_on) {
-        f0d = a.take<double>(N);
-        if (!f0d) return goofer_fail(ctx, GOOFER_ENOMEM, "scratch arena too small");
-        HIP_TRY(ctx, hipMemcpyAsync(f0d, b->f0_64, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, st));
-    }
-    {
-        const void *ptrs[] = {frame_note, row_src, f0s, pulse, S_h, S_uv, S_br, frames, env_h, env_n, short_s, note_mag, note_peak, onset_cnt};
-        size_t bytes[] = {F * sizeof(int), F * sizeof(int64_t), N * sizeof(float), N * sizeof(float), spec_n * sizeof(float2),
-                          spec_n * sizeof(float2), spec_n * sizeof(float2), frame_n * sizeof(float),
-                          (size_t)F * ld * sizeof(float), walkers ? 0 : (size_t)F * ld * sizeof(float), (N / 4 + n) * sizeof(double),
-                          n * sizeof(float), n * sizeof(float), n * sizeof(int32_t)};
-        for (int i = 0; i < 14; ++i) { ctx->dbg_ptr[i] = ptrs[i]; ctx->dbg_bytes[i] = bytes[i]; }
-        ctx->dbg_ptr[14] = onset_idx; ctx->dbg_bytes[14] = (N / 2 + 16 * (size_t)n) * sizeof(int32_t);
-        ctx->dbg_ptr[15] = frame_skip; ctx->dbg_bytes[15] = frame_skip ? (size_t)F : 0;   // per frame: bit 0 unvoiced, bit 1 breath transform skipped
-    }
+    s.note_peak = s.note_mag + n;
+    if (r.f64_on) HIP_TRY(ctx, hipMemcpyAsync(s.f0d, b->f0_64, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, st));
+    if (r.f0_alias) s.f0s = const_cast<float *>(b->f0);
+    // the debug views (goofer_debug_fetch); frame_skip per frame: bit 0 unvoiced, bit 1 breath transform skipped
+    const void *views[16] = {s.frame_note, s.row_src, s.f0s, s.pulse, s.S_h, s.S_uv, s.S_br, s.frames, s.env_h, s.env_n, s.short_s,
+                             s.note_mag, s.note_peak, s.onset_cnt, s.onset_idx, s.frame_skip};
+    const size_t view_bytes[16] = {F * sizeof(int), F * sizeof(int64_t), N * sizeof(float), N * sizeof(float), s.spec * sizeof(float2),
+                                   s.spec * sizeof(float2), s.spec * sizeof(float2), s.tframes * sizeof(float), (size_t)F * b->ld * sizeof(float),
+                                   s.env_noise * sizeof(float), (N / 4 + n) * sizeof(double), n * sizeof(float), n * sizeof(float),
+                                   n * sizeof(int32_t), s.slots * sizeof(int32_t), s.frame_skip ? (size_t)F : 0};
+    for (int i = 0; i < 16; ++i) { ctx->dbg_ptr[i] = views[i]; ctx->dbg_bytes[i] = view_bytes[i]; }
 
     // mask-smoothing taps for this call's sigma; device copy cached on the handle (steady state:
     // no host work, no synchronisation)
@@ -1448,311 +1626,134 @@ int goofer_synth_batch(goofer_ctx *ctx, const goofer_batch *b, void *stream)
         for (double tv : mtaps) acc += tv * 1.0;
         ctx->mask_taps_sum = acc;
     }
-    const double *d_mtaps = ctx->mask_taps;
-    const int mrad = ctx->mask_taps_radius;
 
-    hipEvent_t *pev = nullptr;
-    if (ctx->prof_on && ctx->prof_steps < ctx->prof_cap) pev = ctx->prof_ev + (size_t)ctx->prof_steps * (PROF_STAGES + 1);
-    int stage = 0;
-    // option "prof_only" = s: only the events stage s needs are recorded (bench.py's timed steps carry the dominant kernel's two
-    // events; the twenty records of the full breakdown cost 0.06 ms of a 2.3 ms step).  The two kernels launched beside the pulse
-    // chain on the caller's stream (stages 6 / 7 of the stem path, 9 / 12 of the other) are bracketed by the prof_main2 pair.
-    const int only = ctx->prof_only;
-    const bool want_q = only < 0 || only == 6 || only == 7 || only == 9 || only == 12;
-#define MARK_Q(q)                                                    \
-    do {                                                             \
-        if (pev && want_q) HIP_TRY(ctx, hipEventRecord(ctx->prof_main2[(size_t)ctx->prof_steps * 2 + (q)], st)); \
-    } while (0)
-#define MARK()                                                       \
-    do {                                                             \
-        if (pev && (only < 0 || stage == only || stage == only + 1 || (stage == 5 && (only == 6 || only == 9)))) \
-            HIP_TRY(ctx, hipEventRecord(pev[stage], st));           \
-        ++stage;                                                     \
-    } while (0)
-
-    // the fused overlap-add rings index by position mod n_fft with a mask: power-of-two transforms only (768 / 1536 take the
-    // separate irFFT + gather kernels)
-    const bool ola_one = ctx->ola_fused && (p.hop % 2 == 0) && (p.n_fft & (p.n_fft - 1)) == 0 && p.bl_L == 0;   // (64 .. 256: Bluestein plans)
-    unsigned fb = (unsigned)((F + 255) / 256);
-    // goofer_render_batch: the assembly recorded ev_f0 right after the f0 / mask kernel.  The pulse chain (f0 scaling,
-    // sequential walk, placement) then runs on the side stream from that point on, beside the envelope assembly and the
-    // map kernels, instead of starting when this call's first kernel is reached in stream order.
-    // Stem-split walkers (stems.hip): no spectra in HBM.  The legacy kernels stay for the other geometries, for the
-    // volume-jitter / sub-harmonic layers (which edit the stems or the pulse train between the steps) and as the A/B path.
-    const bool stem_path = walkers;                           // (== ctx->stems && ola_one && stems_supported(p) && !sub_on && !jit_vol)
-    if (pev) ctx->prof_stems = stem_path;
-    const bool side_on = ctx->overlap && ola_one && !sub_on;
-    const bool early = side_on && !jit_f0 && ctx->early_req && ctx->early_f0 == b->f0 && ctx->side != nullptr;
-    // f0 * pitch_shift (GOOFER.py:995).  When the caller vouches that every pitch_shift is 1 (the resampler path: the pitch
-    // lives in the curve) and nothing jitters f0 in place, the input array IS the scaled f0 and the pass is skipped.
-    const bool f0_alias = b->unit_pitch_shift && !jit_f0 && !sub_jit;
-    if (f0_alias) {
-        f0s = const_cast<float *>(b->f0);
-        ctx->dbg_ptr[2] = f0s;
-    }
+    stage_clock clk(ctx, st, r);
+    synth_call c{ctx, b, r, s, clk, st, F, N, n};
     // goofer_render_batch ran the f0 / mask kernel on the side stream: the caller's stream reads them from here on
     if (ctx->f0_on_side) {
         HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_f0, 0));
         ctx->f0_on_side = false;
     }
-    // stem path: one launch for all the frame maps
-    const bool maps_fused = stem_path;
-    if (!maps_fused) HIP_TRY(ctx, hipMemsetAsync(note_mag, 0, 2 * (size_t)n * sizeof(float), st));
-    MARK();   // 0: setup
-    if (early) {
+    if (!r.walkers) HIP_TRY(ctx, hipMemsetAsync(s.note_mag, 0, 2 * (size_t)n * sizeof(float), st));
+    if ((rc = clk.at(0))) return rc;                          // 0: setup
+    // goofer_render_batch: the assembly recorded ev_f0 right after the f0 / mask kernel.  The pulse chain (f0 scaling,
+    // sequential walk, placement) then runs on the side stream from that point on, beside the envelope assembly and the
+    // map kernels, instead of starting when this call's first kernel is reached in stream order.
+    if (r.early) {
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->side, ctx->ev_entry, 0));
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->side, ctx->ev_f0, 0));
-        if (!f0_alias) {
+        if (!r.f0_alias) {
             hipLaunchKernelGGL(k_scale_f0, dim3((unsigned)((N + 1023) / 1024)), dim3(256), 0, ctx->side, b->f0, b->sample_off, n, N,
-                               b->params, f0s);
+                               b->params, s.f0s);
             LAUNCH_CHECK(ctx);
         }
         HIP_TRY(ctx, hipEventRecord(ctx->ev_f0s, ctx->side));
     }
-    if (!maps_fused && (rc = launch_frame_note(ctx, b->frame_off, n, F, frame_note, st))) return rc;
-    if (!early && !f0_alias) {
+    if (!r.walkers && (rc = launch_frame_note(ctx, b->frame_off, n, F, s.frame_note, st))) return rc;
+    if (!r.early && !r.f0_alias) {
         hipLaunchKernelGGL(k_scale_f0, dim3((unsigned)((N + 1023) / 1024)), dim3(256), 0, st, b->f0, b->sample_off, n, N, b->params,
-                           f0s);                                     // (the pulse walk divides by sr itself)
+                           s.f0s);                                   // (the pulse walk divides by sr itself)
         LAUNCH_CHECK(ctx);
     }
-    // per-frame (f0, mask) picks ride on the map kernel when the scaled f0 is final at this point of the caller's stream:
-    // nothing jitters it in place later, and it is not being produced on the side stream
-    const bool picks_on = !jit_f0 && !sub_jit && !(early && !f0_alias);
-    ctx->frame_picks = picks_on ? picks : nullptr;
-    if (maps_fused) {
+    ctx->frame_picks = r.picks_on ? s.picks : nullptr;
+    if (r.walkers) {   // the stem walkers' frame maps in one launch
         const int64_t threads = std::max<int64_t>(F, 2 * (int64_t)n);
-        hipLaunchKernelGGL(k_frame_maps, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, b->frame_off, b->env_off, n, F, frame_note,
-                           row_src, b->sample_off, (const float *)f0s, b->mask, p.hop, picks_on ? picks : (float2 *)nullptr, note_steps, note_mag);
+        hipLaunchKernelGGL(k_frame_maps, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, b->frame_off, b->env_off, n, F, s.frame_note,
+                           s.row_src, b->sample_off, (const float *)s.f0s, b->mask, p.hop, r.picks_on ? s.picks : (float2 *)nullptr, s.note_steps,
+                           s.note_mag);
     } else {
-        hipLaunchKernelGGL(k_row_src, dim3(fb), dim3(256), 0, st, b->frame_off, b->env_off, frame_note, F, row_src, b->sample_off,
-                           (const float *)f0s, b->mask, p.hop, picks_on ? picks : (float2 *)nullptr);
+        hipLaunchKernelGGL(k_row_src, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, st, b->frame_off, b->env_off, s.frame_note, F, s.row_src,
+                           b->sample_off, (const float *)s.f0s, b->mask, p.hop, r.picks_on ? s.picks : (float2 *)nullptr);
     }
     LAUNCH_CHECK(ctx);
-    if (jit_f0 || jit_vol) {
-        hipLaunchKernelGGL(k_note_flags, dim3((n + 255) / 256), dim3(256), 0, st, b->params, n, on_f0, on_vol);
+    if (r.jit_f0 || r.jit_vol) {
+        hipLaunchKernelGGL(k_note_flags, dim3((n + 255) / 256), dim3(256), 0, st, b->params, n, s.on_f0, s.on_vol);
         LAUNCH_CHECK(ctx);
-        HIP_TRY(ctx, hipMemsetAsync(jit_max, 0, 3 * (size_t)n * sizeof(unsigned long long), st));
+        HIP_TRY(ctx, hipMemsetAsync(s.jit_max, 0, 3 * (size_t)n * sizeof(unsigned long long), st));
     }
-    if (jit_f0) {   // 'sh': f0 *= 1 + (jitter - 1) * mask, after pitch_shift and before the pulse train (GOOFER.py:1069-1071)
-        const double *d_t; int r;
-        if ((rc = upload_jitter_taps(ctx, (double)b->f0_jitter_sigma, 0, &d_t, &r, st))) return rc;
-        if ((rc = launch_gauss_samples<double>(ctx, b->noise_f0, b->sample_off, n, N, d_t, r, on_f0, jit_a, st))) return rc;
-        if ((rc = launch_note_absmax(ctx, jit_a, b->sample_off, n, N, on_f0, jit_max, st))) return rc;
-        if ((rc = launch_f0_jitter(ctx, f0s, f0d, b->mask, jit_a, jit_max, b->sample_off, n, N, b->params, 0, st))) return rc;
+    if (r.jit_f0) {   // 'sh': f0 *= 1 + (jitter - 1) * mask, after pitch_shift and before the pulse train (GOOFER.py:1069-1071)
+        const double *d_t; int rt;
+        if ((rc = upload_jitter_taps(ctx, (double)b->f0_jitter_sigma, 0, &d_t, &rt, st))) return rc;
+        if ((rc = launch_gauss_samples<double>(ctx, b->noise_f0, b->sample_off, n, N, d_t, rt, s.on_f0, s.jit_a, st))) return rc;
+        if ((rc = launch_note_absmax(ctx, s.jit_a, b->sample_off, n, N, s.on_f0, s.jit_max, st))) return rc;
+        if ((rc = launch_f0_jitter(ctx, s.f0s, s.f0d, b->mask, s.jit_a, s.jit_max, b->sample_off, n, N, b->params, 0, st))) return rc;
     }
-    // aperiodic half of the stem-split path: smoothed mask knots, then the two noise stems straight to samples.  Needs the
-    // final scaled f0 (frame picks) and nothing of the pulse chain.
-    auto stems_aperiodic = [&]() -> int {
-        int r2;
-        if (!picks_on && (r2 = launch_frame_picks(ctx, b->frame_off, frame_note, F, b->sample_off, f0s, b->mask, picks, st))) return r2;
-        if ((r2 = launch_mask_short(ctx, b->mask, b->sample_off, n, N, d_mtaps, mrad, ctx->mask_taps_sum, short_s, st))) return r2;
-        if (side_on) MARK_Q(0);
-        if (!maps_fused && (r2 = launch_note_steps(ctx, b->sample_off, n, note_steps, st))) return r2;
-        if ((r2 = launch_noise_stems(ctx, b->env_noise ? b->env_noise : b->env, ld, row_src, b->phi, F, frame_note, b->frame_off,
-                                     b->sample_off, picks, b->params, b->seed, b->env_noise != nullptr, short_s, note_steps, b->uv,
-                                     b->bre, hopz, st)))
-            return r2;
-        if (side_on) MARK_Q(1);
-        return GOOFER_OK;
-    };
     // The pulse walk is one latency-bound wave per SIMD: it goes to a side stream FIRST (so its workgroups are resident
-    // from the start), and the aperiodic branch — noise spectra, mask smoothing, which depend only on the maps and
-    // the scaled f0 — fills the rest of the machine from the caller's stream meanwhile.
-    hipEvent_t *sev = nullptr;
+    // from the start), and the aperiodic branch — noise, mask smoothing, which depend only on the maps and the scaled f0 —
+    // fills the rest of the machine from the caller's stream meanwhile.
     hipStream_t pst = st;                                     // stream of the pulse chain
-    if (side_on) {
-        int rc2 = ensure_side_stream(ctx);
-        if (rc2) return rc2;
-        if (pev && (only < 0 || (only >= 3 && only <= 5))) sev = ctx->prof_side + (size_t)ctx->prof_steps * 4;
-        if (stem_path && !ctx->warp_done) HIP_TRY(ctx, hipEventRecord(ctx->ev_maps, st));   // the frame maps and everything before them on this stream (for k_warp_bins)
-        if (!early) {
+    if (r.side_on) {
+        if ((rc = ensure_side_stream(ctx))) return rc;
+        if (r.walkers && !ctx->warp_done) HIP_TRY(ctx, hipEventRecord(ctx->ev_maps, st));   // the frame maps and everything before them on this stream (for k_warp_bins)
+        if (!r.early) {
             HIP_TRY(ctx, hipEventRecord(ctx->ev_fork, st));
             HIP_TRY(ctx, hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
         }
         pst = ctx->side;
-        ctx->prof_side_used = true;
-    } else if (pev) {
-        ctx->prof_side_used = false;
     }
-    MARK();   // 1: noise envelope = sigma-1.75 blur of the un-warped rows (GOOFER.py:993)
-    // (folded into k_noise_spectra / k_harm_shape: the standalone envelope kernels remain as C-ABI entry points)
-    MARK();   // 2: harmonic envelope = formant-anchored + uniform warp
-
-    MARK();   // 3..5: pulse train
-    if (sev) HIP_TRY(ctx, hipEventRecord(sev[0], pst));
-    MARK();
-    if (sev) HIP_TRY(ctx, hipEventRecord(sev[1], pst));
-    if ((rc = launch_pulse_onsets(ctx, f0s, 1.0f, b->sample_off, n, (onset_t *)onsets, onset_idx, onset_cnt, ovf, N, pulse_tiles, pst))) return rc;
-    MARK();
-    if (sev) HIP_TRY(ctx, hipEventRecord(sev[2], pst));
-    if ((rc = launch_pulse_place(ctx, (onset_t *)onsets, onset_cnt, b->sample_off, n, N, pulse, pulse_tiles, pst))) return rc;
-    // Harmonic envelope rows for the harmonic walker: formant-anchored + uniform warp, one wave per row (GOOFER.py:1004-1017),
-    // behind the pulse placement on its stream (the caller's stream carries the mask smoothing and the noise walker meanwhile).
-    // Not inside the walker: the crossing-anchor path is several times slower than the sorted one, and a walker wave holds
-    // ~95 frames of ONE note, so the slow notes would set the kernel's time.
-    const bool warp_ready = stem_path && ctx->warp_done;               // goofer_render_batch: the assembly already wrote the warped rows
-    if (stem_path && side_on && !warp_ready) {
-        HIP_TRY(ctx, hipStreamWaitEvent(pst, ctx->ev_maps, 0));   // frame_note / row_src come from the caller's stream
-        if ((rc = launch_warp_bins(ctx, b->env, env_h, F, p.n_bins, ld, b->formants, nullptr, b->params, frame_note, row_src, 1.0, pst)))
-            return rc;
-    }
-    if (side_on) {
-        if (sev) HIP_TRY(ctx, hipEventRecord(sev[3], pst));
+    // 1: noise envelope = sigma-1.75 blur of the un-warped rows (GOOFER.py:993), 2: harmonic envelope = formant-anchored +
+    // uniform warp (folded into the shaping kernels / walkers: the standalone envelope kernels remain as C-ABI entry points)
+    if ((rc = clk.at(3))) return rc;                          // 3..5: pulse train
+    if ((rc = clk.pulse(0, pst))) return rc;
+    if ((rc = clk.at(4))) return rc;
+    if ((rc = clk.pulse(1, pst))) return rc;
+    if ((rc = launch_pulse_onsets(ctx, s.f0s, 1.0f, b->sample_off, n, s.onsets, s.onset_idx, s.onset_cnt, ctx->ovf_flag, N, s.pulse_tiles, pst)))
+        return rc;
+    if ((rc = clk.at(5))) return rc;
+    if ((rc = clk.pulse(2, pst))) return rc;
+    if ((rc = launch_pulse_place(ctx, s.onsets, s.onset_cnt, b->sample_off, n, N, s.pulse, s.pulse_tiles, pst))) return rc;
+    if (r.side_on) {
+        // the warp behind the pulse placement on its stream (the caller's stream carries the mask smoothing and the noise walker)
+        if (r.walkers && !ctx->warp_done) {
+            HIP_TRY(ctx, hipStreamWaitEvent(pst, ctx->ev_maps, 0));   // frame_note / row_src come from the caller's stream
+            if ((rc = c.warp(pst))) return rc;
+        }
+        if ((rc = clk.pulse(3, pst))) return rc;
         HIP_TRY(ctx, hipEventRecord(ctx->ev_join, pst));
         // meanwhile, on the caller's stream
-        if (early && !f0_alias) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_f0s, 0));   // the scaled f0 comes from the side stream
-        if (stem_path) {
-            if ((rc = stems_aperiodic())) return rc;
+        if (r.early && !r.f0_alias) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_f0s, 0));   // the scaled f0 comes from the side stream
+        if (r.walkers) {
+            if ((rc = c.frame_picks()) || (rc = c.mask_short()) || (rc = clk.beside(0)) || (rc = c.noise_walker()) || (rc = clk.beside(1)))
+                return rc;
         } else {
             // (the skip bits need the smoothed mask: it goes first then)
-            if (skip_frames) {
-                if ((rc = launch_mask_short(ctx, b->mask, b->sample_off, n, N, d_mtaps, mrad, ctx->mask_taps_sum, short_s, st))) return rc;
-                if ((rc = launch_frame_skip(ctx, short_s, N / 4 + n, b->sample_off, b->frame_off, frame_note, n, F, knot_eq, hop_flat, frame_skip, st))) return rc;
+            if (r.skip_frames) {
+                if ((rc = c.mask_short())) return rc;
+                if ((rc = launch_frame_skip(ctx, s.short_s, N / 4 + n, b->sample_off, b->frame_off, s.frame_note, n, F, s.knot_eq, s.hop_flat,
+                                            s.frame_skip, st)))
+                    return rc;
             }
-            if ((rc = launch_noise_spectra(ctx, S_uv, S_br, ldc, F, frame_note, b->frame_off, b->sample_off, f0s, b->mask,
-                                           b->env_noise ? b->env_noise : b->env, b->phi, ld, b->params, b->seed, row_src,
-                                           b->env_noise != nullptr, frame_skip, st)))
-                return rc;
-            MARK_Q(0);
-            if (!skip_frames && (rc = launch_mask_short(ctx, b->mask, b->sample_off, n, N, d_mtaps, mrad, ctx->mask_taps_sum, short_s, st))) return rc;
-            MARK_Q(1);
+            if ((rc = c.noise_spectra()) || (rc = clk.beside(0))) return rc;
+            if (!r.skip_frames && (rc = c.mask_short())) return rc;
+            if ((rc = clk.beside(1))) return rc;
         }
         HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_join, 0));
     }
-    if (sub_on) {   // 'sg': extra LF pulse layer at f0 * ratio with vibrato, added to the pulse train (GOOFER.py:1076-1097)
-        hipLaunchKernelGGL(k_note_sub_flags, dim3((n + 255) / 256), dim3(256), 0, st, b->params, n, on_sub, on_subj);
+    if (r.sub_on) {   // 'sg': extra LF pulse layer at f0 * ratio with vibrato, added to the pulse train (GOOFER.py:1076-1097)
+        hipLaunchKernelGGL(k_note_sub_flags, dim3((n + 255) / 256), dim3(256), 0, st, b->params, n, s.on_sub, s.on_subj);
         LAUNCH_CHECK(ctx);
-        HIP_TRY(ctx, hipMemsetAsync(sub_max, 0, (size_t)n * sizeof(unsigned long long), st));
-        if (sub_jit) {   // subharm_f0_jitter: f0 (the array itself, as in the reference) *= 1 + (jitter - 1) * mask   :1078-1080
-            const double *d_t; int r;
-            if ((rc = upload_jitter_taps(ctx, (double)b->f0_jitter_sigma, 0, &d_t, &r, st))) return rc;
-            HIP_TRY(ctx, hipMemsetAsync(jit_max, 0, (size_t)n * sizeof(unsigned long long), st));
-            if ((rc = launch_gauss_samples<double>(ctx, b->noise_subharm, b->sample_off, n, N, d_t, r, on_subj, jit_a, st))) return rc;
-            if ((rc = launch_note_absmax(ctx, jit_a, b->sample_off, n, N, on_subj, jit_max, st))) return rc;
-            if ((rc = launch_f0_jitter(ctx, f0s, f0d, b->mask, jit_a, jit_max, b->sample_off, n, N, b->params, 1, st))) return rc;
+        HIP_TRY(ctx, hipMemsetAsync(s.sub_max, 0, (size_t)n * sizeof(unsigned long long), st));
+        if (r.sub_jit) {   // subharm_f0_jitter: f0 (the array itself, as in the reference) *= 1 + (jitter - 1) * mask   :1078-1080
+            const double *d_t; int rt;
+            if ((rc = upload_jitter_taps(ctx, (double)b->f0_jitter_sigma, 0, &d_t, &rt, st))) return rc;
+            HIP_TRY(ctx, hipMemsetAsync(s.jit_max, 0, (size_t)n * sizeof(unsigned long long), st));
+            if ((rc = launch_gauss_samples<double>(ctx, b->noise_subharm, b->sample_off, n, N, d_t, rt, s.on_subj, s.jit_a, st))) return rc;
+            if ((rc = launch_note_absmax(ctx, s.jit_a, b->sample_off, n, N, s.on_subj, s.jit_max, st))) return rc;
+            if ((rc = launch_f0_jitter(ctx, s.f0s, s.f0d, b->mask, s.jit_a, s.jit_max, b->sample_off, n, N, b->params, 1, st))) return rc;
         }
         double ratios[16];
         ratios[0] = b->subharm_ratio;
         for (int q = 0; q < 15; ++q) ratios[q + 1] = b->subharm_more[q];
         int n_ratios = 1;
         while (n_ratios < 16 && ratios[n_ratios] > 0.0) ++n_ratios;
-        if ((rc = launch_subharm(ctx, f0s, f0d, b->mask, b->sample_off, n, N, b->params, ratios, n_ratios, b->subharm_vibrato,
-                                 b->subharm_vib_rate, b->subharm_vib_depth, b->subharm_vib_delay, sub_fm, inc, (onset_t *)onsets,
-                                 onset_idx, onset_cnt, ovf, on_sub, sub_buf, sub_max, pulse, st)))
+        if ((rc = launch_subharm(ctx, s.f0s, s.f0d, b->mask, b->sample_off, n, N, b->params, ratios, n_ratios, b->subharm_vibrato,
+                                 b->subharm_vib_rate, b->subharm_vib_depth, b->subharm_vib_delay, s.sub_fm, s.inc, s.onsets,
+                                 s.onset_idx, s.onset_cnt, ctx->ovf_flag, s.on_sub, s.sub_buf, s.sub_max, s.pulse, st)))
             return rc;
     }
-    if (stem_path) {
-        MARK();   // 6: mask_short, 7: noise_stems (here when nothing runs beside the pulse chain)
-        if (!side_on && (rc = launch_mask_short(ctx, b->mask, b->sample_off, n, N, d_mtaps, mrad, ctx->mask_taps_sum, short_s, st))) return rc;
-        MARK();
-        if (!side_on) {
-            if (!picks_on && (rc = launch_frame_picks(ctx, b->frame_off, frame_note, F, b->sample_off, f0s, b->mask, picks, st))) return rc;
-            if (!maps_fused && (rc = launch_note_steps(ctx, b->sample_off, n, note_steps, st))) return rc;
-            if ((rc = launch_noise_stems(ctx, b->env_noise ? b->env_noise : b->env, ld, row_src, b->phi, F, frame_note, b->frame_off,
-                                         b->sample_off, picks, b->params, b->seed, b->env_noise != nullptr, short_s, note_steps, b->uv,
-                                         b->bre, hopz, st)))
-                return rc;
-            if (!ctx->warp_done &&
-                (rc = launch_warp_bins(ctx, b->env, env_h, F, p.n_bins, ld, b->formants, nullptr, b->params, frame_note, row_src, 1.0, st)))
-                return rc;
-        }
-        MARK();   // 8
-        MARK();   // 9: harm_stem = rFFT + shaping + irFFT + overlap-add of the harmonic stem
-        if ((rc = launch_harm_stem(ctx, pulse, ctx->warp_done ? ctx->warp_rows : env_h, ctx->warp_done ? b->env : nullptr, b->formants != nullptr, ld,
-                                   ctx->warp_done ? row_src : nullptr, F, frame_note,
-                                   b->frame_off, b->sample_off, picks, b->params, b->harm, note_mag, st)))
-            return rc;
-        MARK();   // 10..12
-        MARK();
-        MARK();
-        MARK();   // 13: harm / max|S|, peak, gain, reconstruct, mix
-        if ((rc = launch_note_finish(ctx, b->harm, b->uv, b->bre, b->rec, b->mix, b->sample_off, n, b->params, note_mag, note_peak,
-                                     !(b->mix_only && (b->mix || b->rec)), hopz, b->frame_off, st)))
-            return rc;
-        MARK();   // 14..17 unused
-        MARK();
-        MARK();
-        MARK();
-        MARK();   // end
-        if (pev) ctx->prof_steps++;
-        ctx->frame_picks = nullptr;
-        return GOOFER_OK;
-    }
-    // spectra -> windowed time frames of the three stems
-    {
-        MARK();   // 6: framewise rFFT of the pulse train
-        if ((rc = launch_rfft_frames_mapped(ctx, pulse, b->sample_off, b->frame_off, frame_note, F, S_h, ldc, st))) return rc;
-        MARK();   // 7
-        if ((rc = launch_harm_shape(ctx, S_h, ldc, F, frame_note, b->frame_off, b->sample_off, f0s, b->mask, b->env, ld, b->params,
-                                    note_mag, row_src, b->formants, b->no_warp != 0, st)))
-            return rc;
-        MARK();   // 8
-        if (!ola_one && (rc = launch_irfft_frames(ctx, S_h, ldc, F, frames, st))) return rc;
-        MARK();   // 9: aperiodic spectra
-        if (!side_on && (rc = launch_noise_spectra(ctx, S_uv, S_br, ldc, F, frame_note, b->frame_off, b->sample_off, f0s, b->mask,
-                                                   b->env_noise ? b->env_noise : b->env, b->phi, ld, b->params, b->seed, row_src,
-                                                   b->env_noise != nullptr, nullptr, st)))
-            return rc;
-        MARK();   // 10, 11
-        if (!ola_one && (rc = launch_irfft_frames(ctx, S_br, ldc, F, frames_b, st))) return rc;
-        MARK();
-        if (!ola_one && (rc = launch_irfft_frames(ctx, S_uv, ldc, F, frames_u, st))) return rc;
-    }
-    MARK();   // 12: decimated + smoothed voicing mask
-    if (!side_on && (rc = launch_mask_short(ctx, b->mask, b->sample_off, n, N, d_mtaps, mrad, ctx->mask_taps_sum, short_s, st))) return rc;
-    MARK();   // 13: (irFFT of the three stems +) overlap-add + gains + per-note peak, one pass
-    if (ola_split) {
-        if ((rc = launch_irfft_ola1(ctx, S_h, S_uv, S_br, ldc, F, frame_note, b->frame_off, b->sample_off, n, short_s, note_steps,
-                                    b->params, b->harm, b->uv, b->bre, frame_skip, st)))
-            return rc;
-        MARK();   // 14
-        if ((rc = launch_note_finish(ctx, b->harm, b->uv, b->bre, b->rec, b->mix, b->sample_off, n, b->params, note_mag, note_peak,
-                                     !(b->mix_only && (b->mix || b->rec)), nullptr, nullptr, st)))
-            return rc;
-        MARK();   // 15..17 unused
-        MARK();
-        MARK();
-        MARK();   // end
-        if (pev) ctx->prof_steps++;
-        ctx->frame_picks = nullptr;
-        return GOOFER_OK;
-    }
-    if (ola_one) {
-        if ((rc = launch_irfft_ola3(ctx, S_h, S_uv, S_br, ldc, F, frame_note, b->frame_off, b->sample_off, n, note_mag, short_s,
-                                    note_steps, b->params, b->harm, b->uv, b->bre, note_peak, st)))
-            return rc;
-    } else if ((rc = launch_ola3_gains(ctx, frames, frames_u, frames_b, note_mag, short_s, b->sample_off, b->frame_off, n, N,
-                                       b->params, note_steps, b->harm, b->uv, b->bre, note_peak, st)))
-        return rc;
-    if (jit_vol) {  // 'sr': volume jitter on harm / breath, then the peak is taken again (GOOFER.py:1185-1193)
-        const double *d_t = nullptr, *d_t20; int r = 0, r20;
-        if (!vol_vib && (rc = upload_jitter_taps(ctx, (double)b->vol_jitter_sigma, 1, &d_t, &r, st))) return rc;
-        if ((rc = upload_jitter_taps(ctx, 20.0, 2, &d_t20, &r20, st))) return rc;
-        if (!vol_vib) {
-            if ((rc = launch_gauss_samples<double>(ctx, b->noise_vol_h, b->sample_off, n, N, d_t, r, on_vol, jit_a, st))) return rc;
-            if ((rc = launch_gauss_samples<double>(ctx, b->noise_vol_b, b->sample_off, n, N, d_t, r, on_vol, jit_b, st))) return rc;
-            if ((rc = launch_note_absmax(ctx, jit_a, b->sample_off, n, N, on_vol, jit_max + n, st))) return rc;
-            if ((rc = launch_note_absmax(ctx, jit_b, b->sample_off, n, N, on_vol, jit_max + 2 * (size_t)n, st))) return rc;
-        }
-        if ((rc = launch_gauss_samples<float>(ctx, b->mask, b->sample_off, n, N, d_t20, r20, on_vol, jit_c, st))) return rc;
-        if ((rc = launch_volume_jitter(ctx, b->harm, b->bre, jit_a, jit_b, jit_c, jit_max + n, jit_max + 2 * (size_t)n, b->sample_off, n,
-                                       N, b->params, vol_vib ? 1 : 0, (double)b->vol_jitter_speed, st)))
-            return rc;
-        HIP_TRY(ctx, hipMemsetAsync(note_peak, 0, (size_t)n * sizeof(float), st));
-        if ((rc = launch_stem_peak(ctx, b->harm, b->uv, b->bre, b->sample_off, n, N, note_peak, st))) return rc;
-    }
-    MARK();   // 14: gain, reconstruct, mix
-    if ((rc = launch_apply_gain(ctx, b->harm, b->uv, b->bre, b->rec, b->mix, b->sample_off, n, N, b->params, note_peak,
-                                !(b->mix_only && (b->mix || b->rec)), st)))
-        return rc;
-    MARK();   // 15..17 unused
-    MARK();
-    MARK();
-    MARK();   // end
-#undef MARK
-    if (pev) ctx->prof_steps++;
+    rc = r.walkers ? c.walker_tail() : c.spectra_tail();
     ctx->frame_picks = nullptr;
-    return GOOFER_OK;
+    return rc;
 }
 
 // SillySampler.resample end to end for one batch (SillySampler.py:698-1151 up to the post chain): assembly and synthesis as
@@ -1774,11 +1775,9 @@ int goofer_render_batch(goofer_ctx *ctx, const goofer_assembly *asmb, const goof
     // hand, so it writes the warped copy too (k_env_rows<true>) — one pass instead of a separate read + write of the matrix.
     ctx->warp_out = nullptr;
     ctx->warp_done = false;
-    if (ctx->stems && ctx->ola_fused && ctx->overlap && stems_supported(ctx->plan) && asmb->env_out == b->env &&
-        asmb->n_notes == b->n_notes && asmb->total_out_rows == b->total_env_rows && asmb->ld == b->ld && !asmb->any_fry &&
-        // ... and the synthesis will take the stem path (the 'sg' layer and the volume jitter run the legacy kernels, which warp
-        // in k_harm_shape: a warped copy written here would never be read)
-        !(b->subharm_ratio > 0.0) && !(b->volume_vibrato != 0 || (b->noise_vol_h != nullptr && b->noise_vol_b != nullptr))) {
+    // (the other routes warp in k_harm_shape: a warped copy written here would never be read)
+    if (synth_route_of(ctx, b).walkers && ctx->overlap && asmb->env_out == b->env && asmb->n_notes == b->n_notes &&
+        asmb->total_out_rows == b->total_env_rows && asmb->ld == b->ld && !asmb->any_fry) {
         const size_t need = (size_t)b->total_env_rows * b->ld * sizeof(float);
         if (need > ctx->warp_rows_bytes) {
             HIP_TRY(ctx, hipDeviceSynchronize());

@@ -118,7 +118,8 @@ class Context:
 
     def debug_fetch(self, name: str) -> np.ndarray:
         """Intermediate of the last synth_batch (onset_cnt / onset_idx: also of the last pulse_train) as a flat host array
-        (tests / debugging only).  onset_idx: note k's onset samples start at sample_off[k] // 2 + 16 k."""
+        (tests / debugging only).  onset_idx: every onset slot; note k's onset samples start at sample_off[k] // 2 + 16 k —
+        after a batch with the 'sg' layer at sample_off[k] + 16 k, the sub-harmonic onsets of its last ratio."""
         which, dt = self._DBG[name]
         size = self.lib.goofer_debug_fetch(self.h, which, None, 0)
         if size < 0:

@@ -400,7 +400,8 @@ int goofer_host_parse_floats(const char *text, const int64_t *text_off, int n, i
 int64_t goofer_host_pack(const void *const *src, const int64_t *nbytes, int64_t count, void *dst, int64_t capacity, int threads);
 
 /* Synchronise the device and report errors the asynchronous batch calls detect on the device (today: a note with more
- * pulse onsets than its n / 2 + 16 onset slots, GOOFER.py:493 with f0 above sr / 2).  0, or GOOFER_EINVAL + goofer_last_error. */
+ * pulse onsets than its n / 2 + 16 onset slots, GOOFER.py:493 with f0 above sr / 2; a batch with the 'sg' layer leaves its
+ * sub-harmonic onsets in n + 16 slots per note, one per sample at most).  0, or GOOFER_EINVAL + goofer_last_error. */
 int goofer_check(goofer_ctx *ctx);
 
 /* Cumulative per-handle counters kept on the device (the call synchronises): "pulse_scanned_notes" = notes whose pulse onsets
