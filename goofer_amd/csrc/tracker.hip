@@ -1,0 +1,594 @@
+// The f0 and formant half of the cold-cache analysis (gfx950), for a ragged batch of fp64 signals at one sample rate.
+//
+// Pitch, Boersma (1993) autocorrelation method with the settings the reference hands to Praat (floor 75 Hz, ceiling 950 Hz,
+// time step hop / sr, 15 candidates, silence 0.03, voicing 0.45, octave 0.01, octave jump 0.35, voiced/unvoiced 0.14):
+//   k_pitch_stats    per signal: mean and peak of |y - mean| (the unvoiced candidate needs the whole signal's peak)
+//   k_pitch_frames   per frame: mean removed, Hann window of 3 / floor, autocorrelation over the lag range divided by the
+//                    window's own, parabolic peaks, octave cost, unvoiced strength; up to 15 candidates
+//   k_pitch_viterbi  per signal, one wave: the best candidate path under octave-jump and voicing costs; unvoiced frames 0
+// Formants, Burg's method as Praat's to_formant_burg defaults describe it (5 formants, ceiling 5500 Hz, 50 ms Gaussian):
+//   k_resample11k    windowed-sinc interpolation to 11 kHz, one output sample per thread
+//   k_formant_frames per frame, one wave: pre-emphasis from 50 Hz, Gaussian window, Burg order 10 in fp64, roots of the
+//                    predictor by Aberth's method plus Newton polishing, roots at 50 < f < 5450 Hz sorted into F1..F5
+// Every frame and signal is computed from its own samples in a fixed order, so a signal's tracks do not depend on the batch.
+// tests/tracker_ref.py restates the same algorithm in numpy.
+#include <math.h>
+
+#include <vector>
+
+#include "common.h"
+
+namespace {
+
+constexpr int TR_FLOOR = 75, TR_PERIODS = 3, TR_MAX_CAND = 15;
+constexpr double TR_CEILING = 950.0, TR_SILENCE = 0.03, TR_VOICING = 0.45;
+constexpr double TR_OCTAVE = 0.01, TR_OCTAVE_JUMP = 0.35, TR_VUV = 0.14;
+constexpr double TR_SILENT_PEAK = 1e-10;               // a signal whose peak deviation from its mean is below this is silence
+constexpr int TR_SR_MIN = 8000, TR_SR_MAX = 96000;     // the pitch frame (sr / 25 doubles) and its lags stay inside 48 KB of LDS
+
+constexpr int FM_SR = 11000, FM_WIN = 550, FM_ORDER = 10, FM_N = 5, FM_PER_LANE = (FM_WIN + WAVE - 1) / WAVE;
+constexpr double FM_PRE_HZ = 50.0, FM_SINC_ZEROS = 20.0;
+constexpr int FM_ABERTH_ITERS = 100;
+
+constexpr int TR_THREADS = 256;
+
+struct pitch_geom {
+    int W, min_lag, max_lag, lo, hi;                      // r[] is kept for lags lo..hi
+    double ceiling;
+};
+
+pitch_geom pitch_geometry(int sr)
+{
+    pitch_geom g;
+    g.W = TR_PERIODS * sr / TR_FLOOR;
+    g.ceiling = std::min(TR_CEILING, 0.5 * sr);
+    g.min_lag = (int)floor(sr / g.ceiling);
+    g.max_lag = (sr + TR_FLOOR - 1) / TR_FLOOR;
+    g.lo = std::max(1, g.min_lag - 1);
+    g.hi = std::min(g.max_lag + 1, g.W - 1);
+    return g;
+}
+
+int64_t pitch_min_length(int sr) { return ((int64_t)TR_PERIODS * sr + TR_FLOOR - 1) / TR_FLOOR; }
+
+int64_t pitch_frames(int64_t n, int sr, int hop)
+{
+    const int64_t d = (int64_t)TR_FLOOR * n - (int64_t)TR_PERIODS * sr;
+    return d < 0 ? 0 : d / ((int64_t)TR_FLOOR * hop) + 1;
+}
+
+int64_t resampled_length(int64_t n, int sr) { return n * FM_SR / sr; }
+
+int64_t formant_frames(int64_t n, int sr, int hop)
+{
+    const int64_t m = resampled_length(n, sr);
+    return m < FM_WIN ? 0 : (m - FM_WIN) * sr / ((int64_t)FM_SR * hop) + 1;
+}
+
+size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// ---- device helpers ----------------------------------------------------------------------------------------------
+__device__ __forceinline__ double wave_sum_d(double v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+__device__ __forceinline__ double wave_max_d(double v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+// fixed-order block reductions over TR_THREADS threads (every thread gets the result); red: 4 doubles of LDS
+__device__ double block_sum_d(double v, double *red)
+{
+    v = wave_sum_d(v);
+    const int wave = threadIdx.x >> 6;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[wave] = v;
+    __syncthreads();
+    return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+__device__ double block_max_d(double v, double *red)
+{
+    v = wave_max_d(v);
+    const int wave = threadIdx.x >> 6;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[wave] = v;
+    __syncthreads();
+    return fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+}
+
+// ---- pitch -------------------------------------------------------------------------------------------------------
+// stats[2 s] = mean of signal s, stats[2 s + 1] = max |y - mean|
+__global__ __launch_bounds__(TR_THREADS) void k_pitch_stats(const double *__restrict__ y, const int64_t *__restrict__ soff,
+                                                            double *__restrict__ stats)
+{
+    __shared__ double red[4];
+    const int s = blockIdx.x;
+    const int64_t a = soff[s], n = soff[s + 1] - a;
+    double acc = 0.0;
+    for (int64_t j = threadIdx.x; j < n; j += TR_THREADS) acc += y[a + j];
+    const double mean = block_sum_d(acc, red) / (double)n;
+    double pk = 0.0;
+    for (int64_t j = threadIdx.x; j < n; j += TR_THREADS) pk = fmax(pk, fabs(y[a + j] - mean));
+    pk = block_max_d(pk, red);
+    if (threadIdx.x == 0) {
+        stats[2 * s] = mean;
+        stats[2 * s + 1] = pk;
+    }
+}
+
+// One frame per workgroup.  LDS: the windowed frame [W], the normalised autocorrelation for lags lo..hi, reductions.
+__global__ __launch_bounds__(TR_THREADS) void k_pitch_frames(const double *__restrict__ y, const int64_t *__restrict__ soff,
+                                                             const int64_t *__restrict__ foff, int n_sig, int sr, int hop,
+                                                             pitch_geom g, const double *__restrict__ win,
+                                                             const double *__restrict__ rw, const double *__restrict__ stats,
+                                                             double *__restrict__ cand_f, double *__restrict__ cand_s,
+                                                             int *__restrict__ cand_n)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    double *xw = reinterpret_cast<double *>(smem);
+    double *r = xw + g.W;                                 // r[t - lo]
+    __shared__ double red[4];
+    __shared__ double kf[TR_MAX_CAND - 1], ks[TR_MAX_CAND - 1];
+    const int64_t f = blockIdx.x;
+    const int s = csr_find(foff, n_sig, f);
+    const int64_t n = soff[s + 1] - soff[s], nf = foff[s + 1] - foff[s], i = f - foff[s];
+    const int W = g.W;
+    const double *x = y + soff[s] + (n - (nf - 1) * hop - W) / 2 + i * hop;
+
+    double acc = 0.0;
+    for (int j = threadIdx.x; j < W; j += TR_THREADS) {
+        const double v = x[j];
+        xw[j] = v;
+        acc += v;
+    }
+    const double mean = block_sum_d(acc, red) / (double)W;
+    double pk = 0.0, e = 0.0;
+    for (int j = threadIdx.x; j < W; j += TR_THREADS) {
+        const double v = xw[j] - mean;
+        pk = fmax(pk, fabs(v));
+        const double u = v * win[j];
+        xw[j] = u;
+        e += u * u;
+    }
+    pk = block_max_d(pk, red);
+    const double r0 = block_sum_d(e, red);               // also orders the xw writes before the lag products
+    const double gp = stats[2 * s + 1];
+    const double ratio = gp > TR_SILENT_PEAK ? pk / gp : 0.0;
+    const double uv = TR_VOICING + fmax(0.0, 2.0 - ratio / (TR_SILENCE / (1.0 + TR_VOICING)));
+    double *cf = cand_f + f * TR_MAX_CAND, *cs = cand_s + f * TR_MAX_CAND;
+    if (!(r0 > 0.0)) {
+        if (threadIdx.x == 0) {
+            cf[0] = 0.0;
+            cs[0] = uv;
+            cand_n[f] = 1;
+        }
+        return;
+    }
+    for (int t = g.lo + threadIdx.x; t <= g.hi; t += TR_THREADS) {
+        double a = 0.0;
+        for (int j = 0; j < W - t; ++j) a += xw[j] * xw[j + t];
+        r[t - g.lo] = a / (r0 * rw[t]);
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    // serial peak scan in lag order; keep the 14 strongest (the earlier lag among equals), in lag order
+    int cnt = 0;
+    const int t0 = max(g.lo + 1, g.min_lag), t1 = min(g.max_lag, g.hi - 1);
+    for (int t = t0; t <= t1; ++t) {
+        const double rm1 = r[t - 1 - g.lo], rc = r[t - g.lo], rp1 = r[t + 1 - g.lo];
+        if (!(rc > 0.5 * TR_VOICING && rc > rm1 && rc >= rp1)) continue;
+        const double dr = 0.5 * (rp1 - rm1), d2r = 2.0 * rc - rm1 - rp1;
+        const double delta = d2r > 0.0 ? dr / d2r : 0.0;
+        double rmax = rc + 0.5 * dr * delta;
+        if (rmax > 1.0) rmax = 1.0 / rmax;
+        const double fr = (double)sr / ((double)t + delta);
+        if (fr < (double)TR_FLOOR || fr > g.ceiling) continue;
+        const double st = rmax - TR_OCTAVE * log2((double)TR_FLOOR / fr);
+        if (cnt < TR_MAX_CAND - 1) {
+            kf[cnt] = fr;
+            ks[cnt] = st;
+            ++cnt;
+            continue;
+        }
+        int w = 0;                                        // the weakest kept, the latest among equals
+        for (int k = 1; k < cnt; ++k)
+            if (ks[k] <= ks[w]) w = k;
+        if (!(st > ks[w])) continue;
+        for (int k = w; k < cnt - 1; ++k) {
+            kf[k] = kf[k + 1];
+            ks[k] = ks[k + 1];
+        }
+        kf[cnt - 1] = fr;
+        ks[cnt - 1] = st;
+    }
+    cf[0] = 0.0;
+    cs[0] = uv;
+    for (int k = 0; k < cnt; ++k) {
+        cf[k + 1] = kf[k];
+        cs[k + 1] = ks[k];
+    }
+    cand_n[f] = cnt + 1;
+}
+
+__device__ __forceinline__ double pitch_transition(double fp, double fc, double tsc)
+{
+    if (fp == 0.0 && fc == 0.0) return 0.0;
+    if (fp == 0.0 || fc == 0.0) return TR_VUV * tsc;
+    return TR_OCTAVE_JUMP * tsc * fabs(log2(fp / fc));
+}
+
+// One wave per signal: lane c holds candidate c of the current frame; back pointers go to global memory.
+__global__ __launch_bounds__(WAVE) void k_pitch_viterbi(const int64_t *__restrict__ foff, const double *__restrict__ cand_f,
+                                                        const double *__restrict__ cand_s, const int *__restrict__ cand_n,
+                                                        double tsc, unsigned char *__restrict__ back, double *__restrict__ f0)
+{
+    __shared__ double pf[TR_MAX_CAND], pd[TR_MAX_CAND];
+    __shared__ int pn;
+    const int s = blockIdx.x, c = threadIdx.x;
+    const int64_t a = foff[s], nf = foff[s + 1] - a;
+    if (nf <= 0) return;
+    if (c < TR_MAX_CAND) {
+        const bool on = c < cand_n[a];
+        pf[c] = on ? cand_f[a * TR_MAX_CAND + c] : 0.0;
+        pd[c] = on ? cand_s[a * TR_MAX_CAND + c] : -INFINITY;
+    }
+    if (c == 0) pn = cand_n[a];
+    wave_lds_sync();
+    for (int64_t i = 1; i < nf; ++i) {
+        const int64_t fr = a + i;
+        const int cn = cand_n[fr];
+        double fc = 0.0, best = -INFINITY;
+        int arg = 0;
+        if (c < cn) {
+            fc = cand_f[fr * TR_MAX_CAND + c];
+            for (int p = 0; p < pn; ++p) {
+                const double v = pd[p] - pitch_transition(pf[p], fc, tsc);
+                if (v > best) {
+                    best = v;
+                    arg = p;
+                }
+            }
+            best += cand_s[fr * TR_MAX_CAND + c];
+            back[fr * TR_MAX_CAND + c] = (unsigned char)arg;
+        }
+        wave_lds_sync();                                  // every lane has read the previous frame
+        if (c < TR_MAX_CAND) {
+            pf[c] = fc;
+            pd[c] = c < cn ? best : -INFINITY;
+        }
+        if (c == 0) pn = cn;
+        wave_lds_sync();
+    }
+    if (c != 0) return;
+    int k = 0;
+    for (int p = 1; p < pn; ++p)
+        if (pd[p] > pd[k]) k = p;
+    for (int64_t i = nf - 1; i >= 0; --i) {
+        const int64_t fr = a + i;
+        f0[fr] = cand_f[fr * TR_MAX_CAND + k];
+        if (i > 0) k = back[fr * TR_MAX_CAND + k];
+    }
+}
+
+// ---- formants ----------------------------------------------------------------------------------------------------
+// out[m] = sum_k y[k] h(k - p), p = m sr / 11000: a Hann-windowed sinc with its cut-off at the lower Nyquist
+__global__ __launch_bounds__(TR_THREADS) void k_resample11k(const double *__restrict__ y, const int64_t *__restrict__ soff,
+                                                            const int64_t *__restrict__ moff, int n_sig, int64_t m_total, int sr,
+                                                            double *__restrict__ out)
+{
+    const int64_t g = (int64_t)blockIdx.x * TR_THREADS + threadIdx.x;
+    if (g >= m_total) return;
+    const int s = csr_find(moff, n_sig, g);
+    const int64_t m = g - moff[s], n = soff[s + 1] - soff[s];
+    const double *x = y + soff[s];
+    const double fc = 0.5 * (double)min(sr, FM_SR) / (double)sr;
+    const double half = FM_SINC_ZEROS * fmax(1.0, (double)sr / (double)FM_SR);
+    const double p = (double)m * (double)sr / (double)FM_SR;
+    const int64_t k0 = max((int64_t)0, (int64_t)ceil(p - half)), k1 = min(n - 1, (int64_t)floor(p + half));
+    double acc = 0.0;
+    for (int64_t k = k0; k <= k1; ++k) {
+        const double d = (double)k - p;
+        const double u = M_PI * (2.0 * fc * d);
+        const double sinc = u == 0.0 ? 1.0 : sin(u) / u;
+        acc += 2.0 * fc * sinc * (0.5 + 0.5 * cos(M_PI * d / half)) * x[k];
+    }
+    out[g] = acc;
+}
+
+struct cplx {
+    double re, im;
+};
+__device__ __forceinline__ cplx cmul(cplx a, cplx b) { return {a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
+__device__ __forceinline__ cplx cdiv(cplx a, cplx b)
+{
+    const double d = b.re * b.re + b.im * b.im;
+    return {(a.re * b.re + a.im * b.im) / d, (a.im * b.re - a.re * b.im) / d};
+}
+
+// p(z) and p'(z) of z^m + a[1] z^(m-1) + ... + a[m]
+__device__ __forceinline__ void poly_eval(const double *a, int m, cplx z, cplx &p, cplx &d)
+{
+    p = {1.0, 0.0};
+    d = {0.0, 0.0};
+    for (int k = 1; k <= m; ++k) {
+        d = cmul(d, z);
+        d.re += p.re;
+        d.im += p.im;
+        p = cmul(p, z);
+        p.re += a[k];
+    }
+}
+
+// One wave per frame.  LDS per frame: the forward / backward prediction errors, the predictor, the roots.
+__global__ __launch_bounds__(WAVE) void k_formant_frames(const double *__restrict__ x11, const int64_t *__restrict__ moff,
+                                                         const int64_t *__restrict__ foff, int n_sig, int sr, int hop,
+                                                         const double *__restrict__ gwin, double *__restrict__ formants)
+{
+    __shared__ double fe[FM_WIN], be[FM_WIN];
+    __shared__ double a[FM_ORDER + 1];
+    __shared__ cplx z[FM_ORDER], w[FM_ORDER];
+    const int lane = threadIdx.x;
+    const int64_t f = blockIdx.x;
+    const int s = csr_find(foff, n_sig, f);
+    const int64_t m = moff[s + 1] - moff[s], nf = foff[s + 1] - foff[s], i = f - foff[s];
+    const int64_t num = (m - FM_WIN) * sr + (2 * i - nf + 1) * (int64_t)hop * FM_SR;
+    int64_t st = (num + sr) / (2 * (int64_t)sr);          // num + sr >= 0 for every frame of the layout
+    st = min(max(st, (int64_t)0), m - FM_WIN);
+    const double *x = x11 + moff[s];
+    const double alpha = exp(-2.0 * M_PI * FM_PRE_HZ / FM_SR);
+
+    double pk = 0.0;
+    for (int j = lane; j < FM_WIN; j += WAVE) {
+        const int64_t q = st + j;
+        const double v = (q > 0 ? x[q] - alpha * x[q - 1] : x[q]) * gwin[j];
+        fe[j] = be[j] = v;
+        pk = fmax(pk, fabs(v));
+    }
+    double *out = formants + f * FM_N;
+    if (wave_max_d(pk) == 0.0) {
+        if (lane < FM_N) out[lane] = 0.0;
+        return;
+    }
+    if (lane == 0) a[0] = 1.0;
+    wave_lds_sync();
+    int order = 0;
+    for (int mo = 1; mo <= FM_ORDER; ++mo) {
+        double nu = 0.0, de = 0.0;
+        double fn[FM_PER_LANE], bn[FM_PER_LANE];
+#pragma unroll
+        for (int q = 0; q < FM_PER_LANE; ++q) {
+            const int j = mo + lane + q * WAVE;
+            if (j < FM_WIN) {
+                const double ff = fe[j], bb = be[j - 1];
+                nu += ff * bb;
+                de += ff * ff + bb * bb;
+            }
+        }
+        nu = wave_sum_d(nu);
+        de = wave_sum_d(de);
+        if (!(de > 0.0)) break;
+        const double k = -2.0 * nu / de;
+#pragma unroll
+        for (int q = 0; q < FM_PER_LANE; ++q) {
+            const int j = mo + lane + q * WAVE;
+            if (j < FM_WIN) {
+                const double ff = fe[j], bb = be[j - 1];
+                fn[q] = ff + k * bb;
+                bn[q] = bb + k * ff;
+            }
+        }
+        wave_lds_sync();                                  // all old values read before any is replaced
+#pragma unroll
+        for (int q = 0; q < FM_PER_LANE; ++q) {
+            const int j = mo + lane + q * WAVE;
+            if (j < FM_WIN) {
+                fe[j] = fn[q];
+                be[j] = bn[q];
+            }
+        }
+        if (lane == 0) {
+            a[mo] = 0.0;
+            for (int l = 0; 2 * l <= mo; ++l) {           // a[l], a[mo - l] <- a[l] + k a[mo - l], a[mo - l] + k a[l]
+                const double lo = a[l], hi = a[mo - l];
+                a[l] = lo + k * hi;
+                if (mo - l != l) a[mo - l] = hi + k * lo;
+            }
+        }
+        wave_lds_sync();
+        order = mo;
+    }
+    if (lane != 0) return;
+
+    // Aberth-Ehrlich: all corrections from the current roots, then all roots move
+    for (int k = 0; k < order; ++k) {
+        const double ang = 2.0 * M_PI * k / order + 0.25;
+        z[k] = {0.9 * cos(ang), 0.9 * sin(ang)};
+    }
+    for (int it = 0; it < FM_ABERTH_ITERS && order > 0; ++it) {
+        for (int k = 0; k < order; ++k) {
+            cplx p, d;
+            poly_eval(a, order, z[k], p, d);
+            const cplx ratio = (d.re != 0.0 || d.im != 0.0) ? cdiv(p, d) : cplx{0.0, 0.0};
+            cplx sum = {0.0, 0.0};
+            for (int j = 0; j < order; ++j) {
+                if (j == k) continue;
+                const cplx q = cdiv({1.0, 0.0}, {z[k].re - z[j].re, z[k].im - z[j].im});
+                sum.re += q.re;
+                sum.im += q.im;
+            }
+            const cplx rs = cmul(ratio, sum);
+            w[k] = cdiv(ratio, {1.0 - rs.re, -rs.im});
+        }
+        bool done = true;
+        for (int k = 0; k < order; ++k) {
+            z[k].re -= w[k].re;
+            z[k].im -= w[k].im;
+            const double wa = hypot(w[k].re, w[k].im), za = fmax(hypot(z[k].re, z[k].im), 1e-300);
+            done &= wa <= 1e-14 * za;
+        }
+        if (done) break;
+    }
+    for (int pass = 0; pass < 2; ++pass)
+        for (int k = 0; k < order; ++k) {
+            cplx p, d;
+            poly_eval(a, order, z[k], p, d);
+            if (d.re != 0.0 || d.im != 0.0) {
+                const cplx c = cdiv(p, d);
+                z[k].re -= c.re;
+                z[k].im -= c.im;
+            }
+        }
+    double fk[FM_N];
+    int nk = 0;
+    for (int k = 0; k < order; ++k) {
+        if (!(z[k].im > 0.0)) continue;
+        const double fr = atan2(z[k].im, z[k].re) * FM_SR / (2.0 * M_PI);
+        if (!(fr > 50.0 && fr < 0.5 * FM_SR - 50.0)) continue;
+        int pos = nk < FM_N ? nk++ : FM_N;                // insertion into the FM_N lowest
+        while (pos > 0 && fk[pos - 1] > fr) {
+            if (pos < FM_N) fk[pos] = fk[pos - 1];
+            --pos;
+        }
+        if (pos < FM_N) fk[pos] = fr;
+    }
+    for (int k = 0; k < FM_N; ++k) out[k] = k < nk ? fk[k] : 0.0;
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------
+int check_batch(goofer_ctx *ctx, const int64_t *sample_off, int n_sig, int sr, int hop, int64_t min_len)
+{
+    if (!sample_off || n_sig <= 0) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: empty batch");
+    if (sr < TR_SR_MIN || sr > TR_SR_MAX) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: sample rate %d outside [%d, %d]", sr, TR_SR_MIN, TR_SR_MAX);
+    if (hop <= 0) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: hop %d", hop);
+    if (sample_off[0] != 0) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: sample_off[0] must be 0");
+    for (int s = 0; s < n_sig; ++s) {
+        const int64_t n = sample_off[s + 1] - sample_off[s];
+        if (n < min_len || n < 1)
+            return goofer_fail(ctx, GOOFER_EINVAL, "tracker: signal %d has %lld samples, the pitch window needs at least %lld", s,
+                               (long long)n, (long long)std::max<int64_t>(min_len, 1));
+    }
+    return GOOFER_OK;
+}
+
+template <typename T>
+T *carve(char *&p, size_t count)
+{
+    T *r = reinterpret_cast<T *>(p);
+    p += align256(count * sizeof(T));
+    return r;
+}
+
+}  // namespace
+
+/* Exported: see include/goofer_hip.h */
+extern "C" int goofer_track_pitch(goofer_ctx *ctx, const double *y, const int64_t *sample_off, int n_signals, int sr, int hop,
+                                  int64_t *frame_off, double *f0, void *scratch, int64_t *scratch_bytes, void *stream)
+{
+    int rc = check_batch(ctx, sample_off, n_signals, sr, hop, pitch_min_length(sr));
+    if (rc) return rc;
+    if (!frame_off || !scratch_bytes) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: null frame_off / scratch_bytes");
+    frame_off[0] = 0;
+    for (int s = 0; s < n_signals; ++s) frame_off[s + 1] = frame_off[s] + pitch_frames(sample_off[s + 1] - sample_off[s], sr, hop);
+    const int64_t F = frame_off[n_signals];
+    const pitch_geom g = pitch_geometry(sr);
+    const size_t need = 2 * align256(8 * (size_t)(n_signals + 1)) + align256(16 * (size_t)n_signals) + align256(8 * (size_t)g.W) +
+                        align256(8 * (size_t)(g.hi + 1)) + 2 * align256(8 * TR_MAX_CAND * (size_t)F) + align256(4 * (size_t)F) +
+                        align256(TR_MAX_CAND * (size_t)F);
+    if (!scratch) {
+        *scratch_bytes = (int64_t)need;
+        return GOOFER_OK;
+    }
+    if (!ctx) return GOOFER_EINVAL;
+    if (!y || !f0) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: null signal / f0");
+    if (*scratch_bytes < (int64_t)need) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: scratch of %lld bytes, %zu needed", (long long)*scratch_bytes, need);
+    hipStream_t st = (hipStream_t)stream;
+    char *p = (char *)scratch;
+    int64_t *d_soff = carve<int64_t>(p, n_signals + 1), *d_foff = carve<int64_t>(p, n_signals + 1);
+    double *stats = carve<double>(p, 2 * (size_t)n_signals), *d_win = carve<double>(p, g.W), *d_rw = carve<double>(p, g.hi + 1);
+    double *cand_f = carve<double>(p, TR_MAX_CAND * (size_t)F), *cand_s = carve<double>(p, TR_MAX_CAND * (size_t)F);
+    int *cand_n = carve<int>(p, F);
+    unsigned char *back = carve<unsigned char>(p, TR_MAX_CAND * (size_t)F);
+
+    // Hann window of W samples and its own autocorrelation, normalised at lag 0
+    std::vector<double> win(g.W), rw(g.hi + 1);
+    for (int j = 0; j < g.W; ++j) win[j] = 0.5 - 0.5 * cos(2.0 * M_PI * (j + 1.0) / (g.W + 1.0));
+    for (int t = 0; t <= g.hi; ++t) {
+        double acc = 0.0;
+        for (int j = 0; j < g.W - t; ++j) acc += win[j] * win[j + t];
+        rw[t] = acc;
+    }
+    for (int t = g.hi; t >= 0; --t) rw[t] /= rw[0];
+    HIP_TRY(ctx, hipMemcpyAsync(d_soff, sample_off, 8 * (size_t)(n_signals + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_foff, frame_off, 8 * (size_t)(n_signals + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_win, win.data(), 8 * (size_t)g.W, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_rw, rw.data(), 8 * (size_t)(g.hi + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));                                            // the host vectors go out of scope
+
+    hipLaunchKernelGGL(k_pitch_stats, dim3(n_signals), dim3(TR_THREADS), 0, st, y, d_soff, stats);
+    LAUNCH_CHECK(ctx);
+    if (F > 0) {
+        const size_t lds = 8 * (size_t)(g.W + g.hi - g.lo + 1);
+        hipLaunchKernelGGL(k_pitch_frames, dim3((unsigned)F), dim3(TR_THREADS), lds, st, y, d_soff, d_foff, n_signals, sr, hop, g, d_win,
+                           d_rw, stats, cand_f, cand_s, cand_n);
+        LAUNCH_CHECK(ctx);
+        hipLaunchKernelGGL(k_pitch_viterbi, dim3(n_signals), dim3(WAVE), 0, st, d_foff, cand_f, cand_s, cand_n, 0.01 * sr / hop, back, f0);
+        LAUNCH_CHECK(ctx);
+    }
+    return GOOFER_OK;
+}
+
+extern "C" int goofer_track_formants(goofer_ctx *ctx, const double *y, const int64_t *sample_off, int n_signals, int sr, int hop,
+                                     int64_t *frame_off, double *formants, void *scratch, int64_t *scratch_bytes, void *stream)
+{
+    int rc = check_batch(ctx, sample_off, n_signals, sr, hop, 1);
+    if (rc) return rc;
+    if (!frame_off || !scratch_bytes) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: null frame_off / scratch_bytes");
+    std::vector<int64_t> moff(n_signals + 1, 0);
+    frame_off[0] = 0;
+    for (int s = 0; s < n_signals; ++s) {
+        const int64_t n = sample_off[s + 1] - sample_off[s];
+        moff[s + 1] = moff[s] + resampled_length(n, sr);
+        frame_off[s + 1] = frame_off[s] + formant_frames(n, sr, hop);
+    }
+    const int64_t F = frame_off[n_signals], M = moff[n_signals];
+    const size_t need = 3 * align256(8 * (size_t)(n_signals + 1)) + align256(8 * (size_t)M) + align256(8 * (size_t)FM_WIN);
+    if (!scratch) {
+        *scratch_bytes = (int64_t)need;
+        return GOOFER_OK;
+    }
+    if (!ctx) return GOOFER_EINVAL;
+    if (F == 0) return GOOFER_OK;                                                      // every signal shorter than a formant window
+    if (!y || !formants) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: null signal / formants");
+    if (*scratch_bytes < (int64_t)need) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: scratch of %lld bytes, %zu needed", (long long)*scratch_bytes, need);
+    hipStream_t st = (hipStream_t)stream;
+    char *p = (char *)scratch;
+    int64_t *d_soff = carve<int64_t>(p, n_signals + 1), *d_moff = carve<int64_t>(p, n_signals + 1), *d_foff = carve<int64_t>(p, n_signals + 1);
+    double *x11 = carve<double>(p, M), *d_gwin = carve<double>(p, FM_WIN);
+
+    // Praat's Gaussian-like window: exp(-48 (i - mid)^2 / (W + 1)^2), i = 1..W, lifted to zero at the ends
+    std::vector<double> gwin(FM_WIN);
+    const double e12 = exp(-12.0);
+    for (int j = 0; j < FM_WIN; ++j) {
+        const double d = (j + 1.0) - 0.5 * (FM_WIN + 1);
+        gwin[j] = (exp(-48.0 * d * d / ((FM_WIN + 1.0) * (FM_WIN + 1.0))) - e12) / (1.0 - e12);
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(d_soff, sample_off, 8 * (size_t)(n_signals + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_moff, moff.data(), 8 * (size_t)(n_signals + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_foff, frame_off, 8 * (size_t)(n_signals + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_gwin, gwin.data(), 8 * (size_t)FM_WIN, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));                                            // the host vectors go out of scope
+
+    hipLaunchKernelGGL(k_resample11k, dim3((unsigned)((M + TR_THREADS - 1) / TR_THREADS)), dim3(TR_THREADS), 0, st, y, d_soff, d_moff,
+                       n_signals, M, sr, x11);
+    LAUNCH_CHECK(ctx);
+    hipLaunchKernelGGL(k_formant_frames, dim3((unsigned)F), dim3(WAVE), 0, st, x11, d_moff, d_foff, n_signals, sr, hop, d_gwin, formants);
+    LAUNCH_CHECK(ctx);
+    return GOOFER_OK;
+}

@@ -221,6 +221,28 @@ class Context:
                                               float(ratio), self._stream()))
         return out
 
+    # -- f0 / formant tracks of the cold-cache analysis (csrc/tracker.hip) --------------------------------------
+    def track(self, y, lengths, sr: int, hop: int):
+        """Pitch and formant tracks of a ragged batch of signals: ``y`` a contiguous fp64 device tensor holding
+        ``lengths`` samples per signal.  Returns (f0 [frames] fp64, f0 frame_off, formants [frames', 5] fp64, formant
+        frame_off), the offsets as host int64 arrays.  Each call's scratch is a tensor of this method, released in
+        stream order when it returns."""
+        if not (isinstance(y, torch.Tensor) and y.dtype == torch.float64 and y.is_contiguous() and y.device == self.device):
+            raise ValueError("track expects a contiguous fp64 tensor on this context's device")
+        lengths = [int(v) for v in lengths]
+        if not lengths or any(v < 0 for v in lengths) or sum(lengths) != y.numel():
+            raise ValueError(f"track: the lengths sum to {sum(lengths)}, the signal has {y.numel()} samples")
+        s_off = self.offsets(lengths)
+        out = []
+        for fn, width in ((self.lib.goofer_track_pitch, 1), (self.lib.goofer_track_formants, 5)):
+            f_off, need = _track_query(fn, self.h, s_off, sr, hop, self._check)
+            res = torch.empty((int(f_off[-1]), width), dtype=torch.float64, device=self.device)
+            scratch = torch.empty(max(int(need.value), 1), dtype=torch.uint8, device=self.device)
+            self._check(fn(self.h, _ptr(y), s_off.ctypes.data_as(C.c_void_p), len(lengths), int(sr), int(hop),
+                           f_off.ctypes.data_as(C.c_void_p), _ptr(res), _ptr(scratch), C.byref(need), self._stream()))
+            out += [res if width > 1 else res[:, 0], f_off]
+        return tuple(out)
+
     # -- analysis (GOOFER.py:942-946, 97-147) -----------------------------------------------------
     def mag_rows(self, S):
         """complex64 [R, >=n_bins] -> |S| + 1e-8 as fp32 rows."""
@@ -440,6 +462,28 @@ class Context:
         out["_keep"] = (d_s, d_f, d_e, d_par, f0_64)   # keep device-side descriptors alive until the caller syncs
         out["sample_off"], out["frame_off"] = s_off, f_off
         return out
+
+
+def _track_query(fn, h, s_off, sr, hop, check):
+    """(frame_off, scratch bytes) of a goofer_track_* call: its query form, which runs no device code."""
+    f_off = np.zeros(len(s_off), dtype=np.int64)
+    need = C.c_int64(0)
+    check(fn(h, None, s_off.ctypes.data_as(C.c_void_p), len(s_off) - 1, int(sr), int(hop), f_off.ctypes.data_as(C.c_void_p),
+             None, None, C.byref(need), None))
+    return f_off, need
+
+
+def track_frame_offsets(lengths, sr: int, hop: int):
+    """(f0 frame_off, formant frame_off) the tracker gives signals of these lengths, from the library's own layout; needs
+    no device."""
+    lib = _lib.load()
+    s_off = np.zeros(len(lengths) + 1, dtype=np.int64)
+    np.cumsum(np.asarray(lengths, dtype=np.int64), out=s_off[1:])
+
+    def check(rc):
+        if rc != 0:
+            raise GooferError(f"libgoofer_hip error {rc}: the tracker refuses this batch (sample rate, hop or a signal length)")
+    return tuple(_track_query(fn, None, s_off, sr, hop, check)[0] for fn in (lib.goofer_track_pitch, lib.goofer_track_formants))
 
 
 def _ratios(subharm):

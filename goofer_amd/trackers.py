@@ -8,12 +8,14 @@ This module is the plug for that half and the host logic the reference wraps aro
 
 * a *tracker* is ``fn(y, sr, hop_length, n_frames) -> (f0_track [frames'], {1..5: formant track [n_frames]})``;
   ``praat_tracker`` makes the reference's very calls when ``parselmouth`` is importable (GOOFER.py:341-353, 768-792);
-  ``get()`` resolves the tracker to use (argument, ``GOOFER_TRACKER=module:function``, Praat when present);
+  ``native_tracker`` computes the same tracks on the GPU from the published methods without Praat (``tracker="native"``
+  or ``GOOFER_TRACKER=native``; its numbers are its own, not Praat's);
+  ``get()`` resolves the tracker to use (argument, ``GOOFER_TRACKER=name`` or ``module:function``, Praat when present);
 * ``fix_f0_gaps`` (GOOFER.py:415-435) and ``per_sample_f0`` (GOOFER.py:957-966) — pinned by ``tests/golden/cold_cache.npz``,
   which ``make_golden.py`` generates by running the reference's own ``extract_features`` over a fake ``parselmouth``;
 * ``analyse`` / ``ensure_features`` / ``extract_folder``: wav -> features -> byte-compatible ``.goofy`` next to the wav.
 
-Nothing here re-implements Praat.
+Nothing here re-implements Praat: the native tracker follows the published methods, not Praat's code.
 """
 from __future__ import annotations
 
@@ -58,7 +60,38 @@ def praat_tracker(y, sr, hop_length, n_frames):
     return pitch.selected_array["frequency"], fit_formants(tracks, n_frames)
 
 
-_REGISTRY = {"praat": praat_tracker}
+NATIVE_SR_RANGE = (8000, 96000)
+
+
+def native_min_length(sr) -> int:
+    """Samples in one pitch window of the native tracker: 3 periods of 75 Hz (40 ms), rounded up."""
+    return -(-3 * int(sr) // 75)
+
+
+def native_tracker(y, sr, hop_length, n_frames, ctx=None):
+    """``praat_tracker``'s contract on the GPU (csrc/tracker.hip): f0 by Boersma's autocorrelation method with a Viterbi
+    path and Praat's AC settings as the reference passes them (floor 75 Hz, ceiling 950 Hz, time step hop / sr), formants
+    by Burg's method with ``to_formant_burg``'s defaults (5 formants up to 5500 Hz, 50 ms Gaussian, pre-emphasis from 50 Hz).
+    Written from the published methods: its tracks are not Praat's numbers (parity unpinned), and the f0 track has its own
+    frame layout like Praat's does.  Raises ValueError for a signal shorter than one pitch window."""
+    import torch
+    from .device import default_context
+    y = np.asarray(y, dtype=np.float64)
+    if y.ndim != 1:
+        raise ValueError("native_tracker expects a mono signal")
+    sr = int(sr)
+    if not NATIVE_SR_RANGE[0] <= sr <= NATIVE_SR_RANGE[1]:
+        raise ValueError(f"native_tracker: sample rate {sr} Hz is outside {NATIVE_SR_RANGE[0]}..{NATIVE_SR_RANGE[1]} Hz")
+    if len(y) < native_min_length(sr):
+        raise ValueError(f"native_tracker: {len(y)} samples is shorter than one pitch window; at {sr} Hz the minimum length "
+                         f"is {native_min_length(sr)} samples (40 ms)")
+    c = ctx or default_context()
+    f0, _, forms, _ = c.track(torch.as_tensor(y).to(c.device), [len(y)], sr, int(hop_length))
+    f0, forms = f0.cpu().numpy(), forms.cpu().numpy()
+    return f0, fit_formants({k: forms[:, k - 1].tolist() for k in range(1, 6)}, n_frames)
+
+
+_REGISTRY = {"praat": praat_tracker, "native": native_tracker}
 
 
 def register(name: str, fn) -> None:
@@ -67,7 +100,8 @@ def register(name: str, fn) -> None:
 
 def get(tracker=None):
     """The tracker to use: the argument if it is callable; else the name given (or ``$GOOFER_TRACKER``) looked up in the
-    registry or imported as ``module:function``; else Praat when parselmouth is importable.  Raises TrackerUnavailable."""
+    registry ("praat", "native") or imported as ``module:function``; else Praat when parselmouth is importable.  Raises
+    TrackerUnavailable.  The native tracker is used only when named."""
     if callable(tracker):
         return tracker
     name = tracker or os.environ.get("GOOFER_TRACKER")
@@ -81,7 +115,7 @@ def get(tracker=None):
     if importlib.util.find_spec("parselmouth") is not None:
         return praat_tracker
     raise TrackerUnavailable("this sample has no _features.goofy and no f0 / formant tracker is available: install "
-                             "praat-parselmouth (what the reference uses), set GOOFER_TRACKER=module:function, or run the "
+                             "praat-parselmouth (what the reference uses), set GOOFER_TRACKER=native (the GPU tracker) or module:function, or run the "
                              "reference's extractor once")
 
 

@@ -305,6 +305,23 @@ int goofer_knot_fit_error(goofer_ctx *ctx, const double *env, int ld64, const in
 int goofer_knot_gather(goofer_ctx *ctx, const double *env, int ld64, int64_t rows, const int32_t *knot_bin, int K,
                        uint16_t *knots_f16, void *stream);
 
+/* ---- f0 and formant tracks of the cold-cache analysis (goofer_amd/csrc/tracker.hip) -------------------------------
+ * A ragged batch of fp64 signals y (device) at one sample rate sr in [8000, 96000]; sample_off[n_signals+1] and
+ * frame_off[n_signals+1] are HOST arrays, frame_off is written by the call.  Call once with scratch = NULL (ctx may be NULL
+ * too): frame_off and *scratch_bytes are filled in and nothing else happens.  Then call with device scratch of at least
+ * that many bytes; the scratch is the caller's and is in use until the stream reaches the end of the call.
+ *
+ * goofer_track_pitch: Boersma's autocorrelation method with a Viterbi path, floor 75 Hz, ceiling min(950, sr/2) Hz,
+ * time step hop / sr, window 3 / 75 s (Hann).  Frames: floor((n - 3 sr / 75) / hop) + 1 per signal, centred in it.
+ * f0 [frame_off[n]] in Hz, 0 where unvoiced.  Every signal needs ceil(3 sr / 75) samples at least (GOOFER_EINVAL).
+ * goofer_track_formants: Burg LPC of order 10 on the signal resampled to 11 kHz and pre-emphasised from 50 Hz, 50 ms
+ * Gaussian window, same time step; frames: floor((m - 550) sr / (11000 hop)) + 1 for m = n * 11000 / sr resampled samples
+ * (0 when m < 550).  formants [frame_off[n] x 5] in Hz, ascending, 0 where fewer than five roots lie in (50, 5450) Hz. */
+int goofer_track_pitch(goofer_ctx *ctx, const double *y, const int64_t *sample_off, int n_signals, int sr, int hop,
+                       int64_t *frame_off, double *f0, void *scratch, int64_t *scratch_bytes, void *stream);
+int goofer_track_formants(goofer_ctx *ctx, const double *y, const int64_t *sample_off, int n_signals, int sr, int hop,
+                          int64_t *frame_off, double *formants, void *scratch, int64_t *scratch_bytes, void *stream);
+
 /* ---- the hot path --------------------------------------------------------------------------- */
 
 /* gf.synthesize for a ragged batch (GOOFER.py:971-1220) + the V/B/U mix (SillySampler.py:1142-1151). */
