@@ -184,9 +184,22 @@ class BatchCollector:
                 gc.freeze()
         return src
 
+    def _analyse_cold(self, batch, renderer):
+        """The batch's voicebank samples without a cache, each once, analysed together (trackers.ensure_features_batch):
+        {wav path: .goofy path or the exception every note naming that sample fails with}."""
+        cold = list(dict.fromkeys(Path(p.args[0]) for p in batch
+                                  if len(p.args) >= 13 and not trackers.features_path(Path(p.args[0])).exists()))
+        if not cold:
+            return {}
+        try:
+            return trackers.ensure_features_batch(cold, hop_length=renderer.hop, tracker=self.tracker, ctx=renderer.ctx)
+        except Exception as e:          # noqa: BLE001 - e.g. no tracker: the notes of these samples fail with it
+            return {f: e for f in cold}
+
     def _render(self, batch, renderer=None):
         from .render import write_wav
         renderer = renderer or self.renderer
+        cold = self._analyse_cold(batch, renderer)
         jobs, owners = [], []
         for p in batch:                                    # per-note decode / feature load: errors stay per note
             try:
@@ -196,6 +209,8 @@ class BatchCollector:
                 req = S.decode_request(*p.args[2:13])
                 # cached features, or analysed from the wav and cached on the first request for a sample (SillySampler.py:415-432)
                 feat = trackers.features_path(in_file)
+                if isinstance(cold.get(in_file), BaseException):
+                    raise cold[in_file]
                 if not feat.exists():
                     feat = trackers.ensure_features(in_file, hop_length=renderer.hop, tracker=self.tracker, ctx=renderer.ctx)
                 src = self._source(feat)

@@ -335,6 +335,24 @@ def make_mel_knots(sr, n_fft, K):
     return np.fft.rfftfreq(n_fft, 1.0 / sr).astype(np.float32), mel_knots_hz(sr, K)
 
 
+def _knot_bins(hz, sr, n_fft, nb):
+    """int32 nearest bin of every knot frequency (GOOFER.py:114)."""
+    res = sr / n_fft
+    return np.clip(np.round(hz / res).astype(int), 0, nb - 1).astype(np.int32)
+
+
+KNOT_CANDIDATES = tuple(range(32, 193, 16))     # compress_env_to_knots' K_start, K_step, K_max defaults
+
+
+def knot_candidate_tables(sr, n_fft):
+    """(hz fp32, bins int32) of every candidate of KNOT_CANDIDATES back to back, exactly as compress_env_to_knots makes them:
+    the tables goofer_envelope_knots_batch scores."""
+    nb = n_fft // 2 + 1
+    hz = [make_mel_knots(sr, n_fft, K)[1] for K in KNOT_CANDIDATES]
+    return (np.ascontiguousarray(np.concatenate(hz), dtype=np.float32),
+            np.ascontiguousarray(np.concatenate([_knot_bins(h, sr, n_fft, nb) for h in hz]), dtype=np.int32))
+
+
 def compress_env_to_knots(env_spec, sr, n_fft, eps=1e-2, K_start=32, K_step=16, K_max=192, smooth_sigma_bins=0.5, ctx=None,
                           _rows=None):
     """Smallest mel-knot count whose 2-tap lerp reproduces the (sigma 0.5 blurred) envelope to < eps max relative
@@ -346,13 +364,11 @@ def compress_env_to_knots(env_spec, sr, n_fft, eps=1e-2, K_start=32, K_step=16, 
     taps = gaussian_taps(smooth_sigma_bins) if smooth_sigma_bins > 0 and int(4.0 * smooth_sigma_bins + 0.5) > 0 else np.ones(1)
     env2 = c.gauss_bins_f64(rows, taps)
     probe = c.tensor(np.linspace(0, T - 1, min(256, T), dtype=int).astype(np.int64))
-    res = sr / n_fft
     chosen = None
     for K in list(range(K_start, K_max + 1, K_step)) + [None]:
         last = K is None
         _, hz = make_mel_knots(sr, n_fft, K_max if last else K)
-        at = np.clip(np.round(hz / res).astype(int), 0, nb - 1).astype(np.int32)
-        d_at = c.tensor(at)
+        d_at = c.tensor(_knot_bins(hz, sr, n_fft, nb))
         if not last and not (c.knot_fit_error(env2, probe, d_at, hz) < eps):
             continue
         vals = c.knot_gather(env2, d_at).cpu().numpy().T
@@ -385,6 +401,13 @@ def extract_features(y, sr, n_fft=1024, hop_length=256, f0_min=75, f0_max=600, f
     ``trackers.TrackerUnavailable`` (a NotImplementedError).  ``f0_max`` is accepted and unused, as in the reference."""
     from . import trackers
     return trackers.analyse(y, sr, n_fft, hop_length, f0_min, f0_merge_range, tracker=pitch_tracker, ctx=ctx)
+
+
+def extract_features_batch(signals, sr, n_fft=1024, hop_length=256, f0_min=75, f0_merge_range=2, pitch_tracker=None, ctx=None):
+    """``extract_features`` for a list of signals at one sample rate, in batched device passes: one 5-tuple per signal, or
+    the exception that signal raised.  The results equal ``extract_features`` run on each signal alone (trackers.analyse_batch)."""
+    from . import trackers
+    return trackers.analyse_batch(signals, sr, n_fft, hop_length, f0_min, f0_merge_range, tracker=pitch_tracker, ctx=ctx)
 
 
 # -- synthesize --------------------------------------------------------------------------------------

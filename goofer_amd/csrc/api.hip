@@ -47,6 +47,12 @@ int launch_gauss_rows64(goofer_ctx *, const float *, int, double *, int, int64_t
 int launch_knot_error(goofer_ctx *, const double *, int, const int64_t *, int, int, const int *, int, const int *, const float *,
                       const float *, unsigned long long *, hipStream_t);
 int launch_knot_gather(goofer_ctx *, const double *, int, int64_t, const int *, int, uint16_t *, hipStream_t);
+int launch_env_rows_fused(goofer_ctx *, const float2 *, int, int64_t, int, const double *, int, const double *, int, double *, int, double *,
+                          int, hipStream_t);
+int launch_knot_search(goofer_ctx *, const double *, int, const int64_t *, const int *, int, int, const int *, const int *, const float *,
+                       const float *, unsigned long long *, hipStream_t);
+int launch_knot_pick(goofer_ctx *, const double *, int, int64_t, const int *, const int64_t *, const int *, const unsigned long long *,
+                     uint16_t *, int32_t *, hipStream_t);
 int launch_ola3_gains(goofer_ctx *, const float *, const float *, const float *, const float *, const double *, const int64_t *,
                       const int64_t *, int, int64_t, const goofer_note_params *, double *, float *, float *, float *, float *, hipStream_t);
 template <typename Tin>
@@ -1134,6 +1140,111 @@ int goofer_knot_gather(goofer_ctx *ctx, const double *env, int ld64, int64_t row
 {
     if (!ctx) return GOOFER_EINVAL;
     return launch_knot_gather(ctx, env, ld64, rows, knot_bin, K, knots_f16, (hipStream_t)stream);
+}
+
+int goofer_envelope_knots_batch(goofer_ctx *ctx, const float *y, const int64_t *sample_off, int n_signals, const double *taps_env,
+                                int radius_env, const double *taps_fit, int radius_fit, const float *hz_knots, const int32_t *knot_bin,
+                                int64_t *frame_off, uint16_t *knots_f16, int32_t *K_out, double *env_rows, int ld64, void *scratch,
+                                int64_t *scratch_bytes, void *stream)
+{
+    NEED_PLAN(ctx);
+    const goofer_plan_t &p = ctx->plan;
+    const int nb = p.n_bins, ldc = spec_stride(nb), ld2 = (nb + 1) & ~1;
+    if (!sample_off || n_signals <= 0 || !frame_off || !scratch_bytes) return goofer_fail(ctx, GOOFER_EINVAL, "envelope batch: null argument");
+    if (sample_off[0] != 0) return goofer_fail(ctx, GOOFER_EINVAL, "envelope batch: sample_off[0] must be 0");
+    if (radius_env < 0 || radius_env > 64 || radius_fit < 0 || radius_fit > 64 || !taps_env || !taps_fit)
+        return goofer_fail(ctx, GOOFER_EINVAL, "envelope batch: bad taps");
+    frame_off[0] = 0;
+    int64_t n_probe = 0;
+    for (int s = 0; s < n_signals; ++s) {
+        const int64_t n = sample_off[s + 1] - sample_off[s];
+        if (n < 1) return goofer_fail(ctx, GOOFER_EINVAL, "envelope batch: signal %d is empty", s);
+        const int64_t T = 1 + n / p.hop;                                               // frames of gf.stft
+        frame_off[s + 1] = frame_off[s] + T;
+        n_probe += std::min<int64_t>(256, T);
+    }
+    const int64_t F = frame_off[n_signals];
+    int64_t *d_soff, *d_foff, *probe_row;
+    int *frame_sig, *probe_sig, *d_bin, *d_idx;
+    float2 *S;
+    double *env2, *d_taps;
+    float *d_w0, *d_w1;
+    unsigned long long *err;
+    auto carve = [&](arena &a) {
+        d_soff = a.take<int64_t>(n_signals + 1);
+        d_foff = a.take<int64_t>(n_signals + 1);
+        frame_sig = a.take<int>(F);
+        S = a.take<float2>((size_t)F * ldc);
+        env2 = a.take<double>((size_t)F * ld2);
+        probe_row = a.take<int64_t>(n_probe);
+        probe_sig = a.take<int>(n_probe);
+        err = a.take<unsigned long long>((size_t)n_signals * KN_CAND);
+        d_taps = a.take<double>(2 * (radius_env + radius_fit) + 2);
+        d_bin = a.take<int>(KN_BINS_TOTAL);
+        d_idx = a.take<int>((size_t)KN_CAND * nb);
+        d_w0 = a.take<float>((size_t)KN_CAND * nb);
+        d_w1 = a.take<float>((size_t)KN_CAND * nb);
+    };
+    arena count{nullptr, 0};
+    carve(count);
+    if (!y) {                                                                           // query form: no device code
+        *scratch_bytes = (int64_t)count.used;
+        return GOOFER_OK;
+    }
+    if (!knots_f16 || !K_out || !hz_knots || !knot_bin || (env_rows && ld64 < nb))
+        return goofer_fail(ctx, GOOFER_EINVAL, "envelope batch: null output or ld64 < n_bins");
+    if (!scratch || *scratch_bytes < (int64_t)count.used)
+        return goofer_fail(ctx, GOOFER_EINVAL, "envelope batch: scratch of %lld bytes, %zu needed", (long long)*scratch_bytes, count.used);
+    for (int i = 0; i < KN_BINS_TOTAL; ++i)
+        if (knot_bin[i] < 0 || knot_bin[i] >= nb) return goofer_fail(ctx, GOOFER_EINVAL, "envelope batch: knot bin %d out of range", knot_bin[i]);
+    arena a{(char *)scratch, 0};
+    carve(a);
+
+    // probe rows: linspace(0, T - 1, min(256, T), dtype=int) per signal, as numpy computes it (start + j * step, last = stop, floor)
+    std::vector<int64_t> prow;
+    std::vector<int> psig;
+    prow.reserve(n_probe);
+    psig.reserve(n_probe);
+    for (int s = 0; s < n_signals; ++s) {
+        const int64_t T = frame_off[s + 1] - frame_off[s], num = std::min<int64_t>(256, T);
+        const double step = num > 1 ? (double)(T - 1) / (double)(num - 1) : 0.0;
+        for (int64_t j = 0; j < num; ++j) {
+            const int64_t v = j == num - 1 ? T - 1 : (int64_t)floor((double)j * step);
+            prow.push_back(frame_off[s] + v);
+            psig.push_back(s);
+        }
+    }
+    // the lerp tables of every candidate, from the helper goofer_knot_fit_error / goofer_knot_decode use
+    std::vector<int> idx_all((size_t)KN_CAND * nb), idx;
+    std::vector<float> w0_all((size_t)KN_CAND * nb), w1_all((size_t)KN_CAND * nb), w0, w1;
+    for (int c = 0, kb = 0; c < KN_CAND; kb += KN_K0 + KN_DK * c, ++c) {
+        knot_lerp_plan(p, hz_knots + kb, KN_K0 + KN_DK * c, nb, idx, w0, w1);
+        std::copy(idx.begin(), idx.end(), idx_all.begin() + (size_t)c * nb);
+        std::copy(w0.begin(), w0.end(), w0_all.begin() + (size_t)c * nb);
+        std::copy(w1.begin(), w1.end(), w1_all.begin() + (size_t)c * nb);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(ctx, hipMemcpyAsync(d_soff, sample_off, 8 * (size_t)(n_signals + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_foff, frame_off, 8 * (size_t)(n_signals + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(probe_row, prow.data(), 8 * (size_t)n_probe, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(probe_sig, psig.data(), 4 * (size_t)n_probe, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_taps, taps_env, 8 * (size_t)(2 * radius_env + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_taps + 2 * radius_env + 1, taps_fit, 8 * (size_t)(2 * radius_fit + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_bin, knot_bin, 4 * (size_t)KN_BINS_TOTAL, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_idx, idx_all.data(), 4 * idx_all.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_w0, w0_all.data(), 4 * w0_all.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_w1, w1_all.data(), 4 * w1_all.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemsetAsync(err, 0, 8 * (size_t)n_signals * KN_CAND, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));                                            // the host vectors go out of scope
+
+    int rc;
+    if ((rc = launch_frame_note(ctx, d_foff, n_signals, F, frame_sig, st))) return rc;
+    if ((rc = launch_rfft_frames_mapped(ctx, y, d_soff, d_foff, frame_sig, F, S, ldc, st))) return rc;
+    if ((rc = launch_env_rows_fused(ctx, S, ldc, F, nb, d_taps, radius_env, d_taps + 2 * radius_env + 1, radius_fit, env_rows, ld64, env2, ld2,
+                                    st)))
+        return rc;
+    if ((rc = launch_knot_search(ctx, env2, ld2, probe_row, probe_sig, (int)n_probe, nb, d_bin, d_idx, d_w0, d_w1, err, st))) return rc;
+    return launch_knot_pick(ctx, env2, ld2, F, frame_sig, d_foff, d_bin, err, knots_f16, K_out, st);
 }
 
 /* gf.smooth_mask_ds (GOOFER.py:556-569) for a ragged batch of masks: decimate by 4, Gaussian sigma/4 (fp64), linear

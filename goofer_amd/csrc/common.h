@@ -13,6 +13,12 @@
 #define PROF_ASM0 15           // profile stages 15..17: the assembly's k_env_edit, k_env_rows, k_sample_assemble
 #define PP_SPT 8                // k_pulse_place: consecutive samples per thread; a tile = one workgroup = 256 * PP_SPT samples
 #define PULSE_TILE_INTS(samples) (4 * (((samples) + 256 * PP_SPT - 1) / (256 * PP_SPT)) + 64)   // k_pulse_tiles' table: 4 ints per tile
+// compress_env_to_knots' candidate knot counts (GOOFER.py:97-147): K = KN_K0, KN_K0 + KN_DK, ..., KN_KMAX
+#define KN_K0 32
+#define KN_DK 16
+#define KN_KMAX 192
+#define KN_CAND ((KN_KMAX - KN_K0) / KN_DK + 1)
+#define KN_BINS_TOTAL (KN_CAND * KN_K0 + KN_DK * KN_CAND * (KN_CAND - 1) / 2)   // knots of all candidates back to back (1232)
 #define PULSE_TAB_MAX 8192     // pulse lengths served from the shape table: all of them (the reference caps T0 at 8192, GOOFER.py:497-498) — 134 MB of
                                // a 288 GB device; until late in round 5 the table ended at 2048 and k_pulse_place evaluated longer pulses on the fly, whose
                                // fp64 sin / exp / cos set the kernel's registers (115, four waves per SIMD) though no note of the workloads reached them

@@ -244,6 +244,41 @@ class Context:
         return tuple(out)
 
     # -- analysis (GOOFER.py:942-946, 97-147) -----------------------------------------------------
+    def envelope_knots(self, y32, lengths, want_env: bool = False):
+        """The envelope half of gf.extract_features for a ragged batch at the current plan (goofer_envelope_knots_batch):
+        ``y32`` a contiguous fp32 device tensor holding ``lengths`` samples per signal.  Returns (knots fp16 [frames, 192]:
+        signal i's [T_i, K_i] knots frames-major from row frame_off[i] on, K int32 [n] on the device, frame_off host int64
+        [n + 1], the sigma-2 envelope fp64 [frames, n_bins] or None).  Nothing is synchronised: the results are ready when
+        the stream is.  The call's scratch is a tensor of this method, released in stream order when it returns."""
+        from . import core
+        if not (isinstance(y32, torch.Tensor) and y32.dtype == torch.float32 and y32.is_contiguous() and y32.device == self.device):
+            raise ValueError("envelope_knots expects a contiguous fp32 tensor on this context's device")
+        lengths = [int(v) for v in lengths]
+        if not lengths or any(v < 1 for v in lengths) or sum(lengths) != y32.numel():
+            raise ValueError(f"envelope_knots: {len(lengths)} lengths summing to {sum(lengths)} for {y32.numel()} samples "
+                             "(every signal needs a sample at least)")
+        sr, n_fft, _ = self.geom
+        tabs = getattr(self, "_knot_tabs", None)
+        if tabs is None or tabs[0] != (sr, n_fft):
+            tabs = self._knot_tabs = ((sr, n_fft), core.knot_candidate_tables(sr, n_fft), core.gaussian_taps(2.0), core.gaussian_taps(0.5))
+        (hz, bins), t_env, t_fit = tabs[1], tabs[2], tabs[3]
+        s_off = self.offsets(lengths)
+        f_off = np.zeros(len(lengths) + 1, dtype=np.int64)
+        need = C.c_int64(0)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+        args = (vp(t_env), (t_env.size - 1) // 2, vp(t_fit), (t_fit.size - 1) // 2, vp(hz), vp(bins), vp(f_off))
+        self._check(self.lib.goofer_envelope_knots_batch(self.h, None, vp(s_off), len(lengths), *args, None, None, None, 0, None,
+                                                         C.byref(need), None))
+        F, nb = int(f_off[-1]), self.n_bins
+        knots = torch.empty((F, 192), dtype=torch.float16, device=self.device)
+        K = torch.empty(len(lengths), dtype=torch.int32, device=self.device)
+        ld64 = (nb + 1) & ~1
+        env = torch.empty((F, ld64), dtype=torch.float64, device=self.device) if want_env else None
+        scratch = torch.empty(max(int(need.value), 1), dtype=torch.uint8, device=self.device)
+        self._check(self.lib.goofer_envelope_knots_batch(self.h, _ptr(y32), vp(s_off), len(lengths), *args, _ptr(knots), _ptr(K),
+                                                         _ptr(env), ld64, _ptr(scratch), C.byref(need), self._stream()))
+        return knots, K, f_off, (env[:, :nb] if want_env else None)
+
     def mag_rows(self, S):
         """complex64 [R, >=n_bins] -> |S| + 1e-8 as fp32 rows."""
         R, nb = S.shape

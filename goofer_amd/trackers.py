@@ -13,7 +13,8 @@ This module is the plug for that half and the host logic the reference wraps aro
   ``get()`` resolves the tracker to use (argument, ``GOOFER_TRACKER=name`` or ``module:function``, Praat when present);
 * ``fix_f0_gaps`` (GOOFER.py:415-435) and ``per_sample_f0`` (GOOFER.py:957-966) — pinned by ``tests/golden/cold_cache.npz``,
   which ``make_golden.py`` generates by running the reference's own ``extract_features`` over a fake ``parselmouth``;
-* ``analyse`` / ``ensure_features`` / ``extract_folder``: wav -> features -> byte-compatible ``.goofy`` next to the wav.
+* ``analyse`` / ``ensure_features`` / ``extract_folder``: wav -> features -> byte-compatible ``.goofy`` next to the wav;
+  ``analyse_batch`` / ``ensure_features_batch`` do the same for many samples in batched device passes.
 
 Nothing here re-implements Praat: the native tracker follows the published methods, not Praat's code.
 """
@@ -68,6 +69,17 @@ def native_min_length(sr) -> int:
     return -(-3 * int(sr) // 75)
 
 
+def native_refusal(n_samples, sr):
+    """The ValueError native_tracker raises for a mono signal of this length and rate, or None when it takes the signal."""
+    sr = int(sr)
+    if not NATIVE_SR_RANGE[0] <= sr <= NATIVE_SR_RANGE[1]:
+        return ValueError(f"native_tracker: sample rate {sr} Hz is outside {NATIVE_SR_RANGE[0]}..{NATIVE_SR_RANGE[1]} Hz")
+    if n_samples < native_min_length(sr):
+        return ValueError(f"native_tracker: {n_samples} samples is shorter than one pitch window; at {sr} Hz the minimum length "
+                          f"is {native_min_length(sr)} samples (40 ms)")
+    return None
+
+
 def native_tracker(y, sr, hop_length, n_frames, ctx=None):
     """``praat_tracker``'s contract on the GPU (csrc/tracker.hip): f0 by Boersma's autocorrelation method with a Viterbi
     path and Praat's AC settings as the reference passes them (floor 75 Hz, ceiling 950 Hz, time step hop / sr), formants
@@ -80,11 +92,9 @@ def native_tracker(y, sr, hop_length, n_frames, ctx=None):
     if y.ndim != 1:
         raise ValueError("native_tracker expects a mono signal")
     sr = int(sr)
-    if not NATIVE_SR_RANGE[0] <= sr <= NATIVE_SR_RANGE[1]:
-        raise ValueError(f"native_tracker: sample rate {sr} Hz is outside {NATIVE_SR_RANGE[0]}..{NATIVE_SR_RANGE[1]} Hz")
-    if len(y) < native_min_length(sr):
-        raise ValueError(f"native_tracker: {len(y)} samples is shorter than one pitch window; at {sr} Hz the minimum length "
-                         f"is {native_min_length(sr)} samples (40 ms)")
+    refused = native_refusal(len(y), sr)
+    if refused is not None:
+        raise refused
     c = ctx or default_context()
     f0, _, forms, _ = c.track(torch.as_tensor(y).to(c.device), [len(y)], sr, int(hop_length))
     f0, forms = f0.cpu().numpy(), forms.cpu().numpy()
@@ -230,13 +240,20 @@ def ensure_features(audio_path, n_fft=1024, hop_length=256, tracker=None, ctx=No
     logging.info("Extracting features")
     y, sr = read_audio(audio_path)
     _, f0, vmask, forms, knots = analyse(y, sr, n_fft, hop_length, tracker=track_fn, ctx=ctx)
-    # a name of its own per writer (two threads of one process may analyse the same cold sample), gone again if anything fails
+    return _write_features(feat, knots, f0, vmask, forms, sr, len(y))
+
+
+def _write_features(feat, knots, f0, vmask, forms, sr, y_len) -> Path:
+    """save_features into a temporary file beside ``feat``, then renamed over it: a concurrent render never loads half a cache.
+    The temporary name is one of its own per writer (two threads of one process may analyse the same cold sample) and is gone
+    again if anything fails."""
+    from . import core
     import tempfile
     fd, tmp_name = tempfile.mkstemp(prefix=feat.name + ".tmp", dir=str(feat.parent))
     os.close(fd)
     tmp = Path(tmp_name)
     try:
-        core.save_features(tmp, knots, f0, vmask, forms, sr, len(y))
+        core.save_features(tmp, knots, f0, vmask, forms, sr, y_len)
         os.replace(tmp, feat)
     finally:
         if tmp.exists():
@@ -246,23 +263,194 @@ def ensure_features(audio_path, n_fft=1024, hop_length=256, tracker=None, ctx=No
 
 def extract_folder(path, tracker=None, ctx=None) -> dict:
     """Folder mode (SillySampler.py:214-240): every audio file under ``path`` (or the file itself) gets its ``.goofy``;
-    existing ones are skipped, a failing file is logged and does not stop the others.  Files go one after the other — the
-    analysis of a file is GPU work plus the tracker, and one context serves one host thread.  Returns the tallies."""
+    existing ones are skipped, a failing file is logged and does not stop the others.  The files without a cache are analysed
+    together by ``ensure_features_batch`` (device passes of many files each).  Returns the tallies."""
     root = Path(path)
     files = [f for f in (sorted(root.rglob("*")) if root.is_dir() else [root]) if f.is_file() and f.suffix.lower() in AUDIO_SUFFIXES]
     track_fn = get(tracker)                                      # fail before the first file, not at every file
     done = {"extracted": 0, "skipped": 0, "failed": 0}
+    todo = []
     for f in files:
         if features_path(f).exists():
             logging.info(f"[SKIP] {features_path(f).name} already exists")
             done["skipped"] += 1
             continue
-        try:
-            logging.info(f"[EXTRACT] {f}")
-            ensure_features(f, tracker=track_fn, ctx=ctx)
-            done["extracted"] += 1
-        except Exception as e:                                    # noqa: BLE001 - per-file isolation like the reference
-            logging.error(f"[ERROR] Failed to extract {f.name}: {e}")
+        logging.info(f"[EXTRACT] {f}")
+        todo.append(f)
+    try:
+        results = ensure_features_batch(todo, tracker=track_fn, ctx=ctx) if todo else {}
+    except Exception as e:                                        # noqa: BLE001 - nothing could run: every file failed with it
+        results = {f: e for f in todo}
+    for f in todo:
+        if isinstance(results[f], BaseException):
+            logging.error(f"[ERROR] Failed to extract {f.name}: {results[f]}")
             done["failed"] += 1
+        else:
+            done["extracted"] += 1
     logging.info(f"[DONE] Extracted features from {len(files)} files.")
     return done
+
+
+# -- batched analysis -------------------------------------------------------------------------------------------------
+FRAME_BUDGET = 1 << 16     # STFT frames per device pass: ~6 minutes of 44.1 kHz audio, ~0.6 GB of pass scratch at n_fft 1024
+WORKERS = 8                # host threads that read wavs and write .goofy files (a fixed default: the host's CPU count is no guide)
+
+
+def plan_passes(entries, frame_budget=FRAME_BUDGET):
+    """Cut ``entries`` = [(key, sr, n_frames)] into device passes [(sr, [key, ...])].  A key seen before is dropped.  Sample
+    rates come in the order they first appear; inside a rate the keys keep their input order and are taken greedily while the
+    pass stays within ``frame_budget`` frames.  A signal larger than the budget gets a pass of its own."""
+    if frame_budget < 1:
+        raise ValueError("frame_budget must be at least one frame")
+    seen, groups = set(), {}
+    for key, sr, frames in entries:
+        if key in seen:
+            continue
+        seen.add(key)
+        groups.setdefault(int(sr), []).append((key, int(frames)))
+    passes = []
+    for sr, members in groups.items():
+        cur, used = [], 0
+        for key, frames in members:
+            if cur and used + frames > frame_budget:
+                passes.append((sr, cur))
+                cur, used = [], 0
+            cur.append(key)
+            used += frames
+        if cur:
+            passes.append((sr, cur))
+    return passes
+
+
+def analyse_batch(signals, sr, n_fft=1024, hop_length=256, f0_min=75, f0_merge_range=2, tracker=None, ctx=None, want_env=True,
+                  timings=None):
+    """``analyse`` for many signals at one sample rate: one ``extract_features`` 5-tuple per signal, or the exception that
+    signal raised (env_spec is None unless ``want_env``).  The envelope and knots of every signal come from one
+    ``Context.envelope_knots`` call; with the native tracker one ``Context.track`` call follows on the same stream and the
+    host waits once for both.  Any other tracker is called per signal.  The f0 post-processing stays per signal on the host.
+    ``timings``, a dict, collects seconds under "device" (upload to results on the host) and "host"."""
+    import time
+    import torch
+    from . import core
+    from .device import default_context
+    track_fn = get(tracker)
+    native = track_fn is native_tracker
+    sr, hop = int(sr), int(hop_length)
+    out = [None] * len(signals)
+    ys, live = [], []
+    for i, y in enumerate(signals):
+        y = np.asarray(y)
+        refused = (ValueError("analyse_batch: expected a mono signal") if y.ndim != 1 else
+                   ValueError("analyse_batch: empty signal") if y.size == 0 else
+                   native_refusal(y.size, sr) if native else None)
+        if refused is not None:
+            out[i] = refused
+        else:
+            ys.append(y)
+            live.append(i)
+    if not live:
+        return out
+    t0 = time.perf_counter()
+    c = (ctx or default_context()).plan(sr, n_fft, hop)
+    lengths = [y.size for y in ys]
+    y32 = torch.from_numpy(np.concatenate([np.asarray(y, dtype=np.float32) for y in ys])).to(c.device)
+    knots, K, f_off, env = c.envelope_knots(y32, lengths, want_env=want_env)
+    if native:
+        y64 = torch.from_numpy(np.concatenate([np.asarray(y, dtype=np.float64) for y in ys])).to(c.device)
+        f0, p_off, forms, m_off = c.track(y64, lengths, sr, hop)
+        f0, forms = f0.cpu().numpy(), forms.cpu().numpy()
+    knots, K = knots.cpu().numpy(), K.cpu().numpy()
+    env = env.cpu().numpy() if want_env else None
+    t1 = time.perf_counter()
+    nb = c.n_bins
+    for j, (i, y) in enumerate(zip(live, ys)):
+        try:
+            a, b = int(f_off[j]), int(f_off[j + 1])
+            T, Kj = b - a, int(K[j])
+            vals = knots[a:b].reshape(-1)[:T * Kj].reshape(T, Kj).T
+            env_knots = {"mode": "knots", "knot_vals_log": np.ascontiguousarray(vals),
+                         "hz_knots": core.make_mel_knots(sr, n_fft, Kj)[1].astype(np.float32), "n_bins": int(nb),
+                         "n_fft": int(n_fft), "sr": int(sr)}
+            env_spec = np.ascontiguousarray(env[a:b].T) if want_env else None
+            if native:
+                f0_track = f0[p_off[j]:p_off[j + 1]]
+                formants = fit_formants({k: forms[m_off[j]:m_off[j + 1], k - 1].tolist() for k in range(1, 6)}, T)
+            else:
+                f0_track, formants = track_fn(y, sr, hop, T)
+            f0_s, vmask = per_sample_f0(f0_track, y.size, sr, f0_min, f0_merge_range)
+            out[i] = (env_spec, f0_s, vmask, fit_formants(dict(formants), T), env_knots)
+        except Exception as e:                                    # noqa: BLE001 - per-signal isolation
+            out[i] = e
+    if timings is not None:
+        timings["device"] = timings.get("device", 0.0) + (t1 - t0)
+        timings["host"] = timings.get("host", 0.0) + (time.perf_counter() - t1)
+    return out
+
+
+def _read_or_error(path):
+    try:
+        return read_audio(path)
+    except Exception as e:                                        # noqa: BLE001 - reported per file
+        return e
+
+
+def ensure_features_batch(paths, n_fft=1024, hop_length=256, tracker=None, ctx=None, frame_budget=FRAME_BUDGET, workers=WORKERS,
+                          timings=None) -> dict:
+    """``ensure_features`` for many samples: ``{path: .goofy Path or the exception for that path}`` in input order, each
+    path once.  Existing caches are returned untouched.  The wavs are read on ``workers`` threads, grouped by sample rate and
+    analysed in device passes of at most ``frame_budget`` STFT frames (``plan_passes``); the ``.goofy`` files are written on
+    the same threads, the way ``ensure_features`` writes them.  With the native tracker a file it would refuse (too short,
+    sample rate out of range) fails up front with its ValueError and the rest of its group still goes.  The tracker is
+    resolved first: TrackerUnavailable is raised for the whole call.  ``timings``, a dict, collects seconds under "read",
+    "device", "host" and "write" (waiting for the writes still running after the last pass)."""
+    import time
+    from concurrent.futures import ThreadPoolExecutor
+    order = list(dict.fromkeys(paths))
+    out, todo = {}, []
+    for p in order:
+        feat = features_path(p)
+        if feat.exists():
+            out[p] = feat
+        elif not Path(p).exists():
+            out[p] = FileNotFoundError(f"{p} not found (and no {feat.name} beside it)")
+        else:
+            todo.append(p)
+    if todo:
+        track_fn = get(tracker)
+        native = track_fn is native_tracker
+        timings = {} if timings is None else timings
+        with ThreadPoolExecutor(max_workers=max(1, int(workers))) as pool:
+            t0 = time.perf_counter()
+            audio = {}
+            for p, r in zip(todo, pool.map(_read_or_error, todo)):
+                if isinstance(r, BaseException):
+                    out[p] = r
+                    continue
+                refused = native_refusal(len(r[0]), r[1]) if native else None
+                if refused is not None:
+                    out[p] = refused
+                else:
+                    audio[p] = r
+            timings["read"] = timings.get("read", 0.0) + time.perf_counter() - t0
+            writes = []
+            for sr, keys in plan_passes([(p, sr, 1 + len(y) // hop_length) for p, (y, sr) in audio.items()], frame_budget):
+                try:
+                    res = analyse_batch([audio[p][0] for p in keys], sr, n_fft, hop_length, tracker=track_fn, ctx=ctx, want_env=False,
+                                        timings=timings)
+                except Exception as e:                            # noqa: BLE001 - the pass failed as a whole: each of its files did
+                    res = [e] * len(keys)
+                for p, r in zip(keys, res):
+                    y_len = len(audio.pop(p)[0])
+                    if isinstance(r, BaseException):
+                        out[p] = r
+                    else:
+                        _, f0, vmask, forms, knots = r
+                        writes.append((p, pool.submit(_write_features, features_path(p), knots, f0, vmask, forms, sr, y_len)))
+            t0 = time.perf_counter()
+            for p, fut in writes:
+                try:
+                    out[p] = fut.result()
+                except Exception as e:                            # noqa: BLE001
+                    out[p] = e
+            timings["write"] = timings.get("write", 0.0) + time.perf_counter() - t0
+    return {p: out[p] for p in order}

@@ -305,6 +305,26 @@ int goofer_knot_fit_error(goofer_ctx *ctx, const double *env, int ld64, const in
 int goofer_knot_gather(goofer_ctx *ctx, const double *env, int ld64, int64_t rows, const int32_t *knot_bin, int K,
                        uint16_t *knots_f16, void *stream);
 
+/* The envelope half of gf.extract_features (GOOFER.py:942-946) with compress_env_to_knots (GOOFER.py:97-147) for a ragged
+ * batch of fp32 signals y (device) at the plan's (sr, n_fft, hop): per signal gf.stft's T = 1 + n / hop frames (reflect-padded
+ * at its own ends), |S| + 1e-8, the sigma-2 bin blur in fp64, rounded to fp32, the sigma-0.5 blur in fp64, then the smallest
+ * knot count K of 32, 48, ..., 192 whose 2-tap lerp reproduces that envelope to < 1e-2 max relative error on the probe rows
+ * linspace(0, T - 1, min(256, T)) (else 192), and log(max(env, 1e-8)) at its knots' bins as fp16.  The arithmetic is that of
+ * goofer_mag_rows, goofer_gauss_bins_f64, goofer_knot_fit_error and goofer_knot_gather, bit for bit.
+ *   sample_off [n_signals+1], frame_off [n_signals+1]: HOST arrays; frame_off is written.  Every signal has >= 1 sample.
+ *   taps_env [2*radius_env+1], taps_fit [2*radius_fit+1]: fp64 taps of the two blurs in HOST memory (core.gaussian_taps).
+ *   hz_knots, knot_bin: fp32 knot frequencies and int32 nearest bins of the eleven candidates back to back (32 + 48 + ... + 192
+ *   = 1232 entries each) in HOST memory.
+ *   knots_f16 [frame_off[n] x 192] (device): signal s writes its [T_s x K_s] knots frames-major at frame_off[s] * 192.
+ *   K_out [n_signals] int32 (device).  env_rows (device, or NULL): the sigma-2 envelope in fp64, [frame_off[n] x ld64].
+ * Call once with y = NULL: frame_off and *scratch_bytes are filled in and no device code runs.  Then call with device scratch of
+ * at least that many bytes; it is in use until the stream reaches the end of the call.  The call synchronises the stream once,
+ * after uploading its tables and before its kernels. */
+int goofer_envelope_knots_batch(goofer_ctx *ctx, const float *y, const int64_t *sample_off, int n_signals, const double *taps_env,
+                                int radius_env, const double *taps_fit, int radius_fit, const float *hz_knots, const int32_t *knot_bin,
+                                int64_t *frame_off, uint16_t *knots_f16, int32_t *K_out, double *env_rows, int ld64, void *scratch,
+                                int64_t *scratch_bytes, void *stream);
+
 /* ---- f0 and formant tracks of the cold-cache analysis (goofer_amd/csrc/tracker.hip) -------------------------------
  * A ragged batch of fp64 signals y (device) at one sample rate sr in [8000, 96000]; sample_off[n_signals+1] and
  * frame_off[n_signals+1] are HOST arrays, frame_off is written by the call.  Call once with scratch = NULL (ctx may be NULL
