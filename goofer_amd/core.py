@@ -6,7 +6,7 @@ numpy arrays in, numpy arrays out) and error behaviour, but every array operatio
 runs in libgoofer_hip.so on the GPU.  Host code here only marshals: it never computes audio.
 
 Reference: GOOFER.py:355-413 (stft/istft), :473-554 (pulse train), :149-168 (knot decode),
-:971-1220 (synthesize).  Per-call overheads (H2D/D2H of one note) make this single-note surface a
+:971-1220 (synthesize).  Per-call overheads (H2D/D2H of one note) make the single-note surface a
 convenience; throughput comes from :func:`synthesize_batch`.
 """
 from __future__ import annotations
@@ -451,23 +451,6 @@ def subharm_from_kwargs(kw):
             "delay": kw.get("subharm_vibrato_delay", 0.1)}
 
 
-def _stretch(c, x, a, b, factor):
-    """concat(x[:a], stretch_feature(x[a:b], factor), x[b:]) along axis 0 of a device array (GOOFER.py:1019-1057)."""
-    n = x.shape[0]
-    a, b, _ = slice(a, b).indices(n)
-    b = max(a, b)
-    if b - a == 0:
-        raise ValueError("x cannot be empty")                   # what gf.interp1d raises for an empty stretch region
-    mid = c.stretch_rows(x[a:b], int((b - a) * factor))
-    if x.dim() == 1:
-        return torch.cat([x[:a], mid, x[b:]])
-    out = c.rows(a + mid.shape[0] + (n - b), x.shape[1])
-    out[:a].copy_(x[:a])
-    out[a:a + mid.shape[0]].copy_(mid)
-    out[a + mid.shape[0]:].copy_(x[b:])
-    return out
-
-
 def _stretch64(x, a, b, factor):
     """concat(x[:a], stretch_feature(x[a:b], factor), x[b:]) of a 1-D float32 array in the type the reference holds it in
     afterwards: FLOAT64 — its interp1d is np.interp on float64 abscissae (GOOFER.py:173-239, 597-606, 1019-1053).  None where
@@ -492,83 +475,328 @@ def _roughness_params(params, kw):
     return params
 
 
-def _finish(c, out, d_mask, n, sr, kw):
-    """The tail of gf.synthesize.  Without roughness the batch call has produced everything.  With it: the roughness layer on
-    the device (only `reconstruct` hears it), then peak and gain like the reference."""
-    if not kw.get("roughness_on"):
-        return tuple(out[k].cpu().numpy() for k in ("rec", "harm", "uv", "bre"))
+_SYNTH_CALL_ARGS = ("env_spec", "f0_interp", "voicing_mask", "y", "sr", "n_fft", "hop_length", "phi", "seed", "ctx")
+_NOTE_ARRAYS = ("env_spec", "f0_interp", "voicing_mask", "y")
+SYNTH_FRAME_BUDGET = 1 << 18      # STFT frames per synthesis pass (about 25 minutes of audio at 44.1 kHz, hop 256)
+
+
+def _synth_defaults():
+    """gf.synthesize's keyword arguments and their defaults (the notes' settings start from these)."""
+    global _SYNTH_DEFAULTS
+    if _SYNTH_DEFAULTS is None:
+        import inspect
+        _SYNTH_DEFAULTS = {k: v.default for k, v in inspect.signature(synthesize).parameters.items() if k not in _SYNTH_CALL_ARGS}
+    return _SYNTH_DEFAULTS
+
+
+_SYNTH_DEFAULTS = None
+
+
+def synth_pass_key(kw, has_phi=False, f64_missing=False):
+    """(strict, loose) pass key of a note with the merged keywords ``kw``: notes share a ``goofer_synth_batch`` pass when their
+    strict parts are equal and their loose parts compatible.  Strict: the route (time-stretched or not), injected phases,
+    noise_transition_smoothness, the sub-harmonic call settings and the volume jitter's form and speed — the last two only
+    for notes that use them, so they also keep the spectra route (sub-harmonic layer, volume jitter) apart from the walkers.
+    ``f64_missing``: a stretched note with f0 jitter or the sub-harmonic layer whose f0 stays float32 (a one-sample region).
+    Loose: f0_jitter_speed of a note with f0 jitter, None (fits any pass) otherwise."""
+    sub = None
+    if kw.get("add_subharm"):
+        st = np.atleast_1d(np.asarray(kw.get("subharm_semitones", -12), dtype=np.float64))
+        sub = (tuple(st.tolist()), bool(kw.get("subharm_vibrato", False)), float(kw.get("subharm_vibrato_rate", 6.0)),
+               float(kw.get("subharm_vibrato_depth", 0.1)), float(kw.get("subharm_vibrato_delay", 0.1)),
+               bool(kw.get("subharm_f0_jitter", 0) > 0.0))
+    vol = (bool(kw.get("volume_vibrato")), float(kw.get("volume_jitter_speed", 150))) if kw.get("volume_jitter") else None
+    strict = (bool(kw.get("stretch_factor", 1.0) != 1.0), bool(has_phi), float(kw.get("noise_transition_smoothness", 100)), sub, vol,
+              bool(f64_missing))
+    loose = float(kw.get("f0_jitter_speed", 100)) if kw.get("f0_jitter") else None
+    return strict, loose
+
+
+def plan_synth_passes(keys, frames, frame_budget=SYNTH_FRAME_BUDGET):
+    """Device passes of synthesize_batch: ``keys`` the notes' synth_pass_key (None: the note renders nothing), ``frames``
+    their STFT frame counts.  Inside a strict key, a note without f0 jitter joins the first f0 jitter speed of its group;
+    passes are then cut by ``frame_budget`` in note order (trackers.plan_keyed_passes).  Returns [[note index, ...], ...]."""
+    from .trackers import plan_keyed_passes
+    speeds = {}
+    for k in keys:
+        if k is not None and k[1] is not None:
+            speeds.setdefault(k[0], k[1])
+    entries = [(i, (k[0], k[1] if k[1] is not None else speeds.get(k[0])), int(f)) for i, (k, f) in enumerate(zip(keys, frames))
+               if k is not None]
+    return [idxs for _, idxs in plan_keyed_passes(entries, frame_budget)]
+
+
+def _empty4():
+    z = np.zeros(0, dtype=np.float32)
+    return z, z.copy(), z.copy(), z.copy()
+
+
+def _cut(length, a, b, factor):
+    """(a, b, stretched length) of concat(x[:a], stretch_feature(x[a:b], factor), x[b:]) on an axis of ``length``."""
+    a, b, _ = slice(a, b).indices(length)
+    b = max(a, b)
+    if b - a == 0:
+        raise ValueError("x cannot be empty")                   # what gf.interp1d raises for an empty stretch region
+    return a, b, int((b - a) * factor)
+
+
+def _rough_settings(kw, sr):
+    """The roughness layer's settings (GOOFER.py:901-940, 1195-1217): k and h lists as zip() pairs them, alpha, the two smoothing
+    sigmas, noise amplitude and high-pass corner."""
     k_list = list(kw.get("rough_k_list", (2, 3, 4)))
     h_list = kw.get("rough_h_list")
     if h_list is None:                                        # default partial weights: 0.45, 0.28, 0.18, then x 0.6 per further partial
         base = (0.45, 0.28, 0.18)
         h_list = [base[i] if i < 3 else base[2] * 0.6 ** (i - 2) for i in range(len(k_list))]
     k_list, h_list = k_list[:len(h_list)], list(h_list)[:len(k_list)]          # zip() of the reference
-    alpha = float(kw.get("rough_alpha", 0.6))
-    d_f0 = c.tensor(c.debug_fetch("f0")[:n])                  # f0_interp as the synthesis left it (scaled, stretched, jittered)
-    noises = []
-    for idx in range(len(k_list)):                            # make_smooth_noise re-seeds the LEGACY global generator
-        np.random.seed(1337 + idx)
-        noises.append(np.random.randn(n).astype(np.float32).astype(np.float64))
     sig_n = max(1.0, (float(kw.get("rough_noise_smooth_ms", 120.0)) * 0.001 * sr) / 6.0)
     sig_a = max(1.0, (float(kw.get("rough_alpha_slew_ms", 120.0)) * 0.001 * sr) / 6.0)
-    nz = c.gauss_rows_f64(c.tensor(np.stack(noises)), gaussian_taps(sig_n)) if noises else None
-    a_track = (d_mask.float() * np.float32(alpha)).double().reshape(1, n)      # alpha * vmask in fp32, filtered in fp64
-    a_slew = c.gauss_rows_f64(a_track, gaussian_taps(sig_a)).reshape(n).float()
-    rough = c.vocal_roughness(out["harm"], d_f0, d_mask, nz, k_list, h_list, float(kw.get("rough_noise_amp", 0.6)),
-                              float(kw.get("rough_hp_fc", 320.0)), a_slew)
-    harm, uv, bre = (out[k].cpu().numpy() for k in ("harm", "uv", "bre"))
-    combined = rough.cpu().numpy() + uv + bre
-    peak = float(np.max(np.abs(combined)) + 1e-12)
-    gain = (1.0 / peak) ** float(np.clip(kw.get("normalize", 1.0), 0.0, 1.0))
-    return combined * np.float32(gain), harm * np.float32(gain), uv * np.float32(gain), bre * np.float32(gain)
+    return (tuple(float(v) for v in k_list), tuple(float(v) for v in h_list), float(kw.get("rough_alpha", 0.6)), sig_n, sig_a,
+            float(kw.get("rough_noise_amp", 0.6)), float(kw.get("rough_hp_fc", 320.0)))
 
 
-def _synthesize_stretched(c, d_env, f0, mask, F, params, sr, hop, phi, seed, kw):
-    """gf.synthesize with stretch_factor != 1 (GOOFER.py:1019-1067): the warped envelope and the blurred noise envelope
-    are made first, then both, f0 (already scaled by pitch_shift) and the mask are resampled along time, and the
-    synth runs on the stretched features with its in-kernel warps and blur switched off."""
-    factor = float(kw["stretch_factor"])
-    f_shift = [kw.get("F%d_shift" % i, 1.0) for i in (1, 2, 3, 4)]
-    fs = float(kw.get("formant_shift", 1.0))
-    env_n = c.gauss_bins(d_env, gaussian_taps(1.75))
-    env_h = d_env
-    if any(v != 1.0 for v in f_shift) or fs != 1.0:
-        env_h = c.warp_bins(d_env, c.tensor(F), f_shift if any(v != 1.0 for v in f_shift) else None, fs)
-    f0 = (f0 * np.float32(kw.get("pitch_shift", 1.0))).astype(np.float32) if kw.get("pitch_shift", 1.0) != 1.0 else f0
-    d_f0, d_mask = c.tensor(f0), c.tensor(mask)
-    s0, s1 = kw.get("start_sec"), kw.get("end_sec")
-    if s0 is not None and s1 is not None:
-        a, b = int(s0 * sr), int(s1 * sr)
-        fa, fb = int((s0 * sr) / hop), int((s1 * sr) / hop)
-    else:
-        a, b, fa, fb = 0, None, 0, None
-    # f0_interp is a float64 array from here on in the reference: the jitter's product and the sub-harmonic phase trackers work on
-    # it (their float32 versions land one event in ~10^5 a sample off, which a soak run of random keyword sets found)
-    f0_64 = _stretch64(f0, a, b, factor) if (kw.get("f0_jitter") or kw.get("add_subharm")) else None
-    d_f0, d_mask = _stretch(c, d_f0, a, b, factor), _stretch(c, d_mask, a, b, factor)
-    env_h, env_n = _stretch(c, env_h, fa, fb, factor), _stretch(c, env_n, fa, fb, factor)
-    n = int(d_f0.numel())
-    d_f0_64 = c.tensor(f0_64) if f0_64 is not None and f0_64.size == n else None
+def _prepare_note(c, note, kw, seed, phi, sr, n_fft, hop):
+    """Everything gf.synthesize does for one note before the device renders it, in its order: the checks that make it raise,
+    the fresh Philox key, then the legacy-RNG draws (f0, sub-harmonic, harmonic volume, breath volume jitter, then the
+    roughness noises re-seeded 1337 + idx).  Returns the note's job, or the four empty stems of a note with no samples."""
+    env_spec = note["env_spec"]
+    if isinstance(env_spec, dict) and env_spec.get("mode") == "knots":
+        env_spec = decode_env_from_knots(env_spec, ctx=c)
+        c.plan(sr, n_fft, hop)
+    env = np.asarray(env_spec)
+    if env.dtype not in (np.float32, np.float64):
+        env = env.astype(np.float32)                          # to_compute (fp64 is rounded on the device, the same bits)
+    n = len(note["y"])
+    f0 = np.asarray(note["f0_interp"], dtype=np.float32)
+    mask = np.asarray(note["voicing_mask"], dtype=np.float32)
     if n == 0:
-        z = np.zeros(0, dtype=np.float32)
-        return z, z.copy(), z.copy(), z.copy()
-    params = _roughness_params(params, kw).copy()
-    params["pitch_shift"], params["formant_shift"], params["f_shift"] = 1.0, 1.0, [1.0, 1.0, 1.0, 1.0]
-    d_phi = None
+        return _empty4()
+    if f0.ndim != 1 or mask.ndim != 1:
+        raise ValueError("f0_interp and voicing_mask must be 1-D arrays")
+    T_env = env.shape[1]
+    if env.ndim != 2 or env.shape[0] != c.n_bins:
+        raise ValueError(f"env_spec must be [{c.n_bins}, frames] for n_fft {n_fft}, got {list(env.shape)}")
+    fm = formants_to_int_keys(kw.get("formants"))
+    F = np.stack([_fit(fm[i], T_env) for i in (1, 2, 3, 4)], axis=1)           # [T_env, 4] fp64
+    params = _roughness_params(note_params_from_kwargs(1, **kw), kw)
+    job = {"kw": kw, "env": env, "T_env": T_env, "F": F, "f64_missing": False}
+    if kw.get("stretch_factor", 1.0) != 1.0:
+        # gf.synthesize with stretch_factor != 1 (GOOFER.py:1019-1067): the envelope is warped and its blurred noise copy made
+        # first, then both, f0 (already scaled by pitch_shift) and the mask are resampled along time; the synth runs on the
+        # stretched features with its in-kernel warps and blur switched off
+        factor = float(kw["stretch_factor"])
+        f_shift = [kw.get("F%d_shift" % i, 1.0) for i in (1, 2, 3, 4)]
+        ps = kw.get("pitch_shift", 1.0)
+        f0 = (f0 * np.float32(ps)).astype(np.float32) if ps != 1.0 else f0
+        s0, s1 = kw.get("start_sec"), kw.get("end_sec")
+        if s0 is not None and s1 is not None:
+            a, b = int(s0 * sr), int(s1 * sr)
+            fa, fb = int((s0 * sr) / hop), int((s1 * sr) / hop)
+        else:
+            a, b, fa, fb = 0, None, 0, None
+        # f0_interp is a float64 array from here on in the reference: the jitter's product and the sub-harmonic phase trackers work on
+        # it (their float32 versions land one event in ~10^5 a sample off, which a soak run of random keyword sets found)
+        needs64 = bool(kw.get("f0_jitter") or kw.get("add_subharm"))
+        f0_64 = _stretch64(f0, a, b, factor) if needs64 else None
+        s_cut, _, e_cut = _cut(len(f0), a, b, factor), _cut(len(mask), a, b, factor), _cut(T_env, fa, fb, factor)
+        n = s_cut[0] + s_cut[2] + len(f0) - s_cut[1]
+        if n == 0:
+            return _empty4()
+        if len(mask) != len(f0):                              # (the ragged stretch cuts both on one sample axis)
+            raise ValueError("f0_interp and voicing_mask must have the same length")
+        f0_64 = f0_64 if f0_64 is not None and f0_64.size == n else None
+        params = params.copy()
+        params["pitch_shift"], params["formant_shift"], params["f_shift"] = 1.0, 1.0, [1.0, 1.0, 1.0, 1.0]
+        job.update(stretched=True, f0=f0, mask=mask, s_cut=s_cut[:2], e_cut=e_cut[:2], rows_out=e_cut[0] + e_cut[2] + T_env - e_cut[1],
+                   f_shift=f_shift, ratio=float(kw.get("formant_shift", 1.0)), anchor=any(v != 1.0 for v in f_shift),
+                   f0_64=f0_64, f64_missing=needs64 and f0_64 is None)
+    else:
+        if len(f0) < n or len(mask) < n:
+            raise ValueError(f"f0_interp and voicing_mask need len(y) = {n} samples")
+        job.update(stretched=False, f0=f0[:n], mask=mask[:n], rows_out=T_env)
+    job["n"] = n
+    frames = 1 + n // hop
     if phi is not None:
-        d_phi = c.rows_from(np.asarray(phi, dtype=np.float32).T)
+        phi = np.asarray(phi)
+        if phi.dtype not in (np.float32, np.float64):
+            phi = phi.astype(np.float32)
+        if phi.shape != (c.n_bins, frames):
+            raise ValueError(f"phi must be [{c.n_bins}, {frames}] for this note, got {list(phi.shape)}")
+    job.update(phi=phi, frames=frames, params=params)
     if seed is None:
         seed = int(np.random.SeedSequence().generate_state(1, dtype=np.uint64)[0])
-    noise_f0 = c.tensor(np.random.randn(n)) if kw.get("f0_jitter") else None
-    noise_sub = c.tensor(np.random.randn(n)) if kw.get("add_subharm") and kw.get("subharm_f0_jitter", 0) > 0.0 else None
-    vib = bool(kw.get("volume_jitter") and kw.get("volume_vibrato"))
-    noise_vol = (c.tensor(np.random.randn(n)), c.tensor(np.random.randn(n))) if kw.get("volume_jitter") and not vib else None
-    out = c.synth_batch(env_h, [env_h.shape[0]], d_f0, d_mask, [n], params, formants=None, phi=d_phi, seed=seed,
+    job["seed"] = int(seed) & 0xFFFFFFFFFFFFFFFF
+    # jitter flags draw from the legacy global np.random stream in the reference's order: f0, sub-harmonic, harm volume, breath volume
+    job["noise_f0"] = np.random.randn(n) if kw.get("f0_jitter") else None
+    job["noise_sub"] = np.random.randn(n) if kw.get("add_subharm") and kw.get("subharm_f0_jitter", 0) > 0.0 else None
+    vib = bool(kw.get("volume_jitter") and kw.get("volume_vibrato"))          # the sinusoid variant draws nothing
+    job["noise_vol"] = (np.random.randn(n), np.random.randn(n)) if kw.get("volume_jitter") and not vib else None
+    job["rough"] = None
+    if kw.get("roughness_on"):
+        rs = _rough_settings(kw, sr)
+        noises = []
+        for idx in range(len(rs[0])):                         # make_smooth_noise re-seeds the LEGACY global generator
+            np.random.seed(1337 + idx)
+            noises.append(np.random.randn(n).astype(np.float32).astype(np.float64))
+        job["rough"] = (rs, noises)
+    return job
+
+
+def _concat(arrs, dtype):
+    return np.concatenate([np.ascontiguousarray(a, dtype=dtype).ravel() for a in arrs]) if arrs else np.zeros(0, dtype=dtype)
+
+
+def _noise(c, js, key, part=None):
+    """One fp64 device array of a jitter's draws for the pass (zeros for the notes without that jitter), or None."""
+    if not any(j[key] is not None for j in js):
+        return None
+    return c.tensor(np.concatenate([(j[key] if part is None else j[key][part]) if j[key] is not None else np.zeros(j["n"])
+                                    for j in js]))
+
+
+def _ingest(c, arrays, lengths):
+    """ld-strided fp32 rows of [bins, T] host arrays, one upload and one goofer_ingest_rows launch."""
+    dt = np.float64 if any(a.dtype == np.float64 for a in arrays) else np.float32
+    return c.ingest_rows(c.tensor(_concat(arrays, dt)), lengths, c.n_bins)
+
+
+def _run_pass(c, js, sr):
+    """One goofer_synth_batch for the jobs of a pass (and, for the time-stretched route, the ragged warp, blur and stretch in
+    front of it).  Returns (host stems {rec, harm, uv, bre}, sample offsets)."""
+    env_lens = [j["T_env"] for j in js]
+    lens = [j["n"] for j in js]
+    kw = js[0]["kw"]
+    d_env = _ingest(c, [j["env"] for j in js], env_lens)
+    d_phi = _ingest(c, [j["phi"] for j in js], [j["frames"] for j in js]) if js[0]["phi"] is not None else None
+    params = c._c_params(np.concatenate([j["params"] for j in js]))
+    seeds = np.array([j["seed"] for j in js], dtype=np.uint64)
+    params["seed"][:, 0] = (seeds & np.uint64(0xFFFFFFFF)).astype(np.uint32)    # the kernels XOR it with the batch seed 0: each
+    params["seed"][:, 1] = (seeds >> np.uint64(32)).astype(np.uint32)            # note's key is the key of its single call
+    F = c.tensor(np.concatenate([j["F"] for j in js]))
+    fm = c.tensor(_concat([j["f0"] for j in js] + [j["mask"] for j in js], np.float32))
+    n_in = fm.numel() // 2
+    d_f0, d_mask = fm[:n_in], fm[n_in:]
+    jit = next((j["kw"] for j in js if j["kw"].get("f0_jitter")), kw)
+    sub = next((j["kw"] for j in js if j["kw"].get("add_subharm")), None)
+    vol = next((j["kw"] for j in js if j["kw"].get("volume_jitter")), kw)
+    vib = bool(vol.get("volume_jitter") and vol.get("volume_vibrato"))
+    extra = {}
+    if js[0]["stretched"]:
+        env_n = c.gauss_bins(d_env, gaussian_taps(1.75))
+        env_h = d_env
+        if any(j["anchor"] or j["ratio"] != 1.0 for j in js):
+            env_h = c.warp_bins_ragged(d_env, env_lens, F, [j["f_shift"] for j in js], [j["ratio"] for j in js], [j["anchor"] for j in js])
+        env_h, env_n, d_f0, d_mask = c.stretch_ragged(env_h, env_n, env_lens, [j["e_cut"] for j in js], [j["rows_out"] for j in js],
+                                                      d_f0, d_mask, [len(j["f0"]) for j in js], [j["s_cut"] for j in js], lens)
+        d_env, F, env_lens = env_h, None, [j["rows_out"] for j in js]
+        extra["env_noise"] = env_n
+        if any(j["f0_64"] is not None for j in js):
+            # the fp64 f0 of the notes with jitter or the sub-harmonic layer; the others hold their (exact) fp32 values widened
+            f64 = d_f0.double()
+            off = c.offsets(lens)
+            idx = np.concatenate([np.arange(off[i], off[i + 1]) for i, j in enumerate(js) if j["f0_64"] is not None])
+            f64[c.tensor(idx)] = c.tensor(np.concatenate([j["f0_64"] for j in js if j["f0_64"] is not None]))
+            extra["f0_64"] = f64
+    out = c.synth_batch(d_env, env_lens, d_f0, d_mask, lens, params, formants=F, phi=d_phi, seed=0,
                         transition_sigma=float(kw.get("noise_transition_smoothness", 100)), want_mix=False,
-                        noise_f0=noise_f0, noise_vol=noise_vol, f0_jitter_speed=float(kw.get("f0_jitter_speed", 100)),
-                        vol_jitter_speed=float(kw.get("volume_jitter_speed", 150)), subharm=subharm_from_kwargs(kw),
-                        volume_vibrato=vib, env_noise=env_n, noise_subharm=noise_sub, f0_64=d_f0_64)
-    return _finish(c, out, d_mask, n, sr, kw)
+                        noise_f0=_noise(c, js, "noise_f0"),
+                        noise_vol=(_noise(c, js, "noise_vol", 0), _noise(c, js, "noise_vol", 1)) if any(j["noise_vol"] is not None for j in js) else None,
+                        f0_jitter_speed=float(jit.get("f0_jitter_speed", 100)), vol_jitter_speed=float(vol.get("volume_jitter_speed", 150)),
+                        subharm=subharm_from_kwargs(sub) if sub is not None else None, volume_vibrato=vib,
+                        noise_subharm=_noise(c, js, "noise_sub"), **extra)
+    s_off = out["sample_off"]
+    rough = _roughness(c, js, out, d_mask, s_off, sr) if any(j["rough"] is not None for j in js) else {}
+    host = {k: out[k].cpu().numpy() for k in ("rec", "harm", "uv", "bre")}
+    return host, s_off, rough
+
+
+def _roughness(c, js, out, d_mask, s_off, sr):
+    """gf.synthesize's roughness_on layer for the pass's notes that have it (only `reconstruct` hears it, GOOFER.py:1195-1217):
+    one goofer_gauss_rows_f64 pair and one goofer_vocal_roughness per distinct setting, f0 as the synthesis left it from one
+    fetch.  Returns {note position in the pass: roughened harmonic stem (host)}."""
+    f0_all = c.debug_fetch("f0")                               # f0_interp as the synthesis left it (scaled, stretched, jittered)
+    groups = {}
+    for i, j in enumerate(js):
+        if j["rough"] is not None:
+            groups.setdefault(j["rough"][0], []).append(i)
+    res = {}
+    for (k_list, h_list, alpha, sig_n, sig_a, amp, fc), idxs in groups.items():
+        sl = [slice(int(s_off[i]), int(s_off[i + 1])) for i in idxs]
+        lens = [js[i]["n"] for i in idxs]
+        cat = lambda t: torch.cat([t[s] for s in sl]) if len(sl) > 1 else t[sl[0]].contiguous()    # noqa: E731
+        harm, mask = cat(out["harm"]), cat(d_mask)
+        d_f0 = c.tensor(np.concatenate([f0_all[s] for s in sl]))
+        nz = None
+        if k_list:                                            # [n_k, N]: noise k of every note back to back, one ragged row each
+            flat = np.concatenate([js[i]["rough"][1][k] for k in range(len(k_list)) for i in idxs])
+            nz = c.gauss_rows_f64(c.tensor(flat), gaussian_taps(sig_n), lengths=lens * len(k_list)).reshape(len(k_list), -1)
+        a_track = (mask.float() * np.float32(alpha)).double().contiguous()      # alpha * vmask in fp32, filtered in fp64
+        a_slew = c.gauss_rows_f64(a_track, gaussian_taps(sig_a), lengths=lens).float()
+        rough = c.vocal_roughness(harm, d_f0, mask, nz, list(k_list), list(h_list), amp, fc, a_slew, lengths=lens).cpu().numpy()
+        o = np.concatenate([[0], np.cumsum(lens)])
+        for q, i in enumerate(idxs):
+            res[i] = rough[o[q]:o[q + 1]]
+    return res
+
+
+def synthesize_batch(notes, sr, n_fft=1024, hop_length=256, *, seeds=None, phis=None, ctx=None, **kw):
+    """gf.synthesize for many notes in batched device passes -> one (reconstruct, harmonic, aper_uv, aper_bre) fp32 tuple per
+    note, or the exception that note's ``synthesize`` call raises (an empty stretch region, more than sixteen sub-harmonic
+    ratios, a non-1-D f0 or mask, ...).
+
+    ``notes``: mappings with ``env_spec`` ([bins, T] fp32 / fp64 array or a knots dict), ``f0_interp``, ``voicing_mask`` and
+    ``y`` (only its length is used), plus any ``synthesize`` keyword, which overrides ``**kw`` for that note.  One geometry
+    (``sr``, ``n_fft``, ``hop_length``) per call.  ``seeds``: one Philox key per note (None entries or ``seeds=None``: a
+    fresh key each, like ``synthesize(seed=None)``); ``phis``: one injected [bins, T] phase array (or None) per note.
+
+    Result i equals ``synthesize(**notes[i] merged over kw, sr=sr, ..., seed=seeds[i], phi=phis[i])`` bit for bit, and the
+    legacy ``np.random`` state afterwards equals its state after those calls in list order: every host draw is made in
+    note order before any device work.  Notes are cut into passes by ``synth_pass_key`` / ``plan_synth_passes``.  The
+    returned arrays may be views into one host block per stem and pass: copy before writing in place.  An unknown keyword
+    or ``seeds`` / ``phis`` of the wrong length raise before anything is drawn or launched; a note with ``len(y) == 0``
+    gives four empty arrays."""
+    notes = list(notes)
+    defaults = _synth_defaults()
+    for name in list(kw) + [k for note in notes for k in note if k not in _NOTE_ARRAYS]:
+        if name not in defaults:
+            raise TypeError(f"synthesize() got an unexpected keyword argument '{name}'")
+    for note in notes:
+        missing = [k for k in _NOTE_ARRAYS if k not in note]
+        if missing:
+            raise TypeError(f"synthesize() missing required argument '{missing[0]}'")
+    n = len(notes)
+    seeds = [None] * n if seeds is None else list(seeds)
+    phis = [None] * n if phis is None else list(phis)
+    if len(seeds) != n or len(phis) != n:
+        raise ValueError(f"synthesize_batch: {n} notes, {len(seeds)} seeds and {len(phis)} phase arrays")
+    c = _ctx(sr, n_fft, hop_length, ctx)
+    base = {**defaults, **kw}
+    results, jobs = [None] * n, [None] * n
+    for i, note in enumerate(notes):
+        merged = {**base, **{k: v for k, v in note.items() if k not in _NOTE_ARRAYS}}
+        try:
+            r = _prepare_note(c, note, merged, seeds[i], phis[i], sr, n_fft, hop_length)
+        except Exception as e:                                  # the note's own refusal: its slot, the others render
+            results[i] = e
+            continue
+        if isinstance(r, tuple):
+            results[i] = r
+        else:
+            jobs[i] = r
+    keys = [synth_pass_key(j["kw"], j["phi"] is not None, j["f64_missing"]) if j is not None else None for j in jobs]
+    for idxs in plan_synth_passes(keys, [j["frames"] if j is not None else 0 for j in jobs]):
+        js = [jobs[i] for i in idxs]
+        host, s_off, rough = _run_pass(c, js, sr)
+        for q, i in enumerate(idxs):
+            s = slice(int(s_off[q]), int(s_off[q + 1]))
+            rec, harm, uv, bre = (host[k][s] for k in ("rec", "harm", "uv", "bre"))
+            if q in rough:                                    # the peak gain of the roughened sum, like the reference
+                combined = rough[q] + uv + bre
+                peak = float(np.max(np.abs(combined)) + 1e-12)
+                gain = (1.0 / peak) ** float(np.clip(js[q]["kw"].get("normalize", 1.0), 0.0, 1.0))
+                rec, harm, uv, bre = combined * np.float32(gain), harm * np.float32(gain), uv * np.float32(gain), bre * np.float32(gain)
+            results[i] = (rec, harm, uv, bre)
+    return results
 
 
 def synthesize(env_spec, f0_interp, voicing_mask, y, sr, n_fft=1024, hop_length=256, glottal_smoothing=False,
@@ -581,47 +809,16 @@ def synthesize(env_spec, f0_interp, voicing_mask, y, sr, n_fft=1024, hop_length=
                F3_shift=1.0, F4_shift=1.0, formants=None, roughness_on=False, rough_k_list=(2, 3, 4), rough_h_list=None,
                rough_alpha=0.6, rough_hp_fc=320.0, rough_noise_amp=0.6, rough_noise_smooth_ms=120.0, rough_alpha_slew_ms=120.0,
                *, phi=None, seed=None, ctx=None):
-    """gf.synthesize for one note on the GPU -> (reconstruct, harmonic, aper_uv, aper_bre), fp32.
+    """gf.synthesize for one note on the GPU -> (reconstruct, harmonic, aper_uv, aper_bre), fp32: synthesize_batch of this
+    one note.
 
     The positional order and keyword set are the reference's (GOOFER.py:971-983; ``glottal_smoothing`` is accepted and
     unused there too); an unknown keyword raises TypeError like it does there.  Three keyword-ONLY additions:
     ``phi`` ``[bins, T]`` injects the aperiodic branch's random phases (parity runs); otherwise the device draws them
     from Philox keyed by ``seed`` (a fresh key per call when None, like the reference's unseeded generator); ``ctx``
     picks the device context."""
-    kw = {k: v for k, v in locals().items() if k not in ("env_spec", "f0_interp", "voicing_mask", "y", "sr", "n_fft", "hop_length",
-                                                         "phi", "seed", "ctx")}
-    c = _ctx(sr, n_fft, hop_length, ctx)
-    if isinstance(env_spec, dict) and env_spec.get("mode") == "knots":
-        env_spec = decode_env_from_knots(env_spec, ctx=c)
-        c.plan(sr, n_fft, hop_length)
-    env = np.asarray(env_spec, dtype=np.float32)
-    n = len(y)
-    f0 = np.asarray(f0_interp, dtype=np.float32)
-    mask = np.asarray(voicing_mask, dtype=np.float32)
-    if n == 0:
-        z = np.zeros(0, dtype=np.float32)
-        return z, z.copy(), z.copy(), z.copy()
-    T_env = env.shape[1]
-    fm = formants_to_int_keys(kw.get("formants"))
-    F = np.stack([_fit(fm[i], T_env) for i in (1, 2, 3, 4)], axis=1)           # [T_env, 4] fp64
-    params = _roughness_params(note_params_from_kwargs(1, **kw), kw)
-    d_env = c.rows_from(env.T)
-    if kw.get("stretch_factor", 1.0) != 1.0:
-        return _synthesize_stretched(c, d_env, f0, mask, F, params, sr, hop_length, phi, seed, kw)
-    d_phi = None
-    if phi is not None:
-        d_phi = c.rows_from(np.asarray(phi, dtype=np.float32).T)
-    if seed is None:
-        seed = int(np.random.SeedSequence().generate_state(1, dtype=np.uint64)[0])
-    # jitter flags draw from the legacy global np.random stream in the reference's order: f0, harm volume, breath volume
-    noise_f0 = c.tensor(np.random.randn(n)) if kw.get("f0_jitter") else None
-    noise_sub = c.tensor(np.random.randn(n)) if kw.get("add_subharm") and kw.get("subharm_f0_jitter", 0) > 0.0 else None
-    vib = bool(kw.get("volume_jitter") and kw.get("volume_vibrato"))          # the sinusoid variant draws nothing
-    noise_vol = (c.tensor(np.random.randn(n)), c.tensor(np.random.randn(n))) if kw.get("volume_jitter") and not vib else None
-    d_mask = c.tensor(mask[:n])
-    out = c.synth_batch(d_env, [T_env], c.tensor(f0[:n]), d_mask, [n], params, formants=c.tensor(F),
-                        phi=d_phi, seed=seed, transition_sigma=float(kw.get("noise_transition_smoothness", 100)),
-                        want_mix=False, noise_f0=noise_f0, noise_vol=noise_vol,
-                        f0_jitter_speed=float(kw.get("f0_jitter_speed", 100)), vol_jitter_speed=float(kw.get("volume_jitter_speed", 150)),
-                        subharm=subharm_from_kwargs(kw), volume_vibrato=vib, noise_subharm=noise_sub)
-    return _finish(c, out, d_mask, n, sr, kw)
+    note = {k: v for k, v in locals().items() if k not in ("sr", "n_fft", "hop_length", "phi", "seed", "ctx")}
+    res = synthesize_batch([note], sr, n_fft, hop_length, seeds=[seed], phis=[phi], ctx=ctx)[0]
+    if isinstance(res, BaseException):
+        raise res
+    return res

@@ -88,6 +88,12 @@ int launch_vocal_roughness(goofer_ctx *, const float *, const float *, const flo
                            double, double, const float *, const int64_t *, int, int64_t, float *, hipStream_t);
 int launch_lerp_axis0(goofer_ctx *, const float *, int64_t, int64_t, float *, int64_t, int64_t, int, hipStream_t);
 int launch_lerp_1d(goofer_ctx *, const float *, int64_t, float *, int64_t, hipStream_t);
+int launch_ingest_rows(goofer_ctx *, const void *, int, const int64_t *, const int64_t *, int, int64_t, int, float *, int, hipStream_t);
+int launch_warp_bins_ragged(goofer_ctx *, const float *, float *, int64_t, int, int, const double *, const int64_t *, int, const double *,
+                            hipStream_t);
+int launch_stretch_ragged(goofer_ctx *, const int64_t *, const int64_t *, const int64_t *, const int64_t *, const int64_t *, const int64_t *,
+                          int, int64_t, int64_t, int, int, const float *, const float *, float *, float *, const float *, const float *,
+                          float *, float *, hipStream_t);
 int launch_stem_peak(goofer_ctx *, const float *, const float *, const float *, const int64_t *, int, int64_t, float *, hipStream_t);
 int launch_stem_gains(goofer_ctx *, float *, float *, float *, const double *, const int64_t *, int, int64_t,
                       const goofer_note_params *, float *, double *, hipStream_t);
@@ -1307,6 +1313,44 @@ int goofer_stretch_rows(goofer_ctx *ctx, const float *in, int64_t ld_in, int64_t
     if (!in || !out) return goofer_fail(ctx, GOOFER_EINVAL, "null pointer");
     if (n_cols == 1 && ld_in == 1 && ld_out == 1) return launch_lerp_1d(ctx, in, rows_in, out, rows_out, (hipStream_t)stream);
     return launch_lerp_axis0(ctx, in, ld_in, rows_in, out, ld_out, rows_out, n_cols, (hipStream_t)stream);
+}
+
+int goofer_ingest_rows(goofer_ctx *ctx, const void *in, int in_f64, const int64_t *row_off, const int64_t *tile_off, int n_notes,
+                       int64_t total_tiles, int n_cols, float *out, int ld, void *stream)
+{
+    if (!ctx) return GOOFER_EINVAL;
+    if (n_notes <= 0 || total_tiles <= 0) return GOOFER_OK;
+    if (!in || !row_off || !tile_off || !out) return goofer_fail(ctx, GOOFER_EINVAL, "null pointer");
+    if (n_cols <= 0 || ld < n_cols) return goofer_fail(ctx, GOOFER_EINVAL, "ingest: %d columns with row stride %d", n_cols, ld);
+    return launch_ingest_rows(ctx, in, in_f64 != 0, row_off, tile_off, n_notes, total_tiles, n_cols, out, ld, (hipStream_t)stream);
+}
+
+int goofer_warp_bins_ragged(goofer_ctx *ctx, const float *in, float *out, int64_t rows, int n_bins, int ld, const double *formants,
+                            const int64_t *row_off, int n_notes, const double *note_args, void *stream)
+{
+    NEED_PLAN(ctx);
+    if (rows <= 0 || n_notes <= 0) return GOOFER_OK;
+    if (!in || !out || !row_off || !note_args) return goofer_fail(ctx, GOOFER_EINVAL, "null pointer");
+    if (n_bins != ctx->plan.n_bins || ld < n_bins) return goofer_fail(ctx, GOOFER_EINVAL, "ragged warp: %d bins, the plan has %d", n_bins, ctx->plan.n_bins);
+    return launch_warp_bins_ragged(ctx, in, out, rows, n_bins, ld, formants, row_off, n_notes, note_args, (hipStream_t)stream);
+}
+
+int goofer_stretch_ragged(goofer_ctx *ctx, const int64_t *row_off_in, const int64_t *row_off_out, const int64_t *row_cut,
+                          const int64_t *sample_off_in, const int64_t *sample_off_out, const int64_t *sample_cut, int n_notes,
+                          int64_t rows_out, int64_t samples_out, int n_cols, int ld, const float *env_h, const float *env_n,
+                          float *env_h_out, float *env_n_out, const float *f0, const float *mask, float *f0_out, float *mask_out,
+                          void *stream)
+{
+    if (!ctx) return GOOFER_EINVAL;
+    if (n_notes <= 0) return GOOFER_OK;
+    if (!row_off_in || !row_off_out || !row_cut || !sample_off_in || !sample_off_out || !sample_cut)
+        return goofer_fail(ctx, GOOFER_EINVAL, "null pointer");
+    if (rows_out > 0 && (!env_h || !env_n || !env_h_out || !env_n_out || n_cols <= 0 || ld < n_cols))
+        return goofer_fail(ctx, GOOFER_EINVAL, "ragged stretch: envelope rows without matrices");
+    if (samples_out > 0 && (!f0 || !mask || !f0_out || !mask_out)) return goofer_fail(ctx, GOOFER_EINVAL, "ragged stretch: samples without arrays");
+    return launch_stretch_ragged(ctx, row_off_in, row_off_out, row_cut, sample_off_in, sample_off_out, sample_cut, n_notes, rows_out,
+                                 samples_out, n_cols, ld, env_h, env_n, env_h_out, env_n_out, f0, mask, f0_out, mask_out,
+                                 (hipStream_t)stream);
 }
 
 int goofer_gauss_rows_f64(goofer_ctx *ctx, const double *in, const int64_t *row_off, int n_rows, int64_t total, const double *taps,

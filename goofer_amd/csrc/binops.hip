@@ -108,6 +108,49 @@ int launch_warp_bins(goofer_ctx *ctx, const float *in, float *out, int64_t rows,
     return GOOFER_OK;
 }
 
+// The same warp for a ragged batch of notes with settings of their own (gf.synthesize's time stretch warps before it
+// stretches, GOOFER.py:1004-1017): row r belongs to the note of row_off (device CSR [n_notes + 1]); note_args [n_notes x 6]
+// fp64 holds f_shift[4], the uniform ratio and the anchor switch (0: no anchor warp, as goofer_warp_bins' f_shift == NULL —
+// distinct from four ones).  Per note the bits of goofer_warp_bins: both kernels are warp_row.
+__global__ __launch_bounds__(256) void k_warp_bins_ragged(const float *__restrict__ in, float *__restrict__ out, int64_t rows,
+                                                          int n_bins, int ld, const double *__restrict__ formants,
+                                                          const int64_t *__restrict__ row_off, int n_notes,
+                                                          const double *__restrict__ note_args, const warp_grid grid)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    __shared__ double s_seg[ROWS_PER_BLOCK][WARP_SEG_DOUBLES];
+    float *s_all = reinterpret_cast<float *>(smem);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * ROWS_PER_BLOCK + wave;
+    if (row >= rows) return;                       // no block-level barrier below
+    int lo = 0, hi = n_notes;                      // the note: largest i with row_off[i] <= row
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (row_off[mid] <= row) lo = mid; else hi = mid;
+    }
+    float *ra = s_all + (2 * wave) * (n_bins + 1);
+    float *rb = ra + n_bins + 1;
+    for (int b = lane; b < n_bins; b += WAVE) ra[b] = in[row * ld + b];
+    wave_lds_sync();
+    const double *a = note_args + 6 * lo;
+    double fs[4] = {a[0], a[1], a[2], a[3]};
+    float *cur = warp_row(ra, rb, n_bins, grid, formants ? formants + row * 4 : nullptr, fs, a[5] != 0.0, a[4], lane, s_seg[wave]);
+    for (int b = lane; b < n_bins; b += WAVE) out[row * ld + b] = cur[b];
+}
+
+int launch_warp_bins_ragged(goofer_ctx *ctx, const float *in, float *out, int64_t rows, int n_bins, int ld, const double *formants,
+                            const int64_t *row_off, int n_notes, const double *note_args, hipStream_t st)
+{
+    if (rows <= 0 || n_notes <= 0) return GOOFER_OK;
+    const int64_t blocks = (rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK;
+    if (blocks > 0x7fffffffLL) return goofer_fail(ctx, GOOFER_EINVAL, "ragged warp: %lld rows in one call", (long long)rows);
+    size_t lds = sizeof(float) * 2 * ROWS_PER_BLOCK * (n_bins + 1);
+    hipLaunchKernelGGL(k_warp_bins_ragged, dim3((unsigned)blocks), dim3(256), lds, st, in, out, rows, n_bins, ld, formants, row_off,
+                       n_notes, note_args, make_warp_grid(ctx->plan.sr, n_bins));
+    LAUNCH_CHECK(ctx);
+    return GOOFER_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // env[row][b] = exp(w0[b]*knot[idx[b]] + w1[b]*knot[idx[b]+1]); the reference's dense W @ knots
 // has exactly these two non-zeros per row.

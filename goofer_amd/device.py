@@ -335,15 +335,97 @@ class Context:
         r.copy_(torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)))
         return r
 
-    def gauss_rows_f64(self, x, taps: np.ndarray):
-        """gf.gaussian_filter1d along the last axis of an fp64 [rows, L] device tensor (each row its own reflect padding)."""
+    def gauss_rows_f64(self, x, taps: np.ndarray, lengths=None):
+        """gf.gaussian_filter1d along the last axis of an fp64 [rows, L] device tensor (each row its own reflect padding).
+        ``lengths``: ragged rows instead — a contiguous fp64 tensor of sum(lengths) values, row r the next lengths[r] of them."""
         taps = np.ascontiguousarray(taps, dtype=np.float64)
-        rows, L = x.shape
-        off = self.tensor(np.arange(rows + 1, dtype=np.int64) * L)
+        if lengths is None:
+            rows, L = x.shape
+            row_off = np.arange(rows + 1, dtype=np.int64) * L
+        else:
+            row_off = self.offsets(lengths)
+            rows = len(lengths)
+            if not (x.dtype == torch.float64 and x.is_contiguous() and x.numel() == int(row_off[-1]) and min(lengths, default=1) >= 1):
+                raise ValueError("gauss_rows_f64: ragged rows need a contiguous fp64 tensor of sum(lengths) values, no row empty")
+        off = self.tensor(row_off)
         out = torch.empty_like(x)
-        self._check(self.lib.goofer_gauss_rows_f64(self.h, _ptr(x), _ptr(off), rows, rows * L, taps.ctypes.data_as(C.c_void_p),
+        self._check(self.lib.goofer_gauss_rows_f64(self.h, _ptr(x), _ptr(off), rows, int(row_off[-1]), taps.ctypes.data_as(C.c_void_p),
                                                    (taps.size - 1) // 2, _ptr(out), self._stream()))
         return out
+
+    # -- ragged feature preparation of core.synthesize_batch -----------------------------------------------------------
+    def ingest_rows(self, flat, lengths, n_cols: int):
+        """to_compute(a).T for a batch of [n_cols, T_i] arrays in one launch (goofer_ingest_rows): ``flat`` a contiguous fp32 or
+        fp64 device tensor holding the arrays back to back (C order), ``lengths`` their T_i.  Returns the ld-strided fp32
+        [sum T_i, n_cols] rows; fp64 is rounded on the device exactly as numpy's astype(np.float32)."""
+        lengths = [int(v) for v in lengths]
+        if not (isinstance(flat, torch.Tensor) and flat.dtype in (torch.float32, torch.float64) and flat.is_contiguous()
+                and flat.device == self.device):
+            raise ValueError("ingest_rows expects a contiguous fp32 or fp64 tensor on this context's device")
+        if any(v < 0 for v in lengths) or sum(lengths) * int(n_cols) != flat.numel():
+            raise ValueError(f"ingest_rows: {len(lengths)} arrays of {n_cols} x {sum(lengths)} values, the buffer has {flat.numel()}")
+        row_off = self.offsets(lengths)
+        tile_off = self.offsets([(v + 63) // 64 for v in lengths])
+        meta = self.tensor(np.concatenate([row_off, tile_off]))
+        out = self.rows(int(row_off[-1]), int(n_cols))
+        n = len(lengths)
+        self._check(self.lib.goofer_ingest_rows(self.h, _ptr(flat), int(flat.dtype == torch.float64), _ptr(meta[:n + 1]),
+                                                _ptr(meta[n + 1:]), n, int(tile_off[-1]), int(n_cols), _ptr(out), out.stride(0),
+                                                self._stream()))
+        return out
+
+    def warp_bins_ragged(self, rows, lengths, formants, f_shift, ratio, anchor):
+        """goofer_warp_bins note by note in one launch (goofer_warp_bins_ragged): ``lengths`` rows per note; per note
+        ``f_shift`` [n, 4], ``ratio`` [n] and ``anchor`` [n] (False: no anchor warp, as f_shift=None of warp_bins)."""
+        lengths = [int(v) for v in lengths]
+        n, R = len(lengths), rows.shape[0]
+        if any(v < 0 for v in lengths) or sum(lengths) != R or (formants is not None and tuple(formants.shape) != (R, 4)):
+            raise ValueError("warp_bins_ragged: the row lengths do not cover the rows (or the formants do not)")
+        args = np.zeros((n, 6), dtype=np.float64)
+        args[:, :4] = np.asarray(f_shift, dtype=np.float64).reshape(n, 4)
+        args[:, 4] = np.asarray(ratio, dtype=np.float64)
+        args[:, 5] = np.asarray(anchor, dtype=bool)
+        meta = self.tensor(np.concatenate([self.offsets(lengths), args.ravel().view(np.int64)]))
+        out = self.rows_like(rows)
+        self._check(self.lib.goofer_warp_bins_ragged(self.h, _ptr(rows), _ptr(out), R, rows.shape[1], rows.stride(0), _ptr(formants),
+                                                     _ptr(meta[:n + 1]), n, _ptr(meta[n + 1:].view(torch.float64)), self._stream()))
+        return out
+
+    def stretch_ragged(self, env_h, env_n, row_lengths, row_cuts, rows_out, f0, mask, sample_lengths, sample_cuts, samples_out):
+        """gf.synthesize's time stretch for every note in one launch (goofer_stretch_ragged): per note concat(x[:a],
+        stretch(x[a:b]), x[b:]) of env_h and env_n (ld-strided, the same stride; ``row_cuts`` (a, b) per note, ``rows_out``
+        output rows per note) and of f0 and mask (``sample_cuts``, ``samples_out``).  Returns (env_h, env_n, f0, mask)."""
+        def axis(lengths, cuts, out_lengths):
+            lengths, out_lengths = np.asarray(lengths, dtype=np.int64), np.asarray(out_lengths, dtype=np.int64)
+            cuts = np.asarray(cuts, dtype=np.int64).reshape(len(lengths), 2)
+            a, b = cuts[:, 0], cuts[:, 1]
+            m = out_lengths - a - (lengths - b)
+            # the kernel indexes by these: a cut outside its array, or a region stretched from nothing, would read out of bounds
+            if np.any(a < 0) or np.any(b < a) or np.any(b > lengths) or np.any(m < 0) or np.any((m > 0) & (b == a)):
+                raise ValueError("stretch_ragged: a cut (a, b) outside its array, or an empty region stretched")
+            return [self.offsets(lengths), self.offsets(out_lengths), cuts.ravel()]
+        n = len(row_lengths)
+        if not (len(row_cuts) == len(rows_out) == len(sample_lengths) == len(sample_cuts) == len(samples_out) == n):
+            raise ValueError("stretch_ragged: one cut and one output length per note on both axes")
+        ra, sa = axis(row_lengths, row_cuts, rows_out), axis(sample_lengths, sample_cuts, samples_out)
+        R, N = int(ra[0][-1]), int(sa[0][-1])
+        if (env_h.shape[0] != R or env_n.shape != env_h.shape or env_n.stride(0) != env_h.stride(0) or env_h.stride(0) != row_stride(env_h.shape[1])
+                or env_h.stride(1) != 1 or env_n.stride(1) != 1 or f0.numel() != N or mask.numel() != N or not (f0.is_contiguous() and mask.is_contiguous())
+                or f0.dtype != torch.float32 or mask.dtype != torch.float32):
+            raise ValueError("stretch_ragged: the arrays do not match the per-note lengths")
+        meta = self.tensor(np.concatenate(ra + sa))
+        pieces, o = [], 0
+        for k in (n + 1, n + 1, 2 * n, n + 1, n + 1, 2 * n):
+            pieces.append(meta[o:o + k])
+            o += k
+        R2, N2 = int(ra[1][-1]), int(sa[1][-1])
+        h2, n2 = self.rows(R2, env_h.shape[1]), self.rows(R2, env_h.shape[1])
+        f2 = torch.empty(N2, dtype=torch.float32, device=self.device)
+        m2 = torch.empty(N2, dtype=torch.float32, device=self.device)
+        self._check(self.lib.goofer_stretch_ragged(self.h, *[_ptr(t) for t in pieces], n, R2, N2, env_h.shape[1], env_h.stride(0),
+                                                   _ptr(env_h), _ptr(env_n), _ptr(h2), _ptr(n2), _ptr(f0), _ptr(mask), _ptr(f2),
+                                                   _ptr(m2), self._stream()))
+        return h2, n2, f2, m2
 
     def vocal_roughness(self, y, f0, mask, noise_s, k_list, h_list, noise_amp: float, hp_fc: float, alpha_slewed, lengths=None):
         """apply_vocal_roughness (GOOFER.py:901-940) on fp32 device signals; ``noise_s`` fp64 [n_k, N] smoothed noises,

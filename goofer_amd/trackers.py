@@ -300,25 +300,31 @@ def plan_passes(entries, frame_budget=FRAME_BUDGET):
     """Cut ``entries`` = [(key, sr, n_frames)] into device passes [(sr, [key, ...])].  A key seen before is dropped.  Sample
     rates come in the order they first appear; inside a rate the keys keep their input order and are taken greedily while the
     pass stays within ``frame_budget`` frames.  A signal larger than the budget gets a pass of its own."""
+    return plan_keyed_passes([(key, int(sr), frames) for key, sr, frames in entries], frame_budget)
+
+
+def plan_keyed_passes(entries, frame_budget=FRAME_BUDGET):
+    """``plan_passes`` with any hashable pass key in place of the sample rate: [(key, pass_key, n_frames)] -> [(pass_key,
+    [key, ...])].  Entries share a pass only when their pass keys are equal."""
     if frame_budget < 1:
         raise ValueError("frame_budget must be at least one frame")
     seen, groups = set(), {}
-    for key, sr, frames in entries:
+    for key, pass_key, frames in entries:
         if key in seen:
             continue
         seen.add(key)
-        groups.setdefault(int(sr), []).append((key, int(frames)))
+        groups.setdefault(pass_key, []).append((key, int(frames)))
     passes = []
-    for sr, members in groups.items():
+    for pass_key, members in groups.items():
         cur, used = [], 0
         for key, frames in members:
             if cur and used + frames > frame_budget:
-                passes.append((sr, cur))
+                passes.append((pass_key, cur))
                 cur, used = [], 0
             cur.append(key)
             used += frames
         if cur:
-            passes.append((sr, cur))
+            passes.append((pass_key, cur))
     return passes
 
 

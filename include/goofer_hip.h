@@ -455,6 +455,35 @@ int goofer_smooth_mask_ds(goofer_ctx *ctx, const float *mask, const int64_t *sam
 int goofer_stretch_rows(goofer_ctx *ctx, const float *in, int64_t ld_in, int64_t rows_in, float *out, int64_t ld_out,
                         int64_t rows_out, int n_cols, void *stream);
 
+/* ---- ragged feature preparation for core.synthesize_batch (many gf.synthesize calls per device pass) ------------------------
+ * All CSR arrays are device memory; every launch covers the whole batch. */
+
+/* to_compute(env_spec).T per note (GOOFER.py:72, 984) in one launch: note i's [n_cols x T_i] array (row-major, the reference's
+ * [bins, frames] layout) starts at element row_off[i] * n_cols of `in` (fp64 when in_f64, else fp32), T_i = row_off[i+1] -
+ * row_off[i]; it becomes rows row_off[i] .. row_off[i+1] of out [row_off[n] x ld] fp32.  fp64 is rounded to nearest even, as
+ * numpy's astype(np.float32).  tile_off [n_notes+1]: prefix sums of ceil(T_i / 64), total_tiles = tile_off[n_notes].  Also
+ * lays out injected phases (gf.synthesize's phi). */
+int goofer_ingest_rows(goofer_ctx *ctx, const void *in, int in_f64, const int64_t *row_off, const int64_t *tile_off, int n_notes,
+                       int64_t total_tiles, int n_cols, float *out, int ld, void *stream);
+
+/* goofer_warp_bins with settings per note: row r of in / out [rows x ld] belongs to the note i with row_off[i] <= r <
+ * row_off[i+1]; formants [rows x 4] fp64 or NULL; note_args [n_notes x 6] fp64 = f_shift[4], ratio, anchor (0: no anchor
+ * warp, goofer_warp_bins' f_shift == NULL; else warp by f_shift even when all four are 1).  Note by note the bits of
+ * goofer_warp_bins(f_shift or NULL, ratio). */
+int goofer_warp_bins_ragged(goofer_ctx *ctx, const float *in, float *out, int64_t rows, int n_bins, int ld, const double *formants,
+                            const int64_t *row_off, int n_notes, const double *note_args, void *stream);
+
+/* gf.synthesize's time stretch (GOOFER.py:1019-1057) for a ragged batch in one launch: per note concat(x[:a],
+ * stretch_feature(x[a:b], factor), x[b:]) of env_h and env_n ([rows x ld] fp32, the frame axis: row_off_in -> row_off_out,
+ * (a, b) = row_cut[2i], row_cut[2i+1] note-relative) and of f0 and mask (fp32, the sample axis: sample_off_in -> sample_off_out,
+ * sample_cut).  The stretched length is implied: out_len - a - (in_len - b); the region b - a must be >= 1 wherever it is
+ * stretched to >= 1 element.  The arithmetic of goofer_stretch_rows, without its 65535-row limit. */
+int goofer_stretch_ragged(goofer_ctx *ctx, const int64_t *row_off_in, const int64_t *row_off_out, const int64_t *row_cut,
+                          const int64_t *sample_off_in, const int64_t *sample_off_out, const int64_t *sample_cut, int n_notes,
+                          int64_t rows_out, int64_t samples_out, int n_cols, int ld, const float *env_h, const float *env_n,
+                          float *env_h_out, float *env_n_out, const float *f0, const float *mask, float *f0_out, float *mask_out,
+                          void *stream);
+
 /* gf.gaussian_filter1d along the last axis of ragged fp64 rows (GOOFER.py:241-261: numpy 'reflect' padding, fp64
  * accumulate in tap order): row r is in[row_off[r] .. row_off[r+1]) (device CSR); taps are HOST memory, 2*radius+1. */
 int goofer_gauss_rows_f64(goofer_ctx *ctx, const double *in, const int64_t *row_off, int n_rows, int64_t total, const double *taps,
