@@ -563,12 +563,15 @@ def _prepare_note(c, note, kw, seed, phi, sr, n_fft, hop):
     if isinstance(env_spec, dict) and env_spec.get("mode") == "knots":
         env_spec = decode_env_from_knots(env_spec, ctx=c)
         c.plan(sr, n_fft, hop)
-    env = np.asarray(env_spec)
-    if env.dtype not in (np.float32, np.float64):
-        env = env.astype(np.float32)                          # to_compute (fp64 is rounded on the device, the same bits)
+    if isinstance(env_spec, torch.Tensor):                    # device-resident: [bins, T] on this context's device
+        env = env_spec if env_spec.dtype in (torch.float32, torch.float64) else env_spec.float()
+    else:
+        env = np.asarray(env_spec)
+        if env.dtype not in (np.float32, np.float64):
+            env = env.astype(np.float32)                      # to_compute (fp64 is rounded on the device, the same bits)
     n = len(note["y"])
-    f0 = np.asarray(note["f0_interp"], dtype=np.float32)
-    mask = np.asarray(note["voicing_mask"], dtype=np.float32)
+    f0 = _f32(note["f0_interp"])
+    mask = _f32(note["voicing_mask"])
     if n == 0:
         return _empty4()
     if f0.ndim != 1 or mask.ndim != 1:
@@ -587,7 +590,8 @@ def _prepare_note(c, note, kw, seed, phi, sr, n_fft, hop):
         factor = float(kw["stretch_factor"])
         f_shift = [kw.get("F%d_shift" % i, 1.0) for i in (1, 2, 3, 4)]
         ps = kw.get("pitch_shift", 1.0)
-        f0 = (f0 * np.float32(ps)).astype(np.float32) if ps != 1.0 else f0
+        if ps != 1.0:
+            f0 = f0 * _f32(np.float32(ps), like=f0) if isinstance(f0, torch.Tensor) else (f0 * np.float32(ps)).astype(np.float32)
         s0, s1 = kw.get("start_sec"), kw.get("end_sec")
         if s0 is not None and s1 is not None:
             a, b = int(s0 * sr), int(s1 * sr)
@@ -596,8 +600,9 @@ def _prepare_note(c, note, kw, seed, phi, sr, n_fft, hop):
             a, b, fa, fb = 0, None, 0, None
         # f0_interp is a float64 array from here on in the reference: the jitter's product and the sub-harmonic phase trackers work on
         # it (their float32 versions land one event in ~10^5 a sample off, which a soak run of random keyword sets found)
+        # (_stretch64 is host arithmetic: a device-resident f0 comes to the host here, and only here)
         needs64 = bool(kw.get("f0_jitter") or kw.get("add_subharm"))
-        f0_64 = _stretch64(f0, a, b, factor) if needs64 else None
+        f0_64 = _stretch64(f0.cpu().numpy() if isinstance(f0, torch.Tensor) else f0, a, b, factor) if needs64 else None
         s_cut, _, e_cut = _cut(len(f0), a, b, factor), _cut(len(mask), a, b, factor), _cut(T_env, fa, fb, factor)
         n = s_cut[0] + s_cut[2] + len(f0) - s_cut[1]
         if n == 0:
@@ -642,8 +647,26 @@ def _prepare_note(c, note, kw, seed, phi, sr, n_fft, hop):
     return job
 
 
+def _f32(x, like=None):
+    """np.asarray(x, dtype=np.float32), or for a device tensor (``like``: a scalar onto like's device) the same rounding there."""
+    if isinstance(x, torch.Tensor):
+        return x if x.dtype == torch.float32 else x.to(torch.float32)
+    if like is not None:
+        return torch.tensor(np.float32(x), device=like.device)
+    return np.asarray(x, dtype=np.float32)
+
+
 def _concat(arrs, dtype):
     return np.concatenate([np.ascontiguousarray(a, dtype=dtype).ravel() for a in arrs]) if arrs else np.zeros(0, dtype=dtype)
+
+
+def _device_concat(c, arrs, dtype):
+    """_concat on the device: one upload when every array is on the host, else one torch.cat of device tensors and uploads."""
+    if not any(isinstance(a, torch.Tensor) for a in arrs):
+        return c.tensor(_concat(arrs, dtype))
+    tdt = torch.float64 if dtype == np.float64 else torch.float32
+    return torch.cat([a.reshape(-1).to(c.device, tdt) if isinstance(a, torch.Tensor)
+                      else torch.from_numpy(np.ascontiguousarray(a, dtype=dtype).ravel()).to(c.device) for a in arrs])
 
 
 def _noise(c, js, key, part=None):
@@ -655,9 +678,18 @@ def _noise(c, js, key, part=None):
 
 
 def _ingest(c, arrays, lengths):
-    """ld-strided fp32 rows of [bins, T] host arrays, one upload and one goofer_ingest_rows launch."""
-    dt = np.float64 if any(a.dtype == np.float64 for a in arrays) else np.float32
-    return c.ingest_rows(c.tensor(_concat(arrays, dt)), lengths, c.n_bins)
+    """ld-strided fp32 rows of [bins, T] host arrays, one upload and one goofer_ingest_rows launch.  Envelopes already on the
+    device ([bins, T] views of frame-major rows, analyse_device's) are rounded to fp32 into the row stride there instead, with
+    the same round-to-nearest-even; host arrays in such a pass are uploaded frame-major beside them."""
+    if not any(isinstance(a, torch.Tensor) for a in arrays):
+        dt = np.float64 if any(a.dtype == np.float64 for a in arrays) else np.float32
+        return c.ingest_rows(c.tensor(_concat(arrays, dt)), lengths, c.n_bins)
+    f64 = any(a.dtype == (torch.float64 if isinstance(a, torch.Tensor) else np.float64) for a in arrays)
+    tdt = torch.float64 if f64 else torch.float32
+    parts = [a.T.to(tdt) if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a.T)).to(c.device, tdt) for a in arrays]
+    rows = c.rows(sum(int(v) for v in lengths), c.n_bins)
+    rows.copy_(torch.cat(parts) if len(parts) > 1 else parts[0])
+    return rows
 
 
 def _run_pass(c, js, sr):
@@ -673,7 +705,7 @@ def _run_pass(c, js, sr):
     params["seed"][:, 0] = (seeds & np.uint64(0xFFFFFFFF)).astype(np.uint32)    # the kernels XOR it with the batch seed 0: each
     params["seed"][:, 1] = (seeds >> np.uint64(32)).astype(np.uint32)            # note's key is the key of its single call
     F = c.tensor(np.concatenate([j["F"] for j in js]))
-    fm = c.tensor(_concat([j["f0"] for j in js] + [j["mask"] for j in js], np.float32))
+    fm = _device_concat(c, [j["f0"] for j in js] + [j["mask"] for j in js], np.float32)
     n_in = fm.numel() // 2
     d_f0, d_mask = fm[:n_in], fm[n_in:]
     jit = next((j["kw"] for j in js if j["kw"].get("f0_jitter")), kw)
@@ -783,6 +815,13 @@ def synthesize_batch(notes, sr, n_fft=1024, hop_length=256, *, seeds=None, phis=
             results[i] = r
         else:
             jobs[i] = r
+    _render(c, jobs, results, sr)
+    return results
+
+
+def _render(c, jobs, results, sr):
+    """The device half of synthesize_batch: the prepared ``jobs`` (None: nothing to render) cut into passes and rendered, each
+    result into its slot of ``results``."""
     keys = [synth_pass_key(j["kw"], j["phi"] is not None, j["f64_missing"]) if j is not None else None for j in jobs]
     for idxs in plan_synth_passes(keys, [j["frames"] if j is not None else 0 for j in jobs]):
         js = [jobs[i] for i in idxs]
@@ -796,7 +835,95 @@ def synthesize_batch(notes, sr, n_fft=1024, hop_length=256, *, seeds=None, phis=
                 gain = (1.0 / peak) ** float(np.clip(js[q]["kw"].get("normalize", 1.0), 0.0, 1.0))
                 rec, harm, uv, bre = combined * np.float32(gain), harm * np.float32(gain), uv * np.float32(gain), bre * np.float32(gain)
             results[i] = (rec, harm, uv, bre)
+
+
+def resynthesize_batch(signals, sr, n_fft=1024, hop_length=256, *, f0_min=75, f0_merge_range=2, pitch_tracker=None, variants=None,
+                       seeds=None, phis=None, ctx=None, **synth_kw):
+    """The reference's wav-to-wav flow (GOOFER.py:1222-1330, test.py) for many signals: per signal ``extract_features``, then
+    one ``synthesize`` per variant on those features.  Returns per signal a (reconstruct, harmonic, aper_uv, aper_bre) tuple
+    (``variants=None``) or a list of them, one per variant (any ``variants`` list, one entry too); a signal whose analysis raised gets that exception in its slot,
+    and a variant whose synthesis raised gets its exception in the list.  The other signals still render.
+
+    ``signals``: mono arrays at one ``sr``.  ``variants``: keyword dicts, each layered over ``synth_kw``; ``formants`` defaults
+    to the signal's own extracted formants, as both reference scripts pass them.  ``seeds`` / ``phis``: one Philox key / one
+    injected phase array (or None) per (signal, variant), signal-major: entry ``i * len(variants) + v``.
+
+    Result (i, v) equals, bit for bit, ``env, f0, mask, forms, _ = extract_features(y_i, sr, n_fft, hop_length, f0_min=...,
+    f0_merge_range=..., pitch_tracker=...)`` then ``synthesize(env, f0, mask, y_i, sr, n_fft, hop_length, formants=forms,
+    **{**synth_kw, **variants[v]}, seed=..., phi=...)`` run signal by signal and variant by variant, and the legacy
+    ``np.random`` state afterwards is the state after those calls: every host draw is made in that order before the device
+    work of its pass.  (A host tracker is called for the signals of an analysis pass before that pass's draws.)
+
+    Signals are analysed in device passes of at most ``trackers.FRAME_BUDGET`` STFT frames (``trackers.plan_passes``); each
+    analysis pass is synthesised (``plan_synth_passes``) before the next one starts, so device memory is bounded by a pass.
+    The envelope, per-sample f0 and voicing mask stay on the device from analysis to synthesis (``trackers.analyse_device``);
+    the one case that brings a signal's f0 to the host is a time-stretched variant with ``f0_jitter`` or ``add_subharm``,
+    whose fp64 stretch is host arithmetic (``_stretch64``).  A one-frame f0 track is post-processed on the host.  An unknown
+    keyword, or ``seeds`` / ``phis`` of the wrong length, raise before anything is analysed or drawn."""
+    from . import trackers
+    signals = list(signals)
+    one = variants is None
+    variants = [{}] if one else [dict(v) for v in variants]
+    defaults = _synth_defaults()
+    for name in list(synth_kw) + [k for v in variants for k in v]:
+        if name not in defaults:
+            raise TypeError(f"synthesize() got an unexpected keyword argument '{name}'")
+    n, V = len(signals), len(variants)
+    seeds = [None] * (n * V) if seeds is None else list(seeds)
+    phis = [None] * (n * V) if phis is None else list(phis)
+    if len(seeds) != n * V or len(phis) != n * V:
+        raise ValueError(f"resynthesize_batch: {n} signals x {V} variants, {len(seeds)} seeds and {len(phis)} phase arrays")
+    c = _ctx(sr, n_fft, hop_length, ctx)
+    track_fn = trackers.get(pitch_tracker)
+    results = [None] * n
+    entries = []
+    for i, y in enumerate(signals):
+        y = np.asarray(y)
+        entries.append((i, int(sr), 1 + (y.shape[0] if y.ndim else 0) // int(hop_length)))
+    for _, idxs in trackers.plan_passes(entries):
+        feats = trackers.analyse_device([signals[i] for i in idxs], sr, n_fft, hop_length, f0_min, f0_merge_range, tracker=track_fn,
+                                        ctx=c, want_env=True)
+        c.plan(sr, n_fft, hop_length)
+        jobs, slots = [], []
+        for i, f in zip(idxs, feats):
+            if isinstance(f, BaseException):
+                results[i] = f
+                continue
+            note = {"env_spec": f["env"].T, "f0_interp": f["f0"], "voicing_mask": f["mask"], "y": signals[i]}
+            out = [None] * V
+            for v, var in enumerate(variants):
+                merged = {**defaults, "formants": f["formants"], **synth_kw, **var}
+                try:
+                    r = _prepare_note(c, note, merged, seeds[i * V + v], phis[i * V + v], sr, n_fft, hop_length)
+                except Exception as e:                          # the variant's own refusal: its slot, the others render
+                    out[v] = e
+                    continue
+                if isinstance(r, tuple):
+                    out[v] = r
+                else:
+                    jobs.append(r)
+                    slots.append((out, v))
+            results[i] = out
+        rendered = [None] * len(jobs)
+        _render(c, jobs, rendered, sr)
+        for (out, v), r in zip(slots, rendered):
+            out[v] = r
+        del feats, jobs                                          # the pass's device buffers go before the next pass
+    if one:
+        results = [r if isinstance(r, BaseException) else r[0] for r in results]
     return results
+
+
+def resynthesize(y, sr, n_fft=1024, hop_length=256, **kw):
+    """``resynthesize_batch`` for one signal: its (reconstruct, harmonic, aper_uv, aper_bre), or a list of them with
+    ``variants``.  Raises what the analysis or a synthesis raised."""
+    res = resynthesize_batch([y], sr, n_fft, hop_length, **kw)[0]
+    if isinstance(res, BaseException):
+        raise res
+    for r in res if isinstance(res, list) else ():
+        if isinstance(r, BaseException):
+            raise r
+    return res
 
 
 def synthesize(env_spec, f0_interp, voicing_mask, y, sr, n_fft=1024, hop_length=256, glottal_smoothing=False,

@@ -243,6 +243,32 @@ class Context:
             out += [res if width > 1 else res[:, 0], f_off]
         return tuple(out)
 
+    def per_sample_f0(self, tracks, track_lengths, sample_lengths, sr, f0_min=75, f0_merge_range=2):
+        """trackers.per_sample_f0 for a ragged batch in one launch (goofer_per_sample_f0): ``tracks`` a contiguous fp64 device
+        tensor holding ``track_lengths`` frames per signal (two at least each), ``sample_lengths`` the signals' sample counts.
+        Returns (f0, voicing mask), fp64 device tensors of sum(sample_lengths) values, bit for bit the host function's.  Bad
+        offsets or lengths raise ValueError before anything is launched."""
+        if not (isinstance(tracks, torch.Tensor) and tracks.dtype == torch.float64 and tracks.is_contiguous() and tracks.device == self.device):
+            raise ValueError("per_sample_f0 expects a contiguous fp64 tensor on this context's device")
+        t_len, s_len = [int(v) for v in track_lengths], [int(v) for v in sample_lengths]
+        if not t_len or len(t_len) != len(s_len):
+            raise ValueError(f"per_sample_f0: {len(t_len)} tracks for {len(s_len)} signals")
+        if min(t_len) < 2 or min(s_len) < 0 or sum(t_len) != tracks.numel():
+            raise ValueError(f"per_sample_f0: track lengths {min(t_len)}.. summing to {sum(t_len)} for {tracks.numel()} frames, "
+                             f"sample lengths from {min(s_len)} (every track needs two frames, no length may be negative)")
+        t_off, s_off = self.offsets(t_len), self.offsets(s_len)
+        args = (t_off.ctypes.data_as(C.c_void_p), s_off.ctypes.data_as(C.c_void_p), len(t_len), float(sr), float(f0_min),
+                int(min(f0_merge_range, 2 ** 31 - 1)))
+        need = C.c_int64(0)
+        self._check(self.lib.goofer_per_sample_f0(self.h, None, *args, None, None, None, C.byref(need), None))
+        n = int(s_off[-1])
+        f0 = torch.empty(n, dtype=torch.float64, device=self.device)
+        mask = torch.empty(n, dtype=torch.float64, device=self.device)
+        scratch = torch.empty(max(int(need.value), 1), dtype=torch.uint8, device=self.device)
+        self._check(self.lib.goofer_per_sample_f0(self.h, _ptr(tracks), *args, _ptr(f0), _ptr(mask), _ptr(scratch), C.byref(need),
+                                                  self._stream()))
+        return f0, mask
+
     # -- analysis (GOOFER.py:942-946, 97-147) -----------------------------------------------------
     def envelope_knots(self, y32, lengths, want_env: bool = False):
         """The envelope half of gf.extract_features for a ragged batch at the current plan (goofer_envelope_knots_batch):

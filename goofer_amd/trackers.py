@@ -328,16 +328,108 @@ def plan_keyed_passes(entries, frame_budget=FRAME_BUDGET):
     return passes
 
 
+def per_sample_f0_batch(c, tracks, n_samples, sr, f0_min=75, f0_merge_range=2):
+    """``per_sample_f0`` for many tracks of one sample rate -> (per track (f0, voicing mask) or the exception it raised, the
+    launch's (f0, mask) buffers or None, {track: (first, end) sample in them}).  Every 1-D track of two frames or more goes
+    through one ``Context.per_sample_f0`` launch and gets fp64 device views of its buffers; a one-frame or empty track
+    (np.isclose's special case, gf.interp1d's ValueError) or any other shape stays on the host and gets host arrays.
+    ``tracks``: fp64 device tensors (the native tracker's) or host arrays."""
+    import torch
+    out, tracks = [None] * len(tracks), list(tracks)
+    dev, host = [], []
+    for j, t in enumerate(tracks):
+        if isinstance(t, torch.Tensor) and t.dim() == 1 and t.numel() >= 2:
+            dev.append(j)
+        elif not isinstance(t, torch.Tensor):
+            a = np.asarray(t, dtype=np.float64)
+            (host if a.ndim != 1 or a.size < 2 else dev).append(j)
+            tracks[j] = a
+        else:
+            host.append(j)
+    for j in host:
+        try:
+            t = tracks[j]
+            out[j] = per_sample_f0(t.cpu().numpy() if isinstance(t, torch.Tensor) else t, n_samples[j], sr, f0_min, f0_merge_range)
+        except Exception as e:                                    # noqa: BLE001 - per-signal isolation
+            out[j] = e
+    if dev:
+        parts = [tracks[j] for j in dev]
+        if isinstance(parts[0], torch.Tensor):
+            flat = parts[0].contiguous() if len(parts) == 1 else torch.cat(parts)
+        else:
+            flat = c.tensor(np.concatenate(parts))
+        f0, mask = c.per_sample_f0(flat, [p.shape[0] for p in parts], [n_samples[j] for j in dev], sr, f0_min, f0_merge_range)
+        off = c.offsets([n_samples[j] for j in dev])
+        slots = {j: (int(off[q]), int(off[q + 1])) for q, j in enumerate(dev)}
+        for j, (a, b) in slots.items():
+            out[j] = (f0[a:b], mask[a:b])
+        return out, (f0, mask), slots
+    return out, None, {}
+
+
 def analyse_batch(signals, sr, n_fft=1024, hop_length=256, f0_min=75, f0_merge_range=2, tracker=None, ctx=None, want_env=True,
                   timings=None):
     """``analyse`` for many signals at one sample rate: one ``extract_features`` 5-tuple per signal, or the exception that
-    signal raised (env_spec is None unless ``want_env``).  The envelope and knots of every signal come from one
-    ``Context.envelope_knots`` call; with the native tracker one ``Context.track`` call follows on the same stream and the
-    host waits once for both.  Any other tracker is called per signal.  The f0 post-processing stays per signal on the host.
-    ``timings``, a dict, collects seconds under "device" (upload to results on the host) and "host"."""
+    signal raised (env_spec is None unless ``want_env``).  ``analyse_device`` does the work; this brings its results to the
+    host.  ``timings``, a dict, collects seconds under "device" (upload to results on the host) and "host"."""
     import time
     import torch
+    t0 = time.perf_counter()
+    res = analyse_device(signals, sr, n_fft, hop_length, f0_min, f0_merge_range, tracker=tracker, ctx=ctx, want_env=want_env,
+                         want_knots=True)
+    out = [None] * len(signals)
+    live = [i for i, r in enumerate(res) if not isinstance(r, BaseException)]
+    for i, r in enumerate(res):
+        if isinstance(r, BaseException):
+            out[i] = r
+    if not live:
+        return out
+    pa = res[live[0]]["pass"]
+    env = pa["env"].cpu().numpy() if want_env else None
+    knots, K = pa["knots"].cpu().numpy(), pa["K"].cpu().numpy()
+    f0_host = pa["f0"].cpu().numpy() if pa["f0"] is not None else None
+    # the 0 / 1 mask comes over as bytes (an eighth of the fp64 copy) and is widened on the host: the same values
+    mask_host = pa["mask"].to(torch.uint8).cpu().numpy().astype(np.float64) if pa["mask"] is not None else None
+    t1 = time.perf_counter()
+    sr = int(sr)
+    f_off = pa["f_off"]
+    for i in live:
+        r = res[i]
+        j = r["slot"]
+        a, b = int(f_off[j]), int(f_off[j + 1])
+        T, Kj = b - a, int(K[j])
+        vals = knots[a:b].reshape(-1)[:T * Kj].reshape(T, Kj).T
+        env_knots = {"mode": "knots", "knot_vals_log": np.ascontiguousarray(vals),
+                     "hz_knots": _mel_knots(sr, n_fft, Kj), "n_bins": int(pa["n_bins"]), "n_fft": int(n_fft), "sr": sr}
+        env_spec = np.ascontiguousarray(env[a:b].T) if want_env else None
+        if r["f0_slot"] is not None:
+            s0, s1 = r["f0_slot"]
+            f0_s, vmask = f0_host[s0:s1], mask_host[s0:s1]
+        else:
+            f0_s, vmask = r["f0"], r["mask"]
+        out[i] = (env_spec, f0_s, vmask, r["formants"], env_knots)
+    if timings is not None:
+        timings["device"] = timings.get("device", 0.0) + (t1 - t0)
+        timings["host"] = timings.get("host", 0.0) + (time.perf_counter() - t1)
+    return out
+
+
+def _mel_knots(sr, n_fft, K):
     from . import core
+    return core.make_mel_knots(sr, n_fft, K)[1].astype(np.float32)
+
+
+def analyse_device(signals, sr, n_fft=1024, hop_length=256, f0_min=75, f0_merge_range=2, tracker=None, ctx=None, want_env=True,
+                   want_knots=False):
+    """The device half of ``analyse_batch``, results left on the device: per signal the exception it raised, or a dict with
+    "env" (the sigma-2 envelope, an fp64 [T, bins] device view, frame-major; None unless ``want_env``), "f0" and "mask" (per
+    sample, fp64: device views, or host arrays for a one-frame track), "formants" (host dict, fitted to T frames), "T", and
+    "pass" / "slot" / "f0_slot" (the shared pass buffers and the signal's place in them).  The envelope and knots of every
+    signal come from one ``Context.envelope_knots`` call; with the native tracker one ``Context.track`` call follows on the
+    same stream, and its f0 tracks never leave the device.  Any other tracker is called per signal, in order, on the host and
+    its tracks uploaded.  Per-sample f0 and voicing come from one ``Context.per_sample_f0`` launch (``per_sample_f0_batch``).
+    Only the formant tracks (and with ``want_knots`` nothing else) are waited for."""
+    import torch
     from .device import default_context
     track_fn = get(tracker)
     native = track_fn is native_tracker
@@ -356,40 +448,41 @@ def analyse_batch(signals, sr, n_fft=1024, hop_length=256, f0_min=75, f0_merge_r
             live.append(i)
     if not live:
         return out
-    t0 = time.perf_counter()
     c = (ctx or default_context()).plan(sr, n_fft, hop)
     lengths = [y.size for y in ys]
     y32 = torch.from_numpy(np.concatenate([np.asarray(y, dtype=np.float32) for y in ys])).to(c.device)
     knots, K, f_off, env = c.envelope_knots(y32, lengths, want_env=want_env)
+    tracks, formants = [None] * len(ys), [None] * len(ys)
     if native:
         y64 = torch.from_numpy(np.concatenate([np.asarray(y, dtype=np.float64) for y in ys])).to(c.device)
         f0, p_off, forms, m_off = c.track(y64, lengths, sr, hop)
-        f0, forms = f0.cpu().numpy(), forms.cpu().numpy()
-    knots, K = knots.cpu().numpy(), K.cpu().numpy()
-    env = env.cpu().numpy() if want_env else None
-    t1 = time.perf_counter()
-    nb = c.n_bins
-    for j, (i, y) in enumerate(zip(live, ys)):
-        try:
-            a, b = int(f_off[j]), int(f_off[j + 1])
-            T, Kj = b - a, int(K[j])
-            vals = knots[a:b].reshape(-1)[:T * Kj].reshape(T, Kj).T
-            env_knots = {"mode": "knots", "knot_vals_log": np.ascontiguousarray(vals),
-                         "hz_knots": core.make_mel_knots(sr, n_fft, Kj)[1].astype(np.float32), "n_bins": int(nb),
-                         "n_fft": int(n_fft), "sr": int(sr)}
-            env_spec = np.ascontiguousarray(env[a:b].T) if want_env else None
-            if native:
-                f0_track = f0[p_off[j]:p_off[j + 1]]
-                formants = fit_formants({k: forms[m_off[j]:m_off[j + 1], k - 1].tolist() for k in range(1, 6)}, T)
-            else:
-                f0_track, formants = track_fn(y, sr, hop, T)
-            f0_s, vmask = per_sample_f0(f0_track, y.size, sr, f0_min, f0_merge_range)
-            out[i] = (env_spec, f0_s, vmask, fit_formants(dict(formants), T), env_knots)
-        except Exception as e:                                    # noqa: BLE001 - per-signal isolation
-            out[i] = e
-    if timings is not None:
-        timings["device"] = timings.get("device", 0.0) + (t1 - t0)
-        timings["host"] = timings.get("host", 0.0) + (time.perf_counter() - t1)
+        forms = forms.cpu().numpy()
+        for j in range(len(ys)):
+            T = int(f_off[j + 1] - f_off[j])
+            tracks[j] = f0[p_off[j]:p_off[j + 1]]
+            formants[j] = fit_formants({k: forms[m_off[j]:m_off[j + 1], k - 1].tolist() for k in range(1, 6)}, T)
+    else:
+        for j, y in enumerate(ys):
+            T = int(f_off[j + 1] - f_off[j])
+            try:
+                f0_track, forms_j = track_fn(y, sr, hop, T)
+                tracks[j], formants[j] = f0_track, fit_formants(dict(forms_j), T)
+            except Exception as e:                                # noqa: BLE001 - per-signal isolation
+                tracks[j] = e
+    ok = [j for j in range(len(ys)) if not isinstance(tracks[j], BaseException)]
+    per, bufs, slots = per_sample_f0_batch(c, [tracks[j] for j in ok], [lengths[j] for j in ok], sr, f0_min, f0_merge_range)
+    pa = {"env": env, "knots": knots, "K": K, "f_off": f_off, "n_bins": c.n_bins, "f0": bufs[0] if bufs else None,
+          "mask": bufs[1] if bufs else None}
+    results = {j: (r, slots.get(q)) for q, (j, r) in enumerate(zip(ok, per))}
+    for j, i in enumerate(live):
+        r, slot = results.get(j, (tracks[j], None))
+        if isinstance(r, BaseException):
+            out[i] = r
+            continue
+        f0_j, mask_j = r
+        a, b = int(f_off[j]), int(f_off[j + 1])
+        out[i] = {"env": env[a:b] if want_env else None, "f0": f0_j, "mask": mask_j, "formants": formants[j], "T": b - a,
+                  "pass": pa, "slot": j, "f0_slot": slot}
     return out
 
 

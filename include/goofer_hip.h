@@ -342,6 +342,17 @@ int goofer_track_pitch(goofer_ctx *ctx, const double *y, const int64_t *sample_o
 int goofer_track_formants(goofer_ctx *ctx, const double *y, const int64_t *sample_off, int n_signals, int sr, int hop,
                           int64_t *frame_off, double *formants, void *scratch, int64_t *scratch_bytes, void *stream);
 
+/* gf.extract_features' f0 post-processing (GOOFER.py:957-966) for a ragged batch of frame-rate f0 tracks (goofer_amd/csrc/f0.hip):
+ * NaN -> 0, zero runs of at most max_gap frames with a neighbour on both sides bridged linearly (GOOFER.py:415-435), np.interp
+ * over np.linspace(0, n / sr) grids of the track and of the n samples (0 outside the track), clip to [1e-5, 2000].
+ * tracks [track_off[n_signals]] fp64 (device); track_off and sample_off [n_signals + 1] are HOST arrays starting at 0, every track
+ * with two frames at least (one frame or none: GOOFER_EINVAL; the host handles them).  Writes f0 and mask (f0 > f0_min as 0 / 1)
+ * [sample_off[n_signals]] fp64, bit for bit numpy's.  Call once with scratch = NULL (ctx may be NULL too) for *scratch_bytes; then
+ * with device scratch of that many bytes, the caller's and in use until the stream reaches the end of the call. */
+int goofer_per_sample_f0(goofer_ctx *ctx, const double *tracks, const int64_t *track_off, const int64_t *sample_off, int n_signals,
+                         double sr, double f0_min, int max_gap, double *f0, double *mask, void *scratch, int64_t *scratch_bytes,
+                         void *stream);
+
 /* ---- the hot path --------------------------------------------------------------------------- */
 
 /* gf.synthesize for a ragged batch (GOOFER.py:971-1220) + the V/B/U mix (SillySampler.py:1142-1151). */
