@@ -18,6 +18,10 @@
 
 constexpr int AN_ROWS = 4;
 
+// numpy's max / maximum: a NaN operand wins (fmax returns the other one).  On non-NaN operands this is fmax, so every
+// finite result keeps its bits; a NaN error's bit pattern orders above every finite one for the atomicMax below.
+__device__ __forceinline__ double nan_max(double a, double b) { return (a > b || a != a) ? a : b; }
+
 __global__ __launch_bounds__(256) void k_mag_rows(const float2 *__restrict__ S, int ldc, int64_t rows, int n_bins,
                                                   float *__restrict__ mag, int ld)
 {
@@ -48,7 +52,7 @@ __global__ __launch_bounds__(256) void k_gauss_rows64(const float *__restrict__ 
     }
 }
 
-// err_bits: max relative error as the bit pattern of a non-negative double (order-preserving for atomicMax)
+// err_bits: max relative error as the bit pattern of a non-negative double or NaN (order-preserving for atomicMax, NaN on top)
 __global__ __launch_bounds__(256) void k_knot_error(const double *__restrict__ env2, int ld64, const int64_t *__restrict__ probe,
                                                     int n_probe, int n_bins, const int *__restrict__ knot_bin, int K,
                                                     const int *__restrict__ lerp_idx, const float *__restrict__ w0,
@@ -61,7 +65,7 @@ __global__ __launch_bounds__(256) void k_knot_error(const double *__restrict__ e
     if (pi >= n_probe) return;
     const double *row = env2 + probe[pi] * (int64_t)ld64;
     float *kv = s_kv + wave * K;
-    for (int k = lane; k < K; k += WAVE) kv[k] = (float)log(fmax(row[knot_bin[k]], 1e-8));
+    for (int k = lane; k < K; k += WAVE) kv[k] = (float)log(nan_max(row[knot_bin[k]], 1e-8));
     wave_lds_sync();
     double worst = 0.0;
     for (int b = lane; b < n_bins; b += WAVE) {
@@ -69,10 +73,10 @@ __global__ __launch_bounds__(256) void k_knot_error(const double *__restrict__ e
         float rec = w0[b] * kv[i] + w1[b] * kv[i + 1];
         double e = row[b];
         double err = fabs((double)expf(rec) - e) / (e + 1e-8);
-        worst = fmax(worst, err);
+        worst = nan_max(worst, err);
     }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) worst = fmax(worst, __shfl_xor(worst, o, 64));
+    for (int o = 32; o > 0; o >>= 1) worst = nan_max(worst, __shfl_xor(worst, o, 64));
     if (lane == 0) atomicMax(err_bits, (unsigned long long)__double_as_longlong(worst));
 }
 
@@ -83,7 +87,7 @@ __global__ __launch_bounds__(256) void k_knot_gather(const double *__restrict__ 
     if (g >= rows * K) return;
     int64_t r = g / K;
     int k = (int)(g - r * K);
-    float v = (float)log(fmax(env2[r * ld64 + knot_bin[k]], 1e-8));     // log in fp64, cast to fp32 (DCOMPUTE)
+    float v = (float)log(nan_max(env2[r * ld64 + knot_bin[k]], 1e-8));     // log in fp64, cast to fp32 (DCOMPUTE)
     knots[g] = __float2half(v);                                         // then to fp16 (DSTORAGE)
 }
 
@@ -181,7 +185,7 @@ __global__ __launch_bounds__(256) void k_knot_search(const double *__restrict__ 
     int kb = 0;
     for (int c = 0; c < KN_CAND; ++c) {
         const int K = KN_K0 + KN_DK * c;
-        for (int k = lane; k < K; k += WAVE) kv[k] = (float)log(fmax(row[knot_bin[kb + k]], 1e-8));
+        for (int k = lane; k < K; k += WAVE) kv[k] = (float)log(nan_max(row[knot_bin[kb + k]], 1e-8));
         wave_lds_sync();
         const int *idx = lerp_idx + (size_t)c * n_bins;
         const float *a0 = w0 + (size_t)c * n_bins, *a1 = w1 + (size_t)c * n_bins;
@@ -191,10 +195,10 @@ __global__ __launch_bounds__(256) void k_knot_search(const double *__restrict__ 
             float rec = a0[b] * kv[i] + a1[b] * kv[i + 1];
             double e = row[b];
             double err = fabs((double)expf(rec) - e) / (e + 1e-8);
-            worst = fmax(worst, err);
+            worst = nan_max(worst, err);
         }
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) worst = fmax(worst, __shfl_xor(worst, o, 64));
+        for (int o = 32; o > 0; o >>= 1) worst = nan_max(worst, __shfl_xor(worst, o, 64));
         if (lane == 0) atomicMax(err_bits + (size_t)sig * KN_CAND + c, (unsigned long long)__double_as_longlong(worst));
         wave_lds_sync();                                                   // every lane is done with kv before the next K fills it
         kb += K;
@@ -222,7 +226,7 @@ __global__ __launch_bounds__(256) void k_knot_pick(const double *__restrict__ en
     const int64_t f0 = frame_off[s];
     if (r == f0 && k == 0) K_out[s] = K;
     if (k >= K) return;
-    float v = (float)log(fmax(env2[r * ld2 + knot_bin[kb + k]], 1e-8));
+    float v = (float)log(nan_max(env2[r * ld2 + knot_bin[kb + k]], 1e-8));
     knots[f0 * KN_KMAX + (r - f0) * K + k] = __float2half(v);
 }
 

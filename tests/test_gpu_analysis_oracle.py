@@ -1,0 +1,322 @@
+"""GPU: the cold-sample analysis against the oracle at every geometry voicebanks are analysed at, stage by stage, on both
+device paths (the per-file core.envelope_features and the batched Context.envelope_knots):
+
+(a) the sigma-2 envelope against the oracle's, and against the fp64 truth no worse than the oracle is;
+(b) the knot encoding of the GPU's own envelope: every candidate's fit error, K, hz_knots and fp16 knots;
+(c) K and knots end to end from the signal;
+(d) signals whose deciding candidate sits at eps (1 -+ 1e-2);
+(e) frames numpy's probe set skips (a burst there must not move K);
+(f) single non-finite samples (numpy's max and maximum propagate NaN);
+(g) folder mode's written .goofy files against the oracle's save_features.
+
+analysis_ref.py holds the restatement and the signals; test_analysis_ref.py checks their oracle margins on the CPU.
+"""
+import wave
+
+import numpy as np
+import pytest
+
+import analysis_ref as A
+from oracle import goofer_ref as R
+
+from goofer_amd import core, trackers
+
+pytestmark = pytest.mark.gpu
+
+ENV_RTOL, ENV_ATOL = 2e-6, 1e-9          # the golden envelope test's per-element bound
+# Kinds with deep spectral dips (harmonics, clipping, resonances, 40 dB level steps): numpy's own fp32 STFT is further than
+# the per-element bound from the fp64 truth in their dips (test_analysis_ref.py::test_dip_kinds_defeat_the_element_bound),
+# so for them the bound is 2e-6 of each frame's own maximum instead.  Silence and dither keep the per-element bound.
+FRAME_BOUND_KINDS = A.DIP_KINDS
+# The worst frame error against the fp64 truth over a geometry's signals: the GPU's <= 3 x the oracle's.  Measured on the
+# MI355X: 1.2 - 2.4 x (the 64-point FFT the most, where pocketfft is nearly exact; Bluestein 1000-point 2.0 x).  Per signal
+# the ratio means little: the oracle's own error is sometimes far below fp32 rounding by cancellation.
+TRUTH_FACTOR = 3.0
+FIT_TOL = 1e-5                           # per-candidate fit error: one fp32 ulp in the lerp, relative to 1 + err
+KNOT_ULP_FRAC = 1e-4                     # knots of one envelope: at most this fraction 1 fp16 ulp apart, none further
+E2E_EQUAL_FRAC = 0.995                   # knots from the signal: the golden test's share of equal entries
+E2E_MARGIN = 1e-3                        # K must match where the deciding oracle error is this far from eps (relative)
+FOLDER_RATES = (22050, 44100, 48000, 96000)
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    from goofer_amd.device import Context
+    c = Context(0)
+    yield c
+    c.close()
+
+
+def _batch(ctx, geom, sigs, want_env=False):
+    """Context.envelope_knots over a ragged batch: per signal (K, knots fp16 [K, T], sigma-2 envelope fp64 [bins, T] or None)."""
+    ctx.plan(*geom)
+    y = ctx.tensor(np.concatenate([np.asarray(s, dtype=np.float32) for s in sigs]))
+    knots, K, f_off, env = ctx.envelope_knots(y, [len(s) for s in sigs], want_env=want_env)
+    knots, K = knots.cpu().numpy(), K.cpu().numpy()
+    env = env.cpu().numpy() if want_env else None
+    out = []
+    for i in range(len(sigs)):
+        a, b = int(f_off[i]), int(f_off[i + 1])
+        vals = knots[a:b].reshape(-1)[:(b - a) * int(K[i])].reshape(b - a, int(K[i]))
+        out.append((int(K[i]), np.ascontiguousarray(vals.T), None if env is None else np.ascontiguousarray(env[a:b].T)))
+    return out
+
+
+def _gpu_candidate_errors(ctx, geom, env):
+    """ctx.knot_fit_error of every candidate on ``env`` [bins, T] (fp32 rows, sigma-0.5 blur and probes as
+    core.compress_env_to_knots makes them)."""
+    sr, n_fft, hop = geom
+    ctx.plan(*geom)
+    rows = ctx.tensor(np.ascontiguousarray(np.asarray(env).T, dtype=np.float32))
+    env2 = ctx.gauss_bins_f64(rows, core.gaussian_taps(0.5))
+    probe = ctx.tensor(A.probe_rows(rows.shape[0]).astype(np.int64))
+    out = []
+    for K in A.CANDIDATES:
+        hz, at = A.candidate_bins(sr, n_fft, K)
+        out.append(ctx.knot_fit_error(env2, probe, ctx.tensor(at.astype(np.int32)), hz))
+    return np.array(out)
+
+
+def _ulps(a, b):
+    """|a - b| in fp16 ulps at the pair's values (np.spacing, the larger of the two); equal non-finite entries count 0."""
+    a, b = np.asarray(a, dtype=np.float16), np.asarray(b, dtype=np.float16)
+    same = (a == b) | (np.isnan(a) & np.isnan(b))
+    sp = np.maximum(np.abs(np.spacing(a)), np.abs(np.spacing(b))).astype(np.float64)
+    with np.errstate(invalid="ignore"):
+        d = np.abs(a.astype(np.float64) - b.astype(np.float64)) / sp
+    return np.where(same, 0.0, d)
+
+
+def _knots_close(got, ref, env_ref, what):
+    """Knots from the signal against the oracle's: at most 1 fp16 ulp apart, plus twice the log-domain reach of the frame
+    bound of (a) where the knot sits in a dip (2 ENV_RTOL max(frame) / exp(knot)): there fp32 STFT noise of the loud bins
+    swamps the envelope on both sides.  Returns how many are equal."""
+    ref32 = ref.astype(np.float64)
+    reach = ENV_RTOL * np.max(env_ref, axis=0)[None, :] / np.exp(ref32)
+    tol = np.abs(np.spacing(ref.astype(np.float16))).astype(np.float64) + 2 * reach
+    d = np.abs(got.astype(np.float64) - ref32)
+    assert np.all(d <= tol), (what, float(np.max(d / tol)))
+    return int(np.sum(got == ref))
+
+
+def _in_band(errs, tol=FIT_TOL):
+    """The deciding candidates' oracle errors lie within one lerp ulp of eps: the GPU may decide either way."""
+    d = A.deciding(errs)
+    return bool(np.any(np.abs(d - A.EPS) <= tol * (1 + np.abs(d))))
+
+
+_RUNS = {}
+
+
+def _run(ctx, geom):
+    """Per geometry, once: the signals, the oracle's envelope / pack / candidate errors, the per-file and batched GPU results."""
+    if geom in _RUNS:
+        return _RUNS[geom]
+    sr, n_fft, hop = geom
+    recs = []
+    for kind, y in A.signal_set(sr, n_fft, hop):
+        env_o, pack_o = R.envelope_of(y, sr, n_fft, hop)
+        env_g, pack_g = core.envelope_features(y, sr, n_fft, hop, ctx=ctx)
+        recs.append(dict(kind=kind, y=y, env_o=env_o, pack_o=pack_o, err_o=A.candidate_errors(env_o, sr, n_fft),
+                         env_g=env_g, pack_g=pack_g))
+    for r, (K, vals, env) in zip(recs, _batch(ctx, geom, [r["y"] for r in recs], want_env=True)):
+        r.update(K_b=K, knots_b=vals, env_b=env)
+    _RUNS[geom] = recs
+    return recs
+
+
+GEOM_IDS = ["%d-%d-%d" % g for g in A.GEOMETRIES]
+
+
+# -- (a) envelope ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("geom", A.GEOMETRIES, ids=GEOM_IDS)
+def test_envelope_against_oracle_and_truth(ctx, geom):
+    sr, n_fft, hop = geom
+    e_gpu = e_ora = 0.0
+    for r in _run(ctx, geom):
+        what = (r["kind"], len(r["y"]))
+        for env in (r["env_g"], r["env_b"]):
+            assert env.dtype == np.float64 and env.shape == r["env_o"].shape, what
+            if r["kind"] in FRAME_BOUND_KINDS:
+                assert A.frame_error(env, r["env_o"]).max() <= ENV_RTOL, what
+            else:
+                np.testing.assert_allclose(env, r["env_o"], rtol=ENV_RTOL, atol=ENV_ATOL, err_msg=str(what))
+        truth = A.truth_envelope(r["y"], sr, n_fft, hop)
+        e_gpu = max(e_gpu, A.frame_error(r["env_g"], truth).max())
+        e_ora = max(e_ora, A.frame_error(r["env_o"], truth).max())
+    assert e_gpu <= TRUTH_FACTOR * e_ora, (e_gpu, e_ora)
+
+
+# -- (b) encoding, given the GPU's own envelope ---------------------------------------------------------------------
+@pytest.mark.parametrize("geom", A.GEOMETRIES, ids=GEOM_IDS)
+def test_encoding_of_the_gpu_envelope(ctx, geom):
+    sr, n_fft, hop = geom
+    ulps = []
+    for r in _run(ctx, geom):
+        what = (r["kind"], len(r["y"]))
+        env = r["env_g"]
+        pack = R.compress_env_to_knots(env, sr=sr, n_fft=n_fft)
+        errs = A.candidate_errors(env, sr, n_fft)
+        got = _gpu_candidate_errors(ctx, geom, env)
+        assert np.all(np.abs(got - errs) <= FIT_TOL * (1 + errs)), (what, got, errs)
+        K = len(pack["hz_knots"])
+        assert A.decide(errs)[0] == K
+        if _in_band(errs):
+            continue
+        assert len(r["pack_g"]["hz_knots"]) == K and r["K_b"] == K, (what, K, len(r["pack_g"]["hz_knots"]), r["K_b"])
+        assert np.array_equal(r["pack_g"]["hz_knots"], pack["hz_knots"]), what
+        for vals in (r["pack_g"]["knot_vals_log"], r["knots_b"]):
+            assert vals.dtype == np.float16 and vals.shape == pack["knot_vals_log"].shape, what
+            u = _ulps(vals, pack["knot_vals_log"])
+            assert u.max() <= 1.0, (what, u.max())
+            ulps.append(u.ravel())
+    ulps = np.concatenate(ulps)
+    assert np.mean(ulps > 0) <= KNOT_ULP_FRAC, np.mean(ulps > 0)
+
+
+# -- (c) end to end -------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("geom", A.GEOMETRIES, ids=GEOM_IDS)
+def test_knots_from_the_signal(ctx, geom):
+    equal, total = 0, 0
+    for r in _run(ctx, geom):
+        what = (r["kind"], len(r["y"]))
+        K = len(r["pack_o"]["hz_knots"])
+        Ks = (len(r["pack_g"]["hz_knots"]), r["K_b"])
+        if A.margin(r["err_o"]) > E2E_MARGIN:
+            assert Ks == (K, K), (what, K, Ks, r["err_o"])
+        for k, vals in zip(Ks, (r["pack_g"]["knot_vals_log"], r["knots_b"])):
+            if k != K:
+                continue
+            equal += _knots_close(vals, r["pack_o"]["knot_vals_log"], r["env_o"], what)
+            total += vals.size
+    assert equal >= E2E_EQUAL_FRAC * total, (equal, total)
+
+
+# -- (d) the eps decision boundary ----------------------------------------------------------------------------------
+def test_decision_boundary(ctx):
+    """Click amplitudes that put the deciding candidate's oracle error at eps (1 -+ 1e-2) for K = 32, 48 and 64: both
+    sides give the oracle's K on the per-file and on the batched path."""
+    geom = A.BOUNDARY_GEOM
+    cases = A.boundary_signals((0, 1, 2))
+    batch = _batch(ctx, geom, [y for _, _, y, _ in cases])
+    for (c, side, y, errs), (K_b, _, _) in zip(cases, batch):
+        K = A.CANDIDATES[c] if side < 0 else A.CANDIDATES[c + 1]
+        _, pack = core.envelope_features(y, *geom, ctx=ctx)
+        assert (len(pack["hz_knots"]), K_b) == (K, K), (c, side, errs)
+
+
+# -- (e) probe rows of the batch ------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", [((44100, 512, 512), T) for T in (295, 310, 343)] + [((16000, 64, 16), 65575)],
+                         ids=lambda c: "T%d" % c[1])
+def test_probe_rows_follow_numpy(ctx, case):
+    """A burst in the frame numpy's linspace floor skips leaves K at the oracle's 32; in the probed neighbour K rises with
+    the oracle's."""
+    geom, T = case
+    sr, n_fft, hop = geom
+    f = A.skipped_probes(T)[0]
+    sigs = [A.with_burst((T - 1) * hop, *A.own_samples(frame, n_fft, hop), sr, seed=frame) for frame in (f, f - 1)]
+    want = [len(R.envelope_of(y, *geom)[1]["hz_knots"]) for y in sigs]
+    assert want[0] == 32 and want[1] > 32
+    for y, K in zip(sigs, want):
+        assert len(core.envelope_features(y, *geom, ctx=ctx)[1]["hz_knots"]) == K
+        assert _batch(ctx, geom, [y])[0][0] == K
+    assert [k for k, _, _ in _batch(ctx, geom, sigs)] == want
+
+
+# -- (f) non-finite samples -----------------------------------------------------------------------------------------
+def _nonfinite_cases():
+    rng = np.random.default_rng(5)
+    silence = np.zeros(4000, dtype=np.float32)
+    noise = (0.1 * R.gauss1d(rng.standard_normal(4000), 8.0)).astype(np.float32)
+    long_T = 295
+    long_y = np.zeros((long_T - 1) * 512, dtype=np.float32)
+    cases = []
+    for name, geom, y, at, val in (("nan-silence", (44100, 1024, 256), silence, 2000, np.nan),
+                                   ("nan-noise", (44100, 1024, 256), noise, 2100, np.nan),
+                                   ("nan-unprobed", (44100, 512, 512), long_y, 98 * 512 + 7, np.nan),
+                                   ("inf-silence", (44100, 1024, 256), silence, 2000, np.inf)):
+        y = y.copy()
+        y[at] = val
+        cases.append((name, geom, y))
+    return cases
+
+
+@pytest.mark.parametrize("case", _nonfinite_cases(), ids=lambda c: c[0])
+def test_non_finite_sample(ctx, case):
+    """One NaN / Inf sample: the oracle's K and non-finite knots at the oracle's positions (NaN stays NaN), per file and in
+    a batch whose finite neighbours keep their results bit for bit."""
+    name, geom, y = case
+    sr, n_fft, hop = geom
+    with np.errstate(invalid="ignore", over="ignore"):
+        env_o, pack_o = R.envelope_of(y, sr, n_fft, hop)
+    K = len(pack_o["hz_knots"])
+    ref = pack_o["knot_vals_log"]
+    bad = ~np.isfinite(ref.astype(np.float32))
+    assert bad.any() and not bad.all()
+    if name == "nan-unprobed":
+        assert K == 32 and not set(np.flatnonzero(bad.any(axis=0))) & set(A.probe_rows(env_o.shape[1]).tolist())
+    else:
+        assert K == 192
+    rng = np.random.default_rng(11)
+    left = A.make_signal("voiced", 3000, sr, seed=3)
+    right = (0.2 * rng.standard_normal(2500)).astype(np.float32)
+    _, pack_g = core.envelope_features(y, sr, n_fft, hop, ctx=ctx)
+    (K_l, v_l, _), (K_b, v_b, _), (K_r, v_r, _) = _batch(ctx, geom, [left, y, right])
+    (K_l0, v_l0, _), (K_r0, v_r0, _) = _batch(ctx, geom, [left, right])
+    for k, vals in ((len(pack_g["hz_knots"]), pack_g["knot_vals_log"]), (K_b, v_b)):
+        assert k == K, (name, k, K)
+        assert np.array_equal(~np.isfinite(vals.astype(np.float32)), bad), name
+        if name.startswith("nan"):
+            assert np.all(np.isnan(vals[np.isnan(ref)])), name
+        assert _ulps(vals[~bad], ref[~bad]).max() <= 1.0, name
+    assert (K_l, K_r) == (K_l0, K_r0)
+    assert np.array_equal(v_l.view(np.uint16), v_l0.view(np.uint16)) and np.array_equal(v_r.view(np.uint16), v_r0.view(np.uint16))
+
+
+# -- (g) the written file -------------------------------------------------------------------------------------------
+def _tracker(y, sr, hop, n_frames):
+    """Deterministic tracks of the frame count alone: a gliding f0 with an unvoiced gap and formants 500 k Hz + a ramp."""
+    t = np.arange(n_frames)
+    f0 = 140.0 + 60.0 * np.sin(t / 7.0)
+    f0[n_frames // 3:n_frames // 3 + 6] = 0.0
+    return f0, {k: list(500.0 * k + 3.0 * t) for k in range(1, 6)}
+
+
+def _write_wav(path, y, sr):
+    with wave.open(str(path), "wb") as w:
+        w.setnchannels(1); w.setsampwidth(2); w.setframerate(sr)
+        w.writeframes(np.round(np.clip(y, -1, 1) * 32767).astype("<i2").tobytes())
+
+
+def test_folder_mode_files_match_the_oracle(ctx, tmp_path):
+    wavs = []
+    for i, sr in enumerate(FOLDER_RATES):
+        for kind in ("voiced", "clicks"):
+            p = tmp_path / f"{kind}_{sr}.wav"
+            _write_wav(p, A.make_signal(kind, int(0.35 * sr) + 17 * i, sr, seed=i), sr)
+            wavs.append(p)
+    done = trackers.extract_folder(tmp_path, tracker=_tracker, ctx=ctx)
+    assert done == {"extracted": len(wavs), "skipped": 0, "failed": 0}
+    equal = total = 0
+    for p in wavs:
+        y, sr = trackers.read_audio(p)
+        env, pack = R.envelope_of(y, sr, 1024, 256)
+        T = env.shape[1]
+        f0_track, forms = _tracker(y, sr, 256, T)
+        f0, vmask = trackers.per_sample_f0(f0_track, len(y), sr)
+        ref_path = tmp_path / (p.stem + "_oracle.npz")
+        R.save_features(ref_path, pack, f0, vmask, trackers.fit_formants(dict(forms), T), sr, len(y))
+        ref, got = R.load_features(ref_path), R.load_features(trackers.features_path(p))
+        for i in (1, 2, 3, 4, 5):                                # f0, mask, formants, sr, y_len
+            if isinstance(ref[i], dict):
+                assert sorted(ref[i]) == sorted(got[i]) and all(np.array_equal(ref[i][k], got[i][k]) for k in ref[i]), p.name
+            else:
+                assert np.array_equal(ref[i], got[i]) and np.asarray(got[i]).dtype == np.asarray(ref[i]).dtype, (p.name, i)
+        a, b = got[0], ref[0]
+        assert (a["mode"], a["n_bins"], a["n_fft"], a["sr"]) == (b["mode"], b["n_bins"], b["n_fft"], b["sr"]), p.name
+        if A.margin(A.candidate_errors(env, sr, 1024)) > E2E_MARGIN:
+            assert np.array_equal(a["hz_knots"], b["hz_knots"]), p.name
+        if a["knot_vals_log"].shape == b["knot_vals_log"].shape:
+            equal += _knots_close(a["knot_vals_log"], b["knot_vals_log"], env, p.name)
+            total += a["knot_vals_log"].size
+    assert total and equal >= E2E_EQUAL_FRAC * total, (equal, total)
