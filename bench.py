@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — resynth frames/s of the GOOFER hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--notes 1024] [--config 3]
+    python bench.py --gpus N --steps K --warmup W [--notes 1024] [--config 3] [--full]
 
 One process per GPU (the driver launches N>1 through torch.distributed.run; RANK / LOCAL_RANK /
 WORLD_SIZE / MASTER_* come from the environment).  A *step* is one pass of the hot path
@@ -10,7 +10,10 @@ their inputs to finished samples — and the per-note finish: 1 / max|S|, peak n
 of synthetic notes already resident in HBM.  Notes are independent, so ranks shard by note id with no data-path collective (weak scaling:
 `--notes` per GPU); the only collectives are the barriers and the MAX of the elapsed time.
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the contract
+fields (metric, value, unit, higher_is_better, dtype, ms_per_step) with the workload's description, nothing more.  With
+`--full` the line also carries
+  stage_ms      HIP-event time of every stage of the step (an untimed pass of the same steps), and of the assembly alone
   roofline      HIP-event duration of the longest kernel of the timed steps against its SURVEY 8(d) algorithmic bytes: `frac` is
                 that kernel's fraction of the 8 TB/s HBM peak; `traffic` (HBM bytes from the committed counter passes) only when
                 those passes were measured on this very source tree, else "stale": true; `valu`: its vector instructions per
@@ -18,11 +21,13 @@ Rank 0 prints ONE JSON line.  Besides the contract fields it carries
   config4 / config5   BASELINE configs 4 (10 000 notes, mixed loop modes) and 5 (96 kHz, n_fft 2048, hop 96) as fixed jobs on
                 this GPU, after the timed region: value, ms per pass, sub-batches, their own roofline + roofline_step
   value_skip_zero_off / value_unvoiced_30pct   the same step with no transform skipped / on 30 %-unvoiced sources
+  value_two_in_flight   the same launches alternating between two handles on two streams
   roofline_fft  the same for the framewise rFFT kernel (the kernel BASELINE's 40 % target names)
   roofline_step the whole step against its end-to-end algorithmic bytes and the HBM traffic the counter passes measured
   cpu_baseline  the numpy/C oracle (a port of the reference's CPU path) timed on this box's host cores: one thread, and a
                 pool of worker processes over notes
-  host_inclusive what a host that starts from argument strings pays around the step (decode, plan, upload, download)
+  pcie_inclusive / host_inclusive   what a host that hands over buffers / starts from argument strings pays around the step
+                (decode, plan, upload, download)
 
 `--job-notes N --config 4` (or 5) renders ONE fixed job of N notes instead: every rank derives the same
 longest-processing-time assignment from the notes' frame counts, renders its share in sub-batches, and the line reports
@@ -543,6 +548,9 @@ def main():
                     "ranks by longest-processing-time assignment, rendered in sub-batches; reports strong scaling")
     ap.add_argument("--sub-batch", type=int, default=4096, help="notes per device batch of a fixed job (4096: the pulse walk runs one wave per note, four rounds of resident waves at most; "
                     "smaller batches fill the device worse, one 10 000-note batch makes the walk the critical path)")
+    ap.add_argument("--full", action="store_true", help="measure and check everything beyond the headline as well: the CPU baseline, "
+                    "the per-stage times and rooflines, the variants of the step, the host-inclusive legs, BASELINE configs 4 / 5 "
+                    "(the --no-* options below leave parts of it out)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-host-inclusive", action="store_true")
     ap.add_argument("--no-variants", action="store_true", help="skip the skip_zero-off / 30 %%-unvoiced variants of the step")
@@ -572,7 +580,7 @@ def main():
     # The CPU baseline runs first, before this process touches the GPU: its pool leg starts worker processes, and nothing
     # that holds a device context should be forked / exec'd from.
     cpu_line = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         from goofer_amd import synthetic as syn0
         g0_ = syn0.config_geometry(args.config)
         n_ids = args.job_notes if args.job_notes > 0 else args.notes
@@ -635,6 +643,7 @@ def main():
     # Which kernel the roofline is about = the longest single-kernel stage of one more untimed step with every stage bracketed.
     # The timed steps then carry that stage's two HIP events only: the ~20 event records of the full breakdown are 0.06 ms of a
     # 2.3 ms step (scripts/prof_cost.py).  The breakdown itself (stage_ms) comes from a further untimed pass of the same steps.
+    # A plain run brackets its steps the same way, so that with and without --full the timed steps are the same launches.
     ctx.profile_begin(len(subs))
     step()
     pre = ctx.profile_end()
@@ -655,25 +664,27 @@ def main():
     timed = ctx.profile_end()
     scan1 = (ctx.counter("pulse_scanned_notes"), ctx.counter("pulse_fallback_notes"))
     ctx.profile_only(None)
-    ctx.profile_begin(args.steps * len(subs))
-    for k in range(args.steps):
-        step()
-    prof = ctx.profile_end()                                   # every stage, untimed pass
-    if dominant is not None:
-        prof["ms"][dominant] = timed["ms"][dominant] * prof["steps"] / max(1, timed["steps"])   # ... the dominant one from the timed steps
+    if args.full:
+        ctx.profile_begin(args.steps * len(subs))
+        for k in range(args.steps):
+            step()
+        prof = ctx.profile_end()                               # every stage, untimed pass
+        if dominant is not None:
+            prof["ms"][dominant] = timed["ms"][dominant] * prof["steps"] / max(1, timed["steps"])   # ... the dominant one from the timed steps
     # the timed path must have produced audio: finite, not silent (the last sub-batch of the last step)
     mix = last["mix"]
     assert bool(torch.isfinite(mix).all()) and float(mix.abs().max()) > 0.0, "the timed steps produced no valid audio"
     dumped = dump_outputs(args.dump_outputs, sub_ids, subs, kept, rank, world) if dump else None
     kept = None
-    # the assembly call on its own (the synth stages overlap on two streams, so step - sum(stages) no longer isolates it)
-    a0, a1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a0.record()
-    for _ in range(args.steps):
-        wl.renderer.assemble(wl.prep)
-    a1.record()
-    torch.cuda.synchronize()
-    prof["ms"]["assemble"] = a0.elapsed_time(a1) / args.steps * max(1, prof["steps"])
+    if args.full:
+        # the assembly call on its own (the synth stages overlap on two streams, so step - sum(stages) no longer isolates it)
+        a0, a1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a0.record()
+        for _ in range(args.steps):
+            wl.renderer.assemble(wl.prep)
+        a1.record()
+        torch.cuda.synchronize()
+        prof["ms"]["assemble"] = a0.elapsed_time(a1) / args.steps * max(1, prof["steps"])
     elapsed, frames_total = reduce_timing(elapsed, my_frames, device="cuda")
     per_rank = [my_frames]
     if world > 1:
@@ -682,28 +693,29 @@ def main():
         dist.all_gather(allf, t)
         per_rank = [int(round(v.item())) for v in allf]
 
-    # the framewise rFFT kernel on its own (the kernel BASELINE's >= 40 % HBM target names): same frames and
-    # CSR geometry as the batch, HIP events on the launch stream (k_frame_note, ~5 us, rides along)
-    o = wl.prep["offsets"]
-    xin = torch.randn(wl.samples, device="cuda")
-    Sout = torch.empty((wl.frames, (B + 15) & ~15), dtype=torch.complex64, device="cuda")      # 128-byte aligned rows
-    for _ in range(2):
-        ctx.rfft_frames(xin, o["d_s"], o["d_f"], wl.frames, out=Sout)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(args.steps):
-        ctx.rfft_frames(xin, o["d_s"], o["d_f"], wl.frames, out=Sout)
-    e1.record()
-    torch.cuda.synchronize()
-    rfft_ms = e0.elapsed_time(e1) / args.steps
-    del xin, Sout
+    if args.full:
+        # the framewise rFFT kernel on its own (the kernel BASELINE's >= 40 % HBM target names): same frames and
+        # CSR geometry as the batch, HIP events on the launch stream (k_frame_note, ~5 us, rides along)
+        o = wl.prep["offsets"]
+        xin = torch.randn(wl.samples, device="cuda")
+        Sout = torch.empty((wl.frames, (B + 15) & ~15), dtype=torch.complex64, device="cuda")      # 128-byte aligned rows
+        for _ in range(2):
+            ctx.rfft_frames(xin, o["d_s"], o["d_f"], wl.frames, out=Sout)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(args.steps):
+            ctx.rfft_frames(xin, o["d_s"], o["d_f"], wl.frames, out=Sout)
+        e1.record()
+        torch.cuda.synchronize()
+        rfft_ms = e0.elapsed_time(e1) / args.steps
+        del xin, Sout
 
     # The headline workload is fully voiced behind the notes' 50 ms offset, so the noise walker skips the unvoiced stem's
     # transform (exactly zero gain) on every frame.  Two variants of the same step say what that is worth: the skipping
     # switched off (both transforms on every frame: SURVEY 8d's "1 rFFT + 3 irFFT-OLA" literally), and 30 % of every source
     # unvoiced in 50 ms gaps.  Same notes, same flags, same step function; `value` stays the BASELINE workload.
     variants = None
-    if world == 1 and not job and not args.no_variants:
+    if args.full and world == 1 and not job and not args.no_variants:
         def timed(w, k):
             best = float("inf")
             for _ in range(2):                                 # the better of two passes (a first pass after a change of option /
@@ -734,7 +746,7 @@ def main():
     # so the f0 / envelope assembly of one batch runs beside the walkers and the gain pass of the other — how a job of many
     # batches is driven for throughput (the latency of a batch and `value` stay those of one batch at a time).  For a fixed job
     # the sub-batches of a pass alternate; for the weak-scaling workload whole steps do.
-    if world == 1 and not args.no_variants:
+    if args.full and world == 1 and not args.no_variants:
         ctx_b = Context(local)
         for name, val in options.items():
             ctx_b.set_option(name, val)
@@ -789,22 +801,7 @@ def main():
 
     if rank == 0:
         value = frames_total * args.steps / elapsed
-        steps = max(1, prof["steps"])
-        per = {k: v / steps for k, v in prof["ms"].items()}              # ms per launch (per sub-batch), this rank
-        # the dominant kernel = the longest single kernel of the step.  (Stages bracketing several launches — the assembly, the
-        # map kernels — and the latency-bound phase scan, which moves 4 B per sample by design, are not roofline candidates.)
-        # Some stages share the chip with the side stream: their event time includes that, see `shared_with`.
-        single = {k: v for k, v in per.items() if k not in MULTI_STAGES and v > 0} or per
-        dom = max(single, key=single.get)
-        per["rfft_frames_standalone"] = rfft_ms
-        Fb, Nb = my_frames / len(subs), my_samples / len(subs)           # frames / samples per launch (mean sub-batch)
-        Eb = sum(int(w.prep["assembly"].total_edit_rows) for w in subs) / len(subs)   # edited source rows per launch
-        Kmax = max(int(w.prep["assembly"].max_K) for w in subs)
-        executed = executed_share(ctx)
-        roof = make_roof(per, Fb, Nb, B, hop, n_fft, executed, Eb, Kmax, wl.frames, leg=None, counters=not job)
-
         step_ms = elapsed / args.steps * 1e3
-        alg_step = (4 * B + 20 * hop) * frames_total / world            # SURVEY 8d ALG_BYTES_FRAME x frames of one rank's step
         if job:
             shape = (f"BASELINE config {args.config} as ONE fixed job of {args.job_notes} notes sharded over {world} GPU(s) by "
                      f"longest-processing-time assignment on frame counts, sub-batches of {args.sub_batch} notes")
@@ -822,27 +819,45 @@ def main():
                        "notes_per_gpu": len(ids), "frames_per_gpu": my_frames, "samples_per_gpu": my_samples,
                        "sub_batches_per_gpu": len(subs),
                        "sharding": "independent notes, no data-path collective"},
-            "stage_ms": per,
-            "stage_ms_from": ("HIP events on the launch streams: `%s` (the roofline's kernel) from the timed steps, which carry its two "
-                              "events only; the other stages from an untimed pass of the same %d steps with every stage bracketed "
-                              "(twenty event records per step: 0.06 ms of it)" % (dominant, args.steps)),
             # pulse onsets (GOOFER.py:487-493): notes of the timed steps settled by the parallel phase scan, and those it had to
             # walk sequentially (a phase within the scan's rounding band of an integer) — rank 0's share
             "pulse_scan": {"notes": scan1[0] - scan0[0], "fallback_notes": scan1[1] - scan0[1]},
-            "roofline": roof(dom),                # the longest kernel of the step (the noise walker on the default workload)
-            "roofline_noise": roof("noise_stems") if per.get("noise_stems", 0) > 0 else None,
-            "roofline_harm": roof("harm_stem") if per.get("harm_stem", 0) > 0 else None,
-            # in-pipeline launch when the active path has a standalone rFFT stage, else the entry-point timing
-            "roofline_fft": roof("rfft_frames", wl.frames, wl.samples) if per.get("rfft_frames", 0) > 0
-            else roof("rfft_frames_standalone", wl.frames, wl.samples),
-            # the whole step against the end-to-end algorithmic bytes (4 B + 20 hop per frame) and, from the committed counter
-            # passes of this command, the HBM bytes all its kernels really moved
-            "roofline_step": {"bound": "hbm", "alg_bytes_per_step": alg_step, "achieved": alg_step / (step_ms * 1e-3) / 1e9,
-                              "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": alg_step / (step_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                              "traffic": None if job else pmc_step_traffic(wl.frames),
-                              "note": "the stem walkers are latency bound at two / three waves per SIMD (about 30 flop per algorithmic "
-                                      "byte): a quarter of the HBM peak and a quarter of the vector pipe each, DESIGN.md section 3"},
         }
+        if args.full:
+            steps = max(1, prof["steps"])
+            per = {k: v / steps for k, v in prof["ms"].items()}          # ms per launch (per sub-batch), this rank
+            # the dominant kernel = the longest single kernel of the step.  (Stages bracketing several launches — the assembly, the
+            # map kernels — and the latency-bound phase scan, which moves 4 B per sample by design, are not roofline candidates.)
+            # Some stages share the chip with the side stream: their event time includes that, see `shared_with`.
+            single = {k: v for k, v in per.items() if k not in MULTI_STAGES and v > 0} or per
+            dom = max(single, key=single.get)
+            per["rfft_frames_standalone"] = rfft_ms
+            Fb, Nb = my_frames / len(subs), my_samples / len(subs)       # frames / samples per launch (mean sub-batch)
+            Eb = sum(int(w.prep["assembly"].total_edit_rows) for w in subs) / len(subs)   # edited source rows per launch
+            Kmax = max(int(w.prep["assembly"].max_K) for w in subs)
+            executed = executed_share(ctx)
+            roof = make_roof(per, Fb, Nb, B, hop, n_fft, executed, Eb, Kmax, wl.frames, leg=None, counters=not job)
+            alg_step = (4 * B + 20 * hop) * frames_total / world        # SURVEY 8d ALG_BYTES_FRAME x frames of one rank's step
+            line.update({
+                "stage_ms": per,
+                "stage_ms_from": ("HIP events on the launch streams: `%s` (the roofline's kernel) from the timed steps, which carry its "
+                                  "two events only; the other stages from an untimed pass of the same %d steps with every stage bracketed "
+                                  "(twenty event records per step: 0.06 ms of it)" % (dominant, args.steps)),
+                "roofline": roof(dom),            # the longest kernel of the step (the noise walker on the default workload)
+                "roofline_noise": roof("noise_stems") if per.get("noise_stems", 0) > 0 else None,
+                "roofline_harm": roof("harm_stem") if per.get("harm_stem", 0) > 0 else None,
+                # in-pipeline launch when the active path has a standalone rFFT stage, else the entry-point timing
+                "roofline_fft": roof("rfft_frames", wl.frames, wl.samples) if per.get("rfft_frames", 0) > 0
+                else roof("rfft_frames_standalone", wl.frames, wl.samples),
+                # the whole step against the end-to-end algorithmic bytes (4 B + 20 hop per frame) and, from the committed counter
+                # passes of this command, the HBM bytes all its kernels really moved
+                "roofline_step": {"bound": "hbm", "alg_bytes_per_step": alg_step, "achieved": alg_step / (step_ms * 1e-3) / 1e9,
+                                  "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": alg_step / (step_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                  "traffic": None if job else pmc_step_traffic(wl.frames),
+                                  "note": "the stem walkers are latency bound at two / three waves per SIMD (about 30 flop per "
+                                          "algorithmic byte): a quarter of the HBM peak and a quarter of the vector pipe each, DESIGN.md "
+                                          "section 3"},
+            })
         if job or world > 1:
             line["per_rank_frames"] = per_rank
             line["imbalance"] = max(per_rank) / (sum(per_rank) / len(per_rank))
@@ -863,7 +878,7 @@ def main():
             line["value_two_in_flight"] = variants["two_in_flight"]["value"]
 
             line["variants"] = variants
-        if world == 1 and not job:
+        if args.full and world == 1 and not job:
             line["pcie_inclusive"] = pcie_leg(wl, elapsed / args.steps)
             if not args.no_host_inclusive:
                 line["host_inclusive"] = host_inclusive(wl, ctx, elapsed / args.steps)
@@ -875,7 +890,7 @@ def main():
             line["cpu_baseline"] = cpu_line
         # BASELINE configs 4 and 5 are 8-GPU jobs: their single-GPU passes ride on the default line, after the timed region,
         # each on a handle of its own (the default workload's buffers are released first)
-        if world == 1 and not job and args.config == 3 and not args.no_legs and not options:
+        if args.full and world == 1 and not job and args.config == 3 and not args.no_legs and not options:
             del last, mix, subs, wl
             ctx.close()
             torch.cuda.empty_cache()

@@ -7,9 +7,9 @@ root=$PWD
 out=$root/gpurun_out/prof_$tag
 dst=$root/gpurun_out/profiles_$tag
 mkdir -p "$out" "$dst"
-python3 bench.py --config $cfg --job-notes $notes --sub-batch $sub --steps 5 --warmup 2 --no-cpu-baseline > "$out/bench.json" 2> "$out/bench.err"
+python3 bench.py --full --config $cfg --job-notes $notes --sub-batch $sub --steps 5 --warmup 2 --no-cpu-baseline > "$out/bench.json" 2> "$out/bench.err"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d "$out/trace" -o r --output-format csv -- python3 "$root/bench.py" --config $cfg --job-notes $notes --sub-batch $sub --steps 2 --warmup 1 --no-cpu-baseline > "$out/trace.log" 2>&1
+rocprofv3 --kernel-trace --stats -d "$out/trace" -o r --output-format csv -- python3 "$root/bench.py" --full --config $cfg --job-notes $notes --sub-batch $sub --steps 2 --warmup 1 --no-cpu-baseline > "$out/trace.log" 2>&1
 cd "$root"
 python3 - "$out" "$dst" "$tag" <<'PY'
 import glob, json, shutil, sys

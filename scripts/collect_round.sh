@@ -19,7 +19,7 @@ for cfg in 4 5; do
   jt=${tag}_c${cfg}
   out=$root/gpurun_out/prof_$jt
   mkdir -p "$out"
-  args="--config $cfg --job-notes $notes --sub-batch 4096 --no-cpu-baseline"
+  args="--full --config $cfg --job-notes $notes --sub-batch 4096 --no-cpu-baseline"
   python3 bench.py $args --steps 10 --warmup 4 > "$out/bench.json" 2> "$out/bench.err"
   cd /tmp && export TMPDIR=/tmp
   # (traced / counted runs without the two-in-flight variant: its overlapped launches would sit in the per-kernel averages)

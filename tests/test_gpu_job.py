@@ -13,7 +13,7 @@ pytestmark = pytest.mark.gpu
 
 def test_bench_job_mode_line_on_one_gpu():
     here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, os.path.join(here, "bench.py"), "--gpus", "1", "--job-notes", "2048", "--config", "4", "--gather",
+    cmd = [sys.executable, os.path.join(here, "bench.py"), "--gpus", "1", "--full", "--job-notes", "2048", "--config", "4", "--gather",
            "--no-cpu-baseline", "--no-variants", "--no-host-inclusive", "--steps", "2", "--warmup", "1", "--sub-batch", "1024"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=here,
                          env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
