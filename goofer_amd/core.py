@@ -353,13 +353,12 @@ def knot_candidate_tables(sr, n_fft):
             np.ascontiguousarray(np.concatenate([_knot_bins(h, sr, n_fft, nb) for h in hz]), dtype=np.int32))
 
 
-def compress_env_to_knots(env_spec, sr, n_fft, eps=1e-2, K_start=32, K_step=16, K_max=192, smooth_sigma_bins=0.5, ctx=None,
-                          _rows=None):
+def compress_env_to_knots(env_spec, sr, n_fft, eps=1e-2, K_start=32, K_step=16, K_max=192, smooth_sigma_bins=0.5, ctx=None):
     """Smallest mel-knot count whose 2-tap lerp reproduces the (sigma 0.5 blurred) envelope to < eps max relative
     error on <= 256 probe frames; knots sampled at the nearest bin, log, fp16.  Blur, error metric and knot
     gather run on the device; the loop over the 9 candidate K is host logic."""
     c = _ctx(sr, n_fft, n_fft // 4, ctx)
-    rows = _rows if _rows is not None else c.rows_from(np.asarray(env_spec, dtype=np.float32).T)
+    rows = c.rows_from(np.asarray(env_spec, dtype=np.float32).T)
     T, nb = rows.shape
     taps = gaussian_taps(smooth_sigma_bins) if smooth_sigma_bins > 0 and int(4.0 * smooth_sigma_bins + 0.5) > 0 else np.ones(1)
     env2 = c.gauss_bins_f64(rows, taps)
@@ -379,17 +378,16 @@ def compress_env_to_knots(env_spec, sr, n_fft, eps=1e-2, K_start=32, K_step=16, 
 
 
 def envelope_features(y, sr, n_fft=1024, hop_length=256, ctx=None):
-    """(env_spec fp64 [bins, T], env_knots) = |stft| + 1e-8 -> sigma-2 bin blur -> knot encode (GOOFER.py:942-946, 968)."""
-    c = _ctx(sr, n_fft, hop_length, ctx)
+    """(env_spec fp64 [bins, T], env_knots) = |stft| + 1e-8 -> sigma-2 bin blur -> knot encode (GOOFER.py:942-946, 968):
+    one ``Context.envelope_knots`` call for this signal.  Raises ValueError for a signal that is not 1-D or is empty."""
+    from . import trackers
     y = np.asarray(y, dtype=np.float32)
-    n = len(y)
-    T = 1 + n // hop_length
-    S = c.rfft_frames(c.tensor(y), c.tensor(np.array([0, n], dtype=np.int64)), c.tensor(np.array([0, T], dtype=np.int64)), T)
-    env_rows = c.gauss_bins_f64(c.mag_rows(S), gaussian_taps(2.0))
-    env_spec = np.ascontiguousarray(env_rows.cpu().numpy().T)
-    rows32 = c.rows(T, c.n_bins)
-    rows32.copy_(env_rows.to(torch.float32))                  # to_compute(env_spec)
-    return env_spec, compress_env_to_knots(None, sr, n_fft, ctx=c, _rows=rows32)
+    if y.ndim != 1 or y.size == 0:
+        raise ValueError(f"envelope_features expects a non-empty mono signal, got shape {y.shape}")
+    c = _ctx(sr, n_fft, hop_length, ctx)
+    knots, K, f_off, env = c.envelope_knots(c.tensor(y), [y.size], want_env=True)
+    env_knots = trackers.knots_pack(knots.cpu().numpy(), K.cpu().numpy(), f_off, 0, sr, n_fft, c.n_bins)
+    return np.ascontiguousarray(env.cpu().numpy().T), env_knots
 
 
 def extract_features(y, sr, n_fft=1024, hop_length=256, f0_min=75, f0_max=600, f0_merge_range=2, pitch_tracker=None, ctx=None):
@@ -398,14 +396,19 @@ def extract_features(y, sr, n_fft=1024, hop_length=256, f0_min=75, f0_max=600, f
     ``pitch_tracker(y, sr, hop_length, n_frames) -> (f0_track [frames'], {1..5: [n_frames]})`` — the reference computes them
     with Praat (third-party, unpinned: SURVEY §8 c, parity unpinned): ``goofer_amd.trackers`` makes the reference's own
     parselmouth calls when that package is installed, ``GOOFER_TRACKER`` names another one, and without any this raises
-    ``trackers.TrackerUnavailable`` (a NotImplementedError).  ``f0_max`` is accepted and unused, as in the reference."""
+    ``trackers.TrackerUnavailable`` (a NotImplementedError).  ``f0_max`` is accepted and unused, as in the reference.
+    ``extract_features_batch`` of this one signal; raises the exception it reports for it (ValueError for a signal that is
+    not 1-D or is empty)."""
     from . import trackers
-    return trackers.analyse(y, sr, n_fft, hop_length, f0_min, f0_merge_range, tracker=pitch_tracker, ctx=ctx)
+    out = trackers.analyse_batch([y], sr, n_fft, hop_length, f0_min, f0_merge_range, tracker=pitch_tracker, ctx=ctx)[0]
+    if isinstance(out, BaseException):
+        raise out
+    return out
 
 
 def extract_features_batch(signals, sr, n_fft=1024, hop_length=256, f0_min=75, f0_merge_range=2, pitch_tracker=None, ctx=None):
     """``extract_features`` for a list of signals at one sample rate, in batched device passes: one 5-tuple per signal, or
-    the exception that signal raised.  The results equal ``extract_features`` run on each signal alone (trackers.analyse_batch)."""
+    the exception that signal raised (trackers.analyse_batch).  A signal's result does not depend on the others."""
     from . import trackers
     return trackers.analyse_batch(signals, sr, n_fft, hop_length, f0_min, f0_merge_range, tracker=pitch_tracker, ctx=ctx)
 

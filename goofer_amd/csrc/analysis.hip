@@ -1,14 +1,14 @@
 // Analysis half that does not need Praat (gfx950): spectral envelope of a wav and its mel-knot encoding.
 //
-//   k_mag_rows     |S| + 1e-8 of the STFT rows (fp32, like np.abs(complex64) + 1e-8)     GOOFER.py:945
 //   k_gauss_rows64 Gaussian FIR along bins with fp64 output (sigma = 0.5 pre-blur)       GOOFER.py:100
 //   k_knot_error   for one knot count K: max over probe frames and bins of
 //                  |exp(lerp(log knots)) - env| / (env + 1e-8)                            GOOFER.py:112-121
 //   k_knot_gather  log-envelope sampled at the knots' nearest bins -> fp16 [rows x K]     GOOFER.py:114-115, 126
-// The sigma = 2 blur of GOOFER.py:946 is goofer_gauss_bins; the K search loop (9 candidates) is host logic.
+// These serve compress_env_to_knots on a caller's envelope; its K search loop (9 candidates) is host logic.
 //
-// The batched analysis (goofer_envelope_knots_batch) runs the same arithmetic for a ragged batch of signals in three launches:
-//   k_env_rows_fused  k_mag_rows -> k_gauss_rows64 (sigma 2) -> fp32 cast -> k_gauss_rows64 (sigma 0.5) for one frame row, in LDS
+// The analysis of signals (goofer_envelope_knots_batch) runs the same arithmetic for a ragged batch in three launches:
+//   k_env_rows_fused  |S| + 1e-8 (fp32) -> k_gauss_rows64 (sigma 2) -> fp32 cast -> k_gauss_rows64 (sigma 0.5) for one frame
+//                     row, in LDS
 //   k_knot_search     every probe row of every signal against all KN_CAND knot counts; per (signal, candidate) the max of
 //                     k_knot_error's relative error
 //   k_knot_pick       per signal the first candidate under 1e-2 (else the last), then k_knot_gather's fp16 knots at its bins
@@ -21,18 +21,6 @@ constexpr int AN_ROWS = 4;
 // numpy's max / maximum: a NaN operand wins (fmax returns the other one).  On non-NaN operands this is fmax, so every
 // finite result keeps its bits; a NaN error's bit pattern orders above every finite one for the atomicMax below.
 __device__ __forceinline__ double nan_max(double a, double b) { return (a > b || a != a) ? a : b; }
-
-__global__ __launch_bounds__(256) void k_mag_rows(const float2 *__restrict__ S, int ldc, int64_t rows, int n_bins,
-                                                  float *__restrict__ mag, int ld)
-{
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int64_t r = (int64_t)blockIdx.x * AN_ROWS + wave;
-    if (r >= rows) return;
-    for (int b = lane; b < n_bins; b += WAVE) {
-        float2 s = S[r * ldc + b];
-        mag[r * ld + b] = hypotf(s.x, s.y) + 1e-8f;
-    }
-}
 
 __global__ __launch_bounds__(256) void k_gauss_rows64(const float *__restrict__ in, int ld, double *__restrict__ out, int ld64,
                                                       int64_t rows, int n_bins, const double *__restrict__ taps, int radius)
@@ -91,14 +79,6 @@ __global__ __launch_bounds__(256) void k_knot_gather(const double *__restrict__ 
     knots[g] = __float2half(v);                                         // then to fp16 (DSTORAGE)
 }
 
-int launch_mag_rows(goofer_ctx *ctx, const float2 *S, int ldc, int64_t rows, int n_bins, float *mag, int ld, hipStream_t st)
-{
-    if (rows <= 0) return GOOFER_OK;
-    hipLaunchKernelGGL(k_mag_rows, dim3((unsigned)((rows + AN_ROWS - 1) / AN_ROWS)), dim3(256), 0, st, S, ldc, rows, n_bins, mag, ld);
-    LAUNCH_CHECK(ctx);
-    return GOOFER_OK;
-}
-
 int launch_gauss_rows64(goofer_ctx *ctx, const float *in, int ld, double *out, int ld64, int64_t rows, int n_bins,
                         const double *d_taps, int radius, hipStream_t st)
 {
@@ -133,7 +113,7 @@ int launch_knot_gather(goofer_ctx *ctx, const double *env2, int ld64, int64_t ro
 // ---- the batched analysis ------------------------------------------------------------------------------------------------
 
 // One wave per frame row: |S| + 1e-8 (fp32), sigma-2 blur (fp64, optionally written out), rounded to fp32, sigma-0.5 blur (fp64)
-// into env2.  Same taps, tap order, reflect_index and casts as k_mag_rows -> k_gauss_rows64 -> .to(float32) -> k_gauss_rows64.
+// into env2.  Same taps, tap order, reflect_index and casts as hypotf + 1e-8 -> k_gauss_rows64 -> .to(float32) -> k_gauss_rows64.
 __global__ __launch_bounds__(256) void k_env_rows_fused(const float2 *__restrict__ S, int ldc, int64_t rows, int n_bins,
                                                         const double *__restrict__ taps_env, int r_env, const double *__restrict__ taps_fit,
                                                         int r_fit, double *__restrict__ env_rows, int ld64, double *__restrict__ env2, int ld2)

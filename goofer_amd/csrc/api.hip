@@ -42,7 +42,6 @@ int launch_frame_skip(goofer_ctx *, const double *, int64_t, const int64_t *, co
 int launch_mask_short(goofer_ctx *, const float *, const int64_t *, int, int64_t, const double *, int, double, double *, hipStream_t);
 int launch_assemble(goofer_ctx *, const goofer_assembly *, int *, int *, void *, hipStream_t);
 size_t env_row_rec_bytes();
-int launch_mag_rows(goofer_ctx *, const float2 *, int, int64_t, int, float *, int, hipStream_t);
 int launch_gauss_rows64(goofer_ctx *, const float *, int, double *, int, int64_t, int, const double *, int, hipStream_t);
 int launch_knot_error(goofer_ctx *, const double *, int, const int64_t *, int, int, const int *, int, const int *, const float *,
                       const float *, unsigned long long *, hipStream_t);
@@ -1092,13 +1091,6 @@ int goofer_knot_decode(goofer_ctx *ctx, const uint16_t *knots_f16, int K, const 
     HIP_TRY(ctx, hipMemcpyAsync(d_w1, w1.data(), n_bins * sizeof(float), hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));   // the host vectors die at return
     return launch_knot_decode(ctx, knots_f16, K, rows, d_idx, d_w0, d_w1, env, n_bins, ld, st);
-}
-
-int goofer_mag_rows(goofer_ctx *ctx, const float *S, int ldc, int64_t rows, int n_bins, float *mag, int ld, void *stream)
-{
-    if (!ctx) return GOOFER_EINVAL;
-    if (ldc < n_bins || ld < n_bins) return goofer_fail(ctx, GOOFER_EINVAL, "bad strides");
-    return launch_mag_rows(ctx, (const float2 *)S, ldc, rows, n_bins, mag, ld, (hipStream_t)stream);
 }
 
 int goofer_gauss_bins_f64(goofer_ctx *ctx, const float *in, int ld, double *out, int ld64, int64_t rows, int n_bins,

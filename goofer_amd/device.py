@@ -305,13 +305,6 @@ class Context:
                                                          _ptr(env), ld64, _ptr(scratch), C.byref(need), self._stream()))
         return knots, K, f_off, (env[:, :nb] if want_env else None)
 
-    def mag_rows(self, S):
-        """complex64 [R, >=n_bins] -> |S| + 1e-8 as fp32 rows."""
-        R, nb = S.shape
-        out = self.rows(R, nb)
-        self._check(self.lib.goofer_mag_rows(self.h, _ptr(S), S.stride(0), R, nb, _ptr(out), out.stride(0), self._stream()))
-        return out
-
     def gauss_bins_f64(self, rows, taps: np.ndarray):
         """fp32 rows -> fp64 rows (the reference's gaussian_filter1d returns float64)."""
         taps = np.ascontiguousarray(taps, dtype=np.float64)

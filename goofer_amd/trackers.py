@@ -13,8 +13,8 @@ This module is the plug for that half and the host logic the reference wraps aro
   ``get()`` resolves the tracker to use (argument, ``GOOFER_TRACKER=name`` or ``module:function``, Praat when present);
 * ``fix_f0_gaps`` (GOOFER.py:415-435) and ``per_sample_f0`` (GOOFER.py:957-966) — pinned by ``tests/golden/cold_cache.npz``,
   which ``make_golden.py`` generates by running the reference's own ``extract_features`` over a fake ``parselmouth``;
-* ``analyse`` / ``ensure_features`` / ``extract_folder``: wav -> features -> byte-compatible ``.goofy`` next to the wav;
-  ``analyse_batch`` / ``ensure_features_batch`` do the same for many samples in batched device passes.
+* ``analyse_batch`` / ``ensure_features_batch`` / ``extract_folder``: wav -> features -> byte-compatible ``.goofy`` next to
+  the wav, many samples per device pass; ``ensure_features`` is the batch of one.
 
 Nothing here re-implements Praat: the native tracker follows the published methods, not Praat's code.
 """
@@ -209,18 +209,6 @@ def _read_wav_stdlib(path):
 
 
 # -- analysis -> .goofy --------------------------------------------------------------------------------------------
-def analyse(y, sr, n_fft=1024, hop_length=256, f0_min=75, f0_merge_range=2, tracker=None, ctx=None):
-    """gf.extract_features (GOOFER.py:940-969): (env_spec fp64 [bins, T], f0 per sample, voicing mask, formants, env_knots).
-    Envelope and knots on the GPU; tracks from ``tracker`` (see ``get``)."""
-    from . import core
-    track_fn = get(tracker)
-    env_spec, env_knots = core.envelope_features(y, sr, n_fft, hop_length, ctx=ctx)
-    n_frames = env_spec.shape[1]
-    f0_track, formants = track_fn(np.asarray(y), sr, hop_length, n_frames)
-    f0, vmask = per_sample_f0(f0_track, len(y), sr, f0_min, f0_merge_range)
-    return env_spec, f0, vmask, fit_formants(dict(formants), n_frames), env_knots
-
-
 def features_path(audio_path) -> Path:
     p = Path(audio_path)
     return p.with_name(f"{p.stem}_features.goofy")
@@ -229,8 +217,7 @@ def features_path(audio_path) -> Path:
 def ensure_features(audio_path, n_fft=1024, hop_length=256, tracker=None, ctx=None) -> Path:
     """The sample's ``.goofy``: returned as is when it exists, else analysed from the wav and written the way the reference
     writes it (knots mode, fp16 f0 / mask, formant dict: save_features) — through a temporary file, so a concurrent render
-    never loads half a cache."""
-    from . import core
+    never loads half a cache.  ``ensure_features_batch`` of this one path; raises the exception it reports for it."""
     feat = features_path(audio_path)
     if feat.exists():
         return feat
@@ -238,9 +225,10 @@ def ensure_features(audio_path, n_fft=1024, hop_length=256, tracker=None, ctx=No
         raise FileNotFoundError(f"{audio_path} not found (and no {feat.name} beside it)")
     track_fn = get(tracker)                                      # before any work: the usual reason a cold sample cannot render
     logging.info("Extracting features")
-    y, sr = read_audio(audio_path)
-    _, f0, vmask, forms, knots = analyse(y, sr, n_fft, hop_length, tracker=track_fn, ctx=ctx)
-    return _write_features(feat, knots, f0, vmask, forms, sr, len(y))
+    out = ensure_features_batch([audio_path], n_fft, hop_length, tracker=track_fn, ctx=ctx, workers=1)[audio_path]
+    if isinstance(out, BaseException):
+        raise out
+    return out
 
 
 def _write_features(feat, knots, f0, vmask, forms, sr, y_len) -> Path:
@@ -369,9 +357,11 @@ def per_sample_f0_batch(c, tracks, n_samples, sr, f0_min=75, f0_merge_range=2):
 
 def analyse_batch(signals, sr, n_fft=1024, hop_length=256, f0_min=75, f0_merge_range=2, tracker=None, ctx=None, want_env=True,
                   timings=None):
-    """``analyse`` for many signals at one sample rate: one ``extract_features`` 5-tuple per signal, or the exception that
-    signal raised (env_spec is None unless ``want_env``).  ``analyse_device`` does the work; this brings its results to the
-    host.  ``timings``, a dict, collects seconds under "device" (upload to results on the host) and "host"."""
+    """gf.extract_features (GOOFER.py:940-969) for many signals at one sample rate: one 5-tuple (env_spec fp64 [bins, T], f0
+    per sample, voicing mask, formants, env_knots) per signal, or the exception that signal raised (env_spec is None unless
+    ``want_env``); a signal's result does not depend on the others.  Envelope and knots on the GPU; tracks from ``tracker``
+    (see ``get``).  ``analyse_device`` does the work; this brings its results to the host.  ``timings``, a dict, collects
+    seconds under "device" (upload to results on the host) and "host"."""
     import time
     import torch
     t0 = time.perf_counter()
@@ -391,16 +381,12 @@ def analyse_batch(signals, sr, n_fft=1024, hop_length=256, f0_min=75, f0_merge_r
     # the 0 / 1 mask comes over as bytes (an eighth of the fp64 copy) and is widened on the host: the same values
     mask_host = pa["mask"].to(torch.uint8).cpu().numpy().astype(np.float64) if pa["mask"] is not None else None
     t1 = time.perf_counter()
-    sr = int(sr)
     f_off = pa["f_off"]
     for i in live:
         r = res[i]
         j = r["slot"]
         a, b = int(f_off[j]), int(f_off[j + 1])
-        T, Kj = b - a, int(K[j])
-        vals = knots[a:b].reshape(-1)[:T * Kj].reshape(T, Kj).T
-        env_knots = {"mode": "knots", "knot_vals_log": np.ascontiguousarray(vals),
-                     "hz_knots": _mel_knots(sr, n_fft, Kj), "n_bins": int(pa["n_bins"]), "n_fft": int(n_fft), "sr": sr}
+        env_knots = knots_pack(knots, K, f_off, j, sr, n_fft, pa["n_bins"])
         env_spec = np.ascontiguousarray(env[a:b].T) if want_env else None
         if r["f0_slot"] is not None:
             s0, s1 = r["f0_slot"]
@@ -414,9 +400,16 @@ def analyse_batch(signals, sr, n_fft=1024, hop_length=256, f0_min=75, f0_merge_r
     return out
 
 
-def _mel_knots(sr, n_fft, K):
+def knots_pack(knots, K, f_off, j, sr, n_fft, n_bins):
+    """Signal j's knots dict (what compress_env_to_knots returns) from ``Context.envelope_knots``' knots [frames, 192] and K
+    as host arrays and its frame offsets ``f_off``: the [T, K] slice of its rows, transposed."""
     from . import core
-    return core.make_mel_knots(sr, n_fft, K)[1].astype(np.float32)
+    sr, a, b = int(sr), int(f_off[j]), int(f_off[j + 1])
+    T, Kj = b - a, int(K[j])
+    vals = knots[a:b].reshape(-1)[:T * Kj].reshape(T, Kj).T
+    return {"mode": "knots", "knot_vals_log": np.ascontiguousarray(vals),
+            "hz_knots": core.make_mel_knots(sr, n_fft, Kj)[1].astype(np.float32), "n_bins": int(n_bins), "n_fft": int(n_fft),
+            "sr": sr}
 
 
 def analyse_device(signals, sr, n_fft=1024, hop_length=256, f0_min=75, f0_merge_range=2, tracker=None, ctx=None, want_env=True,

@@ -287,8 +287,7 @@ int goofer_knot_decode(goofer_ctx *ctx, const uint16_t *knots_f16, int K, const 
 
 /* ---- analysis half that does not need Praat (GOOFER.py:942-946, 97-147) -------------------------------- */
 
-/* mag = abs(S) + 1e-8 per row (fp32).  S [rows x ldc] complex64 -> mag [rows x ld]. */
-int goofer_mag_rows(goofer_ctx *ctx, const float *S, int ldc, int64_t rows, int n_bins, float *mag, int ld, void *stream);
+/* The pieces of compress_env_to_knots for a caller's envelope (core.compress_env_to_knots runs the K search on the host). */
 
 /* gaussian_filter1d(axis=bins) with the reference's fp64 result kept: in fp32 [rows x ld] -> out fp64 [rows x ld64];
  * taps fp64 [2*radius+1] in HOST memory. */
@@ -309,8 +308,9 @@ int goofer_knot_gather(goofer_ctx *ctx, const double *env, int ld64, int64_t row
  * batch of fp32 signals y (device) at the plan's (sr, n_fft, hop): per signal gf.stft's T = 1 + n / hop frames (reflect-padded
  * at its own ends), |S| + 1e-8, the sigma-2 bin blur in fp64, rounded to fp32, the sigma-0.5 blur in fp64, then the smallest
  * knot count K of 32, 48, ..., 192 whose 2-tap lerp reproduces that envelope to < 1e-2 max relative error on the probe rows
- * linspace(0, T - 1, min(256, T)) (else 192), and log(max(env, 1e-8)) at its knots' bins as fp16.  The arithmetic is that of
- * goofer_mag_rows, goofer_gauss_bins_f64, goofer_knot_fit_error and goofer_knot_gather, bit for bit.
+ * linspace(0, T - 1, min(256, T)) (else 192), and log(max(env, 1e-8)) at its knots' bins as fp16.  Each signal's K and knots
+ * are what compress_env_to_knots' defaults (goofer_gauss_bins_f64, goofer_knot_fit_error, goofer_knot_gather) give for its
+ * env_rows rounded to fp32, bit for bit, and do not depend on the other signals of the batch.
  *   sample_off [n_signals+1], frame_off [n_signals+1]: HOST arrays; frame_off is written.  Every signal has >= 1 sample.
  *   taps_env [2*radius_env+1], taps_fit [2*radius_fit+1]: fp64 taps of the two blurs in HOST memory (core.gaussian_taps).
  *   hz_knots, knot_bin: fp32 knot frequencies and int32 nearest bins of the eleven candidates back to back (32 + 48 + ... + 192

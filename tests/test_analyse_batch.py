@@ -49,7 +49,7 @@ def test_planner_holds_every_signal_exactly_once_on_random_input():
         assert idx == sorted(idx)                                 # input order inside a pass
 
 
-def _per_file_error(fn):
+def _alone_error(fn):
     with pytest.raises(Exception) as info:
         fn()
     return info.value
@@ -57,7 +57,7 @@ def _per_file_error(fn):
 
 def test_refusals_carry_the_per_file_exception(tmp_path):
     """Too short for the native tracker, a sample rate it does not take, an unreadable and a missing file: each fails up front,
-    before any device work, with the type and message the per-file path raises for it."""
+    before any device work, with the type and message the tracker or ensure_features on that file alone raises for it."""
     short = _wav(tmp_path / "short.wav", np.zeros(100), 44100)
     slow = _wav(tmp_path / "slow.wav", np.zeros(4000), 4000)
     junk = tmp_path / "junk.wav"
@@ -66,10 +66,10 @@ def test_refusals_carry_the_per_file_exception(tmp_path):
     got = trackers.ensure_features_batch([short, slow, junk, missing, short], tracker="native")
     assert list(got) == [short, slow, junk, missing]
     expect = {
-        short: _per_file_error(lambda: trackers.native_tracker(np.zeros(100), 44100, 256, 1)),
-        slow: _per_file_error(lambda: trackers.native_tracker(np.zeros(4000), 4000, 256, 16)),
-        junk: _per_file_error(lambda: trackers.ensure_features(junk, tracker="native")),
-        missing: _per_file_error(lambda: trackers.ensure_features(missing, tracker="native")),
+        short: _alone_error(lambda: trackers.native_tracker(np.zeros(100), 44100, 256, 1)),
+        slow: _alone_error(lambda: trackers.native_tracker(np.zeros(4000), 4000, 256, 16)),
+        junk: _alone_error(lambda: trackers.ensure_features(junk, tracker="native")),
+        missing: _alone_error(lambda: trackers.ensure_features(missing, tracker="native")),
     }
     for path, err in expect.items():
         assert type(got[path]) is type(err) and str(got[path]) == str(err), path

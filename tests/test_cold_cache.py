@@ -107,6 +107,37 @@ def test_wav_reader_stdlib(tmp_path):
         trackers.ensure_features(tmp_path / "missing.wav", tracker=lambda *a: None)
 
 
+def test_ensure_features_missing_wav_and_existing_cache(tmp_path, caplog):
+    """Before any analysis: an existing .goofy is returned untouched (no tracker is resolved), a missing wav without one is a
+    FileNotFoundError naming both, found before the tracker; an unknown tracker fails before the log line and any work."""
+    import logging
+    wav = tmp_path / "a.wav"
+    feat = trackers.features_path(wav)
+    with pytest.raises(FileNotFoundError) as info:
+        trackers.ensure_features(wav, tracker="no-such-tracker")
+    assert str(info.value) == f"{wav} not found (and no a_features.goofy beside it)"
+    feat.write_bytes(b"old")
+    before = feat.stat().st_mtime_ns
+    assert trackers.ensure_features(wav, tracker="no-such-tracker") == feat
+    assert trackers.ensure_features(str(wav), tracker="no-such-tracker") == feat
+    assert feat.read_bytes() == b"old" and feat.stat().st_mtime_ns == before
+    b = tmp_path / "b.wav"
+    with wave.open(str(b), "wb") as w:
+        w.setnchannels(1); w.setsampwidth(2); w.setframerate(44100)
+        w.writeframes(np.zeros(10000, dtype="<i2").tobytes())
+    with caplog.at_level(logging.INFO), pytest.raises(trackers.TrackerUnavailable):
+        trackers.ensure_features(b, tracker="no-such-tracker")
+    assert "Extracting features" not in caplog.text
+    short = tmp_path / "c.wav"
+    with wave.open(str(short), "wb") as w:
+        w.setnchannels(1); w.setsampwidth(2); w.setframerate(44100)
+        w.writeframes(np.zeros(100, dtype="<i2").tobytes())
+    with caplog.at_level(logging.INFO), pytest.raises(ValueError, match="shorter than one pitch window"):
+        trackers.ensure_features(short, tracker="native")
+    assert caplog.text.count("Extracting features") == 1
+    assert sorted(p.name for p in tmp_path.iterdir()) == ["a_features.goofy", "b.wav", "c.wav"]
+
+
 @pytest.mark.gpu
 def test_extract_features_with_fixture_tracks_matches_reference():
     torch = pytest.importorskip("torch")

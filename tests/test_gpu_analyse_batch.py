@@ -1,5 +1,6 @@
-"""GPU: the batched cold-cache analysis against the per-file path, bit for bit — envelopes and knots
-(Context.envelope_knots), whole features (core.extract_features_batch), folder mode and the HTTP collector."""
+"""GPU: the cold-cache analysis of one signal alone against the same signal inside a many-signal pass, bit for bit —
+envelopes and knots (Context.envelope_knots), whole features (core.extract_features_batch), folder mode and the HTTP
+collector — and what the single-signal calls refuse."""
 import shutil
 import wave
 
@@ -139,6 +140,45 @@ def test_extract_features_batch_calls_another_tracker_per_signal(ctx):
     assert calls == [len(s) for s in sigs]
     for y, g in zip(sigs, got):
         _same_features(g, core.extract_features(y, SR, pitch_tracker=fake, ctx=ctx))
+
+
+def test_single_signal_calls_refuse_empty_and_non_mono(ctx):
+    """envelope_features / extract_features are the batch of one: an empty or a 2-D signal is the ValueError a pass gives it,
+    and the pass's other signals are unaffected."""
+    calls = []
+
+    def fake(y, sr, hop, n_frames):
+        calls.append(y)
+        return np.full(n_frames + 2, 150.0), {k: [500.0 * k] * n_frames for k in range(1, 6)}
+
+    good = _voiced(np.random.default_rng(3), 6000, SR)
+    for y in (np.zeros(0), np.zeros((2, 4096)), np.zeros((4096, 1))):
+        with pytest.raises(ValueError):
+            core.envelope_features(y, SR, ctx=ctx)
+        with pytest.raises(ValueError):
+            core.extract_features(y, SR, pitch_tracker=fake, ctx=ctx)
+        with pytest.raises(ValueError):
+            core.extract_features(y, SR, pitch_tracker="native", ctx=ctx)
+        bad, ok = core.extract_features_batch([y, good], SR, pitch_tracker=fake, ctx=ctx)
+        assert isinstance(bad, ValueError)
+        _same_features(ok, core.extract_features(good, SR, pitch_tracker=fake, ctx=ctx))
+    assert len(calls) == 6 and all(c is good for c in calls)
+
+
+def test_single_call_raises_the_host_trackers_exception(ctx):
+    """A host tracker is called once, with the signal itself, and its exception is what extract_features raises."""
+    err = RuntimeError("no tracks for this one")
+    calls = []
+
+    def failing(y, sr, hop, n_frames):
+        calls.append((y, sr, hop, n_frames))
+        raise err
+
+    y = _voiced(np.random.default_rng(4), 9000, SR)
+    with pytest.raises(RuntimeError) as info:
+        core.extract_features(y, SR, pitch_tracker=failing, ctx=ctx)
+    assert info.value is err
+    assert len(calls) == 1 and calls[0][0] is y and calls[0][1:] == (SR, 256, 1 + len(y) // 256)
 
 
 def test_folder_mode_batched(ctx, tmp_path):

@@ -1,5 +1,6 @@
 """GPU: the cold-sample analysis against the oracle at every geometry voicebanks are analysed at, stage by stage, on both
-device paths (the per-file core.envelope_features and the batched Context.envelope_knots):
+device runs (core.envelope_features on each signal alone, and Context.envelope_knots on all of a geometry's signals in one
+pass):
 
 (a) the sigma-2 envelope against the oracle's, and against the fp64 truth no worse than the oracle is;
 (b) the knot encoding of the GPU's own envelope: every candidate's fit error, K, hz_knots and fp16 knots;
@@ -109,7 +110,8 @@ _RUNS = {}
 
 
 def _run(ctx, geom):
-    """Per geometry, once: the signals, the oracle's envelope / pack / candidate errors, the per-file and batched GPU results."""
+    """Per geometry, once: the signals, the oracle's envelope / pack / candidate errors, the GPU results of each signal alone
+    and of all of them in one pass."""
     if geom in _RUNS:
         return _RUNS[geom]
     sr, n_fft, hop = geom
@@ -195,7 +197,7 @@ def test_knots_from_the_signal(ctx, geom):
 # -- (d) the eps decision boundary ----------------------------------------------------------------------------------
 def test_decision_boundary(ctx):
     """Click amplitudes that put the deciding candidate's oracle error at eps (1 -+ 1e-2) for K = 32, 48 and 64: both
-    sides give the oracle's K on the per-file and on the batched path."""
+    sides give the oracle's K alone and in one pass."""
     geom = A.BOUNDARY_GEOM
     cases = A.boundary_signals((0, 1, 2))
     batch = _batch(ctx, geom, [y for _, _, y, _ in cases])
@@ -243,8 +245,8 @@ def _nonfinite_cases():
 
 @pytest.mark.parametrize("case", _nonfinite_cases(), ids=lambda c: c[0])
 def test_non_finite_sample(ctx, case):
-    """One NaN / Inf sample: the oracle's K and non-finite knots at the oracle's positions (NaN stays NaN), per file and in
-    a batch whose finite neighbours keep their results bit for bit."""
+    """One NaN / Inf sample: the oracle's K and non-finite knots at the oracle's positions (NaN stays NaN), alone and in a
+    batch whose finite neighbours keep their results bit for bit."""
     name, geom, y = case
     sr, n_fft, hop = geom
     with np.errstate(invalid="ignore", over="ignore"):

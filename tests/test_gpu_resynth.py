@@ -237,13 +237,14 @@ def test_resynthesize_keeps_features_on_the_device(ctx, monkeypatch):
 
 
 # -- analyse_batch with the kernel ------------------------------------------------------------------------------------
-def test_analyse_batch_with_kernel_equals_analyse(ctx, tmp_path):
+def test_analyse_batch_with_kernel_equals_extract_features(ctx, tmp_path):
+    """Each signal of a six-signal pass against the same signal alone (core.extract_features), bit for bit, .goofy bytes too."""
     rng = np.random.default_rng(15)
     sr = 44100
     signals = [_voiced(rng, int(rng.integers(sr // 4, 2 * sr)), sr) for _ in range(6)]
     batch = trackers.analyse_batch(signals, sr, tracker="native", ctx=ctx)
     for k, (y, b) in enumerate(zip(signals, batch)):
-        one = trackers.analyse(y, sr, tracker="native", ctx=ctx)
+        one = core.extract_features(y, sr, pitch_tracker="native", ctx=ctx)
         for x, z in zip(one[:3], b[:3]):
             assert np.array_equal(x, z)
         assert one[3] == b[3]
