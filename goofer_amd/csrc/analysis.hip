@@ -214,7 +214,10 @@ int launch_env_rows_fused(goofer_ctx *ctx, const float2 *S, int ldc, int64_t row
                           const double *taps_fit, int r_fit, double *env_rows, int ld64, double *env2, int ld2, hipStream_t st)
 {
     if (rows <= 0) return GOOFER_OK;
-    hipLaunchKernelGGL(k_env_rows_fused, dim3((unsigned)((rows + AN_ROWS - 1) / AN_ROWS)), dim3(256), sizeof(float) * 2 * AN_ROWS * n_bins,
+    const size_t lds = sizeof(float) * 2 * AN_ROWS * n_bins;
+    if (lds > 64 * 1024)                                       // n_fft above 2048: 65.6 KB at 2049 bins
+        if (int arc = kernel_allow_max_lds(ctx, (const void *)k_env_rows_fused)) return arc;
+    hipLaunchKernelGGL(k_env_rows_fused, dim3((unsigned)((rows + AN_ROWS - 1) / AN_ROWS)), dim3(256), lds,
                        st, S, ldc, rows, n_bins, taps_env, r_env, taps_fit, r_fit, env_rows, ld64, env2, ld2);
     LAUNCH_CHECK(ctx);
     return GOOFER_OK;
@@ -226,6 +229,8 @@ int launch_knot_search(goofer_ctx *ctx, const double *env2, int ld2, const int64
 {
     if (n_probe <= 0) return GOOFER_OK;
     const size_t lds = AN_ROWS * (sizeof(double) * n_bins + sizeof(float) * KN_KMAX);
+    if (lds > 64 * 1024)                                       // n_fft above 2048: 68.6 KB at 2049 bins
+        if (int arc = kernel_allow_max_lds(ctx, (const void *)k_knot_search)) return arc;
     hipLaunchKernelGGL(k_knot_search, dim3((n_probe + AN_ROWS - 1) / AN_ROWS), dim3(256), lds, st, env2, ld2, probe_row, probe_sig, n_probe,
                        n_bins, knot_bin, lerp_idx, w0, w1, err_bits);
     LAUNCH_CHECK(ctx);

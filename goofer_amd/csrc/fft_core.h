@@ -602,3 +602,65 @@ __device__ __forceinline__ void rfft_split(const float2 *buf, const float2 *twh,
         put(M, make_float2(z0.x - z0.y, 0.f));
     }
 }
+
+// ---------------------------------------------------------------------------------------------
+// Workgroup transform (complex N = 2048 / 4096: the real n_fft 4096 transform and the Bluestein length of the even n_fft in
+// [2052, 4094]).  One wave would hold 32 / 64 points per lane, past the register file, so the frame is shared by the four
+// waves of a 256-thread workgroup: a thread holds N / 256 = 8 / 16 points, x[tid + 256 t]; the first radix-(N / 256) pass runs
+// in registers, the later Stockham passes (radix 8, 8, 4 / 16, 16) exchange through one padded LDS buffer of N float2 per
+// workgroup, between __syncthreads().  Same butterflies, twiddle rule and index map as radix8_pass.
+constexpr int WG_THREADS = 256;
+
+template <int N> struct wg_cfg {
+    static constexpr int P = N / WG_THREADS;                  // points per thread == first-pass radix
+    static constexpr int BUF = N + (N >> 5);                  // padded float2 slots of the workgroup's buffer
+};
+
+// Radix-R Stockham pass over the workgroup buffer, NS = product of the radices already applied.  Reads x[b + t N / R], writes
+// y[(b / NS) NS R + b % NS + t NS]; every thread's reads precede every thread's writes.
+template <int N, int R, int NS>
+__device__ __forceinline__ void wg_radix_pass(float2 *buf, const float2 *tw, int tid)
+{
+    constexpr int NB = N / R, PER = NB / WG_THREADS, STEP = N / (R * NS);
+    static_assert(NB % WG_THREADS == 0, "whole butterflies per thread");
+    float2 v[PER][R];
+#pragma unroll
+    for (int u = 0; u < PER; ++u) {
+        const int b = tid + WG_THREADS * u;
+#pragma unroll
+        for (int t = 0; t < R; ++t) v[u][t] = buf[lds_pad(b + t * NB)];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < PER; ++u) {
+        const int b = tid + WG_THREADS * u, k = b % NS;
+#pragma unroll
+        for (int t = 1; t < R; ++t) v[u][t] = cmul(v[u][t], tw[t * k * STEP]);   // exp(-2 pi i t k / (R NS)); t k STEP < N
+        dft<R>::run(v[u]);
+        const int j0 = (b / NS) * NS * R + k;
+#pragma unroll
+        for (int t = 0; t < R; ++t) buf[lds_pad(j0 + t * NS)] = v[u][t];
+    }
+    __syncthreads();
+}
+
+// Complex forward FFT of size N for one workgroup.  `v` holds x[tid + 256 t], t < N / 256, on entry; the result is left in
+// natural order in `buf` (padded).  `tw`: the N-entry table exp(-2 pi i k / N).  The caller has finished with `buf` (barrier).
+template <int N>
+__device__ __forceinline__ void wg_fft(float2 *v, float2 *buf, const float2 *tw, int tid)
+{
+    constexpr int P = wg_cfg<N>::P;
+    static_assert(N == 2048 || N == 4096, "radix plan for 2048 = 8 8 8 4 and 4096 = 16 16 16");
+    dft<P>::run(v);                                           // pass 0: NS = 1, no twiddle, y[tid P + t]
+#pragma unroll
+    for (int t = 0; t < P; ++t) buf[lds_pad(tid * P + t)] = v[t];
+    __syncthreads();
+    if constexpr (N == 2048) {
+        wg_radix_pass<N, 8, 8>(buf, tw, tid);
+        wg_radix_pass<N, 8, 64>(buf, tw, tid);
+        wg_radix_pass<N, 4, 512>(buf, tw, tid);
+    } else {
+        wg_radix_pass<N, 16, 16>(buf, tw, tid);
+        wg_radix_pass<N, 16, 256>(buf, tw, tid);
+    }
+}

@@ -22,6 +22,11 @@ from . import sampler as S
 from .device import Context, default_context, default_params, row_stride
 
 
+# The assembly and render kernels of the resampler path stop at the reference sampler's geometry family (SillySampler.py:14
+# fixes n_fft 1024); gf.synthesize's sizes above 2048 are core.synthesize's only.
+RENDER_N_FFT_MAX = 2048
+
+
 @dataclass
 class Source:
     """Features of one voicebank sample, as stored in ``<stem>_features.goofy`` (knots mode, or the dense 'full'
@@ -610,6 +615,10 @@ class Renderer:
             srcs = [j[0] for j in jobs]
             rb = S.RequestBatch.from_requests([j[1] for j in jobs])
         sr, n_fft = srcs[0].sr, srcs[0].n_fft
+        bad_fft = [sc.n_fft for sc in srcs if sc.n_fft > RENDER_N_FFT_MAX]
+        if bad_fft:                                             # before anything is uploaded or launched
+            raise ValueError(f"the resampler renders sources analysed at n_fft <= {RENDER_N_FFT_MAX} (got n_fft {bad_fft[0]}); "
+                             "goofer_amd.core.synthesize takes the larger sizes")
         n = rb.n
         c = rb.col
         # the samples' rows in the arena's tables (a voicebank sample rendered by several notes is resident once: same Source object)

@@ -237,9 +237,10 @@ const char *goofer_last_error(const goofer_ctx *ctx);
 const char *goofer_version(void);
 
 /* Tables per (sr, n_fft, hop): sqrt-Hann window, bin freqs, boost, brightness curves, FFT twiddles
- * (GOOFER.py:12-46, 585-595).  n_fft: 512, 768, 1024, 1536, 2048 (radix plans; the stem walkers run at 1024 with hop 256, the
- * fused overlap-add at the three powers of two) or any other even size in [64, 2048] (Bluestein's chirp-z transform through
- * power-of-two transforms, one kernel per reference step); re-planning replaces the tables. */
+ * (GOOFER.py:12-46, 585-595).  n_fft: 512, 768, 1024, 1536, 2048, 4096 (radix plans; the stem walkers run at 1024 with hop 256,
+ * the fused overlap-add at 512 / 1024 / 2048; at 4096 one workgroup shares a frame) or any other even size in [64, 4096] but 2050
+ * (Bluestein's chirp-z transform through power-of-two transforms, one kernel per reference step; above 2048 at length 4096 on
+ * the workgroup transform); re-planning replaces the tables.  The resampler's assembly and render calls take n_fft <= 2048. */
 int goofer_plan(goofer_ctx *ctx, int sr, int n_fft, int hop);
 
 /* Pre-size handle-owned scratch for batches up to these totals (else grown on demand). */
