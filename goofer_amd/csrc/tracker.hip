@@ -75,10 +75,14 @@ __device__ __forceinline__ double wave_sum_d(double v)
     return v;
 }
 
+// numpy's max: a NaN operand wins (fmax returns the other one).  On non-NaN operands this is fmax, so every finite result
+// keeps its bits.
+__device__ __forceinline__ double nan_max(double a, double b) { return (a > b || a != a) ? a : b; }
+
 __device__ __forceinline__ double wave_max_d(double v)
 {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+    for (int o = 32; o > 0; o >>= 1) v = nan_max(v, __shfl_xor(v, o, 64));
     return v;
 }
 
@@ -100,11 +104,11 @@ __device__ double block_max_d(double v, double *red)
     __syncthreads();
     if ((threadIdx.x & 63) == 0) red[wave] = v;
     __syncthreads();
-    return fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+    return nan_max(nan_max(red[0], red[1]), nan_max(red[2], red[3]));
 }
 
 // ---- pitch -------------------------------------------------------------------------------------------------------
-// stats[2 s] = mean of signal s, stats[2 s + 1] = max |y - mean|
+// stats[2 s] = mean of signal s, stats[2 s + 1] = max |y - mean|, NaN when a sample is NaN or infinite (as numpy's max)
 __global__ __launch_bounds__(TR_THREADS) void k_pitch_stats(const double *__restrict__ y, const int64_t *__restrict__ soff,
                                                             double *__restrict__ stats)
 {
@@ -115,7 +119,7 @@ __global__ __launch_bounds__(TR_THREADS) void k_pitch_stats(const double *__rest
     for (int64_t j = threadIdx.x; j < n; j += TR_THREADS) acc += y[a + j];
     const double mean = block_sum_d(acc, red) / (double)n;
     double pk = 0.0;
-    for (int64_t j = threadIdx.x; j < n; j += TR_THREADS) pk = fmax(pk, fabs(y[a + j] - mean));
+    for (int64_t j = threadIdx.x; j < n; j += TR_THREADS) pk = nan_max(pk, fabs(y[a + j] - mean));
     pk = block_max_d(pk, red);
     if (threadIdx.x == 0) {
         stats[2 * s] = mean;
@@ -152,7 +156,7 @@ __global__ __launch_bounds__(TR_THREADS) void k_pitch_frames(const double *__res
     double pk = 0.0, e = 0.0;
     for (int j = threadIdx.x; j < W; j += TR_THREADS) {
         const double v = xw[j] - mean;
-        pk = fmax(pk, fabs(v));
+        pk = nan_max(pk, fabs(v));
         const double u = v * win[j];
         xw[j] = u;
         e += u * u;
@@ -160,7 +164,8 @@ __global__ __launch_bounds__(TR_THREADS) void k_pitch_frames(const double *__res
     pk = block_max_d(pk, red);
     const double r0 = block_sum_d(e, red);               // also orders the xw writes before the lag products
     const double gp = stats[2 * s + 1];
-    const double ratio = gp > TR_SILENT_PEAK ? pk / gp : 0.0;
+    // a NaN peak (a non-finite sample) gives a NaN ratio, and fmax(0, NaN) = 0 as Python's max(0.0, nan): uv = TR_VOICING
+    const double ratio = !(gp <= TR_SILENT_PEAK) ? pk / gp : 0.0;
     const double uv = TR_VOICING + fmax(0.0, 2.0 - ratio / (TR_SILENCE / (1.0 + TR_VOICING)));
     double *cf = cand_f + f * TR_MAX_CAND, *cs = cand_s + f * TR_MAX_CAND;
     if (!(r0 > 0.0)) {
@@ -224,7 +229,8 @@ __device__ __forceinline__ double pitch_transition(double fp, double fc, double 
     return TR_OCTAVE_JUMP * tsc * fabs(log2(fp / fc));
 }
 
-// One wave per signal: lane c holds candidate c of the current frame; back pointers go to global memory.
+// One wave per signal: lane c holds candidate c of the current frame; back pointers go to global memory.  The first best
+// predecessor wins a tie, and the first best candidate of the last frame.
 __global__ __launch_bounds__(WAVE) void k_pitch_viterbi(const int64_t *__restrict__ foff, const double *__restrict__ cand_f,
                                                         const double *__restrict__ cand_s, const int *__restrict__ cand_n,
                                                         double tsc, unsigned char *__restrict__ back, double *__restrict__ f0)
@@ -234,16 +240,17 @@ __global__ __launch_bounds__(WAVE) void k_pitch_viterbi(const int64_t *__restric
     const int s = blockIdx.x, c = threadIdx.x;
     const int64_t a = foff[s], nf = foff[s + 1] - a;
     if (nf <= 0) return;
+    const int n0 = min(max(cand_n[a], 1), TR_MAX_CAND);   // a caller's count outside [1, 15] is clamped into it
     if (c < TR_MAX_CAND) {
-        const bool on = c < cand_n[a];
+        const bool on = c < n0;
         pf[c] = on ? cand_f[a * TR_MAX_CAND + c] : 0.0;
         pd[c] = on ? cand_s[a * TR_MAX_CAND + c] : -INFINITY;
     }
-    if (c == 0) pn = cand_n[a];
+    if (c == 0) pn = n0;
     wave_lds_sync();
     for (int64_t i = 1; i < nf; ++i) {
         const int64_t fr = a + i;
-        const int cn = cand_n[fr];
+        const int cn = min(max(cand_n[fr], 1), TR_MAX_CAND);
         double fc = 0.0, best = -INFINITY;
         int arg = 0;
         if (c < cn) {
@@ -349,7 +356,7 @@ __global__ __launch_bounds__(WAVE) void k_formant_frames(const double *__restric
         const int64_t q = st + j;
         const double v = (q > 0 ? x[q] - alpha * x[q - 1] : x[q]) * gwin[j];
         fe[j] = be[j] = v;
-        pk = fmax(pk, fabs(v));
+        pk = nan_max(pk, fabs(v));
     }
     double *out = formants + f * FM_N;
     if (wave_max_d(pk) == 0.0) {
@@ -477,6 +484,18 @@ int check_batch(goofer_ctx *ctx, const int64_t *sample_off, int n_sig, int sr, i
     return GOOFER_OK;
 }
 
+// sr and hop as check_batch takes them, and offsets off[0..n_sig] that start at 0 and never decrease
+int check_offsets(goofer_ctx *ctx, const int64_t *off, int n_sig, int sr, int hop, const char *what)
+{
+    if (!off || n_sig <= 0) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: empty batch");
+    if (sr < TR_SR_MIN || sr > TR_SR_MAX) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: sample rate %d outside [%d, %d]", sr, TR_SR_MIN, TR_SR_MAX);
+    if (hop <= 0) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: hop %d", hop);
+    if (off[0] != 0) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: %s[0] must be 0", what);
+    for (int s = 0; s < n_sig; ++s)
+        if (off[s + 1] < off[s]) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: %s decreases at signal %d", what, s);
+    return GOOFER_OK;
+}
+
 template <typename T>
 T *carve(char *&p, size_t count)
 {
@@ -488,8 +507,9 @@ T *carve(char *&p, size_t count)
 }  // namespace
 
 /* Exported: see include/goofer_hip.h */
-extern "C" int goofer_track_pitch(goofer_ctx *ctx, const double *y, const int64_t *sample_off, int n_signals, int sr, int hop,
-                                  int64_t *frame_off, double *f0, void *scratch, int64_t *scratch_bytes, void *stream)
+extern "C" int goofer_track_candidates(goofer_ctx *ctx, const double *y, const int64_t *sample_off, int n_signals, int sr, int hop,
+                                       int64_t *frame_off, double *cand_f, double *cand_s, int32_t *cand_n, void *scratch,
+                                       int64_t *scratch_bytes, void *stream)
 {
     int rc = check_batch(ctx, sample_off, n_signals, sr, hop, pitch_min_length(sr));
     if (rc) return rc;
@@ -499,22 +519,18 @@ extern "C" int goofer_track_pitch(goofer_ctx *ctx, const double *y, const int64_
     const int64_t F = frame_off[n_signals];
     const pitch_geom g = pitch_geometry(sr);
     const size_t need = 2 * align256(8 * (size_t)(n_signals + 1)) + align256(16 * (size_t)n_signals) + align256(8 * (size_t)g.W) +
-                        align256(8 * (size_t)(g.hi + 1)) + 2 * align256(8 * TR_MAX_CAND * (size_t)F) + align256(4 * (size_t)F) +
-                        align256(TR_MAX_CAND * (size_t)F);
+                        align256(8 * (size_t)(g.hi + 1));
     if (!scratch) {
         *scratch_bytes = (int64_t)need;
         return GOOFER_OK;
     }
     if (!ctx) return GOOFER_EINVAL;
-    if (!y || !f0) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: null signal / f0");
+    if (!y || !cand_f || !cand_s || !cand_n) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: null signal / candidates");
     if (*scratch_bytes < (int64_t)need) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: scratch of %lld bytes, %zu needed", (long long)*scratch_bytes, need);
     hipStream_t st = (hipStream_t)stream;
     char *p = (char *)scratch;
     int64_t *d_soff = carve<int64_t>(p, n_signals + 1), *d_foff = carve<int64_t>(p, n_signals + 1);
     double *stats = carve<double>(p, 2 * (size_t)n_signals), *d_win = carve<double>(p, g.W), *d_rw = carve<double>(p, g.hi + 1);
-    double *cand_f = carve<double>(p, TR_MAX_CAND * (size_t)F), *cand_s = carve<double>(p, TR_MAX_CAND * (size_t)F);
-    int *cand_n = carve<int>(p, F);
-    unsigned char *back = carve<unsigned char>(p, TR_MAX_CAND * (size_t)F);
 
     // Hann window of W samples and its own autocorrelation, normalised at lag 0
     std::vector<double> win(g.W), rw(g.hi + 1);
@@ -538,9 +554,134 @@ extern "C" int goofer_track_pitch(goofer_ctx *ctx, const double *y, const int64_
         hipLaunchKernelGGL(k_pitch_frames, dim3((unsigned)F), dim3(TR_THREADS), lds, st, y, d_soff, d_foff, n_signals, sr, hop, g, d_win,
                            d_rw, stats, cand_f, cand_s, cand_n);
         LAUNCH_CHECK(ctx);
-        hipLaunchKernelGGL(k_pitch_viterbi, dim3(n_signals), dim3(WAVE), 0, st, d_foff, cand_f, cand_s, cand_n, 0.01 * sr / hop, back, f0);
-        LAUNCH_CHECK(ctx);
     }
+    return GOOFER_OK;
+}
+
+extern "C" int goofer_track_path(goofer_ctx *ctx, const double *cand_f, const double *cand_s, const int32_t *cand_n,
+                                 const int64_t *frame_off, int n_signals, int sr, int hop, double *f0, void *scratch,
+                                 int64_t *scratch_bytes, void *stream)
+{
+    int rc = check_offsets(ctx, frame_off, n_signals, sr, hop, "frame_off");
+    if (rc) return rc;
+    if (!scratch_bytes) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: null scratch_bytes");
+    const int64_t F = frame_off[n_signals];
+    const size_t need = align256(8 * (size_t)(n_signals + 1)) + align256(TR_MAX_CAND * (size_t)F);
+    if (!scratch) {
+        *scratch_bytes = (int64_t)need;
+        return GOOFER_OK;
+    }
+    if (!ctx) return GOOFER_EINVAL;
+    if (F == 0) return GOOFER_OK;
+    if (!cand_f || !cand_s || !cand_n || !f0) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: null candidates / f0");
+    if (*scratch_bytes < (int64_t)need) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: scratch of %lld bytes, %zu needed", (long long)*scratch_bytes, need);
+    hipStream_t st = (hipStream_t)stream;
+    char *p = (char *)scratch;
+    int64_t *d_foff = carve<int64_t>(p, n_signals + 1);
+    unsigned char *back = carve<unsigned char>(p, TR_MAX_CAND * (size_t)F);
+    HIP_TRY(ctx, hipMemcpyAsync(d_foff, frame_off, 8 * (size_t)(n_signals + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));                                            // frame_off is the caller's host array
+    hipLaunchKernelGGL(k_pitch_viterbi, dim3(n_signals), dim3(WAVE), 0, st, d_foff, cand_f, cand_s, cand_n, 0.01 * sr / hop, back, f0);
+    LAUNCH_CHECK(ctx);
+    return GOOFER_OK;
+}
+
+extern "C" int goofer_track_pitch(goofer_ctx *ctx, const double *y, const int64_t *sample_off, int n_signals, int sr, int hop,
+                                  int64_t *frame_off, double *f0, void *scratch, int64_t *scratch_bytes, void *stream)
+{
+    if (!scratch_bytes) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: null frame_off / scratch_bytes");
+    int64_t need_c = 0, need_p = 0;
+    int rc = goofer_track_candidates(ctx, y, sample_off, n_signals, sr, hop, frame_off, nullptr, nullptr, nullptr, nullptr, &need_c, nullptr);
+    if (rc) return rc;
+    rc = goofer_track_path(ctx, nullptr, nullptr, nullptr, frame_off, n_signals, sr, hop, nullptr, nullptr, &need_p, nullptr);
+    if (rc) return rc;
+    const int64_t F = frame_off[n_signals];
+    const size_t need = 2 * align256(8 * TR_MAX_CAND * (size_t)F) + align256(4 * (size_t)F) + align256((size_t)need_c) + (size_t)need_p;
+    if (!scratch) {
+        *scratch_bytes = (int64_t)need;
+        return GOOFER_OK;
+    }
+    if (!ctx) return GOOFER_EINVAL;
+    if (!y || !f0) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: null signal / f0");
+    if (*scratch_bytes < (int64_t)need) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: scratch of %lld bytes, %zu needed", (long long)*scratch_bytes, need);
+    char *p = (char *)scratch;
+    double *cand_f = carve<double>(p, TR_MAX_CAND * (size_t)F), *cand_s = carve<double>(p, TR_MAX_CAND * (size_t)F);
+    int32_t *cand_n = carve<int32_t>(p, F);
+    char *scratch_c = carve<char>(p, need_c), *scratch_p = p;
+    rc = goofer_track_candidates(ctx, y, sample_off, n_signals, sr, hop, frame_off, cand_f, cand_s, cand_n, scratch_c, &need_c, stream);
+    if (rc) return rc;
+    return goofer_track_path(ctx, cand_f, cand_s, cand_n, frame_off, n_signals, sr, hop, f0, scratch_p, &need_p, stream);
+}
+
+extern "C" int goofer_track_resample(goofer_ctx *ctx, const double *y, const int64_t *sample_off, int n_signals, int sr, int64_t *x_off,
+                                     double *x11, void *scratch, int64_t *scratch_bytes, void *stream)
+{
+    int rc = check_batch(ctx, sample_off, n_signals, sr, 1, 1);
+    if (rc) return rc;
+    if (!x_off || !scratch_bytes) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: null x_off / scratch_bytes");
+    x_off[0] = 0;
+    for (int s = 0; s < n_signals; ++s) x_off[s + 1] = x_off[s] + resampled_length(sample_off[s + 1] - sample_off[s], sr);
+    const int64_t M = x_off[n_signals];
+    const size_t need = 2 * align256(8 * (size_t)(n_signals + 1));
+    if (!scratch) {
+        *scratch_bytes = (int64_t)need;
+        return GOOFER_OK;
+    }
+    if (!ctx) return GOOFER_EINVAL;
+    if (M == 0) return GOOFER_OK;                                                      // every signal shorter than one output sample
+    if (!y || !x11) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: null signal / x11");
+    if (*scratch_bytes < (int64_t)need) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: scratch of %lld bytes, %zu needed", (long long)*scratch_bytes, need);
+    hipStream_t st = (hipStream_t)stream;
+    char *p = (char *)scratch;
+    int64_t *d_soff = carve<int64_t>(p, n_signals + 1), *d_moff = carve<int64_t>(p, n_signals + 1);
+    HIP_TRY(ctx, hipMemcpyAsync(d_soff, sample_off, 8 * (size_t)(n_signals + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_moff, x_off, 8 * (size_t)(n_signals + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));                                            // the offsets are the caller's host arrays
+    hipLaunchKernelGGL(k_resample11k, dim3((unsigned)((M + TR_THREADS - 1) / TR_THREADS)), dim3(TR_THREADS), 0, st, y, d_soff, d_moff,
+                       n_signals, M, sr, x11);
+    LAUNCH_CHECK(ctx);
+    return GOOFER_OK;
+}
+
+extern "C" int goofer_track_formant_frames(goofer_ctx *ctx, const double *x11, const int64_t *x_off, int n_signals, int sr, int hop,
+                                           int64_t *frame_off, double *formants, void *scratch, int64_t *scratch_bytes, void *stream)
+{
+    int rc = check_offsets(ctx, x_off, n_signals, sr, hop, "x_off");
+    if (rc) return rc;
+    if (!frame_off || !scratch_bytes) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: null frame_off / scratch_bytes");
+    frame_off[0] = 0;
+    for (int s = 0; s < n_signals; ++s) {
+        const int64_t m = x_off[s + 1] - x_off[s];
+        frame_off[s + 1] = frame_off[s] + (m < FM_WIN ? 0 : (m - FM_WIN) * sr / ((int64_t)FM_SR * hop) + 1);
+    }
+    const int64_t F = frame_off[n_signals];
+    const size_t need = 2 * align256(8 * (size_t)(n_signals + 1)) + align256(8 * (size_t)FM_WIN);
+    if (!scratch) {
+        *scratch_bytes = (int64_t)need;
+        return GOOFER_OK;
+    }
+    if (!ctx) return GOOFER_EINVAL;
+    if (F == 0) return GOOFER_OK;                                                      // every signal shorter than a formant window
+    if (!x11 || !formants) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: null x11 / formants");
+    if (*scratch_bytes < (int64_t)need) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: scratch of %lld bytes, %zu needed", (long long)*scratch_bytes, need);
+    hipStream_t st = (hipStream_t)stream;
+    char *p = (char *)scratch;
+    int64_t *d_moff = carve<int64_t>(p, n_signals + 1), *d_foff = carve<int64_t>(p, n_signals + 1);
+    double *d_gwin = carve<double>(p, FM_WIN);
+
+    // Praat's Gaussian-like window: exp(-48 (i - mid)^2 / (W + 1)^2), i = 1..W, lifted to zero at the ends
+    std::vector<double> gwin(FM_WIN);
+    const double e12 = exp(-12.0);
+    for (int j = 0; j < FM_WIN; ++j) {
+        const double d = (j + 1.0) - 0.5 * (FM_WIN + 1);
+        gwin[j] = (exp(-48.0 * d * d / ((FM_WIN + 1.0) * (FM_WIN + 1.0))) - e12) / (1.0 - e12);
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(d_moff, x_off, 8 * (size_t)(n_signals + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_foff, frame_off, 8 * (size_t)(n_signals + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_gwin, gwin.data(), 8 * (size_t)FM_WIN, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));                                            // the host vectors go out of scope
+    hipLaunchKernelGGL(k_formant_frames, dim3((unsigned)F), dim3(WAVE), 0, st, x11, d_moff, d_foff, n_signals, sr, hop, d_gwin, formants);
+    LAUNCH_CHECK(ctx);
     return GOOFER_OK;
 }
 
@@ -550,15 +691,14 @@ extern "C" int goofer_track_formants(goofer_ctx *ctx, const double *y, const int
     int rc = check_batch(ctx, sample_off, n_signals, sr, hop, 1);
     if (rc) return rc;
     if (!frame_off || !scratch_bytes) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: null frame_off / scratch_bytes");
-    std::vector<int64_t> moff(n_signals + 1, 0);
-    frame_off[0] = 0;
-    for (int s = 0; s < n_signals; ++s) {
-        const int64_t n = sample_off[s + 1] - sample_off[s];
-        moff[s + 1] = moff[s] + resampled_length(n, sr);
-        frame_off[s + 1] = frame_off[s] + formant_frames(n, sr, hop);
-    }
-    const int64_t F = frame_off[n_signals], M = moff[n_signals];
-    const size_t need = 3 * align256(8 * (size_t)(n_signals + 1)) + align256(8 * (size_t)M) + align256(8 * (size_t)FM_WIN);
+    std::vector<int64_t> x_off(n_signals + 1);
+    int64_t need_r = 0, need_f = 0;
+    rc = goofer_track_resample(ctx, y, sample_off, n_signals, sr, x_off.data(), nullptr, nullptr, &need_r, nullptr);
+    if (rc) return rc;
+    rc = goofer_track_formant_frames(ctx, nullptr, x_off.data(), n_signals, sr, hop, frame_off, nullptr, nullptr, &need_f, nullptr);
+    if (rc) return rc;
+    const int64_t F = frame_off[n_signals], M = x_off[n_signals];
+    const size_t need = align256(8 * (size_t)M) + align256((size_t)need_r) + (size_t)need_f;
     if (!scratch) {
         *scratch_bytes = (int64_t)need;
         return GOOFER_OK;
@@ -567,28 +707,10 @@ extern "C" int goofer_track_formants(goofer_ctx *ctx, const double *y, const int
     if (F == 0) return GOOFER_OK;                                                      // every signal shorter than a formant window
     if (!y || !formants) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: null signal / formants");
     if (*scratch_bytes < (int64_t)need) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: scratch of %lld bytes, %zu needed", (long long)*scratch_bytes, need);
-    hipStream_t st = (hipStream_t)stream;
     char *p = (char *)scratch;
-    int64_t *d_soff = carve<int64_t>(p, n_signals + 1), *d_moff = carve<int64_t>(p, n_signals + 1), *d_foff = carve<int64_t>(p, n_signals + 1);
-    double *x11 = carve<double>(p, M), *d_gwin = carve<double>(p, FM_WIN);
-
-    // Praat's Gaussian-like window: exp(-48 (i - mid)^2 / (W + 1)^2), i = 1..W, lifted to zero at the ends
-    std::vector<double> gwin(FM_WIN);
-    const double e12 = exp(-12.0);
-    for (int j = 0; j < FM_WIN; ++j) {
-        const double d = (j + 1.0) - 0.5 * (FM_WIN + 1);
-        gwin[j] = (exp(-48.0 * d * d / ((FM_WIN + 1.0) * (FM_WIN + 1.0))) - e12) / (1.0 - e12);
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(d_soff, sample_off, 8 * (size_t)(n_signals + 1), hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(d_moff, moff.data(), 8 * (size_t)(n_signals + 1), hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(d_foff, frame_off, 8 * (size_t)(n_signals + 1), hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(d_gwin, gwin.data(), 8 * (size_t)FM_WIN, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));                                            // the host vectors go out of scope
-
-    hipLaunchKernelGGL(k_resample11k, dim3((unsigned)((M + TR_THREADS - 1) / TR_THREADS)), dim3(TR_THREADS), 0, st, y, d_soff, d_moff,
-                       n_signals, M, sr, x11);
-    LAUNCH_CHECK(ctx);
-    hipLaunchKernelGGL(k_formant_frames, dim3((unsigned)F), dim3(WAVE), 0, st, x11, d_moff, d_foff, n_signals, sr, hop, d_gwin, formants);
-    LAUNCH_CHECK(ctx);
-    return GOOFER_OK;
+    double *x11 = carve<double>(p, M);
+    char *scratch_r = carve<char>(p, need_r), *scratch_f = p;
+    rc = goofer_track_resample(ctx, y, sample_off, n_signals, sr, x_off.data(), x11, scratch_r, &need_r, stream);
+    if (rc) return rc;
+    return goofer_track_formant_frames(ctx, x11, x_off.data(), n_signals, sr, hop, frame_off, formants, scratch_f, &need_f, stream);
 }

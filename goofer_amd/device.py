@@ -243,6 +243,76 @@ class Context:
             out += [res if width > 1 else res[:, 0], f_off]
         return tuple(out)
 
+    # the tracker's stages one at a time (goofer_track_candidates / _path / _resample / _formant_frames): track's parts
+    def _track_input(self, y, lengths, what):
+        if not (isinstance(y, torch.Tensor) and y.dtype == torch.float64 and y.is_contiguous() and y.device == self.device):
+            raise ValueError(f"{what} expects a contiguous fp64 tensor on this context's device")
+        lengths = [int(v) for v in lengths]
+        if not lengths or any(v < 0 for v in lengths) or sum(lengths) != y.numel():
+            raise ValueError(f"{what}: the lengths sum to {sum(lengths)}, the signal has {y.numel()} samples")
+        return self.offsets(lengths)
+
+    def track_candidates(self, y, lengths, sr: int, hop: int):
+        """The pitch candidates of every frame: (cand_f [F, 15], cand_s [F, 15] fp64, cand_n [F] int32, frame_off host int64).
+        Slot 0 is the unvoiced candidate; the slots from cand_n on are 0."""
+        s_off = self._track_input(y, lengths, "track_candidates")
+        f_off = np.zeros(len(s_off), dtype=np.int64)
+        need = C.c_int64(0)
+        fn = self.lib.goofer_track_candidates
+        args = (s_off.ctypes.data_as(C.c_void_p), len(s_off) - 1, int(sr), int(hop), f_off.ctypes.data_as(C.c_void_p))
+        self._check(fn(self.h, None, *args, None, None, None, None, C.byref(need), None))
+        F = int(f_off[-1])
+        cf = torch.zeros((F, 15), dtype=torch.float64, device=self.device)
+        cs = torch.zeros((F, 15), dtype=torch.float64, device=self.device)
+        cn = torch.zeros(F, dtype=torch.int32, device=self.device)
+        scratch = torch.empty(max(int(need.value), 1), dtype=torch.uint8, device=self.device)
+        self._check(fn(self.h, _ptr(y), *args, _ptr(cf), _ptr(cs), _ptr(cn), _ptr(scratch), C.byref(need), self._stream()))
+        return cf, cs, cn, f_off
+
+    def track_path(self, cand_f, cand_s, cand_n, frame_off, sr: int, hop: int):
+        """The Viterbi f0 [frame_off[-1]] fp64 of candidates in track_candidates' layout (contiguous device tensors)."""
+        frame_off = np.ascontiguousarray(frame_off, dtype=np.int64)
+        F = int(frame_off[-1])
+        for t, dt in ((cand_f, torch.float64), (cand_s, torch.float64), (cand_n, torch.int32)):
+            if not (isinstance(t, torch.Tensor) and t.dtype == dt and t.is_contiguous() and t.device == self.device
+                    and t.shape[0] == F and t.numel() == F * (1 if dt == torch.int32 else 15)):
+                raise ValueError(f"track_path expects contiguous [{F}, 15] fp64 and [{F}] int32 tensors on this context's device")
+        need = C.c_int64(0)
+        fn = self.lib.goofer_track_path
+        args = (frame_off.ctypes.data_as(C.c_void_p), len(frame_off) - 1, int(sr), int(hop))
+        self._check(fn(self.h, None, None, None, *args, None, None, C.byref(need), None))
+        f0 = torch.empty(F, dtype=torch.float64, device=self.device)
+        scratch = torch.empty(max(int(need.value), 1), dtype=torch.uint8, device=self.device)
+        self._check(fn(self.h, _ptr(cand_f), _ptr(cand_s), _ptr(cand_n), *args, _ptr(f0), _ptr(scratch), C.byref(need), self._stream()))
+        return f0
+
+    def track_resample(self, y, lengths, sr: int):
+        """The 11 kHz signals the formant stage analyses: (x11 fp64 device tensor, x_off host int64)."""
+        s_off = self._track_input(y, lengths, "track_resample")
+        x_off = np.zeros(len(s_off), dtype=np.int64)
+        need = C.c_int64(0)
+        fn = self.lib.goofer_track_resample
+        args = (s_off.ctypes.data_as(C.c_void_p), len(s_off) - 1, int(sr), x_off.ctypes.data_as(C.c_void_p))
+        self._check(fn(self.h, None, *args, None, None, C.byref(need), None))
+        x11 = torch.empty(int(x_off[-1]), dtype=torch.float64, device=self.device)
+        scratch = torch.empty(max(int(need.value), 1), dtype=torch.uint8, device=self.device)
+        self._check(fn(self.h, _ptr(y), *args, _ptr(x11), _ptr(scratch), C.byref(need), self._stream()))
+        return x11, x_off
+
+    def track_formant_frames(self, x11, lengths11, sr: int, hop: int):
+        """Formants [F, 5] fp64 of 11 kHz signals (``lengths11`` samples each) placed as a signal at ``sr`` with ``hop``
+        would place them, and their frame_off (host int64)."""
+        x_off = self._track_input(x11, lengths11, "track_formant_frames")
+        f_off = np.zeros(len(x_off), dtype=np.int64)
+        need = C.c_int64(0)
+        fn = self.lib.goofer_track_formant_frames
+        args = (x_off.ctypes.data_as(C.c_void_p), len(x_off) - 1, int(sr), int(hop), f_off.ctypes.data_as(C.c_void_p))
+        self._check(fn(self.h, None, *args, None, None, C.byref(need), None))
+        forms = torch.empty((int(f_off[-1]), 5), dtype=torch.float64, device=self.device)
+        scratch = torch.empty(max(int(need.value), 1), dtype=torch.uint8, device=self.device)
+        self._check(fn(self.h, _ptr(x11), *args, _ptr(forms), _ptr(scratch), C.byref(need), self._stream()))
+        return forms, f_off
+
     def per_sample_f0(self, tracks, track_lengths, sample_lengths, sr, f0_min=75, f0_merge_range=2):
         """trackers.per_sample_f0 for a ragged batch in one launch (goofer_per_sample_f0): ``tracks`` a contiguous fp64 device
         tensor holding ``track_lengths`` frames per signal (two at least each), ``sample_lengths`` the signals' sample counts.

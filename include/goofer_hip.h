@@ -337,11 +337,39 @@ int goofer_envelope_knots_batch(goofer_ctx *ctx, const float *y, const int64_t *
  * f0 [frame_off[n]] in Hz, 0 where unvoiced.  Every signal needs ceil(3 sr / 75) samples at least (GOOFER_EINVAL).
  * goofer_track_formants: Burg LPC of order 10 on the signal resampled to 11 kHz and pre-emphasised from 50 Hz, 50 ms
  * Gaussian window, same time step; frames: floor((m - 550) sr / (11000 hop)) + 1 for m = n * 11000 / sr resampled samples
- * (0 when m < 550).  formants [frame_off[n] x 5] in Hz, ascending, 0 where fewer than five roots lie in (50, 5450) Hz. */
+ * (0 when m < 550).  formants [frame_off[n] x 5] in Hz, ascending, 0 where fewer than five roots lie in (50, 5450) Hz.
+ * Non-finite samples: a NaN or infinite sample makes its signal's peak deviation NaN, as numpy's max does.  Every pitch frame
+ * of that signal then has the unvoiced strength 0.45 (the silence term max(0, 2 - NaN) is 0), a frame whose window holds such
+ * a sample has no voiced candidate, and a formant frame whose 11 kHz samples are not finite has no formants (0).  The other
+ * signals of the batch are not affected.
+ * Each call is a composition of the single-stage calls below, and gives their bits. */
 int goofer_track_pitch(goofer_ctx *ctx, const double *y, const int64_t *sample_off, int n_signals, int sr, int hop,
                        int64_t *frame_off, double *f0, void *scratch, int64_t *scratch_bytes, void *stream);
 int goofer_track_formants(goofer_ctx *ctx, const double *y, const int64_t *sample_off, int n_signals, int sr, int hop,
                           int64_t *frame_off, double *formants, void *scratch, int64_t *scratch_bytes, void *stream);
+
+/* Single-stage entry points of the tracker (unit parity), with the conventions above: HOST offset arrays, the query form
+ * with scratch = NULL, device arrays otherwise.
+ * goofer_track_candidates: goofer_track_pitch's per-frame stage.  cand_f, cand_s [frame_off[n] x 15] fp64 and cand_n
+ * [frame_off[n]] int32 (device): frame f has cand_n[f] candidates; slot 0 is the unvoiced one (frequency 0, the unvoiced
+ * strength), slots 1.. the voiced ones in lag order (frequency in Hz, strength); the slots from cand_n[f] on are not written.
+ * goofer_track_path: goofer_track_pitch's Viterbi stage on candidates in that layout, for time step hop / sr.  frame_off
+ * [n_signals+1] is read (0 first, never decreasing); a cand_n outside [1, 15] is taken as the nearest of 1 and 15.  f0
+ * [frame_off[n]]: the chosen candidate's frequency; the first best predecessor, and the first best last candidate, win ties.
+ * goofer_track_resample: goofer_track_formants' 11 kHz signal.  x_off [n_signals+1] is written (n * 11000 / sr samples per
+ * signal), x11 [x_off[n]] fp64 (device).  Every signal needs one sample at least.
+ * goofer_track_formant_frames: goofer_track_formants' per-frame stage on a caller's 11 kHz signals x11 [x_off[n]] (device),
+ * x_off read (0 first, never decreasing); sr and hop are the original rate and hop, which place the frames; frame_off is
+ * written; formants as goofer_track_formants. */
+int goofer_track_candidates(goofer_ctx *ctx, const double *y, const int64_t *sample_off, int n_signals, int sr, int hop,
+                            int64_t *frame_off, double *cand_f, double *cand_s, int32_t *cand_n, void *scratch,
+                            int64_t *scratch_bytes, void *stream);
+int goofer_track_path(goofer_ctx *ctx, const double *cand_f, const double *cand_s, const int32_t *cand_n, const int64_t *frame_off,
+                      int n_signals, int sr, int hop, double *f0, void *scratch, int64_t *scratch_bytes, void *stream);
+int goofer_track_resample(goofer_ctx *ctx, const double *y, const int64_t *sample_off, int n_signals, int sr, int64_t *x_off,
+                          double *x11, void *scratch, int64_t *scratch_bytes, void *stream);
+int goofer_track_formant_frames(goofer_ctx *ctx, const double *x11, const int64_t *x_off, int n_signals, int sr, int hop,
+                                int64_t *frame_off, double *formants, void *scratch, int64_t *scratch_bytes, void *stream);
 
 /* gf.extract_features' f0 post-processing (GOOFER.py:957-966) for a ragged batch of frame-rate f0 tracks (goofer_amd/csrc/f0.hip):
  * NaN -> 0, zero runs of at most max_gap frames with a neighbour on both sides bridged linearly (GOOFER.py:415-435), np.interp
