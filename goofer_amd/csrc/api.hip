@@ -257,7 +257,33 @@ __global__ __launch_bounds__(256) void k_scale_f0(const float *__restrict__ f0, 
 }
 
 static void gauss_taps_host(double sigma, std::vector<double> &taps, int &radius);
-static int ensure_small(goofer_ctx *ctx, size_t bytes);
+
+// A handle-owned device block (*p, *bytes) grown to `need` bytes when it is smaller: the device is drained first (work in
+// flight may still read the old block), then the block is freed and allocated anew.
+static int grow_block(goofer_ctx *ctx, void **p, size_t *bytes, size_t need, const char *what)
+{
+    if (*bytes >= need) return GOOFER_OK;
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    if (*p) HIP_TRY(ctx, hipFree(*p));
+    *p = nullptr;
+    *bytes = 0;
+    hipError_t e = hipMalloc(p, need);
+    if (e != hipSuccess) return goofer_fail(ctx, GOOFER_ENOMEM, "%s hipMalloc(%zu) failed: %s", what, need, hipGetErrorString(e));
+    *bytes = need;
+    return GOOFER_OK;
+}
+
+// The handle's small block (ctx->small): host tables a call uploads for its own kernels.  Its regions, by byte offset:
+constexpr size_t SMALL_TABLES = 0;       // [0, 32 KiB): taps of goofer_gauss_bins / _gauss_bins_f64; the lerp tables of
+                                         // goofer_knot_decode / _knot_fit_error (12 bytes per bin)
+constexpr size_t SMALL_WORDS = 32768;    // [32 KiB, 64 KiB): goofer_warp_bins' f_shift (4 doubles), goofer_knot_fit_error's error word
+constexpr size_t SMALL_FIXED = 65536;    // tables and words: what their users grow the block to at least
+constexpr size_t SMALL_JIT = 65536;      // three jitter tap slots of JIT_SLOT_BYTES (upload_jitter_taps)
+constexpr size_t JIT_SLOT_BYTES = 131072;
+constexpr size_t SMALL_RAGGED = SMALL_JIT + 3 * JIT_SLOT_BYTES;   // goofer_gauss_rows_f64's taps, any radius
+// Overlaps: goofer_gauss_bins / _gauss_bins_f64 accept radius 4096, 65 544 bytes of taps from byte 0: through the words and
+// 8 bytes into jitter slot 0.  goofer_smooth_mask_ds uses [0, its size) as one piece (taps, decimated mask, per-note steps),
+// across every region.  Each use is in stream order, which is what keeps the overlaps harmless.
 
 __global__ void k_note_sub_flags(const goofer_note_params *__restrict__ params, int n_notes, unsigned char *__restrict__ on_sub,
                                  unsigned char *__restrict__ on_subj)
@@ -278,19 +304,18 @@ __global__ void k_note_flags(const goofer_note_params *__restrict__ params, int 
     on_vol[i] = params[i].vol_jitter_harm > 0.f || params[i].vol_jitter_breath > 0.f;
 }
 
-// taps of a sample-axis Gaussian, uploaded into the handle's small buffer at `slot` (3 slots of 16 KiB after 64 KiB)
-// three tap slots behind the 64 KiB of tables in ctx->small: radius <= 8000, i.e. a jitter speed down to sr / 12 000 Hz (3.7 Hz at
-// 44.1 kHz; the reference's defaults are 100 and 150 Hz.  Until round 6: radius <= 1000 = 29.4 Hz, which a random keyword set hit)
-constexpr size_t JIT_SLOT_BYTES = 131072;
+// taps of a sample-axis Gaussian, uploaded into jitter slot `slot` of the handle's small block: radius <= 8000, i.e. a jitter speed
+// down to sr / 12 000 Hz (3.7 Hz at 44.1 kHz; the reference's defaults are 100 and 150 Hz.  Until round 6: radius <= 1000 =
+// 29.4 Hz, which a random keyword set hit)
 static int upload_jitter_taps(goofer_ctx *ctx, double sigma, int slot, const double **d_taps, int *radius, hipStream_t st)
 {
     std::vector<double> taps;
     int r;
     gauss_taps_host(sigma, taps, r);
     if (r > 8000) return goofer_fail(ctx, GOOFER_EINVAL, "jitter sigma %g too large", sigma);
-    int rc = ensure_small(ctx, 65536 + 3 * JIT_SLOT_BYTES);
+    int rc = grow_block(ctx, &ctx->small, &ctx->small_bytes, SMALL_RAGGED, "small block");
     if (rc) return rc;
-    double *dst = (double *)((char *)ctx->small + 65536 + (size_t)slot * JIT_SLOT_BYTES);
+    double *dst = (double *)((char *)ctx->small + SMALL_JIT + (size_t)slot * JIT_SLOT_BYTES);
     HIP_TRY(ctx, hipMemcpyAsync(dst, taps.data(), taps.size() * sizeof(double), hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     *d_taps = dst;
@@ -299,41 +324,19 @@ static int upload_jitter_taps(goofer_ctx *ctx, double sigma, int slot, const dou
 }
 
 // ---------------------------------------------------------------------------------------------
-// scratch arena: 256-byte aligned pieces taken in order.  Without a base it only counts, so the code that carves a call's
-// buffers also sizes them (carve_scratch).
-struct arena {
-    char *base;
-    size_t used;
-    template <typename T> T *take(size_t count)
-    {
-        T *p = base ? reinterpret_cast<T *>(base + used) : nullptr;
-        used += (count * sizeof(T) + 255) & ~(size_t)255;
-        return p;
-    }
-};
-
-static int ensure_scratch(goofer_ctx *ctx, size_t bytes)
-{
-    if (ctx->scratch_bytes >= bytes) return GOOFER_OK;
-    HIP_TRY(ctx, hipDeviceSynchronize());
-    if (ctx->scratch) HIP_TRY(ctx, hipFree(ctx->scratch));
-    ctx->scratch = nullptr;
-    ctx->scratch_bytes = 0;
-    hipError_t e = hipMalloc(&ctx->scratch, bytes);
-    if (e != hipSuccess) return goofer_fail(ctx, GOOFER_ENOMEM, "scratch hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-    ctx->scratch_bytes = bytes;
-    return GOOFER_OK;
-}
-
-// carve(arena &) once counting, make room for what it took (+ 4 KiB behind the last piece), then once over the handle's scratch
-template <typename Carve> static int carve_scratch(goofer_ctx *ctx, Carve &&carve)
+// carve(arena &) once counting, grow a handle block to what it took (+ 4 KiB behind the last piece), then carve once over it
+template <typename Carve> static int carve_block(goofer_ctx *ctx, void **block, size_t *bytes, const char *what, Carve &&carve)
 {
     arena count{nullptr, 0};
     carve(count);
-    if (int rc = ensure_scratch(ctx, count.used + 4096)) return rc;
-    arena a{(char *)ctx->scratch, 0};
+    if (int rc = grow_block(ctx, block, bytes, count.used + 4096, what)) return rc;
+    arena a{(char *)*block, 0};
     carve(a);
     return GOOFER_OK;
+}
+template <typename Carve> static int carve_scratch(goofer_ctx *ctx, Carve &&carve)
+{
+    return carve_block(ctx, &ctx->scratch, &ctx->scratch_bytes, "scratch", carve);
 }
 
 // Which pipeline goofer_synth_batch runs for a batch, decided here only (goofer_synth_batch, goofer_render_batch's warped rows,
@@ -442,18 +445,6 @@ static void carve_synth(arena &a, const goofer_plan_t &p, const synth_route &r, 
         s.on_sub = a.take<unsigned char>(n + 16); s.on_subj = a.take<unsigned char>(n + 16);
     }
     if (r.f64_on) s.f0d = a.take<double>(N);
-}
-
-static int ensure_small(goofer_ctx *ctx, size_t bytes)
-{
-    if (ctx->small_bytes >= bytes) return GOOFER_OK;
-    HIP_TRY(ctx, hipDeviceSynchronize());
-    if (ctx->small) HIP_TRY(ctx, hipFree(ctx->small));
-    ctx->small = nullptr;
-    ctx->small_bytes = 0;
-    HIP_TRY(ctx, hipMalloc(&ctx->small, bytes));
-    ctx->small_bytes = bytes;
-    return GOOFER_OK;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -749,7 +740,7 @@ int goofer_reserve(goofer_ctx *ctx, int64_t max_frames, int64_t max_samples, int
     synth_scratch s;
     arena count{nullptr, 0};
     carve_synth(count, p, r, max_frames, max_samples, (int)max_notes, (p.n_bins + 3) & ~3, s);
-    return ensure_scratch(ctx, count.used + 8192);   // (never less than the hand-summed size it replaces)
+    return grow_block(ctx, &ctx->scratch, &ctx->scratch_bytes, count.used + 8192, "scratch");   // (never less than the hand-summed size it replaces)
 }
 
 // copy one plan table to host memory (tests / debugging); which: 0 window 1 freqs 2 boost 3 bright_h
@@ -990,9 +981,9 @@ int goofer_rfft_frames(goofer_ctx *ctx, const float *x, const int64_t *sample_of
     NEED_PLAN(ctx);
     if (ldc < ctx->plan.n_bins) return goofer_fail(ctx, GOOFER_EINVAL, "ldc %d < n_bins %d", ldc, ctx->plan.n_bins);
     hipStream_t st = (hipStream_t)stream;
-    int rc = ensure_scratch(ctx, total_frames * sizeof(int) + 4096);
+    int *frame_note;
+    int rc = carve_scratch(ctx, [&](arena &a) { frame_note = a.take<int>(total_frames); });
     if (rc) return rc;
-    int *frame_note = (int *)ctx->scratch;
     if ((rc = launch_frame_note(ctx, frame_off, n_notes, total_frames, frame_note, st))) return rc;
     return launch_rfft_frames_mapped(ctx, x, sample_off, frame_off, frame_note, total_frames, (float2 *)S, ldc, st);
 }
@@ -1002,9 +993,9 @@ int goofer_irfft_ola(goofer_ctx *ctx, const float *S, int ldc, const int64_t *sa
 {
     NEED_PLAN(ctx);
     hipStream_t st = (hipStream_t)stream;
-    int rc = ensure_scratch(ctx, (size_t)total_frames * ctx->plan.n_fft * sizeof(float) + 4096);
+    float *frames;
+    int rc = carve_scratch(ctx, [&](arena &a) { frames = a.take<float>((size_t)total_frames * ctx->plan.n_fft); });
     if (rc) return rc;
-    float *frames = (float *)ctx->scratch;
     if ((rc = launch_irfft_frames(ctx, (const float2 *)S, ldc, total_frames, frames, st))) return rc;
     return launch_ola_gather(ctx, frames, sample_off, frame_off, n_notes, total_samples, y, nullptr, st);
 }
@@ -1037,10 +1028,12 @@ int goofer_gauss_bins(goofer_ctx *ctx, const float *in, float *out, int64_t rows
     if (!ctx) return GOOFER_EINVAL;
     if (radius < 0 || radius > 4096 || n_bins <= 0 || ld < n_bins) return goofer_fail(ctx, GOOFER_EINVAL, "bad gauss geometry");
     hipStream_t st = (hipStream_t)stream;
-    int rc = ensure_small(ctx, std::max<size_t>(65536, (size_t)(2 * radius + 1) * sizeof(double) + 64));
+    int rc = grow_block(ctx, &ctx->small, &ctx->small_bytes, std::max<size_t>(SMALL_FIXED, (size_t)(2 * radius + 1) * sizeof(double) + 64),
+                        "small block");
     if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->small, taps, (2 * radius + 1) * sizeof(double), hipMemcpyHostToDevice, st));
-    return launch_gauss_bins(ctx, in, out, rows, n_bins, ld, (const double *)ctx->small, radius, nullptr, st);
+    double *d_taps = (double *)((char *)ctx->small + SMALL_TABLES);
+    HIP_TRY(ctx, hipMemcpyAsync(d_taps, taps, (2 * radius + 1) * sizeof(double), hipMemcpyHostToDevice, st));
+    return launch_gauss_bins(ctx, in, out, rows, n_bins, ld, d_taps, radius, nullptr, st);
 }
 
 int goofer_warp_bins(goofer_ctx *ctx, const float *in, float *out, int64_t rows, int n_bins, int ld, const double *formants,
@@ -1050,9 +1043,9 @@ int goofer_warp_bins(goofer_ctx *ctx, const float *in, float *out, int64_t rows,
     hipStream_t st = (hipStream_t)stream;
     const double *d_shift = nullptr;
     if (f_shift) {
-        int rc = ensure_small(ctx, 65536);
+        int rc = grow_block(ctx, &ctx->small, &ctx->small_bytes, SMALL_FIXED, "small block");
         if (rc) return rc;
-        d_shift = (const double *)((char *)ctx->small + 32768);
+        d_shift = (const double *)((char *)ctx->small + SMALL_WORDS);
         HIP_TRY(ctx, hipMemcpyAsync((void *)d_shift, f_shift, 4 * sizeof(double), hipMemcpyHostToDevice, st));
     }
     return launch_warp_bins(ctx, in, out, rows, n_bins, ld, formants, d_shift, nullptr, nullptr, nullptr, ratio, st);
@@ -1084,10 +1077,10 @@ int goofer_knot_decode(goofer_ctx *ctx, const uint16_t *knots_f16, int K, const 
     std::vector<int> idx;
     std::vector<float> w0, w1;
     knot_lerp_plan(ctx->plan, hz_knots, K, n_bins, idx, w0, w1);
-    int rc = ensure_small(ctx, 65536);
+    int rc = grow_block(ctx, &ctx->small, &ctx->small_bytes, SMALL_FIXED, "small block");
     if (rc) return rc;
-    if ((size_t)n_bins * 12 > 32768) return goofer_fail(ctx, GOOFER_EINVAL, "n_bins too large");
-    char *d = (char *)ctx->small;
+    if ((size_t)n_bins * 12 > SMALL_WORDS - SMALL_TABLES) return goofer_fail(ctx, GOOFER_EINVAL, "n_bins too large");
+    char *d = (char *)ctx->small + SMALL_TABLES;
     int *d_idx = (int *)d;
     float *d_w0 = (float *)(d + 4 * (size_t)n_bins), *d_w1 = (float *)(d + 8 * (size_t)n_bins);
     HIP_TRY(ctx, hipMemcpyAsync(d_idx, idx.data(), n_bins * sizeof(int), hipMemcpyHostToDevice, st));
@@ -1103,10 +1096,12 @@ int goofer_gauss_bins_f64(goofer_ctx *ctx, const float *in, int ld, double *out,
     if (!ctx) return GOOFER_EINVAL;
     if (radius < 0 || radius > 4096 || ld < n_bins || ld64 < n_bins) return goofer_fail(ctx, GOOFER_EINVAL, "bad gauss geometry");
     hipStream_t st = (hipStream_t)stream;
-    int rc = ensure_small(ctx, std::max<size_t>(65536, (size_t)(2 * radius + 1) * sizeof(double) + 64));
+    int rc = grow_block(ctx, &ctx->small, &ctx->small_bytes, std::max<size_t>(SMALL_FIXED, (size_t)(2 * radius + 1) * sizeof(double) + 64),
+                        "small block");
     if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->small, taps, (2 * radius + 1) * sizeof(double), hipMemcpyHostToDevice, st));
-    return launch_gauss_rows64(ctx, in, ld, out, ld64, rows, n_bins, (const double *)ctx->small, radius, st);
+    double *d_taps = (double *)((char *)ctx->small + SMALL_TABLES);
+    HIP_TRY(ctx, hipMemcpyAsync(d_taps, taps, (2 * radius + 1) * sizeof(double), hipMemcpyHostToDevice, st));
+    return launch_gauss_rows64(ctx, in, ld, out, ld64, rows, n_bins, d_taps, radius, st);
 }
 
 int goofer_knot_fit_error(goofer_ctx *ctx, const double *env, int ld64, const int64_t *probe_rows, int n_probe, int n_bins,
@@ -1118,13 +1113,13 @@ int goofer_knot_fit_error(goofer_ctx *ctx, const double *env, int ld64, const in
     std::vector<int> idx;
     std::vector<float> w0, w1;
     knot_lerp_plan(ctx->plan, hz_knots, K, n_bins, idx, w0, w1);
-    int rc = ensure_small(ctx, 65536);
+    int rc = grow_block(ctx, &ctx->small, &ctx->small_bytes, SMALL_FIXED, "small block");
     if (rc) return rc;
-    if ((size_t)n_bins * 12 + 64 > 32768) return goofer_fail(ctx, GOOFER_EINVAL, "n_bins too large");
-    char *d = (char *)ctx->small;
+    if ((size_t)n_bins * 12 + 64 > SMALL_WORDS - SMALL_TABLES) return goofer_fail(ctx, GOOFER_EINVAL, "n_bins too large");
+    char *d = (char *)ctx->small + SMALL_TABLES;
     int *d_idx = (int *)d;
     float *d_w0 = (float *)(d + 4 * (size_t)n_bins), *d_w1 = (float *)(d + 8 * (size_t)n_bins);
-    unsigned long long *d_err = (unsigned long long *)(d + 32768);
+    unsigned long long *d_err = (unsigned long long *)((char *)ctx->small + SMALL_WORDS);
     HIP_TRY(ctx, hipMemcpyAsync(d_idx, idx.data(), n_bins * sizeof(int), hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemcpyAsync(d_w0, w0.data(), n_bins * sizeof(float), hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemcpyAsync(d_w1, w1.data(), n_bins * sizeof(float), hipMemcpyHostToDevice, st));
@@ -1187,20 +1182,12 @@ int goofer_envelope_knots_batch(goofer_ctx *ctx, const float *y, const int64_t *
         d_w0 = a.take<float>((size_t)KN_CAND * nb);
         d_w1 = a.take<float>((size_t)KN_CAND * nb);
     };
-    arena count{nullptr, 0};
-    carve(count);
-    if (!y) {                                                                           // query form: no device code
-        *scratch_bytes = (int64_t)count.used;
-        return GOOFER_OK;
-    }
-    if (!knots_f16 || !K_out || !hz_knots || !knot_bin || (env_rows && ld64 < nb))
-        return goofer_fail(ctx, GOOFER_EINVAL, "envelope batch: null output or ld64 < n_bins");
-    if (!scratch || *scratch_bytes < (int64_t)count.used)
-        return goofer_fail(ctx, GOOFER_EINVAL, "envelope batch: scratch of %lld bytes, %zu needed", (long long)*scratch_bytes, count.used);
+    if (scratch && (!y || !knots_f16 || !K_out || !hz_knots || !knot_bin || (env_rows && ld64 < nb)))
+        return goofer_fail(ctx, GOOFER_EINVAL, "envelope batch: null signal, output or ld64 < n_bins");
+    int rc = caller_scratch(ctx, scratch, scratch_bytes, "envelope batch", carve);
+    if (rc || !scratch) return rc;
     for (int i = 0; i < KN_BINS_TOTAL; ++i)
         if (knot_bin[i] < 0 || knot_bin[i] >= nb) return goofer_fail(ctx, GOOFER_EINVAL, "envelope batch: knot bin %d out of range", knot_bin[i]);
-    arena a{(char *)scratch, 0};
-    carve(a);
 
     // probe rows: linspace(0, T - 1, min(256, T), dtype=int) per signal, as numpy computes it (start + j * step, last = stop, floor)
     std::vector<int64_t> prow;
@@ -1239,7 +1226,6 @@ int goofer_envelope_knots_batch(goofer_ctx *ctx, const float *y, const int64_t *
     HIP_TRY(ctx, hipMemsetAsync(err, 0, 8 * (size_t)n_signals * KN_CAND, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));                                            // the host vectors go out of scope
 
-    int rc;
     if ((rc = launch_frame_note(ctx, d_foff, n_signals, F, frame_sig, st))) return rc;
     if ((rc = launch_rfft_frames_mapped(ctx, y, d_soff, d_foff, frame_sig, F, S, ldc, st))) return rc;
     if ((rc = launch_env_rows_fused(ctx, S, ldc, F, nb, d_taps, radius_env, d_taps + 2 * radius_env + 1, radius_fit, env_rows, ld64, env2, ld2,
@@ -1262,8 +1248,9 @@ int goofer_smooth_mask_ds(goofer_ctx *ctx, const float *mask, const int64_t *sam
     gauss_taps_host(std::max(1.0, (double)sigma / 4.0), taps, radius);                // GOOFER.py:561
     if (radius > 2048) return goofer_fail(ctx, GOOFER_EINVAL, "transition sigma too large");
     const size_t n_short = (size_t)(total_samples / 4 + n_notes + 16);
-    const size_t need = (taps.size() + 16 + n_short + 2 * (size_t)n_notes + 16) * sizeof(double);
-    int rc = ensure_small(ctx, need);
+    // the small block from byte 0 as one piece (see SMALL_*): taps, decimated mask, per-note steps
+    int rc = grow_block(ctx, &ctx->small, &ctx->small_bytes, (taps.size() + 16 + n_short + 2 * (size_t)n_notes + 16) * sizeof(double),
+                        "small block");
     if (rc) return rc;
     double *d_taps = (double *)ctx->small, *short_s = d_taps + taps.size() + 16, *steps = short_s + n_short;
     HIP_TRY(ctx, hipMemcpyAsync(d_taps, taps.data(), taps.size() * sizeof(double), hipMemcpyHostToDevice, st));
@@ -1283,24 +1270,19 @@ int goofer_assemble_batch(goofer_ctx *ctx, const goofer_assembly *asmb, void *st
     if (asmb->any_fry && ctx->plan.hop <= 0) return goofer_fail(ctx, GOOFER_EINVAL, "the fry envelope warp needs goofer_plan first");
     hipStream_t st = (hipStream_t)stream;
     goofer_assembly a = *asmb;
-    size_t map_bytes = ((size_t)(a.total_edit_rows + a.total_out_rows) * sizeof(int) + 511) & ~(size_t)255;
-    size_t rows_bytes = a.edit_rows ? 0 : (((size_t)a.total_edit_rows * a.ld * sizeof(float) + 255) & ~(size_t)255);
-    size_t rec_bytes = ctx->value_f64 ? 0 : (size_t)a.total_out_rows * env_row_rec_bytes();   // per-row records of k_row_recs / k_env_rows
-    size_t need = map_bytes + rows_bytes + rec_bytes + 4096;
-    if (ctx->asm_bytes < need) {
-        HIP_TRY(ctx, hipDeviceSynchronize());
-        if (ctx->asm_scratch) HIP_TRY(ctx, hipFree(ctx->asm_scratch));
-        ctx->asm_scratch = nullptr;
-        ctx->asm_bytes = 0;
-        hipError_t e = hipMalloc(&ctx->asm_scratch, need);
-        if (e != hipSuccess) return goofer_fail(ctx, GOOFER_ENOMEM, "assembly scratch hipMalloc(%zu) failed: %s", need, hipGetErrorString(e));
-        ctx->asm_bytes = need;
-    }
-    int *map_edit = (int *)ctx->asm_scratch;
-    int *map_out = map_edit + a.total_edit_rows;
-    if (!a.edit_rows) a.edit_rows = (float *)((char *)ctx->asm_scratch + map_bytes);
-    void *recs = (char *)ctx->asm_scratch + map_bytes + rows_bytes;
-    return launch_assemble(ctx, &a, map_edit, map_out, recs, st);
+    // the row -> note maps (map_out right behind map_edit, 64 ints of padding behind both), the edited rows unless the caller
+    // gives them, the per-row records of k_row_recs / k_env_rows; 4 KiB behind the last piece
+    int *map_edit;
+    float *edit_rows;
+    char *recs;
+    int rc = carve_block(ctx, &ctx->asm_scratch, &ctx->asm_bytes, "assembly scratch", [&](arena &m) {
+        map_edit = m.take<int>((size_t)(a.total_edit_rows + a.total_out_rows) + 64);
+        edit_rows = m.take<float>(a.edit_rows ? 0 : (size_t)a.total_edit_rows * a.ld);
+        recs = m.take<char>(ctx->value_f64 ? 0 : (size_t)a.total_out_rows * env_row_rec_bytes());
+    });
+    if (rc) return rc;
+    if (!a.edit_rows) a.edit_rows = edit_rows;
+    return launch_assemble(ctx, &a, map_edit, map_edit + a.total_edit_rows, recs, st);
 }
 
 int goofer_stretch_rows(goofer_ctx *ctx, const float *in, int64_t ld_in, int64_t rows_in, float *out, int64_t ld_out, int64_t rows_out,
@@ -1358,11 +1340,10 @@ int goofer_gauss_rows_f64(goofer_ctx *ctx, const double *in, const int64_t *row_
     if (radius < 0 || radius > (1 << 22)) return goofer_fail(ctx, GOOFER_EINVAL, "gaussian radius %d outside [0, 2^22]", radius);
     if (n_rows <= 0 || total <= 0) return GOOFER_OK;
     hipStream_t st = (hipStream_t)stream;
-    // taps behind the fixed small areas (tables at 0, the three jitter tap slots at 64 KiB)
-    const size_t tap_off = 65536 + 3 * JIT_SLOT_BYTES, tap_bytes = (size_t)(2 * radius + 1) * sizeof(double);
-    int rc = ensure_small(ctx, tap_off + tap_bytes);
+    const size_t tap_bytes = (size_t)(2 * radius + 1) * sizeof(double);
+    int rc = grow_block(ctx, &ctx->small, &ctx->small_bytes, SMALL_RAGGED + tap_bytes, "small block");
     if (rc) return rc;
-    double *d_taps = (double *)((char *)ctx->small + tap_off);
+    double *d_taps = (double *)((char *)ctx->small + SMALL_RAGGED);
     HIP_TRY(ctx, hipMemcpyAsync(d_taps, taps, tap_bytes, hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));                   // the caller's taps buffer may be transient
     return launch_gauss_samples<double>(ctx, in, row_off, n_rows, total, d_taps, radius, nullptr, out, st);
@@ -1770,7 +1751,7 @@ int goofer_synth_batch(goofer_ctx *ctx, const goofer_batch *b, void *stream)
         gauss_taps_host(std::max(1.0, (double)b->transition_sigma / 4.0), mtaps, mrad);   // GOOFER.py:561
         if (mrad > 2048) return goofer_fail(ctx, GOOFER_EINVAL, "transition sigma too large");
         HIP_TRY(ctx, hipDeviceSynchronize());
-        if (!ctx->mask_taps) HIP_TRY(ctx, hipMalloc((void **)&ctx->mask_taps, 4097 * sizeof(double)));
+        if ((rc = grow_block(ctx, (void **)&ctx->mask_taps, &ctx->mask_taps_bytes, 4097 * sizeof(double), "mask taps"))) return rc;
         HIP_TRY(ctx, hipMemcpy(ctx->mask_taps, mtaps.data(), mtaps.size() * sizeof(double), hipMemcpyHostToDevice));
         ctx->mask_taps_sigma = b->transition_sigma;
         ctx->mask_taps_radius = mrad;
@@ -1932,14 +1913,9 @@ int goofer_render_batch(goofer_ctx *ctx, const goofer_assembly *asmb, const goof
     if (synth_route_of(ctx, b).walkers && ctx->overlap && asmb->env_out == b->env && asmb->n_notes == b->n_notes &&
         asmb->total_out_rows == b->total_env_rows && asmb->ld == b->ld && !asmb->any_fry) {
         const size_t need = (size_t)b->total_env_rows * b->ld * sizeof(float);
-        if (need > ctx->warp_rows_bytes) {
-            HIP_TRY(ctx, hipDeviceSynchronize());
-            if (ctx->warp_rows) HIP_TRY(ctx, hipFree(ctx->warp_rows));
-            ctx->warp_rows = nullptr;
-            ctx->warp_rows_bytes = 0;
-            HIP_TRY(ctx, hipMalloc((void **)&ctx->warp_rows, need + need / 4));
-            ctx->warp_rows_bytes = need + need / 4;
-        }
+        if (need > ctx->warp_rows_bytes &&                                            // grown with 25 % to spare
+            (rc = grow_block(ctx, (void **)&ctx->warp_rows, &ctx->warp_rows_bytes, need + need / 4, "warped rows")))
+            return rc;
         ctx->warp_formants = b->formants;
         ctx->warp_params = b->params;
         ctx->warp_out = ctx->warp_rows;

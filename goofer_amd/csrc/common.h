@@ -61,12 +61,12 @@ struct goofer_ctx {
     int device = 0;
     char err[512] = {0};
     goofer_plan_t plan;
-    // scratch (grown by ensure_scratch)
+    // handle-owned device blocks, each grown by grow_block (api.hip)
     void *scratch = nullptr;
     size_t scratch_bytes = 0;
     void *asm_scratch = nullptr;  // assembly scratch: edited rows + row->note maps
     size_t asm_bytes = 0;
-    void *small = nullptr;        // small staging buffer for taps etc.
+    void *small = nullptr;        // small staging buffer for taps etc. (its regions: SMALL_* in api.hip)
     size_t small_bytes = 0;
     // device pointers of the last synth batch's intermediates (goofer_debug_fetch; tests only)
     const void *dbg_ptr[16] = {nullptr};
@@ -124,6 +124,7 @@ struct goofer_ctx {
     int prof_steps = 0, prof_cap = 0;
     hipEvent_t *prof_ev = nullptr;      // [prof_cap][PROF_STAGES + 1]
     double *mask_taps = nullptr;  // device taps of the voicing-mask smoother, cached per sigma
+    size_t mask_taps_bytes = 0;
     float mask_taps_sigma = -1.f;
     int mask_taps_radius = 0;
     double mask_taps_sum = 0.0;   // running fp64 sum of the taps in tap order (the FIR's answer on a window of ones)
@@ -153,6 +154,40 @@ int kernel_resident_waves(goofer_ctx *ctx, const void *fn, size_t lds, int *wave
             return goofer_fail((ctx), GOOFER_EHIP, "kernel launch failed: %s (%s:%d)",           \
                                hipGetErrorString(e_), __FILE__, __LINE__);                       \
     } while (0)
+
+// ---- scratch layouts -----------------------------------------------------------------------
+
+// scratch arena: 256-byte aligned pieces taken in order.  Without a base it only counts, so the code that carves a call's
+// buffers also sizes them.
+struct arena {
+    char *base;
+    size_t used;
+    template <typename T> T *take(size_t count)
+    {
+        T *p = base ? reinterpret_cast<T *>(base + used) : nullptr;
+        used += (count * sizeof(T) + 255) & ~(size_t)255;
+        return p;
+    }
+};
+
+// The caller-scratch protocol of include/goofer_hip.h: carve(arena &) runs once counting.  With scratch NULL the count goes to
+// *scratch_bytes and nothing else happens (GOOFER_OK: the caller returns, as `scratch` tells it); otherwise a block shorter
+// than the count is refused and carve runs again over the caller's block.
+template <typename Carve>
+int caller_scratch(goofer_ctx *ctx, void *scratch, int64_t *scratch_bytes, const char *what, Carve &&carve)
+{
+    arena a{nullptr, 0};
+    carve(a);
+    if (!scratch) {
+        *scratch_bytes = (int64_t)a.used;
+        return GOOFER_OK;
+    }
+    if (*scratch_bytes < (int64_t)a.used)
+        return goofer_fail(ctx, GOOFER_EINVAL, "%s: scratch of %lld bytes, %zu needed", what, (long long)*scratch_bytes, a.used);
+    a = arena{(char *)scratch, 0};
+    carve(a);
+    return GOOFER_OK;
+}
 
 // ---- device helpers ------------------------------------------------------------------------
 

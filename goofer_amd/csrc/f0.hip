@@ -16,8 +16,6 @@
 
 namespace {
 
-size_t f0_align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // Largest s < n with off[s] <= g (off ascending, off[0] <= g): the signal a flat sample index belongs to, empty signals skipped.
 __device__ __forceinline__ int f0_signal(const int64_t *__restrict__ off, int n, int64_t g)
 {
@@ -127,20 +125,20 @@ extern "C" int goofer_per_sample_f0(goofer_ctx *ctx, const double *tracks, const
         if (sample_off[s + 1] < sample_off[s]) return goofer_fail(ctx, GOOFER_EINVAL, "per_sample_f0: sample offsets descend at %d", s);
     }
     const int64_t total = sample_off[n_signals];
-    const size_t need = 2 * f0_align256(8 * (size_t)(n_signals + 1));
-    if (!scratch) {
-        *scratch_bytes = (int64_t)need;
-        return GOOFER_OK;
+    if (scratch) {
+        if (!ctx) return GOOFER_EINVAL;
+        if (total > 0 && (!tracks || !f0 || !mask)) return goofer_fail(ctx, GOOFER_EINVAL, "per_sample_f0: null tracks / outputs");
     }
-    if (!ctx) return GOOFER_EINVAL;
-    if (total > 0 && (!tracks || !f0 || !mask)) return goofer_fail(ctx, GOOFER_EINVAL, "per_sample_f0: null tracks / outputs");
-    if (*scratch_bytes < (int64_t)need)
-        return goofer_fail(ctx, GOOFER_EINVAL, "per_sample_f0: scratch of %lld bytes, %zu needed", (long long)*scratch_bytes, need);
+    int64_t *d_toff, *d_soff;
+    int rc = caller_scratch(ctx, scratch, scratch_bytes, "per_sample_f0", [&](arena &a) {
+        d_toff = a.take<int64_t>(n_signals + 1);
+        d_soff = a.take<int64_t>(n_signals + 1);
+    });
+    if (rc || !scratch) return rc;
     const int64_t blocks = (total + 255) / 256;
     if (blocks > 0x7fffffffLL) return goofer_fail(ctx, GOOFER_EINVAL, "per_sample_f0: %lld samples in one call", (long long)total);
     if (total == 0) return GOOFER_OK;
     hipStream_t st = (hipStream_t)stream;
-    int64_t *d_toff = (int64_t *)scratch, *d_soff = (int64_t *)((char *)scratch + f0_align256(8 * (size_t)(n_signals + 1)));
     HIP_TRY(ctx, hipMemcpyAsync(d_toff, track_off, 8 * (size_t)(n_signals + 1), hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemcpyAsync(d_soff, sample_off, 8 * (size_t)(n_signals + 1), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_per_sample_f0, dim3((unsigned)blocks), dim3(256), 0, st, tracks, d_toff, d_soff, n_signals, total, sr, f0_min,

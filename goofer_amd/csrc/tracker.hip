@@ -59,13 +59,8 @@ int64_t pitch_frames(int64_t n, int sr, int hop)
 
 int64_t resampled_length(int64_t n, int sr) { return n * FM_SR / sr; }
 
-int64_t formant_frames(int64_t n, int sr, int hop)
-{
-    const int64_t m = resampled_length(n, sr);
-    return m < FM_WIN ? 0 : (m - FM_WIN) * sr / ((int64_t)FM_SR * hop) + 1;
-}
-
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+// formant frames of a signal of m samples at 11 kHz placed as a signal at sr with hop would place them
+int64_t formant_frames(int64_t m, int sr, int hop) { return m < FM_WIN ? 0 : (m - FM_WIN) * sr / ((int64_t)FM_SR * hop) + 1; }
 
 // ---- device helpers ----------------------------------------------------------------------------------------------
 __device__ __forceinline__ double wave_sum_d(double v)
@@ -496,13 +491,26 @@ int check_offsets(goofer_ctx *ctx, const int64_t *off, int n_sig, int sr, int ho
     return GOOFER_OK;
 }
 
-template <typename T>
-T *carve(char *&p, size_t count)
+// the offsets each stage writes: out[s + 1] - out[s] = count(in[s + 1] - in[s])
+template <typename Count> void fill_offsets(const int64_t *in, int n_sig, int64_t *out, Count count)
 {
-    T *r = reinterpret_cast<T *>(p);
-    p += align256(count * sizeof(T));
-    return r;
+    out[0] = 0;
+    for (int s = 0; s < n_sig; ++s) out[s + 1] = out[s] + count(in[s + 1] - in[s]);
 }
+
+// Each stage's scratch, in arena order (a braced list takes its pieces left to right).  A composite call carves its stages'
+// blocks behind its own pieces and hands each stage its block.
+struct cand_scratch { int64_t *soff, *foff; double *stats, *win, *rw; };
+cand_scratch carve_candidates(arena &a, int n, const pitch_geom &g)
+{
+    return {a.take<int64_t>(n + 1), a.take<int64_t>(n + 1), a.take<double>(2 * (size_t)n), a.take<double>(g.W), a.take<double>(g.hi + 1)};
+}
+struct path_scratch { int64_t *foff; unsigned char *back; };
+path_scratch carve_path(arena &a, int n, int64_t F) { return {a.take<int64_t>(n + 1), a.take<unsigned char>(TR_MAX_CAND * (size_t)F)}; }
+struct resample_scratch { int64_t *soff, *moff; };
+resample_scratch carve_resample(arena &a, int n) { return {a.take<int64_t>(n + 1), a.take<int64_t>(n + 1)}; }
+struct formant_scratch { int64_t *moff, *foff; double *gwin; };
+formant_scratch carve_formant_frames(arena &a, int n) { return {a.take<int64_t>(n + 1), a.take<int64_t>(n + 1), a.take<double>(FM_WIN)}; }
 
 }  // namespace
 
@@ -514,23 +522,17 @@ extern "C" int goofer_track_candidates(goofer_ctx *ctx, const double *y, const i
     int rc = check_batch(ctx, sample_off, n_signals, sr, hop, pitch_min_length(sr));
     if (rc) return rc;
     if (!frame_off || !scratch_bytes) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: null frame_off / scratch_bytes");
-    frame_off[0] = 0;
-    for (int s = 0; s < n_signals; ++s) frame_off[s + 1] = frame_off[s] + pitch_frames(sample_off[s + 1] - sample_off[s], sr, hop);
+    fill_offsets(sample_off, n_signals, frame_off, [&](int64_t n) { return pitch_frames(n, sr, hop); });
     const int64_t F = frame_off[n_signals];
     const pitch_geom g = pitch_geometry(sr);
-    const size_t need = 2 * align256(8 * (size_t)(n_signals + 1)) + align256(16 * (size_t)n_signals) + align256(8 * (size_t)g.W) +
-                        align256(8 * (size_t)(g.hi + 1));
-    if (!scratch) {
-        *scratch_bytes = (int64_t)need;
-        return GOOFER_OK;
+    if (scratch) {
+        if (!ctx) return GOOFER_EINVAL;
+        if (!y || !cand_f || !cand_s || !cand_n) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: null signal / candidates");
     }
-    if (!ctx) return GOOFER_EINVAL;
-    if (!y || !cand_f || !cand_s || !cand_n) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: null signal / candidates");
-    if (*scratch_bytes < (int64_t)need) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: scratch of %lld bytes, %zu needed", (long long)*scratch_bytes, need);
+    cand_scratch s;
+    if ((rc = caller_scratch(ctx, scratch, scratch_bytes, "tracker", [&](arena &a) { s = carve_candidates(a, n_signals, g); })) || !scratch)
+        return rc;
     hipStream_t st = (hipStream_t)stream;
-    char *p = (char *)scratch;
-    int64_t *d_soff = carve<int64_t>(p, n_signals + 1), *d_foff = carve<int64_t>(p, n_signals + 1);
-    double *stats = carve<double>(p, 2 * (size_t)n_signals), *d_win = carve<double>(p, g.W), *d_rw = carve<double>(p, g.hi + 1);
 
     // Hann window of W samples and its own autocorrelation, normalised at lag 0
     std::vector<double> win(g.W), rw(g.hi + 1);
@@ -541,18 +543,18 @@ extern "C" int goofer_track_candidates(goofer_ctx *ctx, const double *y, const i
         rw[t] = acc;
     }
     for (int t = g.hi; t >= 0; --t) rw[t] /= rw[0];
-    HIP_TRY(ctx, hipMemcpyAsync(d_soff, sample_off, 8 * (size_t)(n_signals + 1), hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(d_foff, frame_off, 8 * (size_t)(n_signals + 1), hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(d_win, win.data(), 8 * (size_t)g.W, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(d_rw, rw.data(), 8 * (size_t)(g.hi + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(s.soff, sample_off, 8 * (size_t)(n_signals + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(s.foff, frame_off, 8 * (size_t)(n_signals + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(s.win, win.data(), 8 * (size_t)g.W, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(s.rw, rw.data(), 8 * (size_t)(g.hi + 1), hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));                                            // the host vectors go out of scope
 
-    hipLaunchKernelGGL(k_pitch_stats, dim3(n_signals), dim3(TR_THREADS), 0, st, y, d_soff, stats);
+    hipLaunchKernelGGL(k_pitch_stats, dim3(n_signals), dim3(TR_THREADS), 0, st, y, s.soff, s.stats);
     LAUNCH_CHECK(ctx);
     if (F > 0) {
         const size_t lds = 8 * (size_t)(g.W + g.hi - g.lo + 1);
-        hipLaunchKernelGGL(k_pitch_frames, dim3((unsigned)F), dim3(TR_THREADS), lds, st, y, d_soff, d_foff, n_signals, sr, hop, g, d_win,
-                           d_rw, stats, cand_f, cand_s, cand_n);
+        hipLaunchKernelGGL(k_pitch_frames, dim3((unsigned)F), dim3(TR_THREADS), lds, st, y, s.soff, s.foff, n_signals, sr, hop, g, s.win,
+                           s.rw, s.stats, cand_f, cand_s, cand_n);
         LAUNCH_CHECK(ctx);
     }
     return GOOFER_OK;
@@ -566,22 +568,18 @@ extern "C" int goofer_track_path(goofer_ctx *ctx, const double *cand_f, const do
     if (rc) return rc;
     if (!scratch_bytes) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: null scratch_bytes");
     const int64_t F = frame_off[n_signals];
-    const size_t need = align256(8 * (size_t)(n_signals + 1)) + align256(TR_MAX_CAND * (size_t)F);
-    if (!scratch) {
-        *scratch_bytes = (int64_t)need;
-        return GOOFER_OK;
+    if (scratch) {
+        if (!ctx) return GOOFER_EINVAL;
+        if (F == 0) return GOOFER_OK;
+        if (!cand_f || !cand_s || !cand_n || !f0) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: null candidates / f0");
     }
-    if (!ctx) return GOOFER_EINVAL;
-    if (F == 0) return GOOFER_OK;
-    if (!cand_f || !cand_s || !cand_n || !f0) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: null candidates / f0");
-    if (*scratch_bytes < (int64_t)need) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: scratch of %lld bytes, %zu needed", (long long)*scratch_bytes, need);
+    path_scratch s;
+    if ((rc = caller_scratch(ctx, scratch, scratch_bytes, "tracker", [&](arena &a) { s = carve_path(a, n_signals, F); })) || !scratch)
+        return rc;
     hipStream_t st = (hipStream_t)stream;
-    char *p = (char *)scratch;
-    int64_t *d_foff = carve<int64_t>(p, n_signals + 1);
-    unsigned char *back = carve<unsigned char>(p, TR_MAX_CAND * (size_t)F);
-    HIP_TRY(ctx, hipMemcpyAsync(d_foff, frame_off, 8 * (size_t)(n_signals + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(s.foff, frame_off, 8 * (size_t)(n_signals + 1), hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));                                            // frame_off is the caller's host array
-    hipLaunchKernelGGL(k_pitch_viterbi, dim3(n_signals), dim3(WAVE), 0, st, d_foff, cand_f, cand_s, cand_n, 0.01 * sr / hop, back, f0);
+    hipLaunchKernelGGL(k_pitch_viterbi, dim3(n_signals), dim3(WAVE), 0, st, s.foff, cand_f, cand_s, cand_n, 0.01 * sr / hop, s.back, f0);
     LAUNCH_CHECK(ctx);
     return GOOFER_OK;
 }
@@ -590,27 +588,33 @@ extern "C" int goofer_track_pitch(goofer_ctx *ctx, const double *y, const int64_
                                   int64_t *frame_off, double *f0, void *scratch, int64_t *scratch_bytes, void *stream)
 {
     if (!scratch_bytes) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: null frame_off / scratch_bytes");
-    int64_t need_c = 0, need_p = 0;
-    int rc = goofer_track_candidates(ctx, y, sample_off, n_signals, sr, hop, frame_off, nullptr, nullptr, nullptr, nullptr, &need_c, nullptr);
+    int rc = check_batch(ctx, sample_off, n_signals, sr, hop, pitch_min_length(sr));
     if (rc) return rc;
-    rc = goofer_track_path(ctx, nullptr, nullptr, nullptr, frame_off, n_signals, sr, hop, nullptr, nullptr, &need_p, nullptr);
-    if (rc) return rc;
+    if (!frame_off) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: null frame_off / scratch_bytes");
+    fill_offsets(sample_off, n_signals, frame_off, [&](int64_t n) { return pitch_frames(n, sr, hop); });
     const int64_t F = frame_off[n_signals];
-    const size_t need = 2 * align256(8 * TR_MAX_CAND * (size_t)F) + align256(4 * (size_t)F) + align256((size_t)need_c) + (size_t)need_p;
-    if (!scratch) {
-        *scratch_bytes = (int64_t)need;
-        return GOOFER_OK;
+    if (scratch) {
+        if (!ctx) return GOOFER_EINVAL;
+        if (!y || !f0) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: null signal / f0");
     }
-    if (!ctx) return GOOFER_EINVAL;
-    if (!y || !f0) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: null signal / f0");
-    if (*scratch_bytes < (int64_t)need) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: scratch of %lld bytes, %zu needed", (long long)*scratch_bytes, need);
+    double *cand_f, *cand_s;
+    int32_t *cand_n;
+    size_t at_c, at_p, end;                                                            // the stages' blocks
+    auto carve = [&](arena &a) {
+        cand_f = a.take<double>(TR_MAX_CAND * (size_t)F);
+        cand_s = a.take<double>(TR_MAX_CAND * (size_t)F);
+        cand_n = a.take<int32_t>(F);
+        at_c = a.used;
+        carve_candidates(a, n_signals, pitch_geometry(sr));
+        at_p = a.used;
+        carve_path(a, n_signals, F);
+        end = a.used;
+    };
+    if ((rc = caller_scratch(ctx, scratch, scratch_bytes, "tracker", carve)) || !scratch) return rc;
+    int64_t need_c = at_p - at_c, need_p = end - at_p;
     char *p = (char *)scratch;
-    double *cand_f = carve<double>(p, TR_MAX_CAND * (size_t)F), *cand_s = carve<double>(p, TR_MAX_CAND * (size_t)F);
-    int32_t *cand_n = carve<int32_t>(p, F);
-    char *scratch_c = carve<char>(p, need_c), *scratch_p = p;
-    rc = goofer_track_candidates(ctx, y, sample_off, n_signals, sr, hop, frame_off, cand_f, cand_s, cand_n, scratch_c, &need_c, stream);
-    if (rc) return rc;
-    return goofer_track_path(ctx, cand_f, cand_s, cand_n, frame_off, n_signals, sr, hop, f0, scratch_p, &need_p, stream);
+    if ((rc = goofer_track_candidates(ctx, y, sample_off, n_signals, sr, hop, frame_off, cand_f, cand_s, cand_n, p + at_c, &need_c, stream))) return rc;
+    return goofer_track_path(ctx, cand_f, cand_s, cand_n, frame_off, n_signals, sr, hop, f0, p + at_p, &need_p, stream);
 }
 
 extern "C" int goofer_track_resample(goofer_ctx *ctx, const double *y, const int64_t *sample_off, int n_signals, int sr, int64_t *x_off,
@@ -619,25 +623,21 @@ extern "C" int goofer_track_resample(goofer_ctx *ctx, const double *y, const int
     int rc = check_batch(ctx, sample_off, n_signals, sr, 1, 1);
     if (rc) return rc;
     if (!x_off || !scratch_bytes) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: null x_off / scratch_bytes");
-    x_off[0] = 0;
-    for (int s = 0; s < n_signals; ++s) x_off[s + 1] = x_off[s] + resampled_length(sample_off[s + 1] - sample_off[s], sr);
+    fill_offsets(sample_off, n_signals, x_off, [&](int64_t n) { return resampled_length(n, sr); });
     const int64_t M = x_off[n_signals];
-    const size_t need = 2 * align256(8 * (size_t)(n_signals + 1));
-    if (!scratch) {
-        *scratch_bytes = (int64_t)need;
-        return GOOFER_OK;
+    if (scratch) {
+        if (!ctx) return GOOFER_EINVAL;
+        if (M == 0) return GOOFER_OK;                                                  // every signal shorter than one output sample
+        if (!y || !x11) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: null signal / x11");
     }
-    if (!ctx) return GOOFER_EINVAL;
-    if (M == 0) return GOOFER_OK;                                                      // every signal shorter than one output sample
-    if (!y || !x11) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: null signal / x11");
-    if (*scratch_bytes < (int64_t)need) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: scratch of %lld bytes, %zu needed", (long long)*scratch_bytes, need);
+    resample_scratch s;
+    if ((rc = caller_scratch(ctx, scratch, scratch_bytes, "tracker", [&](arena &a) { s = carve_resample(a, n_signals); })) || !scratch)
+        return rc;
     hipStream_t st = (hipStream_t)stream;
-    char *p = (char *)scratch;
-    int64_t *d_soff = carve<int64_t>(p, n_signals + 1), *d_moff = carve<int64_t>(p, n_signals + 1);
-    HIP_TRY(ctx, hipMemcpyAsync(d_soff, sample_off, 8 * (size_t)(n_signals + 1), hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(d_moff, x_off, 8 * (size_t)(n_signals + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(s.soff, sample_off, 8 * (size_t)(n_signals + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(s.moff, x_off, 8 * (size_t)(n_signals + 1), hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));                                            // the offsets are the caller's host arrays
-    hipLaunchKernelGGL(k_resample11k, dim3((unsigned)((M + TR_THREADS - 1) / TR_THREADS)), dim3(TR_THREADS), 0, st, y, d_soff, d_moff,
+    hipLaunchKernelGGL(k_resample11k, dim3((unsigned)((M + TR_THREADS - 1) / TR_THREADS)), dim3(TR_THREADS), 0, st, y, s.soff, s.moff,
                        n_signals, M, sr, x11);
     LAUNCH_CHECK(ctx);
     return GOOFER_OK;
@@ -649,25 +649,17 @@ extern "C" int goofer_track_formant_frames(goofer_ctx *ctx, const double *x11, c
     int rc = check_offsets(ctx, x_off, n_signals, sr, hop, "x_off");
     if (rc) return rc;
     if (!frame_off || !scratch_bytes) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: null frame_off / scratch_bytes");
-    frame_off[0] = 0;
-    for (int s = 0; s < n_signals; ++s) {
-        const int64_t m = x_off[s + 1] - x_off[s];
-        frame_off[s + 1] = frame_off[s] + (m < FM_WIN ? 0 : (m - FM_WIN) * sr / ((int64_t)FM_SR * hop) + 1);
-    }
+    fill_offsets(x_off, n_signals, frame_off, [&](int64_t m) { return formant_frames(m, sr, hop); });
     const int64_t F = frame_off[n_signals];
-    const size_t need = 2 * align256(8 * (size_t)(n_signals + 1)) + align256(8 * (size_t)FM_WIN);
-    if (!scratch) {
-        *scratch_bytes = (int64_t)need;
-        return GOOFER_OK;
+    if (scratch) {
+        if (!ctx) return GOOFER_EINVAL;
+        if (F == 0) return GOOFER_OK;                                                  // every signal shorter than a formant window
+        if (!x11 || !formants) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: null x11 / formants");
     }
-    if (!ctx) return GOOFER_EINVAL;
-    if (F == 0) return GOOFER_OK;                                                      // every signal shorter than a formant window
-    if (!x11 || !formants) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: null x11 / formants");
-    if (*scratch_bytes < (int64_t)need) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: scratch of %lld bytes, %zu needed", (long long)*scratch_bytes, need);
+    formant_scratch s;
+    if ((rc = caller_scratch(ctx, scratch, scratch_bytes, "tracker", [&](arena &a) { s = carve_formant_frames(a, n_signals); })) || !scratch)
+        return rc;
     hipStream_t st = (hipStream_t)stream;
-    char *p = (char *)scratch;
-    int64_t *d_moff = carve<int64_t>(p, n_signals + 1), *d_foff = carve<int64_t>(p, n_signals + 1);
-    double *d_gwin = carve<double>(p, FM_WIN);
 
     // Praat's Gaussian-like window: exp(-48 (i - mid)^2 / (W + 1)^2), i = 1..W, lifted to zero at the ends
     std::vector<double> gwin(FM_WIN);
@@ -676,11 +668,11 @@ extern "C" int goofer_track_formant_frames(goofer_ctx *ctx, const double *x11, c
         const double d = (j + 1.0) - 0.5 * (FM_WIN + 1);
         gwin[j] = (exp(-48.0 * d * d / ((FM_WIN + 1.0) * (FM_WIN + 1.0))) - e12) / (1.0 - e12);
     }
-    HIP_TRY(ctx, hipMemcpyAsync(d_moff, x_off, 8 * (size_t)(n_signals + 1), hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(d_foff, frame_off, 8 * (size_t)(n_signals + 1), hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(d_gwin, gwin.data(), 8 * (size_t)FM_WIN, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(s.moff, x_off, 8 * (size_t)(n_signals + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(s.foff, frame_off, 8 * (size_t)(n_signals + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(s.gwin, gwin.data(), 8 * (size_t)FM_WIN, hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));                                            // the host vectors go out of scope
-    hipLaunchKernelGGL(k_formant_frames, dim3((unsigned)F), dim3(WAVE), 0, st, x11, d_moff, d_foff, n_signals, sr, hop, d_gwin, formants);
+    hipLaunchKernelGGL(k_formant_frames, dim3((unsigned)F), dim3(WAVE), 0, st, x11, s.moff, s.foff, n_signals, sr, hop, s.gwin, formants);
     LAUNCH_CHECK(ctx);
     return GOOFER_OK;
 }
@@ -692,25 +684,27 @@ extern "C" int goofer_track_formants(goofer_ctx *ctx, const double *y, const int
     if (rc) return rc;
     if (!frame_off || !scratch_bytes) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: null frame_off / scratch_bytes");
     std::vector<int64_t> x_off(n_signals + 1);
-    int64_t need_r = 0, need_f = 0;
-    rc = goofer_track_resample(ctx, y, sample_off, n_signals, sr, x_off.data(), nullptr, nullptr, &need_r, nullptr);
-    if (rc) return rc;
-    rc = goofer_track_formant_frames(ctx, nullptr, x_off.data(), n_signals, sr, hop, frame_off, nullptr, nullptr, &need_f, nullptr);
-    if (rc) return rc;
+    fill_offsets(sample_off, n_signals, x_off.data(), [&](int64_t n) { return resampled_length(n, sr); });
+    fill_offsets(x_off.data(), n_signals, frame_off, [&](int64_t m) { return formant_frames(m, sr, hop); });
     const int64_t F = frame_off[n_signals], M = x_off[n_signals];
-    const size_t need = align256(8 * (size_t)M) + align256((size_t)need_r) + (size_t)need_f;
-    if (!scratch) {
-        *scratch_bytes = (int64_t)need;
-        return GOOFER_OK;
+    if (scratch) {
+        if (!ctx) return GOOFER_EINVAL;
+        if (F == 0) return GOOFER_OK;                                                  // every signal shorter than a formant window
+        if (!y || !formants) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: null signal / formants");
     }
-    if (!ctx) return GOOFER_EINVAL;
-    if (F == 0) return GOOFER_OK;                                                      // every signal shorter than a formant window
-    if (!y || !formants) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: null signal / formants");
-    if (*scratch_bytes < (int64_t)need) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: scratch of %lld bytes, %zu needed", (long long)*scratch_bytes, need);
+    double *x11;
+    size_t at_r, at_f, end;                                                            // the stages' blocks
+    auto carve = [&](arena &a) {
+        x11 = a.take<double>(M);
+        at_r = a.used;
+        carve_resample(a, n_signals);
+        at_f = a.used;
+        carve_formant_frames(a, n_signals);
+        end = a.used;
+    };
+    if ((rc = caller_scratch(ctx, scratch, scratch_bytes, "tracker", carve)) || !scratch) return rc;
+    int64_t need_r = at_f - at_r, need_f = end - at_f;
     char *p = (char *)scratch;
-    double *x11 = carve<double>(p, M);
-    char *scratch_r = carve<char>(p, need_r), *scratch_f = p;
-    rc = goofer_track_resample(ctx, y, sample_off, n_signals, sr, x_off.data(), x11, scratch_r, &need_r, stream);
-    if (rc) return rc;
-    return goofer_track_formant_frames(ctx, x11, x_off.data(), n_signals, sr, hop, frame_off, formants, scratch_f, &need_f, stream);
+    if ((rc = goofer_track_resample(ctx, y, sample_off, n_signals, sr, x_off.data(), x11, p + at_r, &need_r, stream))) return rc;
+    return goofer_track_formant_frames(ctx, x11, x_off.data(), n_signals, sr, hop, frame_off, formants, p + at_f, &need_f, stream);
 }

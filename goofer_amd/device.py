@@ -37,6 +37,11 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
+def _host(a):
+    """a host numpy array as a C pointer"""
+    return a.ctypes.data_as(C.c_void_p)
+
+
 class Context:
     """Owns a ``goofer_ctx`` for one device and the current (sr, n_fft, hop) plan."""
 
@@ -72,6 +77,24 @@ class Context:
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _scratch_call(self, fn, args, outs=(), tail=(), check=None):
+        """``fn`` by the caller-scratch protocol (include/goofer_hip.h): its query form, NULL outputs and scratch, which fills the
+        host offset arrays among ``args``; then the outputs the callables ``outs`` make, a scratch tensor of the reported size and
+        the call on the current stream.  ``args`` / ``tail``: fn's arguments before / behind the outputs.  Returns (outputs, call),
+        call() running the device call again.  ``Context._scratch_call(None, fn, args, check=check)``: the query alone, no handle."""
+        h, check = (None, check) if self is None else (self.h, self._check)
+        need = C.c_int64(0)
+        check(fn(h, *args, *[None] * len(outs), *tail, None, C.byref(need), None))
+        if self is None:
+            return None
+        res = [make() for make in outs]
+        scratch = torch.empty(max(int(need.value), 1), dtype=torch.uint8, device=self.device)
+
+        def call():
+            self._check(fn(self.h, *args, *map(_ptr, res), *tail, _ptr(scratch), C.byref(need), self._stream()))
+        call()
+        return res, call
 
     def tensor(self, a, dtype=None):
         t = torch.as_tensor(np.ascontiguousarray(a))
@@ -227,19 +250,13 @@ class Context:
         ``lengths`` samples per signal.  Returns (f0 [frames] fp64, f0 frame_off, formants [frames', 5] fp64, formant
         frame_off), the offsets as host int64 arrays.  Each call's scratch is a tensor of this method, released in
         stream order when it returns."""
-        if not (isinstance(y, torch.Tensor) and y.dtype == torch.float64 and y.is_contiguous() and y.device == self.device):
-            raise ValueError("track expects a contiguous fp64 tensor on this context's device")
-        lengths = [int(v) for v in lengths]
-        if not lengths or any(v < 0 for v in lengths) or sum(lengths) != y.numel():
-            raise ValueError(f"track: the lengths sum to {sum(lengths)}, the signal has {y.numel()} samples")
-        s_off = self.offsets(lengths)
+        s_off = self._track_input(y, lengths, "track")
         out = []
         for fn, width in ((self.lib.goofer_track_pitch, 1), (self.lib.goofer_track_formants, 5)):
-            f_off, need = _track_query(fn, self.h, s_off, sr, hop, self._check)
-            res = torch.empty((int(f_off[-1]), width), dtype=torch.float64, device=self.device)
-            scratch = torch.empty(max(int(need.value), 1), dtype=torch.uint8, device=self.device)
-            self._check(fn(self.h, _ptr(y), s_off.ctypes.data_as(C.c_void_p), len(lengths), int(sr), int(hop),
-                           f_off.ctypes.data_as(C.c_void_p), _ptr(res), _ptr(scratch), C.byref(need), self._stream()))
+            f_off = np.zeros(len(s_off), dtype=np.int64)
+            [res], _ = self._scratch_call(fn, (_ptr(y), _host(s_off), len(s_off) - 1, int(sr), int(hop), _host(f_off)),
+                                          [lambda f_off=f_off, width=width: torch.empty((int(f_off[-1]), width), dtype=torch.float64,
+                                                                                        device=self.device)])
             out += [res if width > 1 else res[:, 0], f_off]
         return tuple(out)
 
@@ -257,16 +274,10 @@ class Context:
         Slot 0 is the unvoiced candidate; the slots from cand_n on are 0."""
         s_off = self._track_input(y, lengths, "track_candidates")
         f_off = np.zeros(len(s_off), dtype=np.int64)
-        need = C.c_int64(0)
-        fn = self.lib.goofer_track_candidates
-        args = (s_off.ctypes.data_as(C.c_void_p), len(s_off) - 1, int(sr), int(hop), f_off.ctypes.data_as(C.c_void_p))
-        self._check(fn(self.h, None, *args, None, None, None, None, C.byref(need), None))
-        F = int(f_off[-1])
-        cf = torch.zeros((F, 15), dtype=torch.float64, device=self.device)
-        cs = torch.zeros((F, 15), dtype=torch.float64, device=self.device)
-        cn = torch.zeros(F, dtype=torch.int32, device=self.device)
-        scratch = torch.empty(max(int(need.value), 1), dtype=torch.uint8, device=self.device)
-        self._check(fn(self.h, _ptr(y), *args, _ptr(cf), _ptr(cs), _ptr(cn), _ptr(scratch), C.byref(need), self._stream()))
+        cand = lambda: torch.zeros((int(f_off[-1]), 15), dtype=torch.float64, device=self.device)   # noqa: E731
+        count = lambda: torch.zeros(int(f_off[-1]), dtype=torch.int32, device=self.device)        # noqa: E731
+        (cf, cs, cn), _ = self._scratch_call(self.lib.goofer_track_candidates,
+                                             (_ptr(y), _host(s_off), len(s_off) - 1, int(sr), int(hop), _host(f_off)), (cand, cand, count))
         return cf, cs, cn, f_off
 
     def track_path(self, cand_f, cand_s, cand_n, frame_off, sr: int, hop: int):
@@ -277,26 +288,17 @@ class Context:
             if not (isinstance(t, torch.Tensor) and t.dtype == dt and t.is_contiguous() and t.device == self.device
                     and t.shape[0] == F and t.numel() == F * (1 if dt == torch.int32 else 15)):
                 raise ValueError(f"track_path expects contiguous [{F}, 15] fp64 and [{F}] int32 tensors on this context's device")
-        need = C.c_int64(0)
-        fn = self.lib.goofer_track_path
-        args = (frame_off.ctypes.data_as(C.c_void_p), len(frame_off) - 1, int(sr), int(hop))
-        self._check(fn(self.h, None, None, None, *args, None, None, C.byref(need), None))
-        f0 = torch.empty(F, dtype=torch.float64, device=self.device)
-        scratch = torch.empty(max(int(need.value), 1), dtype=torch.uint8, device=self.device)
-        self._check(fn(self.h, _ptr(cand_f), _ptr(cand_s), _ptr(cand_n), *args, _ptr(f0), _ptr(scratch), C.byref(need), self._stream()))
+        [f0], _ = self._scratch_call(self.lib.goofer_track_path, (_ptr(cand_f), _ptr(cand_s), _ptr(cand_n), _host(frame_off),
+                                                                  len(frame_off) - 1, int(sr), int(hop)),
+                                     [lambda: torch.empty(F, dtype=torch.float64, device=self.device)])
         return f0
 
     def track_resample(self, y, lengths, sr: int):
         """The 11 kHz signals the formant stage analyses: (x11 fp64 device tensor, x_off host int64)."""
         s_off = self._track_input(y, lengths, "track_resample")
         x_off = np.zeros(len(s_off), dtype=np.int64)
-        need = C.c_int64(0)
-        fn = self.lib.goofer_track_resample
-        args = (s_off.ctypes.data_as(C.c_void_p), len(s_off) - 1, int(sr), x_off.ctypes.data_as(C.c_void_p))
-        self._check(fn(self.h, None, *args, None, None, C.byref(need), None))
-        x11 = torch.empty(int(x_off[-1]), dtype=torch.float64, device=self.device)
-        scratch = torch.empty(max(int(need.value), 1), dtype=torch.uint8, device=self.device)
-        self._check(fn(self.h, _ptr(y), *args, _ptr(x11), _ptr(scratch), C.byref(need), self._stream()))
+        [x11], _ = self._scratch_call(self.lib.goofer_track_resample, (_ptr(y), _host(s_off), len(s_off) - 1, int(sr), _host(x_off)),
+                                      [lambda: torch.empty(int(x_off[-1]), dtype=torch.float64, device=self.device)])
         return x11, x_off
 
     def track_formant_frames(self, x11, lengths11, sr: int, hop: int):
@@ -304,13 +306,9 @@ class Context:
         would place them, and their frame_off (host int64)."""
         x_off = self._track_input(x11, lengths11, "track_formant_frames")
         f_off = np.zeros(len(x_off), dtype=np.int64)
-        need = C.c_int64(0)
-        fn = self.lib.goofer_track_formant_frames
-        args = (x_off.ctypes.data_as(C.c_void_p), len(x_off) - 1, int(sr), int(hop), f_off.ctypes.data_as(C.c_void_p))
-        self._check(fn(self.h, None, *args, None, None, C.byref(need), None))
-        forms = torch.empty((int(f_off[-1]), 5), dtype=torch.float64, device=self.device)
-        scratch = torch.empty(max(int(need.value), 1), dtype=torch.uint8, device=self.device)
-        self._check(fn(self.h, _ptr(x11), *args, _ptr(forms), _ptr(scratch), C.byref(need), self._stream()))
+        [forms], _ = self._scratch_call(self.lib.goofer_track_formant_frames,
+                                        (_ptr(x11), _host(x_off), len(x_off) - 1, int(sr), int(hop), _host(f_off)),
+                                        [lambda: torch.empty((int(f_off[-1]), 5), dtype=torch.float64, device=self.device)])
         return forms, f_off
 
     def per_sample_f0(self, tracks, track_lengths, sample_lengths, sr, f0_min=75, f0_merge_range=2):
@@ -327,16 +325,10 @@ class Context:
             raise ValueError(f"per_sample_f0: track lengths {min(t_len)}.. summing to {sum(t_len)} for {tracks.numel()} frames, "
                              f"sample lengths from {min(s_len)} (every track needs two frames, no length may be negative)")
         t_off, s_off = self.offsets(t_len), self.offsets(s_len)
-        args = (t_off.ctypes.data_as(C.c_void_p), s_off.ctypes.data_as(C.c_void_p), len(t_len), float(sr), float(f0_min),
-                int(min(f0_merge_range, 2 ** 31 - 1)))
-        need = C.c_int64(0)
-        self._check(self.lib.goofer_per_sample_f0(self.h, None, *args, None, None, None, C.byref(need), None))
-        n = int(s_off[-1])
-        f0 = torch.empty(n, dtype=torch.float64, device=self.device)
-        mask = torch.empty(n, dtype=torch.float64, device=self.device)
-        scratch = torch.empty(max(int(need.value), 1), dtype=torch.uint8, device=self.device)
-        self._check(self.lib.goofer_per_sample_f0(self.h, _ptr(tracks), *args, _ptr(f0), _ptr(mask), _ptr(scratch), C.byref(need),
-                                                  self._stream()))
+        samples = lambda: torch.empty(int(s_off[-1]), dtype=torch.float64, device=self.device)   # noqa: E731
+        (f0, mask), _ = self._scratch_call(self.lib.goofer_per_sample_f0, (_ptr(tracks), _host(t_off), _host(s_off), len(t_len), float(sr),
+                                                                          float(f0_min), int(min(f0_merge_range, 2 ** 31 - 1))),
+                                           (samples, samples))
         return f0, mask
 
     # -- analysis (GOOFER.py:942-946, 97-147) -----------------------------------------------------
@@ -360,19 +352,16 @@ class Context:
         (hz, bins), t_env, t_fit = tabs[1], tabs[2], tabs[3]
         s_off = self.offsets(lengths)
         f_off = np.zeros(len(lengths) + 1, dtype=np.int64)
-        need = C.c_int64(0)
-        vp = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
-        args = (vp(t_env), (t_env.size - 1) // 2, vp(t_fit), (t_fit.size - 1) // 2, vp(hz), vp(bins), vp(f_off))
-        self._check(self.lib.goofer_envelope_knots_batch(self.h, None, vp(s_off), len(lengths), *args, None, None, None, 0, None,
-                                                         C.byref(need), None))
-        F, nb = int(f_off[-1]), self.n_bins
-        knots = torch.empty((F, 192), dtype=torch.float16, device=self.device)
-        K = torch.empty(len(lengths), dtype=torch.int32, device=self.device)
+        nb = self.n_bins
         ld64 = (nb + 1) & ~1
-        env = torch.empty((F, ld64), dtype=torch.float64, device=self.device) if want_env else None
-        scratch = torch.empty(max(int(need.value), 1), dtype=torch.uint8, device=self.device)
-        self._check(self.lib.goofer_envelope_knots_batch(self.h, _ptr(y32), vp(s_off), len(lengths), *args, _ptr(knots), _ptr(K),
-                                                         _ptr(env), ld64, _ptr(scratch), C.byref(need), self._stream()))
+        (knots, K, env), _ = self._scratch_call(
+            self.lib.goofer_envelope_knots_batch,
+            (_ptr(y32), _host(s_off), len(lengths), _host(t_env), (t_env.size - 1) // 2, _host(t_fit), (t_fit.size - 1) // 2, _host(hz),
+             _host(bins), _host(f_off)),
+            (lambda: torch.empty((int(f_off[-1]), 192), dtype=torch.float16, device=self.device),
+             lambda: torch.empty(len(lengths), dtype=torch.int32, device=self.device),
+             lambda: torch.empty((int(f_off[-1]), ld64), dtype=torch.float64, device=self.device) if want_env else None),
+            tail=(ld64,))
         return knots, K, f_off, (env[:, :nb] if want_env else None)
 
     def gauss_bins_f64(self, rows, taps: np.ndarray):
@@ -670,15 +659,6 @@ class Context:
         return out
 
 
-def _track_query(fn, h, s_off, sr, hop, check):
-    """(frame_off, scratch bytes) of a goofer_track_* call: its query form, which runs no device code."""
-    f_off = np.zeros(len(s_off), dtype=np.int64)
-    need = C.c_int64(0)
-    check(fn(h, None, s_off.ctypes.data_as(C.c_void_p), len(s_off) - 1, int(sr), int(hop), f_off.ctypes.data_as(C.c_void_p),
-             None, None, C.byref(need), None))
-    return f_off, need
-
-
 def track_frame_offsets(lengths, sr: int, hop: int):
     """(f0 frame_off, formant frame_off) the tracker gives signals of these lengths, from the library's own layout; needs
     no device."""
@@ -689,7 +669,12 @@ def track_frame_offsets(lengths, sr: int, hop: int):
     def check(rc):
         if rc != 0:
             raise GooferError(f"libgoofer_hip error {rc}: the tracker refuses this batch (sample rate, hop or a signal length)")
-    return tuple(_track_query(fn, None, s_off, sr, hop, check)[0] for fn in (lib.goofer_track_pitch, lib.goofer_track_formants))
+    out = []
+    for fn in (lib.goofer_track_pitch, lib.goofer_track_formants):
+        f_off = np.zeros(len(s_off), dtype=np.int64)
+        Context._scratch_call(None, fn, (None, _host(s_off), len(s_off) - 1, int(sr), int(hop), _host(f_off), None), check=check)
+        out.append(f_off)
+    return tuple(out)
 
 
 def _ratios(subharm):

@@ -288,6 +288,12 @@ int goofer_knot_decode(goofer_ctx *ctx, const uint16_t *knots_f16, int K, const 
 
 /* ---- analysis half that does not need Praat (GOOFER.py:942-946, 97-147) -------------------------------- */
 
+/* Caller scratch: goofer_envelope_knots_batch, the goofer_track_* calls and goofer_per_sample_f0 take device scratch from the
+ * caller.  Call once with scratch = NULL, the query form: the batch is checked as the call checks it, the HOST offset arrays
+ * the call writes and *scratch_bytes are filled in, and no device code runs (ctx may be NULL, but for
+ * goofer_envelope_knots_batch, which needs the plan).  Then call with device scratch of at least *scratch_bytes bytes (a
+ * shorter block: GOOFER_EINVAL, before anything is launched); it is in use until the stream reaches the end of the call. */
+
 /* The pieces of compress_env_to_knots for a caller's envelope (core.compress_env_to_knots runs the K search on the host). */
 
 /* gaussian_filter1d(axis=bins) with the reference's fp64 result kept: in fp32 [rows x ld] -> out fp64 [rows x ld64];
@@ -318,9 +324,7 @@ int goofer_knot_gather(goofer_ctx *ctx, const double *env, int ld64, int64_t row
  *   = 1232 entries each) in HOST memory.
  *   knots_f16 [frame_off[n] x 192] (device): signal s writes its [T_s x K_s] knots frames-major at frame_off[s] * 192.
  *   K_out [n_signals] int32 (device).  env_rows (device, or NULL): the sigma-2 envelope in fp64, [frame_off[n] x ld64].
- * Call once with y = NULL: frame_off and *scratch_bytes are filled in and no device code runs.  Then call with device scratch of
- * at least that many bytes; it is in use until the stream reaches the end of the call.  The call synchronises the stream once,
- * after uploading its tables and before its kernels. */
+ * Caller scratch as above.  The call synchronises the stream once, after uploading its tables and before its kernels. */
 int goofer_envelope_knots_batch(goofer_ctx *ctx, const float *y, const int64_t *sample_off, int n_signals, const double *taps_env,
                                 int radius_env, const double *taps_fit, int radius_fit, const float *hz_knots, const int32_t *knot_bin,
                                 int64_t *frame_off, uint16_t *knots_f16, int32_t *K_out, double *env_rows, int ld64, void *scratch,
@@ -328,9 +332,7 @@ int goofer_envelope_knots_batch(goofer_ctx *ctx, const float *y, const int64_t *
 
 /* ---- f0 and formant tracks of the cold-cache analysis (goofer_amd/csrc/tracker.hip) -------------------------------
  * A ragged batch of fp64 signals y (device) at one sample rate sr in [8000, 96000]; sample_off[n_signals+1] and
- * frame_off[n_signals+1] are HOST arrays, frame_off is written by the call.  Call once with scratch = NULL (ctx may be NULL
- * too): frame_off and *scratch_bytes are filled in and nothing else happens.  Then call with device scratch of at least
- * that many bytes; the scratch is the caller's and is in use until the stream reaches the end of the call.
+ * frame_off[n_signals+1] are HOST arrays, frame_off is written by the call; caller scratch as above.
  *
  * goofer_track_pitch: Boersma's autocorrelation method with a Viterbi path, floor 75 Hz, ceiling min(950, sr/2) Hz,
  * time step hop / sr, window 3 / 75 s (Hann).  Frames: floor((n - 3 sr / 75) / hop) + 1 per signal, centred in it.
@@ -348,8 +350,8 @@ int goofer_track_pitch(goofer_ctx *ctx, const double *y, const int64_t *sample_o
 int goofer_track_formants(goofer_ctx *ctx, const double *y, const int64_t *sample_off, int n_signals, int sr, int hop,
                           int64_t *frame_off, double *formants, void *scratch, int64_t *scratch_bytes, void *stream);
 
-/* Single-stage entry points of the tracker (unit parity), with the conventions above: HOST offset arrays, the query form
- * with scratch = NULL, device arrays otherwise.
+/* Single-stage entry points of the tracker (unit parity), with the conventions above: HOST offset arrays, caller scratch,
+ * device arrays otherwise.
  * goofer_track_candidates: goofer_track_pitch's per-frame stage.  cand_f, cand_s [frame_off[n] x 15] fp64 and cand_n
  * [frame_off[n]] int32 (device): frame f has cand_n[f] candidates; slot 0 is the unvoiced one (frequency 0, the unvoiced
  * strength), slots 1.. the voiced ones in lag order (frequency in Hz, strength); the slots from cand_n[f] on are not written.
@@ -376,8 +378,7 @@ int goofer_track_formant_frames(goofer_ctx *ctx, const double *x11, const int64_
  * over np.linspace(0, n / sr) grids of the track and of the n samples (0 outside the track), clip to [1e-5, 2000].
  * tracks [track_off[n_signals]] fp64 (device); track_off and sample_off [n_signals + 1] are HOST arrays starting at 0, every track
  * with two frames at least (one frame or none: GOOFER_EINVAL; the host handles them).  Writes f0 and mask (f0 > f0_min as 0 / 1)
- * [sample_off[n_signals]] fp64, bit for bit numpy's.  Call once with scratch = NULL (ctx may be NULL too) for *scratch_bytes; then
- * with device scratch of that many bytes, the caller's and in use until the stream reaches the end of the call. */
+ * [sample_off[n_signals]] fp64, bit for bit numpy's.  Caller scratch as above. */
 int goofer_per_sample_f0(goofer_ctx *ctx, const double *tracks, const int64_t *track_off, const int64_t *sample_off, int n_signals,
                          double sr, double f0_min, int max_gap, double *f0, double *mask, void *scratch, int64_t *scratch_bytes,
                          void *stream);

@@ -3,7 +3,6 @@
 python scripts/tracker_rate.py [--signals 64] [--seconds 1.0] [--sr 44100] [--hop 256] [--reps 5]
 Prints one JSON line.  The batch is ground-truth-like signals (harmonics through five resonators) of equal length."""
 import argparse
-import ctypes as C
 import json
 import os
 import sys
@@ -13,7 +12,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from goofer_amd.device import Context, _ptr  # noqa: E402
+from goofer_amd.device import Context, _host, _ptr  # noqa: E402
 
 
 def main():
@@ -38,19 +37,16 @@ def main():
     times = {}
     for name, fn, width in (("pitch", ctx.lib.goofer_track_pitch, 1), ("formants", ctx.lib.goofer_track_formants, 5)):
         f_off = np.zeros(a.signals + 1, dtype=np.int64)
-        need = C.c_int64(0)
-        args = (off.ctypes.data_as(C.c_void_p), a.signals, a.sr, a.hop, f_off.ctypes.data_as(C.c_void_p))
-        ctx._check(fn(ctx.h, None, *args, None, None, C.byref(need), None))
-        out = torch.empty((int(f_off[-1]), width), dtype=torch.float64, device=ctx.device)
-        scratch = torch.empty(int(need.value), dtype=torch.uint8, device=ctx.device)
+        # the first call (the helper's) warms up; the timed ones reuse its output and scratch
+        _, call = ctx._scratch_call(fn, (_ptr(y), _host(off), a.signals, a.sr, a.hop, _host(f_off)),
+                                    [lambda: torch.empty((int(f_off[-1]), width), dtype=torch.float64, device=ctx.device)])
         best = []
-        for r in range(a.reps + 1):
+        for _ in range(a.reps):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            ctx._check(fn(ctx.h, _ptr(y), *args, _ptr(out), _ptr(scratch), C.byref(need), ctx._stream()))
+            call()
             torch.cuda.synchronize()
-            if r:                                                   # the first call warms up
-                best.append(time.perf_counter() - t0)
+            best.append(time.perf_counter() - t0)
         times[name] = {"median_s": float(np.median(best)), "frames": int(f_off[-1])}
     audio = a.signals * a.seconds
     res = {"signals": a.signals, "seconds_each": a.seconds, "sr": a.sr, "hop": a.hop,
