@@ -164,17 +164,14 @@ int kernel_resident_waves(goofer_ctx *ctx, const void *fn, size_t lds, int *wave
 
 // ---------------------------------------------------------------------------------------------
 // small helper kernels of the batch driver
-// picks != nullptr: also the frame's picks of the per-sample arrays, x[::hop] edge-padded to the frame count
-// (GOOFER.py:1104-1106), as one (f0, mask) record per frame.  The shaping kernels then find them one dependent load
-// earlier (frame -> record) instead of three (frame -> note -> offsets -> sample).
-__global__ void k_row_src(const int64_t *__restrict__ frame_off, const int64_t *__restrict__ env_off,
-                          const int *__restrict__ frame_note, int64_t total_frames, int64_t *__restrict__ row_src,
-                          const int64_t *__restrict__ sample_off, const float *__restrict__ f0, const float *__restrict__ mask,
-                          int hop, float2 *__restrict__ picks)
+// Frame f of `note` -> its envelope row and, with picks != nullptr, the frame's picks of the per-sample arrays, x[::hop]
+// edge-padded to the frame count (GOOFER.py:1104-1106), as one (f0, mask) record per frame.  The shaping kernels then find
+// them one dependent load earlier (frame -> record) instead of three (frame -> note -> offsets -> sample).
+__device__ __forceinline__ void frame_pick_and_row(int64_t f, int note, const int64_t *__restrict__ frame_off,
+                                                   const int64_t *__restrict__ env_off, int64_t *__restrict__ row_src,
+                                                   const int64_t *__restrict__ sample_off, const float *__restrict__ f0,
+                                                   const float *__restrict__ mask, int hop, float2 *__restrict__ picks)
 {
-    int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= total_frames) return;
-    int note = frame_note[f];
     int64_t t = f - frame_off[note];
     if (picks) {
         const int64_t base = sample_off[note], n = sample_off[note + 1] - base;
@@ -186,10 +183,20 @@ __global__ void k_row_src(const int64_t *__restrict__ frame_off, const int64_t *
         }
         picks[f] = pv;
     }
-    int64_t rows = env_off[note + 1] - env_off[note];
+    const int64_t rows = env_off[note + 1] - env_off[note];
     if (t > rows - 1) t = rows - 1;     // edge-repeat (np.pad mode='edge'); truncation is implicit
     if (t < 0) t = 0;
     row_src[f] = env_off[note] + t;
+}
+
+__global__ void k_row_src(const int64_t *__restrict__ frame_off, const int64_t *__restrict__ env_off,
+                          const int *__restrict__ frame_note, int64_t total_frames, int64_t *__restrict__ row_src,
+                          const int64_t *__restrict__ sample_off, const float *__restrict__ f0, const float *__restrict__ mask,
+                          int hop, float2 *__restrict__ picks)
+{
+    int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= total_frames) return;
+    frame_pick_and_row(f, frame_note[f], frame_off, env_off, row_src, sample_off, f0, mask, hop, picks);
 }
 
 // The frame maps of the stem path in one launch (they were a memset and three small kernels in a row on the critical path,
@@ -211,21 +218,7 @@ __global__ void k_frame_maps(const int64_t *__restrict__ frame_off, const int64_
     if (f >= total_frames) return;
     const int note = csr_find(frame_off, n_notes, f);
     frame_note[f] = note;
-    int64_t t = f - frame_off[note];
-    if (picks) {
-        const int64_t base = sample_off[note], n = sample_off[note + 1] - base;
-        float2 pv = make_float2(0.f, 0.f);
-        if (n > 0) {
-            int64_t at = t * hop;
-            if (at >= n) at = ((n - 1) / hop) * hop;          // edge-padded: the last pick
-            pv = make_float2(f0[base + at], mask[base + at]);
-        }
-        picks[f] = pv;
-    }
-    const int64_t rows = env_off[note + 1] - env_off[note];
-    if (t > rows - 1) t = rows - 1;     // edge-repeat (np.pad mode='edge'); truncation is implicit
-    if (t < 0) t = 0;
-    row_src[f] = env_off[note] + t;
+    frame_pick_and_row(f, note, frame_off, env_off, row_src, sample_off, f0, mask, hop, picks);
 }
 
 // f0 *= pitch_shift (GOOFER.py:995), fp32.  1024 samples per workgroup, 16-byte accesses when the tile sits in one note.

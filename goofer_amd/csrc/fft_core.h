@@ -524,85 +524,6 @@ template <int M> constexpr size_t fft_lds_bytes()
 }
 
 
-// irFFT input stage: X[k], k = 0..M (any addressable array: global row or LDS) -> the M/64 values this
-// lane feeds into wave_fft (conj trick).  Im(DC) and Im(Nyquist) are ignored like pocketfft's c2r.
-template <int M, typename Spec>
-__device__ __forceinline__ void irfft_load(float2 *v, const Spec &X, const float2 *twh, int lane)
-{
-    constexpr int R = fft_cfg<M>::R;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        int k = lane + WAVE * r;
-        float2 xk = X(k);
-        float2 xm = X(M - k);
-        if (k == 0) { xk.y = 0.f; xm.y = 0.f; }
-        float2 wc = (k <= M / 2) ? cconj(twh[k]) : make_float2(-twh[M - k].x, -twh[M - k].y);
-        v[r] = irfft_pre(xk, xm, wc);                                     // conj(A + iC); the 1/2 rides on irfft_store's scale
-    }
-}
-
-// irFFT output stage: natural-order result in `buf` -> windowed time frame (`frames*window`, GOOFER.py:383)
-template <int M>
-__device__ __forceinline__ void irfft_store(const float2 *buf, const float *win, float *frame, int lane)
-{
-    constexpr int R = fft_cfg<M>::R;
-    const float inv_m = 0.5f / (float)M;                    // 1/M of the transform and the 1/2 of the input stage
-    float2 *out = reinterpret_cast<float2 *>(frame);
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        int m = lane + WAVE * r;
-        float2 z = buf[lds_pad(m)];
-        float a = z.x * inv_m, b = -z.y * inv_m;
-        out[m] = make_float2(a * win[2 * m], b * win[2 * m + 1]);
-    }
-}
-
-// rFFT input stage: M/64 (even, odd) windowed sample pairs of the frame starting at un-padded sample
-// `start` of a note of n samples (numpy 'reflect' padding; n == 1 is 'edge')   GOOFER.py:358-369
-template <int M>
-__device__ __forceinline__ void rfft_load(float2 *v, const float *xs, int64_t start, int64_t n, const float *win, int lane)
-{
-    constexpr int R = fft_cfg<M>::R;
-    if (start >= 0 && start + 2 * M <= n) {
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            int m = lane + WAVE * r;
-            v[r] = make_float2(xs[start + 2 * m] * win[2 * m], xs[start + 2 * m + 1] * win[2 * m + 1]);
-        }
-    } else {
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            int m = lane + WAVE * r;
-            float a = n > 0 ? xs[reflect_index(start + 2 * m, n)] : 0.f;
-            float b = n > 0 ? xs[reflect_index(start + 2 * m + 1, n)] : 0.f;
-            v[r] = make_float2(a * win[2 * m], b * win[2 * m + 1]);
-        }
-    }
-}
-
-// rFFT output stage: even/odd split of the complex result in `buf` -> X[k], k = 0..M, through a sink
-//   X[k] = (Z[k] + conj Z[M-k])/2 - i/2 e^{-i pi k/M} (Z[k] - conj Z[M-k])
-template <int M, typename Sink>
-__device__ __forceinline__ void rfft_split(const float2 *buf, const float2 *twh, int lane, Sink &&put)
-{
-    constexpr int R = fft_cfg<M>::R;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        int k = lane + WAVE * r;
-        float2 zk = buf[lds_pad(k)];
-        float2 zm = buf[lds_pad(k == 0 ? 0 : M - k)];
-        float2 w = (k <= M / 2) ? twh[k] : make_float2(-twh[M - k].x, twh[M - k].y);
-        float2 A = make_float2(zk.x + zm.x, zk.y - zm.y);
-        float2 B = make_float2(zk.x - zm.x, zk.y + zm.y);
-        float2 C = cmul(w, B);
-        put(k, make_float2(0.5f * (A.x + C.y), 0.5f * (A.y - C.x)));
-    }
-    if (lane == 0) {
-        float2 z0 = buf[0];
-        put(M, make_float2(z0.x - z0.y, 0.f));
-    }
-}
-
 // ---------------------------------------------------------------------------------------------
 // Workgroup transform (complex N = 2048 / 4096: the real n_fft 4096 transform and the Bluestein length of the even n_fft in
 // [2052, 4094]).  One wave would hold 32 / 64 points per lane, past the register file, so the frame is shared by the four
@@ -664,3 +585,28 @@ __device__ __forceinline__ void wg_fft(float2 *v, float2 *buf, const float2 *tw,
         wg_radix_pass<N, 16, 256>(buf, tw, tid);
     }
 }
+
+// ---------------------------------------------------------------------------------------------
+// Who holds a frame.  The framewise kernels of fft.hip are written once, against an owner: the 64-lane wave (transforms of up
+// to 2048 points) or the 256-thread workgroup (above).  Compile-time policy only, nothing is decided at run time.
+//   W, P     threads of the owner; points of the N-point transform per thread (its first-pass radix)
+//   BUF      float2 slots of the owner's padded exchange buffer
+//   FRAMES   contiguous frames per 256-thread block; the owner visits first(), first() + STEP, ... of them — a wave every
+//            fourth of 32 (first() is also the index of its buffer), a workgroup all 16 in turn
+constexpr int WG_FRAMES_PER_BLOCK = 16;
+
+template <int N_> struct wave_owner {
+    static constexpr int N = N_, W = WAVE, P = fft_cfg<N>::R, BUF = fft_cfg<N>::BUF, FRAMES = FRAMES_PER_BLOCK, STEP = WAVES_PER_BLOCK;
+    __device__ __forceinline__ static int tid() { return threadIdx.x & 63; }
+    __device__ __forceinline__ static int first() { return __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); }
+    __device__ __forceinline__ static void fft(float2 *v, float2 *buf, const float2 *tw, int tid) { wave_fft<N>(v, buf, tw, tid); }
+    __device__ __forceinline__ static void sync() { wave_lds_sync(); }
+};
+
+template <int N_> struct wg_owner {
+    static constexpr int N = N_, W = WG_THREADS, P = wg_cfg<N>::P, BUF = wg_cfg<N>::BUF, FRAMES = WG_FRAMES_PER_BLOCK, STEP = 1;
+    __device__ __forceinline__ static int tid() { return threadIdx.x; }
+    __device__ __forceinline__ static int first() { return 0; }
+    __device__ __forceinline__ static void fft(float2 *v, float2 *buf, const float2 *tw, int tid) { wg_fft<N>(v, buf, tw, tid); }
+    __device__ __forceinline__ static void sync() { __syncthreads(); }       // uniform over the workgroup: its frame loop has one bound
+};
