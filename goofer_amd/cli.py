@@ -47,10 +47,17 @@ class BatchCollector:
     """Gathers concurrent render requests and runs them as device batches — up to ``lanes`` batches in flight: each lane is a
     Renderer with its own library handle and HIP stream (the voicebank arena is shared), so while one batch is on the device
     or being written out, the requests that arrived meanwhile are decoded, planned and rendered on the other lane
-    (SillySampler.py:1196-1224 answers every request with its own render; a song is thousands of them)."""
+    (SillySampler.py:1196-1224 answers every request with its own render; a song is thousands of them).
+    ``noise``: "host" / "device" for the lanes made here (sampler.resolve_noise: None reads ``$GOOFER_NOISE``); an injected
+    renderer brings its own."""
 
     def __init__(self, renderer=None, window_s: float = 0.005, max_batch: int = 4096, max_sources: int = 512, tracker=None,
-                 lanes: int = 2):
+                 lanes: int = 2, noise=None):
+        self.noise = S.resolve_noise(noise)                 # (raises before a thread or a lane exists)
+        if renderer is not None:
+            if noise is not None and getattr(renderer, "noise", self.noise) != self.noise:
+                raise ValueError(f"noise={noise!r}, but the renderer handed in was made with noise={renderer.noise!r}")
+            self.noise = getattr(renderer, "noise", self.noise)
         self._renderer = renderer                           # an injected renderer is the only lane
         self._n_lanes = 1 if renderer is not None else max(1, int(lanes))
         self._lanes = None                                  # made on first use: [(Renderer, stream or None)]
@@ -80,10 +87,10 @@ class BatchCollector:
                 import torch
                 from .device import Context
                 from .render import Renderer
-                first = Renderer()
+                first = Renderer(noise=self.noise)
                 self._lanes = [(first, torch.cuda.Stream(first.ctx.device))]
                 for _ in range(self._n_lanes - 1):
-                    r = Renderer(Context(first.ctx.device.index if first.ctx.device.index is not None else 0), hop=first.hop)
+                    r = Renderer(Context(first.ctx.device.index if first.ctx.device.index is not None else 0), hop=first.hop, noise=self.noise)
                     r.sources = first.sources
                     self._lanes.append((r, torch.cuda.Stream(r.ctx.device)))
             self._free = queue.Queue()

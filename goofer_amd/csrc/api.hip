@@ -64,6 +64,8 @@ int launch_f0_jitter(goofer_ctx *, float *, double *, const float *, const doubl
 int launch_volume_jitter(goofer_ctx *, float *, float *, const double *, const double *, const double *, const unsigned long long *,
                          const unsigned long long *, const int64_t *, int, int64_t, const goofer_note_params *, int, double, hipStream_t);
 int launch_onepole(goofer_ctx *, const float *, float *, const float *, const goofer_onepole_job *, int, hipStream_t);
+int launch_normal_fill(goofer_ctx *, uint64_t, const goofer_note_params *, const int64_t *, int, int64_t, int, const unsigned char *,
+                       const double *, double *, hipStream_t);
 int launch_post_layers(goofer_ctx *, float *, const float *, const float *, const goofer_post_note *, const int64_t *, int, int64_t,
                        hipStream_t);
 int launch_post_fry(goofer_ctx *, float *, float *, const float *, const float *, const goofer_post_note *, const int64_t *, int, int64_t,
@@ -1276,6 +1278,19 @@ int goofer_assemble_batch(goofer_ctx *ctx, const goofer_assembly *asmb, void *st
     if (rc) return rc;
     if (!a.edit_rows) a.edit_rows = edit_rows;
     return launch_assemble(ctx, &a, map_edit, map_edit + a.total_edit_rows, recs, st);
+}
+
+int goofer_normal_fill(goofer_ctx *ctx, uint64_t seed, const goofer_note_params *params, const int64_t *sample_off, int n_notes,
+                       int64_t total_samples, int stream_tag, const unsigned char *note_on, const double *growl_scale, double *out,
+                       void *stream)
+{
+    if (!ctx) return GOOFER_EINVAL;
+    if (!params || !sample_off || !out) return goofer_fail(ctx, GOOFER_EINVAL, "goofer_normal_fill: null pointer");
+    if (n_notes < 0 || total_samples < 0)
+        return goofer_fail(ctx, GOOFER_EINVAL, "goofer_normal_fill: negative count (%d notes, %lld samples)", n_notes, (long long)total_samples);
+    if (stream_tag < 0 || stream_tag > 4) return goofer_fail(ctx, GOOFER_EINVAL, "goofer_normal_fill: stream tag %d outside 0..4", stream_tag);
+    if ((uintptr_t)out & 15) return goofer_fail(ctx, GOOFER_EINVAL, "goofer_normal_fill: out must be 16-byte aligned");
+    return launch_normal_fill(ctx, seed, params, sample_off, n_notes, total_samples, stream_tag, note_on, growl_scale, out, (hipStream_t)stream);
 }
 
 int goofer_stretch_rows(goofer_ctx *ctx, const float *in, int64_t ld_in, int64_t rows_in, float *out, int64_t ld_out, int64_t rows_out,

@@ -486,12 +486,14 @@ __device__ __forceinline__ float2 blur5(const float2 *r, int k, int n_bins, cons
 // reference's float32 uniforms resolve finer, no ear or statistic does).  The phase of bin k comes from slot (k & 63) + 64 (k >> 9),
 // word (k >> 7) & 3, half (k >> 6) & 1 — so a lane that owns bins lane, lane + 64, ... needs ONE block per eight of its bins (one
 // block per frame for n_fft 1024; it was two with 24-bit phases).  philox_u16 is the same mapping evaluated for a single bin.
-__device__ __forceinline__ uint4 philox_4x32(uint64_t seed, uint64_t ctr_hi, uint32_t ctr_lo)
+// philox_rounds: the block function itself, counter words and key passed through (ROUNDS = 10 is Random123's philox4x32-10);
+// the phases' 7 rounds and the jitter / growl normals' 10 (noise.hip) share it.
+#define PHILOX_PHASE_C3 0x9E3779B9u   // counter word 3 of every phase block; the normals use another (noise.hip)
+template <int ROUNDS>
+__device__ __forceinline__ uint4 philox_rounds(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1)
 {
-    uint32_t c0 = ctr_lo, c1 = (uint32_t)ctr_hi, c2 = (uint32_t)(ctr_hi >> 32), c3 = 0x9E3779B9u;
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
 #pragma unroll
-    for (int i = 0; i < 7; ++i) {
+    for (int i = 0; i < ROUNDS; ++i) {
         uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
         uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1;
         uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
@@ -499,6 +501,11 @@ __device__ __forceinline__ uint4 philox_4x32(uint64_t seed, uint64_t ctr_hi, uin
         k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
     }
     return make_uint4(c0, c1, c2, c3);
+}
+
+__device__ __forceinline__ uint4 philox_4x32(uint64_t seed, uint64_t ctr_hi, uint32_t ctr_lo)
+{
+    return philox_rounds<7>(ctr_lo, (uint32_t)ctr_hi, (uint32_t)(ctr_hi >> 32), PHILOX_PHASE_C3, (uint32_t)seed, (uint32_t)(seed >> 32));
 }
 
 __device__ __forceinline__ uint32_t philox_half(const uint4 &v, int i)       // i = index of the bin among its lane's eight

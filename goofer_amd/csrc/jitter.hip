@@ -6,7 +6,10 @@
 //   k_note_absmax     per-note max(|x| + 1e-6)  ("noise /= np.max(np.abs(noise) + 1e-6)")   GOOFER.py:655, 668
 //   k_f0_jitter       f0 *= 1 + (jitter - 1) * mask,  jitter = 1 + noise/max * strength    GOOFER.py:669, 1071
 //   k_volume_jitter   harm *= 1 + (jh - 1) * vjm ;  bre *= 1 + (jb - 1) * vjm              GOOFER.py:1187-1191
-// The random draws themselves come from the host (the reference uses the legacy global np.random stream);
+// The random draws are the caller's arrays (goofer_batch.noise_f0 / noise_vol_h / noise_vol_b): from the host's legacy global
+// np.random stream, the reference's and what seeded fixtures pin (the default), or from goofer_normal_fill (noise.hip:
+// noise="device", a counter-based stream keyed like the phases).  The kernels here gate per note and read no sample of a note
+// without the flag, so either source leaves those ranges as it likes;
 // each wave stages its window in LDS so every input sample is fetched once per 64 outputs.
 #include "common.h"
 

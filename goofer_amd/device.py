@@ -186,6 +186,50 @@ class Context:
         self._check(self.lib.goofer_pcm16(self.h, _ptr(x), x.numel(), _ptr(out), self._stream()))
         return out
 
+    def normal_fill(self, seed: int, params, lengths_or_offsets, tag: int, note_on=None, growl_scale=None, out=None):
+        """float64 standard normals of stream ``tag`` (0 f0 jitter, 1 / 2 harmonic / breath volume jitter, 3 sub-harmonic f0
+        jitter, 4 growl) for the notes of a ragged batch, drawn on the device (goofer_normal_fill; the stream's definition:
+        include/goofer_hip.h, restated in tests/noise_ref.py).  A note's draws depend on ``seed ^ params[note].seed`` and the
+        tag only.  Asynchronous on the current stream.
+
+        ``params``: a NOTE_PARAMS array, or its device copy (``device_offsets(..)["d_par"]``).  ``lengths_or_offsets``: the notes'
+        sample counts (host sequence), or the device int64 CSR offsets ``[n + 1]`` — then ``out`` gives the total.
+        ``note_on``: per-note switch (host sequence or device uint8 tensor); the samples of the other notes are left as they
+        are.  ``growl_scale``: per-note float64 (host or device) — writes ``0.5 * 2 ** (scale * z)`` instead of z.  ``out``:
+        a contiguous float64 device tensor of the batch's samples to fill (default: a new one)."""
+        keep = []
+
+        def dev(a, dtype):
+            if a is None or isinstance(a, torch.Tensor):
+                return a
+            keep.append(self.tensor(np.ascontiguousarray(np.asarray(a), dtype=dtype)))
+            return keep[-1]
+        if isinstance(lengths_or_offsets, torch.Tensor):
+            d_s = lengths_or_offsets
+            if out is None:
+                raise ValueError("normal_fill: device offsets need the tensor to fill (out=)")
+            n, total = d_s.numel() - 1, out.numel()
+        else:
+            s_off = self.offsets(lengths_or_offsets)
+            n, total = len(s_off) - 1, int(s_off[-1])
+            d_s = dev(s_off, np.int64)
+        if out is None:
+            out = torch.empty(total, dtype=torch.float64, device=self.device)
+        elif out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != total:
+            raise ValueError("normal_fill: out must be a contiguous float64 tensor of the batch's %d samples" % total)
+        if not isinstance(params, torch.Tensor):
+            params = dev(self._c_params(params).view(np.uint8), np.uint8)
+        if params.numel() * params.element_size() != n * _lib.NOTE_PARAMS.itemsize:
+            raise ValueError("normal_fill: one parameter record per note")
+        note_on, growl_scale = dev(note_on, np.uint8), dev(growl_scale, np.float64)
+        for t, dt, what in ((note_on, torch.uint8, "note_on"), (growl_scale, torch.float64, "growl_scale")):
+            if t is not None and (t.dtype != dt or t.numel() != n):
+                raise ValueError(f"normal_fill: {what} is one {dt} per note")
+        self._check(self.lib.goofer_normal_fill(self.h, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(params), _ptr(d_s), n, total, int(tag),
+                                                _ptr(note_on), _ptr(growl_scale), _ptr(out), self._stream()))
+        self._fill_keep = keep                                  # this call's uploads, until the next call (stream order frees them safely)
+        return out
+
     def counter(self, name: str) -> int:
         """Cumulative device-side counter of the handle (goofer_counter): 'pulse_scanned_notes', 'pulse_fallback_notes'."""
         v = C.c_int64(0)

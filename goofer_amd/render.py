@@ -411,7 +411,10 @@ class SourceArena:
 
 
 class Renderer:
-    def __init__(self, ctx: Context | None = None, hop: int = S.HOP):
+    def __init__(self, ctx: Context | None = None, hop: int = S.HOP, noise="host"):
+        # where the sh / sr / sj draws come from (sampler.resolve_noise): "host", the legacy np.random stream a seeded parity
+        # run reproduces the reference with, or "device", Context.normal_fill keyed like the phases (None: $GOOFER_NOISE)
+        self.noise = S.resolve_noise(noise)
         self.ctx = ctx or default_context()
         self.hop = hop
         self.sources = SourceArena(self.ctx)
@@ -425,7 +428,8 @@ class Renderer:
         """jobs: list of (Source, Request).  Returns a list of fp32 arrays (the mix the reference writes to
         out.wav); with ``return_parts`` also a dict of device-side intermediates for tests.
         ``phi_seeds``: per-note seeds for INJECTED phases (parity with a seeded reference run); otherwise the
-        device draws phases from Philox keyed by ``seed`` and the note index."""
+        device draws phases from Philox keyed by ``seed`` and the note index.  A renderer made with ``noise="device"``
+        draws the jitter / growl normals on the device whether or not the phases are injected."""
         if not jobs:
             return []
         prep = self.prepare(jobs, phi_seeds=phi_seeds, trim_rows=not return_parts)   # tests look at the whole assembled envelope
@@ -450,6 +454,10 @@ class Renderer:
         ``split=True`` issues goofer_assemble_batch and goofer_synth_batch separately (same results)."""
         ctx = self.ctx
         par = prep["params"]
+        noise_f0, noise_vol = prep["noise_f0"], prep["noise_vol"]
+        drawn = None
+        if prep.get("device_noise") is not None:              # before the assembly (it reads f0_mul) and the synthesis are enqueued
+            noise_f0, noise_vol, drawn = self._device_noise(prep, seed)
         # Notes with the 'sg' pulse layer or the 'sr' volume jitter are synthesised by the one-kernel-per-step pipeline (those
         # layers edit the pulse train / the stems between its steps), everything else by the stem walkers — and the library
         # picks the pipeline per BATCH (synth_route_of in goofer_amd/csrc/api.hip).  So that a note renders to the same bits
@@ -458,21 +466,44 @@ class Renderer:
         slow = np.nonzero((par["subharm_weight"] > 0) | (par["vol_jitter_harm"] != 0) | (par["vol_jitter_breath"] != 0))[0]
         if 0 < slow.size < len(par):
             self.assemble(prep)
-            out = self._synth_partitioned(prep, [np.setdiff1d(np.arange(len(par)), slow), slow], seed, keep_stems)
+            out = self._synth_partitioned(prep, [np.setdiff1d(np.arange(len(par)), slow), slow], seed, keep_stems, noise_f0, noise_vol)
         else:
             if split:
                 self.assemble(prep)
             out = ctx.synth_batch(prep["env"], prep["env_lens"], prep["f0"], prep["mask"], prep["lens"], par,
                                   formants=prep["formants"], phi=prep["phi"], seed=seed, want_rec=False, want_mix=True,
-                                  offsets=prep["offsets"], noise_f0=prep["noise_f0"], noise_vol=prep["noise_vol"],
+                                  offsets=prep["offsets"], noise_f0=noise_f0, noise_vol=noise_vol,
                                   subharm=S.SUBHARM if prep["subharm"] else None,
                                   mix_only=prep["post"] is None and not keep_stems,
                                   assembly=None if split else prep["assembly"])
         if prep["post"] is not None:
             self._post_chain(prep, out, seed)
+        if drawn is not None:
+            out["_keep_noise"] = drawn                         # alive until the caller has synchronised, like the stems
         return out
 
-    def _synth_partitioned(self, prep, groups, seed, keep_stems):
+    def _device_noise(self, prep, seed):
+        """noise="device": this run's sh / sr / sj draws, made by Context.normal_fill on the current stream — each stream of a
+        note keyed by ``seed`` ^ its id like its phases, so what a note draws does not depend on the batch around it.  The
+        jitter normals go where the host's uploads go (goofer_batch.noise_f0 / noise_vol_h / noise_vol_b; the notes without
+        the flag are not written and not read: the kernels gate per note); the growl factor goes into the assembly's f0_mul,
+        1.0 for the notes without 'sj' (k_sample_assemble multiplies every sample).  Returns (noise_f0, noise_vol, tensors)."""
+        ctx, dn, o = self.ctx, prep["device_noise"], prep["offsets"]
+        total = int(o["s_off"][-1])
+
+        def fill(tag, on, out=None, growl_scale=None):
+            out = torch.empty(total, dtype=torch.float64, device=ctx.device) if out is None else out
+            return ctx.normal_fill(seed, o["d_par"], o["d_s"], tag, note_on=on, growl_scale=growl_scale, out=out)
+        noise_f0 = fill(0, dn["on_f0"]) if dn["on_f0"] is not None else None
+        noise_vol = (fill(1, dn["on_vol"]), fill(2, dn["on_vol"])) if dn["on_vol"] is not None else None
+        mul = prep["keep"].get("f0_mul") if dn["on_sj"] is not None else None
+        if mul is not None:
+            if not dn["all_sj"]:
+                mul.fill_(1.0)
+            fill(4, dn["on_sj"], growl_scale=dn["sj_scale"], out=mul)
+        return noise_f0, noise_vol, (noise_f0, noise_vol, mul)
+
+    def _synth_partitioned(self, prep, groups, seed, keep_stems, noise_f0=None, noise_vol=None):
         """goofer_synth_batch once per group of notes of an assembled batch; the stems land at the notes' places."""
         ctx = self.ctx
         so = prep["sample_off"]
@@ -484,12 +515,12 @@ class Renderer:
             sub = self._subset(prep, idxs)
             par = prep["params"][idxs].copy()
             lens, env_lens = [prep["lens"][i] for i in idxs], [prep["env_lens"][i] for i in idxs]
-            nv = prep["noise_vol"]
+            nv = noise_vol
             wants_sub = bool(np.any(par["subharm_weight"] > 0))
             wants_vol = nv is not None and bool(np.any((par["vol_jitter_harm"] != 0) | (par["vol_jitter_breath"] != 0)))
             o = ctx.synth_batch(sub["env"], env_lens, sub["f0"], sub["mask"], lens, par, formants=sub["formants"], phi=sub["phi"],
                                 seed=seed, want_rec=False, want_mix=True,
-                                noise_f0=cat(prep["noise_f0"], idxs) if bool(np.any(par["f0_jitter"] != 0)) else None,
+                                noise_f0=cat(noise_f0, idxs) if bool(np.any(par["f0_jitter"] != 0)) else None,
                                 noise_vol=(cat(nv[0], idxs), cat(nv[1], idxs)) if wants_vol else None,
                                 subharm=S.SUBHARM if (prep["subharm"] and wants_sub) else None,
                                 mix_only=prep["post"] is None and not keep_stems)
@@ -580,6 +611,8 @@ class Renderer:
         envelope frames than the note has STFT frames (every cross-faded repeat is appended again, SillySampler.py:657-672)
         and ``gf.synthesize`` cuts the envelope to ``1 + n // hop`` frames (GOOFER.py:1115-1119): the rows behind that are
         never read — a fifth of the rows of a one-second note.  ``False`` keeps them (tests that compare the whole envelope).
+        A renderer made with ``noise="device"`` draws no random number here and makes no per-sample host array for sh / sr / sj:
+        ``run`` draws them on the device, keyed by its seed.
 
         Host cost: the per-note decisions run in the library's host planner (a batch per call, csrc/planner.hip) and everything
         here is column arithmetic over the batch — no per-note Python except a handful of attribute reads."""
@@ -600,6 +633,7 @@ class Renderer:
                 del stg
 
     def _prepare(self, stg, jobs, phi_seeds, note_ids, trim_rows, device_calls=True):
+        device_noise = self.noise == "device"
         tr = getattr(self, "trace_prepare", None)              # a list: (label, perf_counter) marks of the host phases (scripts/prepare_phases.py)
         if tr is None:
             _T = lambda label: None
@@ -784,11 +818,20 @@ class Renderer:
         par["f0_jitter"], par["vol_jitter_harm"], par["vol_jitter_breath"], par["subharm_weight"] = c_f0j, c_vj, c_vj * 2, c_sub
         lens_l = lens.tolist()
         env_lens_l = env_lens.tolist()
-        # sh / sr draws come from the legacy global np.random stream, note by note, in the reference's order
-        # (f0 jitter, harmonic volume, breath volume: GOOFER.py:666, 653)
-        noise_f0 = noise_vol = None
+        noise_f0 = noise_vol = dev_noise = None
         any_f0j, any_vj = bool((c["f0_jitter"] != 0).any()), bool((c["volume_jitter"] != 0).any())
-        if any_f0j or any_vj:
+        if device_noise:
+            # run() draws them (Context.normal_fill, keyed by its seed): here only which notes take which stream — the notes
+            # host mode draws for — and the growl layer's scale, a byte / a double per note
+            on_sj = c_sj > 0.0
+            dev_noise = {"on_f0": stg.put((c["f0_jitter"] != 0).astype(np.uint8)) if any_f0j else None,
+                         "on_vol": stg.put((c["volume_jitter"] != 0).astype(np.uint8)) if any_vj else None,
+                         "on_sj": stg.put(on_sj.astype(np.uint8)) if on_sj.any() else None,
+                         "sj_scale": stg.put(np.where(on_sj, c_sj.astype(np.float64) ** 2, 0.0)) if on_sj.any() else None,
+                         "all_sj": bool(on_sj.all())}
+        elif any_f0j or any_vj:
+            # sh / sr draws come from the legacy global np.random stream, note by note, in the reference's order
+            # (f0 jitter, harmonic volume, breath volume: GOOFER.py:666, 653)
             nf, nh, nb = [], [], []
             for jf, jv, n_ in zip(c["f0_jitter"] != 0, c["volume_jitter"] != 0, lens_l):
                 nf.append(np.random.randn(n_) if jf else np.zeros(n_))
@@ -805,11 +848,15 @@ class Renderer:
         post["su_gain"], post["sj_mix"], post["sa_mix"], post["sd_strength"], post["tension"], post["pitch_dyn"] = c_su, c_sj, c_sa, c_sd, c_st, c_pd
         post["fry_a"], post["fry_b"], post["fry_fade"] = geo["fry_a"], geo["fry_b"], geo["fry_fade"]
         growl = {}
-        for i in np.nonzero(c_sj > 0.0)[0]:                    # 'sj': f0 * 0.5 * 2^N(0, mix^2), a fresh generator per call  :1063-1065
+        for i in (() if device_noise else np.nonzero(c_sj > 0.0)[0]):   # 'sj': f0 * 0.5 * 2^N(0, mix^2), a fresh generator per call  :1063-1065
             rng = np.random.default_rng(phi_seeds[i]) if phi_seeds is not None else np.random.default_rng()
             growl[int(i)] = 0.5 * (2.0 ** rng.normal(loc=0.0, scale=float(c_sj[i]) ** 2, size=lens_l[i]))
         f0_growl = None
-        if growl:
+        if device_noise and dev_noise["on_sj"] is not None:    # f0_mul is filled by run(), before the assembly that reads it
+            d["f0_mul"] = torch.empty(o_off, dtype=torch.float64, device=ctx.device)
+            f0_growl = torch.zeros(o_off, dtype=torch.float32, device=ctx.device)
+            a.f0_mul, a.f0_mul_out = d["f0_mul"].data_ptr(), f0_growl.data_ptr()
+        elif growl:
             # the layer's f0 is the fp64 pitch curve times the factor, rounded to fp32 once (SillySampler.py:1065): the
             # assembly kernel writes it next to f0 while it still holds the fp64 value
             mul = np.ones(o_off, dtype=np.float64)
@@ -836,7 +883,7 @@ class Renderer:
             torch.cuda.current_stream(ctx.device).synchronize()   # (this batch's uploads; other lanes' streams are not waited for)
         _T("ship+sync")
         return {"assembly": a, "keep": d, "env": env, "f0": f0, "mask": mask, "params": par, "lens": lens_l, "env_lens": env_lens_l,
-                "noise_f0": noise_f0, "noise_vol": noise_vol, "subharm": bool((c_sub > 0).any()),
+                "noise_f0": noise_f0, "noise_vol": noise_vol, "device_noise": dev_noise, "subharm": bool((c_sub > 0).any()),
                 "post": post if has_post else None, "growl": growl, "f0_growl": f0_growl, "bend_out": bend_out, "requests": rb, "sources": srcs, "geometry": (sr, n_fft, self.hop, frames, o_off, n),
                 "formants": d_formants, "phi": phi, "planned": pb, "offsets": offsets,
                 "sample_off": sample_off, "env_off": env_off, "frames": frames, "samples": o_off, "edit_rows": e_off}
@@ -855,7 +902,8 @@ class GooferResampler:
     envelope.  wav output uses the stdlib ``wave`` module (PCM16, what soundfile's default WAV subtype writes)."""
 
     def __init__(self, in_file, out_file, pitch, velocity, flags="", offset=0, length=1000, consonant=0, cutoff=0,
-                 volume=100, modulation=0, tempo="!120", pitch_string="AA", renderer: Renderer | None = None, seed=None, tracker=None):
+                 volume=100, modulation=0, tempo="!120", pitch_string="AA", renderer: Renderer | None = None, seed=None, tracker=None,
+                 noise=None):
         from pathlib import Path
         from . import core
         self.in_file, self.out_file = Path(in_file), Path(out_file)
@@ -864,7 +912,9 @@ class GooferResampler:
         # cached features, or — the first render of a sample — analysed now and cached (SillySampler.py:415-432): the envelope
         # half on the GPU, the f0 / formant tracks from the tracker (goofer_amd.trackers; raises when none is available)
         from . import trackers
-        self.renderer = renderer or Renderer()
+        # the noise source (the argument, else $GOOFER_NOISE: refused here, before anything is launched) of the Renderer made here;
+        # a renderer handed in brings its own
+        self.renderer = renderer or Renderer(noise=_own_noise(noise, renderer))
         feat = trackers.ensure_features(self.in_file, hop_length=self.renderer.hop, tracker=tracker, ctx=self.renderer.ctx)
         env, f0, mask, forms, sr, ylen = core.load_features(feat)
         self.source = Source.from_pack(env, f0, mask, forms, sr, ylen)
@@ -872,6 +922,15 @@ class GooferResampler:
             seed = int(np.random.SeedSequence().generate_state(1, dtype=np.uint64)[0])
         self.out = self.renderer.render([(self.source, self.request)], seed=seed)[0]
         write_wav(self.out_file, self.out, sr)
+
+
+def _own_noise(noise, renderer):
+    """``noise`` resolved (sampler.resolve_noise: None reads $GOOFER_NOISE) for a front end that makes its own Renderer; with a
+    renderer handed in the source is that renderer's, and naming another one is an error."""
+    resolved = S.resolve_noise(noise)
+    if renderer is not None and noise is not None and getattr(renderer, "noise", resolved) != resolved:
+        raise ValueError(f"noise={noise!r}, but the renderer handed in was made with noise={renderer.noise!r}")
+    return resolved
 
 
 def write_wav(path, x, sr):
@@ -917,12 +976,16 @@ class PipelinedRenderer:
     (``Request`` objects / argument lists) start a new device batch; ``RequestBatch`` objects are not merged.  First-audio
     latency grows with ``coalesce``.  The default 1 keeps a server's latency and per-batch path choice.
 
+    ``noise``: the lanes' noise source (``Renderer``); with "device" the worker threads draw nothing and a note's jitter / growl
+    draws, like its phases, follow its ``note_ids`` id wherever it is rendered.
+
     ``render_iter`` yields ``(mix, sample_off)`` per batch, in order: ``mix`` is a float32 numpy view of the lane's pinned
     buffer, valid until ``depth`` more batches have been taken from the iterator (copy what must live longer)."""
 
     def __init__(self, device: int = 0, hop: int = S.HOP, depth: int = 2, workers: int = 4, staging_bytes: int = 48 << 20,
-                 freeze_gc: bool = True, coalesce: int = 1):
+                 freeze_gc: bool = True, coalesce: int = 1, noise="host"):
         from concurrent.futures import ThreadPoolExecutor
+        self.noise = S.resolve_noise(noise)                    # every lane's noise source (Renderer)
         self.coalesce = max(1, int(coalesce))
         staging_bytes = int(staging_bytes) * self.coalesce
         self.device = torch.device("cuda", device)
@@ -935,7 +998,7 @@ class PipelinedRenderer:
         # belongs to the start of a job and not to whichever batch first finds its lane's free list empty.
         per_lane = (2 * depth + 1 + workers + depth - 1) // depth   # (depth + 1 on the device: see _render_iter)
         for _ in range(depth):
-            r = Renderer(Context(device), hop=hop)
+            r = Renderer(Context(device), hop=hop, noise=self.noise)
             if arena is None:
                 arena = r.sources
             r.sources = arena

@@ -28,6 +28,21 @@ _SEMI = {"C": 0, "C#": 1, "D": 2, "D#": 3, "E": 4, "F": 5, "F#": 6, "G": 7, "G#"
 # the resampler's fixed sub-harmonic layer settings (SillySampler.py:1027-1033)
 SUBHARM = {"semitones": 12, "vibrato": True, "rate": 75, "depth": 3, "delay": 0.01}
 
+NOISE_SOURCES = ("host", "device")
+
+
+def resolve_noise(noise=None) -> str:
+    """Where the sh / sr / sj draws of a render come from: ``"host"`` (the legacy ``np.random`` stream, note by note — what a
+    seeded run needs to reproduce the reference's draws) or ``"device"`` (the library's counter-based stream,
+    ``goofer_normal_fill``: no host draws, a note's draws are its own in any batch).  ``None`` reads ``$GOOFER_NOISE``
+    (default ``host``); anything else raises ``ValueError``."""
+    if noise is None:
+        import os
+        noise = os.environ.get("GOOFER_NOISE") or "host"
+    if noise not in NOISE_SOURCES:
+        raise ValueError(f"noise source {noise!r}: GOOFER_NOISE / noise= is one of {', '.join(NOISE_SOURCES)}")
+    return noise
+
 
 # ---------------------------------------------------------------------------------------------
 # string decode (integer path — bit-exact)

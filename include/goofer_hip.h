@@ -551,6 +551,22 @@ int goofer_post_batch(goofer_ctx *ctx, const goofer_post *post, void *stream);
  * sample across PCIe instead of four. */
 int goofer_pcm16(goofer_ctx *ctx, const float *x, int64_t n, int16_t *out, void *stream);
 
+/* Standard normal draws of the jitter / growl flags on the device (noise.hip): out[sample_off[k] + i], float64, for every note
+ * k with note_on[k] != 0 (NULL: every note); the samples of the other notes are not written.  The stream is defined:
+ * Philox-4x32 with 10 rounds, key = seed ^ (params[k].seed[0] | params[k].seed[1] << 32) (the noise phases' key), counter
+ * (i >> 1, stream_tag, 0, 0x6A09E667); the block's words w0..w3 give u1 = ((w0 | (w1 & 0x1FFFFF) << 32) + 1) * 2^-53,
+ * u2 = (w2 | (w3 & 0x1FFFFF) << 32) * 2^-53, r = sqrt(-2 ln u1), sample 2q = r cos(2 pi u2), sample 2q + 1 = r sin(2 pi u2) — a
+ * note's draws depend on its key and the tag only, not on the batch.  stream_tag: 0 f0 jitter, 1 harmonic volume jitter,
+ * 2 breath volume jitter, 3 sub-harmonic f0 jitter, 4 growl.  growl_scale ([n_notes], or NULL for the plain normals z): writes
+ * 0.5 * 2^(growl_scale[k] * z) instead (SillySampler.py:1063-1065 with scale = mix^2).  params, sample_off ([n_notes + 1], from
+ * 0 to total_samples), note_on, growl_scale and out (16-byte aligned, the caller's) are device arrays; asynchronous on
+ * `stream`; needs no plan.  GOOFER_EINVAL for a null pointer, a negative count, a tag outside 0..4 or an `out` that is not
+ * 16-byte aligned (an odd element of a float64 array).  The counter word is 32 bits wide: a note of more than 2^33 samples
+ * would repeat its stream. */
+int goofer_normal_fill(goofer_ctx *ctx, uint64_t seed, const goofer_note_params *params, const int64_t *sample_off, int n_notes,
+                       int64_t total_samples, int stream_tag, const unsigned char *note_on, const double *growl_scale, double *out,
+                       void *stream);
+
 /* ---- measurement / test hooks --------------------------------------------------------------- */
 
 /* HIP-event timing of every stage of goofer_synth_batch on the caller's stream: begin() arms up to
