@@ -15,6 +15,7 @@
 #include <hip/hip_fp16.h>
 
 #include "common.h"
+#include "launchers.h"
 
 constexpr int AN_ROWS = 4;
 

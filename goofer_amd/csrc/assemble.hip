@@ -13,6 +13,7 @@
 #include <type_traits>
 
 #include "binops_core.h"
+#include "launchers.h"
 
 constexpr int A_ROWS = 4;   // rows (waves) per workgroup
 constexpr int ES_HALO = 64; // k_env_edit: halo floats either side of the staged row (the 'es' blur has radius <= 28)
@@ -1061,20 +1062,6 @@ __global__ __launch_bounds__(256) void k_env_fry(const goofer_assembly a, int64_
 }
 
 // ---------------------------------------------------------------------------------------------
-__global__ void k_row_notes(const goofer_note_plan *__restrict__ notes, int n_notes, int64_t total_rows, int which,
-                            int *__restrict__ row_note)
-{
-    int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= total_rows) return;
-    int lo = 0, hi = n_notes;
-    while (hi - lo > 1) {
-        int mid = (lo + hi) >> 1;
-        int64_t off = which == 0 ? notes[mid].edit_off : notes[mid].env_off;
-        if (off <= r) lo = mid; else hi = mid;
-    }
-    row_note[r] = lo;
-}
-
 // both row -> note maps of an assembly (edited source rows, output rows) in one launch
 __global__ void k_row_notes2(const goofer_note_plan *__restrict__ notes, int n_notes, int64_t edit_rows, int64_t out_rows,
                              int *__restrict__ row_note_edit, int *__restrict__ row_note_out)
@@ -1096,13 +1083,14 @@ __global__ void k_row_notes2(const goofer_note_plan *__restrict__ notes, int n_n
     if (r < out_rows) row_note_out[r] = lo2;
 }
 
-int launch_assemble(goofer_ctx *ctx, const goofer_assembly *a, int *row_note_edit, int *row_note_out, void *row_recs, hipStream_t st)
+int launch_assemble(goofer_ctx *ctx, const goofer_assembly *a, int *row_note_edit, int *row_note_out, void *row_recs, render_link &link,
+                    hipStream_t st)
 {
     const int B = a->n_bins;
     // per-kernel HIP events of a profiled run (goofer_profile_begin): stage PROF_ASM0 + which, on the stream the kernel runs on
     hipEvent_t *pq = nullptr;
-    if (ctx->prof_on && ctx->prof_asm && ctx->prof_asm_steps < ctx->prof_cap && ctx->prof_asm_steps < (int)sizeof(ctx->prof_asm_mask)) {
-        pq = ctx->prof_asm + (size_t)ctx->prof_asm_steps * 6;
+    if (ctx->prof_on && ctx->prof_asm.ev && ctx->prof_asm_steps < ctx->prof_cap && ctx->prof_asm_steps < (int)sizeof(ctx->prof_asm_mask)) {
+        pq = ctx->prof_asm.step(ctx->prof_asm_steps);
         ctx->prof_asm_mask[ctx->prof_asm_steps] = 0;
     }
     auto mark = [&](int which, int edge, hipStream_t s) -> hipError_t {
@@ -1112,14 +1100,12 @@ int launch_assemble(goofer_ctx *ctx, const goofer_assembly *a, int *row_note_edi
     };
     // f0 and voicing mask first: the pulse chain of the synthesis (a long sequential walk) depends on nothing else, and
     // goofer_render_batch starts it on the side stream while the envelope kernels below are still running
-    ctx->early_f0 = nullptr;
-    ctx->f0_on_side = false;
     if (a->total_samples > 0) {
         // goofer_render_batch: the kernel goes to the side stream itself — the only consumers of f0 / mask before the frame maps
         // are the pulse walk and placement queued behind it there, and the envelope kernels below then run BESIDE it on the
         // caller's stream instead of behind it (it is 0.3 ms at the head of a 2.6 ms step).  The caller's stream waits for
         // ev_f0 where it first reads f0 / mask (goofer_synth_batch).  Not with the fry edit, which reads them here.
-        const bool on_side = ctx->early_req && ctx->ev_f0 && ctx->side && !a->any_fry;
+        const bool on_side = link.fork_early && ctx->ev_f0 && ctx->side && !a->any_fry;
         hipStream_t fst = on_side ? ctx->side : st;
         if (on_side) HIP_TRY(ctx, hipStreamWaitEvent(ctx->side, ctx->ev_entry, 0));
         constexpr int spt = 4;                                  // (8 / 16 samples per thread measured no faster)
@@ -1129,10 +1115,10 @@ int launch_assemble(goofer_ctx *ctx, const goofer_assembly *a, int *row_note_edi
         hipLaunchKernelGGL(k_sample_assemble<spt>, sgrid, dim3(256), 0, fst, *a, a->total_samples, sa_fast);
         LAUNCH_CHECK(ctx);
         HIP_TRY(ctx, mark(2, 1, fst));
-        if (ctx->early_req && ctx->ev_f0) {
+        if (link.fork_early && ctx->ev_f0) {
             HIP_TRY(ctx, hipEventRecord(ctx->ev_f0, fst));
-            ctx->early_f0 = a->f0_out;
-            ctx->f0_on_side = on_side;
+            link.f0_ready = a->f0_out;
+            link.f0_side = on_side;
         }
     }
     {
@@ -1171,12 +1157,11 @@ int launch_assemble(goofer_ctx *ctx, const goofer_assembly *a, int *row_note_edi
     }
     if (a->total_out_rows > 0) {
         const dim3 lgrid((unsigned)((a->total_out_rows + A_ROWS - 1) / A_ROWS));
-        ctx->warp_done = false;
-        const bool fused_warp = ctx->warp_out && !a->any_fry;   // (the fry edit rewrites rows afterwards: the warp then stays a pass of its own)
+        const bool fused_warp = link.warp_dst && !a->any_fry;   // (the fry edit rewrites rows afterwards: the warp then stays a pass of its own)
         const size_t lds_w = fused_warp ? sizeof(float) * 2 * A_ROWS * (B + 1) : 0;
-        const double *wf = fused_warp ? ctx->warp_formants : nullptr;
-        const goofer_note_params *wp = fused_warp ? ctx->warp_params : nullptr;
-        float *wo = fused_warp ? ctx->warp_out : nullptr;
+        const double *wf = fused_warp ? link.formants : nullptr;
+        const goofer_note_params *wp = fused_warp ? link.params : nullptr;
+        float *wo = fused_warp ? link.warp_dst : nullptr;
         env_loop_grid eg;
         eg.nt = 0;
         eg.fstep = ((double)a->sr / 2.0) / (double)(B - 1);
@@ -1196,7 +1181,7 @@ int launch_assemble(goofer_ctx *ctx, const goofer_assembly *a, int *row_note_edi
             if (chunks == 9) ENV_ROWS(true, 9);
             else if (chunks == 17) ENV_ROWS(true, 17);
             else ENV_ROWS(true, 0);
-            ctx->warp_done = true;
+            link.warped = true;
         } else {
             if (chunks == 9) ENV_ROWS(false, 9);
             else if (chunks == 17) ENV_ROWS(false, 17);

@@ -10,6 +10,7 @@
 #include <hip/hip_fp16.h>
 
 #include "binops_core.h"
+#include "launchers.h"
 
 constexpr int ROWS_PER_BLOCK = 4;   // one wave per row, 256-thread workgroups
 // the dynamic-LDS limit of kernels that also hold static LDS (warp_row's s_seg): 160 KiB less 1 KiB
@@ -335,7 +336,7 @@ __global__ __launch_bounds__(256, ITERS <= 9 ? 4 : (ITERS <= 17 ? 3 : 2)) void k
 int launch_harm_shape(goofer_ctx *ctx, float2 *S, int ldc, int64_t total_frames, const int *frame_note, const int64_t *frame_off,
                       const int64_t *sample_off, const float *f0, const float *mask, const float *env, int ld,
                       const goofer_note_params *params, float *note_mag, const int64_t *row_src, const double *formants,
-                      bool no_warp, hipStream_t st)
+                      bool no_warp, const float2 *picks, hipStream_t st)
 {
     if (total_frames <= 0) return GOOFER_OK;
     const goofer_plan_t &pl = ctx->plan;
@@ -345,7 +346,7 @@ int launch_harm_shape(goofer_ctx *ctx, float2 *S, int ldc, int64_t total_frames,
 #define HARM_SHAPE_NT(IT, NT)                                                                                                      \
     hipLaunchKernelGGL((k_harm_shape<IT, NT>), grid, dim3(256), lds, st, S, ldc, total_frames, frame_note, frame_off, sample_off, f0, \
                        mask, env, ld, params, note_mag, pl.freqs, pl.boost, pl.bright_h, pl.blur5, pl.n_bins, pl.hop, row_src,    \
-                       formants, make_warp_grid(pl.sr, pl.n_bins), ctx->frame_picks, warp_rows)
+                       formants, make_warp_grid(pl.sr, pl.n_bins), picks, warp_rows)
     // (the shaped rows are written once and read once, by the inverse transform: non-temporal stores)
 #define HARM_SHAPE(IT)                                                                                                             \
     do {                                                                                                                           \
@@ -583,7 +584,8 @@ __global__ __launch_bounds__(256, (ITERS <= 9 || RB) ? 4 : (ITERS <= 17 ? 3 : 2)
 int launch_noise_spectra(goofer_ctx *ctx, float2 *S_uv, float2 *S_br, int ldc, int64_t total_frames, const int *frame_note,
                          const int64_t *frame_off, const int64_t *sample_off, const float *f0, const float *mask,
                          const float *env_noise, const float *phi, int ld, const goofer_note_params *params, uint64_t seed,
-                         const int64_t *row_src, bool preblurred, const unsigned char *frame_skip, hipStream_t st)
+                         const int64_t *row_src, bool preblurred, const unsigned char *frame_skip, const float2 *picks,
+                         hipStream_t st)
 {
     if (total_frames <= 0) return GOOFER_OK;
     const goofer_plan_t &pl = ctx->plan;
@@ -602,7 +604,7 @@ int launch_noise_spectra(goofer_ctx *ctx, float2 *S_uv, float2 *S_br, int ldc, i
 #define NOISE_SPECTRA_LAUNCH(IT, NT, PH, RBV)                                                                                      \
     hipLaunchKernelGGL((k_noise_spectra<IT, NT, PH, RBV>), grid, dim3(256), lds, st, S_uv, S_br, ldc, total_frames, frame_note, frame_off,  \
                        sample_off, f0, mask, env_noise, phi, ld, params, seed, pl.freqs, pl.bright_b, pl.blur5, pl.n_bins, pl.hop, \
-                       row_src, preblurred ? (const double *)nullptr : pl.blur175, ctx->frame_picks, frame_skip)
+                       row_src, preblurred ? (const double *)nullptr : pl.blur175, picks, frame_skip)
 #define NOISE_SPECTRA_P(IT, NT, PH)                                                                                                \
     do {                                                                                                                           \
         if constexpr (IT == 9 || IT == 17) {                                                                                       \

@@ -6,6 +6,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <vector>
+
 #include "../../include/goofer_hip.h"
 
 #define WAVE 64
@@ -57,16 +59,39 @@ struct goofer_plan_t {
     float taps5_f[5] = {0}, taps175_f[15] = {0};   // the same taps rounded to fp32, host side (passed to kernels by value)
 };
 
+// HIP events of a profiled run (goofer_profile_begin): `per_step` for each step the pool was grown to
+struct event_pool {
+    int per_step;
+    hipEvent_t *ev = nullptr;     // null until the first goofer_profile_begin
+    int steps = 0;
+    hipEvent_t *step(int k) const { return ev + (size_t)k * per_step; }
+};
+
+// What one goofer_render_batch hands from its assembly half to its synthesis half (synth.hip).  It lives on that call's stack;
+// goofer_assemble_batch and goofer_synth_batch pass an empty one.
+struct render_link {
+    // asked of the assembly
+    bool fork_early = false;              // ev_entry is recorded: record ev_f0 behind the f0 / mask kernel, so that the pulse chain may fork there
+    float *warp_dst = nullptr;            // the frame-gather kernel also writes the rows the harmonic walker needs (formant-anchored +
+    const double *formants = nullptr;     // uniform warp) here, from these formants and note parameters
+    const goofer_note_params *params = nullptr;
+    // answered by the assembly
+    const float *f0_ready = nullptr;      // the f0 array ev_f0 stands for (null: no event recorded)
+    bool f0_side = false;                 // the f0 / mask kernel ran on the side stream, in front of the pulse chain it feeds: the caller's
+                                          // stream waits for ev_f0 before it reads f0 / mask (cleared by whoever places that wait)
+    bool warped = false;                  // warp_dst holds the warped rows of the batch
+};
+
 struct goofer_ctx {
     int device = 0;
     char err[512] = {0};
     goofer_plan_t plan;
-    // handle-owned device blocks, each grown by grow_block (api.hip)
+    // handle-owned device blocks, each grown by grow_block
     void *scratch = nullptr;
     size_t scratch_bytes = 0;
     void *asm_scratch = nullptr;  // assembly scratch: edited rows + row->note maps
     size_t asm_bytes = 0;
-    void *small = nullptr;        // small staging buffer for taps etc. (its regions: SMALL_* in api.hip)
+    void *small = nullptr;        // small staging buffer for taps etc. (its regions: SMALL_* below)
     size_t small_bytes = 0;
     // device pointers of the last synth batch's intermediates (goofer_debug_fetch; tests only)
     const void *dbg_ptr[16] = {nullptr};
@@ -79,22 +104,13 @@ struct goofer_ctx {
     hipEvent_t ev_entry = nullptr, ev_f0 = nullptr, ev_f0s = nullptr;
     int32_t *ovf_flag = nullptr;           // handle-owned device words ([1], [2]: cumulative counters, goofer_counter); [0] sticky between goofer_check calls: 1 + index (inside its batch) of a
                                            // note whose pulse onsets overflowed their slots, written with atomicMax by every pulse-chain launch
-    // goofer_render_batch, stem-split path: the assembly's frame-gather kernel also writes the rows the harmonic walker needs
-    // (formant-anchored + uniform warp), into a buffer the handle owns
-    const double *warp_formants = nullptr;
-    const goofer_note_params *warp_params = nullptr;
-    float *warp_out = nullptr;            // non-null for the duration of one goofer_render_batch that wants the fused warp
-    bool warp_done = false;               // the assembly wrote warp_rows for the batch being synthesised
+    // goofer_render_batch, stem-split path: the buffer the assembly's frame-gather kernel writes the harmonic walker's warped rows
+    // to (render_link::warp_dst)
     float *warp_rows = nullptr;
     size_t warp_rows_bytes = 0;
-    const float2 *frame_picks = nullptr;   // per-frame (f0, mask) picks of the running goofer_synth_batch, or null
-    bool early_req = false;           // set for the duration of one goofer_render_batch
-    const float *early_f0 = nullptr;  // f0 array ev_f0 stands for (null: no event recorded)
-    bool f0_on_side = false;          // goofer_render_batch ran the f0 / mask kernel on the side stream, in front of the pulse chain it feeds: the
-                                      // caller's stream waits for ev_f0 before it reads f0 / mask
-    hipEvent_t *prof_side = nullptr;    // [prof_cap][4]: boundaries of the pulse chain on the side stream
-    hipEvent_t *prof_main2 = nullptr;   // [prof_cap][2]: ends of noise_spectra / mask_short when they run beside it
-    hipEvent_t *prof_asm = nullptr;     // [prof_cap][3][2]: the assembly's three large kernels, each on its own stream
+    event_pool prof_side{4};            // boundaries of the pulse chain on the side stream
+    event_pool prof_main2{2};           // ends of noise_spectra / mask_short when they run beside it
+    event_pool prof_asm{6};             // [3][2]: the assembly's three large kernels, each on its own stream
     unsigned char prof_asm_mask[4096] = {0};   // which of the three pairs assembly k of the profiled run recorded
     int prof_asm_steps = 0;
     bool prof_side_used = false;
@@ -122,7 +138,7 @@ struct goofer_ctx {
     bool prof_on = false;
     int prof_only = -1;           // >= 0: goofer_profile_begin .. end bracket this stage only (option "prof_only")
     int prof_steps = 0, prof_cap = 0;
-    hipEvent_t *prof_ev = nullptr;      // [prof_cap][PROF_STAGES + 1]
+    event_pool prof_ev{PROF_STAGES + 1};   // stage s of a step runs from event s to event s + 1
     double *mask_taps = nullptr;  // device taps of the voicing-mask smoother, cached per sigma
     size_t mask_taps_bytes = 0;
     float mask_taps_sigma = -1.f;
@@ -131,6 +147,9 @@ struct goofer_ctx {
 };
 
 int goofer_fail(goofer_ctx *ctx, int code, const char *fmt, ...);
+#define NEED_PLAN(ctx)                                                                    \
+    if (!(ctx)) return GOOFER_EINVAL;                                                     \
+    if (!(ctx)->plan.n_fft) return goofer_fail((ctx), GOOFER_ENOPLAN, "goofer_plan first")
 // float2 slots per row of a [frames x bins] complex spectrum matrix: n_bins rounded up to 16 (128-byte aligned rows, so that
 // the framewise rFFT's 16-byte stores and every row-wise reader start on a cache-line boundary)
 static inline int spec_stride(int n_bins) { return (n_bins + 15) & ~15; }
@@ -188,6 +207,43 @@ int caller_scratch(goofer_ctx *ctx, void *scratch, int64_t *scratch_bytes, const
     carve(a);
     return GOOFER_OK;
 }
+
+// grow a handle-owned device block (*p, *bytes) to `need` bytes (api.hip)
+int grow_block(goofer_ctx *ctx, void **p, size_t *bytes, size_t need, const char *what);
+
+// carve(arena &) once counting, grow a handle block to what it took (+ 4 KiB behind the last piece), then carve once over it
+template <typename Carve> int carve_block(goofer_ctx *ctx, void **block, size_t *bytes, const char *what, Carve &&carve)
+{
+    arena count{nullptr, 0};
+    carve(count);
+    if (int rc = grow_block(ctx, block, bytes, count.used + 4096, what)) return rc;
+    arena a{(char *)*block, 0};
+    carve(a);
+    return GOOFER_OK;
+}
+template <typename Carve> int carve_scratch(goofer_ctx *ctx, Carve &&carve)
+{
+    return carve_block(ctx, &ctx->scratch, &ctx->scratch_bytes, "scratch", carve);
+}
+
+// The handle's small block (ctx->small): host tables a call uploads for its own kernels.  Its regions, by byte offset:
+constexpr size_t SMALL_TABLES = 0;       // [0, 32 KiB): taps of goofer_gauss_bins / _gauss_bins_f64; the lerp tables of
+                                         // goofer_knot_decode / _knot_fit_error (12 bytes per bin)
+constexpr size_t SMALL_WORDS = 32768;    // [32 KiB, 64 KiB): goofer_warp_bins' f_shift (4 doubles), goofer_knot_fit_error's error word
+constexpr size_t SMALL_FIXED = 65536;    // tables and words: what their users grow the block to at least
+constexpr size_t SMALL_JIT = 65536;      // three jitter tap slots of JIT_SLOT_BYTES (upload_jitter_taps)
+constexpr size_t JIT_SLOT_BYTES = 131072;
+constexpr size_t SMALL_RAGGED = SMALL_JIT + 3 * JIT_SLOT_BYTES;   // goofer_gauss_rows_f64's taps, any radius
+// Overlaps: goofer_gauss_bins / _gauss_bins_f64 accept radius 4096, 65 544 bytes of taps from byte 0: through the words and
+// 8 bytes into jitter slot 0.  goofer_smooth_mask_ds uses [0, its size) as one piece (taps, decimated mask, per-note steps),
+// across every region.  Each use is in stream order, which is what keeps the overlaps harmless.
+
+// host helpers of api.hip that synth.hip and post.hip use as well: normalised taps of a Gaussian of radius int(4 sigma + 0.5), fp64
+void gauss_taps_host(double sigma, std::vector<double> &taps, int &radius);
+// taps of a sample-axis Gaussian, uploaded into jitter slot `slot` of the small block (api.hip)
+int upload_jitter_taps(goofer_ctx *ctx, double sigma, int slot, const double **d_taps, int *radius, hipStream_t st);
+
+static const size_t ONSET_BYTES = 24;    // bytes per onset slot (onset_t, pulse.hip)
 
 // ---- device helpers ------------------------------------------------------------------------
 
@@ -312,10 +368,3 @@ __device__ __forceinline__ void atomic_max_pos(float *addr, float v)
 {
     atomicMax(reinterpret_cast<unsigned int *>(addr), __float_as_uint(v));
 }
-
-// ---- kernel launchers implemented in the .hip files ---------------------------------------
-int launch_rfft_frames(goofer_ctx *ctx, const float *x, const int64_t *sample_off, const int64_t *frame_off,
-                       int n_notes, int64_t total_frames, float2 *S, int ldc, hipStream_t st);
-int launch_irfft_frames(goofer_ctx *ctx, const float2 *S, int ldc, int64_t total_frames, float *frames, hipStream_t st);
-int launch_ola_gather(goofer_ctx *ctx, const float *frames, const int64_t *sample_off, const int64_t *frame_off,
-                      int n_notes, int64_t total_samples, float *y, const float *scale_per_note, hipStream_t st);

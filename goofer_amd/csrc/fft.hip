@@ -18,6 +18,7 @@
 // of their own around the same stages: k_rfft_frames, the hot one (two frames in flight), and k_irfft_frames (its input stage
 // in place).  No MFMA: ~5 flop/B, HBM-bound.
 #include "fft_core.h"
+#include "launchers.h"
 
 struct frame_tables {
     const float2 *tw;                     // exp(-2 pi i k / N) of the owner's N-point transform (LDS)

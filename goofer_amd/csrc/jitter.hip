@@ -12,6 +12,7 @@
 // without the flag, so either source leaves those ranges as it likes;
 // each wave stages its window in LDS so every input sample is fetched once per 64 outputs.
 #include "common.h"
+#include "launchers.h"
 
 
 // The taps are consumed GS_CHUNK at a time: a chunk of taps and the 256 + GS_CHUNK window values it meets are staged in LDS,

@@ -16,6 +16,7 @@
 // concatenated array (note offsets are arbitrary: a note that starts on an odd index has its pairs straddle the
 // alignment and takes two 8-byte stores, and its first / last odd sample are single stores).
 #include "binops_core.h"
+#include "launchers.h"
 
 #define NORMAL_C3 0x6A09E667u
 #define NF_THREADS 256

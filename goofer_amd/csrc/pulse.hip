@@ -12,6 +12,7 @@
 //                   reference's `pulse[j] += cache[k]`
 // Shapes are evaluated on the fly in fp64 (numba's typing) and normalised by a per-T0 peak table.
 #include "common.h"
+#include "launchers.h"
 
 #define PT_PI 3.141592653589793
 
@@ -845,15 +846,6 @@ __global__ __launch_bounds__(256) void k_pulse_place(const onset_t *__restrict__
         }
         pulse[g] = acc;
     }
-}
-
-int launch_phase_inc(goofer_ctx *ctx, const float *f0, float f0_scale, int64_t total_samples, double *inc, hipStream_t st)
-{
-    if (total_samples <= 0) return GOOFER_OK;
-    hipLaunchKernelGGL(k_phase_inc, dim3((unsigned)((total_samples + 255) / 256)), dim3(256), 0, st, f0, total_samples,
-                       (double)ctx->plan.sr, f0_scale, inc);
-    LAUNCH_CHECK(ctx);
-    return GOOFER_OK;
 }
 
 // tiles != nullptr (16-byte aligned, 4 ints per tile of 256 * PP_SPT samples of total_samples): also the pulse placement's tile table

@@ -2,6 +2,7 @@
 // cols = 1) to R_out rows on normalised coordinates — np.interp(linspace(0, 1, R_out), linspace(0, 1, R_in), column),
 // evaluated in fp64 like numpy and rounded to fp32.  Used by gf.synthesize's optional time stretch (GOOFER.py:1019-1067).
 #include "common.h"
+#include "launchers.h"
 
 // np.linspace(0, 1, n)[i]
 __device__ __forceinline__ double lin01(int64_t i, int64_t n, double step)

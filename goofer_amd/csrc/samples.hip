@@ -1,13 +1,14 @@
 // Per-sample kernels for gfx950: voicing-mask smoothing, stem gains, peak normalisation, V/B/U mix.
 //
 //   k_mask_short   mask[::4] -> Gaussian sigma/4 (fp64)              GOOFER.py:556-562 (smooth_mask_ds)
-//   k_stem_gains   lerp-upsample the smoothed mask, scale the three stems, per-note peak
+//   k_ola3_gains   overlap-add, lerp-upsample the smoothed mask, scale the three stems, per-note peak
 //                                                                    GOOFER.py:563-567, 1179-1193, 1210
 //   k_apply_gain   gain = (1/peak)^normalize, reconstruct, V/B/U mix GOOFER.py:1208-1218, SillySampler.py:1142-1151
 #include <type_traits>
 #include "fft_core.h"
 
 #include "samples_core.h"
+#include "launchers.h"
 
 // A workgroup owns MS_TILE consecutive short samples of the concatenated axis.  For every note that tile touches (one,
 // almost always) it parks the decimated mask values of the segment plus 2*radius in LDS — each fetched once instead of
@@ -105,73 +106,12 @@ __global__ void k_note_steps(const int64_t *__restrict__ sample_off, int n_notes
     steps[2 * note + 1] = ns > 1 ? 1.0 / (double)(ns - 1) : 0.0;
 }
 
-// In place on the three OLA outputs: harm already divided by the per-note spectrum max.
-// Each thread owns 4 consecutive samples (16-byte loads/stores, four independent interpolations in
-// flight); a block of 256 threads covers 1024 samples and issues ONE atomic when it lies in one note.
+// The per-sample kernels below: each thread owns SPT consecutive samples (16-byte loads / stores); a block of 256 threads
+// covers 1024 samples.
 #define SPT 4
 
-__global__ __launch_bounds__(256) void k_stem_gains(float *__restrict__ harm, float *__restrict__ uv, float *__restrict__ bre,
-                                                    const double *__restrict__ short_s, const int64_t *__restrict__ sample_off,
-                                                    int n_notes, int64_t total_samples,
-                                                    const goofer_note_params *__restrict__ params, float *__restrict__ note_peak,
-                                                    const double *__restrict__ steps)
-{
-    __shared__ int s_pair[2];
-    __shared__ float s_red[4];
-    const int64_t g0 = (int64_t)blockIdx.x * (blockDim.x * SPT);
-    int lo, hi;
-    {
-        int64_t gl = g0 + (int64_t)blockDim.x * SPT - 1;
-        if (gl > total_samples - 1) gl = total_samples - 1;
-        block_note_range_last(sample_off, n_notes, g0, gl, s_pair, lo, hi);
-    }
-    const int64_t g = g0 + (int64_t)threadIdx.x * SPT;
-
-    auto one = [&](int note, int64_t gi, float h, float u_in, float b_in, float &u_out, float &b_out) -> float {
-        const int64_t base = sample_off[note], n = sample_off[note + 1] - base;
-        const int64_t ns = (n + MASK_DS - 1) / MASK_DS;
-        const float ms = smooth_mask_at(short_s + short_base(sample_off, note), ns, gi - base, n, steps[2 * note], steps[2 * note + 1]);
-        b_out = (b_in * ms) * params[note].breath_strength;
-        u_out = (u_in * (1.0f - ms)) * params[note].uv_strength;
-        return fabsf((h + u_out) + b_out);
-    };
-
-    if (lo == hi && g + SPT <= total_samples) {
-        const float4 h4 = *reinterpret_cast<const float4 *>(harm + g);
-        const float4 u4 = *reinterpret_cast<const float4 *>(uv + g);
-        const float4 b4 = *reinterpret_cast<const float4 *>(bre + g);
-        float4 uo, bo;
-        float pk = one(lo, g, h4.x, u4.x, b4.x, uo.x, bo.x);
-        pk = fmaxf(pk, one(lo, g + 1, h4.y, u4.y, b4.y, uo.y, bo.y));
-        pk = fmaxf(pk, one(lo, g + 2, h4.z, u4.z, b4.z, uo.z, bo.z));
-        pk = fmaxf(pk, one(lo, g + 3, h4.w, u4.w, b4.w, uo.w, bo.w));
-        *reinterpret_cast<float4 *>(uv + g) = uo;
-        *reinterpret_cast<float4 *>(bre + g) = bo;
-        pk = wave_max(pk);
-        if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = pk;
-    } else {
-        float pk_lo = 0.f;
-        for (int k = 0; k < SPT; ++k) {
-            const int64_t gi = g + k;
-            if (gi >= total_samples) break;
-            int note = lo;
-            while (sample_off[note + 1] <= gi) ++note;
-            float uo, bo;
-            const float pk = one(note, gi, harm[gi], uv[gi], bre[gi], uo, bo);
-            uv[gi] = uo;
-            bre[gi] = bo;
-            if (lo == hi) pk_lo = fmaxf(pk_lo, pk); else atomic_max_pos(note_peak + note, pk);
-        }
-        pk_lo = wave_max(pk_lo);
-        if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = pk_lo;
-    }
-    __syncthreads();
-    if (lo == hi && threadIdx.x == 0)
-        atomic_max_pos(note_peak + lo, fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3])));
-}
-
 // Overlap-add of the three stems + mask upsample + stem gains + per-note peak in ONE pass over the samples
-// (k_ola_gather x3 + k_stem_gains): each output sample gathers its covering windowed frames of the three
+// (k_ola_gather x3 + a gain pass): each output sample gathers its covering windowed frames of the three
 // stems in ascending frame order (the reference's fp32 accumulation order), normalises by the summed
 // squared window, then applies the gains.  Saves one full write + read of the three stems.
 __global__ __launch_bounds__(256) void k_ola3_gains(const float *__restrict__ fr_h, const float *__restrict__ fr_u,
@@ -1028,14 +968,6 @@ int launch_mask_upsample(goofer_ctx *ctx, const double *short_s, const int64_t *
     return GOOFER_OK;
 }
 
-int launch_note_steps(goofer_ctx *ctx, const int64_t *sample_off, int n_notes, double *steps, hipStream_t st)
-{
-    if (n_notes <= 0) return GOOFER_OK;
-    hipLaunchKernelGGL(k_note_steps, dim3((n_notes + 255) / 256), dim3(256), 0, st, sample_off, n_notes, steps);
-    LAUNCH_CHECK(ctx);
-    return GOOFER_OK;
-}
-
 int launch_irfft_ola3(goofer_ctx *ctx, const float2 *S_h, const float2 *S_u, const float2 *S_b, int ldc, int64_t total_frames,
                       const int *frame_note, const int64_t *frame_off, const int64_t *sample_off, int n_notes, const float *note_mag,
                       const double *short_s, double *steps, const goofer_note_params *params, float *harm, float *uv, float *bre,
@@ -1155,19 +1087,6 @@ int launch_mask_short(goofer_ctx *ctx, const float *mask, const int64_t *sample_
     hipLaunchKernelGGL(k_mask_short, dim3((unsigned)((total_short + MS_TILE - 1) / MS_TILE)), dim3(256),
                        sizeof(double) * (2 * radius + 1) + sizeof(float) * 4 * MS_MAXWIN, st, mask, sample_off, n_notes, total_short,
                        d_taps, radius, short_s, tap_sum);
-    LAUNCH_CHECK(ctx);
-    return GOOFER_OK;
-}
-
-int launch_stem_gains(goofer_ctx *ctx, float *harm, float *uv, float *bre, const double *short_s, const int64_t *sample_off,
-                      int n_notes, int64_t total_samples, const goofer_note_params *params, float *note_peak, double *steps,
-                      hipStream_t st)
-{
-    if (total_samples <= 0) return GOOFER_OK;
-    hipLaunchKernelGGL(k_note_steps, dim3((n_notes + 255) / 256), dim3(256), 0, st, sample_off, n_notes, steps);
-    LAUNCH_CHECK(ctx);
-    hipLaunchKernelGGL(k_stem_gains, dim3((unsigned)((total_samples + 1023) / 1024)), dim3(256), 0, st, harm, uv, bre, short_s,
-                       sample_off, n_notes, total_samples, params, note_peak, steps);
     LAUNCH_CHECK(ctx);
     return GOOFER_OK;
 }

@@ -25,6 +25,7 @@
 #include "fft_core.h"
 #include "samples_core.h"
 #include "stems_core.h"
+#include "launchers.h"
 
 
 // The two sigmas are constants of the reference (gaussian_filter1d(env, 1.75), GOOFER.py:993; sigma = 0.5, :1143 / :1171), so

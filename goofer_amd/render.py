@@ -460,7 +460,7 @@ class Renderer:
             noise_f0, noise_vol, drawn = self._device_noise(prep, seed)
         # Notes with the 'sg' pulse layer or the 'sr' volume jitter are synthesised by the one-kernel-per-step pipeline (those
         # layers edit the pulse train / the stems between its steps), everything else by the stem walkers — and the library
-        # picks the pipeline per BATCH (synth_route_of in goofer_amd/csrc/api.hip).  So that a note renders to the same bits
+        # picks the pipeline per BATCH (synth_route_of in goofer_amd/csrc/synth.hip).  So that a note renders to the same bits
         # whatever company it keeps (the two pipelines agree to fp32 rounding, not to the bit: the walkers fold the voiced
         # frames' bin blur into the synthesis window), a mixed batch is synthesised as two: one per pipeline.
         slow = np.nonzero((par["subharm_weight"] > 0) | (par["vol_jitter_harm"] != 0) | (par["vol_jitter_breath"] != 0))[0]
