@@ -624,7 +624,7 @@ int goofer_pulse_train(goofer_ctx *ctx, const float *f0, const int64_t *sample_o
 {
     NEED_PLAN(ctx);
     hipStream_t st = (hipStream_t)stream;
-    const size_t slots = (size_t)(total_samples / 2) + 16 * (size_t)n_notes + 16;   // n / 2 + 16 per note: an f0 above sr / 2 is refused
+    const size_t slots = onset_slots(total_samples, n_notes, false);
     double *inc;
     onset_t *onsets;
     int32_t *oidx, *cnt;

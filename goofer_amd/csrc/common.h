@@ -244,6 +244,18 @@ void gauss_taps_host(double sigma, std::vector<double> &taps, int &radius);
 int upload_jitter_taps(goofer_ctx *ctx, double sigma, int slot, const double **d_taps, int *radius, hipStream_t st);
 
 static const size_t ONSET_BYTES = 24;    // bytes per onset slot (onset_t, pulse.hip)
+// Onset slots (the onset index list and the onset_t list share the layout): n / 2 + 16 per note for the pulse train (an f0 above
+// sr / 2 is refused) — n + 16 with the sub-harmonic layer, whose tracker fires at most once per sample and does so on every sample
+// once its increment passes 1 (the resampler's vibrato depth of 3 takes the layer to 8 x f0: above sr / 2 from F7 on).
+// base = sample_off[note]; a pulse-train note's slots end where the next note's begin.
+__host__ __device__ __forceinline__ int64_t pulse_slot_base(int64_t base, int note) { return base / 2 + 16 * (int64_t)note; }
+__host__ __device__ __forceinline__ int64_t sub_slot_base(int64_t base, int note) { return base + 16 * (int64_t)note; }
+__host__ __device__ __forceinline__ int32_t pulse_slot_cap(const int64_t *sample_off, int note)
+{
+    return (int32_t)(pulse_slot_base(sample_off[note + 1], note + 1) - pulse_slot_base(sample_off[note], note));
+}
+// slots of a batch of n notes, N samples in all (+ 16 behind the last note)
+static inline size_t onset_slots(int64_t N, int n, bool sub_on) { return (size_t)(sub_on ? N : N / 2) + 16 * (size_t)n + 16; }
 
 // ---- device helpers ------------------------------------------------------------------------
 

@@ -3,9 +3,10 @@
 // The onset positions are a discontinuous function of a strictly sequential fp64 sum
 // (`total_phase += f0[i]/sr`, GOOFER.py:491-493): re-associating it moves onsets by a sample
 // (SURVEY.md §7.3-1).  So the work is split three ways:
-//   (k_phase_inc    inc[i] = (double)f0[i] / sr as a pass of its own: the sub-harmonic layer's tracker still uses one)
-//   k_pulse_onsets_scan  one WAVE per note walks its increments in order (nothing but the dependent fp64 adds) and
-//                   extracts the onset samples from the partial sums chunk by chunk, in parallel; k_onset_finish
+//   k_pulse_onsets_par   a workgroup per note takes the onset samples from a parallel scan of the increments f0[i] / sr
+//                   wherever that provably gives the walk's integers; a note it cannot settle is walked in order by one
+//                   WAVE (onset_walk: nothing but the dependent fp64 adds, the onsets extracted from the partial sums
+//                   chunk by chunk, in parallel); k_pulse_onsets_scan walks every note (pulse_scan = 0).  k_onset_finish
 //                   completes the onset list (sample, T0, period, running max of sample+T0)
 //   k_pulse_place   fully parallel gather: every output sample sums, in ascending onset order, the
 //                   LF shapes that cover it — no atomics, same fp32 accumulation order as the
@@ -91,6 +92,8 @@ int launch_pulse_shape_table(goofer_ctx *ctx, float *tab, const float *peak, dou
     return GOOFER_OK;
 }
 
+// inc[i] = (double)(f0[i] * scale) / sr as a pass of its own.  No launcher calls it any more (the pulse train's walk forms its
+// increments in its fetch stage, the sub-harmonic layer's come from k_subharm_inc); the benchmark's stage map still names it.
 __global__ __launch_bounds__(256) void k_phase_inc(const float *__restrict__ f0, int64_t n, double sr, float scale,
                                                    double *__restrict__ inc)
 {
@@ -106,6 +109,7 @@ struct onset_t {
     double T;         // period used for the shape
 };
 
+// ---- what the trackers share -----------------------------------------------------------------
 // One wave per note.  The walk itself is wave-uniform (every lane carries the same phase), which lets
 // the memory side be fully parallel: the wave fetches 512-sample chunks of increments with coalesced
 // vector loads (next chunk prefetched into registers while the current one is walked), parks them in
@@ -115,11 +119,75 @@ struct onset_t {
 // bit-exact.  Zero padding of the last chunk adds +0.0, which leaves the phase unchanged.
 #define OC 512   // samples per chunk (64 lanes x 8)
 #define OB 16    // samples per walk block
+constexpr int SPL = OC / WAVE;   // samples of a chunk per lane
 
 // Placement: a workgroup is 4 waves = 4 notes (one per SIMD of a CU), and the launcher pads the
 // dynamic LDS request so that only ceil(blocks/256) workgroups fit on a CU — otherwise the dispatcher
-// packs many of these latency-bound waves onto a few CUs and they time-slice one SIMD.
-//
+// packs many of these latency-bound waves onto a few CUs and they time-slice one SIMD.  `clamp` (0: none) caps the
+// request: 81 KiB means two of these cannot share a CU while 79 KiB stay free for the kernel running beside the walk.
+static size_t walk_lds_request(int blocks, size_t need, size_t clamp)
+{
+    const int per_cu = (blocks + 255) / 256;                  // MI355X: 256 CUs, 160 KiB LDS each
+    size_t lds = (size_t)(160 * 1024) / per_cu;
+    if (clamp && lds > clamp) lds = clamp;
+    lds = lds / 1024 * 1024;
+    return lds < need ? need : lds;
+}
+
+// This lane's SPL samples of the chunk that starts at sample c0 of a note of n samples at `a`; behind the note: zero.
+// NOTE the branch is wave-uniform on purpose: a per-lane if/else writing the same registers makes
+// the compiler drain vmcnt(0) between the two arms, i.e. right after issuing the prefetch.
+template <typename T>
+__device__ __forceinline__ void fetch_chunk(T (&r)[SPL], const T *__restrict__ a, int64_t c0, int64_t n, int lane)
+{
+    const int64_t s = c0 + (int64_t)lane * SPL;
+    if (c0 + OC <= n) {
+#pragma unroll
+        for (int k = 0; k < SPL; ++k) r[k] = a[s + k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < SPL; ++k) {
+            const int64_t i = s + k;
+            const T v = n > 0 ? a[i < n ? i : n - 1] : T(0);
+            r[k] = i < n ? v : T(0);                          // + 0.0: the padding leaves the phase alone
+        }
+    }
+}
+
+// The pulse train's increment f0[i] / sr (GOOFER.py:491), formed in the parallel fetch stage instead of by a pass of its own
+// that writes 8 bytes per sample and reads them back.  With rsr = RN(1 / sr) the quotient correction q + fma(-q, sr, x) rsr is
+// the correctly rounded x / sr (Markstein), i.e. the increment the reference divides out.
+__device__ __forceinline__ double inc_of(float f, double sr, double rsr)
+{
+    const double x = (double)f, q = x * rsr;
+    return fma(fma(-q, sr, x), rsr, q);
+}
+
+// The walk blocks 0 .. blocks - 1 of the chunk t (LDS) in order, on two ping-ponged register sets: the LDS broadcasts of block
+// g + 1 are in flight during block g's adds.  Blocks go in pairs.  A load behind the last block re-reads the last one; whether
+// the second block of the last pair is walked is the caller's: pad_odd = true walks it always (the caller has rounded `blocks` up
+// to even and the block holds +0.0), false skips a block that is not there.
+template <typename Walk>
+__device__ __forceinline__ void walk_blocks(const double *t, int blocks, bool pad_odd, Walk &&walk)
+{
+    auto load = [&](double (&x)[OB], int g) {
+        const double *q = t + (g < blocks ? g : blocks - 1) * OB;
+#pragma unroll
+        for (int k = 0; k < OB; ++k) x[k] = q[k];
+    };
+    double xa[OB], xb[OB];
+    load(xa, 0);
+#pragma unroll 1
+    for (int g = 0; g < blocks; g += 2) {
+        load(xb, g + 1);
+        __builtin_amdgcn_sched_barrier(0);
+        walk(xa, g);
+        load(xa, g + 2);
+        __builtin_amdgcn_sched_barrier(0);
+        if (pad_odd || g + 1 < blocks) walk(xb, g + 1);
+    }
+}
+
 // k_pulse_onsets_wrap is the sub-harmonic layer's tracker (GOOFER.py:693-696): an event fires when the phase reaches 1
 // and the phase then drops by 1.0, so the events feed back into the chain.  Increments are >= 0 in practice, so a
 // block of 16 can only hold an event if its last partial sum reaches 1; only then (or when the chunk holds a negative
@@ -143,11 +211,9 @@ __global__ __launch_bounds__(256) void k_pulse_onsets_wrap(const double *__restr
     double (*tile)[OC] = reinterpret_cast<double (*)[OC]>(smem) + 2 * wv;
     const int64_t base = sample_off[note];
     const int64_t n = sample_off[note + 1] - base;
-    // a slot per sample (+ 16): the tracker fires at most once per sample — and on every sample once the increment passes 1
-    const int64_t obase = base + 16 * (int64_t)note;
-    const int32_t cap = (int32_t)(n + 16);
+    const int32_t cap = (int32_t)(n + 16);                    // a slot per sample (+ 16): see onset_slots
     const double *__restrict__ a = inc + base;
-    int32_t *__restrict__ out = onset_idx + obase;
+    int32_t *__restrict__ out = onset_idx + sub_slot_base(base, note);
     double phase = 0.0;
     int32_t cnt = 0;
     // Event samples are parked in a 64-entry LDS queue and written out once per chunk as one coalesced store, issued
@@ -161,6 +227,8 @@ __global__ __launch_bounds__(256) void k_pulse_onsets_wrap(const double *__restr
         pend = 0;
     };
     auto push = [&](int32_t idx) {
+        if (idx >= (int32_t)n) return;                        // the +0.0 padding behind the note: a phase that an increment above 1
+                                                              // has carried past 1 "fires" there as well
         if (lane == 0) queue[pend] = idx;
         ++pend;
         ++cnt;
@@ -170,41 +238,26 @@ __global__ __launch_bounds__(256) void k_pulse_onsets_wrap(const double *__restr
         }
     };
 
-    double r[8];
-    // NOTE the branch is wave-uniform on purpose: a per-lane if/else writing the same registers makes
-    // the compiler drain vmcnt(0) between the two arms, i.e. right after issuing the prefetch.
-    auto fetch = [&](int64_t c0) {
-        const int64_t s = c0 + (int64_t)lane * 8;
-        if (c0 + OC <= n) {
-#pragma unroll
-            for (int k = 0; k < 8; ++k) r[k] = a[s + k];
-        } else {
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const int64_t i = s + k;
-                const double v = a[i < n ? i : n - 1];
-                r[k] = i < n ? v : 0.0;
-            }
-        }
-    };
-    fetch(0);
+    double r[SPL];
+    fetch_chunk(r, a, 0, n, lane);
     int buf = 0;
     for (int64_t c0 = 0; c0 < n; c0 += OC, buf ^= 1) {
         double *t = tile[buf];
         bool r_neg = false;
 #pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            t[lane * 8 + k] = r[k];
+        for (int k = 0; k < SPL; ++k) {
+            t[lane * SPL + k] = r[k];
             r_neg |= r[k] < 0.0;
         }
         const bool chunk_neg = __any(r_neg);
         wave_lds_sync();
-        if (c0 + OC < n) fetch(c0 + OC);                    // in flight during the walk below
+        if (c0 + OC < n) fetch_chunk(r, a, c0 + OC, n, lane);   // in flight during the walk below
         flush();                                            // the previous chunk's onsets
         const int64_t left = n - c0;
         const int blocks = left >= OC ? OC / OB : (int)((left + OB - 1) / OB);
-        // one walk block from registers: chain, group test, rare per-sample checks
-        auto walk = [&](const double (&x)[OB], int g) {
+        // one walk block from registers: chain, group test, rare per-sample checks.  No padded block here: a block walked twice
+        // could fire its events twice.
+        walk_blocks(t, blocks, false, [&](const double (&x)[OB], int g) {
             double ps[OB];
             ps[0] = phase + x[0];
 #pragma unroll
@@ -224,24 +277,7 @@ __global__ __launch_bounds__(256) void k_pulse_onsets_wrap(const double *__restr
             } else {
                 phase = ps[OB - 1];
             }
-        };
-        auto load = [&](double (&x)[OB], int g) {
-            const double *q = t + (g < blocks ? g : blocks - 1) * OB;
-#pragma unroll
-            for (int k = 0; k < OB; ++k) x[k] = q[k];
-        };
-        // ping-pong two register sets: the LDS broadcasts of block g+1 are in flight during block g's adds
-        double xa[OB], xb[OB];
-        load(xa, 0);
-#pragma unroll 1
-        for (int g = 0; g < blocks; g += 2) {
-            load(xb, g + 1);
-            __builtin_amdgcn_sched_barrier(0);
-            walk(xa, g);
-            load(xa, g + 2);
-            __builtin_amdgcn_sched_barrier(0);
-            if (g + 1 < blocks) walk(xb, g + 1);
-        }
+        });
     }
     wave_lds_sync();
     flush();
@@ -264,91 +300,62 @@ __device__ __forceinline__ int32_t wave_scan_incl(int32_t x, Op op)
     x = op(x, __builtin_amdgcn_update_dpp(0, x, 0x143, 0xc, 0xf, false));   // row_bcast:31 -> rows 2, 3
     return x;
 }
-
-// The same scan inside segments of LPN consecutive lanes (16: one DPP row, 32: two rows, 64: the wave): the row-broadcast
-// steps that would carry a segment's total into the next one are left out.
-template <int LPN, typename Op>
-__device__ __forceinline__ int32_t note_scan_incl(int32_t x, Op op)
+__device__ __forceinline__ int32_t wave_scan_max(int32_t x)
 {
-    x = op(x, __builtin_amdgcn_update_dpp(0, x, 0x111, 0xf, 0xf, false));   // row_shr:1
-    x = op(x, __builtin_amdgcn_update_dpp(0, x, 0x112, 0xf, 0xf, false));   // row_shr:2
-    x = op(x, __builtin_amdgcn_update_dpp(0, x, 0x114, 0xf, 0xf, false));   // row_shr:4
-    x = op(x, __builtin_amdgcn_update_dpp(0, x, 0x118, 0xf, 0xf, false));   // row_shr:8
-    if (LPN >= 32) x = op(x, __builtin_amdgcn_update_dpp(0, x, 0x142, 0xa, 0xf, false));   // row_bcast:15 -> rows 1, 3
-    if (LPN >= 64) x = op(x, __builtin_amdgcn_update_dpp(0, x, 0x143, 0xc, 0xf, false));   // row_bcast:31 -> rows 2, 3
-    return x;
+    return wave_scan_incl(x, [](int32_t p, int32_t q) { return max(p, q); });
+}
+
+// The onsets of a wave's OC samples, from floors to slots.  After sample i the reference has recorded
+// R_i = max(R_{i-1}, floor(phase_i)) onsets (GOOFER.py:487-493: its `while phase >= next_k` loop, next_k = R + 1), so onset
+// number k + 1 lies at the first sample whose R reaches k + 1, and its slot is k.  m[k] = the running max of the floors of this
+// lane's samples up to its k-th, run = m[SPL - 1], upto = wave_scan_max(run) (taken by the caller: the scan kernel needs it in
+// front of a barrier), cnt = R in front of the wave's first sample, i0 = the sample index of this lane's first sample.  Negative
+// increments and several onsets at one sample need no special case.  Returns R behind the wave's last sample.
+__device__ __forceinline__ int32_t emit_onsets(const int32_t (&m)[SPL], int32_t run, int32_t upto, int32_t cnt, int32_t cap,
+                                               int32_t *__restrict__ out, int32_t i0)
+{
+    int32_t before = __shfl_up(upto, 1);
+    if ((threadIdx.x & 63) == 0) before = 0;
+    const int32_t start = max(cnt, before);                   // R in front of this lane's first sample
+    if (run > start) {
+        int32_t at = start, prev = start;                     // the slot of onset number k + 1 is k
+#pragma unroll
+        for (int k = 0; k < SPL; ++k) {
+            const int32_t c = max(prev, m[k]);
+            for (; prev < c; ++prev, ++at)
+                if (at < cap) out[at] = i0 + k;
+        }
+    }
+    return max(cnt, __builtin_amdgcn_readlane(upto, WAVE - 1));
 }
 
 // The plain (non-wrapping) accumulator of the pulse train, GOOFER.py:487-493, with the onset test taken off the
-// sequential chain.  After sample i the reference has recorded R_i = max(R_{i-1}, floor(phase_i)) onsets (its
-// `while phase >= next_k` loop, next_k = R + 1), so the onsets are a function of the partial sums alone.  The
-// walk therefore runs nothing but the dependent fp64 adds; on the way a lane keeps the phase in front of its own
-// samples of the chunk (one v_cndmask per walk block, in the shadow of the adds).  The onsets of a finished chunk are
-// then extracted in parallel while the next chunk is already being walked: every lane replays its additions from the
-// phase it kept — the same additions in the same order, so the same partial sums — takes floor, and a max-scan and a
-// sum-scan across the note's lanes give each lane R in front of its samples and the slot of its first onset.  Negative
-// increments and several onsets at one sample need no special case.
-//
-// NPW notes share a wave, 64 / NPW lanes each.  A walk instruction is one dependent add whatever the lanes hold, and with
-// one note per wave all 64 lanes held the same chain: a quarter of the wave per note runs FOUR chains on the same
-// instructions (the chunk of a note is spread over its 16 lanes, 32 samples each, and the scans stop at the 16-lane DPP
-// rows).  The chain latency — one dependent v_add_f64 per sample, 16.8 cycles — is what the kernel takes either way; what
-// shrinks is the vector-issue and LDS bandwidth it takes from the kernels running beside it (94 M -> 30 M wave
-// instructions per 1024-note batch).  The notes of a wave are walked to the longest one's length (padding adds +0.0).
-template <int NPW>
+// sequential chain: the onsets are a function of the partial sums alone (emit_onsets), so the walk runs nothing but the
+// dependent fp64 adds.  One note per wave; of a chunk's 512 samples lane l owns 8 l .. 8 l + 7, half a walk block.  So two
+// lanes share a walk block, and on the way lane 2g keeps the phase in front of block g and lane 2g + 1 the phase in its
+// middle (a v_cndmask each, in the shadow of the adds).  The onsets of a finished chunk are then extracted in parallel while
+// the next chunk is already being walked: every lane replays its additions from the phase it kept — the same additions in the
+// same order, so the same partial sums — and takes floor.
+// tiles: 2 x OC doubles of LDS, this wave's.
 __device__ __forceinline__ void onset_walk(double *tiles, int group, const float *__restrict__ f0, double sr, const int64_t *__restrict__ sample_off,
                                            int n_notes, int32_t *__restrict__ onset_idx, int32_t *__restrict__ onset_cnt,
                                            int32_t *__restrict__ overflow)
 {
-    constexpr int LPN = WAVE / NPW;                           // lanes per note
-    constexpr int SPL = OC / LPN;                             // samples of a chunk per lane
-    constexpr int BPL = SPL / OB > 0 ? SPL / OB : 1;          // walk blocks per lane (NPW = 4: 2), or lanes per block (NPW = 1: 2)
-    static_assert(NPW == 1 || NPW == 2 || NPW == 4, "a note's lanes are whole DPP rows");
     __builtin_amdgcn_s_setprio(3);                            // see k_pulse_onsets_wrap
     const int lane = threadIdx.x & 63;
-    const int sub = lane / LPN, ln = lane % LPN;              // which note of the wave, lane inside the note
-    const int note_raw = group * NPW + sub;
-    if (__builtin_amdgcn_readfirstlane(group * NPW) >= n_notes) return;   // whole wave; no block barrier below
-    const bool live = note_raw < n_notes;
-    const int note = live ? note_raw : n_notes - 1;
-    // tiles: [buffer][note of the wave][OC] increments of this wave
+    const int note = __builtin_amdgcn_readfirstlane(group);   // (uniform: the offsets come by scalar loads)
+    if (note >= n_notes) return;                              // whole wave; no block barrier below
     const int64_t base = sample_off[note];
-    const int64_t n = live ? sample_off[note + 1] - base : 0;
-    const int64_t obase = base / 2 + 16 * (int64_t)note;
-    const int32_t cap = (int32_t)((sample_off[note + 1] / 2 + 16 * (int64_t)(note + 1)) - obase);
-    // longest note of the wave: the walk's trip count
-    int64_t n_max = n;
-#pragma unroll
-    for (int o = LPN; o < WAVE; o <<= 1) {
-        const int64_t other = __shfl_xor(n_max, o, WAVE);
-        n_max = other > n_max ? other : n_max;
-    }
-    n_max = __builtin_amdgcn_readfirstlane((int)(n_max >> 32)) * (int64_t(1) << 32) + (uint32_t)__builtin_amdgcn_readfirstlane((int)n_max);
-    // The increments f0[i] / sr (GOOFER.py:491) are formed here, in the parallel fetch stage, instead of by a pass of their
-    // own that writes 8 bytes per sample and reads them back.  With r = RN(1 / sr) the quotient correction
-    // q + fma(-q, sr, x) r is the correctly rounded x / sr (Markstein), i.e. the increment the reference divides out.
+    const int64_t n = sample_off[note + 1] - base;
+    const int32_t cap = pulse_slot_cap(sample_off, note);
     const float *__restrict__ a = f0 + base;
     const double rsr = 1.0 / sr;
-    int32_t *__restrict__ out = onset_idx + obase;
-    double phase = 0.0;                                       // per lane: the chain of this lane's note
-    int32_t cnt = 0;                                          // onsets recorded so far == R (the same in all lanes of a note)
+    int32_t *__restrict__ out = onset_idx + pulse_slot_base(base, note);
+    double phase = 0.0;                                       // the chain: the same in every lane
+    int32_t cnt = 0;                                          // onsets recorded so far == R
 
     float r[SPL];
-    auto fetch = [&](int64_t c0) {
-        const int64_t s = c0 + (int64_t)ln * SPL;
-        if (__all(c0 + OC <= n)) {                            // wave-uniform branch on purpose, see k_pulse_onsets_wrap
-#pragma unroll
-            for (int k = 0; k < SPL; ++k) r[k] = a[s + k];
-        } else {
-#pragma unroll
-            for (int k = 0; k < SPL; ++k) {
-                const int64_t i = s + k;
-                const float v = n > 0 ? a[i < n ? i : n - 1] : 0.f;
-                r[k] = i < n ? v : 0.f;                       // 0 / sr = +0.0: the padding leaves the phase alone
-            }
-        }
-    };
-    // onsets of a walked chunk: t = the note's increments, p0 = this lane's phase in front of its SPL samples
+    // onsets of a walked chunk: t = its increments, p0 = this lane's phase in front of its SPL samples
     auto emit = [&](const double *t, double p0, int32_t c0, int64_t n_left) {
         const int valid = n_left >= OC ? OC : (n_left > 0 ? (int)n_left : 0);
         int32_t m[SPL];
@@ -356,104 +363,62 @@ __device__ __forceinline__ void onset_walk(double *tiles, int group, const float
         double acc = p0;
 #pragma unroll
         for (int k = 0; k < SPL; ++k) {
-            const int i = ln * SPL + k;
+            const int i = lane * SPL + k;
             acc += t[i];
             const int32_t f = i < valid ? (int32_t)acc : 0;   // trunc == floor wherever it can raise the running max
             run = max(run, f);
             m[k] = run;
         }
-        const int32_t upto = note_scan_incl<LPN>(run, [](int32_t x, int32_t y) { return max(x, y); });
-        int32_t before = __shfl_up(upto, 1);
-        if (ln == 0) before = 0;
-        const int32_t start = max(cnt, before);               // R in front of this lane's first sample
-        const int32_t mine = max(run, start) - start;
-        const int32_t s = note_scan_incl<LPN>(mine, [](int32_t x, int32_t y) { return x + y; });
-        const int32_t tot = __shfl(s, (lane | (LPN - 1)), WAVE);              // the note's last lane
-        if (mine > 0) {
-            int32_t at = cnt + s - mine, prev = start;
-#pragma unroll
-            for (int k = 0; k < SPL; ++k) {
-                const int32_t c = max(prev, m[k]);
-                for (; prev < c; ++prev, ++at)
-                    if (at < cap) out[at] = c0 + ln * SPL + k;
-            }
-        }
-        cnt += tot;
+        cnt = emit_onsets(m, run, wave_scan_max(run), cnt, cap, out, c0 + lane * SPL);
     };
 
-    fetch(0);
+    fetch_chunk(r, a, 0, n, lane);
     int buf = 0;
     double kept = 0.0, kept_prev = 0.0;
-    for (int64_t c0 = 0; c0 < n_max; c0 += OC, buf ^= 1) {
-        double *t = tiles + ((size_t)buf * NPW + sub) * OC;                  // this lane's note
-        double *t_prev = tiles + ((size_t)(buf ^ 1) * NPW + sub) * OC;
+    for (int64_t c0 = 0; c0 < n; c0 += OC, buf ^= 1) {
+        double *t = tiles + buf * OC, *t_prev = tiles + (buf ^ 1) * OC;
 #pragma unroll
-        for (int k = 0; k < SPL; ++k) {
-            const double x = (double)r[k], q = x * rsr;
-            t[ln * SPL + k] = fma(fma(-q, sr, x), rsr, q);
-        }
+        for (int k = 0; k < SPL; ++k) t[lane * SPL + k] = inc_of(r[k], sr, rsr);
         wave_lds_sync();
-        if (c0 + OC < n_max) fetch(c0 + OC);                // in flight during the walk below
+        if (c0 + OC < n) fetch_chunk(r, a, c0 + OC, n, lane);   // in flight during the walk below
         if (c0 > 0) emit(t_prev, kept_prev, (int32_t)(c0 - OC), n - (c0 - OC));   // its stores complete during the walk as well
-        const int64_t left = n_max - c0;
+        const int64_t left = n - c0;
         // blocks are walked in pairs; a padded block adds +0.0 sixteen times and leaves the phase where it was
         const int blocks = left >= OC ? OC / OB : (int)((left + 2 * OB - 1) / (2 * OB)) * 2;
-        auto walk = [&](const double (&x)[OB], int g) {
-            double ps[OB];
-            if (NPW == 1) {                                   // two lanes per block: lane 2g in front of it, lane 2g + 1 in its middle
-                kept = ln == 2 * g ? phase : kept;
-            } else {                                          // BPL blocks per lane: lane g / BPL in front of its first one
-                kept = (g % BPL == 0 && ln == g / BPL) ? phase : kept;
-            }
-            ps[0] = phase + x[0];
-#pragma unroll
-            for (int k = 1; k < OB; ++k) ps[k] = ps[k - 1] + x[k];
-            if (NPW == 1) kept = ln == 2 * g + 1 ? ps[OB / 2 - 1] : kept;
-            phase = ps[OB - 1];
-        };
-        auto load = [&](double (&x)[OB], int g) {
-            const double *q = t + (g < blocks ? g : blocks - 1) * OB;
-#pragma unroll
-            for (int k = 0; k < OB; ++k) x[k] = q[k];
-        };
-        double xa[OB], xb[OB];
         // lgkmcnt(0) here, once per chunk: a scalar load left pending on some path above makes the compiler treat the
         // counter as out of order inside the loop and wait for *all* LDS reads in front of every block
         __builtin_amdgcn_s_waitcnt(0xc07f);
-        load(xa, 0);
-#pragma unroll 1
-        for (int g = 0; g < blocks; g += 2) {
-            load(xb, g + 1);
-            __builtin_amdgcn_sched_barrier(0);
-            walk(xa, g);
-            load(xa, g + 2);
-            __builtin_amdgcn_sched_barrier(0);
-            walk(xb, g + 1);
-        }
+        walk_blocks(t, blocks, true, [&](const double (&x)[OB], int g) {
+            double ps[OB];
+            kept = lane == 2 * g ? phase : kept;
+            ps[0] = phase + x[0];
+#pragma unroll
+            for (int k = 1; k < OB; ++k) ps[k] = ps[k - 1] + x[k];
+            kept = lane == 2 * g + 1 ? ps[OB / 2 - 1] : kept;
+            phase = ps[OB - 1];
+        });
         kept_prev = kept;
     }
-    if (n_max > 0) {
-        const int64_t c_last = (n_max - 1) / OC * OC;
-        double *t_last = tiles + ((size_t)(buf ^ 1) * NPW + sub) * OC;
-        emit(t_last, kept_prev, (int32_t)c_last, n - c_last);
+    if (n > 0) {
+        const int64_t c_last = (n - 1) / OC * OC;
+        emit(tiles + (buf ^ 1) * OC, kept_prev, (int32_t)c_last, n - c_last);
     }
-    if (ln == 0 && live) {
+    if (lane == 0) {
         onset_cnt[note] = cnt < cap ? cnt : cap;
         if (cnt > cap) atomicMax(overflow, note + 1);          // reported at the next synchronising call (goofer_check)
     }
 }
 
-// a workgroup is 4 / NPW waves = four notes either way: the same 32 KiB of tiles per workgroup (and, with the launcher's
-// padded LDS request, one workgroup per CU)
-template <int NPW>
+// the sequential walk for every note: a workgroup is four waves = four notes, 32 KiB of tiles (and, with the launcher's padded
+// LDS request, one workgroup per CU)
 __global__ __launch_bounds__(256) void k_pulse_onsets_scan(const float *__restrict__ f0, double sr, const int64_t *__restrict__ sample_off,
                                                            int n_notes, int32_t *__restrict__ onset_idx,
                                                            int32_t *__restrict__ onset_cnt, int32_t *__restrict__ overflow)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     const int wv = threadIdx.x >> 6;
-    onset_walk<NPW>(reinterpret_cast<double *>(smem) + (size_t)wv * 2 * NPW * OC, blockIdx.x * (4 / NPW) + wv, f0, sr, sample_off, n_notes,
-                    onset_idx, onset_cnt, overflow);
+    onset_walk(reinterpret_cast<double *>(smem) + (size_t)wv * 2 * OC, blockIdx.x * 4 + wv, f0, sr, sample_off, n_notes, onset_idx, onset_cnt,
+               overflow);
 }
 
 // Inclusive fp64 sum scan across the wave on the DPP path (see wave_scan_incl): lanes without a source add +0.0.  Any
@@ -479,7 +444,7 @@ __device__ __forceinline__ double wave_scan_add_f64(double x)
 // The onsets WITHOUT the sequential walk, wherever that is provably the same thing.
 //
 // The reference's phase after sample i is the fp64 running sum p_i = fl(p_{i-1} + x_i), x_i = f0[i] / sr (GOOFER.py:491), and
-// the onsets depend on it only through floor(p_i) (R_i = max(R_{i-1}, floor(p_i)), see onset_walk).  A blocked parallel scan
+// the onsets depend on it only through floor(p_i) (R_i = max(R_{i-1}, floor(p_i)), see emit_onsets).  A blocked parallel scan
 // S_i adds the same x_1 .. x_i in another order.  For ANY order of fp64 additions of i terms the computed sum differs from
 // the exact one by at most gamma_{i-1} sum|x_j|, gamma_k = k u / (1 - k u), u = 2^-53 (Higham, Accuracy and Stability of
 // Numerical Algorithms, 4.2), so |p_i - S_i| <= 2 gamma_{i-1} A_i with A_i = sum_{j<=i} |x_j|.  With every x_j >= 0
@@ -503,7 +468,6 @@ __global__ __launch_bounds__(256) void k_pulse_onsets_par(const float *__restric
                                                           int32_t *__restrict__ onset_cnt, int32_t *__restrict__ overflow,
                                                           int32_t *__restrict__ stats, int force)
 {
-    constexpr int SPL = OC / WAVE;
     extern __shared__ __align__(16) unsigned char smem[];     // the walk's tiles (one wave: 2 x OC doubles)
     __shared__ double s_tot[2][4];
     __shared__ int32_t s_top[2][4], s_bad[2][4];
@@ -511,31 +475,16 @@ __global__ __launch_bounds__(256) void k_pulse_onsets_par(const float *__restric
     const int note = blockIdx.x;
     const int64_t base = sample_off[note];
     const int64_t n = sample_off[note + 1] - base;
-    const int64_t obase = base / 2 + 16 * (int64_t)note;
-    const int32_t cap = (int32_t)((sample_off[note + 1] / 2 + 16 * (int64_t)(note + 1)) - obase);
+    const int32_t cap = pulse_slot_cap(sample_off, note);
     const float *__restrict__ a = f0 + base;
     const double rsr = 1.0 / sr;
-    int32_t *__restrict__ out = onset_idx + obase;
+    int32_t *__restrict__ out = onset_idx + pulse_slot_base(base, note);
     double carry = 0.0;                                       // the scan's phase in front of the round (uniform)
     int32_t cnt = 0;                                          // onsets in front of the round (uniform)
     bool unsure = force != 0;
 
-    float r[SPL];
-    auto fetch = [&](int64_t w0) {                            // w0: first sample of this wave's part of a round
-        const int64_t s = w0 + (int64_t)lane * SPL;
-        if (w0 + OC <= n) {
-#pragma unroll
-            for (int k = 0; k < SPL; ++k) r[k] = a[s + k];
-        } else {
-#pragma unroll
-            for (int k = 0; k < SPL; ++k) {
-                const int64_t i = s + k;
-                const float v = n > 0 ? a[i < n ? i : n - 1] : 0.f;
-                r[k] = i < n ? v : 0.f;                       // 0 / sr = +0.0: the padding leaves the phase alone
-            }
-        }
-    };
-    if (!unsure) fetch((int64_t)wv * OC);
+    float r[SPL];                                             // (fetched from the first sample of this wave's part of a round)
+    if (!unsure) fetch_chunk(r, a, (int64_t)wv * OC, n, lane);
     int par = 0;
     for (int64_t c0 = 0; c0 < n && !unsure; c0 += PAR_ROUND, par ^= 1) {
         const int64_t w0 = c0 + (int64_t)wv * OC;
@@ -543,12 +492,11 @@ __global__ __launch_bounds__(256) void k_pulse_onsets_par(const float *__restric
         bool nb = false;
 #pragma unroll
         for (int k = 0; k < SPL; ++k) {
-            const double x = (double)r[k], q = x * rsr;
-            const double inc = fma(fma(-q, sr, x), rsr, q);   // RN(x / sr), as in onset_walk
+            const double inc = inc_of(r[k], sr, rsr);
             nb |= !(inc >= 0.0);                              // negative or NaN
             l[k] = k ? l[k - 1] + inc : inc;
         }
-        if (c0 + PAR_ROUND < n) fetch(w0 + PAR_ROUND);
+        if (c0 + PAR_ROUND < n) fetch_chunk(r, a, w0 + PAR_ROUND, n, lane);
         const double incl = wave_scan_add_f64(l[SPL - 1]);
         double excl = __shfl_up(incl, 1, WAVE);
         excl = lane == 0 ? 0.0 : excl;
@@ -578,7 +526,7 @@ __global__ __launch_bounds__(256) void k_pulse_onsets_par(const float *__restric
             run = max(run, f);
             m[k] = run;
         }
-        const int32_t upto = wave_scan_incl(run, [](int32_t x, int32_t y) { return max(x, y); });
+        const int32_t upto = wave_scan_max(run);
         const bool wave_bad = __any(nb);
         if (lane == WAVE - 1) { s_top[par][wv] = upto; s_bad[par][wv] = wave_bad ? 1 : 0; }
         __syncthreads();
@@ -591,20 +539,7 @@ __global__ __launch_bounds__(256) void k_pulse_onsets_par(const float *__restric
             bad |= s_bad[par][q];
         }
         if (bad) { unsure = true; break; }
-        // onsets of the wave's samples: as onset_walk's emit
-        int32_t before = __shfl_up(upto, 1);
-        if (lane == 0) before = 0;
-        const int32_t start = max(cnt_w, before);             // R in front of this lane's first sample
-        const int32_t mine = max(run, start) - start;
-        if (mine > 0) {
-            int32_t at = start, prev = start;                 // the slot of onset number k + 1 is k
-#pragma unroll
-            for (int k = 0; k < SPL; ++k) {
-                const int32_t c = max(prev, m[k]);
-                for (; prev < c; ++prev, ++at)
-                    if (at < cap) out[at] = (int32_t)w0 + lane * SPL + k;
-            }
-        }
+        emit_onsets(m, run, upto, cnt_w, cap, out, (int32_t)w0 + lane * SPL);
         cnt = cnt_all;
         carry = total;
     }
@@ -613,13 +548,22 @@ __global__ __launch_bounds__(256) void k_pulse_onsets_par(const float *__restric
         if (unsure) atomicAdd(stats + 1, 1);
     }
     if (unsure) {
-        if (wv == 0) onset_walk<1>(reinterpret_cast<double *>(smem), note, f0, sr, sample_off, n_notes, onset_idx, onset_cnt, overflow);
+        if (wv == 0) onset_walk(reinterpret_cast<double *>(smem), note, f0, sr, sample_off, n_notes, onset_idx, onset_cnt, overflow);
         return;
     }
     if (threadIdx.x == 0) {
         onset_cnt[note] = cnt < cap ? cnt : cap;
         if (cnt > cap) atomicMax(overflow, note + 1);          // reported at the next synchronising call (goofer_check)
     }
+}
+
+// end_max of a strip of 64 onsets in the finish kernels: the inclusive prefix max of e = sample + length (0 in a lane without an
+// onset) across the wave, joined with the strips before it (carry, which moves on to this strip's last value)
+__device__ __forceinline__ int32_t strip_end_max(int32_t e, int32_t &carry)
+{
+    const int32_t m = max(wave_scan_max(e), carry);
+    carry = __shfl(m, WAVE - 1, WAVE);
+    return m;
 }
 
 // One wave per note, lanes over onsets: T = 1/max(last_valid_f0, 1e-6) with last_valid_f0 the most
@@ -632,7 +576,7 @@ __global__ __launch_bounds__(64) void k_onset_finish(const float *__restrict__ f
 {
     const int note = blockIdx.x, lane = threadIdx.x;
     const int64_t base = sample_off[note];
-    const int64_t obase = base / 2 + 16 * (int64_t)note;
+    const int64_t obase = pulse_slot_base(base, note);
     const float *__restrict__ f = f0 + base;
     const int cnt = onset_cnt[note];
     int32_t carry = 0;
@@ -650,20 +594,12 @@ __global__ __launch_bounds__(64) void k_onset_finish(const float *__restrict__ f
             T0 = (int32_t)(t0 < 3 ? 3 : (t0 > 8192 ? 8192 : t0));
             e = i + T0;
         }
-        // inclusive prefix max across the wave, then across chunks
-        int32_t m = e;
-#pragma unroll
-        for (int off = 1; off < WAVE; off <<= 1) {
-            int32_t o = __shfl_up(m, off, WAVE);
-            if (lane >= off) m = o > m ? o : m;
-        }
-        m = m > carry ? m : carry;
+        const int32_t m = strip_end_max(e, carry);
         if (k < cnt) {
             onset_t o;
             o.i = i; o.T0 = T0; o.end_max = m; o.pad = 0; o.T = T;
             onsets[obase + k] = o;
         }
-        carry = __shfl(m, WAVE - 1, WAVE);
     }
 }
 
@@ -676,11 +612,27 @@ __global__ __launch_bounds__(64) void k_onset_finish(const float *__restrict__ f
 // once the on-the-fly pulses had left the kernel (with them it held 115 registers either way and sixteen was the faster)
 #define PP_MAXON 512
 
-__device__ __forceinline__ float pulse_value(const onset_t &o, int j, const float *__restrict__ peak, const float *__restrict__ tab)
+__device__ __forceinline__ float pulse_value(const onset_t &o, int j, const float *__restrict__ tab)
 {
     const int d = j - o.i;
     if (d < 0 || d >= o.T0) return 0.f;
     return tab[pulse_tab_row(o.T0) + d];                      // (T0 <= PULSE_TAB_MAX = the cap of the onset kernels)
+}
+
+// The onsets of `list` (count of them, ascending; global memory or LDS) that can cover samples j_first .. j_last of the note:
+// last = the last onset starting at or before j_last, first = back from it while the running end_max of the onset in front
+// passes j_first.  false: none starts that early.  Summing first .. last in ascending order is the reference's accumulation order.
+__device__ __forceinline__ bool covering_onsets(const onset_t *list, int count, int32_t j_last, int32_t j_first, int &first, int &last)
+{
+    int lo = -1, hi = count;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (list[mid].i <= j_last) lo = mid; else hi = mid;
+    }
+    if (lo < 0) return false;
+    last = first = lo;
+    while (first > 0 && list[first - 1].end_max > j_first) --first;
+    return true;
 }
 
 // Which onsets can touch which tile, once per tile instead of once per workgroup through two rounds of note search, a count over
@@ -702,7 +654,7 @@ __global__ void k_pulse_tiles(const onset_t *__restrict__ onsets, const int32_t 
         return;
     }
     const int64_t base = sample_off[lo_n];
-    const onset_t *ol = onsets + (base / 2 + 16 * (int64_t)lo_n);
+    const onset_t *ol = onsets + pulse_slot_base(base, lo_n);
     const int cnt = onset_cnt[lo_n];
     const int32_t j_lo = (int32_t)(g0 - base), j_hi = (int32_t)(gl - base);
     int a = 0, b = cnt;                                       // onsets with end_max <= j_lo: a prefix
@@ -720,98 +672,49 @@ __global__ void k_pulse_tiles(const onset_t *__restrict__ onsets, const int32_t 
 }
 
 __global__ __launch_bounds__(256) void k_pulse_place(const onset_t *__restrict__ onsets, const int32_t *__restrict__ onset_cnt,
-                                                     const float *__restrict__ peak, const float *__restrict__ tab,
-                                                     const int64_t *__restrict__ sample_off, int n_notes, int64_t total_samples,
-                                                     float *__restrict__ pulse, const int4 *__restrict__ tiles)
+                                                     const float *__restrict__ tab, const int64_t *__restrict__ sample_off,
+                                                     int64_t total_samples, float *__restrict__ pulse, const int4 *__restrict__ tiles)
 {
-    __shared__ int s_pair[2];
-    __shared__ int s_rng[2];
     __shared__ onset_t s_on[PP_MAXON];
     const int64_t g0 = (int64_t)blockIdx.x * (blockDim.x * PP_SPT);
     int64_t gl = g0 + (int64_t)blockDim.x * PP_SPT - 1;
     if (gl > total_samples - 1) gl = total_samples - 1;
-    int lo_n, hi_n;
-    int k0 = 0, k1 = -1;
-    if (tiles) {
-        const int4 tl = tiles[blockIdx.x];                    // (workgroup-uniform: a scalar load)
-        lo_n = tl.x >= 0 ? tl.x : tl.y;
-        hi_n = tl.x >= 0 ? tl.x : tl.z;
-        k0 = tl.y;
-        k1 = tl.z;
-    } else {
-    if (threadIdx.x == 0) {
-        s_rng[0] = 0;
-        s_rng[1] = 0;
-    }
-    block_note_range_last(sample_off, n_notes, g0, gl, s_pair, lo_n, hi_n);
-    if (lo_n == hi_n) {
-        // onsets that can touch the tile: [first with end_max > j_lo (end_max is monotone), last with i <= j_hi].  Both
-        // are counts over the sorted list, taken by the whole workgroup at once instead of two serial binary searches.
+    const int4 tl = tiles[blockIdx.x];                        // (workgroup-uniform: a scalar load)
+    const int lo_n = tl.x >= 0 ? tl.x : tl.y;
+    const int k0 = tl.y, nk = tl.z - tl.y + 1;
+    if (tl.x >= 0 && nk <= PP_MAXON) {
         const int64_t base = sample_off[lo_n];
-        const onset_t *ol = onsets + (base / 2 + 16 * (int64_t)lo_n);
-        const int cnt = onset_cnt[lo_n];
-        const int32_t j_lo = (int32_t)(g0 - base), j_hi = (int32_t)(gl - base);
-        int c_first = 0, c_last = 0;
-        for (int k = threadIdx.x; k < cnt; k += blockDim.x) {
-            c_first += ol[k].end_max <= j_lo;
-            c_last += ol[k].i <= j_hi;
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            c_first += __shfl_xor(c_first, o, 64);
-            c_last += __shfl_xor(c_last, o, 64);
-        }
-        if ((threadIdx.x & 63) == 0) {
-            atomicAdd(&s_rng[0], c_first);
-            atomicAdd(&s_rng[1], c_last);
-        }
-        __syncthreads();
-        k0 = __builtin_amdgcn_readfirstlane(s_rng[0]);
-        k1 = __builtin_amdgcn_readfirstlane(s_rng[1]) - 1;
-    }
-    }
-    const int nk = k1 - k0 + 1;
-    if (lo_n == hi_n && nk <= PP_MAXON) {
-        const int64_t base = sample_off[lo_n];
-        const onset_t *ol = onsets + (base / 2 + 16 * (int64_t)lo_n);
+        const onset_t *ol = onsets + pulse_slot_base(base, lo_n);
         for (int k = threadIdx.x; k < nk; k += blockDim.x) s_on[k] = ol[k0 + k];
         __syncthreads();
         // a thread owns PP_SPT consecutive samples (16-byte stores): they share their covering onsets, so the short
-        // search — last onset starting at or before the fourth sample, back to the first whose running end_max passes
+        // search — last onset starting at or before the last sample, back to the first whose running end_max passes
         // the first sample — is paid once per PP_SPT outputs, and the sums run over those one to three onsets only
         const int64_t g = g0 + (int64_t)threadIdx.x * PP_SPT;
         if (g > gl) return;
         const int32_t j = (int32_t)(g - base);
         const int live = gl - g + 1 < PP_SPT ? (int)(gl - g + 1) : PP_SPT;
-        int lo = -1, hi = nk;
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (s_on[mid].i <= j + live - 1) lo = mid; else hi = mid;
-        }
         float acc[PP_SPT];
 #pragma unroll
         for (int e = 0; e < PP_SPT; ++e) acc[e] = 0.f;
-        if (lo >= 0) {
-            int first = lo;
-            while (first > 0 && s_on[first - 1].end_max > j) --first;
-            for (int k = first; k <= lo; ++k) {                                  // ascending onsets: the reference's order
+        int first, last;
+        if (covering_onsets(s_on, nk, j + live - 1, j, first, last)) {
+            for (int k = first; k <= last; ++k) {                                // ascending onsets: the reference's order
                 const onset_t o = s_on[k];
-                {
-                    // the eight table values first (index clamped into the pulse), then the range test as a select: the loads of
-                    // a thread's samples are in flight together instead of one round trip per sample behind its own branch
-                    const float *__restrict__ row = tab + pulse_tab_row(o.T0);
-                    const int d0 = j - o.i;
-                    float tv[PP_SPT];
+                // the eight table values first (index clamped into the pulse), then the range test as a select: the loads of
+                // a thread's samples are in flight together instead of one round trip per sample behind its own branch
+                const float *__restrict__ row = tab + pulse_tab_row(o.T0);
+                const int d0 = j - o.i;
+                float tv[PP_SPT];
 #pragma unroll
-                    for (int e = 0; e < PP_SPT; ++e) {
-                        const int d = d0 + e;
-                        tv[e] = row[d < 0 ? 0 : (d >= o.T0 ? o.T0 - 1 : d)];
-                    }
+                for (int e = 0; e < PP_SPT; ++e) {
+                    const int d = d0 + e;
+                    tv[e] = row[d < 0 ? 0 : (d >= o.T0 ? o.T0 - 1 : d)];
+                }
 #pragma unroll
-                    for (int e = 0; e < PP_SPT; ++e) {
-                        const int d = d0 + e;
-                        acc[e] += (d < 0 || d >= o.T0) ? 0.f : tv[e];
-                    }
+                for (int e = 0; e < PP_SPT; ++e) {
+                    const int d = d0 + e;
+                    acc[e] += (d < 0 || d >= o.T0) ? 0.f : tv[e];
                 }
             }
         }
@@ -831,31 +734,32 @@ __global__ __launch_bounds__(256) void k_pulse_place(const onset_t *__restrict__
         while (sample_off[note + 1] <= g) ++note;
         const int64_t base = sample_off[note];
         const int32_t j = (int32_t)(g - base);
-        const onset_t *ol = onsets + (base / 2 + 16 * (int64_t)note);
-        const int cnt = onset_cnt[note];
+        const onset_t *ol = onsets + pulse_slot_base(base, note);
         float acc = 0.f;
-        int lo = -1, hi = cnt;   // last onset with i <= j
-        while (hi - lo > 1) {
-            int mid = (lo + hi) >> 1;
-            if (ol[mid].i <= j) lo = mid; else hi = mid;
-        }
-        if (lo >= 0) {
-            int first = lo;
-            while (first > 0 && ol[first - 1].end_max > j) --first;
-            for (int k = first; k <= lo; ++k) acc += pulse_value(ol[k], j, peak, tab);
-        }
+        int first, last;
+        if (covering_onsets(ol, onset_cnt[note], j, j, first, last))
+            for (int k = first; k <= last; ++k) acc += pulse_value(ol[k], j, tab);
         pulse[g] = acc;
     }
 }
 
-// tiles != nullptr (16-byte aligned, 4 ints per tile of 256 * PP_SPT samples of total_samples): also the pulse placement's tile table
-// (k_pulse_tiles) — launch_pulse_place then is a single launch
+// The placement's tile table (4 ints per tile of 256 * PP_SPT samples, PULSE_TILE_INTS of them) is read with 16-byte scalar
+// loads.  Every caller takes it from an arena over a handle-owned block (goofer_pulse_train: the head of its scratch; the batch
+// driver: a piece of its own), i.e. 256-byte aligned; anything else is a bug in the caller, not a case to serve.
+static int check_tiles(goofer_ctx *ctx, const int32_t *tiles)
+{
+    if (!tiles || ((uintptr_t)tiles & 15) != 0) return goofer_fail(ctx, GOOFER_EINVAL, "pulse tile table: null or not 16-byte aligned");
+    return GOOFER_OK;
+}
+
+// tiles: made here for launch_pulse_place (k_pulse_tiles), which then is a single launch
 int launch_pulse_onsets(goofer_ctx *ctx, const float *f0, float f0_scale, const int64_t *sample_off,
                         int n_notes, onset_t *onsets, int32_t *onset_idx, int32_t *onset_cnt, int32_t *overflow, int64_t total_samples,
                         int32_t *tiles, hipStream_t st)
 {
     if (n_notes <= 0) return GOOFER_OK;
     if (f0_scale != 1.0f) return goofer_fail(ctx, GOOFER_EINVAL, "pulse onsets expect pre-scaled f0");
+    if (int rc = check_tiles(ctx, tiles)) return rc;
     if (ctx->pulse_scan != 0) {
         // parallel phase scan, the sequential walk inside it for the notes it cannot settle; `overflow` is the handle's block of
         // sticky words: [0] overflow, [1] notes walked, [2] notes scanned
@@ -865,21 +769,15 @@ int launch_pulse_onsets(goofer_ctx *ctx, const float *f0, float f0_scale, const 
     } else {
         // the sequential walk for every note (A/B reference of the scan): one note per wave, four notes per workgroup
         const int blocks = (n_notes + 3) / 4;
-        const int per_cu = (blocks + 255) / 256;              // MI355X: 256 CUs, 160 KiB LDS each
-        size_t lds = (size_t)(160 * 1024) / per_cu;
-        if (lds > (size_t)81 * 1024) lds = (size_t)81 * 1024;   // 81 KiB: two of these cannot share a CU, and 79 KiB stay free for
-                                                                // the kernel running beside the walk
-        lds = lds / 1024 * 1024;
-        const size_t need = 4 * 2 * OC * sizeof(double);      // 32 KiB actually used
-        if (lds < need) lds = need;
-        if (int arc = kernel_allow_max_lds(ctx, (const void *)k_pulse_onsets_scan<1>)) return arc;
-        hipLaunchKernelGGL(k_pulse_onsets_scan<1>, dim3(blocks), dim3(256), lds, st, f0, (double)ctx->plan.sr, sample_off, n_notes, onset_idx, onset_cnt, overflow);
+        const size_t lds = walk_lds_request(blocks, 4 * 2 * OC * sizeof(double), (size_t)81 * 1024);   // 32 KiB actually used
+        if (int arc = kernel_allow_max_lds(ctx, (const void *)k_pulse_onsets_scan)) return arc;
+        hipLaunchKernelGGL(k_pulse_onsets_scan, dim3(blocks), dim3(256), lds, st, f0, (double)ctx->plan.sr, sample_off, n_notes, onset_idx, onset_cnt, overflow);
         LAUNCH_CHECK(ctx);
     }
     hipLaunchKernelGGL(k_onset_finish, dim3(n_notes), dim3(64), 0, st, f0, sample_off, n_notes, (double)ctx->plan.sr, onset_idx,
                        onset_cnt, onsets);
     LAUNCH_CHECK(ctx);
-    if (total_samples > 0 && tiles && ((uintptr_t)tiles & 15) == 0) {
+    if (total_samples > 0) {
         const unsigned n_tiles = (unsigned)((total_samples + 256 * PP_SPT - 1) / (256 * PP_SPT));
         hipLaunchKernelGGL(k_pulse_tiles, dim3((n_tiles + 63) / 64), dim3(64), 0, st, onsets, onset_cnt, sample_off, n_notes, total_samples,
                            (int)n_tiles, reinterpret_cast<int4 *>(tiles));
@@ -888,16 +786,15 @@ int launch_pulse_onsets(goofer_ctx *ctx, const float *f0, float f0_scale, const 
     return GOOFER_OK;
 }
 
-// tiles: the table launch_pulse_onsets made (4 ints per tile of 256 * PP_SPT samples), or nullptr: every
-// workgroup searches for itself (goofer_pulse_train with an unaligned scratch pointer)
+// tiles: the table launch_pulse_onsets made
 int launch_pulse_place(goofer_ctx *ctx, const onset_t *onsets, const int32_t *onset_cnt, const int64_t *sample_off, int n_notes,
                        int64_t total_samples, float *pulse, const int32_t *tiles, hipStream_t st)
 {
     if (total_samples <= 0) return GOOFER_OK;
+    if (int rc = check_tiles(ctx, tiles)) return rc;
     const unsigned n_tiles = (unsigned)((total_samples + 256 * PP_SPT - 1) / (256 * PP_SPT));
-    const int4 *tl = (tiles && ((uintptr_t)tiles & 15) == 0) ? reinterpret_cast<const int4 *>(tiles) : nullptr;
-    hipLaunchKernelGGL(k_pulse_place, dim3(n_tiles), dim3(256), 0, st, onsets, onset_cnt, ctx->plan.pulse_peak, ctx->plan.pulse_shape,
-                       sample_off, n_notes, total_samples, pulse, tl);
+    hipLaunchKernelGGL(k_pulse_place, dim3(n_tiles), dim3(256), 0, st, onsets, onset_cnt, ctx->plan.pulse_shape, sample_off, total_samples,
+                       pulse, reinterpret_cast<const int4 *>(tiles));
     LAUNCH_CHECK(ctx);
     return GOOFER_OK;
 }
@@ -996,7 +893,7 @@ __global__ __launch_bounds__(64) void k_subharm_finish(const double *__restrict_
 {
     const int note = blockIdx.x, lane = threadIdx.x;
     const int64_t base = sample_off[note];
-    const int64_t obase = base + 16 * (int64_t)note;         // (the sub-harmonic layer's slots: one per sample, k_pulse_onsets_wrap)
+    const int64_t obase = sub_slot_base(base, note);
     const int cnt = onset_cnt[note];
     double *keys = keys_all + base;                              // (cnt <= n: at most one event per sample)
     const int64_t n_note = sample_off[note + 1] - base;
@@ -1026,19 +923,12 @@ __global__ __launch_bounds__(64) void k_subharm_finish(const double *__restrict_
             for (int q = 0; q < n; ++q) peak = fmaxf(peak, fabsf(sub_lf_raw(q, n, T)));
             e = i + n;
         }
-        int32_t m = e;
-#pragma unroll
-        for (int off = 1; off < WAVE; off <<= 1) {
-            int32_t o = __shfl_up(m, off, WAVE);
-            if (lane >= off) m = o > m ? o : m;
-        }
-        m = m > carry ? m : carry;
+        const int32_t m = strip_end_max(e, carry);
         if (k < cnt) {
             onset_t o;
             o.i = i; o.T0 = n; o.end_max = m; o.pad = __float_as_int(peak); o.T = T;
             onsets[obase + k] = o;
         }
-        carry = __shfl(m, WAVE - 1, WAVE);
     }
 }
 
@@ -1061,18 +951,11 @@ __global__ __launch_bounds__(256) void k_subharm_place(const onset_t *__restrict
     if (!(params[note].subharm_weight > 0.f)) return;
     const int64_t base = sample_off[note];
     const int32_t j = (int32_t)(g - base);
-    const onset_t *ol = onsets + (base + 16 * (int64_t)note);
-    const int cnt = onset_cnt[note];
+    const onset_t *ol = onsets + sub_slot_base(base, note);
     double acc = 0.0;
-    int lo = -1, hi = cnt;
-    while (hi - lo > 1) {
-        int mid = (lo + hi) >> 1;
-        if (ol[mid].i <= j) lo = mid; else hi = mid;
-    }
-    if (lo >= 0) {
-        int first = lo;
-        while (first > 0 && ol[first - 1].end_max > j) --first;
-        for (int k = first; k <= lo; ++k) {
+    int k_first, k_last;
+    if (covering_onsets(ol, onset_cnt[note], j, j, k_first, k_last)) {
+        for (int k = k_first; k <= k_last; ++k) {
             const onset_t o = ol[k];
             const int d = j - o.i;
             if (d < o.T0) {
@@ -1131,11 +1014,7 @@ int launch_subharm(goofer_ctx *ctx, const float *f0s, const double *f0_64, const
         LAUNCH_CHECK(ctx);
         {
             const int blocks = (n_notes + 3) / 4;
-            const int per_cu = (blocks + 255) / 256;
-            size_t lds = (size_t)(160 * 1024) / per_cu;
-            lds = lds / 1024 * 1024;
-            const size_t need = 4 * 2 * OC * sizeof(double) + 4 * WAVE * sizeof(int32_t);
-            if (lds < need) lds = need;
+            const size_t lds = walk_lds_request(blocks, 4 * 2 * OC * sizeof(double) + 4 * WAVE * sizeof(int32_t), 0);   // tiles + event queues
             if (int arc = kernel_allow_max_lds(ctx, (const void *)k_pulse_onsets_wrap)) return arc;
             hipLaunchKernelGGL(k_pulse_onsets_wrap, dim3(blocks), dim3(256), lds, st, inc, sample_off, n_notes, onset_idx, onset_cnt,
                                overflow, note_on);

@@ -179,10 +179,7 @@ struct synth_scratch {
 
 static void carve_synth(arena &a, const goofer_plan_t &p, const synth_route &r, int64_t F, int64_t N, int n, int ld, synth_scratch &s)
 {
-    // onset slots: n / 2 + 16 per note for the pulse train (an f0 above sr / 2 is refused) — n + 16 with the sub-harmonic layer,
-    // whose tracker fires at most once per sample and does so on every sample once its increment passes 1 (the resampler's
-    // vibrato depth of 3 takes the layer to 8 x f0: above sr / 2 from F7 on)
-    s.slots = (size_t)(r.sub_on ? N : N / 2) + 16 * (size_t)n + 16;
+    s.slots = onset_slots(N, n, r.sub_on);
     s.spec = r.walkers ? 0 : (size_t)F * spec_stride(p.n_bins);
     s.tframes = r.walkers ? 0 : (size_t)F * p.n_fft;
     s.env_noise = r.walkers ? 0 : (size_t)F * ld;

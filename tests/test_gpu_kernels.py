@@ -169,6 +169,22 @@ def _onset_lists(c, lens):
     return [idx[off[k] // 2 + 16 * k: off[k] // 2 + 16 * k + cnt[k]].copy() for k in range(len(lens))]
 
 
+def _pulse_scan_modes(ctx, f0s):
+    """{pulse_scan mode: (pulse, onset lists, notes scanned, notes walked)} of one batch"""
+    lens = [len(f) for f in f0s]
+    d_f0, off = ctx.tensor(np.concatenate(f0s)), _off(ctx, lens)
+    res = {}
+    try:
+        for mode in (0, 1, 2):
+            ctx.set_option("pulse_scan", mode)
+            s0, w0 = ctx.counter("pulse_scanned_notes"), ctx.counter("pulse_fallback_notes")
+            pulse = ctx.pulse_train(d_f0, off).cpu().numpy()
+            res[mode] = (pulse, _onset_lists(ctx, lens), ctx.counter("pulse_scanned_notes") - s0, ctx.counter("pulse_fallback_notes") - w0)
+    finally:
+        ctx.set_option("pulse_scan", 1)
+    return res
+
+
 def test_pulse_onsets_parallel_scan_equals_sequential_walk(ctx):
     """Option pulse_scan: 1 (default) takes the onsets from the parallel fp64 phase scan wherever its rounding band cannot move
     floor(phase) and walks the other notes sequentially inside the same kernel; 0 runs the sequential walk kernel on every
@@ -201,16 +217,7 @@ def test_pulse_onsets_parallel_scan_equals_sequential_walk(ctx):
         f0s.append(f.astype(np.float32))
         must_walk.append(walk)
     lens = [len(f) for f in f0s]
-    d_f0, off = ctx.tensor(np.concatenate(f0s)), _off(ctx, lens)
-    res = {}
-    try:
-        for mode in (0, 1, 2):
-            ctx.set_option("pulse_scan", mode)
-            s0, w0 = ctx.counter("pulse_scanned_notes"), ctx.counter("pulse_fallback_notes")
-            pulse = ctx.pulse_train(d_f0, off).cpu().numpy()
-            res[mode] = (pulse, _onset_lists(ctx, lens), ctx.counter("pulse_scanned_notes") - s0, ctx.counter("pulse_fallback_notes") - w0)
-    finally:
-        ctx.set_option("pulse_scan", 1)
+    res = _pulse_scan_modes(ctx, f0s)
     assert res[0][2:] == (0, 0)
     assert res[2][2:] == (len(lens), len(lens))
     assert res[1][2] == len(lens)
@@ -225,6 +232,32 @@ def test_pulse_onsets_parallel_scan_equals_sequential_walk(ctx):
         if k % 3 == 0:
             assert np.max(np.abs(res[1][0][o:o + n] - R.pulse_train(f, 44100))) < 4e-6, k
         o += n
+    # The edges of a walk block (16 samples), of the even-padded block pair (32) and of the scan's 2048-sample round, in batches
+    # of 1, 3, 4 and 5 notes: a walk workgroup is four waves, so its last one holds 1, 3, 4 and 1 live waves.  f0 of a few kHz
+    # gives even the 15-sample note an onset; 4410 Hz crosses an integer phase every ten samples (those notes must be walked).
+    edge = []
+    for i, n in enumerate([15, 16, 17, 31, 32, 33, 2047, 2048, 2049, 4095]):
+        f = rng.uniform(4000, 9000) * 2 ** (0.3 * np.sin(2 * np.pi * rng.uniform(20, 200) * np.arange(n) / 44100))
+        if i % 3 == 1:
+            f[:] = 4410.0
+        edge.append(f.astype(np.float32))
+    refs = [R.pulse_train(f, 44100) for f in edge]
+    for pick in ([6], [0, 7, 2], [3, 8, 1, 9], [4, 5, 9, 0, 6], list(range(10))):
+        part = [edge[k] for k in pick]
+        res = _pulse_scan_modes(ctx, part)
+        assert res[0][2:] == (0, 0)
+        assert res[2][2:] == (len(pick), len(pick))
+        assert res[1][2] == len(pick)
+        for mode in (1, 2):
+            assert np.array_equal(res[mode][0], res[0][0]), (pick, mode)
+            for k, (a, b) in enumerate(zip(res[mode][1], res[0][1])):
+                assert np.array_equal(a, b), (pick, mode, k)
+        assert all(len(a) > 0 for a in res[0][1]), pick
+        o = 0
+        for k in pick:
+            n = len(edge[k])
+            assert np.max(np.abs(res[1][0][o:o + n] - refs[k])) < 4e-6, (pick, k)
+            o += n
 
 
 def test_pulse_train_negative_and_oversized_increments(ctx):

@@ -23,7 +23,7 @@ def ctx():
     c.close()
 
 
-def _batch(ctx, sr, n_fft, hop, lens, seed, subharm_weight=None):
+def _batch(ctx, sr, n_fft, hop, lens, seed, subharm_weight=None, fixed_f0=None):
     from goofer_amd.device import default_params
     ctx.plan(sr, n_fft, hop)
     rng = np.random.default_rng(seed)
@@ -37,6 +37,9 @@ def _batch(ctx, sr, n_fft, hop, lens, seed, subharm_weight=None):
         m[n // 4:n // 2] = 1.0
         masks.append(m)
         f0s.append((150.0 + 100.0 * rng.random(n)).astype(np.float32) * m)
+    for k, hz in (fixed_f0 or {}).items():                     # note k: voiced throughout at a constant f0
+        masks[k][:] = 1.0
+        f0s[k][:] = hz
     par = default_params(len(lens))
     if subharm_weight is not None:
         par["subharm_weight"] = subharm_weight
@@ -94,7 +97,11 @@ def _sub_onsets(f0, mask, sr, ratio):
 
 def test_onset_view_after_a_subharmonic_batch(ctx):
     """After a batch with the 'sg' layer the onset slots hold the sub-harmonic trackers' onsets (k_pulse_onsets_wrap runs last),
-    n + 16 per note: the view covers every carved slot, and note k's onsets start at sample_off[k] + 16 k."""
+    n + 16 per note: the view covers every carved slot, and note k's onsets start at sample_off[k] + 16 k.
+
+    The second batch has lengths at the edges of a walk block (16 samples) and of a chunk (512), a workgroup whose last wave has
+    no note (nine notes, four per workgroup), and a note whose sub-harmonic increment 3000 * 16 / 44100 is above 1 throughout:
+    the tracker fires on every sample, 512 events per chunk, so its 64-entry queue is flushed from inside the walk."""
     lens = [4000, 9000, 2500, 12000, 6000]
     weight = np.array([0.5, 0.0, 0.8, 0.5, 0.3], dtype=np.float32)
     args, f0s, masks = _batch(ctx, 44100, 1024, 256, lens, 11, weight)
@@ -110,3 +117,18 @@ def test_onset_view_after_a_subharmonic_batch(ctx):
         assert want.size > 0 or weight[k] == 0
         assert cnt[k] == want.size, k
         assert np.array_equal(idx[off[k] + 16 * k: off[k] + 16 * k + cnt[k]], want), k
+    lens = [1, 15, 16, 17, 511, 512, 513, 1025, 1500]
+    args, f0s, masks = _batch(ctx, 44100, 1024, 256, lens, 12, np.full(len(lens), 0.5, dtype=np.float32), fixed_f0={8: 3000.0})
+    ctx.synth_batch(*args, seed=2, subharm=dict(semitones=48))
+    cnt = ctx.debug_fetch("onset_cnt")
+    idx = ctx.debug_fetch("onset_idx")
+    N, n = sum(lens), len(lens)
+    assert cnt.size == n
+    assert idx.size == N + 16 * n + 16
+    off = np.concatenate([[0], np.cumsum(lens)])
+    for k in range(n):
+        want = _sub_onsets(f0s[k], masks[k], 44100, 16.0)
+        assert want.size <= lens[k] + 16, k
+        assert cnt[k] == want.size, k
+        assert np.array_equal(idx[off[k] + 16 * k: off[k] + 16 * k + cnt[k]], want), k
+    assert cnt[8] == lens[8]
