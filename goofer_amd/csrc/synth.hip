@@ -429,7 +429,8 @@ static int assemble_batch(goofer_ctx *ctx, const goofer_assembly *asmb, render_l
     int rc = carve_block(ctx, &ctx->asm_scratch, &ctx->asm_bytes, "assembly scratch", [&](arena &m) {
         map_edit = m.take<int>((size_t)(a.total_edit_rows + a.total_out_rows) + 64);
         edit_rows = m.take<float>(a.edit_rows ? 0 : (size_t)a.total_edit_rows * a.ld);
-        recs = m.take<char>(ctx->value_f64 ? 0 : (size_t)a.total_out_rows * env_row_rec_bytes());
+        // (whatever "value_f64" says: launch_assemble runs k_row_recs / k_env_rows under either arithmetic)
+        recs = m.take<char>((size_t)a.total_out_rows * env_row_rec_bytes());
     });
     if (rc) return rc;
     if (!a.edit_rows) a.edit_rows = edit_rows;
