@@ -18,20 +18,6 @@
 constexpr int A_ROWS = 4;   // rows (waves) per workgroup
 constexpr int ES_HALO = 64; // k_env_edit: halo floats either side of the staged row (the 'es' blur has radius <= 28)
 
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // e^x for the log-domain knot lerp (|x| < 80): x log2(e) split into the rounded product and its exact remainder (one FMA for
 // the product's rounding error, one for the constant's), the hardware exp2 of the first, a first-order correction for the
 // second — six full-rate instructions, within 2 ulp of fp32 of libm's expf (~20 instructions).
@@ -777,15 +763,6 @@ __device__ __forceinline__ double mask_stage1(const float *__restrict__ m, const
     return mask_src(m, p, p.s_tail + (int)k);
 }
 
-// x / d with r = RN(1 / d) at hand: q = RN(x r), the FMA residual x - q d is exact, and RN(q + residual r) is the
-// correctly rounded quotient (Markstein 1990) for operands and quotients in the normal range — three FMAs instead of
-// the dozen instructions of the IEEE division sequence.
-__device__ __forceinline__ double div_by(double x, double d, double r)
-{
-    const double q = x * r;
-    return fma(fma(-q, d, x), r, q);
-}
-
 // 2^x in fp64 for |x| < 1000: round-to-nearest split x = n + f, |f| <= 1/2, and the degree-12 Taylor polynomial of
 // e^(f ln 2) with the powers of ln 2 folded into the coefficients (truncation 1.7e-16, Horner rounding ~2e-16 relative).
 // libm's exp2 costs 80 vector instructions per sample here (half of them moves of its table constants); the curve only
@@ -876,9 +853,7 @@ __device__ __forceinline__ void sample_assemble_one(const goofer_assembly &a, co
             f0 = base_hz;
         } else if (i >= p.fry_glide_lo && i < p.fry_glide_hi) {
             const int m = p.fry_glide_hi - p.fry_glide_lo, k = i - p.fry_glide_lo;
-            double w;                                         // np.linspace(0, 1, m) or np.linspace(1, 0, m), endpoint pinned
-            if (p.fry_dir > 0) w = m > 1 ? (k == m - 1 ? 1.0 : (double)k * (1.0 / (double)(m - 1))) : 0.0;
-            else w = m > 1 ? (k == m - 1 ? 0.0 : (double)k * (-1.0 / (double)(m - 1)) + 1.0) : 1.0;
+            const double w = p.fry_dir > 0 ? ramp_up(k, m) : ramp_down(k, m);
             f0 = (1.0 - w) * base_hz + w * f0;
         }
     }
@@ -1008,28 +983,6 @@ __global__ __launch_bounds__(256) void k_sample_assemble(const goofer_assembly a
 }
 
 // vocal fry part 1b: frames under the fry mask get their bin axis squeezed by 1 - 0.08 w   SillySampler.py:966-994
-__device__ __forceinline__ float plan_fry_mask(const goofer_note_plan &p, int64_t i)
-{
-    const int a = p.fry_a, b = p.fry_b, fade = p.fry_fade;
-    if (i < a || i >= b) return 0.f;
-    float v = 1.0f;
-    if (fade > 0) {
-        const int a1 = b < a + fade ? b : a + fade;
-        if (i < a1) {
-            const int m = a1 - a, k = (int)(i - a);
-            const double w = m > 1 ? (k == m - 1 ? 1.0 : (double)k * (1.0 / (double)(m - 1))) : 0.0;
-            v = (float)((double)v * w);
-        }
-        const int b0 = a > b - fade ? a : b - fade;
-        if (i >= b0) {
-            const int m = b - b0, k = (int)(i - b0);
-            const double w = m > 1 ? (k == m - 1 ? 0.0 : (double)k * (-1.0 / (double)(m - 1)) + 1.0) : 1.0;
-            v = (float)((double)v * w);
-        }
-    }
-    return v;
-}
-
 __global__ __launch_bounds__(256) void k_env_fry(const goofer_assembly a, int64_t total_out_rows, const int *__restrict__ row_note, int hop)
 {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -1043,7 +996,7 @@ __global__ __launch_bounds__(256) void k_env_fry(const goofer_assembly a, int64_
     const int64_t j = orow - p.env_off;
     int64_t c = j * hop + hop / 2;
     if (c > p.n_out - 1) c = p.n_out - 1;
-    const float w = plan_fry_mask(p, c);
+    const float w = fade_mask(c, p.fry_a, p.fry_b, p.fry_fade);
     if (!(w > 1e-6f)) return;
     const double sc = 1.0 - (double)w * (1.0 - 0.92);
     if (fabs(sc - 1.0) < 1e-6) return;

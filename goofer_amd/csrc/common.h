@@ -271,65 +271,6 @@ __device__ __forceinline__ int64_t reflect_index(int64_t i, int64_t n)
     return m < n ? m : period - m;
 }
 
-// note owning global frame/sample index g given CSR offsets off[0..n]: largest k with off[k] <= g.
-__device__ __forceinline__ int csr_find(const int64_t *__restrict__ off, int n, int64_t g)
-{
-    int lo = 0, hi = n;  // invariant off[lo] <= g < off[hi]
-    while (hi - lo > 1) {
-        int mid = (lo + hi) >> 1;
-        if (off[mid] <= g) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// Wave-cooperative version of csr_find for any non-decreasing key(k), k in [0, n]: all 64 lanes probe 64 evenly
-// spaced positions per round (one round of dependent loads narrows the range 64x: 2 rounds for 4096 notes instead
-// of 12 serial steps).  Every lane of the calling wave must be active; every lane gets the result.
-template <typename Key>
-__device__ __forceinline__ int wave_find(int n, int64_t g, int lane, Key key)
-{
-    int lo = 0, hi = n;                                      // invariant key(lo) <= g < key(hi)
-    while (hi - lo > 1) {
-        const int step = (hi - lo + 63) >> 6;
-        const int p = lo + (lane + 1) * step;
-        const bool le = p < hi && key(p) <= g;
-        const int c = __popcll(__ballot(le));                // probes <= g form a prefix (keys are sorted)
-        const int nhi = lo + (c + 1) * step;
-        lo += c * step;
-        if (nhi < hi) hi = nhi;
-    }
-    return lo;
-}
-
-// Kernels that tile the concatenated sample axis call this first: it finds the notes of the block's
-// first and last sample.  When they coincide (almost always: a note is ~190 blocks long) the caller
-// runs its body with that index held in an SGPR, so every per-note load behind it (offsets, params,
-// constants) is a scalar load instead of a chain of dependent per-lane vector loads.  The search itself is
-// done by the first wave cooperatively (the serial binary search used to cost ~20 dependent loads per block,
-// which bounded the short elementwise kernels).  Workgroups must be at least one full wave.
-__device__ __forceinline__ void block_note_range_last(const int64_t *__restrict__ off, int n_notes, int64_t g0, int64_t gl,
-                                                      int *s_pair, int &lo, int &hi)
-{
-    if (threadIdx.x < WAVE) {
-        const int lane = threadIdx.x;
-        auto key = [&](int k) { return off[k]; };
-        const int a = wave_find(n_notes, g0, lane, key);
-        const int b = wave_find(n_notes, gl, lane, key);
-        if (lane == 0) { s_pair[0] = a; s_pair[1] = b; }
-    }
-    __syncthreads();
-    lo = __builtin_amdgcn_readfirstlane(s_pair[0]);
-    hi = __builtin_amdgcn_readfirstlane(s_pair[1]);
-}
-
-__device__ __forceinline__ void block_note_range(const int64_t *__restrict__ off, int n_notes, int64_t g0, int64_t total,
-                                                 int *s_pair, int &lo, int &hi)
-{
-    int64_t gl = g0 + blockDim.x - 1;
-    if (gl > total - 1) gl = total - 1;
-    block_note_range_last(off, n_notes, g0, gl, s_pair, lo, hi);
-}
-
 __device__ __forceinline__ void wave_lds_sync()
 {
     // LDS ops of one wave complete in issue order; this only stops the compiler reordering
@@ -338,10 +279,23 @@ __device__ __forceinline__ void wave_lds_sync()
     __builtin_amdgcn_wave_barrier();
 }
 
+// butterfly reductions over the 64 lanes (o = 32 .. 1): every lane gets the result
 __device__ __forceinline__ float wave_max(float v)
 {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ float wave_sum(float v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ double wave_sum(double v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
 
@@ -380,3 +334,62 @@ __device__ __forceinline__ void atomic_max_pos(float *addr, float v)
 {
     atomicMax(reinterpret_cast<unsigned int *>(addr), __float_as_uint(v));
 }
+
+// x / d for a divisor whose correctly rounded reciprocal r = RN(1 / d) is at hand: q = RN(x r) is within an ulp,
+// the FMA residual x - q d is exact, and RN(q + residual r) is the correctly rounded quotient (Markstein 1990) —
+// for finite operands and a quotient in the normal range, which is where audio samples over a window sum live
+// (a zero stays a zero; a subnormal quotient may differ from the division in its last subnormal bit).  Three FMAs
+// instead of the dozen instructions of the IEEE division sequence.
+__device__ __forceinline__ float div_by(float x, float d, float r)
+{
+    const float q = x * r;
+    return fmaf(fmaf(-q, d, x), r, q);
+}
+__device__ __forceinline__ double div_by(double x, double d, double r)
+{
+    const double q = x * r;
+    return fma(fma(-q, d, x), r, q);
+}
+
+// np.linspace(0, 1, m)[k] and np.linspace(1, 0, m)[k] in fp64, 0 <= k < m: numpy's step form with the last point pinned
+__device__ __forceinline__ double ramp_up(int k, int m) { return m > 1 ? (k == m - 1 ? 1.0 : (double)k * (1.0 / (double)(m - 1))) : 0.0; }
+__device__ __forceinline__ double ramp_down(int k, int m) { return m > 1 ? (k == m - 1 ? 0.0 : (double)k * (-1.0 / (double)(m - 1)) + 1.0) : 1.0; }
+
+// 1 inside [a, b), 0 outside, with linear fades of up to `fade` samples at both ends (fp32 products of fp64 weights): the
+// vocal-fry mask of the resampler, per sample in the post chain and per frame centre in the assembly   SillySampler.py:883-934
+__device__ __forceinline__ float fade_mask(int64_t i, int a, int b, int fade)
+{
+    if (i < a || i >= b) return 0.f;
+    float v = 1.0f;
+    if (fade > 0) {
+        const int a1 = b < a + fade ? b : a + fade;
+        if (i < a1) v = (float)((double)v * ramp_up((int)(i - a), a1 - a));
+        const int b0 = a > b - fade ? a : b - fade;
+        if (i >= b0) v = (float)((double)v * ramp_down((int)(i - b0), b - b0));
+    }
+    return v;
+}
+
+// gf.create_volume_jitter(vibrato=True) before its strength and clip: a zero-phase sinusoid at `speed` Hz with a 0.1 s linear
+// fade-in (none for a note no longer than the fade), sample i of n   GOOFER.py:638-660
+__device__ __forceinline__ double vibrato_env(int64_t i, int64_t n, double sr, double speed)
+{
+    double z = sin(((2.0 * 3.141592653589793) * speed) * ((double)i / sr) + 0.0);
+    const int fade = (int)(0.1 * sr);
+    if (fade < n && i < fade) z *= ramp_up((int)i, fade);
+    return z;
+}
+
+// Read a kernel argument from the kernarg segment at the point of use.  The frame walkers keep ~40 scalars of wave state across
+// their frame loop; arguments that are only needed every 64 frames (the frame-record arrays) or once per note kept live
+// beside them pushed the compiler past the 102 SGPRs of a wave, and every overflow costs a v_writelane / v_readlane pair in
+// the loop (the noise walker carried 105 such spills).  The empty asm hides the segment pointer from the optimiser, so the
+// load cannot be hoisted back to the kernel entry; it is a scalar load from the constant cache.
+template <typename T>
+__device__ __forceinline__ T cold_arg(size_t offset)
+{
+    const char __attribute__((address_space(4))) *ka = (const char __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ka));
+    return *reinterpret_cast<const T __attribute__((address_space(4))) *>(ka + offset);
+}
+#define COLD(type, field) cold_arg<decltype(type::field)>(offsetof(type, field))

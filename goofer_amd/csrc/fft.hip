@@ -491,12 +491,9 @@ __global__ __launch_bounds__(256) void k_ola_gather(const float *__restrict__ fr
                                                     int n_notes, int64_t total_samples, int n_fft, int hop,
                                                     float *__restrict__ y, const float *__restrict__ divisor)
 {
-    __shared__ int s_pair[2];
-    const int64_t g0 = (int64_t)blockIdx.x * blockDim.x;
-    int lo_n, hi_n;
-    block_note_range(sample_off, n_notes, g0, total_samples, s_pair, lo_n, hi_n);
-    const int64_t g = g0 + threadIdx.x;
-    if (g >= total_samples) return;
+    const sample_tile<> t(sample_off, n_notes, total_samples);
+    if (!t.live) return;
+    const int64_t g = t.g;
 
     auto body = [&](int note) {
         const int64_t i = g - sample_off[note];
@@ -521,13 +518,8 @@ __global__ __launch_bounds__(256) void k_ola_gather(const float *__restrict__ fr
         }
         y[g] = out;
     };
-    if (lo_n == hi_n) {
-        body(lo_n);
-    } else {
-        int note = lo_n;
-        while (sample_off[note + 1] <= g) ++note;
-        body(note);
-    }
+    if (t.uniform()) body(t.lo);
+    else body(t.note(sample_off));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -628,10 +620,7 @@ int launch_irfft_frames(goofer_ctx *ctx, const float2 *S, int ldc, int64_t total
 int launch_ola_gather(goofer_ctx *ctx, const float *frames, const int64_t *sample_off, const int64_t *frame_off,
                       int n_notes, int64_t total_samples, float *y, const float *inv_scale, hipStream_t st)
 {
-    if (total_samples <= 0) return GOOFER_OK;
     const goofer_plan_t &p = ctx->plan;
-    hipLaunchKernelGGL(k_ola_gather, dim3((unsigned)((total_samples + 255) / 256)), dim3(256), 0, st, frames, p.win_sq,
-                       sample_off, frame_off, n_notes, total_samples, p.n_fft, p.hop, y, inv_scale);
-    LAUNCH_CHECK(ctx);
-    return GOOFER_OK;
+    return launch_per_sample(ctx, k_ola_gather, total_samples, 256, 0, st, frames, p.win_sq, sample_off, frame_off, n_notes, total_samples,
+                             p.n_fft, p.hop, y, inv_scale);
 }

@@ -31,12 +31,10 @@ __global__ __launch_bounds__(256) void k_gauss_samples(const Tin *__restrict__ i
     const int nt = 2 * radius + 1;
     const int chunk = nt < GS_CHUNK ? nt : GS_CHUNK;
     double *s_win = s_taps + chunk;                           // [256 + chunk]
-    __shared__ int s_pair[2];
-    const int64_t g0 = (int64_t)blockIdx.x * blockDim.x;
-    int lo, hi;
-    block_note_range(sample_off, n_notes, g0, total, s_pair, lo, hi);   // includes a __syncthreads
-    const int64_t g = g0 + threadIdx.x;
-    if (lo == hi) {
+    const sample_tile<> t(sample_off, n_notes, total);        // includes a __syncthreads
+    const int64_t g0 = t.g0, g = t.g;
+    const int lo = t.lo;
+    if (t.uniform()) {
         if (note_on && !note_on[lo]) return;                  // whole block: nothing to do for this note
         const int64_t base = sample_off[lo], n = sample_off[lo + 1] - base;
         const int64_t i0 = g0 - base;
@@ -57,9 +55,8 @@ __global__ __launch_bounds__(256) void k_gauss_samples(const Tin *__restrict__ i
         if (g < total) out[g] = acc;
         return;
     }
-    if (g >= total) return;
-    int note = lo;
-    while (sample_off[note + 1] <= g) ++note;
+    if (!t.live) return;
+    const int note = t.note(sample_off);
     if (note_on && !note_on[note]) return;
     const int64_t base = sample_off[note], n = sample_off[note + 1] - base, i = g - base;
     double acc = 0.0;
@@ -71,30 +68,16 @@ __global__ __launch_bounds__(256) void k_note_absmax(const double *__restrict__ 
                                                      int64_t total, const unsigned char *__restrict__ note_on,
                                                      unsigned long long *__restrict__ max_bits)
 {
-    __shared__ int s_pair[2];
-    __shared__ double s_red[4];
-    const int64_t g0 = (int64_t)blockIdx.x * blockDim.x;
-    int lo, hi;
-    block_note_range(sample_off, n_notes, g0, total, s_pair, lo, hi);
-    const int64_t g = g0 + threadIdx.x;
+    const sample_tile<> t(sample_off, n_notes, total);
     double v = 0.0;
-    int note = lo;
-    if (g < total) {
-        while (sample_off[note + 1] <= g) ++note;
-        if (!note_on || note_on[note]) v = fabs(x[g]) + 1e-6;
+    int note = t.lo;
+    if (t.live) {
+        note = t.note(sample_off);
+        if (!note_on || note_on[note]) v = fabs(x[t.g]) + 1e-6;
     }
-    if (lo == hi) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-        if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double m = fmax(fmax(s_red[0], s_red[1]), fmax(s_red[2], s_red[3]));
-            if (m > 0.0) atomicMax(max_bits + lo, (unsigned long long)__double_as_longlong(m));
-        }
-    } else if (g < total && v > 0.0) {
-        atomicMax(max_bits + note, (unsigned long long)__double_as_longlong(v));
-    }
+    note_reduce(t, note, t.live, v, [](double a, double b) { return fmax(a, b); }, [&](int k, double m) {
+        if (m > 0.0) atomicMax(max_bits + k, (unsigned long long)__double_as_longlong(m));
+    });
 }
 
 // f0 (fp32, in place) *= 1 + ((1 + noise/max*strength) - 1) * mask, evaluated in fp64 then rounded to fp32.
@@ -105,14 +88,10 @@ __global__ __launch_bounds__(256) void k_f0_jitter(float *__restrict__ f0, doubl
                                                    const unsigned long long *__restrict__ max_bits, const int64_t *__restrict__ sample_off,
                                                    int n_notes, int64_t total, const goofer_note_params *__restrict__ params, int which)
 {
-    __shared__ int s_pair[2];
-    const int64_t g0 = (int64_t)blockIdx.x * blockDim.x;
-    int lo, hi;
-    block_note_range(sample_off, n_notes, g0, total, s_pair, lo, hi);
-    const int64_t g = g0 + threadIdx.x;
-    if (g >= total) return;
-    int note = lo;
-    while (sample_off[note + 1] <= g) ++note;
+    const sample_tile<1, false> t(sample_off, n_notes, total);
+    if (!t.live) return;
+    const int64_t g = t.g;
+    const int note = t.note(sample_off);
     const double strength = which == 0 ? params[note].f0_jitter                                   // :1071 / :1080
                                        : (params[note].subharm_weight > 0.f ? params[note].subharm_f0_jitter : 0.0);
     if (!(strength > 0.0)) return;
@@ -135,22 +114,16 @@ __global__ __launch_bounds__(256) void k_volume_jitter(float *__restrict__ harm,
                                                        int n_notes, int64_t total, const goofer_note_params *__restrict__ params,
                                                        int vibrato, double speed, double sr)
 {
-    __shared__ int s_pair[2];
-    const int64_t g0 = (int64_t)blockIdx.x * blockDim.x;
-    int lo, hi;
-    block_note_range(sample_off, n_notes, g0, total, s_pair, lo, hi);
-    const int64_t g = g0 + threadIdx.x;
-    if (g >= total) return;
-    int note = lo;
-    while (sample_off[note + 1] <= g) ++note;
+    const sample_tile<1, false> t(sample_off, n_notes, total);
+    if (!t.live) return;
+    const int64_t g = t.g;
+    const int note = t.note(sample_off);
     const float sh = params[note].vol_jitter_harm, sb = params[note].vol_jitter_breath;
     if (!(sh > 0.f) && !(sb > 0.f)) return;
     double jh, jb;
-    if (vibrato) {   // volume_vibrato: zero-phase sinusoid, 0.1 s fade-in, clip [0.5, 1.5]   GOOFER.py:643-660
+    if (vibrato) {   // volume_vibrato: the vibrato envelope, clip [0.5, 1.5]   GOOFER.py:643-660
         const int64_t i = g - sample_off[note], n = sample_off[note + 1] - sample_off[note];
-        double z = sin(((2.0 * 3.141592653589793) * speed) * ((double)i / sr) + 0.0);
-        const int fade = (int)(0.1 * sr);
-        if (fade < n && i < fade) z *= fade > 1 ? (i == fade - 1 ? 1.0 : (double)i * (1.0 / (double)(fade - 1))) : 0.0;
+        const double z = vibrato_env(i, n, sr, speed);
         jh = fmin(fmax(1.0 + z * (double)sh, 0.5), 1.5);
         jb = fmin(fmax(1.0 + z * (double)sb, 0.5), 1.5);
     } else {
@@ -170,10 +143,7 @@ int launch_gauss_samples(goofer_ctx *ctx, const Tin *in, const int64_t *sample_o
     if (radius < 0) return goofer_fail(ctx, GOOFER_EINVAL, "negative gaussian radius");
     const int nt = 2 * radius + 1, chunk = nt < GS_CHUNK ? nt : GS_CHUNK;
     size_t lds = sizeof(double) * ((size_t)chunk + 256 + chunk);              // at most 36 KB
-    hipLaunchKernelGGL(k_gauss_samples<Tin>, dim3((unsigned)((total + 255) / 256)), dim3(256), lds, st, in, sample_off, n_notes, total,
-                       d_taps, radius, note_on, out);
-    LAUNCH_CHECK(ctx);
-    return GOOFER_OK;
+    return launch_per_sample(ctx, k_gauss_samples<Tin>, total, 256, lds, st, in, sample_off, n_notes, total, d_taps, radius, note_on, out);
 }
 template int launch_gauss_samples<double>(goofer_ctx *, const double *, const int64_t *, int, int64_t, const double *, int,
                                           const unsigned char *, double *, hipStream_t);
@@ -183,30 +153,20 @@ template int launch_gauss_samples<float>(goofer_ctx *, const float *, const int6
 int launch_note_absmax(goofer_ctx *ctx, const double *x, const int64_t *sample_off, int n_notes, int64_t total,
                        const unsigned char *note_on, unsigned long long *max_bits, hipStream_t st)
 {
-    if (total <= 0) return GOOFER_OK;
-    hipLaunchKernelGGL(k_note_absmax, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, x, sample_off, n_notes, total, note_on,
-                       max_bits);
-    LAUNCH_CHECK(ctx);
-    return GOOFER_OK;
+    return launch_per_sample(ctx, k_note_absmax, total, 256, 0, st, x, sample_off, n_notes, total, note_on, max_bits);
 }
 
 int launch_f0_jitter(goofer_ctx *ctx, float *f0, double *f0_64, const float *mask, const double *noise_s, const unsigned long long *max_bits,
                      const int64_t *sample_off, int n_notes, int64_t total, const goofer_note_params *params, int which, hipStream_t st)
 {
-    if (total <= 0) return GOOFER_OK;
-    hipLaunchKernelGGL(k_f0_jitter, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, f0, f0_64, mask, noise_s, max_bits, sample_off,
-                       n_notes, total, params, which);
-    LAUNCH_CHECK(ctx);
-    return GOOFER_OK;
+    return launch_per_sample(ctx, k_f0_jitter, total, 256, 0, st, f0, f0_64, mask, noise_s, max_bits, sample_off, n_notes, total, params,
+                             which);
 }
 
 int launch_volume_jitter(goofer_ctx *ctx, float *harm, float *bre, const double *nh, const double *nb, const double *vjm,
                          const unsigned long long *max_h, const unsigned long long *max_b, const int64_t *sample_off, int n_notes,
                          int64_t total, const goofer_note_params *params, int vibrato, double speed, hipStream_t st)
 {
-    if (total <= 0) return GOOFER_OK;
-    hipLaunchKernelGGL(k_volume_jitter, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, harm, bre, nh, nb, vjm, max_h, max_b,
-                       sample_off, n_notes, total, params, vibrato, speed, (double)ctx->plan.sr);
-    LAUNCH_CHECK(ctx);
-    return GOOFER_OK;
+    return launch_per_sample(ctx, k_volume_jitter, total, 256, 0, st, harm, bre, nh, nb, vjm, max_h, max_b, sample_off, n_notes, total,
+                             params, vibrato, speed, (double)ctx->plan.sr);
 }

@@ -3,6 +3,7 @@
 #pragma once
 
 #include "common.h"
+#include "ragged.h"
 
 struct onset_t;   // pulse.hip
 

@@ -54,14 +54,13 @@ __global__ __launch_bounds__(NF_THREADS) void k_normal_fill(uint64_t seed, const
                                                             uint32_t tag, const unsigned char *__restrict__ note_on,
                                                             const double *__restrict__ growl_scale, double *__restrict__ out)
 {
-    __shared__ int s_pair[2];
-    const int64_t g0 = (int64_t)blockIdx.x * NF_TILE;
+    const sample_tile<2> t(sample_off, n_notes, total);       // a lane's two samples: one pair where the note starts on an even index
+    const int64_t g0 = t.g0;
     const int64_t g1 = g0 + NF_TILE < total ? g0 + NF_TILE : total;   // the tile is [g0, g1)
-    int lo, hi;
-    block_note_range_last(sample_off, n_notes, g0, g1 - 1, s_pair, lo, hi);
+    const int lo = t.lo;
     const bool growl = growl_scale != nullptr;
     auto key_of = [&](int note) { return seed ^ ((uint64_t)params[note].seed[0] | ((uint64_t)params[note].seed[1] << 32)); };
-    if (lo == hi) {                                            // the tile lies inside one note: everything per note is scalar
+    if (t.uniform()) {                                         // the tile lies inside one note: everything per note is scalar
         if (note_on && !note_on[lo]) return;
         const int64_t base = sample_off[lo];
         const uint64_t key = key_of(lo);
@@ -75,8 +74,8 @@ __global__ __launch_bounds__(NF_THREADS) void k_normal_fill(uint64_t seed, const
     }
     // a tile over a note boundary (or short notes): each lane takes the two samples at g, g + 1 on their own where they
     // belong to different pairs
-    const int64_t g = g0 + 2 * (int64_t)threadIdx.x;
-    if (g >= g1) return;
+    const int64_t g = t.g;
+    if (!t.live) return;
     int note = lo;
     while (note + 1 < n_notes && sample_off[note + 1] <= g) ++note;
     int64_t base = sample_off[note];
@@ -94,8 +93,6 @@ int launch_normal_fill(goofer_ctx *ctx, uint64_t seed, const goofer_note_params 
                        int64_t total, int tag, const unsigned char *note_on, const double *growl_scale, double *out, hipStream_t st)
 {
     if (total <= 0 || n_notes <= 0) return GOOFER_OK;
-    hipLaunchKernelGGL(k_normal_fill, dim3((unsigned)((total + NF_TILE - 1) / NF_TILE)), dim3(NF_THREADS), 0, st, seed, params, sample_off,
-                       n_notes, total, (uint32_t)tag, note_on, growl_scale, out);
-    LAUNCH_CHECK(ctx);
-    return GOOFER_OK;
+    return launch_per_sample(ctx, k_normal_fill, total, NF_TILE, 0, st, seed, params, sample_off, n_notes, total, (uint32_t)tag, note_on,
+                             growl_scale, out);
 }

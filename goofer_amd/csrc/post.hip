@@ -162,46 +162,15 @@ int launch_onepole(goofer_ctx *ctx, const float *src, float *dst, const float *f
 
 // ---------------------------------------------------------------------------------------------
 // elementwise stages; each thread owns one sample and exits unless its note carries the flag
-#define POST_PROLOGUE()                                                                       \
-    __shared__ int s_pair[2];                                                                 \
-    const int64_t g0 = (int64_t)blockIdx.x * blockDim.x;                                      \
-    int lo_, hi_;                                                                             \
-    block_note_range(sample_off, n_notes, g0, total, s_pair, lo_, hi_);                       \
-    const int64_t g = g0 + threadIdx.x;                                                       \
-    if (g >= total) return;                                                                   \
-    int note = lo_;                                                                           \
-    while (sample_off[note + 1] <= g) ++note;                                                 \
-    const goofer_post_note pn = notes[note];                                                  \
-    const int64_t i = g - sample_off[note];                                                   \
-    (void)i
-
-__device__ __forceinline__ float fry_mask_at(const goofer_post_note &pn, int64_t i)
-{
-    const int a = pn.fry_a, b = pn.fry_b, fade = pn.fry_fade;
-    if (i < a || i >= b) return 0.f;
-    float v = 1.0f;
-    if (fade > 0) {
-        const int a1 = b < a + fade ? b : a + fade;
-        if (i < a1) {
-            const int m = a1 - a, k = (int)(i - a);
-            const double w = m > 1 ? (k == m - 1 ? 1.0 : (double)k * (1.0 / (double)(m - 1))) : 0.0;   // np.linspace(0, 1, m)
-            v = (float)((double)v * w);
-        }
-        const int b0 = a > b - fade ? a : b - fade;
-        if (i >= b0) {
-            const int m = b - b0, k = (int)(i - b0);
-            const double w = m > 1 ? (k == m - 1 ? 0.0 : (double)k * (-1.0 / (double)(m - 1)) + 1.0) : 1.0;   // np.linspace(1, 0, m)
-            v = (float)((double)v * w);
-        }
-    }
-    return v;
-}
-
 __global__ __launch_bounds__(256) void k_post_layers(float *__restrict__ harm, const float *__restrict__ su, const float *__restrict__ sj,
                                                      const goofer_post_note *__restrict__ notes, const int64_t *__restrict__ sample_off,
                                                      int n_notes, int64_t total)
 {
-    POST_PROLOGUE();
+    const sample_tile<1, false> t(sample_off, n_notes, total);
+    if (!t.live) return;
+    const int note = t.note(sample_off);
+    const goofer_post_note pn = notes[note];
+    const int64_t g = t.g, i = g - sample_off[note];
     if (pn.su_off < 0 && pn.sj_off < 0) return;
     float h = harm[g];
     if (pn.su_off >= 0) h = h + su[pn.su_off + i] * pn.su_gain;                               // :1059
@@ -213,9 +182,13 @@ __global__ __launch_bounds__(256) void k_post_fry(float *__restrict__ harm, floa
                                                   const float *__restrict__ bre_hp, const goofer_post_note *__restrict__ notes,
                                                   const int64_t *__restrict__ sample_off, int n_notes, int64_t total)
 {
-    POST_PROLOGUE();
+    const sample_tile<1, false> t(sample_off, n_notes, total);
+    if (!t.live) return;
+    const int note = t.note(sample_off);
+    const goofer_post_note pn = notes[note];
+    const int64_t g = t.g, i = g - sample_off[note];
     if (pn.fry_a >= pn.fry_b) return;
-    const float m = fry_mask_at(pn, i);
+    const float m = fade_mask(i, pn.fry_a, pn.fry_b, pn.fry_fade);
     harm[g] = harm[g] * (1.0f - m) + harm_hp[g] * m;                                          // :1097-1098
     bre[g] = bre[g] * (1.0f - m) + bre_hp[g] * m;
 }
@@ -224,13 +197,15 @@ __global__ __launch_bounds__(256) void k_post_sd(float *__restrict__ bre, const 
                                                  const goofer_post_note *__restrict__ notes, const int64_t *__restrict__ sample_off,
                                                  int n_notes, int64_t total, double sr)
 {
-    POST_PROLOGUE();
+    const sample_tile<1, false> t(sample_off, n_notes, total);
+    if (!t.live) return;
+    const int note = t.note(sample_off);
+    const goofer_post_note pn = notes[note];
+    const int64_t g = t.g, i = g - sample_off[note];
     if (!(pn.sd_strength > 0.f)) return;
     const int64_t n = sample_off[note + 1] - sample_off[note];
-    // gf.create_volume_jitter(vibrato=True): zero-phase 150 Hz sinusoid, 0.1 s fade-in, clip [0.5, 1.5]   GOOFER.py:638-660
-    double z = sin(((2.0 * 3.141592653589793) * 150.0) * ((double)i / sr) + 0.0);
-    const int fade = (int)(0.1 * sr);
-    if (fade < n && i < fade) z *= fade > 1 ? (i == fade - 1 ? 1.0 : (double)i * (1.0 / (double)(fade - 1))) : 0.0;
+    // gf.create_volume_jitter(vibrato=True) at 150 Hz, clip [0.5, 1.5]   GOOFER.py:638-660
+    const double z = vibrato_env(i, n, sr, 150.0);
     double env = 1.0 + z * ((double)pn.sd_strength / 200.0);
     env = fmin(fmax(env, 0.5), 1.5);
     float b = (float)((double)bre[g] * (1.0 + (env - 1.0) * vmask_s[g]));                     // :1110
@@ -242,51 +217,45 @@ __global__ __launch_bounds__(256) void k_note_sumsq(const float *__restrict__ ha
                                                     const goofer_post_note *__restrict__ notes, const int64_t *__restrict__ sample_off,
                                                     int n_notes, int64_t total, double *__restrict__ sums)
 {
-    __shared__ int s_pair[2];
-    __shared__ double s_red[4];
-    const int64_t g0 = (int64_t)blockIdx.x * blockDim.x;
-    int lo, hi;
-    block_note_range(sample_off, n_notes, g0, total, s_pair, lo, hi);
-    const int64_t g = g0 + threadIdx.x;
+    const sample_tile<> t(sample_off, n_notes, total);
     double v = 0.0;
-    int note = lo;
-    if (g < total) {
-        while (sample_off[note + 1] <= g) ++note;
+    int note = t.lo;
+    if (t.live) {
+        note = t.note(sample_off);
         if (notes[note].tension != 0.f) {
-            const float s = harm[g] + bre[g];
+            const float s = harm[t.g] + bre[t.g];
             v = (double)s * (double)s;
         }
     }
-    if (lo == hi) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-        if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const double t = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
-            if (t != 0.0) atomicAdd(sums + lo, t);
-        }
-    } else if (g < total && v != 0.0) {
-        atomicAdd(sums + note, v);
-    }
+    note_reduce(t, note, t.live, v, [](double a, double b) { return a + b; }, [&](int k, double sum) {
+        if (sum != 0.0) atomicAdd(sums + k, sum);
+    });
 }
 
 __global__ __launch_bounds__(256) void k_post_tension(float *__restrict__ harm, float *__restrict__ bre, const float *__restrict__ harm_hp,
                                                       const goofer_post_note *__restrict__ notes, const int64_t *__restrict__ sample_off,
                                                       int n_notes, int64_t total)
 {
-    POST_PROLOGUE();
+    const sample_tile<1, false> t(sample_off, n_notes, total);
+    if (!t.live) return;
+    const int note = t.note(sample_off);
+    const goofer_post_note pn = notes[note];
+    const int64_t g = t.g;
     if (!(pn.tension > 0.f)) return;
-    const float t = pn.tension;
-    harm[g] = harm[g] + harm_hp[g] * (float)(1.0 + (double)t * 20.0);                         // :1130-1131
-    bre[g] = bre[g] * (float)(1.0 - (double)t);                                              // :1135
+    const float ten = pn.tension;
+    harm[g] = harm[g] + harm_hp[g] * (float)(1.0 + (double)ten * 20.0);                       // :1130-1131
+    bre[g] = bre[g] * (float)(1.0 - (double)ten);                                            // :1135
 }
 
 __global__ __launch_bounds__(256) void k_post_scale(float *__restrict__ harm, float *__restrict__ bre, const double *__restrict__ before,
                                                     const double *__restrict__ after, const goofer_post_note *__restrict__ notes,
                                                     const int64_t *__restrict__ sample_off, int n_notes, int64_t total)
 {
-    POST_PROLOGUE();
+    const sample_tile<1, false> t(sample_off, n_notes, total);
+    if (!t.live) return;
+    const int note = t.note(sample_off);
+    const goofer_post_note pn = notes[note];
+    const int64_t g = t.g;
     if (pn.tension == 0.f) return;
     const double n = (double)(sample_off[note + 1] - sample_off[note]);
     const double r0 = sqrt(before[note] / n + 1e-12), r1 = sqrt(after[note] / n + 1e-12);   // gf.rms   GOOFER.py:171
@@ -302,7 +271,11 @@ __global__ __launch_bounds__(256) void k_post_mix(const float *__restrict__ harm
                                                   const unsigned char *__restrict__ note_on, const goofer_note_params *__restrict__ params,
                                                   const int64_t *__restrict__ sample_off, int n_notes, int64_t total, float *__restrict__ mix)
 {
-    POST_PROLOGUE();
+    const sample_tile<1, false> t(sample_off, n_notes, total);
+    if (!t.live) return;
+    const int note = t.note(sample_off);
+    const goofer_post_note pn = notes[note];
+    const int64_t g = t.g, i = g - sample_off[note];
     if (!note_on[note]) return;
     const goofer_note_params p = params[note];
     float o = ((harm[g] * p.mix_harm + bre[g] * p.mix_breath) + uv[g] * p.mix_unvoiced) * p.volume;    // :1142-1151
@@ -387,7 +360,11 @@ __global__ __launch_bounds__(256) void k_dyn_gain(const double *__restrict__ ben
                                                   const int64_t *__restrict__ sample_off, int n_notes, int64_t total,
                                                   double *__restrict__ dyn)
 {
-    POST_PROLOGUE();
+    const sample_tile<1, false> t(sample_off, n_notes, total);
+    if (!t.live) return;
+    const int note = t.note(sample_off);
+    const goofer_post_note pn = notes[note];
+    const int64_t g = t.g;
     if (pn.pitch_dyn == 0.f) return;
     const double r = ref[note] + 1e-8;
     double v = bend_s[g] / r;
@@ -400,64 +377,48 @@ __global__ __launch_bounds__(256) void k_dyn_gain(const double *__restrict__ ben
 }
 
 // ---------------------------------------------------------------------------------------------
-#define ELEMENTWISE_GRID dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st
-
 int launch_post_layers(goofer_ctx *ctx, float *harm, const float *su, const float *sj, const goofer_post_note *notes,
                        const int64_t *sample_off, int n_notes, int64_t total, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_post_layers, ELEMENTWISE_GRID, harm, su, sj, notes, sample_off, n_notes, total);
-    LAUNCH_CHECK(ctx);
-    return GOOFER_OK;
+    return launch_per_sample(ctx, k_post_layers, total, 256, 0, st, harm, su, sj, notes, sample_off, n_notes, total);
 }
 
 int launch_post_fry(goofer_ctx *ctx, float *harm, float *bre, const float *harm_hp, const float *bre_hp, const goofer_post_note *notes,
                     const int64_t *sample_off, int n_notes, int64_t total, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_post_fry, ELEMENTWISE_GRID, harm, bre, harm_hp, bre_hp, notes, sample_off, n_notes, total);
-    LAUNCH_CHECK(ctx);
-    return GOOFER_OK;
+    return launch_per_sample(ctx, k_post_fry, total, 256, 0, st, harm, bre, harm_hp, bre_hp, notes, sample_off, n_notes, total);
 }
 
 int launch_post_sd(goofer_ctx *ctx, float *bre, const double *vmask_s, const goofer_post_note *notes, const int64_t *sample_off,
                    int n_notes, int64_t total, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_post_sd, ELEMENTWISE_GRID, bre, vmask_s, notes, sample_off, n_notes, total, (double)ctx->plan.sr);
-    LAUNCH_CHECK(ctx);
-    return GOOFER_OK;
+    return launch_per_sample(ctx, k_post_sd, total, 256, 0, st, bre, vmask_s, notes, sample_off, n_notes, total, (double)ctx->plan.sr);
 }
 
 int launch_note_sumsq(goofer_ctx *ctx, const float *harm, const float *bre, const goofer_post_note *notes, const int64_t *sample_off,
                       int n_notes, int64_t total, double *sums, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_note_sumsq, ELEMENTWISE_GRID, harm, bre, notes, sample_off, n_notes, total, sums);
-    LAUNCH_CHECK(ctx);
-    return GOOFER_OK;
+    return launch_per_sample(ctx, k_note_sumsq, total, 256, 0, st, harm, bre, notes, sample_off, n_notes, total, sums);
 }
 
 int launch_post_tension(goofer_ctx *ctx, float *harm, float *bre, const float *harm_hp, const goofer_post_note *notes,
                         const int64_t *sample_off, int n_notes, int64_t total, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_post_tension, ELEMENTWISE_GRID, harm, bre, harm_hp, notes, sample_off, n_notes, total);
-    LAUNCH_CHECK(ctx);
-    return GOOFER_OK;
+    return launch_per_sample(ctx, k_post_tension, total, 256, 0, st, harm, bre, harm_hp, notes, sample_off, n_notes, total);
 }
 
 int launch_post_scale(goofer_ctx *ctx, float *harm, float *bre, const double *before, const double *after,
                       const goofer_post_note *notes, const int64_t *sample_off, int n_notes, int64_t total, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_post_scale, ELEMENTWISE_GRID, harm, bre, before, after, notes, sample_off, n_notes, total);
-    LAUNCH_CHECK(ctx);
-    return GOOFER_OK;
+    return launch_per_sample(ctx, k_post_scale, total, 256, 0, st, harm, bre, before, after, notes, sample_off, n_notes, total);
 }
 
 int launch_post_mix(goofer_ctx *ctx, const float *harm, const float *uv, const float *bre, const float *sa_uv, const float *sa_bre,
                     const double *dyn, const goofer_post_note *notes, const unsigned char *note_on, const goofer_note_params *params,
                     const int64_t *sample_off, int n_notes, int64_t total, float *mix, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_post_mix, ELEMENTWISE_GRID, harm, uv, bre, sa_uv, sa_bre, dyn, notes, note_on, params, sample_off, n_notes,
-                       total, mix);
-    LAUNCH_CHECK(ctx);
-    return GOOFER_OK;
+    return launch_per_sample(ctx, k_post_mix, total, 256, 0, st, harm, uv, bre, sa_uv, sa_bre, dyn, notes, note_on, params, sample_off, n_notes,
+                             total, mix);
 }
 
 int launch_dyn_gain(goofer_ctx *ctx, const double *bend_s, const double *vmask_s, const unsigned char *note_on, double *ref,
@@ -465,9 +426,7 @@ int launch_dyn_gain(goofer_ctx *ctx, const double *bend_s, const double *vmask_s
 {
     hipLaunchKernelGGL(k_percentile95, dim3(n_notes), dim3(256), 0, st, bend_s, sample_off, note_on, ref);
     LAUNCH_CHECK(ctx);
-    hipLaunchKernelGGL(k_dyn_gain, ELEMENTWISE_GRID, bend_s, vmask_s, ref, notes, sample_off, n_notes, total, dyn);
-    LAUNCH_CHECK(ctx);
-    return GOOFER_OK;
+    return launch_per_sample(ctx, k_dyn_gain, total, 256, 0, st, bend_s, vmask_s, ref, notes, sample_off, n_notes, total, dyn);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -852,14 +852,10 @@ __global__ __launch_bounds__(256) void k_subharm_inc(const float *__restrict__ f
                                                      const goofer_note_params *__restrict__ params, sub_cfg c,
                                                      double *__restrict__ fm, double *__restrict__ inc)
 {
-    __shared__ int s_pair[2];
-    const int64_t g0 = (int64_t)blockIdx.x * blockDim.x;
-    int lo, hi;
-    block_note_range(sample_off, n_notes, g0, total, s_pair, lo, hi);
-    const int64_t g = g0 + threadIdx.x;
-    if (g >= total) return;
-    int note = lo;
-    while (sample_off[note + 1] <= g) ++note;
+    const sample_tile<1, false> t(sample_off, n_notes, total);
+    if (!t.live) return;
+    const int64_t g = t.g;
+    const int note = t.note(sample_off);
     if (!(params[note].subharm_weight > 0.f)) { inc[g] = 0.0; fm[g] = 0.0; return; }
     const int64_t base = sample_off[note], n = sample_off[note + 1] - base, i = g - base;
     // the f0 array the layer tracks is float32 in the reference (modulated_f0 = f0_interp.copy() keeps the type, :763-764) —
@@ -868,8 +864,7 @@ __global__ __launch_bounds__(256) void k_subharm_inc(const float *__restrict__ f
     if (c.vib_on && f > 0.0) {
         double v = sin(((2.0 * 3.141592653589793) * c.vib_rate) * ((double)i / c.sr) + 0.0);
         if (c.vib_fade < n && i < c.vib_fade) {
-            const double fade = c.vib_fade > 1 ? (i >= c.vib_fade - 1 ? 1.0 : (double)i * (1.0 / (double)(c.vib_fade - 1))) : 0.0;
-            v *= fade;
+            v *= ramp_up((int)i, c.vib_fade);
         }
         f = f * (1.0 + v * c.vib_depth);
         if (!f0_64) f = (double)(float)f;
@@ -940,14 +935,10 @@ __global__ __launch_bounds__(256) void k_subharm_place(const onset_t *__restrict
 {
     // several ratios (a list of subharm_semitones): each has its own event list; the pulses of all of them are summed
     // (accumulate), and the voicing mask and the joint maximum are applied once, after the last one
-    __shared__ int s_pair[2];
-    const int64_t g0 = (int64_t)blockIdx.x * blockDim.x;
-    int lo_n, hi_n;
-    block_note_range(sample_off, n_notes, g0, total, s_pair, lo_n, hi_n);
-    const int64_t g = g0 + threadIdx.x;
-    if (g >= total) return;
-    int note = lo_n;
-    while (sample_off[note + 1] <= g) ++note;
+    const sample_tile<1, false> t(sample_off, n_notes, total);
+    if (!t.live) return;
+    const int64_t g = t.g;
+    const int note = t.note(sample_off);
     if (!(params[note].subharm_weight > 0.f)) return;
     const int64_t base = sample_off[note];
     const int32_t j = (int32_t)(g - base);
@@ -980,14 +971,10 @@ __global__ __launch_bounds__(256) void k_subharm_add(float *__restrict__ pulse, 
                                                      const int64_t *__restrict__ sample_off, int n_notes, int64_t total,
                                                      const goofer_note_params *__restrict__ params)
 {
-    __shared__ int s_pair[2];
-    const int64_t g0 = (int64_t)blockIdx.x * blockDim.x;
-    int lo, hi;
-    block_note_range(sample_off, n_notes, g0, total, s_pair, lo, hi);
-    const int64_t g = g0 + threadIdx.x;
-    if (g >= total) return;
-    int note = lo;
-    while (sample_off[note + 1] <= g) ++note;
+    const sample_tile<1, false> t(sample_off, n_notes, total);
+    if (!t.live) return;
+    const int64_t g = t.g;
+    const int note = t.note(sample_off);
     const float w = params[note].subharm_weight;
     if (!(w > 0.f)) return;
     double v = sub[g];
@@ -1004,14 +991,13 @@ int launch_subharm(goofer_ctx *ctx, const float *f0s, const double *f0_64, const
                    hipStream_t st)
 {
     if (total <= 0 || n_notes <= 0 || n_ratios <= 0) return GOOFER_OK;
-    const unsigned nb = (unsigned)((total + 255) / 256);
     for (int ri = 0; ri < n_ratios; ++ri) {
         sub_cfg c;
         c.ratio = ratios[ri]; c.vib_rate = vib_rate; c.vib_depth = vib_depth; c.vib_on = vib_on;
         c.sr = (double)ctx->plan.sr;
         c.vib_fade = (int)(vib_delay * c.sr);
-        hipLaunchKernelGGL(k_subharm_inc, dim3(nb), dim3(256), 0, st, f0s, f0_64, mask, sample_off, n_notes, total, params, c, fm, inc);
-        LAUNCH_CHECK(ctx);
+        if (int rc = launch_per_sample(ctx, k_subharm_inc, total, 256, 0, st, f0s, f0_64, mask, sample_off, n_notes, total, params, c, fm, inc))
+            return rc;
         {
             const int blocks = (n_notes + 3) / 4;
             const size_t lds = walk_lds_request(blocks, 4 * 2 * OC * sizeof(double) + 4 * WAVE * sizeof(int32_t), 0);   // tiles + event queues
@@ -1022,11 +1008,9 @@ int launch_subharm(goofer_ctx *ctx, const float *f0s, const double *f0_64, const
         }
         hipLaunchKernelGGL(k_subharm_finish, dim3(n_notes), dim3(64), 0, st, fm, sample_off, n_notes, c, onset_idx, onset_cnt, inc, onsets);
         LAUNCH_CHECK(ctx);
-        hipLaunchKernelGGL(k_subharm_place, dim3(nb), dim3(256), 0, st, onsets, onset_cnt, mask, sample_off, n_notes, total, params, sub,
-                           max_bits, ri > 0 ? 1 : 0, ri == n_ratios - 1 ? 1 : 0);
-        LAUNCH_CHECK(ctx);
+        if (int rc = launch_per_sample(ctx, k_subharm_place, total, 256, 0, st, onsets, onset_cnt, mask, sample_off, n_notes, total, params,
+                                       sub, max_bits, ri > 0 ? 1 : 0, ri == n_ratios - 1 ? 1 : 0))
+            return rc;
     }
-    hipLaunchKernelGGL(k_subharm_add, dim3(nb), dim3(256), 0, st, pulse, sub, max_bits, sample_off, n_notes, total, params);
-    LAUNCH_CHECK(ctx);
-    return GOOFER_OK;
+    return launch_per_sample(ctx, k_subharm_add, total, 256, 0, st, pulse, sub, max_bits, sample_off, n_notes, total, params);
 }

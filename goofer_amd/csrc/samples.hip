@@ -123,13 +123,8 @@ __global__ __launch_bounds__(256) void k_ola3_gains(const float *__restrict__ fr
                                                     float *__restrict__ harm, float *__restrict__ uv, float *__restrict__ bre,
                                                     float *__restrict__ note_peak)
 {
-    __shared__ int s_pair[2];
-    __shared__ float s_red[4];
-    const int64_t g0 = (int64_t)blockIdx.x * blockDim.x;
-    int lo_n, hi_n;
-    block_note_range(sample_off, n_notes, g0, total_samples, s_pair, lo_n, hi_n);
-    const int64_t g = g0 + threadIdx.x;
-    const bool live = g < total_samples;
+    const sample_tile<> t(sample_off, n_notes, total_samples);
+    const int64_t g = t.g;
 
     auto body = [&](int note) -> float {
         const int64_t base = sample_off[note], n = sample_off[note + 1] - base;
@@ -164,17 +159,10 @@ __global__ __launch_bounds__(256) void k_ola3_gains(const float *__restrict__ fr
         bre[g] = b;
         return fabsf((h + u) + b);
     };
-    if (lo_n == hi_n) {
-        float pk = live ? body(lo_n) : 0.f;
-        pk = wave_max(pk);
-        if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = pk;
-        __syncthreads();
-        if (threadIdx.x == 0) atomic_max_pos(note_peak + lo_n, fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3])));
-    } else if (live) {
-        int note = lo_n;
-        while (sample_off[note + 1] <= g) ++note;
-        atomic_max_pos(note_peak + note, body(note));
-    }
+    // (the body twice, so that the uniform tile's runs on a scalar note index)
+    const int note = t.live && !t.uniform() ? t.note(sample_off) : t.lo;
+    const float pk = !t.live ? 0.f : (t.uniform() ? body(t.lo) : body(note));
+    note_reduce(t, note, t.live, pk, [](float a, float b) { return fmaxf(a, b); }, [&](int k, float m) { atomic_max_pos(note_peak + k, m); });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -516,15 +504,6 @@ struct ola1_args {
     const float *g_win;
     const unsigned char *frame_skip;
 };
-template <typename T>
-__device__ __forceinline__ T ola1_cold(size_t offset)
-{
-    const char __attribute__((address_space(4))) *ka = (const char __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(ka));
-    return *reinterpret_cast<const T __attribute__((address_space(4))) *>(ka + offset);
-}
-#define OCOLD(field) ola1_cold<decltype(ola1_args::field)>(offsetof(ola1_args, field))
-
 template <int M, int WPB>
 __global__ __launch_bounds__(64 * WPB, 2) void k_irfft_ola1(const ola1_args A)
 {
@@ -538,7 +517,7 @@ __global__ __launch_bounds__(64 * WPB, 2) void k_irfft_ola1(const ola1_args A)
     float *win = reinterpret_cast<float *>(bufs + WPB * BUF);
     float *rings = win + NF;
     double *knots = reinterpret_cast<double *>(rings + (size_t)WPB * NF);
-    load_tables<M>(tw, twh, win, OCOLD(g_tw), OCOLD(g_twh), OCOLD(g_win));
+    load_tables<M>(tw, twh, win, COLD(ola1_args, g_tw), COLD(ola1_args, g_twh), COLD(ola1_args, g_win));
 
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     float2 *buf = bufs + wave * BUF;
@@ -549,8 +528,8 @@ __global__ __launch_bounds__(64 * WPB, 2) void k_irfft_ola1(const ola1_args A)
     // waves only idled beside the others.
     const int stem = (int)(blockIdx.x % 3);                   // workgroup-uniform
     const int64_t f0 = ((int64_t)(blockIdx.x / 3) * WPB + wave) * run;
-    if (f0 >= OCOLD(total_frames)) return;                    // no block barrier below
-    const unsigned skip_bit = OCOLD(frame_skip) ? (unsigned)stem : 0u;   // bit 0 (1): unvoiced stem, bit 1 (2): breath stem; harmonic: never
+    if (f0 >= COLD(ola1_args, total_frames)) return;                    // no block barrier below
+    const unsigned skip_bit = COLD(ola1_args, frame_skip) ? (unsigned)stem : 0u;   // bit 0 (1): unvoiced stem, bit 1 (2): breath stem; harmonic: never
     // the skip bits of 64 consecutive frames as one ballot (a byte load per frame would sit on the loop's critical path)
     uint64_t skip_mask = 0;
     int64_t skip_base = -(int64_t)WAVE;
@@ -559,19 +538,19 @@ __global__ __launch_bounds__(64 * WPB, 2) void k_irfft_ola1(const ola1_args A)
         if (f >= skip_base + WAVE || f < skip_base) {
             skip_base = f;
             const int64_t g = f + lane;
-            skip_mask = __ballot(g < OCOLD(total_frames) && (OCOLD(frame_skip)[g] & skip_bit) != 0);
+            skip_mask = __ballot(g < COLD(ola1_args, total_frames) && (COLD(ola1_args, frame_skip)[g] & skip_bit) != 0);
         }
         return ((skip_mask >> (int)(f - skip_base)) & 1ull) != 0;
     };
-    const int64_t f1 = f0 + run < OCOLD(total_frames) ? f0 + run : OCOLD(total_frames);
+    const int64_t f1 = f0 + run < COLD(ola1_args, total_frames) ? f0 + run : COLD(ola1_args, total_frames);
     const float inv_m = 0.5f / (float)M;                     // 1/M of the transform and the 1/2 of the input stage (irfft_pre)
     const float2 *S = stem == 0 ? A.S_h : (stem == 1 ? A.S_u : A.S_b);
-    float *out = stem == 0 ? OCOLD(harm) : (stem == 1 ? OCOLD(uv) : OCOLD(bre));
+    float *out = stem == 0 ? COLD(ola1_args, harm) : (stem == 1 ? COLD(ola1_args, uv) : COLD(ola1_args, bre));
 
     int64_t fs = f0;
     {
         const int nt = frame_note[f0];
-        const int64_t t0 = f0 - OCOLD(frame_off)[nt];
+        const int64_t t0 = f0 - COLD(ola1_args, frame_off)[nt];
         fs = f0 - (t0 < halo ? t0 : halo);
     }
     // spectrum row of the next frame, fetched during the transform: bins lane + 64 r and the Nyquist bin; the mirrored bins
@@ -674,20 +653,20 @@ __global__ __launch_bounds__(64 * WPB, 2) void k_irfft_ola1(const ola1_args A)
         const int nt = frame_note[f];
         if (nt != note) {
             note = nt;
-            const int64_t *sample_off = OCOLD(sample_off), *frame_off = OCOLD(frame_off);
+            const int64_t *sample_off = COLD(ola1_args, sample_off), *frame_off = COLD(ola1_args, frame_off);
             base = sample_off[note];
             n = (int)(sample_off[note + 1] - base);
             fbase = frame_off[note];
             T = (int)(frame_off[note + 1] - fbase);
             ns = (n + MASK_DS - 1) / MASK_DS;
             out_len = hop * (T - 1);
-            const goofer_note_params *params = OCOLD(params);
-            const double *steps = OCOLD(steps);
+            const goofer_note_params *params = COLD(ola1_args, params);
+            const double *steps = COLD(ola1_args, steps);
             gain = stem == 1 ? params[note].uv_strength : params[note].breath_strength;
             step_n = steps[2 * note];
             step_s = steps[2 * note + 1];
             kps = n > 1 ? (float)(ns - 1) / (float)(n - 1) : 0.f;
-            ss = OCOLD(short_s) + short_base(sample_off, note);
+            ss = COLD(ola1_args, short_s) + short_base(sample_off, note);
         }
         const int t = (int)(f - fbase);
         const int shift = (t * hop) & (NF - 1);
@@ -936,14 +915,10 @@ __global__ __launch_bounds__(256) void k_mask_upsample(const double *__restrict_
                                                        int n_notes, int64_t total_samples, const double *__restrict__ steps, int fast,
                                                        float *__restrict__ out)
 {
-    __shared__ int s_pair[2];
-    const int64_t g0 = (int64_t)blockIdx.x * blockDim.x;
-    int lo, hi;
-    block_note_range(sample_off, n_notes, g0, total_samples, s_pair, lo, hi);
-    const int64_t g = g0 + threadIdx.x;
-    if (g >= total_samples) return;
-    int note = lo;
-    while (sample_off[note + 1] <= g) ++note;
+    const sample_tile<1, false> t(sample_off, n_notes, total_samples);
+    if (!t.live) return;
+    const int64_t g = t.g;
+    const int note = t.note(sample_off);
     const int64_t base = sample_off[note], n = sample_off[note + 1] - base;
     const int64_t ns = (n + MASK_DS - 1) / MASK_DS;
     const double *ss = short_s + short_base(sample_off, note);
@@ -962,10 +937,8 @@ int launch_mask_upsample(goofer_ctx *ctx, const double *short_s, const int64_t *
     if (total_samples <= 0) return GOOFER_OK;
     hipLaunchKernelGGL(k_note_steps, dim3((n_notes + 255) / 256), dim3(256), 0, st, sample_off, n_notes, steps);
     LAUNCH_CHECK(ctx);
-    hipLaunchKernelGGL(k_mask_upsample, dim3((unsigned)((total_samples + 255) / 256)), dim3(256), 0, st, short_s, sample_off, n_notes,
-                       total_samples, steps, fast ? 1 : 0, out);
-    LAUNCH_CHECK(ctx);
-    return GOOFER_OK;
+    return launch_per_sample(ctx, k_mask_upsample, total_samples, 256, 0, st, short_s, sample_off, n_notes, total_samples, steps,
+                             fast ? 1 : 0, out);
 }
 
 int launch_irfft_ola3(goofer_ctx *ctx, const float2 *S_h, const float2 *S_u, const float2 *S_b, int ldc, int64_t total_frames,
@@ -992,16 +965,10 @@ __global__ __launch_bounds__(256) void k_apply_gain(float *__restrict__ harm, fl
                                                     const goofer_note_params *__restrict__ params, const float *__restrict__ note_peak,
                                                     int write_stems)
 {
-    __shared__ int s_pair[2];
-    const int64_t g0 = (int64_t)blockIdx.x * (blockDim.x * SPT);
-    int lo, hi;
-    {
-        int64_t gl = g0 + (int64_t)blockDim.x * SPT - 1;
-        if (gl > total_samples - 1) gl = total_samples - 1;
-        block_note_range_last(sample_off, n_notes, g0, gl, s_pair, lo, hi);
-    }
-    const int64_t g = g0 + (int64_t)threadIdx.x * SPT;
-    if (g >= total_samples) return;
+    const sample_tile<SPT> t(sample_off, n_notes, total_samples);
+    if (!t.live) return;
+    const int64_t g = t.g;
+    const int lo = t.lo;
 
     auto gain_of = [&](int note) -> float {
         const float peak = note_peak[note] + 1e-12f;                 // fp32 add, like np.float32 + 1e-12
@@ -1010,7 +977,7 @@ __global__ __launch_bounds__(256) void k_apply_gain(float *__restrict__ harm, fl
     auto mixdown = [&](int note, float h, float u, float b) -> float {
         return ((h * params[note].mix_harm + b * params[note].mix_breath) + u * params[note].mix_unvoiced) * params[note].volume;
     };
-    if (lo == hi && g + SPT <= total_samples) {
+    if (t.uniform() && g + SPT <= total_samples) {
         const float gain = gain_of(lo);
         float4 h = *reinterpret_cast<const float4 *>(harm + g);
         float4 u = *reinterpret_cast<const float4 *>(uv + g);
@@ -1033,8 +1000,7 @@ __global__ __launch_bounds__(256) void k_apply_gain(float *__restrict__ harm, fl
     for (int k = 0; k < SPT; ++k) {
         const int64_t gi = g + k;
         if (gi >= total_samples) break;
-        int note = lo;
-        while (sample_off[note + 1] <= gi) ++note;
+        const int note = t.note(sample_off, gi);
         const float gain = gain_of(note);
         float h = harm[gi], u = uv[gi], b = bre[gi];
         const float comb = (h + u) + b;
@@ -1050,33 +1016,17 @@ __global__ __launch_bounds__(256) void k_stem_peak(const float *__restrict__ har
                                                    const int64_t *__restrict__ sample_off, int n_notes, int64_t total,
                                                    float *__restrict__ note_peak)
 {
-    __shared__ int s_pair[2];
-    __shared__ float s_red[4];
-    const int64_t g0 = (int64_t)blockIdx.x * blockDim.x;
-    int lo, hi;
-    block_note_range(sample_off, n_notes, g0, total, s_pair, lo, hi);
-    const int64_t g = g0 + threadIdx.x;
-    float pk = g < total ? fabsf((harm[g] + uv[g]) + bre[g]) : 0.f;
-    if (lo == hi) {
-        pk = wave_max(pk);
-        if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = pk;
-        __syncthreads();
-        if (threadIdx.x == 0) atomic_max_pos(note_peak + lo, fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3])));
-    } else if (g < total) {
-        int note = lo;
-        while (sample_off[note + 1] <= g) ++note;
-        atomic_max_pos(note_peak + note, pk);
-    }
+    const sample_tile<> t(sample_off, n_notes, total);
+    const int64_t g = t.g;
+    const float pk = t.live ? fabsf((harm[g] + uv[g]) + bre[g]) : 0.f;
+    const int note = t.live && !t.uniform() ? t.note(sample_off) : t.lo;
+    note_reduce(t, note, t.live, pk, [](float a, float b) { return fmaxf(a, b); }, [&](int k, float m) { atomic_max_pos(note_peak + k, m); });
 }
 
 int launch_stem_peak(goofer_ctx *ctx, const float *harm, const float *uv, const float *bre, const int64_t *sample_off, int n_notes,
                      int64_t total, float *note_peak, hipStream_t st)
 {
-    if (total <= 0) return GOOFER_OK;
-    hipLaunchKernelGGL(k_stem_peak, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, harm, uv, bre, sample_off, n_notes, total,
-                       note_peak);
-    LAUNCH_CHECK(ctx);
-    return GOOFER_OK;
+    return launch_per_sample(ctx, k_stem_peak, total, 256, 0, st, harm, uv, bre, sample_off, n_notes, total, note_peak);
 }
 
 int launch_mask_short(goofer_ctx *ctx, const float *mask, const int64_t *sample_off, int n_notes, int64_t total_samples,
@@ -1095,11 +1045,8 @@ int launch_apply_gain(goofer_ctx *ctx, float *harm, float *uv, float *bre, float
                       int n_notes, int64_t total_samples, const goofer_note_params *params, const float *note_peak, bool write_stems,
                       hipStream_t st)
 {
-    if (total_samples <= 0) return GOOFER_OK;
-    hipLaunchKernelGGL(k_apply_gain, dim3((unsigned)((total_samples + 1023) / 1024)), dim3(256), 0, st, harm, uv, bre, rec, mix,
-                       sample_off, n_notes, total_samples, params, note_peak, write_stems ? 1 : 0);
-    LAUNCH_CHECK(ctx);
-    return GOOFER_OK;
+    return launch_per_sample(ctx, k_apply_gain, total_samples, 256 * SPT, 0, st, harm, uv, bre, rec, mix, sample_off, n_notes, total_samples,
+                             params, note_peak, write_stems ? 1 : 0);
 }
 
 int launch_ola3_gains(goofer_ctx *ctx, const float *fr_h, const float *fr_u, const float *fr_b, const float *note_mag,
@@ -1111,9 +1058,6 @@ int launch_ola3_gains(goofer_ctx *ctx, const float *fr_h, const float *fr_u, con
     const goofer_plan_t &p = ctx->plan;
     hipLaunchKernelGGL(k_note_steps, dim3((n_notes + 255) / 256), dim3(256), 0, st, sample_off, n_notes, steps);
     LAUNCH_CHECK(ctx);
-    hipLaunchKernelGGL(k_ola3_gains, dim3((unsigned)((total_samples + 255) / 256)), dim3(256), 0, st, fr_h, fr_u, fr_b, p.win_sq,
-                       note_mag, short_s, sample_off, frame_off, n_notes, total_samples, p.n_fft, p.hop, params, steps, harm, uv, bre,
-                       note_peak);
-    LAUNCH_CHECK(ctx);
-    return GOOFER_OK;
+    return launch_per_sample(ctx, k_ola3_gains, total_samples, 256, 0, st, fr_h, fr_u, fr_b, p.win_sq, note_mag, short_s, sample_off,
+                             frame_off, n_notes, total_samples, p.n_fft, p.hop, params, steps, harm, uv, bre, note_peak);
 }

@@ -1,5 +1,5 @@
 // Per-sample device helpers shared by samples.hip and stems.hip (gfx950): the smoothed voicing-mask upsampler
-// (GOOFER.py:563-567) and the corrected-reciprocal quotient.
+// (GOOFER.py:563-567) and the peak gain.
 #pragma once
 
 #include "common.h"
@@ -85,16 +85,6 @@ __device__ __forceinline__ float smooth_mask_at32(Knot knot, int ns, int i, int 
     const double s0 = knot(j), s1 = knot(j + 1);
     const double slope = (s1 - s0) * fast_rcp(xn - xj);
     return (float)(slope * (x - xj) + s0);
-}
-
-// x / d for a divisor whose correctly rounded reciprocal r = RN(1 / d) is at hand: q = RN(x r) is within an ulp,
-// the FMA residual x - q d is exact, and RN(q + residual r) is the correctly rounded quotient (Markstein 1990) —
-// for finite operands and a quotient in the normal range, which is where audio samples over a window sum live
-// (a zero stays a zero; a subnormal quotient may differ from the division in its last subnormal bit).
-__device__ __forceinline__ float div_by(float x, float d, float r)
-{
-    const float q = x * r;
-    return fmaf(fmaf(-q, d, x), r, q);
 }
 
 // gain = (1 / (peak + 1e-12))^normalize (GOOFER.py:1208-1214), `pk12` = the fp32 sum.  numpy's float64 power returns x for an

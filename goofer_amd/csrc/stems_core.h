@@ -1,23 +1,9 @@
 // Shared pieces of the frame walkers (stems.hip: registers for the overlap-add, hop == n_fft / 4; round 5's stems_ring.hip, removed: an LDS
-// ring, n_fft 2048 with any even hop): kernel arguments read where they are used, and the per-frame records of 64 frames.
+// ring, n_fft 2048 with any even hop): the per-frame records of 64 frames (kernel arguments read where they are used: COLD, common.h).
 #pragma once
 #include "binops_core.h"
 
 typedef float2 __attribute__((aligned(4))) float2_u;   // stems start at arbitrary sample offsets: pair stores are 4-byte aligned
-
-// Read a kernel argument from the kernarg segment at the point of use.  The walkers keep ~40 scalars of wave state across
-// their frame loop; arguments that are only needed every 64 frames (the frame-record arrays) or once per note kept live
-// beside them pushed the compiler past the 102 SGPRs of a wave, and every overflow costs a v_writelane / v_readlane pair in
-// the loop (the noise walker carried 105 such spills).  The empty asm hides the segment pointer from the optimiser, so the
-// load cannot be hoisted back to the kernel entry; it is a scalar load from the constant cache.
-template <typename T>
-__device__ __forceinline__ T cold_arg(size_t offset)
-{
-    const char __attribute__((address_space(4))) *ka = (const char __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(ka));
-    return *reinterpret_cast<const T __attribute__((address_space(4))) *>(ka + offset);
-}
-#define COLD(type, field) cold_arg<decltype(type::field)>(offsetof(type, field))
 
 // Per-frame records of 64 consecutive frames, one frame per lane: which note, where in it, which envelope row, the frame's
 // picks of f0 and the voicing mask.  A wave reads the record of its current frame with v_readlane — no memory access and

@@ -71,28 +71,18 @@ __global__ void k_frame_maps(const int64_t *__restrict__ frame_off, const int64_
 __global__ __launch_bounds__(256) void k_scale_f0(const float *__restrict__ f0, const int64_t *__restrict__ sample_off, int n_notes,
                                                   int64_t total, const goofer_note_params *__restrict__ params, float *__restrict__ out)
 {
-    __shared__ int s_pair[2];
-    const int64_t g0 = (int64_t)blockIdx.x * 1024;
-    int64_t gl = g0 + 1023;
-    if (gl > total - 1) gl = total - 1;
-    int lo, hi;
-    block_note_range_last(sample_off, n_notes, g0, gl, s_pair, lo, hi);
-    const int64_t g = g0 + (int64_t)threadIdx.x * 4;
-    if (g >= total) return;
+    const sample_tile<4> t(sample_off, n_notes, total);
+    if (!t.live) return;
+    const int64_t g = t.g;
     const bool vec = (((uintptr_t)f0 | (uintptr_t)out) & 15) == 0;
-    if (lo == hi && g + 4 <= total && vec) {
-        const float ps = params[lo].pitch_shift;
+    if (t.uniform() && g + 4 <= total && vec) {
+        const float ps = params[t.lo].pitch_shift;
         float4 v = *reinterpret_cast<const float4 *>(f0 + g);
         v.x *= ps; v.y *= ps; v.z *= ps; v.w *= ps;
         *reinterpret_cast<float4 *>(out + g) = v;
         return;
     }
-    int note = lo;
-    for (int k = 0; k < 4 && g + k < total; ++k) {
-        while (sample_off[note + 1] <= g + k) ++note;
-        const float v = f0[g + k] * params[note].pitch_shift;
-        out[g + k] = v;
-    }
+    for (int k = 0; k < 4 && g + k < total; ++k) out[g + k] = f0[g + k] * params[t.note(sample_off, g + k)].pitch_shift;
 }
 
 __global__ void k_note_sub_flags(const goofer_note_params *__restrict__ params, int n_notes, unsigned char *__restrict__ on_sub,
@@ -494,19 +484,12 @@ static int synth_batch(goofer_ctx *ctx, const goofer_batch *b, render_link &link
     if (r.early) {
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->side, ctx->ev_entry, 0));
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->side, ctx->ev_f0, 0));
-        if (!r.f0_alias) {
-            hipLaunchKernelGGL(k_scale_f0, dim3((unsigned)((N + 1023) / 1024)), dim3(256), 0, ctx->side, b->f0, b->sample_off, n, N,
-                               b->params, s.f0s);
-            LAUNCH_CHECK(ctx);
-        }
+        if (!r.f0_alias && (rc = launch_per_sample(ctx, k_scale_f0, N, 1024, 0, ctx->side, b->f0, b->sample_off, n, N, b->params, s.f0s))) return rc;
         HIP_TRY(ctx, hipEventRecord(ctx->ev_f0s, ctx->side));
     }
     if (!r.walkers && (rc = launch_frame_note(ctx, b->frame_off, n, F, s.frame_note, st))) return rc;
-    if (!r.early && !r.f0_alias) {
-        hipLaunchKernelGGL(k_scale_f0, dim3((unsigned)((N + 1023) / 1024)), dim3(256), 0, st, b->f0, b->sample_off, n, N, b->params,
-                           s.f0s);                                   // (the pulse walk divides by sr itself)
-        LAUNCH_CHECK(ctx);
-    }
+    // (the pulse walk divides by sr itself)
+    if (!r.early && !r.f0_alias && (rc = launch_per_sample(ctx, k_scale_f0, N, 1024, 0, st, b->f0, b->sample_off, n, N, b->params, s.f0s))) return rc;
     if (r.walkers) {   // the stem walkers' frame maps in one launch
         const int64_t threads = std::max<int64_t>(F, 2 * (int64_t)n);
         hipLaunchKernelGGL(k_frame_maps, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, b->frame_off, b->env_off, n, F, s.frame_note,

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "common.h"
+#include "ragged.h"
 
 namespace {
 
@@ -63,13 +64,6 @@ int64_t resampled_length(int64_t n, int sr) { return n * FM_SR / sr; }
 int64_t formant_frames(int64_t m, int sr, int hop) { return m < FM_WIN ? 0 : (m - FM_WIN) * sr / ((int64_t)FM_SR * hop) + 1; }
 
 // ---- device helpers ----------------------------------------------------------------------------------------------
-__device__ __forceinline__ double wave_sum_d(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // numpy's max: a NaN operand wins (fmax returns the other one).  On non-NaN operands this is fmax, so every finite result
 // keeps its bits.
 __device__ __forceinline__ double nan_max(double a, double b) { return (a > b || a != a) ? a : b; }
@@ -84,7 +78,7 @@ __device__ __forceinline__ double wave_max_d(double v)
 // fixed-order block reductions over TR_THREADS threads (every thread gets the result); red: 4 doubles of LDS
 __device__ double block_sum_d(double v, double *red)
 {
-    v = wave_sum_d(v);
+    v = wave_sum(v);
     const int wave = threadIdx.x >> 6;
     __syncthreads();
     if ((threadIdx.x & 63) == 0) red[wave] = v;
@@ -373,8 +367,8 @@ __global__ __launch_bounds__(WAVE) void k_formant_frames(const double *__restric
                 de += ff * ff + bb * bb;
             }
         }
-        nu = wave_sum_d(nu);
-        de = wave_sum_d(de);
+        nu = wave_sum(nu);
+        de = wave_sum(de);
         if (!(de > 0.0)) break;
         const double k = -2.0 * nu / de;
 #pragma unroll

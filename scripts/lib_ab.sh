@@ -4,7 +4,7 @@
 A=$1; B=$2; R=${3:-3}; N=${4:-1024}; C=${5:-3}
 for r in $(seq 1 $R); do
   for L in "$A" "$B"; do
-    GOOFER_HIP_LIB=$PWD/$L python - $N $C <<'PY'
+    GOOFER_HIP_LIB=$PWD/$L timeout -k 10 300 python - $N $C <<'PY' || exit $?   # a run that fails ends the comparison
 import os, sys
 sys.path.insert(0, os.getcwd())
 import torch

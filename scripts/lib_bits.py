@@ -1,0 +1,172 @@
+#!/usr/bin/env python
+"""Do two builds of libgoofer_hip.so compute the same bits?  The before / after check of a refactor of the per-sample kernels.
+
+usage: scripts/lib_bits.py <libA.so> <libB.so> [--out FILE] [--limit SECONDS]
+
+Each library gets one fresh child process (GOOFER_HIP_LIB set, as scripts/lib_ab.sh does) under its own `timeout -k 10`; the
+second starts only if the first exited 0.  A child runs a fixed, seeded case list twice through the entry points that reach the
+kernels built on csrc/ragged.h — the post chain, the cascade, the synthesis on its spectra routes with the jitter, vibrato and
+sub-harmonic keyword sets, normal_fill, smooth_mask_ds, irfft_ola — and prints {case: {output: sha256}} of both runs.
+
+An output whose digest differs between the two runs of one library is listed as non-deterministic and not compared across the
+libraries.  Only outputs behind k_note_sumsq are expected there (post chain, notes with tension != 0 that are longer than a
+workgroup: float64 atomics across workgroups).  Anything else listed there is a finding.
+
+Writes {"A": .., "B": .., "nondeterministic": [..], "differ": [..]} to FILE (default: standard output only) and prints the two
+lists; exit status 1 if an output differs, the child's if a child failed.
+"""
+import hashlib
+import json
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _sha(a):
+    import numpy as np
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+def _cases(ctx):
+    """{case: {output name: sha256}} of one pass over the list."""
+    import numpy as np
+    import post_ref as P
+    import synth_ref as SR
+    import test_gpu_post_chain as PC
+    import test_gpu_ragged_tiles as RT
+    from goofer_amd.device import default_params, spec_stride
+    out = {}
+
+    # the post chain: one flag at a time and all together, the fry ramps, the pd levels, the ragged-tile batch
+    sr = 44100
+    ctx.plan(sr, 1024, 256)
+    post = {"post/" + kind: PC._boundary_batch(kind, sr) for kind in PC.KINDS}
+    post.update({"post/fry_ramps": P.fry_cases(sr), "post/pd_levels": P.pd_cases(sr), "post/tiles": RT.post_notes(False),
+                 "post/tiles_st": RT.post_notes(True)})
+    for name, notes in post.items():
+        res = PC.run_post(ctx, notes)
+        out[name] = {"%s[%d]" % (k, i): _sha(v) for i, r in enumerate(res) for k, v in zip(("harm", "bre", "mix"), r)}
+    xs, f0s = P.cascade_inputs()
+    for order, btype, mode, cf in P.CASCADE_SETTINGS[::4]:
+        y = ctx.onepole_cascade(ctx.tensor(np.concatenate(xs)), ctx.tensor(np.concatenate(f0s)), cf, order, btype, f0_mode=mode,
+                                lengths=[len(x) for x in xs])
+        out["cascade/%s%d_mode%d_cf%g" % (btype, order, mode, cf)] = {"y": _sha(y.cpu().numpy())}
+
+    # the synthesis on the spectra routes (fused and separate overlap-add), each keyword set on every second note
+    sets = {"plain": ({}, {}), "jitter": (RT.JITTER, dict(noise=True)),
+            "vibrato": (RT.JITTER, dict(volume_vibrato=True, vol_jitter_speed=9.0)),
+            "subharm": (dict(add_subharm=True, subharm_weight=0.7, subharm_f0_jitter=0.4),
+                        dict(noise=True, subharm=dict(semitones=[-12, 7], vibrato=True, rate=40.0, depth=0.2, delay=0.01)))}
+    try:
+        ctx.set_option("stems", 0)
+        for geo in ((44100, 1024, 256), (44100, 768, 192)):
+            for batch in ("main", "tiny"):
+                base = SR.batches(geo)[batch][1]
+                noise = [np.random.default_rng(5 + q).standard_normal(sum(c["n"] for c in base)) for q in range(4)]
+                for tag, (kw, call) in sets.items():
+                    if batch == "tiny" and tag != "plain":
+                        continue
+                    cases = [dict(c, kw=dict(c["kw"], **kw)) if k % 2 else c for k, c in enumerate(base)]
+                    res = RT.run_synth(ctx, geo, cases, call, noise)
+                    out["synth/%d_%d/%s/%s" % (geo[1], geo[2], batch, tag)] = {k: _sha(v) for k, v in res.items()}
+        # the tile batch of tests/test_gpu_ragged_tiles.py: boundaries at every offset the tiles treat differently
+        for geo in ((RT.SR_HZ, 1024, 256), (RT.SR_HZ, 768, 192)):
+            for tag in RT.VARIANTS:
+                cases = RT.synth_cases(geo, tag)
+                res = RT.run_synth(ctx, geo, cases, RT.VARIANTS[tag][1], RT.synth_noise(cases))
+                out["synth/%d_%d/tiles/%s" % (geo[1], geo[2], tag)] = {k: _sha(v) for k, v in res.items()}
+    finally:
+        ctx.set_option("stems", 1)
+
+    # single kernels over the tile batch
+    ctx.plan(44100, 1024, 256)
+    lens, n = RT.LENGTHS, len(RT.LENGTHS)
+    par = default_params(n)
+    par["seed"][:, 0] = np.arange(n) + 11
+    on = np.array([k % 3 != 1 for k in range(n)], dtype=np.uint8)
+    for tag in range(5):
+        import torch
+        z = ctx.normal_fill(2026, par, lens, tag, note_on=on if tag % 2 == 0 else None,
+                            growl_scale=np.linspace(0.1, 0.9, n) if tag == 4 else None,
+                            out=torch.zeros(sum(lens), dtype=torch.float64, device=ctx.device))
+        out["normal_fill/tag%d" % tag] = {"z": _sha(z.cpu().numpy())}
+    rng = np.random.default_rng(31)
+    mask = np.concatenate([np.repeat(rng.random(m // 37 + 1) > 0.4, 37)[:m] for m in lens]).astype(np.float32)
+    for fast in (False, True):
+        for sigma in (4.0, 100.0):
+            m = ctx.smooth_mask_ds(ctx.tensor(mask), lens, sigma=sigma, fast_interp=fast)
+            out["smooth_mask_ds/sigma%g_fast%d" % (sigma, fast)] = {"mask": _sha(m.cpu().numpy())}
+    for geo in ((44100, 1024, 256), (44100, 768, 192), (44100, 1000, 250)):
+        ctx.plan(*geo)
+        nb = geo[1] // 2 + 1
+        f_off = ctx.offsets(ctx.frame_counts(lens))
+        rng = np.random.default_rng(57)
+        S = np.zeros((int(f_off[-1]), spec_stride(nb)), dtype=np.complex64)
+        S[:, :nb] = (rng.standard_normal((len(S), nb)) + 1j * rng.standard_normal((len(S), nb))).astype(np.complex64)
+        y = ctx.irfft_ola(ctx.tensor(S), ctx.tensor(ctx.offsets(lens)), ctx.tensor(f_off), sum(lens))
+        out["irfft_ola/%d_%d" % geo[1:]] = {"y": _sha(y.cpu().numpy())}
+    ctx.plan(44100, 1024, 256)
+    return out
+
+
+def child():
+    sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+    from goofer_amd.device import Context
+    ctx = Context(0)
+    runs = [_cases(ctx), _cases(ctx)]
+    ctx.close()
+    print("LIB_BITS " + json.dumps(runs))
+
+
+def _flat(d):
+    return {"%s:%s" % (case, name): h for case, outs in d.items() for name, h in outs.items()}
+
+
+def main(argv):
+    if argv == ["--child"]:
+        return child()
+    opts = {"--out": None, "--limit": "600"}
+    libs = []
+    it = iter(argv)
+    for a in it:
+        if a in opts:
+            opts[a] = next(it)
+        else:
+            libs.append(a)
+    if len(libs) != 2:
+        sys.exit(__doc__)
+    runs = {}
+    for tag, lib in zip("AB", libs):
+        env = dict(os.environ, GOOFER_HIP_LIB=os.path.abspath(lib))
+        p = subprocess.run(["timeout", "-k", "10", opts["--limit"], sys.executable, os.path.abspath(__file__), "--child"], env=env,
+                           cwd=ROOT, stdout=subprocess.PIPE, text=True)
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith("LIB_BITS ")]
+        if p.returncode != 0 or not lines:
+            sys.stdout.write(p.stdout[-4000:])
+            print("lib_bits: the child of %s exited %d; nothing more is started" % (lib, p.returncode))
+            sys.exit(p.returncode or 2)
+        runs[tag] = json.loads(lines[-1][len("LIB_BITS "):])
+    flat = {tag: [_flat(r) for r in runs[tag]] for tag in runs}
+    keys = sorted(flat["A"][0])
+    assert all(sorted(f) == keys for tag in flat for f in flat[tag]), "the libraries ran different case lists"
+    loose = [k for k in keys if any(flat[tag][0][k] != flat[tag][1][k] for tag in flat)]
+    differ = [k for k in keys if k not in loose and flat["A"][0][k] != flat["B"][0][k]]
+    report = {"A": runs["A"][0], "B": runs["B"][0], "libs": [os.path.basename(v) for v in libs], "nondeterministic": loose,
+              "differ": differ}
+    if opts["--out"]:
+        with open(opts["--out"], "w") as fh:
+            json.dump(report, fh, indent=1, sort_keys=True)
+            fh.write("\n")
+    print("%d outputs of %d cases; non-deterministic (not compared): %d; differing: %d" % (len(keys), len(runs["A"][0]), len(loose),
+                                                                                        len(differ)))
+    for k in loose:
+        print("  non-deterministic  " + k)
+    for k in differ:
+        print("  DIFFERS            " + k)
+    sys.exit(1 if differ else 0)
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])
