@@ -177,7 +177,7 @@ int goofer_create(int device_id, goofer_ctx **out)
     goofer_ctx *c = new goofer_ctx();
     c->device = device_id;
     // the onset-overflow word lives as long as the handle (never inside the re-carved, re-allocated scratch arena)
-    if (hipMalloc((void **)&c->ovf_flag, 64) != hipSuccess || hipMemset(c->ovf_flag, 0, 64) != hipSuccess) {
+    if (hipMalloc((void **)&c->ovf_flag, OVF_WORDS * sizeof(int32_t)) != hipSuccess || hipMemset(c->ovf_flag, 0, OVF_WORDS * sizeof(int32_t)) != hipSuccess) {
         delete c;
         return GOOFER_EHIP;
     }
@@ -450,13 +450,27 @@ int goofer_check(goofer_ctx *ctx)
 /* Cumulative counters of the handle (device words beside the overflow flag; the call synchronises the device):
  *   "pulse_scanned_notes"   notes whose onsets went through the parallel phase scan (k_pulse_onsets_par)
  *   "pulse_fallback_notes"  ... of which were walked sequentially afterwards (a sample within the error band of an integer
- *                           phase, a negative / non-finite increment, or option pulse_scan = 2) */
+ *                           phase, a negative / non-finite increment, or option pulse_scan = 2)
+ *   "mask_flag_segments"    note segments of k_mask_short's tiles (goofer_synth_batch / goofer_render_batch) answered from the
+ *                           f0 kernel's tile flags alone
+ *   "mask_staged_segments"  ... that staged their mask window in LDS (every segment when there are no flags; the large-radius
+ *                           loop counts nothing) */
 int goofer_counter(goofer_ctx *ctx, const char *name, int64_t *value)
 {
     if (!ctx || !name || !value) return GOOFER_EINVAL;
     int which = !strcmp(name, "pulse_fallback_notes") ? 1 : (!strcmp(name, "pulse_scanned_notes") ? 2 : -1);
-    if (which < 0) return goofer_fail(ctx, GOOFER_EINVAL, "unknown counter %s", name);
+    const int mask_c = !strcmp(name, "mask_flag_segments") ? 0 : (!strcmp(name, "mask_staged_segments") ? 1 : -1);
+    if (which < 0 && mask_c < 0) return goofer_fail(ctx, GOOFER_EINVAL, "unknown counter %s", name);
     HIP_TRY(ctx, hipDeviceSynchronize());
+    if (mask_c >= 0) {                                        // the sum of the counter's slots
+        static_assert(OVF_WORDS <= 8192, "goofer_counter reads the words through a stack buffer");
+        int32_t w[OVF_WORDS];
+        HIP_TRY(ctx, hipMemcpy(w, ctx->ovf_flag, sizeof(w), hipMemcpyDeviceToHost));
+        int64_t sum = 0;
+        for (int sl = 0; sl < MASK_COUNTER_SLOTS; ++sl) sum += (int64_t)(uint32_t)w[MASK_COUNTERS + (2 * sl + mask_c) * MASK_COUNTER_STRIDE];
+        *value = sum;
+        return GOOFER_OK;
+    }
     int32_t v = 0;
     HIP_TRY(ctx, hipMemcpy(&v, ctx->ovf_flag + which, sizeof(v), hipMemcpyDeviceToHost));
     *value = (int64_t)(uint32_t)v;
@@ -574,6 +588,7 @@ int goofer_set_option(goofer_ctx *ctx, const char *name, int value)
     if (!strcmp(name, "td_blur")) { ctx->td_blur = value != 0; return GOOFER_OK; }
     if (!strcmp(name, "pulse_scan")) { ctx->pulse_scan = value < 0 ? 0 : (value > 2 ? 2 : value); return GOOFER_OK; }
     if (!strcmp(name, "sa_fast")) { ctx->sa_fast = value != 0; return GOOFER_OK; }
+    if (!strcmp(name, "mask_flags")) { ctx->mask_flags = value != 0; return GOOFER_OK; }
     if (!strcmp(name, "value_f64")) { ctx->value_f64 = value != 0; return GOOFER_OK; }
     return goofer_fail(ctx, GOOFER_EINVAL, "unknown option %s", name);
 }
@@ -876,7 +891,7 @@ int goofer_smooth_mask_ds(goofer_ctx *ctx, const float *mask, const int64_t *sam
     HIP_TRY(ctx, hipStreamSynchronize(st));                                            // the host vector goes out of scope
     double acc = 0.0;
     for (double tv : taps) acc += tv * 1.0;
-    if ((rc = launch_mask_short(ctx, mask, sample_off, n_notes, total_samples, d_taps, radius, acc, short_s, st))) return rc;
+    if ((rc = launch_mask_short(ctx, mask, sample_off, n_notes, total_samples, d_taps, radius, acc, short_s, nullptr, nullptr, st))) return rc;
     return launch_mask_upsample(ctx, short_s, sample_off, n_notes, total_samples, steps, fast_interp != 0, out, st);
 }
 

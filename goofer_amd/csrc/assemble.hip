@@ -782,7 +782,8 @@ __device__ __forceinline__ double exp2_poly(double x)
     return ldexp(q, (int)n);
 }
 
-__device__ __forceinline__ void sample_assemble_one(const goofer_assembly &a, const goofer_note_plan &p, int64_t g)
+// (returns the mask value it stored: the tile-flag vote of k_sample_assemble)
+__device__ __forceinline__ float sample_assemble_one(const goofer_assembly &a, const goofer_note_plan &p, int64_t g)
 {
     const int i = (int)(g - p.out_sample_off);
     const float *m = a.mask_src + p.src_sample_off;
@@ -843,7 +844,8 @@ __device__ __forceinline__ void sample_assemble_one(const goofer_assembly &a, co
         }
     }
     const double hz = 440.0 * exp2_poly(div_by(midi - 69.0, 12.0, 0.083333333333333329));   // RN(1/12)
-    a.mask_out[g] = (float)mk;
+    const float mk_f = (float)mk;
+    a.mask_out[g] = mk_f;
     double f0 = mk * hz;
     if (p.pd_on && a.bend_out) a.bend_out[g] = (float)(midi - p.pd_base);                    // 'pd' bend in semitones   :861-863
     // vocal fry part 1: f0 pulled to fry_hz over a constant stretch plus a linear glide       :883-934
@@ -859,6 +861,7 @@ __device__ __forceinline__ void sample_assemble_one(const goofer_assembly &a, co
     }
     a.f0_out[g] = (float)f0;
     if (a.f0_mul_out) a.f0_mul_out[g] = (float)(f0 * a.f0_mul[g]);                           // 'sj' layer f0, one rounding   :1065
+    return mk_f;
 }
 
 
@@ -871,8 +874,19 @@ __device__ __forceinline__ void sample_assemble_one(const goofer_assembly &a, co
 // fp64 curve, 2^x and the stores.  sample_assemble_one does the same per sample with a branch at every decision, so the
 // thread's samples wait out their round trips to memory one after the other (k_sample_assemble was 0.31 ms alone for the same
 // arithmetic).  Same operations on the same values: bit-identical to sample_assemble_one (tested through option "sa_fast" 0).
-template <int SA_SPT>
-__device__ __forceinline__ void sample_assemble_fast(const goofer_assembly &a, const goofer_note_plan &p, int64_t g0, int64_t total_samples)
+// the tile-flag vote of k_sample_assemble on one stored mask value: bit 0: not == 0.0f, bit 1: not == 1.0f (-0.0f is a zero, a NaN neither)
+__device__ __forceinline__ unsigned mask_vote(float mk) { return (mk == 0.0f ? 0u : 1u) | (mk == 1.0f ? 0u : 2u); }
+
+struct sa_kernarg {                                          // k_sample_assemble's argument list as the kernarg segment lays it out (COLD)
+    goofer_assembly a;
+    int64_t total_samples;
+    int fast;
+    unsigned char *tile_flags;
+};
+// bad: mask_vote of every live mask value of this thread, or-ed into
+template <int SA_SPT, bool FLAGS>
+__device__ __forceinline__ void sample_assemble_fast(const goofer_assembly &a, const goofer_note_plan &p, int64_t g0, int64_t total_samples,
+                                                     unsigned &bad, unsigned char *&flag_dst)
 {
     const float *__restrict__ m = a.mask_src + p.src_sample_off;
     const double *__restrict__ bend = a.bend + p.bend_off;
@@ -933,6 +947,12 @@ __device__ __forceinline__ void sample_assemble_fast(const goofer_assembly &a, c
         const double hz = 440.0 * exp2_poly(div_by(midi - 69.0, 12.0, 0.083333333333333329));   // RN(1/12)
         fo[u] = (float)((double)mv[u] * hz);
     }
+    if (FLAGS) {
+        // the flag pointer's scalar load goes out here, behind the fp64 curve (tied to its last result, or the compiler issues it at the
+        // kernel's entry and the pointer costs two scalar registers all the way), and arrives while the stores are issued
+        asm volatile("" : "+v"(fo[SA_SPT - 1]));
+        flag_dst = COLD(sa_kernarg, tile_flags);
+    }
 #pragma unroll
     for (int u = 0; u < SA_SPT; ++u) {
         const int64_t g = g0 + threadIdx.x + (int64_t)u * blockDim.x;
@@ -941,10 +961,20 @@ __device__ __forceinline__ void sample_assemble_fast(const goofer_assembly &a, c
             f0_out[g] = fo[u];
         }
     }
+    // (behind the stores, where mv[] is the only array still live)
+#pragma unroll
+    for (int u = 0; u < SA_SPT; ++u)
+        if (live[u]) bad |= mask_vote(mv[u]);
 }
 
-template <int SA_SPT>
-__global__ __launch_bounds__(256) void k_sample_assemble(const goofer_assembly a, int64_t total_samples, int fast)
+// FLAGS: every wave also leaves one byte about the SA_TILE / 4 mask values it stored, tile_flags[4 * blockIdx.x + wave] = the or of
+// mask_vote over them (bit 0: some value is not == 0.0f, bit 1: some value is not == 1.0f; -0.0f is a zero) — so the four bytes of
+// a tile, read as one word, say whether the tile of the mask is all zeros, all ones or neither, whatever notes it belongs to.
+// k_mask_short answers whole windows from these words instead of loading the mask again (goofer_render_batch; every other
+// caller: FLAGS false, the kernel as it was).  A byte per wave and not one per workgroup: combining the waves costs a barrier
+// at the end of a kernel that lives on its occupancy.
+template <int SA_SPT, bool FLAGS>
+__global__ __launch_bounds__(256) void k_sample_assemble(const goofer_assembly a, int64_t total_samples, int fast, unsigned char *__restrict__ tile_flags)
 {
     __shared__ int s_pair[2];
     const int64_t g0 = (int64_t)blockIdx.x * (blockDim.x * SA_SPT);
@@ -959,17 +989,20 @@ __global__ __launch_bounds__(256) void k_sample_assemble(const goofer_assembly a
     }
     __syncthreads();
     const int n_lo = __builtin_amdgcn_readfirstlane(s_pair[0]), n_hi = __builtin_amdgcn_readfirstlane(s_pair[1]);
+    unsigned bad = 0u;                                       // mask_vote of the values this thread stored
+    unsigned char *flag_dst = nullptr;                       // (the fast path reads the pointer itself, ahead of its stores)
+    auto vote = [&](float mk) { bad |= mask_vote(mk); };
     if (n_lo == n_hi) {
         const goofer_note_plan &p = a.notes[n_lo];           // uniform note: the 300-byte plan comes in through scalar loads
         if (fast && !p.vel_active && p.fry_dir == 0 && !(p.pd_on && a.bend_out) && !a.f0_mul_out && p.n_out < (1 << 21) && p.tail_len < (1 << 24) &&
             p.tail_len > 0 && p.n_bend >= 1) {
-            sample_assemble_fast<SA_SPT>(a, p, g0, total_samples);
-            return;
-        }
+            sample_assemble_fast<SA_SPT, FLAGS>(a, p, g0, total_samples, bad, flag_dst);
+        } else {
 #pragma unroll
-        for (int u = 0; u < SA_SPT; ++u) {
-            const int64_t g = g0 + threadIdx.x + (int64_t)u * blockDim.x;
-            if (g < total_samples) sample_assemble_one(a, p, g);
+            for (int u = 0; u < SA_SPT; ++u) {
+                const int64_t g = g0 + threadIdx.x + (int64_t)u * blockDim.x;
+                if (g < total_samples) vote(sample_assemble_one(a, p, g));
+            }
         }
     } else {
         for (int u = 0; u < SA_SPT; ++u) {
@@ -977,8 +1010,16 @@ __global__ __launch_bounds__(256) void k_sample_assemble(const goofer_assembly a
             if (g >= total_samples) break;
             int note = n_lo;
             while (note + 1 < a.n_notes && a.notes[note + 1].out_sample_off <= g) ++note;
-            sample_assemble_one(a, a.notes[note], g);
+            vote(sample_assemble_one(a, a.notes[note], g));
         }
+    }
+    if (FLAGS) {
+        const int bits = (__any(bad & 1u) ? 1 : 0) | (__any(bad & 2u) ? 2 : 0);
+        // (the slow paths read the pointer here, from the kernarg segment: held in two scalar registers across the kernel it made 98 of them where
+        // 96 is the most that leaves eight waves per SIMD — alone the kernel went from 0.209 to 0.227 ms, and beside k_env_edit,
+        // which then found room on every SIMD, to twice its time)
+        if (!flag_dst) flag_dst = COLD(sa_kernarg, tile_flags);
+        if ((threadIdx.x & (WAVE - 1)) == 0) flag_dst[4 * (size_t)blockIdx.x + (threadIdx.x >> 6)] = (unsigned char)bits;
     }
 }
 
@@ -1065,7 +1106,13 @@ int launch_assemble(goofer_ctx *ctx, const goofer_assembly *a, int *row_note_edi
         const dim3 sgrid((unsigned)((a->total_samples + 256 * spt - 1) / (256 * spt)));
         const int sa_fast = ctx->sa_fast ? 1 : 0;
         HIP_TRY(ctx, mark(2, 0, fst));
-        hipLaunchKernelGGL(k_sample_assemble<spt>, sgrid, dim3(256), 0, fst, *a, a->total_samples, sa_fast);
+        static_assert(256 * spt == SA_TILE, "one tile-flag word per workgroup of k_sample_assemble");
+        if (link.tile_flags_dst) {
+            hipLaunchKernelGGL((k_sample_assemble<spt, true>), sgrid, dim3(256), 0, fst, *a, a->total_samples, sa_fast, link.tile_flags_dst);
+            link.tile_flags = link.tile_flags_dst;
+        } else {
+            hipLaunchKernelGGL((k_sample_assemble<spt, false>), sgrid, dim3(256), 0, fst, *a, a->total_samples, sa_fast, (unsigned char *)nullptr);
+        }
         LAUNCH_CHECK(ctx);
         HIP_TRY(ctx, mark(2, 1, fst));
         if (link.fork_early && ctx->ev_f0) {

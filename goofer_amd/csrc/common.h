@@ -13,6 +13,11 @@
 #define WAVE 64
 #define PROF_STAGES 18
 #define PROF_ASM0 15           // profile stages 15..17: the assembly's k_env_edit, k_env_rows, k_sample_assemble
+#define SA_TILE 1024            // k_sample_assemble<4>: samples per workgroup (256 threads x 4), and per tile-flag word (render_link::tile_flags)
+#define MASK_COUNTERS 32        // goofer_ctx::ovf_flag + MASK_COUNTERS: k_mask_short's two counters (segments answered from tile flags, segments staged),
+#define MASK_COUNTER_SLOTS 64   // each spread over this many words a cache line apart (slot = workgroup & 63): thirteen thousand atomics on
+#define MASK_COUNTER_STRIDE 32  // ONE word took longer than the kernel; counter c, slot s: word MASK_COUNTERS + (2 * s + c) * MASK_COUNTER_STRIDE
+#define OVF_WORDS (MASK_COUNTERS + 2 * MASK_COUNTER_SLOTS * MASK_COUNTER_STRIDE)
 #define PP_SPT 8                // k_pulse_place: consecutive samples per thread; a tile = one workgroup = 256 * PP_SPT samples
 #define PULSE_TILE_INTS(samples) (4 * (((samples) + 256 * PP_SPT - 1) / (256 * PP_SPT)) + 64)   // k_pulse_tiles' table: 4 ints per tile
 // compress_env_to_knots' candidate knot counts (GOOFER.py:97-147): K = KN_K0, KN_K0 + KN_DK, ..., KN_KMAX
@@ -75,11 +80,16 @@ struct render_link {
     float *warp_dst = nullptr;            // the frame-gather kernel also writes the rows the harmonic walker needs (formant-anchored +
     const double *formants = nullptr;     // uniform warp) here, from these formants and note parameters
     const goofer_note_params *params = nullptr;
+    bool want_tile_flags = false;         // carve tile_flags_dst (assemble_batch), where the f0 / mask kernel also leaves a word per SA_TILE samples
+    unsigned char *tile_flags_dst = nullptr;   // of the mask it writes: four bytes, one per wave, bit 0: some value is not == 0.0f, bit 1: some value
+                                          // is not == 1.0f (word & 0x01010101 == 0: the tile is all zeros, & 0x02020202 == 0: all ones)
     // answered by the assembly
     const float *f0_ready = nullptr;      // the f0 array ev_f0 stands for (null: no event recorded)
     bool f0_side = false;                 // the f0 / mask kernel ran on the side stream, in front of the pulse chain it feeds: the caller's
                                           // stream waits for ev_f0 before it reads f0 / mask (cleared by whoever places that wait)
     bool warped = false;                  // warp_dst holds the warped rows of the batch
+    const unsigned char *tile_flags = nullptr;   // the tile flags of the mask as the f0 / mask kernel wrote it (ready where f0 / mask are), for
+                                          // k_mask_short; null: none were written
 };
 
 struct goofer_ctx {
@@ -102,7 +112,7 @@ struct goofer_ctx {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_maps = nullptr;
     // goofer_render_batch: the pulse chain forks as soon as the assembled f0 exists, not when the synthesis call starts
     hipEvent_t ev_entry = nullptr, ev_f0 = nullptr, ev_f0s = nullptr;
-    int32_t *ovf_flag = nullptr;           // handle-owned device words ([1], [2]: cumulative counters, goofer_counter); [0] sticky between goofer_check calls: 1 + index (inside its batch) of a
+    int32_t *ovf_flag = nullptr;           // handle-owned device words (OVF_WORDS of them; [1], [2] and from MASK_COUNTERS on: cumulative counters, goofer_counter); [0] sticky between goofer_check calls: 1 + index (inside its batch) of a
                                            // note whose pulse onsets overflowed their slots, written with atomicMax by every pulse-chain launch
     // goofer_render_batch, stem-split path: the buffer the assembly's frame-gather kernel writes the harmonic walker's warped rows
     // to (render_link::warp_dst)
@@ -120,6 +130,8 @@ struct goofer_ctx {
     bool skip_zero = true;        // noise walker: skip transforms whose stem gain is exactly zero over everything they reach (option "skip_zero")
     bool td_blur = true;          // stem walkers: the 5-tap bin blur of voiced frames as a window on the frame's samples (option "td_blur")
     bool prof_stems = false;      // the last profiled batch ran the stem-split path (stage order differs)
+    bool mask_flags = true;       // goofer_render_batch: k_sample_assemble leaves tile flags of the mask and k_mask_short answers flat windows from
+                                  // them without loading the mask (option "mask_flags"; 0: A/B, the same bits)
     bool sa_fast = true;          // k_sample_assemble: the branch-free path with all of a thread's loads in flight together (option "sa_fast"; 0: A/B)
     bool value_f64 = false;       // k_env_edit: round 4's fp64 value arithmetic (fw interpolation, es blur) instead of fp32 — A/B and the
                                   // error-budget tests (option "value_f64")

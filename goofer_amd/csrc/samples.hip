@@ -19,10 +19,22 @@
 // almost everywhere.  fp64 accumulate in tap order.
 #define MS_MAXWIN 1152     // LDS floats per workgroup = 4 * MS_MAXWIN >= MS_TILE + 2*radius
 #define MS_TILE 1024
+#define MS_QUART (MS_TILE / 4)   // the flags decide per quarter of a segment: 256 knots, the four chunks the waves take side by side
 
+// tile_flags (goofer_render_batch: a word per SA_TILE samples from the kernel that wrote the mask — four bytes, bit 0 of each: some
+// value of that wave is not == 0.0f, bit 1: some value is not == 1.0f; null otherwise) settle most of this without a load of
+// the mask.  The windows of a quarter's knots [q, q + l) touch the decimated indices [q - radius, q + l - 1 + radius] clipped to
+// the note (the reflect map never leaves that range), i.e. the samples MASK_DS times those: when the words of every SA_TILE
+// tile over them say all zeros (all ones), each chunk of the quarter would find its window all zeros (ones) below and its
+// knots are 0.0 (tap_sum).  A segment whose quarters are all settled that way is written at once: no mask load, no LDS
+// window, no barrier.  Otherwise the window is staged for the unsettled quarters only.  Every wave reads the same flag words
+// (one load, two votes), so the decisions are workgroup-uniform.
+// counters (or null): segments answered from the flags / segments that staged a window, one atomic per segment, each counter
+// spread over MASK_COUNTER_SLOTS words by workgroup (common.h).
 __global__ __launch_bounds__(256) void k_mask_short(const float *__restrict__ mask, const int64_t *__restrict__ sample_off,
                                                     int n_notes, int64_t total_short, const double *__restrict__ taps, int radius,
-                                                    double *__restrict__ short_s, double tap_sum)
+                                                    double *__restrict__ short_s, double tap_sum,
+                                                    const unsigned char *__restrict__ tile_flags, int32_t *__restrict__ counters)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     double *s_taps = reinterpret_cast<double *>(smem);
@@ -43,6 +55,7 @@ __global__ __launch_bounds__(256) void k_mask_short(const float *__restrict__ ma
     const int n_lo = __builtin_amdgcn_readfirstlane(s_lo[0]), n_hi = __builtin_amdgcn_readfirstlane(s_lo[1]);
 
     if (2 * radius + MS_TILE <= 4 * MS_MAXWIN) {
+        bool staged = false;                                 // some segment of this workgroup has used the LDS window
         for (int note = n_lo; note <= n_hi; ++note) {
             const int64_t sb = short_base(sample_off, note);
             const int64_t base = sample_off[note], n = sample_off[note + 1] - base;
@@ -52,29 +65,66 @@ __global__ __launch_bounds__(256) void k_mask_short(const float *__restrict__ ma
             const int64_t q0 = s0 - sb;
             const int len = (int)(s1 - s0);
             const float *m = mask + base;
-            if (note != n_lo) __syncthreads();               // the previous note's window is no longer read
-            for (int w = threadIdx.x; w < len + 2 * radius; w += blockDim.x) s_all[w] = m[MASK_DS * reflect_index(q0 - radius + w, ns)];
+            // bit k of flat0 (flat1): the flags say every window of quarter k is all zeros (ones)
+            unsigned flat0 = 0u, flat1 = 0u;
+            const int nq = (len + MS_QUART - 1) / MS_QUART;
+            if (tile_flags) {
+                auto tile_of = [&](int64_t q) {              // flag tile of decimated index q (clipped to the note) of this note
+                    q = q < 0 ? 0 : (q > ns - 1 ? ns - 1 : q);
+                    return (base + MASK_DS * q) / SA_TILE;
+                };
+                const int64_t t0 = tile_of(q0 - radius), t1 = tile_of(q0 + len - 1 + radius);
+                if (t1 - t0 < WAVE) {                        // (19 tiles at the largest radius of this path)
+                    const uint32_t f = lane <= (int)(t1 - t0) ? reinterpret_cast<const uint32_t *>(tile_flags)[t0 + lane] : 0x03030303u;
+                    const uint64_t z = __ballot((f & 0x01010101u) == 0u), o = __ballot((f & 0x02020202u) == 0u);
+                    // lane k settles quarter k: the tiles a .. b (relative to t0) of its windows against the two votes
+                    const int ql = (lane < nq ? lane : 0) * MS_QUART, qh = ql + MS_QUART < len ? ql + MS_QUART : len;
+                    const int a = (int)(tile_of(q0 + ql - radius) - t0), b = (int)(tile_of(q0 + qh - 1 + radius) - t0);
+                    const uint64_t need = (b - a >= 63 ? ~0ull : (1ull << (b - a + 1)) - 1ull) << a;
+                    const bool is0 = lane < nq && (z & need) == need, is1 = lane < nq && !is0 && (o & need) == need;
+                    flat0 = (unsigned)__ballot(is0);
+                    flat1 = (unsigned)__ballot(is1);
+                }
+            }
+            const unsigned flat = flat0 | flat1;
+            if (flat == (1u << nq) - 1u) {                   // answered from the flags: the values the all0 / all1 chunks get below
+                for (int w = threadIdx.x; w < len; w += blockDim.x) short_s[s0 + w] = ((flat1 >> (w / MS_QUART)) & 1u) ? tap_sum : 0.0;
+                if (counters && threadIdx.x == 0) atomicAdd(counters + (2 * (blockIdx.x % MASK_COUNTER_SLOTS)) * MASK_COUNTER_STRIDE, 1);
+                continue;
+            }
+            if (counters && threadIdx.x == 0) atomicAdd(counters + (2 * (blockIdx.x % MASK_COUNTER_SLOTS) + 1) * MASK_COUNTER_STRIDE, 1);
+            if (staged) __syncthreads();                     // the previous segment's window is no longer read
+            staged = true;
+            for (int w = threadIdx.x; w < len + 2 * radius; w += blockDim.x) {
+                bool want = flat == 0u;                      // a settled quarter's part of the window is not read
+                for (int k = 0; k < nq && !want; ++k) want = !((flat >> k) & 1u) && w >= k * MS_QUART && w < (k + 1) * MS_QUART + 2 * radius;
+                if (want) s_all[w] = m[MASK_DS * reflect_index(q0 - radius + w, ns)];
+            }
             __syncthreads();
             for (int c0 = wv * WAVE; c0 < len; c0 += 4 * WAVE) {
                 const float *x0 = s_all + c0;                // this chunk's window: cl + 2r values
                 const int cl = len - c0 < WAVE ? len - c0 : WAVE;
                 const bool live = lane < cl;
-                bool all0 = true, all1 = true;
-                for (int w = lane; w < cl + 2 * radius; w += WAVE) {
-                    const float v = x0[w];
-                    all0 &= v == 0.0f;
-                    all1 &= v == 1.0f;
-                }
                 double acc;
-                if (__all(all0)) {
-                    acc = 0.0;
-                } else if (__all(all1)) {
-                    acc = tap_sum;
+                if ((flat >> (c0 / MS_QUART)) & 1u) {        // (a chunk lies inside one quarter)
+                    acc = ((flat1 >> (c0 / MS_QUART)) & 1u) ? tap_sum : 0.0;
                 } else {
-                    acc = 0.0;
-                    const float *x = x0 + lane;
-                    if (live)
-                        for (int j = 0; j <= 2 * radius; ++j) acc += s_taps[j] * (double)x[j];
+                    bool all0 = true, all1 = true;
+                    for (int w = lane; w < cl + 2 * radius; w += WAVE) {
+                        const float v = x0[w];
+                        all0 &= v == 0.0f;
+                        all1 &= v == 1.0f;
+                    }
+                    if (__all(all0)) {
+                        acc = 0.0;
+                    } else if (__all(all1)) {
+                        acc = tap_sum;
+                    } else {
+                        acc = 0.0;
+                        const float *x = x0 + lane;
+                        if (live)
+                            for (int j = 0; j <= 2 * radius; ++j) acc += s_taps[j] * (double)x[j];
+                    }
                 }
                 if (live) short_s[s0 + c0 + lane] = acc;
             }
@@ -1030,13 +1080,14 @@ int launch_stem_peak(goofer_ctx *ctx, const float *harm, const float *uv, const 
 }
 
 int launch_mask_short(goofer_ctx *ctx, const float *mask, const int64_t *sample_off, int n_notes, int64_t total_samples,
-                      const double *d_taps, int radius, double tap_sum, double *short_s, hipStream_t st)
+                      const double *d_taps, int radius, double tap_sum, double *short_s, const unsigned char *tile_flags,
+                      int32_t *counters, hipStream_t st)
 {
     int64_t total_short = total_samples / MASK_DS + n_notes;
     if (total_short <= 0) return GOOFER_OK;
     hipLaunchKernelGGL(k_mask_short, dim3((unsigned)((total_short + MS_TILE - 1) / MS_TILE)), dim3(256),
                        sizeof(double) * (2 * radius + 1) + sizeof(float) * 4 * MS_MAXWIN, st, mask, sample_off, n_notes, total_short,
-                       d_taps, radius, short_s, tap_sum);
+                       d_taps, radius, short_s, tap_sum, tile_flags, counters);
     LAUNCH_CHECK(ctx);
     return GOOFER_OK;
 }

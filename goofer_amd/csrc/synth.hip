@@ -282,7 +282,9 @@ struct synth_call {
 
     int mask_short() const
     {
-        return launch_mask_short(ctx, b->mask, b->sample_off, n, N, ctx->mask_taps, ctx->mask_taps_radius, ctx->mask_taps_sum, s.short_s, st);
+        // (link.tile_flags: goofer_render_batch, the flags of b->mask as the f0 kernel wrote it — no kernel of any route writes the mask)
+        return launch_mask_short(ctx, b->mask, b->sample_off, n, N, ctx->mask_taps, ctx->mask_taps_radius, ctx->mask_taps_sum, s.short_s,
+                                 link.tile_flags, ctx->ovf_flag ? ctx->ovf_flag + MASK_COUNTERS : nullptr, st);
     }
     int late_picks() const
     {
@@ -416,13 +418,18 @@ static int assemble_batch(goofer_ctx *ctx, const goofer_assembly *asmb, render_l
     int *map_edit;
     float *edit_rows;
     char *recs;
+    unsigned char *flags;
+    const bool want_flags = link.want_tile_flags && a.mask_out && a.total_samples > 0;
     int rc = carve_block(ctx, &ctx->asm_scratch, &ctx->asm_bytes, "assembly scratch", [&](arena &m) {
         map_edit = m.take<int>((size_t)(a.total_edit_rows + a.total_out_rows) + 64);
         edit_rows = m.take<float>(a.edit_rows ? 0 : (size_t)a.total_edit_rows * a.ld);
         // (whatever "value_f64" says: launch_assemble runs k_row_recs / k_env_rows under either arithmetic)
         recs = m.take<char>((size_t)a.total_out_rows * env_row_rec_bytes());
+        // goofer_render_batch: a word per SA_TILE samples of the mask, written by the f0 / mask kernel for k_mask_short
+        flags = m.take<unsigned char>(want_flags ? 4 * (size_t)((a.total_samples + SA_TILE - 1) / SA_TILE) + 64 : 0);
     });
     if (rc) return rc;
+    link.tile_flags_dst = want_flags ? flags : nullptr;
     if (!a.edit_rows) a.edit_rows = edit_rows;
     return launch_assemble(ctx, &a, map_edit, map_edit + a.total_edit_rows, recs, link, st);
 }
@@ -653,6 +660,10 @@ int goofer_render_batch(goofer_ctx *ctx, const goofer_assembly *asmb, const goof
         link.params = b->params;
         link.warp_dst = ctx->warp_rows;
     }
+    // The smoothing of the voicing mask answers flat windows from a word per tile that the kernel which writes the mask leaves
+    // behind.  Only when the synthesis reads the very array the assembly writes, over the same concatenated sample axis.
+    link.want_tile_flags = ctx->mask_flags && asmb->mask_out && asmb->mask_out == b->mask && asmb->total_samples == b->total_samples &&
+                           asmb->n_notes == b->n_notes;
     rc = assemble_batch(ctx, asmb, link, st);
     if (!rc) rc = synth_batch(ctx, b, link, st);
     // the synthesis did not come to place the wait (it refused its batch, or was not reached): f0 / mask are in flight on the side

@@ -231,7 +231,8 @@ class Context:
         return out
 
     def counter(self, name: str) -> int:
-        """Cumulative device-side counter of the handle (goofer_counter): 'pulse_scanned_notes', 'pulse_fallback_notes'."""
+        """Cumulative device-side counter of the handle (goofer_counter): 'pulse_scanned_notes', 'pulse_fallback_notes',
+        'mask_flag_segments', 'mask_staged_segments'."""
         v = C.c_int64(0)
         self._check(self.lib.goofer_counter(self.h, name.encode(), C.byref(v)))
         return int(v.value)

@@ -484,7 +484,10 @@ int goofer_check(goofer_ctx *ctx);
 
 /* Cumulative per-handle counters kept on the device (the call synchronises): "pulse_scanned_notes" = notes whose pulse onsets
  * (GOOFER.py:487-493) were taken from the parallel phase scan, "pulse_fallback_notes" = those of them that had to be walked
- * sequentially afterwards because a sample's phase lay within the scan's rounding band of an integer. */
+ * sequentially afterwards because a sample's phase lay within the scan's rounding band of an integer.
+ * "mask_flag_segments" / "mask_staged_segments": note segments of the mask smoother's 1024-knot tiles (goofer_synth_batch /
+ * goofer_render_batch) that were answered from the f0 kernel's tile flags alone / that staged their window of the mask (option
+ * "mask_flags"; without flags every segment stages; the per-sample loop of a radius above 1792 knots counts nothing). */
 int goofer_counter(goofer_ctx *ctx, const char *name, int64_t *value);
 
 /* gf.smooth_mask_ds (GOOFER.py:556-569) on its own, for a ragged batch of voicing masks (sample_off[n_notes + 1]): decimate by
@@ -594,6 +597,9 @@ const char *goofer_profile_stage_name_ex(const goofer_ctx *ctx, int stage);   /*
  *               decides an index, a threshold or the pitch curve stays fp64; 1: round 4's fp64
  *               arithmetic there (agrees to 2e-8 sample-RMS on the 1024-note batch; not bit-identical)
  *   "sa_fast"   1 (default): k_sample_assemble's branch-free path with all of a thread's loads in flight together; 0: per sample
+ *   "mask_flags" 1 (default): goofer_render_batch has k_sample_assemble leave a word per 1024 samples of the voicing mask (all == 0,
+ *               all == 1, neither) and k_mask_short answer the windows those words settle without loading the mask; 0: no flags
+ *               (goofer_assemble_batch / goofer_synth_batch on their own and goofer_smooth_mask_ds never have them).  Same bits.
  *   "prof_only" s >= 0: goofer_profile_begin .. end record the events of stage s only; -1 (default): every stage     */
 int goofer_set_option(goofer_ctx *ctx, const char *name, int value);
 
