@@ -49,11 +49,15 @@ class BatchCollector:
     or being written out, the requests that arrived meanwhile are decoded, planned and rendered on the other lane
     (SillySampler.py:1196-1224 answers every request with its own render; a song is thousands of them).
     ``noise``: "host" / "device" for the lanes made here (sampler.resolve_noise: None reads ``$GOOFER_NOISE``); an injected
-    renderer brings its own."""
+    renderer brings its own.
+    ``phi_seed`` (keyword only): every note of every batch is rendered with the phases the reference draws under that numpy
+    seed (``Renderer.render(phi_seeds=)``) — what a seeded reference process per note does; a request then renders to the
+    same bytes whatever batch it lands in.  None: each batch keys the device's own phase stream afresh."""
 
     def __init__(self, renderer=None, window_s: float = 0.005, max_batch: int = 4096, max_sources: int = 512, tracker=None,
-                 lanes: int = 2, noise=None):
+                 lanes: int = 2, noise=None, *, phi_seed=None):
         self.noise = S.resolve_noise(noise)                 # (raises before a thread or a lane exists)
+        self.phi_seed = S.check_phi_seed(phi_seed)
         if renderer is not None:
             if noise is not None and getattr(renderer, "noise", self.noise) != self.noise:
                 raise ValueError(f"noise={noise!r}, but the renderer handed in was made with noise={renderer.noise!r}")
@@ -229,16 +233,20 @@ class BatchCollector:
         groups = {}
         for j, (job, own) in enumerate(zip(jobs, owners)):
             groups.setdefault((job[0].sr, job[0].n_fft), []).append(j)
+        if self.phi_seed is None:
+            render = lambda js: renderer.render(js, seed=int(np.random.SeedSequence().generate_state(1)[0]))   # noqa: E731
+        else:                                              # the seeded reference's phases for every note; nothing keyed per batch
+            render = lambda js: renderer.render(js, seed=self.phi_seed & 0xFFFFFFFFFFFFFFFF, phi_seeds=[self.phi_seed] * len(js))   # noqa: E731
         for idxs in groups.values():
             try:
-                outs = renderer.render([jobs[j] for j in idxs], seed=int(np.random.SeedSequence().generate_state(1)[0]))
+                outs = render([jobs[j] for j in idxs])
                 results = dict(zip(idxs, outs))
                 errors = {}
             except Exception:           # noqa: BLE001 - isolate the offender by rendering one by one
                 results, errors = {}, {}
                 for j in idxs:
                     try:
-                        results[j] = renderer.render([jobs[j]], seed=int(np.random.SeedSequence().generate_state(1)[0]))[0]
+                        results[j] = render([jobs[j]])[0]
                     except Exception as e:   # noqa: BLE001
                         errors[j] = e
             self.batches.append(len(idxs))
@@ -296,9 +304,15 @@ def main(argv=None) -> int:
     logging.basicConfig(format="%(message)s", level=logging.INFO)
     argv = list(sys.argv[1:] if argv is None else argv)
     logging.info(f"SillySampler {S.VERSION} (goofer_amd / MI355X)")
+    try:
+        phi_seed = S.env_phi_seed()                        # $GOOFER_PHI_SEED: the server's and the one-note call's phase seed
+    except ValueError as e:
+        logging.error("%s", e)
+        return 1
+    seeded = {} if phi_seed is None else {"phi_seed": phi_seed}
     if not argv or argv[0] == "--host":
         host = argv[1] if len(argv) > 1 else "127.0.0.1"
-        httpd, _ = serve(host=host)
+        httpd, _ = serve(host=host, **({"collector": BatchCollector(phi_seed=phi_seed)} if seeded else {}))
         # A server keeps a voicebank's samples and its own set-up alive for hours: a full collection that walks them is 50-100 ms
         # in the middle of a batch whose device work is 2 ms.  What exists now moves to the permanent generation; the young
         # generations still collect the per-request garbage.
@@ -319,7 +333,7 @@ def main(argv=None) -> int:
         if len(argv) < 13:
             raise TypeError(f"Expected 13 arguments but got {len(argv)}")
         from .render import GooferResampler
-        GooferResampler(*argv[:13])
+        GooferResampler(*argv[:13], **seeded)
     except TypeError as e:
         logging.error("Argument parsing failed: %s", str(e))
         logging.error(HELP)

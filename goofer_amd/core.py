@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .device import Context, default_context, default_params, row_stride
+from .device import Context, check_phi_seed, default_context, default_params, row_stride
 
 DSTORAGE = np.float16
 DCOMPUTE = np.float32
@@ -478,7 +478,7 @@ def _roughness_params(params, kw):
     return params
 
 
-_SYNTH_CALL_ARGS = ("env_spec", "f0_interp", "voicing_mask", "y", "sr", "n_fft", "hop_length", "phi", "seed", "ctx")
+_SYNTH_CALL_ARGS = ("env_spec", "f0_interp", "voicing_mask", "y", "sr", "n_fft", "hop_length", "phi", "phi_seed", "seed", "ctx")
 _NOTE_ARRAYS = ("env_spec", "f0_interp", "voicing_mask", "y")
 SYNTH_FRAME_BUDGET = 1 << 18      # STFT frames per synthesis pass (about 25 minutes of audio at 44.1 kHz, hop 256)
 
@@ -558,7 +558,7 @@ def _rough_settings(kw, sr):
             float(kw.get("rough_noise_amp", 0.6)), float(kw.get("rough_hp_fc", 320.0)))
 
 
-def _prepare_note(c, note, kw, seed, phi, sr, n_fft, hop):
+def _prepare_note(c, note, kw, seed, phi, sr, n_fft, hop, phi_seed=None):
     """Everything gf.synthesize does for one note before the device renders it, in its order: the checks that make it raise,
     the fresh Philox key, then the legacy-RNG draws (f0, sub-harmonic, harmonic volume, breath volume jitter, then the
     roughness noises re-seeded 1337 + idx).  Returns the note's job, or the four empty stems of a note with no samples."""
@@ -630,7 +630,7 @@ def _prepare_note(c, note, kw, seed, phi, sr, n_fft, hop):
             phi = phi.astype(np.float32)
         if phi.shape != (c.n_bins, frames):
             raise ValueError(f"phi must be [{c.n_bins}, {frames}] for this note, got {list(phi.shape)}")
-    job.update(phi=phi, frames=frames, params=params)
+    job.update(phi=phi, phi_seed=phi_seed, frames=frames, params=params)
     if seed is None:
         seed = int(np.random.SeedSequence().generate_state(1, dtype=np.uint64)[0])
     job["seed"] = int(seed) & 0xFFFFFFFFFFFFFFFF
@@ -695,6 +695,37 @@ def _ingest(c, arrays, lengths):
     return rows
 
 
+def _phase_seeds(seeds, phis, n, who):
+    """The per-note numpy phase seeds of a batch call as a checked list (None entries: not seeded): the length, a negative or
+    non-integer seed and a note with both a seed and a phase array raise ValueError — before a context exists."""
+    seeds = [None] * n if seeds is None else [check_phi_seed(s, "phi_seeds[%d]" % i) for i, s in enumerate(seeds)]
+    if len(seeds) != n:
+        raise ValueError(f"{who}: {n} notes and {len(seeds)} phase seeds")
+    both = [i for i, (s, p) in enumerate(zip(seeds, phis)) if s is not None and p is not None]
+    if both:
+        raise ValueError(f"{who}: note {both[0]} has a phase array and a phase seed; give one of them")
+    return seeds
+
+
+def _phases(c, js):
+    """The injected phase rows of a pass (its notes all have them, or none: synth_pass_key): the notes' arrays through
+    goofer_ingest_rows, the seeded notes' numpy streams drawn on the device (goofer_phase_fill), one matrix."""
+    seeds = [j["phi_seed"] for j in js]
+    arrays = [k for k, j in enumerate(js) if j["phi"] is not None]
+    frames = [j["frames"] for j in js]
+    if not arrays and seeds[0] is None:
+        return None
+    if len(arrays) == len(js):
+        return _ingest(c, [j["phi"] for j in js], frames)
+    d_phi = c.phase_fill(seeds, frames)
+    if arrays:                                                # the arrays' rows, ingested back to back, to their notes' places
+        rows = _ingest(c, [js[k]["phi"] for k in arrays], [frames[k] for k in arrays])
+        f_off, a_off = c.offsets(frames), c.offsets([frames[k] for k in arrays])
+        for q, k in enumerate(arrays):
+            d_phi[int(f_off[k]):int(f_off[k + 1])].copy_(rows[int(a_off[q]):int(a_off[q + 1])])
+    return d_phi
+
+
 def _run_pass(c, js, sr):
     """One goofer_synth_batch for the jobs of a pass (and, for the time-stretched route, the ragged warp, blur and stretch in
     front of it).  Returns (host stems {rec, harm, uv, bre}, sample offsets)."""
@@ -702,7 +733,7 @@ def _run_pass(c, js, sr):
     lens = [j["n"] for j in js]
     kw = js[0]["kw"]
     d_env = _ingest(c, [j["env"] for j in js], env_lens)
-    d_phi = _ingest(c, [j["phi"] for j in js], [j["frames"] for j in js]) if js[0]["phi"] is not None else None
+    d_phi = _phases(c, js)
     params = c._c_params(np.concatenate([j["params"] for j in js]))
     seeds = np.array([j["seed"] for j in js], dtype=np.uint64)
     params["seed"][:, 0] = (seeds & np.uint64(0xFFFFFFFF)).astype(np.uint32)    # the kernels XOR it with the batch seed 0: each
@@ -774,7 +805,7 @@ def _roughness(c, js, out, d_mask, s_off, sr):
     return res
 
 
-def synthesize_batch(notes, sr, n_fft=1024, hop_length=256, *, seeds=None, phis=None, ctx=None, **kw):
+def synthesize_batch(notes, sr, n_fft=1024, hop_length=256, *, seeds=None, phis=None, phi_seeds=None, ctx=None, **kw):
     """gf.synthesize for many notes in batched device passes -> one (reconstruct, harmonic, aper_uv, aper_bre) fp32 tuple per
     note, or the exception that note's ``synthesize`` call raises (an empty stretch region, more than sixteen sub-harmonic
     ratios, a non-1-D f0 or mask, ...).
@@ -782,9 +813,11 @@ def synthesize_batch(notes, sr, n_fft=1024, hop_length=256, *, seeds=None, phis=
     ``notes``: mappings with ``env_spec`` ([bins, T] fp32 / fp64 array or a knots dict), ``f0_interp``, ``voicing_mask`` and
     ``y`` (only its length is used), plus any ``synthesize`` keyword, which overrides ``**kw`` for that note.  One geometry
     (``sr``, ``n_fft``, ``hop_length``) per call.  ``seeds``: one Philox key per note (None entries or ``seeds=None``: a
-    fresh key each, like ``synthesize(seed=None)``); ``phis``: one injected [bins, T] phase array (or None) per note.
+    fresh key each, like ``synthesize(seed=None)``); ``phis``: one injected [bins, T] phase array (or None) per note;
+    ``phi_seeds``: one numpy seed (or None) per note, ``synthesize(phi_seed=)`` — a note takes an array or a seed, not both.
+    Seeded notes share their passes with array-injected ones; their phases are drawn on the device (goofer_phase_fill).
 
-    Result i equals ``synthesize(**notes[i] merged over kw, sr=sr, ..., seed=seeds[i], phi=phis[i])`` bit for bit, and the
+    Result i equals ``synthesize(**notes[i] merged over kw, sr=sr, ..., seed=seeds[i], phi=phis[i], phi_seed=phi_seeds[i])`` bit for bit, and the
     legacy ``np.random`` state afterwards equals its state after those calls in list order: every host draw is made in
     note order before any device work.  Notes are cut into passes by ``synth_pass_key`` / ``plan_synth_passes``.  The
     returned arrays may be views into one host block per stem and pass: copy before writing in place.  An unknown keyword
@@ -804,13 +837,14 @@ def synthesize_batch(notes, sr, n_fft=1024, hop_length=256, *, seeds=None, phis=
     phis = [None] * n if phis is None else list(phis)
     if len(seeds) != n or len(phis) != n:
         raise ValueError(f"synthesize_batch: {n} notes, {len(seeds)} seeds and {len(phis)} phase arrays")
+    phi_seeds = _phase_seeds(phi_seeds, phis, n, "synthesize_batch")
     c = _ctx(sr, n_fft, hop_length, ctx)
     base = {**defaults, **kw}
     results, jobs = [None] * n, [None] * n
     for i, note in enumerate(notes):
         merged = {**base, **{k: v for k, v in note.items() if k not in _NOTE_ARRAYS}}
         try:
-            r = _prepare_note(c, note, merged, seeds[i], phis[i], sr, n_fft, hop_length)
+            r = _prepare_note(c, note, merged, seeds[i], phis[i], sr, n_fft, hop_length, phi_seeds[i])
         except Exception as e:                                  # the note's own refusal: its slot, the others render
             results[i] = e
             continue
@@ -825,7 +859,8 @@ def synthesize_batch(notes, sr, n_fft=1024, hop_length=256, *, seeds=None, phis=
 def _render(c, jobs, results, sr):
     """The device half of synthesize_batch: the prepared ``jobs`` (None: nothing to render) cut into passes and rendered, each
     result into its slot of ``results``."""
-    keys = [synth_pass_key(j["kw"], j["phi"] is not None, j["f64_missing"]) if j is not None else None for j in jobs]
+    keys = [synth_pass_key(j["kw"], j["phi"] is not None or j["phi_seed"] is not None, j["f64_missing"]) if j is not None else None
+            for j in jobs]
     for idxs in plan_synth_passes(keys, [j["frames"] if j is not None else 0 for j in jobs]):
         js = [jobs[i] for i in idxs]
         host, s_off, rough = _run_pass(c, js, sr)
@@ -841,7 +876,7 @@ def _render(c, jobs, results, sr):
 
 
 def resynthesize_batch(signals, sr, n_fft=1024, hop_length=256, *, f0_min=75, f0_merge_range=2, pitch_tracker=None, variants=None,
-                       seeds=None, phis=None, ctx=None, **synth_kw):
+                       seeds=None, phis=None, phi_seeds=None, ctx=None, **synth_kw):
     """The reference's wav-to-wav flow (GOOFER.py:1222-1330, test.py) for many signals: per signal ``extract_features``, then
     one ``synthesize`` per variant on those features.  Returns per signal a (reconstruct, harmonic, aper_uv, aper_bre) tuple
     (``variants=None``) or a list of them, one per variant (any ``variants`` list, one entry too); a signal whose analysis raised gets that exception in its slot,
@@ -849,11 +884,12 @@ def resynthesize_batch(signals, sr, n_fft=1024, hop_length=256, *, f0_min=75, f0
 
     ``signals``: mono arrays at one ``sr``.  ``variants``: keyword dicts, each layered over ``synth_kw``; ``formants`` defaults
     to the signal's own extracted formants, as both reference scripts pass them.  ``seeds`` / ``phis``: one Philox key / one
-    injected phase array (or None) per (signal, variant), signal-major: entry ``i * len(variants) + v``.
+    injected phase array (or None) per (signal, variant), signal-major: entry ``i * len(variants) + v``; ``phi_seeds``: one numpy
+    phase seed (or None) per (signal, variant) in the same order, ``synthesize(phi_seed=)`` — an array or a seed, not both.
 
     Result (i, v) equals, bit for bit, ``env, f0, mask, forms, _ = extract_features(y_i, sr, n_fft, hop_length, f0_min=...,
     f0_merge_range=..., pitch_tracker=...)`` then ``synthesize(env, f0, mask, y_i, sr, n_fft, hop_length, formants=forms,
-    **{**synth_kw, **variants[v]}, seed=..., phi=...)`` run signal by signal and variant by variant, and the legacy
+    **{**synth_kw, **variants[v]}, seed=..., phi=..., phi_seed=...)`` run signal by signal and variant by variant, and the legacy
     ``np.random`` state afterwards is the state after those calls: every host draw is made in that order before the device
     work of its pass.  (A host tracker is called for the signals of an analysis pass before that pass's draws.)
 
@@ -876,6 +912,7 @@ def resynthesize_batch(signals, sr, n_fft=1024, hop_length=256, *, f0_min=75, f0
     phis = [None] * (n * V) if phis is None else list(phis)
     if len(seeds) != n * V or len(phis) != n * V:
         raise ValueError(f"resynthesize_batch: {n} signals x {V} variants, {len(seeds)} seeds and {len(phis)} phase arrays")
+    phi_seeds = _phase_seeds(phi_seeds, phis, n * V, "resynthesize_batch")
     c = _ctx(sr, n_fft, hop_length, ctx)
     track_fn = trackers.get(pitch_tracker)
     results = [None] * n
@@ -897,7 +934,8 @@ def resynthesize_batch(signals, sr, n_fft=1024, hop_length=256, *, f0_min=75, f0
             for v, var in enumerate(variants):
                 merged = {**defaults, "formants": f["formants"], **synth_kw, **var}
                 try:
-                    r = _prepare_note(c, note, merged, seeds[i * V + v], phis[i * V + v], sr, n_fft, hop_length)
+                    r = _prepare_note(c, note, merged, seeds[i * V + v], phis[i * V + v], sr, n_fft, hop_length,
+                                      phi_seeds[i * V + v])
                 except Exception as e:                          # the variant's own refusal: its slot, the others render
                     out[v] = e
                     continue
@@ -938,17 +976,23 @@ def synthesize(env_spec, f0_interp, voicing_mask, y, sr, n_fft=1024, hop_length=
                subharm_vibrato_depth=0.1, subharm_f0_jitter=0, subharm_vibrato_delay=0.1, F1_shift=1.0, F2_shift=1.0,
                F3_shift=1.0, F4_shift=1.0, formants=None, roughness_on=False, rough_k_list=(2, 3, 4), rough_h_list=None,
                rough_alpha=0.6, rough_hp_fc=320.0, rough_noise_amp=0.6, rough_noise_smooth_ms=120.0, rough_alpha_slew_ms=120.0,
-               *, phi=None, seed=None, ctx=None):
+               *, phi=None, phi_seed=None, seed=None, ctx=None):
     """gf.synthesize for one note on the GPU -> (reconstruct, harmonic, aper_uv, aper_bre), fp32: synthesize_batch of this
     one note.
 
     The positional order and keyword set are the reference's (GOOFER.py:971-983; ``glottal_smoothing`` is accepted and
-    unused there too); an unknown keyword raises TypeError like it does there.  Three keyword-ONLY additions:
-    ``phi`` ``[bins, T]`` injects the aperiodic branch's random phases (parity runs); otherwise the device draws them
-    from Philox keyed by ``seed`` (a fresh key per call when None, like the reference's unseeded generator); ``ctx``
-    picks the device context."""
-    note = {k: v for k, v in locals().items() if k not in ("sr", "n_fft", "hop_length", "phi", "seed", "ctx")}
-    res = synthesize_batch([note], sr, n_fft, hop_length, seeds=[seed], phis=[phi], ctx=ctx)[0]
+    unused there too); an unknown keyword raises TypeError like it does there.  Four keyword-ONLY additions:
+    ``phi`` ``[bins, T]`` injects the aperiodic branch's random phases (parity runs); ``phi_seed``, a non-negative integer
+    of any size, injects the phases the reference draws with that seed — ``np.random.default_rng(phi_seed).uniform(0, 2 pi,
+    (bins, T)).astype(float32)`` for the note's own frame count T (behind a time stretch: the stretched note's), made on the
+    device, the same bits as passing that array as ``phi``; both together, or a negative seed, raise ValueError.  Otherwise
+    the device draws the phases from Philox keyed by ``seed`` (a fresh key per call when None, like the reference's unseeded
+    generator); ``ctx`` picks the device context."""
+    note = {k: v for k, v in locals().items() if k not in ("sr", "n_fft", "hop_length", "phi", "phi_seed", "seed", "ctx")}
+    if phi is not None and phi_seed is not None:
+        raise ValueError("synthesize: phi and phi_seed are exclusive; give one of them")
+    phi_seed = check_phi_seed(phi_seed)
+    res = synthesize_batch([note], sr, n_fft, hop_length, seeds=[seed], phis=[phi], phi_seeds=[phi_seed], ctx=ctx)[0]
     if isinstance(res, BaseException):
         raise res
     return res

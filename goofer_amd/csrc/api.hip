@@ -908,6 +908,19 @@ int goofer_normal_fill(goofer_ctx *ctx, uint64_t seed, const goofer_note_params 
     return launch_normal_fill(ctx, seed, params, sample_off, n_notes, total_samples, stream_tag, note_on, growl_scale, out, (hipStream_t)stream);
 }
 
+int goofer_phase_fill(goofer_ctx *ctx, const uint64_t *pcg_words, const int64_t *frame_off, int n_notes, int64_t total_frames, int n_bins,
+                      float *out, int ld, void *stream)
+{
+    if (!ctx) return GOOFER_EINVAL;
+    if (!pcg_words || !frame_off || !out) return goofer_fail(ctx, GOOFER_EINVAL, "goofer_phase_fill: null pointer");
+    if (n_notes < 0 || total_frames < 0)
+        return goofer_fail(ctx, GOOFER_EINVAL, "goofer_phase_fill: negative count (%d notes, %lld frames)", n_notes, (long long)total_frames);
+    if (n_bins <= 0 || ld < n_bins) return goofer_fail(ctx, GOOFER_EINVAL, "goofer_phase_fill: %d bins with row stride %d", n_bins, ld);
+    if (((uintptr_t)pcg_words & 7) || ((uintptr_t)frame_off & 7) || ((uintptr_t)out & 3))
+        return goofer_fail(ctx, GOOFER_EINVAL, "goofer_phase_fill: pcg_words and frame_off must be 8-byte aligned, out 4-byte aligned");
+    return launch_phase_fill(ctx, pcg_words, frame_off, n_notes, total_frames, n_bins, out, ld, (hipStream_t)stream);
+}
+
 int goofer_stretch_rows(goofer_ctx *ctx, const float *in, int64_t ld_in, int64_t rows_in, float *out, int64_t ld_out, int64_t rows_out,
                         int n_cols, void *stream)
 {

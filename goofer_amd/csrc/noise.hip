@@ -2,6 +2,8 @@
 //
 //   k_normal_fill     float64 N(0, 1) for every sample of the notes that are switched on (note_on), nothing for the others;
 //                     with a per-note scale the growl factor 0.5 * 2^(scale * z) instead      SillySampler.py:1063-1065
+//   k_phase_fill      the aperiodic branch's phases as a seeded reference run draws them: numpy's PCG64 stream of every note's
+//                     seed, written frame-major into the batch's phase matrix (second half of this file)      GOOFER.py:1151-1152
 //
 // The stream is a definition (tests/noise_ref.py restates it in numpy, word for word):
 //   block    Philox-4x32, 10 rounds (philox_rounds<10>, the round function the phases use with 7)
@@ -95,4 +97,127 @@ int launch_normal_fill(goofer_ctx *ctx, uint64_t seed, const goofer_note_params 
     if (total <= 0 || n_notes <= 0) return GOOFER_OK;
     return launch_per_sample(ctx, k_normal_fill, total, NF_TILE, 0, st, seed, params, sample_off, n_notes, total, (uint32_t)tag, note_on,
                              growl_scale, out);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Seeded phases: np.random.default_rng(seed).uniform(0.0, 2 pi, (n_bins, T)).astype(np.float32) of every note, transposed into
+// the frame-major [total_frames x ld] matrix goofer_batch.phi takes.  The stream (tests/pcg_ref.py restates it):
+//   state    128 bits, state <- state * PCG_MULT + inc (mod 2^128); (state, inc) of a seed come from the host (numpy's
+//            PCG64(seed).state: the SeedSequence hashing is not redone here), four 64-bit words per note: state lo, hi, inc lo, hi
+//   output   of the NEW state: x = hi ^ lo, v = rotr64(x, hi >> 58), d = (v >> 11) * 2^-53 (float64)
+//   value    float32(0.0 + 2 pi * d): the float64 product rounded to nearest even
+//   order    element (b, t) is draw k = b * T + t of its note (C order over (bins, T)), k a 64-bit value
+// The matrix is frame-major and the draws bin-major, so a lane (one bin) jumps to its first draw and then steps from frame to
+// frame: k steps of the generator are state <- A_k state + G_k inc with A_k = MULT^k, G_k = 1 + MULT + .. + MULT^(k-1), and
+// (A, G) of 2^j steps, j < 64, is a table made at compile time (PCG_JUMP) that composes any k from its set bits.
+// A wave owns PF_FRAMES consecutive frames of the concatenated frame axis x 64 consecutive bins: every store instruction covers
+// 256 contiguous bytes of a row; a tile that crosses a note boundary jumps again in the next note.
+struct u128 {
+    uint64_t lo, hi;
+};
+#define PCG_MULT_HI 0x2360ED051FC65DA4ull
+#define PCG_MULT_LO 0x4385DF649FCCF645ull
+#define PF_FRAMES 64
+
+// high 64 bits of a 64 x 64 product from 32-bit pieces (the table below is made by the compiler, for host and device alike)
+constexpr uint64_t mulhi64_c(uint64_t a, uint64_t b)
+{
+    const uint64_t a0 = a & 0xFFFFFFFFull, a1 = a >> 32, b0 = b & 0xFFFFFFFFull, b1 = b >> 32;
+    const uint64_t p00 = a0 * b0, p01 = a0 * b1, p10 = a1 * b0, p11 = a1 * b1;
+    const uint64_t mid = (p00 >> 32) + (p01 & 0xFFFFFFFFull) + (p10 & 0xFFFFFFFFull);
+    return p11 + (p01 >> 32) + (p10 >> 32) + (mid >> 32);
+}
+constexpr u128 mul128_c(u128 a, u128 b)   // a * b mod 2^128
+{
+    return u128{a.lo * b.lo, mulhi64_c(a.lo, b.lo) + a.lo * b.hi + a.hi * b.lo};
+}
+constexpr u128 add128_c(u128 a, u128 b)
+{
+    const uint64_t lo = a.lo + b.lo;
+    return u128{lo, a.hi + b.hi + (lo < a.lo ? 1u : 0u)};
+}
+
+struct pcg_jump_table {
+    uint64_t w[64][4];   // A lo, A hi, G lo, G hi of 2^j steps
+};
+constexpr pcg_jump_table make_pcg_jump()
+{
+    pcg_jump_table t{};
+    u128 A{PCG_MULT_LO, PCG_MULT_HI}, G{1, 0};
+    for (int j = 0; j < 64; ++j) {
+        t.w[j][0] = A.lo; t.w[j][1] = A.hi; t.w[j][2] = G.lo; t.w[j][3] = G.hi;
+        G = add128_c(mul128_c(G, A), G);                      // (A, G) o (A, G) = (A A, G A + G)
+        A = mul128_c(A, A);
+    }
+    return t;
+}
+__constant__ const pcg_jump_table PCG_JUMP = make_pcg_jump();
+
+__device__ __forceinline__ u128 mul128(u128 a, u128 b)
+{
+    return u128{a.lo * b.lo, __umul64hi(a.lo, b.lo) + a.lo * b.hi + a.hi * b.lo};
+}
+__device__ __forceinline__ u128 add128(u128 a, u128 b)
+{
+    const uint64_t lo = a.lo + b.lo;
+    return u128{lo, a.hi + b.hi + (lo < a.lo ? 1u : 0u)};
+}
+
+__global__ __launch_bounds__(256) void k_phase_fill(const uint64_t *__restrict__ words, const int64_t *__restrict__ frame_off,
+                                                    int n_notes, int64_t total_frames, int n_bins, int chunks, int ld,
+                                                    float *__restrict__ out)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t unit = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // wave-uniform
+    const int64_t ft = unit / chunks;
+    const int b = (int)(unit - ft * chunks) * 64 + lane;       // this lane's bin
+    const int64_t g0 = ft * PF_FRAMES;
+    if (g0 >= total_frames) return;
+    const int64_t g1 = g0 + PF_FRAMES < total_frames ? g0 + PF_FRAMES : total_frames;   // the tile's frames are [g0, g1)
+    const bool live = b < n_bins;
+    int note = __builtin_amdgcn_readfirstlane(csr_find(frame_off, n_notes, g0));
+    int64_t g = g0;
+    while (g < g1) {
+        while (note + 1 < n_notes && frame_off[note + 1] <= g) ++note;      // (notes without a frame)
+        const int64_t t0 = frame_off[note], t1 = frame_off[note + 1];
+        const int64_t end = t1 < g1 ? t1 : g1;
+        if (end <= g) break;                                   // offsets that do not reach total_frames: nothing beyond them
+        const uint64_t *w = words + 4 * (int64_t)note;
+        const u128 inc{w[2], w[3]};
+        if (!(inc.lo & 1)) {                                   // an increment is odd: a zero record is a note that is not seeded
+            g = end;
+            continue;
+        }
+        u128 s{w[0], w[1]};
+        const uint64_t k = (uint64_t)b * (uint64_t)(t1 - t0) + (uint64_t)(g - t0);   // the lane's first draw of this note
+        for (int j = 0; j < 64 && (k >> j) != 0; ++j) {
+            if ((k >> j) & 1) {
+                const u128 A{PCG_JUMP.w[j][0], PCG_JUMP.w[j][1]}, G{PCG_JUMP.w[j][2], PCG_JUMP.w[j][3]};
+                s = add128(mul128(A, s), mul128(G, inc));
+            }
+        }
+        float *row = out + g * (int64_t)ld + b;
+        for (; g < end; ++g, row += ld) {
+            s = add128(mul128(s, u128{PCG_MULT_LO, PCG_MULT_HI}), inc);
+            const uint64_t x = s.hi ^ s.lo;
+            const unsigned r = (unsigned)(s.hi >> 58);
+            const uint64_t v = (x >> r) | (x << ((64u - r) & 63u));
+            const double d = (double)(v >> 11) * 0x1p-53;
+            if (live) *row = (float)(0.0 + 0x1.921fb54442d18p+2 * d);   // low + (high - low) * d, 2 pi as numpy holds it
+        }
+    }
+}
+
+int launch_phase_fill(goofer_ctx *ctx, const uint64_t *words, const int64_t *frame_off, int n_notes, int64_t total_frames, int n_bins,
+                      float *out, int ld, hipStream_t st)
+{
+    if (total_frames <= 0 || n_notes <= 0) return GOOFER_OK;
+    const int chunks = (n_bins + 63) / 64;
+    const int64_t units = ((total_frames + PF_FRAMES - 1) / PF_FRAMES) * chunks;
+    const int64_t blocks = (units + 3) / 4;
+    if (blocks > 0x7fffffffLL) return goofer_fail(ctx, GOOFER_EINVAL, "goofer_phase_fill: %lld tiles in one call", (long long)blocks);
+    hipLaunchKernelGGL(k_phase_fill, dim3((unsigned)blocks), dim3(256), 0, st, words, frame_off, n_notes, total_frames, n_bins, chunks, ld,
+                       out);
+    LAUNCH_CHECK(ctx);
+    return GOOFER_OK;
 }

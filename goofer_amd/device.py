@@ -7,11 +7,13 @@ of the reference's ``[bins, frames]`` — with fp32 rows padded to ``ld`` (a mul
 from __future__ import annotations
 
 import ctypes as C
+import functools
 
 import numpy as np
 import torch
 
 from . import _lib
+from .sampler import check_phi_seed
 
 
 _ROW_ALIGN = int(__import__("os").environ.get("GOOFER_ROW_ALIGN", "4"))
@@ -31,6 +33,25 @@ def spec_stride(n_bins: int) -> int:
 
 class GooferError(RuntimeError):
     pass
+
+
+@functools.lru_cache(maxsize=4096)
+def _pcg64_state(seed: int):
+    st = np.random.PCG64(seed).state["state"]
+    s, inc = int(st["state"]), int(st["inc"])
+    m = 0xFFFFFFFFFFFFFFFF
+    return s & m, s >> 64, inc & m, inc >> 64
+
+
+def pcg64_words(seeds) -> np.ndarray:
+    """goofer_phase_fill's per-note records, uint64 [n, 4]: (state lo, state hi, inc lo, inc hi) of ``np.random.PCG64(seed)`` —
+    the generator ``default_rng(seed)`` starts from; the seeding itself (SeedSequence) stays numpy's.  A ``None`` seed gives
+    the zero record: that note is not seeded and the fill leaves its rows alone."""
+    w = np.zeros((len(seeds), 4), dtype=np.uint64)
+    for i, sd in enumerate(seeds):
+        if sd is not None:
+            w[i] = _pcg64_state(check_phi_seed(sd))
+    return w
 
 
 def _ptr(t):
@@ -227,6 +248,52 @@ class Context:
                 raise ValueError(f"normal_fill: {what} is one {dt} per note")
         self._check(self.lib.goofer_normal_fill(self.h, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(params), _ptr(d_s), n, total, int(tag),
                                                 _ptr(note_on), _ptr(growl_scale), _ptr(out), self._stream()))
+        self._fill_keep = keep                                  # this call's uploads, until the next call (stream order frees them safely)
+        return out
+
+    def phase_fill(self, seeds, frames, out=None, n_bins=None):
+        """The aperiodic branch's phases of a seeded reference run for the notes of a ragged batch, drawn on the device
+        (goofer_phase_fill; the stream's definition: include/goofer_hip.h, restated in tests/pcg_ref.py): note i's rows are
+        ``np.random.default_rng(seeds[i]).uniform(0, 2 pi, (n_bins, T_i)).astype(np.float32).T``, bit for bit — what
+        ``synth_batch(phi=)`` takes.  Asynchronous on the current stream.
+
+        ``seeds``: one non-negative int (any size) or None per note — the rows of a None note are not written — or the device
+        copy of ``pcg64_words(seeds)`` (int64 [n, 4]).  ``frames``: the notes' frame counts (host sequence), or the device int64
+        CSR offsets ``[n + 1]`` — then ``out`` gives the total.  ``out``: the ld-strided fp32 ``[sum T_i, n_bins]`` rows to fill
+        (``Context.rows``; default: new ones, of the plan's ``n_bins`` unless given).  Returns the rows."""
+        keep = []
+        if isinstance(frames, torch.Tensor):
+            d_f = frames
+            if out is None:
+                raise ValueError("phase_fill: device offsets need the rows to fill (out=)")
+            n, total = d_f.numel() - 1, out.shape[0]
+        else:
+            counts = [int(v) for v in frames]
+            if any(v < 0 for v in counts):
+                raise ValueError("phase_fill: a negative frame count")
+            f_off = self.offsets(counts)
+            n, total = len(counts), int(f_off[-1])
+            keep.append(self.tensor(f_off))
+            d_f = keep[-1]
+        if d_f.dtype != torch.int64 or not d_f.is_contiguous():
+            raise ValueError("phase_fill: the frame offsets are a contiguous int64 tensor")
+        if isinstance(seeds, torch.Tensor):
+            d_w = seeds
+        else:
+            if len(seeds) != n:
+                raise ValueError(f"phase_fill: {len(seeds)} seeds for {n} notes")
+            keep.append(self.tensor(pcg64_words(seeds).view(np.int64)))
+            d_w = keep[-1]
+        if d_w.dtype != torch.int64 or not d_w.is_contiguous() or d_w.numel() != 4 * n:
+            raise ValueError("phase_fill: the seed records are a contiguous int64 [n, 4] tensor (pcg64_words)")
+        if out is None:
+            out = self.rows(total, self.n_bins if n_bins is None else int(n_bins))
+        nb = out.shape[1] if out.dim() == 2 else -1
+        if (out.dim() != 2 or out.dtype != torch.float32 or out.device != self.device or out.shape[0] != total
+                or (n_bins is not None and nb != int(n_bins)) or (total and (out.stride(1) != 1 or out.stride(0) < nb))):
+            raise ValueError("phase_fill: out must be the batch's fp32 [%d, n_bins] rows on this context's device" % total)
+        if total and n:
+            self._check(self.lib.goofer_phase_fill(self.h, _ptr(d_w), _ptr(d_f), n, total, nb, _ptr(out), out.stride(0), self._stream()))
         self._fill_keep = keep                                  # this call's uploads, until the next call (stream order frees them safely)
         return out
 

@@ -19,7 +19,7 @@ import torch
 
 from . import _lib
 from . import sampler as S
-from .device import Context, default_context, default_params, row_stride
+from .device import Context, check_phi_seed, default_context, default_params, pcg64_words, row_stride
 
 
 # The assembly and render kernels of the resampler path stop at the reference sampler's geometry family (SillySampler.py:14
@@ -427,8 +427,9 @@ class Renderer:
     def render(self, jobs, seed: int = 0, phi_seeds=None, return_parts: bool = False):
         """jobs: list of (Source, Request).  Returns a list of fp32 arrays (the mix the reference writes to
         out.wav); with ``return_parts`` also a dict of device-side intermediates for tests.
-        ``phi_seeds``: per-note seeds for INJECTED phases (parity with a seeded reference run); otherwise the
-        device draws phases from Philox keyed by ``seed`` and the note index.  A renderer made with ``noise="device"``
+        ``phi_seeds``: per-note seeds for INJECTED phases (parity with a seeded reference run: numpy's stream of each seed,
+        drawn on the device by ``Context.phase_fill``); otherwise the device draws phases from Philox keyed by ``seed`` and
+        the note index.  A renderer made with ``noise="device"``
         draws the jitter / growl normals on the device whether or not the phases are injected."""
         if not jobs:
             return []
@@ -458,6 +459,8 @@ class Renderer:
         drawn = None
         if prep.get("device_noise") is not None:              # before the assembly (it reads f0_mul) and the synthesis are enqueued
             noise_f0, noise_vol, drawn = self._device_noise(prep, seed)
+        if prep.get("phi_words") is not None:                 # the seeded phases of every note, ahead of the synthesis that reads them
+            ctx.phase_fill(prep["phi_words"], prep["offsets"]["d_f"], out=prep["phi"])
         # Notes with the 'sg' pulse layer or the 'sr' volume jitter are synthesised by the one-kernel-per-step pipeline (those
         # layers edit the pulse train / the stems between its steps), everything else by the stem walkers — and the library
         # picks the pipeline per BATCH (synth_route_of in goofer_amd/csrc/synth.hip).  So that a note renders to the same bits
@@ -613,6 +616,9 @@ class Renderer:
         never read — a fifth of the rows of a one-second note.  ``False`` keeps them (tests that compare the whole envelope).
         A renderer made with ``noise="device"`` draws no random number here and makes no per-sample host array for sh / sr / sj:
         ``run`` draws them on the device, keyed by its seed.
+        ``phi_seeds``: one non-negative int per note — the phases a reference run seeded with it draws.  Only the generators'
+        starting words are staged here (four 64-bit words per note); ``run`` fills ``prep["phi"]`` on the device before the
+        synthesis (``Context.phase_fill``), so the matrix holds nothing until a run has been enqueued.
 
         Host cost: the per-note decisions run in the library's host planner (a batch per call, csrc/planner.hip) and everything
         here is column arithmetic over the batch — no per-note Python except a handful of attribute reads."""
@@ -634,6 +640,10 @@ class Renderer:
 
     def _prepare(self, stg, jobs, phi_seeds, note_ids, trim_rows, device_calls=True):
         device_noise = self.noise == "device"
+        if phi_seeds is not None:                              # before anything is planned or uploaded
+            phi_seeds = [check_phi_seed(sd, "phi_seeds[%d]" % i) for i, sd in enumerate(phi_seeds)]
+            if None in phi_seeds:
+                raise ValueError("phi_seeds: one seed per note (a batch injects the phases of all its notes or of none)")
         tr = getattr(self, "trace_prepare", None)              # a list: (label, perf_counter) marks of the host phases (scripts/prepare_phases.py)
         if tr is None:
             _T = lambda label: None
@@ -655,6 +665,8 @@ class Renderer:
                              "goofer_amd.core.synthesize takes the larger sizes")
         n = rb.n
         c = rb.col
+        if phi_seeds is not None and len(phi_seeds) != n:
+            raise ValueError(f"{n} notes and {len(phi_seeds)} phase seeds")
         # the samples' rows in the arena's tables (a voicebank sample rendered by several notes is resident once: same Source object)
         rows, T_, g_lerp_tabs, d_knots, d_mask_src = self.sources.lookup(srcs, stg)   # resident in HBM; new samples are uploaded here
         _T("uniq")
@@ -866,16 +878,16 @@ class Renderer:
             f0_growl = torch.zeros(o_off, dtype=torch.float32, device=ctx.device)
             a.f0_mul, a.f0_mul_out = d["f0_mul"].data_ptr(), f0_growl.data_ptr()
         has_post = bool(((c_su > 0) | (c_sj > 0) | (c_sa > 0) | (c_sd > 0) | (c_st != 0) | (c_pd != 0)).any()) or any_fry
-        phi = None
+        phi = phi_words = None
         if phi_seeds is not None:
-            mats = []
-            for n_, sd in zip(lens_l, phi_seeds):
-                T = 1 + n_ // self.hop
-                mats.append(np.random.default_rng(sd).uniform(0.0, 2.0 * np.pi, size=(B, T)).astype(np.float32).T)
-            phi = ctx.rows_from(np.concatenate(mats))
+            # run() draws them (Context.phase_fill: numpy's stream of each seed, made on the device): here the generators'
+            # starting words, four per note, in the staging block
+            phi_words = stg.put(pcg64_words(phi_seeds).view(np.int64))
         _T("post")
         offsets = ctx.device_offsets(env_lens_l, lens_l, par, put=stg.put, hop=self.hop)
         frames = int(offsets["f_off"][-1])
+        if phi_words is not None:
+            phi = torch.empty((frames, ld), dtype=torch.float32, device=ctx.device)[:, :B]
         _T("offsets")
         stg.ship()                                             # one H2D copy for everything above
         if device_calls:
@@ -885,7 +897,7 @@ class Renderer:
         return {"assembly": a, "keep": d, "env": env, "f0": f0, "mask": mask, "params": par, "lens": lens_l, "env_lens": env_lens_l,
                 "noise_f0": noise_f0, "noise_vol": noise_vol, "device_noise": dev_noise, "subharm": bool((c_sub > 0).any()),
                 "post": post if has_post else None, "growl": growl, "f0_growl": f0_growl, "bend_out": bend_out, "requests": rb, "sources": srcs, "geometry": (sr, n_fft, self.hop, frames, o_off, n),
-                "formants": d_formants, "phi": phi, "planned": pb, "offsets": offsets,
+                "formants": d_formants, "phi": phi, "phi_words": phi_words, "planned": pb, "offsets": offsets,
                 "sample_off": sample_off, "env_off": env_off, "frames": frames, "samples": o_off, "edit_rows": e_off}
 
 
@@ -899,13 +911,18 @@ class GooferResampler:
     Uses ``<in_stem>_features.goofy`` next to the input wav; when it is missing the wav is analysed and the cache written
     first, like the reference does (``goofer_amd.trackers``: needs a tracker for the Praat half — parity unpinned).  The first
     render then uses the features as cached (fp16 knots), where the reference's first render still holds the unquantised
-    envelope.  wav output uses the stdlib ``wave`` module (PCM16, what soundfile's default WAV subtype writes)."""
+    envelope.  wav output uses the stdlib ``wave`` module (PCM16, what soundfile's default WAV subtype writes).
+
+    ``phi_seed`` (keyword only): the note's phases are the ones the reference draws when its generator is seeded with it
+    (numpy's stream, made on the device); ``seed`` keeps its meaning, the Philox key of the device's own phases, when
+    ``phi_seed`` is None."""
 
     def __init__(self, in_file, out_file, pitch, velocity, flags="", offset=0, length=1000, consonant=0, cutoff=0,
                  volume=100, modulation=0, tempo="!120", pitch_string="AA", renderer: Renderer | None = None, seed=None, tracker=None,
-                 noise=None):
+                 noise=None, *, phi_seed=None):
         from pathlib import Path
         from . import core
+        phi_seed = check_phi_seed(phi_seed)                    # (refused here, before anything is read or launched)
         self.in_file, self.out_file = Path(in_file), Path(out_file)
         self.request = S.decode_request(pitch, velocity, flags, offset, length, consonant, cutoff, volume, modulation, tempo,
                                         pitch_string)
@@ -920,7 +937,7 @@ class GooferResampler:
         self.source = Source.from_pack(env, f0, mask, forms, sr, ylen)
         if seed is None:
             seed = int(np.random.SeedSequence().generate_state(1, dtype=np.uint64)[0])
-        self.out = self.renderer.render([(self.source, self.request)], seed=seed)[0]
+        self.out = self.renderer.render([(self.source, self.request)], seed=seed, **({} if phi_seed is None else {"phi_seeds": [phi_seed]}))[0]
         write_wav(self.out_file, self.out, sr)
 
 

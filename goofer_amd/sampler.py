@@ -12,6 +12,7 @@ Reference: ``SillySampler.py:50-93`` (decode), ``:286-411`` (flag scaling), ``:4
 from __future__ import annotations
 
 import functools
+import operator
 import re
 from dataclasses import dataclass, field
 
@@ -42,6 +43,34 @@ def resolve_noise(noise=None) -> str:
     if noise not in NOISE_SOURCES:
         raise ValueError(f"noise source {noise!r}: GOOFER_NOISE / noise= is one of {', '.join(NOISE_SOURCES)}")
     return noise
+
+
+def check_phi_seed(seed, what="phi_seed"):
+    """``seed`` as the Python int numpy's ``default_rng`` would take: a non-negative integer of any size (None stays None)."""
+    if seed is None:
+        return None
+    try:
+        if isinstance(seed, (bool, np.bool_)):
+            raise TypeError
+        seed = int(operator.index(seed))
+    except TypeError:
+        raise ValueError(f"{what} must be a non-negative integer, got {seed!r}") from None
+    if seed < 0:
+        raise ValueError(f"{what} must be a non-negative integer, got {seed}")
+    return seed
+
+
+def env_phi_seed():
+    """``$GOOFER_PHI_SEED``: the numpy seed of the injected phases for the front ends (``GooferResampler(phi_seed=)``,
+    ``cli.BatchCollector(phi_seed=)``) as an int, None when unset or empty; a value that is not a non-negative decimal
+    integer raises ``ValueError``."""
+    import os
+    text = (os.environ.get("GOOFER_PHI_SEED") or "").strip()
+    if not text:
+        return None
+    if not (text.isascii() and text.isdigit()):
+        raise ValueError(f"GOOFER_PHI_SEED={text!r}: the phase seed is a non-negative integer")
+    return int(text)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -570,6 +570,20 @@ int goofer_normal_fill(goofer_ctx *ctx, uint64_t seed, const goofer_note_params 
                        int64_t total_samples, int stream_tag, const unsigned char *note_on, const double *growl_scale, double *out,
                        void *stream);
 
+/* The aperiodic branch's phases as a seeded reference run draws them (GOOFER.py:1151-1152), on the device (noise.hip): for note
+ * k with T_k = frame_off[k + 1] - frame_off[k] frames, out[(frame_off[k] + t) * ld + b], b < n_bins, is element [b, t] of
+ * np.random.default_rng(seed_k).uniform(0.0, 2 pi, (n_bins, T_k)).astype(np.float32), bit for bit: the layout goofer_batch.phi
+ * takes.  The stream is numpy's PCG64: state <- state * 0x2360ED051FC65DA44385DF649FCCF645 + inc (mod 2^128), and from the NEW
+ * state x = hi ^ lo, v = rotr64(x, hi >> 58), d = (v >> 11) * 2^-53 in float64, value = float32(0.0 + 2 pi * d) rounded to
+ * nearest even; element [b, t] is draw b * T_k + t of its note (a 64-bit index), reached by the generator's jump-ahead.
+ * Seeding stays with the caller: pcg_words holds four 64-bit words per note, (state lo, state hi, inc lo, inc hi) of
+ * np.random.PCG64(seed_k).state; a note whose increment is even (a zero record: a real increment is odd) is not seeded, and
+ * its rows are not written.  The columns n_bins .. ld - 1 are not written either.  pcg_words, frame_off ([n_notes + 1], from 0
+ * to total_frames) and out are device arrays; asynchronous on `stream`; needs no plan and no scratch.  GOOFER_EINVAL for a null
+ * pointer, a negative count, n_bins < 1 or ld < n_bins, pcg_words or frame_off not 8-byte aligned, out not 4-byte aligned. */
+int goofer_phase_fill(goofer_ctx *ctx, const uint64_t *pcg_words, const int64_t *frame_off, int n_notes, int64_t total_frames,
+                      int n_bins, float *out, int ld, void *stream);
+
 /* ---- measurement / test hooks --------------------------------------------------------------- */
 
 /* HIP-event timing of every stage of goofer_synth_batch on the caller's stream: begin() arms up to
