@@ -52,12 +52,16 @@ class BatchCollector:
     renderer brings its own.
     ``phi_seed`` (keyword only): every note of every batch is rendered with the phases the reference draws under that numpy
     seed (``Renderer.render(phi_seeds=)``) — what a seeded reference process per note does; a request then renders to the
-    same bytes whatever batch it lands in.  None: each batch keys the device's own phase stream afresh."""
+    same bytes whatever batch it lands in.  None: each batch keys the device's own phase stream afresh.
+    ``noise_seed`` (keyword only): an int in [0, 2**32) — every request's sh / sr jitter is what a reference process draws after
+    ``np.random.seed(noise_seed)`` (``Renderer.render(noise_seeds=)``: each request is one reference process), made on the
+    device.  None: the lanes' ``noise`` source."""
 
     def __init__(self, renderer=None, window_s: float = 0.005, max_batch: int = 4096, max_sources: int = 512, tracker=None,
-                 lanes: int = 2, noise=None, *, phi_seed=None):
+                 lanes: int = 2, noise=None, *, phi_seed=None, noise_seed=None):
         self.noise = S.resolve_noise(noise)                 # (raises before a thread or a lane exists)
         self.phi_seed = S.check_phi_seed(phi_seed)
+        self.noise_seed = S.check_noise_seed(noise_seed)
         if renderer is not None:
             if noise is not None and getattr(renderer, "noise", self.noise) != self.noise:
                 raise ValueError(f"noise={noise!r}, but the renderer handed in was made with noise={renderer.noise!r}")
@@ -233,10 +237,12 @@ class BatchCollector:
         groups = {}
         for j, (job, own) in enumerate(zip(jobs, owners)):
             groups.setdefault((job[0].sr, job[0].n_fft), []).append(j)
+        jitter = (lambda js: {}) if self.noise_seed is None else (lambda js: {"noise_seeds": [self.noise_seed] * len(js)})
         if self.phi_seed is None:
-            render = lambda js: renderer.render(js, seed=int(np.random.SeedSequence().generate_state(1)[0]))   # noqa: E731
+            render = lambda js: renderer.render(js, seed=int(np.random.SeedSequence().generate_state(1)[0]), **jitter(js))   # noqa: E731
         else:                                              # the seeded reference's phases for every note; nothing keyed per batch
-            render = lambda js: renderer.render(js, seed=self.phi_seed & 0xFFFFFFFFFFFFFFFF, phi_seeds=[self.phi_seed] * len(js))   # noqa: E731
+            render = lambda js: renderer.render(js, seed=self.phi_seed & 0xFFFFFFFFFFFFFFFF, phi_seeds=[self.phi_seed] * len(js),   # noqa: E731
+                                                **jitter(js))
         for idxs in groups.values():
             try:
                 outs = render([jobs[j] for j in idxs])
@@ -306,13 +312,16 @@ def main(argv=None) -> int:
     logging.info(f"SillySampler {S.VERSION} (goofer_amd / MI355X)")
     try:
         phi_seed = S.env_phi_seed()                        # $GOOFER_PHI_SEED: the server's and the one-note call's phase seed
+        noise_seed = S.env_noise_seed()                    # $GOOFER_NOISE_SEED: their legacy seed of the sh / sr jitter
     except ValueError as e:
         logging.error("%s", e)
         return 1
     seeded = {} if phi_seed is None else {"phi_seed": phi_seed}
+    if noise_seed is not None:
+        seeded["noise_seed"] = noise_seed
     if not argv or argv[0] == "--host":
         host = argv[1] if len(argv) > 1 else "127.0.0.1"
-        httpd, _ = serve(host=host, **({"collector": BatchCollector(phi_seed=phi_seed)} if seeded else {}))
+        httpd, _ = serve(host=host, **({"collector": BatchCollector(**seeded)} if seeded else {}))
         # A server keeps a voicebank's samples and its own set-up alive for hours: a full collection that walks them is 50-100 ms
         # in the middle of a batch whose device work is 2 ms.  What exists now moves to the permanent generation; the young
         # generations still collect the per-request garbage.

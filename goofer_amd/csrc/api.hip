@@ -431,14 +431,21 @@ int goofer_host_gauss_rows(const double *x, int64_t rows, int T, const double *t
  * onset slots (n / 2 + 16 per note — more than one pulse per two samples; the onsets beyond were dropped.  The 'sg' layer's
  * trackers fire at most once per sample into n + 16 slots per note, the layout such a batch leaves behind).  The flag is a
  * handle-owned word every pulse-chain launch (goofer_pulse_train, goofer_synth_batch / goofer_render_batch incl. the extra
- * synthesis calls of the post chain) raises with atomicMax; it stays up until this call reads and clears it. */
+ * synthesis calls of the post chain) raises with atomicMax; it stays up until this call reads and clears it.  Word LEGACY_FLAG
+ * beside it is goofer_legacy_normal_fill's: a note that ran into the bound of its block loop. */
 int goofer_check(goofer_ctx *ctx)
 {
     if (!ctx) return GOOFER_EINVAL;
     HIP_TRY(ctx, hipDeviceSynchronize());
     if (!ctx->ovf_flag) return GOOFER_OK;
-    int32_t v = 0;
-    HIP_TRY(ctx, hipMemcpy(&v, ctx->ovf_flag, sizeof(v), hipMemcpyDeviceToHost));
+    int32_t w[LEGACY_FLAG + 1] = {0};
+    HIP_TRY(ctx, hipMemcpy(w, ctx->ovf_flag, sizeof(w), hipMemcpyDeviceToHost));
+    if (w[LEGACY_FLAG] != 0) {                                       // goofer_legacy_normal_fill: a note ran into its block bound
+        HIP_TRY(ctx, hipMemset(ctx->ovf_flag + LEGACY_FLAG, 0, sizeof(int32_t)));   // reported once
+        return goofer_fail(ctx, GOOFER_EINVAL, "note %d of a legacy normal fill since the last check did not get its normals within "
+                           "its block bound: its outputs are incomplete", w[LEGACY_FLAG] - 1);
+    }
+    const int32_t v = w[0];
     if (v != 0) {
         HIP_TRY(ctx, hipMemset(ctx->ovf_flag, 0, sizeof(v)));        // reported once
         return goofer_fail(ctx, GOOFER_EINVAL, "note %d of a batch since the last check has more pulse onsets than n / 2 + 16 (f0 above "
@@ -588,6 +595,7 @@ int goofer_set_option(goofer_ctx *ctx, const char *name, int value)
     if (!strcmp(name, "td_blur")) { ctx->td_blur = value != 0; return GOOFER_OK; }
     if (!strcmp(name, "pulse_scan")) { ctx->pulse_scan = value < 0 ? 0 : (value > 2 ? 2 : value); return GOOFER_OK; }
     if (!strcmp(name, "sa_fast")) { ctx->sa_fast = value != 0; return GOOFER_OK; }
+    if (!strcmp(name, "legacy_wave")) { ctx->legacy_wave = value != 0; return GOOFER_OK; }
     if (!strcmp(name, "mask_flags")) { ctx->mask_flags = value != 0; return GOOFER_OK; }
     if (!strcmp(name, "value_f64")) { ctx->value_f64 = value != 0; return GOOFER_OK; }
     return goofer_fail(ctx, GOOFER_EINVAL, "unknown option %s", name);
@@ -919,6 +927,21 @@ int goofer_phase_fill(goofer_ctx *ctx, const uint64_t *pcg_words, const int64_t 
     if (((uintptr_t)pcg_words & 7) || ((uintptr_t)frame_off & 7) || ((uintptr_t)out & 3))
         return goofer_fail(ctx, GOOFER_EINVAL, "goofer_phase_fill: pcg_words and frame_off must be 8-byte aligned, out 4-byte aligned");
     return launch_phase_fill(ctx, pcg_words, frame_off, n_notes, total_frames, n_bins, out, ld, (hipStream_t)stream);
+}
+
+int goofer_legacy_normal_fill(goofer_ctx *ctx, const uint32_t *seeds, const unsigned char *stream_on, const int64_t *sample_off, int n_notes,
+                              int64_t total_samples, double *out_f0, double *out_vol_h, double *out_vol_b, int64_t *attempts, void *stream)
+{
+    if (!ctx) return GOOFER_EINVAL;
+    if (!seeds || !stream_on || !sample_off) return goofer_fail(ctx, GOOFER_EINVAL, "goofer_legacy_normal_fill: null pointer");
+    if (!out_f0 && !out_vol_h && !out_vol_b && !attempts) return goofer_fail(ctx, GOOFER_EINVAL, "goofer_legacy_normal_fill: no output");
+    if (n_notes < 0 || total_samples < 0)
+        return goofer_fail(ctx, GOOFER_EINVAL, "goofer_legacy_normal_fill: negative count (%d notes, %lld samples)", n_notes, (long long)total_samples);
+    if (((uintptr_t)seeds & 3) || ((uintptr_t)sample_off & 7) || ((uintptr_t)out_f0 & 7) || ((uintptr_t)out_vol_h & 7) || ((uintptr_t)out_vol_b & 7) ||
+        ((uintptr_t)attempts & 7))
+        return goofer_fail(ctx, GOOFER_EINVAL, "goofer_legacy_normal_fill: seeds must be 4-byte aligned, sample_off, the outputs and attempts 8-byte aligned");
+    if (total_samples == 0 && !attempts) return GOOFER_OK;
+    return launch_legacy_normal_fill(ctx, seeds, stream_on, sample_off, n_notes, out_f0, out_vol_h, out_vol_b, attempts, (hipStream_t)stream);
 }
 
 int goofer_stretch_rows(goofer_ctx *ctx, const float *in, int64_t ld_in, int64_t rows_in, float *out, int64_t ld_out, int64_t rows_out,

@@ -17,6 +17,7 @@
 #define MASK_COUNTERS 32        // goofer_ctx::ovf_flag + MASK_COUNTERS: k_mask_short's two counters (segments answered from tile flags, segments staged),
 #define MASK_COUNTER_SLOTS 64   // each spread over this many words a cache line apart (slot = workgroup & 63): thirteen thousand atomics on
 #define MASK_COUNTER_STRIDE 32  // ONE word took longer than the kernel; counter c, slot s: word MASK_COUNTERS + (2 * s + c) * MASK_COUNTER_STRIDE
+#define LEGACY_FLAG 3           // goofer_ctx::ovf_flag[LEGACY_FLAG]: sticky like [0]: 1 + index of a note whose legacy normal fill ran into its block bound
 #define OVF_WORDS (MASK_COUNTERS + 2 * MASK_COUNTER_SLOTS * MASK_COUNTER_STRIDE)
 #define PP_SPT 8                // k_pulse_place: consecutive samples per thread; a tile = one workgroup = 256 * PP_SPT samples
 #define PULSE_TILE_INTS(samples) (4 * (((samples) + 256 * PP_SPT - 1) / (256 * PP_SPT)) + 64)   // k_pulse_tiles' table: 4 ints per tile
@@ -135,6 +136,7 @@ struct goofer_ctx {
     bool sa_fast = true;          // k_sample_assemble: the branch-free path with all of a thread's loads in flight together (option "sa_fast"; 0: A/B)
     bool value_f64 = false;       // k_env_edit: round 4's fp64 value arithmetic (fw interpolation, es blur) instead of fp32 — A/B and the
                                   // error-budget tests (option "value_f64")
+    bool legacy_wave = false;     // k_legacy_normal_fill: one wave per note instead of one 256-thread workgroup (option "legacy_wave"; A/B, the same bits)
     int pulse_scan = 1;           // 1: onsets from the parallel phase scan, the sequential walk only for the notes it cannot settle;
                                   // 0: the sequential walk kernel for every note; 2: the scan kernel walks every note (tests)
     // per-context kernel state: hipFuncSetAttribute is per device, and a handle belongs to one device, so what was set /

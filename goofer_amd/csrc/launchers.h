@@ -72,6 +72,8 @@ int launch_normal_fill(goofer_ctx *ctx, uint64_t seed, const goofer_note_params 
                        int64_t total, int tag, const unsigned char *note_on, const double *growl_scale, double *out, hipStream_t st);
 int launch_phase_fill(goofer_ctx *ctx, const uint64_t *words, const int64_t *frame_off, int n_notes, int64_t total_frames, int n_bins,
                       float *out, int ld, hipStream_t st);
+int launch_legacy_normal_fill(goofer_ctx *ctx, const uint32_t *seeds, const unsigned char *stream_on, const int64_t *sample_off, int n_notes,
+                              double *out_f0, double *out_vol_h, double *out_vol_b, int64_t *attempts, hipStream_t st);
 
 // post.hip
 int launch_onepole(goofer_ctx *ctx, const float *src, float *dst, const float *f0, const goofer_onepole_job *jobs, int n_jobs,

@@ -3,7 +3,9 @@
 //   k_normal_fill     float64 N(0, 1) for every sample of the notes that are switched on (note_on), nothing for the others;
 //                     with a per-note scale the growl factor 0.5 * 2^(scale * z) instead      SillySampler.py:1063-1065
 //   k_phase_fill      the aperiodic branch's phases as a seeded reference run draws them: numpy's PCG64 stream of every note's
-//                     seed, written frame-major into the batch's phase matrix (second half of this file)      GOOFER.py:1151-1152
+//                     seed, written frame-major into the batch's phase matrix (second part of this file)      GOOFER.py:1151-1152
+//   k_legacy_normal_fill   the sh / sr normals as a seeded reference process draws them: numpy's legacy MT19937 + polar Box-Muller
+//                     stream of every note's seed, one workgroup per note (last part of this file)      GOOFER.py:653, 666
 //
 // The stream is a definition (tests/noise_ref.py restates it in numpy, word for word):
 //   block    Philox-4x32, 10 rounds (philox_rounds<10>, the round function the phases use with 7)
@@ -218,6 +220,169 @@ int launch_phase_fill(goofer_ctx *ctx, const uint64_t *words, const int64_t *fra
     if (blocks > 0x7fffffffLL) return goofer_fail(ctx, GOOFER_EINVAL, "goofer_phase_fill: %lld tiles in one call", (long long)blocks);
     hipLaunchKernelGGL(k_phase_fill, dim3((unsigned)blocks), dim3(256), 0, st, words, frame_off, n_notes, total_frames, n_bins, chunks, ld,
                        out);
+    LAUNCH_CHECK(ctx);
+    return GOOFER_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Legacy normals: what a reference process draws for the sh / sr jitter (GOOFER.py:653, 666) after np.random.seed(s) —
+// numpy's global MT19937 + polar Box-Muller (`np.random.randn`).  The stream (tests/mt_ref.py restates it; the full text is
+// goofer_legacy_normal_fill's in include/goofer_hip.h):
+//   seed     mt[0] = s, mt[i] = 1812433253 * (mt[i-1] ^ (mt[i-1] >> 30)) + i; the first draw regenerates the block
+//   block    624 words twisted in place in index order, then tempered
+//   double   two words a, b: ((a >> 5) * 2^26 + (b >> 6)) * 2^-53
+//   attempt  two doubles: x1 = 2 d0 - 1, x2 = 2 d1 - 1, r2 = x1 x1 + x2 x2 (two rounded products, one rounded sum); rejected
+//            when r2 >= 1 or r2 == 0, else f = sqrt(-2 log(r2) / r2) and the normals f x2, f x1 in that order
+// A block is 156 whole attempts.  One workgroup owns one note (LN_WG threads; option "legacy_wave": one wave) and walks its
+// blocks in order.  The in-place twist has a fixed dependency order: k in [0, 227) reads old words only, [227, 454) the new
+// words of [0, 227), [454, 624) the new words of [227, 397) and, for k = 623, of mt[0] — three steps, each of which loads every
+// operand (mt[k + 1] must still be old) before any lane stores.  The attempts of a block are independent: a lane tempers its
+// four words, and the accepted ones are compacted behind the note's running count by wave ballots (and the wave totals in
+// LDS).  Normal p of the note goes to enabled stream p / n at sample p % n (n the note's samples; streams in the reference's
+// order: f0 jitter, harmonic volume, breath volume).  The block loop is bounded: 2 ceil(m / 245) + 4 blocks for m normals
+// (a block accepts 156 pi / 4 = 122.5 attempts on average, 245 normals, sd 10); a note that needs more raises the handle's
+// check word LEGACY_FLAG (goofer_check) and stops.
+#define LN_WORDS 624
+#define LN_SHIFT 397
+#define LN_ATTEMPTS 156
+#define LN_WG 256
+
+template <int NT, int LO, int HI>
+__device__ __forceinline__ void mt_twist_step(uint32_t *mt, int tid)
+{
+    constexpr int R = (HI - LO + NT - 1) / NT;
+    uint32_t nv[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int k = LO + r * NT + tid;
+        nv[r] = 0u;
+        if (k < HI) {
+            const int k1 = k + 1 == LN_WORDS ? 0 : k + 1;
+            const int km = k + LN_SHIFT >= LN_WORDS ? k + LN_SHIFT - LN_WORDS : k + LN_SHIFT;
+            const uint32_t y = (mt[k] & 0x80000000u) | (mt[k1] & 0x7fffffffu);
+            nv[r] = mt[km] ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
+        }
+    }
+    __syncthreads();                                           // every operand of the step is in a register
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int k = LO + r * NT + tid;
+        if (k < HI) mt[k] = nv[r];
+    }
+    __syncthreads();
+}
+
+__device__ __forceinline__ uint32_t mt_temper(uint32_t y)
+{
+    y ^= y >> 11;
+    y ^= (y << 7) & 0x9d2c5680u;
+    y ^= (y << 15) & 0xefc60000u;
+    y ^= y >> 18;
+    return y;
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT) void k_legacy_normal_fill(const uint32_t *__restrict__ seeds, const unsigned char *__restrict__ stream_on,
+                                                           const int64_t *__restrict__ sample_off, double *__restrict__ out_f0,
+                                                           double *__restrict__ out_vol_h, double *__restrict__ out_vol_b,
+                                                           int64_t *__restrict__ attempts, int32_t *__restrict__ flag)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t mt[LN_WORDS];
+    __shared__ int wave_cnt[NT / 64];
+    const int note = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const int64_t base = sample_off[note];
+    const int64_t n = sample_off[note + 1] - base;
+    const unsigned char *on = stream_on + 3 * (int64_t)note;
+    const bool e0 = on[0] != 0, e1 = on[1] != 0, e2 = on[2] != 0;
+    const int64_t m = n > 0 ? n * ((int)e0 + (int)e1 + (int)e2) : 0;   // normals of the note
+    if (m <= 0) {                                              // (uniform: nobody waits at a barrier)
+        if (attempts && tid == 0) attempts[note] = 0;
+        return;
+    }
+    // the enabled streams in order (a null output: its draws are consumed and dropped)
+    // (as stream numbers and branches: a select chain over the three pointers becomes a table in scratch)
+    const int sid0 = e0 ? 0 : (e1 ? 1 : 2), sid1 = (e0 && e1) ? 1 : 2;
+    auto put = [=](int64_t p, double v) {
+        const int s = (p >= n) + (p >= 2 * n);
+        const int sid = s == 0 ? sid0 : (s == 1 ? sid1 : 2);
+        const int64_t i = base + (p - s * n);
+        if (sid == 0) {
+            if (out_f0) out_f0[i] = v;
+        } else if (sid == 1) {
+            if (out_vol_h) out_vol_h[i] = v;
+        } else if (out_vol_b) {
+            out_vol_b[i] = v;
+        }
+    };
+    uint32_t v = seeds[note];                                  // every lane runs the recurrence and keeps the words it owns
+    for (int i = 0; i < LN_WORDS; ++i) {
+        if ((i & (NT - 1)) == tid) mt[i] = v;
+        v = 1812433253u * (v ^ (v >> 30)) + (uint32_t)(i + 1);
+    }
+    __syncthreads();
+    const int64_t need = (m + 1) >> 1;                         // accepted attempts that cover m normals
+    const int64_t max_blocks = 2 * ((m + 244) / 245) + 4;
+    int64_t done = 0;                                          // accepted so far (uniform)
+    for (int64_t blk = 0; done < need; ++blk) {
+        if (blk >= max_blocks) {
+            if (tid == 0) atomicMax(flag, note + 1);
+            break;
+        }
+        mt_twist_step<NT, 0, LN_WORDS - LN_SHIFT>(mt, tid);
+        mt_twist_step<NT, LN_WORDS - LN_SHIFT, 2 * (LN_WORDS - LN_SHIFT)>(mt, tid);
+        mt_twist_step<NT, 2 * (LN_WORDS - LN_SHIFT), LN_WORDS>(mt, tid);
+#pragma unroll
+        for (int r = 0; r < (LN_ATTEMPTS + NT - 1) / NT; ++r) {
+            const int a = r * NT + tid;
+            bool acc = false;
+            double x1 = 0.0, x2 = 0.0, r2 = 1.0;
+            if (a < LN_ATTEMPTS) {
+                const uint4 w = *reinterpret_cast<const uint4 *>(mt + 4 * a);
+                const double d0 = ((double)(mt_temper(w.x) >> 5) * 67108864.0 + (double)(mt_temper(w.y) >> 6)) * 0x1p-53;
+                const double d1 = ((double)(mt_temper(w.z) >> 5) * 67108864.0 + (double)(mt_temper(w.w) >> 6)) * 0x1p-53;
+                x1 = 2.0 * d0 - 1.0;                           // (exact: multiples of 2^-52 in [-1, 1))
+                x2 = 2.0 * d1 - 1.0;
+                r2 = __dadd_rn(__dmul_rn(x1, x1), __dmul_rn(x2, x2));
+                acc = !(r2 >= 1.0 || r2 == 0.0);
+            }
+            const unsigned long long bal = __ballot(acc);
+            int before = __popcll(bal & ((1ull << lane) - 1ull));
+            int round_total = __popcll(bal);
+            if constexpr (NT > 64) {                           // (one round per block: wave_cnt is rewritten two barriers later)
+                if (lane == 0) wave_cnt[tid >> 6] = round_total;
+                __syncthreads();
+                round_total = 0;
+#pragma unroll
+                for (int w2 = 0; w2 < NT / 64; ++w2) {
+                    const int c = wave_cnt[w2];
+                    before += w2 < (tid >> 6) ? c : 0;
+                    round_total += c;
+                }
+            }
+            const int64_t j = done + before;
+            const int64_t p = 2 * j;
+            if (acc && p < m) {
+                const double f = sqrt(-2.0 * log(r2) / r2);
+                put(p, f * x2);
+                if (p + 1 < m) put(p + 1, f * x1);
+                if (attempts && j == need - 1) attempts[note] = blk * LN_ATTEMPTS + a + 1;
+            }
+            done += round_total;
+        }
+    }
+}
+
+int launch_legacy_normal_fill(goofer_ctx *ctx, const uint32_t *seeds, const unsigned char *stream_on, const int64_t *sample_off, int n_notes,
+                              double *out_f0, double *out_vol_h, double *out_vol_b, int64_t *attempts, hipStream_t st)
+{
+    if (n_notes <= 0) return GOOFER_OK;
+    int32_t *flag = ctx->ovf_flag + LEGACY_FLAG;
+    if (ctx->legacy_wave)
+        hipLaunchKernelGGL(k_legacy_normal_fill<64>, dim3((unsigned)n_notes), dim3(64), 0, st, seeds, stream_on, sample_off, out_f0, out_vol_h,
+                           out_vol_b, attempts, flag);
+    else
+        hipLaunchKernelGGL(k_legacy_normal_fill<LN_WG>, dim3((unsigned)n_notes), dim3(LN_WG), 0, st, seeds, stream_on, sample_off, out_f0,
+                           out_vol_h, out_vol_b, attempts, flag);
     LAUNCH_CHECK(ctx);
     return GOOFER_OK;
 }

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .sampler import check_phi_seed
+from .sampler import check_noise_seed, check_phi_seed
 
 
 _ROW_ALIGN = int(__import__("os").environ.get("GOOFER_ROW_ALIGN", "4"))
@@ -296,6 +296,69 @@ class Context:
             self._check(self.lib.goofer_phase_fill(self.h, _ptr(d_w), _ptr(d_f), n, total, nb, _ptr(out), out.stride(0), self._stream()))
         self._fill_keep = keep                                  # this call's uploads, until the next call (stream order frees them safely)
         return out
+
+    def legacy_normal_fill(self, seeds, lengths_or_offsets, stream_on, out=None, attempts=False):
+        """The sh / sr jitter normals of a seeded reference run for the notes of a ragged batch, drawn on the device
+        (goofer_legacy_normal_fill; the stream's definition: include/goofer_hip.h, restated in tests/mt_ref.py): note i draws
+        what ``np.random.seed(seeds[i])`` followed by one ``np.random.randn(n_i)`` per enabled stream gives, in the reference's
+        order (f0 jitter, harmonic volume, breath volume) — exact up to the last place of ``log``.  Asynchronous on the current
+        stream; a note that runs into its block bound is reported by ``check()``.
+
+        ``seeds``: one int in [0, 2**32) per note, or the device copy (int32 [n]: the 32-bit words).  ``lengths_or_offsets``: the
+        notes' sample counts (host sequence), or the device int64 CSR offsets ``[n + 1]`` — then ``out`` gives the total.
+        ``stream_on``: [n, 3] switches (host, or a device uint8 tensor): which of the three streams each note draws.  ``out``:
+        up to three contiguous float64 device tensors of the batch's samples (f0, harmonic volume, breath volume; None: that
+        stream's draws are dropped); default: three new ones.  Samples of streams that are off are left as they are.
+        Returns ``out`` as a tuple — with ``attempts=True`` also the int64 [n] tensor of attempts each note's normals took."""
+        keep = []
+        if isinstance(lengths_or_offsets, torch.Tensor):
+            d_s = lengths_or_offsets
+            if out is None or all(t is None for t in out):
+                raise ValueError("legacy_normal_fill: device offsets need the tensors to fill (out=)")
+            n, total = d_s.numel() - 1, next(t for t in out if t is not None).numel()
+        else:
+            counts = [int(v) for v in lengths_or_offsets]
+            if any(v < 0 for v in counts):
+                raise ValueError("legacy_normal_fill: a negative sample count")
+            s_off = self.offsets(counts)
+            n, total = len(counts), int(s_off[-1])
+            keep.append(self.tensor(s_off))
+            d_s = keep[-1]
+        if d_s.dtype != torch.int64 or not d_s.is_contiguous():
+            raise ValueError("legacy_normal_fill: the sample offsets are a contiguous int64 tensor")
+        if isinstance(seeds, torch.Tensor):
+            d_seed = seeds
+        else:
+            if len(seeds) != n:
+                raise ValueError(f"legacy_normal_fill: {len(seeds)} seeds for {n} notes")
+            if any(sd is None for sd in seeds):
+                raise ValueError("legacy_normal_fill: one seed per note")
+            words = np.array([check_noise_seed(sd, "seeds[%d]" % i) for i, sd in enumerate(seeds)], dtype=np.uint32)
+            keep.append(self.tensor(words.view(np.int32)))
+            d_seed = keep[-1]
+        if d_seed.dtype != torch.int32 or not d_seed.is_contiguous() or d_seed.numel() != n:
+            raise ValueError("legacy_normal_fill: the seeds are one 32-bit word per note (a contiguous int32 tensor)")
+        if isinstance(stream_on, torch.Tensor):
+            d_on = stream_on
+        else:
+            keep.append(self.tensor(np.ascontiguousarray(np.asarray(stream_on) != 0, dtype=np.uint8).reshape(-1)))
+            d_on = keep[-1]
+        if d_on.dtype != torch.uint8 or not d_on.is_contiguous() or d_on.numel() != 3 * n:
+            raise ValueError("legacy_normal_fill: stream_on is three uint8 switches per note")
+        if out is None:
+            out = tuple(torch.empty(total, dtype=torch.float64, device=self.device) for _ in range(3))
+        out = tuple(out)
+        if len(out) != 3:
+            raise ValueError("legacy_normal_fill: out is (f0, harmonic volume, breath volume), None for a stream that is dropped")
+        for t in out:
+            if t is not None and (t.dtype != torch.float64 or not t.is_contiguous() or t.numel() != total or t.device != self.device):
+                raise ValueError("legacy_normal_fill: an output must be a contiguous float64 tensor of the batch's %d samples" % total)
+        d_att = torch.zeros(n, dtype=torch.int64, device=self.device) if attempts else None
+        if n and (d_att is not None or any(t is not None for t in out)):
+            self._check(self.lib.goofer_legacy_normal_fill(self.h, _ptr(d_seed), _ptr(d_on), _ptr(d_s), n, total, _ptr(out[0]), _ptr(out[1]),
+                                                           _ptr(out[2]), _ptr(d_att), self._stream()))
+        self._fill_keep = keep                                  # this call's uploads, until the next call (stream order frees them safely)
+        return (out, d_att) if attempts else out
 
     def counter(self, name: str) -> int:
         """Cumulative device-side counter of the handle (goofer_counter): 'pulse_scanned_notes', 'pulse_fallback_notes',

@@ -19,7 +19,7 @@ import torch
 
 from . import _lib
 from . import sampler as S
-from .device import Context, check_phi_seed, default_context, default_params, pcg64_words, row_stride
+from .device import Context, check_noise_seed, check_phi_seed, default_context, default_params, pcg64_words, row_stride
 
 
 # The assembly and render kernels of the resampler path stop at the reference sampler's geometry family (SillySampler.py:14
@@ -424,16 +424,19 @@ class Renderer:
         lw = int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", "1")) or 1)
         self.plan_threads = 0 if lw <= 1 else max(1, min(8, (os.cpu_count() or 8) // lw))
 
-    def render(self, jobs, seed: int = 0, phi_seeds=None, return_parts: bool = False):
+    def render(self, jobs, seed: int = 0, phi_seeds=None, return_parts: bool = False, noise_seeds=None):
         """jobs: list of (Source, Request).  Returns a list of fp32 arrays (the mix the reference writes to
         out.wav); with ``return_parts`` also a dict of device-side intermediates for tests.
         ``phi_seeds``: per-note seeds for INJECTED phases (parity with a seeded reference run: numpy's stream of each seed,
         drawn on the device by ``Context.phase_fill``); otherwise the device draws phases from Philox keyed by ``seed`` and
         the note index.  A renderer made with ``noise="device"``
-        draws the jitter / growl normals on the device whether or not the phases are injected."""
+        draws the jitter / growl normals on the device whether or not the phases are injected.
+        ``noise_seeds``: per-note seeds of the sh / sr jitter: note i gets the normals a reference process draws after
+        ``np.random.seed(noise_seeds[i])``, made on the device by ``Context.legacy_normal_fill`` — no ``np.random.randn`` is
+        called and the global generator is left as it is.  The 'sj' draws stay what the renderer's ``noise`` says."""
         if not jobs:
             return []
-        prep = self.prepare(jobs, phi_seeds=phi_seeds, trim_rows=not return_parts)   # tests look at the whole assembled envelope
+        prep = self.prepare(jobs, phi_seeds=phi_seeds, trim_rows=not return_parts, noise_seeds=noise_seeds)   # tests look at the whole assembled envelope
         out = self.run(prep, seed=seed, keep_stems=return_parts)
         self.ctx.check()                                   # synchronises; raises if the device flagged a note
         mix = out["mix"].cpu().numpy()
@@ -459,6 +462,9 @@ class Renderer:
         drawn = None
         if prep.get("device_noise") is not None:              # before the assembly (it reads f0_mul) and the synthesis are enqueued
             noise_f0, noise_vol, drawn = self._device_noise(prep, seed)
+        if prep.get("legacy_noise") is not None:              # noise_seeds: the reference's own sh / sr normals of every note
+            noise_f0, noise_vol = self._legacy_noise(prep)
+            drawn = (drawn, noise_f0, noise_vol)
         if prep.get("phi_words") is not None:                 # the seeded phases of every note, ahead of the synthesis that reads them
             ctx.phase_fill(prep["phi_words"], prep["offsets"]["d_f"], out=prep["phi"])
         # Notes with the 'sg' pulse layer or the 'sr' volume jitter are synthesised by the one-kernel-per-step pipeline (those
@@ -497,14 +503,26 @@ class Renderer:
         def fill(tag, on, out=None, growl_scale=None):
             out = torch.empty(total, dtype=torch.float64, device=ctx.device) if out is None else out
             return ctx.normal_fill(seed, o["d_par"], o["d_s"], tag, note_on=on, growl_scale=growl_scale, out=out)
-        noise_f0 = fill(0, dn["on_f0"]) if dn["on_f0"] is not None else None
-        noise_vol = (fill(1, dn["on_vol"]), fill(2, dn["on_vol"])) if dn["on_vol"] is not None else None
+        legacy = prep.get("legacy_noise") is not None          # noise_seeds: sh / sr come from _legacy_noise, only 'sj' from here
+        noise_f0 = fill(0, dn["on_f0"]) if dn["on_f0"] is not None and not legacy else None
+        noise_vol = (fill(1, dn["on_vol"]), fill(2, dn["on_vol"])) if dn["on_vol"] is not None and not legacy else None
         mul = prep["keep"].get("f0_mul") if dn["on_sj"] is not None else None
         if mul is not None:
             if not dn["all_sj"]:
                 mul.fill_(1.0)
             fill(4, dn["on_sj"], growl_scale=dn["sj_scale"], out=mul)
         return noise_f0, noise_vol, (noise_f0, noise_vol, mul)
+
+    def _legacy_noise(self, prep):
+        """noise_seeds: this run's sh / sr draws, numpy's legacy stream of each note's seed made by Context.legacy_normal_fill
+        on the current stream.  They go where the host's uploads go (goofer_batch.noise_f0 / noise_vol_h / noise_vol_b); the
+        streams a note does not draw are not written and not read (the kernels gate per note).  Returns (noise_f0, noise_vol)."""
+        ctx, ln, o = self.ctx, prep["legacy_noise"], prep["offsets"]
+        total = int(o["s_off"][-1])
+        new = lambda: torch.empty(total, dtype=torch.float64, device=ctx.device)
+        out = (new() if ln["any_f0"] else None, new() if ln["any_vol"] else None, new() if ln["any_vol"] else None)
+        ctx.legacy_normal_fill(ln["seeds"], o["d_s"], ln["on"], out=out)
+        return out[0], ((out[1], out[2]) if ln["any_vol"] else None)
 
     def _synth_partitioned(self, prep, groups, seed, keep_stems, noise_f0=None, noise_vol=None):
         """goofer_synth_batch once per group of notes of an assembled batch; the stems land at the notes' places."""
@@ -601,7 +619,7 @@ class Renderer:
         ctx._check(ctx.lib.goofer_post_batch(ctx.h, C.byref(P), ctx._stream()))
         out["_keep_post"] = (extra, post, s_host)
 
-    def prepare(self, jobs, phi_seeds=None, note_ids=None, trim_rows: bool = True, device_calls: bool = True):
+    def prepare(self, jobs, phi_seeds=None, note_ids=None, trim_rows: bool = True, device_calls: bool = True, noise_seeds=None):
         """Plan every note on the host and make the batch resident in HBM (plans, tables, sources).
         ``device_calls=False`` (PipelinedRenderer: this runs on a worker thread while the handle is rendering another batch):
         nothing here touches the library handle or waits for the device — the caller plans / reserves on the handle
@@ -619,6 +637,10 @@ class Renderer:
         ``phi_seeds``: one non-negative int per note — the phases a reference run seeded with it draws.  Only the generators'
         starting words are staged here (four 64-bit words per note); ``run`` fills ``prep["phi"]`` on the device before the
         synthesis (``Context.phase_fill``), so the matrix holds nothing until a run has been enqueued.
+        ``noise_seeds``: one int in [0, 2**32) per note — the sh / sr normals a reference process draws after
+        ``np.random.seed`` of it.  Only the seeds and three switches per note are staged here, and no ``np.random.randn`` is
+        called (the global generator keeps its state); ``run`` draws them on the device before the assembly and the synthesis
+        (``Context.legacy_normal_fill``).  The 'sj' draws follow the renderer's ``noise`` either way.
 
         Host cost: the per-note decisions run in the library's host planner (a batch per call, csrc/planner.hip) and everything
         here is column arithmetic over the batch — no per-note Python except a handful of attribute reads."""
@@ -633,13 +655,17 @@ class Renderer:
                 stg = Staging(self.ctx.device, max(need, 48 << 20))
             stg.reset()
             try:
-                return self._prepare(stg, jobs, phi_seeds, note_ids, trim_rows, device_calls)
+                return self._prepare(stg, jobs, phi_seeds, note_ids, trim_rows, device_calls, noise_seeds)
             except S.StagingFull as e:
                 need = max(int(stg.nbytes * 3 // 2), 2 * int(e.args[0]) if e.args[0] > stg.nbytes else 0, stg.nbytes + (16 << 20))
                 del stg
 
-    def _prepare(self, stg, jobs, phi_seeds, note_ids, trim_rows, device_calls=True):
+    def _prepare(self, stg, jobs, phi_seeds, note_ids, trim_rows, device_calls=True, noise_seeds=None):
         device_noise = self.noise == "device"
+        if noise_seeds is not None:                            # before anything is planned or uploaded
+            noise_seeds = [check_noise_seed(sd, "noise_seeds[%d]" % i) for i, sd in enumerate(noise_seeds)]
+            if None in noise_seeds:
+                raise ValueError("noise_seeds: one seed per note (a batch seeds the jitter of all its notes or of none)")
         if phi_seeds is not None:                              # before anything is planned or uploaded
             phi_seeds = [check_phi_seed(sd, "phi_seeds[%d]" % i) for i, sd in enumerate(phi_seeds)]
             if None in phi_seeds:
@@ -667,6 +693,8 @@ class Renderer:
         c = rb.col
         if phi_seeds is not None and len(phi_seeds) != n:
             raise ValueError(f"{n} notes and {len(phi_seeds)} phase seeds")
+        if noise_seeds is not None and len(noise_seeds) != n:
+            raise ValueError(f"{n} notes and {len(noise_seeds)} noise seeds")
         # the samples' rows in the arena's tables (a voicebank sample rendered by several notes is resident once: same Source object)
         rows, T_, g_lerp_tabs, d_knots, d_mask_src = self.sources.lookup(srcs, stg)   # resident in HBM; new samples are uploaded here
         _T("uniq")
@@ -830,8 +858,15 @@ class Renderer:
         par["f0_jitter"], par["vol_jitter_harm"], par["vol_jitter_breath"], par["subharm_weight"] = c_f0j, c_vj, c_vj * 2, c_sub
         lens_l = lens.tolist()
         env_lens_l = env_lens.tolist()
-        noise_f0 = noise_vol = dev_noise = None
+        noise_f0 = noise_vol = dev_noise = legacy_noise = None
         any_f0j, any_vj = bool((c["f0_jitter"] != 0).any()), bool((c["volume_jitter"] != 0).any())
+        if noise_seeds is not None and (any_f0j or any_vj):
+            # run() draws them (Context.legacy_normal_fill: numpy's legacy stream of each seed, made on the device): here a
+            # 32-bit word and three switches per note — f0 jitter, harmonic volume, breath volume, the reference's order
+            jf, jv = c["f0_jitter"] != 0, c["volume_jitter"] != 0
+            legacy_noise = {"seeds": stg.put(np.asarray(noise_seeds, dtype=np.uint32).view(np.int32)),
+                            "on": stg.put(np.stack([jf, jv, jv], axis=1).astype(np.uint8).reshape(-1)),
+                            "any_f0": any_f0j, "any_vol": any_vj}
         if device_noise:
             # run() draws them (Context.normal_fill, keyed by its seed): here only which notes take which stream — the notes
             # host mode draws for — and the growl layer's scale, a byte / a double per note
@@ -841,7 +876,7 @@ class Renderer:
                          "on_sj": stg.put(on_sj.astype(np.uint8)) if on_sj.any() else None,
                          "sj_scale": stg.put(np.where(on_sj, c_sj.astype(np.float64) ** 2, 0.0)) if on_sj.any() else None,
                          "all_sj": bool(on_sj.all())}
-        elif any_f0j or any_vj:
+        if not device_noise and legacy_noise is None and (any_f0j or any_vj):
             # sh / sr draws come from the legacy global np.random stream, note by note, in the reference's order
             # (f0 jitter, harmonic volume, breath volume: GOOFER.py:666, 653)
             nf, nh, nb = [], [], []
@@ -895,7 +930,7 @@ class Renderer:
             torch.cuda.current_stream(ctx.device).synchronize()   # (this batch's uploads; other lanes' streams are not waited for)
         _T("ship+sync")
         return {"assembly": a, "keep": d, "env": env, "f0": f0, "mask": mask, "params": par, "lens": lens_l, "env_lens": env_lens_l,
-                "noise_f0": noise_f0, "noise_vol": noise_vol, "device_noise": dev_noise, "subharm": bool((c_sub > 0).any()),
+                "noise_f0": noise_f0, "noise_vol": noise_vol, "device_noise": dev_noise, "legacy_noise": legacy_noise, "subharm": bool((c_sub > 0).any()),
                 "post": post if has_post else None, "growl": growl, "f0_growl": f0_growl, "bend_out": bend_out, "requests": rb, "sources": srcs, "geometry": (sr, n_fft, self.hop, frames, o_off, n),
                 "formants": d_formants, "phi": phi, "phi_words": phi_words, "planned": pb, "offsets": offsets,
                 "sample_off": sample_off, "env_off": env_off, "frames": frames, "samples": o_off, "edit_rows": e_off}
@@ -915,14 +950,17 @@ class GooferResampler:
 
     ``phi_seed`` (keyword only): the note's phases are the ones the reference draws when its generator is seeded with it
     (numpy's stream, made on the device); ``seed`` keeps its meaning, the Philox key of the device's own phases, when
-    ``phi_seed`` is None."""
+    ``phi_seed`` is None.  ``noise_seed`` (keyword only): an int in [0, 2**32) — the note's sh / sr jitter is what a reference
+    process draws after ``np.random.seed(noise_seed)``, made on the device; None: the renderer's ``noise`` source.  With both
+    seeds a note of any flags but 'sj' is the seeded reference's note."""
 
     def __init__(self, in_file, out_file, pitch, velocity, flags="", offset=0, length=1000, consonant=0, cutoff=0,
                  volume=100, modulation=0, tempo="!120", pitch_string="AA", renderer: Renderer | None = None, seed=None, tracker=None,
-                 noise=None, *, phi_seed=None):
+                 noise=None, *, phi_seed=None, noise_seed=None):
         from pathlib import Path
         from . import core
         phi_seed = check_phi_seed(phi_seed)                    # (refused here, before anything is read or launched)
+        noise_seed = check_noise_seed(noise_seed)
         self.in_file, self.out_file = Path(in_file), Path(out_file)
         self.request = S.decode_request(pitch, velocity, flags, offset, length, consonant, cutoff, volume, modulation, tempo,
                                         pitch_string)
@@ -937,7 +975,10 @@ class GooferResampler:
         self.source = Source.from_pack(env, f0, mask, forms, sr, ylen)
         if seed is None:
             seed = int(np.random.SeedSequence().generate_state(1, dtype=np.uint64)[0])
-        self.out = self.renderer.render([(self.source, self.request)], seed=seed, **({} if phi_seed is None else {"phi_seeds": [phi_seed]}))[0]
+        seeded = {} if phi_seed is None else {"phi_seeds": [phi_seed]}
+        if noise_seed is not None:
+            seeded["noise_seeds"] = [noise_seed]
+        self.out = self.renderer.render([(self.source, self.request)], seed=seed, **seeded)[0]
         write_wav(self.out_file, self.out, sr)
 
 

@@ -73,6 +73,35 @@ def env_phi_seed():
     return int(text)
 
 
+def check_noise_seed(seed, what="noise_seed"):
+    """``seed`` as the Python int the legacy ``np.random.seed`` takes for one 32-bit word: an integer in [0, 2**32) (None stays
+    None).  A bool, a float, a negative or a larger value is a ``ValueError``."""
+    if seed is None:
+        return None
+    try:
+        if isinstance(seed, (bool, np.bool_)):
+            raise TypeError
+        seed = int(operator.index(seed))
+    except TypeError:
+        raise ValueError(f"{what} must be an integer in [0, 2**32), got {seed!r}") from None
+    if not 0 <= seed < 2 ** 32:
+        raise ValueError(f"{what} must be an integer in [0, 2**32), got {seed}")
+    return seed
+
+
+def env_noise_seed():
+    """``$GOOFER_NOISE_SEED``: the legacy ``np.random.seed`` of the sh / sr jitter draws for the front ends
+    (``GooferResampler(noise_seed=)``, ``cli.BatchCollector(noise_seed=)``) as an int, None when unset or empty; a value that
+    is not a decimal integer in [0, 2**32) raises ``ValueError``."""
+    import os
+    text = (os.environ.get("GOOFER_NOISE_SEED") or "").strip()
+    if not text:
+        return None
+    if not (text.isascii() and text.isdigit()) or int(text) >= 2 ** 32:
+        raise ValueError(f"GOOFER_NOISE_SEED={text!r}: the noise seed is an integer in [0, 2**32)")
+    return int(text)
+
+
 # ---------------------------------------------------------------------------------------------
 # string decode (integer path — bit-exact)
 # ---------------------------------------------------------------------------------------------

@@ -584,6 +584,36 @@ int goofer_normal_fill(goofer_ctx *ctx, uint64_t seed, const goofer_note_params 
 int goofer_phase_fill(goofer_ctx *ctx, const uint64_t *pcg_words, const int64_t *frame_off, int n_notes, int64_t total_frames,
                       int n_bins, float *out, int ld, void *stream);
 
+/* The normals a reference process draws for the sh / sr jitter (GOOFER.py:653, 666) after np.random.seed(seed_k): numpy's legacy
+ * global stream, `np.random.randn`, made on the device (noise.hip) for every note k of a ragged batch.  The stream:
+ *   seeding  (np.random.seed(s), 0 <= s < 2^32) mt[0] = s, mt[i] = (1812433253 * (mt[i-1] ^ (mt[i-1] >> 30)) + i) mod 2^32 for
+ *            i = 1..623; position 624 (the first draw regenerates the block); no cached normal
+ *   block    of 624 words, for k = 0..623 in order and in place: y = (mt[k] & 0x80000000) | (mt[(k+1) % 624] & 0x7fffffff),
+ *            mt[k] = mt[(k+397) % 624] ^ (y >> 1) ^ (y & 1 ? 0x9908b0df : 0); a word is tempered as it is drawn: y ^= y >> 11,
+ *            y ^= (y << 7) & 0x9d2c5680, y ^= (y << 15) & 0xefc60000, y ^= y >> 18
+ *   double   two consecutive words a, b: ((a >> 5) * 67108864.0 + (b >> 6)) / 9007199254740992.0 (exact)
+ *   attempt  two doubles d0, d1 — always four words: x1 = 2 d0 - 1, x2 = 2 d1 - 1, r2 = x1 x1 + x2 x2 (two rounded products and
+ *            one rounded sum, no fused multiply-add); rejected when r2 >= 1.0 or r2 == 0.0; otherwise f = sqrt(-2.0 * log(r2) / r2)
+ *            (IEEE division and square root) and two normals in this order: f x2, then f x1
+ *   randn(n) the next n normals; the second normal of a pair waits for the next call, so a note's consecutive randn calls are
+ *            consecutive slices of one stream of normals.  A block is 156 whole attempts.
+ * Everything but `log` is exact, so a value differs from the host's by what the two `log` differ in their last place, and the
+ * acceptances (every later position of the stream) not at all.
+ * stream_on holds three bytes per note: whether it draws the f0 jitter, the harmonic volume jitter, the breath volume jitter
+ * (the reference's order).  With n = sample_off[k + 1] - sample_off[k], normal p of note k goes to its enabled stream p / n at
+ * sample p % n: out_f0 / out_vol_h / out_vol_b [sample_off[k] + p % n], the concatenated float64 arrays goofer_batch.noise_f0 /
+ * noise_vol_h / noise_vol_b take.  The samples of a stream that is off, and everything of a note with nothing on or without
+ * samples, are not written; a NULL output drops the draws of its stream (they are still consumed).  attempts (int64 [n_notes],
+ * or NULL): the attempts the note's normals took — the reference's generator has drawn 4 * attempts words — 0 for a note that
+ * draws nothing.  A note walks at most 2 * ceil(m / 245) + 4 blocks for its m normals (a block yields 245 on average, with a
+ * standard deviation of 10); one that would need more stops there and is reported by the next goofer_check.
+ * seeds (uint32 [n_notes]), stream_on, sample_off ([n_notes + 1], from 0 to total_samples), the outputs and attempts are device
+ * arrays; asynchronous on `stream`; needs no plan and no scratch.  GOOFER_EINVAL for a null seeds / stream_on / sample_off, no
+ * output at all, a negative count, seeds not 4-byte aligned, sample_off, an output or attempts not 8-byte aligned. */
+int goofer_legacy_normal_fill(goofer_ctx *ctx, const uint32_t *seeds, const unsigned char *stream_on, const int64_t *sample_off,
+                              int n_notes, int64_t total_samples, double *out_f0, double *out_vol_h, double *out_vol_b,
+                              int64_t *attempts, void *stream);
+
 /* ---- measurement / test hooks --------------------------------------------------------------- */
 
 /* HIP-event timing of every stage of goofer_synth_batch on the caller's stream: begin() arms up to
@@ -614,6 +644,7 @@ const char *goofer_profile_stage_name_ex(const goofer_ctx *ctx, int stage);   /*
  *   "mask_flags" 1 (default): goofer_render_batch has k_sample_assemble leave a word per 1024 samples of the voicing mask (all == 0,
  *               all == 1, neither) and k_mask_short answer the windows those words settle without loading the mask; 0: no flags
  *               (goofer_assemble_batch / goofer_synth_batch on their own and goofer_smooth_mask_ds never have them).  Same bits.
+ *   "legacy_wave" 0 (default): goofer_legacy_normal_fill gives a note a workgroup of 256 threads; 1: one wave.  Same bits.
  *   "prof_only" s >= 0: goofer_profile_begin .. end record the events of stage s only; -1 (default): every stage     */
 int goofer_set_option(goofer_ctx *ctx, const char *name, int value);
 
