@@ -67,6 +67,12 @@ POST_NOTE = np.dtype([
     ("reserved", "<i4"),
 ], align=True)
 
+# goofer_legacy_job (goofer_legacy_normal_jobs)
+LEGACY_JOB = np.dtype([
+    ("seed", "<u4"), ("flags", "<u4"), ("n", "<i8"), ("n_dst", "<i4"), ("reserved", "<i4"), ("dst", "<u8", 4), ("off", "<i8", 4),
+], align=True)
+LEGACY_F32 = 1
+
 
 class Assembly(C.Structure):
     """goofer_assembly"""
@@ -159,6 +165,7 @@ EXPORTS = {
     "goofer_phase_fill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "goofer_legacy_normal_fill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p]),
+    "goofer_legacy_normal_jobs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "goofer_assemble_batch": (C.c_int, [C.c_void_p, C.POINTER(Assembly), C.c_void_p]),
     "goofer_render_batch": (C.c_int, [C.c_void_p, C.POINTER(Assembly), C.POINTER(Batch), C.c_void_p]),
     "goofer_profile_begin": (C.c_int, [C.c_void_p, C.c_int]),

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .device import Context, check_phi_seed, default_context, default_params, row_stride
+from .device import Context, check_noise_seed, check_phi_seed, default_context, default_params, row_stride
 
 DSTORAGE = np.float16
 DCOMPUTE = np.float32
@@ -478,7 +478,8 @@ def _roughness_params(params, kw):
     return params
 
 
-_SYNTH_CALL_ARGS = ("env_spec", "f0_interp", "voicing_mask", "y", "sr", "n_fft", "hop_length", "phi", "phi_seed", "seed", "ctx")
+_SYNTH_CALL_ARGS = ("env_spec", "f0_interp", "voicing_mask", "y", "sr", "n_fft", "hop_length", "phi", "phi_seed", "noise_seed", "seed",
+                    "ctx")
 _NOTE_ARRAYS = ("env_spec", "f0_interp", "voicing_mask", "y")
 SYNTH_FRAME_BUDGET = 1 << 18      # STFT frames per synthesis pass (about 25 minutes of audio at 44.1 kHz, hop 256)
 
@@ -558,10 +559,12 @@ def _rough_settings(kw, sr):
             float(kw.get("rough_noise_amp", 0.6)), float(kw.get("rough_hp_fc", 320.0)))
 
 
-def _prepare_note(c, note, kw, seed, phi, sr, n_fft, hop, phi_seed=None):
+def _prepare_note(c, note, kw, seed, phi, sr, n_fft, hop, phi_seed=None, noise_seed=None):
     """Everything gf.synthesize does for one note before the device renders it, in its order: the checks that make it raise,
     the fresh Philox key, then the legacy-RNG draws (f0, sub-harmonic, harmonic volume, breath volume jitter, then the
-    roughness noises re-seeded 1337 + idx).  Returns the note's job, or the four empty stems of a note with no samples."""
+    roughness noises re-seeded 1337 + idx).  With a ``noise_seed`` none of them is drawn here and the global generator is
+    left alone: the job records which streams the note draws (``want``) and the pass makes them on the device
+    (``_pass_noise``, ``_roughness``).  Returns the note's job, or the four empty stems of a note with no samples."""
     env_spec = note["env_spec"]
     if isinstance(env_spec, dict) and env_spec.get("mode") == "knots":
         env_spec = decode_env_from_knots(env_spec, ctx=c)
@@ -635,17 +638,23 @@ def _prepare_note(c, note, kw, seed, phi, sr, n_fft, hop, phi_seed=None):
         seed = int(np.random.SeedSequence().generate_state(1, dtype=np.uint64)[0])
     job["seed"] = int(seed) & 0xFFFFFFFFFFFFFFFF
     # jitter flags draw from the legacy global np.random stream in the reference's order: f0, sub-harmonic, harm volume, breath volume
-    job["noise_f0"] = np.random.randn(n) if kw.get("f0_jitter") else None
-    job["noise_sub"] = np.random.randn(n) if kw.get("add_subharm") and kw.get("subharm_f0_jitter", 0) > 0.0 else None
     vib = bool(kw.get("volume_jitter") and kw.get("volume_vibrato"))          # the sinusoid variant draws nothing
-    job["noise_vol"] = (np.random.randn(n), np.random.randn(n)) if kw.get("volume_jitter") and not vib else None
+    want = (bool(kw.get("f0_jitter")), bool(kw.get("add_subharm") and kw.get("subharm_f0_jitter", 0) > 0.0),
+            bool(kw.get("volume_jitter") and not vib))
+    host = noise_seed is None                                 # a seeded note: the same draws of its own seed, made by the pass
+    job.update(want=want, legacy_seed=noise_seed)
+    job["noise_f0"] = np.random.randn(n) if want[0] and host else None
+    job["noise_sub"] = np.random.randn(n) if want[1] and host else None
+    job["noise_vol"] = (np.random.randn(n), np.random.randn(n)) if want[2] and host else None
     job["rough"] = None
     if kw.get("roughness_on"):
         rs = _rough_settings(kw, sr)
-        noises = []
-        for idx in range(len(rs[0])):                         # make_smooth_noise re-seeds the LEGACY global generator
-            np.random.seed(1337 + idx)
-            noises.append(np.random.randn(n).astype(np.float32).astype(np.float64))
+        noises = None                                         # (a seeded note: _rough_noise makes them on the device)
+        if host:
+            noises = []
+            for idx in range(len(rs[0])):                     # make_smooth_noise re-seeds the LEGACY global generator
+                np.random.seed(1337 + idx)
+                noises.append(np.random.randn(n).astype(np.float32).astype(np.float64))
         job["rough"] = (rs, noises)
     return job
 
@@ -673,11 +682,41 @@ def _device_concat(c, arrs, dtype):
 
 
 def _noise(c, js, key, part=None):
-    """One fp64 device array of a jitter's draws for the pass (zeros for the notes without that jitter), or None."""
+    """One fp64 device array of a jitter's host draws for the pass (zeros for the notes without them), or None."""
     if not any(j[key] is not None for j in js):
         return None
     return c.tensor(np.concatenate([(j[key] if part is None else j[key][part]) if j[key] is not None else np.zeros(j["n"])
                                     for j in js]))
+
+
+def _noise_seeds(seeds, n, who):
+    """The per-note legacy seeds of a batch call as a checked list (None entries: that note draws on the host): the length and
+    anything that is not an integer in [0, 2**32) raise ValueError — before a context exists."""
+    seeds = [None] * n if seeds is None else [check_noise_seed(s, "noise_seeds[%d]" % i) for i, s in enumerate(seeds)]
+    if len(seeds) != n:
+        raise ValueError(f"{who}: {n} notes and {len(seeds)} noise seeds")
+    return seeds
+
+
+def _pass_noise(c, js):
+    """The pass's four fp64 jitter arrays (f0, sub-harmonic f0, harmonic volume, breath volume; None: no note of the pass
+    draws it).  The unseeded notes' host draws are uploaded (``_noise``: zeros elsewhere; an array only seeded notes draw is
+    zeroed on the device, nothing uploaded); then one goofer_legacy_normal_jobs fills the seeded notes' slices: a note's
+    draws are one job, its streams in the reference's order."""
+    streams = (("noise_f0", None, 0), ("noise_sub", None, 1), ("noise_vol", 0, 2), ("noise_vol", 1, 2))
+    total = sum(j["n"] for j in js)
+    out = []
+    for key, part, w in streams:
+        t = _noise(c, js, key, part)
+        if t is None and any(j["want"][w] and j["legacy_seed"] is not None for j in js):
+            t = torch.zeros(total, dtype=torch.float64, device=c.device)
+        out.append(t)
+    off = c.offsets([j["n"] for j in js])
+    table = [(j["legacy_seed"], j["n"], [(out[k], int(off[i])) for k, (_, _, w) in enumerate(streams) if j["want"][w]], False)
+             for i, j in enumerate(js) if j["legacy_seed"] is not None and any(j["want"])]
+    if table:
+        c.legacy_normal_jobs(table)
+    return out
 
 
 def _ingest(c, arrays, lengths):
@@ -763,17 +802,34 @@ def _run_pass(c, js, sr):
             idx = np.concatenate([np.arange(off[i], off[i + 1]) for i, j in enumerate(js) if j["f0_64"] is not None])
             f64[c.tensor(idx)] = c.tensor(np.concatenate([j["f0_64"] for j in js if j["f0_64"] is not None]))
             extra["f0_64"] = f64
+    n_f0, n_sub, n_vh, n_vb = _pass_noise(c, js)
     out = c.synth_batch(d_env, env_lens, d_f0, d_mask, lens, params, formants=F, phi=d_phi, seed=0,
                         transition_sigma=float(kw.get("noise_transition_smoothness", 100)), want_mix=False,
-                        noise_f0=_noise(c, js, "noise_f0"),
-                        noise_vol=(_noise(c, js, "noise_vol", 0), _noise(c, js, "noise_vol", 1)) if any(j["noise_vol"] is not None for j in js) else None,
+                        noise_f0=n_f0, noise_vol=(n_vh, n_vb) if n_vh is not None else None,
                         f0_jitter_speed=float(jit.get("f0_jitter_speed", 100)), vol_jitter_speed=float(vol.get("volume_jitter_speed", 150)),
                         subharm=subharm_from_kwargs(sub) if sub is not None else None, volume_vibrato=vib,
-                        noise_subharm=_noise(c, js, "noise_sub"), **extra)
+                        noise_subharm=n_sub, **extra)
     s_off = out["sample_off"]
     rough = _roughness(c, js, out, d_mask, s_off, sr) if any(j["rough"] is not None for j in js) else {}
     host = {k: out[k].cpu().numpy() for k in ("rec", "harm", "uv", "bre")}
     return host, s_off, rough
+
+
+def _rough_noise(c, host, lens, n_k):
+    """The roughness layer's unfiltered noises of one setting group, fp64 [n_k x sum(lens)] flat: noise k of every note back to
+    back.  ``host``: per note its host draws (an unseeded note: uploaded, zeros for the others) or None — a seeded note, whose
+    rows are made in place by one float32-rounded job per partial (the generator re-seeded 1337 + k: nothing of the note's own
+    seed reaches them).  A group of seeded notes uploads nothing."""
+    N = sum(lens)
+    if all(h is None for h in host):
+        d_flat = torch.empty(n_k * N, dtype=torch.float64, device=c.device)
+    else:
+        d_flat = c.tensor(np.concatenate([h[k] if h is not None else np.zeros(ln) for k in range(n_k) for h, ln in zip(host, lens)]))
+    o = c.offsets(lens)
+    table = [(1337 + k, lens[q], [(d_flat, k * N + int(o[q]))], True) for k in range(n_k) for q, h in enumerate(host) if h is None]
+    if table:
+        c.legacy_normal_jobs(table)
+    return d_flat
 
 
 def _roughness(c, js, out, d_mask, s_off, sr):
@@ -794,8 +850,8 @@ def _roughness(c, js, out, d_mask, s_off, sr):
         d_f0 = c.tensor(np.concatenate([f0_all[s] for s in sl]))
         nz = None
         if k_list:                                            # [n_k, N]: noise k of every note back to back, one ragged row each
-            flat = np.concatenate([js[i]["rough"][1][k] for k in range(len(k_list)) for i in idxs])
-            nz = c.gauss_rows_f64(c.tensor(flat), gaussian_taps(sig_n), lengths=lens * len(k_list)).reshape(len(k_list), -1)
+            d_flat = _rough_noise(c, [js[i]["rough"][1] for i in idxs], lens, len(k_list))
+            nz = c.gauss_rows_f64(d_flat, gaussian_taps(sig_n), lengths=lens * len(k_list)).reshape(len(k_list), -1)
         a_track = (mask.float() * np.float32(alpha)).double().contiguous()      # alpha * vmask in fp32, filtered in fp64
         a_slew = c.gauss_rows_f64(a_track, gaussian_taps(sig_a), lengths=lens).float()
         rough = c.vocal_roughness(harm, d_f0, mask, nz, list(k_list), list(h_list), amp, fc, a_slew, lengths=lens).cpu().numpy()
@@ -805,7 +861,7 @@ def _roughness(c, js, out, d_mask, s_off, sr):
     return res
 
 
-def synthesize_batch(notes, sr, n_fft=1024, hop_length=256, *, seeds=None, phis=None, phi_seeds=None, ctx=None, **kw):
+def synthesize_batch(notes, sr, n_fft=1024, hop_length=256, *, seeds=None, phis=None, phi_seeds=None, noise_seeds=None, ctx=None, **kw):
     """gf.synthesize for many notes in batched device passes -> one (reconstruct, harmonic, aper_uv, aper_bre) fp32 tuple per
     note, or the exception that note's ``synthesize`` call raises (an empty stretch region, more than sixteen sub-harmonic
     ratios, a non-1-D f0 or mask, ...).
@@ -816,13 +872,18 @@ def synthesize_batch(notes, sr, n_fft=1024, hop_length=256, *, seeds=None, phis=
     fresh key each, like ``synthesize(seed=None)``); ``phis``: one injected [bins, T] phase array (or None) per note;
     ``phi_seeds``: one numpy seed (or None) per note, ``synthesize(phi_seed=)`` — a note takes an array or a seed, not both.
     Seeded notes share their passes with array-injected ones; their phases are drawn on the device (goofer_phase_fill).
+    ``noise_seeds``: one int in [0, 2**32) (or None) per note, ``synthesize(noise_seed=)``: note i renders what a reference
+    process produces that calls ``np.random.seed(noise_seeds[i])`` immediately before ``gf.synthesize`` — its f0, sub-harmonic
+    and volume jitter normals and its roughness noises are drawn on the device (goofer_legacy_normal_jobs), and numpy's global
+    generator is neither read nor advanced for that note.  Seeded and unseeded notes share passes; the unseeded ones keep
+    their host draws in note order, so the global state after the call is what those notes alone leave.
 
-    Result i equals ``synthesize(**notes[i] merged over kw, sr=sr, ..., seed=seeds[i], phi=phis[i], phi_seed=phi_seeds[i])`` bit for bit, and the
-    legacy ``np.random`` state afterwards equals its state after those calls in list order: every host draw is made in
-    note order before any device work.  Notes are cut into passes by ``synth_pass_key`` / ``plan_synth_passes``.  The
+    Result i equals ``synthesize(**notes[i] merged over kw, sr=sr, ..., seed=seeds[i], phi=phis[i], phi_seed=phi_seeds[i],
+    noise_seed=noise_seeds[i])`` bit for bit, and the legacy ``np.random`` state afterwards equals its state after those calls
+    in list order: every host draw is made in note order before any device work.  Notes are cut into passes by ``synth_pass_key`` / ``plan_synth_passes``.  The
     returned arrays may be views into one host block per stem and pass: copy before writing in place.  An unknown keyword
-    or ``seeds`` / ``phis`` of the wrong length raise before anything is drawn or launched; a note with ``len(y) == 0``
-    gives four empty arrays."""
+    or ``seeds`` / ``phis`` of the wrong length raise before anything is drawn or launched, a bad legacy seed or ``noise_seeds``
+    of the wrong length ValueError likewise; a note with ``len(y) == 0`` gives four empty arrays."""
     notes = list(notes)
     defaults = _synth_defaults()
     for name in list(kw) + [k for note in notes for k in note if k not in _NOTE_ARRAYS]:
@@ -838,13 +899,14 @@ def synthesize_batch(notes, sr, n_fft=1024, hop_length=256, *, seeds=None, phis=
     if len(seeds) != n or len(phis) != n:
         raise ValueError(f"synthesize_batch: {n} notes, {len(seeds)} seeds and {len(phis)} phase arrays")
     phi_seeds = _phase_seeds(phi_seeds, phis, n, "synthesize_batch")
+    noise_seeds = _noise_seeds(noise_seeds, n, "synthesize_batch")
     c = _ctx(sr, n_fft, hop_length, ctx)
     base = {**defaults, **kw}
     results, jobs = [None] * n, [None] * n
     for i, note in enumerate(notes):
         merged = {**base, **{k: v for k, v in note.items() if k not in _NOTE_ARRAYS}}
         try:
-            r = _prepare_note(c, note, merged, seeds[i], phis[i], sr, n_fft, hop_length, phi_seeds[i])
+            r = _prepare_note(c, note, merged, seeds[i], phis[i], sr, n_fft, hop_length, phi_seeds[i], noise_seeds[i])
         except Exception as e:                                  # the note's own refusal: its slot, the others render
             results[i] = e
             continue
@@ -876,7 +938,7 @@ def _render(c, jobs, results, sr):
 
 
 def resynthesize_batch(signals, sr, n_fft=1024, hop_length=256, *, f0_min=75, f0_merge_range=2, pitch_tracker=None, variants=None,
-                       seeds=None, phis=None, phi_seeds=None, ctx=None, **synth_kw):
+                       seeds=None, phis=None, phi_seeds=None, noise_seeds=None, ctx=None, **synth_kw):
     """The reference's wav-to-wav flow (GOOFER.py:1222-1330, test.py) for many signals: per signal ``extract_features``, then
     one ``synthesize`` per variant on those features.  Returns per signal a (reconstruct, harmonic, aper_uv, aper_bre) tuple
     (``variants=None``) or a list of them, one per variant (any ``variants`` list, one entry too); a signal whose analysis raised gets that exception in its slot,
@@ -886,11 +948,14 @@ def resynthesize_batch(signals, sr, n_fft=1024, hop_length=256, *, f0_min=75, f0
     to the signal's own extracted formants, as both reference scripts pass them.  ``seeds`` / ``phis``: one Philox key / one
     injected phase array (or None) per (signal, variant), signal-major: entry ``i * len(variants) + v``; ``phi_seeds``: one numpy
     phase seed (or None) per (signal, variant) in the same order, ``synthesize(phi_seed=)`` — an array or a seed, not both.
+    ``noise_seeds``: one legacy seed (an int in [0, 2**32), or None) per SIGNAL, given to each of its variants as
+    ``synthesize(noise_seed=)``: every variant renders as if ``np.random.seed(noise_seeds[i])`` ran just before its
+    ``synthesize``.  Its draws are made on the device and numpy's global generator is neither read nor advanced for it.
 
     Result (i, v) equals, bit for bit, ``env, f0, mask, forms, _ = extract_features(y_i, sr, n_fft, hop_length, f0_min=...,
     f0_merge_range=..., pitch_tracker=...)`` then ``synthesize(env, f0, mask, y_i, sr, n_fft, hop_length, formants=forms,
-    **{**synth_kw, **variants[v]}, seed=..., phi=..., phi_seed=...)`` run signal by signal and variant by variant, and the legacy
-    ``np.random`` state afterwards is the state after those calls: every host draw is made in that order before the device
+    **{**synth_kw, **variants[v]}, seed=..., phi=..., phi_seed=..., noise_seed=noise_seeds[i])`` run signal by signal and
+    variant by variant, and the legacy ``np.random`` state afterwards is the state after those calls: every host draw is made in that order before the device
     work of its pass.  (A host tracker is called for the signals of an analysis pass before that pass's draws.)
 
     Signals are analysed in device passes of at most ``trackers.FRAME_BUDGET`` STFT frames (``trackers.plan_passes``); each
@@ -898,7 +963,8 @@ def resynthesize_batch(signals, sr, n_fft=1024, hop_length=256, *, f0_min=75, f0
     The envelope, per-sample f0 and voicing mask stay on the device from analysis to synthesis (``trackers.analyse_device``);
     the one case that brings a signal's f0 to the host is a time-stretched variant with ``f0_jitter`` or ``add_subharm``,
     whose fp64 stretch is host arithmetic (``_stretch64``).  A one-frame f0 track is post-processed on the host.  An unknown
-    keyword, or ``seeds`` / ``phis`` of the wrong length, raise before anything is analysed or drawn."""
+    keyword, ``seeds`` / ``phis`` of the wrong length, a bad legacy seed or ``noise_seeds`` of the wrong length raise before
+    anything is analysed or drawn."""
     from . import trackers
     signals = list(signals)
     one = variants is None
@@ -913,6 +979,7 @@ def resynthesize_batch(signals, sr, n_fft=1024, hop_length=256, *, f0_min=75, f0
     if len(seeds) != n * V or len(phis) != n * V:
         raise ValueError(f"resynthesize_batch: {n} signals x {V} variants, {len(seeds)} seeds and {len(phis)} phase arrays")
     phi_seeds = _phase_seeds(phi_seeds, phis, n * V, "resynthesize_batch")
+    noise_seeds = _noise_seeds(noise_seeds, n, "resynthesize_batch")
     c = _ctx(sr, n_fft, hop_length, ctx)
     track_fn = trackers.get(pitch_tracker)
     results = [None] * n
@@ -935,7 +1002,7 @@ def resynthesize_batch(signals, sr, n_fft=1024, hop_length=256, *, f0_min=75, f0
                 merged = {**defaults, "formants": f["formants"], **synth_kw, **var}
                 try:
                     r = _prepare_note(c, note, merged, seeds[i * V + v], phis[i * V + v], sr, n_fft, hop_length,
-                                      phi_seeds[i * V + v])
+                                      phi_seeds[i * V + v], noise_seeds[i])
                 except Exception as e:                          # the variant's own refusal: its slot, the others render
                     out[v] = e
                     continue
@@ -955,10 +1022,11 @@ def resynthesize_batch(signals, sr, n_fft=1024, hop_length=256, *, f0_min=75, f0
     return results
 
 
-def resynthesize(y, sr, n_fft=1024, hop_length=256, **kw):
+def resynthesize(y, sr, n_fft=1024, hop_length=256, *, noise_seed=None, **kw):
     """``resynthesize_batch`` for one signal: its (reconstruct, harmonic, aper_uv, aper_bre), or a list of them with
-    ``variants``.  Raises what the analysis or a synthesis raised."""
-    res = resynthesize_batch([y], sr, n_fft, hop_length, **kw)[0]
+    ``variants``.  ``noise_seed``: the signal's legacy seed (``resynthesize_batch(noise_seeds=[noise_seed])``).  Raises what the
+    analysis or a synthesis raised."""
+    res = resynthesize_batch([y], sr, n_fft, hop_length, noise_seeds=[noise_seed], **kw)[0]
     if isinstance(res, BaseException):
         raise res
     for r in res if isinstance(res, list) else ():
@@ -976,23 +1044,30 @@ def synthesize(env_spec, f0_interp, voicing_mask, y, sr, n_fft=1024, hop_length=
                subharm_vibrato_depth=0.1, subharm_f0_jitter=0, subharm_vibrato_delay=0.1, F1_shift=1.0, F2_shift=1.0,
                F3_shift=1.0, F4_shift=1.0, formants=None, roughness_on=False, rough_k_list=(2, 3, 4), rough_h_list=None,
                rough_alpha=0.6, rough_hp_fc=320.0, rough_noise_amp=0.6, rough_noise_smooth_ms=120.0, rough_alpha_slew_ms=120.0,
-               *, phi=None, phi_seed=None, seed=None, ctx=None):
+               *, phi=None, phi_seed=None, noise_seed=None, seed=None, ctx=None):
     """gf.synthesize for one note on the GPU -> (reconstruct, harmonic, aper_uv, aper_bre), fp32: synthesize_batch of this
     one note.
 
     The positional order and keyword set are the reference's (GOOFER.py:971-983; ``glottal_smoothing`` is accepted and
-    unused there too); an unknown keyword raises TypeError like it does there.  Four keyword-ONLY additions:
+    unused there too); an unknown keyword raises TypeError like it does there.  Five keyword-ONLY additions:
     ``phi`` ``[bins, T]`` injects the aperiodic branch's random phases (parity runs); ``phi_seed``, a non-negative integer
     of any size, injects the phases the reference draws with that seed — ``np.random.default_rng(phi_seed).uniform(0, 2 pi,
     (bins, T)).astype(float32)`` for the note's own frame count T (behind a time stretch: the stretched note's), made on the
     device, the same bits as passing that array as ``phi``; both together, or a negative seed, raise ValueError.  Otherwise
     the device draws the phases from Philox keyed by ``seed`` (a fresh key per call when None, like the reference's unseeded
-    generator); ``ctx`` picks the device context."""
-    note = {k: v for k, v in locals().items() if k not in ("sr", "n_fft", "hop_length", "phi", "phi_seed", "seed", "ctx")}
+    generator); ``ctx`` picks the device context.  ``noise_seed``, an integer in [0, 2**32) (anything else: ValueError), renders
+    what a reference process produces that calls ``np.random.seed(noise_seed)`` immediately before ``gf.synthesize``: the
+    f0, sub-harmonic f0, harmonic and breath volume jitter normals are one run of that seed's legacy stream and each
+    roughness partial's noise is the stream of 1337 + idx, all drawn on the device (goofer_legacy_normal_jobs; equal to the
+    host's draws up to the last place of ``log``).  numpy's global generator is then neither read nor advanced — not seeded
+    with ``noise_seed``, and not left re-seeded by the roughness layer as the reference leaves it.  None (default): the draws
+    come from the global generator on the host, as they always have."""
+    note = {k: v for k, v in locals().items() if k not in ("sr", "n_fft", "hop_length", "phi", "phi_seed", "noise_seed", "seed", "ctx")}
     if phi is not None and phi_seed is not None:
         raise ValueError("synthesize: phi and phi_seed are exclusive; give one of them")
     phi_seed = check_phi_seed(phi_seed)
-    res = synthesize_batch([note], sr, n_fft, hop_length, seeds=[seed], phis=[phi], phi_seeds=[phi_seed], ctx=ctx)[0]
+    res = synthesize_batch([note], sr, n_fft, hop_length, seeds=[seed], phis=[phi], phi_seeds=[phi_seed], noise_seeds=[noise_seed],
+                           ctx=ctx)[0]
     if isinstance(res, BaseException):
         raise res
     return res

@@ -613,6 +613,7 @@ int goofer_sizeof(int which)
     case 6: return (int)sizeof(goofer_post);
     case 7: return (int)sizeof(goofer_plan_request);
     case 8: return (int)sizeof(goofer_plan_geometry);
+    case 9: return (int)sizeof(goofer_legacy_job);
     }
     return -1;
 }
@@ -942,6 +943,16 @@ int goofer_legacy_normal_fill(goofer_ctx *ctx, const uint32_t *seeds, const unsi
         return goofer_fail(ctx, GOOFER_EINVAL, "goofer_legacy_normal_fill: seeds must be 4-byte aligned, sample_off, the outputs and attempts 8-byte aligned");
     if (total_samples == 0 && !attempts) return GOOFER_OK;
     return launch_legacy_normal_fill(ctx, seeds, stream_on, sample_off, n_notes, out_f0, out_vol_h, out_vol_b, attempts, (hipStream_t)stream);
+}
+
+int goofer_legacy_normal_jobs(goofer_ctx *ctx, const goofer_legacy_job *jobs, int n_jobs, int64_t *attempts, void *stream)
+{
+    if (!ctx) return GOOFER_EINVAL;
+    if (!jobs) return goofer_fail(ctx, GOOFER_EINVAL, "goofer_legacy_normal_jobs: null pointer");
+    if (n_jobs < 0) return goofer_fail(ctx, GOOFER_EINVAL, "goofer_legacy_normal_jobs: negative count (%d jobs)", n_jobs);
+    if (((uintptr_t)jobs & 7) || ((uintptr_t)attempts & 7))
+        return goofer_fail(ctx, GOOFER_EINVAL, "goofer_legacy_normal_jobs: jobs and attempts must be 8-byte aligned");
+    return launch_legacy_normal_jobs(ctx, jobs, n_jobs, attempts, (hipStream_t)stream);
 }
 
 int goofer_stretch_rows(goofer_ctx *ctx, const float *in, int64_t ld_in, int64_t rows_in, float *out, int64_t ld_out, int64_t rows_out,

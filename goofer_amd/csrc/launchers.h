@@ -74,6 +74,7 @@ int launch_phase_fill(goofer_ctx *ctx, const uint64_t *words, const int64_t *fra
                       float *out, int ld, hipStream_t st);
 int launch_legacy_normal_fill(goofer_ctx *ctx, const uint32_t *seeds, const unsigned char *stream_on, const int64_t *sample_off, int n_notes,
                               double *out_f0, double *out_vol_h, double *out_vol_b, int64_t *attempts, hipStream_t st);
+int launch_legacy_normal_jobs(goofer_ctx *ctx, const goofer_legacy_job *jobs, int n_jobs, int64_t *attempts, hipStream_t st);
 
 // post.hip
 int launch_onepole(goofer_ctx *ctx, const float *src, float *dst, const float *f0, const goofer_onepole_job *jobs, int n_jobs,

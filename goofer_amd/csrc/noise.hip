@@ -6,6 +6,8 @@
 //                     seed, written frame-major into the batch's phase matrix (second part of this file)      GOOFER.py:1151-1152
 //   k_legacy_normal_fill   the sh / sr normals as a seeded reference process draws them: numpy's legacy MT19937 + polar Box-Muller
 //                     stream of every note's seed, one workgroup per note (last part of this file)      GOOFER.py:653, 666
+//   k_legacy_normal_jobs   the same stream by job table: a seed, a sample count, up to four destinations and a float32 switch
+//                     per job — every legacy draw of gf.synthesize (f0, sub-harmonic, volume jitter; the roughness noises)
 //
 // The stream is a definition (tests/noise_ref.py restates it in numpy, word for word):
 //   block    Philox-4x32, 10 rounds (philox_rounds<10>, the round function the phases use with 7)
@@ -233,15 +235,16 @@ int launch_phase_fill(goofer_ctx *ctx, const uint64_t *words, const int64_t *fra
 //   double   two words a, b: ((a >> 5) * 2^26 + (b >> 6)) * 2^-53
 //   attempt  two doubles: x1 = 2 d0 - 1, x2 = 2 d1 - 1, r2 = x1 x1 + x2 x2 (two rounded products, one rounded sum); rejected
 //            when r2 >= 1 or r2 == 0, else f = sqrt(-2 log(r2) / r2) and the normals f x2, f x1 in that order
-// A block is 156 whole attempts.  One workgroup owns one note (LN_WG threads; option "legacy_wave": one wave) and walks its
+// A block is 156 whole attempts.  One workgroup owns one job (LN_WG threads; option "legacy_wave": one wave) — a note's enabled
+// streams (k_legacy_normal_fill), or an entry of a job table (k_legacy_normal_jobs; both run legacy_fill_job) — and walks its
 // blocks in order.  The in-place twist has a fixed dependency order: k in [0, 227) reads old words only, [227, 454) the new
 // words of [0, 227), [454, 624) the new words of [227, 397) and, for k = 623, of mt[0] — three steps, each of which loads every
 // operand (mt[k + 1] must still be old) before any lane stores.  The attempts of a block are independent: a lane tempers its
 // four words, and the accepted ones are compacted behind the note's running count by wave ballots (and the wave totals in
-// LDS).  Normal p of the note goes to enabled stream p / n at sample p % n (n the note's samples; streams in the reference's
-// order: f0 jitter, harmonic volume, breath volume).  The block loop is bounded: 2 ceil(m / 245) + 4 blocks for m normals
-// (a block accepts 156 pi / 4 = 122.5 attempts on average, 245 normals, sd 10); a note that needs more raises the handle's
-// check word LEGACY_FLAG (goofer_check) and stops.
+// LDS).  Normal p of the job goes to destination p / n at sample p % n (n the job's samples; a note's destinations are its
+// enabled streams in the reference's order: f0 jitter, harmonic volume, breath volume).  The block loop is bounded:
+// 2 ceil(m / 245) + 4 blocks for m normals (a block accepts 156 pi / 4 = 122.5 attempts on average, 245 normals, sd 10); a
+// job that needs more raises the handle's check word LEGACY_FLAG (goofer_check) and stops.
 #define LN_WORDS 624
 #define LN_SHIFT 397
 #define LN_ATTEMPTS 156
@@ -281,40 +284,36 @@ __device__ __forceinline__ uint32_t mt_temper(uint32_t y)
     return y;
 }
 
+// One job of one workgroup: the first m = n * nd normals after np.random.seed(seed), normal p to destination p / n at sample
+// p % n (d0..d3: the first nd of them are the job's destinations in order, already at the job's first sample; a null one drops
+// its draws), each rounded to float32 and widened again first when f32 is set.  att: where the attempts go (or null); id: what
+// the check word takes when the block bound is hit.  Every argument is uniform over the workgroup.
+// (the destinations as four pointers and branches: a select chain or an indexed array over them becomes a table in scratch)
 template <int NT>
-__global__ __launch_bounds__(NT) void k_legacy_normal_fill(const uint32_t *__restrict__ seeds, const unsigned char *__restrict__ stream_on,
-                                                           const int64_t *__restrict__ sample_off, double *__restrict__ out_f0,
-                                                           double *__restrict__ out_vol_h, double *__restrict__ out_vol_b,
-                                                           int64_t *__restrict__ attempts, int32_t *__restrict__ flag)
+__device__ __forceinline__ void legacy_fill_job(uint32_t *mt, int *wave_cnt, uint32_t seed, int64_t n, int nd, double *d0, double *d1,
+                                                double *d2, double *d3, bool f32, int64_t *att, int32_t *flag, int id)
 {
-    __shared__ __attribute__((aligned(16))) uint32_t mt[LN_WORDS];
-    __shared__ int wave_cnt[NT / 64];
-    const int note = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
-    const int64_t base = sample_off[note];
-    const int64_t n = sample_off[note + 1] - base;
-    const unsigned char *on = stream_on + 3 * (int64_t)note;
-    const bool e0 = on[0] != 0, e1 = on[1] != 0, e2 = on[2] != 0;
-    const int64_t m = n > 0 ? n * ((int)e0 + (int)e1 + (int)e2) : 0;   // normals of the note
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int64_t m = n > 0 ? n * nd : 0;                      // normals of the job
     if (m <= 0) {                                              // (uniform: nobody waits at a barrier)
-        if (attempts && tid == 0) attempts[note] = 0;
+        if (att && tid == 0) *att = 0;
         return;
     }
-    // the enabled streams in order (a null output: its draws are consumed and dropped)
-    // (as stream numbers and branches: a select chain over the three pointers becomes a table in scratch)
-    const int sid0 = e0 ? 0 : (e1 ? 1 : 2), sid1 = (e0 && e1) ? 1 : 2;
     auto put = [=](int64_t p, double v) {
-        const int s = (p >= n) + (p >= 2 * n);
-        const int sid = s == 0 ? sid0 : (s == 1 ? sid1 : 2);
-        const int64_t i = base + (p - s * n);
-        if (sid == 0) {
-            if (out_f0) out_f0[i] = v;
-        } else if (sid == 1) {
-            if (out_vol_h) out_vol_h[i] = v;
-        } else if (out_vol_b) {
-            out_vol_b[i] = v;
+        const int s = (p >= n) + (p >= 2 * n) + (p >= 3 * n);
+        const int64_t i = p - s * n;
+        if (f32) v = (double)(float)v;
+        if (s == 0) {
+            if (d0) d0[i] = v;
+        } else if (s == 1) {
+            if (d1) d1[i] = v;
+        } else if (s == 2) {
+            if (d2) d2[i] = v;
+        } else if (d3) {
+            d3[i] = v;
         }
     };
-    uint32_t v = seeds[note];                                  // every lane runs the recurrence and keeps the words it owns
+    uint32_t v = seed;                                         // every lane runs the recurrence and keeps the words it owns
     for (int i = 0; i < LN_WORDS; ++i) {
         if ((i & (NT - 1)) == tid) mt[i] = v;
         v = 1812433253u * (v ^ (v >> 30)) + (uint32_t)(i + 1);
@@ -325,7 +324,7 @@ __global__ __launch_bounds__(NT) void k_legacy_normal_fill(const uint32_t *__res
     int64_t done = 0;                                          // accepted so far (uniform)
     for (int64_t blk = 0; done < need; ++blk) {
         if (blk >= max_blocks) {
-            if (tid == 0) atomicMax(flag, note + 1);
+            if (tid == 0) atomicMax(flag, id);
             break;
         }
         mt_twist_step<NT, 0, LN_WORDS - LN_SHIFT>(mt, tid);
@@ -338,10 +337,10 @@ __global__ __launch_bounds__(NT) void k_legacy_normal_fill(const uint32_t *__res
             double x1 = 0.0, x2 = 0.0, r2 = 1.0;
             if (a < LN_ATTEMPTS) {
                 const uint4 w = *reinterpret_cast<const uint4 *>(mt + 4 * a);
-                const double d0 = ((double)(mt_temper(w.x) >> 5) * 67108864.0 + (double)(mt_temper(w.y) >> 6)) * 0x1p-53;
-                const double d1 = ((double)(mt_temper(w.z) >> 5) * 67108864.0 + (double)(mt_temper(w.w) >> 6)) * 0x1p-53;
-                x1 = 2.0 * d0 - 1.0;                           // (exact: multiples of 2^-52 in [-1, 1))
-                x2 = 2.0 * d1 - 1.0;
+                const double u0 = ((double)(mt_temper(w.x) >> 5) * 67108864.0 + (double)(mt_temper(w.y) >> 6)) * 0x1p-53;
+                const double u1 = ((double)(mt_temper(w.z) >> 5) * 67108864.0 + (double)(mt_temper(w.w) >> 6)) * 0x1p-53;
+                x1 = 2.0 * u0 - 1.0;                           // (exact: multiples of 2^-52 in [-1, 1))
+                x2 = 2.0 * u1 - 1.0;
                 r2 = __dadd_rn(__dmul_rn(x1, x1), __dmul_rn(x2, x2));
                 acc = !(r2 >= 1.0 || r2 == 0.0);
             }
@@ -365,11 +364,50 @@ __global__ __launch_bounds__(NT) void k_legacy_normal_fill(const uint32_t *__res
                 const double f = sqrt(-2.0 * log(r2) / r2);
                 put(p, f * x2);
                 if (p + 1 < m) put(p + 1, f * x1);
-                if (attempts && j == need - 1) attempts[note] = blk * LN_ATTEMPTS + a + 1;
+                if (att && j == need - 1) *att = blk * LN_ATTEMPTS + a + 1;
             }
             done += round_total;
         }
     }
+}
+
+// goofer_legacy_normal_fill: a note's job is its enabled streams of (f0, harmonic volume, breath volume), in that order
+template <int NT>
+__global__ __launch_bounds__(NT) void k_legacy_normal_fill(const uint32_t *__restrict__ seeds, const unsigned char *__restrict__ stream_on,
+                                                           const int64_t *__restrict__ sample_off, double *__restrict__ out_f0,
+                                                           double *__restrict__ out_vol_h, double *__restrict__ out_vol_b,
+                                                           int64_t *__restrict__ attempts, int32_t *__restrict__ flag)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t mt[LN_WORDS];
+    __shared__ int wave_cnt[NT / 64];
+    const int note = blockIdx.x;
+    const int64_t base = sample_off[note];
+    const int64_t n = sample_off[note + 1] - base;
+    const unsigned char *on = stream_on + 3 * (int64_t)note;
+    const bool e0 = on[0] != 0, e1 = on[1] != 0, e2 = on[2] != 0;
+    double *const s0 = out_f0 ? out_f0 + base : nullptr, *const s1 = out_vol_h ? out_vol_h + base : nullptr,
+                 *const s2 = out_vol_b ? out_vol_b + base : nullptr;
+    // the enabled streams moved to the front (a null output: its draws are consumed and dropped)
+    double *const d0 = e0 ? s0 : (e1 ? s1 : s2);
+    double *const d1 = (e0 && e1) ? s1 : s2;
+    legacy_fill_job<NT>(mt, wave_cnt, seeds[note], n, (int)e0 + (int)e1 + (int)e2, d0, d1, s2, nullptr, false,
+                        attempts ? attempts + note : nullptr, flag, note + 1);
+}
+
+// goofer_legacy_normal_jobs: the job table
+template <int NT>
+__global__ __launch_bounds__(NT) void k_legacy_normal_jobs(const goofer_legacy_job *__restrict__ jobs, int64_t *__restrict__ attempts,
+                                                           int32_t *__restrict__ flag)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t mt[LN_WORDS];
+    __shared__ int wave_cnt[NT / 64];
+    const goofer_legacy_job *jb = jobs + blockIdx.x;
+    int nd = jb->n_dst;
+    nd = nd < 0 ? 0 : (nd > 4 ? 4 : nd);
+    double *const d0 = jb->dst[0] ? jb->dst[0] + jb->off[0] : nullptr, *const d1 = jb->dst[1] ? jb->dst[1] + jb->off[1] : nullptr,
+                 *const d2 = jb->dst[2] ? jb->dst[2] + jb->off[2] : nullptr, *const d3 = jb->dst[3] ? jb->dst[3] + jb->off[3] : nullptr;
+    legacy_fill_job<NT>(mt, wave_cnt, jb->seed, jb->n, nd, d0, d1, d2, d3, (jb->flags & GOOFER_LEGACY_F32) != 0,
+                        attempts ? attempts + blockIdx.x : nullptr, flag, (int)blockIdx.x + 1);
 }
 
 int launch_legacy_normal_fill(goofer_ctx *ctx, const uint32_t *seeds, const unsigned char *stream_on, const int64_t *sample_off, int n_notes,
@@ -383,6 +421,18 @@ int launch_legacy_normal_fill(goofer_ctx *ctx, const uint32_t *seeds, const unsi
     else
         hipLaunchKernelGGL(k_legacy_normal_fill<LN_WG>, dim3((unsigned)n_notes), dim3(LN_WG), 0, st, seeds, stream_on, sample_off, out_f0,
                            out_vol_h, out_vol_b, attempts, flag);
+    LAUNCH_CHECK(ctx);
+    return GOOFER_OK;
+}
+
+int launch_legacy_normal_jobs(goofer_ctx *ctx, const goofer_legacy_job *jobs, int n_jobs, int64_t *attempts, hipStream_t st)
+{
+    if (n_jobs <= 0) return GOOFER_OK;
+    int32_t *flag = ctx->ovf_flag + LEGACY_FLAG;
+    if (ctx->legacy_wave)
+        hipLaunchKernelGGL(k_legacy_normal_jobs<64>, dim3((unsigned)n_jobs), dim3(64), 0, st, jobs, attempts, flag);
+    else
+        hipLaunchKernelGGL(k_legacy_normal_jobs<LN_WG>, dim3((unsigned)n_jobs), dim3(LN_WG), 0, st, jobs, attempts, flag);
     LAUNCH_CHECK(ctx);
     return GOOFER_OK;
 }

@@ -360,6 +360,53 @@ class Context:
         self._fill_keep = keep                                  # this call's uploads, until the next call (stream order frees them safely)
         return (out, d_att) if attempts else out
 
+    def legacy_normal_jobs(self, jobs, attempts=False):
+        """numpy's legacy normal stream by job table, drawn on the device (goofer_legacy_normal_jobs; the stream's definition:
+        include/goofer_hip.h, restated in tests/mt_ref.py and tests/legacy_jobs_ref.py) — every legacy draw of ``gf.synthesize``.
+        ``jobs``: a sequence of ``(seed, n, destinations, f32)``: ``seed`` an int in [0, 2**32); ``n`` the samples per destination;
+        ``destinations`` up to four ``(tensor, offset)`` pairs in order, or None for a destination whose ``n`` draws are consumed
+        and dropped — ``tensor`` a contiguous float64 tensor on this context's device that holds ``offset + n`` elements;
+        ``f32`` rounds every normal to float32 and widens it again (``randn(n).astype(np.float32)`` held in float64).  Job j writes
+        what ``np.random.seed(seed)`` followed by one ``np.random.randn(n)`` per destination gives, normal p to destination p // n
+        at ``offset + p % n`` — exact up to the last place of ``log``.  A job with ``n == 0`` or no destination draws nothing.
+        Everything is checked before anything is uploaded or launched (ValueError).  Asynchronous on the current stream; a job
+        that runs into its block bound is reported by ``check()``.  Returns None, or with ``attempts=True`` the int64 [len(jobs)]
+        tensor of attempts each job's normals took."""
+        jobs = list(jobs)
+        tab = np.zeros(len(jobs), dtype=_lib.LEGACY_JOB)
+        for j, job in enumerate(jobs):
+            try:
+                seed, n, dsts, f32 = job
+                n = int(n)
+                dsts = list(dsts)
+            except (TypeError, ValueError):
+                raise ValueError(f"legacy_normal_jobs: job {j} is (seed, n, destinations, f32)") from None
+            if seed is None:
+                raise ValueError(f"legacy_normal_jobs: job {j} has no seed")
+            seed = check_noise_seed(seed, "the seed of job %d" % j)
+            if n < 0 or len(dsts) > 4:
+                raise ValueError(f"legacy_normal_jobs: job {j} has {n} samples and {len(dsts)} destinations (at most four)")
+            rec = tab[j]
+            rec["seed"], rec["flags"], rec["n"], rec["n_dst"] = seed, _lib.LEGACY_F32 if f32 else 0, n, len(dsts)
+            for k, d in enumerate(dsts):
+                if d is None:
+                    continue
+                t, off = d
+                off = int(off)
+                if (not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or not t.is_contiguous() or t.device != self.device
+                        or off < 0 or off + n > t.numel()):
+                    raise ValueError(f"legacy_normal_jobs: destination {k} of job {j} must be a contiguous float64 tensor on this "
+                                     f"context's device that holds offset + n = {off} + {n} elements")
+                rec["dst"][k], rec["off"][k] = t.data_ptr(), off
+        if self.lib.goofer_sizeof(9) != _lib.LEGACY_JOB.itemsize:
+            raise GooferError("goofer_legacy_job layout mismatch between libgoofer_hip.so and the binding")
+        d_att = torch.zeros(len(jobs), dtype=torch.int64, device=self.device) if attempts else None
+        if jobs:
+            d_tab = self.tensor(tab.view(np.uint8))
+            self._check(self.lib.goofer_legacy_normal_jobs(self.h, _ptr(d_tab), len(jobs), _ptr(d_att), self._stream()))
+            self._fill_keep = [d_tab]                           # this call's upload, until the next call (stream order frees it safely)
+        return d_att
+
     def counter(self, name: str) -> int:
         """Cumulative device-side counter of the handle (goofer_counter): 'pulse_scanned_notes', 'pulse_fallback_notes',
         'mask_flag_segments', 'mask_staged_segments'."""

@@ -1073,16 +1073,16 @@ class PipelinedRenderer:
             ln["r"].ctx.close()
         self.lanes = []
 
-    def _prepare(self, k, group, note_ids):
+    def _prepare(self, k, group, note_ids, noise_seeds=None):
         if self.trace is not None:
             t0 = time.perf_counter()
             try:
-                return self._prepare_batch(k, group, note_ids)
+                return self._prepare_batch(k, group, note_ids, noise_seeds)
             finally:
                 self.trace.append(("prepare", k, t0, time.perf_counter()))
-        return self._prepare_batch(k, group, note_ids)
+        return self._prepare_batch(k, group, note_ids, noise_seeds)
 
-    def _prepare_batch(self, k, group, note_ids):
+    def _prepare_batch(self, k, group, note_ids, noise_seeds=None):
         """group: [(index of the caller's batch, (sources, requests)), ...] — one device batch.  Returns (prep, note counts)."""
         ln = self.lanes[k % len(self.lanes)]
         if len(group) == 1:
@@ -1101,8 +1101,20 @@ class PipelinedRenderer:
                 counts.append(len(rj))
                 ids.extend(note_ids(j, len(rj)) if note_ids else range(len(rj)))   # the ids the batch has when it is rendered alone
             reqs = S.RequestBatch.from_requests(reqs) if (reqs and isinstance(reqs[0], S.Request)) else S.decode_request_batch(reqs)
+        legacy = None
+        if noise_seeds is not None:                            # the caller's batches' seed lists, back to back like their notes
+            if any(j >= len(noise_seeds) for j, _ in group):
+                raise ValueError(f"noise_seeds: {len(noise_seeds)} entries, and a batch {max(j for j, _ in group)}")
+            per = [noise_seeds[j] for j, _ in group]
+            if any(p is not None for p in per):
+                if any(p is None for p in per):
+                    raise ValueError("noise_seeds: batches %s share one device batch (coalesce): seed all of them or none"
+                                     % [j for j, _ in group])
+                if [len(p) for p in per] != counts:
+                    raise ValueError(f"noise_seeds: batches {[j for j, _ in group]} have {counts} notes and {[len(p) for p in per]} seeds")
+                legacy = [check_noise_seed(sd, "noise_seeds[%d][%d]" % (j, i)) for (j, _), p in zip(group, per) for i, sd in enumerate(p)]
         with torch.cuda.stream(ln["stream"]):
-            return ln["r"].prepare((srcs, reqs), note_ids=ids, device_calls=False), counts
+            return ln["r"].prepare((srcs, reqs), note_ids=ids, device_calls=False, noise_seeds=legacy), counts
 
     def _groups(self, batches):
         """The caller's batches, ``coalesce`` of them to a device batch (RequestBatch objects and the tail of the job: as they come)."""
@@ -1127,11 +1139,15 @@ class PipelinedRenderer:
         if group:
             yield group
 
-    def render_iter(self, batches, seed: int = 0, note_ids=None, pcm16: bool = False):
+    def render_iter(self, batches, seed: int = 0, note_ids=None, pcm16: bool = False, noise_seeds=None):
         """``batches``: an iterable of (sources, requests) — requests as a ``RequestBatch``, a list of ``Request`` or a list of
         argument lists (decoded on the worker threads).  ``note_ids(k, n)``: the Philox ids of batch k's notes (default: the
         position in the batch).  ``pcm16``: yield the wav's int16 samples (converted on the device, goofer_pcm16: what
-        ``write_wav`` computes on the host) — half the bytes over PCIe, which is what bounds a long job."""
+        ``write_wav`` computes on the host) — half the bytes over PCIe, which is what bounds a long job.  ``noise_seeds``: a
+        sequence with one entry per batch — the batch's per-note legacy seeds, ``Renderer.render(noise_seeds=)`` (the sh / sr
+        normals of a reference process seeded per note, drawn on the device; numpy's global generator is not touched), or None
+        for a batch that draws as the renderer's ``noise`` says.  A bad seed, a list of the wrong length or a batch without an
+        entry raises ValueError from the iterator when that batch is reached."""
         import collections
         import sys
         it = iter(enumerate(self._groups(batches)))
@@ -1148,13 +1164,13 @@ class PipelinedRenderer:
         if frozen:
             gc.freeze()
         try:
-            yield from self._render_iter(it, ahead, seed, note_ids, pcm16)
+            yield from self._render_iter(it, ahead, seed, note_ids, pcm16, noise_seeds)
         finally:
             sys.setswitchinterval(old_interval)
             if frozen:
                 gc.unfreeze()
 
-    def _render_iter(self, it, ahead, seed, note_ids, pcm16):
+    def _render_iter(self, it, ahead, seed, note_ids, pcm16, noise_seeds=None):
         import collections
 
         def feed():
@@ -1162,7 +1178,7 @@ class PipelinedRenderer:
                 nxt = next(it, None)
                 if nxt is None:
                     return
-                ahead.append(self.pool.submit(self._prepare, nxt[0], nxt[1], note_ids))
+                ahead.append(self.pool.submit(self._prepare, nxt[0], nxt[1], note_ids, noise_seeds))
 
         flying = collections.deque()                           # (lane, event, prep, out, samples)
         k = 0

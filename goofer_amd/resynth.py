@@ -2,7 +2,7 @@
 
     python -m goofer_amd.resynth [--out DIR] [--n-fft 1024] [--hop N] [--tracker native|praat|module:fn]
            [--pitch R] [--formant R] [--stretch R] [--F1 R ... --F4 R] [--set key=value ...]
-           [--variant "key=value,key=value" ...] [--stems] [--seed S] INPUT...
+           [--variant "key=value,key=value" ...] [--stems] [--seed S] [--noise-seed N] INPUT...
 
 Each INPUT is an audio file or a folder, scanned like folder mode (every audio file below it; files this command wrote
 itself, ``*_reconstruct.wav`` and the stems, are left out).  Files are read with ``trackers.read_audio`` (channels averaged),
@@ -15,7 +15,10 @@ folder input's layout below it is kept).
 ``--set key=value`` takes any ``synthesize`` keyword, the value a Python literal (a bare word is a string); ``--variant``
 takes a comma-separated list of them, one synthesis per ``--variant`` from one analysis.  An unknown keyword exits with
 status 2 before anything is read.  ``--seed S`` seeds the legacy ``np.random`` stream (the jitter draws) and gives
-variant v of the k-th file (in input order) the Philox key S + k * variants + v.  A file that fails is logged and skipped;
+variant v of the k-th file (in input order) the Philox key S + k * variants + v.  ``--noise-seed N`` (an integer in
+[0, 2**32)) renders every variant of every file as a reference process does that calls ``np.random.seed(N)`` just before its
+``synthesize``: the jitter and roughness draws are then made on the device (``resynthesize_batch(noise_seeds=)``) and the
+``np.random`` stream is not used for them.  A file that fails is logged and skipped;
 the exit status is 1 if any file failed, else 0.
 """
 from __future__ import annotations
@@ -47,6 +50,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--variant", action="append", default=[], metavar="K=V,K=V", help="one synthesis per --variant")
     ap.add_argument("--stems", action="store_true", help="also write the harmonic, breathiness and unvoiced stems")
     ap.add_argument("--seed", type=int, default=None)
+    ap.add_argument("--noise-seed", type=int, default=None, metavar="N",
+                    help="np.random.seed(N) before every synthesize: its jitter and roughness draws, made on the device")
     return ap
 
 
@@ -135,6 +140,8 @@ def main(argv=None) -> int:
     hop = args.hop if args.hop is not None else args.n_fft // 4
     if args.n_fft < 2 or hop < 1:
         ap.error(f"n_fft {args.n_fft} and hop {hop} must be positive")
+    if args.noise_seed is not None and not 0 <= args.noise_seed < 2 ** 32:
+        ap.error(f"--noise-seed must be an integer in [0, 2**32), got {args.noise_seed}")
 
     import numpy as np
     from . import core, trackers
@@ -162,7 +169,8 @@ def main(argv=None) -> int:
             seeds = [args.seed + k * n_var + v for k, *_ in members for v in range(n_var)]
         try:
             res = core.resynthesize_batch([m[3] for m in members], sr, args.n_fft, hop, pitch_tracker=args.tracker, variants=variants,
-                                          seeds=seeds, **kw)
+                                          seeds=seeds, noise_seeds=None if args.noise_seed is None else [args.noise_seed] * len(members),
+                                          **kw)
         except Exception as e:                                    # noqa: BLE001 - the group could not run: each of its files failed
             res = [e] * len(members)
         for (k, f, root, _), r in zip(members, res):

@@ -614,6 +614,31 @@ int goofer_legacy_normal_fill(goofer_ctx *ctx, const uint32_t *seeds, const unsi
                               int n_notes, int64_t total_samples, double *out_f0, double *out_vol_h, double *out_vol_b,
                               int64_t *attempts, void *stream);
 
+/* The same stream by job table: every legacy draw of gf.synthesize.  Job j draws the first n * n_dst normals after
+ * np.random.seed(seed), and normal p goes to its destination p / n at sample p % n: dst[p / n][off[p / n] + p % n].  That is one
+ * np.random.randn(n) per destination, in order, with the polar method's second value carried from one to the next (an odd n) —
+ * the f0, sub-harmonic f0, harmonic volume and breath volume jitter of a note are one job of up to four destinations
+ * (GOOFER.py:1069-1080, 1185-1191).  A NULL destination among the n_dst consumes its n draws and stores nothing; a job with
+ * n <= 0 or n_dst == 0 draws nothing.  With GOOFER_LEGACY_F32 in flags every normal is rounded to float32 and widened again
+ * before the store — np.random.randn(n).astype(np.float32) held in float64, make_smooth_noise's draw (GOOFER.py:894-899: one job
+ * per roughness partial, seed 1337 + idx, one destination).  One workgroup per job, the arithmetic, the block bound and the
+ * goofer_check report of goofer_legacy_normal_fill (which is the job table of a note's enabled streams: the same bits);
+ * attempts (int64 [n_jobs], or NULL) as there.  Destinations of one call must not overlap.
+ * jobs, everything a job points to and attempts are device arrays; asynchronous on `stream`; needs no plan and no scratch.  The
+ * table is read on the device: the caller answers for n_dst <= 4 (larger counts as 4) and for off[k] + n staying inside dst[k].
+ * GOOFER_EINVAL for a null jobs, a negative count, jobs or attempts not 8-byte aligned. */
+#define GOOFER_LEGACY_F32 1u
+typedef struct {
+    uint32_t seed;              /* np.random.seed's one 32-bit word                                                   */
+    uint32_t flags;             /* GOOFER_LEGACY_F32                                                                   */
+    int64_t n;                  /* samples per destination                                                            */
+    int32_t n_dst;              /* destinations in use, 0..4                                                          */
+    int32_t reserved;
+    double *dst[4];             /* device float64 arrays (NULL: that destination's draws are dropped)                 */
+    int64_t off[4];             /* first element of the job in dst[k]                                                 */
+} goofer_legacy_job;
+int goofer_legacy_normal_jobs(goofer_ctx *ctx, const goofer_legacy_job *jobs, int n_jobs, int64_t *attempts, void *stream);
+
 /* ---- measurement / test hooks --------------------------------------------------------------- */
 
 /* HIP-event timing of every stage of goofer_synth_batch on the caller's stream: begin() arms up to
@@ -644,7 +669,7 @@ const char *goofer_profile_stage_name_ex(const goofer_ctx *ctx, int stage);   /*
  *   "mask_flags" 1 (default): goofer_render_batch has k_sample_assemble leave a word per 1024 samples of the voicing mask (all == 0,
  *               all == 1, neither) and k_mask_short answer the windows those words settle without loading the mask; 0: no flags
  *               (goofer_assemble_batch / goofer_synth_batch on their own and goofer_smooth_mask_ds never have them).  Same bits.
- *   "legacy_wave" 0 (default): goofer_legacy_normal_fill gives a note a workgroup of 256 threads; 1: one wave.  Same bits.
+ *   "legacy_wave" 0 (default): goofer_legacy_normal_fill / _jobs give a job a workgroup of 256 threads; 1: one wave.  Same bits.
  *   "prof_only" s >= 0: goofer_profile_begin .. end record the events of stage s only; -1 (default): every stage     */
 int goofer_set_option(goofer_ctx *ctx, const char *name, int value);
 
@@ -652,7 +677,7 @@ int goofer_set_option(goofer_ctx *ctx, const char *name, int value);
  * intermediate of the last synth batch to HOST memory; return element count / byte size. Tests only. */
 int goofer_debug_table(goofer_ctx *ctx, int which, float *host_out, int capacity);
 /* sizeof of the ABI structs (0 note_params, 1 batch, 2 note_plan, 3 assembly, 4 onepole_job, 5 post_note, 6 post,
- * 7 plan_request, 8 plan_geometry) so bindings can verify layout */
+ * 7 plan_request, 8 plan_geometry, 9 legacy_job) so bindings can verify layout */
 int goofer_sizeof(int which);
 int64_t goofer_debug_fetch(goofer_ctx *ctx, int which, void *host_out, int64_t capacity_bytes);
 
