@@ -119,6 +119,15 @@ class Batch(C.Structure):
     ]
 
 
+class TrackSettings(C.Structure):
+    """goofer_track_settings"""
+    _fields_ = [
+        ("pitch_floor", C.c_int), ("pitch_ceiling", C.c_double), ("silence_threshold", C.c_double),
+        ("voicing_threshold", C.c_double), ("octave_cost", C.c_double), ("octave_jump_cost", C.c_double),
+        ("voiced_unvoiced_cost", C.c_double), ("max_formant", C.c_int), ("n_formants", C.c_int),
+    ]
+
+
 EXPORTS = {
     # name: (restype, argtypes)
     "goofer_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
@@ -185,6 +194,9 @@ EXPORTS = {
     "goofer_host_parse_floats": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "goofer_host_pack": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int]),
     "goofer_host_decode_bends": (C.c_int64, [C.c_char_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    "goofer_track_settings_default": (None, [C.POINTER(TrackSettings)]),
+    "goofer_track_configure": (C.c_int, [C.c_void_p, C.POINTER(TrackSettings)]),
+    "goofer_track_layout": (C.c_int, [C.POINTER(TrackSettings), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "goofer_track_pitch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]),
     "goofer_track_formants": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,

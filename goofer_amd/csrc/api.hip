@@ -614,6 +614,7 @@ int goofer_sizeof(int which)
     case 7: return (int)sizeof(goofer_plan_request);
     case 8: return (int)sizeof(goofer_plan_geometry);
     case 9: return (int)sizeof(goofer_legacy_job);
+    case 10: return (int)sizeof(goofer_track_settings);
     }
     return -1;
 }

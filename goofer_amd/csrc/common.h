@@ -97,6 +97,7 @@ struct goofer_ctx {
     int device = 0;
     char err[512] = {0};
     goofer_plan_t plan;
+    goofer_track_settings track = GOOFER_TRACK_SETTINGS_DEFAULT;   // goofer_track_configure
     // handle-owned device blocks, each grown by grow_block
     void *scratch = nullptr;
     size_t scratch_bytes = 0;

@@ -1,15 +1,20 @@
 // The f0 and formant half of the cold-cache analysis (gfx950), for a ragged batch of fp64 signals at one sample rate.
 //
-// Pitch, Boersma (1993) autocorrelation method with the settings the reference hands to Praat (floor 75 Hz, ceiling 950 Hz,
-// time step hop / sr, 15 candidates, silence 0.03, voicing 0.45, octave 0.01, octave jump 0.35, voiced/unvoiced 0.14):
+// The settings are the handle's goofer_track_settings (goofer_track_configure); their defaults, in brackets below, are what
+// the reference hands to Praat.
+//
+// Pitch, Boersma (1993) autocorrelation method (floor [75] Hz, ceiling [950] Hz, time step hop / sr, 15 candidates, silence
+// [0.03], voicing [0.45], octave [0.01], octave jump [0.35], voiced/unvoiced [0.14]):
 //   k_pitch_stats    per signal: mean and peak of |y - mean| (the unvoiced candidate needs the whole signal's peak)
 //   k_pitch_frames   per frame: mean removed, Hann window of 3 / floor, autocorrelation over the lag range divided by the
 //                    window's own, parabolic peaks, octave cost, unvoiced strength; up to 15 candidates
 //   k_pitch_viterbi  per signal, one wave: the best candidate path under octave-jump and voicing costs; unvoiced frames 0
-// Formants, Burg's method as Praat's to_formant_burg defaults describe it (5 formants, ceiling 5500 Hz, 50 ms Gaussian):
-//   k_resample11k    windowed-sinc interpolation to 11 kHz, one output sample per thread
-//   k_formant_frames per frame, one wave: pre-emphasis from 50 Hz, Gaussian window, Burg order 10 in fp64, roots of the
-//                    predictor by Aberth's method plus Newton polishing, roots at 50 < f < 5450 Hz sorted into F1..F5
+// Formants, Burg's method as Praat's to_formant_burg describes it ([5] formants, ceiling [5500] Hz, 50 ms Gaussian):
+//   k_resample       windowed-sinc interpolation to R = 2 x ceiling [11 kHz], up or down, one output sample per thread
+//   k_formant_frames per frame, one wave: pre-emphasis from 50 Hz, Gaussian window of R / 20 samples [550], Burg of order
+//                    2 x formants [10] in fp64, roots of the predictor by Aberth's method plus Newton polishing, roots at
+//                    50 < f < R / 2 - 50 Hz sorted into F1..; a template on (window slots per lane, order), the default
+//                    settings' instantiation with its window and rate as compile-time constants
 // Every frame and signal is computed from its own samples in a fixed order, so a signal's tracks do not depend on the batch.
 // tests/tracker_ref.py restates the same algorithm in numpy.
 #include <math.h>
@@ -21,47 +26,66 @@
 
 namespace {
 
-constexpr int TR_FLOOR = 75, TR_PERIODS = 3, TR_MAX_CAND = 15;
-constexpr double TR_CEILING = 950.0, TR_SILENCE = 0.03, TR_VOICING = 0.45;
-constexpr double TR_OCTAVE = 0.01, TR_OCTAVE_JUMP = 0.35, TR_VUV = 0.14;
+constexpr int TR_PERIODS = 3, TR_MAX_CAND = 15;
 constexpr double TR_SILENT_PEAK = 1e-10;               // a signal whose peak deviation from its mean is below this is silence
-constexpr int TR_SR_MIN = 8000, TR_SR_MAX = 96000;     // the pitch frame (sr / 25 doubles) and its lags stay inside 48 KB of LDS
+constexpr int TR_SR_MIN = 8000, TR_SR_MAX = 96000;
+constexpr int TR_FLOOR_MIN = 20, TR_FLOOR_MAX = 600;   // W = 3 sr / floor: 14400 doubles at most, 40 at least
+constexpr double TR_CEILING_MAX = 20000.0;
+constexpr size_t TR_LDS_OPT_IN = 64 * 1024, TR_LDS_MAX = 160 * 1024;   // a pitch frame and its lags in LDS (k_pitch_frames)
 
-constexpr int FM_SR = 11000, FM_WIN = 550, FM_ORDER = 10, FM_N = 5, FM_PER_LANE = (FM_WIN + WAVE - 1) / WAVE;
+constexpr goofer_track_settings TR_DEFAULT = GOOFER_TRACK_SETTINGS_DEFAULT;
+// the default settings' formant geometry: k_formant_frames' instantiation with compile-time sizes
+constexpr int FM_SR = 2 * TR_DEFAULT.max_formant, FM_WIN = FM_SR / 20, FM_ORDER = 2 * TR_DEFAULT.n_formants;
+constexpr int FM_N = 5;                                // output columns
+constexpr int FM_MAX_FORMANT_MIN = 2500, FM_MAX_FORMANT_MAX = 8000, FM_WIN_MAX = 2 * FM_MAX_FORMANT_MAX / 20;
+constexpr int FM_SLOTS_MIN = (2 * FM_MAX_FORMANT_MIN / 20 + WAVE - 1) / WAVE, FM_SLOTS_MAX = (FM_WIN_MAX + WAVE - 1) / WAVE;
 constexpr double FM_PRE_HZ = 50.0, FM_SINC_ZEROS = 20.0;
 constexpr int FM_ABERTH_ITERS = 100;
 
 constexpr int TR_THREADS = 256;
 
+// the settings a call runs with: the handle's, or the defaults where a query form has no handle
+const goofer_track_settings &settings_of(const goofer_ctx *ctx) { return ctx ? ctx->track : TR_DEFAULT; }
+
 struct pitch_geom {
-    int W, min_lag, max_lag, lo, hi;                      // r[] is kept for lags lo..hi
+    int floor, W, min_lag, max_lag, lo, hi;               // r[] is kept for lags lo..hi
     double ceiling;
 };
 
-pitch_geom pitch_geometry(int sr)
+pitch_geom pitch_geometry(const goofer_track_settings &ts, int sr)
 {
     pitch_geom g;
-    g.W = TR_PERIODS * sr / TR_FLOOR;
-    g.ceiling = std::min(TR_CEILING, 0.5 * sr);
+    g.floor = ts.pitch_floor;
+    g.W = TR_PERIODS * sr / g.floor;
+    g.ceiling = std::min(ts.pitch_ceiling, 0.5 * sr);
     g.min_lag = (int)floor(sr / g.ceiling);
-    g.max_lag = (sr + TR_FLOOR - 1) / TR_FLOOR;
+    g.max_lag = (sr + g.floor - 1) / g.floor;
     g.lo = std::max(1, g.min_lag - 1);
     g.hi = std::min(g.max_lag + 1, g.W - 1);
     return g;
 }
 
-int64_t pitch_min_length(int sr) { return ((int64_t)TR_PERIODS * sr + TR_FLOOR - 1) / TR_FLOOR; }
+int64_t pitch_min_length(const goofer_track_settings &ts, int sr) { return ((int64_t)TR_PERIODS * sr + ts.pitch_floor - 1) / ts.pitch_floor; }
 
-int64_t pitch_frames(int64_t n, int sr, int hop)
+int64_t pitch_frames(const goofer_track_settings &ts, int64_t n, int sr, int hop)
 {
-    const int64_t d = (int64_t)TR_FLOOR * n - (int64_t)TR_PERIODS * sr;
-    return d < 0 ? 0 : d / ((int64_t)TR_FLOOR * hop) + 1;
+    const int64_t d = (int64_t)ts.pitch_floor * n - (int64_t)TR_PERIODS * sr;
+    return d < 0 ? 0 : d / ((int64_t)ts.pitch_floor * hop) + 1;
 }
 
-int64_t resampled_length(int64_t n, int sr) { return n * FM_SR / sr; }
+// the formant stage's rate R, its window and its Burg order
+struct formant_geom {
+    int fsr, win, order;
+};
+formant_geom formant_geometry(const goofer_track_settings &ts) { return {2 * ts.max_formant, 2 * ts.max_formant / 20, 2 * ts.n_formants}; }
 
-// formant frames of a signal of m samples at 11 kHz placed as a signal at sr with hop would place them
-int64_t formant_frames(int64_t m, int sr, int hop) { return m < FM_WIN ? 0 : (m - FM_WIN) * sr / ((int64_t)FM_SR * hop) + 1; }
+int64_t resampled_length(const formant_geom &fg, int64_t n, int sr) { return n * fg.fsr / sr; }
+
+// formant frames of a signal of m samples at R Hz placed as a signal at sr with hop would place them
+int64_t formant_frames(const formant_geom &fg, int64_t m, int sr, int hop)
+{
+    return m < fg.win ? 0 : (m - fg.win) * sr / ((int64_t)fg.fsr * hop) + 1;
+}
 
 // ---- device helpers ----------------------------------------------------------------------------------------------
 // numpy's max: a NaN operand wins (fmax returns the other one).  On non-NaN operands this is fmax, so every finite result
@@ -119,8 +143,9 @@ __global__ __launch_bounds__(TR_THREADS) void k_pitch_stats(const double *__rest
 // One frame per workgroup.  LDS: the windowed frame [W], the normalised autocorrelation for lags lo..hi, reductions.
 __global__ __launch_bounds__(TR_THREADS) void k_pitch_frames(const double *__restrict__ y, const int64_t *__restrict__ soff,
                                                              const int64_t *__restrict__ foff, int n_sig, int sr, int hop,
-                                                             pitch_geom g, const double *__restrict__ win,
-                                                             const double *__restrict__ rw, const double *__restrict__ stats,
+                                                             pitch_geom g, double silence, double voicing, double octave,
+                                                             const double *__restrict__ win, const double *__restrict__ rw,
+                                                             const double *__restrict__ stats,
                                                              double *__restrict__ cand_f, double *__restrict__ cand_s,
                                                              int *__restrict__ cand_n)
 {
@@ -153,9 +178,9 @@ __global__ __launch_bounds__(TR_THREADS) void k_pitch_frames(const double *__res
     pk = block_max_d(pk, red);
     const double r0 = block_sum_d(e, red);               // also orders the xw writes before the lag products
     const double gp = stats[2 * s + 1];
-    // a NaN peak (a non-finite sample) gives a NaN ratio, and fmax(0, NaN) = 0 as Python's max(0.0, nan): uv = TR_VOICING
+    // a NaN peak (a non-finite sample) gives a NaN ratio, and fmax(0, NaN) = 0 as Python's max(0.0, nan): uv = voicing
     const double ratio = !(gp <= TR_SILENT_PEAK) ? pk / gp : 0.0;
-    const double uv = TR_VOICING + fmax(0.0, 2.0 - ratio / (TR_SILENCE / (1.0 + TR_VOICING)));
+    const double uv = voicing + fmax(0.0, 2.0 - ratio / (silence / (1.0 + voicing)));
     double *cf = cand_f + f * TR_MAX_CAND, *cs = cand_s + f * TR_MAX_CAND;
     if (!(r0 > 0.0)) {
         if (threadIdx.x == 0) {
@@ -177,14 +202,14 @@ __global__ __launch_bounds__(TR_THREADS) void k_pitch_frames(const double *__res
     const int t0 = max(g.lo + 1, g.min_lag), t1 = min(g.max_lag, g.hi - 1);
     for (int t = t0; t <= t1; ++t) {
         const double rm1 = r[t - 1 - g.lo], rc = r[t - g.lo], rp1 = r[t + 1 - g.lo];
-        if (!(rc > 0.5 * TR_VOICING && rc > rm1 && rc >= rp1)) continue;
+        if (!(rc > 0.5 * voicing && rc > rm1 && rc >= rp1)) continue;
         const double dr = 0.5 * (rp1 - rm1), d2r = 2.0 * rc - rm1 - rp1;
         const double delta = d2r > 0.0 ? dr / d2r : 0.0;
         double rmax = rc + 0.5 * dr * delta;
         if (rmax > 1.0) rmax = 1.0 / rmax;
         const double fr = (double)sr / ((double)t + delta);
-        if (fr < (double)TR_FLOOR || fr > g.ceiling) continue;
-        const double st = rmax - TR_OCTAVE * log2((double)TR_FLOOR / fr);
+        if (fr < (double)g.floor || fr > g.ceiling) continue;
+        const double st = rmax - octave * log2((double)g.floor / fr);
         if (cnt < TR_MAX_CAND - 1) {
             kf[cnt] = fr;
             ks[cnt] = st;
@@ -211,18 +236,19 @@ __global__ __launch_bounds__(TR_THREADS) void k_pitch_frames(const double *__res
     cand_n[f] = cnt + 1;
 }
 
-__device__ __forceinline__ double pitch_transition(double fp, double fc, double tsc)
+__device__ __forceinline__ double pitch_transition(double fp, double fc, double tsc, double octave_jump, double vuv)
 {
     if (fp == 0.0 && fc == 0.0) return 0.0;
-    if (fp == 0.0 || fc == 0.0) return TR_VUV * tsc;
-    return TR_OCTAVE_JUMP * tsc * fabs(log2(fp / fc));
+    if (fp == 0.0 || fc == 0.0) return vuv * tsc;
+    return octave_jump * tsc * fabs(log2(fp / fc));
 }
 
 // One wave per signal: lane c holds candidate c of the current frame; back pointers go to global memory.  The first best
 // predecessor wins a tie, and the first best candidate of the last frame.
 __global__ __launch_bounds__(WAVE) void k_pitch_viterbi(const int64_t *__restrict__ foff, const double *__restrict__ cand_f,
                                                         const double *__restrict__ cand_s, const int *__restrict__ cand_n,
-                                                        double tsc, unsigned char *__restrict__ back, double *__restrict__ f0)
+                                                        double tsc, double octave_jump, double vuv,
+                                                        unsigned char *__restrict__ back, double *__restrict__ f0)
 {
     __shared__ double pf[TR_MAX_CAND], pd[TR_MAX_CAND];
     __shared__ int pn;
@@ -245,7 +271,7 @@ __global__ __launch_bounds__(WAVE) void k_pitch_viterbi(const int64_t *__restric
         if (c < cn) {
             fc = cand_f[fr * TR_MAX_CAND + c];
             for (int p = 0; p < pn; ++p) {
-                const double v = pd[p] - pitch_transition(pf[p], fc, tsc);
+                const double v = pd[p] - pitch_transition(pf[p], fc, tsc, octave_jump, vuv);
                 if (v > best) {
                     best = v;
                     arg = p;
@@ -274,19 +300,23 @@ __global__ __launch_bounds__(WAVE) void k_pitch_viterbi(const int64_t *__restric
 }
 
 // ---- formants ----------------------------------------------------------------------------------------------------
-// out[m] = sum_k y[k] h(k - p), p = m sr / 11000: a Hann-windowed sinc with its cut-off at the lower Nyquist
-__global__ __launch_bounds__(TR_THREADS) void k_resample11k(const double *__restrict__ y, const int64_t *__restrict__ soff,
-                                                            const int64_t *__restrict__ moff, int n_sig, int64_t m_total, int sr,
-                                                            double *__restrict__ out)
+// out[m] = sum_k y[k] h(k - p), p = m sr / fsr: a Hann-windowed sinc with its cut-off at the lower Nyquist, its half-width
+// 20 zero crossings of the lower rate (fsr > sr interpolates between the samples).  FSR > 0: the output rate as a compile-time
+// constant (the default settings; fsr_rt is not read), FSR = 0: fsr_rt.
+template <int FSR>
+__global__ __launch_bounds__(TR_THREADS) void k_resample(const double *__restrict__ y, const int64_t *__restrict__ soff,
+                                                         const int64_t *__restrict__ moff, int n_sig, int64_t m_total, int sr,
+                                                         int fsr_rt, double *__restrict__ out)
 {
+    const int fsr = FSR > 0 ? FSR : fsr_rt;
     const int64_t g = (int64_t)blockIdx.x * TR_THREADS + threadIdx.x;
     if (g >= m_total) return;
     const int s = csr_find(moff, n_sig, g);
     const int64_t m = g - moff[s], n = soff[s + 1] - soff[s];
     const double *x = y + soff[s];
-    const double fc = 0.5 * (double)min(sr, FM_SR) / (double)sr;
-    const double half = FM_SINC_ZEROS * fmax(1.0, (double)sr / (double)FM_SR);
-    const double p = (double)m * (double)sr / (double)FM_SR;
+    const double fc = 0.5 * (double)min(sr, fsr) / (double)sr;
+    const double half = FM_SINC_ZEROS * fmax(1.0, (double)sr / (double)fsr);
+    const double p = (double)m * (double)sr / (double)fsr;
     const int64_t k0 = max((int64_t)0, (int64_t)ceil(p - half)), k1 = min(n - 1, (int64_t)floor(p + half));
     double acc = 0.0;
     for (int64_t k = k0; k <= k1; ++k) {
@@ -323,25 +353,33 @@ __device__ __forceinline__ void poly_eval(const double *a, int m, cplx z, cplx &
 }
 
 // One wave per frame.  LDS per frame: the forward / backward prediction errors, the predictor, the roots.
+// PER_LANE: window samples per lane, ORDER: the Burg order (twice the formants looked for).  FSR > 0: the rate and, with it,
+// the window FSR / 20 and the pre-emphasis factor are compile-time constants and fsr_rt / win_rt / alpha_rt are not read (the
+// default settings); FSR = 0: any rate whose window fits PER_LANE slots, with alpha_rt = exp(-2 pi 50 / fsr_rt) from the host.
+template <int PER_LANE, int ORDER, int FSR>
 __global__ __launch_bounds__(WAVE) void k_formant_frames(const double *__restrict__ x11, const int64_t *__restrict__ moff,
                                                          const int64_t *__restrict__ foff, int n_sig, int sr, int hop,
+                                                         int fsr_rt, int win_rt, double alpha_rt,
                                                          const double *__restrict__ gwin, double *__restrict__ formants)
 {
-    __shared__ double fe[FM_WIN], be[FM_WIN];
-    __shared__ double a[FM_ORDER + 1];
-    __shared__ cplx z[FM_ORDER], w[FM_ORDER];
+    constexpr int WIN_CAP = FSR > 0 ? FSR / 20 : PER_LANE * WAVE, NF = ORDER / 2;
+    static_assert(WIN_CAP <= PER_LANE * WAVE && NF <= FM_N, "the window fits the lanes' slots, the formants the output row");
+    __shared__ double fe[WIN_CAP], be[WIN_CAP];
+    __shared__ double a[ORDER + 1];
+    __shared__ cplx z[ORDER], w[ORDER];
+    const int fsr = FSR > 0 ? FSR : fsr_rt, win = FSR > 0 ? FSR / 20 : win_rt;
     const int lane = threadIdx.x;
     const int64_t f = blockIdx.x;
     const int s = csr_find(foff, n_sig, f);
     const int64_t m = moff[s + 1] - moff[s], nf = foff[s + 1] - foff[s], i = f - foff[s];
-    const int64_t num = (m - FM_WIN) * sr + (2 * i - nf + 1) * (int64_t)hop * FM_SR;
+    const int64_t num = (m - win) * sr + (2 * i - nf + 1) * (int64_t)hop * fsr;
     int64_t st = (num + sr) / (2 * (int64_t)sr);          // num + sr >= 0 for every frame of the layout
-    st = min(max(st, (int64_t)0), m - FM_WIN);
+    st = min(max(st, (int64_t)0), m - win);
     const double *x = x11 + moff[s];
-    const double alpha = exp(-2.0 * M_PI * FM_PRE_HZ / FM_SR);
+    const double alpha = FSR > 0 ? exp(-2.0 * M_PI * FM_PRE_HZ / FSR) : alpha_rt;
 
     double pk = 0.0;
-    for (int j = lane; j < FM_WIN; j += WAVE) {
+    for (int j = lane; j < win; j += WAVE) {
         const int64_t q = st + j;
         const double v = (q > 0 ? x[q] - alpha * x[q - 1] : x[q]) * gwin[j];
         fe[j] = be[j] = v;
@@ -355,13 +393,13 @@ __global__ __launch_bounds__(WAVE) void k_formant_frames(const double *__restric
     if (lane == 0) a[0] = 1.0;
     wave_lds_sync();
     int order = 0;
-    for (int mo = 1; mo <= FM_ORDER; ++mo) {
+    for (int mo = 1; mo <= ORDER; ++mo) {
         double nu = 0.0, de = 0.0;
-        double fn[FM_PER_LANE], bn[FM_PER_LANE];
+        double fn[PER_LANE], bn[PER_LANE];
 #pragma unroll
-        for (int q = 0; q < FM_PER_LANE; ++q) {
+        for (int q = 0; q < PER_LANE; ++q) {
             const int j = mo + lane + q * WAVE;
-            if (j < FM_WIN) {
+            if (j < win) {
                 const double ff = fe[j], bb = be[j - 1];
                 nu += ff * bb;
                 de += ff * ff + bb * bb;
@@ -372,9 +410,9 @@ __global__ __launch_bounds__(WAVE) void k_formant_frames(const double *__restric
         if (!(de > 0.0)) break;
         const double k = -2.0 * nu / de;
 #pragma unroll
-        for (int q = 0; q < FM_PER_LANE; ++q) {
+        for (int q = 0; q < PER_LANE; ++q) {
             const int j = mo + lane + q * WAVE;
-            if (j < FM_WIN) {
+            if (j < win) {
                 const double ff = fe[j], bb = be[j - 1];
                 fn[q] = ff + k * bb;
                 bn[q] = bb + k * ff;
@@ -382,9 +420,9 @@ __global__ __launch_bounds__(WAVE) void k_formant_frames(const double *__restric
         }
         wave_lds_sync();                                  // all old values read before any is replaced
 #pragma unroll
-        for (int q = 0; q < FM_PER_LANE; ++q) {
+        for (int q = 0; q < PER_LANE; ++q) {
             const int j = mo + lane + q * WAVE;
-            if (j < FM_WIN) {
+            if (j < win) {
                 fe[j] = fn[q];
                 be[j] = bn[q];
             }
@@ -441,18 +479,18 @@ __global__ __launch_bounds__(WAVE) void k_formant_frames(const double *__restric
                 z[k].im -= c.im;
             }
         }
-    double fk[FM_N];
+    double fk[NF];
     int nk = 0;
     for (int k = 0; k < order; ++k) {
         if (!(z[k].im > 0.0)) continue;
-        const double fr = atan2(z[k].im, z[k].re) * FM_SR / (2.0 * M_PI);
-        if (!(fr > 50.0 && fr < 0.5 * FM_SR - 50.0)) continue;
-        int pos = nk < FM_N ? nk++ : FM_N;                // insertion into the FM_N lowest
+        const double fr = atan2(z[k].im, z[k].re) * fsr / (2.0 * M_PI);
+        if (!(fr > 50.0 && fr < 0.5 * fsr - 50.0)) continue;
+        int pos = nk < NF ? nk++ : NF;                    // insertion into the NF lowest
         while (pos > 0 && fk[pos - 1] > fr) {
-            if (pos < FM_N) fk[pos] = fk[pos - 1];
+            if (pos < NF) fk[pos] = fk[pos - 1];
             --pos;
         }
-        if (pos < FM_N) fk[pos] = fr;
+        if (pos < NF) fk[pos] = fr;
     }
     for (int k = 0; k < FM_N; ++k) out[k] = k < nk ? fk[k] : 0.0;
 }
@@ -504,21 +542,133 @@ path_scratch carve_path(arena &a, int n, int64_t F) { return {a.take<int64_t>(n 
 struct resample_scratch { int64_t *soff, *moff; };
 resample_scratch carve_resample(arena &a, int n) { return {a.take<int64_t>(n + 1), a.take<int64_t>(n + 1)}; }
 struct formant_scratch { int64_t *moff, *foff; double *gwin; };
-formant_scratch carve_formant_frames(arena &a, int n) { return {a.take<int64_t>(n + 1), a.take<int64_t>(n + 1), a.take<double>(FM_WIN)}; }
+formant_scratch carve_formant_frames(arena &a, int n, const formant_geom &fg)
+{
+    return {a.take<int64_t>(n + 1), a.take<int64_t>(n + 1), a.take<double>(fg.win)};
+}
+
+// dynamic LDS of k_pitch_frames: the windowed frame and the lags lo..hi
+size_t pitch_lds(const pitch_geom &g) { return 8 * (size_t)(g.W + g.hi - g.lo + 1); }
+constexpr size_t PITCH_STATIC_LDS = 8 * (4 + 2 * (TR_MAX_CAND - 1));   // red, kf, ks
+
+// a floor and rate whose frame does not fit a workgroup's LDS: refused by every form of the pitch calls
+int check_pitch_lds(goofer_ctx *ctx, const pitch_geom &g, int sr)
+{
+    const size_t need = pitch_lds(g) + PITCH_STATIC_LDS;
+    if (need > TR_LDS_MAX)
+        return goofer_fail(ctx, GOOFER_EINVAL, "tracker: pitch floor %d Hz at %d Hz needs %zu bytes of LDS per frame (window %d, lags %d..%d), "
+                           "more than %zu", g.floor, sr, need, g.W, g.lo, g.hi, TR_LDS_MAX);
+    return GOOFER_OK;
+}
+
+const char *settings_error(const goofer_track_settings &t, char *buf, size_t cap)
+{
+    auto cost_ok = [](double v) { return std::isfinite(v) && v >= 0.0; };
+    if (t.pitch_floor < TR_FLOOR_MIN || t.pitch_floor > TR_FLOOR_MAX)
+        snprintf(buf, cap, "pitch_floor %d outside [%d, %d]", t.pitch_floor, TR_FLOOR_MIN, TR_FLOOR_MAX);
+    else if (!(t.pitch_ceiling > (double)t.pitch_floor && t.pitch_ceiling <= TR_CEILING_MAX))
+        snprintf(buf, cap, "pitch_ceiling %g must be above the floor (%d) and at most %g", t.pitch_ceiling, t.pitch_floor, TR_CEILING_MAX);
+    else if (!cost_ok(t.silence_threshold))
+        snprintf(buf, cap, "silence_threshold %g must be finite and >= 0", t.silence_threshold);
+    else if (!(t.voicing_threshold > 0.0 && t.voicing_threshold < 1.0))
+        snprintf(buf, cap, "voicing_threshold %g outside (0, 1)", t.voicing_threshold);
+    else if (!cost_ok(t.octave_cost))
+        snprintf(buf, cap, "octave_cost %g must be finite and >= 0", t.octave_cost);
+    else if (!cost_ok(t.octave_jump_cost))
+        snprintf(buf, cap, "octave_jump_cost %g must be finite and >= 0", t.octave_jump_cost);
+    else if (!cost_ok(t.voiced_unvoiced_cost))
+        snprintf(buf, cap, "voiced_unvoiced_cost %g must be finite and >= 0", t.voiced_unvoiced_cost);
+    else if (t.max_formant < FM_MAX_FORMANT_MIN || t.max_formant > FM_MAX_FORMANT_MAX)
+        snprintf(buf, cap, "max_formant %d outside [%d, %d]", t.max_formant, FM_MAX_FORMANT_MIN, FM_MAX_FORMANT_MAX);
+    else if (t.n_formants < 3 || t.n_formants > FM_N)
+        snprintf(buf, cap, "n_formants %d is not 3, 4 or 5", t.n_formants);
+    else
+        return nullptr;
+    return buf;
+}
+
+// k_formant_frames by (slots per lane, order): the default geometry runs its compile-time instantiation
+using formant_kernel = void (*)(const double *, const int64_t *, const int64_t *, int, int, int, int, int, double, const double *, double *);
+template <int ORDER> formant_kernel formant_kernel_of_slots(int slots)
+{
+    switch (slots) {
+    case 4: return k_formant_frames<4, ORDER, 0>;
+    case 5: return k_formant_frames<5, ORDER, 0>;
+    case 6: return k_formant_frames<6, ORDER, 0>;
+    case 7: return k_formant_frames<7, ORDER, 0>;
+    case 8: return k_formant_frames<8, ORDER, 0>;
+    case 9: return k_formant_frames<9, ORDER, 0>;
+    case 10: return k_formant_frames<10, ORDER, 0>;
+    case 11: return k_formant_frames<11, ORDER, 0>;
+    case 12: return k_formant_frames<12, ORDER, 0>;
+    case 13: return k_formant_frames<13, ORDER, 0>;
+    }
+    return nullptr;
+}
+static_assert(FM_SLOTS_MIN == 4 && FM_SLOTS_MAX == 13, "formant_kernel_of_slots covers the admitted windows");
+
+formant_kernel formant_kernel_of(const formant_geom &fg)
+{
+    if (fg.fsr == FM_SR && fg.order == FM_ORDER) return k_formant_frames<(FM_WIN + WAVE - 1) / WAVE, FM_ORDER, FM_SR>;
+    const int slots = (fg.win + WAVE - 1) / WAVE;
+    switch (fg.order) {
+    case 6: return formant_kernel_of_slots<6>(slots);
+    case 8: return formant_kernel_of_slots<8>(slots);
+    case 10: return formant_kernel_of_slots<10>(slots);
+    }
+    return nullptr;
+}
 
 }  // namespace
 
 /* Exported: see include/goofer_hip.h */
+extern "C" void goofer_track_settings_default(goofer_track_settings *settings)
+{
+    if (settings) *settings = TR_DEFAULT;
+}
+
+extern "C" int goofer_track_configure(goofer_ctx *ctx, const goofer_track_settings *settings)
+{
+    if (!ctx) return GOOFER_EINVAL;
+    char why[160];
+    if (settings && settings_error(*settings, why, sizeof why)) return goofer_fail(ctx, GOOFER_EINVAL, "goofer_track_configure: %s", why);
+    ctx->track = settings ? *settings : TR_DEFAULT;
+    return GOOFER_OK;
+}
+
+extern "C" int goofer_track_layout(const goofer_track_settings *settings, const int64_t *sample_off, int n_signals, int sr, int hop,
+                                   int64_t *pitch_off, int64_t *x_off, int64_t *formant_off)
+{
+    const goofer_track_settings &ts = settings ? *settings : TR_DEFAULT;
+    char why[160];
+    if (settings_error(ts, why, sizeof why)) return GOOFER_EINVAL;
+    const formant_geom fg = formant_geometry(ts);
+    int rc;
+    if (pitch_off) {
+        if ((rc = check_batch(nullptr, sample_off, n_signals, sr, hop, pitch_min_length(ts, sr)))) return rc;
+        if ((rc = check_pitch_lds(nullptr, pitch_geometry(ts, sr), sr))) return rc;
+        fill_offsets(sample_off, n_signals, pitch_off, [&](int64_t n) { return pitch_frames(ts, n, sr, hop); });
+    }
+    if ((rc = check_batch(nullptr, sample_off, n_signals, sr, hop, 1))) return rc;
+    std::vector<int64_t> xo(n_signals + 1);
+    fill_offsets(sample_off, n_signals, xo.data(), [&](int64_t n) { return resampled_length(fg, n, sr); });
+    if (x_off) std::copy(xo.begin(), xo.end(), x_off);
+    if (formant_off) fill_offsets(xo.data(), n_signals, formant_off, [&](int64_t m) { return formant_frames(fg, m, sr, hop); });
+    return GOOFER_OK;
+}
+
 extern "C" int goofer_track_candidates(goofer_ctx *ctx, const double *y, const int64_t *sample_off, int n_signals, int sr, int hop,
                                        int64_t *frame_off, double *cand_f, double *cand_s, int32_t *cand_n, void *scratch,
                                        int64_t *scratch_bytes, void *stream)
 {
-    int rc = check_batch(ctx, sample_off, n_signals, sr, hop, pitch_min_length(sr));
+    const goofer_track_settings ts = settings_of(ctx);
+    int rc = check_batch(ctx, sample_off, n_signals, sr, hop, pitch_min_length(ts, sr));
     if (rc) return rc;
     if (!frame_off || !scratch_bytes) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: null frame_off / scratch_bytes");
-    fill_offsets(sample_off, n_signals, frame_off, [&](int64_t n) { return pitch_frames(n, sr, hop); });
+    const pitch_geom g = pitch_geometry(ts, sr);
+    if ((rc = check_pitch_lds(ctx, g, sr))) return rc;
+    fill_offsets(sample_off, n_signals, frame_off, [&](int64_t n) { return pitch_frames(ts, n, sr, hop); });
     const int64_t F = frame_off[n_signals];
-    const pitch_geom g = pitch_geometry(sr);
     if (scratch) {
         if (!ctx) return GOOFER_EINVAL;
         if (!y || !cand_f || !cand_s || !cand_n) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: null signal / candidates");
@@ -546,9 +696,11 @@ extern "C" int goofer_track_candidates(goofer_ctx *ctx, const double *y, const i
     hipLaunchKernelGGL(k_pitch_stats, dim3(n_signals), dim3(TR_THREADS), 0, st, y, s.soff, s.stats);
     LAUNCH_CHECK(ctx);
     if (F > 0) {
-        const size_t lds = 8 * (size_t)(g.W + g.hi - g.lo + 1);
-        hipLaunchKernelGGL(k_pitch_frames, dim3((unsigned)F), dim3(TR_THREADS), lds, st, y, s.soff, s.foff, n_signals, sr, hop, g, s.win,
-                           s.rw, s.stats, cand_f, cand_s, cand_n);
+        const size_t lds = pitch_lds(g);
+        // the opt-in is for dynamic LDS: what the kernel's static arrays leave of a workgroup's 160 KiB
+        if (lds > TR_LDS_OPT_IN && (rc = kernel_allow_max_lds(ctx, (const void *)k_pitch_frames, (int)(TR_LDS_MAX - PITCH_STATIC_LDS)))) return rc;
+        hipLaunchKernelGGL(k_pitch_frames, dim3((unsigned)F), dim3(TR_THREADS), lds, st, y, s.soff, s.foff, n_signals, sr, hop, g,
+                           ts.silence_threshold, ts.voicing_threshold, ts.octave_cost, s.win, s.rw, s.stats, cand_f, cand_s, cand_n);
         LAUNCH_CHECK(ctx);
     }
     return GOOFER_OK;
@@ -573,7 +725,9 @@ extern "C" int goofer_track_path(goofer_ctx *ctx, const double *cand_f, const do
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(ctx, hipMemcpyAsync(s.foff, frame_off, 8 * (size_t)(n_signals + 1), hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));                                            // frame_off is the caller's host array
-    hipLaunchKernelGGL(k_pitch_viterbi, dim3(n_signals), dim3(WAVE), 0, st, s.foff, cand_f, cand_s, cand_n, 0.01 * sr / hop, s.back, f0);
+    const goofer_track_settings &ts = settings_of(ctx);
+    hipLaunchKernelGGL(k_pitch_viterbi, dim3(n_signals), dim3(WAVE), 0, st, s.foff, cand_f, cand_s, cand_n, 0.01 * sr / hop,
+                       ts.octave_jump_cost, ts.voiced_unvoiced_cost, s.back, f0);
     LAUNCH_CHECK(ctx);
     return GOOFER_OK;
 }
@@ -582,10 +736,13 @@ extern "C" int goofer_track_pitch(goofer_ctx *ctx, const double *y, const int64_
                                   int64_t *frame_off, double *f0, void *scratch, int64_t *scratch_bytes, void *stream)
 {
     if (!scratch_bytes) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: null frame_off / scratch_bytes");
-    int rc = check_batch(ctx, sample_off, n_signals, sr, hop, pitch_min_length(sr));
+    const goofer_track_settings ts = settings_of(ctx);
+    int rc = check_batch(ctx, sample_off, n_signals, sr, hop, pitch_min_length(ts, sr));
     if (rc) return rc;
     if (!frame_off) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: null frame_off / scratch_bytes");
-    fill_offsets(sample_off, n_signals, frame_off, [&](int64_t n) { return pitch_frames(n, sr, hop); });
+    const pitch_geom g = pitch_geometry(ts, sr);
+    if ((rc = check_pitch_lds(ctx, g, sr))) return rc;
+    fill_offsets(sample_off, n_signals, frame_off, [&](int64_t n) { return pitch_frames(ts, n, sr, hop); });
     const int64_t F = frame_off[n_signals];
     if (scratch) {
         if (!ctx) return GOOFER_EINVAL;
@@ -599,7 +756,7 @@ extern "C" int goofer_track_pitch(goofer_ctx *ctx, const double *y, const int64_
         cand_s = a.take<double>(TR_MAX_CAND * (size_t)F);
         cand_n = a.take<int32_t>(F);
         at_c = a.used;
-        carve_candidates(a, n_signals, pitch_geometry(sr));
+        carve_candidates(a, n_signals, g);
         at_p = a.used;
         carve_path(a, n_signals, F);
         end = a.used;
@@ -617,7 +774,8 @@ extern "C" int goofer_track_resample(goofer_ctx *ctx, const double *y, const int
     int rc = check_batch(ctx, sample_off, n_signals, sr, 1, 1);
     if (rc) return rc;
     if (!x_off || !scratch_bytes) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: null x_off / scratch_bytes");
-    fill_offsets(sample_off, n_signals, x_off, [&](int64_t n) { return resampled_length(n, sr); });
+    const formant_geom fg = formant_geometry(settings_of(ctx));
+    fill_offsets(sample_off, n_signals, x_off, [&](int64_t n) { return resampled_length(fg, n, sr); });
     const int64_t M = x_off[n_signals];
     if (scratch) {
         if (!ctx) return GOOFER_EINVAL;
@@ -631,8 +789,8 @@ extern "C" int goofer_track_resample(goofer_ctx *ctx, const double *y, const int
     HIP_TRY(ctx, hipMemcpyAsync(s.soff, sample_off, 8 * (size_t)(n_signals + 1), hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemcpyAsync(s.moff, x_off, 8 * (size_t)(n_signals + 1), hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));                                            // the offsets are the caller's host arrays
-    hipLaunchKernelGGL(k_resample11k, dim3((unsigned)((M + TR_THREADS - 1) / TR_THREADS)), dim3(TR_THREADS), 0, st, y, s.soff, s.moff,
-                       n_signals, M, sr, x11);
+    hipLaunchKernelGGL(fg.fsr == FM_SR ? k_resample<FM_SR> : k_resample<0>, dim3((unsigned)((M + TR_THREADS - 1) / TR_THREADS)), dim3(TR_THREADS), 0, st, y, s.soff, s.moff,
+                       n_signals, M, sr, fg.fsr, x11);
     LAUNCH_CHECK(ctx);
     return GOOFER_OK;
 }
@@ -643,7 +801,8 @@ extern "C" int goofer_track_formant_frames(goofer_ctx *ctx, const double *x11, c
     int rc = check_offsets(ctx, x_off, n_signals, sr, hop, "x_off");
     if (rc) return rc;
     if (!frame_off || !scratch_bytes) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: null frame_off / scratch_bytes");
-    fill_offsets(x_off, n_signals, frame_off, [&](int64_t m) { return formant_frames(m, sr, hop); });
+    const formant_geom fg = formant_geometry(settings_of(ctx));
+    fill_offsets(x_off, n_signals, frame_off, [&](int64_t m) { return formant_frames(fg, m, sr, hop); });
     const int64_t F = frame_off[n_signals];
     if (scratch) {
         if (!ctx) return GOOFER_EINVAL;
@@ -651,22 +810,25 @@ extern "C" int goofer_track_formant_frames(goofer_ctx *ctx, const double *x11, c
         if (!x11 || !formants) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: null x11 / formants");
     }
     formant_scratch s;
-    if ((rc = caller_scratch(ctx, scratch, scratch_bytes, "tracker", [&](arena &a) { s = carve_formant_frames(a, n_signals); })) || !scratch)
+    if ((rc = caller_scratch(ctx, scratch, scratch_bytes, "tracker", [&](arena &a) { s = carve_formant_frames(a, n_signals, fg); })) || !scratch)
         return rc;
+    const formant_kernel kernel = formant_kernel_of(fg);
+    if (!kernel) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: no formant kernel for a window of %d samples and order %d", fg.win, fg.order);
     hipStream_t st = (hipStream_t)stream;
 
     // Praat's Gaussian-like window: exp(-48 (i - mid)^2 / (W + 1)^2), i = 1..W, lifted to zero at the ends
-    std::vector<double> gwin(FM_WIN);
+    std::vector<double> gwin(fg.win);
     const double e12 = exp(-12.0);
-    for (int j = 0; j < FM_WIN; ++j) {
-        const double d = (j + 1.0) - 0.5 * (FM_WIN + 1);
-        gwin[j] = (exp(-48.0 * d * d / ((FM_WIN + 1.0) * (FM_WIN + 1.0))) - e12) / (1.0 - e12);
+    for (int j = 0; j < fg.win; ++j) {
+        const double d = (j + 1.0) - 0.5 * (fg.win + 1);
+        gwin[j] = (exp(-48.0 * d * d / ((fg.win + 1.0) * (fg.win + 1.0))) - e12) / (1.0 - e12);
     }
     HIP_TRY(ctx, hipMemcpyAsync(s.moff, x_off, 8 * (size_t)(n_signals + 1), hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemcpyAsync(s.foff, frame_off, 8 * (size_t)(n_signals + 1), hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(s.gwin, gwin.data(), 8 * (size_t)FM_WIN, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(s.gwin, gwin.data(), 8 * (size_t)fg.win, hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));                                            // the host vectors go out of scope
-    hipLaunchKernelGGL(k_formant_frames, dim3((unsigned)F), dim3(WAVE), 0, st, x11, s.moff, s.foff, n_signals, sr, hop, s.gwin, formants);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)F), dim3(WAVE), 0, st, x11, s.moff, s.foff, n_signals, sr, hop, fg.fsr, fg.win,
+                       exp(-2.0 * M_PI * FM_PRE_HZ / fg.fsr), s.gwin, formants);
     LAUNCH_CHECK(ctx);
     return GOOFER_OK;
 }
@@ -677,9 +839,10 @@ extern "C" int goofer_track_formants(goofer_ctx *ctx, const double *y, const int
     int rc = check_batch(ctx, sample_off, n_signals, sr, hop, 1);
     if (rc) return rc;
     if (!frame_off || !scratch_bytes) return goofer_fail(ctx, GOOFER_EINVAL, "tracker: null frame_off / scratch_bytes");
+    const formant_geom fg = formant_geometry(settings_of(ctx));
     std::vector<int64_t> x_off(n_signals + 1);
-    fill_offsets(sample_off, n_signals, x_off.data(), [&](int64_t n) { return resampled_length(n, sr); });
-    fill_offsets(x_off.data(), n_signals, frame_off, [&](int64_t m) { return formant_frames(m, sr, hop); });
+    fill_offsets(sample_off, n_signals, x_off.data(), [&](int64_t n) { return resampled_length(fg, n, sr); });
+    fill_offsets(x_off.data(), n_signals, frame_off, [&](int64_t m) { return formant_frames(fg, m, sr, hop); });
     const int64_t F = frame_off[n_signals], M = x_off[n_signals];
     if (scratch) {
         if (!ctx) return GOOFER_EINVAL;
@@ -693,7 +856,7 @@ extern "C" int goofer_track_formants(goofer_ctx *ctx, const double *y, const int
         at_r = a.used;
         carve_resample(a, n_signals);
         at_f = a.used;
-        carve_formant_frames(a, n_signals);
+        carve_formant_frames(a, n_signals, fg);
         end = a.used;
     };
     if ((rc = caller_scratch(ctx, scratch, scratch_bytes, "tracker", carve)) || !scratch) return rc;

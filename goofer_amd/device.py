@@ -78,6 +78,7 @@ class Context:
             raise GooferError(f"goofer_create failed ({rc})")
         self.h = h
         self.geom = None
+        self._track_settings = None                        # the tracker settings last applied (None: the defaults)
 
     def close(self):
         self._stem_scratch = None
@@ -467,12 +468,22 @@ class Context:
         return out
 
     # -- f0 / formant tracks of the cold-cache analysis (csrc/tracker.hip) --------------------------------------
-    def track(self, y, lengths, sr: int, hop: int):
+    def _track_configure(self, settings):
+        """The handle's tracker settings for the call that follows (goofer_track_configure): ``settings`` a
+        ``trackers.TrackerSettings`` or None, the defaults.  The handle is told only when they differ from the last applied."""
+        key = _track_key(settings)
+        if key != self._track_settings:
+            self._check(self.lib.goofer_track_configure(self.h, None if key is None else C.byref(_lib.TrackSettings(*key))))
+            self._track_settings = key
+
+    def track(self, y, lengths, sr: int, hop: int, settings=None):
         """Pitch and formant tracks of a ragged batch of signals: ``y`` a contiguous fp64 device tensor holding
-        ``lengths`` samples per signal.  Returns (f0 [frames] fp64, f0 frame_off, formants [frames', 5] fp64, formant
-        frame_off), the offsets as host int64 arrays.  Each call's scratch is a tensor of this method, released in
-        stream order when it returns."""
+        ``lengths`` samples per signal, ``settings`` a ``trackers.TrackerSettings`` (None: the defaults, whatever ran on
+        this context before; the same for every track_* method).  Returns (f0 [frames] fp64, f0 frame_off, formants
+        [frames', 5] fp64, formant frame_off), the offsets as host int64 arrays.  Each call's scratch is a tensor of this
+        method, released in stream order when it returns."""
         s_off = self._track_input(y, lengths, "track")
+        self._track_configure(settings)
         out = []
         for fn, width in ((self.lib.goofer_track_pitch, 1), (self.lib.goofer_track_formants, 5)):
             f_off = np.zeros(len(s_off), dtype=np.int64)
@@ -491,10 +502,11 @@ class Context:
             raise ValueError(f"{what}: the lengths sum to {sum(lengths)}, the signal has {y.numel()} samples")
         return self.offsets(lengths)
 
-    def track_candidates(self, y, lengths, sr: int, hop: int):
+    def track_candidates(self, y, lengths, sr: int, hop: int, settings=None):
         """The pitch candidates of every frame: (cand_f [F, 15], cand_s [F, 15] fp64, cand_n [F] int32, frame_off host int64).
         Slot 0 is the unvoiced candidate; the slots from cand_n on are 0."""
         s_off = self._track_input(y, lengths, "track_candidates")
+        self._track_configure(settings)
         f_off = np.zeros(len(s_off), dtype=np.int64)
         cand = lambda: torch.zeros((int(f_off[-1]), 15), dtype=torch.float64, device=self.device)   # noqa: E731
         count = lambda: torch.zeros(int(f_off[-1]), dtype=torch.int32, device=self.device)        # noqa: E731
@@ -502,8 +514,9 @@ class Context:
                                              (_ptr(y), _host(s_off), len(s_off) - 1, int(sr), int(hop), _host(f_off)), (cand, cand, count))
         return cf, cs, cn, f_off
 
-    def track_path(self, cand_f, cand_s, cand_n, frame_off, sr: int, hop: int):
+    def track_path(self, cand_f, cand_s, cand_n, frame_off, sr: int, hop: int, settings=None):
         """The Viterbi f0 [frame_off[-1]] fp64 of candidates in track_candidates' layout (contiguous device tensors)."""
+        self._track_configure(settings)
         frame_off = np.ascontiguousarray(frame_off, dtype=np.int64)
         F = int(frame_off[-1])
         for t, dt in ((cand_f, torch.float64), (cand_s, torch.float64), (cand_n, torch.int32)):
@@ -515,18 +528,22 @@ class Context:
                                      [lambda: torch.empty(F, dtype=torch.float64, device=self.device)])
         return f0
 
-    def track_resample(self, y, lengths, sr: int):
-        """The 11 kHz signals the formant stage analyses: (x11 fp64 device tensor, x_off host int64)."""
+    def track_resample(self, y, lengths, sr: int, settings=None):
+        """The signals the formant stage analyses, at 2 x max_formant (11 kHz by default): (x11 fp64 device tensor, x_off
+        host int64)."""
         s_off = self._track_input(y, lengths, "track_resample")
+        self._track_configure(settings)
         x_off = np.zeros(len(s_off), dtype=np.int64)
         [x11], _ = self._scratch_call(self.lib.goofer_track_resample, (_ptr(y), _host(s_off), len(s_off) - 1, int(sr), _host(x_off)),
                                       [lambda: torch.empty(int(x_off[-1]), dtype=torch.float64, device=self.device)])
         return x11, x_off
 
-    def track_formant_frames(self, x11, lengths11, sr: int, hop: int):
-        """Formants [F, 5] fp64 of 11 kHz signals (``lengths11`` samples each) placed as a signal at ``sr`` with ``hop``
-        would place them, and their frame_off (host int64)."""
+    def track_formant_frames(self, x11, lengths11, sr: int, hop: int, settings=None):
+        """Formants [F, 5] fp64 of signals at 2 x max_formant (11 kHz by default; ``lengths11`` samples each) placed as a
+        signal at ``sr`` with ``hop`` would place them, and their frame_off (host int64).  The columns from n_formants on
+        are 0."""
         x_off = self._track_input(x11, lengths11, "track_formant_frames")
+        self._track_configure(settings)
         f_off = np.zeros(len(x_off), dtype=np.int64)
         [forms], _ = self._scratch_call(self.lib.goofer_track_formant_frames,
                                         (_ptr(x11), _host(x_off), len(x_off) - 1, int(sr), int(hop), _host(f_off)),
@@ -881,22 +898,28 @@ class Context:
         return out
 
 
-def track_frame_offsets(lengths, sr: int, hop: int):
-    """(f0 frame_off, formant frame_off) the tracker gives signals of these lengths, from the library's own layout; needs
-    no device."""
+def _track_key(settings):
+    """A ``trackers.TrackerSettings`` (or anything with goofer_track_settings' fields) as the struct's values in order;
+    None stays None, the defaults."""
+    if settings is None:
+        return None
+    return tuple(getattr(settings, name) for name, _ in _lib.TrackSettings._fields_)
+
+
+def track_frame_offsets(lengths, sr: int, hop: int, settings=None):
+    """(f0 frame_off, formant frame_off) the tracker gives signals of these lengths under ``settings`` (a
+    ``trackers.TrackerSettings``; None: the defaults), from the library's own layout (goofer_track_layout); needs no
+    device."""
     lib = _lib.load()
     s_off = np.zeros(len(lengths) + 1, dtype=np.int64)
     np.cumsum(np.asarray(lengths, dtype=np.int64), out=s_off[1:])
-
-    def check(rc):
-        if rc != 0:
-            raise GooferError(f"libgoofer_hip error {rc}: the tracker refuses this batch (sample rate, hop or a signal length)")
-    out = []
-    for fn in (lib.goofer_track_pitch, lib.goofer_track_formants):
-        f_off = np.zeros(len(s_off), dtype=np.int64)
-        Context._scratch_call(None, fn, (None, _host(s_off), len(s_off) - 1, int(sr), int(hop), _host(f_off), None), check=check)
-        out.append(f_off)
-    return tuple(out)
+    key = _track_key(settings)
+    p_off, f_off = np.zeros(len(s_off), dtype=np.int64), np.zeros(len(s_off), dtype=np.int64)
+    rc = lib.goofer_track_layout(None if key is None else C.byref(_lib.TrackSettings(*key)), _host(s_off), len(s_off) - 1, int(sr),
+                                 int(hop), _host(p_off), None, _host(f_off))
+    if rc != 0:
+        raise GooferError(f"libgoofer_hip error {rc}: the tracker refuses this batch (settings, sample rate, hop or a signal length)")
+    return p_off, f_off
 
 
 def _ratios(subharm):

@@ -1,6 +1,6 @@
 """Wav-to-wav resynthesis from the command line: GOOFER.py's script mode (GOOFER.py:1222-1330) batched over many files.
 
-    python -m goofer_amd.resynth [--out DIR] [--n-fft 1024] [--hop N] [--tracker native|praat|module:fn]
+    python -m goofer_amd.resynth [--out DIR] [--n-fft 1024] [--hop N] [--tracker native|native:key=value,...|praat|module:fn]
            [--pitch R] [--formant R] [--stretch R] [--F1 R ... --F4 R] [--set key=value ...]
            [--variant "key=value,key=value" ...] [--stems] [--seed S] [--noise-seed N] INPUT...
 
@@ -43,7 +43,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--out", default=None, help="output folder (default: next to each input)")
     ap.add_argument("--n-fft", type=int, default=1024)
     ap.add_argument("--hop", type=int, default=None, help="hop length (default n_fft // 4)")
-    ap.add_argument("--tracker", default=None, help="native, praat or module:function (default: $GOOFER_TRACKER, else Praat)")
+    ap.add_argument("--tracker", default=None, help="native, native:key=value,... (trackers.TrackerSettings, e.g. native:pitch_floor=40,max_formant=5000), praat or "
+                                                    "module:function (default: $GOOFER_TRACKER, else Praat)")
     for flag, key in _SHORTCUTS:
         ap.add_argument(f"--{flag}", type=float, default=None, dest=key, help=f"synthesize's {key}")
     ap.add_argument("--set", action="append", default=[], metavar="KEY=VALUE", help="any synthesize keyword (repeatable)")

@@ -9,7 +9,8 @@ This module is the plug for that half and the host logic the reference wraps aro
 * a *tracker* is ``fn(y, sr, hop_length, n_frames) -> (f0_track [frames'], {1..5: formant track [n_frames]})``;
   ``praat_tracker`` makes the reference's very calls when ``parselmouth`` is importable (GOOFER.py:341-353, 768-792);
   ``native_tracker`` computes the same tracks on the GPU from the published methods without Praat (``tracker="native"``
-  or ``GOOFER_TRACKER=native``; its numbers are its own, not Praat's);
+  or ``GOOFER_TRACKER=native``; its numbers are its own, not Praat's); ``TrackerSettings`` are its pitch range, costs and
+  formant ceiling, ``native(settings)`` a tracker bound to them (``"native:pitch_floor=40,max_formant=5000"`` by name);
   ``get()`` resolves the tracker to use (argument, ``GOOFER_TRACKER=name`` or ``module:function``, Praat when present);
 * ``fix_f0_gaps`` (GOOFER.py:415-435) and ``per_sample_f0`` (GOOFER.py:957-966) — pinned by ``tests/golden/cold_cache.npz``,
   which ``make_golden.py`` generates by running the reference's own ``extract_features`` over a fake ``parselmouth``;
@@ -20,9 +21,11 @@ Nothing here re-implements Praat: the native tracker follows the published metho
 """
 from __future__ import annotations
 
+import dataclasses
 import importlib
 import importlib.util
 import logging
+import math
 import os
 from pathlib import Path
 
@@ -64,41 +67,137 @@ def praat_tracker(y, sr, hop_length, n_frames):
 NATIVE_SR_RANGE = (8000, 96000)
 
 
-def native_min_length(sr) -> int:
-    """Samples in one pitch window of the native tracker: 3 periods of 75 Hz (40 ms), rounded up."""
-    return -(-3 * int(sr) // 75)
+@dataclasses.dataclass(frozen=True)
+class TrackerSettings:
+    """The native tracker's settings (``goofer_track_settings`` of include/goofer_hip.h; the defaults are what the reference
+    hands to Praat): the pitch range in Hz (``pitch_floor`` an integer in [20, 600] — the pitch window is three of its
+    periods —, ``pitch_ceiling`` above it and at most 20000; a call uses min(ceiling, sr / 2)), Boersma's thresholds and
+    costs (finite and >= 0, the voicing threshold in (0, 1)), and the formant stage's ceiling ``max_formant`` (an integer in
+    [2500, 8000] Hz; Praat's advice is 5000 for a male voice, 5500 for a female one) and count ``n_formants`` (3, 4 or 5).
+    A value outside its range raises ValueError naming the field, as ``goofer_track_configure`` refuses it."""
+    pitch_floor: int = 75
+    pitch_ceiling: float = 950.0
+    silence_threshold: float = 0.03
+    voicing_threshold: float = 0.45
+    octave_cost: float = 0.01
+    octave_jump_cost: float = 0.35
+    voiced_unvoiced_cost: float = 0.14
+    max_formant: int = 5500
+    n_formants: int = 5
+
+    def __post_init__(self):
+        for f in dataclasses.fields(self):
+            v = getattr(self, f.name)
+            try:
+                if isinstance(v, bool):
+                    raise TypeError
+                x = float(v)
+            except (TypeError, ValueError):
+                raise ValueError(f"TrackerSettings: {f.name} must be a number (got {v!r})") from None
+            if f.type in (int, "int"):
+                if not (math.isfinite(x) and x == int(x)):
+                    raise ValueError(f"TrackerSettings: {f.name} must be an integer (got {v!r})")
+                x = int(x)
+            object.__setattr__(self, f.name, x)
+        if not 20 <= self.pitch_floor <= 600:
+            raise ValueError(f"TrackerSettings: pitch_floor {self.pitch_floor} outside [20, 600]")
+        if not self.pitch_floor < self.pitch_ceiling <= 20000.0:
+            raise ValueError(f"TrackerSettings: pitch_ceiling {self.pitch_ceiling:g} must be above the floor ({self.pitch_floor}) and at "
+                             "most 20000")
+        for name in ("silence_threshold", "octave_cost", "octave_jump_cost", "voiced_unvoiced_cost"):
+            if not (math.isfinite(getattr(self, name)) and getattr(self, name) >= 0.0):
+                raise ValueError(f"TrackerSettings: {name} {getattr(self, name):g} must be finite and >= 0")
+        if not 0.0 < self.voicing_threshold < 1.0:
+            raise ValueError(f"TrackerSettings: voicing_threshold {self.voicing_threshold:g} outside (0, 1)")
+        if not 2500 <= self.max_formant <= 8000:
+            raise ValueError(f"TrackerSettings: max_formant {self.max_formant} outside [2500, 8000]")
+        if self.n_formants not in (3, 4, 5):
+            raise ValueError(f"TrackerSettings: n_formants {self.n_formants} is not 3, 4 or 5")
+
+    @classmethod
+    def parse(cls, text: str) -> "TrackerSettings":
+        """``"key=value,key=value"`` (what follows ``native:`` in a tracker name) -> settings; an unknown key or a value that
+        is no number raises ValueError."""
+        names = {f.name for f in dataclasses.fields(cls)}
+        kw = {}
+        for item in text.split(","):
+            key, eq, value = (p.strip() for p in item.partition("="))
+            if not eq or key not in names or key in kw:
+                raise ValueError(f"tracker settings {text!r}: {item.strip()!r} is not one key=value with a key of {sorted(names)}")
+            try:
+                kw[key] = float(value)
+            except ValueError:
+                raise ValueError(f"tracker settings {text!r}: {key}={value!r} is not a number") from None
+        return cls(**kw)
 
 
-def native_refusal(n_samples, sr):
+def native_min_length(sr, settings=None) -> int:
+    """Samples in one pitch window of the native tracker: 3 periods of the pitch floor (40 ms at 75 Hz), rounded up."""
+    return -(-3 * int(sr) // (settings or TrackerSettings()).pitch_floor)
+
+
+def native_refusal(n_samples, sr, settings=None):
     """The ValueError native_tracker raises for a mono signal of this length and rate, or None when it takes the signal."""
     sr = int(sr)
     if not NATIVE_SR_RANGE[0] <= sr <= NATIVE_SR_RANGE[1]:
         return ValueError(f"native_tracker: sample rate {sr} Hz is outside {NATIVE_SR_RANGE[0]}..{NATIVE_SR_RANGE[1]} Hz")
-    if n_samples < native_min_length(sr):
+    if n_samples < native_min_length(sr, settings):
+        floor = (settings or TrackerSettings()).pitch_floor
         return ValueError(f"native_tracker: {n_samples} samples is shorter than one pitch window; at {sr} Hz the minimum length "
-                          f"is {native_min_length(sr)} samples (40 ms)")
+                          f"is {native_min_length(sr, settings)} samples ({3000 / floor:g} ms)")
     return None
 
 
-def native_tracker(y, sr, hop_length, n_frames, ctx=None):
+def native_tracker(y, sr, hop_length, n_frames, ctx=None, settings=None):
     """``praat_tracker``'s contract on the GPU (csrc/tracker.hip): f0 by Boersma's autocorrelation method with a Viterbi
     path and Praat's AC settings as the reference passes them (floor 75 Hz, ceiling 950 Hz, time step hop / sr), formants
-    by Burg's method with ``to_formant_burg``'s defaults (5 formants up to 5500 Hz, 50 ms Gaussian, pre-emphasis from 50 Hz).
-    Written from the published methods: its tracks are not Praat's numbers (parity unpinned), and the f0 track has its own
-    frame layout like Praat's does.  Raises ValueError for a signal shorter than one pitch window."""
+    by Burg's method with ``to_formant_burg``'s defaults (5 formants up to 5500 Hz, 50 ms Gaussian, pre-emphasis from 50 Hz);
+    ``settings`` (a ``TrackerSettings``) replaces those values.  Written from the published methods: its tracks are not
+    Praat's numbers (parity unpinned), and the f0 track has its own frame layout like Praat's does.  Raises ValueError for a
+    signal shorter than one pitch window."""
     import torch
     from .device import default_context
     y = np.asarray(y, dtype=np.float64)
     if y.ndim != 1:
         raise ValueError("native_tracker expects a mono signal")
     sr = int(sr)
-    refused = native_refusal(len(y), sr)
+    refused = native_refusal(len(y), sr, settings)
     if refused is not None:
         raise refused
     c = ctx or default_context()
-    f0, _, forms, _ = c.track(torch.as_tensor(y).to(c.device), [len(y)], sr, int(hop_length))
+    f0, _, forms, _ = c.track(torch.as_tensor(y).to(c.device), [len(y)], sr, int(hop_length), settings=settings)
     f0, forms = f0.cpu().numpy(), forms.cpu().numpy()
     return f0, fit_formants({k: forms[:, k - 1].tolist() for k in range(1, 6)}, n_frames)
+
+
+class NativeTracker:
+    """``native_tracker`` bound to settings (``native(settings)``): a tracker like any other, which the batched paths
+    recognise (``native_settings``) and serve with one ``Context.track`` call per pass."""
+
+    def __init__(self, settings: TrackerSettings):
+        if not isinstance(settings, TrackerSettings):
+            raise TypeError("native() expects a TrackerSettings")
+        self.settings = settings
+
+    def __call__(self, y, sr, hop_length, n_frames, ctx=None):
+        return native_tracker(y, sr, hop_length, n_frames, ctx=ctx, settings=self.settings)
+
+    def __repr__(self):
+        return f"native({self.settings!r})"
+
+
+def native(settings=None):
+    """The native tracker bound to ``settings`` (None: ``native_tracker`` itself, the defaults)."""
+    return native_tracker if settings is None else NativeTracker(settings)
+
+
+def native_settings(track_fn):
+    """(True, its settings or None) when ``track_fn`` is the native tracker, bound or not; else (False, None)."""
+    if track_fn is native_tracker:
+        return True, None
+    if isinstance(track_fn, NativeTracker):
+        return True, track_fn.settings
+    return False, None
 
 
 _REGISTRY = {"praat": praat_tracker, "native": native_tracker}
@@ -110,14 +209,18 @@ def register(name: str, fn) -> None:
 
 def get(tracker=None):
     """The tracker to use: the argument if it is callable; else the name given (or ``$GOOFER_TRACKER``) looked up in the
-    registry ("praat", "native") or imported as ``module:function``; else Praat when parselmouth is importable.  Raises
-    TrackerUnavailable.  The native tracker is used only when named."""
+    registry ("praat", "native"), read as ``native:key=value,...`` (the native tracker bound to ``TrackerSettings``, for
+    example ``native:pitch_floor=40,pitch_ceiling=1200,max_formant=5000``; a bad key or value is a ValueError) or imported
+    as ``module:function``; else Praat when parselmouth is importable.  Raises TrackerUnavailable.  The native tracker is
+    used only when named."""
     if callable(tracker):
         return tracker
     name = tracker or os.environ.get("GOOFER_TRACKER")
     if name:
         if name in _REGISTRY:
             return _REGISTRY[name]
+        if name.startswith("native:"):
+            return native(TrackerSettings.parse(name[len("native:"):]))
         if ":" in name:
             mod, attr = name.split(":", 1)
             return getattr(importlib.import_module(mod), attr)
@@ -419,21 +522,24 @@ def analyse_device(signals, sr, n_fft=1024, hop_length=256, f0_min=75, f0_merge_
     sample, fp64: device views, or host arrays for a one-frame track), "formants" (host dict, fitted to T frames), "T", and
     "pass" / "slot" / "f0_slot" (the shared pass buffers and the signal's place in them).  The envelope and knots of every
     signal come from one ``Context.envelope_knots`` call; with the native tracker one ``Context.track`` call follows on the
-    same stream, and its f0 tracks never leave the device.  Any other tracker is called per signal, in order, on the host and
+    same stream (with a bound native tracker's settings), and its f0 tracks never leave the device.  Any other tracker is called per signal, in order, on the host and
     its tracks uploaded.  Per-sample f0 and voicing come from one ``Context.per_sample_f0`` launch (``per_sample_f0_batch``).
-    Only the formant tracks (and with ``want_knots`` nothing else) are waited for."""
+    Only the formant tracks (and with ``want_knots`` nothing else) are waited for.  A bound native tracker whose pitch floor
+    lies below ``f0_min`` lowers ``f0_min`` to its floor, so that what it tracks down there counts as voiced."""
     import torch
     from .device import default_context
     track_fn = get(tracker)
-    native = track_fn is native_tracker
+    native, settings = native_settings(track_fn)
     sr, hop = int(sr), int(hop_length)
+    if settings is not None:
+        f0_min = min(f0_min, settings.pitch_floor)               # voiced is f0 > f0_min: a floor below it would be tracked, then masked
     out = [None] * len(signals)
     ys, live = [], []
     for i, y in enumerate(signals):
         y = np.asarray(y)
         refused = (ValueError("analyse_batch: expected a mono signal") if y.ndim != 1 else
                    ValueError("analyse_batch: empty signal") if y.size == 0 else
-                   native_refusal(y.size, sr) if native else None)
+                   native_refusal(y.size, sr, settings) if native else None)
         if refused is not None:
             out[i] = refused
         else:
@@ -448,7 +554,7 @@ def analyse_device(signals, sr, n_fft=1024, hop_length=256, f0_min=75, f0_merge_
     tracks, formants = [None] * len(ys), [None] * len(ys)
     if native:
         y64 = torch.from_numpy(np.concatenate([np.asarray(y, dtype=np.float64) for y in ys])).to(c.device)
-        f0, p_off, forms, m_off = c.track(y64, lengths, sr, hop)
+        f0, p_off, forms, m_off = c.track(y64, lengths, sr, hop, settings=settings)
         forms = forms.cpu().numpy()
         for j in range(len(ys)):
             T = int(f_off[j + 1] - f_off[j])
@@ -509,7 +615,7 @@ def ensure_features_batch(paths, n_fft=1024, hop_length=256, tracker=None, ctx=N
             todo.append(p)
     if todo:
         track_fn = get(tracker)
-        native = track_fn is native_tracker
+        native, settings = native_settings(track_fn)
         timings = {} if timings is None else timings
         with ThreadPoolExecutor(max_workers=max(1, int(workers))) as pool:
             t0 = time.perf_counter()
@@ -518,7 +624,7 @@ def ensure_features_batch(paths, n_fft=1024, hop_length=256, tracker=None, ctx=N
                 if isinstance(r, BaseException):
                     out[p] = r
                     continue
-                refused = native_refusal(len(r[0]), r[1]) if native else None
+                refused = native_refusal(len(r[0]), r[1], settings) if native else None
                 if refused is not None:
                     out[p] = refused
                 else:

@@ -331,19 +331,52 @@ int goofer_envelope_knots_batch(goofer_ctx *ctx, const float *y, const int64_t *
                                 int64_t *scratch_bytes, void *stream);
 
 /* ---- f0 and formant tracks of the cold-cache analysis (goofer_amd/csrc/tracker.hip) -------------------------------
- * A ragged batch of fp64 signals y (device) at one sample rate sr in [8000, 96000]; sample_off[n_signals+1] and
- * frame_off[n_signals+1] are HOST arrays, frame_off is written by the call; caller scratch as above.
+ * The tracker's settings belong to the handle, as goofer_pulse_model's do: goofer_create starts at the defaults, and
+ * goofer_track_configure replaces them for every goofer_track_* call that follows on the handle, their query forms
+ * included (a query form with ctx NULL reads the defaults). */
+typedef struct goofer_track_settings {
+    int pitch_floor;             /* Hz, integer in [20, 600]; the pitch window is 3 / pitch_floor seconds             75   */
+    double pitch_ceiling;        /* Hz, above the floor and at most 20000; a call uses min(pitch_ceiling, sr / 2)     950  */
+    double silence_threshold;    /* finite, >= 0                                                                      0.03 */
+    double voicing_threshold;    /* in (0, 1)                                                                         0.45 */
+    double octave_cost;          /* finite, >= 0                                                                      0.01 */
+    double octave_jump_cost;     /* finite, >= 0                                                                      0.35 */
+    double voiced_unvoiced_cost; /* finite, >= 0                                                                      0.14 */
+    int max_formant;             /* Hz, integer in [2500, 8000]; the formant stage resamples to 2 max_formant         5500 */
+    int n_formants;              /* 3, 4 or 5; Burg order 2 n_formants                                                5    */
+} goofer_track_settings;
+#define GOOFER_TRACK_SETTINGS_DEFAULT {75, 950.0, 0.03, 0.45, 0.01, 0.35, 0.14, 5500, 5}
+
+/* The default settings (the values above). */
+void goofer_track_settings_default(goofer_track_settings *settings);
+/* The handle's tracker settings from now on; NULL: the defaults.  A value outside its range above: GOOFER_EINVAL, a message
+ * that names the field, and the handle keeps the settings it had. */
+int goofer_track_configure(goofer_ctx *ctx, const goofer_track_settings *settings);
+/* The frame layout the tracker gives a batch under `settings` (NULL: the defaults), without a handle or a device:
+ * pitch_off, x_off and formant_off [n_signals+1] (HOST, any may be NULL) as goofer_track_pitch, goofer_track_resample and
+ * goofer_track_formants write them, and their refusals (GOOFER_EINVAL). */
+int goofer_track_layout(const goofer_track_settings *settings, const int64_t *sample_off, int n_signals, int sr, int hop,
+                        int64_t *pitch_off, int64_t *x_off, int64_t *formant_off);
+
+/* A ragged batch of fp64 signals y (device) at one sample rate sr in [8000, 96000]; sample_off[n_signals+1] and
+ * frame_off[n_signals+1] are HOST arrays, frame_off is written by the call; caller scratch as above.  With the handle's
+ * settings (defaults in brackets), all in the integer arithmetic written here:
  *
- * goofer_track_pitch: Boersma's autocorrelation method with a Viterbi path, floor 75 Hz, ceiling min(950, sr/2) Hz,
- * time step hop / sr, window 3 / 75 s (Hann).  Frames: floor((n - 3 sr / 75) / hop) + 1 per signal, centred in it.
- * f0 [frame_off[n]] in Hz, 0 where unvoiced.  Every signal needs ceil(3 sr / 75) samples at least (GOOFER_EINVAL).
- * goofer_track_formants: Burg LPC of order 10 on the signal resampled to 11 kHz and pre-emphasised from 50 Hz, 50 ms
- * Gaussian window, same time step; frames: floor((m - 550) sr / (11000 hop)) + 1 for m = n * 11000 / sr resampled samples
- * (0 when m < 550).  formants [frame_off[n] x 5] in Hz, ascending, 0 where fewer than five roots lie in (50, 5450) Hz.
+ * goofer_track_pitch: Boersma's autocorrelation method with a Viterbi path, floor pitch_floor (75) Hz, ceiling
+ * min(pitch_ceiling (950), sr/2) Hz, time step hop / sr, Hann window of W = 3 sr / floor samples, lags floor(sr / ceiling) ..
+ * ceil(sr / floor), up to 15 candidates per frame.  Frames: (floor n - 3 sr) / (floor hop) + 1 per signal, centred in it.
+ * f0 [frame_off[n]] in Hz, 0 where unvoiced.  Every signal needs ceil(3 sr / floor) samples at least (GOOFER_EINVAL).  A frame
+ * and its lags live in LDS: a floor and rate that need more than 160 KiB are refused (GOOFER_EINVAL; none of the admitted
+ * floors does at an admitted rate).
+ * goofer_track_formants: Burg LPC of order 2 n_formants (10) on the signal resampled to R = 2 max_formant (11000) Hz (up as
+ * well as down) and pre-emphasised from 50 Hz (factor exp(-2 pi 50 / R)), Gaussian window of R / 20 samples (50 ms; 550),
+ * same time step; frames: floor((m - R / 20) sr / (R hop)) + 1 for m = n * R / sr resampled samples (0 when m < R / 20).
+ * formants [frame_off[n] x 5] in Hz, ascending, 0 where fewer than five roots lie in (50, R / 2 - 50) Hz; the columns from
+ * n_formants on are 0.
  * Non-finite samples: a NaN or infinite sample makes its signal's peak deviation NaN, as numpy's max does.  Every pitch frame
- * of that signal then has the unvoiced strength 0.45 (the silence term max(0, 2 - NaN) is 0), a frame whose window holds such
- * a sample has no voiced candidate, and a formant frame whose 11 kHz samples are not finite has no formants (0).  The other
- * signals of the batch are not affected.
+ * of that signal then has the unvoiced strength voicing_threshold (the silence term max(0, 2 - NaN) is 0), a frame whose
+ * window holds such a sample has no voiced candidate, and a formant frame whose resampled samples are not finite has no
+ * formants (0).  The other signals of the batch are not affected.
  * Each call is a composition of the single-stage calls below, and gives their bits. */
 int goofer_track_pitch(goofer_ctx *ctx, const double *y, const int64_t *sample_off, int n_signals, int sr, int hop,
                        int64_t *frame_off, double *f0, void *scratch, int64_t *scratch_bytes, void *stream);
@@ -358,9 +391,9 @@ int goofer_track_formants(goofer_ctx *ctx, const double *y, const int64_t *sampl
  * goofer_track_path: goofer_track_pitch's Viterbi stage on candidates in that layout, for time step hop / sr.  frame_off
  * [n_signals+1] is read (0 first, never decreasing); a cand_n outside [1, 15] is taken as the nearest of 1 and 15.  f0
  * [frame_off[n]]: the chosen candidate's frequency; the first best predecessor, and the first best last candidate, win ties.
- * goofer_track_resample: goofer_track_formants' 11 kHz signal.  x_off [n_signals+1] is written (n * 11000 / sr samples per
- * signal), x11 [x_off[n]] fp64 (device).  Every signal needs one sample at least.
- * goofer_track_formant_frames: goofer_track_formants' per-frame stage on a caller's 11 kHz signals x11 [x_off[n]] (device),
+ * goofer_track_resample: goofer_track_formants' resampled signal (11 kHz by default).  x_off [n_signals+1] is written
+ * (n * R / sr samples per signal), x11 [x_off[n]] fp64 (device).  Every signal needs one sample at least.
+ * goofer_track_formant_frames: goofer_track_formants' per-frame stage on a caller's signals at R Hz, x11 [x_off[n]] (device),
  * x_off read (0 first, never decreasing); sr and hop are the original rate and hop, which place the frames; frame_off is
  * written; formants as goofer_track_formants. */
 int goofer_track_candidates(goofer_ctx *ctx, const double *y, const int64_t *sample_off, int n_signals, int sr, int hop,
@@ -677,7 +710,7 @@ int goofer_set_option(goofer_ctx *ctx, const char *name, int value);
  * intermediate of the last synth batch to HOST memory; return element count / byte size. Tests only. */
 int goofer_debug_table(goofer_ctx *ctx, int which, float *host_out, int capacity);
 /* sizeof of the ABI structs (0 note_params, 1 batch, 2 note_plan, 3 assembly, 4 onepole_job, 5 post_note, 6 post,
- * 7 plan_request, 8 plan_geometry, 9 legacy_job) so bindings can verify layout */
+ * 7 plan_request, 8 plan_geometry, 9 legacy_job, 10 track_settings) so bindings can verify layout */
 int goofer_sizeof(int which);
 int64_t goofer_debug_fetch(goofer_ctx *ctx, int which, void *host_out, int64_t capacity_bytes);
 
