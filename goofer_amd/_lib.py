@@ -73,6 +73,10 @@ LEGACY_JOB = np.dtype([
 ], align=True)
 LEGACY_F32 = 1
 
+# goofer_phrase_note (goofer_host_phrase_plan / goofer_phrase_mix)
+PHRASE_NOTE = np.dtype([("start", "<i8"), ("skip", "<i4"), ("take", "<i4"), ("pos", "<f4", 7), ("val", "<f4", 7)], align=True)
+PHRASE_TILE = 2048              # GOOFER_PHRASE_TILE
+
 
 class Assembly(C.Structure):
     """goofer_assembly"""
@@ -214,6 +218,9 @@ EXPORTS = {
     "goofer_envelope_knots_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                               C.POINTER(C.c_int64), C.c_void_p]),
+    "goofer_host_phrase_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    "goofer_phrase_mix": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                    C.c_void_p]),
     "goofer_smooth_mask_ds": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_int, C.c_void_p,
                                         C.c_void_p]),
 }

@@ -615,6 +615,7 @@ int goofer_sizeof(int which)
     case 8: return (int)sizeof(goofer_plan_geometry);
     case 9: return (int)sizeof(goofer_legacy_job);
     case 10: return (int)sizeof(goofer_track_settings);
+    case 11: return (int)sizeof(goofer_phrase_note);
     }
     return -1;
 }

@@ -967,4 +967,49 @@ int64_t goofer_host_pack(const void *const *src, const int64_t *nbytes, int64_t 
     return rc ? rc : total;
 }
 
+/* Phrase assembly (include/goofer_hip.h; the kernel: phrase.hip): the records checked, and which notes each tile of the track
+ * mixes.  [lo, hi) of note i = its effective range on the track, empty for a note that contributes nothing. */
+static bool phrase_range(const goofer_phrase_note &r, int64_t len, int64_t total_out, int64_t *lo, int64_t *hi)
+{
+    const int64_t eff = std::min<int64_t>(r.take, len - r.skip);           // samples of the note that exist and are used
+    if (eff <= 0 || r.start >= total_out || r.start <= -eff) return false;   // (start may be anywhere in int64: no sum before this)
+    *lo = std::max<int64_t>(r.start, 0);
+    *hi = std::min(r.start + eff, total_out);
+    return *lo < *hi;
+}
+
+int goofer_host_phrase_plan(const goofer_phrase_note *notes, const int64_t *note_len, int n, int64_t total_out, int64_t *tile_off,
+                            int32_t *tile_notes, int64_t cap, int64_t *need)
+{
+    if (n < 0 || total_out < 0 || cap < 0 || !tile_off || !need || (n > 0 && (!notes || !note_len)) || (cap > 0 && !tile_notes))
+        return GOOFER_EINVAL;
+    const int64_t T = GOOFER_PHRASE_TILE, tiles = total_out / T + (total_out % T != 0);
+    if (tiles >= ((int64_t)1 << 31)) return GOOFER_EINVAL;
+    for (int i = 0; i < n; ++i) {
+        const goofer_phrase_note &r = notes[i];
+        if (note_len[i] < 0 || r.skip < 0 || r.take < 0 || r.take > (1 << 24)) return GOOFER_EINVAL;
+        if (r.pos[0] != 0.0f || r.pos[6] != (float)r.take) return GOOFER_EINVAL;
+        for (int k = 0; k < 7; ++k)
+            if (!std::isfinite(r.pos[k]) || !std::isfinite(r.val[k]) || (k > 0 && r.pos[k] < r.pos[k - 1])) return GOOFER_EINVAL;
+    }
+    // counts at tile_off[t + 1]; then the tiles' first entries there, which the fill advances to the first entry of tile t + 1
+    for (int64_t t = 0; t <= tiles; ++t) tile_off[t] = 0;
+    int64_t lo, hi;
+    for (int i = 0; i < n; ++i)
+        if (phrase_range(notes[i], note_len[i], total_out, &lo, &hi))
+            for (int64_t t = lo / T; t <= (hi - 1) / T; ++t) ++tile_off[t + 1];
+    int64_t run = 0;
+    for (int64_t t = 0; t < tiles; ++t) {
+        const int64_t c = tile_off[t + 1];
+        tile_off[t + 1] = run;
+        run += c;
+    }
+    *need = run;
+    if (run > cap) return 1;
+    for (int i = 0; i < n; ++i)
+        if (phrase_range(notes[i], note_len[i], total_out, &lo, &hi))
+            for (int64_t t = lo / T; t <= (hi - 1) / T; ++t) tile_notes[tile_off[t + 1]++] = i;
+    return GOOFER_OK;
+}
+
 }  // extern "C"

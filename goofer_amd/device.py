@@ -208,6 +208,31 @@ class Context:
         self._check(self.lib.goofer_pcm16(self.h, _ptr(x), x.numel(), _ptr(out), self._stream()))
         return out
 
+    def phrase_mix(self, x, sample_off, plan, out=None):
+        """The notes of a batch enveloped and mixed into one track on the device (goofer_phrase_mix; the definition:
+        include/goofer_hip.h, restated in tests/phrase_ref.py).  ``x``: the notes' samples back to back, a contiguous fp32 device
+        tensor (``out["mix"]`` of a batch); ``sample_off``: their int64 CSR offsets ``[n + 1]``, a device tensor or a host
+        sequence; ``plan``: a ``goofer_amd.phrase.PhrasePlan`` for these notes (records and cover table, shipped in one upload the
+        first time it is used on this device); ``out``: a contiguous fp32 device tensor of ``plan.total_out`` samples (default: a
+        new one; it need not be cleared, every sample is stored).  Asynchronous on the current stream."""
+        n, total = plan.n, plan.total_out
+        if not isinstance(sample_off, torch.Tensor):
+            sample_off = self.tensor(np.ascontiguousarray(sample_off, dtype=np.int64))
+        if sample_off.dtype != torch.int64 or not sample_off.is_contiguous() or sample_off.numel() != n + 1:
+            raise ValueError("phrase_mix: sample_off is one contiguous int64 CSR of the plan's %d notes" % n)
+        if x.dtype != torch.float32 or not x.is_contiguous():
+            raise ValueError("phrase_mix: x must be a contiguous float32 tensor")
+        if out is None:
+            out = torch.empty(total, dtype=torch.float32, device=self.device)
+        elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != total:
+            raise ValueError("phrase_mix: out must be a contiguous float32 tensor of the track's %d samples" % total)
+        notes, tile_off, tile_notes = plan.device_tables(self)
+        if n and not x.numel():                                # notes without samples: the library still wants an array
+            x = torch.zeros(4, dtype=torch.float32, device=self.device)
+        self._check(self.lib.goofer_phrase_mix(self.h, _ptr(x), _ptr(sample_off), n, _ptr(notes), _ptr(tile_off),
+                                               _ptr(tile_notes), total, _ptr(out), self._stream()))
+        return out
+
     def normal_fill(self, seed: int, params, lengths_or_offsets, tag: int, note_on=None, growl_scale=None, out=None):
         """float64 standard normals of stream ``tag`` (0 f0 jitter, 1 / 2 harmonic / breath volume jitter, 3 sub-harmonic f0
         jitter, 4 growl) for the notes of a ragged batch, drawn on the device (goofer_normal_fill; the stream's definition:

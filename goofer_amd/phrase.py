@@ -1,0 +1,289 @@
+"""Phrase assembly: the rendered notes of a batch enveloped, cross-faded and mixed into one track on the device.
+
+UTAU hands this step to a separate ``wavtool``: each note is trimmed (``stp``, ``length``), shaped by a seven-knot volume
+envelope, overlapped with its neighbour and summed onto the song's time line.  The reference project has no counterpart; the
+definition is this project's own (``include/goofer_hip.h``, goofer_phrase_note) and the kernel is
+``goofer_phrase_mix``.  Here: wavtool's arguments turned into note records (host, float64), the records checked and the
+cover table made by the library's planner (``goofer_host_phrase_plan``), and a command line,
+
+    python -m goofer_amd.phrase job.txt out.wav
+
+``job.txt`` holds one line per note, the 13 resampler arguments, ``|``, then wavtool's ``stp length p1 p2 p3 v1 v2 v3 v4 [ovr
+[p4 [p5 v5]]]``::
+
+    voice/a.wav a.wav C4 100 g-5 30 600 80 50 100 0 !120 AA | 0 480@120+20 5 35 40 0 100 100 0 20
+    R 240@120
+
+(the second argument, the resampler's out file, is not written: the notes stay on the device).  ``R <length>`` is a rest; empty
+lines and lines that start with ``#`` are skipped.  ``Renderer.render_phrase`` is the same for (Source, Request) jobs.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+import sys
+from dataclasses import dataclass, field
+
+import numpy as np
+
+from . import _lib
+
+TILE = _lib.PHRASE_TILE
+MAX_TAKE = 1 << 24
+
+
+def parse_length(text) -> float:
+    """wavtool's length in ms: plain milliseconds, or ``ticks@tempo[+-ms]`` = ticks / 480 * 60000 / tempo +- ms."""
+    if isinstance(text, (int, float)):
+        return float(text)
+    s = str(text).strip()
+    if "@" not in s:
+        return float(s)
+    ticks, rest = s.split("@", 1)
+    cut = max(rest.rfind("+"), rest.rfind("-"))
+    if cut > 0 and rest[cut - 1] not in "eE":
+        tempo, extra = rest[:cut], float(rest[cut:])
+    else:
+        tempo, extra = rest, 0.0
+    return float(ticks) / 480.0 * 60000.0 / float(tempo) + extra
+
+
+def samples(ms: float, sr) -> int:
+    """floor(ms * sr / 1000 + 0.5)"""
+    return int(math.floor(float(ms) * float(sr) / 1000.0 + 0.5))
+
+
+def envelope_overlap(args) -> float:
+    """``ovr`` of wavtool's envelope arguments ``p1 p2 p3 v1 v2 v3 v4 [ovr [p4 [p5 v5]]]`` in ms (missing: 0)."""
+    return float(args[7]) if len(args) > 7 else 0.0
+
+
+def envelope_knots(args, length_ms: float, sr):
+    """The seven knots of a note's record from wavtool's envelope arguments ``p1 p2 p3 v1 v2 v3 v4 [ovr [p4 [p5 v5]]]`` (ms
+    positions, percent values): (pos float32 [7] in samples, val float32 [7] linear).  In ms the knots are [0, p1, p1 + p2,
+    p1 + p2 + p5, L - p4 - p3, L - p4, L] with the values [0, v1, v2, v5, v3, v4, 0] / 100; a missing p4 is 0, a missing
+    p5 / v5 repeats knot 2.  Positions are clamped to [0, L], made non-decreasing by a running maximum, converted to samples
+    (* sr / 1000, not rounded), rounded to float32 and held at or below ``(float)take``, which the last one is set to
+    (take = floor(L * sr / 1000 + 0.5) may lie below L * sr / 1000)."""
+    a = [float(v) for v in args]
+    if len(a) < 7 or len(a) == 10 or len(a) > 11:
+        raise ValueError(f"envelope: p1 p2 p3 v1 v2 v3 v4 [ovr [p4 [p5 v5]]] expected, got {len(a)} values")
+    L = float(length_ms)
+    if not (L >= 0.0) or not all(math.isfinite(v) for v in a):
+        raise ValueError("envelope: the length must be >= 0 ms and every argument finite")
+    p1, p2, p3, v1, v2, v3, v4 = a[:7]
+    p4 = a[8] if len(a) > 8 else 0.0
+    p5, v5 = (a[9], a[10]) if len(a) > 10 else (0.0, v2)
+    pos_ms = np.array([0.0, p1, p1 + p2, p1 + p2 + p5, L - p4 - p3, L - p4, L], dtype=np.float64)
+    pos_ms = np.maximum.accumulate(np.clip(pos_ms, 0.0, L))
+    take = samples(L, sr)
+    pos = np.minimum((pos_ms * float(sr) / 1000.0).astype(np.float32), np.float32(take))
+    pos[0], pos[6] = 0.0, np.float32(take)
+    val = (np.array([0.0, v1, v2, v5, v3, v4, 0.0], dtype=np.float64) / 100.0).astype(np.float32)
+    return pos, val
+
+
+def place(lengths_ms, overlaps_ms, sr) -> np.ndarray:
+    """Track positions of the entries of a phrase laid end to end: b_0 = -ovr_0, b_i = b_(i-1) + L_(i-1) - ovr_i in ms and
+    float64; start_i = floor(b_i * sr / 1000 + 0.5), int64 (a first overlap puts start_0 below 0: those samples are dropped)."""
+    starts = np.zeros(len(lengths_ms), dtype=np.int64)
+    b = 0.0
+    for i, (L, ovr) in enumerate(zip(lengths_ms, overlaps_ms)):
+        b = b - float(ovr) if i == 0 else b + float(lengths_ms[i - 1]) - float(ovr)
+        starts[i] = samples(b, sr)
+    return starts
+
+
+@dataclass
+class Entry:
+    """One line of a phrase: a note (wavtool's arguments) or a rest (``rest=True``: only ``length`` counts)."""
+    length: float                                  # ms
+    envelope: tuple = ()                           # p1 p2 p3 v1 v2 v3 v4 [ovr [p4 [p5 v5]]]
+    stp: float = 0.0                               # ms dropped from the note's head
+    rest: bool = False
+
+    @classmethod
+    def parse(cls, text):
+        """``stp length p1 p2 p3 v1 v2 v3 v4 [ovr [p4 [p5 v5]]]`` (a string or its tokens), or ``R length``."""
+        toks = text.split() if isinstance(text, str) else list(text)
+        if toks and str(toks[0]) in ("R", "r"):
+            if len(toks) != 2:
+                raise ValueError("a rest is `R <length>`")
+            return cls(parse_length(toks[1]), rest=True)
+        if len(toks) < 9:
+            raise ValueError(f"wavtool arguments: stp length p1 p2 p3 v1 v2 v3 v4 [ovr [p4 [p5 v5]]] expected, got {len(toks)} values")
+        return cls(parse_length(toks[1]), tuple(float(v) for v in toks[2:]), float(toks[0]))
+
+    @property
+    def overlap(self) -> float:
+        return 0.0 if self.rest else envelope_overlap(self.envelope)
+
+
+@dataclass
+class PhrasePlan:
+    """What goofer_phrase_mix takes for one phrase: ``notes`` (_lib.PHRASE_NOTE [n]), the cover table ``tile_off`` (int64
+    [tiles + 1]) / ``tile_notes`` (int32), ``total_out``; ``blob`` holds the three back to back for one upload."""
+    n: int
+    total_out: int
+    sr: int
+    notes: np.ndarray
+    note_len: np.ndarray
+    tile_off: np.ndarray
+    tile_notes: np.ndarray
+    blob: np.ndarray
+    _dev: dict = field(default_factory=dict, repr=False)
+
+    def device_tables(self, ctx):
+        """(notes, tile_off, tile_notes) on ``ctx``'s device: views of the blob, uploaded on first use."""
+        import torch
+        hit = self._dev.get(ctx.device)
+        if hit is None:
+            d = ctx.tensor(self.blob)
+            a, b = self.notes.nbytes, self.notes.nbytes + self.tile_off.nbytes
+            hit = self._dev[ctx.device] = (d[:a], d[a:b].view(torch.int64), d[b:].view(torch.int32), d)
+        return hit[:3]
+
+
+def cover(notes: np.ndarray, note_len, total_out: int):
+    """goofer_host_phrase_plan: the records checked and the cover table of the track's tiles, (tile_off, tile_notes).  Raises
+    ValueError for a record the library refuses."""
+    lib = _lib.load()
+    notes = np.ascontiguousarray(notes, dtype=_lib.PHRASE_NOTE)
+    note_len = np.ascontiguousarray(note_len, dtype=np.int64)
+    if note_len.shape != notes.shape:
+        raise ValueError("one length per note")
+    tiles = (int(total_out) + TILE - 1) // TILE if total_out > 0 else 0
+    tile_off = np.zeros(tiles + 1, dtype=np.int64)
+    need = C.c_int64(0)
+    tile_notes = np.zeros(max(len(notes), 1), dtype=np.int32)
+    for _ in range(2):
+        rc = lib.goofer_host_phrase_plan(notes.ctypes.data, note_len.ctypes.data, len(notes), int(total_out), tile_off.ctypes.data,
+                                         tile_notes.ctypes.data, tile_notes.size, C.byref(need))
+        if rc != 1:
+            break
+        tile_notes = np.zeros(int(need.value), dtype=np.int32)
+    if rc != 0:
+        raise ValueError("goofer_host_phrase_plan refused the phrase (%d): knots must be finite and non-decreasing from 0 to take, "
+                         "0 <= take <= 2^24, skip >= 0, lengths and total_out >= 0" % rc)
+    return tile_off, tile_notes[:int(need.value)]
+
+
+def plan_records(notes, note_len, total_out: int, sr: int = 0) -> PhrasePlan:
+    """A PhrasePlan from finished records (any starts): checked, covered and packed."""
+    notes = np.ascontiguousarray(notes, dtype=_lib.PHRASE_NOTE)
+    note_len = np.ascontiguousarray(note_len, dtype=np.int64)
+    total_out = int(total_out)
+    tile_off, tile_notes = cover(notes, note_len, total_out)
+    pad = np.zeros(1, dtype=np.int32)                      # (no empty tensor on the device: an empty table still has an address)
+    blob = np.concatenate([notes.view(np.uint8).ravel(), tile_off.view(np.uint8), tile_notes.view(np.uint8), pad.view(np.uint8)])
+    return PhrasePlan(len(notes), total_out, int(sr), notes, note_len, tile_off, tile_notes, blob)
+
+
+def plan_phrase(entries, note_lens, sr, starts=None, total_out=None) -> PhrasePlan:
+    """The records, the cover table and the track length of a phrase, ready for one upload.  ``entries``: ``Entry`` objects
+    (or what ``Entry.parse`` takes), rests included; ``note_lens``: the rendered sample counts of the notes (the entries that
+    are not rests), in order; ``sr``: the batch's rate.  Notes are placed end to end with their overlaps (``place``) unless
+    ``starts`` gives each note's track position in samples; ``total_out`` defaults to the largest end of any note or rest."""
+    entries = [e if isinstance(e, Entry) else Entry.parse(e) for e in entries]
+    idx = [i for i, e in enumerate(entries) if not e.rest]
+    note_lens = np.asarray(note_lens, dtype=np.int64)
+    if len(idx) != len(note_lens):
+        raise ValueError(f"{len(idx)} notes among the entries, {len(note_lens)} rendered lengths")
+    takes = np.array([samples(e.length, sr) for e in entries], dtype=np.int64)
+    if takes.size and takes.max() > MAX_TAKE:
+        raise ValueError("an entry longer than 2^24 samples")
+    placed = place([e.length for e in entries], [e.overlap for e in entries], sr)
+    if starts is None:
+        note_starts = placed[idx]
+    else:
+        note_starts = np.asarray(starts, dtype=np.int64)
+        if note_starts.shape != (len(idx),):
+            raise ValueError("starts: one track position per note")
+    if total_out is None:
+        ends = placed + takes
+        if starts is not None and idx:
+            ends = np.concatenate([ends, note_starts + takes[idx]])
+        total_out = max(0, int(ends.max())) if ends.size else 0
+    notes = np.zeros(len(idx), dtype=_lib.PHRASE_NOTE)
+    for k, i in enumerate(idx):
+        e = entries[i]
+        pos, val = envelope_knots(e.envelope, e.length, sr)
+        skip = samples(e.stp, sr)
+        if skip < 0:
+            raise ValueError("stp must be >= 0")
+        notes[k] = (note_starts[k], skip, takes[i], pos, val)
+    return plan_records(notes, note_lens, total_out, sr)
+
+
+def read_job(path):
+    """The lines of a job file: [(resampler arguments or None for a rest, Entry)]."""
+    from . import sampler as S
+    out = []
+    with open(path, encoding="utf-8") as fh:
+        for ln, line in enumerate(fh, 1):
+            line = line.strip()
+            if not line or line.startswith("#"):
+                continue
+            try:
+                if "|" not in line:
+                    e = Entry.parse(line)
+                    if not e.rest:
+                        raise ValueError("a note is `<13 resampler arguments> | <wavtool arguments>`")
+                    out.append((None, e))
+                else:
+                    left, right = line.rsplit("|", 1)
+                    out.append((S.split_arguments(left.strip()), Entry.parse(right)))
+            except ValueError as err:
+                raise ValueError(f"{path}:{ln}: {err}") from None
+    return out
+
+
+def render_job(path, out_wav, renderer=None, seed=None, tracker=None, pcm16=True):
+    """``python -m goofer_amd.phrase``: the notes of a job file rendered as one batch and written as one wav.  ``in_file`` is
+    resolved like the resampler front end does: ``<stem>_features.goofy`` beside the wav, analysed and cached first when it is
+    missing (``trackers.ensure_features_batch``; the tracker: the argument, else ``$GOOFER_TRACKER``)."""
+    from pathlib import Path
+    from . import core, trackers
+    from . import sampler as S
+    from .render import Renderer, Source, write_wav
+    lines = read_job(path)
+    renderer = renderer or Renderer()
+    wavs = [Path(a[0]) for a, _ in lines if a is not None]
+    feats = trackers.ensure_features_batch(wavs, hop_length=renderer.hop, tracker=tracker, ctx=renderer.ctx) if wavs else {}
+    sources, jobs = {}, []
+    for a, _ in lines:
+        if a is None:
+            continue
+        feat = feats[Path(a[0])]
+        if isinstance(feat, BaseException):
+            raise feat
+        if feat not in sources:
+            sources[feat] = Source.from_pack(*core.load_features(feat))
+        jobs.append((sources[feat], S.decode_request(*a[2:13])))
+    if not jobs:
+        raise ValueError(f"{path}: no note")
+    if seed is None:
+        seed = int(np.random.SeedSequence().generate_state(1, dtype=np.uint64)[0])
+    track = renderer.render_phrase(jobs, [e for _, e in lines], seed=seed, pcm16=pcm16)
+    write_wav(out_wav, track, jobs[0][0].sr)
+    return track
+
+
+def main(argv=None) -> int:
+    import logging
+    logging.basicConfig(format="%(message)s", level=logging.INFO)
+    argv = list(sys.argv[1:] if argv is None else argv)
+    if len(argv) != 2:
+        logging.error("Usage:\n  python -m goofer_amd.phrase job.txt out.wav")
+        return 1
+    try:
+        track = render_job(argv[0], argv[1])
+    except Exception:                   # noqa: BLE001
+        logging.exception("Failed to render")
+        return 1
+    logging.info(f"Writing {argv[1]}: {len(track)} samples")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

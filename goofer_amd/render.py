@@ -448,6 +448,28 @@ class Renderer:
             return res, parts
         return res
 
+    def render_phrase(self, jobs, entries, seed: int = 0, phi_seeds=None, noise_seeds=None, pcm16: bool = False):
+        """The notes of ``jobs`` rendered as one batch and assembled into one track on the device: what a ``wavtool`` does with
+        the notes ``render`` returns, without bringing them home first (goofer_amd.phrase; goofer_phrase_mix).  ``entries``:
+        the phrase in order, one ``phrase.Entry`` (or its wavtool argument string ``stp length p1 p2 p3 v1 v2 v3 v4 [ovr [p4
+        [p5 v5]]]``) per job and ``R <length>`` rests between them where the song has them.  ``seed`` / ``phi_seeds`` /
+        ``noise_seeds`` as in ``render``: the notes are the same bits.  Returns the fp32 track, or with ``pcm16`` the wav's int16
+        samples (``Context.pcm16``: what ``write_wav`` makes of the fp32 track); one download either way."""
+        from . import phrase as P
+        entries = [e if isinstance(e, P.Entry) else P.Entry.parse(e) for e in entries]
+        if not jobs:
+            raise ValueError("render_phrase: a phrase without a note has no sample rate")
+        if len({src.sr for src, _ in jobs}) != 1:
+            raise ValueError("render_phrase: the notes of a phrase share one sample rate")
+        prep = self.prepare(jobs, phi_seeds=phi_seeds, noise_seeds=noise_seeds)
+        plan = P.plan_phrase(entries, np.diff(np.asarray(prep["sample_off"], dtype=np.int64)), jobs[0][0].sr)
+        out = self.run(prep, seed=seed)
+        track = self.ctx.phrase_mix(out["mix"], prep["offsets"]["d_s"], plan)
+        if pcm16:
+            track = self.ctx.pcm16(track)
+        self.ctx.check()                                   # synchronises; raises if the device flagged a note
+        return track.cpu().numpy()
+
     def assemble(self, prep):
         """goofer_assemble_batch alone (asynchronous): envelope rows, f0 and voicing mask of the batch."""
         ctx = self.ctx

@@ -672,6 +672,53 @@ typedef struct {
 } goofer_legacy_job;
 int goofer_legacy_normal_jobs(goofer_ctx *ctx, const goofer_legacy_job *jobs, int n_jobs, int64_t *attempts, void *stream);
 
+/* ---- phrase assembly: envelope and mix the notes of a batch into one track ------------------------------------------------
+ * What UTAU leaves to a separate `wavtool`: every rendered note trimmed, enveloped, cross-faded with its neighbours and summed
+ * onto one time line.  The reference has no counterpart; this is the definition (restated in float64 numpy by
+ * tests/phrase_ref.py).
+ *
+ * A batch of n notes holds samples x[sample_off[i] .. sample_off[i+1]), len_i that difference (goofer_batch.mix with its CSR).
+ * Note i has a record:
+ *   start   track position of the note's first used sample, any sign
+ *   skip    >= 0: samples dropped from the note's head (wavtool's stp)
+ *   take    in [0, 2^24]: samples used
+ *   pos[7]  knot positions in samples, non-decreasing, pos[0] == 0 and pos[6] == (float)take
+ *   val[7]  linear gains, finite
+ * For t in [0, total_out):  track[t] = sum_i g_i(u) * x_i[skip_i + u],  u = t - start_i,  over the notes with 0 <= u < take_i and
+ * skip_i + u < len_i (beyond a note's end is silence; what falls before 0 or past total_out is dropped).  The sum runs in
+ * ascending note index from +0.0f, each term one fp32 multiply, then one fp32 add (the library is built with
+ * -ffp-contract=off).  The gain: k = the largest index with pos[k] <= (float)u — pos[6] = take > u, so k <= 5 and
+ * pos[k+1] > pos[k] — and, in fp32 and in this order,
+ *   g = val[k] + (val[k+1] - val[k]) * (((float)u - pos[k]) / (pos[k+1] - pos[k]))
+ * Coincident knots are a step (the later value holds from that position on); nothing divides by zero. */
+#define GOOFER_PHRASE_TILE 2048
+typedef struct {
+    int64_t start;
+    int32_t skip;
+    int32_t take;
+    float pos[7];
+    float val[7];
+} goofer_phrase_note;
+
+/* Host side (no device, no handle): check the n records against note_len[n] (len_i, >= 0) and write the cover table of the
+ * track's tiles of GOOFER_PHRASE_TILE samples, tiles = ceil(total_out / GOOFER_PHRASE_TILE): tile_off[tiles + 1] (CSR) and
+ * tile_notes, the notes whose effective range [max(start, 0), min(start + min(take, len - skip), total_out)) meets the tile, in
+ * ascending note index (a note with an empty effective range is in no tile).  *need = entries of tile_notes.  Returns 0 with
+ * both arrays written; 1 when cap < *need (only *need is valid: grow, call again); GOOFER_EINVAL for a null argument, a negative
+ * count or length, decreasing knots, a position or value that is not finite, pos[0] != 0, pos[6] != take, take outside
+ * [0, 2^24], skip < 0, or a track of 2^31 tiles or more. */
+int goofer_host_phrase_plan(const goofer_phrase_note *notes, const int64_t *note_len, int n, int64_t total_out, int64_t *tile_off,
+                            int32_t *tile_notes, int64_t cap, int64_t *need);
+
+/* The track (phrase.hip): out[0 .. total_out), every sample stored exactly once — zeros where no note sounds — so `out` needs
+ * no clearing.  x, sample_off ([n + 1]), notes ([n], as validated by goofer_host_phrase_plan), tile_off and tile_notes (that
+ * call's table for the same records, lengths and total_out) and out are device arrays of the caller; `out` must not overlap x.
+ * One workgroup per tile, no atomics, no scratch; 16-byte stores when `out` is 16-byte aligned.  Asynchronous on `stream`;
+ * needs no plan.  total_out == 0: nothing is launched; n == 0: zeros.  GOOFER_EINVAL for a null pointer (x and notes may be null
+ * when n == 0), a negative count, x or out not 4-byte aligned, sample_off / notes / tile_off not 8-byte aligned. */
+int goofer_phrase_mix(goofer_ctx *ctx, const float *x, const int64_t *sample_off, int n, const goofer_phrase_note *notes,
+                      const int64_t *tile_off, const int32_t *tile_notes, int64_t total_out, float *out, void *stream);
+
 /* ---- measurement / test hooks --------------------------------------------------------------- */
 
 /* HIP-event timing of every stage of goofer_synth_batch on the caller's stream: begin() arms up to
@@ -710,7 +757,7 @@ int goofer_set_option(goofer_ctx *ctx, const char *name, int value);
  * intermediate of the last synth batch to HOST memory; return element count / byte size. Tests only. */
 int goofer_debug_table(goofer_ctx *ctx, int which, float *host_out, int capacity);
 /* sizeof of the ABI structs (0 note_params, 1 batch, 2 note_plan, 3 assembly, 4 onepole_job, 5 post_note, 6 post,
- * 7 plan_request, 8 plan_geometry, 9 legacy_job, 10 track_settings) so bindings can verify layout */
+ * 7 plan_request, 8 plan_geometry, 9 legacy_job, 10 track_settings, 11 phrase_note) so bindings can verify layout */
 int goofer_sizeof(int which);
 int64_t goofer_debug_fetch(goofer_ctx *ctx, int which, void *host_out, int64_t capacity_bytes);
 
