@@ -743,6 +743,17 @@ __global__ __launch_bounds__(256, 3) void k_harm_stem(const float *__restrict__ 
 #pragma unroll
     for (int q = 0; q < 4; ++q) ec[q] = g_edge[q * WAVE + lane];
 
+    // The note's spectrum maximum: a frame only folds its bins' |s|^2 into this lane's running maximum; the reduction over the
+    // lanes, the root and the atomic run once per note of the wave — where the loop leaves a note and behind the loop.  max, sqrt
+    // and + 1e-8f are non-decreasing, so sqrt(max over the note's frames, lanes and bins) + 1e-8f is the float the per-frame
+    // maxima arrived at, however the frames are grouped into runs.  Halo frames (f < f0) contribute: they lie in the note of
+    // frame f0, and the wave that owns them sends the same values.
+    float mx = 0.f;
+    auto note_max_out = [&]() {
+        const float m = __builtin_amdgcn_sqrtf(wave_max(mx)) + 1e-8f;   // max(|s| + 1e-8) = sqrt(max |s|^2) + 1e-8: sqrt is monotone
+        if (lane == 0) atomic_max_pos(note_mag + w.note, m);
+    };
+
     for (int64_t f = fs; f < f1; ++f) {
         float2 X[PER];
         float evc[PER];
@@ -754,6 +765,8 @@ __global__ __launch_bounds__(256, 3) void k_harm_stem(const float *__restrict__ 
         fetch(idx);
         const int t = FB_GET(fb, t, idx);
         if (FB_GET(fb, note, idx) != w.note) {
+            if (w.note >= 0) note_max_out();                      // the note being left
+            mx = 0.f;
             w.enter_note(fb, idx);
             const goofer_note_params &p = params[w.note];
             apply_bright = p.apply_brightness;
@@ -792,7 +805,6 @@ __global__ __launch_bounds__(256, 3) void k_harm_stem(const float *__restrict__ 
 
         // 3. shaping (GOOFER.py:1102-1144); 1 / max(|S| + 1e-8) commutes with the linear chain and is applied by k_note_finish
         const bool hp_low_only = t_fq[WAVE] - f0f > 100.0f;
-        float mx = 0.f;
 #pragma unroll
         for (int i = 0; i < PER; ++i) {
             const int k = lane + WAVE * i;
@@ -802,7 +814,7 @@ __global__ __launch_bounds__(256, 3) void k_harm_stem(const float *__restrict__ 
                 const float h = hp_mask(t_fq[k], f0f);
                 s.x *= h; s.y *= h;
             }
-            mx = fmaxf(mx, s.x * s.x + s.y * s.y);                 // |s|^2: the square root is taken once, of the maximum
+            mx = fmaxf(mx, s.x * s.x + s.y * s.y);                 // |s|^2: the square root is taken once per note, of the maximum
             const float bo = t_bo[k];
             s.x = (s.x * evc[i]) * bo;
             s.y = (s.y * evc[i]) * bo;
@@ -812,8 +824,6 @@ __global__ __launch_bounds__(256, 3) void k_harm_stem(const float *__restrict__ 
             }
             X[i] = s;
         }
-        mx = __builtin_amdgcn_sqrtf(wave_max(mx)) + 1e-8f;          // max(|s| + 1e-8) = sqrt(max |s|^2) + 1e-8: sqrt is monotone
-        if (lane == 0) atomic_max_pos(note_mag + w.note, mx);
         if (voiced && !td_blur) {
 #pragma unroll
             for (int i = 0; i < PER; ++i) {
@@ -882,6 +892,7 @@ __global__ __launch_bounds__(256, 3) void k_harm_stem(const float *__restrict__ 
         }
         wave_lds_sync();
     }
+    note_max_out();                                               // the last note of the run (fs < f1: the wave is in a note)
 }
 
 // ---------------------------------------------------------------------------------------------
