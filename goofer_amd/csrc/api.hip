@@ -595,6 +595,7 @@ int goofer_set_option(goofer_ctx *ctx, const char *name, int value)
     if (!strcmp(name, "td_blur")) { ctx->td_blur = value != 0; return GOOFER_OK; }
     if (!strcmp(name, "pulse_scan")) { ctx->pulse_scan = value < 0 ? 0 : (value > 2 ? 2 : value); return GOOFER_OK; }
     if (!strcmp(name, "sa_fast")) { ctx->sa_fast = value != 0; return GOOFER_OK; }
+    if (!strcmp(name, "sa_table")) { ctx->sa_table = value != 0; return GOOFER_OK; }
     if (!strcmp(name, "legacy_wave")) { ctx->legacy_wave = value != 0; return GOOFER_OK; }
     if (!strcmp(name, "mask_flags")) { ctx->mask_flags = value != 0; return GOOFER_OK; }
     if (!strcmp(name, "value_f64")) { ctx->value_f64 = value != 0; return GOOFER_OK; }

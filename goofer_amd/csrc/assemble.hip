@@ -882,6 +882,7 @@ struct sa_kernarg {                                          // k_sample_assembl
     int64_t total_samples;
     int fast;
     unsigned char *tile_flags;
+    const int2 *tile_notes;
 };
 // bad: mask_vote of every live mask value of this thread, or-ed into
 template <int SA_SPT, bool FLAGS>
@@ -967,28 +968,65 @@ __device__ __forceinline__ void sample_assemble_fast(const goofer_assembly &a, c
         if (live[u]) bad |= mask_vote(mv[u]);
 }
 
+// tile_notes[t] = {note of the first sample of tile t, note of its last sample} for the SA_TILE-sample tiles of the batch, without a
+// search: a wave per note.  Note k owns the samples [off[k], off[k + 1]) — off[n_notes] = total_samples, and what lies ahead of
+// off[0] goes to note 0 — which is what the search answers (the largest k with off[k] <= g): an empty note owns nothing, and over
+// sorted offsets every sample has exactly one owner, so every word is written once.  The lanes take the tiles the note touches
+// in turn; it writes .x where it owns the tile's first sample and .y where it owns its last (the batch's last in the last tile).
+__global__ __launch_bounds__(256) void k_sample_tile_notes(const goofer_note_plan *__restrict__ notes, int n_notes, int64_t total_samples,
+                                                           int2 *__restrict__ tile_notes)
+{
+    const int k = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (k >= n_notes) return;
+    int64_t s = k == 0 ? 0 : notes[k].out_sample_off;
+    int64_t e = k + 1 < n_notes ? notes[k + 1].out_sample_off : total_samples;
+    if (s < 0) s = 0;
+    if (e > total_samples) e = total_samples;
+    if (s >= e) return;
+    const int64_t t1 = (e - 1) / SA_TILE;                     // (inside the table: e <= total_samples)
+    for (int64_t t = s / SA_TILE + lane; t <= t1; t += WAVE) {
+        const int64_t g0 = t * SA_TILE;
+        int64_t gl = g0 + SA_TILE - 1;
+        if (gl > total_samples - 1) gl = total_samples - 1;
+        if (g0 >= s) tile_notes[t].x = k;
+        if (gl < e) tile_notes[t].y = k;
+    }
+}
+
 // FLAGS: every wave also leaves one byte about the SA_TILE / 4 mask values it stored, tile_flags[4 * blockIdx.x + wave] = the or of
 // mask_vote over them (bit 0: some value is not == 0.0f, bit 1: some value is not == 1.0f; -0.0f is a zero) — so the four bytes of
 // a tile, read as one word, say whether the tile of the mask is all zeros, all ones or neither, whatever notes it belongs to.
 // k_mask_short answers whole windows from these words instead of loading the mask again (goofer_render_batch; every other
 // caller: FLAGS false, the kernel as it was).  A byte per wave and not one per workgroup: combining the waves costs a barrier
 // at the end of a kernel that lives on its occupancy.
-template <int SA_SPT, bool FLAGS>
-__global__ __launch_bounds__(256) void k_sample_assemble(const goofer_assembly a, int64_t total_samples, int fast, unsigned char *__restrict__ tile_flags)
+// TABLE: the notes of the tile's first and last sample come from k_sample_tile_notes' table, one scalar load (the index of a
+// plan that is read next: held inside the batch whatever the table says).  Without it the first wave searches the plans for
+// both — two rounds of 64 loads across the plans' 300-byte stride each — and the other three wait at a barrier for the answer.
+template <int SA_SPT, bool FLAGS, bool TABLE>
+__global__ __launch_bounds__(256) void k_sample_assemble(const goofer_assembly a, int64_t total_samples, int fast, unsigned char *__restrict__ tile_flags,
+                                                         const int2 *__restrict__ tile_notes)
 {
-    __shared__ int s_pair[2];
     const int64_t g0 = (int64_t)blockIdx.x * (blockDim.x * SA_SPT);
-    if (threadIdx.x < WAVE) {
-        // notes own [out_sample_off, out_sample_off + n_out): first wave searches the plan array cooperatively
-        auto key = [&](int k) { return a.notes[k].out_sample_off; };
-        int64_t gl = g0 + (int64_t)blockDim.x * SA_SPT - 1;
-        if (gl > total_samples - 1) gl = total_samples - 1;
-        const int lo = wave_find(a.n_notes, g0, (int)threadIdx.x, key);
-        const int hi = wave_find(a.n_notes, gl, (int)threadIdx.x, key);
-        if (threadIdx.x == 0) { s_pair[0] = lo; s_pair[1] = hi; }
+    int n_lo, n_hi;
+    if (TABLE) {
+        const int2 pr = tile_notes[blockIdx.x];
+        n_lo = __builtin_amdgcn_readfirstlane(min(max(pr.x, 0), a.n_notes - 1));
+        n_hi = __builtin_amdgcn_readfirstlane(min(max(pr.y, 0), a.n_notes - 1));
+    } else {
+        __shared__ int s_pair[2];
+        if (threadIdx.x < WAVE) {
+            // notes own [out_sample_off, out_sample_off + n_out): first wave searches the plan array cooperatively
+            auto key = [&](int k) { return a.notes[k].out_sample_off; };
+            int64_t gl = g0 + (int64_t)blockDim.x * SA_SPT - 1;
+            if (gl > total_samples - 1) gl = total_samples - 1;
+            const int lo = wave_find(a.n_notes, g0, (int)threadIdx.x, key);
+            const int hi = wave_find(a.n_notes, gl, (int)threadIdx.x, key);
+            if (threadIdx.x == 0) { s_pair[0] = lo; s_pair[1] = hi; }
+        }
+        __syncthreads();
+        n_lo = __builtin_amdgcn_readfirstlane(s_pair[0]);
+        n_hi = __builtin_amdgcn_readfirstlane(s_pair[1]);
     }
-    __syncthreads();
-    const int n_lo = __builtin_amdgcn_readfirstlane(s_pair[0]), n_hi = __builtin_amdgcn_readfirstlane(s_pair[1]);
     unsigned bad = 0u;                                       // mask_vote of the values this thread stored
     unsigned char *flag_dst = nullptr;                       // (the fast path reads the pointer itself, ahead of its stores)
     auto vote = [&](float mk) { bad |= mask_vote(mk); };
@@ -1077,8 +1115,8 @@ __global__ void k_row_notes2(const goofer_note_plan *__restrict__ notes, int n_n
     if (r < out_rows) row_note_out[r] = lo2;
 }
 
-int launch_assemble(goofer_ctx *ctx, const goofer_assembly *a, int *row_note_edit, int *row_note_out, void *row_recs, render_link &link,
-                    hipStream_t st)
+int launch_assemble(goofer_ctx *ctx, const goofer_assembly *a, int *row_note_edit, int *row_note_out, void *row_recs, int2 *tile_notes,
+                    render_link &link, hipStream_t st)
 {
     const int B = a->n_bins;
     // per-kernel HIP events of a profiled run (goofer_profile_begin): stage PROF_ASM0 + which, on the stream the kernel runs on
@@ -1106,13 +1144,23 @@ int launch_assemble(goofer_ctx *ctx, const goofer_assembly *a, int *row_note_edi
         const dim3 sgrid((unsigned)((a->total_samples + 256 * spt - 1) / (256 * spt)));
         const int sa_fast = ctx->sa_fast ? 1 : 0;
         HIP_TRY(ctx, mark(2, 0, fst));
-        static_assert(256 * spt == SA_TILE, "one tile-flag word per workgroup of k_sample_assemble");
-        if (link.tile_flags_dst) {
-            hipLaunchKernelGGL((k_sample_assemble<spt, true>), sgrid, dim3(256), 0, fst, *a, a->total_samples, sa_fast, link.tile_flags_dst);
-            link.tile_flags = link.tile_flags_dst;
-        } else {
-            hipLaunchKernelGGL((k_sample_assemble<spt, false>), sgrid, dim3(256), 0, fst, *a, a->total_samples, sa_fast, (unsigned char *)nullptr);
+        static_assert(256 * spt == SA_TILE, "one tile-flag word and one tile_notes pair per workgroup of k_sample_assemble");
+        if (tile_notes) {
+            hipLaunchKernelGGL(k_sample_tile_notes, dim3((unsigned)((a->n_notes + 3) / 4)), dim3(256), 0, fst, a->notes, a->n_notes, a->total_samples,
+                               tile_notes);
+            LAUNCH_CHECK(ctx);
         }
+        unsigned char *const fl = link.tile_flags_dst;
+#define SAMPLE_ASSEMBLE(F, T) hipLaunchKernelGGL((k_sample_assemble<spt, F, T>), sgrid, dim3(256), 0, fst, *a, a->total_samples, sa_fast, fl, (const int2 *)tile_notes)
+        if (fl) {
+            if (tile_notes) SAMPLE_ASSEMBLE(true, true);
+            else SAMPLE_ASSEMBLE(true, false);
+            link.tile_flags = fl;
+        } else {
+            if (tile_notes) SAMPLE_ASSEMBLE(false, true);
+            else SAMPLE_ASSEMBLE(false, false);
+        }
+#undef SAMPLE_ASSEMBLE
         LAUNCH_CHECK(ctx);
         HIP_TRY(ctx, mark(2, 1, fst));
         if (link.fork_early && ctx->ev_f0) {

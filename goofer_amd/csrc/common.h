@@ -135,6 +135,8 @@ struct goofer_ctx {
     bool mask_flags = true;       // goofer_render_batch: k_sample_assemble leaves tile flags of the mask and k_mask_short answers flat windows from
                                   // them without loading the mask (option "mask_flags"; 0: A/B, the same bits)
     bool sa_fast = true;          // k_sample_assemble: the branch-free path with all of a thread's loads in flight together (option "sa_fast"; 0: A/B)
+    bool sa_table = true;         // k_sample_assemble reads the notes of its tile from k_sample_tile_notes' table instead of searching the plans
+                                  // (option "sa_table"; 0: A/B, the same bits)
     bool value_f64 = false;       // k_env_edit: round 4's fp64 value arithmetic (fw interpolation, es blur) instead of fp32 — A/B and the
                                   // error-budget tests (option "value_f64")
     bool legacy_wave = false;     // k_legacy_normal_fill: one wave per note instead of one 256-thread workgroup (option "legacy_wave"; A/B, the same bits)

@@ -24,8 +24,9 @@ int launch_knot_pick(goofer_ctx *ctx, const double *env2, int ld2, int64_t rows,
 
 // assemble.hip
 size_t env_row_rec_bytes();
-int launch_assemble(goofer_ctx *ctx, const goofer_assembly *a, int *row_note_edit, int *row_note_out, void *row_recs, render_link &link,
-                    hipStream_t st);
+// tile_notes: scratch for one int2 per SA_TILE samples (k_sample_tile_notes), or null: k_sample_assemble searches the plans
+int launch_assemble(goofer_ctx *ctx, const goofer_assembly *a, int *row_note_edit, int *row_note_out, void *row_recs, int2 *tile_notes,
+                    render_link &link, hipStream_t st);
 
 // binops.hip
 int launch_gauss_bins(goofer_ctx *ctx, const float *in, float *out, int64_t rows, int n_bins, int ld, const double *d_taps, int radius,

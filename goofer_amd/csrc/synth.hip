@@ -420,6 +420,8 @@ static int assemble_batch(goofer_ctx *ctx, const goofer_assembly *asmb, render_l
     char *recs;
     unsigned char *flags;
     const bool want_flags = link.want_tile_flags && a.mask_out && a.total_samples > 0;
+    int2 *tile_notes;
+    const bool want_table = ctx->sa_table && a.total_samples > 0;
     int rc = carve_block(ctx, &ctx->asm_scratch, &ctx->asm_bytes, "assembly scratch", [&](arena &m) {
         map_edit = m.take<int>((size_t)(a.total_edit_rows + a.total_out_rows) + 64);
         edit_rows = m.take<float>(a.edit_rows ? 0 : (size_t)a.total_edit_rows * a.ld);
@@ -427,11 +429,13 @@ static int assemble_batch(goofer_ctx *ctx, const goofer_assembly *asmb, render_l
         recs = m.take<char>((size_t)a.total_out_rows * env_row_rec_bytes());
         // goofer_render_batch: a word per SA_TILE samples of the mask, written by the f0 / mask kernel for k_mask_short
         flags = m.take<unsigned char>(want_flags ? 4 * (size_t)((a.total_samples + SA_TILE - 1) / SA_TILE) + 64 : 0);
+        // the notes of each SA_TILE tile's first and last sample, written by k_sample_tile_notes for the f0 / mask kernel
+        tile_notes = m.take<int2>(want_table ? (size_t)((a.total_samples + SA_TILE - 1) / SA_TILE) : 0);
     });
     if (rc) return rc;
     link.tile_flags_dst = want_flags ? flags : nullptr;
     if (!a.edit_rows) a.edit_rows = edit_rows;
-    return launch_assemble(ctx, &a, map_edit, map_edit + a.total_edit_rows, recs, link, st);
+    return launch_assemble(ctx, &a, map_edit, map_edit + a.total_edit_rows, recs, want_table ? tile_notes : nullptr, link, st);
 }
 
 // goofer_synth_batch; under goofer_render_batch `link` says what the assembly in front of it left: an f0 event to fork the pulse

@@ -746,6 +746,8 @@ const char *goofer_profile_stage_name_ex(const goofer_ctx *ctx, int stage);   /*
  *               decides an index, a threshold or the pitch curve stays fp64; 1: round 4's fp64
  *               arithmetic there (agrees to 2e-8 sample-RMS on the 1024-note batch; not bit-identical)
  *   "sa_fast"   1 (default): k_sample_assemble's branch-free path with all of a thread's loads in flight together; 0: per sample
+ *   "sa_table"  1 (default): k_sample_assemble reads the notes of its 1024-sample tile from a table a small kernel ahead of it
+ *               writes without a search; 0: every workgroup searches the note plans.  Same bits.
  *   "mask_flags" 1 (default): goofer_render_batch has k_sample_assemble leave a word per 1024 samples of the voicing mask (all == 0,
  *               all == 1, neither) and k_mask_short answer the windows those words settle without loading the mask; 0: no flags
  *               (goofer_assemble_batch / goofer_synth_batch on their own and goofer_smooth_mask_ds never have them).  Same bits.
