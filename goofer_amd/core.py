@@ -1035,6 +1035,23 @@ def resynthesize(y, sr, n_fft=1024, hop_length=256, *, noise_seed=None, **kw):
     return res
 
 
+def resample_batch(signals, sr_in, sr_out, ctx=None):
+    """Audio-rate conversion of many signals in one device pass (goofer_amd.rate; goofer_rate_convert): ``signals``, 1-D arrays
+    at ``sr_in``, come back as a list of fp32 arrays at ``sr_out``, signal i with ceil(len_i * sr_out / sr_in) samples.  The
+    converter is a polyphase Kaiser-windowed sinc, this project's own definition (include/goofer_hip.h); not GOOFER.py's
+    stretch_feature, which interpolates feature rows.  ``sr_in == sr_out`` is refused: there is nothing to convert."""
+    from . import rate as RT
+    c = ctx or default_context()
+    xs = [np.ascontiguousarray(s, dtype=np.float32).reshape(-1) for s in signals]
+    plan = RT.plan(sr_in, sr_out, [len(s) for s in xs])
+    if not plan.total_out:
+        return [np.zeros(0, dtype=np.float32) for _ in xs]
+    y = c.rate_convert(c.tensor(np.concatenate(xs)), None, plan)
+    c.check()
+    y = y.cpu().numpy()
+    return [y[plan.out_off[i]:plan.out_off[i + 1]] for i in range(plan.n)]
+
+
 def synthesize(env_spec, f0_interp, voicing_mask, y, sr, n_fft=1024, hop_length=256, glottal_smoothing=False,
                stretch_factor=1.0, start_sec=None, end_sec=None, apply_brightness=True, normalize=1.0, uv_strength=0.75,
                breath_strength=0.1, noise_transition_smoothness=100, pitch_shift=1.0, formant_shift=1.0, f0_jitter=False,

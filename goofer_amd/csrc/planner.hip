@@ -1012,4 +1012,57 @@ int goofer_host_phrase_plan(const goofer_phrase_note *notes, const int64_t *note
     return GOOFER_OK;
 }
 
+/* Output-rate conversion (include/goofer_hip.h; the kernel: rate.hip): geometry, the Kaiser-windowed sinc table in float64 and
+ * the output CSR.  I0 by its power series sum_k ((x/2)^k / k!)^2: every term positive, 45 terms at x = 14. */
+static double rate_i0(double x)
+{
+    const double t = 0.25 * x * x;
+    double term = 1.0, sum = 1.0;
+    for (int k = 1; k < 500; ++k) {
+        term *= t / ((double)k * (double)k);
+        sum += term;
+        if (term < 1e-18 * sum) break;
+    }
+    return sum;
+}
+
+int goofer_host_rate_plan(int sr_in, int sr_out, const int64_t *in_off, int n, int *L, int *M, int *H, float *taps, int64_t cap,
+                          int64_t *need, int64_t *out_off)
+{
+    if (!L || !M || !H || !need || !out_off || n < 0 || cap < 0 || (n > 0 && !in_off) || (cap > 0 && !taps)) return GOOFER_EINVAL;
+    if (sr_in < 1 || sr_out < 1 || sr_in == sr_out) return GOOFER_EINVAL;
+    int a = sr_in, b = sr_out;
+    while (b) { const int c = a % b; a = b; b = c; }
+    const int l = sr_out / a, m = sr_in / a, big = std::max(l, m);
+    if (big > GOOFER_RATE_MAX_PHASES) return GOOFER_EINVAL;
+    for (int i = 0; i < n; ++i) {
+        const int64_t len = in_off[i + 1] - in_off[i];
+        if (len < 0 || len >= ((int64_t)1 << 31)) return GOOFER_EINVAL;
+    }
+    const int h = (GOOFER_RATE_ZEROS * big + l - 1) / l, W = 2 * h;
+    *L = l, *M = m, *H = h;
+    *need = (int64_t)l * W;
+    if (cap < *need) return 1;
+    out_off[0] = 0;
+    for (int i = 0; i < n; ++i) out_off[i + 1] = out_off[i] + ((in_off[i + 1] - in_off[i]) * l + m - 1) / m;
+    const double pi = 3.14159265358979323846, fc = GOOFER_RATE_ROLLOFF * std::min(1.0, (double)l / (double)m);
+    const double i0b = rate_i0(GOOFER_RATE_BETA);
+    std::vector<double> row(W);
+    for (int p = 0; p < l; ++p) {
+        double sum = 0.0;
+        for (int c = 0; c < W; ++c) {
+            const double t = (double)(c - h + 1) - (double)p / (double)l, u = t / (double)h;
+            double v = 0.0;
+            if (std::fabs(t) < (double)h) {
+                const double w = rate_i0(GOOFER_RATE_BETA * std::sqrt(std::max(0.0, 1.0 - u * u))) / i0b, z = fc * t;
+                v = fc * (z == 0.0 ? 1.0 : std::sin(pi * z) / (pi * z)) * w;
+            }
+            row[c] = v;
+            sum += v;
+        }
+        for (int c = 0; c < W; ++c) taps[(int64_t)p * W + c] = (float)(row[c] / sum);
+    }
+    return GOOFER_OK;
+}
+
 }  // extern "C"

@@ -233,6 +233,34 @@ class Context:
                                                _ptr(tile_notes), total, _ptr(out), self._stream()))
         return out
 
+    def rate_convert(self, x, in_off, plan, out=None):
+        """The signals of a ragged batch converted to another sample rate on the device (goofer_rate_convert; the definition:
+        include/goofer_hip.h, restated in tests/rate_ref.py).  ``x``: the signals' samples back to back, a contiguous fp32 device
+        tensor (``out["mix"]`` of a batch, a phrase's track); ``in_off``: their int64 CSR offsets ``[n + 1]``, a device tensor,
+        a host sequence (checked against the plan) or None for the plan's own; ``plan``: a ``goofer_amd.rate.RatePlan`` for
+        these lengths (offsets and tap table, shipped in one upload the first time it is used on this device); ``out``: a
+        contiguous fp32 device tensor of ``plan.total_out`` samples that does not overlap ``x`` (default: a new one; it need
+        not be cleared, every sample is stored).  Signal i's output is ``out[plan.out_off[i]:plan.out_off[i + 1]]``.
+        Asynchronous on the current stream."""
+        n, total = plan.n, plan.total_out
+        d_in, d_out, taps = plan.device_tables(self)
+        if isinstance(in_off, torch.Tensor):
+            if in_off.dtype != torch.int64 or not in_off.is_contiguous() or in_off.numel() != n + 1:
+                raise ValueError("rate_convert: in_off is one contiguous int64 CSR of the plan's %d signals" % n)
+            d_in = in_off
+        elif in_off is not None and not np.array_equal(np.asarray(in_off, dtype=np.int64), plan.in_off):
+            raise ValueError("rate_convert: in_off is not the CSR the plan was made for")
+        if x.dtype != torch.float32 or not x.is_contiguous() or x.numel() < plan.total_in:
+            raise ValueError("rate_convert: x must be a contiguous float32 tensor of the plan's %d samples" % plan.total_in)
+        if out is None:
+            out = torch.empty(total, dtype=torch.float32, device=self.device)
+        elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != total:
+            raise ValueError("rate_convert: out must be a contiguous float32 tensor of the %d output samples" % total)
+        if total:                                              # (signals without samples have no output: nothing to launch)
+            self._check(self.lib.goofer_rate_convert(self.h, _ptr(x), _ptr(d_in), n, plan.L, plan.M, plan.H, _ptr(taps), _ptr(d_out),
+                                                     _ptr(out), self._stream()))
+        return out
+
     def normal_fill(self, seed: int, params, lengths_or_offsets, tag: int, note_on=None, growl_scale=None, out=None):
         """float64 standard normals of stream ``tag`` (0 f0 jitter, 1 / 2 harmonic / breath volume jitter, 3 sub-harmonic f0
         jitter, 4 growl) for the notes of a ragged batch, drawn on the device (goofer_normal_fill; the stream's definition:

@@ -6,7 +6,7 @@ definition is this project's own (``include/goofer_hip.h``, goofer_phrase_note; 
 ``goofer_phrase_mix``.  Here: wavtool's arguments turned into note records (host, float64), the records checked and the
 cover table made by the library's planner (``goofer_host_phrase_plan``), and a command line,
 
-    python -m goofer_amd.phrase job.txt out.wav
+    python -m goofer_amd.phrase [--rate HZ] job.txt out.wav
 
 ``job.txt`` holds one line per note, the 13 resampler arguments, ``|``, then wavtool's ``stp length p1 p2 p3 v1 v2 v3 v4 [ovr
 [p4 [p5 v5]]]``::
@@ -15,7 +15,9 @@ cover table made by the library's planner (``goofer_host_phrase_plan``), and a c
     R 240@120
 
 (the second argument, the resampler's out file, is not written: the notes stay on the device).  ``R <length>`` is a rest; empty
-lines and lines that start with ``#`` are skipped.  ``Renderer.render_phrase`` is the same for (Source, Request) jobs.
+lines and lines that start with ``#`` are skipped.  ``--rate HZ`` converts the mixed track from the voicebank's rate to HZ on
+the device (goofer_amd.rate) before it becomes int16; the wav's header carries HZ.  ``Renderer.render_phrase`` is the same for
+(Source, Request) jobs.
 """
 from __future__ import annotations
 
@@ -238,10 +240,11 @@ def read_job(path):
     return out
 
 
-def render_job(path, out_wav, renderer=None, seed=None, tracker=None, pcm16=True):
+def render_job(path, out_wav, renderer=None, seed=None, tracker=None, pcm16=True, out_sr=None):
     """``python -m goofer_amd.phrase``: the notes of a job file rendered as one batch and written as one wav.  ``in_file`` is
     resolved like the resampler front end does: ``<stem>_features.goofy`` beside the wav, analysed and cached first when it is
-    missing (``trackers.ensure_features_batch``; the tracker: the argument, else ``$GOOFER_TRACKER``)."""
+    missing (``trackers.ensure_features_batch``; the tracker: the argument, else ``$GOOFER_TRACKER``).  ``out_sr``: the rate of
+    the wav (``render_phrase``'s; None: the voicebank's)."""
     from pathlib import Path
     from . import core, trackers
     from . import sampler as S
@@ -264,8 +267,8 @@ def render_job(path, out_wav, renderer=None, seed=None, tracker=None, pcm16=True
         raise ValueError(f"{path}: no note")
     if seed is None:
         seed = int(np.random.SeedSequence().generate_state(1, dtype=np.uint64)[0])
-    track = renderer.render_phrase(jobs, [e for _, e in lines], seed=seed, pcm16=pcm16)
-    write_wav(out_wav, track, jobs[0][0].sr)
+    track = renderer.render_phrase(jobs, [e for _, e in lines], seed=seed, pcm16=pcm16, out_sr=out_sr)
+    write_wav(out_wav, track, jobs[0][0].sr if out_sr is None else int(out_sr))
     return track
 
 
@@ -273,11 +276,18 @@ def main(argv=None) -> int:
     import logging
     logging.basicConfig(format="%(message)s", level=logging.INFO)
     argv = list(sys.argv[1:] if argv is None else argv)
+    out_sr = None
+    if len(argv) == 4 and argv[0] == "--rate":
+        try:
+            out_sr = int(argv[1])
+            argv = argv[2:]
+        except ValueError:
+            pass                        # (four arguments left: the usage line)
     if len(argv) != 2:
-        logging.error("Usage:\n  python -m goofer_amd.phrase job.txt out.wav")
+        logging.error("Usage:\n  python -m goofer_amd.phrase [--rate HZ] job.txt out.wav")
         return 1
     try:
-        track = render_job(argv[0], argv[1])
+        track = render_job(argv[0], argv[1], out_sr=out_sr)
     except Exception:                   # noqa: BLE001
         logging.exception("Failed to render")
         return 1

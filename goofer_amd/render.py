@@ -424,7 +424,18 @@ class Renderer:
         lw = int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", "1")) or 1)
         self.plan_threads = 0 if lw <= 1 else max(1, min(8, (os.cpu_count() or 8) // lw))
 
-    def render(self, jobs, seed: int = 0, phi_seeds=None, return_parts: bool = False, noise_seeds=None):
+    def _out_rate(self, jobs, out_sr, who):
+        """The rate to convert to, or None where ``out_sr`` asks for none (None, or the notes' own rate)."""
+        if out_sr is None:
+            return None
+        rates = {int(src.sr) for src, _ in jobs}
+        if len(rates) != 1:
+            raise ValueError(f"{who}: out_sr converts notes that share one sample rate")
+        if int(out_sr) != out_sr or int(out_sr) < 1:
+            raise ValueError(f"{who}: out_sr is a whole number of Hz")
+        return None if int(out_sr) in rates else int(out_sr)
+
+    def render(self, jobs, seed: int = 0, phi_seeds=None, return_parts: bool = False, noise_seeds=None, out_sr=None):
         """jobs: list of (Source, Request).  Returns a list of fp32 arrays (the mix the reference writes to
         out.wav); with ``return_parts`` also a dict of device-side intermediates for tests.
         ``phi_seeds``: per-note seeds for INJECTED phases (parity with a seeded reference run: numpy's stream of each seed,
@@ -433,38 +444,51 @@ class Renderer:
         draws the jitter / growl normals on the device whether or not the phases are injected.
         ``noise_seeds``: per-note seeds of the sh / sr jitter: note i gets the normals a reference process draws after
         ``np.random.seed(noise_seeds[i])``, made on the device by ``Context.legacy_normal_fill`` — no ``np.random.randn`` is
-        called and the global generator is left as it is.  The 'sj' draws stay what the renderer's ``noise`` says."""
+        called and the global generator is left as it is.  The 'sj' draws stay what the renderer's ``noise`` says.
+        ``out_sr``: the notes converted from their sources' rate to this one on the device before the download (goofer_amd.rate;
+        the whole batch in one goofer_rate_convert); None, or the sources' own rate: no conversion."""
         if not jobs:
             return []
+        to_sr = self._out_rate(jobs, out_sr, "render")
         prep = self.prepare(jobs, phi_seeds=phi_seeds, trim_rows=not return_parts, noise_seeds=noise_seeds)   # tests look at the whole assembled envelope
         out = self.run(prep, seed=seed, keep_stems=return_parts)
+        mix, offs = out["mix"], prep["sample_off"]
+        if to_sr is not None:
+            from . import rate as RT
+            plan = RT.plan(jobs[0][0].sr, to_sr, np.diff(np.asarray(offs, dtype=np.int64)))
+            mix, offs = self.ctx.rate_convert(mix, prep["offsets"]["d_s"], plan), plan.out_off
         self.ctx.check()                                   # synchronises; raises if the device flagged a note
-        mix = out["mix"].cpu().numpy()
-        offs = prep["sample_off"]
+        mix = mix.cpu().numpy()
         res = [mix[offs[i]:offs[i + 1]] for i in range(len(jobs))]
         if return_parts:
-            parts = {"env": prep["env"], "f0": prep["f0"], "mask": prep["mask"], "env_off": prep["env_off"], "sample_off": offs,
+            parts = {"env": prep["env"], "f0": prep["f0"], "mask": prep["mask"], "env_off": prep["env_off"], "sample_off": prep["sample_off"],
                      "planned": prep["planned"], "stems": out}
             return res, parts
         return res
 
-    def render_phrase(self, jobs, entries, seed: int = 0, phi_seeds=None, noise_seeds=None, pcm16: bool = False):
+    def render_phrase(self, jobs, entries, seed: int = 0, phi_seeds=None, noise_seeds=None, pcm16: bool = False, out_sr=None):
         """The notes of ``jobs`` rendered as one batch and assembled into one track on the device: what a ``wavtool`` does with
         the notes ``render`` returns, without bringing them home first (goofer_amd.phrase; goofer_phrase_mix).  ``entries``:
         the phrase in order, one ``phrase.Entry`` (or its wavtool argument string ``stp length p1 p2 p3 v1 v2 v3 v4 [ovr [p4
         [p5 v5]]]``) per job and ``R <length>`` rests between them where the song has them.  ``seed`` / ``phi_seeds`` /
         ``noise_seeds`` as in ``render``: the notes are the same bits.  Returns the fp32 track, or with ``pcm16`` the wav's int16
-        samples (``Context.pcm16``: what ``write_wav`` makes of the fp32 track); one download either way."""
+        samples (``Context.pcm16``: what ``write_wav`` makes of the fp32 track); one download either way.  ``out_sr``: the
+        mixed track converted from the notes' rate to this one on the device (goofer_amd.rate) — mix, convert, then int16;
+        None, or the notes' own rate: no conversion."""
         from . import phrase as P
         entries = [e if isinstance(e, P.Entry) else P.Entry.parse(e) for e in entries]
         if not jobs:
             raise ValueError("render_phrase: a phrase without a note has no sample rate")
         if len({src.sr for src, _ in jobs}) != 1:
             raise ValueError("render_phrase: the notes of a phrase share one sample rate")
+        to_sr = self._out_rate(jobs, out_sr, "render_phrase")
         prep = self.prepare(jobs, phi_seeds=phi_seeds, noise_seeds=noise_seeds)
         plan = P.plan_phrase(entries, np.diff(np.asarray(prep["sample_off"], dtype=np.int64)), jobs[0][0].sr)
         out = self.run(prep, seed=seed)
         track = self.ctx.phrase_mix(out["mix"], prep["offsets"]["d_s"], plan)
+        if to_sr is not None:
+            from . import rate as RT
+            track = self.ctx.rate_convert(track, None, RT.plan(jobs[0][0].sr, to_sr, [plan.total_out]))
         if pcm16:
             track = self.ctx.pcm16(track)
         self.ctx.check()                                   # synchronises; raises if the device flagged a note

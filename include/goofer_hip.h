@@ -719,6 +719,58 @@ int goofer_host_phrase_plan(const goofer_phrase_note *notes, const int64_t *note
 int goofer_phrase_mix(goofer_ctx *ctx, const float *x, const int64_t *sample_off, int n, const goofer_phrase_note *notes,
                       const int64_t *tile_off, const int32_t *tile_notes, int64_t total_out, float *out, void *stream);
 
+/* ---- output-rate conversion: a ragged polyphase resampler ----------------------------------------------------------------
+ * Every note and every track is rendered at the voicebank's rate; this converts finished audio to another one (44.1 -> 48 kHz
+ * for a session, 96 kHz, ...) on the device, in front of goofer_pcm16 and the one download.  The reference has no counterpart;
+ * this is the definition (restated in numpy by tests/rate_ref.py).
+ *
+ * Geometry.  g = gcd(sr_in, sr_out), L = sr_out / g, M = sr_in / g, r = min(1, L / M).  Half width in input samples
+ *   H = ceil(GOOFER_RATE_ZEROS / r) = (GOOFER_RATE_ZEROS * max(L, M) + L - 1) div L,
+ * cutoff fc = GOOFER_RATE_ROLLOFF * r as a fraction of the input Nyquist rate.
+ *
+ * Taps (host, float64, stored as fp32).  The table is taps[L][2H], phase-major: row p holds h_p[j] for j = -H+1 .. H at column
+ * j + H - 1.  With t = j - p / L:
+ *   w(t) = I0(GOOFER_RATE_BETA * sqrt(1 - (t/H)^2)) / I0(GOOFER_RATE_BETA)  for |t| < H, else 0     (a Kaiser window)
+ *   h    = fc * sinc(fc * t) * w(t),  sinc(z) = sin(pi z) / (pi z), sinc(0) = 1
+ * Each row is divided by its float64 sum, then rounded to fp32 to nearest even.
+ *
+ * Output of a signal x of n samples: m = (n * L + M - 1) div M samples.  For 0 <= k < m, in int64,
+ *   q = (k * M) div L,  p = (k * M) mod L,
+ *   y[k] = sum over j = -H+1 .. H with 0 <= q + j < n of h_p[j] * x[q + j].
+ * The sum runs in ascending j from +0.0f, each term one fp32 multiply, then one fp32 add (the library is built with
+ * -ffp-contract=off).  For finite input, adding the out-of-range taps as products with zero gives the same bits (the
+ * accumulator is never -0.0); non-finite input propagates exactly as the sum says.
+ *
+ * Refused (GOOFER_EINVAL): a rate below 1, sr_in == sr_out, max(L, M) > GOOFER_RATE_MAX_PHASES (the table stays under 67 000
+ * floats: every pair among 8, 11.025, 16, 22.05, 24, 32, 44.1, 48, 88.2, 96 and 192 kHz but a few with L > 1024), a signal of
+ * 2^31 samples or more.
+ *
+ * Of the definition (float64 sums on the fp32 table): a unit sine up to 0.8 of the lower Nyquist rate comes out within 2.6e-7 of
+ * the analytic sine, a tone at 1.12 of the new Nyquist rate stays below 1.1e-7 after down-conversion, row sums are 1 within
+ * 6.1e-8 and max_p sum_j |h_p[j]| <= 2.30; the fp32 sum defined above is within 7.1e-7. */
+#define GOOFER_RATE_ZEROS 32
+#define GOOFER_RATE_ROLLOFF 0.945
+#define GOOFER_RATE_BETA 14.0
+#define GOOFER_RATE_MAX_PHASES 1024
+
+/* Host side (no device, no handle): the geometry of sr_in -> sr_out, the tap table and, for n signals whose samples lie back to
+ * back with the CSR in_off[n + 1] (non-decreasing), out_off[n + 1], the CSR of the m_i.  *need = L * 2H, the floats of `taps`.
+ * Returns 0 with L, M, H, taps, need and out_off written; 1 when cap < *need (only *need, *L, *M and *H are valid: grow, call
+ * again); GOOFER_EINVAL for what the definition refuses, a null argument (in_off may be null when n == 0, taps when cap == 0), a
+ * negative count or capacity, or offsets that decrease. */
+int goofer_host_rate_plan(int sr_in, int sr_out, const int64_t *in_off, int n, int *L, int *M, int *H, float *taps, int64_t cap,
+                          int64_t *need, int64_t *out_off);
+
+/* The conversion (rate.hip): out[out_off[i] .. out_off[i+1]) = y of signal x[in_off[i] .. in_off[i+1]), every output sample stored
+ * exactly once.  x, in_off ([n + 1]), taps ([L][2H]), out_off ([n + 1]) and out are device arrays of the caller, the geometry,
+ * table and offsets those of goofer_host_rate_plan for the same in_off; `out` must not overlap x.  One thread per output sample,
+ * no atomics, no scratch; the table is staged in LDS where it fits in 160 KiB (option "rate_lds").  Asynchronous on `stream` (the
+ * output count is read on the device: a fixed grid walks the batch); needs no plan.  n == 0: nothing is launched.  GOOFER_EINVAL for a null pointer (all arrays may be null when n == 0), a negative count, L, M or H outside the
+ * definition's range (1 <= L, M <= GOOFER_RATE_MAX_PHASES, H as defined), x, taps or out not 4-byte aligned, in_off or out_off
+ * not 8-byte aligned. */
+int goofer_rate_convert(goofer_ctx *ctx, const float *x, const int64_t *in_off, int n, int L, int M, int H, const float *taps,
+                        const int64_t *out_off, float *out, void *stream);
+
 /* ---- measurement / test hooks --------------------------------------------------------------- */
 
 /* HIP-event timing of every stage of goofer_synth_batch on the caller's stream: begin() arms up to
@@ -752,6 +804,8 @@ const char *goofer_profile_stage_name_ex(const goofer_ctx *ctx, int stage);   /*
  *               all == 1, neither) and k_mask_short answer the windows those words settle without loading the mask; 0: no flags
  *               (goofer_assemble_batch / goofer_synth_batch on their own and goofer_smooth_mask_ds never have them).  Same bits.
  *   "legacy_wave" 0 (default): goofer_legacy_normal_fill / _jobs give a job a workgroup of 256 threads; 1: one wave.  Same bits.
+ *   "rate_lds"  1 (default): goofer_rate_convert stages the tap table in LDS where it fits in 160 KiB; 0: every lane reads its
+ *               row from global memory, as it does for a table that does not fit.  Same bits.
  *   "prof_only" s >= 0: goofer_profile_begin .. end record the events of stage s only; -1 (default): every stage     */
 int goofer_set_option(goofer_ctx *ctx, const char *name, int value);
 
