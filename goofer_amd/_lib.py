@@ -225,6 +225,10 @@ EXPORTS = {
                                         C.c_int64, C.POINTER(C.c_int64), C.c_void_p]),
     "goofer_rate_convert": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p]),
+    "goofer_host_limit_plan": (C.c_int, [C.c_int, C.c_double, C.c_float, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_int64, C.c_void_p,
+                                         C.c_int64, C.c_void_p]),
+    "goofer_limit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_int64,
+                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "goofer_smooth_mask_ds": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_int, C.c_void_p,
                                         C.c_void_p]),
 }

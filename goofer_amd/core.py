@@ -1052,6 +1052,24 @@ def resample_batch(signals, sr_in, sr_out, ctx=None):
     return [y[plan.out_off[i]:plan.out_off[i + 1]] for i in range(plan.n)]
 
 
+def limit_batch(signals, sr, ceiling=32767.0 / 32768.0, lookahead_ms=5.0, ctx=None):
+    """The look-ahead peak limiter over many signals in one device pass (goofer_amd.limit; goofer_limit): ``signals``, 1-D
+    arrays at ``sr``, come back as a list of fp32 arrays of the same lengths whose samples stay within ``ceiling`` (0 < ceiling
+    <= 1), with two fp32 arrays: per signal its greatest ``|x|`` and the smallest gain it was given (0 and 1 for an empty one).
+    ``lookahead_ms``: how far ahead of a peak the gain starts to fall, and how long after it it recovers.  This project's own
+    definition (include/goofer_hip.h); a signal that never exceeds the ceiling comes back bit for bit."""
+    from . import limit as LM
+    xs = [np.ascontiguousarray(s, dtype=np.float32).reshape(-1) for s in signals]
+    plan = LM.plan(sr, [len(s) for s in xs], ceiling, lookahead_ms)
+    if not plan.n:
+        return [], np.zeros(0, dtype=np.float32), np.zeros(0, dtype=np.float32)
+    c = ctx or default_context()
+    y, peak, gain = c.limit(c.tensor(np.concatenate(xs + [np.zeros(1, dtype=np.float32)])), None, plan)
+    c.check()
+    y = y.cpu().numpy()
+    return [y[plan.in_off[i]:plan.in_off[i + 1]] for i in range(plan.n)], peak.cpu().numpy(), gain.cpu().numpy()
+
+
 def synthesize(env_spec, f0_interp, voicing_mask, y, sr, n_fft=1024, hop_length=256, glottal_smoothing=False,
                stretch_factor=1.0, start_sec=None, end_sec=None, apply_brightness=True, normalize=1.0, uv_strength=0.75,
                breath_strength=0.1, noise_transition_smoothness=100, pitch_shift=1.0, formant_shift=1.0, f0_jitter=False,

@@ -600,6 +600,7 @@ int goofer_set_option(goofer_ctx *ctx, const char *name, int value)
     if (!strcmp(name, "mask_flags")) { ctx->mask_flags = value != 0; return GOOFER_OK; }
     if (!strcmp(name, "value_f64")) { ctx->value_f64 = value != 0; return GOOFER_OK; }
     if (!strcmp(name, "rate_lds")) { ctx->rate_lds = value != 0; return GOOFER_OK; }
+    if (!strcmp(name, "limit_skip")) { ctx->limit_skip = value != 0; return GOOFER_OK; }
     return goofer_fail(ctx, GOOFER_EINVAL, "unknown option %s", name);
 }
 

@@ -141,6 +141,7 @@ struct goofer_ctx {
                                   // error-budget tests (option "value_f64")
     bool legacy_wave = false;     // k_legacy_normal_fill: one wave per note instead of one 256-thread workgroup (option "legacy_wave"; A/B, the same bits)
     bool rate_lds = true;         // goofer_rate_convert: the tap table staged in LDS where it fits (option "rate_lds"; 0: read from global memory, A/B, the same bits)
+    bool limit_skip = true;       // goofer_limit: a tile with nothing above the ceiling, halo included, copies its samples (option "limit_skip"; 0: the full arithmetic for every tile, A/B, the same bits)
     int pulse_scan = 1;           // 1: onsets from the parallel phase scan, the sequential walk only for the notes it cannot settle;
                                   // 0: the sequential walk kernel for every note; 2: the scan kernel walks every note (tests)
     // per-context kernel state: hipFuncSetAttribute is per device, and a handle belongs to one device, so what was set /

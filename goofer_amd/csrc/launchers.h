@@ -68,6 +68,10 @@ int launch_volume_jitter(goofer_ctx *ctx, float *harm, float *bre, const double 
                          const unsigned long long *max_h, const unsigned long long *max_b, const int64_t *sample_off, int n_notes,
                          int64_t total, const goofer_note_params *params, int vibrato, double speed, hipStream_t st);
 
+// limit.hip
+int launch_limit(goofer_ctx *ctx, const float *x, const int64_t *in_off, int n, int W, const float *taps, float c, const int32_t *tiles,
+                 int64_t n_tiles, float *out, float *peak_in, float *min_gain, hipStream_t st);
+
 // noise.hip
 int launch_normal_fill(goofer_ctx *ctx, uint64_t seed, const goofer_note_params *params, const int64_t *sample_off, int n_notes,
                        int64_t total, int tag, const unsigned char *note_on, const double *growl_scale, double *out, hipStream_t st);

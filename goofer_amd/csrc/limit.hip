@@ -1,0 +1,227 @@
+// Look-ahead peak limiter on the device (gfx950): finished audio — the notes of a batch back to back, or a phrase's track, at the
+// output rate — brought under a ceiling c immediately in front of goofer_pcm16, over a ragged batch in one launch.  The
+// definition (the raised-cosine table, the windowed minimum, the order of the fp32 sum) is in include/goofer_hip.h; the host
+// half, goofer_host_limit_plan (planner.hip), makes the look-ahead W, the table w[2W + 1] and the tile table.
+//
+// All FIR and min / max, no recursion: an output sample depends on the 4W + 1 input samples around it, of its own signal only.
+// One workgroup of 512 threads per tile of GOOFER_LIMIT_TILE samples of one signal (the planner's table says which: no search):
+//   1  r = c / |x| (or 1) of the tile and 2W samples of halo on either side into LDS; positions outside the signal hold 1, the
+//      identity of a minimum over values that are at most 1, so an edge runs the code of the inside.  The tile's |x| maximum on the
+//      way.  A tile without a sample above c, halo included, copies x to out and is done (option "limit_skip"; the definition's
+//      identity property: the same bits).
+//   2  window minima by doubling, in place: after the pass of step s, entry k holds min r[k .. k + 2s - 1].  K passes for the
+//      largest 2^K <= 2W + 1; a window of 2W + 1 is two overlapping reads of that.  Exact in any order.
+//   3  d = 1 - m of the tile and W samples on either side into a second LDS array, with the definition's index clamp applied
+//      here (a position outside the signal holds the d of the signal's first or last sample), so the sum below has no guard.
+//   4  the 2W + 1-tap sum: a thread owns eight consecutive samples and slides a window of d over them in registers, four taps and
+//      one 16-byte LDS read a step; at a given tap all lanes use the same w[j] (scalar loads).  One rounded multiply and one
+//      rounded add per tap in ascending j (the library is built with -ffp-contract=off).
+//   5  s = max(1 - acc, 0), g = min(s, r) with r made again from x, y = x g stored once; the tile's minimum of g.
+// Statistics: a butterfly per wave (peak_in: then over the workgroup's waves through LDS), then an integer atomic on the fp32
+// bits (max for peak_in, min for min_gain; exact for non-negative values, any order) where the value would move the word, into
+// words a small kernel in front has set to 0 and 1.  No scratch buffer.
+#include "launchers.h"
+
+#define LM_THREADS 512
+#define LM_SPT 8                       // consecutive samples per thread in the tap sum
+#define LM_T GOOFER_LIMIT_TILE
+static_assert(LM_T == LM_THREADS * LM_SPT, "one workgroup of 512 threads per tile");
+#define LM_STAGE ((LM_T + 4 * GOOFER_LIMIT_MAX_LOOK) / LM_THREADS)   // entries of the r array per thread, at most
+
+__global__ __launch_bounds__(256) void k_limit_init(int n, float *__restrict__ peak_in, float *__restrict__ min_gain)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) { peak_in[i] = 0.0f; min_gain[i] = 1.0f; }
+}
+
+__device__ __forceinline__ float limit_r(float a, float c) { return a > c ? __fdiv_rn(c, a) : 1.0f; }
+
+// A statistic of a signal, v >= 0, into its word: the integer order of the bits is the order of the values.  The word only ever
+// rises (max) or falls (min), so a value that would not move what a plain look finds there needs no atomic: the waves of
+// thousands of tiles on one address are otherwise one queue (a 48.7 M-sample signal with an atomic per wave and statistic: 1.11 ms
+// where its tiles only copy and 1.37 ms where they all do the arithmetic, against 0.17 and 1.02 ms with the look first).
+__device__ __forceinline__ void limit_stat_max(float *p, float v)
+{
+    unsigned int *w = reinterpret_cast<unsigned int *>(p);
+    const unsigned int b = __float_as_uint(v);
+    if (b > __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(w, b);
+}
+__device__ __forceinline__ void limit_stat_min(float *p, float v)
+{
+    unsigned int *w = reinterpret_cast<unsigned int *>(p);
+    const unsigned int b = __float_as_uint(v);
+    if (b < __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(w, b);
+}
+
+__global__ __launch_bounds__(LM_THREADS)
+void k_limit(const float *__restrict__ x, const int64_t *__restrict__ in_off, int n, int W, int span, const float *__restrict__ taps, float c,
+             const int32_t *__restrict__ tiles, float *__restrict__ out, float *__restrict__ peak_in, float *__restrict__ min_gain, int skip)
+{
+    extern __shared__ __align__(16) float s_lim[];
+    __shared__ float s_pk[LM_THREADS / 64];
+    const int tid = threadIdx.x;
+    const int sig = __builtin_amdgcn_readfirstlane(tiles[2 * blockIdx.x]), kt = __builtin_amdgcn_readfirstlane(tiles[2 * blockIdx.x + 1]);
+    if (sig < 0 || sig >= n || kt < 0) return;                  // (a table that is not the planner's: nothing is read or written)
+    const int64_t base = in_off[sig], len = in_off[sig + 1] - base, t0 = (int64_t)kt * LM_T;
+    if (t0 >= len) return;
+    const int NA = LM_T + 4 * W, NB = LM_T + 2 * W;             // r on [t0 - 2W, t0 + T + 2W), d on [t0 - W, t0 + T + W)
+    float *__restrict__ A = s_lim, *__restrict__ B = s_lim + NA;   // (NA is a multiple of 4: B is 16-byte aligned; B has NB + 4 entries)
+    const float *__restrict__ xs = x + base;
+    float *__restrict__ ys = out + base;
+    const int live = (int)(len - t0 < LM_T ? len - t0 : LM_T);  // samples of the tile that exist
+
+    // 1: r, the tile's peak, whether anything is above c
+    float pk = 0.0f;
+    bool over = false;
+    for (int k = tid; k < NA; k += LM_THREADS) {
+        const int64_t p = t0 - 2 * W + k;
+        float r = 1.0f;
+        if (p >= 0 && p < len) {
+            const float a = fabsf(xs[p]);
+            r = limit_r(a, c);
+            over |= a > c;
+            if (k >= 2 * W && k < 2 * W + LM_T) pk = fmaxf(pk, a);
+        }
+        A[k] = r;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) pk = fmaxf(pk, __shfl_xor(pk, o, 64));
+    if ((tid & 63) == 0) s_pk[tid >> 6] = pk;
+    const bool any = __syncthreads_or(over);                    // (the barrier also publishes A and s_pk)
+    if (tid == 0) {
+#pragma unroll
+        for (int w = 1; w < LM_THREADS / 64; ++w) pk = fmaxf(pk, s_pk[w]);
+        limit_stat_max(peak_in + sig, pk);
+    }
+    if (!any && skip) {
+        for (int e = tid; e < live; e += LM_THREADS) ys[t0 + e] = xs[t0 + e];
+        return;
+    }
+
+    // 2: in place, A[k] = min r[k .. k + span - 1]
+    for (int s = 1; s < span; s <<= 1) {
+        float v[LM_STAGE];
+#pragma unroll
+        for (int e = 0; e < LM_STAGE; ++e) {
+            const int k = tid + e * LM_THREADS;
+            if (k < NA) v[e] = fminf(A[k], k + s < NA ? A[k + s] : 1.0f);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < LM_STAGE; ++e) {
+            const int k = tid + e * LM_THREADS;
+            if (k < NA) A[k] = v[e];
+        }
+        __syncthreads();
+    }
+
+    // 3: B[k] = d[clamp(t0 - W + k, 0, len - 1)]; m of position t0 - W + kc is the minimum over A[kc .. kc + 2W]
+    const int second = 2 * W + 1 - span;
+    for (int k = tid; k < NB + 4; k += LM_THREADS) {
+        float d = 0.0f;                                         // (the four entries behind NB are loaded by step 4, never used)
+        if (k < NB) {
+            int64_t p = t0 - W + k;
+            p = p < 0 ? 0 : (p > len - 1 ? len - 1 : p);
+            const int kc = (int)(p - (t0 - W));                 // 0 <= kc < NB: W at most where p was raised to 0, at most k elsewhere
+            d = 1.0f - fminf(A[kc], A[kc + second]);            // kc + second < NB + W <= NA
+        }
+        B[k] = d;
+    }
+    __syncthreads();
+
+    // 4: acc[e] = sum_j w[j] d[i + j] of the thread's samples i = t0 + o + e
+    if ((tid & ~63) * LM_SPT >= live) return;                   // a wave without a sample (no barrier from here on)
+    const int o = tid * LM_SPT;
+    float gmin = 1.0f;
+    if (o < live) {
+        float acc[LM_SPT], win[LM_SPT + 4];
+#pragma unroll
+        for (int e = 0; e < LM_SPT; ++e) acc[e] = 0.0f;
+        {
+            const float4 q0 = *reinterpret_cast<const float4 *>(B + o), q1 = *reinterpret_cast<const float4 *>(B + o + 4);
+            win[0] = q0.x; win[1] = q0.y; win[2] = q0.z; win[3] = q0.w; win[4] = q1.x; win[5] = q1.y; win[6] = q1.z; win[7] = q1.w;
+        }
+        const int n_taps = 2 * W + 1;
+        int j = 0;                                              // win[k] = B[o + j + k]
+        for (; j + 4 <= n_taps; j += 4) {
+            const float4 q = *reinterpret_cast<const float4 *>(B + o + j + LM_SPT);
+            win[LM_SPT] = q.x; win[LM_SPT + 1] = q.y; win[LM_SPT + 2] = q.z; win[LM_SPT + 3] = q.w;
+            float w[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) w[u] = taps[j + u];
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+#pragma unroll
+                for (int e = 0; e < LM_SPT; ++e) acc[e] = acc[e] + w[u] * win[e + u];
+#pragma unroll
+            for (int e = 0; e < LM_SPT; ++e) win[e] = win[e + 4];
+        }
+        {                                                       // the last one or three taps (2W + 1 is odd)
+            const float4 q = *reinterpret_cast<const float4 *>(B + o + j + LM_SPT);
+            win[LM_SPT] = q.x; win[LM_SPT + 1] = q.y; win[LM_SPT + 2] = q.z; win[LM_SPT + 3] = q.w;
+#pragma unroll
+            for (int u = 0; u < 3; ++u) {
+                if (j + u < n_taps) {
+                    const float w = taps[j + u];
+#pragma unroll
+                    for (int e = 0; e < LM_SPT; ++e) acc[e] = acc[e] + w * win[e + u];
+                }
+            }
+        }
+        // 5: the gain and the output
+#pragma unroll
+        for (int e = 0; e < LM_SPT; ++e) {
+            if (o + e < live) {
+                const float xv = xs[t0 + o + e];
+                const float r = limit_r(fabsf(xv), c);
+                const float s = fmaxf(1.0f - acc[e], 0.0f);
+                const float g = fminf(s, r);
+                ys[t0 + o + e] = xv * g;
+                gmin = fminf(gmin, g);
+            }
+        }
+    }
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) gmin = fminf(gmin, __shfl_xor(gmin, s, 64));
+    if ((tid & 63) == 0 && gmin < 1.0f) limit_stat_min(min_gain + sig, gmin);
+}
+
+int launch_limit(goofer_ctx *ctx, const float *x, const int64_t *in_off, int n, int W, const float *taps, float c, const int32_t *tiles,
+                 int64_t n_tiles, float *out, float *peak_in, float *min_gain, hipStream_t st)
+{
+    if (n <= 0) return GOOFER_OK;
+    hipLaunchKernelGGL(k_limit_init, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, peak_in, min_gain);
+    LAUNCH_CHECK(ctx);
+    if (n_tiles <= 0) return GOOFER_OK;
+    int span = 1;
+    while (2 * span <= 2 * W + 1) span *= 2;
+    const size_t lds = ((size_t)(LM_T + 4 * W) + (size_t)(LM_T + 2 * W + 4)) * sizeof(float);   // 57 360 bytes at W = 1024
+    if (lds > 64 * 1024)
+        if (int rc = kernel_allow_max_lds(ctx, (const void *)k_limit)) return rc;
+    hipLaunchKernelGGL(k_limit, dim3((unsigned)n_tiles), dim3(LM_THREADS), lds, st, x, in_off, n, W, span, taps, c, tiles, out, peak_in,
+                       min_gain, ctx->limit_skip ? 1 : 0);
+    LAUNCH_CHECK(ctx);
+    return GOOFER_OK;
+}
+
+extern "C" int goofer_limit(goofer_ctx *ctx, const float *x, const int64_t *in_off, int n, int64_t total, int W, const float *taps, float c,
+                            const int32_t *tiles, int64_t n_tiles, float *out, float *peak_in, float *min_gain, void *stream)
+{
+    if (!ctx) return GOOFER_EINVAL;
+    if (n < 0 || total < 0 || n_tiles < 0)
+        return goofer_fail(ctx, GOOFER_EINVAL, "goofer_limit: negative count (%d signals, %lld samples, %lld tiles)", n, (long long)total,
+                           (long long)n_tiles);
+    // every signal with samples has ceil(len / tile) tiles: between ceil(total / tile) and that plus one per signal
+    const int64_t least = (total + LM_T - 1) / LM_T;
+    if (W < 1 || W > GOOFER_LIMIT_MAX_LOOK || !(c > 0.0f && c <= 1.0f) || n_tiles < least || n_tiles > least + n || n_tiles >= ((int64_t)1 << 31))
+        return goofer_fail(ctx, GOOFER_EINVAL, "goofer_limit: W = %d, c = %g, %lld tiles for %lld samples in %d signals is not a geometry of goofer_host_limit_plan",
+                           W, (double)c, (long long)n_tiles, (long long)total, n);
+    if (n == 0) return GOOFER_OK;
+    if (!in_off || !taps || !peak_in || !min_gain || (total > 0 && (!x || !out || !tiles)))
+        return goofer_fail(ctx, GOOFER_EINVAL, "goofer_limit: null pointer");
+    if (((uintptr_t)x | (uintptr_t)taps | (uintptr_t)out | (uintptr_t)tiles | (uintptr_t)peak_in | (uintptr_t)min_gain) & 3 || ((uintptr_t)in_off) & 7)
+        return goofer_fail(ctx, GOOFER_EINVAL, "goofer_limit: x, taps, tiles, out, peak_in and min_gain must be 4-byte aligned, in_off 8-byte aligned");
+    if (total > 0 && (uintptr_t)out < (uintptr_t)(x + total) && (uintptr_t)x < (uintptr_t)(out + total))
+        return goofer_fail(ctx, GOOFER_EINVAL, "goofer_limit: out overlaps x (halos are read from x again: not in place)");
+    return launch_limit(ctx, x, in_off, n, W, taps, c, tiles, n_tiles, out, peak_in, min_gain, (hipStream_t)stream);
+}

@@ -1065,4 +1065,41 @@ int goofer_host_rate_plan(int sr_in, int sr_out, const int64_t *in_off, int n, i
     return GOOFER_OK;
 }
 
+/* Look-ahead peak limiter (include/goofer_hip.h; the kernel: limit.hip): the look-ahead in samples, the raised-cosine table in
+ * float64 and, per tile of GOOFER_LIMIT_TILE samples of a signal, the pair (signal, tile of the signal) a workgroup reads. */
+int goofer_host_limit_plan(int sr, double look_ms, float c, const int64_t *in_off, int n, int *W, float *taps, int64_t taps_cap,
+                           int32_t *tiles, int64_t tiles_cap, int64_t *need)
+{
+    if (!W || !need || n < 0 || taps_cap < 0 || tiles_cap < 0 || (n > 0 && !in_off) || (taps_cap > 0 && !taps) || (tiles_cap > 0 && !tiles))
+        return GOOFER_EINVAL;
+    if (sr < 1 || !std::isfinite(look_ms) || !(c > 0.0f && c <= 1.0f)) return GOOFER_EINVAL;
+    const double look = std::floor(look_ms * (double)sr / 1000.0 + 0.5);
+    if (!(look >= 1.0 && look <= (double)GOOFER_LIMIT_MAX_LOOK)) return GOOFER_EINVAL;
+    int64_t n_tiles = 0;
+    for (int i = 0; i < n; ++i) {
+        const int64_t len = in_off[i + 1] - in_off[i];
+        if (len < 0 || len >= ((int64_t)1 << 31)) return GOOFER_EINVAL;
+        n_tiles += (len + GOOFER_LIMIT_TILE - 1) / GOOFER_LIMIT_TILE;
+    }
+    if (n_tiles >= ((int64_t)1 << 31)) return GOOFER_EINVAL;
+    const int w = (int)look, K = 2 * w + 1;
+    *W = w;
+    need[0] = K, need[1] = n_tiles;
+    if (taps_cap < K || tiles_cap < n_tiles) return 1;
+    const double pi = 3.14159265358979323846;
+    std::vector<double> row(K);
+    double sum = 0.0;
+    for (int k = 0; k < K; ++k) {
+        row[k] = 1.0 + std::cos(pi * (double)(k - w) / (double)(w + 1));
+        sum += row[k];
+    }
+    for (int k = 0; k < K; ++k) taps[k] = (float)(row[k] / sum);
+    int64_t t = 0;
+    for (int i = 0; i < n; ++i) {
+        const int64_t cnt = (in_off[i + 1] - in_off[i] + GOOFER_LIMIT_TILE - 1) / GOOFER_LIMIT_TILE;
+        for (int64_t k = 0; k < cnt; ++k, ++t) tiles[2 * t] = i, tiles[2 * t + 1] = (int32_t)k;
+    }
+    return GOOFER_OK;
+}
+
 }  // extern "C"

@@ -261,6 +261,38 @@ class Context:
                                                      _ptr(out), self._stream()))
         return out
 
+    def limit(self, x, d_off, plan, out=None):
+        """The signals of a ragged batch brought under a ceiling by the look-ahead peak limiter on the device (goofer_limit; the
+        definition: include/goofer_hip.h, restated in tests/limit_ref.py).  ``x``: the signals' samples back to back, a contiguous
+        fp32 device tensor (``out["mix"]`` of a batch, a phrase's track, the output of ``rate_convert``); ``d_off``: their int64
+        CSR offsets ``[n + 1]``, a device tensor, a host sequence (checked against the plan) or None for the plan's own;
+        ``plan``: a ``goofer_amd.limit.LimitPlan`` for these lengths (offsets, tile table and tap table, shipped in one upload
+        the first time it is used on this device); ``out``: a contiguous fp32 device tensor of ``plan.total`` samples that does
+        not overlap ``x`` (default: a new one; it need not be cleared).  Returns ``(y, peak_in, min_gain)``, device tensors:
+        signal i is ``y[plan.in_off[i]:plan.in_off[i + 1]]``, ``peak_in[i]`` its greatest ``|x|`` and ``min_gain[i]`` the
+        smallest gain it was given (fp32 ``[n]``).  Asynchronous on the current stream."""
+        n, total = plan.n, plan.total
+        d_in, tiles, taps = plan.device_tables(self)
+        if isinstance(d_off, torch.Tensor):
+            if d_off.dtype != torch.int64 or not d_off.is_contiguous() or d_off.numel() != n + 1:
+                raise ValueError("limit: d_off is one contiguous int64 CSR of the plan's %d signals" % n)
+            d_in = d_off
+        elif d_off is not None and not np.array_equal(np.asarray(d_off, dtype=np.int64), plan.in_off):
+            raise ValueError("limit: d_off is not the CSR the plan was made for")
+        if x.dtype != torch.float32 or not x.is_contiguous() or x.numel() < total:
+            raise ValueError("limit: x must be a contiguous float32 tensor of the plan's %d samples" % total)
+        if out is None:
+            out = torch.empty(total, dtype=torch.float32, device=self.device)
+        elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != total:
+            raise ValueError("limit: out must be a contiguous float32 tensor of the %d samples" % total)
+        peak_in = torch.empty(n, dtype=torch.float32, device=self.device)
+        min_gain = torch.empty(n, dtype=torch.float32, device=self.device)
+        if n:
+            self._check(self.lib.goofer_limit(self.h, _ptr(x) if total else None, _ptr(d_in), n, total, plan.W, _ptr(taps),
+                                              C.c_float(plan.ceiling), _ptr(tiles) if total else None, plan.n_tiles,
+                                              _ptr(out) if total else None, _ptr(peak_in), _ptr(min_gain), self._stream()))
+        return out, peak_in, min_gain
+
     def normal_fill(self, seed: int, params, lengths_or_offsets, tag: int, note_on=None, growl_scale=None, out=None):
         """float64 standard normals of stream ``tag`` (0 f0 jitter, 1 / 2 harmonic / breath volume jitter, 3 sub-harmonic f0
         jitter, 4 growl) for the notes of a ragged batch, drawn on the device (goofer_normal_fill; the stream's definition:

@@ -1,0 +1,108 @@
+"""Look-ahead peak limiter: finished audio brought under a ceiling on the device, in front of the int16 conversion.
+
+``goofer_pcm16`` hard-clips whatever arrives above full scale, and a finished track can: notes are peak-normalised before their
+volume, the phrase mix sums cross-faded neighbours, and the rate converter's windowed sinc overshoots.  The limiter is all FIR
+and min / max over a ragged batch, the definition this project's own (``include/goofer_hip.h``): the look-ahead, the
+raised-cosine table and the tile table come from the library's host planner (``goofer_host_limit_plan``), the kernel is
+``goofer_limit`` (``Context.limit``).  ``core.limit_batch`` is the numpy-in, numpy-out form; ``Renderer.render`` /
+``render_phrase`` take ``limit``.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from dataclasses import dataclass, field
+
+import numpy as np
+
+from . import _lib
+
+MAX_LOOK = 1024                     # GOOFER_LIMIT_MAX_LOOK
+TILE = 4096                         # GOOFER_LIMIT_TILE
+CEILING = 32767.0 / 32768.0         # GOOFER_LIMIT_CEILING
+LOOK_MS = 5.0                       # GOOFER_LIMIT_LOOK_MS
+
+
+@dataclass
+class LimitPlan:
+    """What goofer_limit takes for one ragged batch: the look-ahead ``W`` in samples, the ceiling (an fp32 value), the table
+    ``taps`` (float32 [2W + 1]), the signals' CSR ``in_off`` (int64 [n + 1]) and the tile table ``tiles`` (int32 [n_tiles, 2]:
+    signal, tile of the signal); ``blob`` holds offsets, tiles and table back to back for one upload."""
+    sr: int
+    n: int
+    W: int
+    ceiling: float
+    taps: np.ndarray
+    in_off: np.ndarray
+    tiles: np.ndarray
+    blob: np.ndarray
+    _dev: dict = field(default_factory=dict, repr=False)
+
+    @property
+    def total(self) -> int:
+        return int(self.in_off[-1])
+
+    @property
+    def n_tiles(self) -> int:
+        return len(self.tiles)
+
+    def device_tables(self, ctx):
+        """(in_off, tiles, taps) on ``ctx``'s device: views of the blob, uploaded on first use."""
+        import torch
+        hit = self._dev.get(ctx.device)
+        if hit is None:
+            d = ctx.tensor(self.blob)
+            a, b = self.in_off.nbytes, self.in_off.nbytes + self.tiles.nbytes
+            hit = self._dev[ctx.device] = (d[:a].view(torch.int64), d[a:b].view(torch.int32), d[b:].view(torch.float32), d)
+        return hit[:3]
+
+
+def parse(limit):
+    """``limit`` as Renderer.render takes it — a ceiling, or a (ceiling, lookahead_ms) pair — as that pair."""
+    if isinstance(limit, (tuple, list)):
+        if len(limit) != 2:
+            raise ValueError("limit is a ceiling or a (ceiling, lookahead_ms) pair")
+        return float(limit[0]), float(limit[1])
+    return float(limit), LOOK_MS
+
+
+def plan(sr, lengths, ceiling=CEILING, lookahead_ms=LOOK_MS) -> LimitPlan:
+    """goofer_host_limit_plan for signals of ``lengths`` samples lying back to back.  Raises ValueError for what the library
+    refuses: a look-ahead that rounds to less than 1 or more than 1024 samples, a ceiling that is not in (0, 1] as fp32, a rate
+    below 1, a signal of 2^31 samples or more."""
+    lib = _lib.load()
+    lengths = np.ascontiguousarray(lengths, dtype=np.int64).reshape(-1)
+    if lengths.size and lengths.min() < 0:
+        raise ValueError("limit.plan: a negative length")
+    if int(sr) != sr:
+        raise ValueError("limit.plan: the sample rate is a whole number of Hz")
+    n = len(lengths)
+    in_off = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(lengths, out=in_off[1:])
+    c = float(np.float32(ceiling))
+    W, need = C.c_int(0), (C.c_int64 * 2)(0, 0)
+    taps, tiles = np.zeros(0, dtype=np.float32), np.zeros((0, 2), dtype=np.int32)
+    rc = -1
+    for _ in range(2):
+        rc = lib.goofer_host_limit_plan(int(sr), float(lookahead_ms), C.c_float(c), in_off.ctypes.data, n, C.byref(W),
+                                        taps.ctypes.data if taps.size else None, taps.size,
+                                        tiles.ctypes.data if tiles.size else None, len(tiles), need)
+        if rc != 1:
+            break
+        taps, tiles = np.zeros(int(need[0]), dtype=np.float32), np.zeros((int(need[1]), 2), dtype=np.int32)
+    if rc != 0:
+        raise ValueError("goofer_host_limit_plan refused a ceiling of %r and %r ms at %s Hz (%d): a ceiling in (0, 1], a look-ahead of "
+                         "1 to %d samples, a rate >= 1, signals shorter than 2^31 samples" % (ceiling, lookahead_ms, sr, rc, MAX_LOOK))
+    blob = np.concatenate([in_off.view(np.uint8), tiles.view(np.uint8).ravel(), taps.view(np.uint8)])
+    return LimitPlan(int(sr), n, W.value, c, taps, in_off, tiles, blob)
+
+
+def look_samples(sr, lookahead_ms=LOOK_MS) -> int:
+    """W of the definition: floor(look_ms * sr / 1000 + 0.5) in float64."""
+    return int(math.floor(float(lookahead_ms) * float(sr) / 1000.0 + 0.5))
+
+
+def reduction_db(min_gain) -> float:
+    """a gain as the reduction it is, in dB (0 for a gain of 1; inf for 0)"""
+    g = float(min_gain)
+    return -20.0 * math.log10(g) if g > 0.0 else math.inf

@@ -6,7 +6,7 @@ definition is this project's own (``include/goofer_hip.h``, goofer_phrase_note; 
 ``goofer_phrase_mix``.  Here: wavtool's arguments turned into note records (host, float64), the records checked and the
 cover table made by the library's planner (``goofer_host_phrase_plan``), and a command line,
 
-    python -m goofer_amd.phrase [--rate HZ] job.txt out.wav
+    python -m goofer_amd.phrase [--rate HZ] [--limit [DBFS]] job.txt out.wav
 
 ``job.txt`` holds one line per note, the 13 resampler arguments, ``|``, then wavtool's ``stp length p1 p2 p3 v1 v2 v3 v4 [ovr
 [p4 [p5 v5]]]``::
@@ -16,8 +16,10 @@ cover table made by the library's planner (``goofer_host_phrase_plan``), and a c
 
 (the second argument, the resampler's out file, is not written: the notes stay on the device).  ``R <length>`` is a rest; empty
 lines and lines that start with ``#`` are skipped.  ``--rate HZ`` converts the mixed track from the voicebank's rate to HZ on
-the device (goofer_amd.rate) before it becomes int16; the wav's header carries HZ.  ``Renderer.render_phrase`` is the same for
-(Source, Request) jobs.
+the device (goofer_amd.rate) before it becomes int16; the wav's header carries HZ.  ``--limit [DBFS]`` runs the look-ahead peak
+limiter (goofer_amd.limit) over the track at the rate of the wav, with the ceiling DBFS decibels relative to full scale (bare:
+32767/32768), and reports the track's peak in front of it and its greatest gain reduction on stderr.
+``Renderer.render_phrase`` is the same for (Source, Request) jobs.
 """
 from __future__ import annotations
 
@@ -240,11 +242,12 @@ def read_job(path):
     return out
 
 
-def render_job(path, out_wav, renderer=None, seed=None, tracker=None, pcm16=True, out_sr=None):
+def render_job(path, out_wav, renderer=None, seed=None, tracker=None, pcm16=True, out_sr=None, limit=None, stats=None):
     """``python -m goofer_amd.phrase``: the notes of a job file rendered as one batch and written as one wav.  ``in_file`` is
     resolved like the resampler front end does: ``<stem>_features.goofy`` beside the wav, analysed and cached first when it is
     missing (``trackers.ensure_features_batch``; the tracker: the argument, else ``$GOOFER_TRACKER``).  ``out_sr``: the rate of
-    the wav (``render_phrase``'s; None: the voicebank's)."""
+    the wav (``render_phrase``'s; None: the voicebank's).  ``limit``: ``render_phrase``'s (None: no limiter); with it ``stats``,
+    a dict, receives the limiter's ``peak_in`` and ``min_gain``."""
     from pathlib import Path
     from . import core, trackers
     from . import sampler as S
@@ -267,7 +270,12 @@ def render_job(path, out_wav, renderer=None, seed=None, tracker=None, pcm16=True
         raise ValueError(f"{path}: no note")
     if seed is None:
         seed = int(np.random.SeedSequence().generate_state(1, dtype=np.uint64)[0])
-    track = renderer.render_phrase(jobs, [e for _, e in lines], seed=seed, pcm16=pcm16, out_sr=out_sr)
+    if limit is None:
+        track = renderer.render_phrase(jobs, [e for _, e in lines], seed=seed, pcm16=pcm16, out_sr=out_sr)
+    else:
+        track, st = renderer.render_phrase(jobs, [e for _, e in lines], seed=seed, pcm16=pcm16, out_sr=out_sr, limit=limit, return_stats=True)
+        if stats is not None:
+            stats.update(st)
     write_wav(out_wav, track, jobs[0][0].sr if out_sr is None else int(out_sr))
     return track
 
@@ -276,21 +284,37 @@ def main(argv=None) -> int:
     import logging
     logging.basicConfig(format="%(message)s", level=logging.INFO)
     argv = list(sys.argv[1:] if argv is None else argv)
-    out_sr = None
-    if len(argv) == 4 and argv[0] == "--rate":
-        try:
-            out_sr = int(argv[1])
+    out_sr = limit = None
+    while len(argv) > 2 and argv[0] in ("--rate", "--limit"):
+        if argv[0] == "--rate":
+            try:
+                out_sr = int(argv[1])
+            except ValueError:
+                break                   # (more than two arguments left: the usage line)
             argv = argv[2:]
-        except ValueError:
-            pass                        # (four arguments left: the usage line)
+        else:
+            from . import limit as LM
+            try:                        # --limit DBFS, or bare: the default ceiling
+                limit = 10.0 ** (float(argv[1]) / 20.0)
+                argv = argv[2:]
+            except ValueError:
+                limit = LM.CEILING
+                argv = argv[1:]
     if len(argv) != 2:
-        logging.error("Usage:\n  python -m goofer_amd.phrase [--rate HZ] job.txt out.wav")
+        logging.error("Usage:\n  python -m goofer_amd.phrase [--rate HZ] [--limit [DBFS]] job.txt out.wav")
         return 1
+    stats = {}
     try:
-        track = render_job(argv[0], argv[1], out_sr=out_sr)
+        track = render_job(argv[0], argv[1], out_sr=out_sr, limit=limit, stats=stats)
     except Exception:                   # noqa: BLE001
         logging.exception("Failed to render")
         return 1
+    if limit is not None:
+        from . import limit as LM
+        peak = stats["peak_in"]
+        print("Limiter: input peak %.2f dBFS, greatest reduction %.2f dB (ceiling %.2f dBFS)"
+              % (20.0 * math.log10(peak) if peak > 0.0 else -math.inf, LM.reduction_db(stats["min_gain"]), 20.0 * math.log10(limit)),
+              file=sys.stderr)
     logging.info(f"Writing {argv[1]}: {len(track)} samples")
     return 0
 

@@ -771,6 +771,70 @@ int goofer_host_rate_plan(int sr_in, int sr_out, const int64_t *in_off, int n, i
 int goofer_rate_convert(goofer_ctx *ctx, const float *x, const int64_t *in_off, int n, int L, int M, int H, const float *taps,
                         const int64_t *out_off, float *out, void *stream);
 
+/* ---- look-ahead peak limiter ----------------------------------------------------------------------------------------------
+ * goofer_pcm16 clamps to [-1, 1 - 2^-15]: whatever arrives above full scale is hard-clipped.  Notes are peak-normalised to 1
+ * before `volume`, goofer_phrase_mix sums cross-faded neighbours, and goofer_rate_convert's rows have sum_j |h_p[j]| up to 2.30,
+ * so a finished track can exceed 1.  This stage brings it under a ceiling on the device, at the output rate, immediately in
+ * front of goofer_pcm16.  The reference has no counterpart; this is the definition (restated in numpy by tests/limit_ref.py).
+ * All FIR and min / max, no recursion: an output sample depends on at most 4W + 1 input samples of its own signal, and a signal
+ * gets the same bits alone as at any position in any batch.
+ *
+ * Parameters.  Ceiling c: fp32, 0 < c <= 1 (default 32767/32768).  Look-ahead W = floor(look_ms * sr / 1000 + 0.5) samples, in
+ * float64 (default look_ms 5).  Refused (GOOFER_EINVAL): W < 1, W > GOOFER_LIMIT_MAX_LOOK, a non-finite or out-of-range c,
+ * sr < 1, a signal of 2^31 samples or more.
+ *
+ * Table (host, float64, stored as fp32).  w[j] for j = -W .. W (at index j + W) is 1 + cos(pi j / (W + 1)), divided by the
+ * float64 sum of the 2W + 1 values (taken in ascending j; 2W + 2 in the reals) and rounded to fp32 to nearest even.
+ *
+ * Per signal x[0 .. n), all arithmetic fp32, no contraction:
+ *   1  a[i] = |x[i]|
+ *   2  r[i] = a[i] > c ? c / a[i] : 1                 (the division correctly rounded)
+ *   3  m[i] = min r[k] over k in [i - W, i + W] intersected with [0, n)
+ *   4  d[i] = 1 - m[i]
+ *   5  acc[i] = sum_j w[j] * d[clamp(i + j, 0, n - 1)], in ascending j from +0.0f, one rounded multiply and one rounded add
+ *      per tap
+ *   6  s[i] = max(1 - acc[i], 0)
+ *   7  g[i] = min(s[i], r[i])
+ *   8  y[i] = x[i] * g[i]
+ * A signal with n = 0 produces nothing.  Statistics per signal, both exact: peak_in = max_i a[i] (0 for an empty signal),
+ * min_gain = min_i g[i] (1 for an empty signal).
+ *
+ * Properties (tried in numpy, fp32, at W = 1, 7, 220 and c = 32767/32768, 0.891, 0.5).  Ceiling: every term of acc uses an m
+ * whose window contains i, so in the reals s[i] <= r[i]; the final min takes care of the table's rounding; g <= r = fl(c / a)
+ * and y = fl(a g), so |y[i]| <= c (1 + 2^-24)^2 (the tests use c (1 + 2^-22); worst seen c (1 + 2^-23)); at the default c
+ * goofer_pcm16 of a limited track gives what an unclamped round would give.  Identity: where a <= c on all of [i - 2W, i + 2W]
+ * every d is +0, acc is +0 and g is exactly 1, so a signal that never exceeds c comes back bit for bit — which is why the sum
+ * is over the deficiency d and not over m.  Non-finite samples follow the arithmetic as written (a NaN asks for gain 1 and
+ * stays NaN).  True-peak (oversampled) detection, loudness metering and normalisation are not part of this. */
+#define GOOFER_LIMIT_MAX_LOOK 1024
+#define GOOFER_LIMIT_TILE 4096
+#define GOOFER_LIMIT_CEILING (32767.0f / 32768.0f)
+#define GOOFER_LIMIT_LOOK_MS 5.0
+
+/* Host side (no device, no handle): W, the table and the tile table for n signals whose samples lie back to back with the CSR
+ * in_off[n + 1] (non-decreasing; the limited signals lie at the same offsets).  need[0] = 2W + 1, the floats of `taps`;
+ * need[1] = sum_i ceil(len_i / GOOFER_LIMIT_TILE), the tiles: `tiles` holds one pair of int32 per tile, (signal, tile of that
+ * signal), in ascending order — the workgroups of goofer_limit.  Returns 0 with W, taps, tiles and need written; 1 when
+ * taps_cap < need[0] or tiles_cap (in pairs) < need[1] (only *W and need are valid: grow, call again); GOOFER_EINVAL for what the
+ * definition refuses, a null argument (in_off may be null when n == 0, taps / tiles when their capacity is 0), a negative count
+ * or capacity, or offsets that decrease. */
+int goofer_host_limit_plan(int sr, double look_ms, float c, const int64_t *in_off, int n, int *W, float *taps, int64_t taps_cap,
+                           int32_t *tiles, int64_t tiles_cap, int64_t *need);
+
+/* The limiter (limit.hip): out[in_off[i] .. in_off[i+1]) = y of signal x[in_off[i] .. in_off[i+1]), every sample stored exactly
+ * once; peak_in[i] and min_gain[i] (fp32 [n]) the statistics, set by the call (they need not be cleared).  x, in_off ([n + 1]),
+ * taps ([2W + 1]), tiles ([n_tiles] pairs), out, peak_in and min_gain are device arrays of the caller; W, taps, tiles and n_tiles
+ * those of goofer_host_limit_plan for the same in_off, total = in_off[n].  One workgroup per tile: the tile's r with 2W samples of
+ * halo on either side in LDS (halos are read from x again, so `out` must not overlap x: in place is a race), window minima by
+ * doubling, the tap sum from LDS, statistics by integer atomics on the fp32 bits.  A tile with nothing above c, halo included,
+ * copies its samples (option "limit_skip").  No scratch buffer, no plan; asynchronous on `stream`.  n == 0: nothing is launched;
+ * total == 0: only the statistics are set.  GOOFER_EINVAL, with nothing launched, for a null pointer (all arrays may be null when
+ * n == 0; x, out and tiles when total == 0), a negative count, W or c outside the definition's range, an n_tiles that is not
+ * between ceil(total / GOOFER_LIMIT_TILE) and that plus n, x, taps, tiles, out, peak_in or min_gain not 4-byte aligned, in_off not
+ * 8-byte aligned, or an out that overlaps x. */
+int goofer_limit(goofer_ctx *ctx, const float *x, const int64_t *in_off, int n, int64_t total, int W, const float *taps, float c,
+                 const int32_t *tiles, int64_t n_tiles, float *out, float *peak_in, float *min_gain, void *stream);
+
 /* ---- measurement / test hooks --------------------------------------------------------------- */
 
 /* HIP-event timing of every stage of goofer_synth_batch on the caller's stream: begin() arms up to
@@ -806,6 +870,8 @@ const char *goofer_profile_stage_name_ex(const goofer_ctx *ctx, int stage);   /*
  *   "legacy_wave" 0 (default): goofer_legacy_normal_fill / _jobs give a job a workgroup of 256 threads; 1: one wave.  Same bits.
  *   "rate_lds"  1 (default): goofer_rate_convert stages the tap table in LDS where it fits in 160 KiB; 0: every lane reads its
  *               row from global memory, as it does for a table that does not fit.  Same bits.
+ *   "limit_skip" 1 (default): a tile of goofer_limit with no sample above the ceiling, its halo of 2W samples on either side
+ *               included, copies x to out; 0: every tile does the full arithmetic.  Same bits (the identity property).
  *   "prof_only" s >= 0: goofer_profile_begin .. end record the events of stage s only; -1 (default): every stage     */
 int goofer_set_option(goofer_ctx *ctx, const char *name, int value);
 
