@@ -461,14 +461,25 @@ int goofer_check(goofer_ctx *ctx)
  *   "mask_flag_segments"    note segments of k_mask_short's tiles (goofer_synth_batch / goofer_render_batch) answered from the
  *                           f0 kernel's tile flags alone
  *   "mask_staged_segments"  ... that staged their mask window in LDS (every segment when there are no flags; the large-radius
- *                           loop counts nothing) */
+ *                           loop counts nothing)
+ * and, host-side ints of the handle (no device word is read): the frames per wave the LAST launch of a frame walker was given,
+ *   "walk_run_noise" k_noise_stems   "walk_run_harm" k_harm_stem   "walk_run_ola3" k_irfft_ola3   "walk_run_ola1" k_irfft_ola1
+ * (0: not launched on this handle yet; option "walk_run", walk_run_choice in launchers.h) */
 int goofer_counter(goofer_ctx *ctx, const char *name, int64_t *value)
 {
     if (!ctx || !name || !value) return GOOFER_EINVAL;
     int which = !strcmp(name, "pulse_fallback_notes") ? 1 : (!strcmp(name, "pulse_scanned_notes") ? 2 : -1);
     const int mask_c = !strcmp(name, "mask_flag_segments") ? 0 : (!strcmp(name, "mask_staged_segments") ? 1 : -1);
-    if (which < 0 && mask_c < 0) return goofer_fail(ctx, GOOFER_EINVAL, "unknown counter %s", name);
+    static const char *const walk_names[4] = {"walk_run_noise", "walk_run_harm", "walk_run_ola3", "walk_run_ola1"};
+    int walk = -1;
+    for (int k = 0; k < 4; ++k)
+        if (!strcmp(name, walk_names[k])) walk = k;
+    if (which < 0 && mask_c < 0 && walk < 0) return goofer_fail(ctx, GOOFER_EINVAL, "unknown counter %s", name);
     HIP_TRY(ctx, hipDeviceSynchronize());
+    if (walk >= 0) {
+        *value = ctx->walk_run_used[walk];
+        return GOOFER_OK;
+    }
     if (mask_c >= 0) {                                        // the sum of the counter's slots
         static_assert(OVF_WORDS <= 8192, "goofer_counter reads the words through a stack buffer");
         int32_t w[OVF_WORDS];
@@ -601,6 +612,7 @@ int goofer_set_option(goofer_ctx *ctx, const char *name, int value)
     if (!strcmp(name, "value_f64")) { ctx->value_f64 = value != 0; return GOOFER_OK; }
     if (!strcmp(name, "rate_lds")) { ctx->rate_lds = value != 0; return GOOFER_OK; }
     if (!strcmp(name, "limit_skip")) { ctx->limit_skip = value != 0; return GOOFER_OK; }
+    if (!strcmp(name, "walk_run")) { ctx->walk_run = value < 0 ? 0 : value; return GOOFER_OK; }   // clamped per kernel where the run is chosen (walk_run_choice)
     return goofer_fail(ctx, GOOFER_EINVAL, "unknown option %s", name);
 }
 

@@ -7,6 +7,32 @@
 
 struct onset_t;   // pulse.hip
 
+// Frames per wave of the four kernels in which a wave walks a run of consecutive frames (k_noise_stems, k_harm_stem, k_irfft_ola3,
+// k_irfft_ola1).  A run replays the `halo` frames in front of it without emitting them, so longer runs waste less; and every wave
+// does the same work, so the grid should fill the device a whole number of times: with k rounds of `slots` waves,
+// run = ceil(work / (k slots)), k the smallest that keeps a run at or below `cap` frames, and never below `floor_run`
+// (0.92 -> 0.85 ms for k_irfft_ola3 on the 1024-note batch: 95 frames per wave in one round instead of 32 in three).
+// `work`: the frames the waves share — k_irfft_ola1 gives a stem of a run to a wave: three times the batch's frames.
+// Option "walk_run" N > 0 replaces the choice by N clamped to what the choice itself can return for this kernel,
+// [floor_run, max(cap, floor_run)]: a test reaches long runs on a small batch and never a run no batch could get.
+// `which`: 0 k_noise_stems, 1 k_harm_stem, 2 k_irfft_ola3, 3 k_irfft_ola1 — the run is kept for goofer_counter "walk_run_*".
+enum { WALK_NOISE = 0, WALK_HARM = 1, WALK_OLA3 = 2, WALK_OLA1 = 3 };
+static inline int walk_floor(int halo) { return halo <= 4 ? 32 : 8 * halo; }
+static inline int walk_run_choice(goofer_ctx *ctx, int which, int64_t work, int64_t slots, int floor_run, int cap)
+{
+    int64_t run;
+    if (ctx->walk_run > 0) {
+        const int hi = cap > floor_run ? cap : floor_run;
+        run = ctx->walk_run < floor_run ? floor_run : (ctx->walk_run > hi ? hi : ctx->walk_run);
+    } else {
+        const int64_t rounds = (work + slots * cap - 1) / (slots * cap);
+        const int64_t fit = (work + rounds * slots - 1) / (rounds * slots);
+        run = fit > floor_run ? fit : floor_run;
+    }
+    ctx->walk_run_used[which] = (int)run;
+    return (int)run;
+}
+
 // analysis.hip
 int launch_gauss_rows64(goofer_ctx *ctx, const float *in, int ld, double *out, int ld64, int64_t rows, int n_bins, const double *d_taps,
                         int radius, hipStream_t st);

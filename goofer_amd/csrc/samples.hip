@@ -814,11 +814,8 @@ static int irfft_ola1_impl(goofer_ctx *ctx, const float2 *S_h, const float2 *S_u
     int cus = 0;
     HIP_TRY(ctx, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
     const int64_t slots = (int64_t)(cus > 0 ? cus : 256) * WPB;          // one workgroup per CU
-    // jobs = 3 stems x runs; runs sized so that the jobs fill the device a whole number of times, a run >= 8 halos
-    const int min_run = halo <= 4 ? 32 : 8 * halo;
-    const int64_t rounds = (3 * total_frames + slots * 256 - 1) / (slots * 256);
-    int64_t fit = (3 * total_frames + rounds * slots - 1) / (rounds * slots);
-    const int run = (int)(fit > min_run ? fit : min_run);
+    // jobs = 3 stems x runs: a wave walks one stem of a run, a run >= 8 halos
+    const int run = walk_run_choice(ctx, WALK_OLA1, 3 * total_frames, slots, walk_floor(halo), 256);
     const int64_t runs = (total_frames + run - 1) / run;
     ola1_args A;
     A.S_h = S_h; A.S_u = S_u; A.S_b = S_b; A.frame_note = frame_note; A.ldc = ldc; A.hop = p.hop; A.run = run; A.halo = halo;
@@ -942,14 +939,7 @@ static int irfft_ola3_impl(goofer_ctx *ctx, const float2 *S_h, const float2 *S_u
     if (rc) return rc;
     int slots = 0;                                            // waves of this kernel the device holds at once
     if ((rc = kernel_resident_waves(ctx, (const void *)k_irfft_ola3<M>, lds, &slots))) return rc;
-    // Frames per wave.  A run replays `halo` frames it does not emit, so longer runs waste less; and every wave does the
-    // same work, so the grid should fill the device a whole number of times: with k rounds of `slots` waves,
-    // run = ceil(frames / (k slots)), k the smallest that keeps a run at or below 128 frames (0.92 -> 0.85 ms on the
-    // 1024-note batch: 95 frames per wave in one round instead of 32 in three).
-    const int min_run = halo <= 4 ? 32 : 8 * halo;
-    const int64_t rounds = (total_frames + (int64_t)slots * 128 - 1) / ((int64_t)slots * 128);
-    int64_t fit = (total_frames + rounds * slots - 1) / (rounds * slots);
-    const int run = (int)(fit > min_run ? fit : min_run);
+    const int run = walk_run_choice(ctx, WALK_OLA3, total_frames, slots, walk_floor(halo), 128);
     const int64_t runs = (total_frames + run - 1) / run;
     hipLaunchKernelGGL(k_irfft_ola3<M>, dim3((unsigned)((runs + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK)), dim3(256), lds, st, S_h, S_u,
                        S_b, ldc, total_frames, frame_note, frame_off, sample_off, p.hop, run, halo, note_mag, short_s, steps, params,

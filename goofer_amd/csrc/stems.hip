@@ -1099,17 +1099,6 @@ __global__ void k_frame_picks(const int64_t *__restrict__ frame_off, const int *
     picks[f] = pv;
 }
 
-// ---------------------------------------------------------------------------------------------
-// Frames per wave.  A run replays `halo` frames it does not emit, so longer runs waste less; and every wave does the same
-// work, so the grid should fill the device a whole number of times: with k rounds of `slots` waves,
-// run = ceil(frames / (k slots)), k the smallest that keeps a run at or below 128 frames.
-static int run_length(int64_t total_frames, int slots)
-{
-    const int64_t rounds = (total_frames + (int64_t)slots * 128 - 1) / ((int64_t)slots * 128);
-    const int64_t fit = (total_frames + rounds * slots - 1) / (rounds * slots);
-    return (int)(fit > 32 ? fit : 32);
-}
-
 bool stems_supported(const goofer_plan_t &p) { return p.n_fft == 1024 && p.hop * 4 == p.n_fft; }
 
 int launch_frame_picks(goofer_ctx *ctx, const int64_t *frame_off, const int *frame_note, int64_t F, const int64_t *sample_off,
@@ -1138,7 +1127,7 @@ int launch_noise_stems(goofer_ctx *ctx, const float *env, int ld, const int64_t 
     int rc, slots = 0;
     if ((rc = kernel_allow_max_lds(ctx, fn))) return rc;
     if ((rc = kernel_resident_waves(ctx, fn, lds, &slots))) return rc;
-    const int run = run_length(F, slots);
+    const int run = walk_run_choice(ctx, WALK_NOISE, F, slots, walk_floor(p.n_fft / p.hop - 1), 128);
     const int64_t runs = (F + run - 1) / run;
     const dim3 grid((unsigned)((runs + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK));
     noise_args A;
@@ -1170,7 +1159,7 @@ int launch_harm_stem(goofer_ctx *ctx, const float *pulse, const float *env, cons
     int rc, slots = 0;
     if ((rc = kernel_allow_max_lds(ctx, fn))) return rc;
     if ((rc = kernel_resident_waves(ctx, fn, lds, &slots))) return rc;
-    const int run = run_length(F, slots);
+    const int run = walk_run_choice(ctx, WALK_HARM, F, slots, walk_floor(p.n_fft / p.hop - 1), 128);
     const int64_t runs = (F + run - 1) / run;
     hipLaunchKernelGGL(k_harm_stem<M>, dim3((unsigned)((runs + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK)), dim3(256), lds, st, pulse, env,
                        env_plain, have_formants ? 1 : 0, ld, row_src, F, frame_note, frame_off, sample_off, picks, params, p.freqs, p.boost, p.bright_h, harm,

@@ -495,7 +495,8 @@ class Context:
 
     def counter(self, name: str) -> int:
         """Cumulative device-side counter of the handle (goofer_counter): 'pulse_scanned_notes', 'pulse_fallback_notes',
-        'mask_flag_segments', 'mask_staged_segments'."""
+        'mask_flag_segments', 'mask_staged_segments'; and, host-side and not cumulative, the frames per wave of the last launch
+        of each frame walker: 'walk_run_noise', 'walk_run_harm', 'walk_run_ola3', 'walk_run_ola1' (option 'walk_run')."""
         v = C.c_int64(0)
         self._check(self.lib.goofer_counter(self.h, name.encode(), C.byref(v)))
         return int(v.value)

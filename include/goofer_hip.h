@@ -520,7 +520,10 @@ int goofer_check(goofer_ctx *ctx);
  * sequentially afterwards because a sample's phase lay within the scan's rounding band of an integer.
  * "mask_flag_segments" / "mask_staged_segments": note segments of the mask smoother's 1024-knot tiles (goofer_synth_batch /
  * goofer_render_batch) that were answered from the f0 kernel's tile flags alone / that staged their window of the mask (option
- * "mask_flags"; without flags every segment stages; the per-sample loop of a radius above 1792 knots counts nothing). */
+ * "mask_flags"; without flags every segment stages; the per-sample loop of a radius above 1792 knots counts nothing).
+ * "walk_run_noise" / "walk_run_harm" / "walk_run_ola3" / "walk_run_ola1": not cumulative and not on the device — the frames per
+ * wave that the last launch of k_noise_stems / k_harm_stem / k_irfft_ola3 / k_irfft_ola1 on this handle was given (0: none
+ * yet; option "walk_run"). */
 int goofer_counter(goofer_ctx *ctx, const char *name, int64_t *value);
 
 /* gf.smooth_mask_ds (GOOFER.py:556-569) on its own, for a ragged batch of voicing masks (sample_off[n_notes + 1]): decimate by
@@ -872,6 +875,12 @@ const char *goofer_profile_stage_name_ex(const goofer_ctx *ctx, int stage);   /*
  *               row from global memory, as it does for a table that does not fit.  Same bits.
  *   "limit_skip" 1 (default): a tile of goofer_limit with no sample above the ceiling, its halo of 2W samples on either side
  *               included, copies x to out; 0: every tile does the full arithmetic.  Same bits (the identity property).
+ *   "walk_run"  0 (default): the four frame walkers (k_noise_stems, k_harm_stem, k_irfft_ola3, k_irfft_ola1) get the frames per
+ *               wave that fill the device a whole number of times: from a floor of 32 frames (8 halos where the halo
+ *               (n_fft - 1) / hop is above 4) to 128, k_irfft_ola1 256; a batch leaves the floor only with tens of thousands of
+ *               frames.  N > 0: N frames per wave, clamped per kernel to that same range [floor, max(cap, floor)] — the runs of
+ *               a full-size batch on a small one, never a run no batch could get.  Same bits (the overlap-add runs in ascending
+ *               frame order however the frames are cut into runs).  Read back with goofer_counter "walk_run_*".
  *   "prof_only" s >= 0: goofer_profile_begin .. end record the events of stage s only; -1 (default): every stage     */
 int goofer_set_option(goofer_ctx *ctx, const char *name, int value);
 

@@ -597,6 +597,91 @@ def tiny_batch(geo):
     return notes
 
 
+# ---------------------------------------------------------------------------------------------
+# long runs: a batch for tests/test_gpu_walker_runs.py (option "walk_run") and what a partition into runs must cover on it
+# ---------------------------------------------------------------------------------------------
+# Frames per note, in batch order: notes of 1..5 frames, forty one-frame notes in a row, notes of 61 / 64 / 65 / 67, 127 .. 130,
+# 257 and 307 frames around the 64-frame record block and the runs 61, 62, 64, 65, 95, 128 and 256, and five fillers.  The ORDER
+# is the result of a search for run_coverage() to hold at every one of those runs (halo 3; run 256 also at halo 21) and is
+# asserted by tests/test_synth_ref.py: a change here that loses a condition fails there, without a GPU.
+LONG_FRAMES = (64, 25, 5, 25, 4, 130, 257, 3, 29) + (1,) * 40 + (27, 9, 127, 23, 65, 61, 129, 12, 67, 1, 2, 128, 3, 307, 4, 30, 35, 17, 25)
+# (halo 3 for hop == n_fft / 4; 21 at n_fft 2048 with hop 96, whose floor is 168 frames)
+LONG_RUNS = ((61, 3), (62, 3), (64, 3), (65, 3), (95, 3), (128, 3), (256, 3), (256, 21))
+
+
+def run_coverage(frame_off, run, halo, blocks):
+    """What the partition of a batch's frame axis into runs of ``run`` frames reaches.  A wave owns the frames [f0, f1) of a run,
+    starts ``min(t0, halo)`` frames earlier (t0: f0's index in its note) at fs, and — ``blocks``: the two stem walkers of
+    csrc/stems.hip — holds the frame records of [fs + 64 j, fs + 64 j + 64).  {condition: holds}:
+      t0=0 / 1 / 2 / 3 / >halo   a run behind the first starts at that frame of a note
+      ends_last, ends_last-1     a run in front of the last ends on a note's last frame (whose owner flushes the trailing hops) /
+                                 on its last but one
+      3_notes, 3_runs            a run holds three whole notes; a note spans three runs
+      refill_inside, refill_first   (blocks, run + halo > 64) frame fs + 64 of a run, inside the run, is a later frame of its note /
+                                 in another run the first frame of a note
+      final_block                (blocks) the last run's last record block reaches past the batch's last frame"""
+    f_off = np.asarray(frame_off, dtype=np.int64)
+    total = int(f_off[-1])
+    note_of = np.repeat(np.arange(f_off.size - 1), np.diff(f_off))
+    t_of = np.arange(total) - f_off[note_of]
+    T_of = np.diff(f_off)[note_of]
+    c = {k: False for k in ("t0=0", "t0=1", "t0=2", "t0=3", "t0>halo", "ends_last", "ends_last-1", "3_notes", "3_runs")}
+    if blocks:
+        c["final_block"] = False
+        if run + halo > 64:
+            c["refill_inside"] = c["refill_first"] = False
+    starts = list(range(0, total, run))
+    for f0 in starts:
+        f1 = min(f0 + run, total)
+        t0 = int(t_of[f0])
+        fs = f0 - min(t0, halo)
+        if f0 > 0:
+            for k in (0, 1, 2, 3):
+                c["t0=%d" % k] |= t0 == k
+            c["t0>halo"] |= t0 > halo
+        if f1 < total:
+            c["ends_last"] |= bool(t_of[f1 - 1] == T_of[f1 - 1] - 1)
+            c["ends_last-1"] |= bool(t_of[f1 - 1] == T_of[f1 - 1] - 2)
+        whole = np.count_nonzero((f_off[:-1] >= f0) & (f_off[1:] <= f1) & (np.diff(f_off) > 0))
+        c["3_notes"] |= whole >= 3
+        if blocks and run + halo > 64 and fs + 64 < f1:
+            c["refill_inside"] |= bool(t_of[fs + 64] > 0)
+            c["refill_first"] |= bool(t_of[fs + 64] == 0)
+        if blocks and f1 == total:
+            last = fs + 64 * ((total - 1 - fs) // 64)
+            c["final_block"] = last + 64 > total
+    first_run, last_run = f_off[:-1] // run, (f_off[1:] - 1) // run
+    c["3_runs"] = bool(np.any(last_run - first_run >= 2))
+    return c
+
+
+def long_batch(geo):
+    """The notes of LONG_FRAMES (transition sigma 100, like main_batch): sample counts that leave 0, 1, hop / 2 and hop - 1
+    samples behind a note's last hop; the long notes cycle through the masks one / step / zero / blocks — flat hops and skipped
+    transforms inside long runs — and alternate between formant shifts (warped envelope rows) and none (the source rows)."""
+    sr, n_fft, hop = geo
+    s = 4000 * n_fft + hop
+    rows = ["T", "T-1", "T+2", "1"]
+    notes, longs = [], 0
+    for k, T in enumerate(LONG_FRAMES):
+        rest = (0, 1, hop // 2, hop - 1)[k % 4]
+        n = max(1, (T - 1) * hop + rest)
+        kw, formants = {}, None
+        if T < 40:
+            mask = ("random", "one", "zero", "blocks")[k % 4]
+        else:
+            mask = ("one", lambda i, n, k=k: i >= (n // 3 if k % 2 else 2 * n // 3) + 5, "zero", "blocks")[longs % 4]
+            if longs % 2 == 0:
+                kw, formants = {"F%d_shift" % (1 + longs % 4): (0.8, 1.3)[(longs // 2) % 2], "F2_shift": 1.2}, "plain"
+            if longs % 5 == 3:
+                kw = dict(kw, formant_shift=f32(1.1))
+            if longs == 4:
+                kw = dict(kw, apply_brightness=False)
+            longs += 1
+        notes.append(make_case(geo, s + k, n, "long%d_T%d" % (k, T), mask=mask, rows=rows[k % 4], kw=kw, formants=formants))
+    return notes
+
+
 def batches(geo):
     """{batch name: (transition sigma, notes)}"""
     return {"main": (100.0, main_batch(geo)), "sigma4": (4.0, sigma_batch(geo, 4)), "sigma2000": (2000.0, sigma_batch(geo, 2000)),

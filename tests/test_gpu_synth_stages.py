@@ -35,8 +35,11 @@ about 1 100 frames (main), 150-250 (the others), so frame_block splits it into m
 replay, the flush of a note's last hops by the wave that owns its last frame, runs that hold several whole notes: the seventy
 tiny ones).  run_length stays at its floor of 32 frames per wave (no batch here fills the device's wave slots), so with notes of
 up to 36 frames a run ends inside a note and the next one replays its halo; frame_block::load runs once per wave and its refill
-after 64 frames is NOT reached.  Runs longer than 64 frames (the refill), run lengths above the floor and the grid that fills the
-device a whole number of times stay with tests/test_gpu_fullsize.py.
+after 64 frames is NOT reached.  tests/test_gpu_walker_runs.py forces the runs of a full-size batch (option "walk_run": 61 to 128
+frames per wave, 256 for k_irfft_ola1) on a batch of under 2 000 frames with notes of up to 303 frames and judges them with this
+file's judge_notes(): the 64-frame record refill with its load_nyquist / mark_plain, the clamp of a block that reaches past the
+last frame, runs of several long notes and notes longer than a run.  What remains with tests/test_gpu_fullsize.py: the grid that
+fills the device a whole number of times (the automatic run above its floor) and offsets at the 2^31 scale.
 
 MEASURED on the MI355X: worst note per route and stage over the four batches, E_ref / e_gpu (ratio = (e_gpu - 2^-23) / E_ref, floored
 at 0).  Every stage holds the project's factor 3 — the largest ratio is 2.00 — so no factor was raised.  Left out of the figures, not
@@ -163,8 +166,9 @@ def _params(notes):
     return par
 
 
-def _run(ctx, geo, notes, sigma, views=True, profile=False):
-    """One goofer_synth_batch over ``notes``; the outputs and (views) the debug views as host arrays."""
+def _run(ctx, geo, notes, sigma, views=True, profile=False, seed=None):
+    """One goofer_synth_batch over ``notes``; the outputs and (views) the debug views as host arrays.  ``seed``: no phases are
+    injected, the noise walker draws its own (Philox) under this seed."""
     from goofer_amd.device import GooferError
     sr, n_fft, hop = geo
     nb = n_fft // 2 + 1
@@ -173,13 +177,13 @@ def _run(ctx, geo, notes, sigma, views=True, profile=False):
     env_len = [c["env"].shape[1] for c in notes]
     env = ctx.rows_from(np.concatenate([c["env"].T for c in notes]))
     forms = ctx.tensor(np.concatenate([SR.formant_rows(c).T for c in notes]).astype(F64))
-    phi = ctx.rows_from(np.concatenate([c["phi"].T for c in notes]))
+    phi = ctx.rows_from(np.concatenate([c["phi"].T for c in notes])) if seed is None else None
     if profile:
         ctx.profile_begin(1)
     try:
         out = ctx.synth_batch(env, env_len, ctx.tensor(np.concatenate([c["f0"] for c in notes])),
                               ctx.tensor(np.concatenate([c["mask"] for c in notes])), lens, _params(notes), formants=forms, phi=phi,
-                              transition_sigma=sigma)
+                              seed=seed or 0, transition_sigma=sigma)
         torch.cuda.synchronize()
     except RuntimeError as e:                                 # GooferError or torch's device error: nothing more is started on this GPU
         pytest.exit("goofer_synth_batch failed on the device: %r" % (e,), returncode=3)
@@ -296,6 +300,21 @@ def test_stages_against_the_float64_truth(ctx, route, batch):
     assert (d["frame_skip"] is not None and d["frame_skip"].size > 0) == has_skip
     assert int(d["f_off"][-1]) > 32 or batch != "main"
     tally = Tally("%s/%s" % (route, batch))
+    skipped = judge_notes(d, notes, geo, sigma, batch, kind, has_skip, tally)
+    tally.report()
+    if has_skip and batch == "main":
+        print("frame_skip: unvoiced %d  breath %d  neither %d of %d" % (skipped[1], skipped[2], skipped[0], int(d["f_off"][-1])))
+        assert skipped[1] > 0 and skipped[2] > 0 and skipped[0] > 0
+    assert not tally.bad, tally.bad[:12]
+
+
+def judge_notes(d, notes, geo, sigma, batch, kind, has_skip, tally):
+    """Every stage of every note of one _run() against the float64 truth, unit by unit, into ``tally``; asserts what has no
+    tolerance (f0, the pulse's and mask_short's own bounds, zero gains, zero tails, the frame_skip check).  ``batch`` names the
+    notes in the cache of the CPU runs.  Returns the frame_skip counts {1: unvoiced, 2: breath, 0: neither}.  Shared with
+    tests/test_gpu_walker_runs.py."""
+    sr, n_fft, hop = geo
+    radius = int(4.0 * max(1.0, sigma / SR.MASK_DS) + 0.5)
     s_off, f_off = d["s_off"], d["f_off"]
     skipped = {1: 0, 2: 0, 0: 0}
     for k, c in enumerate(notes):
@@ -362,11 +381,7 @@ def test_stages_against_the_float64_truth(ctx, route, batch):
                 skipped[1] += int(sk & 1 != 0)
                 skipped[2] += int(sk & 2 != 0)
                 skipped[0] += int(sk == 0)
-    tally.report()
-    if has_skip and batch == "main":
-        print("frame_skip: unvoiced %d  breath %d  neither %d of %d" % (skipped[1], skipped[2], skipped[0], int(f_off[-1])))
-        assert skipped[1] > 0 and skipped[2] > 0 and skipped[0] > 0
-    assert not tally.bad, tally.bad[:12]
+    return skipped
 
 
 def _zero_gain(notes, sigma):

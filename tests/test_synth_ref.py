@@ -116,6 +116,31 @@ def test_restatement_equals_oracle_on_the_gpu_matrix(geo):
     assert int(4.0 * (sigma / 4) + 0.5) == 2000
 
 
+def test_long_batch_covers_every_forced_run():
+    """synth_ref.long_batch (tests/test_gpu_walker_runs.py): its frame counts are LONG_FRAMES at every geometry that test uses, and
+    every condition of run_coverage holds at every run and halo it forces — with and without the stem walkers' record blocks."""
+    for geo in ((44100, 1024, 256), (22050, 512, 128), (44100, 2048, 512), (96000, 2048, 96)):
+        notes = SR.long_batch(geo)
+        assert [1 + c["n"] // geo[2] for c in notes] == list(SR.LONG_FRAMES)
+    assert sum(SR.LONG_FRAMES) < 2000 and SR.LONG_FRAMES.count(1) >= 41
+    assert {1, 2, 3, 4, 5, 61, 64, 65, 67, 127, 128, 129, 130, 257} <= set(SR.LONG_FRAMES) and max(SR.LONG_FRAMES) >= 300
+    f_off = np.concatenate([[0], np.cumsum(SR.LONG_FRAMES)])
+    for run, halo in SR.LONG_RUNS:
+        cov = SR.run_coverage(f_off, run, halo, blocks=halo == 3 and run <= 128)
+        assert all(cov.values()), (run, halo, [k for k, v in cov.items() if not v])
+        assert ("refill_inside" in cov) == (halo == 3 and 61 < run <= 128)
+    # ... and the conditions can fail: one long note has no run of three notes, a batch of one-frame notes no note of three runs
+    assert not SR.run_coverage([0, 1000], 95, 3, True)["3_notes"]
+    assert not SR.run_coverage(np.arange(400), 95, 3, True)["3_runs"]
+    assert not SR.run_coverage([0, 189], 128, 3, True)["final_block"]           # the last run starts at fs = 125: its block ends with the batch
+
+
+def test_restatement_equals_oracle_on_the_long_batch():
+    """The long notes too (the main geometry; the 2048 geometries differ by the transform size, which the matrix above covers)."""
+    for case in SR.long_batch((44100, 1024, 256)):
+        _assert_equals_oracle(case, (44100, 1024, 256), 100.0, "long")
+
+
 @pytest.mark.parametrize("geo", SR.GEOMETRIES, ids=lambda g: "%d-%d-%d" % g)
 def test_print_reference_errors(geo):
     """The note-level E_ref of each stage, worst note of the main batch: oracle arithmetic / plain fp32 transform."""
