@@ -1070,6 +1070,32 @@ def limit_batch(signals, sr, ceiling=32767.0 / 32768.0, lookahead_ms=5.0, ctx=No
     return [y[plan.in_off[i]:plan.in_off[i + 1]] for i in range(plan.n)], peak.cpu().numpy(), gain.cpu().numpy()
 
 
+def loudness_batch(signals, sr, target=None, max_gain_db=20.0, ctx=None):
+    """Integrated loudness of many signals in one device pass (goofer_amd.loudness; goofer_loudness_measure): ``signals``, 1-D
+    arrays at ``sr`` (8000 to 192000 Hz), are measured after ITU-R BS.1770-4 for one channel and, with a ``target`` in LUFS,
+    each scaled to it, the gain capped at ``max_gain_db``.  Returns ``(ys, loud, gain, seg_energy)``: the scaled signals as a
+    list of fp32 arrays (None when ``target`` is None: measure only), ``loud`` float64 ``[n, 2]`` (integrated loudness and the
+    greatest momentary loudness, LUFS; -inf for a signal without a block above the gates), ``gain`` fp32 ``[n]`` (1 where
+    nothing was measured) and a list of float64 arrays, each signal's K-weighted energy per whole 100 ms segment
+    (``loudness.momentary`` makes the momentary-loudness curve of one).  This project's own definition (include/goofer_hip.h)."""
+    from . import loudness as LD
+    xs = [np.ascontiguousarray(s, dtype=np.float32).reshape(-1) for s in signals]
+    plan = LD.plan(sr, [len(s) for s in xs])
+    if target is not None:
+        target, max_gain_db = LD.parse((target, max_gain_db))
+    if not plan.n:
+        return (None if target is None else []), np.zeros((0, 2)), np.zeros(0, dtype=np.float32), []
+    c = ctx or default_context()
+    y, loud, gain, seg = c.loudness(c.tensor(np.concatenate(xs + [np.zeros(1, dtype=np.float32)])), None, plan, target, max_gain_db)
+    c.check()
+    seg = seg.cpu().numpy()
+    segs = [seg[plan.seg_off[i]:plan.seg_off[i + 1]] for i in range(plan.n)]
+    if y is not None:
+        y = y.cpu().numpy()
+        y = [y[plan.in_off[i]:plan.in_off[i + 1]] for i in range(plan.n)]
+    return y, loud.cpu().numpy(), gain.cpu().numpy(), segs
+
+
 def synthesize(env_spec, f0_interp, voicing_mask, y, sr, n_fft=1024, hop_length=256, glottal_smoothing=False,
                stretch_factor=1.0, start_sec=None, end_sec=None, apply_brightness=True, normalize=1.0, uv_strength=0.75,
                breath_strength=0.1, noise_transition_smoothness=100, pitch_shift=1.0, formant_shift=1.0, f0_jitter=False,

@@ -98,6 +98,14 @@ int launch_volume_jitter(goofer_ctx *ctx, float *harm, float *bre, const double 
 int launch_limit(goofer_ctx *ctx, const float *x, const int64_t *in_off, int n, int W, const float *taps, float c, const int32_t *tiles,
                  int64_t n_tiles, float *out, float *peak_in, float *min_gain, hipStream_t st);
 
+// loudness.hip
+int launch_loudness_measure(goofer_ctx *ctx, const float *x, const int64_t *in_off, int n, int S, const double *coef, const double *mats,
+                            const int64_t *seg_off, const int32_t *tiles, int64_t n_tiles, double target, double max_gain_db,
+                            double *seg_energy, double *loud, float *gain, double *ends, double *starts, double *partial,
+                            int32_t *first_tile, hipStream_t st);
+int launch_loudness_apply(goofer_ctx *ctx, const float *x, const int64_t *in_off, int n, int64_t total, const float *gain, float *out,
+                          hipStream_t st);
+
 // noise.hip
 int launch_normal_fill(goofer_ctx *ctx, uint64_t seed, const goofer_note_params *params, const int64_t *sample_off, int n_notes,
                        int64_t total, int tag, const unsigned char *note_on, const double *growl_scale, double *out, hipStream_t st);

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import functools
+import math
 
 import numpy as np
 import torch
@@ -292,6 +293,57 @@ class Context:
                                               C.c_float(plan.ceiling), _ptr(tiles) if total else None, plan.n_tiles,
                                               _ptr(out) if total else None, _ptr(peak_in), _ptr(min_gain), self._stream()))
         return out, peak_in, min_gain
+
+    def loudness(self, x, d_off, plan, target=None, max_gain_db=20.0, out=None):
+        """The integrated loudness of the signals of a ragged batch measured on the device and, with a ``target`` in LUFS, the
+        signals scaled to it (goofer_loudness_measure, goofer_loudness_apply; the definition: include/goofer_hip.h, restated in
+        tests/loudness_ref.py).  ``x``: the signals' samples back to back, a contiguous fp32 device tensor; ``d_off``: their
+        int64 CSR offsets ``[n + 1]``, a device tensor, a host sequence (checked against the plan) or None for the plan's own;
+        ``plan``: a ``goofer_amd.loudness.LoudnessPlan`` for these lengths (shipped in one upload the first time it is used on
+        this device); ``target``: None measures only; ``max_gain_db``: the cap of the gain; ``out``: a contiguous fp32 device
+        tensor of ``plan.total`` samples, which may be ``x`` itself (default: a new one).  Returns ``(y, loud, gain,
+        seg_energy)``, device tensors: ``y`` the scaled signals (None when measuring only), ``loud`` float64 ``[n, 2]``
+        (integrated loudness and the greatest momentary loudness, LUFS), ``gain`` fp32 ``[n]`` (1 when measuring only; it goes
+        from the measurement to the scaling without visiting the host) and ``seg_energy`` float64 ``[plan.n_segments]``, the
+        K-weighted energy of every whole 100 ms segment (signal i: ``plan.seg_off[i]:plan.seg_off[i + 1]``).  Asynchronous on
+        the current stream."""
+        from . import loudness as LD
+        n, total = plan.n, plan.total
+        cap = float(max_gain_db)
+        if target is not None:
+            target, cap = LD.parse((target, cap))
+        elif not 0.0 <= cap <= LD.MAX_GAIN_DB_CAP:
+            raise ValueError("loudness: max_gain_db lies in [0, %g]" % LD.MAX_GAIN_DB_CAP)
+        d_in, d_seg, coef, mats, tiles = plan.device_tables(self)
+        if isinstance(d_off, torch.Tensor):
+            if d_off.dtype != torch.int64 or not d_off.is_contiguous() or d_off.numel() != n + 1:
+                raise ValueError("loudness: d_off is one contiguous int64 CSR of the plan's %d signals" % n)
+            d_in = d_off
+        elif d_off is not None and not np.array_equal(np.asarray(d_off, dtype=np.int64), plan.in_off):
+            raise ValueError("loudness: d_off is not the CSR the plan was made for")
+        if x.dtype != torch.float32 or not x.is_contiguous() or x.numel() < total:
+            raise ValueError("loudness: x must be a contiguous float32 tensor of the plan's %d samples" % total)
+        if out is not None and (target is None or out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != total):
+            raise ValueError("loudness: out, with a target only, must be a contiguous float32 tensor of the %d samples" % total)
+        seg_buf = torch.empty(max(plan.n_segments, 1), dtype=torch.float64, device=self.device)     # (never a null pointer)
+        seg = seg_buf[:plan.n_segments]
+        loud = torch.empty((n, 2), dtype=torch.float64, device=self.device)
+        gain = torch.empty(n, dtype=torch.float32, device=self.device)
+        y = None
+        if target is not None:
+            y = torch.empty(total, dtype=torch.float32, device=self.device) if out is None else out
+        if n:
+            args = (self.h, _ptr(x) if total else None, _ptr(d_in), n, total, plan.S, _ptr(coef), _ptr(mats), _ptr(d_seg),
+                    _ptr(tiles) if total else None, plan.n_tiles, math.nan if target is None else target, cap,
+                    _ptr(seg_buf), _ptr(loud), _ptr(gain))
+            size = C.c_int64(0)
+            self._check(self.lib.goofer_loudness_measure(*args, None, C.byref(size), None))
+            scratch = torch.empty(max(int(size.value), 256), dtype=torch.uint8, device=self.device)
+            size = C.c_int64(scratch.numel())
+            self._check(self.lib.goofer_loudness_measure(*args, _ptr(scratch), C.byref(size), self._stream()))
+            if y is not None and total:
+                self._check(self.lib.goofer_loudness_apply(self.h, _ptr(x), _ptr(d_in), n, total, _ptr(gain), _ptr(y), self._stream()))
+        return y, loud, gain, seg
 
     def normal_fill(self, seed: int, params, lengths_or_offsets, tag: int, note_on=None, growl_scale=None, out=None):
         """float64 standard normals of stream ``tag`` (0 f0 jitter, 1 / 2 harmonic / breath volume jitter, 3 sub-harmonic f0

@@ -6,7 +6,7 @@ definition is this project's own (``include/goofer_hip.h``, goofer_phrase_note; 
 ``goofer_phrase_mix``.  Here: wavtool's arguments turned into note records (host, float64), the records checked and the
 cover table made by the library's planner (``goofer_host_phrase_plan``), and a command line,
 
-    python -m goofer_amd.phrase [--rate HZ] [--limit [DBFS]] job.txt out.wav
+    python -m goofer_amd.phrase [--rate HZ] [--loudness LUFS] [--limit [DBFS]] job.txt out.wav
 
 ``job.txt`` holds one line per note, the 13 resampler arguments, ``|``, then wavtool's ``stp length p1 p2 p3 v1 v2 v3 v4 [ovr
 [p4 [p5 v5]]]``::
@@ -18,7 +18,9 @@ cover table made by the library's planner (``goofer_host_phrase_plan``), and a c
 lines and lines that start with ``#`` are skipped.  ``--rate HZ`` converts the mixed track from the voicebank's rate to HZ on
 the device (goofer_amd.rate) before it becomes int16; the wav's header carries HZ.  ``--limit [DBFS]`` runs the look-ahead peak
 limiter (goofer_amd.limit) over the track at the rate of the wav, with the ceiling DBFS decibels relative to full scale (bare:
-32767/32768), and reports the track's peak in front of it and its greatest gain reduction on stderr.
+32767/32768), and reports the track's peak in front of it and its greatest gain reduction on stderr.  ``--loudness LUFS``
+measures the track's integrated loudness after BS.1770 (goofer_amd.loudness) and scales the track to LUFS, in front of the
+limiter, the gain capped at 20 dB; the measured loudness and the gain go to stderr too.
 ``Renderer.render_phrase`` is the same for (Source, Request) jobs.
 """
 from __future__ import annotations
@@ -242,12 +244,13 @@ def read_job(path):
     return out
 
 
-def render_job(path, out_wav, renderer=None, seed=None, tracker=None, pcm16=True, out_sr=None, limit=None, stats=None):
+def render_job(path, out_wav, renderer=None, seed=None, tracker=None, pcm16=True, out_sr=None, limit=None, stats=None, loudness=None):
     """``python -m goofer_amd.phrase``: the notes of a job file rendered as one batch and written as one wav.  ``in_file`` is
     resolved like the resampler front end does: ``<stem>_features.goofy`` beside the wav, analysed and cached first when it is
     missing (``trackers.ensure_features_batch``; the tracker: the argument, else ``$GOOFER_TRACKER``).  ``out_sr``: the rate of
     the wav (``render_phrase``'s; None: the voicebank's).  ``limit``: ``render_phrase``'s (None: no limiter); with it ``stats``,
-    a dict, receives the limiter's ``peak_in`` and ``min_gain``."""
+    a dict, receives the limiter's ``peak_in`` and ``min_gain``.  ``loudness``: ``render_phrase``'s (None: the track's level is
+    left as it is); with it ``stats`` receives ``lufs_in``, ``momentary_max`` and ``gain``."""
     from pathlib import Path
     from . import core, trackers
     from . import sampler as S
@@ -270,10 +273,11 @@ def render_job(path, out_wav, renderer=None, seed=None, tracker=None, pcm16=True
         raise ValueError(f"{path}: no note")
     if seed is None:
         seed = int(np.random.SeedSequence().generate_state(1, dtype=np.uint64)[0])
-    if limit is None:
+    if limit is None and loudness is None:
         track = renderer.render_phrase(jobs, [e for _, e in lines], seed=seed, pcm16=pcm16, out_sr=out_sr)
     else:
-        track, st = renderer.render_phrase(jobs, [e for _, e in lines], seed=seed, pcm16=pcm16, out_sr=out_sr, limit=limit, return_stats=True)
+        track, st = renderer.render_phrase(jobs, [e for _, e in lines], seed=seed, pcm16=pcm16, out_sr=out_sr, limit=limit, return_stats=True,
+                                           loudness=loudness)
         if stats is not None:
             stats.update(st)
     write_wav(out_wav, track, jobs[0][0].sr if out_sr is None else int(out_sr))
@@ -284,13 +288,19 @@ def main(argv=None) -> int:
     import logging
     logging.basicConfig(format="%(message)s", level=logging.INFO)
     argv = list(sys.argv[1:] if argv is None else argv)
-    out_sr = limit = None
-    while len(argv) > 2 and argv[0] in ("--rate", "--limit"):
+    out_sr = limit = loudness = None
+    while len(argv) > 2 and argv[0] in ("--rate", "--limit", "--loudness"):
         if argv[0] == "--rate":
             try:
                 out_sr = int(argv[1])
             except ValueError:
                 break                   # (more than two arguments left: the usage line)
+            argv = argv[2:]
+        elif argv[0] == "--loudness":
+            try:
+                loudness = float(argv[1])
+            except ValueError:
+                break
             argv = argv[2:]
         else:
             from . import limit as LM
@@ -301,14 +311,18 @@ def main(argv=None) -> int:
                 limit = LM.CEILING
                 argv = argv[1:]
     if len(argv) != 2:
-        logging.error("Usage:\n  python -m goofer_amd.phrase [--rate HZ] [--limit [DBFS]] job.txt out.wav")
+        logging.error("Usage:\n  python -m goofer_amd.phrase [--rate HZ] [--loudness LUFS] [--limit [DBFS]] job.txt out.wav")
         return 1
     stats = {}
     try:
-        track = render_job(argv[0], argv[1], out_sr=out_sr, limit=limit, stats=stats)
+        track = render_job(argv[0], argv[1], out_sr=out_sr, limit=limit, stats=stats, loudness=loudness)
     except Exception:                   # noqa: BLE001
         logging.exception("Failed to render")
         return 1
+    if loudness is not None:
+        print("Loudness: measured %.2f LUFS (momentary max %.2f), gain %.2f dB (target %.2f LUFS)"
+              % (stats["lufs_in"], stats["momentary_max"], 20.0 * math.log10(stats["gain"]) if stats["gain"] > 0.0 else -math.inf, loudness),
+              file=sys.stderr)
     if limit is not None:
         from . import limit as LM
         peak = stats["peak_in"]

@@ -435,7 +435,8 @@ class Renderer:
             raise ValueError(f"{who}: out_sr is a whole number of Hz")
         return None if int(out_sr) in rates else int(out_sr)
 
-    def render(self, jobs, seed: int = 0, phi_seeds=None, return_parts: bool = False, noise_seeds=None, out_sr=None, limit=None):
+    def render(self, jobs, seed: int = 0, phi_seeds=None, return_parts: bool = False, noise_seeds=None, out_sr=None, limit=None,
+               loudness=None):
         """jobs: list of (Source, Request).  Returns a list of fp32 arrays (the mix the reference writes to
         out.wav); with ``return_parts`` also a dict of device-side intermediates for tests.
         ``phi_seeds``: per-note seeds for INJECTED phases (parity with a seeded reference run: numpy's stream of each seed,
@@ -449,12 +450,20 @@ class Renderer:
         the whole batch in one goofer_rate_convert); None, or the sources' own rate: no conversion.
         ``limit``: None, a ceiling in (0, 1] or a ``(ceiling, lookahead_ms)`` pair: every note brought under the ceiling by the
         look-ahead peak limiter on the device (goofer_amd.limit; the whole batch in one goofer_limit), after the conversion, at
-        the rate the notes are returned at."""
+        the rate the notes are returned at.
+        ``loudness``: None, a target in LUFS or a ``(target, max_gain_db)`` pair: every note measured after BS.1770 and scaled
+        to the target on the device (goofer_amd.loudness; the whole batch in one pass), after the conversion and in front of
+        the limiter."""
         if not jobs:
             return []
         to_sr = self._out_rate(jobs, out_sr, "render")
         if limit is not None and len({int(src.sr) for src, _ in jobs}) != 1:
             raise ValueError("render: limit takes notes that share one sample rate")
+        if loudness is not None:
+            from . import loudness as LD
+            loudness = LD.parse(loudness)
+            if len({int(src.sr) for src, _ in jobs}) != 1:
+                raise ValueError("render: loudness takes notes that share one sample rate")
         prep = self.prepare(jobs, phi_seeds=phi_seeds, trim_rows=not return_parts, noise_seeds=noise_seeds)   # tests look at the whole assembled envelope
         out = self.run(prep, seed=seed, keep_stems=return_parts)
         mix, offs = out["mix"], prep["sample_off"]
@@ -462,6 +471,9 @@ class Renderer:
             from . import rate as RT
             plan = RT.plan(jobs[0][0].sr, to_sr, np.diff(np.asarray(offs, dtype=np.int64)))
             mix, offs = self.ctx.rate_convert(mix, prep["offsets"]["d_s"], plan), plan.out_off
+        if loudness is not None:
+            dplan = LD.plan(jobs[0][0].sr if to_sr is None else to_sr, np.diff(np.asarray(offs, dtype=np.int64)))
+            mix = self.ctx.loudness(mix, None, dplan, *loudness)[0]
         if limit is not None:
             from . import limit as LM
             lplan = LM.plan(jobs[0][0].sr if to_sr is None else to_sr, np.diff(np.asarray(offs, dtype=np.int64)), *LM.parse(limit))
@@ -476,7 +488,7 @@ class Renderer:
         return res
 
     def render_phrase(self, jobs, entries, seed: int = 0, phi_seeds=None, noise_seeds=None, pcm16: bool = False, out_sr=None, limit=None,
-                      return_stats: bool = False):
+                      return_stats: bool = False, loudness=None):
         """The notes of ``jobs`` rendered as one batch and assembled into one track on the device: what a ``wavtool`` does with
         the notes ``render`` returns, without bringing them home first (goofer_amd.phrase; goofer_phrase_mix).  ``entries``:
         the phrase in order, one ``phrase.Entry`` (or its wavtool argument string ``stp length p1 p2 p3 v1 v2 v3 v4 [ovr [p4
@@ -486,11 +498,18 @@ class Renderer:
         mixed track converted from the notes' rate to this one on the device (goofer_amd.rate) — mix, convert, then int16;
         None, or the notes' own rate: no conversion.  ``limit``: None, a ceiling in (0, 1] or a ``(ceiling, lookahead_ms)`` pair:
         the track brought under the ceiling by the look-ahead peak limiter on the device (goofer_amd.limit) — mix, convert,
-        limit at the output rate, then int16.  ``return_stats`` (with ``limit``): also a dict with the track's ``peak_in``, its
-        greatest ``|x|`` in front of the limiter, and ``min_gain``, the smallest gain the limiter applied (Python floats)."""
+        limit at the output rate, then int16.  ``loudness``: None, a target in LUFS or a ``(target, max_gain_db)`` pair: the
+        track measured after BS.1770 and scaled to the target on the device (goofer_amd.loudness) — mix, convert, loudness,
+        limit, then int16.  ``return_stats`` (with ``limit`` or ``loudness``): also a dict; with ``limit`` the track's
+        ``peak_in``, its greatest ``|x|`` in front of the limiter, and ``min_gain``, the smallest gain the limiter applied; with
+        ``loudness`` ``lufs_in``, the track's integrated loudness in front of the scaling, ``momentary_max``, its greatest
+        momentary loudness, and ``gain``, the factor it was scaled by (Python floats)."""
         from . import phrase as P
-        if return_stats and limit is None:
-            raise ValueError("render_phrase: return_stats reports the limiter's statistics and needs limit")
+        if return_stats and limit is None and loudness is None:
+            raise ValueError("render_phrase: return_stats reports the limiter's and the loudness stage's statistics and needs limit or loudness")
+        if loudness is not None:
+            from . import loudness as LD
+            loudness = LD.parse(loudness)
         entries = [e if isinstance(e, P.Entry) else P.Entry.parse(e) for e in entries]
         if not jobs:
             raise ValueError("render_phrase: a phrase without a note has no sample rate")
@@ -504,7 +523,10 @@ class Renderer:
         if to_sr is not None:
             from . import rate as RT
             track = self.ctx.rate_convert(track, None, RT.plan(jobs[0][0].sr, to_sr, [plan.total_out]))
-        stats = None
+        stats = lstats = None
+        if loudness is not None:
+            dplan = LD.plan(jobs[0][0].sr if to_sr is None else to_sr, [track.numel()])
+            track, *lstats = self.ctx.loudness(track, None, dplan, *loudness)
         if limit is not None:
             from . import limit as LM
             lplan = LM.plan(jobs[0][0].sr if to_sr is None else to_sr, [track.numel()], *LM.parse(limit))
@@ -513,7 +535,13 @@ class Renderer:
             track = self.ctx.pcm16(track)
         self.ctx.check()                                   # synchronises; raises if the device flagged a note
         if return_stats:
-            return track.cpu().numpy(), {"peak_in": float(stats[0].cpu()[0]), "min_gain": float(stats[1].cpu()[0])}
+            res = {}
+            if stats is not None:
+                res.update({"peak_in": float(stats[0].cpu()[0]), "min_gain": float(stats[1].cpu()[0])})
+            if lstats is not None:
+                loud = lstats[0].cpu()
+                res.update({"lufs_in": float(loud[0, 0]), "momentary_max": float(loud[0, 1]), "gain": float(lstats[1].cpu()[0])})
+            return track.cpu().numpy(), res
         return track.cpu().numpy()
 
     def assemble(self, prep):

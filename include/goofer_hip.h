@@ -808,7 +808,8 @@ int goofer_rate_convert(goofer_ctx *ctx, const float *x, const int64_t *in_off, 
  * goofer_pcm16 of a limited track gives what an unclamped round would give.  Identity: where a <= c on all of [i - 2W, i + 2W]
  * every d is +0, acc is +0 and g is exactly 1, so a signal that never exceeds c comes back bit for bit — which is why the sum
  * is over the deficiency d and not over m.  Non-finite samples follow the arithmetic as written (a NaN asks for gain 1 and
- * stays NaN).  True-peak (oversampled) detection, loudness metering and normalisation are not part of this. */
+ * stays NaN).  Loudness metering and normalisation live in goofer_loudness_* below, in front of this stage; true-peak
+ * (oversampled) detection does not exist. */
 #define GOOFER_LIMIT_MAX_LOOK 1024
 #define GOOFER_LIMIT_TILE 4096
 #define GOOFER_LIMIT_CEILING (32767.0f / 32768.0f)
@@ -837,6 +838,89 @@ int goofer_host_limit_plan(int sr, double look_ms, float c, const int64_t *in_of
  * 8-byte aligned, or an out that overlaps x. */
 int goofer_limit(goofer_ctx *ctx, const float *x, const int64_t *in_off, int n, int64_t total, int W, const float *taps, float c,
                  const int32_t *tiles, int64_t n_tiles, float *out, float *peak_in, float *min_gain, void *stream);
+
+/* ---- loudness metering and normalisation ------------------------------------------------------------------------------------
+ * The limiter watches peaks; this stage watches level: a signal's integrated loudness measured on the device and the signal
+ * scaled to a target, in front of the limiter (mix, rate conversion, loudness, limiter, int16).  The definition is this
+ * project's own, after ITU-R BS.1770-4 for one channel (restated in numpy by tests/loudness_ref.py).  A signal gets the same
+ * bits alone as at any position in any batch, on every run: no floating-point atomics.
+ *
+ * Parameters.  sr: an integer, GOOFER_LOUDNESS_MIN_SR <= sr <= GOOFER_LOUDNESS_MAX_SR.  target: LUFS, finite, or NaN for
+ * "measure only"; max_gain_db in [0, GOOFER_LOUDNESS_MAX_GAIN_DB_CAP] (default GOOFER_LOUDNESS_MAX_GAIN_DB).  Anything else is
+ * refused (GOOFER_EINVAL).
+ *
+ * K-weighting (host, float64): two biquads from the analogue prototypes by the bilinear transform.
+ *   Shelf: f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196; K = tan(pi f0 / sr), Vh = 10^(G/20),
+ *     Vb = Vh^0.4996667741545416, a0 = 1 + K/Q + K^2;
+ *     b = [(Vh + Vb K/Q + K^2), 2 (K^2 - Vh), (Vh - Vb K/Q + K^2)] / a0,  a = [2 (K^2 - 1), (1 - K/Q + K^2)] / a0
+ *   High-pass: f0 = 38.13547087602444, Q = 0.5003270373238773; K = tan(pi f0 / sr), a0 = 1 + K/Q + K^2;
+ *     b = [1, -2, 1],  a = [2 (K^2 - 1), (1 - K/Q + K^2)] / a0
+ * At 48 kHz these are the standard's table within 9e-16.  coef[10] = shelf b0 b1 b2 a1 a2, high-pass b0 b1 b2 a1 a2.
+ *
+ * Per signal x[0 .. n), zero history in front of every signal, all recurrences and sums in float64 (an fp32 state misses the
+ * tolerance below by a factor of 200: the high-pass has poles of radius 0.9950 at 48 kHz):
+ *   u[i] = b0 x[i] + b1 x[i-1] + b2 x[i-2] - a1 u[i-1] - a2 u[i-2]       (shelf), then v from u likewise (high-pass)
+ *   S = floor(sr / 10 + 0.5);  E[k] = sum v[i]^2 over kS <= i < (k+1)S  for k < Kn = floor(n / S)   (a trailing partial
+ *     segment is not counted)
+ *   z[j] = (E[j] + E[j+1] + E[j+2] + E[j+3]) / (4S)  for j < max(0, Kn - 3)          (400 ms blocks, 75 % overlap)
+ *   absolute gate: z[j] > 10^((-70 + 0.691) / 10);  relative gate: z[j] > 0.1 * mean of z over the absolutely gated blocks
+ *     (both in the linear domain: no logarithm decides a gate)
+ *   L = -0.691 + 10 log10(mean of z over the blocks passing both gates), -inf when none passes
+ *   momentary_max = -0.691 + 10 log10(max_j z[j]), -inf without a block
+ *   g = fp32(min(10^((target - L) / 20), 10^(max_gain_db / 20))); exactly 1.0f when L is -inf or when measuring only
+ *   y[i] = x[i] * g, one rounded fp32 multiply
+ * The sums may be taken in any order.  A NaN sample makes E NaN from its segment on; where any z[j] is NaN, L, momentary_max and
+ * g are NaN (a NaN is not dropped by a gate).  An infinite sample leaves E, L, momentary_max and g of its signal unspecified from
+ * its segment on (non-finite or not: carrying the state by matrix powers multiplies their structural zeros by it, which the
+ * recurrence as written does not).  Either way the other signals of the batch are untouched.
+ *
+ * The recurrence is of order 4 with state s = (u[i-1], u[i-2], v[i-1], v[i-2]); with A its 4x4 transition matrix for x = 0, a
+ * run of m samples from state s ends in A^m s + (the end state of the same run from s = 0).  The kernels cut a signal into
+ * tiles of GOOFER_LOUDNESS_TILE samples and a tile into runs of GOOFER_LOUDNESS_SPT, and carry the state across them with
+ * mats[k] = A^(GOOFER_LOUDNESS_SPT * 2^k), k < GOOFER_LOUDNESS_MATS (row-major, float64; by repeated squaring on the host in long
+ * double, rounded once: squaring in float64 costs the tolerance at 192 kHz).
+ * Tolerance: |E[k] - E_longdouble[k]| <= 2^-26 max_k E_longdouble[k] per signal, which keeps g within one fp32 ulp. */
+#define GOOFER_LOUDNESS_MIN_SR 8000
+#define GOOFER_LOUDNESS_MAX_SR 192000
+#define GOOFER_LOUDNESS_MAX_GAIN_DB 20.0
+#define GOOFER_LOUDNESS_MAX_GAIN_DB_CAP 60.0
+#define GOOFER_LOUDNESS_TILE 4096
+#define GOOFER_LOUDNESS_SPT 16
+#define GOOFER_LOUDNESS_MATS 20      /* A^16 .. A^(16 * 2^19): 8 for the 256 runs of a tile, A^4096 for a tile, 8 from A^(4096 * 16) on for 256 runs of 16 tiles */
+#define GOOFER_LOUDNESS_SLOTS 8      /* segments a tile can touch: S >= 800 */
+
+/* Host side (no device, no handle): for n signals whose samples lie back to back with the CSR in_off[n + 1] (non-decreasing),
+ * S, coef[10], mats[GOOFER_LOUDNESS_MATS][16], the segment CSR seg_off[n + 1] (signal i has floor(len_i / S) segments) and the
+ * tile table: need[0] = sum_i ceil(len_i / GOOFER_LOUDNESS_TILE) pairs of int32 (signal, tile of that signal), ascending.
+ * Returns 0 with everything written; 1 when tiles_cap (in pairs) < need[0] (only *S and need are valid: grow, call again);
+ * GOOFER_EINVAL for an sr out of range, a null argument (in_off may be null when n == 0, tiles when tiles_cap == 0), a negative
+ * count or capacity, offsets that decrease, a signal of 2^31 samples or more. */
+int goofer_host_loudness_plan(int sr, const int64_t *in_off, int n, int *S, double *coef, double *mats, int64_t *seg_off,
+                              int32_t *tiles, int64_t tiles_cap, int64_t *need);
+
+/* The measurement (loudness.hip).  x, in_off ([n + 1]), coef, mats, seg_off ([n + 1]) and tiles are device arrays of the
+ * caller, S and the tables those of goofer_host_loudness_plan for the same in_off, total = in_off[n].  Outputs, device arrays:
+ * seg_energy, float64 [seg_off[n]], the E[k] (the momentary-loudness curve follows from them); loud, float64 [n][2]: L and
+ * momentary_max; gain, fp32 [n]: g.  Four launches in stream order, and no workgroup ever waits for another: (A) a workgroup
+ * per tile runs its samples from a zero state and scans the runs' end states into the tile's; (B) a workgroup per signal scans the
+ * tiles' end states, 4096 at a time, into the tiles' start states; (C) every tile again, from its start state, with v^2 summed
+ * per segment into a slot of its own per (tile, segment); (D) a workgroup per signal sums the slots in a fixed order, forms the
+ * blocks, gates them and writes L, momentary_max and g.  x is read twice and nothing of the signal's size is written.
+ * Scratch by the caller-scratch protocol: with scratch NULL the size goes to *scratch_bytes and nothing runs.  Asynchronous on
+ * `stream`.  n == 0: nothing is launched.  GOOFER_EINVAL, with nothing launched, for a null pointer (all arrays may be null when
+ * n == 0; x and tiles when total == 0), a negative count, S, target or max_gain_db outside the definition's range, an n_tiles
+ * that is not between ceil(total / GOOFER_LOUDNESS_TILE) and that plus n, x or gain not 4-byte aligned, the others not 8-byte
+ * aligned, or a scratch block that is too short. */
+int goofer_loudness_measure(goofer_ctx *ctx, const float *x, const int64_t *in_off, int n, int64_t total, int S, const double *coef,
+                            const double *mats, const int64_t *seg_off, const int32_t *tiles, int64_t n_tiles, double target,
+                            double max_gain_db, double *seg_energy, double *loud, float *gain, void *scratch, int64_t *scratch_bytes,
+                            void *stream);
+
+/* out[i] = x[i] * gain[signal of i] over the ragged batch: one rounded fp32 multiply, every sample stored once.  gain is the
+ * device array goofer_loudness_measure wrote: it never visits the host.  out == x is allowed (there is no halo); any other
+ * overlap is refused.  Asynchronous on `stream`; n == 0 or total == 0: nothing is launched. */
+int goofer_loudness_apply(goofer_ctx *ctx, const float *x, const int64_t *in_off, int n, int64_t total, const float *gain, float *out,
+                          void *stream);
 
 /* ---- measurement / test hooks --------------------------------------------------------------- */
 
