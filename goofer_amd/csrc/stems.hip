@@ -905,6 +905,10 @@ __global__ __launch_bounds__(256, 3) void k_harm_stem(const float *__restrict__ 
 constexpr int FIN_THREADS = 1024;
 constexpr int FIN_KEEP = 12;              // float4 per stem and thread kept across the peak reduction
 
+// MIX_ONLY: the mix alone is stored (a mix_only batch: no stems, no rec).  Then nothing but the mix of a row is alive in the
+// second pass and the kernel holds its 96 kept registers without a spill (128 VGPRs, no scratch; with the stores of the stems and
+// of rec behind run-time flags the one kernel for both spilled four).  Same operations in the same order in both.
+template <bool MIX_ONLY>
 __global__ __launch_bounds__(FIN_THREADS) void k_note_finish(float *__restrict__ harm, float *__restrict__ uv, float *__restrict__ bre,
                                                              float *__restrict__ rec, float *__restrict__ mix,
                                                              const int64_t *__restrict__ sample_off,
@@ -1041,13 +1045,13 @@ __global__ __launch_bounds__(FIN_THREADS) void k_note_finish(float *__restrict__
                 one_kept(h.y, u.y, b.y, ho.y, uo.y, bo.y, ro.y, mo.y);
                 one_kept(h.z, u.z, b.z, ho.z, uo.z, bo.z, ro.z, mo.z);
                 one_kept(h.w, u.w, b.w, ho.w, uo.w, bo.w, ro.w, mo.w);
-                if (write_stems & 1) {
+                if (!MIX_ONLY && (write_stems & 1)) {
                     *reinterpret_cast<float4 *>(h_ + i) = ho;
                     *reinterpret_cast<float4 *>(u_ + i) = uo;
                     *reinterpret_cast<float4 *>(b_ + i) = bo;
                 }
-                if (rec) store_f4(rec + base + i, ro, (write_stems & 2) != 0);
-                if (mix) store_f4(mix + base + i, mo, (write_stems & 2) != 0);
+                if (!MIX_ONLY && rec) store_f4(rec + base + i, ro, (write_stems & 2) != 0);
+                if (MIX_ONLY || mix) store_f4(mix + base + i, mo, (write_stems & 2) != 0);
             }
             if (q % 2 == 1) asm volatile("" ::: "memory");
         }
@@ -1061,13 +1065,13 @@ __global__ __launch_bounds__(FIN_THREADS) void k_note_finish(float *__restrict__
             one(h.y, u.y, b.y, ho.y, uo.y, bo.y, ro.y, mo.y);
             one(h.z, u.z, b.z, ho.z, uo.z, bo.z, ro.z, mo.z);
             one(h.w, u.w, b.w, ho.w, uo.w, bo.w, ro.w, mo.w);
-            if (write_stems & 1) {
+            if (!MIX_ONLY && (write_stems & 1)) {
                 *reinterpret_cast<float4 *>(h_ + i) = ho;
                 *reinterpret_cast<float4 *>(u_ + i) = uo;
                 *reinterpret_cast<float4 *>(b_ + i) = bo;
             }
-            if (rec) store_f4(rec + base + i, ro, (write_stems & 2) != 0);
-            if (mix) store_f4(mix + base + i, mo, (write_stems & 2) != 0);
+            if (!MIX_ONLY && rec) store_f4(rec + base + i, ro, (write_stems & 2) != 0);
+            if (MIX_ONLY || mix) store_f4(mix + base + i, mo, (write_stems & 2) != 0);
         }
     }
     for (int i = (int)threadIdx.x; i < n; i += FIN_THREADS) {
@@ -1075,9 +1079,9 @@ __global__ __launch_bounds__(FIN_THREADS) void k_note_finish(float *__restrict__
         const unsigned z = zbits(i);
         float ho, uo, bo, ro, mo;
         one(h_[i], (z & 1u) ? 0.f : u_[i], (z & 2u) ? 0.f : b_[i], ho, uo, bo, ro, mo);
-        if (write_stems & 1) { h_[i] = ho; u_[i] = uo; b_[i] = bo; }
-        if (rec) rec[base + i] = ro;
-        if (mix) mix[base + i] = mo;
+        if (!MIX_ONLY && (write_stems & 1)) { h_[i] = ho; u_[i] = uo; b_[i] = bo; }
+        if (!MIX_ONLY && rec) rec[base + i] = ro;
+        if (MIX_ONLY || mix) mix[base + i] = mo;
     }
 }
 
@@ -1178,12 +1182,19 @@ int launch_note_finish(goofer_ctx *ctx, float *harm, float *uv, float *bre, floa
     // One 1024-thread workgroup fills a CU's register file (16 waves x 128 VGPRs), so its LDS is the workgroup's own: the first
     // rows of the breath stem wait there between the passes (9 rows x 16 KB)
     const int rows = 9;
+    const bool mix_only = !write_stems && !rec && mix;    // the instantiation that stores nothing else
+    const void *fn = mix_only ? (const void *)k_note_finish<true> : (const void *)k_note_finish<false>;
     const size_t lds = (size_t)rows * FIN_THREADS * sizeof(float4);
     if (lds > 48 * 1024)
-        if (int arc = kernel_allow_max_lds(ctx, (const void *)k_note_finish, FIN_KEEP * FIN_THREADS * (int)sizeof(float4) > 159 * 1024 ? 159 * 1024 : FIN_KEEP * FIN_THREADS * (int)sizeof(float4))) return arc;   // (beside 64 B of static LDS)
-    hipLaunchKernelGGL(k_note_finish, dim3((unsigned)n_notes), dim3(FIN_THREADS), lds, st, harm, uv, bre, rec, mix, sample_off, params,
-                       note_mag, note_peak, (write_stems ? 1 : 0) | 2 /* mix / rec: non-temporal stores */, rows, hopz, frame_off,
-                       ctx->plan.n_fft / 2, 31 - __builtin_clz((unsigned)ctx->plan.hop));
+        if (int arc = kernel_allow_max_lds(ctx, fn, FIN_KEEP * FIN_THREADS * (int)sizeof(float4) > 159 * 1024 ? 159 * 1024 : FIN_KEEP * FIN_THREADS * (int)sizeof(float4))) return arc;   // (beside 64 B of static LDS)
+    const int ws = (write_stems ? 1 : 0) | 2;   // (2: mix / rec go out as non-temporal stores)
+    const int hz_m = ctx->plan.n_fft / 2, hz_shift = 31 - __builtin_clz((unsigned)ctx->plan.hop);
+    if (mix_only)
+        hipLaunchKernelGGL(k_note_finish<true>, dim3((unsigned)n_notes), dim3(FIN_THREADS), lds, st, harm, uv, bre, rec, mix, sample_off, params,
+                           note_mag, note_peak, ws, rows, hopz, frame_off, hz_m, hz_shift);
+    else
+        hipLaunchKernelGGL(k_note_finish<false>, dim3((unsigned)n_notes), dim3(FIN_THREADS), lds, st, harm, uv, bre, rec, mix, sample_off, params,
+                           note_mag, note_peak, ws, rows, hopz, frame_off, hz_m, hz_shift);
     LAUNCH_CHECK(ctx);
     return GOOFER_OK;
 }
