@@ -1096,6 +1096,29 @@ def loudness_batch(signals, sr, target=None, max_gain_db=20.0, ctx=None):
     return y, loud.cpu().numpy(), gain.cpu().numpy(), segs
 
 
+def compress_batch(signals, sr, threshold_db, ratio, knee_db=6.0, attack_ms=5.0, release_ms=100.0, makeup_db=0.0, curve=False, ctx=None):
+    """Many signals through the dynamic range compressor in one device pass (goofer_amd.compress; goofer_compress): ``signals``,
+    1-D arrays at ``sr`` (8000 to 192000 Hz), each compressed above ``threshold_db`` (dB re full scale) at ``ratio`` with a soft
+    knee of ``knee_db``, a decoupled smooth peak detector with the time constants ``attack_ms`` and ``release_ms``, and
+    ``makeup_db`` of gain.  Returns ``(ys, max_reduction)``: the compressed signals as a list of fp32 arrays and float64
+    ``[n]``, every signal's greatest gain reduction in dB; with ``curve`` also a list of float64 arrays, the gain reduction in
+    dB per sample.  This project's own definition (include/goofer_hip.h)."""
+    from . import compress as CP
+    xs = [np.ascontiguousarray(s, dtype=np.float32).reshape(-1) for s in signals]
+    plan = CP.plan(sr, [len(s) for s in xs], CP.Compressor(threshold_db, ratio, knee_db, attack_ms, release_ms, makeup_db))
+    if not plan.n:
+        return ([], np.zeros(0), []) if curve else ([], np.zeros(0))
+    c = ctx or default_context()
+    y, red, yl = c.compress(c.tensor(np.concatenate(xs + [np.zeros(1, dtype=np.float32)])), None, plan, curve=curve)
+    c.check()
+    y = y.cpu().numpy()
+    ys = [y[plan.in_off[i]:plan.in_off[i + 1]] for i in range(plan.n)]
+    if not curve:
+        return ys, red.cpu().numpy()
+    yl = yl.cpu().numpy()
+    return ys, red.cpu().numpy(), [yl[plan.in_off[i]:plan.in_off[i + 1]] for i in range(plan.n)]
+
+
 def synthesize(env_spec, f0_interp, voicing_mask, y, sr, n_fft=1024, hop_length=256, glottal_smoothing=False,
                stretch_factor=1.0, start_sec=None, end_sec=None, apply_brightness=True, normalize=1.0, uv_strength=0.75,
                breath_strength=0.1, noise_transition_smoothness=100, pitch_shift=1.0, formant_shift=1.0, f0_jitter=False,

@@ -106,6 +106,11 @@ int launch_loudness_measure(goofer_ctx *ctx, const float *x, const int64_t *in_o
 int launch_loudness_apply(goofer_ctx *ctx, const float *x, const int64_t *in_off, int n, int64_t total, const float *gain, float *out,
                           hipStream_t st);
 
+// compress.hip
+int launch_compress(goofer_ctx *ctx, const float *x, const int64_t *in_off, int n, const double *coef, const double *pows,
+                    const int32_t *tiles, int64_t n_tiles, float *out, double *max_reduction, double *curve, double *rsum,
+                    double *rstart, double *asum, double *astart, int32_t *first_tile, double *xl, hipStream_t st);
+
 // noise.hip
 int launch_normal_fill(goofer_ctx *ctx, uint64_t seed, const goofer_note_params *params, const int64_t *sample_off, int n_notes,
                        int64_t total, int tag, const unsigned char *note_on, const double *growl_scale, double *out, hipStream_t st);

@@ -1177,4 +1177,42 @@ int goofer_host_loudness_plan(int sr, const int64_t *in_off, int n, int *S, doub
     return GOOFER_OK;
 }
 
+/* The compressor (include/goofer_hip.h; the kernels: compress.hip): the refusals, the coefficients, the tile table and the
+ * powers a^(16 * 2^k) of the two one-pole coefficients, each by one long-double pow rounded once to float64 (23 squarings
+ * would double the relative error 23 times: 2^-30 in float64, of a number every carried state is multiplied by). */
+int goofer_host_compress_plan(int sr, double threshold_db, double ratio, double knee_db, double attack_ms, double release_ms,
+                              double makeup_db, const int64_t *in_off, int n, double *coef, double *pows, int32_t *tiles,
+                              int64_t tiles_cap, int64_t *need)
+{
+    if (!coef || !pows || !need || n < 0 || tiles_cap < 0 || (n > 0 && !in_off) || (tiles_cap > 0 && !tiles)) return GOOFER_EINVAL;
+    if (sr < GOOFER_COMPRESS_MIN_SR || sr > GOOFER_COMPRESS_MAX_SR) return GOOFER_EINVAL;
+    if (!(threshold_db >= -80.0 && threshold_db <= 0.0) || !(ratio >= 1.0) || !(knee_db >= 0.0 && knee_db <= 40.0) ||
+        !(attack_ms >= 0.0 && attack_ms <= 1000.0) || !(release_ms >= 0.0 && release_ms <= 5000.0) ||
+        !(makeup_db >= -24.0 && makeup_db <= 24.0))
+        return GOOFER_EINVAL;                                   // (written so that a NaN is refused too; ratio may be +inf)
+    int64_t n_tiles = 0;
+    for (int i = 0; i < n; ++i) {
+        const int64_t len = in_off[i + 1] - in_off[i];
+        if (len < 0 || len >= ((int64_t)1 << 31)) return GOOFER_EINVAL;
+        n_tiles += (len + GOOFER_COMPRESS_TILE - 1) / GOOFER_COMPRESS_TILE;
+    }
+    if (n_tiles >= ((int64_t)1 << 31)) return GOOFER_EINVAL;
+    need[0] = n_tiles;
+    if (tiles_cap < n_tiles) return 1;
+    const double aA = attack_ms == 0.0 ? 0.0 : std::exp(-1.0 / (attack_ms * 1e-3 * (double)sr));
+    const double aR = release_ms == 0.0 ? 0.0 : std::exp(-1.0 / (release_ms * 1e-3 * (double)sr));
+    coef[0] = threshold_db, coef[1] = knee_db, coef[2] = 1.0 / ratio - 1.0, coef[3] = makeup_db, coef[4] = aR, coef[5] = aA;
+    for (int which = 0; which < 2; ++which) {
+        const long double a = which == 0 ? (long double)aR : (long double)aA;
+        long double m = (long double)GOOFER_COMPRESS_SPT;
+        for (int k = 0; k < GOOFER_COMPRESS_POWS; ++k, m *= 2.0L) pows[GOOFER_COMPRESS_POWS * which + k] = (double)std::pow(a, m);
+    }
+    int64_t t = 0;
+    for (int i = 0; i < n; ++i) {
+        const int64_t cnt = (in_off[i + 1] - in_off[i] + GOOFER_COMPRESS_TILE - 1) / GOOFER_COMPRESS_TILE;
+        for (int64_t k = 0; k < cnt; ++k, ++t) tiles[2 * t] = i, tiles[2 * t + 1] = (int32_t)k;
+    }
+    return GOOFER_OK;
+}
+
 }  // extern "C"

@@ -345,6 +345,41 @@ class Context:
                 self._check(self.lib.goofer_loudness_apply(self.h, _ptr(x), _ptr(d_in), n, total, _ptr(gain), _ptr(y), self._stream()))
         return y, loud, gain, seg
 
+    def compress(self, x, d_off, plan, out=None, curve=False):
+        """The signals of a ragged batch through the dynamic range compressor on the device (goofer_compress; the definition:
+        include/goofer_hip.h, restated in tests/compress_ref.py).  ``x``: the signals' samples back to back, a contiguous fp32
+        device tensor; ``d_off``: their int64 CSR offsets ``[n + 1]``, a device tensor, a host sequence (checked against the
+        plan) or None for the plan's own; ``plan``: a ``goofer_amd.compress.CompressPlan`` for these lengths, which carries the
+        settings (shipped in one upload the first time it is used on this device); ``out``: a contiguous fp32 device tensor of
+        ``plan.total`` samples, which may be ``x`` itself (default: a new one); ``curve``: also the detector's curve.  Returns
+        ``(y, max_reduction, yl)``, device tensors: ``y`` fp32 ``[plan.total]``, ``max_reduction`` float64 ``[n]``, the greatest
+        gain reduction of every signal in dB (0 for a signal without a sample), and ``yl`` float64 ``[plan.total]``, the gain
+        reduction in dB per sample, or None without ``curve``.  Asynchronous on the current stream."""
+        n, total = plan.n, plan.total
+        d_in, coef, pows, tiles = plan.device_tables(self)
+        if isinstance(d_off, torch.Tensor):
+            if d_off.dtype != torch.int64 or not d_off.is_contiguous() or d_off.numel() != n + 1:
+                raise ValueError("compress: d_off is one contiguous int64 CSR of the plan's %d signals" % n)
+            d_in = d_off
+        elif d_off is not None and not np.array_equal(np.asarray(d_off, dtype=np.int64), plan.in_off):
+            raise ValueError("compress: d_off is not the CSR the plan was made for")
+        if x.dtype != torch.float32 or not x.is_contiguous() or x.numel() < total:
+            raise ValueError("compress: x must be a contiguous float32 tensor of the plan's %d samples" % total)
+        if out is not None and (out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != total):
+            raise ValueError("compress: out must be a contiguous float32 tensor of the %d samples" % total)
+        y = torch.empty(total, dtype=torch.float32, device=self.device) if out is None else out
+        red = torch.zeros(n, dtype=torch.float64, device=self.device)
+        yl = torch.empty(total, dtype=torch.float64, device=self.device) if curve else None
+        if n:
+            args = (self.h, _ptr(x) if total else None, _ptr(d_in), n, total, _ptr(coef), _ptr(pows), _ptr(tiles) if total else None,
+                    plan.n_tiles, _ptr(y) if total else None, _ptr(red), _ptr(yl) if curve and total else None)
+            size = C.c_int64(0)
+            self._check(self.lib.goofer_compress(*args, None, C.byref(size), None))
+            scratch = torch.empty(max(int(size.value), 256), dtype=torch.uint8, device=self.device)
+            size = C.c_int64(scratch.numel())
+            self._check(self.lib.goofer_compress(*args, _ptr(scratch), C.byref(size), self._stream()))
+        return y, red, yl
+
     def normal_fill(self, seed: int, params, lengths_or_offsets, tag: int, note_on=None, growl_scale=None, out=None):
         """float64 standard normals of stream ``tag`` (0 f0 jitter, 1 / 2 harmonic / breath volume jitter, 3 sub-harmonic f0
         jitter, 4 growl) for the notes of a ragged batch, drawn on the device (goofer_normal_fill; the stream's definition:

@@ -6,7 +6,7 @@ definition is this project's own (``include/goofer_hip.h``, goofer_phrase_note; 
 ``goofer_phrase_mix``.  Here: wavtool's arguments turned into note records (host, float64), the records checked and the
 cover table made by the library's planner (``goofer_host_phrase_plan``), and a command line,
 
-    python -m goofer_amd.phrase [--rate HZ] [--loudness LUFS] [--limit [DBFS]] job.txt out.wav
+    python -m goofer_amd.phrase [--rate HZ] [--compress T:R[:ATTACK:RELEASE[:KNEE[:MAKEUP]]]] [--loudness LUFS] [--limit [DBFS]] job.txt out.wav
 
 ``job.txt`` holds one line per note, the 13 resampler arguments, ``|``, then wavtool's ``stp length p1 p2 p3 v1 v2 v3 v4 [ovr
 [p4 [p5 v5]]]``::
@@ -20,7 +20,10 @@ the device (goofer_amd.rate) before it becomes int16; the wav's header carries H
 limiter (goofer_amd.limit) over the track at the rate of the wav, with the ceiling DBFS decibels relative to full scale (bare:
 32767/32768), and reports the track's peak in front of it and its greatest gain reduction on stderr.  ``--loudness LUFS``
 measures the track's integrated loudness after BS.1770 (goofer_amd.loudness) and scales the track to LUFS, in front of the
-limiter, the gain capped at 20 dB; the measured loudness and the gain go to stderr too.
+limiter, the gain capped at 20 dB; the measured loudness and the gain go to stderr too.  ``--compress
+T:R[:ATTACK:RELEASE[:KNEE[:MAKEUP]]]`` runs the dynamic range compressor (goofer_amd.compress) over the track behind the rate
+conversion and in front of the loudness stage: threshold T in dB re full scale, ratio R (``inf`` allowed), attack and release in
+ms (5 and 100), knee width in dB (6), make-up gain in dB (0); its greatest gain reduction goes to stderr.
 ``Renderer.render_phrase`` is the same for (Source, Request) jobs.
 """
 from __future__ import annotations
@@ -244,13 +247,15 @@ def read_job(path):
     return out
 
 
-def render_job(path, out_wav, renderer=None, seed=None, tracker=None, pcm16=True, out_sr=None, limit=None, stats=None, loudness=None):
+def render_job(path, out_wav, renderer=None, seed=None, tracker=None, pcm16=True, out_sr=None, limit=None, stats=None, loudness=None,
+               compress=None):
     """``python -m goofer_amd.phrase``: the notes of a job file rendered as one batch and written as one wav.  ``in_file`` is
     resolved like the resampler front end does: ``<stem>_features.goofy`` beside the wav, analysed and cached first when it is
     missing (``trackers.ensure_features_batch``; the tracker: the argument, else ``$GOOFER_TRACKER``).  ``out_sr``: the rate of
     the wav (``render_phrase``'s; None: the voicebank's).  ``limit``: ``render_phrase``'s (None: no limiter); with it ``stats``,
     a dict, receives the limiter's ``peak_in`` and ``min_gain``.  ``loudness``: ``render_phrase``'s (None: the track's level is
-    left as it is); with it ``stats`` receives ``lufs_in``, ``momentary_max`` and ``gain``."""
+    left as it is); with it ``stats`` receives ``lufs_in``, ``momentary_max`` and ``gain``.  ``compress``: ``render_phrase``'s (None:
+    no compressor); with it ``stats`` receives ``max_reduction_db``."""
     from pathlib import Path
     from . import core, trackers
     from . import sampler as S
@@ -273,11 +278,11 @@ def render_job(path, out_wav, renderer=None, seed=None, tracker=None, pcm16=True
         raise ValueError(f"{path}: no note")
     if seed is None:
         seed = int(np.random.SeedSequence().generate_state(1, dtype=np.uint64)[0])
-    if limit is None and loudness is None:
+    if limit is None and loudness is None and compress is None:
         track = renderer.render_phrase(jobs, [e for _, e in lines], seed=seed, pcm16=pcm16, out_sr=out_sr)
     else:
         track, st = renderer.render_phrase(jobs, [e for _, e in lines], seed=seed, pcm16=pcm16, out_sr=out_sr, limit=limit, return_stats=True,
-                                           loudness=loudness)
+                                           loudness=loudness, compress=compress)
         if stats is not None:
             stats.update(st)
     write_wav(out_wav, track, jobs[0][0].sr if out_sr is None else int(out_sr))
@@ -288,8 +293,8 @@ def main(argv=None) -> int:
     import logging
     logging.basicConfig(format="%(message)s", level=logging.INFO)
     argv = list(sys.argv[1:] if argv is None else argv)
-    out_sr = limit = loudness = None
-    while len(argv) > 2 and argv[0] in ("--rate", "--limit", "--loudness"):
+    out_sr = limit = loudness = compress = None
+    while len(argv) > 2 and argv[0] in ("--rate", "--limit", "--loudness", "--compress"):
         if argv[0] == "--rate":
             try:
                 out_sr = int(argv[1])
@@ -302,6 +307,13 @@ def main(argv=None) -> int:
             except ValueError:
                 break
             argv = argv[2:]
+        elif argv[0] == "--compress":
+            from . import compress as CP
+            try:
+                compress = CP.parse(argv[1])
+            except ValueError:
+                break
+            argv = argv[2:]
         else:
             from . import limit as LM
             try:                        # --limit DBFS, or bare: the default ceiling
@@ -311,14 +323,19 @@ def main(argv=None) -> int:
                 limit = LM.CEILING
                 argv = argv[1:]
     if len(argv) != 2:
-        logging.error("Usage:\n  python -m goofer_amd.phrase [--rate HZ] [--loudness LUFS] [--limit [DBFS]] job.txt out.wav")
+        logging.error("Usage:\n  python -m goofer_amd.phrase [--rate HZ] [--compress T:R[:ATTACK:RELEASE[:KNEE[:MAKEUP]]]] [--loudness LUFS] "
+                      "[--limit [DBFS]] job.txt out.wav")
         return 1
     stats = {}
     try:
-        track = render_job(argv[0], argv[1], out_sr=out_sr, limit=limit, stats=stats, loudness=loudness)
+        track = render_job(argv[0], argv[1], out_sr=out_sr, limit=limit, stats=stats, loudness=loudness, compress=compress)
     except Exception:                   # noqa: BLE001
         logging.exception("Failed to render")
         return 1
+    if compress is not None:
+        print("Compressor: greatest reduction %.2f dB (threshold %.2f dBFS, ratio %g, attack %g ms, release %g ms, knee %g dB, make-up %g dB)"
+              % (stats["max_reduction_db"], compress.threshold_db, compress.ratio, compress.attack_ms, compress.release_ms, compress.knee_db,
+                 compress.makeup_db), file=sys.stderr)
     if loudness is not None:
         print("Loudness: measured %.2f LUFS (momentary max %.2f), gain %.2f dB (target %.2f LUFS)"
               % (stats["lufs_in"], stats["momentary_max"], 20.0 * math.log10(stats["gain"]) if stats["gain"] > 0.0 else -math.inf, loudness),

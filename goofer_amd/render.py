@@ -436,7 +436,7 @@ class Renderer:
         return None if int(out_sr) in rates else int(out_sr)
 
     def render(self, jobs, seed: int = 0, phi_seeds=None, return_parts: bool = False, noise_seeds=None, out_sr=None, limit=None,
-               loudness=None):
+               loudness=None, compress=None):
         """jobs: list of (Source, Request).  Returns a list of fp32 arrays (the mix the reference writes to
         out.wav); with ``return_parts`` also a dict of device-side intermediates for tests.
         ``phi_seeds``: per-note seeds for INJECTED phases (parity with a seeded reference run: numpy's stream of each seed,
@@ -453,7 +453,11 @@ class Renderer:
         the rate the notes are returned at.
         ``loudness``: None, a target in LUFS or a ``(target, max_gain_db)`` pair: every note measured after BS.1770 and scaled
         to the target on the device (goofer_amd.loudness; the whole batch in one pass), after the conversion and in front of
-        the limiter."""
+        the limiter.
+        ``compress``: None, a ``goofer_amd.compress.Compressor``, a ``(threshold_db, ratio[, attack_ms, release_ms[, knee_db[,
+        makeup_db]]])`` sequence or the string ``T:R[:ATTACK:RELEASE[:KNEE[:MAKEUP]]]``: every note through the dynamic range
+        compressor on the device (goofer_amd.compress; the whole batch in one goofer_compress), after the conversion and in
+        front of the loudness stage."""
         if not jobs:
             return []
         to_sr = self._out_rate(jobs, out_sr, "render")
@@ -464,6 +468,11 @@ class Renderer:
             loudness = LD.parse(loudness)
             if len({int(src.sr) for src, _ in jobs}) != 1:
                 raise ValueError("render: loudness takes notes that share one sample rate")
+        if compress is not None:
+            from . import compress as CP
+            compress = CP.parse(compress)
+            if len({int(src.sr) for src, _ in jobs}) != 1:
+                raise ValueError("render: compress takes notes that share one sample rate")
         prep = self.prepare(jobs, phi_seeds=phi_seeds, trim_rows=not return_parts, noise_seeds=noise_seeds)   # tests look at the whole assembled envelope
         out = self.run(prep, seed=seed, keep_stems=return_parts)
         mix, offs = out["mix"], prep["sample_off"]
@@ -471,6 +480,9 @@ class Renderer:
             from . import rate as RT
             plan = RT.plan(jobs[0][0].sr, to_sr, np.diff(np.asarray(offs, dtype=np.int64)))
             mix, offs = self.ctx.rate_convert(mix, prep["offsets"]["d_s"], plan), plan.out_off
+        if compress is not None:
+            cplan = CP.plan(jobs[0][0].sr if to_sr is None else to_sr, np.diff(np.asarray(offs, dtype=np.int64)), compress)
+            mix = self.ctx.compress(mix, None, cplan)[0]
         if loudness is not None:
             dplan = LD.plan(jobs[0][0].sr if to_sr is None else to_sr, np.diff(np.asarray(offs, dtype=np.int64)))
             mix = self.ctx.loudness(mix, None, dplan, *loudness)[0]
@@ -488,7 +500,7 @@ class Renderer:
         return res
 
     def render_phrase(self, jobs, entries, seed: int = 0, phi_seeds=None, noise_seeds=None, pcm16: bool = False, out_sr=None, limit=None,
-                      return_stats: bool = False, loudness=None):
+                      return_stats: bool = False, loudness=None, compress=None):
         """The notes of ``jobs`` rendered as one batch and assembled into one track on the device: what a ``wavtool`` does with
         the notes ``render`` returns, without bringing them home first (goofer_amd.phrase; goofer_phrase_mix).  ``entries``:
         the phrase in order, one ``phrase.Entry`` (or its wavtool argument string ``stp length p1 p2 p3 v1 v2 v3 v4 [ovr [p4
@@ -500,13 +512,19 @@ class Renderer:
         the track brought under the ceiling by the look-ahead peak limiter on the device (goofer_amd.limit) — mix, convert,
         limit at the output rate, then int16.  ``loudness``: None, a target in LUFS or a ``(target, max_gain_db)`` pair: the
         track measured after BS.1770 and scaled to the target on the device (goofer_amd.loudness) — mix, convert, loudness,
-        limit, then int16.  ``return_stats`` (with ``limit`` or ``loudness``): also a dict; with ``limit`` the track's
+        limit, then int16.  ``compress``: None or what ``render`` takes: the track through the dynamic range compressor on the
+        device (goofer_amd.compress), behind the conversion and in front of the loudness stage — mix, convert, compress,
+        loudness, limit, then int16; with it the statistics gain ``max_reduction_db``, the compressor's greatest gain reduction
+        in dB.  ``return_stats`` (with ``limit``, ``loudness`` or ``compress``): also a dict; with ``limit`` the track's
         ``peak_in``, its greatest ``|x|`` in front of the limiter, and ``min_gain``, the smallest gain the limiter applied; with
         ``loudness`` ``lufs_in``, the track's integrated loudness in front of the scaling, ``momentary_max``, its greatest
         momentary loudness, and ``gain``, the factor it was scaled by (Python floats)."""
         from . import phrase as P
-        if return_stats and limit is None and loudness is None:
+        if return_stats and limit is None and loudness is None and compress is None:
             raise ValueError("render_phrase: return_stats reports the limiter's and the loudness stage's statistics and needs limit or loudness")
+        if compress is not None:
+            from . import compress as CP
+            compress = CP.parse(compress)
         if loudness is not None:
             from . import loudness as LD
             loudness = LD.parse(loudness)
@@ -523,7 +541,10 @@ class Renderer:
         if to_sr is not None:
             from . import rate as RT
             track = self.ctx.rate_convert(track, None, RT.plan(jobs[0][0].sr, to_sr, [plan.total_out]))
-        stats = lstats = None
+        stats = lstats = cstats = None
+        if compress is not None:
+            cplan = CP.plan(jobs[0][0].sr if to_sr is None else to_sr, [track.numel()], compress)
+            track, cstats, _ = self.ctx.compress(track, None, cplan)
         if loudness is not None:
             dplan = LD.plan(jobs[0][0].sr if to_sr is None else to_sr, [track.numel()])
             track, *lstats = self.ctx.loudness(track, None, dplan, *loudness)
@@ -541,6 +562,8 @@ class Renderer:
             if lstats is not None:
                 loud = lstats[0].cpu()
                 res.update({"lufs_in": float(loud[0, 0]), "momentary_max": float(loud[0, 1]), "gain": float(lstats[1].cpu()[0])})
+            if cstats is not None:
+                res["max_reduction_db"] = float(cstats.cpu()[0])
             return track.cpu().numpy(), res
         return track.cpu().numpy()
 

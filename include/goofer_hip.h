@@ -922,6 +922,88 @@ int goofer_loudness_measure(goofer_ctx *ctx, const float *x, const int64_t *in_o
 int goofer_loudness_apply(goofer_ctx *ctx, const float *x, const int64_t *in_off, int n, int64_t total, const float *gain, float *out,
                           void *stream);
 
+/* ---- dynamic range compressor ----------------------------------------------------------------------------------------------
+ * Phrase mix, loudness and the limiter are linear or protect peaks; this stage evens out level: a feed-forward log-domain
+ * compressor with a smooth decoupled peak detector behind the gain computer (after Giannoulis, Massberg and Reiss, 2012), in
+ * front of the loudness stage (mix, rate conversion, compressor, loudness, limiter, int16).  The definition is this project's
+ * own (restated in numpy by tests/compress_ref.py).  A signal gets the same bits alone as at any position in any batch, on
+ * every run: no floating-point atomics.
+ *
+ * Parameters.  sr: an integer, GOOFER_COMPRESS_MIN_SR <= sr <= GOOFER_COMPRESS_MAX_SR.  threshold_db T in [-80, 0]; ratio R in
+ * [1, +inf]; knee_db W in [0, 40] (default 6); attack_ms in [0, 1000] (default 5); release_ms in [0, 5000] (default 100);
+ * makeup_db M in [-24, 24] (default 0).  Anything else, a NaN included, is refused (GOOFER_EINVAL).
+ *
+ * Coefficients (host, float64): aA = attack_ms == 0 ? 0 : exp(-1 / (attack_ms * 1e-3 * sr)), aR likewise from release_ms,
+ * s = 1/R - 1, in [-1, 0].  coef[GOOFER_COMPRESS_COEF] = T, W, s, M, aR, aA.
+ *
+ * Per signal x[0 .. n), zero state in front of every signal, everything in float64 until the last step:
+ *   a[i]  = max(|x[i]|, 1e-6);  xg[i] = 20 log10 a[i];  d = xg[i] - T
+ *   xl[i] = 0                        if 2d < -W
+ *         = -s (d + W/2)^2 / (2W)    if |2d| <= W   (W > 0)
+ *         = -s d                     otherwise                  (xl >= 0: the reduction asked for, in dB)
+ *   y1[i] = max(xl[i], aR y1[i-1] + (1 - aR) xl[i])             (release; y1[-1] = 0)
+ *   yl[i] = aA yl[i-1] + (1 - aA) y1[i]                         (attack;  yl[-1] = 0)
+ *   g[i]  = 10^((M - yl[i]) / 20), exactly 1 where M - yl[i] == 0
+ *   y[i]  = fp32(double(x[i]) * g[i])                           (one rounding to fp32)
+ * Statistic per signal: max_reduction = max_k yl[k], float64 dB, 0 for a signal without a sample.  Optional output: the curve
+ * yl, float64 [total].
+ *
+ * Identity: where every sample has 20 log10 a <= T - W/2 and M == 0, xl, y1 and yl are exactly 0 and g exactly 1: the signal
+ * comes back bit for bit.  Non-finite samples: a non-finite sample leaves its own signal unspecified from that sample on
+ * (max_reduction included); the other signals of the batch are untouched.
+ *
+ * The release stage is a recurrence with a max in it.  One sample is the map f(y) = max(C, A y + B) with C = xl, A = aR,
+ * B = (1 - aR) xl; two such maps compose to one of the same form, C' = max(C2, A2 C1 + B2), A' = A2 A1, B' = A2 B1 + B2, and
+ * the composition is associative: a scan.  Samples past a signal's end count as xl = 0 (no later tile reads that state), so
+ * all elements of a scan level share A, a power of aR from the host, and only (C, B) are carried; xl >= 0 and the state starts
+ * at 0, so C = 0 is the neutral element (never -inf: A underflows to 0 over many tiles, and 0 * -inf is NaN).  C of a prefix
+ * is the state behind it from the true start, B the linear path alone (B <= C).  The attack stage is a linear scan over y1 with
+ * powers of aA.  pows[2][GOOFER_COMPRESS_POWS]: aR^(GOOFER_COMPRESS_SPT * 2^k), then aA^(...) likewise, each by one
+ * long-double pow on the host, rounded once.
+ * Tolerance: |yl - yl_ref| <= 2^-22 dB, which keeps g within 2^-25 (an error of e dB moves g by a relative 0.1151 e); with the
+ * one fp32 rounding, |y - y_ref| <= 2^-23 |y_ref| + 2^-149 per sample.  An fp32 detector state does not hold it (eps / (1 - a),
+ * a up to 0.99999). */
+#define GOOFER_COMPRESS_MIN_SR 8000
+#define GOOFER_COMPRESS_MAX_SR 192000
+#define GOOFER_COMPRESS_KNEE_DB 6.0
+#define GOOFER_COMPRESS_ATTACK_MS 5.0
+#define GOOFER_COMPRESS_RELEASE_MS 100.0
+#define GOOFER_COMPRESS_FLOOR 1e-6   /* the least |x| the level detector sees: -120 dB */
+#define GOOFER_COMPRESS_TILE 4096
+#define GOOFER_COMPRESS_SPT 16
+#define GOOFER_COMPRESS_COEF 6
+#define GOOFER_COMPRESS_POWS 20      /* a^16 .. a^(16 * 2^19): 8 for the 256 runs of a tile, a^4096 for a tile, 8 from a^(4096 * 16) on for 256 runs of 16 tiles */
+#define GOOFER_COMPRESS_RUN_TILES 16 /* tiles a thread of the carry kernels walks */
+#define GOOFER_COMPRESS_ROUND_TILES 4096   /* tiles the carry kernels take per round: 256 threads of GOOFER_COMPRESS_RUN_TILES; the state in front of a round goes through its first thread */
+
+/* Host side (no device, no handle): for n signals whose samples lie back to back with the CSR in_off[n + 1] (non-decreasing),
+ * coef[GOOFER_COMPRESS_COEF], pows[2 * GOOFER_COMPRESS_POWS] and the tile table: need[0] = sum_i ceil(len_i /
+ * GOOFER_COMPRESS_TILE) pairs of int32 (signal, tile of that signal), ascending.  Returns 0 with everything written; 1 when
+ * tiles_cap (in pairs) < need[0] (only need is valid: grow, call again); GOOFER_EINVAL for a parameter outside the
+ * definition's range, a null argument (in_off may be null when n == 0, tiles when tiles_cap == 0), a negative count or
+ * capacity, offsets that decrease, a signal of 2^31 samples or more. */
+int goofer_host_compress_plan(int sr, double threshold_db, double ratio, double knee_db, double attack_ms, double release_ms,
+                              double makeup_db, const int64_t *in_off, int n, double *coef, double *pows, int32_t *tiles,
+                              int64_t tiles_cap, int64_t *need);
+
+/* The compressor (compress.hip).  x, in_off ([n + 1]), coef, pows and tiles are device arrays of the caller, the tables those
+ * of goofer_host_compress_plan for the same in_off, total = in_off[n].  Outputs, device arrays: out, fp32 [total], y;
+ * max_reduction, float64 [n]; curve, float64 [total], yl, or NULL: not written.  Five launches in stream order, and no
+ * workgroup ever waits for another: (1) a workgroup per tile composes its samples' release maps from the neutral element;
+ * (2) a workgroup per signal scans the tiles' maps, GOOFER_COMPRESS_ROUND_TILES at a time, into the release state in front of
+ * every tile; (3) every tile again: y1 from its true start, the attack recurrence from zero, the tile's end state; (4) a
+ * workgroup per signal scans those into the attack state in front of every tile; (5) every tile a third time: y1, yl and g from
+ * the true states, y stored once, the curve stored, and the tile's greatest yl folded into max_reduction by an integer atomic
+ * maximum over the bits of the non-negative values.  x is read three times and written once.  out == x is allowed (there is no
+ * halo); any other overlap of out with x is refused.  Scratch by the caller-scratch protocol: with scratch NULL the size goes
+ * to *scratch_bytes and nothing runs.  Asynchronous on `stream`.  n == 0: nothing is launched.  GOOFER_EINVAL, with nothing
+ * launched, for a null pointer (all arrays may be null when n == 0; x, tiles and out when total == 0), a negative count, an
+ * n_tiles that is not between ceil(total / GOOFER_COMPRESS_TILE) and that plus n, x, tiles or out not 4-byte aligned, the
+ * others not 8-byte aligned, or a scratch block that is too short. */
+int goofer_compress(goofer_ctx *ctx, const float *x, const int64_t *in_off, int n, int64_t total, const double *coef, const double *pows,
+                    const int32_t *tiles, int64_t n_tiles, float *out, double *max_reduction, double *curve, void *scratch,
+                    int64_t *scratch_bytes, void *stream);
+
 /* ---- measurement / test hooks --------------------------------------------------------------- */
 
 /* HIP-event timing of every stage of goofer_synth_batch on the caller's stream: begin() arms up to
@@ -959,6 +1041,11 @@ const char *goofer_profile_stage_name_ex(const goofer_ctx *ctx, int stage);   /*
  *               row from global memory, as it does for a table that does not fit.  Same bits.
  *   "limit_skip" 1 (default): a tile of goofer_limit with no sample above the ceiling, its halo of 2W samples on either side
  *               included, copies x to out; 0: every tile does the full arithmetic.  Same bits (the identity property).
+ *   "compress_skip" 1 (default): goofer_compress finds a sample under the lower end of the knee (|x| <= 10^((T - W/2) / 20)) by
+ *               one compare and takes xl = 0 without the logarithm; 0: the logarithm for every sample.  The curve is continuous
+ *               there, so the two agree within rounding (and bit for bit wherever the identity property holds).
+ *   "compress_store" 0 (default): every pass of goofer_compress computes xl again from x; 1: the first pass writes xl (float64
+ *               [total], more scratch: ask for the size with the option set) and the other two read it.  Same bits.
  *   "walk_run"  0 (default): the four frame walkers (k_noise_stems, k_harm_stem, k_irfft_ola3, k_irfft_ola1) get the frames per
  *               wave that fill the device a whole number of times: from a floor of 32 frames (8 halos where the halo
  *               (n_fft - 1) / hop is above 4) to 128, k_irfft_ola1 256; a batch leaves the floor only with tens of thousands of
