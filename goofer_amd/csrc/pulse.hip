@@ -11,7 +11,7 @@
 //   k_pulse_place   fully parallel gather: every output sample sums, in ascending onset order, the
 //                   LF shapes that cover it — no atomics, same fp32 accumulation order as the
 //                   reference's `pulse[j] += cache[k]`
-// Shapes are evaluated on the fly in fp64 (numba's typing) and normalised by a per-T0 peak table.
+// Shapes come from a table of every length T0 = 3 .. 8192 (k_pulse_shape_table), evaluated in fp64 (numba's typing) and normalised by a per-T0 peak table.
 #include "common.h"
 #include "launchers.h"
 
@@ -60,7 +60,7 @@ __global__ __launch_bounds__(256) void k_pulse_peak(float *__restrict__ peak, do
 
 // The normalised pulse of length T0, tabulated at the nominal period T = T0/sr.  The LF shape depends on the period
 // only through ratios (ti/Tp = k / (Ra T0), tau = (k/T0 - Ra) / (Rk (1 - Ra))), so an onset's true period
-// 1/f0 moves the fp64 value by ~1e-11 relative (the 1e-12 guards) — below fp32 resolution except on rare ties.
+// 1/f0 moves tau by 1e-12 |f0 - sr/T0| / (Rk (1 - Ra)) relative (the guards): a rare fp32 tie inside the clamps, up to 3 * 2^-24 of the value at a clamped T0 = 3 (tests/pulse_ref.py).
 static_assert((int64_t)PULSE_TAB_MAX * (PULSE_TAB_MAX + 1) / 2 < (1ll << 31), "32-bit row offsets");
 __device__ __forceinline__ int pulse_tab_row(int T0) { return T0 * (T0 - 1) / 2 - 3; }
 

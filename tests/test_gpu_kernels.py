@@ -103,7 +103,7 @@ def test_pulse_train_against_reference(ctx):
 
 def test_pulse_train_other_lf_models_against_reference(ctx):
     """goofer_pulse_model: Ra / Rg / Rk other than gf.synthesize's constants (GOOFER.py:474, 508-519) against pulse trains the
-    reference wrote — the shape table (T0 <= 2048) and the on-the-fly path (f0 18.3 Hz: T0 = 2410) — through the handle and
+    reference wrote — rows of the shape table up to T0 = 2410 (f0 18.3 Hz; tests/test_gpu_pulse_train.py goes on to 8192) — through the handle and
     through core.pulse_train_numba, which puts the constants back; a new plan starts from the constants as well."""
     from goofer_amd import core
     g = golden("pulse_train_lf")
