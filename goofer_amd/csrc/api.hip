@@ -504,7 +504,7 @@ int goofer_counter(goofer_ctx *ctx, const char *name, int64_t *value)
 // Returns the byte size.
 int64_t goofer_debug_fetch(goofer_ctx *ctx, int which, void *host_out, int64_t capacity_bytes)
 {
-    if (!ctx || which < 0 || which >= 16 || !ctx->dbg_ptr[which]) return GOOFER_EINVAL;
+    if (!ctx || which < 0 || which >= 17 || !ctx->dbg_ptr[which]) return GOOFER_EINVAL;
     if (int rc = goofer_check(ctx)) return rc;
     size_t nb = ctx->dbg_bytes[which] < (size_t)capacity_bytes ? ctx->dbg_bytes[which] : (size_t)capacity_bytes;
     if (hipMemcpy(host_out, ctx->dbg_ptr[which], nb, hipMemcpyDeviceToHost) != hipSuccess) return GOOFER_EHIP;
@@ -609,6 +609,7 @@ int goofer_set_option(goofer_ctx *ctx, const char *name, int value)
     if (!strcmp(name, "sa_table")) { ctx->sa_table = value != 0; return GOOFER_OK; }
     if (!strcmp(name, "legacy_wave")) { ctx->legacy_wave = value != 0; return GOOFER_OK; }
     if (!strcmp(name, "mask_flags")) { ctx->mask_flags = value != 0; return GOOFER_OK; }
+    if (!strcmp(name, "mask_sparse")) { ctx->mask_sparse = value != 0; return GOOFER_OK; }
     if (!strcmp(name, "value_f64")) { ctx->value_f64 = value != 0; return GOOFER_OK; }
     if (!strcmp(name, "rate_lds")) { ctx->rate_lds = value != 0; return GOOFER_OK; }
     if (!strcmp(name, "limit_skip")) { ctx->limit_skip = value != 0; return GOOFER_OK; }
@@ -678,7 +679,7 @@ int goofer_pulse_train(goofer_ctx *ctx, const float *f0, const int64_t *sample_o
         cnt = a.take<int32_t>(n_notes + 16);
     });
     if (rc) return rc;
-    for (int i = 0; i < 16; ++i) ctx->dbg_ptr[i] = nullptr;
+    for (int i = 0; i < 17; ++i) ctx->dbg_ptr[i] = nullptr;
     ctx->dbg_ptr[13] = cnt; ctx->dbg_bytes[13] = n_notes * sizeof(int32_t);
     ctx->dbg_ptr[14] = oidx; ctx->dbg_bytes[14] = slots * sizeof(int32_t);
     return launch_pulse_train(ctx, f0, 1.0f, sample_off, n_notes, total_samples, pulse, inc, onsets, oidx, cnt, ctx->ovf_flag, st);
@@ -919,7 +920,7 @@ int goofer_smooth_mask_ds(goofer_ctx *ctx, const float *mask, const int64_t *sam
     HIP_TRY(ctx, hipStreamSynchronize(st));                                            // the host vector goes out of scope
     double acc = 0.0;
     for (double tv : taps) acc += tv * 1.0;
-    if ((rc = launch_mask_short(ctx, mask, sample_off, n_notes, total_samples, d_taps, radius, acc, short_s, nullptr, nullptr, st))) return rc;
+    if ((rc = launch_mask_short(ctx, mask, sample_off, n_notes, total_samples, d_taps, radius, acc, short_s, nullptr, nullptr, false, st))) return rc;
     return launch_mask_upsample(ctx, short_s, sample_off, n_notes, total_samples, steps, fast_interp != 0, out, st);
 }
 

@@ -885,7 +885,12 @@ struct sa_kernarg {                                          // k_sample_assembl
     const int2 *tile_notes;
 };
 // bad: mask_vote of every live mask value of this thread, or-ed into
-template <int SA_SPT, bool FLAGS>
+// SPARSE (with FLAGS): a wave whose live mask values are all +0.0f or all 1.0f to the bit stores none of them and says so by
+// MASK_UNSTORED in every lane's `bad` (the kernel puts it into the wave's flag byte).  The vote is taken behind the fp64 curve and
+// in front of the flag pointer's load and the stores, where mv[] and fo[] are the only arrays live: it crosses nothing, and its
+// verdict lives on in a vector register the kernel already has — as a scalar pair beside the flag pointer it made 98 scalar
+// registers.  By the bits and not by ==, so that a -0.0f, which the flags count as a zero, is stored and read back as what it is.
+template <int SA_SPT, bool FLAGS, bool SPARSE>
 __device__ __forceinline__ void sample_assemble_fast(const goofer_assembly &a, const goofer_note_plan &p, int64_t g0, int64_t total_samples,
                                                      unsigned &bad, unsigned char *&flag_dst)
 {
@@ -948,6 +953,16 @@ __device__ __forceinline__ void sample_assemble_fast(const goofer_assembly &a, c
         const double hz = 440.0 * exp2_poly(div_by(midi - 69.0, 12.0, 0.083333333333333329));   // RN(1/12)
         fo[u] = (float)((double)mv[u] * hz);
     }
+    if (FLAGS && SPARSE) {
+        bool z = true, o = true;
+#pragma unroll
+        for (int u = 0; u < SA_SPT; ++u) {
+            const unsigned bits = __float_as_uint(mv[u]);
+            z &= !live[u] || bits == 0u;
+            o &= !live[u] || bits == 0x3f800000u;
+        }
+        if (__all(z) || __all(o)) bad |= MASK_UNSTORED;
+    }
     if (FLAGS) {
         // the flag pointer's scalar load goes out here, behind the fp64 curve (tied to its last result, or the compiler issues it at the
         // kernel's entry and the pointer costs two scalar registers all the way), and arrives while the stores are issued
@@ -958,7 +973,7 @@ __device__ __forceinline__ void sample_assemble_fast(const goofer_assembly &a, c
     for (int u = 0; u < SA_SPT; ++u) {
         const int64_t g = g0 + threadIdx.x + (int64_t)u * blockDim.x;
         if (live[u]) {
-            mask_out[g] = mv[u];
+            if (!(FLAGS && SPARSE) || !(bad & MASK_UNSTORED)) mask_out[g] = mv[u];
             f0_out[g] = fo[u];
         }
     }
@@ -1002,7 +1017,10 @@ __global__ __launch_bounds__(256) void k_sample_tile_notes(const goofer_note_pla
 // TABLE: the notes of the tile's first and last sample come from k_sample_tile_notes' table, one scalar load (the index of a
 // plan that is read next: held inside the batch whatever the table says).  Without it the first wave searches the plans for
 // both — two rounds of 64 loads across the plans' 300-byte stride each — and the other three wait at a barrier for the answer.
-template <int SA_SPT, bool FLAGS, bool TABLE>
+// SPARSE (render_link::mask_sparse; with FLAGS): a wave of the fast path whose values are all 0.0f or all 1.0f writes its byte with
+// MASK_UNSTORED set and not its 256 mask values — on the timed route nothing reads them but the frame picks and k_mask_short's staged
+// windows, which ask the byte first (mask_value).  The other paths (a tile of two notes, fry, velocity, 'pd' / 'sj') store as ever.
+template <int SA_SPT, bool FLAGS, bool TABLE, bool SPARSE = false>
 __global__ __launch_bounds__(256) void k_sample_assemble(const goofer_assembly a, int64_t total_samples, int fast, unsigned char *__restrict__ tile_flags,
                                                          const int2 *__restrict__ tile_notes)
 {
@@ -1034,7 +1052,7 @@ __global__ __launch_bounds__(256) void k_sample_assemble(const goofer_assembly a
         const goofer_note_plan &p = a.notes[n_lo];           // uniform note: the 300-byte plan comes in through scalar loads
         if (fast && !p.vel_active && p.fry_dir == 0 && !(p.pd_on && a.bend_out) && !a.f0_mul_out && p.n_out < (1 << 21) && p.tail_len < (1 << 24) &&
             p.tail_len > 0 && p.n_bend >= 1) {
-            sample_assemble_fast<SA_SPT, FLAGS>(a, p, g0, total_samples, bad, flag_dst);
+            sample_assemble_fast<SA_SPT, FLAGS, SPARSE>(a, p, g0, total_samples, bad, flag_dst);
         } else {
 #pragma unroll
             for (int u = 0; u < SA_SPT; ++u) {
@@ -1052,12 +1070,12 @@ __global__ __launch_bounds__(256) void k_sample_assemble(const goofer_assembly a
         }
     }
     if (FLAGS) {
-        const int bits = (__any(bad & 1u) ? 1 : 0) | (__any(bad & 2u) ? 2 : 0);
+        const int bits = (__any(bad & 1u) ? 1 : 0) | (__any(bad & 2u) ? 2 : 0) | (SPARSE && __any(bad & MASK_UNSTORED) ? (int)MASK_UNSTORED : 0);
         // (the slow paths read the pointer here, from the kernarg segment: held in two scalar registers across the kernel it made 98 of them where
         // 96 is the most that leaves eight waves per SIMD — alone the kernel went from 0.209 to 0.227 ms, and beside k_env_edit,
         // which then found room on every SIMD, to twice its time)
         if (!flag_dst) flag_dst = COLD(sa_kernarg, tile_flags);
-        if ((threadIdx.x & (WAVE - 1)) == 0) flag_dst[4 * (size_t)blockIdx.x + (threadIdx.x >> 6)] = (unsigned char)bits;
+        if ((threadIdx.x & (WAVE - 1)) == 0) flag_dst[4 * (size_t)blockIdx.x + (threadIdx.x >> 6)] = (unsigned char)bits;   // = mask_flag_index of the wave's samples (common.h)
     }
 }
 
@@ -1152,7 +1170,12 @@ int launch_assemble(goofer_ctx *ctx, const goofer_assembly *a, int *row_note_edi
         }
         unsigned char *const fl = link.tile_flags_dst;
 #define SAMPLE_ASSEMBLE(F, T) hipLaunchKernelGGL((k_sample_assemble<spt, F, T>), sgrid, dim3(256), 0, fst, *a, a->total_samples, sa_fast, fl, (const int2 *)tile_notes)
-        if (fl) {
+#define SAMPLE_ASSEMBLE_SPARSE(T) hipLaunchKernelGGL((k_sample_assemble<spt, true, T, true>), sgrid, dim3(256), 0, fst, *a, a->total_samples, sa_fast, fl, (const int2 *)tile_notes)
+        if (fl && link.mask_sparse) {
+            if (tile_notes) SAMPLE_ASSEMBLE_SPARSE(true);
+            else SAMPLE_ASSEMBLE_SPARSE(false);
+            link.tile_flags = fl;
+        } else if (fl) {
             if (tile_notes) SAMPLE_ASSEMBLE(true, true);
             else SAMPLE_ASSEMBLE(true, false);
             link.tile_flags = fl;
@@ -1161,6 +1184,7 @@ int launch_assemble(goofer_ctx *ctx, const goofer_assembly *a, int *row_note_edi
             else SAMPLE_ASSEMBLE(false, false);
         }
 #undef SAMPLE_ASSEMBLE
+#undef SAMPLE_ASSEMBLE_SPARSE
         LAUNCH_CHECK(ctx);
         HIP_TRY(ctx, mark(2, 1, fst));
         if (link.fork_early && ctx->ev_f0) {

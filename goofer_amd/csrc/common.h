@@ -84,6 +84,9 @@ struct render_link {
     bool want_tile_flags = false;         // carve tile_flags_dst (assemble_batch), where the f0 / mask kernel also leaves a word per SA_TILE samples
     unsigned char *tile_flags_dst = nullptr;   // of the mask it writes: four bytes, one per wave, bit 0: some value is not == 0.0f, bit 1: some value
                                           // is not == 1.0f (word & 0x01010101 == 0: the tile is all zeros, & 0x02020202 == 0: all ones)
+    bool mask_sparse = false;             // the f0 / mask kernel may leave the mask values of a wave unwritten where one byte says them all (MASK_UNSTORED):
+                                          // decided by goofer_render_batch from synth_route::sparse_ok, cleared by the assembly when it writes no flags; the
+                                          // synthesis then reads the mask through mask_value() only
     // answered by the assembly
     const float *f0_ready = nullptr;      // the f0 array ev_f0 stands for (null: no event recorded)
     bool f0_side = false;                 // the f0 / mask kernel ran on the side stream, in front of the pulse chain it feeds: the caller's
@@ -92,6 +95,25 @@ struct render_link {
     const unsigned char *tile_flags = nullptr;   // the tile flags of the mask as the f0 / mask kernel wrote it (ready where f0 / mask are), for
                                           // k_mask_short; null: none were written
 };
+
+// The tile-flag byte of sample g of the concatenated axis: k_sample_assemble<4> gives wave w of the workgroup of tile g / SA_TILE the
+// four 64-sample strips at 64 w + 256 u of the tile, and its byte is the w-th of the tile's word.  The kernel's own store of the
+// byte is this map for the samples of thread threadIdx.x of workgroup blockIdx.x, written out there as 4 * blockIdx.x +
+// (threadIdx.x >> 6): through this function the same instructions came out in another order, and the instantiations from before
+// the sparse mask are kept instruction for instruction.
+__host__ __device__ __forceinline__ int64_t mask_flag_index(int64_t g) { return 4 * (g / SA_TILE) + (((g % SA_TILE) & 255) >> 6); }
+// bit 2 of a flag byte (render_link::mask_sparse only): the wave's 256 values are all 0.0f or all 1.0f to the bit and were NOT stored;
+// bit 0 then says which.  (The two words k_mask_short masks the bytes with do not see the bit.)
+#define MASK_UNSTORED 4u
+// mask[g] where the mask may be sparse (`sparse_flags`: render_link::tile_flags under mask_sparse, else null).  Both loads go out
+// together — the array is allocated whether or not the wave stored, and what an unstored place holds is discarded.
+__device__ __forceinline__ float mask_value(const float *__restrict__ mask, const unsigned char *__restrict__ sparse_flags, int64_t g)
+{
+    const float v = mask[g];
+    if (!sparse_flags) return v;
+    const unsigned f = sparse_flags[mask_flag_index(g)];
+    return (f & MASK_UNSTORED) ? ((f & 1u) ? 1.0f : 0.0f) : v;
+}
 
 struct goofer_ctx {
     int device = 0;
@@ -106,8 +128,8 @@ struct goofer_ctx {
     void *small = nullptr;        // small staging buffer for taps etc. (its regions: SMALL_* below)
     size_t small_bytes = 0;
     // device pointers of the last synth batch's intermediates (goofer_debug_fetch; tests only)
-    const void *dbg_ptr[16] = {nullptr};
-    size_t dbg_bytes[16] = {0};
+    const void *dbg_ptr[17] = {nullptr};
+    size_t dbg_bytes[17] = {0};
     bool overlap = true;          // noise spectra + mask smoothing on a side stream, beside the latency-bound pulse walk
     hipStream_t side = nullptr;   // created on first use
                                   // ... with the highest stream priority (measured: 2.41 ms per step against 2.50 at the default, 2.54 at the lowest)
@@ -134,6 +156,8 @@ struct goofer_ctx {
     bool prof_stems = false;      // the last profiled batch ran the stem-split path (stage order differs)
     bool mask_flags = true;       // goofer_render_batch: k_sample_assemble leaves tile flags of the mask and k_mask_short answers flat windows from
                                   // them without loading the mask (option "mask_flags"; 0: A/B, the same bits)
+    bool mask_sparse = true;      // goofer_render_batch, walker route, mix_only: k_sample_assemble does not store the mask values of a wave that are all 0.0f or
+                                  // all 1.0f, and the picks / k_mask_short take them from the wave's flag byte (option "mask_sparse"; 0: A/B, the same bits)
     bool sa_fast = true;          // k_sample_assemble: the branch-free path with all of a thread's loads in flight together (option "sa_fast"; 0: A/B)
     bool sa_table = true;         // k_sample_assemble reads the notes of its tile from k_sample_tile_notes' table instead of searching the plans
                                   // (option "sa_table"; 0: A/B, the same bits)

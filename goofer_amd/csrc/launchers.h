@@ -190,10 +190,10 @@ int launch_irfft_ola3(goofer_ctx *ctx, const float2 *S_h, const float2 *S_u, con
                       float *note_peak, hipStream_t st);
 int launch_stem_peak(goofer_ctx *ctx, const float *harm, const float *uv, const float *bre, const int64_t *sample_off, int n_notes,
                      int64_t total, float *note_peak, hipStream_t st);
-// tile_flags: render_link::tile_flags of this very mask, or null; counters: goofer_ctx::ovf_flag + MASK_COUNTERS (the slotted words of the two segment counters), or null
+// tile_flags: render_link::tile_flags of this very mask, or null (sparse: render_link::mask_sparse — the mask is read through mask_value); counters: goofer_ctx::ovf_flag + MASK_COUNTERS (the slotted words of the two segment counters), or null
 int launch_mask_short(goofer_ctx *ctx, const float *mask, const int64_t *sample_off, int n_notes, int64_t total_samples,
                       const double *d_taps, int radius, double tap_sum, double *short_s, const unsigned char *tile_flags,
-                      int32_t *counters, hipStream_t st);
+                      int32_t *counters, bool sparse, hipStream_t st);
 int launch_apply_gain(goofer_ctx *ctx, float *harm, float *uv, float *bre, float *rec, float *mix, const int64_t *sample_off, int n_notes,
                       int64_t total_samples, const goofer_note_params *params, const float *note_peak, bool write_stems, hipStream_t st);
 int launch_ola3_gains(goofer_ctx *ctx, const float *fr_h, const float *fr_u, const float *fr_b, const float *note_mag,
@@ -204,7 +204,7 @@ int launch_ola3_gains(goofer_ctx *ctx, const float *fr_h, const float *fr_u, con
 // stems.hip
 bool stems_supported(const goofer_plan_t &p);
 int launch_frame_picks(goofer_ctx *ctx, const int64_t *frame_off, const int *frame_note, int64_t F, const int64_t *sample_off,
-                       const float *f0, const float *mask, float2 *picks, hipStream_t st);
+                       const float *f0, const float *mask, const unsigned char *sparse_flags, float2 *picks, hipStream_t st);
 int launch_noise_stems(goofer_ctx *ctx, const float *env, int ld, const int64_t *row_src, const float *phi, int64_t F,
                        const int *frame_note, const int64_t *frame_off, const int64_t *sample_off, const float2 *picks,
                        const goofer_note_params *params, uint64_t seed, bool preblurred, const double *short_s, const double *steps,

@@ -29,14 +29,18 @@
 // knots are 0.0 (tap_sum).  A segment whose quarters are all settled that way is written at once: no mask load, no LDS
 // window, no barrier.  Otherwise the window is staged for the unsettled quarters only.  Every wave reads the same flag words
 // (one load, two votes), so the decisions are workgroup-uniform.
+// sparse (render_link::mask_sparse): a wave of the kernel that wrote the mask left its values unwritten where its flag byte carries
+// MASK_UNSTORED.  A settled quarter never asked for them; the staged window of an unsettled one can reach into such a wave (its own
+// tile's other waves, the tiles under its halo), and takes those values from the bytes (mask_value).
 // counters (or null): segments answered from the flags / segments that staged a window, one atomic per segment, each counter
 // spread over MASK_COUNTER_SLOTS words by workgroup (common.h).
 __global__ __launch_bounds__(256) void k_mask_short(const float *__restrict__ mask, const int64_t *__restrict__ sample_off,
                                                     int n_notes, int64_t total_short, const double *__restrict__ taps, int radius,
                                                     double *__restrict__ short_s, double tap_sum,
-                                                    const unsigned char *__restrict__ tile_flags, int32_t *__restrict__ counters)
+                                                    const unsigned char *__restrict__ tile_flags, int32_t *__restrict__ counters, int sparse)
 {
     extern __shared__ __align__(16) unsigned char smem[];
+    const unsigned char *const sparse_flags = sparse ? tile_flags : nullptr;
     double *s_taps = reinterpret_cast<double *>(smem);
     float *s_all = reinterpret_cast<float *>(s_taps + (2 * radius + 1));          // 4 * MS_MAXWIN floats
     __shared__ int s_lo[2];
@@ -64,7 +68,6 @@ __global__ __launch_bounds__(256) void k_mask_short(const float *__restrict__ ma
             if (s1 <= s0) continue;                          // workgroup-uniform
             const int64_t q0 = s0 - sb;
             const int len = (int)(s1 - s0);
-            const float *m = mask + base;
             // bit k of flat0 (flat1): the flags say every window of quarter k is all zeros (ones)
             unsigned flat0 = 0u, flat1 = 0u;
             const int nq = (len + MS_QUART - 1) / MS_QUART;
@@ -98,7 +101,7 @@ __global__ __launch_bounds__(256) void k_mask_short(const float *__restrict__ ma
             for (int w = threadIdx.x; w < len + 2 * radius; w += blockDim.x) {
                 bool want = flat == 0u;                      // a settled quarter's part of the window is not read
                 for (int k = 0; k < nq && !want; ++k) want = !((flat >> k) & 1u) && w >= k * MS_QUART && w < (k + 1) * MS_QUART + 2 * radius;
-                if (want) s_all[w] = m[MASK_DS * reflect_index(q0 - radius + w, ns)];
+                if (want) s_all[w] = mask_value(mask, sparse_flags, base + MASK_DS * reflect_index(q0 - radius + w, ns));
             }
             __syncthreads();
             for (int c0 = wv * WAVE; c0 < len; c0 += 4 * WAVE) {
@@ -138,9 +141,8 @@ __global__ __launch_bounds__(256) void k_mask_short(const float *__restrict__ ma
         const int64_t base = sample_off[note], n = sample_off[note + 1] - base;
         const int64_t ns = (n + MASK_DS - 1) / MASK_DS;
         if (q >= ns) continue;
-        const float *m = mask + base;
         double acc = 0.0;
-        for (int j = 0; j <= 2 * radius; ++j) acc += s_taps[j] * (double)m[MASK_DS * reflect_index(q + j - radius, ns)];
+        for (int j = 0; j <= 2 * radius; ++j) acc += s_taps[j] * (double)mask_value(mask, sparse_flags, base + MASK_DS * reflect_index(q + j - radius, ns));
         short_s[g] = acc;
     }
 }
@@ -1071,13 +1073,13 @@ int launch_stem_peak(goofer_ctx *ctx, const float *harm, const float *uv, const 
 
 int launch_mask_short(goofer_ctx *ctx, const float *mask, const int64_t *sample_off, int n_notes, int64_t total_samples,
                       const double *d_taps, int radius, double tap_sum, double *short_s, const unsigned char *tile_flags,
-                      int32_t *counters, hipStream_t st)
+                      int32_t *counters, bool sparse, hipStream_t st)
 {
     int64_t total_short = total_samples / MASK_DS + n_notes;
     if (total_short <= 0) return GOOFER_OK;
     hipLaunchKernelGGL(k_mask_short, dim3((unsigned)((total_short + MS_TILE - 1) / MS_TILE)), dim3(256),
                        sizeof(double) * (2 * radius + 1) + sizeof(float) * 4 * MS_MAXWIN, st, mask, sample_off, n_notes, total_short,
-                       d_taps, radius, short_s, tap_sum, tile_flags, counters);
+                       d_taps, radius, short_s, tap_sum, tile_flags, counters, sparse && tile_flags ? 1 : 0);
     LAUNCH_CHECK(ctx);
     return GOOFER_OK;
 }

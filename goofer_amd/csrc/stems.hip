@@ -1088,7 +1088,7 @@ __global__ __launch_bounds__(FIN_THREADS) void k_note_finish(float *__restrict__
 // per-frame picks of the per-sample arrays: x[::hop] edge-padded to the frame count (GOOFER.py:1104-1106)
 __global__ void k_frame_picks(const int64_t *__restrict__ frame_off, const int *__restrict__ frame_note, int64_t total_frames,
                               const int64_t *__restrict__ sample_off, const float *__restrict__ f0, const float *__restrict__ mask,
-                              int hop, float2 *__restrict__ picks)
+                              const unsigned char *__restrict__ sparse_flags, int hop, float2 *__restrict__ picks)
 {
     const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= total_frames) return;
@@ -1098,7 +1098,7 @@ __global__ void k_frame_picks(const int64_t *__restrict__ frame_off, const int *
     float2 pv = make_float2(0.f, 0.f);
     if (n > 0) {
         const int64_t at = pick_index(t, n, hop);
-        pv = make_float2(f0[base + at], mask[base + at]);
+        pv = make_float2(f0[base + at], mask_value(mask, sparse_flags, base + at));
     }
     picks[f] = pv;
 }
@@ -1106,11 +1106,11 @@ __global__ void k_frame_picks(const int64_t *__restrict__ frame_off, const int *
 bool stems_supported(const goofer_plan_t &p) { return p.n_fft == 1024 && p.hop * 4 == p.n_fft; }
 
 int launch_frame_picks(goofer_ctx *ctx, const int64_t *frame_off, const int *frame_note, int64_t F, const int64_t *sample_off,
-                       const float *f0, const float *mask, float2 *picks, hipStream_t st)
+                       const float *f0, const float *mask, const unsigned char *sparse_flags, float2 *picks, hipStream_t st)
 {
     if (F <= 0) return GOOFER_OK;
     hipLaunchKernelGGL(k_frame_picks, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, st, frame_off, frame_note, F, sample_off, f0, mask,
-                       ctx->plan.hop, picks);
+                       sparse_flags, ctx->plan.hop, picks);
     LAUNCH_CHECK(ctx);
     return GOOFER_OK;
 }

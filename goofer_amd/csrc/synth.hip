@@ -16,7 +16,8 @@
 __device__ __forceinline__ void frame_pick_and_row(int64_t f, int note, const int64_t *__restrict__ frame_off,
                                                    const int64_t *__restrict__ env_off, int64_t *__restrict__ row_src,
                                                    const int64_t *__restrict__ sample_off, const float *__restrict__ f0,
-                                                   const float *__restrict__ mask, int hop, float2 *__restrict__ picks)
+                                                   const float *__restrict__ mask, int hop, float2 *__restrict__ picks,
+                                                   const unsigned char *__restrict__ sparse_flags = nullptr)
 {
     int64_t t = f - frame_off[note];
     if (picks) {
@@ -25,7 +26,7 @@ __device__ __forceinline__ void frame_pick_and_row(int64_t f, int note, const in
         if (n > 0) {
             int64_t at = t * hop;
             if (at >= n) at = ((n - 1) / hop) * hop;          // edge-padded: the last pick
-            pv = make_float2(f0[base + at], mask[base + at]);
+            pv = make_float2(f0[base + at], mask_value(mask, sparse_flags, base + at));
         }
         picks[f] = pv;
     }
@@ -51,7 +52,7 @@ __global__ void k_row_src(const int64_t *__restrict__ frame_off, const int64_t *
 __global__ void k_frame_maps(const int64_t *__restrict__ frame_off, const int64_t *__restrict__ env_off, int n_notes, int64_t total_frames,
                              int *__restrict__ frame_note, int64_t *__restrict__ row_src, const int64_t *__restrict__ sample_off,
                              const float *__restrict__ f0, const float *__restrict__ mask, int hop, float2 *__restrict__ picks,
-                             double *__restrict__ steps, float *__restrict__ note_mag)
+                             double *__restrict__ steps, float *__restrict__ note_mag, const unsigned char *__restrict__ sparse_flags)
 {
     const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (f < 2 * (int64_t)n_notes) note_mag[f] = 0.f;
@@ -64,7 +65,7 @@ __global__ void k_frame_maps(const int64_t *__restrict__ frame_off, const int64_
     if (f >= total_frames) return;
     const int note = csr_find(frame_off, n_notes, f);
     frame_note[f] = note;
-    frame_pick_and_row(f, note, frame_off, env_off, row_src, sample_off, f0, mask, hop, picks);
+    frame_pick_and_row(f, note, frame_off, env_off, row_src, sample_off, f0, mask, hop, picks, sparse_flags);
 }
 
 // f0 *= pitch_shift (GOOFER.py:995), fp32.  1024 samples per workgroup, 16-byte accesses when the tile sits in one note.
@@ -115,6 +116,7 @@ struct synth_route {
     bool skip_frames;                // ola_split with the noise stems' exact sparsity decided per frame up front (k_frame_skip)
     bool side_on, early;             // the pulse chain on the side stream (early: forked from goofer_render_batch's ev_f0)
     bool f0_alias, picks_on;         // the input f0 is the scaled f0; the map kernel takes the per-frame (f0, mask) picks
+    bool sparse_ok;                  // nothing of the route reads b->mask but the picks and k_mask_short, and the caller is not handed it
 };
 
 static synth_route synth_route_of(const goofer_ctx *ctx, const goofer_batch *b, const render_link &link)
@@ -148,6 +150,10 @@ static synth_route synth_route_of(const goofer_ctx *ctx, const goofer_batch *b, 
     // the picks ride on the map kernel when the scaled f0 is final at that point of the caller's stream: nothing jitters it in
     // place later, and it is not being produced on the side stream
     r.picks_on = !r.jit_f0 && !r.sub_jit && !(r.early && !r.f0_alias);
+    // The voicing mask may stay sparse (render_link::mask_sparse) on the walker route — no sub-harmonic layer, no volume jitter, and the
+    // spectra routes' k_harm_shape / k_noise_spectra are not run — without the f0 jitter, which reads it sample by sample, in a
+    // mix_only batch: there the per-sample arrays of the call are scratch to the caller (goofer_batch::mix_only), the mask with them.
+    r.sparse_ok = ctx->mask_sparse && r.walkers && !r.jit_f0 && !r.jit_vol && !r.sub_on && !r.sub_jit && b->mix_only && (b->mix || b->rec);
     return r;
 }
 
@@ -280,15 +286,17 @@ struct synth_call {
     int64_t F, N;
     int n;
 
+    // the flag bytes the mask is to be read through (mask_value), or null: the mask is whole
+    const unsigned char *sparse_flags() const { return link.mask_sparse ? link.tile_flags : nullptr; }
     int mask_short() const
     {
         // (link.tile_flags: goofer_render_batch, the flags of b->mask as the f0 kernel wrote it — no kernel of any route writes the mask)
         return launch_mask_short(ctx, b->mask, b->sample_off, n, N, ctx->mask_taps, ctx->mask_taps_radius, ctx->mask_taps_sum, s.short_s,
-                                 link.tile_flags, ctx->ovf_flag ? ctx->ovf_flag + MASK_COUNTERS : nullptr, st);
+                                 link.tile_flags, ctx->ovf_flag ? ctx->ovf_flag + MASK_COUNTERS : nullptr, link.mask_sparse, st);
     }
     int late_picks() const
     {
-        return r.picks_on ? GOOFER_OK : launch_frame_picks(ctx, b->frame_off, s.frame_note, F, b->sample_off, s.f0s, b->mask, s.picks, st);
+        return r.picks_on ? GOOFER_OK : launch_frame_picks(ctx, b->frame_off, s.frame_note, F, b->sample_off, s.f0s, b->mask, sparse_flags(), s.picks, st);
     }
     // aperiodic half of the stem-split path: the two noise stems straight to samples (needs the smoothed mask knots and the final
     // scaled f0, nothing of the pulse chain)
@@ -434,6 +442,7 @@ static int assemble_batch(goofer_ctx *ctx, const goofer_assembly *asmb, render_l
     });
     if (rc) return rc;
     link.tile_flags_dst = want_flags ? flags : nullptr;
+    if (!want_flags) link.mask_sparse = false;                // no bytes to say what was left out: the mask is written in full
     if (!a.edit_rows) a.edit_rows = edit_rows;
     return launch_assemble(ctx, &a, map_edit, map_edit + a.total_edit_rows, recs, want_table ? tile_notes : nullptr, link, st);
 }
@@ -448,6 +457,8 @@ static int synth_batch(goofer_ctx *ctx, const goofer_batch *b, render_link &link
     const int64_t F = b->total_frames, N = b->total_samples;
     const int n = b->n_notes;
     const synth_route r = synth_route_of(ctx, b, link);
+    if (link.mask_sparse && !(r.sparse_ok && link.tile_flags))
+        return goofer_fail(ctx, GOOFER_EINVAL, "the mask was left sparse for a route that reads it in full");
     synth_scratch s;
     int rc = carve_scratch(ctx, [&](arena &a) { carve_synth(a, p, r, F, N, n, b->ld, s); });
     if (rc) return rc;
@@ -462,6 +473,8 @@ static int synth_batch(goofer_ctx *ctx, const goofer_batch *b, render_link &link
                                    s.env_noise * sizeof(float), (N / 4 + n) * sizeof(double), n * sizeof(float), n * sizeof(float),
                                    n * sizeof(int32_t), s.slots * sizeof(int32_t), s.frame_skip ? (size_t)F : 0};
     for (int i = 0; i < 16; ++i) { ctx->dbg_ptr[i] = views[i]; ctx->dbg_bytes[i] = view_bytes[i]; }
+    ctx->dbg_ptr[16] = s.picks;                               // view 16: the per-frame (f0, mask) picks
+    ctx->dbg_bytes[16] = F * sizeof(float2);
 
     // mask-smoothing taps for this call's sigma; device copy cached on the handle (steady state:
     // no host work, no synchronisation)
@@ -505,7 +518,7 @@ static int synth_batch(goofer_ctx *ctx, const goofer_batch *b, render_link &link
         const int64_t threads = std::max<int64_t>(F, 2 * (int64_t)n);
         hipLaunchKernelGGL(k_frame_maps, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, b->frame_off, b->env_off, n, F, s.frame_note,
                            s.row_src, b->sample_off, (const float *)s.f0s, b->mask, p.hop, r.picks_on ? s.picks : (float2 *)nullptr, s.note_steps,
-                           s.note_mag);
+                           s.note_mag, c.sparse_flags());
     } else {
         hipLaunchKernelGGL(k_row_src, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, st, b->frame_off, b->env_off, s.frame_note, F, s.row_src,
                            b->sample_off, (const float *)s.f0s, b->mask, p.hop, r.picks_on ? s.picks : (float2 *)nullptr);
@@ -668,6 +681,8 @@ int goofer_render_batch(goofer_ctx *ctx, const goofer_assembly *asmb, const goof
     // behind.  Only when the synthesis reads the very array the assembly writes, over the same concatenated sample axis.
     link.want_tile_flags = ctx->mask_flags && asmb->mask_out && asmb->mask_out == b->mask && asmb->total_samples == b->total_samples &&
                            asmb->n_notes == b->n_notes;
+    // ... and where the route has no other reader of the mask than those of the flag bytes, the flat waves' values are not stored at all
+    link.mask_sparse = link.want_tile_flags && synth_route_of(ctx, b, link).sparse_ok;
     rc = assemble_batch(ctx, asmb, link, st);
     if (!rc) rc = synth_batch(ctx, b, link, st);
     // the synthesis did not come to place the wait (it refused its batch, or was not reached): f0 / mask are in flight on the side

@@ -574,7 +574,9 @@ class Renderer:
 
     def run(self, prep, seed: int = 0, keep_stems: bool = False, split: bool = False):
         """The device work of one batch (asynchronous): goofer_render_batch, i.e. assembly + synthesis as one call;
-        ``split=True`` issues goofer_assemble_batch and goofer_synth_batch separately (same results)."""
+        ``split=True`` issues goofer_assemble_batch and goofer_synth_batch separately (same results).
+        Without ``keep_stems`` and without a post chain the batch is rendered mix_only: the stems and ``prep["mask"]`` are scratch
+        then (library option "mask_sparse": the stretches of the mask that are all 0 or all 1 are not written)."""
         ctx = self.ctx
         par = prep["params"]
         noise_f0, noise_vol = prep["noise_f0"], prep["noise_vol"]

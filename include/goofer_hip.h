@@ -1036,6 +1036,10 @@ const char *goofer_profile_stage_name_ex(const goofer_ctx *ctx, int stage);   /*
  *   "mask_flags" 1 (default): goofer_render_batch has k_sample_assemble leave a word per 1024 samples of the voicing mask (all == 0,
  *               all == 1, neither) and k_mask_short answer the windows those words settle without loading the mask; 0: no flags
  *               (goofer_assemble_batch / goofer_synth_batch on their own and goofer_smooth_mask_ds never have them).  Same bits.
+ *   "mask_sparse" 1 (default): where goofer_render_batch writes those words, takes the stem walkers, renders mix_only and runs no
+ *               layer that reads the mask sample by sample (f0 / volume jitter, sub-harmonics), k_sample_assemble does not store
+ *               the 256 mask values of a wave that are all 0.0f or all 1.0f: the frame picks and k_mask_short take them from the
+ *               wave's byte.  `mask` is scratch in such a call, like the stems.  0: the mask is always written in full.  Same bits.
  *   "legacy_wave" 0 (default): goofer_legacy_normal_fill / _jobs give a job a workgroup of 256 threads; 1: one wave.  Same bits.
  *   "rate_lds"  1 (default): goofer_rate_convert stages the tap table in LDS where it fits in 160 KiB; 0: every lane reads its
  *               row from global memory, as it does for a table that does not fit.  Same bits.
