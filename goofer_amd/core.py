@@ -1052,15 +1052,17 @@ def resample_batch(signals, sr_in, sr_out, ctx=None):
     return [y[plan.out_off[i]:plan.out_off[i + 1]] for i in range(plan.n)]
 
 
-def limit_batch(signals, sr, ceiling=32767.0 / 32768.0, lookahead_ms=5.0, ctx=None):
+def limit_batch(signals, sr, ceiling=32767.0 / 32768.0, lookahead_ms=5.0, ctx=None, true_peak=False):
     """The look-ahead peak limiter over many signals in one device pass (goofer_amd.limit; goofer_limit): ``signals``, 1-D
     arrays at ``sr``, come back as a list of fp32 arrays of the same lengths whose samples stay within ``ceiling`` (0 < ceiling
     <= 1), with two fp32 arrays: per signal its greatest ``|x|`` and the smallest gain it was given (0 and 1 for an empty one).
     ``lookahead_ms``: how far ahead of a peak the gain starts to fall, and how long after it it recovers.  This project's own
-    definition (include/goofer_hip.h); a signal that never exceeds the ceiling comes back bit for bit."""
+    definition (include/goofer_hip.h); a signal that never exceeds the ceiling comes back bit for bit.  ``true_peak``: the
+    ceiling holds for the signal reconstructed between the samples too (goofer_limit_tp; ``sr`` of 8000 to 192000 Hz), and the
+    first statistic is the true peak."""
     from . import limit as LM
     xs = [np.ascontiguousarray(s, dtype=np.float32).reshape(-1) for s in signals]
-    plan = LM.plan(sr, [len(s) for s in xs], ceiling, lookahead_ms)
+    plan = LM.plan(sr, [len(s) for s in xs], ceiling, lookahead_ms, bool(true_peak))
     if not plan.n:
         return [], np.zeros(0, dtype=np.float32), np.zeros(0, dtype=np.float32)
     c = ctx or default_context()
@@ -1068,6 +1070,22 @@ def limit_batch(signals, sr, ceiling=32767.0 / 32768.0, lookahead_ms=5.0, ctx=No
     c.check()
     y = y.cpu().numpy()
     return [y[plan.in_off[i]:plan.in_off[i + 1]] for i in range(plan.n)], peak.cpu().numpy(), gain.cpu().numpy()
+
+
+def true_peak_batch(signals, sr, ctx=None):
+    """The true peak of many signals in one device pass (goofer_amd.limit; goofer_true_peak): ``signals``, 1-D arrays at ``sr``
+    (8000 to 192000 Hz); returns fp32 ``[n]``, per signal the greatest magnitude, linear, of the signal reconstructed at 4 times
+    its rate (2 times from 96 kHz on), 0 for an empty one — after ITU-R BS.1770-4 Annex 2, this project's own definition
+    (include/goofer_hip.h).  ``limit.dbtp`` makes dBTP of one."""
+    from . import limit as LM
+    xs = [np.ascontiguousarray(s, dtype=np.float32).reshape(-1) for s in signals]
+    plan = LM.true_peak_plan(sr, [len(s) for s in xs])
+    if not plan.n:
+        return np.zeros(0, dtype=np.float32)
+    c = ctx or default_context()
+    peak = c.true_peak(c.tensor(np.concatenate(xs + [np.zeros(1, dtype=np.float32)])), None, plan)
+    c.check()
+    return peak.cpu().numpy()
 
 
 def loudness_batch(signals, sr, target=None, max_gain_db=20.0, ctx=None):

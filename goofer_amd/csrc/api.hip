@@ -613,6 +613,7 @@ int goofer_set_option(goofer_ctx *ctx, const char *name, int value)
     if (!strcmp(name, "value_f64")) { ctx->value_f64 = value != 0; return GOOFER_OK; }
     if (!strcmp(name, "rate_lds")) { ctx->rate_lds = value != 0; return GOOFER_OK; }
     if (!strcmp(name, "limit_skip")) { ctx->limit_skip = value != 0; return GOOFER_OK; }
+    if (!strcmp(name, "limit_tp_skip")) { ctx->limit_tp_skip = value != 0; return GOOFER_OK; }
     if (!strcmp(name, "compress_skip")) { ctx->compress_skip = value != 0; return GOOFER_OK; }
     if (!strcmp(name, "compress_store")) { ctx->compress_store = value != 0; return GOOFER_OK; }
     if (!strcmp(name, "walk_run")) { ctx->walk_run = value < 0 ? 0 : value; return GOOFER_OK; }   // clamped per kernel where the run is chosen (walk_run_choice)

@@ -166,6 +166,7 @@ struct goofer_ctx {
     bool legacy_wave = false;     // k_legacy_normal_fill: one wave per note instead of one 256-thread workgroup (option "legacy_wave"; A/B, the same bits)
     bool rate_lds = true;         // goofer_rate_convert: the tap table staged in LDS where it fits (option "rate_lds"; 0: read from global memory, A/B, the same bits)
     bool limit_skip = true;       // goofer_limit: a tile with nothing above the ceiling, halo included, copies its samples (option "limit_skip"; 0: the full arithmetic for every tile, A/B, the same bits)
+    bool limit_tp_skip = true;    // goofer_limit_tp: a tile whose true-peak envelope never exceeds the ceiling, halo included, copies its samples (option "limit_tp_skip"; 0: the full arithmetic for every tile, A/B, the same bits)
     bool compress_skip = true;    // goofer_compress: a sample under the knee's lower end is found by one compare and its logarithm is not taken (option "compress_skip"; 0: A/B, equal within rounding)
     bool compress_store = false;  // goofer_compress: xl is written to scratch by the first pass and read back by the other two instead of being computed again (option "compress_store"; A/B, the same bits)
     int walk_run = 0;             // frames per wave of the four frame walkers (option "walk_run"; 0: chosen from the device, N > 0: N clamped to the

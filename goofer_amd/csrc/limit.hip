@@ -20,6 +20,14 @@
 // Statistics: a butterfly per wave (peak_in: then over the workgroup's waves through LDS), then an integer atomic on the fp32
 // bits (max for peak_in, min for min_gain; exact for non-negative values, any order) where the value would move the word, into
 // words a small kernel in front has set to 0 and 1.  No scratch buffer.
+//
+// True-peak detection (the header's "true-peak detection" section; table: goofer_host_true_peak_plan).  k_limit<true> differs
+// in step 1 only: x of [t0 - 2W - Z, t0 + T + 2W + Z) goes to LDS first (where B will live later), a thread then makes the
+// envelope e of eight consecutive positions from a window of 32 staged samples sliding through its registers (tp_envelope: the
+// R - 1 rows of 24 taps by scalar loads, the nine interval maxima u the eight positions touch), and r = c / e.  Step 5 cannot
+// make r again from x, so the r of the tile's own samples waits in a third LDS array.  A tile whose e never exceeds c, halo
+// included, copies its samples (option "limit_tp_skip").  k_true_peak, the meter, is step 1 alone on a tile with Z samples of
+// halo: the maximum of e, through limit_stat_max.
 #include "launchers.h"
 
 #define LM_THREADS 512
@@ -27,11 +35,20 @@
 #define LM_T GOOFER_LIMIT_TILE
 static_assert(LM_T == LM_THREADS * LM_SPT, "one workgroup of 512 threads per tile");
 #define LM_STAGE ((LM_T + 4 * GOOFER_LIMIT_MAX_LOOK) / LM_THREADS)   // entries of the r array per thread, at most
+#define TP_Z GOOFER_TP_ZEROS
+#define TP_K (2 * GOOFER_TP_ZEROS)     // taps of a row
+#define TP_CH LM_SPT                   // consecutive envelope values per thread and step
+#define TP_WIN (TP_CH + TP_K)          // staged samples they are made from
+static_assert(TP_WIN % 4 == 0 && TP_CH % 4 == 0, "the window is read as float4");
 
+// (min_gain may be null: the meter has a peak alone)
 __global__ __launch_bounds__(256) void k_limit_init(int n, float *__restrict__ peak_in, float *__restrict__ min_gain)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) { peak_in[i] = 0.0f; min_gain[i] = 1.0f; }
+    if (i < n) {
+        peak_in[i] = 0.0f;
+        if (min_gain) min_gain[i] = 1.0f;
+    }
 }
 
 __device__ __forceinline__ float limit_r(float a, float c) { return a > c ? __fdiv_rn(c, a) : 1.0f; }
@@ -53,9 +70,46 @@ __device__ __forceinline__ void limit_stat_min(float *p, float v)
     if (b < __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(w, b);
 }
 
+// e[0 .. TP_CH) of the positions p0 .. p0 + TP_CH - 1 of a signal.  X (LDS, 16-byte aligned) holds the samples of positions
+// p0 - Z .. p0 + TP_CH + Z - 1, zero outside the signal.  um[m] is u of position p0 - 1 + m, the interval between p0 - 1 + m and
+// p0 + m: sum_c h[c] X[m + c], in ascending c from +0.0f.  Every lane uses the same coefficient at a given tap (scalar loads).
+__device__ __forceinline__ void tp_envelope(const float *__restrict__ X, int R, const float *__restrict__ taps, int64_t p0, float *__restrict__ e)
+{
+    float win[TP_WIN], um[TP_CH + 1];
+#pragma unroll
+    for (int q = 0; q < TP_WIN / 4; ++q) {
+        const float4 v = reinterpret_cast<const float4 *>(X)[q];
+        win[4 * q] = v.x; win[4 * q + 1] = v.y; win[4 * q + 2] = v.z; win[4 * q + 3] = v.w;
+    }
+#pragma unroll
+    for (int m = 0; m <= TP_CH; ++m) um[m] = 0.0f;
+#pragma unroll 1
+    for (int ph = 0; ph < R - 1; ++ph) {
+        const float *__restrict__ h = taps + ph * TP_K;
+        float acc[TP_CH + 1];
+#pragma unroll
+        for (int m = 0; m <= TP_CH; ++m) acc[m] = 0.0f;
+#pragma unroll
+        for (int t = 0; t < TP_K; ++t) {
+            const float ht = h[t];
+#pragma unroll
+            for (int m = 0; m <= TP_CH; ++m) acc[m] = acc[m] + ht * win[m + t];
+        }
+#pragma unroll
+        for (int m = 0; m <= TP_CH; ++m) um[m] = fmaxf(um[m], fabsf(acc[m]));
+    }
+#pragma unroll
+    for (int i = 0; i < TP_CH; ++i) {
+        const float v = fmaxf(fabsf(win[i + TP_Z]), um[i + 1]);
+        e[i] = p0 + i == 0 ? v : fmaxf(v, um[i]);               // u[-1] = 0
+    }
+}
+
+template <bool TP>
 __global__ __launch_bounds__(LM_THREADS)
 void k_limit(const float *__restrict__ x, const int64_t *__restrict__ in_off, int n, int W, int span, const float *__restrict__ taps, float c,
-             const int32_t *__restrict__ tiles, float *__restrict__ out, float *__restrict__ peak_in, float *__restrict__ min_gain, int skip)
+             const int32_t *__restrict__ tiles, float *__restrict__ out, float *__restrict__ peak_in, float *__restrict__ min_gain, int skip,
+             int R, const float *__restrict__ tp_taps)
 {
     extern __shared__ __align__(16) float s_lim[];
     __shared__ float s_pk[LM_THREADS / 64];
@@ -73,16 +127,49 @@ void k_limit(const float *__restrict__ x, const int64_t *__restrict__ in_off, in
     // 1: r, the tile's peak, whether anything is above c
     float pk = 0.0f;
     bool over = false;
-    for (int k = tid; k < NA; k += LM_THREADS) {
-        const int64_t p = t0 - 2 * W + k;
-        float r = 1.0f;
-        if (p >= 0 && p < len) {
-            const float a = fabsf(xs[p]);
-            r = limit_r(a, c);
-            over |= a > c;
-            if (k >= 2 * W && k < 2 * W + LM_T) pk = fmaxf(pk, a);
+    if constexpr (TP) {
+        // x on [t0 - 2W - Z, t0 + T + 2W + Z + TP_CH) where B will live; the r of the tile's own samples behind it
+        const int NX = NA + TP_WIN;
+        float *__restrict__ X = B, *__restrict__ Rt = B + NX;
+        for (int k = tid; k < NX; k += LM_THREADS) {
+            const int64_t p = t0 - 2 * W - TP_Z + k;
+            X[k] = p >= 0 && p < len ? xs[p] : 0.0f;
         }
-        A[k] = r;
+        __syncthreads();
+        for (int k0 = tid * TP_CH; k0 < NA; k0 += LM_THREADS * TP_CH) {     // (NA is a multiple of 4: the last step may be half one)
+            const int64_t p0 = t0 - 2 * W + k0;
+            float e[TP_CH];
+            const bool inside = p0 + TP_CH > 0 && p0 < len;
+            if (inside) tp_envelope(X + k0, R, tp_taps, p0, e);
+#pragma unroll
+            for (int i = 0; i < TP_CH; ++i) {
+                const int k = k0 + i;
+                const int64_t p = p0 + i;
+                if (k < NA) {
+                    float r = 1.0f;
+                    const bool own = k >= 2 * W && k < 2 * W + LM_T;
+                    if (inside && p >= 0 && p < len) {
+                        r = limit_r(e[i], c);
+                        over |= e[i] > c;
+                        if (own) pk = fmaxf(pk, e[i]);
+                    }
+                    A[k] = r;
+                    if (own) Rt[k - 2 * W] = r;
+                }
+            }
+        }
+    } else {
+        for (int k = tid; k < NA; k += LM_THREADS) {
+            const int64_t p = t0 - 2 * W + k;
+            float r = 1.0f;
+            if (p >= 0 && p < len) {
+                const float a = fabsf(xs[p]);
+                r = limit_r(a, c);
+                over |= a > c;
+                if (k >= 2 * W && k < 2 * W + LM_T) pk = fmaxf(pk, a);
+            }
+            A[k] = r;
+        }
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) pk = fmaxf(pk, __shfl_xor(pk, o, 64));
@@ -173,7 +260,9 @@ void k_limit(const float *__restrict__ x, const int64_t *__restrict__ in_off, in
         for (int e = 0; e < LM_SPT; ++e) {
             if (o + e < live) {
                 const float xv = xs[t0 + o + e];
-                const float r = limit_r(fabsf(xv), c);
+                float r;
+                if constexpr (TP) r = s_lim[NA + NA + TP_WIN + o + e];     // (Rt of step 1)
+                else r = limit_r(fabsf(xv), c);
                 const float s = fmaxf(1.0f - acc[e], 0.0f);
                 const float g = fminf(s, r);
                 ys[t0 + o + e] = xv * g;
@@ -186,8 +275,48 @@ void k_limit(const float *__restrict__ x, const int64_t *__restrict__ in_off, in
     if ((tid & 63) == 0 && gmin < 1.0f) limit_stat_min(min_gain + sig, gmin);
 }
 
+// The meter: the maximum of e over a signal.  One workgroup per tile, a thread per TP_CH samples; always computes.
+__global__ __launch_bounds__(LM_THREADS)
+void k_true_peak(const float *__restrict__ x, const int64_t *__restrict__ in_off, int n, int R, const float *__restrict__ taps,
+                 const int32_t *__restrict__ tiles, float *__restrict__ peak)
+{
+    __shared__ __align__(16) float X[LM_T + TP_K];              // positions t0 - Z .. t0 + T + Z - 1
+    __shared__ float s_pk[LM_THREADS / 64];
+    const int tid = threadIdx.x;
+    const int sig = __builtin_amdgcn_readfirstlane(tiles[2 * blockIdx.x]), kt = __builtin_amdgcn_readfirstlane(tiles[2 * blockIdx.x + 1]);
+    if (sig < 0 || sig >= n || kt < 0) return;
+    const int64_t base = in_off[sig], len = in_off[sig + 1] - base, t0 = (int64_t)kt * LM_T;
+    if (t0 >= len) return;
+    const float *__restrict__ xs = x + base;
+    const int live = (int)(len - t0 < LM_T ? len - t0 : LM_T);
+    for (int k = tid; k < LM_T + TP_K; k += LM_THREADS) {
+        const int64_t p = t0 - TP_Z + k;
+        X[k] = p >= 0 && p < len ? xs[p] : 0.0f;
+    }
+    __syncthreads();
+    float pk = 0.0f;
+    const int o = tid * TP_CH;
+    if (o < live) {
+        float e[TP_CH];
+        tp_envelope(X + o, R, taps, t0 + o, e);
+#pragma unroll
+        for (int i = 0; i < TP_CH; ++i)
+            if (o + i < live) pk = fmaxf(pk, e[i]);
+    }
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) pk = fmaxf(pk, __shfl_xor(pk, s, 64));
+    if ((tid & 63) == 0) s_pk[tid >> 6] = pk;
+    __syncthreads();
+    if (tid == 0) {
+#pragma unroll
+        for (int w = 1; w < LM_THREADS / 64; ++w) pk = fmaxf(pk, s_pk[w]);
+        limit_stat_max(peak + sig, pk);
+    }
+}
+
+// R == 0: sample peaks (goofer_limit); R == 2 or 4 with tp_taps: true-peak detection (goofer_limit_tp)
 int launch_limit(goofer_ctx *ctx, const float *x, const int64_t *in_off, int n, int W, const float *taps, float c, const int32_t *tiles,
-                 int64_t n_tiles, float *out, float *peak_in, float *min_gain, hipStream_t st)
+                 int64_t n_tiles, float *out, float *peak_in, float *min_gain, hipStream_t st, int R, const float *tp_taps)
 {
     if (n <= 0) return GOOFER_OK;
     hipLaunchKernelGGL(k_limit_init, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, peak_in, min_gain);
@@ -195,33 +324,90 @@ int launch_limit(goofer_ctx *ctx, const float *x, const int64_t *in_off, int n, 
     if (n_tiles <= 0) return GOOFER_OK;
     int span = 1;
     while (2 * span <= 2 * W + 1) span *= 2;
+    if (R) {
+        // r, x (later d) and the tile's own r: 56 960 bytes at W = 240, 82 048 at W = 1024
+        const size_t lds = (2 * (size_t)(LM_T + 4 * W) + TP_WIN + LM_T) * sizeof(float);
+        if (lds > 64 * 1024)
+            if (int rc = kernel_allow_max_lds(ctx, (const void *)k_limit<true>, 96 * 1024)) return rc;   // (beside s_pk's static bytes)
+        hipLaunchKernelGGL(k_limit<true>, dim3((unsigned)n_tiles), dim3(LM_THREADS), lds, st, x, in_off, n, W, span, taps, c, tiles, out, peak_in,
+                           min_gain, ctx->limit_tp_skip ? 1 : 0, R, tp_taps);
+        LAUNCH_CHECK(ctx);
+        return GOOFER_OK;
+    }
     const size_t lds = ((size_t)(LM_T + 4 * W) + (size_t)(LM_T + 2 * W + 4)) * sizeof(float);   // 57 360 bytes at W = 1024
     if (lds > 64 * 1024)
-        if (int rc = kernel_allow_max_lds(ctx, (const void *)k_limit)) return rc;
-    hipLaunchKernelGGL(k_limit, dim3((unsigned)n_tiles), dim3(LM_THREADS), lds, st, x, in_off, n, W, span, taps, c, tiles, out, peak_in,
-                       min_gain, ctx->limit_skip ? 1 : 0);
+        if (int rc = kernel_allow_max_lds(ctx, (const void *)k_limit<false>)) return rc;
+    hipLaunchKernelGGL(k_limit<false>, dim3((unsigned)n_tiles), dim3(LM_THREADS), lds, st, x, in_off, n, W, span, taps, c, tiles, out, peak_in,
+                       min_gain, ctx->limit_skip ? 1 : 0, 0, (const float *)nullptr);
     LAUNCH_CHECK(ctx);
     return GOOFER_OK;
+}
+
+// every signal with samples has ceil(len / tile) tiles: between ceil(total / tile) and that plus one per signal
+static bool limit_tiles_ok(int n, int64_t total, int64_t n_tiles)
+{
+    const int64_t least = (total + LM_T - 1) / LM_T;
+    return n_tiles >= least && n_tiles <= least + n && n_tiles < ((int64_t)1 << 31);
+}
+
+// the checks of goofer_limit and goofer_limit_tp (`tp`: R, Z and tp_taps too), then the launch
+static int limit_entry(goofer_ctx *ctx, const char *who, bool tp, const float *x, const int64_t *in_off, int n, int64_t total, int W,
+                       const float *taps, float c, const int32_t *tiles, int64_t n_tiles, float *out, float *peak_in, float *min_gain, int R,
+                       int Z, const float *tp_taps, void *stream)
+{
+    if (!ctx) return GOOFER_EINVAL;
+    if (n < 0 || total < 0 || n_tiles < 0)
+        return goofer_fail(ctx, GOOFER_EINVAL, "%s: negative count (%d signals, %lld samples, %lld tiles)", who, n, (long long)total,
+                           (long long)n_tiles);
+    if (W < 1 || W > GOOFER_LIMIT_MAX_LOOK || !(c > 0.0f && c <= 1.0f) || !limit_tiles_ok(n, total, n_tiles))
+        return goofer_fail(ctx, GOOFER_EINVAL, "%s: W = %d, c = %g, %lld tiles for %lld samples in %d signals is not a geometry of goofer_host_limit_plan",
+                           who, W, (double)c, (long long)n_tiles, (long long)total, n);
+    if (tp && ((R != 2 && R != 4) || Z != GOOFER_TP_ZEROS))
+        return goofer_fail(ctx, GOOFER_EINVAL, "%s: R = %d, Z = %d is not a geometry of goofer_host_true_peak_plan", who, R, Z);
+    if (n == 0) return GOOFER_OK;
+    if (!in_off || !taps || !peak_in || !min_gain || (tp && !tp_taps) || (total > 0 && (!x || !out || !tiles)))
+        return goofer_fail(ctx, GOOFER_EINVAL, "%s: null pointer", who);
+    if (((uintptr_t)x | (uintptr_t)taps | (uintptr_t)out | (uintptr_t)tiles | (uintptr_t)peak_in | (uintptr_t)min_gain | (uintptr_t)tp_taps) & 3 ||
+        ((uintptr_t)in_off) & 7)
+        return goofer_fail(ctx, GOOFER_EINVAL, "%s: x, taps, tiles, out, peak_in and min_gain must be 4-byte aligned, in_off 8-byte aligned", who);
+    if (total > 0 && (uintptr_t)out < (uintptr_t)(x + total) && (uintptr_t)x < (uintptr_t)(out + total))
+        return goofer_fail(ctx, GOOFER_EINVAL, "%s: out overlaps x (halos are read from x again: not in place)", who);
+    return launch_limit(ctx, x, in_off, n, W, taps, c, tiles, n_tiles, out, peak_in, min_gain, (hipStream_t)stream, tp ? R : 0, tp_taps);
 }
 
 extern "C" int goofer_limit(goofer_ctx *ctx, const float *x, const int64_t *in_off, int n, int64_t total, int W, const float *taps, float c,
                             const int32_t *tiles, int64_t n_tiles, float *out, float *peak_in, float *min_gain, void *stream)
 {
+    return limit_entry(ctx, "goofer_limit", false, x, in_off, n, total, W, taps, c, tiles, n_tiles, out, peak_in, min_gain, 0, 0, nullptr, stream);
+}
+
+extern "C" int goofer_limit_tp(goofer_ctx *ctx, const float *x, const int64_t *in_off, int n, int64_t total, int W, const float *taps, float c,
+                               const int32_t *tiles, int64_t n_tiles, float *out, float *peak_in, float *min_gain, int R, int Z,
+                               const float *tp_taps, void *stream)
+{
+    return limit_entry(ctx, "goofer_limit_tp", true, x, in_off, n, total, W, taps, c, tiles, n_tiles, out, peak_in, min_gain, R, Z, tp_taps, stream);
+}
+
+extern "C" int goofer_true_peak(goofer_ctx *ctx, const float *x, const int64_t *in_off, int n, int64_t total, int R, int Z, const float *taps,
+                                const int32_t *tiles, int64_t n_tiles, float *peak, void *stream)
+{
     if (!ctx) return GOOFER_EINVAL;
     if (n < 0 || total < 0 || n_tiles < 0)
-        return goofer_fail(ctx, GOOFER_EINVAL, "goofer_limit: negative count (%d signals, %lld samples, %lld tiles)", n, (long long)total,
+        return goofer_fail(ctx, GOOFER_EINVAL, "goofer_true_peak: negative count (%d signals, %lld samples, %lld tiles)", n, (long long)total,
                            (long long)n_tiles);
-    // every signal with samples has ceil(len / tile) tiles: between ceil(total / tile) and that plus one per signal
-    const int64_t least = (total + LM_T - 1) / LM_T;
-    if (W < 1 || W > GOOFER_LIMIT_MAX_LOOK || !(c > 0.0f && c <= 1.0f) || n_tiles < least || n_tiles > least + n || n_tiles >= ((int64_t)1 << 31))
-        return goofer_fail(ctx, GOOFER_EINVAL, "goofer_limit: W = %d, c = %g, %lld tiles for %lld samples in %d signals is not a geometry of goofer_host_limit_plan",
-                           W, (double)c, (long long)n_tiles, (long long)total, n);
+    if ((R != 2 && R != 4) || Z != GOOFER_TP_ZEROS || !limit_tiles_ok(n, total, n_tiles))
+        return goofer_fail(ctx, GOOFER_EINVAL, "goofer_true_peak: R = %d, Z = %d, %lld tiles for %lld samples in %d signals is not a geometry of goofer_host_true_peak_plan and goofer_host_limit_plan",
+                           R, Z, (long long)n_tiles, (long long)total, n);
     if (n == 0) return GOOFER_OK;
-    if (!in_off || !taps || !peak_in || !min_gain || (total > 0 && (!x || !out || !tiles)))
-        return goofer_fail(ctx, GOOFER_EINVAL, "goofer_limit: null pointer");
-    if (((uintptr_t)x | (uintptr_t)taps | (uintptr_t)out | (uintptr_t)tiles | (uintptr_t)peak_in | (uintptr_t)min_gain) & 3 || ((uintptr_t)in_off) & 7)
-        return goofer_fail(ctx, GOOFER_EINVAL, "goofer_limit: x, taps, tiles, out, peak_in and min_gain must be 4-byte aligned, in_off 8-byte aligned");
-    if (total > 0 && (uintptr_t)out < (uintptr_t)(x + total) && (uintptr_t)x < (uintptr_t)(out + total))
-        return goofer_fail(ctx, GOOFER_EINVAL, "goofer_limit: out overlaps x (halos are read from x again: not in place)");
-    return launch_limit(ctx, x, in_off, n, W, taps, c, tiles, n_tiles, out, peak_in, min_gain, (hipStream_t)stream);
+    if (!in_off || !taps || !peak || (total > 0 && (!x || !tiles)))
+        return goofer_fail(ctx, GOOFER_EINVAL, "goofer_true_peak: null pointer");
+    if (((uintptr_t)x | (uintptr_t)taps | (uintptr_t)tiles | (uintptr_t)peak) & 3 || ((uintptr_t)in_off) & 7)
+        return goofer_fail(ctx, GOOFER_EINVAL, "goofer_true_peak: x, taps, tiles and peak must be 4-byte aligned, in_off 8-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_limit_init, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, peak, (float *)nullptr);
+    LAUNCH_CHECK(ctx);
+    if (n_tiles <= 0) return GOOFER_OK;
+    hipLaunchKernelGGL(k_true_peak, dim3((unsigned)n_tiles), dim3(LM_THREADS), 0, st, x, in_off, n, R, taps, tiles, peak);
+    LAUNCH_CHECK(ctx);
+    return GOOFER_OK;
 }

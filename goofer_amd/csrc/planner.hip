@@ -1102,6 +1102,31 @@ int goofer_host_limit_plan(int sr, double look_ms, float c, const int64_t *in_of
     return GOOFER_OK;
 }
 
+/* True-peak detection (include/goofer_hip.h; the kernels: limit.hip): the oversampling factor and the R - 1 rows of the
+ * Kaiser-windowed sinc that reconstruct the signal between two samples, in float64, each row divided by its sum. */
+int goofer_host_true_peak_plan(int sr, int *R, int *Z, float *taps, int64_t cap, int64_t *need)
+{
+    if (!R || !Z || !need || cap < 0 || (cap > 0 && !taps)) return GOOFER_EINVAL;
+    if (sr < GOOFER_TP_MIN_SR || sr > GOOFER_TP_MAX_SR) return GOOFER_EINVAL;
+    const int r = sr < 96000 ? 4 : 2, z = GOOFER_TP_ZEROS, K = 2 * z;
+    *R = r, *Z = z;
+    *need = (int64_t)(r - 1) * K;
+    if (cap < *need) return 1;
+    const double pi = 3.14159265358979323846, i0b = rate_i0(GOOFER_TP_BETA);
+    double row[2 * GOOFER_TP_ZEROS];
+    for (int p = 1; p < r; ++p) {
+        double sum = 0.0;
+        for (int c = 0; c < K; ++c) {
+            const double t = (double)(c - z + 1) - (double)p / (double)r, u = t / (double)z;
+            const double w = rate_i0(GOOFER_TP_BETA * std::sqrt(std::max(0.0, 1.0 - u * u))) / i0b;   // |t| < Z for every p >= 1
+            row[c] = std::sin(pi * t) / (pi * t) * w;                                                  // t is never 0
+            sum += row[c];
+        }
+        for (int c = 0; c < K; ++c) taps[(int64_t)(p - 1) * K + c] = (float)(row[c] / sum);
+    }
+    return GOOFER_OK;
+}
+
 /* Loudness metering (include/goofer_hip.h; the kernels: loudness.hip): the K-weighting coefficients by the bilinear transform,
  * the segment length and CSR, the tile table and the powers A^(16 * 2^k) of the recurrence's 4x4 state-transition matrix.
  * The high-pass has two nearly equal poles just inside the unit circle, so squaring amplifies rounding: squared in float64,

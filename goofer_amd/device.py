@@ -272,7 +272,9 @@ class Context:
         the first time it is used on this device); ``out``: a contiguous fp32 device tensor of ``plan.total`` samples that does
         not overlap ``x`` (default: a new one; it need not be cleared).  Returns ``(y, peak_in, min_gain)``, device tensors:
         signal i is ``y[plan.in_off[i]:plan.in_off[i + 1]]``, ``peak_in[i]`` its greatest ``|x|`` and ``min_gain[i]`` the
-        smallest gain it was given (fp32 ``[n]``).  Asynchronous on the current stream."""
+        smallest gain it was given (fp32 ``[n]``).  A plan made with ``true_peak`` runs goofer_limit_tp: the ceiling holds for
+        the oversampled envelope (restated in tests/true_peak_ref.py) and ``peak_in`` is the true peak.  Asynchronous on the
+        current stream."""
         n, total = plan.n, plan.total
         d_in, tiles, taps = plan.device_tables(self)
         if isinstance(d_off, torch.Tensor):
@@ -290,10 +292,39 @@ class Context:
         peak_in = torch.empty(n, dtype=torch.float32, device=self.device)
         min_gain = torch.empty(n, dtype=torch.float32, device=self.device)
         if n:
-            self._check(self.lib.goofer_limit(self.h, _ptr(x) if total else None, _ptr(d_in), n, total, plan.W, _ptr(taps),
-                                              C.c_float(plan.ceiling), _ptr(tiles) if total else None, plan.n_tiles,
-                                              _ptr(out) if total else None, _ptr(peak_in), _ptr(min_gain), self._stream()))
+            args = (self.h, _ptr(x) if total else None, _ptr(d_in), n, total, plan.W, _ptr(taps), C.c_float(plan.ceiling),
+                    _ptr(tiles) if total else None, plan.n_tiles, _ptr(out) if total else None, _ptr(peak_in), _ptr(min_gain))
+            if plan.true_peak:
+                self._check(self.lib.goofer_limit_tp(*args, plan.R, plan.Z, _ptr(plan.device_tp_taps(self)), self._stream()))
+            else:
+                self._check(self.lib.goofer_limit(*args, self._stream()))
         return out, peak_in, min_gain
+
+    def true_peak(self, x, d_off, plan):
+        """The true peak of every signal of a ragged batch, measured on the device (goofer_true_peak; the definition:
+        include/goofer_hip.h, "true-peak detection", restated in tests/true_peak_ref.py): the greatest magnitude of the signal
+        reconstructed at ``plan.R`` times its rate, linear.  ``x``, ``d_off`` as ``limit`` takes them; ``plan``: a
+        ``goofer_amd.limit.LimitPlan`` with the true-peak table (``limit.true_peak_plan``, or the plan of a true-peak limiter
+        for the same lengths).  Returns fp32 ``[n]`` on the device (0 for a signal without a sample).  Asynchronous on the
+        current stream."""
+        if not plan.true_peak:
+            raise ValueError("true_peak: the plan has no true-peak table (limit.true_peak_plan)")
+        n, total = plan.n, plan.total
+        d_in, tiles, _ = plan.device_tables(self)
+        if isinstance(d_off, torch.Tensor):
+            if d_off.dtype != torch.int64 or not d_off.is_contiguous() or d_off.numel() != n + 1:
+                raise ValueError("true_peak: d_off is one contiguous int64 CSR of the plan's %d signals" % n)
+            d_in = d_off
+        elif d_off is not None and not np.array_equal(np.asarray(d_off, dtype=np.int64), plan.in_off):
+            raise ValueError("true_peak: d_off is not the CSR the plan was made for")
+        if x.dtype != torch.float32 or not x.is_contiguous() or x.numel() < total:
+            raise ValueError("true_peak: x must be a contiguous float32 tensor of the plan's %d samples" % total)
+        peak = torch.empty(n, dtype=torch.float32, device=self.device)
+        if n:
+            self._check(self.lib.goofer_true_peak(self.h, _ptr(x) if total else None, _ptr(d_in), n, total, plan.R, plan.Z,
+                                                  _ptr(plan.device_tp_taps(self)), _ptr(tiles) if total else None, plan.n_tiles,
+                                                  _ptr(peak), self._stream()))
+        return peak
 
     def loudness(self, x, d_off, plan, target=None, max_gain_db=20.0, out=None):
         """The integrated loudness of the signals of a ragged batch measured on the device and, with a ``target`` in LUFS, the

@@ -6,6 +6,11 @@ and min / max over a ragged batch, the definition this project's own (``include/
 raised-cosine table and the tile table come from the library's host planner (``goofer_host_limit_plan``), the kernel is
 ``goofer_limit`` (``Context.limit``).  ``core.limit_batch`` is the numpy-in, numpy-out form; ``Renderer.render`` /
 ``render_phrase`` take ``limit``.
+
+With ``true_peak`` the limiter watches the reconstructed signal between the samples as well (after BS.1770-4 Annex 2; the
+header's "true-peak detection"): the plan then carries the oversampling factor ``R`` and the interpolation table of
+``goofer_host_true_peak_plan``, the kernel is ``goofer_limit_tp`` and the ceiling is a true-peak ceiling (dBTP).  The meter
+alone is ``goofer_true_peak`` (``Context.true_peak``, ``core.true_peak_batch``) on a ``true_peak_plan``.
 """
 from __future__ import annotations
 
@@ -21,6 +26,17 @@ MAX_LOOK = 1024                     # GOOFER_LIMIT_MAX_LOOK
 TILE = 4096                         # GOOFER_LIMIT_TILE
 CEILING = 32767.0 / 32768.0         # GOOFER_LIMIT_CEILING
 LOOK_MS = 5.0                       # GOOFER_LIMIT_LOOK_MS
+TP_ZEROS = 12                       # GOOFER_TP_ZEROS
+TP_MIN_SR, TP_MAX_SR = 8000, 192000  # GOOFER_TP_MIN_SR, GOOFER_TP_MAX_SR
+
+
+@dataclass(frozen=True)
+class Limiter:
+    """The limiter's settings as ``Renderer.render`` takes them: the ceiling in (0, 1], the look-ahead in ms, and whether the
+    ceiling holds for the true peak (the oversampled envelope) or for the samples."""
+    ceiling: float = CEILING
+    lookahead_ms: float = LOOK_MS
+    true_peak: bool = False
 
 
 @dataclass
@@ -36,7 +52,14 @@ class LimitPlan:
     in_off: np.ndarray
     tiles: np.ndarray
     blob: np.ndarray
+    R: int = 0
+    Z: int = 0
+    tp_taps: np.ndarray = None
     _dev: dict = field(default_factory=dict, repr=False)
+
+    @property
+    def true_peak(self) -> bool:
+        return self.R != 0
 
     @property
     def total(self) -> int:
@@ -48,28 +71,75 @@ class LimitPlan:
 
     def device_tables(self, ctx):
         """(in_off, tiles, taps) on ``ctx``'s device: views of the blob, uploaded on first use."""
+        return self._tables(ctx)[:3]
+
+    def device_tp_taps(self, ctx):
+        """the true-peak table on ``ctx``'s device: a view of the same blob"""
+        return self._tables(ctx)[3]
+
+    def _tables(self, ctx):
         import torch
         hit = self._dev.get(ctx.device)
         if hit is None:
             d = ctx.tensor(self.blob)
             a, b = self.in_off.nbytes, self.in_off.nbytes + self.tiles.nbytes
-            hit = self._dev[ctx.device] = (d[:a].view(torch.int64), d[a:b].view(torch.int32), d[b:].view(torch.float32), d)
-        return hit[:3]
+            e = b + self.taps.nbytes
+            hit = self._dev[ctx.device] = (d[:a].view(torch.int64), d[a:b].view(torch.int32), d[b:e].view(torch.float32),
+                                           d[e:].view(torch.float32), d)
+        return hit
 
 
 def parse(limit):
-    """``limit`` as Renderer.render takes it — a ceiling, or a (ceiling, lookahead_ms) pair — as that pair."""
+    """``limit`` as Renderer.render takes it, as the arguments of ``plan`` behind the lengths: a ceiling or a (ceiling,
+    lookahead_ms) pair as that pair; a ``Limiter`` or a (ceiling, lookahead_ms, true_peak) triple, ``true_peak`` a bool, as
+    that triple."""
+    if isinstance(limit, Limiter):
+        limit = (limit.ceiling, limit.lookahead_ms, bool(limit.true_peak))
     if isinstance(limit, (tuple, list)):
+        if len(limit) == 3 and isinstance(limit[2], (bool, np.bool_)):
+            return float(limit[0]), float(limit[1]), bool(limit[2])
         if len(limit) != 2:
-            raise ValueError("limit is a ceiling or a (ceiling, lookahead_ms) pair")
+            raise ValueError("limit is a ceiling, a (ceiling, lookahead_ms) pair, a (ceiling, lookahead_ms, true_peak) triple "
+                             "with a bool last, or a Limiter")
         return float(limit[0]), float(limit[1])
     return float(limit), LOOK_MS
 
 
-def plan(sr, lengths, ceiling=CEILING, lookahead_ms=LOOK_MS) -> LimitPlan:
+def true_peak_table(sr):
+    """goofer_host_true_peak_plan: (R, Z, float32 [R - 1, 2Z]) at ``sr``.  Raises ValueError for a rate outside 8000 .. 192000 Hz."""
+    lib = _lib.load()
+    if int(sr) != sr:
+        raise ValueError("limit.true_peak_table: the sample rate is a whole number of Hz")
+    R, Z, need = C.c_int(0), C.c_int(0), C.c_int64(0)
+    taps = np.zeros(0, dtype=np.float32)
+    rc = -1
+    for _ in range(2):
+        rc = lib.goofer_host_true_peak_plan(int(sr), C.byref(R), C.byref(Z), taps.ctypes.data if taps.size else None, taps.size, C.byref(need))
+        if rc != 1:
+            break
+        taps = np.zeros(int(need.value), dtype=np.float32)
+    if rc != 0:
+        raise ValueError("goofer_host_true_peak_plan refused %s Hz (%d): true-peak detection takes %d to %d Hz" % (sr, rc, TP_MIN_SR, TP_MAX_SR))
+    return R.value, Z.value, taps.reshape(R.value - 1, 2 * Z.value)
+
+
+def true_peak_plan(sr, lengths) -> LimitPlan:
+    """The plan of the meter alone (``Context.true_peak``): the limiter's own tile table for these lengths and the true-peak
+    table at ``sr``."""
+    return plan(sr, lengths, true_peak=True)
+
+
+def dbtp(x) -> float:
+    """a linear peak in dB relative to full scale (-inf for 0): dBTP of a true peak, dBFS of a sample peak"""
+    v = float(x)
+    return 20.0 * math.log10(v) if v > 0.0 else -math.inf
+
+
+def plan(sr, lengths, ceiling=CEILING, lookahead_ms=LOOK_MS, true_peak=False) -> LimitPlan:
     """goofer_host_limit_plan for signals of ``lengths`` samples lying back to back.  Raises ValueError for what the library
     refuses: a look-ahead that rounds to less than 1 or more than 1024 samples, a ceiling that is not in (0, 1] as fp32, a rate
-    below 1, a signal of 2^31 samples or more."""
+    below 1, a signal of 2^31 samples or more.  ``true_peak``: also goofer_host_true_peak_plan's factor and table (a rate of
+    8000 to 192000 Hz), in the same blob."""
     lib = _lib.load()
     lengths = np.ascontiguousarray(lengths, dtype=np.int64).reshape(-1)
     if lengths.size and lengths.min() < 0:
@@ -93,8 +163,9 @@ def plan(sr, lengths, ceiling=CEILING, lookahead_ms=LOOK_MS) -> LimitPlan:
     if rc != 0:
         raise ValueError("goofer_host_limit_plan refused a ceiling of %r and %r ms at %s Hz (%d): a ceiling in (0, 1], a look-ahead of "
                          "1 to %d samples, a rate >= 1, signals shorter than 2^31 samples" % (ceiling, lookahead_ms, sr, rc, MAX_LOOK))
-    blob = np.concatenate([in_off.view(np.uint8), tiles.view(np.uint8).ravel(), taps.view(np.uint8)])
-    return LimitPlan(int(sr), n, W.value, c, taps, in_off, tiles, blob)
+    R, Z, tp_taps = true_peak_table(sr) if true_peak else (0, 0, np.zeros((0, 0), dtype=np.float32))
+    blob = np.concatenate([in_off.view(np.uint8), tiles.view(np.uint8).ravel(), taps.view(np.uint8), tp_taps.view(np.uint8).ravel()])
+    return LimitPlan(int(sr), n, W.value, c, taps, in_off, tiles, blob, R, Z, tp_taps)
 
 
 def look_samples(sr, lookahead_ms=LOOK_MS) -> int:

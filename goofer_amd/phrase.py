@@ -6,7 +6,7 @@ definition is this project's own (``include/goofer_hip.h``, goofer_phrase_note; 
 ``goofer_phrase_mix``.  Here: wavtool's arguments turned into note records (host, float64), the records checked and the
 cover table made by the library's planner (``goofer_host_phrase_plan``), and a command line,
 
-    python -m goofer_amd.phrase [--rate HZ] [--compress T:R[:ATTACK:RELEASE[:KNEE[:MAKEUP]]]] [--loudness LUFS] [--limit [DBFS]] job.txt out.wav
+    python -m goofer_amd.phrase [--rate HZ] [--compress T:R[:ATTACK:RELEASE[:KNEE[:MAKEUP]]]] [--loudness LUFS] [--limit [DBFS] [--true-peak]] job.txt out.wav
 
 ``job.txt`` holds one line per note, the 13 resampler arguments, ``|``, then wavtool's ``stp length p1 p2 p3 v1 v2 v3 v4 [ovr
 [p4 [p5 v5]]]``::
@@ -18,7 +18,9 @@ cover table made by the library's planner (``goofer_host_phrase_plan``), and a c
 lines and lines that start with ``#`` are skipped.  ``--rate HZ`` converts the mixed track from the voicebank's rate to HZ on
 the device (goofer_amd.rate) before it becomes int16; the wav's header carries HZ.  ``--limit [DBFS]`` runs the look-ahead peak
 limiter (goofer_amd.limit) over the track at the rate of the wav, with the ceiling DBFS decibels relative to full scale (bare:
-32767/32768), and reports the track's peak in front of it and its greatest gain reduction on stderr.  ``--loudness LUFS``
+32767/32768), and reports the track's peak in front of it and its greatest gain reduction on stderr; with ``--true-peak`` (a
+flag without a value, only together with ``--limit``) the ceiling is read as dBTP and holds for the signal reconstructed between
+the samples too, and stderr reports the track's true peak in front of and behind the limiter.  ``--loudness LUFS``
 measures the track's integrated loudness after BS.1770 (goofer_amd.loudness) and scales the track to LUFS, in front of the
 limiter, the gain capped at 20 dB; the measured loudness and the gain go to stderr too.  ``--compress
 T:R[:ATTACK:RELEASE[:KNEE[:MAKEUP]]]`` runs the dynamic range compressor (goofer_amd.compress) over the track behind the rate
@@ -253,7 +255,7 @@ def render_job(path, out_wav, renderer=None, seed=None, tracker=None, pcm16=True
     resolved like the resampler front end does: ``<stem>_features.goofy`` beside the wav, analysed and cached first when it is
     missing (``trackers.ensure_features_batch``; the tracker: the argument, else ``$GOOFER_TRACKER``).  ``out_sr``: the rate of
     the wav (``render_phrase``'s; None: the voicebank's).  ``limit``: ``render_phrase``'s (None: no limiter); with it ``stats``,
-    a dict, receives the limiter's ``peak_in`` and ``min_gain``.  ``loudness``: ``render_phrase``'s (None: the track's level is
+    a dict, receives the limiter's ``peak_in`` and ``min_gain`` (a true-peak limiter's ``true_peak_in`` and ``true_peak_out`` too).  ``loudness``: ``render_phrase``'s (None: the track's level is
     left as it is); with it ``stats`` receives ``lufs_in``, ``momentary_max`` and ``gain``.  ``compress``: ``render_phrase``'s (None:
     no compressor); with it ``stats`` receives ``max_reduction_db``."""
     from pathlib import Path
@@ -291,11 +293,16 @@ def render_job(path, out_wav, renderer=None, seed=None, tracker=None, pcm16=True
 
 def main(argv=None) -> int:
     import logging
+    from . import limit as LM
     logging.basicConfig(format="%(message)s", level=logging.INFO)
     argv = list(sys.argv[1:] if argv is None else argv)
     out_sr = limit = loudness = compress = None
-    while len(argv) > 2 and argv[0] in ("--rate", "--limit", "--loudness", "--compress"):
-        if argv[0] == "--rate":
+    true_peak = False
+    while len(argv) > 2 and argv[0] in ("--rate", "--limit", "--loudness", "--compress", "--true-peak"):
+        if argv[0] == "--true-peak":
+            true_peak = True
+            argv = argv[1:]
+        elif argv[0] == "--rate":
             try:
                 out_sr = int(argv[1])
             except ValueError:
@@ -315,20 +322,20 @@ def main(argv=None) -> int:
                 break
             argv = argv[2:]
         else:
-            from . import limit as LM
             try:                        # --limit DBFS, or bare: the default ceiling
                 limit = 10.0 ** (float(argv[1]) / 20.0)
                 argv = argv[2:]
             except ValueError:
                 limit = LM.CEILING
                 argv = argv[1:]
-    if len(argv) != 2:
+    if len(argv) != 2 or (true_peak and limit is None):
         logging.error("Usage:\n  python -m goofer_amd.phrase [--rate HZ] [--compress T:R[:ATTACK:RELEASE[:KNEE[:MAKEUP]]]] [--loudness LUFS] "
-                      "[--limit [DBFS]] job.txt out.wav")
+                      "[--limit [DBFS] [--true-peak]] job.txt out.wav")
         return 1
     stats = {}
     try:
-        track = render_job(argv[0], argv[1], out_sr=out_sr, limit=limit, stats=stats, loudness=loudness, compress=compress)
+        track = render_job(argv[0], argv[1], out_sr=out_sr, limit=LM.Limiter(limit, true_peak=True) if true_peak else limit, stats=stats,
+                           loudness=loudness, compress=compress)
     except Exception:                   # noqa: BLE001
         logging.exception("Failed to render")
         return 1
@@ -340,8 +347,11 @@ def main(argv=None) -> int:
         print("Loudness: measured %.2f LUFS (momentary max %.2f), gain %.2f dB (target %.2f LUFS)"
               % (stats["lufs_in"], stats["momentary_max"], 20.0 * math.log10(stats["gain"]) if stats["gain"] > 0.0 else -math.inf, loudness),
               file=sys.stderr)
-    if limit is not None:
-        from . import limit as LM
+    if true_peak:
+        print("Limiter: input true peak %.2f dBTP, output true peak %.2f dBTP, greatest reduction %.2f dB (ceiling %.2f dBTP)"
+              % (LM.dbtp(stats["true_peak_in"]), LM.dbtp(stats["true_peak_out"]), LM.reduction_db(stats["min_gain"]), LM.dbtp(limit)),
+              file=sys.stderr)
+    elif limit is not None:
         peak = stats["peak_in"]
         print("Limiter: input peak %.2f dBFS, greatest reduction %.2f dB (ceiling %.2f dBFS)"
               % (20.0 * math.log10(peak) if peak > 0.0 else -math.inf, LM.reduction_db(stats["min_gain"]), 20.0 * math.log10(limit)),

@@ -450,7 +450,8 @@ class Renderer:
         the whole batch in one goofer_rate_convert); None, or the sources' own rate: no conversion.
         ``limit``: None, a ceiling in (0, 1] or a ``(ceiling, lookahead_ms)`` pair: every note brought under the ceiling by the
         look-ahead peak limiter on the device (goofer_amd.limit; the whole batch in one goofer_limit), after the conversion, at
-        the rate the notes are returned at.
+        the rate the notes are returned at; a ``limit.Limiter`` or a ``(ceiling, lookahead_ms, true_peak)`` triple with
+        ``true_peak`` set: the ceiling holds for the true peak (goofer_limit_tp).
         ``loudness``: None, a target in LUFS or a ``(target, max_gain_db)`` pair: every note measured after BS.1770 and scaled
         to the target on the device (goofer_amd.loudness; the whole batch in one pass), after the conversion and in front of
         the limiter.
@@ -510,7 +511,10 @@ class Renderer:
         mixed track converted from the notes' rate to this one on the device (goofer_amd.rate) — mix, convert, then int16;
         None, or the notes' own rate: no conversion.  ``limit``: None, a ceiling in (0, 1] or a ``(ceiling, lookahead_ms)`` pair:
         the track brought under the ceiling by the look-ahead peak limiter on the device (goofer_amd.limit) — mix, convert,
-        limit at the output rate, then int16.  ``loudness``: None, a target in LUFS or a ``(target, max_gain_db)`` pair: the
+        limit at the output rate, then int16; a ``limit.Limiter`` or a ``(ceiling, lookahead_ms, true_peak)`` triple with
+        ``true_peak`` set: the ceiling holds for the true peak (goofer_limit_tp), ``peak_in`` is the true peak, and the
+        statistics gain ``true_peak_in`` (the same number) and ``true_peak_out``, the limited track's true peak by one
+        goofer_true_peak in front of the int16 conversion.  ``loudness``: None, a target in LUFS or a ``(target, max_gain_db)`` pair: the
         track measured after BS.1770 and scaled to the target on the device (goofer_amd.loudness) — mix, convert, loudness,
         limit, then int16.  ``compress``: None or what ``render`` takes: the track through the dynamic range compressor on the
         device (goofer_amd.compress), behind the conversion and in front of the loudness stage — mix, convert, compress,
@@ -552,6 +556,8 @@ class Renderer:
             from . import limit as LM
             lplan = LM.plan(jobs[0][0].sr if to_sr is None else to_sr, [track.numel()], *LM.parse(limit))
             track, *stats = self.ctx.limit(track, None, lplan)
+            if return_stats and lplan.true_peak:
+                stats.append(self.ctx.true_peak(track, None, lplan))
         if pcm16:
             track = self.ctx.pcm16(track)
         self.ctx.check()                                   # synchronises; raises if the device flagged a note
@@ -559,6 +565,8 @@ class Renderer:
             res = {}
             if stats is not None:
                 res.update({"peak_in": float(stats[0].cpu()[0]), "min_gain": float(stats[1].cpu()[0])})
+                if len(stats) > 2:
+                    res.update({"true_peak_in": res["peak_in"], "true_peak_out": float(stats[2].cpu()[0])})
             if lstats is not None:
                 loud = lstats[0].cpu()
                 res.update({"lufs_in": float(loud[0, 0]), "momentary_max": float(loud[0, 1]), "gain": float(lstats[1].cpu()[0])})

@@ -809,7 +809,7 @@ int goofer_rate_convert(goofer_ctx *ctx, const float *x, const int64_t *in_off, 
  * every d is +0, acc is +0 and g is exactly 1, so a signal that never exceeds c comes back bit for bit — which is why the sum
  * is over the deficiency d and not over m.  Non-finite samples follow the arithmetic as written (a NaN asks for gain 1 and
  * stays NaN).  Loudness metering and normalisation live in goofer_loudness_* below, in front of this stage; true-peak
- * (oversampled) detection does not exist. */
+ * (oversampled) detection is the next section: goofer_limit_tp is this limiter with a[i] the oversampled envelope. */
 #define GOOFER_LIMIT_MAX_LOOK 1024
 #define GOOFER_LIMIT_TILE 4096
 #define GOOFER_LIMIT_CEILING (32767.0f / 32768.0f)
@@ -838,6 +838,84 @@ int goofer_host_limit_plan(int sr, double look_ms, float c, const int64_t *in_of
  * 8-byte aligned, or an out that overlaps x. */
 int goofer_limit(goofer_ctx *ctx, const float *x, const int64_t *in_off, int n, int64_t total, int W, const float *taps, float c,
                  const int32_t *tiles, int64_t n_tiles, float *out, float *peak_in, float *min_gain, void *stream);
+
+/* ---- true-peak detection ---------------------------------------------------------------------------------------------------
+ * The limiter above looks at sample values.  The signal a converter reconstructs from them passes between them, and can pass
+ * higher: a full-scale sine at a quarter of the sample rate, sampled at 45 degrees, has a sample peak of -3.01 dBFS and a true
+ * peak of 0 dBTP, and the limiter returns it bit for bit at any ceiling down to -3 dBFS.  A delivery specification of "-16 LUFS,
+ * -1 dBTP" means the true peak.  This is the other half of ITU-R BS.1770-4 (Annex 2) beside goofer_loudness_*: the signal
+ * reconstructed at R times its rate by a short windowed sinc, as a meter (goofer_true_peak) and as what the limiter watches
+ * (goofer_limit_tp).  The definition is this project's own (restated in numpy by tests/true_peak_ref.py).
+ *
+ * Geometry.  sr: an integer, GOOFER_TP_MIN_SR <= sr <= GOOFER_TP_MAX_SR; anything else is refused (GOOFER_EINVAL).
+ * Oversampling factor R = 4 for sr < 96000, else 2: the oversampled rate is at least 32 kHz and reaches 192 kHz from 48 kHz
+ * on.  Z = GOOFER_TP_ZEROS: a row has 2Z = 24 taps.
+ *
+ * Table (host, float64, stored as fp32).  taps[R - 1][2Z], one row per phase p = 1 .. R - 1 (phase 0 is the sample itself and
+ * is never filtered): row p - 1 holds h_p[j] for j = -Z+1 .. Z at column j + Z - 1.  With t = j - p / R:
+ *   h = sinc(t) * w(t),  sinc(z) = sin(pi z) / (pi z),
+ *   w(t) = I0(GOOFER_TP_BETA * sqrt(1 - (t/Z)^2)) / I0(GOOFER_TP_BETA)      (goofer_rate_convert's Kaiser window, half width Z)
+ * Each row is divided by its float64 sum (taken in ascending j), then rounded to fp32 to nearest even.
+ *
+ * Per signal x[0 .. n), with x outside [0, n) taken as 0; all arithmetic fp32, no contraction:
+ *   u[i] = max over p of | sum_j h_p[j] * x[i + j] |   for 0 <= i < n: the reconstructed signal at the R - 1 grid points strictly
+ *          between samples i and i + 1.  Each sum runs in ascending j from +0.0f, one rounded multiply and one rounded add per
+ *          tap, the products with the zeros outside the signal included.
+ *   e[i] = max(|x[i]|, u[i], u[i - 1]), u[-1] = 0.  A sample's gain shapes the reconstruction on both sides of it, so a sample
+ *          answers for both neighbouring intervals.
+ * Meter: true_peak = max_i e[i], 0 for an empty signal; exact, a maximum of fp32 values.
+ * Limiter with true-peak detection: step 1 of goofer_limit's definition becomes a[i] = e[i]; steps 2 to 8 stay word for word.
+ * peak_in becomes max_i e[i]; min_gain is unchanged.  An output sample depends on 4W + 1 + 2Z input samples of its own signal,
+ * and a signal gets the same bits alone as at any position in any batch.  The identity property carries over: where e <= c on
+ * all of [i - 2W, i + 2W], g[i] is exactly 1, so a signal whose true peak stays at or under c comes back bit for bit.
+ * Every max above is fmaxf, started from 0 for u: a NaN operand is ignored.  A NaN sample makes the sums it enters NaN, so those
+ * u are 0 unless another phase is finite, and its own e is 0: it asks for gain 1 and stays NaN, as in goofer_limit.  An infinite
+ * sample has e = inf, r = 0 and becomes NaN, as there; its neighbours' sums are infinite or NaN as the arithmetic says.
+ *
+ * Properties (measured on the float64 flavour of tests/true_peak_ref.py, on the fp32 table; tests/test_true_peak_plan.py holds
+ * them).  (a) On unit sines at 0.25, 0.3, 0.4 and 0.45 of the sample rate, over 13 start phases, away from the signal's ends,
+ * the meter reads between -0.40 dB (at 0.4; R = 2: -0.58 dB at 0.25) and +0.0004 dB: the under-read is the grid of R points per
+ * sample itself (cos(pi f / R) of a peak that falls midway between two grid points), not the table; the quarter-rate sine at
+ * 45 degrees reads 0.000 dBTP.  (b) S = max_p sum_j |h_p[j]| = 2.2064, row sums are 1 within 3.1e-8: u <= S max |x|.
+ * (c) Gain smoothing does not commute with interpolation, so the true peak of the limiter's output is held to c closely, not
+ * exactly: on five inputs of 12 000 samples (noise low-passed at 0.9, 0.5 and 1.0 of the Nyquist rate with peaks 3, 1.5 and 8,
+ * a 0.95 square wave, a chirp of amplitude 1.4) at c = 0.891, 0.5 and 32767/32768, the 4-phase true peak of the output exceeds
+ * c by at most 4.96e-3 relative (0.043 dB) at W = 7, 9.85e-6 at W = 48 and 7.9e-8 at W = 240 — the shorter the look-ahead, the
+ * faster the gain moves between two samples and the weaker the guarantee; at the default 5 ms it is below an fp32 rounding of
+ * the samples.  goofer_limit on the same inputs leaves true peaks up to 3.8 dB above c (noise, W = 7; 1.9 dB at W = 240). */
+#define GOOFER_TP_ZEROS 12
+#define GOOFER_TP_BETA 8.0
+#define GOOFER_TP_MIN_SR 8000
+#define GOOFER_TP_MAX_SR 192000
+
+/* Host side (no device, no handle): R, Z and the table at `sr`.  *need = (R - 1) * 2Z, the floats of `taps`.  Returns 0 with R,
+ * Z, taps and need written; 1 when cap < *need (only *need, *R and *Z are valid: grow, call again); GOOFER_EINVAL for a rate out
+ * of range, a null argument (taps may be null when cap == 0) or a negative capacity.  The tile table of a call below is
+ * goofer_host_limit_plan's own, for the same in_off. */
+int goofer_host_true_peak_plan(int sr, int *R, int *Z, float *taps, int64_t cap, int64_t *need);
+
+/* The meter (limit.hip): peak[i] (fp32 [n], set by the call) = true_peak of signal x[in_off[i] .. in_off[i+1]).  x, in_off
+ * ([n + 1]), taps ([R - 1][2Z]), tiles ([n_tiles] pairs) and peak are device arrays of the caller; R, Z and taps those of
+ * goofer_host_true_peak_plan, tiles and n_tiles those of goofer_host_limit_plan for the same in_off (any ceiling and look-ahead),
+ * total = in_off[n].  One workgroup per tile: the tile's x with Z samples of halo on either side in LDS, a thread makes e of
+ * eight consecutive samples from a window sliding through its registers, the maximum goes to the signal's word by an integer
+ * atomic on the fp32 bits.  Every tile computes: a meter has no ceiling under which it could stop.  No scratch buffer, no plan;
+ * asynchronous on `stream`; the same bits alone as in any batch.  n == 0: nothing is launched; total == 0: zeros.
+ * GOOFER_EINVAL, with nothing launched, for a null pointer (all arrays may be null when n == 0; x and tiles when total == 0), a
+ * negative count, R not 2 or 4, Z not GOOFER_TP_ZEROS, an n_tiles that is not between ceil(total / GOOFER_LIMIT_TILE) and that
+ * plus n, x, taps, tiles or peak not 4-byte aligned, in_off not 8-byte aligned. */
+int goofer_true_peak(goofer_ctx *ctx, const float *x, const int64_t *in_off, int n, int64_t total, int R, int Z, const float *taps,
+                     const int32_t *tiles, int64_t n_tiles, float *peak, void *stream);
+
+/* The limiter with true-peak detection (limit.hip): goofer_limit's arguments and contract, with R, Z and tp_taps of
+ * goofer_host_true_peak_plan.  The kernel is goofer_limit's with another first step: x of [t0 - 2W - Z, t0 + T + 2W + Z) staged
+ * in LDS, e and r = c / e made from it.  A tile whose e never exceeds c, halo included, copies its samples (option
+ * "limit_tp_skip"; the identity property: the same bits).  There is no exit in front of the interpolation: peak_in is the
+ * maximum of e, which a tile that did not interpolate could not report.  GOOFER_EINVAL as goofer_limit, and for R not 2 or 4, Z
+ * not GOOFER_TP_ZEROS, a null or misaligned tp_taps. */
+int goofer_limit_tp(goofer_ctx *ctx, const float *x, const int64_t *in_off, int n, int64_t total, int W, const float *taps, float c,
+                    const int32_t *tiles, int64_t n_tiles, float *out, float *peak_in, float *min_gain, int R, int Z, const float *tp_taps,
+                    void *stream);
 
 /* ---- loudness metering and normalisation ------------------------------------------------------------------------------------
  * The limiter watches peaks; this stage watches level: a signal's integrated loudness measured on the device and the signal
@@ -1045,6 +1123,9 @@ const char *goofer_profile_stage_name_ex(const goofer_ctx *ctx, int stage);   /*
  *               row from global memory, as it does for a table that does not fit.  Same bits.
  *   "limit_skip" 1 (default): a tile of goofer_limit with no sample above the ceiling, its halo of 2W samples on either side
  *               included, copies x to out; 0: every tile does the full arithmetic.  Same bits (the identity property).
+ *   "limit_tp_skip" 1 (default): a tile of goofer_limit_tp whose true-peak envelope never exceeds the ceiling, its halo of 2W
+ *               samples on either side included, copies x to out behind the interpolation; 0: every tile does the full
+ *               arithmetic.  Same bits (the identity property).
  *   "compress_skip" 1 (default): goofer_compress finds a sample under the lower end of the knee (|x| <= 10^((T - W/2) / 20)) by
  *               one compare and takes xl = 0 without the logarithm; 0: the logarithm for every sample.  The curve is continuous
  *               there, so the two agree within rounding (and bit for bit wherever the identity property holds).
