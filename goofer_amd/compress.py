@@ -11,11 +11,12 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from dataclasses import dataclass, field
+from dataclasses import dataclass
 
 import numpy as np
 
 from . import _lib
+from . import signal_plan as SP
 
 MIN_SR = 8000                       # GOOFER_COMPRESS_MIN_SR
 MAX_SR = 192000                     # GOOFER_COMPRESS_MAX_SR
@@ -80,7 +81,7 @@ def parse(compress) -> Compressor:
 
 
 @dataclass
-class CompressPlan:
+class CompressPlan(SP.SignalPlan):
     """What goofer_compress takes for one ragged batch: ``coef`` (float64 [6]: T, W, s = 1/R - 1, M, aR, aA), ``pows`` (float64
     [2, 20]: aR^(16 * 2^k), then aA^(16 * 2^k)), the signals' CSR ``in_off`` (int64 [n + 1]) and the tile table ``tiles`` (int32
     [n_tiles, 2]: signal, tile of the signal); ``blob`` holds them back to back for one upload."""
@@ -91,27 +92,7 @@ class CompressPlan:
     pows: np.ndarray
     in_off: np.ndarray
     tiles: np.ndarray
-    blob: np.ndarray
-    _dev: dict = field(default_factory=dict, repr=False)
-
-    @property
-    def total(self) -> int:
-        return int(self.in_off[-1])
-
-    @property
-    def n_tiles(self) -> int:
-        return len(self.tiles)
-
-    def device_tables(self, ctx):
-        """(in_off, coef, pows, tiles) on ``ctx``'s device: views of the blob, uploaded on first use."""
-        import torch
-        hit = self._dev.get(ctx.device)
-        if hit is None:
-            d = ctx.tensor(self.blob)
-            a, b, c = (int(v) for v in np.cumsum([self.in_off.nbytes, self.coef.nbytes, self.pows.nbytes]))
-            hit = self._dev[ctx.device] = (d[:a].view(torch.int64), d[a:b].view(torch.float64), d[b:c].view(torch.float64),
-                                           d[c:].view(torch.int32), d)
-        return hit[:4]
+    BLOB = ("in_off", "coef", "pows", "tiles")                 # device_tables: these four, in this order
 
 
 def plan(sr, lengths, settings) -> CompressPlan:
@@ -120,29 +101,16 @@ def plan(sr, lengths, settings) -> CompressPlan:
     outside their ranges, a negative length, a signal of 2^31 samples or more."""
     lib = _lib.load()
     settings = parse(settings)
-    lengths = np.ascontiguousarray(lengths, dtype=np.int64).reshape(-1)
-    if lengths.size and lengths.min() < 0:
-        raise ValueError("compress.plan: a negative length")
-    if int(sr) != sr:
-        raise ValueError("compress.plan: the sample rate is a whole number of Hz")
-    n = len(lengths)
-    in_off = np.zeros(n + 1, dtype=np.int64)
-    np.cumsum(lengths, out=in_off[1:])
+    in_off = SP.offsets("compress.plan", lengths, sr)
+    n = len(in_off) - 1
     need = (C.c_int64 * 1)(0)
     coef, pows = np.zeros(COEF), np.zeros((2, POWS))
-    tiles = np.zeros((0, 2), dtype=np.int32)
-    rc = -1
-    for _ in range(2):
-        rc = lib.goofer_host_compress_plan(int(sr), *settings.astuple(), in_off.ctypes.data, n, coef.ctypes.data, pows.ctypes.data,
-                                           tiles.ctypes.data if len(tiles) else None, len(tiles), need)
-        if rc != 1:
-            break
-        tiles = np.zeros((int(need[0]), 2), dtype=np.int32)
-    if rc != 0:
-        raise ValueError("goofer_host_compress_plan refused %s Hz (%d): a rate in [%d, %d], signals shorter than 2^31 samples"
-                         % (sr, rc, MIN_SR, MAX_SR))
-    blob = np.concatenate([in_off.view(np.uint8), coef.view(np.uint8), pows.view(np.uint8).ravel(), tiles.view(np.uint8).ravel()])
-    return CompressPlan(int(sr), n, settings, coef, pows, in_off, tiles, blob)
+    tiles, = SP.fit(lambda tiles: lib.goofer_host_compress_plan(int(sr), *settings.astuple(), in_off.ctypes.data, n, coef.ctypes.data,
+                                                                pows.ctypes.data, *SP.cap(tiles), need),
+                    (np.zeros((0, 2), dtype=np.int32),), lambda: (np.zeros((int(need[0]), 2), dtype=np.int32),),
+                    lambda rc: "goofer_host_compress_plan refused %s Hz (%d): a rate in [%d, %d], signals shorter than 2^31 samples"
+                               % (sr, rc, MIN_SR, MAX_SR))
+    return CompressPlan(int(sr), n, settings, coef, pows, in_off, tiles)
 
 
 def coefficient(ms, sr) -> float:

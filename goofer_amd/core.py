@@ -1035,6 +1035,22 @@ def resynthesize(y, sr, n_fft=1024, hop_length=256, *, noise_seed=None, **kw):
     return res
 
 
+def _signal_arrays(signals):
+    """``signals`` as contiguous fp32 1-D arrays: what the batch functions over finished audio plan for"""
+    return [np.ascontiguousarray(s, dtype=np.float32).reshape(-1) for s in signals]
+
+
+def _signal_tensor(c, xs):
+    """the arrays back to back on ``c``'s device, one pad sample behind them (never an empty tensor)"""
+    return c.tensor(np.concatenate(xs + [np.zeros(1, dtype=np.float32)]))
+
+
+def _by_csr(flat, off):
+    """a flat device result on the host, sliced by the CSR ``off``: one array per signal"""
+    flat = flat.cpu().numpy()
+    return [flat[off[i]:off[i + 1]] for i in range(len(off) - 1)]
+
+
 def resample_batch(signals, sr_in, sr_out, ctx=None):
     """Audio-rate conversion of many signals in one device pass (goofer_amd.rate; goofer_rate_convert): ``signals``, 1-D arrays
     at ``sr_in``, come back as a list of fp32 arrays at ``sr_out``, signal i with ceil(len_i * sr_out / sr_in) samples.  The
@@ -1042,14 +1058,13 @@ def resample_batch(signals, sr_in, sr_out, ctx=None):
     stretch_feature, which interpolates feature rows.  ``sr_in == sr_out`` is refused: there is nothing to convert."""
     from . import rate as RT
     c = ctx or default_context()
-    xs = [np.ascontiguousarray(s, dtype=np.float32).reshape(-1) for s in signals]
+    xs = _signal_arrays(signals)
     plan = RT.plan(sr_in, sr_out, [len(s) for s in xs])
     if not plan.total_out:
         return [np.zeros(0, dtype=np.float32) for _ in xs]
-    y = c.rate_convert(c.tensor(np.concatenate(xs)), None, plan)
+    y = c.rate_convert(_signal_tensor(c, xs), None, plan)
     c.check()
-    y = y.cpu().numpy()
-    return [y[plan.out_off[i]:plan.out_off[i + 1]] for i in range(plan.n)]
+    return _by_csr(y, plan.out_off)
 
 
 def limit_batch(signals, sr, ceiling=32767.0 / 32768.0, lookahead_ms=5.0, ctx=None, true_peak=False):
@@ -1061,15 +1076,14 @@ def limit_batch(signals, sr, ceiling=32767.0 / 32768.0, lookahead_ms=5.0, ctx=No
     ceiling holds for the signal reconstructed between the samples too (goofer_limit_tp; ``sr`` of 8000 to 192000 Hz), and the
     first statistic is the true peak."""
     from . import limit as LM
-    xs = [np.ascontiguousarray(s, dtype=np.float32).reshape(-1) for s in signals]
+    xs = _signal_arrays(signals)
     plan = LM.plan(sr, [len(s) for s in xs], ceiling, lookahead_ms, bool(true_peak))
     if not plan.n:
         return [], np.zeros(0, dtype=np.float32), np.zeros(0, dtype=np.float32)
     c = ctx or default_context()
-    y, peak, gain = c.limit(c.tensor(np.concatenate(xs + [np.zeros(1, dtype=np.float32)])), None, plan)
+    y, peak, gain = c.limit(_signal_tensor(c, xs), None, plan)
     c.check()
-    y = y.cpu().numpy()
-    return [y[plan.in_off[i]:plan.in_off[i + 1]] for i in range(plan.n)], peak.cpu().numpy(), gain.cpu().numpy()
+    return _by_csr(y, plan.in_off), peak.cpu().numpy(), gain.cpu().numpy()
 
 
 def true_peak_batch(signals, sr, ctx=None):
@@ -1078,12 +1092,12 @@ def true_peak_batch(signals, sr, ctx=None):
     its rate (2 times from 96 kHz on), 0 for an empty one — after ITU-R BS.1770-4 Annex 2, this project's own definition
     (include/goofer_hip.h).  ``limit.dbtp`` makes dBTP of one."""
     from . import limit as LM
-    xs = [np.ascontiguousarray(s, dtype=np.float32).reshape(-1) for s in signals]
+    xs = _signal_arrays(signals)
     plan = LM.true_peak_plan(sr, [len(s) for s in xs])
     if not plan.n:
         return np.zeros(0, dtype=np.float32)
     c = ctx or default_context()
-    peak = c.true_peak(c.tensor(np.concatenate(xs + [np.zeros(1, dtype=np.float32)])), None, plan)
+    peak = c.true_peak(_signal_tensor(c, xs), None, plan)
     c.check()
     return peak.cpu().numpy()
 
@@ -1097,21 +1111,16 @@ def loudness_batch(signals, sr, target=None, max_gain_db=20.0, ctx=None):
     nothing was measured) and a list of float64 arrays, each signal's K-weighted energy per whole 100 ms segment
     (``loudness.momentary`` makes the momentary-loudness curve of one).  This project's own definition (include/goofer_hip.h)."""
     from . import loudness as LD
-    xs = [np.ascontiguousarray(s, dtype=np.float32).reshape(-1) for s in signals]
+    xs = _signal_arrays(signals)
     plan = LD.plan(sr, [len(s) for s in xs])
     if target is not None:
         target, max_gain_db = LD.parse((target, max_gain_db))
     if not plan.n:
         return (None if target is None else []), np.zeros((0, 2)), np.zeros(0, dtype=np.float32), []
     c = ctx or default_context()
-    y, loud, gain, seg = c.loudness(c.tensor(np.concatenate(xs + [np.zeros(1, dtype=np.float32)])), None, plan, target, max_gain_db)
+    y, loud, gain, seg = c.loudness(_signal_tensor(c, xs), None, plan, target, max_gain_db)
     c.check()
-    seg = seg.cpu().numpy()
-    segs = [seg[plan.seg_off[i]:plan.seg_off[i + 1]] for i in range(plan.n)]
-    if y is not None:
-        y = y.cpu().numpy()
-        y = [y[plan.in_off[i]:plan.in_off[i + 1]] for i in range(plan.n)]
-    return y, loud.cpu().numpy(), gain.cpu().numpy(), segs
+    return (None if y is None else _by_csr(y, plan.in_off)), loud.cpu().numpy(), gain.cpu().numpy(), _by_csr(seg, plan.seg_off)
 
 
 def compress_batch(signals, sr, threshold_db, ratio, knee_db=6.0, attack_ms=5.0, release_ms=100.0, makeup_db=0.0, curve=False, ctx=None):
@@ -1122,19 +1131,14 @@ def compress_batch(signals, sr, threshold_db, ratio, knee_db=6.0, attack_ms=5.0,
     ``[n]``, every signal's greatest gain reduction in dB; with ``curve`` also a list of float64 arrays, the gain reduction in
     dB per sample.  This project's own definition (include/goofer_hip.h)."""
     from . import compress as CP
-    xs = [np.ascontiguousarray(s, dtype=np.float32).reshape(-1) for s in signals]
+    xs = _signal_arrays(signals)
     plan = CP.plan(sr, [len(s) for s in xs], CP.Compressor(threshold_db, ratio, knee_db, attack_ms, release_ms, makeup_db))
     if not plan.n:
         return ([], np.zeros(0), []) if curve else ([], np.zeros(0))
     c = ctx or default_context()
-    y, red, yl = c.compress(c.tensor(np.concatenate(xs + [np.zeros(1, dtype=np.float32)])), None, plan, curve=curve)
+    y, red, yl = c.compress(_signal_tensor(c, xs), None, plan, curve=curve)
     c.check()
-    y = y.cpu().numpy()
-    ys = [y[plan.in_off[i]:plan.in_off[i + 1]] for i in range(plan.n)]
-    if not curve:
-        return ys, red.cpu().numpy()
-    yl = yl.cpu().numpy()
-    return ys, red.cpu().numpy(), [yl[plan.in_off[i]:plan.in_off[i + 1]] for i in range(plan.n)]
+    return (_by_csr(y, plan.in_off), red.cpu().numpy(), _by_csr(yl, plan.in_off)) if curve else (_by_csr(y, plan.in_off), red.cpu().numpy())
 
 
 def synthesize(env_spec, f0_interp, voicing_mask, y, sr, n_fft=1024, hop_length=256, glottal_smoothing=False,

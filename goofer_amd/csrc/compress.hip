@@ -393,11 +393,8 @@ extern "C" int goofer_compress(goofer_ctx *ctx, const float *x, const int64_t *i
                                void *scratch, int64_t *scratch_bytes, void *stream)
 {
     if (!ctx) return GOOFER_EINVAL;
-    if (n < 0 || total < 0 || n_tiles < 0)
-        return goofer_fail(ctx, GOOFER_EINVAL, "goofer_compress: negative count (%d signals, %lld samples, %lld tiles)", n, (long long)total,
-                           (long long)n_tiles);
-    const int64_t least = (total + CP_T - 1) / CP_T;
-    if (n_tiles < least || n_tiles > least + n || n_tiles >= ((int64_t)1 << 31))
+    if (int rc = check_counts(ctx, "goofer_compress", n, total, n_tiles)) return rc;
+    if (!signal_tiles_ok(CP_T, n, total, n_tiles))
         return goofer_fail(ctx, GOOFER_EINVAL, "goofer_compress: %lld tiles for %lld samples in %d signals is not a geometry of goofer_host_compress_plan",
                            (long long)n_tiles, (long long)total, n);
     if (!scratch_bytes) return goofer_fail(ctx, GOOFER_EINVAL, "goofer_compress: null pointer (scratch_bytes)");
@@ -415,11 +412,10 @@ extern "C" int goofer_compress(goofer_ctx *ctx, const float *x, const int64_t *i
     if (scratch) {
         if (n > 0 && (!in_off || !coef || !pows || !max_reduction || (total > 0 && (!x || !tiles || !out))))
             return goofer_fail(ctx, GOOFER_EINVAL, "goofer_compress: null pointer");
-        if (((uintptr_t)x | (uintptr_t)tiles | (uintptr_t)out) & 3 ||
-            ((uintptr_t)in_off | (uintptr_t)coef | (uintptr_t)pows | (uintptr_t)max_reduction | (uintptr_t)curve | (uintptr_t)scratch) & 7)
-            return goofer_fail(ctx, GOOFER_EINVAL, "goofer_compress: x, tiles and out must be 4-byte aligned, in_off, coef, pows, max_reduction, curve and scratch 8-byte aligned");
-        if (out != x && total > 0 && (uintptr_t)out < (uintptr_t)(x + total) && (uintptr_t)x < (uintptr_t)(out + total))
-            return goofer_fail(ctx, GOOFER_EINVAL, "goofer_compress: out overlaps x without being x");
+        if (int rc = check_aligned(ctx, "goofer_compress", "x, tiles and out", {x, tiles, out}, "in_off, coef, pows, max_reduction, curve and scratch",
+                                   {in_off, coef, pows, max_reduction, curve, scratch}))
+            return rc;
+        if (int rc = check_overlap(ctx, "goofer_compress", x, out, total, true)) return rc;
     }
     int rc = caller_scratch(ctx, scratch, scratch_bytes, "goofer_compress", carve);
     if (rc || !scratch) return rc;

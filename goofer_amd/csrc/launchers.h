@@ -2,6 +2,8 @@
 // defines it.  Included by the files that define them and by the files that call them (api.hip, synth.hip, post.hip).
 #pragma once
 
+#include <initializer_list>
+
 #include "common.h"
 #include "ragged.h"
 
@@ -31,6 +33,43 @@ static inline int walk_run_choice(goofer_ctx *ctx, int which, int64_t work, int6
     }
     ctx->walk_run_used[which] = (int)run;
     return (int)run;
+}
+
+// ---- entry checks of the stages over a ragged batch of signals (limit.hip, loudness.hip, compress.hip) ----
+// Host code.  A check fails in the name of the entry point `who` (goofer_fail) and returns its code, or GOOFER_OK.
+
+static inline int check_counts(goofer_ctx *ctx, const char *who, int n, int64_t total, int64_t n_tiles)
+{
+    if (n >= 0 && total >= 0 && n_tiles >= 0) return GOOFER_OK;
+    return goofer_fail(ctx, GOOFER_EINVAL, "%s: negative count (%d signals, %lld samples, %lld tiles)", who, n, (long long)total,
+                       (long long)n_tiles);
+}
+
+// the tile table of a host planner: every signal with samples has ceil(len / tile) tiles, between ceil(total / tile) and that plus
+// one per signal
+static inline bool signal_tiles_ok(int64_t tile, int n, int64_t total, int64_t n_tiles)
+{
+    const int64_t least = (total + tile - 1) / tile;
+    return n_tiles >= least && n_tiles <= least + n && n_tiles < ((int64_t)1 << 31);
+}
+
+// `p4` (null allowed) on 4 bytes, `p8` on 8; `names4` / `names8`: how the message lists them
+static inline int check_aligned(goofer_ctx *ctx, const char *who, const char *names4, std::initializer_list<const void *> p4,
+                                const char *names8, std::initializer_list<const void *> p8)
+{
+    uintptr_t a4 = 0, a8 = 0;
+    for (const void *p : p4) a4 |= (uintptr_t)p;
+    for (const void *p : p8) a8 |= (uintptr_t)p;
+    if (!(a4 & 3) && !(a8 & 7)) return GOOFER_OK;
+    return goofer_fail(ctx, GOOFER_EINVAL, "%s: %s must be 4-byte aligned, %s 8-byte aligned", who, names4, names8);
+}
+
+// `out` [total] may not overlap `x` [total]; with `in_place` it may be x itself
+static inline int check_overlap(goofer_ctx *ctx, const char *who, const float *x, const float *out, int64_t total, bool in_place)
+{
+    if ((in_place && out == x) || total <= 0 || (uintptr_t)out >= (uintptr_t)(x + total) || (uintptr_t)x >= (uintptr_t)(out + total))
+        return GOOFER_OK;
+    return goofer_fail(ctx, GOOFER_EINVAL, in_place ? "%s: out overlaps x without being x" : "%s: out overlaps x (halos are read from x again: not in place)", who);
 }
 
 // analysis.hip

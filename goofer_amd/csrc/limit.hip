@@ -343,23 +343,14 @@ int launch_limit(goofer_ctx *ctx, const float *x, const int64_t *in_off, int n, 
     return GOOFER_OK;
 }
 
-// every signal with samples has ceil(len / tile) tiles: between ceil(total / tile) and that plus one per signal
-static bool limit_tiles_ok(int n, int64_t total, int64_t n_tiles)
-{
-    const int64_t least = (total + LM_T - 1) / LM_T;
-    return n_tiles >= least && n_tiles <= least + n && n_tiles < ((int64_t)1 << 31);
-}
-
 // the checks of goofer_limit and goofer_limit_tp (`tp`: R, Z and tp_taps too), then the launch
 static int limit_entry(goofer_ctx *ctx, const char *who, bool tp, const float *x, const int64_t *in_off, int n, int64_t total, int W,
                        const float *taps, float c, const int32_t *tiles, int64_t n_tiles, float *out, float *peak_in, float *min_gain, int R,
                        int Z, const float *tp_taps, void *stream)
 {
     if (!ctx) return GOOFER_EINVAL;
-    if (n < 0 || total < 0 || n_tiles < 0)
-        return goofer_fail(ctx, GOOFER_EINVAL, "%s: negative count (%d signals, %lld samples, %lld tiles)", who, n, (long long)total,
-                           (long long)n_tiles);
-    if (W < 1 || W > GOOFER_LIMIT_MAX_LOOK || !(c > 0.0f && c <= 1.0f) || !limit_tiles_ok(n, total, n_tiles))
+    if (int rc = check_counts(ctx, who, n, total, n_tiles)) return rc;
+    if (W < 1 || W > GOOFER_LIMIT_MAX_LOOK || !(c > 0.0f && c <= 1.0f) || !signal_tiles_ok(LM_T, n, total, n_tiles))
         return goofer_fail(ctx, GOOFER_EINVAL, "%s: W = %d, c = %g, %lld tiles for %lld samples in %d signals is not a geometry of goofer_host_limit_plan",
                            who, W, (double)c, (long long)n_tiles, (long long)total, n);
     if (tp && ((R != 2 && R != 4) || Z != GOOFER_TP_ZEROS))
@@ -367,11 +358,9 @@ static int limit_entry(goofer_ctx *ctx, const char *who, bool tp, const float *x
     if (n == 0) return GOOFER_OK;
     if (!in_off || !taps || !peak_in || !min_gain || (tp && !tp_taps) || (total > 0 && (!x || !out || !tiles)))
         return goofer_fail(ctx, GOOFER_EINVAL, "%s: null pointer", who);
-    if (((uintptr_t)x | (uintptr_t)taps | (uintptr_t)out | (uintptr_t)tiles | (uintptr_t)peak_in | (uintptr_t)min_gain | (uintptr_t)tp_taps) & 3 ||
-        ((uintptr_t)in_off) & 7)
-        return goofer_fail(ctx, GOOFER_EINVAL, "%s: x, taps, tiles, out, peak_in and min_gain must be 4-byte aligned, in_off 8-byte aligned", who);
-    if (total > 0 && (uintptr_t)out < (uintptr_t)(x + total) && (uintptr_t)x < (uintptr_t)(out + total))
-        return goofer_fail(ctx, GOOFER_EINVAL, "%s: out overlaps x (halos are read from x again: not in place)", who);
+    if (int rc = check_aligned(ctx, who, "x, taps, tiles, out, peak_in and min_gain", {x, taps, out, tiles, peak_in, min_gain, tp_taps}, "in_off", {in_off}))
+        return rc;
+    if (int rc = check_overlap(ctx, who, x, out, total, false)) return rc;
     return launch_limit(ctx, x, in_off, n, W, taps, c, tiles, n_tiles, out, peak_in, min_gain, (hipStream_t)stream, tp ? R : 0, tp_taps);
 }
 
@@ -392,17 +381,14 @@ extern "C" int goofer_true_peak(goofer_ctx *ctx, const float *x, const int64_t *
                                 const int32_t *tiles, int64_t n_tiles, float *peak, void *stream)
 {
     if (!ctx) return GOOFER_EINVAL;
-    if (n < 0 || total < 0 || n_tiles < 0)
-        return goofer_fail(ctx, GOOFER_EINVAL, "goofer_true_peak: negative count (%d signals, %lld samples, %lld tiles)", n, (long long)total,
-                           (long long)n_tiles);
-    if ((R != 2 && R != 4) || Z != GOOFER_TP_ZEROS || !limit_tiles_ok(n, total, n_tiles))
+    if (int rc = check_counts(ctx, "goofer_true_peak", n, total, n_tiles)) return rc;
+    if ((R != 2 && R != 4) || Z != GOOFER_TP_ZEROS || !signal_tiles_ok(LM_T, n, total, n_tiles))
         return goofer_fail(ctx, GOOFER_EINVAL, "goofer_true_peak: R = %d, Z = %d, %lld tiles for %lld samples in %d signals is not a geometry of goofer_host_true_peak_plan and goofer_host_limit_plan",
                            R, Z, (long long)n_tiles, (long long)total, n);
     if (n == 0) return GOOFER_OK;
     if (!in_off || !taps || !peak || (total > 0 && (!x || !tiles)))
         return goofer_fail(ctx, GOOFER_EINVAL, "goofer_true_peak: null pointer");
-    if (((uintptr_t)x | (uintptr_t)taps | (uintptr_t)tiles | (uintptr_t)peak) & 3 || ((uintptr_t)in_off) & 7)
-        return goofer_fail(ctx, GOOFER_EINVAL, "goofer_true_peak: x, taps, tiles and peak must be 4-byte aligned, in_off 8-byte aligned");
+    if (int rc = check_aligned(ctx, "goofer_true_peak", "x, taps, tiles and peak", {x, taps, tiles, peak}, "in_off", {in_off})) return rc;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_limit_init, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, peak, (float *)nullptr);
     LAUNCH_CHECK(ctx);

@@ -367,13 +367,10 @@ extern "C" int goofer_loudness_measure(goofer_ctx *ctx, const float *x, const in
                                        int64_t *scratch_bytes, void *stream)
 {
     if (!ctx) return GOOFER_EINVAL;
-    if (n < 0 || total < 0 || n_tiles < 0)
-        return goofer_fail(ctx, GOOFER_EINVAL, "goofer_loudness_measure: negative count (%d signals, %lld samples, %lld tiles)", n,
-                           (long long)total, (long long)n_tiles);
-    const int64_t least = (total + LD_T - 1) / LD_T;
+    if (int rc = check_counts(ctx, "goofer_loudness_measure", n, total, n_tiles)) return rc;
     const int s_lo = (GOOFER_LOUDNESS_MIN_SR + 5) / 10, s_hi = (GOOFER_LOUDNESS_MAX_SR + 5) / 10;
     if (S < s_lo || S > s_hi || std::isinf(target) || !(max_gain_db >= 0.0 && max_gain_db <= GOOFER_LOUDNESS_MAX_GAIN_DB_CAP) ||
-        n_tiles < least || n_tiles > least + n || n_tiles >= ((int64_t)1 << 31))
+        !signal_tiles_ok(LD_T, n, total, n_tiles))
         return goofer_fail(ctx, GOOFER_EINVAL, "goofer_loudness_measure: S = %d, target %g, max_gain_db %g, %lld tiles for %lld samples in %d signals is not a geometry of goofer_host_loudness_plan",
                            S, target, max_gain_db, (long long)n_tiles, (long long)total, n);
     if (!scratch_bytes) return goofer_fail(ctx, GOOFER_EINVAL, "goofer_loudness_measure: null pointer (scratch_bytes)");
@@ -388,9 +385,9 @@ extern "C" int goofer_loudness_measure(goofer_ctx *ctx, const float *x, const in
     if (scratch) {
         if (n > 0 && (!in_off || !coef || !mats || !seg_off || !seg_energy || !loud || !gain || (total > 0 && (!x || !tiles))))
             return goofer_fail(ctx, GOOFER_EINVAL, "goofer_loudness_measure: null pointer");
-        if (((uintptr_t)x | (uintptr_t)tiles | (uintptr_t)gain) & 3 ||
-            ((uintptr_t)in_off | (uintptr_t)coef | (uintptr_t)mats | (uintptr_t)seg_off | (uintptr_t)seg_energy | (uintptr_t)loud | (uintptr_t)scratch) & 7)
-            return goofer_fail(ctx, GOOFER_EINVAL, "goofer_loudness_measure: x, tiles and gain must be 4-byte aligned, in_off, coef, mats, seg_off, seg_energy, loud and scratch 8-byte aligned");
+        if (int rc = check_aligned(ctx, "goofer_loudness_measure", "x, tiles and gain", {x, tiles, gain}, "in_off, coef, mats, seg_off, seg_energy, loud and scratch",
+                                   {in_off, coef, mats, seg_off, seg_energy, loud, scratch}))
+            return rc;
     }
     int rc = caller_scratch(ctx, scratch, scratch_bytes, "goofer_loudness_measure", carve);
     if (rc || !scratch) return rc;
@@ -405,9 +402,7 @@ extern "C" int goofer_loudness_apply(goofer_ctx *ctx, const float *x, const int6
     if (n < 0 || total < 0) return goofer_fail(ctx, GOOFER_EINVAL, "goofer_loudness_apply: negative count (%d signals, %lld samples)", n, (long long)total);
     if (n == 0 || total == 0) return GOOFER_OK;
     if (!x || !in_off || !gain || !out) return goofer_fail(ctx, GOOFER_EINVAL, "goofer_loudness_apply: null pointer");
-    if (((uintptr_t)x | (uintptr_t)gain | (uintptr_t)out) & 3 || ((uintptr_t)in_off) & 7)
-        return goofer_fail(ctx, GOOFER_EINVAL, "goofer_loudness_apply: x, gain and out must be 4-byte aligned, in_off 8-byte aligned");
-    if (out != x && (uintptr_t)out < (uintptr_t)(x + total) && (uintptr_t)x < (uintptr_t)(out + total))
-        return goofer_fail(ctx, GOOFER_EINVAL, "goofer_loudness_apply: out overlaps x without being x");
+    if (int rc = check_aligned(ctx, "goofer_loudness_apply", "x, gain and out", {x, gain, out}, "in_off", {in_off})) return rc;
+    if (int rc = check_overlap(ctx, "goofer_loudness_apply", x, out, total, true)) return rc;
     return launch_loudness_apply(ctx, x, in_off, n, total, gain, out, (hipStream_t)stream);
 }

@@ -1065,6 +1065,22 @@ int goofer_host_rate_plan(int sr_in, int sr_out, const int64_t *in_off, int n, i
     return GOOFER_OK;
 }
 
+/* The tile table of the stages that cut every signal of a ragged batch into tiles of `tile` samples (limit, loudness,
+ * compress): per tile the pair (signal, tile of the signal), signal by signal.  Without `tiles` it checks and counts: the number
+ * of tiles, or -1 for a signal shorter than 0 or of 2^31 samples or more and for 2^31 tiles or more.  With `tiles` it fills. */
+static int64_t signal_tiles(const int64_t *in_off, int n, int64_t tile, int32_t *tiles)
+{
+    int64_t t = 0;
+    for (int i = 0; i < n; ++i) {
+        const int64_t len = in_off[i + 1] - in_off[i];
+        if (len < 0 || len >= ((int64_t)1 << 31)) return -1;
+        const int64_t cnt = (len + tile - 1) / tile;
+        for (int64_t k = 0; tiles && k < cnt; ++k) tiles[2 * (t + k)] = i, tiles[2 * (t + k) + 1] = (int32_t)k;
+        t += cnt;
+    }
+    return t < ((int64_t)1 << 31) ? t : -1;
+}
+
 /* Look-ahead peak limiter (include/goofer_hip.h; the kernel: limit.hip): the look-ahead in samples, the raised-cosine table in
  * float64 and, per tile of GOOFER_LIMIT_TILE samples of a signal, the pair (signal, tile of the signal) a workgroup reads. */
 int goofer_host_limit_plan(int sr, double look_ms, float c, const int64_t *in_off, int n, int *W, float *taps, int64_t taps_cap,
@@ -1075,13 +1091,8 @@ int goofer_host_limit_plan(int sr, double look_ms, float c, const int64_t *in_of
     if (sr < 1 || !std::isfinite(look_ms) || !(c > 0.0f && c <= 1.0f)) return GOOFER_EINVAL;
     const double look = std::floor(look_ms * (double)sr / 1000.0 + 0.5);
     if (!(look >= 1.0 && look <= (double)GOOFER_LIMIT_MAX_LOOK)) return GOOFER_EINVAL;
-    int64_t n_tiles = 0;
-    for (int i = 0; i < n; ++i) {
-        const int64_t len = in_off[i + 1] - in_off[i];
-        if (len < 0 || len >= ((int64_t)1 << 31)) return GOOFER_EINVAL;
-        n_tiles += (len + GOOFER_LIMIT_TILE - 1) / GOOFER_LIMIT_TILE;
-    }
-    if (n_tiles >= ((int64_t)1 << 31)) return GOOFER_EINVAL;
+    const int64_t n_tiles = signal_tiles(in_off, n, GOOFER_LIMIT_TILE, nullptr);
+    if (n_tiles < 0) return GOOFER_EINVAL;
     const int w = (int)look, K = 2 * w + 1;
     *W = w;
     need[0] = K, need[1] = n_tiles;
@@ -1094,11 +1105,7 @@ int goofer_host_limit_plan(int sr, double look_ms, float c, const int64_t *in_of
         sum += row[k];
     }
     for (int k = 0; k < K; ++k) taps[k] = (float)(row[k] / sum);
-    int64_t t = 0;
-    for (int i = 0; i < n; ++i) {
-        const int64_t cnt = (in_off[i + 1] - in_off[i] + GOOFER_LIMIT_TILE - 1) / GOOFER_LIMIT_TILE;
-        for (int64_t k = 0; k < cnt; ++k, ++t) tiles[2 * t] = i, tiles[2 * t + 1] = (int32_t)k;
-    }
+    signal_tiles(in_off, n, GOOFER_LIMIT_TILE, tiles);
     return GOOFER_OK;
 }
 
@@ -1150,13 +1157,8 @@ int goofer_host_loudness_plan(int sr, const int64_t *in_off, int n, int *S, doub
     if (!S || !coef || !mats || !seg_off || !need || n < 0 || tiles_cap < 0 || (n > 0 && !in_off) || (tiles_cap > 0 && !tiles))
         return GOOFER_EINVAL;
     if (sr < GOOFER_LOUDNESS_MIN_SR || sr > GOOFER_LOUDNESS_MAX_SR) return GOOFER_EINVAL;
-    int64_t n_tiles = 0;
-    for (int i = 0; i < n; ++i) {
-        const int64_t len = in_off[i + 1] - in_off[i];
-        if (len < 0 || len >= ((int64_t)1 << 31)) return GOOFER_EINVAL;
-        n_tiles += (len + GOOFER_LOUDNESS_TILE - 1) / GOOFER_LOUDNESS_TILE;
-    }
-    if (n_tiles >= ((int64_t)1 << 31)) return GOOFER_EINVAL;
+    const int64_t n_tiles = signal_tiles(in_off, n, GOOFER_LOUDNESS_TILE, nullptr);
+    if (n_tiles < 0) return GOOFER_EINVAL;
     const int s = (int)std::floor((double)sr / 10.0 + 0.5);
     *S = s;
     need[0] = n_tiles;
@@ -1193,12 +1195,8 @@ int goofer_host_loudness_plan(int sr, const int64_t *in_off, int n, int *S, doub
         loud_matmul(A, A, A);
     }
     seg_off[0] = 0;
-    int64_t t = 0;
-    for (int i = 0; i < n; ++i) {
-        const int64_t len = in_off[i + 1] - in_off[i], cnt = (len + GOOFER_LOUDNESS_TILE - 1) / GOOFER_LOUDNESS_TILE;
-        seg_off[i + 1] = seg_off[i] + len / s;
-        for (int64_t k = 0; k < cnt; ++k, ++t) tiles[2 * t] = i, tiles[2 * t + 1] = (int32_t)k;
-    }
+    for (int i = 0; i < n; ++i) seg_off[i + 1] = seg_off[i] + (in_off[i + 1] - in_off[i]) / s;
+    signal_tiles(in_off, n, GOOFER_LOUDNESS_TILE, tiles);
     return GOOFER_OK;
 }
 
@@ -1215,13 +1213,8 @@ int goofer_host_compress_plan(int sr, double threshold_db, double ratio, double 
         !(attack_ms >= 0.0 && attack_ms <= 1000.0) || !(release_ms >= 0.0 && release_ms <= 5000.0) ||
         !(makeup_db >= -24.0 && makeup_db <= 24.0))
         return GOOFER_EINVAL;                                   // (written so that a NaN is refused too; ratio may be +inf)
-    int64_t n_tiles = 0;
-    for (int i = 0; i < n; ++i) {
-        const int64_t len = in_off[i + 1] - in_off[i];
-        if (len < 0 || len >= ((int64_t)1 << 31)) return GOOFER_EINVAL;
-        n_tiles += (len + GOOFER_COMPRESS_TILE - 1) / GOOFER_COMPRESS_TILE;
-    }
-    if (n_tiles >= ((int64_t)1 << 31)) return GOOFER_EINVAL;
+    const int64_t n_tiles = signal_tiles(in_off, n, GOOFER_COMPRESS_TILE, nullptr);
+    if (n_tiles < 0) return GOOFER_EINVAL;
     need[0] = n_tiles;
     if (tiles_cap < n_tiles) return 1;
     const double aA = attack_ms == 0.0 ? 0.0 : std::exp(-1.0 / (attack_ms * 1e-3 * (double)sr));
@@ -1232,11 +1225,7 @@ int goofer_host_compress_plan(int sr, double threshold_db, double ratio, double 
         long double m = (long double)GOOFER_COMPRESS_SPT;
         for (int k = 0; k < GOOFER_COMPRESS_POWS; ++k, m *= 2.0L) pows[GOOFER_COMPRESS_POWS * which + k] = (double)std::pow(a, m);
     }
-    int64_t t = 0;
-    for (int i = 0; i < n; ++i) {
-        const int64_t cnt = (in_off[i + 1] - in_off[i] + GOOFER_COMPRESS_TILE - 1) / GOOFER_COMPRESS_TILE;
-        for (int64_t k = 0; k < cnt; ++k, ++t) tiles[2 * t] = i, tiles[2 * t + 1] = (int32_t)k;
-    }
+    signal_tiles(in_off, n, GOOFER_COMPRESS_TILE, tiles);
     return GOOFER_OK;
 }
 

@@ -235,6 +235,29 @@ class Context:
                                                _ptr(tile_notes), total, _ptr(out), self._stream()))
         return out
 
+    def _signals(self, who, x, d_off, plan, out, n_out=None, make_out=True):
+        """The argument checks the stages over a ragged batch share (rate_convert, compress, loudness, limit, true_peak), each a
+        ValueError in ``who``'s name: ``d_off`` a device tensor (one contiguous int64 CSR of ``plan.n`` signals), a host sequence
+        (equal to the plan's) or None for the plan's own; ``x`` a contiguous fp32 tensor of at least ``plan.total`` samples;
+        ``out`` None or a contiguous fp32 tensor of ``n_out`` samples (default: ``plan.total``).  Returns (the offsets on the
+        device, ``out``, or with ``make_out`` a new tensor where it is None).  That ``out`` overlaps ``x`` is the library's to
+        refuse."""
+        n, n_out = plan.n, plan.total if n_out is None else n_out
+        d_in = plan.device_tables(self)[0]
+        if isinstance(d_off, torch.Tensor):
+            if d_off.dtype != torch.int64 or not d_off.is_contiguous() or d_off.numel() != n + 1:
+                raise ValueError("%s: the offsets are one contiguous int64 CSR of the plan's %d signals" % (who, n))
+            d_in = d_off
+        elif d_off is not None and not np.array_equal(np.asarray(d_off, dtype=np.int64), plan.in_off):
+            raise ValueError("%s: the offsets are not the CSR the plan was made for" % who)
+        if x.dtype != torch.float32 or not x.is_contiguous() or x.numel() < plan.total:
+            raise ValueError("%s: x must be a contiguous float32 tensor of the plan's %d samples" % (who, plan.total))
+        if out is None:
+            out = torch.empty(n_out, dtype=torch.float32, device=self.device) if make_out else None
+        elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != n_out:
+            raise ValueError("%s: out must be a contiguous float32 tensor of the %d output samples" % (who, n_out))
+        return d_in, out
+
     def rate_convert(self, x, in_off, plan, out=None):
         """The signals of a ragged batch converted to another sample rate on the device (goofer_rate_convert; the definition:
         include/goofer_hip.h, restated in tests/rate_ref.py).  ``x``: the signals' samples back to back, a contiguous fp32 device
@@ -245,19 +268,8 @@ class Context:
         not be cleared, every sample is stored).  Signal i's output is ``out[plan.out_off[i]:plan.out_off[i + 1]]``.
         Asynchronous on the current stream."""
         n, total = plan.n, plan.total_out
-        d_in, d_out, taps = plan.device_tables(self)
-        if isinstance(in_off, torch.Tensor):
-            if in_off.dtype != torch.int64 or not in_off.is_contiguous() or in_off.numel() != n + 1:
-                raise ValueError("rate_convert: in_off is one contiguous int64 CSR of the plan's %d signals" % n)
-            d_in = in_off
-        elif in_off is not None and not np.array_equal(np.asarray(in_off, dtype=np.int64), plan.in_off):
-            raise ValueError("rate_convert: in_off is not the CSR the plan was made for")
-        if x.dtype != torch.float32 or not x.is_contiguous() or x.numel() < plan.total_in:
-            raise ValueError("rate_convert: x must be a contiguous float32 tensor of the plan's %d samples" % plan.total_in)
-        if out is None:
-            out = torch.empty(total, dtype=torch.float32, device=self.device)
-        elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != total:
-            raise ValueError("rate_convert: out must be a contiguous float32 tensor of the %d output samples" % total)
+        d_in, out = self._signals("rate_convert", x, in_off, plan, out, n_out=total)
+        _, d_out, taps = plan.device_tables(self)
         if total:                                              # (signals without samples have no output: nothing to launch)
             self._check(self.lib.goofer_rate_convert(self.h, _ptr(x), _ptr(d_in), n, plan.L, plan.M, plan.H, _ptr(taps), _ptr(d_out),
                                                      _ptr(out), self._stream()))
@@ -276,19 +288,8 @@ class Context:
         the oversampled envelope (restated in tests/true_peak_ref.py) and ``peak_in`` is the true peak.  Asynchronous on the
         current stream."""
         n, total = plan.n, plan.total
-        d_in, tiles, taps = plan.device_tables(self)
-        if isinstance(d_off, torch.Tensor):
-            if d_off.dtype != torch.int64 or not d_off.is_contiguous() or d_off.numel() != n + 1:
-                raise ValueError("limit: d_off is one contiguous int64 CSR of the plan's %d signals" % n)
-            d_in = d_off
-        elif d_off is not None and not np.array_equal(np.asarray(d_off, dtype=np.int64), plan.in_off):
-            raise ValueError("limit: d_off is not the CSR the plan was made for")
-        if x.dtype != torch.float32 or not x.is_contiguous() or x.numel() < total:
-            raise ValueError("limit: x must be a contiguous float32 tensor of the plan's %d samples" % total)
-        if out is None:
-            out = torch.empty(total, dtype=torch.float32, device=self.device)
-        elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != total:
-            raise ValueError("limit: out must be a contiguous float32 tensor of the %d samples" % total)
+        d_in, out = self._signals("limit", x, d_off, plan, out)
+        _, tiles, taps = plan.device_tables(self)
         peak_in = torch.empty(n, dtype=torch.float32, device=self.device)
         min_gain = torch.empty(n, dtype=torch.float32, device=self.device)
         if n:
@@ -310,15 +311,8 @@ class Context:
         if not plan.true_peak:
             raise ValueError("true_peak: the plan has no true-peak table (limit.true_peak_plan)")
         n, total = plan.n, plan.total
-        d_in, tiles, _ = plan.device_tables(self)
-        if isinstance(d_off, torch.Tensor):
-            if d_off.dtype != torch.int64 or not d_off.is_contiguous() or d_off.numel() != n + 1:
-                raise ValueError("true_peak: d_off is one contiguous int64 CSR of the plan's %d signals" % n)
-            d_in = d_off
-        elif d_off is not None and not np.array_equal(np.asarray(d_off, dtype=np.int64), plan.in_off):
-            raise ValueError("true_peak: d_off is not the CSR the plan was made for")
-        if x.dtype != torch.float32 or not x.is_contiguous() or x.numel() < total:
-            raise ValueError("true_peak: x must be a contiguous float32 tensor of the plan's %d samples" % total)
+        d_in, _ = self._signals("true_peak", x, d_off, plan, None, make_out=False)
+        tiles = plan.device_tables(self)[1]
         peak = torch.empty(n, dtype=torch.float32, device=self.device)
         if n:
             self._check(self.lib.goofer_true_peak(self.h, _ptr(x) if total else None, _ptr(d_in), n, total, plan.R, plan.Z,
@@ -346,33 +340,19 @@ class Context:
             target, cap = LD.parse((target, cap))
         elif not 0.0 <= cap <= LD.MAX_GAIN_DB_CAP:
             raise ValueError("loudness: max_gain_db lies in [0, %g]" % LD.MAX_GAIN_DB_CAP)
-        d_in, d_seg, coef, mats, tiles = plan.device_tables(self)
-        if isinstance(d_off, torch.Tensor):
-            if d_off.dtype != torch.int64 or not d_off.is_contiguous() or d_off.numel() != n + 1:
-                raise ValueError("loudness: d_off is one contiguous int64 CSR of the plan's %d signals" % n)
-            d_in = d_off
-        elif d_off is not None and not np.array_equal(np.asarray(d_off, dtype=np.int64), plan.in_off):
-            raise ValueError("loudness: d_off is not the CSR the plan was made for")
-        if x.dtype != torch.float32 or not x.is_contiguous() or x.numel() < total:
-            raise ValueError("loudness: x must be a contiguous float32 tensor of the plan's %d samples" % total)
-        if out is not None and (target is None or out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != total):
+        if out is not None and target is None:
             raise ValueError("loudness: out, with a target only, must be a contiguous float32 tensor of the %d samples" % total)
+        d_in, y = self._signals("loudness", x, d_off, plan, out, make_out=target is not None)
+        _, d_seg, coef, mats, tiles = plan.device_tables(self)
         seg_buf = torch.empty(max(plan.n_segments, 1), dtype=torch.float64, device=self.device)     # (never a null pointer)
         seg = seg_buf[:plan.n_segments]
         loud = torch.empty((n, 2), dtype=torch.float64, device=self.device)
         gain = torch.empty(n, dtype=torch.float32, device=self.device)
-        y = None
-        if target is not None:
-            y = torch.empty(total, dtype=torch.float32, device=self.device) if out is None else out
         if n:
-            args = (self.h, _ptr(x) if total else None, _ptr(d_in), n, total, plan.S, _ptr(coef), _ptr(mats), _ptr(d_seg),
+            args = (_ptr(x) if total else None, _ptr(d_in), n, total, plan.S, _ptr(coef), _ptr(mats), _ptr(d_seg),
                     _ptr(tiles) if total else None, plan.n_tiles, math.nan if target is None else target, cap,
                     _ptr(seg_buf), _ptr(loud), _ptr(gain))
-            size = C.c_int64(0)
-            self._check(self.lib.goofer_loudness_measure(*args, None, C.byref(size), None))
-            scratch = torch.empty(max(int(size.value), 256), dtype=torch.uint8, device=self.device)
-            size = C.c_int64(scratch.numel())
-            self._check(self.lib.goofer_loudness_measure(*args, _ptr(scratch), C.byref(size), self._stream()))
+            self._scratch_call(self.lib.goofer_loudness_measure, args)
             if y is not None and total:
                 self._check(self.lib.goofer_loudness_apply(self.h, _ptr(x), _ptr(d_in), n, total, _ptr(gain), _ptr(y), self._stream()))
         return y, loud, gain, seg
@@ -388,28 +368,14 @@ class Context:
         gain reduction of every signal in dB (0 for a signal without a sample), and ``yl`` float64 ``[plan.total]``, the gain
         reduction in dB per sample, or None without ``curve``.  Asynchronous on the current stream."""
         n, total = plan.n, plan.total
-        d_in, coef, pows, tiles = plan.device_tables(self)
-        if isinstance(d_off, torch.Tensor):
-            if d_off.dtype != torch.int64 or not d_off.is_contiguous() or d_off.numel() != n + 1:
-                raise ValueError("compress: d_off is one contiguous int64 CSR of the plan's %d signals" % n)
-            d_in = d_off
-        elif d_off is not None and not np.array_equal(np.asarray(d_off, dtype=np.int64), plan.in_off):
-            raise ValueError("compress: d_off is not the CSR the plan was made for")
-        if x.dtype != torch.float32 or not x.is_contiguous() or x.numel() < total:
-            raise ValueError("compress: x must be a contiguous float32 tensor of the plan's %d samples" % total)
-        if out is not None and (out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != total):
-            raise ValueError("compress: out must be a contiguous float32 tensor of the %d samples" % total)
-        y = torch.empty(total, dtype=torch.float32, device=self.device) if out is None else out
+        d_in, y = self._signals("compress", x, d_off, plan, out)
+        _, coef, pows, tiles = plan.device_tables(self)
         red = torch.zeros(n, dtype=torch.float64, device=self.device)
         yl = torch.empty(total, dtype=torch.float64, device=self.device) if curve else None
         if n:
-            args = (self.h, _ptr(x) if total else None, _ptr(d_in), n, total, _ptr(coef), _ptr(pows), _ptr(tiles) if total else None,
+            args = (_ptr(x) if total else None, _ptr(d_in), n, total, _ptr(coef), _ptr(pows), _ptr(tiles) if total else None,
                     plan.n_tiles, _ptr(y) if total else None, _ptr(red), _ptr(yl) if curve and total else None)
-            size = C.c_int64(0)
-            self._check(self.lib.goofer_compress(*args, None, C.byref(size), None))
-            scratch = torch.empty(max(int(size.value), 256), dtype=torch.uint8, device=self.device)
-            size = C.c_int64(scratch.numel())
-            self._check(self.lib.goofer_compress(*args, _ptr(scratch), C.byref(size), self._stream()))
+            self._scratch_call(self.lib.goofer_compress, args)
         return y, red, yl
 
     def normal_fill(self, seed: int, params, lengths_or_offsets, tag: int, note_on=None, growl_scale=None, out=None):

@@ -16,11 +16,12 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from dataclasses import dataclass, field
+from dataclasses import dataclass
 
 import numpy as np
 
 from . import _lib
+from . import signal_plan as SP
 
 MAX_LOOK = 1024                     # GOOFER_LIMIT_MAX_LOOK
 TILE = 4096                         # GOOFER_LIMIT_TILE
@@ -40,10 +41,11 @@ class Limiter:
 
 
 @dataclass
-class LimitPlan:
+class LimitPlan(SP.SignalPlan):
     """What goofer_limit takes for one ragged batch: the look-ahead ``W`` in samples, the ceiling (an fp32 value), the table
     ``taps`` (float32 [2W + 1]), the signals' CSR ``in_off`` (int64 [n + 1]) and the tile table ``tiles`` (int32 [n_tiles, 2]:
-    signal, tile of the signal); ``blob`` holds offsets, tiles and table back to back for one upload."""
+    signal, tile of the signal); with ``true_peak`` the factor ``R``, ``Z`` and the table ``tp_taps`` (float32 [R - 1, 2Z]), else
+    0, 0 and an empty one; ``blob`` holds offsets, tiles and the two tables back to back for one upload."""
     sr: int
     n: int
     W: int
@@ -51,23 +53,14 @@ class LimitPlan:
     taps: np.ndarray
     in_off: np.ndarray
     tiles: np.ndarray
-    blob: np.ndarray
-    R: int = 0
-    Z: int = 0
-    tp_taps: np.ndarray = None
-    _dev: dict = field(default_factory=dict, repr=False)
+    R: int
+    Z: int
+    tp_taps: np.ndarray
+    BLOB = ("in_off", "tiles", "taps", "tp_taps")
 
     @property
     def true_peak(self) -> bool:
         return self.R != 0
-
-    @property
-    def total(self) -> int:
-        return int(self.in_off[-1])
-
-    @property
-    def n_tiles(self) -> int:
-        return len(self.tiles)
 
     def device_tables(self, ctx):
         """(in_off, tiles, taps) on ``ctx``'s device: views of the blob, uploaded on first use."""
@@ -76,17 +69,6 @@ class LimitPlan:
     def device_tp_taps(self, ctx):
         """the true-peak table on ``ctx``'s device: a view of the same blob"""
         return self._tables(ctx)[3]
-
-    def _tables(self, ctx):
-        import torch
-        hit = self._dev.get(ctx.device)
-        if hit is None:
-            d = ctx.tensor(self.blob)
-            a, b = self.in_off.nbytes, self.in_off.nbytes + self.tiles.nbytes
-            e = b + self.taps.nbytes
-            hit = self._dev[ctx.device] = (d[:a].view(torch.int64), d[a:b].view(torch.int32), d[b:e].view(torch.float32),
-                                           d[e:].view(torch.float32), d)
-        return hit
 
 
 def parse(limit):
@@ -111,15 +93,9 @@ def true_peak_table(sr):
     if int(sr) != sr:
         raise ValueError("limit.true_peak_table: the sample rate is a whole number of Hz")
     R, Z, need = C.c_int(0), C.c_int(0), C.c_int64(0)
-    taps = np.zeros(0, dtype=np.float32)
-    rc = -1
-    for _ in range(2):
-        rc = lib.goofer_host_true_peak_plan(int(sr), C.byref(R), C.byref(Z), taps.ctypes.data if taps.size else None, taps.size, C.byref(need))
-        if rc != 1:
-            break
-        taps = np.zeros(int(need.value), dtype=np.float32)
-    if rc != 0:
-        raise ValueError("goofer_host_true_peak_plan refused %s Hz (%d): true-peak detection takes %d to %d Hz" % (sr, rc, TP_MIN_SR, TP_MAX_SR))
+    taps, = SP.fit(lambda taps: lib.goofer_host_true_peak_plan(int(sr), C.byref(R), C.byref(Z), *SP.cap(taps), C.byref(need)),
+                   (np.zeros(0, dtype=np.float32),), lambda: (np.zeros(int(need.value), dtype=np.float32),),
+                   lambda rc: "goofer_host_true_peak_plan refused %s Hz (%d): true-peak detection takes %d to %d Hz" % (sr, rc, TP_MIN_SR, TP_MAX_SR))
     return R.value, Z.value, taps.reshape(R.value - 1, 2 * Z.value)
 
 
@@ -141,31 +117,19 @@ def plan(sr, lengths, ceiling=CEILING, lookahead_ms=LOOK_MS, true_peak=False) ->
     below 1, a signal of 2^31 samples or more.  ``true_peak``: also goofer_host_true_peak_plan's factor and table (a rate of
     8000 to 192000 Hz), in the same blob."""
     lib = _lib.load()
-    lengths = np.ascontiguousarray(lengths, dtype=np.int64).reshape(-1)
-    if lengths.size and lengths.min() < 0:
-        raise ValueError("limit.plan: a negative length")
-    if int(sr) != sr:
-        raise ValueError("limit.plan: the sample rate is a whole number of Hz")
-    n = len(lengths)
-    in_off = np.zeros(n + 1, dtype=np.int64)
-    np.cumsum(lengths, out=in_off[1:])
+    in_off = SP.offsets("limit.plan", lengths, sr)
+    n = len(in_off) - 1
     c = float(np.float32(ceiling))
     W, need = C.c_int(0), (C.c_int64 * 2)(0, 0)
-    taps, tiles = np.zeros(0, dtype=np.float32), np.zeros((0, 2), dtype=np.int32)
-    rc = -1
-    for _ in range(2):
-        rc = lib.goofer_host_limit_plan(int(sr), float(lookahead_ms), C.c_float(c), in_off.ctypes.data, n, C.byref(W),
-                                        taps.ctypes.data if taps.size else None, taps.size,
-                                        tiles.ctypes.data if tiles.size else None, len(tiles), need)
-        if rc != 1:
-            break
-        taps, tiles = np.zeros(int(need[0]), dtype=np.float32), np.zeros((int(need[1]), 2), dtype=np.int32)
-    if rc != 0:
-        raise ValueError("goofer_host_limit_plan refused a ceiling of %r and %r ms at %s Hz (%d): a ceiling in (0, 1], a look-ahead of "
-                         "1 to %d samples, a rate >= 1, signals shorter than 2^31 samples" % (ceiling, lookahead_ms, sr, rc, MAX_LOOK))
+    taps, tiles = SP.fit(
+        lambda taps, tiles: lib.goofer_host_limit_plan(int(sr), float(lookahead_ms), C.c_float(c), in_off.ctypes.data, n, C.byref(W),
+                                                       *SP.cap(taps), *SP.cap(tiles), need),
+        (np.zeros(0, dtype=np.float32), np.zeros((0, 2), dtype=np.int32)),
+        lambda: (np.zeros(int(need[0]), dtype=np.float32), np.zeros((int(need[1]), 2), dtype=np.int32)),
+        lambda rc: "goofer_host_limit_plan refused a ceiling of %r and %r ms at %s Hz (%d): a ceiling in (0, 1], a look-ahead of 1 to %d "
+                   "samples, a rate >= 1, signals shorter than 2^31 samples" % (ceiling, lookahead_ms, sr, rc, MAX_LOOK))
     R, Z, tp_taps = true_peak_table(sr) if true_peak else (0, 0, np.zeros((0, 0), dtype=np.float32))
-    blob = np.concatenate([in_off.view(np.uint8), tiles.view(np.uint8).ravel(), taps.view(np.uint8), tp_taps.view(np.uint8).ravel()])
-    return LimitPlan(int(sr), n, W.value, c, taps, in_off, tiles, blob, R, Z, tp_taps)
+    return LimitPlan(int(sr), n, W.value, c, taps, in_off, tiles, R, Z, tp_taps)
 
 
 def look_samples(sr, lookahead_ms=LOOK_MS) -> int:

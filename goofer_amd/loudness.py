@@ -13,11 +13,12 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from dataclasses import dataclass, field
+from dataclasses import dataclass
 
 import numpy as np
 
 from . import _lib
+from . import signal_plan as SP
 
 MIN_SR = 8000                       # GOOFER_LOUDNESS_MIN_SR
 MAX_SR = 192000                     # GOOFER_LOUDNESS_MAX_SR
@@ -30,7 +31,7 @@ SLOTS = 8                           # GOOFER_LOUDNESS_SLOTS
 
 
 @dataclass
-class LoudnessPlan:
+class LoudnessPlan(SP.SignalPlan):
     """What goofer_loudness_measure takes for one ragged batch: the segment length ``S`` in samples, the K-weighting
     coefficients ``coef`` (float64 [10]: shelf b0 b1 b2 a1 a2, high-pass likewise), ``mats`` (float64 [20, 4, 4], the powers
     A^(16 * 2^k) of the state-transition matrix), the signals' CSR ``in_off`` and the segments' ``seg_off`` (int64 [n + 1]) and
@@ -44,32 +45,11 @@ class LoudnessPlan:
     in_off: np.ndarray
     seg_off: np.ndarray
     tiles: np.ndarray
-    blob: np.ndarray
-    _dev: dict = field(default_factory=dict, repr=False)
-
-    @property
-    def total(self) -> int:
-        return int(self.in_off[-1])
-
-    @property
-    def n_tiles(self) -> int:
-        return len(self.tiles)
+    BLOB = ("in_off", "seg_off", "coef", "mats", "tiles")      # device_tables: these five, in this order
 
     @property
     def n_segments(self) -> int:
         return int(self.seg_off[-1])
-
-    def device_tables(self, ctx):
-        """(in_off, seg_off, coef, mats, tiles) on ``ctx``'s device: views of the blob, uploaded on first use."""
-        import torch
-        hit = self._dev.get(ctx.device)
-        if hit is None:
-            d = ctx.tensor(self.blob)
-            cuts = np.cumsum([0, self.in_off.nbytes, self.seg_off.nbytes, self.coef.nbytes, self.mats.nbytes])
-            a, b, c, e, f = (int(v) for v in cuts)
-            hit = self._dev[ctx.device] = (d[a:b].view(torch.int64), d[b:c].view(torch.int64), d[c:e].view(torch.float64),
-                                           d[e:f].view(torch.float64), d[f:].view(torch.int32), d)
-        return hit[:5]
 
 
 def parse(loudness):
@@ -92,30 +72,16 @@ def plan(sr, lengths) -> LoudnessPlan:
     """goofer_host_loudness_plan for signals of ``lengths`` samples lying back to back.  Raises ValueError for what the library
     refuses: a rate that is not a whole number of Hz in [8000, 192000], a negative length, a signal of 2^31 samples or more."""
     lib = _lib.load()
-    lengths = np.ascontiguousarray(lengths, dtype=np.int64).reshape(-1)
-    if lengths.size and lengths.min() < 0:
-        raise ValueError("loudness.plan: a negative length")
-    if int(sr) != sr:
-        raise ValueError("loudness.plan: the sample rate is a whole number of Hz")
-    n = len(lengths)
-    in_off = np.zeros(n + 1, dtype=np.int64)
-    np.cumsum(lengths, out=in_off[1:])
+    in_off = SP.offsets("loudness.plan", lengths, sr)
+    n = len(in_off) - 1
     S, need = C.c_int(0), (C.c_int64 * 1)(0)
     coef, mats, seg_off = np.zeros(10), np.zeros((MATS, 4, 4)), np.zeros(n + 1, dtype=np.int64)
-    tiles = np.zeros((0, 2), dtype=np.int32)
-    rc = -1
-    for _ in range(2):
-        rc = lib.goofer_host_loudness_plan(int(sr), in_off.ctypes.data, n, C.byref(S), coef.ctypes.data, mats.ctypes.data,
-                                           seg_off.ctypes.data, tiles.ctypes.data if len(tiles) else None, len(tiles), need)
-        if rc != 1:
-            break
-        tiles = np.zeros((int(need[0]), 2), dtype=np.int32)
-    if rc != 0:
-        raise ValueError("goofer_host_loudness_plan refused %s Hz (%d): a rate in [%d, %d], signals shorter than 2^31 samples"
-                         % (sr, rc, MIN_SR, MAX_SR))
-    blob = np.concatenate([in_off.view(np.uint8), seg_off.view(np.uint8), coef.view(np.uint8), mats.view(np.uint8).ravel(),
-                           tiles.view(np.uint8).ravel()])
-    return LoudnessPlan(int(sr), n, S.value, coef, mats, in_off, seg_off, tiles, blob)
+    tiles, = SP.fit(lambda tiles: lib.goofer_host_loudness_plan(int(sr), in_off.ctypes.data, n, C.byref(S), coef.ctypes.data,
+                                                                mats.ctypes.data, seg_off.ctypes.data, *SP.cap(tiles), need),
+                    (np.zeros((0, 2), dtype=np.int32),), lambda: (np.zeros((int(need[0]), 2), dtype=np.int32),),
+                    lambda rc: "goofer_host_loudness_plan refused %s Hz (%d): a rate in [%d, %d], signals shorter than 2^31 samples"
+                               % (sr, rc, MIN_SR, MAX_SR))
+    return LoudnessPlan(int(sr), n, S.value, coef, mats, in_off, seg_off, tiles)
 
 
 def seg_samples(sr) -> int:

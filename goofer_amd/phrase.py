@@ -33,11 +33,12 @@ from __future__ import annotations
 import ctypes as C
 import math
 import sys
-from dataclasses import dataclass, field
+from dataclasses import dataclass
 
 import numpy as np
 
 from . import _lib
+from . import signal_plan as SP
 
 TILE = _lib.PHRASE_TILE
 MAX_TAKE = 1 << 24
@@ -131,9 +132,10 @@ class Entry:
 
 
 @dataclass
-class PhrasePlan:
+class PhrasePlan(SP.BlobPlan):
     """What goofer_phrase_mix takes for one phrase: ``notes`` (_lib.PHRASE_NOTE [n]), the cover table ``tile_off`` (int64
-    [tiles + 1]) / ``tile_notes`` (int32), ``total_out``; ``blob`` holds the three back to back for one upload."""
+    [tiles + 1]) / ``tile_notes`` (int32), ``total_out``; ``blob`` holds the three back to back for one upload, and a pad word
+    (no empty tensor on the device: an empty table still has an address)."""
     n: int
     total_out: int
     sr: int
@@ -141,18 +143,8 @@ class PhrasePlan:
     note_len: np.ndarray
     tile_off: np.ndarray
     tile_notes: np.ndarray
-    blob: np.ndarray
-    _dev: dict = field(default_factory=dict, repr=False)
-
-    def device_tables(self, ctx):
-        """(notes, tile_off, tile_notes) on ``ctx``'s device: views of the blob, uploaded on first use."""
-        import torch
-        hit = self._dev.get(ctx.device)
-        if hit is None:
-            d = ctx.tensor(self.blob)
-            a, b = self.notes.nbytes, self.notes.nbytes + self.tile_off.nbytes
-            hit = self._dev[ctx.device] = (d[:a], d[a:b].view(torch.int64), d[b:].view(torch.int32), d)
-        return hit[:3]
+    BLOB = ("notes", "tile_off", "tile_notes")                 # device_tables: these three (the records as bytes), in this order
+    PAD = 4
 
 
 def cover(notes: np.ndarray, note_len, total_out: int):
@@ -166,16 +158,11 @@ def cover(notes: np.ndarray, note_len, total_out: int):
     tiles = (int(total_out) + TILE - 1) // TILE if total_out > 0 else 0
     tile_off = np.zeros(tiles + 1, dtype=np.int64)
     need = C.c_int64(0)
-    tile_notes = np.zeros(max(len(notes), 1), dtype=np.int32)
-    for _ in range(2):
-        rc = lib.goofer_host_phrase_plan(notes.ctypes.data, note_len.ctypes.data, len(notes), int(total_out), tile_off.ctypes.data,
-                                         tile_notes.ctypes.data, tile_notes.size, C.byref(need))
-        if rc != 1:
-            break
-        tile_notes = np.zeros(int(need.value), dtype=np.int32)
-    if rc != 0:
-        raise ValueError("goofer_host_phrase_plan refused the phrase (%d): knots must be finite and non-decreasing from 0 to take, "
-                         "0 <= take <= 2^24, skip >= 0, lengths and total_out >= 0" % rc)
+    tile_notes, = SP.fit(lambda tile_notes: lib.goofer_host_phrase_plan(notes.ctypes.data, note_len.ctypes.data, len(notes), int(total_out),
+                                                                       tile_off.ctypes.data, *SP.cap(tile_notes), C.byref(need)),
+                         (np.zeros(max(len(notes), 1), dtype=np.int32),), lambda: (np.zeros(int(need.value), dtype=np.int32),),
+                         lambda rc: "goofer_host_phrase_plan refused the phrase (%d): knots must be finite and non-decreasing from 0 to "
+                                    "take, 0 <= take <= 2^24, skip >= 0, lengths and total_out >= 0" % rc)
     return tile_off, tile_notes[:int(need.value)]
 
 
@@ -185,9 +172,7 @@ def plan_records(notes, note_len, total_out: int, sr: int = 0) -> PhrasePlan:
     note_len = np.ascontiguousarray(note_len, dtype=np.int64)
     total_out = int(total_out)
     tile_off, tile_notes = cover(notes, note_len, total_out)
-    pad = np.zeros(1, dtype=np.int32)                      # (no empty tensor on the device: an empty table still has an address)
-    blob = np.concatenate([notes.view(np.uint8).ravel(), tile_off.view(np.uint8), tile_notes.view(np.uint8), pad.view(np.uint8)])
-    return PhrasePlan(len(notes), total_out, int(sr), notes, note_len, tile_off, tile_notes, blob)
+    return PhrasePlan(len(notes), total_out, int(sr), notes, note_len, tile_off, tile_notes)
 
 
 def plan_phrase(entries, note_lens, sr, starts=None, total_out=None) -> PhrasePlan:

@@ -9,17 +9,18 @@ from the library's host planner (``goofer_host_rate_plan``), the kernel is ``goo
 from __future__ import annotations
 
 import ctypes as C
-from dataclasses import dataclass, field
+from dataclasses import dataclass
 
 import numpy as np
 
 from . import _lib
+from . import signal_plan as SP
 
 MAX_PHASES = 1024                   # GOOFER_RATE_MAX_PHASES
 
 
 @dataclass
-class RatePlan:
+class RatePlan(SP.SignalPlan):
     """What goofer_rate_convert takes for one ragged batch: the geometry ``L``, ``M``, ``H``, the table ``taps`` (float32
     [L, 2H]), the signals' CSR ``in_off`` and that of their outputs ``out_off`` (int64 [n + 1]); ``blob`` holds the two offset
     arrays and the table back to back for one upload."""
@@ -32,50 +33,28 @@ class RatePlan:
     taps: np.ndarray
     in_off: np.ndarray
     out_off: np.ndarray
-    blob: np.ndarray
-    _dev: dict = field(default_factory=dict, repr=False)
+    BLOB = ("in_off", "out_off", "taps")                       # device_tables: these three, in this order
 
     @property
     def total_in(self) -> int:
-        return int(self.in_off[-1])
+        return self.total
 
     @property
     def total_out(self) -> int:
         return int(self.out_off[-1])
-
-    def device_tables(self, ctx):
-        """(in_off, out_off, taps) on ``ctx``'s device: views of the blob, uploaded on first use."""
-        import torch
-        hit = self._dev.get(ctx.device)
-        if hit is None:
-            d = ctx.tensor(self.blob)
-            a, b = self.in_off.nbytes, self.in_off.nbytes + self.out_off.nbytes
-            hit = self._dev[ctx.device] = (d[:a].view(torch.int64), d[a:b].view(torch.int64), d[b:].view(torch.float32), d)
-        return hit[:3]
 
 
 def plan(sr_in, sr_out, lengths) -> RatePlan:
     """goofer_host_rate_plan for signals of ``lengths`` samples lying back to back.  Raises ValueError for what the library
     refuses: a rate below 1, equal rates, more than 1024 phases on either side, a signal of 2^31 samples or more."""
     lib = _lib.load()
-    lengths = np.ascontiguousarray(lengths, dtype=np.int64).reshape(-1)
-    if lengths.size and lengths.min() < 0:
-        raise ValueError("rate.plan: a negative length")
-    n = len(lengths)
-    in_off = np.zeros(n + 1, dtype=np.int64)
-    np.cumsum(lengths, out=in_off[1:])
+    in_off = SP.offsets("rate.plan", lengths)
+    n = len(in_off) - 1
     out_off = np.zeros(n + 1, dtype=np.int64)
     L, M, H, need = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int64(0)
-    taps = np.zeros(0, dtype=np.float32)
-    for _ in range(2):
-        rc = lib.goofer_host_rate_plan(int(sr_in), int(sr_out), in_off.ctypes.data, n, C.byref(L), C.byref(M), C.byref(H),
-                                       taps.ctypes.data if taps.size else None, taps.size, C.byref(need), out_off.ctypes.data)
-        if rc != 1:
-            break
-        taps = np.zeros(int(need.value), dtype=np.float32)
-    if rc != 0:
-        raise ValueError("goofer_host_rate_plan refused %s -> %s Hz (%d): rates >= 1 and different, at most %d phases on either side "
-                         "(sr / gcd), signals shorter than 2^31 samples" % (sr_in, sr_out, rc, MAX_PHASES))
-    taps = taps.reshape(L.value, 2 * H.value)
-    blob = np.concatenate([in_off.view(np.uint8), out_off.view(np.uint8), taps.view(np.uint8).ravel()])
-    return RatePlan(int(sr_in), int(sr_out), n, L.value, M.value, H.value, taps, in_off, out_off, blob)
+    taps, = SP.fit(lambda taps: lib.goofer_host_rate_plan(int(sr_in), int(sr_out), in_off.ctypes.data, n, C.byref(L), C.byref(M),
+                                                          C.byref(H), *SP.cap(taps), C.byref(need), out_off.ctypes.data),
+                   (np.zeros(0, dtype=np.float32),), lambda: (np.zeros(int(need.value), dtype=np.float32),),
+                   lambda rc: "goofer_host_rate_plan refused %s -> %s Hz (%d): rates >= 1 and different, at most %d phases on either side "
+                              "(sr / gcd), signals shorter than 2^31 samples" % (sr_in, sr_out, rc, MAX_PHASES))
+    return RatePlan(int(sr_in), int(sr_out), n, L.value, M.value, H.value, taps.reshape(L.value, 2 * H.value), in_off, out_off)

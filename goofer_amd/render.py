@@ -18,6 +18,10 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import compress as CP
+from . import limit as LM
+from . import loudness as LD
+from . import rate as RT
 from . import sampler as S
 from .device import Context, check_noise_seed, check_phi_seed, default_context, default_params, pcg64_words, row_stride
 
@@ -424,16 +428,41 @@ class Renderer:
         lw = int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", "1")) or 1)
         self.plan_threads = 0 if lw <= 1 else max(1, min(8, (os.cpu_count() or 8) // lw))
 
-    def _out_rate(self, jobs, out_sr, who):
-        """The rate to convert to, or None where ``out_sr`` asks for none (None, or the notes' own rate)."""
-        if out_sr is None:
-            return None
+    def _finish_settings(self, jobs, who, out_sr, compress, loudness, limit):
+        """The arguments of the finishing chain, parsed once, as ``_finish`` takes them behind the lengths: (the notes' rate, the
+        rate to convert to or None where ``out_sr`` asks for none — None, or the notes' own rate —, compress, loudness, limit),
+        a stage that is not asked for None.  Raises ValueError, in ``who``'s name, where one is asked for and the notes do not
+        share one sample rate."""
+        chain = (None if compress is None else CP.parse(compress), None if loudness is None else LD.parse(loudness),
+                 None if limit is None else LM.parse(limit))
         rates = {int(src.sr) for src, _ in jobs}
-        if len(rates) != 1:
-            raise ValueError(f"{who}: out_sr converts notes that share one sample rate")
-        if int(out_sr) != out_sr or int(out_sr) < 1:
+        for what, asked in zip(("out_sr converts", "limit takes", "loudness takes", "compress takes"), (out_sr, limit, loudness, compress)):
+            if asked is not None and len(rates) != 1:
+                raise ValueError(f"{who}: {what} notes that share one sample rate")
+        if out_sr is not None and (int(out_sr) != out_sr or int(out_sr) < 1):
             raise ValueError(f"{who}: out_sr is a whole number of Hz")
-        return None if int(out_sr) in rates else int(out_sr)
+        return (jobs[0][0].sr, None if out_sr is None or int(out_sr) in rates else int(out_sr), *chain)
+
+    def _finish(self, x, d_off, lengths, sr, to_sr, compress, loudness, limit, true_peak_out=False):
+        """The finishing chain over the signals of ``lengths`` samples lying back to back in the device tensor ``x`` at ``sr``
+        (``d_off``: their CSR on the device, or None): convert to ``to_sr``, compress, loudness, limit, each with its parsed
+        settings; a stage whose setting is None launches nothing and allocates nothing.  Returns (the tensor, the signals'
+        lengths in it, the statistics as the stages return them, device tensors: ``max_reduction``; ``loud``, ``gain``;
+        ``peak_in``, ``min_gain``, and with ``true_peak_out`` behind a true-peak limiter ``true_peak_out``)."""
+        lengths, stats = np.asarray(lengths, dtype=np.int64), {}
+        if to_sr is not None:
+            plan = RT.plan(sr, to_sr, lengths)
+            x, lengths, sr = self.ctx.rate_convert(x, d_off, plan), np.diff(plan.out_off), to_sr
+        if compress is not None:
+            x, stats["max_reduction"], _ = self.ctx.compress(x, None, CP.plan(sr, lengths, compress))
+        if loudness is not None:
+            x, stats["loud"], stats["gain"], _ = self.ctx.loudness(x, None, LD.plan(sr, lengths), *loudness)
+        if limit is not None:
+            plan = LM.plan(sr, lengths, *limit)
+            x, stats["peak_in"], stats["min_gain"] = self.ctx.limit(x, None, plan)
+            if true_peak_out and plan.true_peak:
+                stats["true_peak_out"] = self.ctx.true_peak(x, None, plan)
+        return x, lengths, stats
 
     def render(self, jobs, seed: int = 0, phi_seeds=None, return_parts: bool = False, noise_seeds=None, out_sr=None, limit=None,
                loudness=None, compress=None):
@@ -461,38 +490,12 @@ class Renderer:
         front of the loudness stage."""
         if not jobs:
             return []
-        to_sr = self._out_rate(jobs, out_sr, "render")
-        if limit is not None and len({int(src.sr) for src, _ in jobs}) != 1:
-            raise ValueError("render: limit takes notes that share one sample rate")
-        if loudness is not None:
-            from . import loudness as LD
-            loudness = LD.parse(loudness)
-            if len({int(src.sr) for src, _ in jobs}) != 1:
-                raise ValueError("render: loudness takes notes that share one sample rate")
-        if compress is not None:
-            from . import compress as CP
-            compress = CP.parse(compress)
-            if len({int(src.sr) for src, _ in jobs}) != 1:
-                raise ValueError("render: compress takes notes that share one sample rate")
+        chain = self._finish_settings(jobs, "render", out_sr, compress, loudness, limit)
         prep = self.prepare(jobs, phi_seeds=phi_seeds, trim_rows=not return_parts, noise_seeds=noise_seeds)   # tests look at the whole assembled envelope
         out = self.run(prep, seed=seed, keep_stems=return_parts)
-        mix, offs = out["mix"], prep["sample_off"]
-        if to_sr is not None:
-            from . import rate as RT
-            plan = RT.plan(jobs[0][0].sr, to_sr, np.diff(np.asarray(offs, dtype=np.int64)))
-            mix, offs = self.ctx.rate_convert(mix, prep["offsets"]["d_s"], plan), plan.out_off
-        if compress is not None:
-            cplan = CP.plan(jobs[0][0].sr if to_sr is None else to_sr, np.diff(np.asarray(offs, dtype=np.int64)), compress)
-            mix = self.ctx.compress(mix, None, cplan)[0]
-        if loudness is not None:
-            dplan = LD.plan(jobs[0][0].sr if to_sr is None else to_sr, np.diff(np.asarray(offs, dtype=np.int64)))
-            mix = self.ctx.loudness(mix, None, dplan, *loudness)[0]
-        if limit is not None:
-            from . import limit as LM
-            lplan = LM.plan(jobs[0][0].sr if to_sr is None else to_sr, np.diff(np.asarray(offs, dtype=np.int64)), *LM.parse(limit))
-            mix = self.ctx.limit(mix, None, lplan)[0]
+        mix, lens, _ = self._finish(out["mix"], prep["offsets"]["d_s"], np.diff(np.asarray(prep["sample_off"], dtype=np.int64)), *chain)
         self.ctx.check()                                   # synchronises; raises if the device flagged a note
-        mix = mix.cpu().numpy()
+        mix, offs = mix.cpu().numpy(), np.concatenate([[0], np.cumsum(lens)])
         res = [mix[offs[i]:offs[i + 1]] for i in range(len(jobs))]
         if return_parts:
             parts = {"env": prep["env"], "f0": prep["f0"], "mask": prep["mask"], "env_off": prep["env_off"], "sample_off": prep["sample_off"],
@@ -526,52 +529,31 @@ class Renderer:
         from . import phrase as P
         if return_stats and limit is None and loudness is None and compress is None:
             raise ValueError("render_phrase: return_stats reports the limiter's and the loudness stage's statistics and needs limit or loudness")
-        if compress is not None:
-            from . import compress as CP
-            compress = CP.parse(compress)
-        if loudness is not None:
-            from . import loudness as LD
-            loudness = LD.parse(loudness)
         entries = [e if isinstance(e, P.Entry) else P.Entry.parse(e) for e in entries]
         if not jobs:
             raise ValueError("render_phrase: a phrase without a note has no sample rate")
         if len({src.sr for src, _ in jobs}) != 1:
             raise ValueError("render_phrase: the notes of a phrase share one sample rate")
-        to_sr = self._out_rate(jobs, out_sr, "render_phrase")
+        chain = self._finish_settings(jobs, "render_phrase", out_sr, compress, loudness, limit)
         prep = self.prepare(jobs, phi_seeds=phi_seeds, noise_seeds=noise_seeds)
         plan = P.plan_phrase(entries, np.diff(np.asarray(prep["sample_off"], dtype=np.int64)), jobs[0][0].sr)
         out = self.run(prep, seed=seed)
         track = self.ctx.phrase_mix(out["mix"], prep["offsets"]["d_s"], plan)
-        if to_sr is not None:
-            from . import rate as RT
-            track = self.ctx.rate_convert(track, None, RT.plan(jobs[0][0].sr, to_sr, [plan.total_out]))
-        stats = lstats = cstats = None
-        if compress is not None:
-            cplan = CP.plan(jobs[0][0].sr if to_sr is None else to_sr, [track.numel()], compress)
-            track, cstats, _ = self.ctx.compress(track, None, cplan)
-        if loudness is not None:
-            dplan = LD.plan(jobs[0][0].sr if to_sr is None else to_sr, [track.numel()])
-            track, *lstats = self.ctx.loudness(track, None, dplan, *loudness)
-        if limit is not None:
-            from . import limit as LM
-            lplan = LM.plan(jobs[0][0].sr if to_sr is None else to_sr, [track.numel()], *LM.parse(limit))
-            track, *stats = self.ctx.limit(track, None, lplan)
-            if return_stats and lplan.true_peak:
-                stats.append(self.ctx.true_peak(track, None, lplan))
+        track, _, st = self._finish(track, None, [plan.total_out], *chain, true_peak_out=return_stats)
         if pcm16:
             track = self.ctx.pcm16(track)
         self.ctx.check()                                   # synchronises; raises if the device flagged a note
         if return_stats:
             res = {}
-            if stats is not None:
-                res.update({"peak_in": float(stats[0].cpu()[0]), "min_gain": float(stats[1].cpu()[0])})
-                if len(stats) > 2:
-                    res.update({"true_peak_in": res["peak_in"], "true_peak_out": float(stats[2].cpu()[0])})
-            if lstats is not None:
-                loud = lstats[0].cpu()
-                res.update({"lufs_in": float(loud[0, 0]), "momentary_max": float(loud[0, 1]), "gain": float(lstats[1].cpu()[0])})
-            if cstats is not None:
-                res["max_reduction_db"] = float(cstats.cpu()[0])
+            if "peak_in" in st:
+                res.update({"peak_in": float(st["peak_in"].cpu()[0]), "min_gain": float(st["min_gain"].cpu()[0])})
+            if "true_peak_out" in st:
+                res.update({"true_peak_in": res["peak_in"], "true_peak_out": float(st["true_peak_out"].cpu()[0])})
+            if "loud" in st:
+                loud = st["loud"].cpu()
+                res.update({"lufs_in": float(loud[0, 0]), "momentary_max": float(loud[0, 1]), "gain": float(st["gain"].cpu()[0])})
+            if "max_reduction" in st:
+                res["max_reduction_db"] = float(st["max_reduction"].cpu()[0])
             return track.cpu().numpy(), res
         return track.cpu().numpy()
 
