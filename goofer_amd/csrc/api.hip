@@ -455,9 +455,11 @@ int goofer_check(goofer_ctx *ctx)
 }
 
 /* Cumulative counters of the handle (device words beside the overflow flag; the call synchronises the device):
- *   "pulse_scanned_notes"   notes whose onsets went through the parallel phase scan (k_pulse_onsets_par)
+ *   "pulse_scanned_notes"   notes whose onsets went through the parallel phase scan (k_pulse_note, or k_pulse_onsets_par with option pulse_fused = 0)
  *   "pulse_fallback_notes"  ... of which were walked sequentially afterwards (a sample within the error band of an integer
  *                           phase, a negative / non-finite increment, or option pulse_scan = 2)
+ *   "pulse_list_notes"      notes k_pulse_note placed from the onset list in global memory and not from its LDS ring (the walked
+ *                           ones, and those with more than 2048 onsets live at once)
  *   "mask_flag_segments"    note segments of k_mask_short's tiles (goofer_synth_batch / goofer_render_batch) answered from the
  *                           f0 kernel's tile flags alone
  *   "mask_staged_segments"  ... that staged their mask window in LDS (every segment when there are no flags; the large-radius
@@ -468,7 +470,7 @@ int goofer_check(goofer_ctx *ctx)
 int goofer_counter(goofer_ctx *ctx, const char *name, int64_t *value)
 {
     if (!ctx || !name || !value) return GOOFER_EINVAL;
-    int which = !strcmp(name, "pulse_fallback_notes") ? 1 : (!strcmp(name, "pulse_scanned_notes") ? 2 : -1);
+    int which = !strcmp(name, "pulse_fallback_notes") ? 1 : (!strcmp(name, "pulse_scanned_notes") ? 2 : (!strcmp(name, "pulse_list_notes") ? PULSE_LIST_COUNTER : -1));
     const int mask_c = !strcmp(name, "mask_flag_segments") ? 0 : (!strcmp(name, "mask_staged_segments") ? 1 : -1);
     static const char *const walk_names[4] = {"walk_run_noise", "walk_run_harm", "walk_run_ola3", "walk_run_ola1"};
     int walk = -1;
@@ -605,6 +607,7 @@ int goofer_set_option(goofer_ctx *ctx, const char *name, int value)
     if (!strcmp(name, "skip_zero")) { ctx->skip_zero = value != 0; return GOOFER_OK; }
     if (!strcmp(name, "td_blur")) { ctx->td_blur = value != 0; return GOOFER_OK; }
     if (!strcmp(name, "pulse_scan")) { ctx->pulse_scan = value < 0 ? 0 : (value > 2 ? 2 : value); return GOOFER_OK; }
+    if (!strcmp(name, "pulse_fused")) { ctx->pulse_fused = value != 0; return GOOFER_OK; }
     if (!strcmp(name, "sa_fast")) { ctx->sa_fast = value != 0; return GOOFER_OK; }
     if (!strcmp(name, "sa_table")) { ctx->sa_table = value != 0; return GOOFER_OK; }
     if (!strcmp(name, "legacy_wave")) { ctx->legacy_wave = value != 0; return GOOFER_OK; }

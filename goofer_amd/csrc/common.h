@@ -18,6 +18,7 @@
 #define MASK_COUNTER_SLOTS 64   // each spread over this many words a cache line apart (slot = workgroup & 63): thirteen thousand atomics on
 #define MASK_COUNTER_STRIDE 32  // ONE word took longer than the kernel; counter c, slot s: word MASK_COUNTERS + (2 * s + c) * MASK_COUNTER_STRIDE
 #define LEGACY_FLAG 3           // goofer_ctx::ovf_flag[LEGACY_FLAG]: sticky like [0]: 1 + index of a note whose legacy normal fill ran into its block bound
+#define PULSE_LIST_COUNTER 4    // goofer_ctx::ovf_flag[PULSE_LIST_COUNTER]: cumulative like [1], [2]: notes k_pulse_note placed from the onset list (goofer_counter "pulse_list_notes")
 #define OVF_WORDS (MASK_COUNTERS + 2 * MASK_COUNTER_SLOTS * MASK_COUNTER_STRIDE)
 #define PP_SPT 8                // k_pulse_place: consecutive samples per thread; a tile = one workgroup = 256 * PP_SPT samples
 #define PULSE_TILE_INTS(samples) (4 * (((samples) + 256 * PP_SPT - 1) / (256 * PP_SPT)) + 64)   // k_pulse_tiles' table: 4 ints per tile
@@ -174,6 +175,8 @@ struct goofer_ctx {
     int walk_run_used[4] = {0, 0, 0, 0};   // the run the last launch of k_noise_stems / k_harm_stem / k_irfft_ola3 / k_irfft_ola1 got (goofer_counter "walk_run_*")
     int pulse_scan = 1;           // 1: onsets from the parallel phase scan, the sequential walk only for the notes it cannot settle;
                                   // 0: the sequential walk kernel for every note; 2: the scan kernel walks every note (tests)
+    bool pulse_fused = true;      // with pulse_scan != 0: scan, periods and placement in one kernel, a workgroup per note (k_pulse_note; option
+                                  // "pulse_fused"); 0: k_pulse_onsets_par, k_onset_finish, k_pulse_tiles, k_pulse_place (A/B, the same bits)
     // per-context kernel state: hipFuncSetAttribute is per device, and a handle belongs to one device, so what was set /
     // queried is remembered here and never in process-wide statics
     struct kernel_state {

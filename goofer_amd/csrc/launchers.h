@@ -191,6 +191,8 @@ int launch_pulse_onsets(goofer_ctx *ctx, const float *f0, float f0_scale, const 
                         int32_t *onset_idx, int32_t *onset_cnt, int32_t *overflow, int64_t total_samples, int32_t *tiles, hipStream_t st);
 int launch_pulse_place(goofer_ctx *ctx, const onset_t *onsets, const int32_t *onset_cnt, const int64_t *sample_off, int n_notes,
                        int64_t total_samples, float *pulse, const int32_t *tiles, hipStream_t st);
+int launch_pulse_note(goofer_ctx *ctx, const float *f0, float f0_scale, const int64_t *sample_off, int n_notes, onset_t *onsets,
+                      int32_t *onset_idx, int32_t *onset_cnt, int32_t *overflow, float *pulse, hipStream_t st);
 int launch_pulse_train(goofer_ctx *ctx, const float *f0, float f0_scale, const int64_t *sample_off, int n_notes, int64_t total_samples,
                        float *pulse, double *inc, onset_t *onsets, int32_t *onset_idx, int32_t *onset_cnt, int32_t *overflow,
                        hipStream_t st);

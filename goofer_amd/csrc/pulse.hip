@@ -2,15 +2,18 @@
 //
 // The onset positions are a discontinuous function of a strictly sequential fp64 sum
 // (`total_phase += f0[i]/sr`, GOOFER.py:491-493): re-associating it moves onsets by a sample
-// (SURVEY.md §7.3-1).  So the work is split three ways:
-//   k_pulse_onsets_par   a workgroup per note takes the onset samples from a parallel scan of the increments f0[i] / sr
-//                   wherever that provably gives the walk's integers; a note it cannot settle is walked in order by one
-//                   WAVE (onset_walk: nothing but the dependent fp64 adds, the onsets extracted from the partial sums
-//                   chunk by chunk, in parallel); k_pulse_onsets_scan walks every note (pulse_scan = 0).  k_onset_finish
-//                   completes the onset list (sample, T0, period, running max of sample+T0)
-//   k_pulse_place   fully parallel gather: every output sample sums, in ascending onset order, the
-//                   LF shapes that cover it — no atomics, same fp32 accumulation order as the
-//                   reference's `pulse[j] += cache[k]`
+// (SURVEY.md §7.3-1).  So the onsets are kept apart from everything that is parallel:
+//   onsets          a workgroup per note takes the onset samples from a parallel scan of the increments f0[i] / sr wherever that
+//                   provably gives the walk's integers; a note it cannot settle is walked in order by one WAVE (onset_walk:
+//                   nothing but the dependent fp64 adds, the onsets extracted from the partial sums chunk by chunk, in parallel)
+//   periods         per onset: T0, the period, the running max of sample + T0 (which bounds the placement's look-back)
+//   placement       fully parallel gather: every output sample sums, in ascending onset order, the LF shapes that cover it — no
+//                   atomics, same fp32 accumulation order as the reference's `pulse[j] += cache[k]`
+// k_pulse_note (pulse_scan != 0, option pulse_fused: the default) does all three in one pass per note: each round of the scan
+// leaves its onsets and their periods in an LDS ring and places its 2048 samples from there, the table gathers in flight under
+// the next round's scan.  The chain it replaces stays as the A/B reference (pulse_fused = 0) and behind the sequential walk for
+// every note (pulse_scan = 0, k_pulse_onsets_scan): k_pulse_onsets_par (the scan alone), k_onset_finish (the onset records in
+// global memory), k_pulse_tiles (which onsets can touch which 2048-sample tile), k_pulse_place.
 // Shapes come from a table of every length T0 = 3 .. 8192 (k_pulse_shape_table), evaluated in fp64 (numba's typing) and normalised by a per-T0 peak table.
 #include "common.h"
 #include "launchers.h"
@@ -310,20 +313,22 @@ __device__ __forceinline__ int32_t wave_scan_max(int32_t x)
 // number k + 1 lies at the first sample whose R reaches k + 1, and its slot is k.  m[k] = the running max of the floors of this
 // lane's samples up to its k-th, run = m[SPL - 1], upto = wave_scan_max(run) (taken by the caller: the scan kernel needs it in
 // front of a barrier), cnt = R in front of the wave's first sample, i0 = the sample index of this lane's first sample.  Negative
-// increments and several onsets at one sample need no special case.  Returns R behind the wave's last sample.
+// increments and several onsets at one sample need no special case.  rec(slot, k): the caller's own record of an onset that has a
+// slot, at this lane's k-th sample.  Returns R behind the wave's last sample.
+template <typename Rec>
 __device__ __forceinline__ int32_t emit_onsets(const int32_t (&m)[SPL], int32_t run, int32_t upto, int32_t cnt, int32_t cap,
-                                               int32_t *__restrict__ out, int32_t i0)
+                                               int32_t *__restrict__ out, int32_t i0, Rec &&rec)
 {
     int32_t before = __shfl_up(upto, 1);
     if ((threadIdx.x & 63) == 0) before = 0;
     const int32_t start = max(cnt, before);                   // R in front of this lane's first sample
-    if (run > start) {
-        int32_t at = start, prev = start;                     // the slot of onset number k + 1 is k
+    for (int32_t at = start; at < run; ++at) {                // the slot of onset number k + 1 is k
+        int k = 0;                                            // m does not decrease: the first sample whose running max passes `at`
 #pragma unroll
-        for (int k = 0; k < SPL; ++k) {
-            const int32_t c = max(prev, m[k]);
-            for (; prev < c; ++prev, ++at)
-                if (at < cap) out[at] = i0 + k;
+        for (int j = 0; j < SPL - 1; ++j) k += m[j] <= at ? 1 : 0;
+        if (at < cap) {
+            out[at] = i0 + k;
+            rec(at, k);
         }
     }
     return max(cnt, __builtin_amdgcn_readlane(upto, WAVE - 1));
@@ -369,7 +374,7 @@ __device__ __forceinline__ void onset_walk(double *tiles, int group, const float
             run = max(run, f);
             m[k] = run;
         }
-        cnt = emit_onsets(m, run, wave_scan_max(run), cnt, cap, out, c0 + lane * SPL);
+        cnt = emit_onsets(m, run, wave_scan_max(run), cnt, cap, out, c0 + lane * SPL, [](int32_t, int) {});
     };
 
     fetch_chunk(r, a, 0, n, lane);
@@ -539,7 +544,7 @@ __global__ __launch_bounds__(256) void k_pulse_onsets_par(const float *__restric
             bad |= s_bad[par][q];
         }
         if (bad) { unsure = true; break; }
-        emit_onsets(m, run, upto, cnt_w, cap, out, (int32_t)w0 + lane * SPL);
+        emit_onsets(m, run, upto, cnt_w, cap, out, (int32_t)w0 + lane * SPL, [](int32_t, int) {});
         cnt = cnt_all;
         carry = total;
     }
@@ -566,10 +571,24 @@ __device__ __forceinline__ int32_t strip_end_max(int32_t e, int32_t &carry)
     return m;
 }
 
-// One wave per note, lanes over onsets: T = 1/max(last_valid_f0, 1e-6) with last_valid_f0 the most
-// recent f0 > 1e-6 at or before the onset sample (160 Hz before any), T0 = clip(round_half_even(sr*T),
-// 3, 8192) (GOOFER.py:488-499), and end_max = running max of (sample + T0) in onset order (the bound
-// k_pulse_place uses to stop its look-back).
+// The period of the onset at sample i of the note f: T = 1/max(last_valid_f0, 1e-6) with last_valid_f0 the most recent
+// f0 > 1e-6 at or before the onset sample (160 Hz before any), and its length T0 = clip(round_half_even(sr*T), 3, 8192)
+// (GOOFER.py:488-499).  own = f[i], which the caller may hold already.
+__device__ __forceinline__ int32_t onset_period(const float *__restrict__ f, int64_t i, float own, double sr, double &T)
+{
+    double last = (double)own;
+    if (!(own > 1e-6f)) {
+        int64_t b = i - 1;
+        while (b >= 0 && !(f[b] > 1e-6f)) --b;
+        last = b >= 0 ? (double)f[b] : 160.0;
+    }
+    T = 1.0 / fmax(last, 1e-6);
+    const long t0 = (long)rint(sr * T);                       // round-half-even, like Python round()
+    return (int32_t)(t0 < 3 ? 3 : (t0 > 8192 ? 8192 : t0));
+}
+
+// One wave per note, lanes over onsets: T and T0 (onset_period), and end_max = running max of (sample + T0) in onset order
+// (the bound the placement uses to stop its look-back).
 __global__ __launch_bounds__(64) void k_onset_finish(const float *__restrict__ f0, const int64_t *__restrict__ sample_off,
                                                      int n_notes, double sr, const int32_t *__restrict__ onset_idx,
                                                      const int32_t *__restrict__ onset_cnt, onset_t *__restrict__ onsets)
@@ -586,12 +605,7 @@ __global__ __launch_bounds__(64) void k_onset_finish(const float *__restrict__ f
         double T = 0.0;
         if (k < cnt) {
             i = onset_idx[obase + k];
-            int64_t b = i;
-            while (b >= 0 && !(f[b] > 1e-6f)) --b;
-            const double last = b >= 0 ? (double)f[b] : 160.0;
-            T = 1.0 / fmax(last, 1e-6);
-            long t0 = (long)rint(sr * T);                    // round-half-even, like Python round()
-            T0 = (int32_t)(t0 < 3 ? 3 : (t0 > 8192 ? 8192 : t0));
+            T0 = onset_period(f, i, f[i], sr, T);
             e = i + T0;
         }
         const int32_t m = strip_end_max(e, carry);
@@ -622,17 +636,22 @@ __device__ __forceinline__ float pulse_value(const onset_t &o, int j, const floa
 // The onsets of `list` (count of them, ascending; global memory or LDS) that can cover samples j_first .. j_last of the note:
 // last = the last onset starting at or before j_last, first = back from it while the running end_max of the onset in front
 // passes j_first.  false: none starts that early.  Summing first .. last in ascending order is the reference's accumulation order.
-__device__ __forceinline__ bool covering_onsets(const onset_t *list, int count, int32_t j_last, int32_t j_first, int &first, int &last)
+template <typename Start, typename EndMax>
+__device__ __forceinline__ bool covering_range(int count, int32_t j_last, int32_t j_first, int &first, int &last, Start start_of, EndMax end_max_of)
 {
     int lo = -1, hi = count;
     while (hi - lo > 1) {
         const int mid = (lo + hi) >> 1;
-        if (list[mid].i <= j_last) lo = mid; else hi = mid;
+        if (start_of(mid) <= j_last) lo = mid; else hi = mid;
     }
     if (lo < 0) return false;
     last = first = lo;
-    while (first > 0 && list[first - 1].end_max > j_first) --first;
+    while (first > 0 && end_max_of(first - 1) > j_first) --first;
     return true;
+}
+__device__ __forceinline__ bool covering_onsets(const onset_t *list, int count, int32_t j_last, int32_t j_first, int &first, int &last)
+{
+    return covering_range(count, j_last, j_first, first, last, [&](int k) { return list[k].i; }, [&](int k) { return list[k].end_max; });
 }
 
 // Which onsets can touch which tile, once per tile instead of once per workgroup through two rounds of note search, a count over
@@ -743,6 +762,323 @@ __global__ __launch_bounds__(256) void k_pulse_place(const onset_t *__restrict__
     }
 }
 
+// ---- scan, periods and placement in one pass per note -------------------------------------------
+// k_pulse_note is k_pulse_onsets_par with the rest of the chain behind each round's second barrier: the loop, the summation
+// tree, PAR_TOL, the band test, `force` and the `unsure` decision are that kernel's (the proof above it holds word for word).
+// What the four-kernel chain rediscovers by searching, the scan holds in registers: m[k] is the number of onsets at or before
+// a sample, so the last onset that starts at or before the lane's last sample is onset number m[SPL - 1] - 1; the lane that
+// emits an onset holds the f0 sample its period is made from; and a lane's SPL samples are the PP_SPT samples a placement
+// thread owns.  Per round:
+//   ring      the emitting lane writes {sample, T0} of onset number k (onset_period) into slot k & (PN_RING - 1) of an LDS ring,
+//             beside onset_idx[k] as before;
+//   end_max   the inclusive running max of sample + T0 over the round's new slots, joined with the rounds before.  Every wave
+//             computes it for itself and stores it (the same values to the same slots): a wave reads only what its own stores,
+//             complete in issue order, or another wave's identical ones have left there, so no barrier follows;
+//   place     every thread sums its SPL samples over the onsets first .. last, first = back from last while the end_max of the
+//             onset in front passes the thread's first sample — k_pulse_place's inner loop, ascending onsets (the reference's
+//             accumulation order), a sample no pulse covers +0.0f.
+// The ring holds the last PN_RING onsets that have a slot.  Before a round places, the workgroup checks (uniformly, from LDS and
+// uniform values) that every onset the round may reach is among them: hi - live <= PN_RING, hi = the onsets up to the round's
+// end, live = the first onset whose end_max passes the round's first sample (end_max does not decrease; live is advanced only
+// when the count alone does not settle it).  The look-back never goes below hi - PN_RING: those onsets are dead by that check.
+//
+// List mode (pulse_list_mode, the whole workgroup, behind the scan loop) serves the notes the ring cannot: those the scan could
+// not settle or `force` (wave 0 has walked them with onset_walk), and a ring that overflowed.  It builds the note's onset_t list
+// in global memory as k_onset_finish does and places every sample of the note from it, covering_onsets per thread and
+// k_pulse_place's sums: the same sums in the same order, so the same bits, also over rounds the ring has placed.
+#define PN_RING 2048
+#define PN_DEFER 2             // pulses per thread whose sum waits for the next round (k_pulse_note)
+static_assert((PN_RING & (PN_RING - 1)) == 0, "ring slots are masked");
+typedef float4 __attribute__((aligned(4))) float4_u;          // a note starts at any sample of the batch: 4-byte aligned 16-byte stores
+
+// The placement of a thread's SPL consecutive samples from sample j of a note, in k_pulse_place's steps: the table values of one
+// pulse of length T0 that starts d0 samples in front of j (index clamped into the pulse, so that the loads are in flight together),
+// the range test as a select, `acc += ...` (the caller: in ascending onset order), the stores cut at the note's end
+__device__ __forceinline__ void pulse_gather(float (&t)[SPL], const float *__restrict__ tab, int32_t d0, int32_t T0)
+{
+    const float *__restrict__ row = tab + pulse_tab_row(T0);
+#pragma unroll
+    for (int e = 0; e < SPL; ++e) {
+        const int d = d0 + e;
+        t[e] = row[d < 0 ? 0 : (d >= T0 ? T0 - 1 : d)];
+    }
+}
+__device__ __forceinline__ void pulse_add(float (&acc)[SPL], const float (&t)[SPL], int32_t d0, int32_t T0)
+{
+#pragma unroll
+    for (int e = 0; e < SPL; ++e) {
+        const int d = d0 + e;
+        acc[e] += (d < 0 || d >= T0) ? 0.f : t[e];
+    }
+}
+__device__ __forceinline__ void pulse_store(const float (&acc)[SPL], float *__restrict__ y, int32_t j, int64_t n)
+{
+    if (j + SPL <= n) {
+#pragma unroll
+        for (int e = 0; e < SPL; e += 4)
+            *reinterpret_cast<float4_u *>(y + j + e) = make_float4(acc[e], acc[e + 1], acc[e + 2], acc[e + 3]);
+    } else {
+        for (int e = 0; e < SPL; ++e)
+            if (j + e < n) y[j + e] = acc[e];
+    }
+}
+
+__device__ __forceinline__ void pulse_list_mode(const float *__restrict__ f, int64_t n, double sr, const int32_t *oidx, int cnt,
+                                                onset_t *ol, const float *__restrict__ tab, float *__restrict__ y, int32_t *r_i,
+                                                int32_t *r_T0, int32_t *r_end)
+{
+    // a list that fits the ring's arrays (slot k = onset k) is searched there: a walked note is alone on its CU by the time it gets
+    // here, and every round of its placement is a chain of dependent reads
+    const bool staged = cnt <= PN_RING;
+    __shared__ int32_t s_e[2][4];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    int32_t carry = 0;                                        // end_max behind the strips before (uniform)
+    int par = 0;
+    for (int k0 = 0; k0 < cnt; k0 += 256, par ^= 1) {         // strips of 256 onsets: a barrier each, s_e in turns
+        const int k = k0 + (int)threadIdx.x;
+        int32_t i = 0, T0 = 0, e = 0;
+        double T = 0.0;
+        if (k < cnt) {
+            i = oidx[k];
+            T0 = onset_period(f, i, f[i], sr, T);
+            e = i + T0;
+        }
+        const int32_t ms = wave_scan_max(e);
+        if (lane == WAVE - 1) s_e[par][wv] = ms;
+        __syncthreads();
+        int32_t pre = carry;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int32_t t = s_e[par][q];
+            pre = q < wv ? max(pre, t) : pre;
+            carry = max(carry, t);
+        }
+        if (k < cnt) {
+            onset_t o;
+            o.i = i; o.T0 = T0; o.end_max = max(ms, pre); o.pad = 0; o.T = T;
+            ol[k] = o;
+            if (staged) { r_i[k] = i; r_T0[k] = T0; r_end[k] = o.end_max; }
+        }
+    }
+    __threadfence_block();
+    __syncthreads();
+    // a thread owns SPL consecutive samples of every round, as in the scan: they share their covering onsets, so the search of
+    // the list is paid once per SPL outputs (a walked note of three seconds is 67 rounds of it, alone on its CU)
+    for (int64_t c0 = (int64_t)threadIdx.x * SPL; c0 < n; c0 += PAR_ROUND) {
+        const int32_t j = (int32_t)c0;
+        const int live = n - c0 < SPL ? (int)(n - c0) : SPL;
+        float acc[SPL], t[SPL];
+#pragma unroll
+        for (int e = 0; e < SPL; ++e) acc[e] = 0.f;
+        int first, last;
+        if (staged ? covering_range(cnt, j + live - 1, j, first, last, [&](int k) { return r_i[k]; }, [&](int k) { return r_end[k]; })
+                   : covering_onsets(ol, cnt, j + live - 1, j, first, last)) {
+            for (int k = first; k <= last; ++k) {             // ascending onsets: the reference's order
+                const int32_t T0 = staged ? r_T0[k] : ol[k].T0, d0 = j - (staged ? r_i[k] : ol[k].i);
+                pulse_gather(t, tab, d0, T0);
+                pulse_add(acc, t, d0, T0);
+            }
+        }
+        pulse_store(acc, y, j, n);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_pulse_note(const float *__restrict__ f0, double sr, const int64_t *__restrict__ sample_off,
+                                                    int n_notes, int32_t *__restrict__ onset_idx, int32_t *__restrict__ onset_cnt,
+                                                    onset_t *__restrict__ onsets, const float *__restrict__ tab, float *__restrict__ pulse,
+                                                    int32_t *__restrict__ overflow, int32_t *__restrict__ stats, int force)
+{
+    extern __shared__ __align__(16) unsigned char smem[];     // the walk's tiles (one wave: 2 x OC doubles)
+    __shared__ double s_tot[2][4];
+    __shared__ int32_t s_top[2][4], s_bad[2][4];
+    __shared__ int32_t r_i[PN_RING], r_T0[PN_RING], r_end[PN_RING];   // the ring: onset sample, length, running max of their sum
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int note = blockIdx.x;
+    const int64_t base = sample_off[note];
+    const int64_t n = sample_off[note + 1] - base;
+    const int32_t cap = pulse_slot_cap(sample_off, note);
+    const float *__restrict__ a = f0 + base;
+    float *__restrict__ y = pulse + base;
+    const double rsr = 1.0 / sr;
+    int32_t *__restrict__ out = onset_idx + pulse_slot_base(base, note);
+    double carry = 0.0;                                       // the scan's phase in front of the round (uniform)
+    int32_t cnt = 0;                                          // onsets in front of the round (uniform)
+    int32_t emax = 0;                                         // end_max of the last onset in the ring (uniform)
+    int32_t live = 0;                                         // no onset in front of this one reaches the round (uniform; see above)
+    bool unsure = force != 0;
+    bool listm = false;                                       // the ring has overflowed (uniform)
+
+    // The round's f0 samples stay in the walk's tiles (free during the scan) for the periods of the round's onsets, past the
+    // prefetch of the next round: a lane reads back only what it wrote itself, indexed by the onset's sample, so nothing is awaited
+    float *kept = reinterpret_cast<float *>(smem) + threadIdx.x * SPL;
+    static_assert(256 * SPL * sizeof(float) <= 2 * OC * sizeof(double), "the kept f0 samples fit the walk's tiles");
+
+    // A thread whose samples up to PN_DEFER pulses cover (nearly all) sums and stores them one round late: the table values
+    // are gathered at the end of the round, from anywhere in a 134 MB table, and that round trip would otherwise stand in every
+    // round's chain.  pend: -1 nothing is pending, else the number of pulses of the samples from pj0
+    int pend = -1;
+    int32_t pj0 = 0, pd0[PN_DEFER], pT0[PN_DEFER];
+    float tv[PN_DEFER][SPL];
+    auto finish = [&]() {
+        if (pend < 0) return;
+        float acc[SPL];
+#pragma unroll
+        for (int e = 0; e < SPL; ++e) acc[e] = 0.f;
+#pragma unroll
+        for (int q = 0; q < PN_DEFER; ++q)
+            if (q < pend) pulse_add(acc, tv[q], pd0[q], pT0[q]);
+        pulse_store(acc, y, pj0, n);
+        pend = -1;
+    };
+
+    float r[SPL];                                             // (fetched from the first sample of this wave's part of a round)
+    if (!unsure) fetch_chunk(r, a, (int64_t)wv * OC, n, lane);
+    int par = 0;
+    for (int64_t c0 = 0; c0 < n && !unsure; c0 += PAR_ROUND, par ^= 1) {
+        const int64_t w0 = c0 + (int64_t)wv * OC;
+        double l[SPL];
+        bool nb = false;
+#pragma unroll
+        for (int k = 0; k < SPL; ++k) {
+            const double inc = inc_of(r[k], sr, rsr);
+            nb |= !(inc >= 0.0);                              // negative or NaN
+            l[k] = k ? l[k - 1] + inc : inc;
+            kept[k] = r[k];
+        }
+        if (c0 + PAR_ROUND < n) fetch_chunk(r, a, w0 + PAR_ROUND, n, lane);
+        const double incl = wave_scan_add_f64(l[SPL - 1]);
+        double excl = __shfl_up(incl, 1, WAVE);
+        excl = lane == 0 ? 0.0 : excl;
+        if (lane == WAVE - 1) s_tot[par][wv] = incl;
+        __syncthreads();
+        double before_w = carry, total = carry;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const double t = s_tot[par][q];
+            total = total + t;
+            before_w = q < wv ? total : before_w;
+        }
+        const double p0 = before_w + excl;
+        const double tolf = PAR_TOL * (double)(c0 + PAR_ROUND);
+        const int64_t left = n - w0;
+        const int valid = left >= OC ? OC : (left > 0 ? (int)left : 0);
+        int32_t m[SPL];
+        int32_t run = 0;
+#pragma unroll
+        for (int k = 0; k < SPL; ++k) {
+            const int i = lane * SPL + k;
+            const double S = p0 + l[k];
+            const double d = S - rint(S), tol = S * tolf;
+            nb |= (fabs(d) <= tol) && (tol > 0.0);
+            nb |= !(S < 1073741824.0);                        // (also inf / NaN)
+            const int32_t f = i < valid ? (int32_t)S : 0;     // S >= 0: trunc == floor
+            run = max(run, f);
+            m[k] = run;
+        }
+        const int32_t upto = wave_scan_max(run);
+        const bool wave_bad = __any(nb);
+        if (lane == WAVE - 1) { s_top[par][wv] = upto; s_bad[par][wv] = wave_bad ? 1 : 0; }
+        __syncthreads();
+        int32_t cnt_w = cnt, cnt_all = cnt;                   // onsets in front of this wave's samples / behind the round
+        int bad = 0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            cnt_all = max(cnt_all, s_top[par][q]);
+            cnt_w = q < wv ? cnt_all : cnt_w;
+            bad |= s_bad[par][q];
+        }
+        if (bad) { unsure = true; break; }
+        const int32_t lo = min(cnt, cap), hi = min(cnt_all, cap);   // the round's new onsets that have a slot: lo .. hi - 1
+        if (!listm) {
+            // will the onsets this round may reach still be in the ring once its new ones are?  (the slots live .. lo - 1 are
+            // intact: the rounds before passed this check)
+            while (hi - live > PN_RING && live < lo) {
+                const int32_t k = live + lane;
+                const bool dead = k < lo && r_end[k & (PN_RING - 1)] <= (int32_t)c0;
+                const unsigned long long alive = ~__ballot(dead);
+                const int nd = alive ? __builtin_ctzll(alive) : WAVE;
+                live += nd;
+                if (nd < WAVE) break;
+            }
+            listm = hi - live > PN_RING;
+        }
+        const int32_t j0 = (int32_t)w0 + lane * SPL;          // this lane's first sample
+        emit_onsets(m, run, upto, cnt_w, cap, out, j0, [&](int32_t at, int k) {
+            const float own = kept[k];
+            double T;
+            r_i[at & (PN_RING - 1)] = j0 + k;
+            r_T0[at & (PN_RING - 1)] = onset_period(a, j0 + k, own, sr, T);
+        });
+        int32_t before = __shfl_up(upto, 1);
+        before = lane == 0 ? 0 : before;
+        const int32_t R = max(max(cnt_w, before), run);       // onsets at or before this lane's last sample
+        cnt = cnt_all;
+        carry = total;
+        finish();                                             // the round before: its table values have had this round's scan to arrive
+        if (listm) continue;                                  // (the scan goes on: the list wants every onset)
+        __syncthreads();
+        for (int32_t k0 = lo; k0 < hi; k0 += WAVE) {
+            const int32_t k = k0 + lane, sl = k & (PN_RING - 1);
+            const int32_t e = k < hi ? r_i[sl] + r_T0[sl] : 0;
+            const int32_t em = strip_end_max(e, emax);
+            if (k < hi) r_end[sl] = em;
+        }
+        wave_lds_sync();
+        if (j0 < n) {
+            const int32_t last = min(R, cap) - 1, floor_k = max(hi - PN_RING, 0);
+            int32_t first = last + 1;                         // (no onset: an empty sum)
+            if (last >= floor_k) {
+                first = last;
+                while (first > floor_k && r_end[(first - 1) & (PN_RING - 1)] > j0) --first;
+            }
+            if (last - first < PN_DEFER) {
+                // the usual one or two pulses (or none): their table values are fetched here and summed behind the next round's scan
+                pend = last - first + 1;
+                pj0 = j0;
+#pragma unroll
+                for (int q = 0; q < PN_DEFER; ++q) {
+                    const int32_t sl = (first + (q < pend ? q : 0)) & (PN_RING - 1);
+                    if (q < pend) {
+                        pT0[q] = r_T0[sl];
+                        pd0[q] = j0 - r_i[sl];
+                        pulse_gather(tv[q], tab, pd0[q], pT0[q]);
+                    }
+                }
+                if (pend == 0) finish();                      // nothing to wait for: +0.0f now
+            } else {
+                float acc[SPL], t[SPL];
+#pragma unroll
+                for (int e = 0; e < SPL; ++e) acc[e] = 0.f;
+                for (int32_t k = first; k <= last; ++k) {     // ascending onsets: the reference's order
+                    const int32_t T0 = r_T0[k & (PN_RING - 1)], d0 = j0 - r_i[k & (PN_RING - 1)];
+                    pulse_gather(t, tab, d0, T0);
+                    pulse_add(acc, t, d0, T0);
+                }
+                pulse_store(acc, y, j0, n);
+            }
+        }
+    }
+    finish();
+    if (threadIdx.x == 0 && stats) {
+        atomicAdd(stats + 2, 1);
+        if (unsure) atomicAdd(stats + 1, 1);
+        if (unsure || listm) atomicAdd(stats + PULSE_LIST_COUNTER, 1);
+    }
+    if (unsure) {
+        if (wv == 0) {
+            onset_walk(reinterpret_cast<double *>(smem), note, f0, sr, sample_off, n_notes, onset_idx, onset_cnt, overflow);
+            __builtin_amdgcn_s_setprio(0);
+        }
+    } else if (threadIdx.x == 0) {
+        onset_cnt[note] = cnt < cap ? cnt : cap;
+        if (cnt > cap) atomicMax(overflow, note + 1);          // reported at the next synchronising call (goofer_check)
+    }
+    if (!unsure && !listm) return;
+    __threadfence_block();                                    // the onset list and its count, for every wave
+    __syncthreads();
+    pulse_list_mode(a, n, sr, out, onset_cnt[note], onsets + pulse_slot_base(base, note), tab, y, r_i, r_T0, r_end);
+}
+
 // The placement's tile table (4 ints per tile of 256 * PP_SPT samples, PULSE_TILE_INTS of them) is read with 16-byte scalar
 // loads.  Every caller takes it from an arena over a handle-owned block (goofer_pulse_train: the head of its scratch; the batch
 // driver: a piece of its own), i.e. 256-byte aligned; anything else is a bug in the caller, not a case to serve.
@@ -799,12 +1135,29 @@ int launch_pulse_place(goofer_ctx *ctx, const onset_t *onsets, const int32_t *on
     return GOOFER_OK;
 }
 
+// scan, periods and placement of every note in one launch (pulse_scan != 0, option pulse_fused): what launch_pulse_onsets +
+// launch_pulse_place make, without the tile table; `onsets` is written only for the notes that take list mode
+int launch_pulse_note(goofer_ctx *ctx, const float *f0, float f0_scale, const int64_t *sample_off, int n_notes, onset_t *onsets,
+                      int32_t *onset_idx, int32_t *onset_cnt, int32_t *overflow, float *pulse, hipStream_t st)
+{
+    if (n_notes <= 0) return GOOFER_OK;
+    if (f0_scale != 1.0f) return goofer_fail(ctx, GOOFER_EINVAL, "pulse onsets expect pre-scaled f0");
+    if (ctx->pulse_scan == 0) return goofer_fail(ctx, GOOFER_EINVAL, "k_pulse_note is the scan's kernel (pulse_scan != 0)");
+    // `overflow` is the handle's block of sticky words: [0] overflow, [1] notes walked, [2] notes scanned, [PULSE_LIST_COUNTER]
+    hipLaunchKernelGGL(k_pulse_note, dim3(n_notes), dim3(256), 2 * OC * sizeof(double), st, f0, (double)ctx->plan.sr, sample_off, n_notes,
+                       onset_idx, onset_cnt, onsets, ctx->plan.pulse_shape, pulse, overflow, overflow, ctx->pulse_scan == 2 ? 1 : 0);
+    LAUNCH_CHECK(ctx);
+    return GOOFER_OK;
+}
+
 int launch_pulse_train(goofer_ctx *ctx, const float *f0, float f0_scale, const int64_t *sample_off, int n_notes,
                        int64_t total_samples, float *pulse, double *inc, onset_t *onsets, int32_t *onset_idx, int32_t *onset_cnt,
                        int32_t *overflow, hipStream_t st)
 {
     if (total_samples <= 0 || n_notes <= 0) return GOOFER_OK;
     int rc;
+    if (ctx->pulse_scan != 0 && ctx->pulse_fused)
+        return launch_pulse_note(ctx, f0, f0_scale, sample_off, n_notes, onsets, onset_idx, onset_cnt, overflow, pulse, st);
     // the walk divides f0 by sr itself: the increments array (8 bytes per sample) is free and holds the placement's tile table
     int32_t *tiles = reinterpret_cast<int32_t *>(inc);
     if ((rc = launch_pulse_onsets(ctx, f0, f0_scale, sample_off, n_notes, onsets, onset_idx, onset_cnt, overflow, total_samples, tiles, st))) return rc;

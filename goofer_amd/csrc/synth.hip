@@ -555,11 +555,16 @@ static int synth_batch(goofer_ctx *ctx, const goofer_batch *b, render_link &link
     if ((rc = clk.pulse(0, pst))) return rc;
     if ((rc = clk.at(4))) return rc;
     if ((rc = clk.pulse(1, pst))) return rc;
-    if ((rc = launch_pulse_onsets(ctx, s.f0s, 1.0f, b->sample_off, n, s.onsets, s.onset_idx, s.onset_cnt, ctx->ovf_flag, N, s.pulse_tiles, pst)))
+    // stage 4 holds the fused kernel (scan, periods and placement per note) and stage 5 is empty, or the four kernels share them
+    const bool pulse_fused = ctx->pulse_scan != 0 && ctx->pulse_fused;
+    if (pulse_fused) {
+        if ((rc = launch_pulse_note(ctx, s.f0s, 1.0f, b->sample_off, n, s.onsets, s.onset_idx, s.onset_cnt, ctx->ovf_flag, s.pulse, pst))) return rc;
+    } else if ((rc = launch_pulse_onsets(ctx, s.f0s, 1.0f, b->sample_off, n, s.onsets, s.onset_idx, s.onset_cnt, ctx->ovf_flag, N, s.pulse_tiles, pst))) {
         return rc;
+    }
     if ((rc = clk.at(5))) return rc;
     if ((rc = clk.pulse(2, pst))) return rc;
-    if ((rc = launch_pulse_place(ctx, s.onsets, s.onset_cnt, b->sample_off, n, N, s.pulse, s.pulse_tiles, pst))) return rc;
+    if (!pulse_fused && (rc = launch_pulse_place(ctx, s.onsets, s.onset_cnt, b->sample_off, n, N, s.pulse, s.pulse_tiles, pst))) return rc;
     if (r.side_on) {
         // the warp behind the pulse placement on its stream (the caller's stream carries the mask smoothing and the noise walker)
         if (r.walkers && !link.warped) {

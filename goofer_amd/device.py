@@ -579,7 +579,7 @@ class Context:
         return d_att
 
     def counter(self, name: str) -> int:
-        """Cumulative device-side counter of the handle (goofer_counter): 'pulse_scanned_notes', 'pulse_fallback_notes',
+        """Cumulative device-side counter of the handle (goofer_counter): 'pulse_scanned_notes', 'pulse_fallback_notes', 'pulse_list_notes',
         'mask_flag_segments', 'mask_staged_segments'; and, host-side and not cumulative, the frames per wave of the last launch
         of each frame walker: 'walk_run_noise', 'walk_run_harm', 'walk_run_ola3', 'walk_run_ola1' (option 'walk_run')."""
         v = C.c_int64(0)

@@ -517,7 +517,9 @@ int goofer_check(goofer_ctx *ctx);
 
 /* Cumulative per-handle counters kept on the device (the call synchronises): "pulse_scanned_notes" = notes whose pulse onsets
  * (GOOFER.py:487-493) were taken from the parallel phase scan, "pulse_fallback_notes" = those of them that had to be walked
- * sequentially afterwards because a sample's phase lay within the scan's rounding band of an integer.
+ * sequentially afterwards because a sample's phase lay within the scan's rounding band of an integer, "pulse_list_notes" =
+ * notes the fused pulse kernel (option "pulse_fused") placed from the onset list in global memory and not from its LDS ring: the
+ * walked ones, and those with more than 2048 onsets alive at once.
  * "mask_flag_segments" / "mask_staged_segments": note segments of the mask smoother's 1024-knot tiles (goofer_synth_batch /
  * goofer_render_batch) that were answered from the f0 kernel's tile flags alone / that staged their window of the mask (option
  * "mask_flags"; without flags every segment stages; the per-sample loop of a radius above 1792 knots counts nothing).
@@ -1105,6 +1107,9 @@ const char *goofer_profile_stage_name_ex(const goofer_ctx *ctx, int stage);   /*
  *   "pulse_scan" 1 (default): pulse onsets from a parallel fp64 phase scan wherever its rounding band provably cannot move
  *               floor(phase), the sequential walk only for the remaining notes; 0: the sequential walk for every note;
  *               2: the scan kernel walks every note (tests the hand-over)
+ *   "pulse_fused" 1 (default): with "pulse_scan" != 0 the pulse train is one kernel, a workgroup per note: scan, periods and
+ *               placement per round of 2048 samples, the onsets in an LDS ring (k_pulse_note); 0: the chain of four kernels
+ *               (scan, onset records, tile table, placement).  A/B, the same bits
  *   "value_f64" 0 (default): k_env_edit's VALUE arithmetic (fw interpolation, es blur, knot exp) in fp32 — everything that
  *               decides an index, a threshold or the pitch curve stays fp64; 1: round 4's fp64
  *               arithmetic there (agrees to 2e-8 sample-RMS on the 1024-note batch; not bit-identical)
