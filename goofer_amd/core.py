@@ -1141,6 +1141,24 @@ def compress_batch(signals, sr, threshold_db, ratio, knee_db=6.0, attack_ms=5.0,
     return (_by_csr(y, plan.in_off), red.cpu().numpy(), _by_csr(yl, plan.in_off)) if curve else (_by_csr(y, plan.in_off), red.cpu().numpy())
 
 
+def eq_batch(signals, sr, bands, ctx=None):
+    """Many signals through the parametric equaliser in one device pass (goofer_amd.eq; goofer_eq): ``signals``, 1-D arrays at
+    ``sr`` (8000 to 192000 Hz), each through the cascade of ``bands`` — ``eq.Band`` objects, ``(kind, f0_hz[, gain_db[, q]])``
+    tuples or the string ``kind:f0[:gain_db[:q]],...``, at most eight, kinds ``highpass lowpass lowshelf highshelf peak notch``
+    — run in float64 and rounded once.  Returns the filtered signals as a list of fp32 arrays of the same lengths; bands that
+    are all the identity (0 dB shelves and peaks, or none) give the input's bits.  This project's own definition
+    (include/goofer_hip.h)."""
+    from . import eq as EQ
+    xs = _signal_arrays(signals)
+    plan = EQ.plan(sr, [len(s) for s in xs], bands)
+    if not plan.total:
+        return [np.zeros(0, dtype=np.float32) for _ in xs]
+    c = ctx or default_context()
+    y = c.eq(_signal_tensor(c, xs), None, plan)
+    c.check()
+    return _by_csr(y, plan.in_off)
+
+
 def synthesize(env_spec, f0_interp, voicing_mask, y, sr, n_fft=1024, hop_length=256, glottal_smoothing=False,
                stretch_factor=1.0, start_sec=None, end_sec=None, apply_brightness=True, normalize=1.0, uv_strength=0.75,
                breath_strength=0.1, noise_transition_smoothness=100, pitch_shift=1.0, formant_shift=1.0, f0_jitter=False,

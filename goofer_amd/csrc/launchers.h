@@ -35,7 +35,7 @@ static inline int walk_run_choice(goofer_ctx *ctx, int which, int64_t work, int6
     return (int)run;
 }
 
-// ---- entry checks of the stages over a ragged batch of signals (limit.hip, loudness.hip, compress.hip) ----
+// ---- entry checks of the stages over a ragged batch of signals (limit.hip, loudness.hip, compress.hip, eq.hip) ----
 // Host code.  A check fails in the name of the entry point `who` (goofer_fail) and returns its code, or GOOFER_OK.
 
 static inline int check_counts(goofer_ctx *ctx, const char *who, int n, int64_t total, int64_t n_tiles)
@@ -149,6 +149,10 @@ int launch_loudness_apply(goofer_ctx *ctx, const float *x, const int64_t *in_off
 int launch_compress(goofer_ctx *ctx, const float *x, const int64_t *in_off, int n, const double *coef, const double *pows,
                     const int32_t *tiles, int64_t n_tiles, float *out, double *max_reduction, double *curve, double *rsum,
                     double *rstart, double *asum, double *astart, int32_t *first_tile, double *xl, hipStream_t st);
+
+// eq.hip
+int launch_eq(goofer_ctx *ctx, const float *x, const int64_t *in_off, int n, int64_t total, int K, const double *coef, const double *mats,
+              const int32_t *tiles, int64_t n_tiles, float *out, double *ends, double *starts, int32_t *first_tile, hipStream_t st);
 
 // noise.hip
 int launch_normal_fill(goofer_ctx *ctx, uint64_t seed, const goofer_note_params *params, const int64_t *sample_off, int n_notes,

@@ -1230,3 +1230,168 @@ int goofer_host_compress_plan(int sr, double threshold_db, double ratio, double 
 }
 
 }  // extern "C"
+
+/* Double-double arithmetic for the equaliser's matrix powers: a value is hi + lo, |lo| <= ulp(hi) / 2, about 104 bits.  Squaring
+ * the transition matrix of a section with poles near z = 1 loses up to 29 bits in 19 squarings (include/goofer_hip.h); in long
+ * double that leaves 2^-35, here 2^-75.  (This file is built without contraction and without fast-math: the error terms below are
+ * not optimised away.) */
+struct eq_dd {
+    double hi, lo;
+};
+static inline eq_dd dd_fast_sum(double a, double b)             // |a| >= |b|
+{
+    const double s = a + b;
+    return {s, b - (s - a)};
+}
+static inline eq_dd dd_two_sum(double a, double b)
+{
+    const double s = a + b, bb = s - a;
+    return {s, (a - (s - bb)) + (b - bb)};
+}
+static inline eq_dd dd_add(eq_dd a, eq_dd b)
+{
+    eq_dd s = dd_two_sum(a.hi, b.hi);
+    const eq_dd t = dd_two_sum(a.lo, b.lo);
+    s = dd_fast_sum(s.hi, s.lo + t.hi);
+    return dd_fast_sum(s.hi, s.lo + t.lo);
+}
+static inline eq_dd dd_mul(eq_dd a, eq_dd b)
+{
+    const double p = a.hi * b.hi;
+    return dd_fast_sum(p, std::fma(a.hi, b.hi, -p) + (a.hi * b.lo + a.lo * b.hi));
+}
+// c = a a, D x D, row-major; entry (i, j) summed in ascending k.  The matrices are block lower triangular (2 x 2 blocks): the
+// entries above stay exactly zero
+static void dd_square(const eq_dd *a, eq_dd *c, int D)
+{
+    for (int i = 0; i < D; ++i)
+        for (int j = 0; j < D; ++j) {
+            eq_dd s = {0.0, 0.0};
+            for (int k = (j & ~1); k <= (i | 1); ++k) s = dd_add(s, dd_mul(a[D * i + k], a[D * k + j]));
+            c[D * i + j] = s;
+        }
+}
+
+// w = C a C for the D x D matrix a, C block diagonal with the blocks [[1, 0], [1, -1]] (its own inverse): a in the coordinates
+// (u[i-1], u[i-1] - u[i-2]) of every section, in which the kernels carry the state.  Block lower triangular like a
+static void dd_to_diff(const eq_dd *a, eq_dd *w, int D)
+{
+    std::vector<eq_dd> r((size_t)D * D);
+    for (int i = 0; i < D; ++i)
+        for (int j = 0; j < D; ++j) {
+            const eq_dd lo = a[D * i + j];
+            r[D * i + j] = (i & 1) ? dd_add(a[D * (i - 1) + j], eq_dd{-lo.hi, -lo.lo}) : lo;      // rows: (u1, u1 - u2)
+        }
+    for (int i = 0; i < D; ++i)
+        for (int j = 0; j < D; j += 2) {
+            const eq_dd odd = r[D * i + j + 1];
+            w[D * i + j] = dd_add(r[D * i + j], odd);                                              // columns: u2 = u1 - d
+            w[D * i + j + 1] = eq_dd{-odd.hi, -odd.lo};
+        }
+}
+
+extern "C" {
+
+/* The equaliser (include/goofer_hip.h; the kernels: eq.hip): the refusals, the bands that are not the identity as cookbook
+ * biquads, the tile table, and the powers of the cascade's transition matrix in double-double, rounded once. */
+int goofer_host_eq_plan(int sr, const int32_t *kind, const double *f0_hz, const double *gain_db, const double *q, int n_bands,
+                        const int64_t *in_off, int n, int *K, double *coef, double *mats, int32_t *tiles, int64_t tiles_cap, int64_t *need)
+{
+    if (!K || !coef || !mats || !need || n < 0 || tiles_cap < 0 || n_bands < 0 || (n > 0 && !in_off) || (tiles_cap > 0 && !tiles) ||
+        (n_bands > 0 && (!kind || !f0_hz || !gain_db || !q)))
+        return GOOFER_EINVAL;
+    if (sr < GOOFER_EQ_MIN_SR || sr > GOOFER_EQ_MAX_SR || n_bands > GOOFER_EQ_MAX_BANDS) return GOOFER_EINVAL;
+    for (int b = 0; b < n_bands; ++b) {
+        const bool gained = kind[b] == GOOFER_EQ_LOWSHELF || kind[b] == GOOFER_EQ_HIGHSHELF || kind[b] == GOOFER_EQ_PEAK;
+        if (kind[b] < 0 || kind[b] >= GOOFER_EQ_KINDS) return GOOFER_EINVAL;
+        if (!(f0_hz[b] * GOOFER_EQ_F_MIN_DIV >= (double)sr && f0_hz[b] <= GOOFER_EQ_F_MAX_REL * (double)sr) ||
+            !(q[b] >= GOOFER_EQ_Q_MIN && q[b] <= (kind[b] == GOOFER_EQ_LOWSHELF || kind[b] == GOOFER_EQ_HIGHSHELF ? GOOFER_EQ_SHELF_Q_MAX : GOOFER_EQ_Q_MAX)) ||
+            !(gained ? gain_db[b] >= -GOOFER_EQ_MAX_GAIN_DB && gain_db[b] <= GOOFER_EQ_MAX_GAIN_DB : gain_db[b] == 0.0))
+            return GOOFER_EINVAL;                               // (written so that a NaN is refused too)
+    }
+    const int64_t n_tiles = signal_tiles(in_off, n, GOOFER_EQ_TILE, nullptr);
+    if (n_tiles < 0) return GOOFER_EINVAL;
+    int k = 0;
+    for (int b = 0; b < n_bands; ++b)
+        if (kind[b] == GOOFER_EQ_HIGHPASS || kind[b] == GOOFER_EQ_LOWPASS || kind[b] == GOOFER_EQ_NOTCH || gain_db[b] != 0.0) ++k;
+    *K = k;
+    need[0] = n_tiles;
+    if (tiles_cap < n_tiles) return 1;
+    const double pi = 3.14159265358979323846;
+    k = 0;
+    for (int b = 0; b < n_bands; ++b) {
+        const bool gained = kind[b] == GOOFER_EQ_LOWSHELF || kind[b] == GOOFER_EQ_HIGHSHELF || kind[b] == GOOFER_EQ_PEAK;
+        if (gained && gain_db[b] == 0.0) continue;              // the identity in exact arithmetic: dropped
+        const double w0 = 2.0 * pi * f0_hz[b] / (double)sr, cs = std::cos(w0), sn = std::sin(w0), alpha = sn / (2.0 * q[b]);
+        const double A = std::pow(10.0, gain_db[b] / 40.0), sq = 2.0 * std::sqrt(A) * alpha;
+        double b0, b1, b2, a0, a1, a2;
+        switch (kind[b]) {
+        case GOOFER_EQ_HIGHPASS:
+            b0 = (1.0 + cs) / 2.0, b1 = -(1.0 + cs), b2 = (1.0 + cs) / 2.0, a0 = 1.0 + alpha, a1 = -2.0 * cs, a2 = 1.0 - alpha;
+            break;
+        case GOOFER_EQ_LOWPASS:
+            b0 = (1.0 - cs) / 2.0, b1 = 1.0 - cs, b2 = (1.0 - cs) / 2.0, a0 = 1.0 + alpha, a1 = -2.0 * cs, a2 = 1.0 - alpha;
+            break;
+        case GOOFER_EQ_LOWSHELF:
+            b0 = A * ((A + 1.0) - (A - 1.0) * cs + sq), b1 = 2.0 * A * ((A - 1.0) - (A + 1.0) * cs), b2 = A * ((A + 1.0) - (A - 1.0) * cs - sq);
+            a0 = (A + 1.0) + (A - 1.0) * cs + sq, a1 = -2.0 * ((A - 1.0) + (A + 1.0) * cs), a2 = (A + 1.0) + (A - 1.0) * cs - sq;
+            break;
+        case GOOFER_EQ_HIGHSHELF:
+            b0 = A * ((A + 1.0) + (A - 1.0) * cs + sq), b1 = -2.0 * A * ((A - 1.0) + (A + 1.0) * cs), b2 = A * ((A + 1.0) + (A - 1.0) * cs - sq);
+            a0 = (A + 1.0) - (A - 1.0) * cs + sq, a1 = 2.0 * ((A - 1.0) - (A + 1.0) * cs), a2 = (A + 1.0) - (A - 1.0) * cs - sq;
+            break;
+        case GOOFER_EQ_PEAK:
+            b0 = 1.0 + alpha * A, b1 = -2.0 * cs, b2 = 1.0 - alpha * A, a0 = 1.0 + alpha / A, a1 = -2.0 * cs, a2 = 1.0 - alpha / A;
+            break;
+        default:                                                // GOOFER_EQ_NOTCH
+            b0 = 1.0, b1 = -2.0 * cs, b2 = 1.0, a0 = 1.0 + alpha, a1 = -2.0 * cs, a2 = 1.0 - alpha;
+            break;
+        }
+        double *c = coef + 5 * k++;
+        c[0] = b0 / a0, c[1] = b1 / a0, c[2] = b2 / a0, c[3] = a1 / a0, c[4] = a2 / a0;
+    }
+    // s' = T s for x = 0, s = (u_1[i-1], u_1[i-2], .., u_K[i-1], u_K[i-2]).  With r_k the row that makes the new u_k from s
+    // (r_0 = 0): r_k = b0 r_(k-1) + b1 e(u_(k-1)[i-1]) + b2 e(u_(k-1)[i-2]) - a1 e(u_k[i-1]) - a2 e(u_k[i-2]); row 2k - 2 of T
+    // is r_k, row 2k - 1 picks u_k[i-1].
+    const int D = 2 * k;
+    std::vector<eq_dd> T((size_t)D * D, eq_dd{0.0, 0.0}), U((size_t)D * D), W((size_t)D * D);
+    for (int s = 0; s < k; ++s) {
+        const double *c = coef + 5 * s;
+        eq_dd *row = T.data() + (size_t)D * 2 * s;
+        if (s > 0) {
+            const eq_dd *prev = T.data() + (size_t)D * 2 * (s - 1);
+            for (int j = 0; j < 2 * s; ++j) row[j] = dd_mul(eq_dd{c[0], 0.0}, prev[j]);
+            row[2 * s - 2] = dd_add(row[2 * s - 2], eq_dd{c[1], 0.0});
+            row[2 * s - 1] = dd_add(row[2 * s - 1], eq_dd{c[2], 0.0});
+        }
+        row[2 * s] = eq_dd{-c[3], 0.0}, row[2 * s + 1] = eq_dd{-c[4], 0.0};
+        row[D + 2 * s] = eq_dd{1.0, 0.0};
+    }
+    int sq = 0;
+    for (int m = GOOFER_EQ_SPT; m > 1; m >>= 1) ++sq;           // SPT is a power of two: T^SPT by squaring
+    for (int i = 0; i < sq; ++i) dd_square(T.data(), U.data(), D), T.swap(U);
+    // Every stored power is C T^m C, the power in the coordinates (u[i-1], u[i-1] - u[i-2]) per section, transformed in
+    // double-double and rounded once: T^m of a section with poles near z = 1 has entries of about 1 / w0 that cancel against
+    // each other on a smooth state, and their float64 rounding alone costs eight bits of the output (include/goofer_hip.h).
+    // sections: the diagonal blocks of C T^(SPT 2^j) C are the sections' own 2 x 2 powers; [K][LEVELS][4]
+    for (int j = 0; j < GOOFER_EQ_LEVELS; ++j) {
+        dd_to_diff(T.data(), W.data(), D);
+        for (int s = 0; s < k; ++s)
+            for (int e = 0; e < 4; ++e) mats[(GOOFER_EQ_LEVELS * s + j) * 4 + e] = W[(size_t)D * (2 * s + (e >> 1)) + 2 * s + (e & 1)].hi;
+        dd_square(T.data(), U.data(), D), T.swap(U);
+    }
+    // carries, behind the sections' powers: C T^TILE C, then C T^(TILE RUN_TILES 2^j) C, [1 + LEVELS][D][D]
+    double *car = mats + 4 * GOOFER_EQ_LEVELS * k;
+    dd_to_diff(T.data(), W.data(), D);
+    for (int e = 0; e < D * D; ++e) car[e] = W[e].hi;
+    for (int m = GOOFER_EQ_RUN_TILES; m > 1; m >>= 1) dd_square(T.data(), U.data(), D), T.swap(U);   // RUN_TILES is a power of two
+    for (int j = 0; j < GOOFER_EQ_LEVELS; ++j) {
+        dd_to_diff(T.data(), W.data(), D);
+        for (int e = 0; e < D * D; ++e) car[(size_t)D * D * (1 + j) + e] = W[e].hi;
+        if (j + 1 < GOOFER_EQ_LEVELS) dd_square(T.data(), U.data(), D), T.swap(U);
+    }
+    signal_tiles(in_off, n, GOOFER_EQ_TILE, tiles);
+    return GOOFER_OK;
+}
+
+}  // extern "C"

@@ -236,7 +236,7 @@ class Context:
         return out
 
     def _signals(self, who, x, d_off, plan, out, n_out=None, make_out=True):
-        """The argument checks the stages over a ragged batch share (rate_convert, compress, loudness, limit, true_peak), each a
+        """The argument checks the stages over a ragged batch share (rate_convert, eq, compress, loudness, limit, true_peak), each a
         ValueError in ``who``'s name: ``d_off`` a device tensor (one contiguous int64 CSR of ``plan.n`` signals), a host sequence
         (equal to the plan's) or None for the plan's own; ``x`` a contiguous fp32 tensor of at least ``plan.total`` samples;
         ``out`` None or a contiguous fp32 tensor of ``n_out`` samples (default: ``plan.total``).  Returns (the offsets on the
@@ -377,6 +377,24 @@ class Context:
                     plan.n_tiles, _ptr(y) if total else None, _ptr(red), _ptr(yl) if curve and total else None)
             self._scratch_call(self.lib.goofer_compress, args)
         return y, red, yl
+
+    def eq(self, x, d_off, plan, out=None):
+        """The signals of a ragged batch through the parametric equaliser on the device (goofer_eq; the definition:
+        include/goofer_hip.h, restated in tests/eq_ref.py).  ``x``: the signals' samples back to back, a contiguous fp32 device
+        tensor; ``d_off``: their int64 CSR offsets ``[n + 1]``, a device tensor, a host sequence (checked against the plan) or
+        None for the plan's own; ``plan``: a ``goofer_amd.eq.EqPlan`` for these lengths, which carries the bands (shipped in one
+        upload the first time it is used on this device); ``out``: a contiguous fp32 device tensor of ``plan.total`` samples
+        that does not overlap ``x`` (default: a new one; it need not be cleared).  Returns ``y``, fp32 ``[plan.total]``: signal i
+        is ``y[plan.in_off[i]:plan.in_off[i + 1]]``; with a plan whose bands are all the identity, a copy of ``x``.
+        Asynchronous on the current stream."""
+        n, total = plan.n, plan.total
+        d_in, y = self._signals("eq", x, d_off, plan, out)
+        _, coef, mats, tiles = plan.device_tables(self)
+        if n and total:
+            args = (_ptr(x), _ptr(d_in), n, total, plan.K, _ptr(coef) if plan.K else None, _ptr(mats) if plan.K else None, _ptr(tiles),
+                    plan.n_tiles, _ptr(y))
+            self._scratch_call(self.lib.goofer_eq, args)
+        return y
 
     def normal_fill(self, seed: int, params, lengths_or_offsets, tag: int, note_on=None, growl_scale=None, out=None):
         """float64 standard normals of stream ``tag`` (0 f0 jitter, 1 / 2 harmonic / breath volume jitter, 3 sub-harmonic f0

@@ -6,7 +6,7 @@ definition is this project's own (``include/goofer_hip.h``, goofer_phrase_note; 
 ``goofer_phrase_mix``.  Here: wavtool's arguments turned into note records (host, float64), the records checked and the
 cover table made by the library's planner (``goofer_host_phrase_plan``), and a command line,
 
-    python -m goofer_amd.phrase [--rate HZ] [--compress T:R[:ATTACK:RELEASE[:KNEE[:MAKEUP]]]] [--loudness LUFS] [--limit [DBFS] [--true-peak]] job.txt out.wav
+    python -m goofer_amd.phrase [--rate HZ] [--eq SPEC] [--compress T:R[:ATTACK:RELEASE[:KNEE[:MAKEUP]]]] [--loudness LUFS] [--limit [DBFS] [--true-peak]] job.txt out.wav
 
 ``job.txt`` holds one line per note, the 13 resampler arguments, ``|``, then wavtool's ``stp length p1 p2 p3 v1 v2 v3 v4 [ovr
 [p4 [p5 v5]]]``::
@@ -25,7 +25,11 @@ measures the track's integrated loudness after BS.1770 (goofer_amd.loudness) and
 limiter, the gain capped at 20 dB; the measured loudness and the gain go to stderr too.  ``--compress
 T:R[:ATTACK:RELEASE[:KNEE[:MAKEUP]]]`` runs the dynamic range compressor (goofer_amd.compress) over the track behind the rate
 conversion and in front of the loudness stage: threshold T in dB re full scale, ratio R (``inf`` allowed), attack and release in
-ms (5 and 100), knee width in dB (6), make-up gain in dB (0); its greatest gain reduction goes to stderr.
+ms (5 and 100), knee width in dB (6), make-up gain in dB (0); its greatest gain reduction goes to stderr.  ``--eq SPEC`` runs
+the parametric equaliser (goofer_amd.eq) over the track behind the rate conversion and in front of the compressor: SPEC is up
+to eight bands joined by commas, each ``kind:f0[:gain_db[:q]]`` with the kinds ``hp lp ls hs peak notch``, f0 in Hz between
+1/600 and 0.45 of the wav's rate, gain_db in [-9, 9] for ``ls hs peak`` and q in [0.1, 8] (``ls hs``: [0.1, 2]; default sqrt(1/2)), as in
+``--eq hp:80,peak:3000:3:1,hs:10000:4``.
 ``Renderer.render_phrase`` is the same for (Source, Request) jobs.
 """
 from __future__ import annotations
@@ -235,14 +239,15 @@ def read_job(path):
 
 
 def render_job(path, out_wav, renderer=None, seed=None, tracker=None, pcm16=True, out_sr=None, limit=None, stats=None, loudness=None,
-               compress=None):
+               compress=None, eq=None):
     """``python -m goofer_amd.phrase``: the notes of a job file rendered as one batch and written as one wav.  ``in_file`` is
     resolved like the resampler front end does: ``<stem>_features.goofy`` beside the wav, analysed and cached first when it is
     missing (``trackers.ensure_features_batch``; the tracker: the argument, else ``$GOOFER_TRACKER``).  ``out_sr``: the rate of
     the wav (``render_phrase``'s; None: the voicebank's).  ``limit``: ``render_phrase``'s (None: no limiter); with it ``stats``,
     a dict, receives the limiter's ``peak_in`` and ``min_gain`` (a true-peak limiter's ``true_peak_in`` and ``true_peak_out`` too).  ``loudness``: ``render_phrase``'s (None: the track's level is
     left as it is); with it ``stats`` receives ``lufs_in``, ``momentary_max`` and ``gain``.  ``compress``: ``render_phrase``'s (None:
-    no compressor); with it ``stats`` receives ``max_reduction_db``."""
+    no compressor); with it ``stats`` receives ``max_reduction_db``.  ``eq``: ``render_phrase``'s (None: no equaliser); it has no
+    statistic."""
     from pathlib import Path
     from . import core, trackers
     from . import sampler as S
@@ -266,10 +271,10 @@ def render_job(path, out_wav, renderer=None, seed=None, tracker=None, pcm16=True
     if seed is None:
         seed = int(np.random.SeedSequence().generate_state(1, dtype=np.uint64)[0])
     if limit is None and loudness is None and compress is None:
-        track = renderer.render_phrase(jobs, [e for _, e in lines], seed=seed, pcm16=pcm16, out_sr=out_sr)
+        track = renderer.render_phrase(jobs, [e for _, e in lines], seed=seed, pcm16=pcm16, out_sr=out_sr, eq=eq)
     else:
         track, st = renderer.render_phrase(jobs, [e for _, e in lines], seed=seed, pcm16=pcm16, out_sr=out_sr, limit=limit, return_stats=True,
-                                           loudness=loudness, compress=compress)
+                                           loudness=loudness, compress=compress, eq=eq)
         if stats is not None:
             stats.update(st)
     write_wav(out_wav, track, jobs[0][0].sr if out_sr is None else int(out_sr))
@@ -281,9 +286,9 @@ def main(argv=None) -> int:
     from . import limit as LM
     logging.basicConfig(format="%(message)s", level=logging.INFO)
     argv = list(sys.argv[1:] if argv is None else argv)
-    out_sr = limit = loudness = compress = None
+    out_sr = limit = loudness = compress = eq = None
     true_peak = False
-    while len(argv) > 2 and argv[0] in ("--rate", "--limit", "--loudness", "--compress", "--true-peak"):
+    while len(argv) > 2 and argv[0] in ("--rate", "--limit", "--loudness", "--compress", "--true-peak", "--eq"):
         if argv[0] == "--true-peak":
             true_peak = True
             argv = argv[1:]
@@ -296,6 +301,13 @@ def main(argv=None) -> int:
         elif argv[0] == "--loudness":
             try:
                 loudness = float(argv[1])
+            except ValueError:
+                break
+            argv = argv[2:]
+        elif argv[0] == "--eq":
+            from . import eq as EQ
+            try:
+                eq = EQ.parse(argv[1])
             except ValueError:
                 break
             argv = argv[2:]
@@ -314,16 +326,19 @@ def main(argv=None) -> int:
                 limit = LM.CEILING
                 argv = argv[1:]
     if len(argv) != 2 or (true_peak and limit is None):
-        logging.error("Usage:\n  python -m goofer_amd.phrase [--rate HZ] [--compress T:R[:ATTACK:RELEASE[:KNEE[:MAKEUP]]]] [--loudness LUFS] "
+        logging.error("Usage:\n  python -m goofer_amd.phrase [--rate HZ] [--eq KIND:F0[:GAIN_DB[:Q]],...] [--compress T:R[:ATTACK:RELEASE[:KNEE[:MAKEUP]]]] [--loudness LUFS] "
                       "[--limit [DBFS] [--true-peak]] job.txt out.wav")
         return 1
     stats = {}
     try:
         track = render_job(argv[0], argv[1], out_sr=out_sr, limit=LM.Limiter(limit, true_peak=True) if true_peak else limit, stats=stats,
-                           loudness=loudness, compress=compress)
+                           loudness=loudness, compress=compress, eq=eq)
     except Exception:                   # noqa: BLE001
         logging.exception("Failed to render")
         return 1
+    if eq is not None:
+        print("Equaliser: %s" % ", ".join("%s %g Hz%s q %.3g" % (b.kind, b.f0_hz, " %+g dB" % b.gain_db if b.kind in EQ.GAINED else "", b.q)
+                                          for b in eq), file=sys.stderr)
     if compress is not None:
         print("Compressor: greatest reduction %.2f dB (threshold %.2f dBFS, ratio %g, attack %g ms, release %g ms, knee %g dB, make-up %g dB)"
               % (stats["max_reduction_db"], compress.threshold_db, compress.ratio, compress.attack_ms, compress.release_ms, compress.knee_db,

@@ -21,6 +21,7 @@ from . import _lib
 from . import compress as CP
 from . import limit as LM
 from . import loudness as LD
+from . import eq as EQ
 from . import rate as RT
 from . import sampler as S
 from .device import Context, check_noise_seed, check_phi_seed, default_context, default_params, pcg64_words, row_stride
@@ -428,24 +429,27 @@ class Renderer:
         lw = int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", "1")) or 1)
         self.plan_threads = 0 if lw <= 1 else max(1, min(8, (os.cpu_count() or 8) // lw))
 
-    def _finish_settings(self, jobs, who, out_sr, compress, loudness, limit):
+    def _finish_settings(self, jobs, who, out_sr, compress, loudness, limit, eq=None):
         """The arguments of the finishing chain, parsed once, as ``_finish`` takes them behind the lengths: (the notes' rate, the
-        rate to convert to or None where ``out_sr`` asks for none — None, or the notes' own rate —, compress, loudness, limit),
-        a stage that is not asked for None.  Raises ValueError, in ``who``'s name, where one is asked for and the notes do not
-        share one sample rate."""
+        rate to convert to or None where ``out_sr`` asks for none — None, or the notes' own rate —, compress, loudness, limit,
+        eq), a stage that is not asked for None.  Raises ValueError, in ``who``'s name, where one is asked for and the notes do
+        not share one sample rate."""
         chain = (None if compress is None else CP.parse(compress), None if loudness is None else LD.parse(loudness),
-                 None if limit is None else LM.parse(limit))
+                 None if limit is None else LM.parse(limit), None if eq is None else EQ.parse(eq))
         rates = {int(src.sr) for src, _ in jobs}
-        for what, asked in zip(("out_sr converts", "limit takes", "loudness takes", "compress takes"), (out_sr, limit, loudness, compress)):
+        for what, asked in zip(("out_sr converts", "limit takes", "loudness takes", "compress takes", "eq takes"),
+                               (out_sr, limit, loudness, compress, eq)):
             if asked is not None and len(rates) != 1:
                 raise ValueError(f"{who}: {what} notes that share one sample rate")
         if out_sr is not None and (int(out_sr) != out_sr or int(out_sr) < 1):
             raise ValueError(f"{who}: out_sr is a whole number of Hz")
+        if eq is not None:                                     # the bands against the rate they will run at, before anything is rendered
+            EQ.plan(jobs[0][0].sr if out_sr is None else int(out_sr), [], chain[3])
         return (jobs[0][0].sr, None if out_sr is None or int(out_sr) in rates else int(out_sr), *chain)
 
-    def _finish(self, x, d_off, lengths, sr, to_sr, compress, loudness, limit, true_peak_out=False):
+    def _finish(self, x, d_off, lengths, sr, to_sr, compress, loudness, limit, eq=None, true_peak_out=False):
         """The finishing chain over the signals of ``lengths`` samples lying back to back in the device tensor ``x`` at ``sr``
-        (``d_off``: their CSR on the device, or None): convert to ``to_sr``, compress, loudness, limit, each with its parsed
+        (``d_off``: their CSR on the device, or None): convert to ``to_sr``, eq, compress, loudness, limit, each with its parsed
         settings; a stage whose setting is None launches nothing and allocates nothing.  Returns (the tensor, the signals'
         lengths in it, the statistics as the stages return them, device tensors: ``max_reduction``; ``loud``, ``gain``;
         ``peak_in``, ``min_gain``, and with ``true_peak_out`` behind a true-peak limiter ``true_peak_out``)."""
@@ -453,6 +457,8 @@ class Renderer:
         if to_sr is not None:
             plan = RT.plan(sr, to_sr, lengths)
             x, lengths, sr = self.ctx.rate_convert(x, d_off, plan), np.diff(plan.out_off), to_sr
+        if eq is not None:
+            x = self.ctx.eq(x, None, EQ.plan(sr, lengths, eq))
         if compress is not None:
             x, stats["max_reduction"], _ = self.ctx.compress(x, None, CP.plan(sr, lengths, compress))
         if loudness is not None:
@@ -465,7 +471,7 @@ class Renderer:
         return x, lengths, stats
 
     def render(self, jobs, seed: int = 0, phi_seeds=None, return_parts: bool = False, noise_seeds=None, out_sr=None, limit=None,
-               loudness=None, compress=None):
+               loudness=None, compress=None, eq=None):
         """jobs: list of (Source, Request).  Returns a list of fp32 arrays (the mix the reference writes to
         out.wav); with ``return_parts`` also a dict of device-side intermediates for tests.
         ``phi_seeds``: per-note seeds for INJECTED phases (parity with a seeded reference run: numpy's stream of each seed,
@@ -487,10 +493,13 @@ class Renderer:
         ``compress``: None, a ``goofer_amd.compress.Compressor``, a ``(threshold_db, ratio[, attack_ms, release_ms[, knee_db[,
         makeup_db]]])`` sequence or the string ``T:R[:ATTACK:RELEASE[:KNEE[:MAKEUP]]]``: every note through the dynamic range
         compressor on the device (goofer_amd.compress; the whole batch in one goofer_compress), after the conversion and in
-        front of the loudness stage."""
+        front of the loudness stage.
+        ``eq``: None, a sequence of ``goofer_amd.eq.Band`` objects or ``(kind, f0_hz[, gain_db[, q]])`` tuples, or the string
+        ``kind:f0[:gain_db[:q]],...``: every note through the parametric equaliser on the device (goofer_amd.eq; the whole batch
+        in one goofer_eq), after the conversion and in front of the compressor."""
         if not jobs:
             return []
-        chain = self._finish_settings(jobs, "render", out_sr, compress, loudness, limit)
+        chain = self._finish_settings(jobs, "render", out_sr, compress, loudness, limit, eq)
         prep = self.prepare(jobs, phi_seeds=phi_seeds, trim_rows=not return_parts, noise_seeds=noise_seeds)   # tests look at the whole assembled envelope
         out = self.run(prep, seed=seed, keep_stems=return_parts)
         mix, lens, _ = self._finish(out["mix"], prep["offsets"]["d_s"], np.diff(np.asarray(prep["sample_off"], dtype=np.int64)), *chain)
@@ -504,7 +513,7 @@ class Renderer:
         return res
 
     def render_phrase(self, jobs, entries, seed: int = 0, phi_seeds=None, noise_seeds=None, pcm16: bool = False, out_sr=None, limit=None,
-                      return_stats: bool = False, loudness=None, compress=None):
+                      return_stats: bool = False, loudness=None, compress=None, eq=None):
         """The notes of ``jobs`` rendered as one batch and assembled into one track on the device: what a ``wavtool`` does with
         the notes ``render`` returns, without bringing them home first (goofer_amd.phrase; goofer_phrase_mix).  ``entries``:
         the phrase in order, one ``phrase.Entry`` (or its wavtool argument string ``stp length p1 p2 p3 v1 v2 v3 v4 [ovr [p4
@@ -525,16 +534,19 @@ class Renderer:
         in dB.  ``return_stats`` (with ``limit``, ``loudness`` or ``compress``): also a dict; with ``limit`` the track's
         ``peak_in``, its greatest ``|x|`` in front of the limiter, and ``min_gain``, the smallest gain the limiter applied; with
         ``loudness`` ``lufs_in``, the track's integrated loudness in front of the scaling, ``momentary_max``, its greatest
-        momentary loudness, and ``gain``, the factor it was scaled by (Python floats)."""
+        momentary loudness, and ``gain``, the factor it was scaled by (Python floats).  ``eq``: None or what ``render``
+        takes: the track through the parametric equaliser on the device (goofer_amd.eq), behind the conversion and in front of
+        the compressor — mix, convert, eq, compress, loudness, limit, then int16; it has no statistic."""
         from . import phrase as P
         if return_stats and limit is None and loudness is None and compress is None:
-            raise ValueError("render_phrase: return_stats reports the limiter's and the loudness stage's statistics and needs limit or loudness")
+            raise ValueError("render_phrase: return_stats reports the statistics of the limiter, the loudness stage and the compressor and needs "
+                             "limit, loudness or compress (eq has no statistic)")
         entries = [e if isinstance(e, P.Entry) else P.Entry.parse(e) for e in entries]
         if not jobs:
             raise ValueError("render_phrase: a phrase without a note has no sample rate")
         if len({src.sr for src, _ in jobs}) != 1:
             raise ValueError("render_phrase: the notes of a phrase share one sample rate")
-        chain = self._finish_settings(jobs, "render_phrase", out_sr, compress, loudness, limit)
+        chain = self._finish_settings(jobs, "render_phrase", out_sr, compress, loudness, limit, eq)
         prep = self.prepare(jobs, phi_seeds=phi_seeds, noise_seeds=noise_seeds)
         plan = P.plan_phrase(entries, np.diff(np.asarray(prep["sample_off"], dtype=np.int64)), jobs[0][0].sr)
         out = self.run(prep, seed=seed)

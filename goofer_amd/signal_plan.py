@@ -1,4 +1,4 @@
-"""What the plans of the stages over finished audio share (phrase, rate, compress, loudness, limit): one blob per plan for one
+"""What the plans of the stages over finished audio share (phrase, rate, eq, compress, loudness, limit): one blob per plan for one
 upload, cut into typed views on the device; the signals' lengths as a CSR with the refusals every stage makes; and the capacity
 protocol of the library's host planners (include/goofer_hip.h)."""
 from __future__ import annotations

@@ -1084,6 +1084,126 @@ int goofer_compress(goofer_ctx *ctx, const float *x, const int64_t *in_off, int 
                     const int32_t *tiles, int64_t n_tiles, float *out, double *max_reduction, double *curve, void *scratch,
                     int64_t *scratch_bytes, void *stream);
 
+/* ---- parametric equaliser -------------------------------------------------------------------------------------------------
+ * Every other stage of the finishing chain acts on level or peaks; this one shapes the spectrum: a cascade of up to
+ * GOOFER_EQ_MAX_BANDS biquads over every signal of a ragged batch, behind the rate conversion and in front of the compressor
+ * (mix, rate conversion, equaliser, compressor, loudness, limiter, int16).  The definition is this project's own (restated in
+ * numpy by tests/eq_ref.py).  A signal gets the same bits alone as at any position in any batch, on every run: no floating-point
+ * atomics.
+ *
+ * Bands.  A plan has K bands, 0 <= K <= GOOFER_EQ_MAX_BANDS, shared by the whole batch; a band is (kind, f0_hz, gain_db, q),
+ * kind one of GOOFER_EQ_HIGHPASS, _LOWPASS, _LOWSHELF, _HIGHSHELF, _PEAK, _NOTCH.  sr: an integer, GOOFER_EQ_MIN_SR <= sr <=
+ * GOOFER_EQ_MAX_SR.  sr / GOOFER_EQ_F_MIN_DIV <= f0_hz <= GOOFER_EQ_F_MAX_REL sr; GOOFER_EQ_Q_MIN <= q <= GOOFER_EQ_Q_MAX
+ * (GOOFER_EQ_SHELF_Q_MAX for the two shelves);
+ * |gain_db| <= GOOFER_EQ_MAX_GAIN_DB for the shelves and the peak, gain_db == 0 for the others, which ignore it.  Anything else,
+ * a NaN included, is refused (GOOFER_EINVAL).  The lowest f0, the highest q and the greatest gain are measured, not chosen: see
+ * the tolerance.
+ *
+ * Coefficients (host, float64): the Audio-EQ-Cookbook biquads.  w0 = 2 pi f0 / sr, c = cos w0, s = sin w0, alpha = s / (2 q),
+ * A = 10^(gain_db / 40), r = 2 sqrt(A) alpha:
+ *   highpass   b = [(1 + c) / 2, -(1 + c), (1 + c) / 2]                        a = [1 + alpha, -2 c, 1 - alpha]
+ *   lowpass    b = [(1 - c) / 2, 1 - c, (1 - c) / 2]                           a = [1 + alpha, -2 c, 1 - alpha]
+ *   notch      b = [1, -2 c, 1]                                                a = [1 + alpha, -2 c, 1 - alpha]
+ *   peak       b = [1 + alpha A, -2 c, 1 - alpha A]                            a = [1 + alpha / A, -2 c, 1 - alpha / A]
+ *   lowshelf   b = [A ((A+1) - (A-1) c + r), 2 A ((A-1) - (A+1) c), A ((A+1) - (A-1) c - r)]
+ *              a = [(A+1) + (A-1) c + r, -2 ((A-1) + (A+1) c), (A+1) + (A-1) c - r]
+ *   highshelf  b = [A ((A+1) + (A-1) c + r), -2 A ((A-1) + (A+1) c), A ((A+1) + (A-1) c - r)]
+ *              a = [(A+1) - (A-1) c + r, 2 ((A-1) - (A+1) c), (A+1) - (A-1) c - r]
+ * each divided by its a0.  coef[5 K] = b0 b1 b2 a1 a2 per band, in band order.
+ *
+ * Identity.  A peak, lowshelf or highshelf band with gain_db == 0 is the identity in exact arithmetic (b = a) and is dropped by
+ * the planner: K counts the bands that are left.  With K == 0 the output is a copy of the input, the same bits.
+ *
+ * Per signal x[0 .. n), zero history in front of every signal, all recurrences in float64, no contraction:
+ *   u_0 = x
+ *   u_k[i] = b0 u_(k-1)[i] + b1 u_(k-1)[i-1] + b2 u_(k-1)[i-2] - a1 u_k[i-1] - a2 u_k[i-2]    for k = 1 .. K, with band k's coef
+ *   y[i] = fp32(u_K[i]), rounded once
+ * A NaN sample makes its own signal NaN from that sample on.  An infinite sample leaves the rest of its signal unspecified, for
+ * the reason the loudness section gives (matrix powers multiply their structural zeros by it).  Either way the other signals of
+ * the batch are untouched.
+ *
+ * The cascade is linear with the state s = (u_1[i-1], u_1[i-2], .., u_K[i-1], u_K[i-2]): a run of m samples from s ends in
+ * T^m s + (the end state of the same run from s = 0), T the 2K x 2K transition matrix for x = 0 — block lower triangular in
+ * 2 x 2 blocks, and the diagonal block of section k in T^m is that section's own 2 x 2 matrix to the m.  The kernels cut a
+ * signal into tiles of GOOFER_EQ_TILE samples and a tile into runs of GOOFER_EQ_SPT.  Only the carry from tile to tile uses the
+ * coupled matrix: inside a tile, once its start state is known, the sections run one after another, each with a scan over its
+ * own 2 x 2 powers (the state of section k - 1 in front of a run is the input history section k needs there).
+ * Between runs and tiles the state travels as (u_k[i-1], u_k[i-1] - u_k[i-2]) per section, and every stored power is C T^m C, C
+ * block diagonal with the blocks [[1, 0], [1, -1]] (its own inverse): T^m of a section with poles near z = 1 has entries of
+ * about 1 / w0 that cancel against each other on a smooth state, and their float64 rounding alone costs eight bits of the
+ * output; in these coordinates the entries are well scaled.
+ * mats (float64): first [K][GOOFER_EQ_LEVELS][4], section k's 2 x 2 block of C T^(SPT 2^j) C, row-major; then
+ * [1 + GOOFER_EQ_LEVELS][2K][2K], row-major: C T^TILE C, which carries the state over one tile, and C T^(TILE RUN_TILES 2^j) C
+ * for the scan over runs of GOOFER_EQ_RUN_TILES tiles: GOOFER_EQ_MATS(K) numbers.  The powers are made by repeated squaring
+ * in double-double on the host, transformed there and rounded once: squared in long double, T^4096 of a 20 Hz high-pass at
+ * 192 kHz is off by 2^-35 of its largest entry.
+ *
+ * Tolerance: |y[i] - u_K_longdouble[i]| <= 2^-24 |u_K_longdouble[i]| + GOOFER_EQ_TOL max_i |u_K_longdouble[i]| per signal; the
+ * first term is the one fp32 rounding, the second covers the carry.  Carrying a recurrence as "zero-state run plus matrix
+ * times start state" is exact in exact arithmetic only: for poles near z = 1 the free response of a state is about
+ * |u[i-1] - u[i-2]| / w0, hundreds of times the output, and a zero-state run is the true output minus that free response, so
+ * its rounding noise is larger by the same factor; and a later band that boosts amplifies the carry noise of the bands in
+ * front of it, most where those have cut the signal itself away.  The ranges above are the widest of those tried for which a
+ * float64 model of the kernels' scheme (tests/eq_ref.py, `tiled`) stays within GOOFER_EQ_TOL / 4 on every corner of the range
+ * (tests/eq_ref.py, `corners`, 63 chains; tests/test_eq_ref.py runs them), every band at the lowest f0, the highest q of its
+ * kind and the greatest gain: one band and eight equal bands of every kind, boost and cut; chains of eight that cut and then
+ * boost (notches, cutting peaks and shelves, high- and low-passes, then peaks or either shelf); chains that boost and then cut;
+ * inverse pairs, the identity in exact arithmetic (four shelves or peaks one way, four the other); unequal splits (1 + 7, 2 + 6,
+ * 3 + 5, 6 + 2); six seeded random chains — at 8, 44.1, 48, 96 and 192 kHz, on noise of 0.3 rms with a 40 Hz sine and a DC step
+ * over 16 tiles.  Measured worst 2^-29.44 of the output's peak (one notch, then seven peaks of +9 dB, q 8, at 96 kHz; 2^-29.51
+ * at 192 kHz, 2^-29.95 at 48 kHz), times 4 under GOOFER_EQ_TOL = 2^-26, a quarter of an fp32 ulp at the signal's peak; the
+ * kernels themselves are at 2^-29.52 on that corner.  This is a statement about these corners and inputs, not a proof for every
+ * chain of the range.  What the same rule refused, at 96 kHz: shelves of q up to 4 (four low shelves of +12 dB and four of -12
+ * dB, the
+ * identity: 2^-22.6; a shelf above q 2 is a resonance, and a cascade of them and their inverses is badly conditioned in
+ * sequential float64 already); with the shelves at q <= 2, gains to 12 dB (two notches and six peaks: 2^-27.6; 2^-27.9 with
+ * every q <= 4); gains
+ * to 24 dB in every range tried from sr / 600 (2^-26.3 at q 4); and, with the state carried as (u[i-1], u[i-2]), every range
+ * down to sr / 150.  Not built: a double-double carry, which would widen the range. */
+#define GOOFER_EQ_MAX_BANDS 8
+#define GOOFER_EQ_MIN_SR 8000
+#define GOOFER_EQ_MAX_SR 192000
+#define GOOFER_EQ_F_MIN_DIV 600.0    /* f0_hz * 600 >= sr: 13.3 Hz at 8 kHz, 73.5 Hz at 44.1 kHz, 80 Hz at 48 kHz, 320 Hz at 192 kHz */
+#define GOOFER_EQ_F_MAX_REL 0.45
+#define GOOFER_EQ_Q_MIN 0.1
+#define GOOFER_EQ_Q_MAX 8.0
+#define GOOFER_EQ_SHELF_Q_MAX 2.0    /* lowshelf, highshelf: above it a shelf is a resonance; cascades of those cost the tolerance */
+#define GOOFER_EQ_MAX_GAIN_DB 9.0
+#define GOOFER_EQ_TOL 0x1p-26
+#define GOOFER_EQ_TILE 4096
+#define GOOFER_EQ_SPT 16
+#define GOOFER_EQ_LEVELS 8          /* 2^8 runs in a tile; 2^8 threads in a round of the tile-to-tile carry */
+#define GOOFER_EQ_RUN_TILES 16      /* tiles a thread of the tile-to-tile carry walks: 4096 tiles a round */
+#define GOOFER_EQ_MATS(K) (4 * GOOFER_EQ_LEVELS * (K) + 4 * (1 + GOOFER_EQ_LEVELS) * (K) * (K))
+enum { GOOFER_EQ_HIGHPASS = 0, GOOFER_EQ_LOWPASS = 1, GOOFER_EQ_LOWSHELF = 2, GOOFER_EQ_HIGHSHELF = 3, GOOFER_EQ_PEAK = 4,
+       GOOFER_EQ_NOTCH = 5, GOOFER_EQ_KINDS = 6 };
+
+/* Host side (no device, no handle): for n_bands bands (kind, f0_hz, gain_db, q: one array each) and n signals whose samples lie
+ * back to back with the CSR in_off[n + 1] (non-decreasing): *K, the bands left; coef[5 K] (room for 5 GOOFER_EQ_MAX_BANDS);
+ * mats[GOOFER_EQ_MATS(K)] (room for GOOFER_EQ_MATS(GOOFER_EQ_MAX_BANDS)); and the tile table: need[0] = sum_i ceil(len_i /
+ * GOOFER_EQ_TILE) pairs of int32 (signal, tile of that signal), ascending.  Returns 0 with everything written; 1 when tiles_cap
+ * (in pairs) < need[0] (only *K and need are valid: grow, call again); GOOFER_EINVAL for what the definition refuses, more than
+ * GOOFER_EQ_MAX_BANDS bands, a null argument (in_off may be null when n == 0, tiles when tiles_cap == 0, the band arrays when
+ * n_bands == 0), a negative count or capacity, offsets that decrease, a signal of 2^31 samples or more. */
+int goofer_host_eq_plan(int sr, const int32_t *kind, const double *f0_hz, const double *gain_db, const double *q, int n_bands,
+                        const int64_t *in_off, int n, int *K, double *coef, double *mats, int32_t *tiles, int64_t tiles_cap, int64_t *need);
+
+/* The equaliser (eq.hip): out[in_off[i] .. in_off[i+1]) = y of signal x[in_off[i] .. in_off[i+1]), every sample stored exactly
+ * once.  x, in_off ([n + 1]), coef, mats, tiles and out are device arrays of the caller, K and the tables those of
+ * goofer_host_eq_plan for the same in_off, total = in_off[n].  Three launches in stream order, and no workgroup ever waits for
+ * another: (A) a workgroup per tile runs the cascade over its samples from a zero state, section by section, and leaves the
+ * tile's end state; (B) a workgroup per signal turns the tiles' end states, 4096 at a time, with the coupled matrices into the
+ * tiles' true start states (a thread walks 16 tiles, the workgroup scans the threads); (C) every tile again from its true start
+ * state, y stored once.  x is read twice and written once.
+ * A tile reads the two samples in front of it from x, so `out` must not overlap x: in place is a race, and is refused.  K == 0:
+ * one device-to-device copy.  Scratch by the caller-scratch protocol: with scratch NULL the size goes to *scratch_bytes and
+ * nothing runs.  Asynchronous on `stream`.  n == 0 or total == 0: nothing is launched.  GOOFER_EINVAL, with nothing launched,
+ * for a null pointer (all arrays may be null when n == 0 or total == 0; coef and mats when K == 0), a negative count, K outside
+ * [0, GOOFER_EQ_MAX_BANDS], an n_tiles that is not between ceil(total / GOOFER_EQ_TILE) and that plus n, x, tiles or out not
+ * 4-byte aligned, the others not 8-byte aligned, an out that overlaps x, or a scratch block that is too short. */
+int goofer_eq(goofer_ctx *ctx, const float *x, const int64_t *in_off, int n, int64_t total, int K, const double *coef, const double *mats,
+              const int32_t *tiles, int64_t n_tiles, float *out, void *scratch, int64_t *scratch_bytes, void *stream);
+
 /* ---- measurement / test hooks --------------------------------------------------------------- */
 
 /* HIP-event timing of every stage of goofer_synth_batch on the caller's stream: begin() arms up to
