@@ -1159,6 +1159,24 @@ def eq_batch(signals, sr, bands, ctx=None):
     return _by_csr(y, plan.in_off)
 
 
+def reverb_batch(signals, sr, reverb, ctx=None):
+    """Many signals through the convolution reverb in one device pass (goofer_amd.reverb; goofer_reverb): ``signals``, 1-D arrays
+    at ``sr`` (8000 to 192000 Hz), each convolved with the impulse response of ``reverb`` — a ``reverb.Reverb``, a tuple
+    ``(ir[, wet_db[, dry_db[, predelay_ms[, tail]]]])`` with ``ir`` an array of up to 2^18 taps or a ``reverb.Room``, or the
+    string ``room:RT60_S[:WET_DB[:PREDELAY_MS[:SEED]]]`` / ``ir:PATH[:WET_DB[:PREDELAY_MS]]`` — and mixed with itself,
+    ``dry x + wet (h * x)``.  Returns the signals as a list of fp32 arrays, each pre-delay + taps - 1 samples longer with the tail
+    (the default; a signal without a sample stays empty).  This project's own definition (include/goofer_hip.h)."""
+    from . import reverb as RV
+    xs = _signal_arrays(signals)
+    plan = RV.plan(sr, [len(s) for s in xs], reverb)
+    if not plan.total_out:
+        return [np.zeros(0, dtype=np.float32) for _ in xs]
+    c = ctx or default_context()
+    y = c.reverb(_signal_tensor(c, xs), None, plan, plan.reverb.spectra(c, plan.sr))
+    c.check()
+    return _by_csr(y, plan.out_off)
+
+
 def synthesize(env_spec, f0_interp, voicing_mask, y, sr, n_fft=1024, hop_length=256, glottal_smoothing=False,
                stretch_factor=1.0, start_sec=None, end_sec=None, apply_brightness=True, normalize=1.0, uv_strength=0.75,
                breath_strength=0.1, noise_transition_smoothness=100, pitch_shift=1.0, formant_shift=1.0, f0_jitter=False,

@@ -619,6 +619,7 @@ int goofer_set_option(goofer_ctx *ctx, const char *name, int value)
     if (!strcmp(name, "limit_tp_skip")) { ctx->limit_tp_skip = value != 0; return GOOFER_OK; }
     if (!strcmp(name, "compress_skip")) { ctx->compress_skip = value != 0; return GOOFER_OK; }
     if (!strcmp(name, "compress_store")) { ctx->compress_store = value != 0; return GOOFER_OK; }
+    if (!strcmp(name, "reverb_skip")) { ctx->reverb_skip = value != 0; return GOOFER_OK; }
     if (!strcmp(name, "walk_run")) { ctx->walk_run = value < 0 ? 0 : value; return GOOFER_OK; }   // clamped per kernel where the run is chosen (walk_run_choice)
     return goofer_fail(ctx, GOOFER_EINVAL, "unknown option %s", name);
 }

@@ -170,6 +170,7 @@ struct goofer_ctx {
     bool limit_tp_skip = true;    // goofer_limit_tp: a tile whose true-peak envelope never exceeds the ceiling, halo included, copies its samples (option "limit_tp_skip"; 0: the full arithmetic for every tile, A/B, the same bits)
     bool compress_skip = true;    // goofer_compress: a sample under the knee's lower end is found by one compare and its logarithm is not taken (option "compress_skip"; 0: A/B, equal within rounding)
     bool compress_store = false;  // goofer_compress: xl is written to scratch by the first pass and read back by the other two instead of being computed again (option "compress_store"; A/B, the same bits)
+    bool reverb_skip = true;      // goofer_reverb: the multiply-accumulate leaves out a partition of the impulse response whose taps are all zero (option "reverb_skip"; 0: A/B, the same bits)
     int walk_run = 0;             // frames per wave of the four frame walkers (option "walk_run"; 0: chosen from the device, N > 0: N clamped to the
                                   // range that choice can produce for the kernel: walk_run_choice, launchers.h; tests, the same bits)
     int walk_run_used[4] = {0, 0, 0, 0};   // the run the last launch of k_noise_stems / k_harm_stem / k_irfft_ola3 / k_irfft_ola1 got (goofer_counter "walk_run_*")

@@ -154,6 +154,11 @@ int launch_compress(goofer_ctx *ctx, const float *x, const int64_t *in_off, int 
 int launch_eq(goofer_ctx *ctx, const float *x, const int64_t *in_off, int n, int64_t total, int K, const double *coef, const double *mats,
               const int32_t *tiles, int64_t n_tiles, float *out, double *ends, double *starts, int32_t *first_tile, hipStream_t st);
 
+// reverb.hip
+int launch_reverb(goofer_ctx *ctx, const float *x, const int64_t *in_off, int n, int64_t total, const void *ir, int L, int pre, float dry,
+                  float wet, const int64_t *out_off, const int64_t *blk_off, int64_t total_blocks, const int32_t *runs, int64_t n_runs,
+                  int64_t total_out, float *out, float2 *X, float2 *Y, hipStream_t st);
+
 // noise.hip
 int launch_normal_fill(goofer_ctx *ctx, uint64_t seed, const goofer_note_params *params, const int64_t *sample_off, int n_notes,
                        int64_t total, int tag, const unsigned char *note_on, const double *growl_scale, double *out, hipStream_t st);

@@ -1394,4 +1394,39 @@ int goofer_host_eq_plan(int sr, const int32_t *kind, const double *f0_hz, const 
     return GOOFER_OK;
 }
 
+/* The convolution reverb (include/goofer_hip.h; the kernels: reverb.hip): the refusals, the output CSR (every signal with samples
+ * grows by the tail), the signals' block CSR and the runs of up to GOOFER_REVERB_RUN blocks of one signal, a workgroup each. */
+int goofer_host_reverb_plan(int sr, const int64_t *in_off, int n, int L, int pre, int tail, int64_t *out_off, int64_t *blk_off,
+                            int32_t *runs, int64_t runs_cap, int64_t *need)
+{
+    if (!out_off || !blk_off || !need || n < 0 || runs_cap < 0 || (n > 0 && !in_off) || (runs_cap > 0 && !runs)) return GOOFER_EINVAL;
+    if (sr < GOOFER_REVERB_MIN_SR || sr > GOOFER_REVERB_MAX_SR || L < 1 || L > GOOFER_REVERB_MAX_TAPS || pre < 0 ||
+        pre > GOOFER_REVERB_MAX_PREDELAY)
+        return GOOFER_EINVAL;
+    const int64_t grow = tail ? (int64_t)pre + L - 1 : 0;
+    int64_t n_runs = 0;
+    for (int i = 0; i < n; ++i) {
+        const int64_t len = in_off[i + 1] - in_off[i];
+        const int64_t n_out = len > 0 ? len + grow : 0;
+        if (len < 0 || n_out >= ((int64_t)1 << 31)) return GOOFER_EINVAL;
+        const int64_t nb = (n_out + GOOFER_REVERB_BLOCK - 1) / GOOFER_REVERB_BLOCK;
+        n_runs += (nb + GOOFER_REVERB_RUN - 1) / GOOFER_REVERB_RUN;
+    }
+    if (n_runs >= ((int64_t)1 << 31)) return GOOFER_EINVAL;
+    need[0] = n_runs;
+    if (runs_cap < n_runs) return 1;
+    out_off[0] = blk_off[0] = 0;
+    int64_t r = 0;
+    for (int i = 0; i < n; ++i) {
+        const int64_t len = in_off[i + 1] - in_off[i];
+        const int64_t n_out = len > 0 ? len + grow : 0, nb = (n_out + GOOFER_REVERB_BLOCK - 1) / GOOFER_REVERB_BLOCK;
+        out_off[i + 1] = out_off[i] + n_out, blk_off[i + 1] = blk_off[i] + nb;
+        for (int64_t first = 0; first < nb; first += GOOFER_REVERB_RUN, ++r) {
+            const int64_t left = nb - first;
+            runs[3 * r] = i, runs[3 * r + 1] = (int32_t)first, runs[3 * r + 2] = (int32_t)(left < GOOFER_REVERB_RUN ? left : GOOFER_REVERB_RUN);
+        }
+    }
+    return GOOFER_OK;
+}
+
 }  // extern "C"

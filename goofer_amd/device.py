@@ -396,6 +396,42 @@ class Context:
             self._scratch_call(self.lib.goofer_eq, args)
         return y
 
+    def reverb_ir(self, h):
+        """The spectra of an impulse response on the device (goofer_reverb_ir), once per IR: ``h``, a host array of 1 to 2^18
+        finite taps (taken as fp32).  Returns the device buffer (uint8) that ``reverb`` takes for every plan with this IR: the
+        transform's tables, a live byte per partition of 1024 taps and the partitions' spectra."""
+        from . import reverb as RV
+        h = np.ascontiguousarray(h, dtype=np.float32).reshape(-1)
+        if not 1 <= h.size <= RV.MAX_TAPS or not np.all(np.isfinite(h)):
+            raise ValueError("reverb_ir: 1 to %d finite taps" % RV.MAX_TAPS)
+        ir = torch.empty(RV.ir_bytes(h.size), dtype=torch.uint8, device=self.device)
+        self._check(self.lib.goofer_reverb_ir(self.h, _host(h), h.size, _ptr(ir), ir.numel(), self._stream()))
+        return ir
+
+    def reverb(self, x, d_off, plan, ir_spectra, out=None):
+        """The signals of a ragged batch through the convolution reverb on the device (goofer_reverb; the definition:
+        include/goofer_hip.h, restated in tests/reverb_ref.py).  ``x``: the signals' samples back to back, a contiguous fp32 device
+        tensor; ``d_off``: their int64 CSR offsets ``[n + 1]``, a device tensor, a host sequence (checked against the plan) or
+        None for the plan's own; ``plan``: a ``goofer_amd.reverb.ReverbPlan`` for these lengths, which carries the settings
+        (shipped in one upload the first time it is used on this device); ``ir_spectra``: ``reverb_ir`` of the plan's IR (None is
+        taken where the plan's wet gain is 0: no transform runs); ``out``: a contiguous fp32 device tensor of ``plan.total_out``
+        samples that does not overlap ``x`` (default: a new one; it need not be cleared).  Returns ``y``, fp32
+        ``[plan.total_out]``: signal i is ``y[plan.out_off[i]:plan.out_off[i + 1]]``, ``plan.added`` samples longer than it was.
+        Asynchronous on the current stream."""
+        from . import reverb as RV
+        n, total, total_out = plan.n, plan.total, plan.total_out
+        d_in, y = self._signals("reverb", x, d_off, plan, out, n_out=total_out)
+        if plan.wet != 0.0 and (not isinstance(ir_spectra, torch.Tensor) or ir_spectra.dtype != torch.uint8 or not ir_spectra.is_contiguous()
+                                or ir_spectra.numel() < RV.ir_bytes(plan.L) or ir_spectra.device != x.device):
+            raise ValueError("reverb: ir_spectra is Context.reverb_ir of the plan's %d taps, on x's device" % plan.L)
+        _, d_out, d_blk, runs = plan.device_tables(self)
+        if n and total_out:
+            args = (_ptr(x), _ptr(d_in), n, total, None if plan.wet == 0.0 else _ptr(ir_spectra), plan.L, plan.pre, int(plan.tail),
+                    C.c_float(plan.dry), C.c_float(plan.wet), _ptr(d_out), _ptr(d_blk), plan.total_blocks, _ptr(runs), plan.n_runs,
+                    total_out, _ptr(y))
+            self._scratch_call(self.lib.goofer_reverb, args)
+        return y
+
     def normal_fill(self, seed: int, params, lengths_or_offsets, tag: int, note_on=None, growl_scale=None, out=None):
         """float64 standard normals of stream ``tag`` (0 f0 jitter, 1 / 2 harmonic / breath volume jitter, 3 sub-harmonic f0
         jitter, 4 growl) for the notes of a ragged batch, drawn on the device (goofer_normal_fill; the stream's definition:

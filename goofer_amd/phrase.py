@@ -6,7 +6,7 @@ definition is this project's own (``include/goofer_hip.h``, goofer_phrase_note; 
 ``goofer_phrase_mix``.  Here: wavtool's arguments turned into note records (host, float64), the records checked and the
 cover table made by the library's planner (``goofer_host_phrase_plan``), and a command line,
 
-    python -m goofer_amd.phrase [--rate HZ] [--eq SPEC] [--compress T:R[:ATTACK:RELEASE[:KNEE[:MAKEUP]]]] [--loudness LUFS] [--limit [DBFS] [--true-peak]] job.txt out.wav
+    python -m goofer_amd.phrase [--rate HZ] [--eq SPEC] [--compress T:R[:ATTACK:RELEASE[:KNEE[:MAKEUP]]]] [--reverb SPEC] [--loudness LUFS] [--limit [DBFS] [--true-peak]] job.txt out.wav
 
 ``job.txt`` holds one line per note, the 13 resampler arguments, ``|``, then wavtool's ``stp length p1 p2 p3 v1 v2 v3 v4 [ovr
 [p4 [p5 v5]]]``::
@@ -30,6 +30,9 @@ the parametric equaliser (goofer_amd.eq) over the track behind the rate conversi
 to eight bands joined by commas, each ``kind:f0[:gain_db[:q]]`` with the kinds ``hp lp ls hs peak notch``, f0 in Hz between
 1/600 and 0.45 of the wav's rate, gain_db in [-9, 9] for ``ls hs peak`` and q in [0.1, 8] (``ls hs``: [0.1, 2]; default sqrt(1/2)), as in
 ``--eq hp:80,peak:3000:3:1,hs:10000:4``.
+``--reverb SPEC`` runs the convolution reverb (goofer_amd.reverb) over the track behind the compressor and in front of the
+loudness stage: ``room:RT60_S[:WET_DB[:PREDELAY_MS[:SEED]]]`` for a synthetic room, ``ir:PATH[:WET_DB[:PREDELAY_MS]]`` for a mono
+wav at the output's rate; the impulse response's length and the tail it adds go to stderr, e.g. ``--reverb room:1.2:-10:20``.
 ``Renderer.render_phrase`` is the same for (Source, Request) jobs.
 """
 from __future__ import annotations
@@ -239,7 +242,7 @@ def read_job(path):
 
 
 def render_job(path, out_wav, renderer=None, seed=None, tracker=None, pcm16=True, out_sr=None, limit=None, stats=None, loudness=None,
-               compress=None, eq=None):
+               compress=None, eq=None, reverb=None):
     """``python -m goofer_amd.phrase``: the notes of a job file rendered as one batch and written as one wav.  ``in_file`` is
     resolved like the resampler front end does: ``<stem>_features.goofy`` beside the wav, analysed and cached first when it is
     missing (``trackers.ensure_features_batch``; the tracker: the argument, else ``$GOOFER_TRACKER``).  ``out_sr``: the rate of
@@ -247,7 +250,8 @@ def render_job(path, out_wav, renderer=None, seed=None, tracker=None, pcm16=True
     a dict, receives the limiter's ``peak_in`` and ``min_gain`` (a true-peak limiter's ``true_peak_in`` and ``true_peak_out`` too).  ``loudness``: ``render_phrase``'s (None: the track's level is
     left as it is); with it ``stats`` receives ``lufs_in``, ``momentary_max`` and ``gain``.  ``compress``: ``render_phrase``'s (None:
     no compressor); with it ``stats`` receives ``max_reduction_db``.  ``eq``: ``render_phrase``'s (None: no equaliser); it has no
-    statistic."""
+    statistic.  ``reverb``: ``render_phrase``'s (None: no reverb); with it ``stats`` receives ``reverb_taps``, the impulse
+    response's length, and ``reverb_tail``, the samples it adds to the track."""
     from pathlib import Path
     from . import core, trackers
     from . import sampler as S
@@ -270,11 +274,17 @@ def render_job(path, out_wav, renderer=None, seed=None, tracker=None, pcm16=True
         raise ValueError(f"{path}: no note")
     if seed is None:
         seed = int(np.random.SeedSequence().generate_state(1, dtype=np.uint64)[0])
+    if reverb is not None:
+        from . import reverb as RV
+        reverb = RV.parse(reverb)
+        rv_plan = RV.plan(jobs[0][0].sr if out_sr is None else int(out_sr), [], reverb)
+        if stats is not None:
+            stats.update({"reverb_taps": rv_plan.L, "reverb_tail": rv_plan.added})
     if limit is None and loudness is None and compress is None:
-        track = renderer.render_phrase(jobs, [e for _, e in lines], seed=seed, pcm16=pcm16, out_sr=out_sr, eq=eq)
+        track = renderer.render_phrase(jobs, [e for _, e in lines], seed=seed, pcm16=pcm16, out_sr=out_sr, eq=eq, reverb=reverb)
     else:
         track, st = renderer.render_phrase(jobs, [e for _, e in lines], seed=seed, pcm16=pcm16, out_sr=out_sr, limit=limit, return_stats=True,
-                                           loudness=loudness, compress=compress, eq=eq)
+                                           loudness=loudness, compress=compress, eq=eq, reverb=reverb)
         if stats is not None:
             stats.update(st)
     write_wav(out_wav, track, jobs[0][0].sr if out_sr is None else int(out_sr))
@@ -286,9 +296,9 @@ def main(argv=None) -> int:
     from . import limit as LM
     logging.basicConfig(format="%(message)s", level=logging.INFO)
     argv = list(sys.argv[1:] if argv is None else argv)
-    out_sr = limit = loudness = compress = eq = None
+    out_sr = limit = loudness = compress = eq = reverb = None
     true_peak = False
-    while len(argv) > 2 and argv[0] in ("--rate", "--limit", "--loudness", "--compress", "--true-peak", "--eq"):
+    while len(argv) > 2 and argv[0] in ("--rate", "--limit", "--loudness", "--compress", "--true-peak", "--eq", "--reverb"):
         if argv[0] == "--true-peak":
             true_peak = True
             argv = argv[1:]
@@ -311,6 +321,13 @@ def main(argv=None) -> int:
             except ValueError:
                 break
             argv = argv[2:]
+        elif argv[0] == "--reverb":
+            from . import reverb as RV
+            try:
+                reverb = RV.parse(argv[1])
+            except ValueError:
+                break
+            argv = argv[2:]
         elif argv[0] == "--compress":
             from . import compress as CP
             try:
@@ -326,13 +343,14 @@ def main(argv=None) -> int:
                 limit = LM.CEILING
                 argv = argv[1:]
     if len(argv) != 2 or (true_peak and limit is None):
-        logging.error("Usage:\n  python -m goofer_amd.phrase [--rate HZ] [--eq KIND:F0[:GAIN_DB[:Q]],...] [--compress T:R[:ATTACK:RELEASE[:KNEE[:MAKEUP]]]] [--loudness LUFS] "
+        logging.error("Usage:\n  python -m goofer_amd.phrase [--rate HZ] [--eq KIND:F0[:GAIN_DB[:Q]],...] [--compress T:R[:ATTACK:RELEASE[:KNEE[:MAKEUP]]]] "
+                      "[--reverb room:RT60_S[:WET_DB[:PREDELAY_MS[:SEED]]] | ir:PATH[:WET_DB[:PREDELAY_MS]]] [--loudness LUFS] "
                       "[--limit [DBFS] [--true-peak]] job.txt out.wav")
         return 1
     stats = {}
     try:
         track = render_job(argv[0], argv[1], out_sr=out_sr, limit=LM.Limiter(limit, true_peak=True) if true_peak else limit, stats=stats,
-                           loudness=loudness, compress=compress, eq=eq)
+                           loudness=loudness, compress=compress, eq=eq, reverb=reverb)
     except Exception:                   # noqa: BLE001
         logging.exception("Failed to render")
         return 1
@@ -343,6 +361,9 @@ def main(argv=None) -> int:
         print("Compressor: greatest reduction %.2f dB (threshold %.2f dBFS, ratio %g, attack %g ms, release %g ms, knee %g dB, make-up %g dB)"
               % (stats["max_reduction_db"], compress.threshold_db, compress.ratio, compress.attack_ms, compress.release_ms, compress.knee_db,
                  compress.makeup_db), file=sys.stderr)
+    if reverb is not None:
+        print("Reverb: impulse response of %d taps, wet %g dB, dry %g dB, pre-delay %g ms; the tail adds %d samples"
+              % (stats["reverb_taps"], reverb.wet_db, reverb.dry_db, reverb.predelay_ms, stats["reverb_tail"]), file=sys.stderr)
     if loudness is not None:
         print("Loudness: measured %.2f LUFS (momentary max %.2f), gain %.2f dB (target %.2f LUFS)"
               % (stats["lufs_in"], stats["momentary_max"], 20.0 * math.log10(stats["gain"]) if stats["gain"] > 0.0 else -math.inf, loudness),

@@ -23,6 +23,7 @@ from . import limit as LM
 from . import loudness as LD
 from . import eq as EQ
 from . import rate as RT
+from . import reverb as RV
 from . import sampler as S
 from .device import Context, check_noise_seed, check_phi_seed, default_context, default_params, pcg64_words, row_stride
 
@@ -429,28 +430,30 @@ class Renderer:
         lw = int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", "1")) or 1)
         self.plan_threads = 0 if lw <= 1 else max(1, min(8, (os.cpu_count() or 8) // lw))
 
-    def _finish_settings(self, jobs, who, out_sr, compress, loudness, limit, eq=None):
+    def _finish_settings(self, jobs, who, out_sr, compress, loudness, limit, eq=None, reverb=None):
         """The arguments of the finishing chain, parsed once, as ``_finish`` takes them behind the lengths: (the notes' rate, the
         rate to convert to or None where ``out_sr`` asks for none — None, or the notes' own rate —, compress, loudness, limit,
-        eq), a stage that is not asked for None.  Raises ValueError, in ``who``'s name, where one is asked for and the notes do
+        eq, reverb), a stage that is not asked for None.  Raises ValueError, in ``who``'s name, where one is asked for and the notes do
         not share one sample rate."""
         chain = (None if compress is None else CP.parse(compress), None if loudness is None else LD.parse(loudness),
-                 None if limit is None else LM.parse(limit), None if eq is None else EQ.parse(eq))
+                 None if limit is None else LM.parse(limit), None if eq is None else EQ.parse(eq), None if reverb is None else RV.parse(reverb))
         rates = {int(src.sr) for src, _ in jobs}
-        for what, asked in zip(("out_sr converts", "limit takes", "loudness takes", "compress takes", "eq takes"),
-                               (out_sr, limit, loudness, compress, eq)):
+        for what, asked in zip(("out_sr converts", "limit takes", "loudness takes", "compress takes", "eq takes", "reverb takes"),
+                               (out_sr, limit, loudness, compress, eq, reverb)):
             if asked is not None and len(rates) != 1:
                 raise ValueError(f"{who}: {what} notes that share one sample rate")
         if out_sr is not None and (int(out_sr) != out_sr or int(out_sr) < 1):
             raise ValueError(f"{who}: out_sr is a whole number of Hz")
         if eq is not None:                                     # the bands against the rate they will run at, before anything is rendered
             EQ.plan(jobs[0][0].sr if out_sr is None else int(out_sr), [], chain[3])
+        if reverb is not None:                                 # the impulse response and the pre-delay against that rate, likewise
+            RV.plan(jobs[0][0].sr if out_sr is None else int(out_sr), [], chain[4])
         return (jobs[0][0].sr, None if out_sr is None or int(out_sr) in rates else int(out_sr), *chain)
 
-    def _finish(self, x, d_off, lengths, sr, to_sr, compress, loudness, limit, eq=None, true_peak_out=False):
+    def _finish(self, x, d_off, lengths, sr, to_sr, compress, loudness, limit, eq=None, reverb=None, true_peak_out=False):
         """The finishing chain over the signals of ``lengths`` samples lying back to back in the device tensor ``x`` at ``sr``
-        (``d_off``: their CSR on the device, or None): convert to ``to_sr``, eq, compress, loudness, limit, each with its parsed
-        settings; a stage whose setting is None launches nothing and allocates nothing.  Returns (the tensor, the signals'
+        (``d_off``: their CSR on the device, or None): convert to ``to_sr``, eq, compress, reverb, loudness, limit, each with its
+        parsed settings (the reverb's longer signals go on like the converter's); a stage whose setting is None launches nothing and allocates nothing.  Returns (the tensor, the signals'
         lengths in it, the statistics as the stages return them, device tensors: ``max_reduction``; ``loud``, ``gain``;
         ``peak_in``, ``min_gain``, and with ``true_peak_out`` behind a true-peak limiter ``true_peak_out``)."""
         lengths, stats = np.asarray(lengths, dtype=np.int64), {}
@@ -461,6 +464,9 @@ class Renderer:
             x = self.ctx.eq(x, None, EQ.plan(sr, lengths, eq))
         if compress is not None:
             x, stats["max_reduction"], _ = self.ctx.compress(x, None, CP.plan(sr, lengths, compress))
+        if reverb is not None:
+            plan = RV.plan(sr, lengths, reverb)
+            x, lengths = self.ctx.reverb(x, None, plan, reverb.spectra(self.ctx, sr)), np.diff(plan.out_off)
         if loudness is not None:
             x, stats["loud"], stats["gain"], _ = self.ctx.loudness(x, None, LD.plan(sr, lengths), *loudness)
         if limit is not None:
@@ -471,7 +477,7 @@ class Renderer:
         return x, lengths, stats
 
     def render(self, jobs, seed: int = 0, phi_seeds=None, return_parts: bool = False, noise_seeds=None, out_sr=None, limit=None,
-               loudness=None, compress=None, eq=None):
+               loudness=None, compress=None, eq=None, reverb=None):
         """jobs: list of (Source, Request).  Returns a list of fp32 arrays (the mix the reference writes to
         out.wav); with ``return_parts`` also a dict of device-side intermediates for tests.
         ``phi_seeds``: per-note seeds for INJECTED phases (parity with a seeded reference run: numpy's stream of each seed,
@@ -496,10 +502,15 @@ class Renderer:
         front of the loudness stage.
         ``eq``: None, a sequence of ``goofer_amd.eq.Band`` objects or ``(kind, f0_hz[, gain_db[, q]])`` tuples, or the string
         ``kind:f0[:gain_db[:q]],...``: every note through the parametric equaliser on the device (goofer_amd.eq; the whole batch
-        in one goofer_eq), after the conversion and in front of the compressor."""
+        in one goofer_eq), after the conversion and in front of the compressor.
+        ``reverb``: None, a ``goofer_amd.reverb.Reverb``, a tuple ``(ir[, wet_db[, dry_db[, predelay_ms[, tail]]]])`` with ``ir`` an
+        array of taps or a ``reverb.Room``, or the string ``room:RT60_S[:WET_DB[:PREDELAY_MS[:SEED]]]`` / ``ir:PATH[:WET_DB[:
+        PREDELAY_MS]]``: every note through the convolution reverb on the device (goofer_amd.reverb; the whole batch in one
+        goofer_reverb), behind the compressor and in front of the loudness stage; with the tail (the default) every note comes
+        back pre-delay + taps - 1 samples longer."""
         if not jobs:
             return []
-        chain = self._finish_settings(jobs, "render", out_sr, compress, loudness, limit, eq)
+        chain = self._finish_settings(jobs, "render", out_sr, compress, loudness, limit, eq, reverb)
         prep = self.prepare(jobs, phi_seeds=phi_seeds, trim_rows=not return_parts, noise_seeds=noise_seeds)   # tests look at the whole assembled envelope
         out = self.run(prep, seed=seed, keep_stems=return_parts)
         mix, lens, _ = self._finish(out["mix"], prep["offsets"]["d_s"], np.diff(np.asarray(prep["sample_off"], dtype=np.int64)), *chain)
@@ -513,7 +524,7 @@ class Renderer:
         return res
 
     def render_phrase(self, jobs, entries, seed: int = 0, phi_seeds=None, noise_seeds=None, pcm16: bool = False, out_sr=None, limit=None,
-                      return_stats: bool = False, loudness=None, compress=None, eq=None):
+                      return_stats: bool = False, loudness=None, compress=None, eq=None, reverb=None):
         """The notes of ``jobs`` rendered as one batch and assembled into one track on the device: what a ``wavtool`` does with
         the notes ``render`` returns, without bringing them home first (goofer_amd.phrase; goofer_phrase_mix).  ``entries``:
         the phrase in order, one ``phrase.Entry`` (or its wavtool argument string ``stp length p1 p2 p3 v1 v2 v3 v4 [ovr [p4
@@ -536,17 +547,21 @@ class Renderer:
         ``loudness`` ``lufs_in``, the track's integrated loudness in front of the scaling, ``momentary_max``, its greatest
         momentary loudness, and ``gain``, the factor it was scaled by (Python floats).  ``eq``: None or what ``render``
         takes: the track through the parametric equaliser on the device (goofer_amd.eq), behind the conversion and in front of
-        the compressor — mix, convert, eq, compress, loudness, limit, then int16; it has no statistic."""
+        the compressor — mix, convert, eq, compress, loudness, limit, then int16; it has no statistic.  ``reverb``: None or what
+        ``render`` takes: the track through the convolution reverb on the device (goofer_amd.reverb), behind the compressor, so
+        that the tail is not pumped, and in front of loudness and the limiter, so that their targets hold for what is written —
+        mix, convert, eq, compress, reverb, loudness, limit, then int16; with the tail (the default) the track is pre-delay +
+        taps - 1 samples longer; it has no statistic."""
         from . import phrase as P
         if return_stats and limit is None and loudness is None and compress is None:
             raise ValueError("render_phrase: return_stats reports the statistics of the limiter, the loudness stage and the compressor and needs "
-                             "limit, loudness or compress (eq has no statistic)")
+                             "limit, loudness or compress (eq and reverb have no statistic)")
         entries = [e if isinstance(e, P.Entry) else P.Entry.parse(e) for e in entries]
         if not jobs:
             raise ValueError("render_phrase: a phrase without a note has no sample rate")
         if len({src.sr for src, _ in jobs}) != 1:
             raise ValueError("render_phrase: the notes of a phrase share one sample rate")
-        chain = self._finish_settings(jobs, "render_phrase", out_sr, compress, loudness, limit, eq)
+        chain = self._finish_settings(jobs, "render_phrase", out_sr, compress, loudness, limit, eq, reverb)
         prep = self.prepare(jobs, phi_seeds=phi_seeds, noise_seeds=noise_seeds)
         plan = P.plan_phrase(entries, np.diff(np.asarray(prep["sample_off"], dtype=np.int64)), jobs[0][0].sr)
         out = self.run(prep, seed=seed)

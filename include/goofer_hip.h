@@ -1204,6 +1204,83 @@ int goofer_host_eq_plan(int sr, const int32_t *kind, const double *f0_hz, const 
 int goofer_eq(goofer_ctx *ctx, const float *x, const int64_t *in_off, int n, int64_t total, int K, const double *coef, const double *mats,
               const int32_t *tiles, int64_t n_tiles, float *out, void *scratch, int64_t *scratch_bytes, void *stream);
 
+/* ---- convolution reverb ---------------------------------------------------------------------------------------------------
+ * Every other stage of the finishing chain acts on level, spectrum or peaks; this one gives the voice a room: every signal of a
+ * ragged batch convolved with one impulse response (the IR; a tap is one of its coefficients), behind the compressor, so that the
+ * tail is not pumped, and in front of the loudness stage and the limiter, so that their targets hold for what is written (mix,
+ * rate conversion, equaliser, compressor, reverb, loudness, limiter, int16).  The definition is this project's own (restated in
+ * numpy by tests/reverb_ref.py).  For a signal x of n samples and the IR h of L taps, shared by the batch:
+ *   c[i] = sum_{k < L} h[k] x[i - pre - k]          (x is 0 outside [0, n))
+ *   y[i] = dry x[i] + wet c[i]                      for 0 <= i < n_out
+ *   n_out = n + (pre + L - 1 if tail else 0)        (and 0 for n == 0)
+ * dry and wet are linear gains, pre is the pre-delay in whole samples, tail keeps the decay past the signal's end.  x, h and y
+ * are fp32.  Signals never bleed into each other, and a signal gets the same bits alone as at any position in any batch, on every
+ * run: no atomics, and every sum has one order.  Ranges, anything else refused (GOOFER_EINVAL): 1 <= L <= GOOFER_REVERB_MAX_TAPS
+ * (2^18: 5.4 s at 48 kHz); 0 <= pre <= GOOFER_REVERB_MAX_PREDELAY (2^16); a sample rate that is a whole number of Hz in
+ * [GOOFER_REVERB_MIN_SR, GOOFER_REVERB_MAX_SR] (the host planner's; it only converts nothing, the rate is what the settings were
+ * given at); dry, wet and every tap finite; n_out < 2^31.
+ *
+ * Scheme: uniformly partitioned overlap-save.  The block is B = GOOFER_REVERB_BLOCK samples, the transform 2 B real points (the
+ * complex B-point transform a 64-lane wave owns in csrc/fft_core.h, rectangular window, zeros outside the signal), and the IR is
+ * cut into P = ceil(L / B) partitions, at most 256.  Blocks are counted from each signal's own start: block j of a signal is the
+ * transform X[j] of x[(j - 1) B - pre .. (j + 1) B - pre), the pre-delay an index shift; Y[b] = sum_p X[b - p] H[p], summed over
+ * p descending (b - P + 1 .. b ascending) for every block wherever it lies; the last B samples of the inverse transform of Y[b]
+ * are c[b B .. (b + 1) B).  A signal has ceil(n_out / B) blocks.  A spectrum row is B complex numbers: bins 1 .. B - 1, and in
+ * slot 0 the two real bins (0 and B) as one pair, multiplied element by element.  wet == 0 runs no transform: y = dry x, the
+ * input's bits for dry == 1, and the tail exact zeros.
+ *
+ * Tolerance: |y[i] - y_float64[i]| <= GOOFER_REVERB_TOL max_i |y_float64[i]| per signal.  The constant is measured, not chosen:
+ * a numpy model of the scheme in float32 / complex64 (tests/reverb_ref.py, `tiled`: the same blocks, partitions and order over
+ * p) is run against the float64 restatement on the cases of tests/test_gpu_reverb.py, and the constant is four times the worst
+ * max|err| / max|ref| per signal, rounded up to a power of two (tests/test_reverb_ref.py does it again on every run); the factor
+ * covers the kernels' other FFT factorisation and their fused multiply-adds. */
+#define GOOFER_REVERB_BLOCK 1024
+#define GOOFER_REVERB_RUN 32                /* blocks of one signal per entry of the run table: one workgroup */
+#define GOOFER_REVERB_MAX_TAPS 262144
+#define GOOFER_REVERB_MAX_PREDELAY 65536
+#define GOOFER_REVERB_MIN_SR 8000
+#define GOOFER_REVERB_MAX_SR 192000
+#define GOOFER_REVERB_TOL 0x1p-19
+#define GOOFER_REVERB_IR_HEAD 12800         /* bytes in front of the partitions' spectra: the transform's tables and the live bytes */
+#define GOOFER_REVERB_IR_BYTES(L) (GOOFER_REVERB_IR_HEAD + 8 * GOOFER_REVERB_BLOCK * (((L) + GOOFER_REVERB_BLOCK - 1) / GOOFER_REVERB_BLOCK))
+
+/* Host side (no device, no handle): for n signals whose samples lie back to back with the CSR in_off[n + 1] (non-decreasing), an
+ * IR of L taps, a pre-delay of pre samples and tail (0 / 1): out_off[n + 1], the CSR of the outputs (n_out per signal);
+ * blk_off[n + 1], the CSR of the signals' blocks (ceil(n_out / GOOFER_REVERB_BLOCK) each: a signal's spectrum rows); and the run
+ * table: need[0] triples of int32 (signal, first block of the run, blocks: up to GOOFER_REVERB_RUN), ascending, every block of
+ * every signal in exactly one run.  Returns 0 with everything written; 1 when runs_cap (in triples) < need[0] (only need is
+ * valid: grow, call again); GOOFER_EINVAL for what the definition refuses (sr, L, pre, an output of 2^31 samples or more), a null
+ * argument (in_off may be null when n == 0, runs when runs_cap == 0), a negative count or capacity, offsets that decrease. */
+int goofer_host_reverb_plan(int sr, const int64_t *in_off, int n, int L, int pre, int tail, int64_t *out_off, int64_t *blk_off,
+                            int32_t *runs, int64_t runs_cap, int64_t *need);
+
+/* The IR's spectra (reverb.hip), once per IR: h is a HOST array of L taps, ir a device buffer of at least
+ * GOOFER_REVERB_IR_BYTES(L) bytes, 16-byte aligned, that the caller keeps and passes to every goofer_reverb with this L.  It
+ * receives the transform's tables, one "live" byte per partition (0: every tap of the partition is zero; its row is exact zeros
+ * and the multiply-accumulate skips it) and H[p], the transform of h[p B .. (p + 1) B) and B zeros, p < ceil(L / B).  The taps
+ * are copied on `stream`, which is synchronised once (h is the caller's again on return); the transforms run asynchronously
+ * behind it.  GOOFER_EINVAL for L outside [1, GOOFER_REVERB_MAX_TAPS], a tap that is not finite, a null or misaligned pointer,
+ * a buffer that is too short. */
+int goofer_reverb_ir(goofer_ctx *ctx, const float *h, int L, void *ir, int64_t ir_bytes, void *stream);
+
+/* The reverb (reverb.hip): out[out_off[i] .. out_off[i+1]) = y of signal x[in_off[i] .. in_off[i+1]), every sample stored exactly
+ * once, the tail included.  x, in_off, out_off, blk_off ([n + 1] each), runs and out are device arrays of the caller, the
+ * tables those of goofer_host_reverb_plan for the same in_off, L, pre and tail; total = in_off[n], total_out = out_off[n],
+ * total_blocks = blk_off[n]; ir: goofer_reverb_ir's buffer for the same L (not read when wet == 0).  Three launches in stream
+ * order, and no workgroup ever waits for another: (A) a wave per block transforms its 2 B samples of x; (B) a workgroup per slice
+ * of 64 bins stages that slice of every H[p] in LDS once and walks runs with it (256 threads and a run at a time up to 64
+ * partitions, 1024 threads and four runs at a time above), a wave keeping eight output blocks' sums in registers and streaming
+ * the input spectra past them once; (C) a wave per block transforms back and stores dry x + wet c.  Both spectra (8 bytes a block
+ * sample each) lie in the caller's scratch, by the caller-scratch protocol: with scratch NULL the size goes to *scratch_bytes
+ * and nothing runs.  Blocks read x again, so `out` must not overlap x.  Asynchronous on `stream`.  n == 0 or total_out == 0:
+ * nothing is launched.  GOOFER_EINVAL, with nothing launched, for a setting outside the definition's ranges, a null pointer (all
+ * arrays may be null when n == 0 or total_out == 0; ir when wet == 0), a negative count, counts that are not a geometry of the
+ * planner, x, runs or out not 4-byte aligned, the others not 8-byte aligned, an out that overlaps x, or a scratch block that is
+ * too short. */
+int goofer_reverb(goofer_ctx *ctx, const float *x, const int64_t *in_off, int n, int64_t total, const void *ir, int L, int pre, int tail,
+                  float dry, float wet, const int64_t *out_off, const int64_t *blk_off, int64_t total_blocks, const int32_t *runs,
+                  int64_t n_runs, int64_t total_out, float *out, void *scratch, int64_t *scratch_bytes, void *stream);
+
 /* ---- measurement / test hooks --------------------------------------------------------------- */
 
 /* HIP-event timing of every stage of goofer_synth_batch on the caller's stream: begin() arms up to
@@ -1256,6 +1333,8 @@ const char *goofer_profile_stage_name_ex(const goofer_ctx *ctx, int stage);   /*
  *               there, so the two agree within rounding (and bit for bit wherever the identity property holds).
  *   "compress_store" 0 (default): every pass of goofer_compress computes xl again from x; 1: the first pass writes xl (float64
  *               [total], more scratch: ask for the size with the option set) and the other two read it.  Same bits.
+ *   "reverb_skip" 1 (default): goofer_reverb's multiply-accumulate leaves out a partition of the impulse response whose taps are
+ *               all zero (its "live" byte); 0: every partition is multiplied.  Same bits on finite input.
  *   "walk_run"  0 (default): the four frame walkers (k_noise_stems, k_harm_stem, k_irfft_ola3, k_irfft_ola1) get the frames per
  *               wave that fill the device a whole number of times: from a floor of 32 frames (8 halos where the halo
  *               (n_fft - 1) / hop is above 4) to 128, k_irfft_ola1 256; a batch leaves the floor only with tens of thousands of
