@@ -200,9 +200,14 @@ int launch_knot_decode(goofer_ctx *ctx, const uint16_t *knots, int K, int64_t ro
 // complex row of the 5-tap blur and, only when the batch may warp (`warp_rows`; the caller's goofer_batch.no_warp hint turns
 // them off), the warp's two fp32 rows: 45 KB instead of 66 KB per workgroup at n_fft 2048.
 __host__ __device__ static inline int harm_shape_tab_floats(int n_bins) { return (n_bins + 4) & ~3; }
+// floats per fp32 warp row: n_bins and the pad element warp_row's fp32 lerp writes behind them (cur[n_bins]), rounded up to
+// an even count (the next wave's complex row stays 8-byte aligned).  An even n_bins takes two floats more, not none: without
+// them the pad of a wave's second row is the real part of bin 0 of the NEXT wave's blur row (behind the last wave: past the
+// allocation).
+__host__ __device__ static inline int harm_shape_row_floats(int n_bins) { return (n_bins + 2) & ~1; }
 __host__ __device__ static inline size_t harm_shape_lds(int n_bins, bool warp_rows)
 {
-    const int rowf = (n_bins + 1) & ~1;
+    const int rowf = harm_shape_row_floats(n_bins);
     return sizeof(float) * 3 * harm_shape_tab_floats(n_bins) + sizeof(float2) * ROWS_PER_BLOCK * (n_bins + (warp_rows ? rowf : 0));
 }
 
@@ -236,7 +241,7 @@ __global__ __launch_bounds__(256, ITERS <= 9 ? 4 : (ITERS <= 17 ? 3 : 2)) void k
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int64_t f = (int64_t)blockIdx.x * ROWS_PER_BLOCK + wave;
     if (f >= total_frames) return;
-    const int rowf = (n_bins + 1) & ~1;                           // floats per fp32 row (even)
+    const int rowf = harm_shape_row_floats(n_bins);               // floats per fp32 row (even, with the pad element)
     float2 *r = reinterpret_cast<float2 *>(t_br + tabf) + (size_t)wave * (n_bins + (warp_rows ? rowf : 0));
     float *ra = reinterpret_cast<float *>(r + n_bins), *rb = ra + rowf;   // (only with warp_rows)
 

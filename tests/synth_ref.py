@@ -432,7 +432,10 @@ def judge(stage, got, truth, *refs, factor=3.0):
 # the matrix of notes, shared by tests/test_synth_ref.py and tests/test_gpu_synth_stages.py
 # ---------------------------------------------------------------------------------------------
 GEOMETRIES = [(44100, 1024, 256), (22050, 512, 128), (44100, 2048, 512), (96000, 2048, 96), (44100, 768, 192), (44100, 1000, 250),
-              (48000, 4096, 1024)]
+              (48000, 4096, 1024),
+              # the transform forms the seven above leave out (csrc/fft.hip, with_transform): Bluestein at L = 256 / 512 / 2048 on a wave,
+              # at L = 4096 on the workgroup, and the wave's native 768 points
+              (16000, 130, 40), (22050, 320, 80), (44100, 2046, 512), (48000, 3000, 750), (44100, 1536, 384)]
 CROSSING = ([1.3, 0.8, 1.1, 0.9], [1.5, 0.6, 0.7, 1.4], [0.7, 1.3, 1.3, 0.6])
 
 

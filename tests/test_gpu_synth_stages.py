@@ -23,6 +23,14 @@ the separate kernels run):
   k_irfft_ola3<256>                   (22050, 512, 128)
   k_irfft_ola1 + k_frame_skip         (44100, 2048, 512), (96000, 2048, 96: hop != n_fft / 4)
   separate kernels: factor three      (44100, 768, 192); Bluestein (44100, 1000, 250); workgroup transform (48000, 4096, 1024)
+  ... and the other forms of with_transform (csrc/fft.hip), each through the separate kernels with `frames` judged:
+      bluestein_256    (16000, 130, 40)     wave, Bluestein L = 256 (66 bins: an even count)
+      bluestein_512    (22050, 320, 80)     wave, Bluestein L = 512
+      bluestein_2048   (44100, 2046, 512)   wave, Bluestein L = 2048, 32 points per lane (1024 bins: an even count)
+      bluestein_wg     (48000, 3000, 750)   workgroup, Bluestein L = 4096, tables re-read per frame
+      radix3_1536      (44100, 1536, 384)   wave, native 768 points (12-point first pass)
+  Every geometry above that is not (.., 1024, 256) or n_fft 2048 reports the stage names of the one-kernel overlap-add (OLA:
+  the names follow the option, fused_ola 1) and runs the separate transforms + k_ola3_gains: the `frames` view is written.
 The views env_harm (spectra routes) and env_noise (every route) are carved but never written: the warp and the sigma-1.75 blur are
 folded into k_harm_shape / k_noise_spectra, so those two are judged through S_harm and S_uv (|S_uv| = env_noise bin by bin).
 
@@ -97,6 +105,33 @@ arithmetic (the oracle's too) makes exactly zero, E_ref = e_gpu = 1.
       note_mag  2.1e-07 / 2.1e-07 (0.42)   frames    1.6e-07 / 2.4e-07 (0.73)   harm      1.5e-07 / 2.7e-07 (0.97)
       uv        1.5e-07 / 2.7e-07 (0.97)   bre       2.2e-07 / 3.8e-07 (1.15)   rec       1.7e-07 / 3.1e-07 (1.16)
       mix       2.0e-07 / 3.3e-07 (1.02)   note_peak 1.5e-07 / 1.9e-07 (0.47)
+The five transform forms added later (the largest ratio is 2.32, still inside the factor 3 with both yardsticks of synth_ref:
+no third yardstick was needed for the Bluestein stages and no factor was raised):
+  16000/130/40: Bluestein L = 256
+      S_harm    5.5e-07 / 8.8e-07 (1.39)   S_uv      8.9e-08 / 3.3e-07 (2.32)   S_breath  6.3e-08 / 2.5e-07 (2.12)
+      note_mag  2.6e-07 / 2.2e-07 (0.36)   frames    2.6e-07 / 4.4e-07 (1.24)   harm      1.2e-07 / 3.1e-07 (1.62)
+      uv        2.1e-07 / 3.5e-07 (1.12)   bre       1.8e-07 / 3.4e-07 (1.23)   rec       1.2e-07 / 2.7e-07 (1.23)
+      mix       1.4e-07 / 3.3e-07 (1.53)   note_peak 2.1e-07 / 3.1e-07 (0.89)
+  22050/320/80: Bluestein L = 512
+      S_harm    3.3e-07 / 3.4e-07 (0.65)   S_uv      5.4e-08 / 2.3e-07 (2.11)   S_breath  5.4e-08 / 2.3e-07 (2.11)
+      note_mag  2.8e-07 / 1.9e-07 (0.27)   frames    5.7e-07 / 9.8e-07 (1.50)   harm      1.8e-07 / 2.9e-07 (0.96)
+      uv        1.7e-07 / 3.4e-07 (1.34)   bre       1.4e-07 / 2.9e-07 (1.15)   rec       1.4e-07 / 2.7e-07 (1.13)
+      mix       1.4e-07 / 2.5e-07 (0.94)   note_peak 1.5e-07 / 2.2e-07 (0.71)
+  44100/2046/512: Bluestein L = 2048
+      S_harm    2.6e-07 / 3.3e-07 (0.81)   S_uv      8.6e-08 / 2.5e-07 (1.54)   S_breath  1.2e-07 / 3.2e-07 (1.66)
+      note_mag  1.8e-07 / 1.7e-07 (0.30)   frames    5.4e-07 / 8.9e-07 (1.42)   harm      2.0e-07 / 3.4e-07 (1.13)
+      uv        2.1e-07 / 3.9e-07 (1.27)   bre       2.1e-07 / 3.3e-07 (1.02)   rec       1.4e-07 / 3.4e-07 (1.62)
+      mix       1.8e-07 / 3.4e-07 (1.19)   note_peak 1.7e-07 / 2.7e-07 (0.88)
+  48000/3000/750: workgroup, Bluestein L = 4096
+      S_harm    1.9e-07 / 3.5e-07 (1.23)   S_uv      9.8e-08 / 2.8e-07 (1.58)   S_breath  1.1e-07 / 2.7e-07 (1.38)
+      note_mag  1.9e-07 / 2.4e-07 (0.64)   frames    2.3e-07 / 3.4e-07 (0.95)   harm      1.7e-07 / 2.9e-07 (1.07)
+      uv        2.6e-07 / 3.8e-07 (1.01)   bre       2.2e-07 / 3.4e-07 (1.01)   rec       2.0e-07 / 3.4e-07 (1.06)
+      mix       1.5e-07 / 3.0e-07 (1.21)   note_peak 2.2e-07 / 2.9e-07 (0.78)
+  44100/1536/384: native 768 points
+      S_harm    3.8e-07 / 5.1e-07 (1.02)   S_uv      9.8e-08 / 2.6e-07 (1.45)   S_breath  1.2e-07 / 2.7e-07 (1.31)
+      note_mag  3.3e-07 / 2.1e-07 (0.27)   frames    6.2e-07 / 5.9e-07 (0.76)   harm      2.0e-07 / 2.8e-07 (0.82)
+      uv        2.7e-07 / 3.6e-07 (0.89)   bre       2.1e-07 / 3.0e-07 (0.86)   rec       1.5e-07 / 2.6e-07 (0.98)
+      mix       2.0e-07 / 3.0e-07 (0.90)   note_peak 2.7e-07 / 2.0e-07 (0.31)
 """
 import numpy as np
 import pytest
@@ -131,6 +166,11 @@ ROUTES = {
     "radix3": ((44100, 768, 192), {}, OLA, "separate", False),
     "bluestein": ((44100, 1000, 250), {}, OLA, "separate", False),
     "workgroup": ((48000, 4096, 1024), {}, OLA, "separate", False),
+    "bluestein_256": ((16000, 130, 40), {}, OLA, "separate", False),
+    "bluestein_512": ((22050, 320, 80), {}, OLA, "separate", False),
+    "bluestein_2048": ((44100, 2046, 512), {}, OLA, "separate", False),
+    "bluestein_wg": ((48000, 3000, 750), {}, OLA, "separate", False),
+    "radix3_1536": ((44100, 1536, 384), {}, OLA, "separate", False),
 }
 DEFAULTS = {"td_blur": 1, "skip_zero": 1, "stems": 1, "fused_ola": 1}
 BATCHES = ("main", "sigma4", "sigma2000", "tiny")
@@ -166,9 +206,10 @@ def _params(notes):
     return par
 
 
-def _run(ctx, geo, notes, sigma, views=True, profile=False, seed=None):
+def _run(ctx, geo, notes, sigma, views=True, profile=False, seed=None, device=False):
     """One goofer_synth_batch over ``notes``; the outputs and (views) the debug views as host arrays.  ``seed``: no phases are
-    injected, the noise walker draws its own (Philox) under this seed."""
+    injected, the noise walker draws its own (Philox) under this seed.  ``device``: the five outputs stay device tensors (a
+    caller that compares them there: tests/test_gpu_repeat.py)."""
     from goofer_amd.device import GooferError
     sr, n_fft, hop = geo
     nb = n_fft // 2 + 1
@@ -187,7 +228,7 @@ def _run(ctx, geo, notes, sigma, views=True, profile=False, seed=None):
         torch.cuda.synchronize()
     except RuntimeError as e:                                 # GooferError or torch's device error: nothing more is started on this GPU
         pytest.exit("goofer_synth_batch failed on the device: %r" % (e,), returncode=3)
-    res = {k: out[k].cpu().numpy() for k in ("harm", "uv", "bre", "rec", "mix")}
+    res = {k: out[k] if device else out[k].cpu().numpy() for k in ("harm", "uv", "bre", "rec", "mix")}
     if profile:
         ctx.profile_end()
         res["names"] = ctx.profile_stage_names()

@@ -289,7 +289,8 @@ def test_judge_rejects_planted_fault_and_the_rms_bound_accepts_it(fault):
 def test_plain_transform_is_a_transform():
     """The plain fp32 transform against numpy's float64 one, every size of the matrix, and its error next to pocketfft's."""
     rng = np.random.default_rng(5)
-    for n in (512, 768, 1000, 1024, 2048, 4096):
+    assert {g[1] for g in SR.GEOMETRIES} == {130, 320, 512, 768, 1000, 1024, 1536, 2046, 2048, 3000, 4096}
+    for n in (130, 320, 512, 768, 1000, 1024, 1536, 2046, 2048, 3000, 4096):
         x = rng.standard_normal((n, 8)).astype(F32)
         X = np.fft.rfft(x.astype(np.float64), axis=0)
         pk = np.max(np.abs(X), axis=0)
