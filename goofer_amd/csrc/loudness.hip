@@ -6,29 +6,23 @@
 // The K-weighting filter is a recurrence of order 4 in fp64, state s = (u1, u2, v1, v2).  It is linear: a run of m samples from
 // state s ends in A^m s + e, e the end state of the same run from zero.  So a long signal is cut into tiles of 4096 samples, a
 // tile into 256 runs of 16, and the states are carried by scans whose operator is "multiply by a constant matrix, add": all
-// elements of a scan level share one matrix, A^(16 * 2^k), made on the host.  Four launches in stream order; no workgroup
-// waits for another one, and every sum has a fixed order:
+// elements of a scan level share one matrix, A^(16 * 2^k), made on the host.  The tiles, the scan and the carry from tile to
+// tile are those of tile_scan.h; this file holds the filter, its element and the statistics.  Four launches in stream order; no
+// workgroup waits for another one, and every sum has a fixed order:
 //   A  k_loud_ends    a workgroup per tile: runs from zero, a workgroup scan, the tile's zero-state end state to scratch
 //   B  k_loud_carry   a workgroup per signal: the tiles' end states into the tiles' true start states, 4096 tiles per scan
 //   C  k_loud_energy  a workgroup per tile: the scan again with the start state put into run 0, every run again from its true
 //                     state, v^2 summed per segment; one partial sum per (tile, segment it touches) into a slot of its own
 //   D  k_loud_stats   a workgroup per signal: the slots into E[k] in ascending tile order, blocks, gates, L, momentary max, g
 // and k_loud_apply, a per-sample kernel over the ragged batch.
-#include "launchers.h"
+#include "tile_scan.h"
 
-#define LD_THREADS 256
-#define LD_SPT GOOFER_LOUDNESS_SPT
-#define LD_T GOOFER_LOUDNESS_TILE
 #define LD_SLOTS GOOFER_LOUDNESS_SLOTS
-#define LD_LEVELS 8                                   // 2^8 runs in a tile
-static_assert(LD_T == LD_THREADS * LD_SPT && LD_SPT == 16 && (1 << LD_LEVELS) == LD_THREADS, "one workgroup of 256 runs of 16 per tile");
-#define LD_RUN 16                                     // tiles a thread of k_loud_carry walks
-static_assert(GOOFER_LOUDNESS_MATS == LD_LEVELS + 4 + LD_LEVELS, "A^16 .. A^2048 inside a tile, A^4096 a tile, A^(4096 * 16 * 2^k) over the runs of 16 tiles");
-static_assert(LD_T / (GOOFER_LOUDNESS_MIN_SR / 10) + 2 <= LD_SLOTS, "segments a tile can touch");
-#define LD_XPAD (LD_T + 16 + (LD_T + 16) / 16)       // the tile and the 16 samples in front of it, one pad word per 16
-
-// entry q of the staged samples (q = 16 + position in the tile): a thread's 16 consecutive words at a lane stride of 17
-__device__ __forceinline__ int ld_idx(int q) { return q + (q >> 4); }
+static_assert(GOOFER_LOUDNESS_TILE == TS_T && GOOFER_LOUDNESS_SPT == TS_SPT && GOOFER_LOUDNESS_LEVELS == TS_LEVELS && GOOFER_LOUDNESS_RUN_TILES == TS_RUN,
+              "the tiling of tile_scan.h");
+static_assert(GOOFER_LOUDNESS_MATS == TS_LEVELS + 4 + TS_LEVELS && TS_RUN == 16, "A^16 .. A^2048 inside a tile, A^4096 a tile, A^(4096 * 16 * 2^k) over the runs of 16 tiles");
+static_assert(TS_T / (GOOFER_LOUDNESS_MIN_SR / 10) + 2 <= LD_SLOTS, "segments a tile can touch");
+#define LD_XPAD TS_XPAD(16)                           // the tile and the 16 samples in front of it
 
 __device__ __forceinline__ void ld_matvec(const double *__restrict__ M, const double (&s)[4], double (&r)[4])
 {
@@ -36,26 +30,17 @@ __device__ __forceinline__ void ld_matvec(const double *__restrict__ M, const do
     for (int i = 0; i < 4; ++i) r[i] = ((M[4 * i] * s[0] + M[4 * i + 1] * s[1]) + M[4 * i + 2] * s[2]) + M[4 * i + 3] * s[3];
 }
 
-// the tile's samples [t0, t0 + T) and the two in front of them into LDS (coalesced); 0 outside the signal
-__device__ __forceinline__ void ld_stage(const float *__restrict__ xs, int64_t len, int64_t t0, float *__restrict__ s_x)
-{
-    for (int q = 14 + threadIdx.x; q < LD_T + 16; q += LD_THREADS) {
-        const int64_t p = t0 - 16 + q;
-        s_x[ld_idx(q)] = p >= 0 && p < len ? xs[p] : 0.0f;
-    }
-}
-
 // the thread's 16 samples through both biquads from state s (left in s); ENERGY: v^2 of the first `bnd` samples summed into
 // e0, of the others into e1, in sample order
 template <bool ENERGY>
 __device__ __forceinline__ void ld_run(const float *__restrict__ s_x, const double *__restrict__ c, double (&s)[4], int bnd, double &e0, double &e1)
 {
-    const int q0 = 16 + threadIdx.x * LD_SPT;
-    double x1 = (double)s_x[ld_idx(q0 - 1)], x2 = (double)s_x[ld_idx(q0 - 2)];
+    const int q0 = 16 + threadIdx.x * TS_SPT;
+    double x1 = (double)s_x[ts_idx(q0 - 1)], x2 = (double)s_x[ts_idx(q0 - 2)];
     double u1 = s[0], u2 = s[1], v1 = s[2], v2 = s[3];
 #pragma unroll
-    for (int e = 0; e < LD_SPT; ++e) {
-        const double x = (double)s_x[ld_idx(q0 + e)];
+    for (int e = 0; e < TS_SPT; ++e) {
+        const double x = (double)s_x[ts_idx(q0 + e)];
         const double u = (((c[0] * x + c[1] * x1) + c[2] * x2) - c[3] * u1) - c[4] * u2;
         const double v = (((c[5] * u + c[6] * u1) + c[7] * u2) - c[8] * v1) - c[9] * v2;
         x2 = x1, x1 = x, u2 = u1, u1 = u, v2 = v1, v1 = v;
@@ -66,205 +51,128 @@ __device__ __forceinline__ void ld_run(const float *__restrict__ s_x, const doub
     s[0] = u1, s[1] = u2, s[2] = v1, s[3] = v2;
 }
 
-// Inclusive scan over the workgroup's runs: v_j <- A^(16 * 2^k) v_(j - 2^k) + v_j for k = 0 .. 7.  Returns the buffer
-// (of s_sc[2]) that holds the result, component-major: s_sc[b][4 * 256].
-__device__ __forceinline__ int ld_scan(double (&v)[4], const double *__restrict__ mats, double (*s_sc)[4 * LD_THREADS])
+// r = M s + v
+__device__ __forceinline__ void ld_affine(const double *__restrict__ M, const double (&s)[4], const double (&v)[4], double (&r)[4])
 {
-    const int tid = threadIdx.x;
-    int cur = 0;
+    double t[4];
+    ld_matvec(M, s, t);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) s_sc[0][i * LD_THREADS + tid] = v[i];
-    __syncthreads();
-    for (int k = 0; k < LD_LEVELS; ++k) {
-        const int off = 1 << k;
-        if (tid >= off) {
-            double o[4], r[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) o[i] = s_sc[cur][i * LD_THREADS + tid - off];
-            ld_matvec(mats + 16 * k, o, r);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) v[i] = r[i] + v[i];
-        }
-        cur ^= 1;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) s_sc[cur][i * LD_THREADS + tid] = v[i];
-        __syncthreads();                                        // (the next level reads this buffer and writes the other one)
-    }
-    return cur;
+    for (int i = 0; i < 4; ++i) r[i] = t[i] + v[i];
 }
 
-// a tile's signal and place from the planner's table; false for a pair that is not the planner's (nothing is read or written)
-__device__ __forceinline__ bool ld_tile(const int32_t *__restrict__ tiles, const int64_t *__restrict__ in_off, int n, int &sig, int &kt,
-                                        int64_t &base, int64_t &len, int64_t &t0)
-{
-    sig = __builtin_amdgcn_readfirstlane(tiles[2 * blockIdx.x]), kt = __builtin_amdgcn_readfirstlane(tiles[2 * blockIdx.x + 1]);
-    if (sig < 0 || sig >= n || kt < 0) return false;
-    base = in_off[sig], len = in_off[sig + 1] - base, t0 = (int64_t)kt * LD_T;
-    return t0 < len && len < ((int64_t)1 << 31);
-}
+// the scan's combination at level k, all elements sharing mats[k]: v <- mats[k] o + v (ts_scan)
+struct ld_level {
+    const double *__restrict__ mats;
+    __device__ __forceinline__ void operator()(const double (&o)[4], int k, double (&v)[4]) const { ld_affine(mats + 16 * k, o, v, v); }
+};
 
-__global__ __launch_bounds__(LD_THREADS)
+__global__ __launch_bounds__(TS_THREADS)
 void k_loud_ends(const float *__restrict__ x, const int64_t *__restrict__ in_off, int n, const double *__restrict__ coef,
                  const double *__restrict__ mats, const int32_t *__restrict__ tiles, double *__restrict__ ends, int32_t *__restrict__ first_tile)
 {
     __shared__ float s_x[LD_XPAD];
-    __shared__ double s_sc[2][4 * LD_THREADS];
+    __shared__ double s_sc[2][4 * TS_THREADS];
     int sig, kt;
     int64_t base, len, t0;
-    if (!ld_tile(tiles, in_off, n, sig, kt, base, len, t0)) return;
-    if (threadIdx.x == 0 && kt == 0) first_tile[sig] = (int32_t)blockIdx.x;
-    ld_stage(x + base, len, t0, s_x);
+    if (!ts_tile(tiles, in_off, n, sig, kt, base, len, t0)) return;
+    ts_first_tile(first_tile, sig, kt);
+    ts_stage<16>(x + base, len, t0, s_x);
     __syncthreads();
     double v[4] = {0.0, 0.0, 0.0, 0.0}, e0 = 0.0, e1 = 0.0;
     ld_run<false>(s_x, coef, v, 0, e0, e1);
-    ld_scan(v, mats, s_sc);
-    if (threadIdx.x == LD_THREADS - 1) {
+    ts_scan(v, ld_level{mats}, s_sc);
+    if (threadIdx.x == TS_THREADS - 1) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) ends[4 * (int64_t)blockIdx.x + i] = v[i];
     }
 }
 
-// starts[tile] = the true state in front of the tile: 0 for a signal's first, A^4096 starts[t] + ends[t] for tile t + 1.  One
-// workgroup per signal, 4096 tiles a round: a thread walks 16 consecutive tiles from zero, the workgroup scans the threads' end
-// states (ld_scan with A^(4096 * 16 * 2^k); the state in front of the round goes through thread 0's run), and every thread walks
-// its tiles again from its true state.  (A single wave scanning 64 tiles a round took 250 us for the 11 882 tiles of a
-// 48.7 M-sample track, 1.3 us a round: a serial chain of seven matrix-vector products whose matrices do not fit the SGPRs.)
-__global__ __launch_bounds__(LD_THREADS)
+// starts[tile] = the true state in front of the tile: 0 for a signal's first, A^4096 starts[t] + ends[t] for tile t + 1
+// (ts_carry).  A thread walks its tiles from zero; the state in front of the round goes into thread 0's element through
+// A^(4096 * 16), and the scan's level k is A^(4096 * 16 * 2^k).
+struct ld_carry {
+    const double *__restrict__ P0, *__restrict__ PR;          // A^4096: one tile; A^(4096 * 16): a thread's run, level k of the scan: PR + 16 k
+    __device__ __forceinline__ void seed(double (&)[4], const double (&)[4]) const {}
+    __device__ __forceinline__ void append(double (&v)[4], const double (&z)[4]) const { ld_affine(P0, v, z, v); }
+    __device__ __forceinline__ void join(double (&v)[4], const double (&carry)[4]) const { ld_affine(PR, carry, v, v); }
+    __device__ __forceinline__ void level(const double (&o)[4], int k, double (&v)[4]) const { ld_affine(PR + 16 * k, o, v, v); }
+    __device__ __forceinline__ void step(double (&st)[4], const double (&z)[4]) const { ld_affine(P0, st, z, st); }
+};
+
+__global__ __launch_bounds__(TS_THREADS)
 void k_loud_carry(const int64_t *__restrict__ in_off, int n, int64_t n_tiles, const double *__restrict__ mats,
                   const double *__restrict__ ends, const int32_t *__restrict__ first_tile, double *__restrict__ starts)
 {
-    __shared__ double s_sc[2][4 * LD_THREADS];
-    const int sig = blockIdx.x, tid = threadIdx.x;
-    const int64_t len = in_off[sig + 1] - in_off[sig];
-    if (len <= 0 || len >= ((int64_t)1 << 31)) return;
-    const int nt = (int)((len + LD_T - 1) / LD_T);
-    const int64_t first = first_tile[sig];
-    if (first < 0 || first + nt > n_tiles) return;              // (a tile table that is not the planner's)
-    const double *__restrict__ P0 = mats + 16 * LD_LEVELS;      // A^4096: one tile
-    const double *__restrict__ PR = mats + 16 * (LD_LEVELS + 4);   // A^(4096 * 16): a thread's run; level k of the scan: PR + 16 k
-    double carry[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int c = 0; c < nt; c += LD_THREADS * LD_RUN) {
-        const int t0 = c + tid * LD_RUN;
-        double z[LD_RUN][4], v[4] = {0.0, 0.0, 0.0, 0.0}, r[4];
-#pragma unroll
-        for (int e = 0; e < LD_RUN; ++e)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) z[e][i] = t0 + e < nt ? ends[4 * (first + t0 + e) + i] : 0.0;
-#pragma unroll
-        for (int e = 0; e < LD_RUN; ++e) {
-            ld_matvec(P0, v, r);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) v[i] = r[i] + z[e][i];
-        }
-        if (tid == 0) {
-            ld_matvec(PR, carry, r);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) v[i] = r[i] + v[i];
-        }
-        const int cur = ld_scan(v, PR, s_sc);
-        double st[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) st[i] = tid == 0 ? carry[i] : s_sc[cur][i * LD_THREADS + tid - 1];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) carry[i] = s_sc[cur][i * LD_THREADS + LD_THREADS - 1];
-#pragma unroll
-        for (int e = 0; e < LD_RUN; ++e) {
-            if (t0 + e < nt) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) starts[4 * (first + t0 + e) + i] = st[i];
-            }
-            ld_matvec(P0, st, r);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) st[i] = r[i] + z[e][i];
-        }
-        __syncthreads();                                        // (the next round's scan writes the buffers read above)
-    }
+    ts_carry<4, 4>(in_off, n_tiles, first_tile, ends, starts, ld_carry{mats + 16 * TS_LEVELS, mats + 16 * (TS_LEVELS + 4)});
 }
 
-__global__ __launch_bounds__(LD_THREADS)
+__global__ __launch_bounds__(TS_THREADS)
 void k_loud_energy(const float *__restrict__ x, const int64_t *__restrict__ in_off, int n, int S, const double *__restrict__ coef,
                    const double *__restrict__ mats, const int32_t *__restrict__ tiles, const double *__restrict__ starts,
                    double *__restrict__ partial)
 {
     __shared__ float s_x[LD_XPAD];
-    __shared__ double s_sc[2][4 * LD_THREADS];
-    __shared__ double s_red[LD_SLOTS][LD_THREADS / 64];
+    __shared__ double s_sc[2][4 * TS_THREADS];
+    __shared__ double s_red[LD_SLOTS][TS_THREADS / 64];
     int sig, kt;
     int64_t base, len, t0;
-    if (!ld_tile(tiles, in_off, n, sig, kt, base, len, t0)) return;
+    if (!ts_tile(tiles, in_off, n, sig, kt, base, len, t0)) return;
     const int tid = threadIdx.x;
-    ld_stage(x + base, len, t0, s_x);
+    ts_stage<16>(x + base, len, t0, s_x);
     __syncthreads();
     double st[4], v[4] = {0.0, 0.0, 0.0, 0.0}, e0 = 0.0, e1 = 0.0;
 #pragma unroll
     for (int i = 0; i < 4; ++i) st[i] = starts[4 * (int64_t)blockIdx.x + i];
     ld_run<false>(s_x, coef, v, 0, e0, e1);
-    if (tid == 0) {
-        double r[4];
-        ld_matvec(mats, st, r);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = r[i] + v[i];
-    }
-    const int cur = ld_scan(v, mats, s_sc);
+    if (tid == 0) ld_affine(mats, st, v, v);
+    const int cur = ts_scan(v, ld_level{mats}, s_sc);
     if (tid > 0) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) st[i] = s_sc[cur][i * LD_THREADS + tid - 1];
+        for (int i = 0; i < 4; ++i) st[i] = s_sc[cur][i * TS_THREADS + tid - 1];
     }
     // segments: sample i of the signal lies in segment i / S; the tile touches kf .. and owns slot k - kf for segment k < Kn
-    const uint32_t us = (uint32_t)S, i0 = (uint32_t)t0 + (uint32_t)(tid * LD_SPT);
+    const uint32_t us = (uint32_t)S, i0 = (uint32_t)t0 + (uint32_t)(tid * TS_SPT);
     const int kf = (int)((uint32_t)t0 / us), kn = (int)((uint32_t)len / us);
     const int k0 = (int)(i0 / us);
-    const int bnd = (int)min((uint32_t)LD_SPT, (uint32_t)(k0 + 1) * us - i0);
+    const int bnd = (int)min((uint32_t)TS_SPT, (uint32_t)(k0 + 1) * us - i0);
     ld_run<true>(s_x, coef, st, bnd, e0, e1);
-    int nq = min((int)(((uint32_t)t0 + LD_T - 1) / us), kn - 1) - kf + 1;
+    int nq = min((int)(((uint32_t)t0 + TS_T - 1) / us), kn - 1) - kf + 1;
     nq = nq > LD_SLOTS ? LD_SLOTS : nq;
     const int q0 = k0 - kf;
+    auto add = [](double a, double b) { return a + b; };
     for (int q = 0; q < nq; ++q) {
-        double r = (q0 == q ? e0 : 0.0) + (q0 + 1 == q ? e1 : 0.0);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) r += __shfl_xor(r, o, 64);
+        const double r = ts_wave_reduce((q0 == q ? e0 : 0.0) + (q0 + 1 == q ? e1 : 0.0), add);
         if ((tid & 63) == 0) s_red[q][tid >> 6] = r;
     }
     __syncthreads();
-    if (tid < nq) partial[LD_SLOTS * (int64_t)blockIdx.x + tid] = ((s_red[tid][0] + s_red[tid][1]) + s_red[tid][2]) + s_red[tid][3];
+    if (tid < nq) partial[LD_SLOTS * (int64_t)blockIdx.x + tid] = ts_waves(add, s_red[tid]);
 }
 
-// a value per thread combined over the workgroup in a fixed order: the butterfly inside each wave, then the four waves in
-// order; every thread gets the result
-template <typename Op>
-__device__ __forceinline__ double ld_block_reduce(double v, Op op, double *s_red)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_xor(v, o, 64));
-    __syncthreads();                                            // (the previous result has been read)
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return op(op(op(s_red[0], s_red[1]), s_red[2]), s_red[3]);
-}
-
-__global__ __launch_bounds__(LD_THREADS)
+__global__ __launch_bounds__(TS_THREADS)
 void k_loud_stats(const int64_t *__restrict__ in_off, int n, int64_t n_tiles, int S, const int64_t *__restrict__ seg_off, const double *__restrict__ partial,
                   const int32_t *__restrict__ first_tile, double abs_gate, double target, double max_gain, int normalise,
                   double *__restrict__ seg_energy, double *__restrict__ loud, float *__restrict__ gain)
 {
-    __shared__ double s_red[LD_THREADS / 64];
+    __shared__ double s_red[TS_THREADS / 64];
     const int sig = blockIdx.x, tid = threadIdx.x;
     const int64_t len = in_off[sig + 1] - in_off[sig], sbase = seg_off[sig];
     const double nan = __longlong_as_double(0x7ff8000000000000LL), ninf = __longlong_as_double(0xfff0000000000000LL);
-    const int64_t kn = len > 0 && len < ((int64_t)1 << 31) ? len / S : 0;
-    const int64_t first = kn > 0 ? first_tile[sig] : 0;
-    if (seg_off[sig + 1] - sbase != kn || first < 0 || first + (len + LD_T - 1) / LD_T > n_tiles) {   // (tables that are not the planner's: no segment is written)
+    int nt = 0;
+    int64_t first = 0;
+    const bool tiled = ts_signal(in_off, n_tiles, first_tile, nt, first);
+    const int64_t kn = tiled ? (uint32_t)len / (uint32_t)S : 0;   // (0 < len < 2^31 there)
+    if (seg_off[sig + 1] - sbase != kn || (len > 0 && !tiled)) {   // (tables that are not the planner's: no segment is written)
         if (tid == 0) { loud[2 * sig] = nan; loud[2 * sig + 1] = nan; gain[sig] = 1.0f; }
         return;
     }
     double *__restrict__ E = seg_energy + sbase;
     if (kn > 0) {
         const uint32_t us = (uint32_t)S;                        // (k + 1) S <= len < 2^31: the quotients are 32-bit
-        for (uint32_t k = tid; k < (uint32_t)kn; k += LD_THREADS) {
-            const uint32_t ta = k * us / LD_T, tb = ((k + 1) * us - 1) / LD_T;
+        for (uint32_t k = tid; k < (uint32_t)kn; k += TS_THREADS) {
+            const uint32_t ta = k * us / TS_T, tb = ((k + 1) * us - 1) / TS_T;
             double sum = 0.0;
             for (uint32_t t = ta; t <= tb; ++t) {
-                const uint32_t slot = k - t * LD_T / us;        // (the tile's first segment is at most k)
+                const uint32_t slot = k - t * TS_T / us;        // (the tile's first segment is at most k)
                 if (slot < LD_SLOTS) sum += partial[LD_SLOTS * (first + t) + slot];
             }
             E[k] = sum;
@@ -276,22 +184,22 @@ void k_loud_stats(const int64_t *__restrict__ in_off, int n, int64_t n_tiles, in
     auto add = [](double a, double b) { return a + b; };
     auto block = [&](int64_t j) { return (((E[j] + E[j + 1]) + E[j + 2]) + E[j + 3]) * inv; };
     double sum = 0.0, cnt = 0.0, top = 0.0;
-    for (int64_t j = tid; j < kb; j += LD_THREADS) {
+    for (int64_t j = tid; j < kb; j += TS_THREADS) {
         const double z = block(j);
         if (!(z <= abs_gate)) sum += z, cnt += 1.0;             // (a NaN block is not dropped: it makes the statistics NaN)
         top = fmax(top, z);
     }
-    sum = ld_block_reduce(sum, add, s_red);
-    cnt = ld_block_reduce(cnt, add, s_red);
-    top = ld_block_reduce(top, [](double a, double b) { return fmax(a, b); }, s_red);
+    sum = ts_block_reduce(sum, add, s_red);
+    cnt = ts_block_reduce(cnt, add, s_red);
+    top = ts_block_reduce(top, [](double a, double b) { return fmax(a, b); }, s_red);
     const double rel = 0.1 * (sum / cnt);                       // (cnt == 0: nothing passes below either)
     double sum2 = 0.0, cnt2 = 0.0;
-    for (int64_t j = tid; j < kb; j += LD_THREADS) {
+    for (int64_t j = tid; j < kb; j += TS_THREADS) {
         const double z = block(j);
         if (z > abs_gate && z > rel) sum2 += z, cnt2 += 1.0;
     }
-    sum2 = ld_block_reduce(sum2, add, s_red);
-    cnt2 = ld_block_reduce(cnt2, add, s_red);
+    sum2 = ts_block_reduce(sum2, add, s_red);
+    cnt2 = ts_block_reduce(cnt2, add, s_red);
     if (tid != 0) return;
     double L = ninf, mm = kb > 0 ? -0.691 + 10.0 * log10(top) : ninf;
     float g = 1.0f;
@@ -335,19 +243,19 @@ int launch_loudness_measure(goofer_ctx *ctx, const float *x, const int64_t *in_o
                             int32_t *first_tile, hipStream_t st)
 {
     if (n <= 0) return GOOFER_OK;
-    HIP_TRY(ctx, hipMemsetAsync(first_tile, 0xff, sizeof(int32_t) * (size_t)n, st));     // -1: no tile seen
+    if (int rc = ts_first_tile_reset(ctx, first_tile, n, st)) return rc;
     if (n_tiles > 0) {
-        hipLaunchKernelGGL(k_loud_ends, dim3((unsigned)n_tiles), dim3(LD_THREADS), 0, st, x, in_off, n, coef, mats, tiles, ends, first_tile);
+        hipLaunchKernelGGL(k_loud_ends, dim3((unsigned)n_tiles), dim3(TS_THREADS), 0, st, x, in_off, n, coef, mats, tiles, ends, first_tile);
         LAUNCH_CHECK(ctx);
-        hipLaunchKernelGGL(k_loud_carry, dim3((unsigned)n), dim3(LD_THREADS), 0, st, in_off, n, n_tiles, mats, (const double *)ends,
+        hipLaunchKernelGGL(k_loud_carry, dim3((unsigned)n), dim3(TS_THREADS), 0, st, in_off, n, n_tiles, mats, (const double *)ends,
                            (const int32_t *)first_tile, starts);
         LAUNCH_CHECK(ctx);
-        hipLaunchKernelGGL(k_loud_energy, dim3((unsigned)n_tiles), dim3(LD_THREADS), 0, st, x, in_off, n, S, coef, mats, tiles,
+        hipLaunchKernelGGL(k_loud_energy, dim3((unsigned)n_tiles), dim3(TS_THREADS), 0, st, x, in_off, n, S, coef, mats, tiles,
                            (const double *)starts, partial);
         LAUNCH_CHECK(ctx);
     }
     const bool normalise = !std::isnan(target);
-    hipLaunchKernelGGL(k_loud_stats, dim3((unsigned)n), dim3(LD_THREADS), 0, st, in_off, n, n_tiles, S, seg_off, (const double *)partial,
+    hipLaunchKernelGGL(k_loud_stats, dim3((unsigned)n), dim3(TS_THREADS), 0, st, in_off, n, n_tiles, S, seg_off, (const double *)partial,
                        (const int32_t *)first_tile, std::pow(10.0, (-70.0 + 0.691) / 10.0), normalise ? target : 0.0,
                        std::pow(10.0, max_gain_db / 20.0), normalise ? 1 : 0, seg_energy, loud, gain);
     LAUNCH_CHECK(ctx);
@@ -370,7 +278,7 @@ extern "C" int goofer_loudness_measure(goofer_ctx *ctx, const float *x, const in
     if (int rc = check_counts(ctx, "goofer_loudness_measure", n, total, n_tiles)) return rc;
     const int s_lo = (GOOFER_LOUDNESS_MIN_SR + 5) / 10, s_hi = (GOOFER_LOUDNESS_MAX_SR + 5) / 10;
     if (S < s_lo || S > s_hi || std::isinf(target) || !(max_gain_db >= 0.0 && max_gain_db <= GOOFER_LOUDNESS_MAX_GAIN_DB_CAP) ||
-        !signal_tiles_ok(LD_T, n, total, n_tiles))
+        !signal_tiles_ok(TS_T, n, total, n_tiles))
         return goofer_fail(ctx, GOOFER_EINVAL, "goofer_loudness_measure: S = %d, target %g, max_gain_db %g, %lld tiles for %lld samples in %d signals is not a geometry of goofer_host_loudness_plan",
                            S, target, max_gain_db, (long long)n_tiles, (long long)total, n);
     if (!scratch_bytes) return goofer_fail(ctx, GOOFER_EINVAL, "goofer_loudness_measure: null pointer (scratch_bytes)");

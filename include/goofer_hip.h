@@ -919,6 +919,13 @@ int goofer_limit_tp(goofer_ctx *ctx, const float *x, const int64_t *in_off, int 
                     const int32_t *tiles, int64_t n_tiles, float *out, float *peak_in, float *min_gain, int R, int Z, const float *tp_taps,
                     void *stream);
 
+/* The tiling of the three stages that carry a recurrence over a signal (loudness, compressor, equaliser; csrc/tile_scan.h): their
+ * planners' tile tables and powers are laid out for these numbers, and each stage's own names below are defined from them. */
+#define GOOFER_SCAN_SPT 16           /* samples of a run: one thread's */
+#define GOOFER_SCAN_LEVELS 8         /* 2^8 runs in a tile; 2^8 threads in a round of the tile-to-tile carry */
+#define GOOFER_SCAN_TILE 4096        /* samples of a tile: SPT << LEVELS */
+#define GOOFER_SCAN_RUN_TILES 16     /* tiles a thread of a tile-to-tile carry walks: RUN_TILES << LEVELS = 4096 tiles a round */
+
 /* ---- loudness metering and normalisation ------------------------------------------------------------------------------------
  * The limiter watches peaks; this stage watches level: a signal's integrated loudness measured on the device and the signal
  * scaled to a target, in front of the limiter (mix, rate conversion, loudness, limiter, int16).  The definition is this
@@ -964,8 +971,10 @@ int goofer_limit_tp(goofer_ctx *ctx, const float *x, const int64_t *in_off, int 
 #define GOOFER_LOUDNESS_MAX_SR 192000
 #define GOOFER_LOUDNESS_MAX_GAIN_DB 20.0
 #define GOOFER_LOUDNESS_MAX_GAIN_DB_CAP 60.0
-#define GOOFER_LOUDNESS_TILE 4096
-#define GOOFER_LOUDNESS_SPT 16
+#define GOOFER_LOUDNESS_TILE GOOFER_SCAN_TILE
+#define GOOFER_LOUDNESS_SPT GOOFER_SCAN_SPT
+#define GOOFER_LOUDNESS_LEVELS GOOFER_SCAN_LEVELS
+#define GOOFER_LOUDNESS_RUN_TILES GOOFER_SCAN_RUN_TILES
 #define GOOFER_LOUDNESS_MATS 20      /* A^16 .. A^(16 * 2^19): 8 for the 256 runs of a tile, A^4096 for a tile, 8 from A^(4096 * 16) on for 256 runs of 16 tiles */
 #define GOOFER_LOUDNESS_SLOTS 8      /* segments a tile can touch: S >= 800 */
 
@@ -1049,12 +1058,13 @@ int goofer_loudness_apply(goofer_ctx *ctx, const float *x, const int64_t *in_off
 #define GOOFER_COMPRESS_ATTACK_MS 5.0
 #define GOOFER_COMPRESS_RELEASE_MS 100.0
 #define GOOFER_COMPRESS_FLOOR 1e-6   /* the least |x| the level detector sees: -120 dB */
-#define GOOFER_COMPRESS_TILE 4096
-#define GOOFER_COMPRESS_SPT 16
+#define GOOFER_COMPRESS_TILE GOOFER_SCAN_TILE
+#define GOOFER_COMPRESS_SPT GOOFER_SCAN_SPT
+#define GOOFER_COMPRESS_LEVELS GOOFER_SCAN_LEVELS
 #define GOOFER_COMPRESS_COEF 6
 #define GOOFER_COMPRESS_POWS 20      /* a^16 .. a^(16 * 2^19): 8 for the 256 runs of a tile, a^4096 for a tile, 8 from a^(4096 * 16) on for 256 runs of 16 tiles */
-#define GOOFER_COMPRESS_RUN_TILES 16 /* tiles a thread of the carry kernels walks */
-#define GOOFER_COMPRESS_ROUND_TILES 4096   /* tiles the carry kernels take per round: 256 threads of GOOFER_COMPRESS_RUN_TILES; the state in front of a round goes through its first thread */
+#define GOOFER_COMPRESS_RUN_TILES GOOFER_SCAN_RUN_TILES   /* tiles a thread of the carry kernels walks */
+#define GOOFER_COMPRESS_ROUND_TILES (GOOFER_SCAN_RUN_TILES << GOOFER_SCAN_LEVELS)   /* 4096 tiles the carry kernels take per round: 256 threads of GOOFER_COMPRESS_RUN_TILES; the state in front of a round goes through its first thread */
 
 /* Host side (no device, no handle): for n signals whose samples lie back to back with the CSR in_off[n + 1] (non-decreasing),
  * coef[GOOFER_COMPRESS_COEF], pows[2 * GOOFER_COMPRESS_POWS] and the tile table: need[0] = sum_i ceil(len_i /
@@ -1170,10 +1180,10 @@ int goofer_compress(goofer_ctx *ctx, const float *x, const int64_t *in_off, int 
 #define GOOFER_EQ_SHELF_Q_MAX 2.0    /* lowshelf, highshelf: above it a shelf is a resonance; cascades of those cost the tolerance */
 #define GOOFER_EQ_MAX_GAIN_DB 9.0
 #define GOOFER_EQ_TOL 0x1p-26
-#define GOOFER_EQ_TILE 4096
-#define GOOFER_EQ_SPT 16
-#define GOOFER_EQ_LEVELS 8          /* 2^8 runs in a tile; 2^8 threads in a round of the tile-to-tile carry */
-#define GOOFER_EQ_RUN_TILES 16      /* tiles a thread of the tile-to-tile carry walks: 4096 tiles a round */
+#define GOOFER_EQ_TILE GOOFER_SCAN_TILE
+#define GOOFER_EQ_SPT GOOFER_SCAN_SPT
+#define GOOFER_EQ_LEVELS GOOFER_SCAN_LEVELS   /* 2^8 runs in a tile; 2^8 threads in a round of the tile-to-tile carry */
+#define GOOFER_EQ_RUN_TILES GOOFER_SCAN_RUN_TILES   /* tiles a thread of the tile-to-tile carry walks: 4096 tiles a round */
 #define GOOFER_EQ_MATS(K) (4 * GOOFER_EQ_LEVELS * (K) + 4 * (1 + GOOFER_EQ_LEVELS) * (K) * (K))
 enum { GOOFER_EQ_HIGHPASS = 0, GOOFER_EQ_LOWPASS = 1, GOOFER_EQ_LOWSHELF = 2, GOOFER_EQ_HIGHSHELF = 3, GOOFER_EQ_PEAK = 4,
        GOOFER_EQ_NOTCH = 5, GOOFER_EQ_KINDS = 6 };

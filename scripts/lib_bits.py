@@ -1,16 +1,21 @@
 #!/usr/bin/env python
-"""Do two builds of libgoofer_hip.so compute the same bits?  The before / after check of a refactor of the per-sample kernels.
+"""Do two builds of libgoofer_hip.so compute the same bits?  The before / after check of a refactor of shared kernel code.
 
-usage: scripts/lib_bits.py <libA.so> <libB.so> [--out FILE] [--limit SECONDS]
+usage: scripts/lib_bits.py <libA.so> <libB.so> [--out FILE] [--limit SECONDS] [--set ragged|stages|all]
 
 Each library gets one fresh child process (GOOFER_HIP_LIB set, as scripts/lib_ab.sh does) under its own `timeout -k 10`; the
-second starts only if the first exited 0.  A child runs a fixed, seeded case list twice through the entry points that reach the
-kernels built on csrc/ragged.h — the post chain, the cascade, the synthesis on its spectra routes with the jitter, vibrato and
-sub-harmonic keyword sets, normal_fill, smooth_mask_ds, irfft_ola — and prints {case: {output: sha256}} of both runs.
+second starts only if the first exited 0.  A child runs a fixed, seeded case list twice and prints {case: {output: sha256}} of
+both runs.  Two sets of cases (default: all):
+  ragged  the entry points that reach the kernels built on csrc/ragged.h — the post chain, the cascade, the synthesis on its
+          spectra routes with the jitter, vibrato and sub-harmonic keyword sets, normal_fill, smooth_mask_ds, irfft_ola
+  stages  the stages built on csrc/tile_scan.h, each on its own test batches at its test rates — loudness measured and normalised
+          (seg_energy, loud, gain, y), the compressor under the settings of tests/test_gpu_compress.py with the curve and all
+          four combinations of compress_skip and compress_store (y, max_reduction, yl), the equaliser at K = 1 .. 8 (y) — and
+          each once on loudness_ref.long_signal(), whose 4116 tiles send a round's carry through thread 0 of the carry kernels
 
 An output whose digest differs between the two runs of one library is listed as non-deterministic and not compared across the
 libraries.  Only outputs behind k_note_sumsq are expected there (post chain, notes with tension != 0 that are longer than a
-workgroup: float64 atomics across workgroups).  Anything else listed there is a finding.
+workgroup: float64 atomics across workgroups).  Anything else listed there is a finding: the stages use no floating-point atomic.
 
 Writes {"A": .., "B": .., "nondeterministic": [..], "differ": [..]} to FILE (default: standard output only) and prints the two
 lists; exit status 1 if an output differs, the child's if a child failed.
@@ -29,8 +34,66 @@ def _sha(a):
     return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
 
 
-def _cases(ctx):
-    """{case: {output name: sha256}} of one pass over the list."""
+def _stage_cases(ctx):
+    """{case: {output name: sha256}} of one pass over the stages on csrc/tile_scan.h"""
+    import numpy as np
+    import compress_ref as CR
+    import eq_ref as ER
+    import loudness_ref as LR
+    from goofer_amd import compress as CP
+    from goofer_amd import eq as EQ
+    from goofer_amd import loudness as LD
+    out = {}
+
+    def dev(xs):
+        return ctx.tensor(np.concatenate(list(xs) + [np.zeros(1, np.float32)]))[:sum(len(x) for x in xs)]     # (never an empty tensor)
+
+    def loudness(name, xs, sr):
+        plan = LD.plan(sr, [len(x) for x in xs])
+        _, loud, gain, seg = ctx.loudness(dev(xs), None, plan)                              # measure only
+        out[name + "/measure"] = {"seg_energy": _sha(seg.cpu().numpy()), "loud": _sha(loud.cpu().numpy()), "gain": _sha(gain.cpu().numpy())}
+        y, loud, gain, seg = ctx.loudness(dev(xs), None, plan, -23.0, 60.0)
+        out[name + "/normalise"] = {"seg_energy": _sha(seg.cpu().numpy()), "loud": _sha(loud.cpu().numpy()), "gain": _sha(gain.cpu().numpy()),
+                                    "y": _sha(y.cpu().numpy())}
+
+    def compress(name, xs, sr, settings):
+        plan = CP.plan(sr, [len(x) for x in xs], CP.Compressor(*settings))
+        y, red, yl = ctx.compress(dev(xs), None, plan, curve=True)
+        out[name] = {"y": _sha(y.cpu().numpy()), "max_reduction": _sha(red.cpu().numpy()), "yl": _sha(yl.cpu().numpy())}
+
+    def eq(name, xs, sr, K):
+        y = ctx.eq(dev(xs), None, EQ.plan(sr, [len(x) for x in xs], ER.chain(sr, K)))
+        out[name] = {"y": _sha(y.cpu().numpy())}
+
+    for sr in LR.RATES:
+        for b, xs in enumerate(LR.batch(sr)):
+            loudness("loudness/%d/%d" % (sr, b), xs, sr)
+    for sr in ER.RATES:
+        for K in range(1, ER.MAX_BANDS + 1):
+            eq("eq/%d/K%d" % (sr, K), ER.batch(sr), sr, K)
+    sr, x = LR.long_signal()
+    loudness("loudness/long", [x], sr)
+    for K in (2, 8):
+        eq("eq/long/K%d" % K, [x], sr, K)
+    try:
+        for skip in (1, 0):
+            for store in (0, 1):
+                ctx.set_option("compress_skip", skip)
+                ctx.set_option("compress_store", store)
+                tag = "skip%d_store%d" % (skip, store)
+                for rate in CR.RATES:
+                    for name, settings in CR.SETS.items():
+                        compress("compress/%d/%s/%s" % (rate, name, tag), CR.batch(rate), rate, settings)
+                if skip == 1:
+                    compress("compress/long/" + tag, [x], sr, CR.SETS["defaults"])
+    finally:
+        ctx.set_option("compress_skip", 1)
+        ctx.set_option("compress_store", 0)
+    return out
+
+
+def _ragged_cases(ctx):
+    """{case: {output name: sha256}} of one pass over the kernels on csrc/ragged.h"""
     import numpy as np
     import post_ref as P
     import synth_ref as SR
@@ -111,11 +174,18 @@ def _cases(ctx):
     return out
 
 
-def child():
+def _cases(ctx, which):
+    out = _ragged_cases(ctx) if which in ("ragged", "all") else {}
+    if which in ("stages", "all"):
+        out.update(_stage_cases(ctx))
+    return out
+
+
+def child(which):
     sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
     from goofer_amd.device import Context
     ctx = Context(0)
-    runs = [_cases(ctx), _cases(ctx)]
+    runs = [_cases(ctx, which), _cases(ctx, which)]
     ctx.close()
     print("LIB_BITS " + json.dumps(runs))
 
@@ -125,9 +195,9 @@ def _flat(d):
 
 
 def main(argv):
-    if argv == ["--child"]:
-        return child()
-    opts = {"--out": None, "--limit": "600"}
+    if argv[:1] == ["--child"]:
+        return child(argv[1])
+    opts = {"--out": None, "--limit": "600", "--set": "all"}
     libs = []
     it = iter(argv)
     for a in it:
@@ -135,12 +205,12 @@ def main(argv):
             opts[a] = next(it)
         else:
             libs.append(a)
-    if len(libs) != 2:
+    if len(libs) != 2 or opts["--set"] not in ("ragged", "stages", "all"):
         sys.exit(__doc__)
     runs = {}
     for tag, lib in zip("AB", libs):
         env = dict(os.environ, GOOFER_HIP_LIB=os.path.abspath(lib))
-        p = subprocess.run(["timeout", "-k", "10", opts["--limit"], sys.executable, os.path.abspath(__file__), "--child"], env=env,
+        p = subprocess.run(["timeout", "-k", "10", opts["--limit"], sys.executable, os.path.abspath(__file__), "--child", opts["--set"]], env=env,
                            cwd=ROOT, stdout=subprocess.PIPE, text=True)
         lines = [ln for ln in p.stdout.splitlines() if ln.startswith("LIB_BITS ")]
         if p.returncode != 0 or not lines:

@@ -309,12 +309,12 @@ CHAINS = (1, 3, 8)
 @functools.lru_cache(maxsize=None)
 def _references(sr):
     coef = cascade_coefficients(chain(sr, MAX_BANDS), sr)
-    return tuple(cascade(x, coef, taps=CHAINS) for x in batch(sr))
+    return tuple(cascade(x, coef, taps=range(1, MAX_BANDS + 1)) for x in batch(sr))
 
 
 def reference(sr, K):
-    """the long-double restatement of every signal of batch(sr) through chain(sr, K), K in CHAINS: a tuple of longdouble arrays;
-    one walk through the eight bands per signal, cached, gives all three"""
+    """the long-double restatement of every signal of batch(sr) through chain(sr, K), 1 <= K <= MAX_BANDS: a tuple of longdouble
+    arrays; one walk through the eight bands per signal, cached, gives every prefix"""
     return tuple(r[K] for r in _references(sr))
 
 

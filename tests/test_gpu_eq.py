@@ -76,6 +76,24 @@ def test_batch_against_the_restatement(ctx, sr, K):
     print("%d Hz, K = %d: worst (|y - t| - 2^-24 |t|) / max |t| = %.3e (TOL %.3e)" % (sr, K, worst, R.TOL))
 
 
+@pytest.mark.parametrize("K", [2, 4, 5, 6, 7])
+def test_the_other_chain_lengths_against_the_restatement(ctx, K):
+    """The tile-to-tile kernel is compiled once per K and R.CHAINS runs three of the eight: the others, on the first K bands of
+    the chain of eight at 48 kHz.  The signal of 16 * 4096 + 100 samples puts 17 tiles through that kernel, one more than a
+    thread walks, so the second thread's state comes through the scan."""
+    sr = 48000
+    xs, ys, ts = R.batch(sr), _batch(ctx, sr, K), R.reference(sr, K)
+    assert K not in R.CHAINS and R.chain(sr, K) == R.chain(sr, 8)[:K] and max(len(x) for x in xs) == 16 * TILE + 100
+    worst = -math.inf
+    for i, (x, y, t) in enumerate(zip(xs, ys, ts)):
+        assert y.dtype == np.float32 and len(y) == len(x) == len(t), i
+        if len(x):
+            e = R.error(y, t)
+            worst = max(worst, e)
+            assert e <= R.TOL, (K, i, len(x), e)
+    print("48000 Hz, K = %d: worst (|y - t| - 2^-24 |t|) / max |t| = %.3e (TOL %.3e)" % (K, worst, R.TOL))
+
+
 @pytest.mark.parametrize("sr", [48000, 96000])
 def test_the_worst_corners_of_the_range(ctx, sr):
     """The corner run's input through the corners that do worst in the float64 model (tests/test_eq_ref.py), on the device: one
