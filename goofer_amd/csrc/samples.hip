@@ -8,6 +8,7 @@
 #include "fft_core.h"
 
 #include "samples_core.h"
+#include "ola_walk.h"
 #include "launchers.h"
 
 // A workgroup owns MS_TILE consecutive short samples of the concatenated axis.  For every note that tile touches (one,
@@ -228,7 +229,11 @@ __global__ __launch_bounds__(256) void k_ola3_gains(const float *__restrict__ fr
 // order (GOOFER.py:379-385).  After frame t, hop t is complete: it is normalised by the summed squared window,
 // scaled by the stem gains and written.  A run that starts inside a note first replays the `halo` preceding
 // frames (accumulate only); the wave that owns a note's last frame also flushes the hops behind it and the
-// zero-filled tail (GOOFER.py:402-413).
+// zero-filled tail (GOOFER.py:402-413).  The walk itself is csrc/ola_walk.h.
+
+// 64-sample register slots of the output stage: hop <= 64 SLOTS; larger hops go sample by sample.  Eight slots in the 1024-point
+// kernel would cost it its second wave per SIMD
+template <int M> constexpr int ola3_slots = M >= 1024 ? 8 : 4;
 template <int M>
 __global__ __launch_bounds__(256, M <= 512 ? 2 : 1) void k_irfft_ola3(const float2 *__restrict__ S_h, const float2 *__restrict__ S_u,
                                                     const float2 *__restrict__ S_b, int ldc, int64_t total_frames,
@@ -240,30 +245,23 @@ __global__ __launch_bounds__(256, M <= 512 ? 2 : 1) void k_irfft_ola3(const floa
                                                     float *__restrict__ note_peak, const float2 *__restrict__ g_tw,
                                                     const float2 *__restrict__ g_twh, const float *__restrict__ g_win)
 {
-    constexpr int R = fft_cfg<M>::R, NF = 2 * M, BUF = fft_cfg<M>::BUF;
+    constexpr int R = fft_cfg<M>::R, NF = 2 * M;
+    constexpr int SLOTS = ola3_slots<M>;
     extern __shared__ __align__(16) unsigned char smem[];
-    float2 *tw = reinterpret_cast<float2 *>(smem);
-    float2 *twh = tw + M;
-    float2 *bufs = twh + (M / 2 + 1);
-    float *win = reinterpret_cast<float *>(bufs + WAVES_PER_BLOCK * BUF);
-    float *rings = win + NF;
-    double *knots = reinterpret_cast<double *>(rings + (size_t)WAVES_PER_BLOCK * 3 * NF);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int KN = hop / MASK_DS + KNOT_MARGIN;
+    ola_lds<M, WAVES_PER_BLOCK, 3> L;
+    L.carve(smem, wave, KN);
+    float2 *const tw = L.tw, *const twh = L.twh, *const buf = L.buf;
+    float *const win = L.win, *const ring = L.ring;
+    double *const kbuf = L.kbuf;
     load_tables<M>(tw, twh, win, g_tw, g_twh, g_win);
 
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    float2 *buf = bufs + wave * BUF;
-    float *ring = rings + (size_t)wave * 3 * NF;
-    const int64_t f0 = ((int64_t)blockIdx.x * WAVES_PER_BLOCK + wave) * run;
+    const int64_t f0 = ola_run_first(blockIdx.x, WAVES_PER_BLOCK, wave, run);
     if (f0 >= total_frames) return;                          // no block barrier below
-    const int64_t f1 = f0 + run < total_frames ? f0 + run : total_frames;
+    int64_t fs, f1;
+    ola_run_span(f0, run, halo, total_frames, frame_note, frame_off, fs, f1);
     const float inv_m = 0.5f / (float)M;                     // 1/M of the transform and the 1/2 of the input stage (irfft_pre)
-
-    int64_t fs = f0;
-    {
-        const int nt = frame_note[f0];
-        const int64_t t0 = f0 - frame_off[nt];
-        fs = f0 - (t0 < halo ? t0 : halo);
-    }
 
     // spectrum rows of the next (frame, stem) job are fetched while the current one is transformed
     float2 nk[R], nm[R];
@@ -278,34 +276,18 @@ __global__ __launch_bounds__(256, M <= 512 ? 2 : 1) void k_irfft_ola3(const floa
     };
     fetch(fs, 0);
 
-    int note = -1;
-    int64_t base = 0, fbase = 0;
-    int n = 0, T = 0, ns = 0, out_len = 0;
-    float mag = 1.f, rmag = 1.f, g_b = 0.f, g_u = 0.f, pk = 0.f, kps = 0.f;
-    double step_n = 0.0, step_s = 0.0;
-    const double *ss = nullptr;
+    ola_note N;
+    float mag = 1.f, rmag = 1.f, g_b = 0.f, g_u = 0.f, pk = 0.f;
 
     // per-lane constants of the output stage for its samples j = lane + 64 u of a hop: the summed squared window
     // when all covering frames exist (interior hops), and its reciprocal
-    constexpr int SLOTS = M >= 1024 ? 8 : 4;                  // hop <= 64 SLOTS; larger hops recompute per sample.  Eight slots
-                                                              // in the 1024-point kernel would cost it its second wave per SIMD
     float ws_u[SLOTS], rws_u[SLOTS];
-    const int max_back = (NF - 1) / hop;                      // every position of a hop >= max_back has all its frames
+    const int max_back = ola_max_back(NF, hop);
 #pragma unroll
     for (int u = 0; u < SLOTS; ++u) {
-        const int j = lane + WAVE * u;
         ws_u[u] = 0.f;
         rws_u[u] = 0.f;
-        if (j < hop) {
-            const int back = (NF - 1 - j) / hop;
-            float ws = 0.f;
-            for (int q = back; q >= 0; --q) {                 // ascending frame order = descending offset
-                const float w = win[j + q * hop];
-                ws += w * w;
-            }
-            ws_u[u] = ws;
-            rws_u[u] = 1.0f / ws;
-        }
+        if (lane + WAVE * u < hop) ola_full_ws(win, NF, hop, lane + WAVE * u, ws_u[u], rws_u[u]);
     }
     // per-lane constants of the transform's two ends: the conj-trick twiddle of bin k and the synthesis window of
     // sample pair m, k = m = lane + 64 r
@@ -325,145 +307,81 @@ __global__ __launch_bounds__(256, M <= 512 ? 2 : 1) void k_irfft_ola3(const floa
         }
     }
 
-    // The smoothed-mask knots a hop needs (hop / MASK_DS of them, plus the +-3 the exact index search may reach) are
-    // fetched lane-parallel a frame ahead and parked in LDS, so the output stage reads them with LDS latency instead of
-    // issuing dependent global loads per sample.
-    constexpr int KPL = (WAVE * SLOTS / MASK_DS + KNOT_MARGIN + WAVE - 1) / WAVE;
-    const int KN = hop / MASK_DS + KNOT_MARGIN;
-    double *kbuf = knots + (size_t)wave * KN;
-    double kn_r[KPL];
-    int kn_lo = 0;
+    // hop <= 64 SLOTS: the hop's knots are parked in LDS (knot_window) and its samples' window sums are the constants above
+    knot_window<WAVE * SLOTS> kw;
     const bool slots_ok = hop <= WAVE * SLOTS;
-    auto knots_fetch = [&](int h) {
-        int i0 = h * hop - M;
-        i0 = i0 < 0 ? 0 : i0;
-        int lo = (int)((float)i0 * kps) - 4;
-        lo = lo < 0 ? 0 : lo;
-#pragma unroll
-        for (int c = 0; c < KPL; ++c) {
-            const int e = lane + WAVE * c;
-            const int k = lo + e < ns - 1 ? lo + e : ns - 1;
-            kn_r[c] = (e < KN && ns > 0) ? ss[k] : 0.0;
-        }
-        kn_lo = lo;
-    };
-    auto knots_park = [&]() {
-#pragma unroll
-        for (int c = 0; c < KPL; ++c) {
-            const int e = lane + WAVE * c;
-            if (e < KN) kbuf[e] = kn_r[c];
-        }
-        wave_lds_sync();
-    };
 
-    // finished hop h of the current note -> gains -> stems; also used for the flush hops and the zero tail.
-    // NS slots of 64 samples cover the hop; loads first, then the arithmetic, then the stores.
+    // finished hop h of the current note -> window-sum quotient -> gains -> stems; also the flush hops and the zero tail.
+    // NS slots of 64 samples cover the hop: loads first, then the arithmetic, then the stores, with the knots parked in LDS and
+    // the interior window sums the constants above.  NS == 0: a hop wider than the slots goes 64 samples a pass, with the
+    // knots from global memory and every window sum taken over the frames that exist.
     auto emit = [&](auto ns_tag, int h) {
-        constexpr int NS = decltype(ns_tag)::value;
+        constexpr int NS = decltype(ns_tag)::value, U = NS > 0 ? NS : 1;
         const int p0 = h * hop - M;                           // output index of the hop's first sample
-        const int e_hi = KN - 1, lo = kn_lo;
+        const int lo = kw.lo;
         auto knot = [&](int k) {
-            const int e = k - lo;
-            return kbuf[e < e_hi ? e : e_hi];
+            if constexpr (NS > 0) return kw.at(kbuf, KN, lo, k);
+            else return N.ss[k];
         };
-        float vh[NS], vu[NS], vb[NS];
+        for (int j0 = lane; j0 < (NS > 0 ? WAVE : hop); j0 += WAVE) {
+            float vh[U], vu[U], vb[U];
 #pragma unroll
-        for (int u = 0; u < NS; ++u) {
-            const int q = (h * hop + lane + WAVE * u) & (NF - 1);
-            vh[u] = ring[q];
-            vu[u] = ring[NF + q];
-            vb[u] = ring[2 * NF + q];
-        }
+            for (int u = 0; u < U; ++u) {
+                const int q = (h * hop + j0 + WAVE * u) & (NF - 1);
+                vh[u] = ring[q];
+                vu[u] = ring[NF + q];
+                vb[u] = ring[2 * NF + q];
+            }
 #pragma unroll
-        for (int u = 0; u < NS; ++u) {
-            const int j = lane + WAVE * u;
-            const int i = p0 + j;
-            if (j >= hop || i < 0 || i >= n) continue;
-            float xh = 0.f, xu = 0.f, xb = 0.f;
-            if (i < out_len) {
-                xh = vh[u]; xu = vu[u]; xb = vb[u];
-                if (h >= max_back && h <= T - 1) {
-                    // interior hop: the divisor is a per-lane constant; with r = RN(1 / ws) the quotient correction
-                    // q + fma(-q, ws, x) * r is the correctly rounded x / ws (Markstein) in three instructions
-                    const float ws = ws_u[u], rw = rws_u[u];
-                    if (ws > 1e-9f) { xh = div_by(xh, ws, rw); xu = div_by(xu, ws, rw); xb = div_by(xb, ws, rw); }
-                } else {
-                    const int back = (NF - 1 - j) / hop;
-                    const int flo = h - back < 0 ? 0 : h - back, fhi = h > T - 1 ? T - 1 : h;
-                    float ws = 0.f;
-                    for (int fr = flo; fr <= fhi; ++fr) {
-                        const float w = win[j + (h - fr) * hop];
-                        ws += w * w;
+            for (int u = 0; u < U; ++u) {
+                const int j = j0 + WAVE * u;
+                const int i = p0 + j;
+                if (j >= hop || i < 0 || i >= N.n) continue;
+                float xh = 0.f, xu = 0.f, xb = 0.f;
+                if (i < N.out_len) {
+                    xh = vh[u]; xu = vu[u]; xb = vb[u];
+                    if (NS > 0 && ola_interior(h, max_back, N.T)) {
+                        // interior hop: the divisor is a per-lane constant; with r = RN(1 / ws) the quotient correction
+                        // q + fma(-q, ws, x) * r is the correctly rounded x / ws (Markstein) in three instructions
+                        const float ws = ws_u[NS > 0 ? u : 0], rw = rws_u[NS > 0 ? u : 0];
+                        if (ws > 1e-9f) { xh = div_by(xh, ws, rw); xu = div_by(xu, ws, rw); xb = div_by(xb, ws, rw); }
+                    } else {
+                        const float ws = ola_partial_ws(win, NF, hop, N.T, h, j);
+                        if (ws > 1e-9f) { xh /= ws; xu /= ws; xb /= ws; }
                     }
-                    if (ws > 1e-9f) { xh /= ws; xu /= ws; xb /= ws; }
+                    // (a wide hop takes the quotient itself, as it always has: under this build's fp32 division the two are not
+                    // the same float on every sample, and the wide form's bits stay what they were)
+                    xh = NS > 0 ? div_by(xh, mag, rmag) : xh / mag;
                 }
-                xh = div_by(xh, mag, rmag);
+                const float ms = smooth_mask_at32(knot, N.ns, i, N.n, N.step_n, N.step_s, N.kps);
+                xb = (xb * ms) * g_b;
+                xu = (xu * (1.0f - ms)) * g_u;
+                harm[N.base + i] = xh;
+                uv[N.base + i] = xu;
+                bre[N.base + i] = xb;
+                pk = fmaxf(pk, fabsf((xh + xu) + xb));
             }
-            const float ms = smooth_mask_at32(knot, ns, i, n, step_n, step_s, kps);
-            xb = (xb * ms) * g_b;
-            xu = (xu * (1.0f - ms)) * g_u;
-            harm[base + i] = xh;
-            uv[base + i] = xu;
-            bre[base + i] = xb;
-            pk = fmaxf(pk, fabsf((xh + xu) + xb));
-        }
-    };
-    auto emit_any = [&](int h) {                              // hops wider than the cached slots
-        auto knot = [&](int k) { return ss[k]; };
-        for (int j = lane; j < hop; j += WAVE) {
-            const int i = h * hop + j - M;
-            if (i < 0 || i >= n) continue;
-            float vh = 0.f, vu = 0.f, vb = 0.f;
-            if (i < out_len) {
-                const int back = (NF - 1 - j) / hop;
-                const int lo = h - back < 0 ? 0 : h - back, hi = h > T - 1 ? T - 1 : h;
-                float ws = 0.f;
-                for (int fr = lo; fr <= hi; ++fr) {
-                    const float w = win[j + (h - fr) * hop];
-                    ws += w * w;
-                }
-                const int q = (h * hop + j) & (NF - 1);
-                vh = ring[q]; vu = ring[NF + q]; vb = ring[2 * NF + q];
-                if (ws > 1e-9f) { vh /= ws; vu /= ws; vb /= ws; }
-                vh = vh / mag;
-            }
-            const float ms = smooth_mask_at32(knot, ns, i, n, step_n, step_s, kps);
-            vb = (vb * ms) * g_b;
-            vu = (vu * (1.0f - ms)) * g_u;
-            harm[base + i] = vh;
-            uv[base + i] = vu;
-            bre[base + i] = vb;
-            pk = fmaxf(pk, fabsf((vh + vu) + vb));
         }
     };
     const int nslot = (hop + WAVE - 1) / WAVE;
+    auto peak_out = [&]() {
+        const float m = wave_max(pk);
+        if (lane == 0) atomic_max_pos(note_peak + N.note, m);
+    };
 
     for (int64_t f = fs; f < f1; ++f) {
         const int nt = frame_note[f];
-        if (nt != note) {
-            if (note >= 0) {
-                const float m = wave_max(pk);
-                if (lane == 0) atomic_max_pos(note_peak + note, m);
-            }
-            note = nt;
+        if (nt != N.note) {
+            if (N.note >= 0) peak_out();
+            N.enter(nt, hop, sample_off, frame_off, steps, short_s);
             pk = 0.f;
-            base = sample_off[note];
-            n = (int)(sample_off[note + 1] - base);
-            fbase = frame_off[note];
-            T = (int)(frame_off[note + 1] - fbase);
-            ns = (n + MASK_DS - 1) / MASK_DS;
-            out_len = hop * (T - 1);
-            mag = note_mag[note];
+            mag = note_mag[nt];
             rmag = 1.0f / mag;
-            g_b = params[note].breath_strength;
-            g_u = params[note].uv_strength;
-            step_n = steps[2 * note];
-            step_s = steps[2 * note + 1];
-            kps = n > 1 ? (float)(ns - 1) / (float)(n - 1) : 0.f;
-            ss = short_s + short_base(sample_off, note);
+            g_b = params[nt].breath_strength;
+            g_u = params[nt].uv_strength;
         }
-        const int t = (int)(f - fbase);
-        if (f >= f0 && slots_ok) knots_fetch(t);              // lands during the three transforms below
+        const int t = (int)(f - N.fbase);
+        if (f >= f0 && slots_ok) kw.fetch(t, hop, M, N.kps, N.ns, N.ss, KN, lane);   // lands during the three transforms below
 #pragma unroll
         for (int stem = 0; stem < 3; ++stem) {
             float2 v[R];
@@ -477,11 +395,7 @@ __global__ __launch_bounds__(256, M <= 512 ? 2 : 1) void k_irfft_ola3(const floa
             // next job's rows: same frame next stem, or the next frame's first stem
             if (stem < 2) fetch(f, stem + 1);
             else if (f + 1 < f1) fetch(f + 1, 0);
-            float *rg = ring + stem * NF;
-            const int shift = (t * hop) & (NF - 1);
-            // all ring reads, then all ring writes: the R slots of a lane are distinct, and a branch-free body lets the
-            // LDS reads overlap instead of paying one round trip per slot
-            float2 z[R], o[R];
+            float2 z[R];
             if constexpr (M == 512) {
                 wave_fft_keep_tw<M>(v, buf, tw1_r, tw2_r, lane, z);   // twiddles and the lane's output points in registers
             } else if constexpr (M >= 512) {
@@ -491,44 +405,29 @@ __global__ __launch_bounds__(256, M <= 512 ? 2 : 1) void k_irfft_ola3(const floa
 #pragma unroll
                 for (int r = 0; r < R; ++r) z[r] = buf[lds_pad(lane + WAVE * r)];
             }
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const int m = lane + WAVE * r;
-                o[r] = *reinterpret_cast<const float2 *>(rg + ((2 * m + shift) & (NF - 1)));
-            }
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const int m = lane + WAVE * r;
-                const float2 wn = HOIST ? win_r[HOIST ? r : 0] : win_of(m);
-                const float a = z[r].x * wn.x, b = z[r].y * wn.y;
-                const bool first = t == 0 || 2 * m >= NF - hop;   // first contribution: y starts from zero
-                *reinterpret_cast<float2 *>(rg + ((2 * m + shift) & (NF - 1))) =
-                    make_float2(first ? a : o[r].x + a, first ? b : o[r].y + b);
-            }
+            // (all R ring reads ahead of the writes)
+            ola_ring_add<NF, R, R>(ring + stem * NF, z, t, hop, lane, [&](int r) { return HOIST ? win_r[HOIST ? r : 0] : win_of(lane + WAVE * r); });
             wave_lds_sync();
         }
-        if (f >= f0) {
-            // hop t; behind a note's last frame also the hops up to the one holding sample out_len - 1 and the zero tail
-            for (int h = t;;) {
-                if (slots_ok) {
-                    knots_park();
-                    if (nslot <= 2) emit(std::integral_constant<int, 2>{}, h);
-                    else if (nslot <= 4) emit(std::integral_constant<int, 4>{}, h);
-                    else if constexpr (SLOTS >= 8) emit(std::integral_constant<int, 8>{}, h);
-                } else {
-                    emit_any(h);
-                }
-                ++h;
-                if (t != T - 1 || h * hop - M >= n) break;
-                if (slots_ok) knots_fetch(h);
-            }
-        }
+        if (f >= f0)
+            ola_finish_hops(
+                t, N.T, hop, M, N.n,
+                [&](int h) {
+                    if (slots_ok) {
+                        kw.park(kbuf, KN, lane);
+                        if (nslot <= 2) emit(std::integral_constant<int, 2>{}, h);
+                        else if (nslot <= 4) emit(std::integral_constant<int, 4>{}, h);
+                        else if constexpr (SLOTS >= 8) emit(std::integral_constant<int, 8>{}, h);
+                    } else {
+                        emit(std::integral_constant<int, 0>{}, h);
+                    }
+                },
+                [&](int h) {
+                    if (slots_ok) kw.fetch(h, hop, M, N.kps, N.ns, N.ss, KN, lane);
+                });
         wave_lds_sync();
     }
-    if (note >= 0) {
-        const float m = wave_max(pk);
-        if (lane == 0) atomic_max_pos(note_peak + note, m);
-    }
+    if (N.note >= 0) peak_out();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -541,6 +440,8 @@ __global__ __launch_bounds__(256, M <= 512 ? 2 : 1) void k_irfft_ola3(const floa
 // Arguments needed once per note, once per 64 frames or at set-up are read from the kernarg segment where they are used
 // (cold_arg, as in the stem walkers): the frame loop holds ~60 scalars of wave state, and with 22 arguments live beside them
 // the compiler spilled 142 SGPRs (a v_writelane / v_readlane pair each) and a vector register to scratch.
+constexpr int OLA1_MAXHOP = 512;                                  // widest hop whose knots are parked in LDS; wider hops read them from global memory
+constexpr int OLA1_KNOTS = OLA1_MAXHOP / MASK_DS + KNOT_MARGIN;   // the knot slice of a wave
 struct ola1_args {
     // every frame
     const float2 *S_h, *S_u, *S_b;
@@ -561,26 +462,25 @@ __global__ __launch_bounds__(64 * WPB, 2) void k_irfft_ola1(const ola1_args A)
 {
     const int ldc = A.ldc, hop = A.hop, run = A.run, halo = A.halo;
     const int *__restrict__ frame_note = A.frame_note;
-    constexpr int R = fft_cfg<M>::R, NF = 2 * M, BUF = fft_cfg<M>::BUF;
+    constexpr int R = fft_cfg<M>::R, NF = 2 * M;
     extern __shared__ __align__(16) unsigned char smem[];
-    float2 *tw = reinterpret_cast<float2 *>(smem);
-    float2 *twh = tw + M;
-    float2 *bufs = twh + (M / 2 + 1);
-    float *win = reinterpret_cast<float *>(bufs + WPB * BUF);
-    float *rings = win + NF;
-    double *knots = reinterpret_cast<double *>(rings + (size_t)WPB * NF);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    ola_lds<M, WPB, 1> L;
+    L.carve(smem, wave, OLA1_KNOTS);
+    float2 *const tw = L.tw, *const twh = L.twh, *const buf = L.buf;
+    float *const win = L.win, *const ring = L.ring;
+    double *const kbuf = L.kbuf;
     load_tables<M>(tw, twh, win, COLD(ola1_args, g_tw), COLD(ola1_args, g_twh), COLD(ola1_args, g_win));
 
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    float2 *buf = bufs + wave * BUF;
-    float *ring = rings + (size_t)wave * NF;
     // A workgroup holds runs of ONE stem (stems interleaved workgroup by workgroup): where a stem's transforms are skipped
     // (frame_skip: its gain is exactly zero over everything the frame reaches) whole workgroups retire early and the
     // dispatcher hands their CU to the next one — with the three stems of a run side by side in one workgroup the skipped
     // waves only idled beside the others.
     const int stem = (int)(blockIdx.x % 3);                   // workgroup-uniform
-    const int64_t f0 = ((int64_t)(blockIdx.x / 3) * WPB + wave) * run;
-    if (f0 >= COLD(ola1_args, total_frames)) return;                    // no block barrier below
+    const int64_t f0 = ola_run_first(blockIdx.x / 3, WPB, wave, run);
+    if (f0 >= COLD(ola1_args, total_frames)) return;          // no block barrier below
+    int64_t fs, f1;
+    ola_run_span(f0, run, halo, COLD(ola1_args, total_frames), frame_note, COLD(ola1_args, frame_off), fs, f1);
     const unsigned skip_bit = COLD(ola1_args, frame_skip) ? (unsigned)stem : 0u;   // bit 0 (1): unvoiced stem, bit 1 (2): breath stem; harmonic: never
     // the skip bits of 64 consecutive frames as one ballot (a byte load per frame would sit on the loop's critical path)
     uint64_t skip_mask = 0;
@@ -594,17 +494,10 @@ __global__ __launch_bounds__(64 * WPB, 2) void k_irfft_ola1(const ola1_args A)
         }
         return ((skip_mask >> (int)(f - skip_base)) & 1ull) != 0;
     };
-    const int64_t f1 = f0 + run < COLD(ola1_args, total_frames) ? f0 + run : COLD(ola1_args, total_frames);
     const float inv_m = 0.5f / (float)M;                     // 1/M of the transform and the 1/2 of the input stage (irfft_pre)
     const float2 *S = stem == 0 ? A.S_h : (stem == 1 ? A.S_u : A.S_b);
     float *out = stem == 0 ? COLD(ola1_args, harm) : (stem == 1 ? COLD(ola1_args, uv) : COLD(ola1_args, bre));
 
-    int64_t fs = f0;
-    {
-        const int nt = frame_note[f0];
-        const int64_t t0 = f0 - COLD(ola1_args, frame_off)[nt];
-        fs = f0 - (t0 < halo ? t0 : halo);
-    }
     // spectrum row of the next frame, fetched during the transform: bins lane + 64 r and the Nyquist bin; the mirrored bins
     // X[M - k] of the inverse transform's input stage come from the row itself through the (idle) exchange buffer — a second
     // set of loads would hold 32 more registers across the whole frame
@@ -618,13 +511,9 @@ __global__ __launch_bounds__(64 * WPB, 2) void k_irfft_ola1(const ola1_args A)
     bool skip_cur = skipped(fs);
     if (!skip_cur) fetch(fs);
 
-    int note = -1;
-    int64_t base = 0, fbase = 0;
-    int n = 0, T = 0, ns = 0, out_len = 0;
-    float gain = 0.f, kps = 0.f;
-    double step_n = 0.0, step_s = 0.0;
-    const double *ss = nullptr;
-    const int max_back = (NF - 1) / hop;
+    ola_note N;
+    float gain = 0.f;
+    const int max_back = ola_max_back(NF, hop);
     auto wc_of = [&](int k) { return (k <= M / 2) ? cconj(twh[k]) : make_float2(-twh[M - k].x, -twh[M - k].y); };
     auto win_of = [&](int k) { return make_float2(win[2 * k] * inv_m, -(win[2 * k + 1] * inv_m)); };
 
@@ -632,98 +521,50 @@ __global__ __launch_bounds__(64 * WPB, 2) void k_irfft_ola1(const ola1_args A)
     // constant per lane, with its correctly rounded reciprocal (div_by); the first two slots only — wider hops take the loop
     float ws_c[2] = {0.f, 0.f}, rws_c[2] = {0.f, 0.f};
 #pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        const int j = lane + WAVE * u;
-        if (j < hop) {
-            float ws = 0.f;
-            for (int q = (NF - 1 - j) / hop; q >= 0; --q) {   // ascending frame order = descending offset
-                const float w = win[j + q * hop];
-                ws += w * w;
-            }
-            ws_c[u] = ws;
-            rws_c[u] = 1.0f / ws;
-        }
-    }
+    for (int u = 0; u < 2; ++u)
+        if (lane + WAVE * u < hop) ola_full_ws(win, NF, hop, lane + WAVE * u, ws_c[u], rws_c[u]);
     const int KN = hop / MASK_DS + KNOT_MARGIN;
-    double *kbuf = knots + (size_t)wave * (512 / MASK_DS + KNOT_MARGIN);
-    constexpr int KPL = (512 / MASK_DS + KNOT_MARGIN + WAVE - 1) / WAVE;
-    double kn_r[KPL];
-    int kn_lo = 0;
-    const bool slots_ok = hop <= 512 && stem != 0;            // the harmonic stem has no mask gain
-    auto knots_fetch = [&](int h) {
-        int i0 = h * hop - M;
-        i0 = i0 < 0 ? 0 : i0;
-        int lo = (int)((float)i0 * kps) - 4;
-        lo = lo < 0 ? 0 : lo;
-#pragma unroll
-        for (int c = 0; c < KPL; ++c) {
-            const int e = lane + WAVE * c;
-            const int k = lo + e < ns - 1 ? lo + e : ns - 1;
-            kn_r[c] = (e < KN && ns > 0) ? ss[k] : 0.0;
-        }
-        kn_lo = lo;
-    };
+    knot_window<OLA1_MAXHOP> kw;
+    const bool slots_ok = hop <= OLA1_MAXHOP && stem != 0;    // the harmonic stem has no mask gain
     // finished hop h of the current note -> window-sum quotient -> (noise stems) mask gain -> out; also the flush hops and the zero tail
     auto emit = [&](int h) {
-        const int e_hi = KN - 1, lo = kn_lo;
-        auto knot_l = [&](int k) {
-            const int e = k - lo;
-            return kbuf[e < e_hi ? e : e_hi];
-        };
-        auto knot_g = [&](int k) { return ss[k]; };
-        const bool inner = h >= max_back && h <= T - 1;       // every covering frame exists
+        const int lo = kw.lo;
+        auto knot_l = [&](int k) { return kw.at(kbuf, KN, lo, k); };
+        auto knot_g = [&](int k) { return N.ss[k]; };
+        const bool inner = ola_interior(h, max_back, N.T);    // every covering frame exists
         for (int j = lane, u = 0; j < hop; j += WAVE, ++u) {
             const int i = h * hop + j - M;
-            if (i < 0 || i >= n) continue;
+            if (i < 0 || i >= N.n) continue;
             float x = 0.f;
-            if (i < out_len) {
+            if (i < N.out_len) {
                 x = ring[(h * hop + j) & (NF - 1)];
                 if (inner && u < 2) {
                     const float ws = u == 0 ? ws_c[0] : ws_c[1], rw = u == 0 ? rws_c[0] : rws_c[1];
                     if (ws > 1e-9f) x = div_by(x, ws, rw);
                 } else {
-                    const int back = (NF - 1 - j) / hop;
-                    const int flo = h - back < 0 ? 0 : h - back, fhi = h > T - 1 ? T - 1 : h;
-                    float ws = 0.f;
-                    for (int fr = flo; fr <= fhi; ++fr) {
-                        const float w = win[j + (h - fr) * hop];
-                        ws += w * w;
-                    }
+                    const float ws = ola_partial_ws(win, NF, hop, N.T, h, j);
                     if (ws > 1e-9f) x /= ws;
                 }
             }
             if (stem != 0) {
-                const float ms = slots_ok ? smooth_mask_at32(knot_l, ns, i, n, step_n, step_s, kps)
-                                          : smooth_mask_at32(knot_g, ns, i, n, step_n, step_s, kps);
+                const float ms = slots_ok ? smooth_mask_at32(knot_l, N.ns, i, N.n, N.step_n, N.step_s, N.kps)
+                                          : smooth_mask_at32(knot_g, N.ns, i, N.n, N.step_n, N.step_s, N.kps);
                 x = (x * (stem == 1 ? 1.0f - ms : ms)) * gain;
             }
-            out[base + i] = x;
+            out[N.base + i] = x;
         }
     };
 
     for (int64_t f = fs; f < f1; ++f) {
         const int nt = frame_note[f];
-        if (nt != note) {
-            note = nt;
-            const int64_t *sample_off = COLD(ola1_args, sample_off), *frame_off = COLD(ola1_args, frame_off);
-            base = sample_off[note];
-            n = (int)(sample_off[note + 1] - base);
-            fbase = frame_off[note];
-            T = (int)(frame_off[note + 1] - fbase);
-            ns = (n + MASK_DS - 1) / MASK_DS;
-            out_len = hop * (T - 1);
+        if (nt != N.note) {
+            N.enter(nt, hop, COLD(ola1_args, sample_off), COLD(ola1_args, frame_off), COLD(ola1_args, steps), COLD(ola1_args, short_s));
             const goofer_note_params *params = COLD(ola1_args, params);
-            const double *steps = COLD(ola1_args, steps);
-            gain = stem == 1 ? params[note].uv_strength : params[note].breath_strength;
-            step_n = steps[2 * note];
-            step_s = steps[2 * note + 1];
-            kps = n > 1 ? (float)(ns - 1) / (float)(n - 1) : 0.f;
-            ss = COLD(ola1_args, short_s) + short_base(sample_off, note);
+            gain = stem == 1 ? params[nt].uv_strength : params[nt].breath_strength;
         }
-        const int t = (int)(f - fbase);
-        const int shift = (t * hop) & (NF - 1);
+        const int t = (int)(f - N.fbase);
         const bool skip_this = skip_cur;
-        if (f >= f0 && slots_ok && !skip_this) knots_fetch(t);
+        if (f >= f0 && slots_ok && !skip_this) kw.fetch(t, hop, M, N.kps, N.ns, N.ss, KN, lane);
         skip_cur = f + 1 < f1 && skipped(f + 1);
         if (skip_this) {
             // no transform: the slots this frame would have started from zero are zeroed, the others keep their sums
@@ -731,7 +572,7 @@ __global__ __launch_bounds__(64 * WPB, 2) void k_irfft_ola1(const ola1_args A)
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 const int m = lane + WAVE * r;
-                if (t == 0 || 2 * m >= NF - hop) *reinterpret_cast<float2 *>(ring + ((2 * m + shift) & (NF - 1))) = make_float2(0.f, 0.f);
+                if (ola_first(t, m, NF, hop)) *ola_slot(ring, ola_shift(t, NF, hop), m, NF) = make_float2(0.f, 0.f);
             }
         } else {
         float2 v[R];
@@ -750,50 +591,28 @@ __global__ __launch_bounds__(64 * WPB, 2) void k_irfft_ola1(const ola1_args A)
         if (f + 1 < f1 && !skip_cur) fetch(f + 1);
         float2 z[R];
         wave_fft_keep<M>(v, buf, tw, lane, z);                // the lane's output points stay in registers
-        // ring reads ahead of ring writes, eight slots at a time (the R slots of a lane are distinct)
-#pragma unroll
-        for (int r0 = 0; r0 < R; r0 += 8) {
-            float2 o[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                const int m = lane + WAVE * (r0 + q);
-                o[q] = *reinterpret_cast<const float2 *>(ring + ((2 * m + shift) & (NF - 1)));
-            }
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                const int m = lane + WAVE * (r0 + q);
-                const float2 wn = win_of(m);
-                const float a = z[r0 + q].x * wn.x, b = z[r0 + q].y * wn.y;
-                const bool first = t == 0 || 2 * m >= NF - hop;   // first contribution: y starts from zero
-                *reinterpret_cast<float2 *>(ring + ((2 * m + shift) & (NF - 1))) = make_float2(first ? a : o[q].x + a, first ? b : o[q].y + b);
-            }
-        }
+        // (ring reads ahead of ring writes eight slots at a time)
+        ola_ring_add<NF, R, 8>(ring, z, t, hop, lane, [&](int r) { return win_of(lane + WAVE * r); });
         }
         wave_lds_sync();
-        if (f >= f0) {
-            for (int h = t;;) {
-                if (slots_ok && !skip_this) {
-#pragma unroll
-                    for (int c = 0; c < KPL; ++c) {
-                        const int e = lane + WAVE * c;
-                        if (e < KN) kbuf[e] = kn_r[c];
+        if (f >= f0)
+            ola_finish_hops(
+                t, N.T, hop, M, N.n,
+                [&](int h) {
+                    if (skip_this) {
+                        // every hop this frame reaches has a gain of exactly zero: the hop (and the flush hops behind a last frame) is zeros
+                        for (int j = lane; j < hop; j += WAVE) {
+                            const int i = h * hop + j - M;
+                            if (i >= 0 && i < N.n) out[N.base + i] = 0.f;
+                        }
+                    } else {
+                        if (slots_ok) kw.park(kbuf, KN, lane);
+                        emit(h);
                     }
-                    wave_lds_sync();
-                }
-                if (skip_this) {
-                    // every hop this frame reaches has a gain of exactly zero: the hop (and the flush hops behind a last frame) is zeros
-                    for (int j = lane; j < hop; j += WAVE) {
-                        const int i = h * hop + j - M;
-                        if (i >= 0 && i < n) out[base + i] = 0.f;
-                    }
-                } else {
-                    emit(h);
-                }
-                ++h;
-                if (t != T - 1 || h * hop - M >= n) break;
-                if (slots_ok && !skip_this) knots_fetch(h);
-            }
-        }
+                },
+                [&](int h) {
+                    if (slots_ok && !skip_this) kw.fetch(h, hop, M, N.kps, N.ns, N.ss, KN, lane);
+                });
         wave_lds_sync();
     }
 }
@@ -807,8 +626,7 @@ static int irfft_ola1_impl(goofer_ctx *ctx, const float2 *S_h, const float2 *S_u
     constexpr int WPB = 8;
     const goofer_plan_t &p = ctx->plan;
     const int halo = (p.n_fft + p.hop - 1) / p.hop - 1;
-    const size_t lds = sizeof(float2) * (M + M / 2 + 1 + WPB * fft_cfg<M>::BUF) + sizeof(float) * 2 * M + sizeof(float) * WPB * 2 * M + 16 +
-                       sizeof(double) * WPB * (512 / MASK_DS + KNOT_MARGIN);
+    const size_t lds = ola_lds<M, WPB, 1>::bytes(OLA1_KNOTS);
     if (lds > 160 * 1024) return goofer_fail(ctx, GOOFER_EINVAL, "one-stem overlap-add: %zu bytes of LDS", lds);
     const void *fn = (const void *)k_irfft_ola1<M, WPB>;
     int rc = kernel_allow_max_lds(ctx, fn);
@@ -934,9 +752,8 @@ static int irfft_ola3_impl(goofer_ctx *ctx, const float2 *S_h, const float2 *S_u
 {
     const goofer_plan_t &p = ctx->plan;
     const int halo = (p.n_fft + p.hop - 1) / p.hop - 1;
-    const size_t lds = sizeof(float2) * (M + M / 2 + 1 + WAVES_PER_BLOCK * fft_cfg<M>::BUF) + sizeof(float) * 2 * M +
-                       sizeof(float) * WAVES_PER_BLOCK * 3 * 2 * M + 16 +
-                       (p.hop <= (M >= 1024 ? 512 : 256) ? sizeof(double) * WAVES_PER_BLOCK * (p.hop / MASK_DS + KNOT_MARGIN) : 0);
+    // (hops wider than the slots park no knots)
+    const size_t lds = ola_lds<M, WAVES_PER_BLOCK, 3>::bytes(p.hop <= WAVE * ola3_slots<M> ? p.hop / MASK_DS + KNOT_MARGIN : 0);
     int rc = kernel_allow_max_lds(ctx, (const void *)k_irfft_ola3<M>);
     if (rc) return rc;
     int slots = 0;                                            // waves of this kernel the device holds at once

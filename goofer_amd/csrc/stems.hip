@@ -25,6 +25,7 @@
 #include "fft_core.h"
 #include "samples_core.h"
 #include "stems_core.h"
+#include "ola_walk.h"
 #include "launchers.h"
 
 
@@ -148,14 +149,8 @@ template <int M, int NTAB, bool WIN, bool WS_LDS = false> struct walker {
             for (int g = 0; g < G; ++g)
 #pragma unroll
                 for (int c = 0; c < 2; ++c) {
-                    const int j = 2 * ((int)threadIdx.x + WAVE * g) + c;
-                    float ws = 0.f;
-                    for (int q = (NF - 1 - j) / HOP; q >= 0; --q) {       // ascending frame order = descending offset
-                        const float wv = g_win[j + q * HOP];
-                        ws += wv * wv;
-                    }
-                    wst[(2 * g + c) * WAVE + threadIdx.x] = ws;
-                    wst[(2 * G + 2 * g + c) * WAVE + threadIdx.x] = 1.0f / ws;
+                    ola_full_ws(g_win, NF, HOP, 2 * ((int)threadIdx.x + WAVE * g) + c, wst[(2 * g + c) * WAVE + threadIdx.x],
+                                wst[(2 * G + 2 * g + c) * WAVE + threadIdx.x]);
                 }
         }
         __syncthreads();
@@ -182,13 +177,9 @@ template <int M, int NTAB, bool WIN, bool WS_LDS = false> struct walker {
     __device__ __forceinline__ bool range(int64_t total_frames, int run, const int *frame_note, const int64_t *frame_off, int64_t &fs,
                                           int64_t &f0, int64_t &f1)
     {
-        const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-        f0 = ((int64_t)blockIdx.x * WAVES_PER_BLOCK + wave) * run;
+        f0 = ola_run_first(blockIdx.x, WAVES_PER_BLOCK, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), run);
         if (f0 >= total_frames) return false;
-        f1 = f0 + run < total_frames ? f0 + run : total_frames;
-        const int64_t t0 = f0 - frame_off[frame_note[f0]];
-        constexpr int halo = NF / HOP - 1;
-        fs = f0 - (t0 < halo ? t0 : halo);
+        ola_run_span(f0, run, NF / HOP - 1, total_frames, frame_note, frame_off, fs, f1);
         return true;
     }
 
@@ -262,18 +253,10 @@ template <int M, int NTAB, bool WIN, bool WS_LDS = false> struct walker {
 
     // Overlap-add divisor of this lane's sample (g, c) of hop h (GOOFER.py:385-389): the summed squared window over the
     // frames that exist.  Interior hops (wave-uniform test) have the per-lane constant and its reciprocal at hand.
-    __device__ __forceinline__ bool interior(int h) const { return h >= (NF - 1) / HOP && h <= T - 1; }
+    __device__ __forceinline__ bool interior(int h) const { return ola_interior(h, ola_max_back(NF, HOP), T); }
     __device__ __forceinline__ float partial_ws(int h, int g, int c, const float *g_win) const
     {
-        const int j = 2 * (lane + WAVE * g) + c;
-        const int back = (NF - 1 - j) / HOP;
-        const int flo = h - back < 0 ? 0 : h - back, fhi = h > T - 1 ? T - 1 : h;
-        float ws = 0.f;
-        for (int fr = flo; fr <= fhi; ++fr) {
-            const float w = g_win[j + (h - fr) * HOP];
-            ws += w * w;
-        }
-        return ws;
+        return ola_partial_ws(g_win, NF, HOP, T, h, 2 * (lane + WAVE * g) + c);
     }
 };
 
@@ -370,6 +353,8 @@ __global__ __launch_bounds__(256, 2) void k_noise_stems(const noise_args A)
 
     // The smoothed-mask knots a hop needs are fetched lane-parallel a frame ahead and parked in LDS, so the output stage
     // reads them with LDS latency instead of issuing dependent global loads per sample.
+    // (knot_window of ola_walk.h as this kernel's own text, like the finished-hop loops below and in k_harm_stem: on the shared
+    // pieces the stage measured 0.4116 ms against the parent's 0.4053 .. 0.4082, or the resource line moved; docs/EXPERIMENTS.md)
     double kn_r[KPL];
     int kn_lo = 0;
     auto knots_fetch = [&](int h) {

@@ -1,21 +1,25 @@
 #!/usr/bin/env python
 """Do two builds of libgoofer_hip.so compute the same bits?  The before / after check of a refactor of shared kernel code.
 
-usage: scripts/lib_bits.py <libA.so> <libB.so> [--out FILE] [--limit SECONDS] [--set ragged|stages|all]
+usage: scripts/lib_bits.py <libA.so> <libB.so> [--out FILE] [--limit SECONDS] [--set ragged|stages|walkers|all]
 
 Each library gets one fresh child process (GOOFER_HIP_LIB set, as scripts/lib_ab.sh does) under its own `timeout -k 10`; the
 second starts only if the first exited 0.  A child runs a fixed, seeded case list twice and prints {case: {output: sha256}} of
-both runs.  Two sets of cases (default: all):
+both runs.  Three sets of cases (default: all):
   ragged  the entry points that reach the kernels built on csrc/ragged.h — the post chain, the cascade, the synthesis on its
           spectra routes with the jitter, vibrato and sub-harmonic keyword sets, normal_fill, smooth_mask_ds, irfft_ola
   stages  the stages built on csrc/tile_scan.h, each on its own test batches at its test rates — loudness measured and normalised
           (seg_energy, loud, gain, y), the compressor under the settings of tests/test_gpu_compress.py with the curve and all
           four combinations of compress_skip and compress_store (y, max_reduction, yl), the equaliser at K = 1 .. 8 (y) — and
           each once on loudness_ref.long_signal(), whose 4116 tiles send a round's carry through thread 0 of the carry kernels
+  walkers the four frame walkers (csrc/ola_walk.h) on synth_ref.long_batch through tests/test_gpu_walker_runs._walk: every route of
+          its WALKERS table at walk_run 0 and at one forced run (95; 256 for k_irfft_ola1), once with injected phases and once
+          with Philox — harm, uv, bre, rec, mix, note_mag, note_peak and, where the route has one, the frame_skip view
 
 An output whose digest differs between the two runs of one library is listed as non-deterministic and not compared across the
 libraries.  Only outputs behind k_note_sumsq are expected there (post chain, notes with tension != 0 that are longer than a
-workgroup: float64 atomics across workgroups).  Anything else listed there is a finding: the stages use no floating-point atomic.
+workgroup: float64 atomics across workgroups).  Anything else listed there is a finding: the stages and the walkers use no
+floating-point atomic but the exact max of non-negative floats.
 
 Writes {"A": .., "B": .., "nondeterministic": [..], "differ": [..]} to FILE (default: standard output only) and prints the two
 lists; exit status 1 if an output differs, the child's if a child failed.
@@ -174,10 +178,34 @@ def _ragged_cases(ctx):
     return out
 
 
+def _walker_cases(ctx):
+    """{case: {output name: sha256}} of one pass over the frame walkers on csrc/ola_walk.h"""
+    import test_gpu_synth_stages as ST
+    import test_gpu_walker_runs as WR
+    out = {}
+    try:
+        for route, (counters, cap) in WR.WALKERS.items():
+            has_skip = ST.ROUTES[route][4]
+            ST._set(ctx, ST.ROUTES[route][1])
+            for run in (0, 256 if "walk_run_ola1" in counters else 95):
+                for tag, seed in (("phi", None), ("philox", 20240611)):
+                    d = WR._walk(ctx, route, run, seed=seed)
+                    if has_skip:
+                        d["frame_skip"] = ctx.debug_fetch("frame_skip")
+                    out["walkers/%s/run%d/%s" % (route, run, tag)] = {k: _sha(d[k]) for k in WR.OUTS + ("note_mag", "note_peak") +
+                                                                      (("frame_skip",) if has_skip else ())}
+    finally:
+        ctx.set_option("walk_run", 0)
+        ST._restore(ctx)
+    return out
+
+
 def _cases(ctx, which):
     out = _ragged_cases(ctx) if which in ("ragged", "all") else {}
     if which in ("stages", "all"):
         out.update(_stage_cases(ctx))
+    if which in ("walkers", "all"):
+        out.update(_walker_cases(ctx))
     return out
 
 
@@ -205,7 +233,7 @@ def main(argv):
             opts[a] = next(it)
         else:
             libs.append(a)
-    if len(libs) != 2 or opts["--set"] not in ("ragged", "stages", "all"):
+    if len(libs) != 2 or opts["--set"] not in ("ragged", "stages", "walkers", "all"):
         sys.exit(__doc__)
     runs = {}
     for tag, lib in zip("AB", libs):

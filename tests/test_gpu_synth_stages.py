@@ -132,6 +132,23 @@ no third yardstick was needed for the Bluestein stages and no factor was raised)
       note_mag  3.3e-07 / 2.1e-07 (0.27)   frames    6.2e-07 / 5.9e-07 (0.76)   harm      2.0e-07 / 2.8e-07 (0.82)
       uv        2.7e-07 / 3.6e-07 (0.89)   bre       2.1e-07 / 3.0e-07 (0.86)   rec       1.5e-07 / 2.6e-07 (0.98)
       mix       2.0e-07 / 3.0e-07 (0.90)   note_peak 2.7e-07 / 2.0e-07 (0.31)
+The three inputs of the LDS-ring walkers that no table reached (the largest ratio is 2.00; the same figures under the build
+before the walkers moved onto csrc/ola_walk.h and after, whose bits are the same):
+  44100/2048/512, stems 0: k_irfft_ola3<1024>, eight register slots per hop
+      S_harm    3.7e-07 / 4.0e-07 (0.74)   S_uv      8.5e-08 / 2.8e-07 (1.90)   S_breath  9.3e-08 / 3.1e-07 (2.00)
+      note_mag  1.4e-07 / 2.3e-07 (0.82)   harm      1.8e-07 / 3.1e-07 (1.06)   uv        2.2e-07 / 3.2e-07 (0.91)
+      bre       2.7e-07 / 3.5e-07 (0.87)   rec       1.4e-07 / 2.7e-07 (1.11)   mix       2.4e-07 / 3.8e-07 (1.10)
+      note_peak 2.0e-07 / 1.8e-07 (0.29)
+  44100/1024/512: k_irfft_ola3<512>, a hop wider than its slots (halo 1)
+      S_harm    2.3e-07 / 2.9e-07 (0.74)   S_uv      9.2e-08 / 2.6e-07 (1.56)   S_breath  7.3e-08 / 2.3e-07 (1.55)
+      note_mag  1.9e-07 / 1.7e-07 (0.29)   harm      2.3e-07 / 4.3e-07 (1.35)   uv        2.7e-07 / 3.7e-07 (0.91)
+      bre       2.1e-07 / 3.6e-07 (1.16)   rec       2.0e-07 / 3.9e-07 (1.37)   mix       1.8e-07 / 3.9e-07 (1.50)
+      note_peak 2.0e-07 / 2.8e-07 (0.81)
+  44100/2048/1024: k_irfft_ola1, knots from global memory, no frame_skip (halo 1)
+      S_harm    1.7e-07 / 3.2e-07 (1.18)   S_uv      9.8e-08 / 2.7e-07 (1.49)   S_breath  1.0e-07 / 2.8e-07 (1.55)
+      note_mag  1.6e-07 / 2.1e-07 (0.56)   harm      1.0e-07 / 2.1e-07 (0.87)   uv        2.0e-07 / 3.0e-07 (0.91)
+      bre       1.9e-07 / 3.0e-07 (0.97)   rec       2.5e-07 / 3.2e-07 (0.80)   mix       1.9e-07 / 2.8e-07 (0.85)
+      note_peak 2.5e-07 / 1.9e-07 (0.30)
 """
 import numpy as np
 import pytest
@@ -163,6 +180,9 @@ ROUTES = {
     "ola3_256": ((22050, 512, 128), {}, OLA, "fused", False),
     "ola1_skip": ((44100, 2048, 512), {}, OLA, "fused", True),
     "ola1_hop96": ((96000, 2048, 96), {}, OLA, "fused", True),
+    "ola3_2048": ((44100, 2048, 512), {"stems": 0}, OLA, "fused", False),      # k_irfft_ola3<1024>: eight register slots per hop
+    "ola3_wide": ((44100, 1024, 512), {}, OLA, "fused", False),               # a hop wider than k_irfft_ola3's slots (halo 1)
+    "ola1_wide": ((44100, 2048, 1024), {}, OLA, "fused", False),              # k_irfft_ola1, knots from global memory, no frame_skip
     "radix3": ((44100, 768, 192), {}, OLA, "separate", False),
     "bluestein": ((44100, 1000, 250), {}, OLA, "separate", False),
     "workgroup": ((48000, 4096, 1024), {}, OLA, "separate", False),

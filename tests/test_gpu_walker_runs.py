@@ -52,6 +52,22 @@ over the six runs on the walkers and td_blur 0 routes, 0 with skip_zero 0 and on
       note_mag  1.7e-07 / 1.6e-07 (0.24)   harm      2.0e-07 / 3.1e-07 (0.93)   bre       3.5e-07 / 5.4e-07 (1.18)
       rec       2.5e-07 / 3.9e-07 (1.09)   mix       2.5e-07 / 4.5e-07 (1.32)   note_peak 2.5e-07 / 3.2e-07 (0.78)
       uv        3.1e-07 / 4.2e-07 (0.96)
+  ola3_2048 (k_irfft_ola3<1024>), walk_run 62, 65, 95, 128
+      S_harm    2.2e-07 / 2.8e-07 (0.75)   S_uv      7.3e-08 / 2.2e-07 (1.46)   S_breath  1.3e-07 / 3.1e-07 (1.46)
+      note_mag  2.1e-07 / 2.2e-07 (0.50)   harm      1.4e-07 / 2.5e-07 (0.91)   bre       2.0e-07 / 3.2e-07 (1.03)
+      rec       1.8e-07 / 2.9e-07 (0.92)   mix       1.9e-07 / 2.9e-07 (0.89)   note_peak 2.7e-07 / 2.3e-07 (0.43)
+      uv        2.2e-07 / 2.9e-07 (0.75)
+  ola3_wide (hop 512 at n_fft 1024: wider than the kernel's slots), walk_run 62, 65, 95, 128
+      S_harm    2.3e-07 / 3.2e-07 (0.88)   S_uv      1.0e-07 / 2.6e-07 (1.43)   S_breath  1.4e-07 / 3.1e-07 (1.41)
+      note_mag  2.4e-07 / 2.1e-07 (0.38)   harm      2.3e-07 / 3.1e-07 (0.85)   bre       2.8e-07 / 4.0e-07 (1.04)
+      rec       1.6e-07 / 2.6e-07 (0.88)   mix       2.4e-07 / 3.6e-07 (1.00)   note_peak 3.3e-07 / 1.6e-07 (0.12)
+      uv        2.2e-07 / 3.2e-07 (0.92)
+  ola1_wide (hop 1024 at n_fft 2048: knots from global memory, no frame_skip), walk_run 95, 256
+      S_harm    1.8e-07 / 2.6e-07 (0.75)   S_uv      7.1e-08 / 2.2e-07 (1.45)   S_breath  1.1e-07 / 2.9e-07 (1.53)
+      note_mag  1.1e-07 / 2.0e-07 (0.71)   harm      1.9e-07 / 3.0e-07 (0.99)   bre       1.7e-07 / 3.2e-07 (1.17)
+      rec       2.2e-07 / 2.9e-07 (0.76)   mix       1.9e-07 / 2.9e-07 (0.90)   note_peak 2.2e-07 / 1.6e-07 (0.20)
+      uv        2.1e-07 / 3.6e-07 (1.17)
+Zero-sign differences on the three, forced runs against walk_run 0: 0.
 """
 import numpy as np
 import pytest
@@ -69,11 +85,12 @@ OUTS = ("harm", "uv", "bre", "rec", "mix")
 # route: (the counters of the walkers it launches, their cap)
 WALKERS = {"walkers": (("walk_run_noise", "walk_run_harm"), 128), "walkers_td_blur0": (("walk_run_noise", "walk_run_harm"), 128),
            "walkers_skip_zero0": (("walk_run_noise", "walk_run_harm"), 128), "ola3": (("walk_run_ola3",), 128),
-           "ola3_256": (("walk_run_ola3",), 128), "ola1_skip": (("walk_run_ola1",), 256), "ola1_hop96": (("walk_run_ola1",), 256)}
+           "ola3_256": (("walk_run_ola3",), 128), "ola1_skip": (("walk_run_ola1",), 256), "ola1_hop96": (("walk_run_ola1",), 256),
+           "ola3_2048": (("walk_run_ola3",), 128), "ola3_wide": (("walk_run_ola3",), 128), "ola1_wide": (("walk_run_ola1",), 256)}
 TRUTH_RUNS = {"walkers": (62, 65, 95, 128), "ola3": (62, 65, 95, 128), "ola3_256": (62, 65, 95, 128), "ola1_skip": (95, 256),
-              "ola1_hop96": (256,)}
+              "ola1_hop96": (256,), "ola3_2048": (62, 65, 95, 128), "ola3_wide": (62, 65, 95, 128), "ola1_wide": (95, 256)}
 BIT_RUNS = dict({r: (61, 62, 64, 65, 95, 128) for r in ("walkers", "walkers_td_blur0", "walkers_skip_zero0", "ola3", "ola3_256")},
-                ola1_skip=(95, 256), ola1_hop96=(256,))
+                ola1_skip=(95, 256), ola1_hop96=(256,), ola3_2048=(62, 65, 95, 128), ola3_wide=(62, 65, 95, 128), ola1_wide=(95, 256))
 
 _long = {}
 
