@@ -77,6 +77,10 @@ LEGACY_F32 = 1
 PHRASE_NOTE = np.dtype([("start", "<i8"), ("skip", "<i4"), ("take", "<i4"), ("pos", "<f4", 7), ("val", "<f4", 7)], align=True)
 PHRASE_TILE = 2048              # GOOFER_PHRASE_TILE
 
+# goofer_bus_track (goofer_host_bus_plan / goofer_bus_mix): x is a device pointer
+BUS_TRACK = np.dtype([("x", "<u8"), ("len", "<i8"), ("start", "<i8"), ("gl", "<f4"), ("gr", "<f4")], align=True)
+BUS_TILE = 2048                 # GOOFER_BUS_TILE
+
 
 class Assembly(C.Structure):
     """goofer_assembly"""
@@ -254,6 +258,13 @@ EXPORTS = {
     "goofer_reverb": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float,
                                 C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                 C.POINTER(C.c_int64), C.c_void_p]),
+    "goofer_host_bus_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    "goofer_bus_mix": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "goofer_limit_linked": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p,
+                                      C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "goofer_loudness_link": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
+    "goofer_pcm16_planar": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
     "goofer_smooth_mask_ds": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_int, C.c_void_p,
                                         C.c_void_p]),
 }

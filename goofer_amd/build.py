@@ -10,7 +10,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libgoofer_hip.so")
-SOURCES = ["api.hip", "synth.hip", "fft.hip", "pulse.hip", "binops.hip", "samples.hip", "assemble.hip", "stems.hip", "analysis.hip", "jitter.hip", "noise.hip", "post.hip", "resample.hip", "planner.hip", "tracker.hip", "f0.hip", "phrase.hip", "rate.hip", "limit.hip", "loudness.hip", "compress.hip", "eq.hip", "reverb.hip"]
+SOURCES = ["api.hip", "synth.hip", "fft.hip", "pulse.hip", "binops.hip", "samples.hip", "assemble.hip", "stems.hip", "analysis.hip", "jitter.hip", "noise.hip", "post.hip", "resample.hip", "planner.hip", "tracker.hip", "f0.hip", "phrase.hip", "rate.hip", "limit.hip", "loudness.hip", "compress.hip", "eq.hip", "reverb.hip", "bus.hip"]
 HOST_ONLY = ("planner.hip",)      # host code in the library: no kernel, cannot change what a counter pass measures
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unused-function", "-Wno-align-mismatch"]
 

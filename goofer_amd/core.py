@@ -1123,6 +1123,38 @@ def loudness_batch(signals, sr, target=None, max_gain_db=20.0, ctx=None):
     return (None if y is None else _by_csr(y, plan.in_off)), loud.cpu().numpy(), gain.cpu().numpy(), _by_csr(seg, plan.seg_off)
 
 
+def bus_mix(xs, sr, tracks, loudness=None, limit=None, ctx=None):
+    """Finished tracks panned and mixed onto a stereo bus in one device pass (goofer_amd.bus; goofer_bus_mix): ``xs``, 1-D
+    arrays at ``sr``, one ``bus.Track`` (or its ``(gain_db, pan, start_ms, mute)`` prefix) each.  ``loudness``: None, a target
+    in LUFS or a ``(target, max_gain_db)`` pair: the stereo programme measured on the sum of the two channels' energies and
+    both channels scaled by one gain (goofer_loudness_link).  ``limit``: None or what ``limit_batch``'s ``Renderer`` form
+    takes (``limit.parse``; the true-peak triple included): the channel-linked limiter (goofer_limit_linked).  Returns the
+    fp32 frames ``[N, 2]``, N the largest start + length of a track that sounds, and a dict of the stages' statistics
+    (``lufs_in``, ``momentary_max``, ``gain``; ``peak_in``, ``min_gain``).  This project's own definition
+    (include/goofer_hip.h)."""
+    from . import bus as B
+    from . import limit as LM
+    from . import loudness as LD
+    xs = _signal_arrays(xs)
+    tracks = [t if isinstance(t, B.Track) else B.Track(*t) for t in tracks]
+    loudness, limit = None if loudness is None else LD.parse(loudness), None if limit is None else LM.parse(limit)
+    c = ctx or default_context()
+    ds = [c.tensor(np.concatenate([x, np.zeros(1, dtype=np.float32)])) for x in xs]      # (never an empty tensor)
+    plan = B.plan(ds, [len(x) for x in xs], tracks, sr)
+    N, stats = plan.total_out, {}
+    bus = c.bus_mix(ds, plan)
+    if loudness is not None:
+        bus, loud, gain, _ = c.loudness(bus, None, LD.plan(sr, [N, N]), *loudness, channels=2)
+    if limit is not None:
+        bus, peak, gmin = c.limit(bus, None, LM.plan(sr, [N, N], *limit, channels=2))
+    c.check()
+    if loudness is not None:
+        stats.update({"lufs_in": float(loud.cpu()[0, 0]), "momentary_max": float(loud.cpu()[0, 1]), "gain": float(gain.cpu()[0])})
+    if limit is not None:
+        stats.update({"peak_in": float(peak.cpu()[0]), "min_gain": float(gmin.cpu()[0])})
+    return np.ascontiguousarray(bus.cpu().numpy().reshape(2, N).T), stats
+
+
 def compress_batch(signals, sr, threshold_db, ratio, knee_db=6.0, attack_ms=5.0, release_ms=100.0, makeup_db=0.0, curve=False, ctx=None):
     """Many signals through the dynamic range compressor in one device pass (goofer_amd.compress; goofer_compress): ``signals``,
     1-D arrays at ``sr`` (8000 to 192000 Hz), each compressed above ``threshold_db`` (dB re full scale) at ``ratio`` with a soft

@@ -135,7 +135,8 @@ int launch_volume_jitter(goofer_ctx *ctx, float *harm, float *bre, const double 
 
 // limit.hip
 int launch_limit(goofer_ctx *ctx, const float *x, const int64_t *in_off, int n, int W, const float *taps, float c, const int32_t *tiles,
-                 int64_t n_tiles, float *out, float *peak_in, float *min_gain, hipStream_t st, int R = 0, const float *tp_taps = nullptr);
+                 int64_t n_tiles, float *out, float *peak_in, float *min_gain, hipStream_t st, int R = 0, const float *tp_taps = nullptr,
+                 int ch = 1);
 
 // loudness.hip
 int launch_loudness_measure(goofer_ctx *ctx, const float *x, const int64_t *in_off, int n, int S, const double *coef, const double *mats,

@@ -105,7 +105,10 @@ __device__ __forceinline__ void tp_envelope(const float *__restrict__ X, int R, 
     }
 }
 
-template <bool TP>
+// CH: the channels of a group (goofer_limit_linked), signals sig CH .. sig CH + CH - 1 of equal length lying back to back; a and
+// so r, the gain and the statistics are the group's.  CH == 1 is goofer_limit / goofer_limit_tp: every loop over the channels
+// has one round and `n` counts signals.
+template <bool TP, int CH>
 __global__ __launch_bounds__(LM_THREADS)
 void k_limit(const float *__restrict__ x, const int64_t *__restrict__ in_off, int n, int W, int span, const float *__restrict__ taps, float c,
              const int32_t *__restrict__ tiles, float *__restrict__ out, float *__restrict__ peak_in, float *__restrict__ min_gain, int skip,
@@ -115,12 +118,15 @@ void k_limit(const float *__restrict__ x, const int64_t *__restrict__ in_off, in
     __shared__ float s_pk[LM_THREADS / 64];
     const int tid = threadIdx.x;
     const int sig = __builtin_amdgcn_readfirstlane(tiles[2 * blockIdx.x]), kt = __builtin_amdgcn_readfirstlane(tiles[2 * blockIdx.x + 1]);
-    if (sig < 0 || sig >= n || kt < 0) return;                  // (a table that is not the planner's: nothing is read or written)
-    const int64_t base = in_off[sig], len = in_off[sig + 1] - base, t0 = (int64_t)kt * LM_T;
+    if (sig < 0 || sig >= n / CH || kt < 0) return;             // (a table that is not the planner's: nothing is read or written)
+    const int64_t base = in_off[sig * CH], len = in_off[sig * CH + 1] - base, t0 = (int64_t)kt * LM_T;
     if (t0 >= len) return;
+#pragma unroll
+    for (int ch = 1; ch < CH; ++ch)
+        if (in_off[sig * CH + ch + 1] - in_off[sig * CH + ch] != len) return;   // (channels of unequal length: likewise)
     const int NA = LM_T + 4 * W, NB = LM_T + 2 * W;             // r on [t0 - 2W, t0 + T + 2W), d on [t0 - W, t0 + T + W)
     float *__restrict__ A = s_lim, *__restrict__ B = s_lim + NA;   // (NA is a multiple of 4: B is 16-byte aligned; B has NB + 4 entries)
-    const float *__restrict__ xs = x + base;
+    const float *__restrict__ xs = x + base;                    // channel ch: xs + ch len
     float *__restrict__ ys = out + base;
     const int live = (int)(len - t0 < LM_T ? len - t0 : LM_T);  // samples of the tile that exist
 
@@ -129,32 +135,40 @@ void k_limit(const float *__restrict__ x, const int64_t *__restrict__ in_off, in
     bool over = false;
     if constexpr (TP) {
         // x on [t0 - 2W - Z, t0 + T + 2W + Z + TP_CH) where B will live; the r of the tile's own samples behind it
+        // one channel after the other through the same X: the r of a later channel joins the one in A by a minimum (min_c c / e_c
+        // = c / max_c e_c; a thread meets its own entries again, so no barrier lies between the two)
         const int NX = NA + TP_WIN;
         float *__restrict__ X = B, *__restrict__ Rt = B + NX;
-        for (int k = tid; k < NX; k += LM_THREADS) {
-            const int64_t p = t0 - 2 * W - TP_Z + k;
-            X[k] = p >= 0 && p < len ? xs[p] : 0.0f;
-        }
-        __syncthreads();
-        for (int k0 = tid * TP_CH; k0 < NA; k0 += LM_THREADS * TP_CH) {     // (NA is a multiple of 4: the last step may be half one)
-            const int64_t p0 = t0 - 2 * W + k0;
-            float e[TP_CH];
-            const bool inside = p0 + TP_CH > 0 && p0 < len;
-            if (inside) tp_envelope(X + k0, R, tp_taps, p0, e);
+#pragma unroll 1
+        for (int ch = 0; ch < CH; ++ch) {
+            const float *__restrict__ xc = xs + ch * len;
+            if (ch > 0) __syncthreads();                        // (the channel before has read X)
+            for (int k = tid; k < NX; k += LM_THREADS) {
+                const int64_t p = t0 - 2 * W - TP_Z + k;
+                X[k] = p >= 0 && p < len ? xc[p] : 0.0f;
+            }
+            __syncthreads();
+            for (int k0 = tid * TP_CH; k0 < NA; k0 += LM_THREADS * TP_CH) {     // (NA is a multiple of 4: the last step may be half one)
+                const int64_t p0 = t0 - 2 * W + k0;
+                float e[TP_CH];
+                const bool inside = p0 + TP_CH > 0 && p0 < len;
+                if (inside) tp_envelope(X + k0, R, tp_taps, p0, e);
 #pragma unroll
-            for (int i = 0; i < TP_CH; ++i) {
-                const int k = k0 + i;
-                const int64_t p = p0 + i;
-                if (k < NA) {
-                    float r = 1.0f;
-                    const bool own = k >= 2 * W && k < 2 * W + LM_T;
-                    if (inside && p >= 0 && p < len) {
-                        r = limit_r(e[i], c);
-                        over |= e[i] > c;
-                        if (own) pk = fmaxf(pk, e[i]);
+                for (int i = 0; i < TP_CH; ++i) {
+                    const int k = k0 + i;
+                    const int64_t p = p0 + i;
+                    if (k < NA) {
+                        float r = 1.0f;
+                        const bool own = k >= 2 * W && k < 2 * W + LM_T;
+                        if (inside && p >= 0 && p < len) {
+                            r = limit_r(e[i], c);
+                            over |= e[i] > c;
+                            if (own) pk = fmaxf(pk, e[i]);
+                        }
+                        if (ch > 0) r = fminf(r, A[k]);
+                        A[k] = r;
+                        if (own) Rt[k - 2 * W] = r;
                     }
-                    A[k] = r;
-                    if (own) Rt[k - 2 * W] = r;
                 }
             }
         }
@@ -163,7 +177,9 @@ void k_limit(const float *__restrict__ x, const int64_t *__restrict__ in_off, in
             const int64_t p = t0 - 2 * W + k;
             float r = 1.0f;
             if (p >= 0 && p < len) {
-                const float a = fabsf(xs[p]);
+                float a = fabsf(xs[p]);
+#pragma unroll
+                for (int ch = 1; ch < CH; ++ch) a = fmaxf(a, fabsf(xs[ch * len + p]));
                 r = limit_r(a, c);
                 over |= a > c;
                 if (k >= 2 * W && k < 2 * W + LM_T) pk = fmaxf(pk, a);
@@ -181,7 +197,9 @@ void k_limit(const float *__restrict__ x, const int64_t *__restrict__ in_off, in
         limit_stat_max(peak_in + sig, pk);
     }
     if (!any && skip) {
-        for (int e = tid; e < live; e += LM_THREADS) ys[t0 + e] = xs[t0 + e];
+#pragma unroll
+        for (int ch = 0; ch < CH; ++ch)
+            for (int e = tid; e < live; e += LM_THREADS) ys[ch * len + t0 + e] = xs[ch * len + t0 + e];
         return;
     }
 
@@ -259,13 +277,19 @@ void k_limit(const float *__restrict__ x, const int64_t *__restrict__ in_off, in
 #pragma unroll
         for (int e = 0; e < LM_SPT; ++e) {
             if (o + e < live) {
-                const float xv = xs[t0 + o + e];
+                float xv[CH], a = 0.0f;
+#pragma unroll
+                for (int ch = 0; ch < CH; ++ch) {
+                    xv[ch] = xs[ch * len + t0 + o + e];
+                    a = ch == 0 ? fabsf(xv[0]) : fmaxf(a, fabsf(xv[ch]));
+                }
                 float r;
                 if constexpr (TP) r = s_lim[NA + NA + TP_WIN + o + e];     // (Rt of step 1)
-                else r = limit_r(fabsf(xv), c);
+                else r = limit_r(a, c);
                 const float s = fmaxf(1.0f - acc[e], 0.0f);
                 const float g = fminf(s, r);
-                ys[t0 + o + e] = xv * g;
+#pragma unroll
+                for (int ch = 0; ch < CH; ++ch) ys[ch * len + t0 + o + e] = xv[ch] * g;
                 gmin = fminf(gmin, g);
             }
         }
@@ -314,43 +338,55 @@ void k_true_peak(const float *__restrict__ x, const int64_t *__restrict__ in_off
     }
 }
 
-// R == 0: sample peaks (goofer_limit); R == 2 or 4 with tp_taps: true-peak detection (goofer_limit_tp)
+// one launch of k_limit<TP, CH>: `lds` dynamic bytes, `allow` the opt-in above 64 KB (beside s_pk's static bytes)
+template <bool TP, int CH>
+static int limit_launch(goofer_ctx *ctx, size_t lds, int allow, const float *x, const int64_t *in_off, int n, int W, int span, const float *taps,
+                        float c, const int32_t *tiles, int64_t n_tiles, float *out, float *peak_in, float *min_gain, int skip, int R,
+                        const float *tp_taps, hipStream_t st)
+{
+    if (lds > 64 * 1024)
+        if (int rc = kernel_allow_max_lds(ctx, (const void *)k_limit<TP, CH>, allow)) return rc;
+    hipLaunchKernelGGL((k_limit<TP, CH>), dim3((unsigned)n_tiles), dim3(LM_THREADS), lds, st, x, in_off, n, W, span, taps, c, tiles, out, peak_in,
+                       min_gain, skip, R, tp_taps);
+    LAUNCH_CHECK(ctx);
+    return GOOFER_OK;
+}
+
+// R == 0: sample peaks (goofer_limit); R == 2 or 4 with tp_taps: true-peak detection (goofer_limit_tp); ch: the channels of a
+// group (goofer_limit_linked), n / ch groups and statistics
 int launch_limit(goofer_ctx *ctx, const float *x, const int64_t *in_off, int n, int W, const float *taps, float c, const int32_t *tiles,
-                 int64_t n_tiles, float *out, float *peak_in, float *min_gain, hipStream_t st, int R, const float *tp_taps)
+                 int64_t n_tiles, float *out, float *peak_in, float *min_gain, hipStream_t st, int R, const float *tp_taps, int ch)
 {
     if (n <= 0) return GOOFER_OK;
-    hipLaunchKernelGGL(k_limit_init, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, peak_in, min_gain);
+    const int groups = n / ch;
+    hipLaunchKernelGGL(k_limit_init, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, st, groups, peak_in, min_gain);
     LAUNCH_CHECK(ctx);
     if (n_tiles <= 0) return GOOFER_OK;
     int span = 1;
     while (2 * span <= 2 * W + 1) span *= 2;
     if (R) {
-        // r, x (later d) and the tile's own r: 56 960 bytes at W = 240, 82 048 at W = 1024
+        // r, x (later d) and the tile's own r: 56 960 bytes at W = 240, 82 048 at W = 1024; the channels share them
         const size_t lds = (2 * (size_t)(LM_T + 4 * W) + TP_WIN + LM_T) * sizeof(float);
-        if (lds > 64 * 1024)
-            if (int rc = kernel_allow_max_lds(ctx, (const void *)k_limit<true>, 96 * 1024)) return rc;   // (beside s_pk's static bytes)
-        hipLaunchKernelGGL(k_limit<true>, dim3((unsigned)n_tiles), dim3(LM_THREADS), lds, st, x, in_off, n, W, span, taps, c, tiles, out, peak_in,
-                           min_gain, ctx->limit_tp_skip ? 1 : 0, R, tp_taps);
-        LAUNCH_CHECK(ctx);
-        return GOOFER_OK;
+        const int skip = ctx->limit_tp_skip ? 1 : 0;
+        return ch == 2 ? limit_launch<true, 2>(ctx, lds, 96 * 1024, x, in_off, n, W, span, taps, c, tiles, n_tiles, out, peak_in, min_gain, skip, R, tp_taps, st)
+                       : limit_launch<true, 1>(ctx, lds, 96 * 1024, x, in_off, n, W, span, taps, c, tiles, n_tiles, out, peak_in, min_gain, skip, R, tp_taps, st);
     }
     const size_t lds = ((size_t)(LM_T + 4 * W) + (size_t)(LM_T + 2 * W + 4)) * sizeof(float);   // 57 360 bytes at W = 1024
-    if (lds > 64 * 1024)
-        if (int rc = kernel_allow_max_lds(ctx, (const void *)k_limit<false>)) return rc;
-    hipLaunchKernelGGL(k_limit<false>, dim3((unsigned)n_tiles), dim3(LM_THREADS), lds, st, x, in_off, n, W, span, taps, c, tiles, out, peak_in,
-                       min_gain, ctx->limit_skip ? 1 : 0, 0, (const float *)nullptr);
-    LAUNCH_CHECK(ctx);
-    return GOOFER_OK;
+    const int skip = ctx->limit_skip ? 1 : 0;
+    return ch == 2 ? limit_launch<false, 2>(ctx, lds, 160 * 1024, x, in_off, n, W, span, taps, c, tiles, n_tiles, out, peak_in, min_gain, skip, 0, nullptr, st)
+                   : limit_launch<false, 1>(ctx, lds, 160 * 1024, x, in_off, n, W, span, taps, c, tiles, n_tiles, out, peak_in, min_gain, skip, 0, nullptr, st);
 }
 
-// the checks of goofer_limit and goofer_limit_tp (`tp`: R, Z and tp_taps too), then the launch
+// the checks of goofer_limit, goofer_limit_tp (`tp`: R, Z and tp_taps too) and goofer_limit_linked (`ch` channels a group: the
+// tile table is the planner's for the n / ch groups), then the launch
 static int limit_entry(goofer_ctx *ctx, const char *who, bool tp, const float *x, const int64_t *in_off, int n, int64_t total, int W,
                        const float *taps, float c, const int32_t *tiles, int64_t n_tiles, float *out, float *peak_in, float *min_gain, int R,
-                       int Z, const float *tp_taps, void *stream)
+                       int Z, const float *tp_taps, void *stream, int ch = 1)
 {
     if (!ctx) return GOOFER_EINVAL;
     if (int rc = check_counts(ctx, who, n, total, n_tiles)) return rc;
-    if (W < 1 || W > GOOFER_LIMIT_MAX_LOOK || !(c > 0.0f && c <= 1.0f) || !signal_tiles_ok(LM_T, n, total, n_tiles))
+    if ((ch != 1 && ch != 2) || n % ch != 0) return goofer_fail(ctx, GOOFER_EINVAL, "%s: %d signals in groups of %d channels (1 or 2)", who, n, ch);
+    if (W < 1 || W > GOOFER_LIMIT_MAX_LOOK || !(c > 0.0f && c <= 1.0f) || !signal_tiles_ok(LM_T, n / ch, total / ch, n_tiles))
         return goofer_fail(ctx, GOOFER_EINVAL, "%s: W = %d, c = %g, %lld tiles for %lld samples in %d signals is not a geometry of goofer_host_limit_plan",
                            who, W, (double)c, (long long)n_tiles, (long long)total, n);
     if (tp && ((R != 2 && R != 4) || Z != GOOFER_TP_ZEROS))
@@ -361,7 +397,7 @@ static int limit_entry(goofer_ctx *ctx, const char *who, bool tp, const float *x
     if (int rc = check_aligned(ctx, who, "x, taps, tiles, out, peak_in and min_gain", {x, taps, out, tiles, peak_in, min_gain, tp_taps}, "in_off", {in_off}))
         return rc;
     if (int rc = check_overlap(ctx, who, x, out, total, false)) return rc;
-    return launch_limit(ctx, x, in_off, n, W, taps, c, tiles, n_tiles, out, peak_in, min_gain, (hipStream_t)stream, tp ? R : 0, tp_taps);
+    return launch_limit(ctx, x, in_off, n, W, taps, c, tiles, n_tiles, out, peak_in, min_gain, (hipStream_t)stream, tp ? R : 0, tp_taps, ch);
 }
 
 extern "C" int goofer_limit(goofer_ctx *ctx, const float *x, const int64_t *in_off, int n, int64_t total, int W, const float *taps, float c,
@@ -375,6 +411,14 @@ extern "C" int goofer_limit_tp(goofer_ctx *ctx, const float *x, const int64_t *i
                                const float *tp_taps, void *stream)
 {
     return limit_entry(ctx, "goofer_limit_tp", true, x, in_off, n, total, W, taps, c, tiles, n_tiles, out, peak_in, min_gain, R, Z, tp_taps, stream);
+}
+
+extern "C" int goofer_limit_linked(goofer_ctx *ctx, const float *x, const int64_t *in_off, int n, int64_t total, int ch, int W, const float *taps,
+                                   float c, const int32_t *tiles, int64_t n_tiles, float *out, float *peak_in, float *min_gain, int R,
+                                   const float *tp_taps, void *stream)
+{
+    return limit_entry(ctx, "goofer_limit_linked", R != 0, x, in_off, n, total, W, taps, c, tiles, n_tiles, out, peak_in, min_gain, R, GOOFER_TP_ZEROS,
+                       R != 0 ? tp_taps : nullptr, stream, ch);
 }
 
 extern "C" int goofer_true_peak(goofer_ctx *ctx, const float *x, const int64_t *in_off, int n, int64_t total, int R, int Z, const float *taps,

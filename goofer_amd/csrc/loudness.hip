@@ -148,6 +148,49 @@ void k_loud_energy(const float *__restrict__ x, const int64_t *__restrict__ in_o
     if (tid < nq) partial[LD_SLOTS * (int64_t)blockIdx.x + tid] = ts_waves(add, s_red[tid]);
 }
 
+// Blocks, both gates, L, momentary_max and g of one signal's (or one channel group's) kn segment energies E(k), by the whole
+// workgroup (k_loud_stats, k_loud_link); E(k) is read by every thread that needs it and gives the same value each time.  The
+// results are thread 0's (true there, false elsewhere).
+template <class Energy>
+__device__ __forceinline__ bool loud_gate(Energy E, int64_t kn, int S, double abs_gate, double target, double max_gain, int normalise,
+                                          double *__restrict__ s_red, double &L, double &mm, float &g)
+{
+    const int tid = threadIdx.x;
+    const double nan = __longlong_as_double(0x7ff8000000000000LL), ninf = __longlong_as_double(0xfff0000000000000LL);
+    const int64_t kb = kn > 3 ? kn - 3 : 0;
+    const double inv = 1.0 / (4.0 * (double)S);
+    auto add = [](double a, double b) { return a + b; };
+    auto block = [&](int64_t j) { return (((E(j) + E(j + 1)) + E(j + 2)) + E(j + 3)) * inv; };
+    double sum = 0.0, cnt = 0.0, top = 0.0;
+    for (int64_t j = tid; j < kb; j += TS_THREADS) {
+        const double z = block(j);
+        if (!(z <= abs_gate)) sum += z, cnt += 1.0;             // (a NaN block is not dropped: it makes the statistics NaN)
+        top = fmax(top, z);
+    }
+    sum = ts_block_reduce(sum, add, s_red);
+    cnt = ts_block_reduce(cnt, add, s_red);
+    top = ts_block_reduce(top, [](double a, double b) { return fmax(a, b); }, s_red);
+    const double rel = 0.1 * (sum / cnt);                       // (cnt == 0: nothing passes below either)
+    double sum2 = 0.0, cnt2 = 0.0;
+    for (int64_t j = tid; j < kb; j += TS_THREADS) {
+        const double z = block(j);
+        if (z > abs_gate && z > rel) sum2 += z, cnt2 += 1.0;
+    }
+    sum2 = ts_block_reduce(sum2, add, s_red);
+    cnt2 = ts_block_reduce(cnt2, add, s_red);
+    if (tid != 0) return false;
+    L = ninf, mm = kb > 0 ? -0.691 + 10.0 * log10(top) : ninf;
+    g = 1.0f;
+    if (sum != sum) {
+        L = mm = nan;
+        g = normalise ? __int_as_float(0x7fc00000) : 1.0f;
+    } else if (cnt2 > 0.0) {
+        L = -0.691 + 10.0 * log10(sum2 / cnt2);
+        if (normalise) g = (float)fmin(pow(10.0, (target - L) / 20.0), max_gain);
+    }
+    return true;
+}
+
 __global__ __launch_bounds__(TS_THREADS)
 void k_loud_stats(const int64_t *__restrict__ in_off, int n, int64_t n_tiles, int S, const int64_t *__restrict__ seg_off, const double *__restrict__ partial,
                   const int32_t *__restrict__ first_tile, double abs_gate, double target, double max_gain, int normalise,
@@ -156,7 +199,7 @@ void k_loud_stats(const int64_t *__restrict__ in_off, int n, int64_t n_tiles, in
     __shared__ double s_red[TS_THREADS / 64];
     const int sig = blockIdx.x, tid = threadIdx.x;
     const int64_t len = in_off[sig + 1] - in_off[sig], sbase = seg_off[sig];
-    const double nan = __longlong_as_double(0x7ff8000000000000LL), ninf = __longlong_as_double(0xfff0000000000000LL);
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
     int nt = 0;
     int64_t first = 0;
     const bool tiled = ts_signal(in_off, n_tiles, first_tile, nt, first);
@@ -179,40 +222,40 @@ void k_loud_stats(const int64_t *__restrict__ in_off, int n, int64_t n_tiles, in
         }
     }
     __syncthreads();                                            // E is read back by other threads of this workgroup
-    const int64_t kb = kn > 3 ? kn - 3 : 0;
-    const double inv = 1.0 / (4.0 * (double)S);
-    auto add = [](double a, double b) { return a + b; };
-    auto block = [&](int64_t j) { return (((E[j] + E[j + 1]) + E[j + 2]) + E[j + 3]) * inv; };
-    double sum = 0.0, cnt = 0.0, top = 0.0;
-    for (int64_t j = tid; j < kb; j += TS_THREADS) {
-        const double z = block(j);
-        if (!(z <= abs_gate)) sum += z, cnt += 1.0;             // (a NaN block is not dropped: it makes the statistics NaN)
-        top = fmax(top, z);
-    }
-    sum = ts_block_reduce(sum, add, s_red);
-    cnt = ts_block_reduce(cnt, add, s_red);
-    top = ts_block_reduce(top, [](double a, double b) { return fmax(a, b); }, s_red);
-    const double rel = 0.1 * (sum / cnt);                       // (cnt == 0: nothing passes below either)
-    double sum2 = 0.0, cnt2 = 0.0;
-    for (int64_t j = tid; j < kb; j += TS_THREADS) {
-        const double z = block(j);
-        if (z > abs_gate && z > rel) sum2 += z, cnt2 += 1.0;
-    }
-    sum2 = ts_block_reduce(sum2, add, s_red);
-    cnt2 = ts_block_reduce(cnt2, add, s_red);
-    if (tid != 0) return;
-    double L = ninf, mm = kb > 0 ? -0.691 + 10.0 * log10(top) : ninf;
-    float g = 1.0f;
-    if (sum != sum) {
-        L = mm = nan;
-        g = normalise ? __int_as_float(0x7fc00000) : 1.0f;
-    } else if (cnt2 > 0.0) {
-        L = -0.691 + 10.0 * log10(sum2 / cnt2);
-        if (normalise) g = (float)fmin(pow(10.0, (target - L) / 20.0), max_gain);
-    }
+    double L, mm;
+    float g;
+    if (!loud_gate([&](int64_t k) { return E[k]; }, kn, S, abs_gate, target, max_gain, normalise, s_red, L, mm, g)) return;
     loud[2 * sig] = L;
     loud[2 * sig + 1] = mm;
     gain[sig] = g;
+}
+
+// The channel-linked gate (goofer_loudness_link): a workgroup per group of CH channels, on the segment energies a measure-only
+// goofer_loudness_measure wrote; E_g[k] = E_0[k] + E_1[k], made again at every read (the same bits each time).
+__global__ __launch_bounds__(TS_THREADS)
+void k_loud_link(const double *__restrict__ seg_energy, const int64_t *__restrict__ seg_off, int ch, int S, double abs_gate, double target,
+                 double max_gain, int normalise, double *__restrict__ loud, float *__restrict__ gain)
+{
+    __shared__ double s_red[TS_THREADS / 64];
+    const int grp = blockIdx.x, tid = threadIdx.x, s0 = grp * ch;
+    const int64_t b0 = seg_off[s0], kn = seg_off[s0 + 1] - b0;
+    const int64_t b1 = ch > 1 ? seg_off[s0 + 1] : b0;
+    if (kn < 0 || (ch > 1 && seg_off[s0 + 2] - b1 != kn)) {      // (channels that differ in segment count: k_loud_stats' convention)
+        if (tid == 0) {
+            loud[2 * grp] = loud[2 * grp + 1] = __longlong_as_double(0x7ff8000000000000LL);
+            for (int c = 0; c < ch; ++c) gain[s0 + c] = 1.0f;
+        }
+        return;
+    }
+    const double *__restrict__ E0 = seg_energy + b0, *__restrict__ E1 = seg_energy + b1;
+    double L, mm;
+    float g;
+    const bool first = ch > 1 ? loud_gate([&](int64_t k) { return E0[k] + E1[k]; }, kn, S, abs_gate, target, max_gain, normalise, s_red, L, mm, g)
+                              : loud_gate([&](int64_t k) { return E0[k]; }, kn, S, abs_gate, target, max_gain, normalise, s_red, L, mm, g);
+    if (!first) return;
+    loud[2 * grp] = L;
+    loud[2 * grp + 1] = mm;
+    for (int c = 0; c < ch; ++c) gain[s0 + c] = g;
 }
 
 #define LD_APPLY_SPT 4
@@ -301,6 +344,27 @@ extern "C" int goofer_loudness_measure(goofer_ctx *ctx, const float *x, const in
     if (rc || !scratch) return rc;
     return launch_loudness_measure(ctx, x, in_off, n, S, coef, mats, seg_off, tiles, n_tiles, target, max_gain_db, seg_energy, loud, gain,
                                    ends, starts, partial, first_tile, (hipStream_t)stream);
+}
+
+extern "C" int goofer_loudness_link(goofer_ctx *ctx, const double *seg_energy, const int64_t *seg_off, int n, int ch, int S, double target,
+                                    double max_gain_db, double *loud, float *gain, void *stream)
+{
+    if (!ctx) return GOOFER_EINVAL;
+    if (n < 0 || (ch != 1 && ch != 2) || n % ch != 0)
+        return goofer_fail(ctx, GOOFER_EINVAL, "goofer_loudness_link: %d signals in groups of %d channels (1 or 2)", n, ch);
+    const int s_lo = (GOOFER_LOUDNESS_MIN_SR + 5) / 10, s_hi = (GOOFER_LOUDNESS_MAX_SR + 5) / 10;
+    if (S < s_lo || S > s_hi || std::isinf(target) || !(max_gain_db >= 0.0 && max_gain_db <= GOOFER_LOUDNESS_MAX_GAIN_DB_CAP))
+        return goofer_fail(ctx, GOOFER_EINVAL, "goofer_loudness_link: S = %d, target %g, max_gain_db %g is outside the definition's range", S, target,
+                           max_gain_db);
+    if (n == 0) return GOOFER_OK;
+    if (!seg_energy || !seg_off || !loud || !gain) return goofer_fail(ctx, GOOFER_EINVAL, "goofer_loudness_link: null pointer");
+    if (int rc = check_aligned(ctx, "goofer_loudness_link", "gain", {gain}, "seg_energy, seg_off and loud", {seg_energy, seg_off, loud})) return rc;
+    const bool normalise = !std::isnan(target);
+    hipLaunchKernelGGL(k_loud_link, dim3((unsigned)(n / ch)), dim3(TS_THREADS), 0, (hipStream_t)stream, seg_energy, seg_off, ch, S,
+                       std::pow(10.0, (-70.0 + 0.691) / 10.0), normalise ? target : 0.0, std::pow(10.0, max_gain_db / 20.0), normalise ? 1 : 0, loud,
+                       gain);
+    LAUNCH_CHECK(ctx);
+    return GOOFER_OK;
 }
 
 extern "C" int goofer_loudness_apply(goofer_ctx *ctx, const float *x, const int64_t *in_off, int n, int64_t total, const float *gain,

@@ -1012,6 +1012,46 @@ int goofer_host_phrase_plan(const goofer_phrase_note *notes, const int64_t *note
     return GOOFER_OK;
 }
 
+/* The stereo bus (include/goofer_hip.h; the kernel: bus.hip): the records checked, and which tracks each tile of the bus mixes.
+ * [start, hi) of track i = its range on the bus, empty for a track that contributes nothing.  x is not read. */
+static bool bus_range(const goofer_bus_track &r, int64_t total_out, int64_t *hi)
+{
+    if (r.len <= 0 || r.start >= total_out) return false;
+    *hi = r.len > total_out - r.start ? total_out : r.start + r.len;   // (no sum that could overflow)
+    return true;
+}
+
+int goofer_host_bus_plan(const goofer_bus_track *tracks, int n, int64_t total_out, int64_t *tile_off, int32_t *tile_tracks, int64_t cap,
+                         int64_t *need)
+{
+    if (n < 0 || total_out < 0 || cap < 0 || !tile_off || !need || (n > 0 && !tracks) || (cap > 0 && !tile_tracks)) return GOOFER_EINVAL;
+    const int64_t T = GOOFER_BUS_TILE, tiles = total_out / T + (total_out % T != 0);
+    if (tiles >= ((int64_t)1 << 31)) return GOOFER_EINVAL;
+    for (int i = 0; i < n; ++i) {
+        const goofer_bus_track &r = tracks[i];
+        if (r.len < 0 || r.start < 0 || !std::isfinite(r.gl) || !std::isfinite(r.gr)) return GOOFER_EINVAL;
+        if ((r.len > 0 && !r.x) || ((uintptr_t)r.x & 3)) return GOOFER_EINVAL;   // (the pointer's value alone)
+    }
+    // counts at tile_off[t + 1]; then the tiles' first entries there, which the fill advances to the first entry of tile t + 1
+    for (int64_t t = 0; t <= tiles; ++t) tile_off[t] = 0;
+    int64_t hi;
+    for (int i = 0; i < n; ++i)
+        if (bus_range(tracks[i], total_out, &hi))
+            for (int64_t t = tracks[i].start / T; t <= (hi - 1) / T; ++t) ++tile_off[t + 1];
+    int64_t run = 0;
+    for (int64_t t = 0; t < tiles; ++t) {
+        const int64_t c = tile_off[t + 1];
+        tile_off[t + 1] = run;
+        run += c;
+    }
+    *need = run;
+    if (run > cap) return 1;
+    for (int i = 0; i < n; ++i)
+        if (bus_range(tracks[i], total_out, &hi))
+            for (int64_t t = tracks[i].start / T; t <= (hi - 1) / T; ++t) tile_tracks[tile_off[t + 1]++] = i;
+    return GOOFER_OK;
+}
+
 /* Output-rate conversion (include/goofer_hip.h; the kernel: rate.hip): geometry, the Kaiser-windowed sinc table in float64 and
  * the output CSR.  I0 by its power series sum_k ((x/2)^k / k!)^2: every term positive, 45 terms at x = 14. */
 static double rate_i0(double x)

@@ -508,15 +508,18 @@ int launch_vocal_roughness(goofer_ctx *ctx, const float *y, const float *f0, con
 // The wav the reference writes is PCM16 (soundfile's default WAV subtype, SillySampler.py:1184-1185): clip to
 // [-1, 1 - 2^-15], times 32768, round half to even.  Done here the finished audio crosses PCIe at two bytes per sample — the
 // download of the fp32 mix is what bounds a long job (199 MB per 1024 notes, 3.6 ms against a 2.3 ms device step).
+__device__ __forceinline__ int16_t pcm16_q(float v)
+{
+    double d = (double)v;
+    d = d < -1.0 ? -1.0 : (d > 1.0 - 1.0 / 32768.0 ? 1.0 - 1.0 / 32768.0 : d);
+    return (int16_t)(int)rint(d * 32768.0);
+}
+
 __global__ __launch_bounds__(256) void k_pcm16(const float *__restrict__ x, int64_t n, int16_t *__restrict__ out)
 {
     const int64_t i0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 8;
     if (i0 >= n) return;
-    auto q = [](float v) {
-        double d = (double)v;
-        d = d < -1.0 ? -1.0 : (d > 1.0 - 1.0 / 32768.0 ? 1.0 - 1.0 / 32768.0 : d);
-        return (int16_t)(int)rint(d * 32768.0);
-    };
+    auto q = [](float v) { return pcm16_q(v); };
     if (i0 + 8 <= n && ((((uintptr_t)x) & 15) == 0) && ((((uintptr_t)out) & 15) == 0)) {
         const float4 a = *reinterpret_cast<const float4 *>(x + i0), b = *reinterpret_cast<const float4 *>(x + i0 + 4);
         union { int16_t s[8]; uint4 v; } o;
@@ -534,6 +537,42 @@ extern "C" int goofer_pcm16(goofer_ctx *ctx, const float *x, int64_t n, int16_t 
     if (n <= 0) return GOOFER_OK;
     if (!x || !out) return goofer_fail(ctx, GOOFER_EINVAL, "null pointer");
     hipLaunchKernelGGL(k_pcm16, dim3((unsigned)((n + 2047) / 2048)), dim3(256), 0, (hipStream_t)stream, x, n, out);
+    LAUNCH_CHECK(ctx);
+    return GOOFER_OK;
+}
+
+// The stereo bus as a wav holds it: the planar pair L = x[0 .. n), R = x[n .. 2n) interleaved frame by frame.  A thread makes
+// four frames: two 16-byte loads where both channels' sources are aligned (R is not when n % 4 != 0), one 16-byte store.
+__global__ __launch_bounds__(256) void k_pcm16_stereo(const float *__restrict__ x, int64_t n, int16_t *__restrict__ out)
+{
+    const int64_t i0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (i0 >= n) return;
+    const float *__restrict__ xl = x, *__restrict__ xr = x + n;
+    if (i0 + 4 <= n && ((((uintptr_t)xl) | ((uintptr_t)xr) | ((uintptr_t)out)) & 15) == 0) {
+        const float4 a = *reinterpret_cast<const float4 *>(xl + i0), b = *reinterpret_cast<const float4 *>(xr + i0);
+        union { int16_t s[8]; uint4 v; } o;
+        o.s[0] = pcm16_q(a.x); o.s[1] = pcm16_q(b.x); o.s[2] = pcm16_q(a.y); o.s[3] = pcm16_q(b.y);
+        o.s[4] = pcm16_q(a.z); o.s[5] = pcm16_q(b.z); o.s[6] = pcm16_q(a.w); o.s[7] = pcm16_q(b.w);
+        *reinterpret_cast<uint4 *>(out + 2 * i0) = o.v;
+    } else {
+        for (int64_t i = i0; i < n && i < i0 + 4; ++i) {
+            out[2 * i] = pcm16_q(xl[i]);
+            out[2 * i + 1] = pcm16_q(xr[i]);
+        }
+    }
+}
+
+extern "C" int goofer_pcm16_planar(goofer_ctx *ctx, const float *x, int64_t n, int ch, int16_t *out, void *stream)
+{
+    if (!ctx) return GOOFER_EINVAL;
+    if (ch != 1 && ch != 2) return goofer_fail(ctx, GOOFER_EINVAL, "goofer_pcm16_planar: %d channels (1 or 2)", ch);
+    if (ch == 1) return goofer_pcm16(ctx, x, n, out, stream);
+    if (n <= 0) return GOOFER_OK;
+    if (!x || !out) return goofer_fail(ctx, GOOFER_EINVAL, "goofer_pcm16_planar: null pointer");
+    if (((uintptr_t)x & 3) || ((uintptr_t)out & 1)) return goofer_fail(ctx, GOOFER_EINVAL, "goofer_pcm16_planar: x must be 4-byte aligned, out 2-byte aligned");
+    const int64_t blocks = (n + 1023) / 1024;
+    if (blocks >= ((int64_t)1 << 31)) return goofer_fail(ctx, GOOFER_EINVAL, "goofer_pcm16_planar: %lld frames", (long long)n);
+    hipLaunchKernelGGL(k_pcm16_stereo, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, n, out);
     LAUNCH_CHECK(ctx);
     return GOOFER_OK;
 }

@@ -204,10 +204,45 @@ class Context:
     def set_option(self, name: str, value: int):
         self._check(self.lib.goofer_set_option(self.h, name.encode(), int(value)))
 
-    def pcm16(self, x, out=None):
-        """The wav samples of fp32 audio on the device (goofer_pcm16: clip, * 32768, round half to even -> int16)."""
-        out = torch.empty(x.numel(), dtype=torch.int16, device=x.device) if out is None else out
-        self._check(self.lib.goofer_pcm16(self.h, _ptr(x), x.numel(), _ptr(out), self._stream()))
+    def pcm16(self, x, out=None, channels=1):
+        """The wav samples of fp32 audio on the device (goofer_pcm16: clip, * 32768, round half to even -> int16).  ``channels``
+        2: ``x`` is a planar stereo bus, L then R (``bus_mix``), and the frames come back interleaved, int16 ``[N, 2]``
+        (goofer_pcm16_planar)."""
+        if channels == 1:
+            out = torch.empty(x.numel(), dtype=torch.int16, device=x.device) if out is None else out
+            self._check(self.lib.goofer_pcm16(self.h, _ptr(x), x.numel(), _ptr(out), self._stream()))
+            return out
+        if channels != 2 or x.dtype != torch.float32 or not x.is_contiguous() or x.numel() % 2:
+            raise ValueError("pcm16: channels is 1 or 2, and a stereo bus is a contiguous float32 tensor of 2 N samples")
+        n = x.numel() // 2
+        if out is None:
+            out = torch.empty((n, 2), dtype=torch.int16, device=x.device)
+        elif out.dtype != torch.int16 or not out.is_contiguous() or out.numel() != 2 * n:
+            raise ValueError("pcm16: out must be a contiguous int16 tensor of the %d frames" % n)
+        self._check(self.lib.goofer_pcm16_planar(self.h, _ptr(x), n, 2, _ptr(out), self._stream()))
+        return out
+
+    def bus_mix(self, xs, plan, out=None):
+        """Finished tracks panned and summed onto a planar stereo bus on the device (goofer_bus_mix; the definition:
+        include/goofer_hip.h, "stereo bus", restated in tests/bus_ref.py).  ``xs``: the tracks, a list of contiguous fp32 device
+        tensors, each wherever it lies (nothing is concatenated), muted ones included (or None for them); ``plan``: the
+        ``goofer_amd.bus.BusPlan`` made for these very tensors (it holds their addresses; records and cover table are shipped
+        in one upload the first time it is used on this device); ``out``: a contiguous fp32 device tensor of ``2 *
+        plan.total_out`` samples (default: a new one; it need not be cleared, every sample is stored).  Returns it: L is
+        ``out[:N]``, R is ``out[N:]``.  Asynchronous on the current stream."""
+        n, total = plan.n, plan.total_out
+        for j, k in enumerate(plan.index):
+            x = xs[int(k)]
+            if x.dtype != torch.float32 or not x.is_contiguous() or x.numel() < int(plan.tracks["len"][j]):
+                raise ValueError("bus_mix: track %d must be a contiguous float32 tensor of the plan's %d samples" % (k, plan.tracks["len"][j]))
+            if int(plan.tracks["len"][j]) and x.data_ptr() != int(plan.tracks["x"][j]):
+                raise ValueError("bus_mix: track %d is not the tensor the plan was made for" % k)
+        if out is None:
+            out = torch.empty(2 * total, dtype=torch.float32, device=self.device)
+        elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != 2 * total:
+            raise ValueError("bus_mix: out must be a contiguous float32 tensor of the bus's 2 * %d samples" % total)
+        tracks, tile_off, tile_tracks = plan.device_tables(self)
+        self._check(self.lib.goofer_bus_mix(self.h, _ptr(tracks), n, _ptr(tile_off), _ptr(tile_tracks), total, _ptr(out), self._stream()))
         return out
 
     def phrase_mix(self, x, sample_off, plan, out=None):
@@ -285,11 +320,22 @@ class Context:
         not overlap ``x`` (default: a new one; it need not be cleared).  Returns ``(y, peak_in, min_gain)``, device tensors:
         signal i is ``y[plan.in_off[i]:plan.in_off[i + 1]]``, ``peak_in[i]`` its greatest ``|x|`` and ``min_gain[i]`` the
         smallest gain it was given (fp32 ``[n]``).  A plan made with ``true_peak`` runs goofer_limit_tp: the ceiling holds for
-        the oversampled envelope (restated in tests/true_peak_ref.py) and ``peak_in`` is the true peak.  Asynchronous on the
-        current stream."""
+        the oversampled envelope (restated in tests/true_peak_ref.py) and ``peak_in`` is the true peak.  A plan made with
+        ``channels=2`` runs goofer_limit_linked: signals 2g and 2g + 1 get one gain (restated in tests/bus_ref.py), and
+        ``peak_in`` / ``min_gain`` are fp32 ``[n / 2]``, one pair per group.  Asynchronous on the current stream."""
         n, total = plan.n, plan.total
         d_in, out = self._signals("limit", x, d_off, plan, out)
         _, tiles, taps = plan.device_tables(self)
+        if plan.channels != 1:
+            groups = n // plan.channels
+            peak_in = torch.empty(groups, dtype=torch.float32, device=self.device)
+            min_gain = torch.empty(groups, dtype=torch.float32, device=self.device)
+            if n:
+                self._check(self.lib.goofer_limit_linked(
+                    self.h, _ptr(x) if total else None, _ptr(d_in), n, total, plan.channels, plan.W, _ptr(taps), C.c_float(plan.ceiling),
+                    _ptr(tiles) if total else None, plan.n_tiles, _ptr(out) if total else None, _ptr(peak_in), _ptr(min_gain), plan.R,
+                    _ptr(plan.device_tp_taps(self)) if plan.true_peak else None, self._stream()))
+            return out, peak_in, min_gain
         peak_in = torch.empty(n, dtype=torch.float32, device=self.device)
         min_gain = torch.empty(n, dtype=torch.float32, device=self.device)
         if n:
@@ -320,7 +366,7 @@ class Context:
                                                   _ptr(peak), self._stream()))
         return peak
 
-    def loudness(self, x, d_off, plan, target=None, max_gain_db=20.0, out=None):
+    def loudness(self, x, d_off, plan, target=None, max_gain_db=20.0, out=None, channels=1):
         """The integrated loudness of the signals of a ragged batch measured on the device and, with a ``target`` in LUFS, the
         signals scaled to it (goofer_loudness_measure, goofer_loudness_apply; the definition: include/goofer_hip.h, restated in
         tests/loudness_ref.py).  ``x``: the signals' samples back to back, a contiguous fp32 device tensor; ``d_off``: their
@@ -331,8 +377,10 @@ class Context:
         seg_energy)``, device tensors: ``y`` the scaled signals (None when measuring only), ``loud`` float64 ``[n, 2]``
         (integrated loudness and the greatest momentary loudness, LUFS), ``gain`` fp32 ``[n]`` (1 when measuring only; it goes
         from the measurement to the scaling without visiting the host) and ``seg_energy`` float64 ``[plan.n_segments]``, the
-        K-weighted energy of every whole 100 ms segment (signal i: ``plan.seg_off[i]:plan.seg_off[i + 1]``).  Asynchronous on
-        the current stream."""
+        K-weighted energy of every whole 100 ms segment (signal i: ``plan.seg_off[i]:plan.seg_off[i + 1]``).  ``channels`` 2:
+        signals 2g and 2g + 1 are the channels of one programme — measure only, then goofer_loudness_link gates the sum of the
+        two channels' energies (restated in tests/bus_ref.py), then the scaling: ``loud`` is float64 ``[n / 2, 2]`` and
+        ``gain`` holds the group's value for both channels.  Asynchronous on the current stream."""
         from . import loudness as LD
         n, total = plan.n, plan.total
         cap = float(max_gain_db)
@@ -348,6 +396,19 @@ class Context:
         seg = seg_buf[:plan.n_segments]
         loud = torch.empty((n, 2), dtype=torch.float64, device=self.device)
         gain = torch.empty(n, dtype=torch.float32, device=self.device)
+        if channels != 1:
+            if channels != 2 or n % 2:
+                raise ValueError("loudness: channels is 1 or 2, and %d signals are not pairs" % n)
+            link = torch.empty((n // 2, 2), dtype=torch.float64, device=self.device)
+            if n:
+                args = (_ptr(x) if total else None, _ptr(d_in), n, total, plan.S, _ptr(coef), _ptr(mats), _ptr(d_seg),
+                        _ptr(tiles) if total else None, plan.n_tiles, math.nan, cap, _ptr(seg_buf), _ptr(loud), _ptr(gain))
+                self._scratch_call(self.lib.goofer_loudness_measure, args)
+                self._check(self.lib.goofer_loudness_link(self.h, _ptr(seg_buf), _ptr(d_seg), n, 2, plan.S, math.nan if target is None else target,
+                                                          cap, _ptr(link), _ptr(gain), self._stream()))
+                if y is not None and total:
+                    self._check(self.lib.goofer_loudness_apply(self.h, _ptr(x), _ptr(d_in), n, total, _ptr(gain), _ptr(y), self._stream()))
+            return y, link, gain, seg
         if n:
             args = (_ptr(x) if total else None, _ptr(d_in), n, total, plan.S, _ptr(coef), _ptr(mats), _ptr(d_seg),
                     _ptr(tiles) if total else None, plan.n_tiles, math.nan if target is None else target, cap,

@@ -56,6 +56,7 @@ class LimitPlan(SP.SignalPlan):
     R: int
     Z: int
     tp_taps: np.ndarray
+    channels: int = 1                 # 2: signals 2g and 2g + 1 are one group (goofer_limit_linked); ``tiles`` is the groups' table
     BLOB = ("in_off", "tiles", "taps", "tp_taps")
 
     @property
@@ -99,6 +100,22 @@ def true_peak_table(sr):
     return R.value, Z.value, taps.reshape(R.value - 1, 2 * Z.value)
 
 
+def group_lengths(who, lengths, channels):
+    """The lengths of the groups of ``channels`` consecutive signals, which must agree within a group (``channels`` 1: the
+    lengths themselves).  Raises ValueError in ``who``'s name."""
+    lengths = np.ascontiguousarray(lengths, dtype=np.int64).reshape(-1)
+    if channels not in (1, 2):
+        raise ValueError("%s: channels is 1 or 2" % who)
+    if channels == 1:
+        return lengths
+    if len(lengths) % channels:
+        raise ValueError("%s: %d signals are not groups of %d channels" % (who, len(lengths), channels))
+    g = lengths.reshape(-1, channels)
+    if (g != g[:, :1]).any():
+        raise ValueError("%s: the channels of a group have equal lengths" % who)
+    return np.ascontiguousarray(g[:, 0])
+
+
 def true_peak_plan(sr, lengths) -> LimitPlan:
     """The plan of the meter alone (``Context.true_peak``): the limiter's own tile table for these lengths and the true-peak
     table at ``sr``."""
@@ -111,25 +128,28 @@ def dbtp(x) -> float:
     return 20.0 * math.log10(v) if v > 0.0 else -math.inf
 
 
-def plan(sr, lengths, ceiling=CEILING, lookahead_ms=LOOK_MS, true_peak=False) -> LimitPlan:
+def plan(sr, lengths, ceiling=CEILING, lookahead_ms=LOOK_MS, true_peak=False, channels=1) -> LimitPlan:
     """goofer_host_limit_plan for signals of ``lengths`` samples lying back to back.  Raises ValueError for what the library
     refuses: a look-ahead that rounds to less than 1 or more than 1024 samples, a ceiling that is not in (0, 1] as fp32, a rate
     below 1, a signal of 2^31 samples or more.  ``true_peak``: also goofer_host_true_peak_plan's factor and table (a rate of
-    8000 to 192000 Hz), in the same blob."""
+    8000 to 192000 Hz), in the same blob.  ``channels`` 2: the plan of goofer_limit_linked — signals 2g and 2g + 1 are the
+    channels of group g, of equal lengths (anything else is refused), and the tile table is the planner's for the group
+    lengths."""
     lib = _lib.load()
     in_off = SP.offsets("limit.plan", lengths, sr)
     n = len(in_off) - 1
+    g_off = in_off if channels == 1 else SP.offsets("limit.plan", group_lengths("limit.plan", np.diff(in_off), channels), sr)
     c = float(np.float32(ceiling))
     W, need = C.c_int(0), (C.c_int64 * 2)(0, 0)
     taps, tiles = SP.fit(
-        lambda taps, tiles: lib.goofer_host_limit_plan(int(sr), float(lookahead_ms), C.c_float(c), in_off.ctypes.data, n, C.byref(W),
+        lambda taps, tiles: lib.goofer_host_limit_plan(int(sr), float(lookahead_ms), C.c_float(c), g_off.ctypes.data, len(g_off) - 1, C.byref(W),
                                                        *SP.cap(taps), *SP.cap(tiles), need),
         (np.zeros(0, dtype=np.float32), np.zeros((0, 2), dtype=np.int32)),
         lambda: (np.zeros(int(need[0]), dtype=np.float32), np.zeros((int(need[1]), 2), dtype=np.int32)),
         lambda rc: "goofer_host_limit_plan refused a ceiling of %r and %r ms at %s Hz (%d): a ceiling in (0, 1], a look-ahead of 1 to %d "
                    "samples, a rate >= 1, signals shorter than 2^31 samples" % (ceiling, lookahead_ms, sr, rc, MAX_LOOK))
     R, Z, tp_taps = true_peak_table(sr) if true_peak else (0, 0, np.zeros((0, 0), dtype=np.float32))
-    return LimitPlan(int(sr), n, W.value, c, taps, in_off, tiles, R, Z, tp_taps)
+    return LimitPlan(int(sr), n, W.value, c, taps, in_off, tiles, R, Z, tp_taps, int(channels))
 
 
 def look_samples(sr, lookahead_ms=LOOK_MS) -> int:

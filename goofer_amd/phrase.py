@@ -241,23 +241,15 @@ def read_job(path):
     return out
 
 
-def render_job(path, out_wav, renderer=None, seed=None, tracker=None, pcm16=True, out_sr=None, limit=None, stats=None, loudness=None,
-               compress=None, eq=None, reverb=None):
-    """``python -m goofer_amd.phrase``: the notes of a job file rendered as one batch and written as one wav.  ``in_file`` is
-    resolved like the resampler front end does: ``<stem>_features.goofy`` beside the wav, analysed and cached first when it is
-    missing (``trackers.ensure_features_batch``; the tracker: the argument, else ``$GOOFER_TRACKER``).  ``out_sr``: the rate of
-    the wav (``render_phrase``'s; None: the voicebank's).  ``limit``: ``render_phrase``'s (None: no limiter); with it ``stats``,
-    a dict, receives the limiter's ``peak_in`` and ``min_gain`` (a true-peak limiter's ``true_peak_in`` and ``true_peak_out`` too).  ``loudness``: ``render_phrase``'s (None: the track's level is
-    left as it is); with it ``stats`` receives ``lufs_in``, ``momentary_max`` and ``gain``.  ``compress``: ``render_phrase``'s (None:
-    no compressor); with it ``stats`` receives ``max_reduction_db``.  ``eq``: ``render_phrase``'s (None: no equaliser); it has no
-    statistic.  ``reverb``: ``render_phrase``'s (None: no reverb); with it ``stats`` receives ``reverb_taps``, the impulse
-    response's length, and ``reverb_tail``, the samples it adds to the track."""
+def load_job(path, renderer, tracker=None):
+    """The notes of a job file as ``Renderer.render_phrase`` takes them: (jobs, entries).  ``in_file`` is resolved like the
+    resampler front end does: ``<stem>_features.goofy`` beside the wav, analysed and cached first when it is missing
+    (``trackers.ensure_features_batch``; the tracker: the argument, else ``$GOOFER_TRACKER``)."""
     from pathlib import Path
     from . import core, trackers
     from . import sampler as S
-    from .render import Renderer, Source, write_wav
+    from .render import Source
     lines = read_job(path)
-    renderer = renderer or Renderer()
     wavs = [Path(a[0]) for a, _ in lines if a is not None]
     feats = trackers.ensure_features_batch(wavs, hop_length=renderer.hop, tracker=tracker, ctx=renderer.ctx) if wavs else {}
     sources, jobs = {}, []
@@ -272,6 +264,23 @@ def render_job(path, out_wav, renderer=None, seed=None, tracker=None, pcm16=True
         jobs.append((sources[feat], S.decode_request(*a[2:13])))
     if not jobs:
         raise ValueError(f"{path}: no note")
+    return jobs, [e for _, e in lines]
+
+
+def render_job(path, out_wav, renderer=None, seed=None, tracker=None, pcm16=True, out_sr=None, limit=None, stats=None, loudness=None,
+               compress=None, eq=None, reverb=None):
+    """``python -m goofer_amd.phrase``: the notes of a job file rendered as one batch and written as one wav.  ``in_file`` is
+    resolved like the resampler front end does: ``<stem>_features.goofy`` beside the wav, analysed and cached first when it is
+    missing (``trackers.ensure_features_batch``; the tracker: the argument, else ``$GOOFER_TRACKER``).  ``out_sr``: the rate of
+    the wav (``render_phrase``'s; None: the voicebank's).  ``limit``: ``render_phrase``'s (None: no limiter); with it ``stats``,
+    a dict, receives the limiter's ``peak_in`` and ``min_gain`` (a true-peak limiter's ``true_peak_in`` and ``true_peak_out`` too).  ``loudness``: ``render_phrase``'s (None: the track's level is
+    left as it is); with it ``stats`` receives ``lufs_in``, ``momentary_max`` and ``gain``.  ``compress``: ``render_phrase``'s (None:
+    no compressor); with it ``stats`` receives ``max_reduction_db``.  ``eq``: ``render_phrase``'s (None: no equaliser); it has no
+    statistic.  ``reverb``: ``render_phrase``'s (None: no reverb); with it ``stats`` receives ``reverb_taps``, the impulse
+    response's length, and ``reverb_tail``, the samples it adds to the track."""
+    from .render import Renderer, write_wav
+    renderer = renderer or Renderer()
+    jobs, entries = load_job(path, renderer, tracker)
     if seed is None:
         seed = int(np.random.SeedSequence().generate_state(1, dtype=np.uint64)[0])
     if reverb is not None:
@@ -281,9 +290,9 @@ def render_job(path, out_wav, renderer=None, seed=None, tracker=None, pcm16=True
         if stats is not None:
             stats.update({"reverb_taps": rv_plan.L, "reverb_tail": rv_plan.added})
     if limit is None and loudness is None and compress is None:
-        track = renderer.render_phrase(jobs, [e for _, e in lines], seed=seed, pcm16=pcm16, out_sr=out_sr, eq=eq, reverb=reverb)
+        track = renderer.render_phrase(jobs, entries, seed=seed, pcm16=pcm16, out_sr=out_sr, eq=eq, reverb=reverb)
     else:
-        track, st = renderer.render_phrase(jobs, [e for _, e in lines], seed=seed, pcm16=pcm16, out_sr=out_sr, limit=limit, return_stats=True,
+        track, st = renderer.render_phrase(jobs, entries, seed=seed, pcm16=pcm16, out_sr=out_sr, limit=limit, return_stats=True,
                                            loudness=loudness, compress=compress, eq=eq, reverb=reverb)
         if stats is not None:
             stats.update(st)

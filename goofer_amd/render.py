@@ -562,11 +562,7 @@ class Renderer:
         if len({src.sr for src, _ in jobs}) != 1:
             raise ValueError("render_phrase: the notes of a phrase share one sample rate")
         chain = self._finish_settings(jobs, "render_phrase", out_sr, compress, loudness, limit, eq, reverb)
-        prep = self.prepare(jobs, phi_seeds=phi_seeds, noise_seeds=noise_seeds)
-        plan = P.plan_phrase(entries, np.diff(np.asarray(prep["sample_off"], dtype=np.int64)), jobs[0][0].sr)
-        out = self.run(prep, seed=seed)
-        track = self.ctx.phrase_mix(out["mix"], prep["offsets"]["d_s"], plan)
-        track, _, st = self._finish(track, None, [plan.total_out], *chain, true_peak_out=return_stats)
+        track, _, st = self._phrase_track(jobs, entries, seed, phi_seeds, noise_seeds, chain, true_peak_out=return_stats)
         if pcm16:
             track = self.ctx.pcm16(track)
         self.ctx.check()                                   # synchronises; raises if the device flagged a note
@@ -583,6 +579,77 @@ class Renderer:
                 res["max_reduction_db"] = float(st["max_reduction"].cpu()[0])
             return track.cpu().numpy(), res
         return track.cpu().numpy()
+
+    def _phrase_track(self, jobs, entries, seed, phi_seeds, noise_seeds, chain, true_peak_out=False):
+        """``render_phrase`` up to its track on the device: the batch, the phrase mix and the finishing chain (``chain``:
+        ``_finish_settings``').  Returns ``_finish``'s (track, [its length], statistics); nothing is synchronised."""
+        from . import phrase as P
+        prep = self.prepare(jobs, phi_seeds=phi_seeds, noise_seeds=noise_seeds)
+        plan = P.plan_phrase(entries, np.diff(np.asarray(prep["sample_off"], dtype=np.int64)), jobs[0][0].sr)
+        out = self.run(prep, seed=seed)
+        track = self.ctx.phrase_mix(out["mix"], prep["offsets"]["d_s"], plan)
+        return self._finish(track, None, [plan.total_out], *chain, true_peak_out=true_peak_out)
+
+    def render_song(self, tracks, seed: int = 0, pcm16: bool = False, out_sr=None, loudness=None, limit=None, return_stats: bool = False):
+        """A song: several phrases, each a track with a volume and a pan fader, mixed onto a stereo bus and finished as a pair on
+        the device (goofer_amd.bus; goofer_bus_mix).  ``tracks``: a list of ``(jobs, entries, bus.Track)``, ``jobs`` and
+        ``entries`` as ``render_phrase`` takes them.  Track k is what ``render_phrase(jobs, entries, seed=track.seed if it is set
+        else seed + k, out_sr=out_sr, eq=track.eq, compress=track.compress, reverb=track.reverb)`` makes, the same bits, and stays
+        on the device; a muted track is not rendered.  Then, in order: the tracks at their ``start_ms`` with their pan gains summed
+        onto the planar bus; ``loudness`` (as ``render_phrase`` takes it): the stereo programme's, gated on the sum of the two
+        channels' energies (goofer_loudness_link), one gain for both; ``limit`` (likewise, the true-peak triple included): the
+        channel-linked limiter (goofer_limit_linked), one gain for both channels, so the image does not move; with ``pcm16`` the
+        interleaved int16 (goofer_pcm16_planar).  Returns an ``[N, 2]`` array, fp32 or int16: what ``write_wav`` takes.
+        ``return_stats`` (with ``loudness`` or ``limit``): also a dict with ``render_phrase``'s names, ``lufs_in``,
+        ``momentary_max``, ``gain``; ``peak_in``, ``min_gain``; behind a true-peak limiter ``true_peak_in`` and ``true_peak_out``,
+        the larger of the two channels' goofer_true_peak.  All tracks must be at one rate on the bus (ValueError).  A master eq,
+        compressor or reverb is not offered: an unlinked compressor would move the image, and the per-track chains cover the
+        use."""
+        from . import bus as B
+        if return_stats and limit is None and loudness is None:
+            raise ValueError("render_song: return_stats reports the statistics of the loudness stage and the limiter and needs loudness or limit")
+        tracks = [(jobs, entries, t if isinstance(t, B.Track) else B.Track(*t)) for jobs, entries, t in tracks]
+        live = [(k, jobs, entries, t) for k, (jobs, entries, t) in enumerate(tracks) if not t.mute]
+        if not live:
+            raise ValueError("render_song: a song without a track that sounds has no sample rate")
+        for _, jobs, _, _ in live:
+            if not jobs:
+                raise ValueError("render_song: a track without a note has no sample rate")
+            if len({src.sr for src, _ in jobs}) != 1:
+                raise ValueError("render_song: the notes of a track share one sample rate")
+        rates = {int(out_sr) if out_sr is not None else int(jobs[0][0].sr) for _, jobs, _, _ in live}
+        if len(rates) != 1:
+            raise ValueError("render_song: all tracks are at one rate on the bus (out_sr converts them to one)")
+        sr = rates.pop()
+        loudness, limit = None if loudness is None else LD.parse(loudness), None if limit is None else LM.parse(limit)
+        chains = [self._finish_settings(jobs, "render_song", out_sr, t.compress, None, None, t.eq, t.reverb) for _, jobs, _, t in live]
+        xs, lens = [None] * len(tracks), np.zeros(len(tracks), dtype=np.int64)
+        for (k, jobs, entries, t), chain in zip(live, chains):
+            x, n, _ = self._phrase_track(jobs, entries, seed + k if t.seed is None else t.seed, None, None, chain)
+            xs[k], lens[k] = x, int(n[0])
+        plan = B.plan([x if x is not None else 0 for x in xs], lens, [t for _, _, t in tracks], sr)
+        bus, N, st = self.ctx.bus_mix(xs, plan), plan.total_out, {}
+        if loudness is not None:
+            bus, st["loud"], st["gain"], _ = self.ctx.loudness(bus, None, LD.plan(sr, [N, N]), *loudness, channels=2)
+        if limit is not None:
+            lplan = LM.plan(sr, [N, N], *limit, channels=2)
+            bus, st["peak_in"], st["min_gain"] = self.ctx.limit(bus, None, lplan)
+            if return_stats and lplan.true_peak:
+                st["true_peak_out"] = self.ctx.true_peak(bus, None, LM.true_peak_plan(sr, [N, N]))
+        out = self.ctx.pcm16(bus, channels=2) if pcm16 else bus.view(2, N).t()
+        self.ctx.check()                                   # synchronises; raises if the device flagged a note
+        out = np.ascontiguousarray(out.cpu().numpy())
+        if not return_stats:
+            return out
+        res = {}
+        if "peak_in" in st:
+            res.update({"peak_in": float(st["peak_in"].cpu()[0]), "min_gain": float(st["min_gain"].cpu()[0])})
+        if "true_peak_out" in st:
+            res.update({"true_peak_in": res["peak_in"], "true_peak_out": float(st["true_peak_out"].cpu().max())})
+        if "loud" in st:
+            loud = st["loud"].cpu()
+            res.update({"lufs_in": float(loud[0, 0]), "momentary_max": float(loud[0, 1]), "gain": float(st["gain"].cpu()[0])})
+        return out, res
 
     def assemble(self, prep):
         """goofer_assemble_batch alone (asynchronous): envelope rows, f0 and voicing mask of the batch."""
@@ -1130,20 +1197,24 @@ def _own_noise(noise, renderer):
 
 
 def write_wav(path, x, sr):
-    """Mono PCM16 wav (soundfile's default subtype, what the reference writes).  int16 input (samples already converted on
-    the device, ``Context.pcm16``) is written as it is."""
+    """PCM16 wav (soundfile's default subtype, what the reference writes): mono for 1-D input, two channels for ``[N, 2]``
+    frames (``Renderer.render_song``).  int16 input (samples already converted on the device, ``Context.pcm16``) is written as
+    it is."""
     import wave
     x = np.asarray(x)
+    if x.ndim == 2 and x.shape[1] != 2 or x.ndim > 2:
+        raise ValueError("write_wav: a 1-D signal or [N, 2] stereo frames")
+    channels = 2 if x.ndim == 2 else 1
     if x.dtype == np.int16:
         pcm = x.astype("<i2", copy=False)
     else:
         pcm = np.clip(x.astype(np.float64), -1.0, 1.0 - 1.0 / 32768)
         pcm = np.round(pcm * 32768.0).astype("<i2")
     with wave.open(str(path), "wb") as w:
-        w.setnchannels(1)
+        w.setnchannels(channels)
         w.setsampwidth(2)
         w.setframerate(int(sr))
-        w.writeframes(pcm.tobytes())
+        w.writeframes(np.ascontiguousarray(pcm).tobytes())
 
 
 # ---------------------------------------------------------------------------------------------

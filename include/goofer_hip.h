@@ -1291,6 +1291,90 @@ int goofer_reverb(goofer_ctx *ctx, const float *x, const int64_t *in_off, int n,
                   float dry, float wet, const int64_t *out_off, const int64_t *blk_off, int64_t total_blocks, const int32_t *runs,
                   int64_t n_runs, int64_t total_out, float *out, void *scratch, int64_t *scratch_bytes, void *stream);
 
+/* ---- stereo bus: pan and mix tracks, channel-linked loudness and limiter ------------------------------------------------------
+ * What follows a `wavtool` in every host: the mixer.  A song is several tracks (goofer_phrase_mix makes one), each with a volume
+ * and a pan fader, summed onto a stereo bus which is then brought to a loudness and under a peak ceiling.  The bus is planar:
+ * out[0 .. N) is L and out[N .. 2N) is R, a ragged batch of two signals of equal length with the CSR [0, N, 2N], so the stages
+ * that treat every signal by itself (rate conversion, equaliser, reverb) run on it unchanged.  Two stages cannot: a limiter
+ * that makes a gain per channel moves the stereo image whenever one side peaks, and BS.1770 gates a programme on the sum of its
+ * channels' energies.  Those have channel-linked forms here.  The reference has no counterpart; this is the definition (restated
+ * in numpy by tests/bus_ref.py).  All fp32 arithmetic is uncontracted.
+ *
+ * Pan law (host, float64, stored as fp32): constant power.  g = 10^(gain_db / 20), gain_db finite in [-144, 24]; pan in [-1, 1]
+ * (-1 left, 1 right), theta = (pan + 1) pi / 4; gl = fp32(g cos theta), gr = fp32(g sin theta).  Three positions are exact:
+ * pan == -1 has gr = +0.0f, pan == 1 has gl = +0.0f, and pan == 0 has gl = gr = fp32(g sqrt(0.5)) (in float64 cos(pi/4) and
+ * sin(pi/4) differ in the last place).  A muted track is not in the table at all.
+ *
+ * Mix.  Track i has a record: x, a device pointer to its len samples (tracks need not lie back to back), len >= 0, start >= 0 its
+ * position on the bus, and the finite gains gl, gr.  For t in [0, total_out):
+ *   L[t] = sum_i gl_i * x_i[t - start_i]  over the tracks with 0 <= t - start_i < len_i,   R[t] likewise with gr_i
+ * in ascending i from +0.0f, each term one rounded multiply, then one rounded add.  out[t] = L[t], out[total_out + t] = R[t];
+ * every sample of both channels is stored exactly once, zeros where no track sounds; what lies past total_out is dropped. */
+#define GOOFER_BUS_TILE 2048
+typedef struct {
+    const float *x;             /* device pointer */
+    int64_t len;                /* >= 0 */
+    int64_t start;              /* >= 0 */
+    float gl, gr;               /* finite */
+} goofer_bus_track;
+
+/* Host side (no device, no handle; x is not read): check the n records and write the cover table of the bus's tiles of
+ * GOOFER_BUS_TILE samples, tiles = ceil(total_out / GOOFER_BUS_TILE): tile_off[tiles + 1] (CSR) and tile_tracks, the tracks whose
+ * range [start, min(start + len, total_out)) meets the tile, in ascending track index (a track with an empty range is in no
+ * tile).  *need = entries of tile_tracks.  Returns 0 with both arrays written; 1 when cap < *need (only *need is valid: grow,
+ * call again); GOOFER_EINVAL for a null argument (tracks may be null when n == 0, tile_tracks when cap == 0), a negative count,
+ * length or start, a gain that is not finite, an x that is null where len > 0 or not 4-byte aligned (the pointer's value alone),
+ * or a bus of 2^31 tiles or more. */
+int goofer_host_bus_plan(const goofer_bus_track *tracks, int n, int64_t total_out, int64_t *tile_off, int32_t *tile_tracks, int64_t cap,
+                         int64_t *need);
+
+/* The bus (bus.hip): out[0 .. 2 total_out), planar, every sample stored exactly once, so `out` needs no clearing.  tracks ([n],
+ * as validated by goofer_host_bus_plan), tile_off and tile_tracks (that call's table for the same records and total_out) and out
+ * are device arrays of the caller; `out` must not overlap any track.  One workgroup per tile, eight consecutive samples of both
+ * channels per thread in registers, every source sample loaded once; no atomics, no LDS, no scratch; 16-byte loads where a
+ * wave's source is 16-byte aligned and 16-byte stores for a channel whose base is (R is not when total_out % 4 != 0).  It moves
+ * 4 sum_i len_i + 8 total_out bytes.  Asynchronous on `stream`; needs no plan.  total_out == 0: nothing is launched; n == 0:
+ * zeros.  GOOFER_EINVAL, with nothing written, for a null pointer (tracks and tile_tracks may be null when n == 0), a negative
+ * count, out or tile_tracks not 4-byte aligned, tracks or tile_off not 8-byte aligned, a bus of 2^31 tiles or more. */
+int goofer_bus_mix(goofer_ctx *ctx, const goofer_bus_track *tracks, int n, const int64_t *tile_off, const int32_t *tile_tracks,
+                   int64_t total_out, float *out, void *stream);
+
+/* The channel-linked limiter (limit.hip).  ch is 1 or 2 and n % ch == 0: signals g ch .. g ch + ch - 1 of the ragged batch are the
+ * channels of group g and have equal lengths.  The definition is goofer_limit's with step 1 replaced by
+ *   1  a[i] = max_c |x_c[i]|        (fmaxf: a NaN operand is ignored)
+ * and with R = 2 or 4 and tp_taps (goofer_host_true_peak_plan's; Z = GOOFER_TP_ZEROS) by a[i] = max_c e_c[i], e_c the envelope of
+ * the true-peak section; R == 0 is sample-peak detection and tp_taps is not read.  Steps 2 to 7 run once per group, word for
+ * word, and step 8 is y_c[i] = x_c[i] * g[i] for every channel: both channels get the same gain, so the image does not move.
+ * peak_in and min_gain are fp32 [n / ch], one pair per group.  `tiles` / n_tiles are goofer_host_limit_plan's for the groups' CSR
+ * (the group lengths; the planner is the same): one workgroup per (group, tile), and the LDS need does not grow with ch.
+ * Properties: ch == 1 gives the bits of goofer_limit (R == 0) or goofer_limit_tp; a pair (x, x) returns goofer_limit's output in
+ * both channels; a group that never exceeds c comes back bit for bit; |y_c| <= c (1 + 2^-24)^2, because g <= fl(c / a) and
+ * a >= |x_c|.  Whether a tile copies its samples (options "limit_skip", "limit_tp_skip") is decided over all channels of the
+ * group: the quiet channel beside a peak in the other one is reduced like it.  A group whose signals differ in length is neither
+ * read nor written (a table that is not the planner's).  GOOFER_EINVAL for ch outside {1, 2}, n % ch != 0, R not 0, 2 or 4, an
+ * n_tiles that is not a tile count of n / ch signals with total / ch samples, and everything goofer_limit and goofer_limit_tp
+ * refuse. */
+int goofer_limit_linked(goofer_ctx *ctx, const float *x, const int64_t *in_off, int n, int64_t total, int ch, int W, const float *taps,
+                        float c, const int32_t *tiles, int64_t n_tiles, float *out, float *peak_in, float *min_gain, int R,
+                        const float *tp_taps, void *stream);
+
+/* The channel-linked loudness gate (loudness.hip), behind a measure-only goofer_loudness_measure (target NaN) of the n channel
+ * signals on the same stream: seg_energy and seg_off ([n + 1]) are that call's.  ch is 1 or 2 and n % ch == 0.  For group g,
+ * E_g[k] = sum_c E_c[k] in ascending channel from channel 0 (BS.1770's channel weight 1.0 for L and R); blocks, both gates, L,
+ * momentary_max and the gain follow the loudness section as written for one channel, on E_g.  loud: float64 [n / ch][2]; gain:
+ * fp32 [n], the group's value in each of its channels, so goofer_loudness_apply runs unchanged.  One workgroup per group, the
+ * gating code goofer_loudness_measure's own.  A group whose channels differ in segment count gets NaN, NaN and a gain of 1.0f;
+ * a NaN energy makes its group NaN as in the definition and leaves the others alone.  target NaN: measure only.  Asynchronous
+ * on `stream`; no scratch, no plan; n == 0: nothing is launched.  GOOFER_EINVAL for ch outside {1, 2}, n % ch != 0, a null
+ * pointer, a negative count, S, target or max_gain_db outside the definition's range, gain not 4-byte aligned, the others not
+ * 8-byte aligned. */
+int goofer_loudness_link(goofer_ctx *ctx, const double *seg_energy, const int64_t *seg_off, int n, int ch, int S, double target,
+                         double max_gain_db, double *loud, float *gain, void *stream);
+
+/* goofer_pcm16 of a planar signal of ch channels of n samples, interleaved for a wav: out[i ch + c] = pcm16(x[c n + i]), the same
+ * arithmetic.  ch is 1 or 2; ch == 1 gives goofer_pcm16's bits.  Asynchronous on `stream`; n <= 0: nothing is launched. */
+int goofer_pcm16_planar(goofer_ctx *ctx, const float *x, int64_t n, int ch, int16_t *out, void *stream);
+
 /* ---- measurement / test hooks --------------------------------------------------------------- */
 
 /* HIP-event timing of every stage of goofer_synth_batch on the caller's stream: begin() arms up to
