@@ -25,7 +25,6 @@ is the stereo programme's and the limiter gives both channels one gain.  The sta
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 import os
 import sys
@@ -83,20 +82,16 @@ def samples(ms, sr) -> int:
 
 
 @dataclass
-class BusPlan(SP.BlobPlan):
+class BusPlan(SP.CoverPlan):
     """What goofer_bus_mix takes for one song: ``tracks`` (_lib.BUS_TRACK [n], the tracks that are not muted, with the device
     pointers they were planned for), the cover table ``tile_off`` (int64 [tiles + 1]) / ``tile_tracks`` (int32), ``total_out``,
     the samples of one channel; ``index``: which of the caller's tracks each record is; ``blob`` holds the three arrays back to
-    back for one upload, and a pad word (an empty table still has an address)."""
-    n: int
-    total_out: int
-    sr: int
+    back for one upload."""
     tracks: np.ndarray
     index: np.ndarray
     tile_off: np.ndarray
     tile_tracks: np.ndarray
     BLOB = ("tracks", "tile_off", "tile_tracks")
-    PAD = 4
 
     @property
     def in_off(self):
@@ -107,21 +102,14 @@ class BusPlan(SP.BlobPlan):
 def cover(records: np.ndarray, total_out: int):
     """goofer_host_bus_plan: the records checked and the cover table of the bus's tiles, (tile_off, tile_tracks).  Raises
     ValueError for a record the library refuses."""
-    lib = _lib.load()
     records = np.ascontiguousarray(records, dtype=_lib.BUS_TRACK)
     if int(total_out) < 0:
         raise ValueError("bus: total_out >= 0")
-    tiles = (int(total_out) + TILE - 1) // TILE
-    if tiles >= 1 << 31:
+    if (int(total_out) + TILE - 1) // TILE >= 1 << 31:
         raise ValueError("bus: a bus of 2^31 tiles or more")
-    tile_off = np.zeros(tiles + 1, dtype=np.int64)
-    need = C.c_int64(0)
-    tile_tracks, = SP.fit(lambda tile_tracks: lib.goofer_host_bus_plan(records.ctypes.data if len(records) else None, len(records), int(total_out),
-                                                                      tile_off.ctypes.data, *SP.cap(tile_tracks), C.byref(need)),
-                          (np.zeros(max(len(records), 1), dtype=np.int32),), lambda: (np.zeros(int(need.value), dtype=np.int32),),
-                          lambda rc: "goofer_host_bus_plan refused the tracks (%d): lengths, starts and total_out >= 0, finite gains, "
-                                     "4-byte aligned pointers" % rc)
-    return tile_off, tile_tracks[:int(need.value)]
+    return SP.cover(_lib.load().goofer_host_bus_plan, records, (), total_out, TILE,
+                    lambda rc: "goofer_host_bus_plan refused the tracks (%d): lengths, starts and total_out >= 0, finite gains, "
+                               "4-byte aligned pointers" % rc)
 
 
 def plan(ptrs_or_tensors, lengths, tracks, sr, total_out=None) -> BusPlan:
@@ -215,7 +203,7 @@ def render_file(path, out_wav, renderer=None, seed=None, tracker=None, pcm16=Tru
     song = read_song(path)
     renderer = renderer or Renderer()
     if seed is None:
-        seed = int(np.random.SeedSequence().generate_state(1, dtype=np.uint32)[0])
+        seed = P.draw_seed(np.uint32)
     tracks = []
     for job, t in song:
         if t.mute:
@@ -227,12 +215,8 @@ def render_file(path, out_wav, renderer=None, seed=None, tracker=None, pcm16=Tru
     if not live:
         raise ValueError(f"{path}: no track that sounds")
     sr = live[0][0][0].sr if out_sr is None else int(out_sr)
-    if loudness is None and limit is None:
-        bus = renderer.render_song(tracks, seed=seed, pcm16=pcm16, out_sr=out_sr)
-    else:
-        bus, st = renderer.render_song(tracks, seed=seed, pcm16=pcm16, out_sr=out_sr, loudness=loudness, limit=limit, return_stats=True)
-        if stats is not None:
-            stats.update(st)
+    bus = P.rendered(renderer.render_song, stats, loudness is not None or limit is not None, tracks=tracks, seed=seed, pcm16=pcm16,
+                     out_sr=out_sr, loudness=loudness, limit=limit)
     write_wav(out_wav, bus, sr)
     return bus
 
@@ -240,33 +224,10 @@ def render_file(path, out_wav, renderer=None, seed=None, tracker=None, pcm16=Tru
 def main(argv=None) -> int:
     import logging
     from . import limit as LM
+    from . import phrase as P
     logging.basicConfig(format="%(message)s", level=logging.INFO)
-    argv = list(sys.argv[1:] if argv is None else argv)
-    out_sr = limit = loudness = None
-    true_peak = False
-    while len(argv) > 2 and argv[0] in ("--rate", "--limit", "--loudness", "--true-peak"):
-        if argv[0] == "--true-peak":
-            true_peak = True
-            argv = argv[1:]
-        elif argv[0] == "--rate":
-            try:
-                out_sr = int(argv[1])
-            except ValueError:
-                break                   # (more than two arguments left: the usage line)
-            argv = argv[2:]
-        elif argv[0] == "--loudness":
-            try:
-                loudness = float(argv[1])
-            except ValueError:
-                break
-            argv = argv[2:]
-        else:
-            try:                        # --limit DB, or bare: the default ceiling
-                limit = 10.0 ** (float(argv[1]) / 20.0)
-                argv = argv[2:]
-            except ValueError:
-                limit = LM.CEILING
-                argv = argv[1:]
+    opts, argv = P.parse_options(list(sys.argv[1:] if argv is None else argv), ("--rate", "--limit", "--loudness", "--true-peak"))
+    out_sr, limit, loudness, true_peak = opts.get("--rate"), opts.get("--limit"), opts.get("--loudness"), "--true-peak" in opts
     if len(argv) != 2 or (true_peak and limit is None):
         logging.error("Usage:\n  python -m goofer_amd.bus [--rate HZ] [--loudness LUFS] [--limit [DB] [--true-peak]] song.txt out.wav")
         return 1
@@ -277,17 +238,7 @@ def main(argv=None) -> int:
     except Exception:                   # noqa: BLE001
         logging.exception("Failed to render")
         return 1
-    if loudness is not None:
-        print("Loudness: measured %.2f LUFS (momentary max %.2f), gain %.2f dB (target %.2f LUFS)"
-              % (stats["lufs_in"], stats["momentary_max"], 20.0 * math.log10(stats["gain"]) if stats["gain"] > 0.0 else -math.inf, loudness),
-              file=sys.stderr)
-    if true_peak:
-        print("Limiter: input true peak %.2f dBTP, output true peak %.2f dBTP, greatest reduction %.2f dB (ceiling %.2f dBTP)"
-              % (LM.dbtp(stats["true_peak_in"]), LM.dbtp(stats["true_peak_out"]), LM.reduction_db(stats["min_gain"]), LM.dbtp(limit)),
-              file=sys.stderr)
-    elif limit is not None:
-        print("Limiter: input peak %.2f dBFS, greatest reduction %.2f dB (ceiling %.2f dBFS)"
-              % (LM.dbtp(stats["peak_in"]), LM.reduction_db(stats["min_gain"]), LM.dbtp(limit)), file=sys.stderr)
+    P.report_levels(stats, loudness, limit, true_peak)
     logging.info(f"Writing {argv[1]}: {len(bus)} frames, 2 channels")
     return 0
 

@@ -3,20 +3,15 @@
 // crosses PCIe instead of every note with its overlapped parts.  The definition is in include/goofer_hip.h (goofer_phrase_note);
 // the host half, goofer_host_phrase_plan (planner.hip), checks the records and lists per tile of the track the notes that reach it.
 //
-// A gather-sum over a ragged batch without atomics: the track is cut into tiles of GOOFER_PHRASE_TILE samples, one 256-thread
-// workgroup per tile, eight consecutive samples per thread held in registers; the workgroup walks the tile's notes in ascending
-// index (the order of the sum is part of the contract) and stores each sample once.  The note index of the walk is wave-uniform,
-// so a note's record, its offsets and its seven knots are scalar loads.  Per wave and note one of three bodies runs, all with the
-// same arithmetic per sample (the same bits whichever runs):
+// A gather-sum over the tiles of the track, on the walk of tile_mix.h; here is what a note contributes.  The note index of the
+// walk is wave-uniform, so a note's record, its offsets and its seven knots are scalar loads.  Per wave and note one of three
+// bodies runs, all with the same arithmetic per sample (the same bits whichever runs):
 //   inside, one segment   the wave's 512 samples lie inside the note and between two knots (a note is tens of thousands of samples
 //                         and six segments long: nearly always) — the segment's four numbers are scalars, no compare per sample
 //   inside, some knot     the segment of each sample by five compares (pos[0] <= u < pos[6] needs none)
 //   edge                  the note starts or ends in the wave: as above, each sample guarded
 // The source of a thread starts wherever skip - start puts it: 16-byte loads where a wave-uniform test finds it aligned.
-#include "common.h"
-
-#define PH_SPT 8                      // consecutive track samples per thread
-static_assert(GOOFER_PHRASE_TILE == 256 * PH_SPT, "one workgroup of 256 threads per tile");
+#include "tile_mix.h"
 
 // g(u) of the definition for any u in [0, take): k = the largest index with pos[k] <= uf, by compares against pos[1..5]
 __device__ __forceinline__ float phrase_gain(float uf, const float (&pos)[7], const float (&val)[7])
@@ -46,18 +41,18 @@ __global__ __launch_bounds__(256) void k_phrase_mix(const float *__restrict__ x,
                                                     const int64_t *__restrict__ tile_off, const int32_t *__restrict__ tile_notes,
                                                     int64_t total_out, float *__restrict__ out)
 {
-    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const int64_t w0 = (int64_t)blockIdx.x * GOOFER_PHRASE_TILE + wave * (WAVE * PH_SPT);   // the wave's first track sample
-    if (w0 >= total_out) return;                               // (no barrier in this kernel)
-    const int64_t t0 = w0 + lane * PH_SPT;
+    int lane;
+    const int64_t w0 = mix_wave_first(lane);                   // the wave's first track sample
+    if (w0 >= total_out) return;
+    const int64_t t0 = w0 + lane * MIX_SPT;
     const bool x16 = (((uintptr_t)x) & 15) == 0;
-    float acc[PH_SPT];
+    float acc[MIX_SPT];
 #pragma unroll
-    for (int e = 0; e < PH_SPT; ++e) acc[e] = 0.0f;
+    for (int e = 0; e < MIX_SPT; ++e) acc[e] = 0.0f;
 
     const int64_t j1 = tile_off[blockIdx.x + 1];
     for (int64_t j = tile_off[blockIdx.x]; j < j1; ++j) {
-        const int i = __builtin_amdgcn_readfirstlane(tile_notes[j]);
+        const int i = mix_entry(tile_notes, j);
         const goofer_phrase_note *__restrict__ r = notes + i;
         const int64_t base = sample_off[i], len = sample_off[i + 1] - base, start = r->start;
         const int skip = r->skip, take = r->take;
@@ -67,38 +62,30 @@ __global__ __launch_bounds__(256) void k_phrase_mix(const float *__restrict__ x,
         // u of the wave's first sample; clamped into an int, out of reach of [0, 2^24) where it does not fit
         int64_t uw = w0 - start;
         uw = uw < -(1 << 30) ? -(1 << 30) : (uw > (1 << 30) ? (1 << 30) : uw);
-        const int uw0 = (int)uw, u0 = uw0 + lane * PH_SPT;
-        if (uw0 >= eff || uw0 + WAVE * PH_SPT <= 0) continue;  // the note does not reach this wave
+        const int uw0 = (int)uw, u0 = uw0 + lane * MIX_SPT;
+        if (mix_off(uw0, eff)) continue;
         float pos[7], val[7];
 #pragma unroll
         for (int k = 0; k < 7; ++k) { pos[k] = r->pos[k]; val[k] = r->val[k]; }
         const float *__restrict__ xs = x + (base + skip);      // x_i[skip + u] = xs[u]
 
-        if (uw0 >= 0 && uw0 + WAVE * PH_SPT <= eff) {          // the wave lies inside the note
-            float v[PH_SPT];
-            // 16-byte loads where the wave's source is 16-byte aligned (the same answer in every lane: a lane is 32 bytes on).  Elsewhere
-            // eight floats per lane as they lie, which the compiler merges into wide loads at 4-byte alignment: measured at 1.04 of
-            // the rate of three aligned loads from the address below and a wave-uniform shift (scripts/phrase_rate.py, docs/EXPERIMENTS.md)
-            if (x16 && ((base + skip + uw0) & 3) == 0) {
-                const float4 q0 = *reinterpret_cast<const float4 *>(xs + u0), q1 = *reinterpret_cast<const float4 *>(xs + u0 + 4);
-                v[0] = q0.x; v[1] = q0.y; v[2] = q0.z; v[3] = q0.w; v[4] = q1.x; v[5] = q1.y; v[6] = q1.z; v[7] = q1.w;
-            } else {
-#pragma unroll
-                for (int e = 0; e < PH_SPT; ++e) v[e] = xs[u0 + e];
-            }
-            const int ka = phrase_segment((float)uw0, pos), kb = phrase_segment((float)(uw0 + WAVE * PH_SPT - 1), pos);
+        if (MIX_INSIDE(uw0, eff)) {
+            float v[MIX_SPT];
+            if (x16 && ((base + skip + uw0) & 3) == 0) mix_load8_vec(xs, u0, v);
+            else mix_load8_any(xs, u0, v);
+            const int ka = phrase_segment((float)uw0, pos), kb = phrase_segment((float)(uw0 + MIX_WAVE - 1), pos);
             if (ka == kb) {                                    // one segment for the wave: its numbers are scalars
                 const int k = __builtin_amdgcn_readfirstlane(ka);
                 const float a = r->val[k], d = r->val[k + 1] - a, p = r->pos[k], w = r->pos[k + 1] - p;
 #pragma unroll
-                for (int e = 0; e < PH_SPT; ++e) acc[e] = acc[e] + (a + d * (((float)(u0 + e) - p) / w)) * v[e];
+                for (int e = 0; e < MIX_SPT; ++e) acc[e] = acc[e] + (a + d * (((float)(u0 + e) - p) / w)) * v[e];
             } else {
 #pragma unroll
-                for (int e = 0; e < PH_SPT; ++e) acc[e] = acc[e] + phrase_gain((float)(u0 + e), pos, val) * v[e];
+                for (int e = 0; e < MIX_SPT; ++e) acc[e] = acc[e] + phrase_gain((float)(u0 + e), pos, val) * v[e];
             }
-        } else {                                               // the note starts or ends in this wave
+        } else {
 #pragma unroll
-            for (int e = 0; e < PH_SPT; ++e) {
+            for (int e = 0; e < MIX_SPT; ++e) {
                 const int u = u0 + e;
                 const bool on = u >= 0 && u < eff;
                 const float xv = on ? xs[u] : 0.0f;
@@ -108,14 +95,7 @@ __global__ __launch_bounds__(256) void k_phrase_mix(const float *__restrict__ x,
         }
     }
 
-    if (t0 + PH_SPT <= total_out && (((uintptr_t)out) & 15) == 0) {
-        *reinterpret_cast<float4 *>(out + t0) = make_float4(acc[0], acc[1], acc[2], acc[3]);
-        *reinterpret_cast<float4 *>(out + t0 + 4) = make_float4(acc[4], acc[5], acc[6], acc[7]);
-    } else {
-#pragma unroll
-        for (int e = 0; e < PH_SPT; ++e)
-            if (t0 + e < total_out) out[t0 + e] = acc[e];
-    }
+    mix_store8(out, t0, total_out, t0 + MIX_SPT <= total_out && (((uintptr_t)out) & 15) == 0, acc);
 }
 
 extern "C" int goofer_phrase_mix(goofer_ctx *ctx, const float *x, const int64_t *sample_off, int n, const goofer_phrase_note *notes,
@@ -129,10 +109,9 @@ extern "C" int goofer_phrase_mix(goofer_ctx *ctx, const float *x, const int64_t 
         return goofer_fail(ctx, GOOFER_EINVAL, "goofer_phrase_mix: null pointer");
     if (((uintptr_t)x | (uintptr_t)out | (uintptr_t)tile_notes) & 3 || ((uintptr_t)sample_off | (uintptr_t)notes | (uintptr_t)tile_off) & 7)
         return goofer_fail(ctx, GOOFER_EINVAL, "goofer_phrase_mix: x, out and tile_notes must be 4-byte aligned, sample_off, notes and tile_off 8-byte aligned");
-    const int64_t tiles = (total_out + GOOFER_PHRASE_TILE - 1) / GOOFER_PHRASE_TILE;
-    if (tiles >= ((int64_t)1 << 31)) return goofer_fail(ctx, GOOFER_EINVAL, "goofer_phrase_mix: a track of %lld samples", (long long)total_out);
-    hipLaunchKernelGGL(k_phrase_mix, dim3((unsigned)tiles), dim3(256), 0, (hipStream_t)stream, x, sample_off, notes, tile_off, tile_notes,
-                       total_out, out);
+    const unsigned tiles = mix_grid(total_out);
+    if (!tiles) return goofer_fail(ctx, GOOFER_EINVAL, "goofer_phrase_mix: a track of %lld samples", (long long)total_out);
+    hipLaunchKernelGGL(k_phrase_mix, dim3(tiles), dim3(256), 0, (hipStream_t)stream, x, sample_off, notes, tile_off, tile_notes, total_out, out);
     LAUNCH_CHECK(ctx);
     return GOOFER_OK;
 }

@@ -627,6 +627,36 @@ void plan_one(const goofer_plan_request &r, int hop, int trim_rows, const double
     }
 }
 
+/* The cover table of a gather-sum mix (csrc/tile_mix.h): which of n sources each tile of GOOFER_MIX_TILE samples of the time line
+ * mixes, as a CSR in ascending source index.  range(i, &lo, &hi): source i sounds on [lo, hi), not empty and inside [0,
+ * total_out), or false for a source that contributes nothing.  The capacity protocol of the callers' contracts: *need = entries;
+ * 1 when cap < *need, with tile_list not written.  The caller has checked its arguments and records: nothing is written before
+ * that, and nothing of `tiles` size is touched for a line of 2^31 tiles or more (GOOFER_EINVAL). */
+template <typename Range>
+int mix_cover(int n, int64_t total_out, int64_t *tile_off, int32_t *tile_list, int64_t cap, int64_t *need, Range range)
+{
+    const int64_t T = GOOFER_MIX_TILE, tiles = total_out / T + (total_out % T != 0);
+    if (tiles >= ((int64_t)1 << 31)) return GOOFER_EINVAL;
+    // counts at tile_off[t + 1]; then the tiles' first entries there, which the fill advances to the first entry of tile t + 1
+    for (int64_t t = 0; t <= tiles; ++t) tile_off[t] = 0;
+    int64_t lo, hi;
+    for (int i = 0; i < n; ++i)
+        if (range(i, &lo, &hi))
+            for (int64_t t = lo / T; t <= (hi - 1) / T; ++t) ++tile_off[t + 1];
+    int64_t run = 0;
+    for (int64_t t = 0; t < tiles; ++t) {
+        const int64_t c = tile_off[t + 1];
+        tile_off[t + 1] = run;
+        run += c;
+    }
+    *need = run;
+    if (run > cap) return 1;
+    for (int i = 0; i < n; ++i)
+        if (range(i, &lo, &hi))
+            for (int64_t t = lo / T; t <= (hi - 1) / T; ++t) tile_list[tile_off[t + 1]++] = i;
+    return GOOFER_OK;
+}
+
 }  // namespace
 
 struct goofer_host_plans {
@@ -983,8 +1013,6 @@ int goofer_host_phrase_plan(const goofer_phrase_note *notes, const int64_t *note
 {
     if (n < 0 || total_out < 0 || cap < 0 || !tile_off || !need || (n > 0 && (!notes || !note_len)) || (cap > 0 && !tile_notes))
         return GOOFER_EINVAL;
-    const int64_t T = GOOFER_PHRASE_TILE, tiles = total_out / T + (total_out % T != 0);
-    if (tiles >= ((int64_t)1 << 31)) return GOOFER_EINVAL;
     for (int i = 0; i < n; ++i) {
         const goofer_phrase_note &r = notes[i];
         if (note_len[i] < 0 || r.skip < 0 || r.take < 0 || r.take > (1 << 24)) return GOOFER_EINVAL;
@@ -992,24 +1020,8 @@ int goofer_host_phrase_plan(const goofer_phrase_note *notes, const int64_t *note
         for (int k = 0; k < 7; ++k)
             if (!std::isfinite(r.pos[k]) || !std::isfinite(r.val[k]) || (k > 0 && r.pos[k] < r.pos[k - 1])) return GOOFER_EINVAL;
     }
-    // counts at tile_off[t + 1]; then the tiles' first entries there, which the fill advances to the first entry of tile t + 1
-    for (int64_t t = 0; t <= tiles; ++t) tile_off[t] = 0;
-    int64_t lo, hi;
-    for (int i = 0; i < n; ++i)
-        if (phrase_range(notes[i], note_len[i], total_out, &lo, &hi))
-            for (int64_t t = lo / T; t <= (hi - 1) / T; ++t) ++tile_off[t + 1];
-    int64_t run = 0;
-    for (int64_t t = 0; t < tiles; ++t) {
-        const int64_t c = tile_off[t + 1];
-        tile_off[t + 1] = run;
-        run += c;
-    }
-    *need = run;
-    if (run > cap) return 1;
-    for (int i = 0; i < n; ++i)
-        if (phrase_range(notes[i], note_len[i], total_out, &lo, &hi))
-            for (int64_t t = lo / T; t <= (hi - 1) / T; ++t) tile_notes[tile_off[t + 1]++] = i;
-    return GOOFER_OK;
+    return mix_cover(n, total_out, tile_off, tile_notes, cap, need,
+                     [&](int i, int64_t *lo, int64_t *hi) { return phrase_range(notes[i], note_len[i], total_out, lo, hi); });
 }
 
 /* The stereo bus (include/goofer_hip.h; the kernel: bus.hip): the records checked, and which tracks each tile of the bus mixes.
@@ -1025,31 +1037,15 @@ int goofer_host_bus_plan(const goofer_bus_track *tracks, int n, int64_t total_ou
                          int64_t *need)
 {
     if (n < 0 || total_out < 0 || cap < 0 || !tile_off || !need || (n > 0 && !tracks) || (cap > 0 && !tile_tracks)) return GOOFER_EINVAL;
-    const int64_t T = GOOFER_BUS_TILE, tiles = total_out / T + (total_out % T != 0);
-    if (tiles >= ((int64_t)1 << 31)) return GOOFER_EINVAL;
     for (int i = 0; i < n; ++i) {
         const goofer_bus_track &r = tracks[i];
         if (r.len < 0 || r.start < 0 || !std::isfinite(r.gl) || !std::isfinite(r.gr)) return GOOFER_EINVAL;
         if ((r.len > 0 && !r.x) || ((uintptr_t)r.x & 3)) return GOOFER_EINVAL;   // (the pointer's value alone)
     }
-    // counts at tile_off[t + 1]; then the tiles' first entries there, which the fill advances to the first entry of tile t + 1
-    for (int64_t t = 0; t <= tiles; ++t) tile_off[t] = 0;
-    int64_t hi;
-    for (int i = 0; i < n; ++i)
-        if (bus_range(tracks[i], total_out, &hi))
-            for (int64_t t = tracks[i].start / T; t <= (hi - 1) / T; ++t) ++tile_off[t + 1];
-    int64_t run = 0;
-    for (int64_t t = 0; t < tiles; ++t) {
-        const int64_t c = tile_off[t + 1];
-        tile_off[t + 1] = run;
-        run += c;
-    }
-    *need = run;
-    if (run > cap) return 1;
-    for (int i = 0; i < n; ++i)
-        if (bus_range(tracks[i], total_out, &hi))
-            for (int64_t t = tracks[i].start / T; t <= (hi - 1) / T; ++t) tile_tracks[tile_off[t + 1]++] = i;
-    return GOOFER_OK;
+    return mix_cover(n, total_out, tile_off, tile_tracks, cap, need, [&](int i, int64_t *lo, int64_t *hi) {
+        *lo = tracks[i].start;
+        return bus_range(tracks[i], total_out, hi);
+    });
 }
 
 /* Output-rate conversion (include/goofer_hip.h; the kernel: rate.hip): geometry, the Kaiser-windowed sinc table in float64 and

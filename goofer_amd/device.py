@@ -222,6 +222,15 @@ class Context:
         self._check(self.lib.goofer_pcm16_planar(self.h, _ptr(x), n, 2, _ptr(out), self._stream()))
         return out
 
+    def _mix_out(self, who, out, samples, channels, what):
+        """``out`` of a mix onto a time line of ``samples`` samples and ``channels`` planar channels (phrase_mix, bus_mix): a new
+        tensor where it is None, else checked, a ValueError in ``who``'s name that calls the samples ``what``."""
+        if out is None:
+            return torch.empty(channels * samples, dtype=torch.float32, device=self.device)
+        if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != channels * samples:
+            raise ValueError("%s: out must be a contiguous float32 tensor of the %s samples" % (who, what))
+        return out
+
     def bus_mix(self, xs, plan, out=None):
         """Finished tracks panned and summed onto a planar stereo bus on the device (goofer_bus_mix; the definition:
         include/goofer_hip.h, "stereo bus", restated in tests/bus_ref.py).  ``xs``: the tracks, a list of contiguous fp32 device
@@ -237,10 +246,7 @@ class Context:
                 raise ValueError("bus_mix: track %d must be a contiguous float32 tensor of the plan's %d samples" % (k, plan.tracks["len"][j]))
             if int(plan.tracks["len"][j]) and x.data_ptr() != int(plan.tracks["x"][j]):
                 raise ValueError("bus_mix: track %d is not the tensor the plan was made for" % k)
-        if out is None:
-            out = torch.empty(2 * total, dtype=torch.float32, device=self.device)
-        elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != 2 * total:
-            raise ValueError("bus_mix: out must be a contiguous float32 tensor of the bus's 2 * %d samples" % total)
+        out = self._mix_out("bus_mix", out, total, 2, "bus's 2 * %d" % total)
         tracks, tile_off, tile_tracks = plan.device_tables(self)
         self._check(self.lib.goofer_bus_mix(self.h, _ptr(tracks), n, _ptr(tile_off), _ptr(tile_tracks), total, _ptr(out), self._stream()))
         return out
@@ -259,10 +265,7 @@ class Context:
             raise ValueError("phrase_mix: sample_off is one contiguous int64 CSR of the plan's %d notes" % n)
         if x.dtype != torch.float32 or not x.is_contiguous():
             raise ValueError("phrase_mix: x must be a contiguous float32 tensor")
-        if out is None:
-            out = torch.empty(total, dtype=torch.float32, device=self.device)
-        elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != total:
-            raise ValueError("phrase_mix: out must be a contiguous float32 tensor of the track's %d samples" % total)
+        out = self._mix_out("phrase_mix", out, total, 1, "track's %d" % total)
         notes, tile_off, tile_notes = plan.device_tables(self)
         if n and not x.numel():                                # notes without samples: the library still wants an array
             x = torch.zeros(4, dtype=torch.float32, device=self.device)

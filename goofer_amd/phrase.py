@@ -37,7 +37,6 @@ wav at the output's rate; the impulse response's length and the tail it adds go 
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 import sys
 from dataclasses import dataclass
@@ -139,38 +138,26 @@ class Entry:
 
 
 @dataclass
-class PhrasePlan(SP.BlobPlan):
+class PhrasePlan(SP.CoverPlan):
     """What goofer_phrase_mix takes for one phrase: ``notes`` (_lib.PHRASE_NOTE [n]), the cover table ``tile_off`` (int64
-    [tiles + 1]) / ``tile_notes`` (int32), ``total_out``; ``blob`` holds the three back to back for one upload, and a pad word
-    (no empty tensor on the device: an empty table still has an address)."""
-    n: int
-    total_out: int
-    sr: int
+    [tiles + 1]) / ``tile_notes`` (int32), ``total_out``; ``blob`` holds the three back to back for one upload."""
     notes: np.ndarray
     note_len: np.ndarray
     tile_off: np.ndarray
     tile_notes: np.ndarray
     BLOB = ("notes", "tile_off", "tile_notes")                 # device_tables: these three (the records as bytes), in this order
-    PAD = 4
 
 
 def cover(notes: np.ndarray, note_len, total_out: int):
     """goofer_host_phrase_plan: the records checked and the cover table of the track's tiles, (tile_off, tile_notes).  Raises
     ValueError for a record the library refuses."""
-    lib = _lib.load()
     notes = np.ascontiguousarray(notes, dtype=_lib.PHRASE_NOTE)
     note_len = np.ascontiguousarray(note_len, dtype=np.int64)
     if note_len.shape != notes.shape:
         raise ValueError("one length per note")
-    tiles = (int(total_out) + TILE - 1) // TILE if total_out > 0 else 0
-    tile_off = np.zeros(tiles + 1, dtype=np.int64)
-    need = C.c_int64(0)
-    tile_notes, = SP.fit(lambda tile_notes: lib.goofer_host_phrase_plan(notes.ctypes.data, note_len.ctypes.data, len(notes), int(total_out),
-                                                                       tile_off.ctypes.data, *SP.cap(tile_notes), C.byref(need)),
-                         (np.zeros(max(len(notes), 1), dtype=np.int32),), lambda: (np.zeros(int(need.value), dtype=np.int32),),
-                         lambda rc: "goofer_host_phrase_plan refused the phrase (%d): knots must be finite and non-decreasing from 0 to "
-                                    "take, 0 <= take <= 2^24, skip >= 0, lengths and total_out >= 0" % rc)
-    return tile_off, tile_notes[:int(need.value)]
+    return SP.cover(_lib.load().goofer_host_phrase_plan, notes, (note_len.ctypes.data,), total_out, TILE,
+                    lambda rc: "goofer_host_phrase_plan refused the phrase (%d): knots must be finite and non-decreasing from 0 to "
+                               "take, 0 <= take <= 2^24, skip >= 0, lengths and total_out >= 0" % rc)
 
 
 def plan_records(notes, note_len, total_out: int, sr: int = 0) -> PhrasePlan:
@@ -282,75 +269,95 @@ def render_job(path, out_wav, renderer=None, seed=None, tracker=None, pcm16=True
     renderer = renderer or Renderer()
     jobs, entries = load_job(path, renderer, tracker)
     if seed is None:
-        seed = int(np.random.SeedSequence().generate_state(1, dtype=np.uint64)[0])
+        seed = draw_seed(np.uint64)
     if reverb is not None:
         from . import reverb as RV
         reverb = RV.parse(reverb)
         rv_plan = RV.plan(jobs[0][0].sr if out_sr is None else int(out_sr), [], reverb)
         if stats is not None:
             stats.update({"reverb_taps": rv_plan.L, "reverb_tail": rv_plan.added})
-    if limit is None and loudness is None and compress is None:
-        track = renderer.render_phrase(jobs, entries, seed=seed, pcm16=pcm16, out_sr=out_sr, eq=eq, reverb=reverb)
-    else:
-        track, st = renderer.render_phrase(jobs, entries, seed=seed, pcm16=pcm16, out_sr=out_sr, limit=limit, return_stats=True,
-                                           loudness=loudness, compress=compress, eq=eq, reverb=reverb)
-        if stats is not None:
-            stats.update(st)
+    track = rendered(renderer.render_phrase, stats, limit is not None or loudness is not None or compress is not None, jobs=jobs,
+                     entries=entries, seed=seed, pcm16=pcm16, out_sr=out_sr, limit=limit, loudness=loudness, compress=compress, eq=eq,
+                     reverb=reverb)
     write_wav(out_wav, track, jobs[0][0].sr if out_sr is None else int(out_sr))
     return track
 
 
-def main(argv=None) -> int:
-    import logging
+# ---- what the two command lines share (this one and goofer_amd.bus) -----------------------------------------------------------
+
+def draw_seed(dtype) -> int:
+    """A seed for a render that was given none, from the system's entropy.  The width is the caller's: a phrase draws 64 bits,
+    a song 32 (its tracks get seed + index)."""
+    return int(np.random.SeedSequence().generate_state(1, dtype=dtype)[0])
+
+
+def rendered(render, stats, with_stats, **kw):
+    """``render(**kw)``: ``Renderer.render_phrase`` or ``render_song``, asked for its statistics only where a stage that has some
+    is on (``with_stats``; they refuse ``return_stats`` otherwise); the statistics go into ``stats``, a dict or None."""
+    if not with_stats:
+        return render(**kw)
+    out, st = render(return_stats=True, **kw)
+    if stats is not None:
+        stats.update(st)
+    return out
+
+
+def parse_options(argv, accepted):
+    """The options in front of the two file names of a command line: ({option: value}, what is left of ``argv``).  ``accepted``:
+    the options this command line takes, of ``--rate HZ``, ``--loudness LUFS``, ``--eq SPEC``, ``--compress SPEC``, ``--reverb
+    SPEC``, ``--limit [DB]`` (a linear ceiling; bare: the default one) and the flag ``--true-peak``.  An option is read only
+    while more than two arguments are left, and a value that does not parse ends the loop, so that more than two are left
+    then: the caller's usage line."""
+    import importlib
     from . import limit as LM
-    logging.basicConfig(format="%(message)s", level=logging.INFO)
-    argv = list(sys.argv[1:] if argv is None else argv)
-    out_sr = limit = loudness = compress = eq = reverb = None
-    true_peak = False
-    while len(argv) > 2 and argv[0] in ("--rate", "--limit", "--loudness", "--compress", "--true-peak", "--eq", "--reverb"):
-        if argv[0] == "--true-peak":
-            true_peak = True
-            argv = argv[1:]
-        elif argv[0] == "--rate":
-            try:
-                out_sr = int(argv[1])
-            except ValueError:
-                break                   # (more than two arguments left: the usage line)
-            argv = argv[2:]
-        elif argv[0] == "--loudness":
-            try:
-                loudness = float(argv[1])
-            except ValueError:
-                break
-            argv = argv[2:]
-        elif argv[0] == "--eq":
-            from . import eq as EQ
-            try:
-                eq = EQ.parse(argv[1])
-            except ValueError:
-                break
-            argv = argv[2:]
-        elif argv[0] == "--reverb":
-            from . import reverb as RV
-            try:
-                reverb = RV.parse(argv[1])
-            except ValueError:
-                break
-            argv = argv[2:]
-        elif argv[0] == "--compress":
-            from . import compress as CP
-            try:
-                compress = CP.parse(argv[1])
-            except ValueError:
-                break
-            argv = argv[2:]
-        else:
-            try:                        # --limit DBFS, or bare: the default ceiling
-                limit = 10.0 ** (float(argv[1]) / 20.0)
+    stages = {"--eq": "eq", "--compress": "compress", "--reverb": "reverb"}       # parsed by their modules, loaded when asked for
+    values = {"--rate": int, "--loudness": float}
+    opts = {}
+    while len(argv) > 2 and argv[0] in accepted:
+        name = argv[0]
+        if name == "--true-peak":
+            opts[name], argv = True, argv[1:]
+        elif name == "--limit":
+            try:                        # --limit DB, or bare: the default ceiling
+                opts[name] = 10.0 ** (float(argv[1]) / 20.0)
                 argv = argv[2:]
             except ValueError:
-                limit = LM.CEILING
-                argv = argv[1:]
+                opts[name], argv = LM.CEILING, argv[1:]
+        else:
+            parse = values.get(name) or importlib.import_module("." + stages[name], __package__).parse
+            try:
+                opts[name] = parse(argv[1])
+            except ValueError:
+                break
+            argv = argv[2:]
+    return opts, argv
+
+
+def report_levels(stats, loudness, limit, true_peak):
+    """The lines of the loudness stage and the limiter on stderr, from a render's statistics.  (A peak of 0 prints as -inf
+    dBFS: ``limit.dbtp``, which is what both command lines spelt out.)"""
+    from . import limit as LM
+    if loudness is not None:
+        print("Loudness: measured %.2f LUFS (momentary max %.2f), gain %.2f dB (target %.2f LUFS)"
+              % (stats["lufs_in"], stats["momentary_max"], LM.dbtp(stats["gain"]), loudness), file=sys.stderr)
+    if true_peak:
+        print("Limiter: input true peak %.2f dBTP, output true peak %.2f dBTP, greatest reduction %.2f dB (ceiling %.2f dBTP)"
+              % (LM.dbtp(stats["true_peak_in"]), LM.dbtp(stats["true_peak_out"]), LM.reduction_db(stats["min_gain"]), LM.dbtp(limit)),
+              file=sys.stderr)
+    elif limit is not None:
+        print("Limiter: input peak %.2f dBFS, greatest reduction %.2f dB (ceiling %.2f dBFS)"
+              % (LM.dbtp(stats["peak_in"]), LM.reduction_db(stats["min_gain"]), LM.dbtp(limit)), file=sys.stderr)
+
+
+def main(argv=None) -> int:
+    import logging
+    from . import eq as EQ
+    from . import limit as LM
+    logging.basicConfig(format="%(message)s", level=logging.INFO)
+    opts, argv = parse_options(list(sys.argv[1:] if argv is None else argv),
+                               ("--rate", "--limit", "--loudness", "--compress", "--true-peak", "--eq", "--reverb"))
+    out_sr, limit, loudness, compress, eq, reverb = (opts.get(k) for k in ("--rate", "--limit", "--loudness", "--compress", "--eq", "--reverb"))
+    true_peak = "--true-peak" in opts
     if len(argv) != 2 or (true_peak and limit is None):
         logging.error("Usage:\n  python -m goofer_amd.phrase [--rate HZ] [--eq KIND:F0[:GAIN_DB[:Q]],...] [--compress T:R[:ATTACK:RELEASE[:KNEE[:MAKEUP]]]] "
                       "[--reverb room:RT60_S[:WET_DB[:PREDELAY_MS[:SEED]]] | ir:PATH[:WET_DB[:PREDELAY_MS]]] [--loudness LUFS] "
@@ -373,19 +380,7 @@ def main(argv=None) -> int:
     if reverb is not None:
         print("Reverb: impulse response of %d taps, wet %g dB, dry %g dB, pre-delay %g ms; the tail adds %d samples"
               % (stats["reverb_taps"], reverb.wet_db, reverb.dry_db, reverb.predelay_ms, stats["reverb_tail"]), file=sys.stderr)
-    if loudness is not None:
-        print("Loudness: measured %.2f LUFS (momentary max %.2f), gain %.2f dB (target %.2f LUFS)"
-              % (stats["lufs_in"], stats["momentary_max"], 20.0 * math.log10(stats["gain"]) if stats["gain"] > 0.0 else -math.inf, loudness),
-              file=sys.stderr)
-    if true_peak:
-        print("Limiter: input true peak %.2f dBTP, output true peak %.2f dBTP, greatest reduction %.2f dB (ceiling %.2f dBTP)"
-              % (LM.dbtp(stats["true_peak_in"]), LM.dbtp(stats["true_peak_out"]), LM.reduction_db(stats["min_gain"]), LM.dbtp(limit)),
-              file=sys.stderr)
-    elif limit is not None:
-        peak = stats["peak_in"]
-        print("Limiter: input peak %.2f dBFS, greatest reduction %.2f dB (ceiling %.2f dBFS)"
-              % (20.0 * math.log10(peak) if peak > 0.0 else -math.inf, LM.reduction_db(stats["min_gain"]), 20.0 * math.log10(limit)),
-              file=sys.stderr)
+    report_levels(stats, loudness, limit, true_peak)
     logging.info(f"Writing {argv[1]}: {len(track)} samples")
     return 0
 

@@ -450,12 +450,14 @@ class Renderer:
             RV.plan(jobs[0][0].sr if out_sr is None else int(out_sr), [], chain[4])
         return (jobs[0][0].sr, None if out_sr is None or int(out_sr) in rates else int(out_sr), *chain)
 
-    def _finish(self, x, d_off, lengths, sr, to_sr, compress, loudness, limit, eq=None, reverb=None, true_peak_out=False):
+    def _finish(self, x, d_off, lengths, sr, to_sr, compress, loudness, limit, eq=None, reverb=None, true_peak_out=False, channels=1):
         """The finishing chain over the signals of ``lengths`` samples lying back to back in the device tensor ``x`` at ``sr``
         (``d_off``: their CSR on the device, or None): convert to ``to_sr``, eq, compress, reverb, loudness, limit, each with its
         parsed settings (the reverb's longer signals go on like the converter's); a stage whose setting is None launches nothing and allocates nothing.  Returns (the tensor, the signals'
         lengths in it, the statistics as the stages return them, device tensors: ``max_reduction``; ``loud``, ``gain``;
-        ``peak_in``, ``min_gain``, and with ``true_peak_out`` behind a true-peak limiter ``true_peak_out``)."""
+        ``peak_in``, ``min_gain``, and with ``true_peak_out`` behind a true-peak limiter ``true_peak_out``).  ``channels`` 2: signals
+        2g and 2g + 1 are the channels of one programme (a planar stereo bus), and loudness and limiter run in their linked
+        forms, one gain for both channels; the stages in front of them treat every signal by itself either way."""
         lengths, stats = np.asarray(lengths, dtype=np.int64), {}
         if to_sr is not None:
             plan = RT.plan(sr, to_sr, lengths)
@@ -468,13 +470,29 @@ class Renderer:
             plan = RV.plan(sr, lengths, reverb)
             x, lengths = self.ctx.reverb(x, None, plan, reverb.spectra(self.ctx, sr)), np.diff(plan.out_off)
         if loudness is not None:
-            x, stats["loud"], stats["gain"], _ = self.ctx.loudness(x, None, LD.plan(sr, lengths), *loudness)
+            x, stats["loud"], stats["gain"], _ = self.ctx.loudness(x, None, LD.plan(sr, lengths), *loudness, channels=channels)
         if limit is not None:
-            plan = LM.plan(sr, lengths, *limit)
+            plan = LM.plan(sr, lengths, *limit, channels=channels)
             x, stats["peak_in"], stats["min_gain"] = self.ctx.limit(x, None, plan)
-            if true_peak_out and plan.true_peak:
-                stats["true_peak_out"] = self.ctx.true_peak(x, None, plan)
+            if true_peak_out and plan.true_peak:               # (a linked plan's tile table is the groups': the meter gets its own)
+                stats["true_peak_out"] = self.ctx.true_peak(x, None, plan if channels == 1 else LM.true_peak_plan(sr, lengths))
         return x, lengths, stats
+
+    @staticmethod
+    def _host_stats(st):
+        """The statistics of ``_finish`` (device tensors of a track or a stereo bus: one programme) as Python floats under the
+        names ``render_phrase`` and ``render_song`` return them by; ``true_peak_out`` is the larger of the channels'."""
+        res = {}
+        if "peak_in" in st:
+            res.update({"peak_in": float(st["peak_in"].cpu()[0]), "min_gain": float(st["min_gain"].cpu()[0])})
+        if "true_peak_out" in st:
+            res.update({"true_peak_in": res["peak_in"], "true_peak_out": float(st["true_peak_out"].cpu().max())})
+        if "loud" in st:
+            loud = st["loud"].cpu()
+            res.update({"lufs_in": float(loud[0, 0]), "momentary_max": float(loud[0, 1]), "gain": float(st["gain"].cpu()[0])})
+        if "max_reduction" in st:
+            res["max_reduction_db"] = float(st["max_reduction"].cpu()[0])
+        return res
 
     def render(self, jobs, seed: int = 0, phi_seeds=None, return_parts: bool = False, noise_seeds=None, out_sr=None, limit=None,
                loudness=None, compress=None, eq=None, reverb=None):
@@ -567,17 +585,7 @@ class Renderer:
             track = self.ctx.pcm16(track)
         self.ctx.check()                                   # synchronises; raises if the device flagged a note
         if return_stats:
-            res = {}
-            if "peak_in" in st:
-                res.update({"peak_in": float(st["peak_in"].cpu()[0]), "min_gain": float(st["min_gain"].cpu()[0])})
-            if "true_peak_out" in st:
-                res.update({"true_peak_in": res["peak_in"], "true_peak_out": float(st["true_peak_out"].cpu()[0])})
-            if "loud" in st:
-                loud = st["loud"].cpu()
-                res.update({"lufs_in": float(loud[0, 0]), "momentary_max": float(loud[0, 1]), "gain": float(st["gain"].cpu()[0])})
-            if "max_reduction" in st:
-                res["max_reduction_db"] = float(st["max_reduction"].cpu()[0])
-            return track.cpu().numpy(), res
+            return track.cpu().numpy(), self._host_stats(st)
         return track.cpu().numpy()
 
     def _phrase_track(self, jobs, entries, seed, phi_seeds, noise_seeds, chain, true_peak_out=False):
@@ -628,28 +636,13 @@ class Renderer:
             x, n, _ = self._phrase_track(jobs, entries, seed + k if t.seed is None else t.seed, None, None, chain)
             xs[k], lens[k] = x, int(n[0])
         plan = B.plan([x if x is not None else 0 for x in xs], lens, [t for _, _, t in tracks], sr)
-        bus, N, st = self.ctx.bus_mix(xs, plan), plan.total_out, {}
-        if loudness is not None:
-            bus, st["loud"], st["gain"], _ = self.ctx.loudness(bus, None, LD.plan(sr, [N, N]), *loudness, channels=2)
-        if limit is not None:
-            lplan = LM.plan(sr, [N, N], *limit, channels=2)
-            bus, st["peak_in"], st["min_gain"] = self.ctx.limit(bus, None, lplan)
-            if return_stats and lplan.true_peak:
-                st["true_peak_out"] = self.ctx.true_peak(bus, None, LM.true_peak_plan(sr, [N, N]))
+        N = plan.total_out
+        bus, _, st = self._finish(self.ctx.bus_mix(xs, plan), None, [N, N], sr, None, None, loudness, limit, true_peak_out=return_stats,
+                                  channels=2)
         out = self.ctx.pcm16(bus, channels=2) if pcm16 else bus.view(2, N).t()
         self.ctx.check()                                   # synchronises; raises if the device flagged a note
         out = np.ascontiguousarray(out.cpu().numpy())
-        if not return_stats:
-            return out
-        res = {}
-        if "peak_in" in st:
-            res.update({"peak_in": float(st["peak_in"].cpu()[0]), "min_gain": float(st["min_gain"].cpu()[0])})
-        if "true_peak_out" in st:
-            res.update({"true_peak_in": res["peak_in"], "true_peak_out": float(st["true_peak_out"].cpu().max())})
-        if "loud" in st:
-            loud = st["loud"].cpu()
-            res.update({"lufs_in": float(loud[0, 0]), "momentary_max": float(loud[0, 1]), "gain": float(st["gain"].cpu()[0])})
-        return out, res
+        return (out, self._host_stats(st)) if return_stats else out
 
     def assemble(self, prep):
         """goofer_assemble_batch alone (asynchronous): envelope rows, f0 and voicing mask of the batch."""

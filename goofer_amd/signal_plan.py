@@ -1,7 +1,10 @@
-"""What the plans of the stages over finished audio share (phrase, rate, eq, compress, loudness, limit): one blob per plan for one
-upload, cut into typed views on the device; the signals' lengths as a CSR with the refusals every stage makes; and the capacity
-protocol of the library's host planners (include/goofer_hip.h)."""
+"""What the plans of the stages over finished audio share (phrase, bus, rate, eq, compress, loudness, limit): one blob per plan
+for one upload, cut into typed views on the device; the signals' lengths as a CSR with the refusals every stage makes; the
+capacity protocol of the library's host planners (include/goofer_hip.h); and the cover table of the two mixers."""
 from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
 
 import numpy as np
 
@@ -37,6 +40,17 @@ class BlobPlan:
     def device_tables(self, ctx):
         """The arrays of ``BLOB``, in that order, on ``ctx``'s device: views of the blob, uploaded on first use."""
         return self._tables(ctx)[:len(self.BLOB)]
+
+
+@dataclass
+class CoverPlan(BlobPlan):
+    """Base of the plan of a gather-sum mix (phrase, bus): ``n`` records, the ``total_out`` samples of the time line they are
+    summed onto and its rate ``sr``; the plan adds its records and the cover table (``cover``), which ``BLOB`` names, and the blob
+    ends in a pad word (no empty tensor on the device: an empty table still has an address)."""
+    n: int
+    total_out: int
+    sr: int
+    PAD = 4
 
 
 class SignalPlan(BlobPlan):
@@ -81,3 +95,17 @@ def fit(call, bufs, grown, refused):
     if rc != 0:
         raise ValueError(refused(rc))
     return bufs
+
+
+def cover(planner, records, extra, total_out, tile, refused):
+    """The cover table of a gather-sum mix by one of the library's planners (goofer_host_phrase_plan, goofer_host_bus_plan):
+    ``planner(records, *extra, n, total_out, tile_off, tile_list, cap, need)`` checks the ``records`` (a contiguous array) and
+    lists per tile of ``tile`` samples the records that reach it.  Returns (tile_off int64 [tiles + 1], tile_list int32).
+    Raises ValueError(refused(rc)) for what the planner refuses."""
+    total_out = int(total_out)
+    tile_off = np.zeros((total_out + tile - 1) // tile + 1 if total_out > 0 else 1, dtype=np.int64)
+    need = C.c_int64(0)
+    tile_list, = fit(lambda tile_list: planner(records.ctypes.data if len(records) else None, *extra, len(records), total_out,
+                                               tile_off.ctypes.data, *cap(tile_list), C.byref(need)),
+                     (np.zeros(max(len(records), 1), dtype=np.int32),), lambda: (np.zeros(int(need.value), dtype=np.int32),), refused)
+    return tile_off, tile_list[:int(need.value)]

@@ -696,7 +696,10 @@ int goofer_legacy_normal_jobs(goofer_ctx *ctx, const goofer_legacy_job *jobs, in
  * pos[k+1] > pos[k] — and, in fp32 and in this order,
  *   g = val[k] + (val[k+1] - val[k]) * (((float)u - pos[k]) / (pos[k+1] - pos[k]))
  * Coincident knots are a step (the later value holds from that position on); nothing divides by zero. */
-#define GOOFER_PHRASE_TILE 2048
+/* The tiling of the gather-sum mixers (this one and the stereo bus below; csrc/tile_mix.h): their planners' cover tables are laid
+ * out for this number, and each mixer's own name is defined from it. */
+#define GOOFER_MIX_TILE 2048         /* samples of a tile: one 256-thread workgroup, eight samples per thread */
+#define GOOFER_PHRASE_TILE GOOFER_MIX_TILE
 typedef struct {
     int64_t start;
     int32_t skip;
@@ -1310,7 +1313,7 @@ int goofer_reverb(goofer_ctx *ctx, const float *x, const int64_t *in_off, int n,
  *   L[t] = sum_i gl_i * x_i[t - start_i]  over the tracks with 0 <= t - start_i < len_i,   R[t] likewise with gr_i
  * in ascending i from +0.0f, each term one rounded multiply, then one rounded add.  out[t] = L[t], out[total_out + t] = R[t];
  * every sample of both channels is stored exactly once, zeros where no track sounds; what lies past total_out is dropped. */
-#define GOOFER_BUS_TILE 2048
+#define GOOFER_BUS_TILE GOOFER_MIX_TILE
 typedef struct {
     const float *x;             /* device pointer */
     int64_t len;                /* >= 0 */

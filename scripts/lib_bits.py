@@ -1,11 +1,11 @@
 #!/usr/bin/env python
 """Do two builds of libgoofer_hip.so compute the same bits?  The before / after check of a refactor of shared kernel code.
 
-usage: scripts/lib_bits.py <libA.so> <libB.so> [--out FILE] [--limit SECONDS] [--set ragged|stages|walkers|all]
+usage: scripts/lib_bits.py <libA.so> <libB.so> [--out FILE] [--limit SECONDS] [--set ragged|stages|walkers|mixes|all]
 
 Each library gets one fresh child process (GOOFER_HIP_LIB set, as scripts/lib_ab.sh does) under its own `timeout -k 10`; the
 second starts only if the first exited 0.  A child runs a fixed, seeded case list twice and prints {case: {output: sha256}} of
-both runs.  Three sets of cases (default: all):
+both runs.  Four sets of cases (default: all):
   ragged  the entry points that reach the kernels built on csrc/ragged.h — the post chain, the cascade, the synthesis on its
           spectra routes with the jitter, vibrato and sub-harmonic keyword sets, normal_fill, smooth_mask_ds, irfft_ola
   stages  the stages built on csrc/tile_scan.h, each on its own test batches at its test rates — loudness measured and normalised
@@ -15,6 +15,11 @@ both runs.  Three sets of cases (default: all):
   walkers the four frame walkers (csrc/ola_walk.h) on synth_ref.long_batch through tests/test_gpu_walker_runs._walk: every route of
           its WALKERS table at walk_run 0 and at one forced run (95; 256 for k_irfft_ola1), once with injected phases and once
           with Philox — harm, uv, bre, rec, mix, note_mag, note_peak and, where the route has one, the frame_skip view
+  mixes   the two gather-sum mixes (csrc/tile_mix.h) on their tests' inputs, by the tests' own builders: goofer_phrase_mix on every
+          entry of tests/test_gpu_phrase.CASES, on _phrase() behind leading rests of 0, 1, 2047 and 2048 samples and with `out` and
+          `x` off a 16-byte boundary; goofer_bus_mix on one track at every pan and length, the three tracks with edges and an empty
+          tile behind source leads 0 and 1, the alignment grid and the order of the sum — the output and, the planner being in the
+          library too, the plan's tile_off and tile list
 
 An output whose digest differs between the two runs of one library is listed as non-deterministic and not compared across the
 libraries.  Only outputs behind k_note_sumsq are expected there (post chain, notes with tension != 0 that are longer than a
@@ -200,12 +205,71 @@ def _walker_cases(ctx):
     return out
 
 
+def _mix_cases(ctx):
+    """{case: {output name: sha256}} of one pass over the two mixes on csrc/tile_mix.h"""
+    import numpy as np
+    import torch
+    import test_gpu_bus as BU
+    import test_gpu_phrase as PH
+    from goofer_amd import bus as B
+    from goofer_amd import phrase as P
+    out = {}
+
+    def phrase(name, xs, notes, total, **kw):
+        plan = P.plan_records(np.array(notes, dtype=PH._lib.PHRASE_NOTE).reshape(-1), [len(x) for x in xs], total)
+        out["phrase/" + name] = {"track": _sha(PH._mix(ctx, xs, notes, total, **kw)), "tile_off": _sha(plan.tile_off),
+                                 "tile_notes": _sha(plan.tile_notes)}
+
+    def bus(name, xs, tracks, *args):
+        got, _, plan = BU._mix(ctx, xs, tracks, *args)
+        out["bus/" + name] = {"bus": _sha(got), "tile_off": _sha(plan.tile_off), "tile_tracks": _sha(plan.tile_tracks)}
+
+    for name, (xs, notes, total) in PH.CASES.items():
+        phrase(name, xs, notes, total)
+    xs, notes, total = PH._phrase(np.random.default_rng(7))
+    for lead in (0, 1, 2047, 2048):
+        moved = [r.copy() for r in notes]
+        for r in moved:
+            r["start"] += lead
+        phrase("lead %d" % lead, xs, moved, total + lead)
+    xs, notes, total = PH.CASES["sources at every alignment"]
+    buf = torch.full((total + 1,), float("nan"), dtype=torch.float32, device=ctx.device)
+    phrase("misaligned out", xs, notes, total, out=buf[1:])
+    x = torch.zeros(sum(len(v) for v in xs) + 1, dtype=torch.float32, device=ctx.device)
+    x[1:] = ctx.tensor(np.concatenate(xs))
+    phrase("misaligned x", xs, notes, total, x_dev=x[1:])
+
+    for pan in (-1.0, 0.0, 1.0, 0.3):                              # test_one_track_pan_and_length
+        rng = np.random.default_rng(11)
+        for N in (1, 7, 2047, 2048, 2049, 5000):
+            bus("one track/pan %g/%d" % (pan, N), [rng.uniform(-1, 1, N).astype(np.float32)], [B.Track(-3.0, pan)])
+    rng = np.random.default_rng(12)                                # test_three_tracks_edges_and_an_empty_tile
+    xs = [rng.uniform(-1, 1, n).astype(np.float32) for n in (1500, 700, 1000, 2048)]
+    tracks = [B.Track(0.0, -0.4), B.Track(-6.0, 0.2, BU._ms(3)), B.Track(2.0, 0.9, BU._ms(2050)), B.Track(-1.0, 0.0, BU._ms(2048))]
+    for lead in (0, 1):
+        bus("three tracks/lead %d" % lead, xs, tracks, 3 * 2048 + 5, lead)
+    rng = np.random.default_rng(14)                                # test_alignment_of_source_and_bus
+    xs = [rng.uniform(-1, 1, 4099).astype(np.float32), rng.uniform(-1, 1, 2600).astype(np.float32)]
+    for lead in (0, 1, 2, 3):
+        for out_lead in (0, 1):
+            for total in (4096, 4097, 4099):
+                bus("alignment/%d_%d_%d" % (lead, out_lead, total), xs, [B.Track(0.0, -0.2), B.Track(0.0, 0.7, BU._ms(512 + lead))], total,
+                    lead, out_lead)
+    xs = [np.full(3000, 1e8, np.float32), np.ones(3000, np.float32), np.full(3000, -1e8, np.float32)]      # test_order_of_the_sum
+    t = B.Track(0.0, -1.0)
+    bus("order/big one minus", xs, [t, t, t])
+    bus("order/big minus one", [xs[0], xs[2], xs[1]], [t, t, t])
+    return out
+
+
 def _cases(ctx, which):
     out = _ragged_cases(ctx) if which in ("ragged", "all") else {}
     if which in ("stages", "all"):
         out.update(_stage_cases(ctx))
     if which in ("walkers", "all"):
         out.update(_walker_cases(ctx))
+    if which in ("mixes", "all"):
+        out.update(_mix_cases(ctx))
     return out
 
 
@@ -233,7 +297,7 @@ def main(argv):
             opts[a] = next(it)
         else:
             libs.append(a)
-    if len(libs) != 2 or opts["--set"] not in ("ragged", "stages", "walkers", "all"):
+    if len(libs) != 2 or opts["--set"] not in ("ragged", "stages", "walkers", "mixes", "all"):
         sys.exit(__doc__)
     runs = {}
     for tag, lib in zip("AB", libs):

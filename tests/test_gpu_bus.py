@@ -125,6 +125,28 @@ def test_order_of_the_sum(ctx):
     assert _same(got, want) and (got[:3000] == 1.0).all()
 
 
+def test_phrase_mix_and_bus_mix_agree_on_the_same_placement(ctx):
+    """The two mixes stand on one walk (csrc/tile_mix.h): three signals at 0, 3 and 2050 summed by both give the same words.
+    Derived, not measured: with every val 1 and distinct knots the phrase's gain is 1 + 0 * q = 1 exactly, and at 0 dB and
+    pan -1 the bus has gl = 1 and gr = +0 (test_pan_law_exact_positions), so L is the phrase's track and R is +0.0f."""
+    from goofer_amd import _lib
+    from goofer_amd import phrase as P
+    rng = np.random.default_rng(15)
+    lens, starts, total = (1500, 700, 5000), (0, 3, 2050), 3 * 2048 + 5
+    xs = [rng.uniform(-1, 1, n).astype(np.float32) for n in lens]
+    notes = np.zeros(3, dtype=_lib.PHRASE_NOTE)
+    for i, (n, s) in enumerate(zip(lens, starts)):
+        notes[i] = (s, 0, n, np.linspace(0, n, 7).astype(np.float32), np.ones(7, np.float32))
+    pplan = P.plan_records(notes, lens, total)
+    tracks = [B.Track(0.0, -1.0, _ms(s)) for s in starts]
+    for lead in (0, 1):
+        bus, want, plan = _mix(ctx, xs, tracks, total_out=total, lead=lead)
+        track = ctx.phrase_mix(_dev(ctx, np.concatenate(xs), lead), ctx.offsets(lens), pplan)
+        ctx.check()
+        assert plan.total_out == total and list(plan.tracks["start"]) == list(starts) and _same(bus, want), lead
+        assert _same(track.cpu().numpy(), bus[:total]) and not L.words(bus[total:]).any(), lead
+
+
 def test_mix_refusals(ctx):
     from goofer_amd.device import GooferError
     lib, z = ctx.lib, C.c_void_p(0)

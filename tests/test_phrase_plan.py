@@ -133,6 +133,23 @@ def test_cover_skips_notes_without_an_effective_range():
     _check_cover([_note(2 ** 63 - 1, 0, 100), _note(-2 ** 63, 0, 100), _note(5, 0, 100)], [100, 100, 100], 4096)
 
 
+def test_planner_against_brute_force():
+    """The twin of test_bus_plan.test_planner_against_brute_force: seeded random records, starts in front of the track included."""
+    rng = np.random.default_rng(20261021)
+    for trial in range(40):
+        n = int(rng.integers(0, 9))
+        total = int(rng.choice([0, 1, 2047, 2048, 2049, 5000, 20000]))
+        starts = rng.integers(-3000, 12000, n)
+        skips = rng.choice([0, 1, 500], n)
+        takes = rng.choice([0, 1, 7, 2048, 3000, 9000], n)
+        lens = rng.choice([0, 1, 7, 2048, 3000, 9000], n)
+        if trial % 5 == 0 and n:
+            starts[0], skips[0], takes[0], lens[0] = 2048, 0, 2048, 2048     # exactly tile 1
+        off, lst = _check_cover([_note(int(s), int(k), int(t)) for s, k, t in zip(starts, skips, takes)], lens, total)
+        for t in range(len(off) - 1):
+            assert list(lst[off[t]:off[t + 1]]) == sorted(lst[off[t]:off[t + 1]])
+
+
 def test_cover_capacity_protocol():
     lib = _lib.load()
     notes = np.array([_note(0, 0, 5000), _note(1000, 0, 3000)], dtype=_lib.PHRASE_NOTE)
